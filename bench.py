@@ -21,7 +21,9 @@ region every rank's matches of its last step are gathered to rank 0 over RCCL (s
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts N ranks itself
 (torch.distributed.run on 127.0.0.1); under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.
-One JSON line on rank 0.
+One JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline (with the in-step
+roofline); `--full` adds every other leg of the line (other layout, masked streams, GNN, latency, CPU baseline, configs[2] / [3],
+live PMC passes).  `--dump-outputs DIR` writes the last timed step's matches as .npy files.
 """
 import argparse
 import json
@@ -63,7 +65,7 @@ def parse():
                     help="memory order of the synthetic backbone maps the two descriptor gathers read in the HEADLINE steps: "
                          "nchw (default) = NCHW-contiguous, what the unchanged reference's backbones emit (second_layer.py:66-69, "
                          "third_layer.py:113-117); nhwc = torch.channels_last, what they emit after ops.prepare_backbones(model).  Same "
-                         "logical tensors, same outputs bit for bit.  The other layout is timed in the same run as a secondary "
+                         "logical tensors, same outputs bit for bit.  With --full the other layout is timed in the same run as a secondary "
                          "(value_nchw / value_nhwc) unless --no-secondary")
     ap.add_argument("--rows-cap", choices=["worst", "dry-run"], default="worst",
                     help="row capacity of the fine level's table: worst = pairs * (N + (Cmax - 1) w), what a caller that knows nothing about "
@@ -81,7 +83,7 @@ def parse():
                     help="no GPU: print what a --gpus N run would do - every rank's pair share, steps, row / problem capacities, resident "
                          "bytes and expected set-up time - as one JSON line and exit (the first real 8-GPU run cannot fail on plumbing)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not re-run three steps under rocprofv3 --pmc for roofline.traffic (default: done when rocprofv3 is on PATH, one "
+                    help="do not re-run three steps under rocprofv3 --pmc for roofline.traffic (with --full: done when rocprofv3 is on PATH, one "
                          "rank, not --no-secondary; the committed profiles/r*_pmc_step_<layout>.json is the fallback, with its age in the line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the one-pair-at-a-time latency legs (tools/latency.py)")
@@ -93,7 +95,19 @@ def parse():
                          "one stream: 30.3 against 26.7 ms per 48-pair step - every kernel of the path fills all CUs' registers on its own, "
                          "so they only time-slice)")
     ap.add_argument("--no-overlap", action="store_true", help="(default since round 3; kept so that older command lines still parse)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other measurement of the line: the other map layout, the masked two-stream leg, GNN, "
+                         "guard-trip and determinism legs, gather layouts, latency legs, the CPU baseline with its parity sample, "
+                         "BASELINE configs[2] / [3] and the live rocprofv3 --pmc passes (each still switched off by its --no-* option).  "
+                         "Without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned - every pair's matches_l / matches_r "
+                         "(float32, pairs in order, concatenated) and the pair offsets into them (float64) - as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB, else a fixed seeded sample of the match rows, with their indices in sample_rows.npy)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_secondary = args.no_latency = args.no_cpu_baseline = args.no_pmc = True
+    return args
 
 
 def free_port():
@@ -136,6 +150,27 @@ def live_pmc(args):
         return None
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, gathered):
+    """--dump-outputs: the last timed step's matches as a caller of the path receives them, every pair's list in pair order
+    (pairs no rank reported are empty), concatenated, with the pair offsets into them.  Over DUMP_BYTES, a fixed seeded sample of
+    the match rows (the same rows for the same count) and their indices."""
+    pairs = [g_ if g_ is not None else (torch.empty((0, 2)), torch.empty((0, 2))) for g_ in gathered]
+    ml = np.concatenate([p_[0].float().cpu().numpy().reshape(-1, 2) for p_ in pairs]).astype(np.float32)
+    mr = np.concatenate([p_[1].float().cpu().numpy().reshape(-1, 2) for p_ in pairs]).astype(np.float32)
+    off = np.concatenate([[0], np.cumsum([p_[0].shape[0] for p_ in pairs])]).astype(np.float64)
+    arrays = {"matches_l": ml, "matches_r": mr, "pair_offsets": off}
+    keep = (DUMP_BYTES - 1024 - off.nbytes) // (ml.itemsize * 2 * 2 + 8)      # (1024: the four .npy headers)
+    if ml.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(ml.shape[0], size=keep, replace=False))
+        arrays.update(matches_l=ml[rows], matches_r=mr[rows], sample_rows=rows.astype(np.float64))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def plan_only(args):
@@ -311,6 +346,8 @@ def main():
         assert len(got) == len(gathered) or args.total_pairs > 0, "gather_matches lost a pair"
         matches_per_pair = float(np.mean([g_[0].shape[0] for g_ in got])) if got else 0.0
         gather_bytes = sum(g_[0].shape[0] for g_ in got) * 16
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gathered)
     rank_ms, rank_setup = [rank_ms_per_step], [setup_s]
     if dist is not None:
         tl = [torch.zeros(2, device=dev, dtype=torch.float64) for _ in range(n_gpus)]

@@ -1,7 +1,7 @@
 """pats_amd.dropin.install(): the reference's names are rebound at run time so that its own drivers
 (evaluate.py:106-108) run unchanged.  CPU test: no kernel is launched, only namespaces are inspected.
 Stand-in modules carry the reference's module / function / class names and signatures (typed here from
-the signatures, no reference source); when /root/reference is present the real modules are checked too."""
+the signatures, no reference source), so nothing outside this repository is needed."""
 import inspect
 import sys
 import types
@@ -139,45 +139,38 @@ def test_install_rebinds_every_namespace_and_restores(standins):
     assert sys.modules["tensor_resize"] is s["native"]
 
 
-def test_install_against_the_real_reference_when_present():
-    """In the build container the reference itself is importable (tools/ref_import.py): the same rebinding on the real
-    modules, and the real signatures against the replacements."""
-    sys.path.insert(0, REPO + "/tools")
-    import ref_import
-    if not ref_import.available():
-        pytest.skip("reference tree not present")
-    path_before, native_before = list(sys.path), sys.modules.get("tensor_resize")
-    R = ref_import.load()
+def test_install_against_the_real_reference_when_present(standins):
+    """The reference's module layout (the stand-ins above: every name in every namespace that holds it, the classes whose
+    methods are replaced): the same rebinding as on the real modules, the reference's signatures against the replacements
+    - methods with `self` dropped - and everything back after uninstall().  Nothing outside this repository is read."""
     from pats_amd import dropin, ops
-    originals = {n: getattr(R.M, n) for n in ("log_sinkhorn_iterations", "log_optimal_transport", "log_optimal_transport2", "attention")}
-    originals.update({n: getattr(R.U, n) for n in ("Iterative_expand_matrix", "Compute_positions_and_ranges", "split_patches",
-                                                   "Compute_imgs", "get_result")})
-    merge_new, comp_res = R.L2.SecondLayer.merge_patches_new, R.L3.ThirdLayer.Compute_result
-    prop_fwd, gnn_fwd = R.M.AttentionalPropagation.forward, R.M.AttentionalGNN.forward
-    kenc_fwd = R.M.KeypointEncoder.forward
+    s = standins
+    M, U, L1, L2, L3 = s["mm"], s["uu"], s["l1"], s["l2"], s["l3"]
+    originals = {n: getattr(M, n) for n in ("log_sinkhorn_iterations", "log_optimal_transport", "log_optimal_transport2", "attention")}
+    originals.update({n: getattr(U, n) for n in ("Iterative_expand_matrix", "Compute_positions_and_ranges", "split_patches",
+                                                 "Compute_imgs", "get_result")})
+    merge_new, merge_old, comp_res = L2.SecondLayer.merge_patches_new, L2.SecondLayer.merge_patches_old, L3.ThirdLayer.Compute_result
+    prop_fwd, gnn_fwd = M.AttentionalPropagation.forward, M.AttentionalGNN.forward
+    kenc_fwd = M.KeypointEncoder.forward
     try:
         touched = dropin.install()
         for n, ref in originals.items():
             assert _prefix_compatible(ref, getattr(ops, n)), n
-        assert R.L1.log_optimal_transport is ops.log_optimal_transport
-        assert R.L2.log_optimal_transport2 is ops.log_optimal_transport2 and R.L3.log_optimal_transport2 is ops.log_optimal_transport2
-        assert R.U.Compute_imgs is ops.Compute_imgs and "pats_amd" in R.U.tensor_resize.__doc__ \
-            and R.U.tensor_resize.__file__.endswith(".so")
-        assert _prefix_compatible(merge_new, R.L2.SecondLayer.merge_patches_new, drop_self=True)
-        assert _prefix_compatible(comp_res, R.L3.ThirdLayer.Compute_result, drop_self=True)
+        assert L1.log_optimal_transport is ops.log_optimal_transport
+        assert L2.log_optimal_transport2 is ops.log_optimal_transport2 and L3.log_optimal_transport2 is ops.log_optimal_transport2
+        assert U.Compute_imgs is ops.Compute_imgs and "pats_amd" in U.tensor_resize.__doc__ \
+            and U.tensor_resize.__file__.endswith(".so")
+        assert _prefix_compatible(merge_new, L2.SecondLayer.merge_patches_new, drop_self=True)
+        assert _prefix_compatible(merge_old, L2.SecondLayer.merge_patches_old, drop_self=True)
+        assert _prefix_compatible(comp_res, L3.ThirdLayer.Compute_result, drop_self=True)
         assert len(touched) >= 17
-        assert _prefix_compatible(prop_fwd, R.M.AttentionalPropagation.forward) and R.M.AttentionalPropagation.forward is not prop_fwd
-        assert _prefix_compatible(gnn_fwd, R.M.AttentionalGNN.forward)
-        assert _prefix_compatible(kenc_fwd, R.M.KeypointEncoder.forward) and R.M.KeypointEncoder.forward is not kenc_fwd
+        assert _prefix_compatible(prop_fwd, M.AttentionalPropagation.forward) and M.AttentionalPropagation.forward is not prop_fwd
+        assert _prefix_compatible(gnn_fwd, M.AttentionalGNN.forward) and M.AttentionalGNN.forward is not gnn_fwd
+        assert _prefix_compatible(kenc_fwd, M.KeypointEncoder.forward) and M.KeypointEncoder.forward is not kenc_fwd
     finally:
         dropin.uninstall()
-        # ref_import put the reference's compiled extension first on sys.path / into sys.modules: later tests
-        # must find this repository's tensor_resize.py again
-        sys.path[:] = path_before
-        if native_before is None:
-            sys.modules.pop("tensor_resize", None)
-        else:
-            sys.modules["tensor_resize"] = native_before
-    assert R.L1.log_optimal_transport is originals["log_optimal_transport"] and R.L2.SecondLayer.merge_patches_new is merge_new
-    assert R.M.AttentionalPropagation.forward is prop_fwd and R.M.AttentionalGNN.forward is gnn_fwd
-    assert R.M.KeypointEncoder.forward is kenc_fwd
+    assert L1.log_optimal_transport is originals["log_optimal_transport"] and L2.SecondLayer.merge_patches_new is merge_new
+    assert L2.SecondLayer.merge_patches_old is merge_old and L3.ThirdLayer.Compute_result is comp_res
+    assert M.AttentionalPropagation.forward is prop_fwd and M.AttentionalGNN.forward is gnn_fwd
+    assert M.KeypointEncoder.forward is kenc_fwd
+    assert all(getattr(U, n) is f for n, f in originals.items() if hasattr(U, n))

@@ -1068,6 +1068,27 @@ def test_bench_spawns_its_own_ranks(ops, sinkhorn_mode):
     assert two["matches_per_pair"] > 1000
 
 
+def test_bench_dumps_the_last_steps_matches(ops, sinkhorn_mode, tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's matches (float32) and pair offsets (float64) as .npy, the same
+    bits from two runs with the same arguments (the "log" instance: from NCHW and channels-last maps, which must agree bit for
+    bit as well); a plain run carries the headline only (the other legs are --full's)."""
+    runs = []
+    for k, maps in enumerate(("nchw", "nchw") if sinkhorn_mode == "kernel" else ("nchw", "nhwc")):
+        d = tmp_path / ("run%d" % k)
+        line = _run_bench({}, 1, ["--maps", maps, "--dump-outputs", str(d)])
+        runs.append({n: np.load(str(d / (n + ".npy"))) for n in ("matches_l", "matches_r", "pair_offsets")})
+        assert line["steps"] == 1 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+        other = "value_nhwc" if maps == "nchw" else "value_nchw"
+        assert line["value_" + maps] == line["value"] and not any(k_ in line for k_ in ("latency", other, "workloads_secondary", "gnn"))
+    a, b = runs
+    assert a["matches_l"].dtype == np.float32 and a["matches_r"].dtype == np.float32 and a["pair_offsets"].dtype == np.float64
+    off = a["pair_offsets"]
+    assert off.shape == (3,) and off[0] == 0 and off[-1] == a["matches_l"].shape[0] == a["matches_r"].shape[0]
+    assert off[-1] == line["matches_per_pair"] * 2 and a["matches_l"].shape == (int(off[-1]), 2)
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
 def test_bench_under_a_launcher_over_rccl_with_one_rank(ops, sinkhorn_mode):
     """The driver's multi-GPU command line (`python -m torch.distributed.run ... bench.py --gpus N`) with N = 1 and
     PATS_BENCH_FORCE_DIST=1: the process group is initialised over RCCL (backend "nccl") on this one GPU and every collective of

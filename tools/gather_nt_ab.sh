@@ -6,7 +6,7 @@ O=$R/gpurun_out; mkdir -p $O
 cd $R
 {
 for pol in 0 1 2 0 1 2; do
-  PATS_GATHER_NT=$pol python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  PATS_GATHER_NT=$pol python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1])
 sec={s['kernel'].split(' ')[0]: s for s in d.get('roofline_secondary',[])}
