@@ -43,7 +43,7 @@ const char* pats_version(void);
  * `row_nomatch` to pats_iterative_expand_f32 under the same symbol: a caller built against the older header would pass
  * its stream where the new pointer goes).  A C consumer checks `pats_abi_version() == PATS_ABI_VERSION` once after
  * loading the library; pats_amd/_lib.py does.  New arguments now come with new entry points instead. */
-#define PATS_ABI_VERSION 6
+#define PATS_ABI_VERSION 7
 int pats_abi_version(void);
 const char* pats_last_error(void);
 /* number of HIP devices visible (0 on a CPU-only box; never fails) */
@@ -494,6 +494,63 @@ int pats_matches_by_pair_summary_f32(const float* matches_l, const float* matche
                                      const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                      float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
                                      void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
+/* ---- ragged batches (ABI 7): pairs of DIFFERENT grids in one throughput batch --------------------------------------------
+ * Pair p has the coarse grid h_p x w_p (N_p = h_p w_p cells) and the images [32 h_p, 32 w_p, 3].  Every per-cell tensor of the
+ * batch is PACKED over cells: pair p owns cells [cell_base[p], cell_base[p+1]) (if_nomatching1, sum_cycle, pts_new, scales,
+ * scores_back [sum N, 16, 9], the chunk masks and row_slot [Cmax, sum N]); a uniform batch is the special case cell_base[p] =
+ * p N, i.e. exactly the layout of the entry points above.  The table is handed over twice: in host memory (validated before
+ * any launch, sizes the launches) and in device memory (what the kernels read).  Bad tables - null arrays, pairs < 1, h_p or
+ * w_p <= 0 or N_p >= 10000 (the crop sequence img * 10000 + patch), cell_base[0] != 0 or cell_base[p+1] - cell_base[p] !=
+ * N_p - are refused with PATS_ERR_INVALID. */
+typedef struct pats_pair_table {
+    int64_t pairs;
+    const int32_t* shape_host;       /* [pairs, 2] (h_p, w_p), host memory */
+    const int64_t* cell_base_host;   /* [pairs + 1], host memory */
+    const int32_t* shape;            /* the same two arrays in device memory */
+    const int64_t* cell_base;
+    const int64_t* img_base;         /* [pairs] device: offset in floats of pair p's image in the flat left / right stores */
+} pats_pair_table_t;
+
+/* pats_chunk_rows_device for a ragged batch: each pair is planned on its own grid with the chunk cap of first_layer.py:131-135
+ * (2 w_p when if_local, 512 otherwise).  second / third [pairs, max h + 1, 2]; masks / row_slot [Cmax, sum N]; row_cell = the
+ * packed cell; row_pair [rows_cap] = the row's pair (-1 past the total).  1 <= Cmax <= max h + 1.  Workspace:
+ * pats_chunk_rows_workspace_bytes(pairs, Cmax). */
+int pats_chunk_rows_ragged(const pats_pair_table_t* tab, const uint8_t* if_nomatching1, int if_local, int Cmax, int64_t rows_cap,
+                           int32_t* sum_cycle, int32_t* cycle_num, int64_t* second, int64_t* third, uint8_t* masks,
+                           int64_t* chunk_base, int64_t* crop_base, int32_t* row_cell, int32_t* row_pair, uint8_t* row_forced,
+                           int32_t* row_crop, int32_t* row_slot, int32_t* status, void* workspace, size_t workspace_bytes,
+                           pats_stream_t stream);
+/* pats_compute_imgs_bounds_batch_f32 / pats_left_crops_counted_f32 / pats_tensor_resize_hwc_counted_f32 for a ragged batch:
+ * per-cell inputs and outputs packed, bound5 [sum N, 5]; pair p's images are read at img_base[p] with its own 32 h_p x 32 w_p,
+ * and every read outside them is the reference's zero padding (utils.py:1352), whatever memory lies beside them. */
+int pats_compute_imgs_bounds_ragged_f32(const pats_pair_table_t* tab, const float* x_scale, const float* y_scale,
+                                        const float* average_point, const uint8_t* if_nomatching, int64_t* bound5, int64_t* K_img,
+                                        int64_t* K_total, float* x_scale_new, float* y_scale_new, float* average_new,
+                                        pats_stream_t stream);
+int pats_left_crops_ragged_f32(const pats_pair_table_t* tab, const float* left, const int64_t* bound5, int64_t K_cap,
+                               const int64_t* K_dev, float* out, pats_stream_t stream);
+int pats_tensor_resize_hwc_ragged_f32(const pats_pair_table_t* tab, const float* right, int margin, const int64_t* bound5,
+                                      int64_t K_cap, const int64_t* K_dev, float* out, int32_t* status, pats_stream_t stream);
+/* pats_merge_patches_batch for a ragged batch (row table of pats_chunk_rows_ragged; scores_back packed [sum N, 16, 9]). */
+size_t pats_merge_ragged_workspace_bytes(int64_t total_cells);
+int pats_merge_patches_ragged(const pats_pair_table_t* tab, int merge_new, int Cmax, int64_t rows_cap, const int64_t* chunk_base,
+                              const int32_t* row_cell, const int32_t* row_pair, const int32_t* row_slot, const uint8_t* row_forced,
+                              float* trust_score, uint8_t* if_nomatching1_L2, double* scores_back, int zero_scores_back,
+                              uint8_t* out, void* workspace, size_t workspace_bytes, pats_stream_t stream);
+/* pats_get_result_chunks_f32 for a ragged batch: level-0 patch_size of pair p is (32, h_p, w_p); masks [Cmax, sum N],
+ * pts_new / scales packed [sum N, 2].  Workspace: pats_get_result_workspace_bytes(Cmax * sum N, rows_cap, n1). */
+int pats_get_result_chunks_ragged_f32(const pats_pair_table_t* tab, int Cmax, const uint8_t* masks, const uint8_t* if_nomatching16,
+                                      int64_t rows_cap, const float* pts_new, const float* pts16, const float* scales,
+                                      const int* patch_size1, const uint8_t* left_choice0, const uint8_t* left_choice1,
+                                      float* matches_l, float* matches_r, int32_t* match_row, int64_t capacity, int64_t* count,
+                                      void* workspace, size_t workspace_bytes, pats_stream_t stream);
+/* pats_matches_by_pair_summary_f32 with the pair of a match taken from the row table's row_pair (any batch, ragged or not).
+ * status may be null: pair_off then holds the pairs + 1 offsets only (as pats_matches_by_pair_f32), and P_dev is ignored. */
+int pats_matches_by_row_pair_summary_f32(const float* matches_l, const float* matches_r, const int32_t* match_row,
+                                         const int64_t* M_dev, const int32_t* row_pair, const int64_t* chunk_base, int Cmax,
+                                         int64_t pairs, float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev,
+                                         const int32_t* status, void* workspace, size_t workspace_bytes, pats_stream_t stream);
 
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the

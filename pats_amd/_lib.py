@@ -17,7 +17,17 @@ if os.environ.get("PATS_AMD_DIAG_LIB", "") not in ("", "0"):
 c_void_p, c_int, c_i64, c_f, c_size = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
                                        ctypes.c_size_t)
 
-ABI_VERSION = 6      # include/pats_amd.h PATS_ABI_VERSION
+ABI_VERSION = 7      # include/pats_amd.h PATS_ABI_VERSION
+
+
+
+class PairTable(ctypes.Structure):
+    """pats_pair_table_t (include/pats_amd.h): the shapes of a ragged batch, host copies + device arrays."""
+    _fields_ = [("pairs", ctypes.c_int64), ("shape_host", c_void_p), ("cell_base_host", c_void_p), ("shape", c_void_p),
+                ("cell_base", c_void_p), ("img_base", c_void_p)]
+
+
+_TAB = ctypes.POINTER(PairTable)
 
 # name -> (restype, argtypes); must list every symbol include/pats_amd.h declares
 SIGNATURES = {
@@ -149,6 +159,17 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_matches_by_pair_summary_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int,
                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_chunk_rows_ragged": (c_int, [_TAB, c_void_p, c_int, c_int, c_i64] + [c_void_p] * 14 + [c_size, c_void_p]),
+    "pats_compute_imgs_bounds_ragged_f32": (c_int, [_TAB] + [c_void_p] * 10 + [c_void_p]),
+    "pats_left_crops_ragged_f32": (c_int, [_TAB, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
+    "pats_tensor_resize_hwc_ragged_f32": (c_int, [_TAB, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pats_merge_ragged_workspace_bytes": (c_size, [c_i64]),
+    "pats_merge_patches_ragged": (c_int, [_TAB, c_int, c_int, c_i64] + [c_void_p] * 8 + [c_int, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_get_result_chunks_ragged_f32": (c_int, [_TAB, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                                                  ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                                  c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_matches_by_row_pair_summary_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -56,6 +56,81 @@ class Capacities:
         self.P_cap = self.pairs * per_pair
 
 
+class MixedCapacities:
+    """Capacities of a batch whose pairs may have different grids: `shapes` = the pairs' (h, w) (any order).  A list of one
+    repeated shape gives exactly Capacities(pairs, h, w, ...).  Otherwise h = w = N = chunk_cap = None and
+    Cmax = max_p Cmax_p, rows_cap = sum_p (N_p + (Cmax_p - 1) w_p), P_cap = sum_p int(1.25 * 16 * N_p) (or p_cap_per_pair
+    for every pair) - the per-pair worst cases of Capacities added up."""
+
+    def __init__(self, shapes, if_local=True, p_cap_per_pair=None, rows_cap=None):
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.if_local = bool(if_local)
+        if not self.shapes:
+            raise ValueError("MixedCapacities: no pairs")
+        if len(set(self.shapes)) == 1:
+            u = Capacities(len(self.shapes), self.shapes[0][0], self.shapes[0][1], if_local, p_cap_per_pair, rows_cap)
+            self.pairs, self.h, self.w, self.N = u.pairs, u.h, u.w, u.N
+            self.chunk_cap, self.Cmax, self.rows_cap, self.P_cap = u.chunk_cap, u.Cmax, u.rows_cap, u.P_cap
+            return
+        self.pairs, self.h, self.w, self.N, self.chunk_cap = len(self.shapes), None, None, None, None
+        cm = [ops.max_chunks(h, w, 2 * w if if_local else 512) for h, w in self.shapes]
+        self.Cmax = max(cm)
+        self.rows_cap = (sum(h * w + (c - 1) * w for (h, w), c in zip(self.shapes, cm)) if rows_cap is None else int(rows_cap))
+        self.P_cap = sum(int(1.25 * 16 * h * w) if p_cap_per_pair is None else int(p_cap_per_pair) for h, w in self.shapes)
+
+
+class MixedPack:
+    """What pack_pairs returns.  Pairs are sorted stably by grid into SLOTS, so every shape group is a contiguous slot range:
+        shapes          (h, w) per slot;  slot_of / caller_of: caller index -> slot, slot -> caller index
+        left, right     the flat HWC image stores (slot order; pair s at table.img_base[s] floats)
+        table           ops.PairTable of the slots (grids, packed cell ranges, image offsets)
+        groups          [(slot_lo, slot_hi, h, w, lefts [g,32h,32w,3], rights)] - views into the stores, for nets.coarse"""
+
+
+def slot_order(shapes):
+    """The slots of a mixed batch: caller indices sorted stably by grid (equal grids keep the caller's order), so that every shape
+    group is a contiguous slot range.  Returns caller_of (slot -> caller index)."""
+    return sorted(range(len(shapes)), key=lambda i: tuple(shapes[i]))
+
+
+def pack_pairs(pairs):
+    """pairs: [(left, right)] HWC float32 GPU tensors, each [H_p, W_p, 3] or [1, H_p, W_p, 3] with H_p, W_p multiples of 32 (the two
+    images of a pair the same size).  Returns a MixedPack for forward_pairs_mixed."""
+    if not pairs:
+        raise ValueError("pack_pairs: no pairs")
+    imgs, shapes = [], []
+    for i, (l, r) in enumerate(pairs):
+        l = l[0] if l.dim() == 4 else l
+        r = r[0] if r.dim() == 4 else r
+        if l.dim() != 3 or l.shape[2] != 3 or l.shape != r.shape or l.shape[0] % 32 or l.shape[1] % 32 or not l.is_cuda:
+            raise ValueError("pack_pairs: pair %d must be two equal [H,W,3] GPU images with H, W multiples of 32" % i)
+        imgs.append((l.float(), r.float()))
+        shapes.append((int(l.shape[0]) // 32, int(l.shape[1]) // 32))
+    caller_of = slot_order(shapes)
+    pk = MixedPack()
+    pk.caller_of = caller_of
+    pk.slot_of = [0] * len(caller_of)
+    for s_, i in enumerate(caller_of):
+        pk.slot_of[i] = s_
+    pk.shapes = [shapes[i] for i in caller_of]
+    dev = imgs[0][0].device
+    pk.left = torch.cat([imgs[i][0].reshape(-1) for i in caller_of])
+    pk.right = torch.cat([imgs[i][1].reshape(-1) for i in caller_of])
+    pk.table = ops.PairTable(pk.shapes, dev)
+    pk.groups = []
+    lo = 0
+    while lo < len(caller_of):
+        hi = lo
+        while hi < len(caller_of) and pk.shapes[hi] == pk.shapes[lo]:
+            hi += 1
+        h, w = pk.shapes[lo]
+        o0, n = int(pk.table.img_base_host[lo]), (hi - lo) * h * w * 1024 * 3
+        pk.groups.append((lo, hi, h, w, pk.left[o0:o0 + n].view(hi - lo, 32 * h, 32 * w, 3),
+                          pk.right[o0:o0 + n].view(hi - lo, 32 * h, 32 * w, 3)))
+        lo = hi
+    return pk
+
+
 _ONE = {}
 
 
@@ -183,6 +258,44 @@ def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, ite
     return fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
 
 
+def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True):
+    """coarse_stage for a MixedPack: the first layer's tail once per shape group (the coarse solvers are chosen by size, so a
+    group is one launch set on one grid - bits independent of the batch), its per-cell outputs packed over the slots, then the
+    row table and the crops in ONE launch set over the whole batch (ops.chunk_rows_ragged, ops.Compute_imgs_ragged)."""
+    ifn1, xs, ys, pts = [], [], [], []
+    for lo, hi, h, w, lefts, rights in pack.groups:
+        mdesc0, mdesc1, scale, alpha = nets.coarse(lefts, rights)
+        Z = ops.cost_ot(mdesc0, mdesc1, 1, alpha, scale, iters)
+        scales, cflag = ops.colmass_sqrt(Z, return_flags=True)
+        _, p_, x_, y_, f_, _ = ops.est_position_first(Z, scales, (32 * h, 32 * w), 32, col_nomatch=cflag)
+        ifn1.append(f_.reshape(-1))
+        xs.append(x_.reshape(-1))
+        ys.append(y_.reshape(-1))
+        pts.append(p_.reshape(-1))
+    one = len(pack.groups) == 1
+    ifn1 = ifn1[0] if one else torch.cat(ifn1)
+    xs, ys, pts = (xs[0], ys[0], pts[0]) if one else (torch.cat(xs), torch.cat(ys), torch.cat(pts))
+    rows = ops.chunk_rows_ragged(ifn1, pack.table, if_local, Cmax=cap.Cmax, rows_cap=cap.rows_cap)
+    new_left, new_right, xsn, ysn, avn, bound5, K_img, K_tot = ops.Compute_imgs_ragged(xs, ys, pts, ifn1, pack.left, pack.right,
+                                                                                       pack.table)
+    return {"rows": rows, "new_left": new_left, "new_right": new_right, "xsn": xsn, "avn": avn, "K_img": K_img, "ifn1": ifn1,
+            "H": None, "W": None}
+
+
+def forward_pairs_mixed(pack, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None):
+    """forward_pairs for pairs of different grids (pack_pairs): the coarse level once per shape group, everything from the row
+    table on ONE launch set over the whole batch, no host read.  Same result dict, in SLOT order (rows.row_pair = the slot;
+    pack.caller_of[slot] = the caller's index); split_by_pair(out, cap) hands the per-pair lists back in the caller's order.
+    Every pair's matches are bit-identical to forward_pairs / pipeline.forward_path on that pair alone.  nets.coarse is called
+    once per group with its [g, 32h, 32w, 3] views; nets.fine / nets.third find a row's pair through rows.row_pair."""
+    if cap.pairs != pack.table.pairs or sorted(cap.shapes) != sorted(pack.shapes):
+        raise ValueError("forward_pairs_mixed: the capacities were made for other shapes than the pack holds")
+    co = coarse_stage_mixed(pack, nets, cap, iters, cap.if_local)
+    out = fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
+    out["caller_of"] = pack.caller_of
+    return out
+
+
 def group_by_pair(out, cap, buffers=None):
     """Device side of the hand-over: the batch's matches regrouped by pair (ops.matches_by_pair), no host read.  Adds
     `by_pair` = (matches_l, matches_r, pair_off) and `summary` (int64 [pairs + 4]: the pairs + 1 offsets, then M, P, table status -
@@ -195,8 +308,8 @@ def group_by_pair(out, cap, buffers=None):
 
 
 def split_by_pair(out, cap):
-    """Host side, AFTER the step: per-pair (matches_l, matches_r) lists from a forward_pairs result, in the reference's
-    order.  Reads the counts back (the one synchronisation of a batch) and raises on a capacity overflow."""
+    """Host side, AFTER the step: per-pair (matches_l, matches_r) lists from a forward_pairs (or forward_pairs_mixed: in the
+    caller's order) result, in the reference's order.  Reads the counts back (the one synchronisation of a batch) and raises on a capacity overflow."""
     if "summary" not in out:
         group_by_pair(out, cap)
     o = out["summary"].cpu().tolist()                 # the one synchronisation of a batch: offsets, M, P, status in one copy
@@ -208,4 +321,10 @@ def split_by_pair(out, cap):
     if P > cap.P_cap:
         raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
     ml, mr, _ = out["by_pair"]
-    return [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]]) for p in range(cap.pairs)]
+    per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]]) for p in range(cap.pairs)]
+    if "caller_of" not in out:
+        return per_slot
+    per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order
+    for s_, i in enumerate(out["caller_of"]):
+        per_caller[i] = per_slot[s_]
+    return per_caller

@@ -17,9 +17,9 @@
 namespace pats {
 
 struct ChunkRowsArgs {
-    const uint8_t* ifn1;      // [pairs, N]   if_nomatching1 of the coarse level (first_layer.py:162-167)
+    const uint8_t* ifn1;      // [pairs, N]   if_nomatching1 of the coarse level (first_layer.py:162-167); packed cells when ragged
     int64_t pairs;
-    int h, w, cap, Cmax;
+    int h, w, cap, Cmax;      // cap 0: the pair's own 2 * w_p (ragged batch, if_local)
     int64_t rows_cap;
     int32_t* sum_cycle;       // [pairs, N]   cumsum of matched flags (first_layer.py:130)
     int32_t* cycle_num;       // [pairs]
@@ -35,6 +35,9 @@ struct ChunkRowsArgs {
     int32_t* counts;          // workspace [Cmax * pairs]
     int64_t* pair_base;       // workspace [Cmax * pairs]
     int32_t* status;          // bit 0: a pair has more than Cmax chunks; bit 1: more rows than rows_cap (both: rows dropped)
+    PairShapes ps;            // the pairs' grids and packed cell ranges (uniform: h x w, p * N)
+    int32_t* row_pair;        // [rows_cap]   pair of the row, or -1 (optional)
+    int srow;                 // entries of a pair in second / third: 2 * (max h + 1)
 };
 
 __device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
@@ -52,9 +55,11 @@ chunk_plan_kernel(ChunkRowsArgs g) {
     __shared__ int wsum[4];
     __shared__ int carry;
     const int64_t p = blockIdx.x;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, N = g.h * g.w;
-    const uint8_t* f = g.ifn1 + p * N;
-    int32_t* sc = g.sum_cycle + p * N;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int h = g.ps.hp(p), w = g.ps.wp(p), N = h * w;
+    const int64_t cb = g.ps.base(p);
+    const uint8_t* f = g.ifn1 + cb;
+    int32_t* sc = g.sum_cycle + cb;
     if (t == 0) carry = 0;
     wg_barrier();
     for (int q0 = 0; q0 < N; q0 += 256) {
@@ -71,11 +76,11 @@ chunk_plan_kernel(ChunkRowsArgs g) {
         wg_barrier();
     }
     if (t != 0) return;
-    const int row = 2 * (g.h + 1);
+    const int row = g.srow;
     int64_t* second = g.second + p * row;
     int64_t* third = g.third + p * row;
     for (int k = 0; k < row; ++k) { second[k] = 0; third[k] = 0; }
-    const int num = split_patches_plan(sc, g.h, g.w, g.cap, second, third);
+    const int num = split_patches_plan(sc, h, w, g.cap > 0 ? g.cap : 2 * w, second, third);
     g.cycle_num[p] = num;
     const int64_t K = sc[N - 1];
     if (num > g.Cmax) atomicOr(g.status, 1);
@@ -125,19 +130,17 @@ chunk_prefix_kernel(ChunkRowsArgs g) {
     }
 }
 
-// one thread per (pair, cell): its chunk masks and, where it belongs to a chunk, its row
+// one thread per (pair, cell) - a packed cell: its chunk masks and, where it belongs to a chunk, its row
 __global__ void __launch_bounds__(256)
 chunk_fill_kernel(ChunkRowsArgs g) {
-    const int N = g.h * g.w;
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= g.pairs * N) return;
-    const int64_t p = e / N;
-    const int q = (int)(e - p * N);
+    if (e >= g.ps.cells) return;
+    const int64_t p = g.ps.pair_of(e);
     const int num = g.cycle_num[p];
     const int32_t sc = g.sum_cycle[e];
     const bool nomatch = g.ifn1[e] != 0;
-    const int64_t K = g.sum_cycle[p * N + N - 1];
-    const int row = 2 * (g.h + 1);
+    const int64_t K = g.sum_cycle[g.ps.base(p) + g.ps.ncell(p) - 1];
+    const int row = g.srow;
     for (int c = 0; c < g.Cmax; ++c) {
         bool m = true;
         int32_t slot = -1;
@@ -151,14 +154,15 @@ chunk_fill_kernel(ChunkRowsArgs g) {
                     const int64_t tail = g.third[p * row + 2 * c + 1];  // pats.py:38-39: if_nomatching1[-tail:, :] = True
                     const bool forced = tail > 0 ? rank >= n - tail : (tail < 0 ? rank >= -tail : false);
                     g.row_cell[r] = (int32_t)e;
+                    if (g.row_pair) g.row_pair[r] = (int32_t)p;
                     g.row_forced[r] = forced ? 1 : 0;
                     g.row_crop[r] = (int32_t)(g.crop_base[p] + sc - 1);
                     slot = (int32_t)r;
                 }
             }
         }
-        g.masks[((int64_t)c * g.pairs + p) * N + q] = m ? 1 : 0;
-        g.row_slot[(int64_t)c * g.pairs * N + e] = slot;
+        g.masks[(int64_t)c * g.ps.cells + e] = m ? 1 : 0;             // [Cmax, pairs, N] when uniform
+        g.row_slot[(int64_t)c * g.ps.cells + e] = slot;
     }
 }
 
@@ -171,6 +175,7 @@ chunk_init_kernel(ChunkRowsArgs g) {
         g.row_cell[r] = -1;
         g.row_crop[r] = -1;
         g.row_forced[r] = 1;
+        if (g.row_pair) g.row_pair[r] = -1;
     }
 }
 
@@ -193,6 +198,18 @@ extern "C" size_t pats_chunk_rows_workspace_bytes(int64_t pairs, int Cmax) {
     return (size_t)(((n + 3) & ~3ll) * sizeof(int32_t) + n * sizeof(int64_t) + 64);
 }
 
+// the four launches of a row table, uniform or ragged (ChunkRowsArgs::ps)
+static int launch_chunk_rows(const ChunkRowsArgs& g, hipStream_t st) {
+    {
+        const int64_t blocks = ceil_div(g.rows_cap > 0 ? g.rows_cap : 1, 256);
+        hipLaunchKernelGGL(chunk_init_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, g);
+    }
+    hipLaunchKernelGGL(chunk_plan_kernel, dim3((unsigned)g.pairs), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(chunk_prefix_kernel, dim3(1), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(chunk_fill_kernel, dim3((unsigned)ceil_div(g.ps.cells, 256)), dim3(256), 0, st, g);
+    return check_launch("chunk_rows_device");
+}
+
 extern "C" int pats_chunk_rows_device(const uint8_t* if_nomatching1, int64_t pairs, int height, int width,
                                       int max_once_used, int Cmax, int64_t rows_cap, int32_t* sum_cycle,
                                       int32_t* cycle_num, int64_t* second, int64_t* third, uint8_t* masks,
@@ -206,18 +223,35 @@ extern "C" int pats_chunk_rows_device(const uint8_t* if_nomatching1, int64_t pai
                      row_forced && row_crop && row_slot && status, "chunk_rows_device: null pointer");
     PATS_REQUIRE(workspace && workspace_bytes >= pats_chunk_rows_workspace_bytes(pairs, Cmax), "chunk_rows_device: workspace too small");
     PATS_REQUIRE(pairs * (int64_t)height * width < (1ll << 31) && rows_cap < (1ll << 31), "chunk_rows_device: batch too large");
-    hipStream_t st = as_stream(stream);
     const int64_t n = pairs * Cmax;
     int64_t* pair_base = reinterpret_cast<int64_t*>(workspace);
     int32_t* counts = reinterpret_cast<int32_t*>(pair_base + n);
     ChunkRowsArgs g{if_nomatching1, pairs, height, width, max_once_used, Cmax, rows_cap, sum_cycle, cycle_num, second, third,
-                    masks, chunk_base, crop_base, row_cell, row_forced, row_crop, row_slot, counts, pair_base, status};
-    {
-        const int64_t blocks = ceil_div(rows_cap > 0 ? rows_cap : 1, 256);
-        hipLaunchKernelGGL(chunk_init_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, g);
-    }
-    hipLaunchKernelGGL(chunk_plan_kernel, dim3((unsigned)pairs), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(chunk_prefix_kernel, dim3(1), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(chunk_fill_kernel, dim3((unsigned)ceil_div(pairs * height * width, 256)), dim3(256), 0, st, g);
-    return check_launch("chunk_rows_device");
+                    masks, chunk_base, crop_base, row_cell, row_forced, row_crop, row_slot, counts, pair_base, status,
+                    uniform_shapes(pairs, height, width, (int64_t)height * width), nullptr, 2 * (height + 1)};
+    return launch_chunk_rows(g, as_stream(stream));
+}
+
+extern "C" int pats_chunk_rows_ragged(const pats_pair_table_t* tab, const uint8_t* if_nomatching1, int if_local, int Cmax,
+                                      int64_t rows_cap, int32_t* sum_cycle, int32_t* cycle_num, int64_t* second, int64_t* third,
+                                      uint8_t* masks, int64_t* chunk_base, int64_t* crop_base, int32_t* row_cell, int32_t* row_pair,
+                                      uint8_t* row_forced, int32_t* row_crop, int32_t* row_slot, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, pats_stream_t stream) {
+    PairShapes ps;
+    int hmax = 0;
+    const int rc = ragged_shapes(tab, &ps, &hmax, "chunk_rows_ragged");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && rows_cap >= 0 && rows_cap < (1ll << 31),
+                 "chunk_rows_ragged: bad argument (1 <= Cmax <= max h + 1)");
+    PATS_REQUIRE(if_nomatching1 && sum_cycle && cycle_num && second && third && masks && chunk_base && crop_base && row_cell &&
+                     row_pair && row_forced && row_crop && row_slot && status, "chunk_rows_ragged: null pointer");
+    PATS_REQUIRE(workspace && workspace_bytes >= pats_chunk_rows_workspace_bytes(ps.pairs, Cmax), "chunk_rows_ragged: workspace too small");
+    PATS_REQUIRE(ps.cells * Cmax < (1ll << 31), "chunk_rows_ragged: batch too large");
+    const int64_t n = ps.pairs * Cmax;
+    int64_t* pair_base = reinterpret_cast<int64_t*>(workspace);
+    int32_t* counts = reinterpret_cast<int32_t*>(pair_base + n);
+    ChunkRowsArgs g{if_nomatching1, ps.pairs, 0, 0, if_local ? 0 : 512, Cmax, rows_cap, sum_cycle, cycle_num, second, third,
+                    masks, chunk_base, crop_base, row_cell, row_forced, row_crop, row_slot, counts, pair_base, status, ps, row_pair,
+                    2 * (hmax + 1)};
+    return launch_chunk_rows(g, as_stream(stream));
 }

@@ -254,4 +254,60 @@ int fill_bytes(void* p, int value, size_t n, hipStream_t st);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- the shapes of a throughput batch (include/pats_amd.h, pats_pair_table_t) ----------------------------------------------
+// Uniform batch (shape == nullptr): every pair has the grid h x w, n cells (n = h w for the row table) and an H x W image at
+// p * img_stride floats - the scalars of the entry points that predate ragged batches.  Ragged batch: the device table.  The
+// kernels of the batch stages read a pair's geometry through these accessors only, so one kernel serves both.
+struct PairShapes {
+    const int32_t* shape = nullptr;
+    const int64_t* cell_base = nullptr;
+    const int64_t* img_base = nullptr;
+    int64_t pairs = 0, cells = 0;
+    int h = 0, w = 0, H = 0, W = 0;
+    int64_t n = 0, img_stride = 0;
+    __device__ __forceinline__ int hp(int64_t p) const { return shape ? shape[2 * p] : h; }
+    __device__ __forceinline__ int wp(int64_t p) const { return shape ? shape[2 * p + 1] : w; }
+    __device__ __forceinline__ int Hpx(int64_t p) const { return shape ? 32 * shape[2 * p] : H; }
+    __device__ __forceinline__ int Wpx(int64_t p) const { return shape ? 32 * shape[2 * p + 1] : W; }
+    __device__ __forceinline__ int64_t base(int64_t p) const { return shape ? cell_base[p] : p * n; }
+    __device__ __forceinline__ int64_t ncell(int64_t p) const { return shape ? cell_base[p + 1] - cell_base[p] : n; }
+    __device__ __forceinline__ int64_t img(int64_t p) const { return shape ? img_base[p] : p * img_stride; }
+    // the pair that owns packed cell e (0 <= e < cells)
+    __device__ __forceinline__ int64_t pair_of(int64_t e) const {
+        if (!shape) return e / n;
+        int64_t lo = 0, hi = pairs - 1;                 // the last p with cell_base[p] <= e
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (cell_base[mid] <= e) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    }
+};
+
+inline PairShapes uniform_shapes(int64_t pairs, int h, int w, int64_t n, int H = 0, int W = 0) {
+    PairShapes s;
+    s.pairs = pairs; s.h = h; s.w = w; s.n = n; s.cells = pairs * n; s.H = H; s.W = W; s.img_stride = (int64_t)H * W * 3;
+    return s;
+}
+
+// a ragged table checked on its host copy before any launch; hmax = the largest h_p
+inline int ragged_shapes(const pats_pair_table_t* tab, PairShapes* s, int* hmax, const char* what) {
+    PATS_REQUIRE(tab && tab->pairs >= 1 && tab->shape_host && tab->cell_base_host && tab->shape && tab->cell_base && tab->img_base,
+                 "%s: null or empty pair table", what);
+    PATS_REQUIRE(tab->cell_base_host[0] == 0, "%s: cell_base[0] must be 0", what);
+    int hm = 0;
+    for (int64_t p = 0; p < tab->pairs; ++p) {
+        const int32_t h = tab->shape_host[2 * p], w = tab->shape_host[2 * p + 1];
+        PATS_REQUIRE(h > 0 && w > 0 && (int64_t)h * w < 10000, "%s: pair %lld has the grid %d x %d", what, (long long)p, h, w);
+        PATS_REQUIRE(tab->cell_base_host[p + 1] == tab->cell_base_host[p] + (int64_t)h * w,
+                     "%s: cell_base is not the prefix of the pairs' cell counts at pair %lld", what, (long long)p);
+        hm = h > hm ? h : hm;
+    }
+    PATS_REQUIRE(tab->cell_base_host[tab->pairs] < (1ll << 26), "%s: batch too large", what);
+    s->shape = tab->shape; s->cell_base = tab->cell_base; s->img_base = tab->img_base;
+    s->pairs = tab->pairs; s->cells = tab->cell_base_host[tab->pairs];
+    if (hmax) *hmax = hm;
+    return PATS_OK;
+}
+
 }  // namespace pats

@@ -199,6 +199,13 @@ struct MergeGeom {
     int64_t per;                 // 4h * 4w * 9
 };
 
+// the geometry of pair p: g itself in a uniform batch, the pair's own grid in a ragged one
+__device__ __forceinline__ MergeGeom pair_geom(const MergeGeom& g, const PairShapes& ps, int64_t p) {
+    if (!ps.shape) return g;
+    const int h = ps.hp(p), w = ps.wp(p);
+    return MergeGeom{h, w, 4 * h, 4 * w, (int64_t)h * w * 144};
+}
+
 // "new" (second_layer.py:214-240) as a gather.  Output entry (patch q, window cell (a,r,c,s)) lives at
 // owner-layout position (Y', X', k') = (4hh + r, 4ww + s, 3a + c).  The only fine cell whose scatter
 // index (:234-236) can hit it is (Y, X) = (Y' + 4(a-1), X' + 4(c-1)) choosing sb = 8 - k'; that cell's
@@ -253,10 +260,11 @@ merge_select_new_kernel(MergeGeom g, RowBlock rb, const int32_t* __restrict__ pa
 // otherwise), applies -10000 to matching ones, takes the first minimum and scatters the flag to the
 // (clamped) source entry.  ATen's CPU scatter is sequential, so the last source wins:
 // atomicMax on ((source index + 1) << 1 | value).
-__device__ __forceinline__ void merge_scatter_old_cell(const MergeGeom& g, int64_t bt, int64_t n, const int32_t* __restrict__ slot,
+// (cb = the pair's first packed cell; its winner slots start at cb * 144)
+__device__ __forceinline__ void merge_scatter_old_cell(const MergeGeom& g, int64_t cb, int64_t n, const int32_t* __restrict__ slot,
                                                        const uint8_t* __restrict__ ifn_L2, const double* __restrict__ scores_back,
                                                        unsigned* __restrict__ winner) {
-    const int Y = (int)(n / g.w4), X = (int)(n % g.w4), hw = g.h * g.w;
+    const int Y = (int)(n / g.w4), X = (int)(n % g.w4);
     int sb = 0;
     double best = 0.0;
     bool m_best = false;
@@ -265,7 +273,7 @@ __device__ __forceinline__ void merge_scatter_old_cell(const MergeGeom& g, int64
         const int dx = k / 3 - 1, dy = k % 3 - 1;
         const bool reach = Y >= 4 * max(dx, 0) && Y < g.h4 + 4 * min(dx, 0) && X >= 4 * max(dy, 0) && X < g.w4 + 4 * min(dy, 0);
         const int sy = reach ? Y - 4 * dx : Y, sx = reach ? X - 4 * dy : X;
-        const int64_t qs = bt * hw + (sy / 4) * g.w + sx / 4;
+        const int64_t qs = cb + (sy / 4) * g.w + sx / 4;
         double v = scores_back[(qs * 16 + (sy % 4) * 4 + sx % 4) * 9 + k];
         const int sl = slot[qs];
         const bool m = sl >= 0 && !ifn_L2[(int64_t)sl * 144 + ((k / 3) * 4 + sy % 4) * 12 + (k % 3) * 4 + sx % 4];
@@ -276,33 +284,40 @@ __device__ __forceinline__ void merge_scatter_old_cell(const MergeGeom& g, int64
     const int64_t hy = n / g.w / 4 - (sb / 3 - 1) * 4, wx = n % g.w4 - (sb % 3 - 1) * 4;
     if (hy < 0 || hy >= g.h4 || wx < 0 || wx >= g.w4) m_best = false;
     s2 = min(max(s2, (int64_t)0), g.per - 1);
-    atomicMax(&winner[bt * g.per + s2], (unsigned)(((n + 1) << 1) | (m_best ? 0 : 1)));
+    atomicMax(&winner[cb * 144 + s2], (unsigned)(((n + 1) << 1) | (m_best ? 0 : 1)));
 }
 
 __global__ void __launch_bounds__(256)
-merge_scatter_old_kernel(MergeGeom g, int batch_num, const int32_t* __restrict__ slot,
+merge_scatter_old_kernel(MergeGeom g, PairShapes ps, int batch_num, const int32_t* __restrict__ slot,
                          const uint8_t* __restrict__ ifn_L2, const double* __restrict__ scores_back,
                          unsigned* __restrict__ winner) {
-    const int64_t cells = (int64_t)g.h4 * g.w4;
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (ps.shape) {                             // ragged: pair p's 16 N_p fine cells are [16 base(p), 16 base(p + 1))
+        if (e >= ps.cells * 16) return;
+        const int64_t p = ps.pair_of(e >> 4), cb = ps.base(p);
+        merge_scatter_old_cell(pair_geom(g, ps, p), cb, e - 16 * cb, slot, ifn_L2, scores_back, winner);
+        return;
+    }
+    const int64_t cells = (int64_t)g.h4 * g.w4;
     if (e >= cells * batch_num) return;
     const int64_t bt = e / cells;
-    merge_scatter_old_cell(g, bt, e - bt * cells, slot, ifn_L2, scores_back, winner);
+    merge_scatter_old_cell(g, bt * g.h * g.w, e - bt * cells, slot, ifn_L2, scores_back, winner);
 }
 
-__device__ __forceinline__ void merge_finish_old_el(const MergeGeom& g, int64_t e, const int32_t* __restrict__ patch_of,
-                                                    const unsigned* __restrict__ winner, const uint8_t* __restrict__ row_forced,
-                                                    uint8_t* __restrict__ out) {
+__device__ __forceinline__ void merge_finish_old_el(const MergeGeom& g0, const PairShapes& ps, int64_t e,
+                                                    const int32_t* __restrict__ patch_of, const unsigned* __restrict__ winner,
+                                                    const uint8_t* __restrict__ row_forced, uint8_t* __restrict__ out) {
     const int64_t b = e / 144;
     const int cell = (int)(e - b * 144), x = cell % 12, y = cell / 12;
     const int a = y / 4, r = y % 4, c = x / 4, s = x % 4;
     const int64_t q = patch_of[b];
     uint8_t res = 1;
     if (q >= 0) {
-        const int hw = g.h * g.w;
-        const int64_t bt = q / hw;
-        const int p = (int)(q - bt * hw), hh = p / g.w, ww = p % g.w;
-        const unsigned v = winner[bt * g.per + ((int64_t)(4 * hh + r) * g.w4 + 4 * ww + s) * 9 + a * 3 + c];
+        const int64_t bt = ps.shape ? ps.pair_of(q) : q / (g0.h * g0.w);
+        const MergeGeom g = pair_geom(g0, ps, bt);
+        const int64_t cb = ps.shape ? ps.base(bt) : bt * g.h * g.w;
+        const int p = (int)(q - cb), hh = p / g.w, ww = p % g.w;
+        const unsigned v = winner[cb * 144 + ((int64_t)(4 * hh + r) * g.w4 + 4 * ww + s) * 9 + a * 3 + c];
         if (v) res = (uint8_t)(v & 1u);
     }
     if (row_forced && row_forced[b]) res = 1;
@@ -310,14 +325,14 @@ __device__ __forceinline__ void merge_finish_old_el(const MergeGeom& g, int64_t 
 }
 
 __global__ void __launch_bounds__(256)
-merge_finish_old_kernel(MergeGeom g, RowBlock rb, const int32_t* __restrict__ patch_of,
+merge_finish_old_kernel(MergeGeom g, PairShapes ps, RowBlock rb, const int32_t* __restrict__ patch_of,
                         const unsigned* __restrict__ winner, const uint8_t* __restrict__ row_forced,
                         uint8_t* __restrict__ out) {
     int64_t base, B;
     rb.get(base, B);
     const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (el >= B * 144) return;
-    merge_finish_old_el(g, el + base * 144, patch_of, winner, row_forced, out);
+    merge_finish_old_el(g, ps, el + base * 144, patch_of, winner, row_forced, out);
 }
 
 // ---- merge_patches_new for SEVERAL chunks of a row table in two fully parallel launches ---------------------------------------
@@ -338,6 +353,8 @@ struct MergeTable {
     int Cmax, c_lo, c_hi;
     int64_t pairs, row_origin, rows_local;
     const int64_t* chunk_base; const int32_t* row_cell; const int32_t* row_slot; const uint8_t* row_forced;
+    PairShapes ps;                // the pairs' grids; row_slot is [Cmax, ps.cells]
+    const int32_t* row_pair;      // ragged: the row's pair (uniform: row_cell / N)
 };
 
 // second_layer.py:194-201 for one cell: weighted trust score and updated flag from the raw ones
@@ -354,17 +371,19 @@ __device__ __forceinline__ float merge_prepared(float t, uint8_t f_in, int x, in
 }
 
 __global__ void __launch_bounds__(256)
-merge_select_new_par_kernel(MergeGeom g, MergeTable tb, const float* __restrict__ trust, const uint8_t* __restrict__ ifn_L2,
+merge_select_new_par_kernel(MergeGeom g0, MergeTable tb, const float* __restrict__ trust, const uint8_t* __restrict__ ifn_L2,
                             const double* __restrict__ scores_back, int fresh, uint8_t* __restrict__ out) {
-    const int64_t first = tb.chunk_base[tb.c_lo], last = tb.chunk_base[tb.c_hi];
+    // the thread window is the walked blocks clipped to the rows this call holds (an overflowing table's chunk_base[Cmax]
+    // exceeds rows_cap)
+    const int64_t first = max(tb.chunk_base[tb.c_lo], tb.row_origin);
+    const int64_t last = min(tb.chunk_base[tb.c_hi], tb.row_origin + tb.rows_local);
     const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (el >= (last - first) * 144) return;
     const int64_t row = first + el / 144;
     const int cell = (int)(el % 144), x = cell % 12, y = cell / 12;
     int c = tb.c_lo;
     while (c + 1 < tb.c_hi && row >= tb.chunk_base[c + 1]) ++c;       // the row's chunk
-    const int N = g.h * g.w;
-    const int64_t NP = tb.pairs * N;
+    const int64_t NP = tb.ps.cells;
     const int32_t q = tb.row_cell[row];
     trust -= tb.row_origin * 144; ifn_L2 -= tb.row_origin * 144; out -= tb.row_origin * 144;
     const int64_t e = row * 144 + cell;
@@ -372,11 +391,14 @@ merge_select_new_par_kernel(MergeGeom g, MergeTable tb, const float* __restrict_
     if (q >= 0) {
         uint8_t f_own;
         (void)merge_prepared(trust[e], ifn_L2[e], x, y, f_own);
-        const int bt = q / N, pl = q - bt * N, hh = pl / g.w, ww = pl - hh * g.w;
+        const int bt = tb.row_pair ? tb.row_pair[row] : q / (g0.h * g0.w);
+        const MergeGeom g = pair_geom(g0, tb.ps, bt);
+        const int64_t cb = tb.ps.shape ? tb.ps.base(bt) : (int64_t)bt * g.h * g.w;
+        const int pl = (int)(q - cb), hh = pl / g.w, ww = pl - hh * g.w;
         const int a = y >> 2, r = y & 3, cc = x >> 2, s_ = x & 3;
         const int Y = 4 * hh + r + 4 * (a - 1), X = 4 * ww + s_ + 4 * (cc - 1);
         if (Y >= 0 && Y < g.h4 && X >= 0 && X < g.w4) {
-            const int64_t qs = (int64_t)bt * N + (Y >> 2) * g.w + (X >> 2);      // the owner of fine cell (Y, X)
+            const int64_t qs = cb + (Y >> 2) * g.w + (X >> 2);                   // the owner of fine cell (Y, X)
             int64_t rs = -1;                                                  // its row in the latest chunk <= c of the walk
             for (int c2 = c; c2 >= tb.c_lo && rs < 0; --c2) rs = tb.row_slot[(int64_t)c2 * NP + qs];
             const double* u = scores_back + (qs * 16 + (Y & 3) * 4 + (X & 3)) * 9;
@@ -404,12 +426,11 @@ merge_select_new_par_kernel(MergeGeom g, MergeTable tb, const float* __restrict_
 }
 
 __global__ void __launch_bounds__(256)
-merge_prepare_new_par_kernel(MergeGeom g, MergeTable tb, float* __restrict__ trust, uint8_t* __restrict__ ifn_L2,
+merge_prepare_new_par_kernel(MergeTable tb, float* __restrict__ trust, uint8_t* __restrict__ ifn_L2,
                              double* __restrict__ scores_back, int fresh, uint8_t* __restrict__ out) {
     const int64_t first = tb.chunk_base[tb.c_lo], last = tb.chunk_base[tb.c_hi];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int N = g.h * g.w;
-    const int64_t NP = tb.pairs * N;
+    const int64_t NP = tb.ps.cells;
     if (fresh && i < NP * 144) {                        // pats.py:32: a pair starts from zeros - patches without a row keep them
         const int64_t qz = i / 144;
         bool has = false;
@@ -501,12 +522,15 @@ struct ResultArgs {
     int64_t period0;
     float ap0_div, ap1_div;
     int32_t* match_row;
+    // ragged batch (ps.shape set): level-0 cell ecell = c * ps.cells + packed cell; patch_size0 of its pair is (s0, h_p, w_p)
+    PairShapes ps;
 };
 
 __global__ void __launch_bounds__(256)
 get_result_kernel(ResultArgs g, const int32_t* __restrict__ row_cell, Scan sc1) {
     // a workgroup stays inside one level-1 row (blocks per row = ceil(n1 / 256)): the row index and everything that
-    // hangs on it is workgroup-uniform, and no thread does a 64-bit division
+    // hangs on it is workgroup-uniform.  In a uniform batch no thread does a 64-bit division; a ragged batch (g.ps.shape)
+    // adds one 64-bit division and a binary search over cell_base per thread, both on the row's workgroup-uniform cell
     const unsigned n0 = (unsigned)(g.h0 * g.w0), n1 = (unsigned)(g.h1 * g.w1), bpr = (n1 + 255u) / 256u;
     const unsigned krow = blockIdx.x / bpr, j = (blockIdx.x - krow * bpr) * 256u + threadIdx.x;
     const int64_t k = krow, f = k * n1 + j;
@@ -515,8 +539,21 @@ get_result_kernel(ResultArgs g, const int32_t* __restrict__ row_cell, Scan sc1) 
     const int64_t M = sc1.at(f);
     if (M >= g.capacity) return;
     const int64_t ecell = row_cell[k];
-    const unsigned bt = (unsigned)ecell / n0, i = (unsigned)ecell - bt * n0;
-    const int64_t e = g.period0 ? ecell % g.period0 : ecell;      // where the level-0 point / scale of that cell live
+    unsigned bt, i, w0;
+    int64_t e;                                                     // where the level-0 point / scale of that cell live
+    if (g.ps.shape) {
+        const int64_t c = ecell / g.ps.cells;
+        e = ecell - c * g.ps.cells;
+        const int64_t p = g.ps.pair_of(e);
+        bt = (unsigned)(c * g.ps.pairs + p);
+        i = (unsigned)(e - g.ps.base(p));
+        w0 = (unsigned)g.ps.wp(p);
+    } else {
+        bt = (unsigned)ecell / n0;
+        i = (unsigned)ecell - bt * n0;
+        w0 = (unsigned)g.w0;
+        e = g.period0 ? ecell % g.period0 : ecell;
+    }
     const bool c0 = g.ch0[bt] != 0, c1 = g.ch1[k] != 0;
     const float z0 = (float)g.s0, z1 = (float)g.s1;
     const float sc1l = g.sc1 ? g.sc1[g.sc1_cell_stride ? f * g.sc1_cell_stride + 1 : k * 2 + 1] : g.sc0[e * 2 + 1];
@@ -524,7 +561,7 @@ get_result_kernel(ResultArgs g, const int32_t* __restrict__ row_cell, Scan sc1) 
     if (g.match_row) g.match_row[M] = (int32_t)k;
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
-        const float pos0 = (float)((d == 0 ? i / (unsigned)g.w0 : i % (unsigned)g.w0) * (unsigned)g.s0);
+        const float pos0 = (float)((d == 0 ? i / w0 : i % w0) * (unsigned)g.s0);
         float dl0 = pos0 + 0.5f * z0;
         dl0 = dl0 - (1.5f * g.sc0[e * 2 + 1]) * z0;
         const float a0 = g.ap0_div != 0.0f ? g.ap0[e * 2 + (1 - d)] / g.ap0_div : g.ap0[e * 2 + d];
@@ -583,15 +620,61 @@ extern "C" int pats_merge_patches(int merge_new, int64_t B, float* trust_score, 
     } else {
         if (hipMemsetAsync(winner, 0, sizeof(unsigned) * (size_t)(batch_num * g.per), st) != hipSuccess)
             return check_launch("merge memset");
-        hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * batch_num)), dim3(256), 0, st, g,
+        const PairShapes ps = uniform_shapes(batch_num, g.h, g.w, (int64_t)g.h * g.w);
+        hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * batch_num)), dim3(256), 0, st, g, ps,
                            batch_num, slot, if_nomatching1_L2, scores_back, winner);
-        hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, g, rb, patch_of, winner,
+        hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, g, ps, rb, patch_of, winner,
                            (const uint8_t*)nullptr, out);
     }
     return check_launch("merge_patches");
 }
 
 // ---- the merges of a batch of pairs: chunk blocks in order, every block over all pairs (row table of batch.hip) ----
+// the merges of a whole row table, uniform or ragged (ps; g = the uniform grid, unused when ragged)
+static int merge_batch_impl(int merge_new, int Cmax, const MergeGeom& g, const PairShapes& ps, int64_t rows_cap, const int64_t* chunk_base,
+                            const int32_t* row_cell, const int32_t* row_pair, const int32_t* row_slot, const uint8_t* row_forced,
+                            float* trust_score, uint8_t* if_nomatching1_L2, double* scores_back, int zero_scores_back, uint8_t* out,
+                            void* workspace, hipStream_t st) {
+    const int64_t pairs = ps.pairs, NP = ps.cells;
+    const int64_t block_cap = NP < rows_cap ? NP : rows_cap;       // a chunk block holds at most one row per coarse cell
+    unsigned* winner = reinterpret_cast<unsigned*>(workspace);
+    // merge_new: two parallel launches for all chunks (merge_select_new_par_kernel); PATS_MERGE_PER_CHUNK=1 (diagnostic library, uniform
+    // batches): the launch chain per chunk of rounds 3-5.  merge_old (indoor: one chunk, cap 512) keeps its chain.
+    static const bool per_chunk = [] { const char* e = diag_env("PATS_MERGE_PER_CHUNK"); return e && atoi(e) != 0; }();
+    if (merge_new && (!per_chunk || ps.shape)) {
+        const MergeTable tb{Cmax, 0, Cmax, pairs, 0, rows_cap, chunk_base, row_cell, row_slot, row_forced, ps, row_pair};
+        hipLaunchKernelGGL(merge_select_new_par_kernel, dim3(blocks256(rows_cap * 144)), dim3(256), 0, st, g, tb, trust_score, if_nomatching1_L2,
+                           scores_back, zero_scores_back, out);
+        const int64_t n2 = rows_cap > NP ? rows_cap : NP;
+        hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n2 * 144)), dim3(256), 0, st, tb, trust_score, if_nomatching1_L2,
+                           scores_back, zero_scores_back, out);
+        return check_launch("merge_patches_batch");
+    }
+    // rows outside every block (padding past the total) are never visited: "no match"
+    if (fill_bytes(out, 1, (size_t)rows_cap * 144, st)) return PATS_ERR_LAUNCH;
+    // pats.py:32: every pair starts from a zeroed scores_back
+    if (zero_scores_back && fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
+    const int64_t fine_cells = ps.shape ? NP * 16 : (int64_t)g.h4 * g.w4 * pairs;
+    for (int c = 0; c < Cmax; ++c) {
+        const RowBlock rb{chunk_base + c, 0};
+        hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, merge_new, rb, trust_score,
+                           if_nomatching1_L2, row_cell, scores_back);
+        if (merge_new) {
+            hipLaunchKernelGGL(merge_select_new_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, rb, row_cell,
+                               if_nomatching1_L2, scores_back, row_forced, out);
+        } else {
+            if (fill_bytes(winner, 0, sizeof(unsigned) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
+            hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256(fine_cells)), dim3(256), 0, st, g, ps,
+                               (int)pairs, row_slot + (int64_t)c * NP, if_nomatching1_L2, scores_back, winner);
+            hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, ps, rb, row_cell, winner,
+                               row_forced, out);
+            // merge_patches_old hands back a zeroed scores_back (second_layer.py:191): the next chunk starts from zeros
+            if (fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
+        }
+    }
+    return check_launch("merge_patches_batch");
+}
+
 extern "C" size_t pats_merge_batch_workspace_bytes(int64_t pairs, int H, int W) {
     if (pairs < 1 || H < 32 || W < 32) return 0;
     return (size_t)(pairs * (int64_t)(H / 32) * 4 * (W / 32) * 4 * 9) * sizeof(unsigned) + 64;
@@ -608,45 +691,10 @@ extern "C" int pats_merge_patches_batch(int merge_new, int Cmax, int64_t pairs, 
                  "merge_patches_batch: null pointer");
     PATS_REQUIRE(merge_new || (workspace && workspace_bytes >= pats_merge_batch_workspace_bytes(pairs, H, W)),
                  "merge_patches_batch: workspace too small");
-    hipStream_t st = as_stream(stream);
     MergeGeom g{H / 32, W / 32, 4 * (H / 32), 4 * (W / 32), (int64_t)(H / 32) * 4 * (W / 32) * 4 * 9};
-    const int64_t NP = pairs * g.h * g.w;
-    const int64_t block_cap = NP < rows_cap ? NP : rows_cap;       // a chunk block holds at most one row per coarse cell
-    unsigned* winner = reinterpret_cast<unsigned*>(workspace);
-    // merge_new: two parallel launches for all chunks (merge_select_new_par_kernel); PATS_MERGE_PER_CHUNK=1 (diagnostic library): the
-    // launch chain per chunk of rounds 3-5.  merge_old (indoor: one chunk, cap 512) keeps its chain.
-    static const bool per_chunk = [] { const char* e = diag_env("PATS_MERGE_PER_CHUNK"); return e && atoi(e) != 0; }();
-    if (merge_new && !per_chunk) {
-        const MergeTable tb{Cmax, 0, Cmax, pairs, 0, rows_cap, chunk_base, row_cell, row_slot, row_forced};
-        hipLaunchKernelGGL(merge_select_new_par_kernel, dim3(blocks256(rows_cap * 144)), dim3(256), 0, st, g, tb, trust_score, if_nomatching1_L2,
-                           scores_back, zero_scores_back, out);
-        const int64_t n2 = rows_cap > NP ? rows_cap : NP;
-        hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n2 * 144)), dim3(256), 0, st, g, tb, trust_score, if_nomatching1_L2,
-                           scores_back, zero_scores_back, out);
-        return check_launch("merge_patches_batch");
-    }
-    // rows outside every block (padding past the total) are never visited: "no match"
-    if (fill_bytes(out, 1, (size_t)rows_cap * 144, st)) return PATS_ERR_LAUNCH;
-    // pats.py:32: every pair starts from a zeroed scores_back
-    if (zero_scores_back && fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
-    for (int c = 0; c < Cmax; ++c) {
-        const RowBlock rb{chunk_base + c, 0};
-        hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, merge_new, rb, trust_score,
-                           if_nomatching1_L2, row_cell, scores_back);
-        if (merge_new) {
-            hipLaunchKernelGGL(merge_select_new_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, rb, row_cell,
-                               if_nomatching1_L2, scores_back, row_forced, out);
-        } else {
-            if (fill_bytes(winner, 0, sizeof(unsigned) * (size_t)(pairs * g.per), st)) return PATS_ERR_LAUNCH;
-            hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * pairs)), dim3(256), 0, st, g,
-                               (int)pairs, row_slot + (int64_t)c * NP, if_nomatching1_L2, scores_back, winner);
-            hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, rb, row_cell, winner,
-                               row_forced, out);
-            // merge_patches_old hands back a zeroed scores_back (second_layer.py:191): the next chunk starts from zeros
-            if (fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
-        }
-    }
-    return check_launch("merge_patches_batch");
+    return merge_batch_impl(merge_new, Cmax, g, uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w), rows_cap, chunk_base, row_cell,
+                            nullptr, row_slot, row_forced, trust_score, if_nomatching1_L2, scores_back, zero_scores_back, out, workspace,
+                            as_stream(stream));
 }
 
 // Chunks [c_lo, c_hi) of the table only, on tensors that hold table rows row_origin .. row_origin + rows_local (trust_score,
@@ -669,11 +717,12 @@ extern "C" int pats_merge_patches_chunks(int merge_new, int Cmax, int c_lo, int 
     hipStream_t st = as_stream(stream);
     const int64_t NP = pairs * g.h * g.w;
     if (merge_new) {
-        const MergeTable tb{Cmax, c_lo, c_hi, pairs, row_origin, rows_local, chunk_base, row_cell, row_slot, row_forced};
+        const MergeTable tb{Cmax, c_lo, c_hi, pairs, row_origin, rows_local, chunk_base, row_cell, row_slot, row_forced,
+                            uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w), nullptr};
         hipLaunchKernelGGL(merge_select_new_par_kernel, dim3(blocks256(rows_local * 144)), dim3(256), 0, st, g, tb, trust_score,
                            if_nomatching1_L2, scores_back, zero_scores_back, out);
         const int64_t n2 = zero_scores_back && NP > rows_local ? NP : rows_local;
-        hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n2 * 144)), dim3(256), 0, st, g, tb, trust_score, if_nomatching1_L2,
+        hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n2 * 144)), dim3(256), 0, st, tb, trust_score, if_nomatching1_L2,
                            scores_back, zero_scores_back, out);
         return check_launch("merge_patches_chunks");
     }
@@ -689,12 +738,36 @@ extern "C" int pats_merge_patches_chunks(int merge_new, int Cmax, int c_lo, int 
         const RowBlock rb{chunk_base + c, 0};
         hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, 0, rb, tr, fl, row_cell, scores_back);
         if (fill_bytes(winner, 0, sizeof(unsigned) * (size_t)(pairs * g.per), st)) return PATS_ERR_LAUNCH;
-        hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * pairs)), dim3(256), 0, st, g, (int)pairs,
+        const PairShapes ps = uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w);
+        hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * pairs)), dim3(256), 0, st, g, ps, (int)pairs,
                            row_slot + (int64_t)c * NP, fl, scores_back, winner);
-        hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, rb, row_cell, winner, row_forced, ou);
+        hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, ps, rb, row_cell, winner, row_forced, ou);
         if (fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
     }
     return check_launch("merge_patches_chunks");
+}
+
+extern "C" size_t pats_merge_ragged_workspace_bytes(int64_t total_cells) {
+    return total_cells < 1 ? 0 : (size_t)total_cells * 144 * sizeof(unsigned) + 64;
+}
+
+extern "C" int pats_merge_patches_ragged(const pats_pair_table_t* tab, int merge_new, int Cmax, int64_t rows_cap, const int64_t* chunk_base,
+                                         const int32_t* row_cell, const int32_t* row_pair, const int32_t* row_slot, const uint8_t* row_forced,
+                                         float* trust_score, uint8_t* if_nomatching1_L2, double* scores_back, int zero_scores_back,
+                                         uint8_t* out, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    PairShapes ps;
+    int hmax = 0;
+    const int rc = ragged_shapes(tab, &ps, &hmax, "merge_patches_ragged");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && rows_cap >= 0 && rows_cap < (1ll << 31), "merge_patches_ragged: bad shape");
+    if (rows_cap == 0) return PATS_OK;
+    PATS_REQUIRE(chunk_base && row_cell && row_pair && row_slot && row_forced && trust_score && if_nomatching1_L2 && scores_back && out,
+                 "merge_patches_ragged: null pointer");
+    PATS_REQUIRE(merge_new || (workspace && workspace_bytes >= pats_merge_ragged_workspace_bytes(ps.cells)),
+                 "merge_patches_ragged: workspace too small");
+    const MergeGeom g{0, 0, 0, 0, 0};
+    return merge_batch_impl(merge_new, Cmax, g, ps, rows_cap, chunk_base, row_cell, row_pair, row_slot, row_forced, trust_score,
+                            if_nomatching1_L2, scores_back, zero_scores_back, out, workspace, as_stream(stream));
 }
 
 // ---- matches of a batch, grouped by pair (throughput mode's hand-over: what batch.split_by_pair did with argsort + bincount) ----
@@ -707,12 +780,13 @@ struct ByPairArgs {
     int Cmax; int64_t pairs; int N;
     float* out_l; float* out_r; int64_t* pair_off; int64_t* seg_lo; int64_t* seg_hi; int64_t* seg_dst;
     const int64_t* P_dev; const int32_t* status;      // optional: the step's summary behind the offsets (pats_matches_by_pair_summary_f32)
+    const int32_t* row_pair;                          // optional: the row's pair (any batch); else row_cell / N
 };
 __device__ __forceinline__ int64_t bypair_key(const ByPairArgs& g, int64_t i) {
     const int64_t row = g.match_row[i];
     int c = 0;
     for (int k = 1; k < g.Cmax; ++k) c += (row >= g.chunk_base[k]) ? 1 : 0;            // chunk blocks are ascending
-    return (int64_t)c * g.pairs + g.row_cell[row] / g.N;
+    return (int64_t)c * g.pairs + (g.row_pair ? g.row_pair[row] : g.row_cell[row] / g.N);
 }
 __global__ void __launch_bounds__(256) bypair_runs_kernel(ByPairArgs g) {
     const int64_t M = *g.M;
@@ -770,7 +844,7 @@ extern "C" size_t pats_matches_by_pair_workspace_bytes(int Cmax, int64_t pairs) 
 static int matches_by_pair_impl(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                 const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                 float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
-                                void* workspace, size_t workspace_bytes, pats_stream_t stream);
+                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair = nullptr);
 extern "C" int pats_matches_by_pair_f32(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                         const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                         float* out_l, float* out_r, int64_t* pair_off, void* workspace, size_t workspace_bytes,
@@ -789,12 +863,20 @@ extern "C" int pats_matches_by_pair_summary_f32(const float* matches_l, const fl
     return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, row_cell, chunk_base, Cmax, pairs, N, out_l, out_r, pair_off, P_dev,
                                 status, workspace, workspace_bytes, stream);
 }
+extern "C" int pats_matches_by_row_pair_summary_f32(const float* matches_l, const float* matches_r, const int32_t* match_row,
+                                                    const int64_t* M_dev, const int32_t* row_pair, const int64_t* chunk_base, int Cmax,
+                                                    int64_t pairs, float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev,
+                                                    const int32_t* status, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(row_pair, "matches_by_row_pair_summary: null row_pair");     // status null: pair_off is the pairs + 1 offsets only
+    return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, nullptr, chunk_base, Cmax, pairs, 1, out_l, out_r, pair_off, P_dev,
+                                status, workspace, workspace_bytes, stream, row_pair);
+}
 static int matches_by_pair_impl(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                 const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                 float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
-                                void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair) {
     PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && N >= 1, "matches_by_pair: bad shape");
-    PATS_REQUIRE(matches_l && matches_r && match_row && M_dev && row_cell && chunk_base && out_l && out_r && pair_off,
+    PATS_REQUIRE(matches_l && matches_r && match_row && M_dev && (row_cell || row_pair) && chunk_base && out_l && out_r && pair_off,
                  "matches_by_pair: null pointer");
     PATS_REQUIRE(workspace && workspace_bytes >= pats_matches_by_pair_workspace_bytes(Cmax, pairs), "matches_by_pair: workspace too small");
     hipStream_t st = as_stream(stream);
@@ -802,7 +884,7 @@ static int matches_by_pair_impl(const float* matches_l, const float* matches_r, 
     const int64_t nseg = (int64_t)Cmax * pairs;
     if (fill_bytes(ws, 0, sizeof(int64_t) * (size_t)(2 * nseg), st)) return PATS_ERR_LAUNCH;        // runs without matches: lo = hi = 0
     ByPairArgs g{matches_l, matches_r, match_row, M_dev, row_cell, chunk_base, Cmax, pairs, N, out_l, out_r, pair_off, ws, ws + nseg,
-                 ws + 2 * nseg, P_dev, status};
+                 ws + 2 * nseg, P_dev, status, row_pair};
     hipLaunchKernelGGL(bypair_runs_kernel, dim3(2048), dim3(256), 0, st, g);
     hipLaunchKernelGGL(bypair_offsets_kernel, dim3(1), dim3(256), 0, st, g);
     hipLaunchKernelGGL(bypair_copy_kernel, dim3(2048), dim3(256), 0, st, g);
@@ -857,13 +939,14 @@ static int get_result_impl(int batch_size, const uint8_t* if_nomatching0, const 
                                    const int* patch_size0, const int* patch_size1, const uint8_t* left_choice0,
                                    const uint8_t* left_choice1, float* matches_l, float* matches_r,
                                    int64_t capacity, int64_t* count, void* workspace, size_t workspace_bytes,
-                                   pats_stream_t stream, int64_t period0, float ap0_div, float ap1_div, int32_t* match_row) {
+                                   pats_stream_t stream, int64_t period0, float ap0_div, float ap1_div, int32_t* match_row,
+                                   const PairShapes* ragged) {
     PATS_REQUIRE(batch_size >= 1 && rows1 >= 0 && capacity >= 0 && patch_size0 && patch_size1, "get_result: bad shape");
     PATS_REQUIRE(scale1_cell_stride == 0 || scale1_cell_stride == 2, "get_result: scale1_cell_stride must be 0 or 2");
     PATS_REQUIRE(count, "get_result: null count");
     const int64_t n0 = (int64_t)patch_size0[1] * patch_size0[2], n1 = (int64_t)patch_size1[1] * patch_size1[2];
     PATS_REQUIRE(n0 > 0 && n1 > 0 && patch_size0[0] > 0 && patch_size1[0] > 0, "get_result: bad patch_size");
-    const int64_t cells0 = batch_size * n0;
+    const int64_t cells0 = ragged ? (int64_t)batch_size / ragged->pairs * ragged->cells : batch_size * n0;
     PATS_REQUIRE(workspace && workspace_bytes >= pats_get_result_workspace_bytes(cells0, rows1, n1), "get_result: workspace too small");
     PATS_REQUIRE(if_nomatching0 && average_point0 && scale0 && left_choice0, "get_result: null pointer");
     hipStream_t st = as_stream(stream);
@@ -882,7 +965,7 @@ static int get_result_impl(int batch_size, const uint8_t* if_nomatching0, const 
     ResultArgs g{if_nomatching1, average_point0, average_point1, scale0, scale1, scale1_cell_stride,
                  patch_size0[0], patch_size0[1], patch_size0[2], patch_size1[0], patch_size1[1], patch_size1[2],
                  left_choice0, left_choice1, rows0_dev, rows1, capacity, matches_l, matches_r, period0, ap0_div, ap1_div,
-                 match_row};
+                 match_row, ragged ? *ragged : PairShapes{}};
     const int64_t blocks = rows1 * (((int64_t)n1 + 255) / 256);
     PATS_REQUIRE(blocks < (1ll << 31), "get_result: grid too large (split the batch)");
     hipLaunchKernelGGL(get_result_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, row_cell, s1);
@@ -898,7 +981,7 @@ extern "C" int pats_get_result_f32(int batch_size, const uint8_t* if_nomatching0
                                    pats_stream_t stream) {
     return get_result_impl(batch_size, if_nomatching0, if_nomatching1, rows1, average_point0, average_point1, scale0, scale1,
                            scale1_cell_stride, patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r,
-                           capacity, count, workspace, workspace_bytes, stream, 0, 0.0f, 0.0f, nullptr);
+                           capacity, count, workspace, workspace_bytes, stream, 0, 0.0f, 0.0f, nullptr, nullptr);
 }
 
 // get_result of a batch of pairs in one call (pats.py:68-73 for every (chunk, pair) at once): level-0 batch = the
@@ -916,5 +999,22 @@ extern "C" int pats_get_result_chunks_f32(int Cmax, int64_t pairs, const uint8_t
     const int64_t period0 = pairs * (int64_t)patch_size0[1] * patch_size0[2];
     return get_result_impl((int)(Cmax * pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0,
                            patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count,
-                           workspace, workspace_bytes, stream, period0, 32.0f, 2.0f, match_row);
+                           workspace, workspace_bytes, stream, period0, 32.0f, 2.0f, match_row, nullptr);
+}
+
+extern "C" int pats_get_result_chunks_ragged_f32(const pats_pair_table_t* tab, int Cmax, const uint8_t* masks, const uint8_t* if_nomatching16,
+                                                 int64_t rows_cap, const float* pts_new, const float* pts16, const float* scales,
+                                                 const int* patch_size1, const uint8_t* left_choice0, const uint8_t* left_choice1,
+                                                 float* matches_l, float* matches_r, int32_t* match_row, int64_t capacity, int64_t* count,
+                                                 void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    PairShapes ps;
+    int hmax = 0;
+    const int rc = ragged_shapes(tab, &ps, &hmax, "get_result_chunks_ragged");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && ps.cells * Cmax < (1ll << 31), "get_result_chunks_ragged: bad shape");
+    // patch_size0 only carries the level-0 step (32); each pair's grid comes from the table
+    const int ps0[3] = {32, 1, 1};
+    return get_result_impl((int)(Cmax * ps.pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0, ps0,
+                           patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count, workspace, workspace_bytes,
+                           stream, ps.cells, 32.0f, 2.0f, match_row, &ps);
 }

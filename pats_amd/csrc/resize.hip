@@ -94,17 +94,20 @@ imgs_bounds_kernel(const float* __restrict__ x_scale, const float* __restrict__ 
 // images before it (its row offset into the compacted bound table; flags are one byte per patch, so
 // even hundreds of images cost a few hundred KB of L2 reads), then compacts its own patches.
 // K_img[i] = matches of image i; K_total (written by the last block) = rows of bound5 that are valid.
+// A ragged batch (PairShapes::shape set): image i has its own grid and owns the packed cells [base(i), base(i) + ncell(i)).
 __global__ void __launch_bounds__(1024)
 imgs_bounds_batch_kernel(const float* __restrict__ x_scale, const float* __restrict__ y_scale,
-                         const float* __restrict__ average_point, const uint8_t* __restrict__ ifn, int Np,
-                         int height, int width, int64_t* __restrict__ bound5, int64_t* __restrict__ K_img,
+                         const float* __restrict__ average_point, const uint8_t* __restrict__ ifn, PairShapes ps,
+                         int64_t* __restrict__ bound5, int64_t* __restrict__ K_img,
                          int64_t* __restrict__ K_total, float* __restrict__ xsn, float* __restrict__ ysn,
                          float* __restrict__ avn) {
     __shared__ int part[16];
     __shared__ int64_t off_s;
     const int img = blockIdx.x, tid = threadIdx.x;
+    const int64_t cb = ps.base(img);
+    const int Np = (int)ps.ncell(img), height = ps.hp(img), width = ps.wp(img);
     int cnt = 0;
-    for (int64_t k = tid; k < (int64_t)img * Np; k += 1024) cnt += ifn[k] ? 0 : 1;
+    for (int64_t k = tid; k < cb; k += 1024) cnt += ifn[k] ? 0 : 1;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o);
     if ((tid & 63) == 0) part[tid >> 6] = cnt;
@@ -118,22 +121,23 @@ imgs_bounds_batch_kernel(const float* __restrict__ x_scale, const float* __restr
     const int64_t off = off_s;
     wg_barrier();
     const int64_t i = img;
-    imgs_bounds_block(x_scale + i * Np, y_scale + i * Np, average_point + i * Np * 2, ifn + i * Np, Np, height, width,
-                      img, bound5 + off * 5, K_img + i, xsn + i * Np * 2, ysn + i * Np * 2, avn + i * Np * 2);
+    imgs_bounds_block(x_scale + cb, y_scale + cb, average_point + cb * 2, ifn + cb, Np, height, width,
+                      img, bound5 + off * 5, K_img + i, xsn + cb * 2, ysn + cb * 2, avn + cb * 2);
     if (tid == 0 && img == (int)gridDim.x - 1 && K_total) *K_total = off + K_img[i];
 }
 
 // ---- left crops: 96x96 windows on the fixed grid of the 32-px zero-padded left image ---------
 template <bool NT>
 __global__ void __launch_bounds__(288)
-left_crops_kernel(const float* __restrict__ left_all, int n_img, int H, int W, const int64_t* __restrict__ bound5,
-                  int width, float* __restrict__ out, const int64_t* __restrict__ K_dev) {
+left_crops_kernel(const float* __restrict__ left_all, int n_img, PairShapes ps, const int64_t* __restrict__ bound5,
+                  float* __restrict__ out, const int64_t* __restrict__ K_dev) {
     const int64_t k = blockIdx.x;
     if (K_dev && k >= *K_dev) return;          // launched over the capacity: rows past the device-side count
     const int64_t seq = bound5[k * 5 + 4];                 // img * 10000 + patch, utils.py:1374-1377
     const int patch = (int)(seq % 10000);
     const int64_t img = min(max(seq / 10000, (int64_t)0), (int64_t)n_img - 1);
-    const float* left = left_all + img * (int64_t)H * W * 3;
+    const int H = ps.Hpx(img), W = ps.Wpx(img), width = ps.wp(img);    // the image's own size: outside it is padding
+    const float* left = left_all + ps.img(img);
     const int r = patch / width, c = patch - r * width;
     // a row of the window is 288 contiguous floats of the source (or zeros): 72 lanes x 16 bytes, four rows per pass of
     // the 288 threads; the source offset is only 4-byte aligned in general (W * 3 floats per image row)
@@ -231,12 +235,14 @@ resize_chw_kernel(const float* __restrict__ input, int n_img, int C, int Hp, int
 // fuses F.pad (utils.py:1352), the NCHW permute and the caller's permute(0,2,3,1) (utils.py:1385)
 template <bool NT>
 __global__ void __launch_bounds__(256)
-resize_hwc_kernel(const float* __restrict__ right, int n_img, int H, int W, int margin,
+resize_hwc_kernel(const float* __restrict__ right, int n_img, PairShapes ps, int margin,
                   const int64_t* __restrict__ bound, float* __restrict__ out,
                   int32_t* __restrict__ status, const int64_t* __restrict__ K_dev) {
     const int64_t i = blockIdx.x;
     if (K_dev && i >= *K_dev) return;
     const int slab = blockIdx.y;
+    const int64_t im = min(max(bound[i * 5 + 4] / 10000, (int64_t)0), (int64_t)n_img - 1);   // an index outside: !g.ok below
+    const int H = ps.Hpx(im), W = ps.Wpx(im);
     const int Hp = H + 2 * margin, Wp = W + 2 * margin;
     const CropGeom g = crop_geom(bound, i, n_img, Hp, Wp);
     float* o = out + i * (96 * 96 * 3);
@@ -246,7 +252,7 @@ resize_hwc_kernel(const float* __restrict__ right, int n_img, int H, int W, int 
         return;
     }
     const float sh = (float)(g.ih - 1) / 95.0f, sw = (float)(g.iw - 1) / 95.0f;
-    const float* img = right + (int64_t)g.img * H * W * 3;
+    const float* img = right + ps.img(g.img);
     // one output PIXEL per thread and pass (taps, bounds tests and addresses once for the three channels; the three
     // floats of a tap are 12 contiguous bytes); coordinates fit 32 bits once the crop geometry has been validated
     const int y0 = (int)g.y0 - margin, x0 = (int)g.x0 - margin, ih = (int)g.ih, iw = (int)g.iw;
@@ -281,6 +287,22 @@ static bool crops_nt() {
     return nt;
 }
 
+static int launch_left_crops(const float* left, int n_img, const PairShapes& ps, const int64_t* bound5, int64_t K,
+                             const int64_t* K_dev, float* out, hipStream_t st) {
+    if (crops_nt()) hipLaunchKernelGGL(left_crops_kernel<true>, dim3((unsigned)K, 12), dim3(288), 0, st, left, n_img, ps, bound5, out, K_dev);
+    else hipLaunchKernelGGL(left_crops_kernel<false>, dim3((unsigned)K, 12), dim3(288), 0, st, left, n_img, ps, bound5, out, K_dev);
+    return check_launch("left_crops_kernel");
+}
+
+static int launch_resize_hwc(const float* right, int n_img, const PairShapes& ps, int margin, const int64_t* bound, int64_t K,
+                             const int64_t* K_dev, float* out, int32_t* status, hipStream_t st) {
+    if (crops_nt()) hipLaunchKernelGGL(resize_hwc_kernel<true>, dim3((unsigned)K, 4), dim3(256), 0, st, right, n_img, ps, margin, bound,
+                                       out, status, K_dev);
+    else hipLaunchKernelGGL(resize_hwc_kernel<false>, dim3((unsigned)K, 4), dim3(256), 0, st, right, n_img, ps, margin, bound, out,
+                            status, K_dev);
+    return check_launch("resize_hwc_kernel");
+}
+
 }  // namespace pats
 
 using namespace pats;
@@ -304,11 +326,8 @@ extern "C" int pats_left_crops_f32(const float* left, int n_img, int H, int W, c
     PATS_REQUIRE(K >= 0 && n_img > 0 && H > 0 && W > 0 && height > 0 && width > 0, "left_crops: bad shape");
     if (K == 0) return PATS_OK;
     PATS_REQUIRE(left && bound5 && out, "left_crops: null pointer");
-    if (crops_nt()) hipLaunchKernelGGL(left_crops_kernel<true>, dim3((unsigned)K, 12), dim3(288), 0, as_stream(stream),
-                                       left, n_img, H, W, bound5, width, out, (const int64_t*)nullptr);
-    else hipLaunchKernelGGL(left_crops_kernel<false>, dim3((unsigned)K, 12), dim3(288), 0, as_stream(stream),
-                            left, n_img, H, W, bound5, width, out, (const int64_t*)nullptr);
-    return check_launch("left_crops_kernel");
+    return launch_left_crops(left, n_img, uniform_shapes(n_img, height, width, 0, H, W), bound5, K, nullptr, out,
+                             as_stream(stream));
 }
 
 extern "C" int pats_compute_imgs_bounds_batch_f32(const float* x_scale, const float* y_scale,
@@ -320,7 +339,7 @@ extern "C" int pats_compute_imgs_bounds_batch_f32(const float* x_scale, const fl
     PATS_REQUIRE(x_scale && y_scale && average_point && if_nomatching && bound5 && K_img && x_scale_new &&
                      y_scale_new && average_new, "compute_imgs_bounds_batch: null pointer");
     hipLaunchKernelGGL(imgs_bounds_batch_kernel, dim3((unsigned)n_img), dim3(1024), 0, as_stream(stream), x_scale,
-                       y_scale, average_point, if_nomatching, Np, height, width, bound5, K_img, K_total,
+                       y_scale, average_point, if_nomatching, uniform_shapes(n_img, height, width, Np), bound5, K_img, K_total,
                        x_scale_new, y_scale_new, average_new);
     return check_launch("imgs_bounds_batch_kernel");
 }
@@ -331,11 +350,8 @@ extern "C" int pats_left_crops_counted_f32(const float* left, int n_img, int H, 
     PATS_REQUIRE(K_cap >= 0 && n_img > 0 && H > 0 && W > 0 && height > 0 && width > 0, "left_crops_counted: bad shape");
     if (K_cap == 0) return PATS_OK;
     PATS_REQUIRE(left && bound5 && out && K_dev, "left_crops_counted: null pointer");
-    if (crops_nt()) hipLaunchKernelGGL(left_crops_kernel<true>, dim3((unsigned)K_cap, 12), dim3(288), 0, as_stream(stream),
-                                       left, n_img, H, W, bound5, width, out, K_dev);
-    else hipLaunchKernelGGL(left_crops_kernel<false>, dim3((unsigned)K_cap, 12), dim3(288), 0, as_stream(stream),
-                            left, n_img, H, W, bound5, width, out, K_dev);
-    return check_launch("left_crops_kernel");
+    return launch_left_crops(left, n_img, uniform_shapes(n_img, height, width, 0, H, W), bound5, K_cap, K_dev, out,
+                             as_stream(stream));
 }
 
 extern "C" int pats_tensor_resize_f32(const float* input, int n_img, int C, int Hp, int Wp,
@@ -356,11 +372,8 @@ extern "C" int pats_tensor_resize_hwc_f32(const float* right, int n_img, int H, 
     PATS_REQUIRE(K >= 0 && n_img > 0 && H > 0 && W > 0 && margin >= 0, "tensor_resize_hwc: bad shape");
     if (K == 0) return PATS_OK;
     PATS_REQUIRE(right && bound && out, "tensor_resize_hwc: null pointer");
-    if (crops_nt()) hipLaunchKernelGGL(resize_hwc_kernel<true>, dim3((unsigned)K, 4), dim3(256), 0, as_stream(stream), right,
-                                       n_img, H, W, margin, bound, out, status, (const int64_t*)nullptr);
-    else hipLaunchKernelGGL(resize_hwc_kernel<false>, dim3((unsigned)K, 4), dim3(256), 0, as_stream(stream), right,
-                            n_img, H, W, margin, bound, out, status, (const int64_t*)nullptr);
-    return check_launch("resize_hwc_kernel");
+    return launch_resize_hwc(right, n_img, uniform_shapes(n_img, H / 32, W / 32, 0, H, W), margin, bound, K, nullptr, out, status,
+                             as_stream(stream));
 }
 
 extern "C" int pats_tensor_resize_hwc_counted_f32(const float* right, int n_img, int H, int W, int margin,
@@ -369,9 +382,45 @@ extern "C" int pats_tensor_resize_hwc_counted_f32(const float* right, int n_img,
     PATS_REQUIRE(K_cap >= 0 && n_img > 0 && H > 0 && W > 0 && margin >= 0, "tensor_resize_hwc_counted: bad shape");
     if (K_cap == 0) return PATS_OK;
     PATS_REQUIRE(right && bound && out && K_dev, "tensor_resize_hwc_counted: null pointer");
-    if (crops_nt()) hipLaunchKernelGGL(resize_hwc_kernel<true>, dim3((unsigned)K_cap, 4), dim3(256), 0, as_stream(stream), right,
-                                       n_img, H, W, margin, bound, out, status, K_dev);
-    else hipLaunchKernelGGL(resize_hwc_kernel<false>, dim3((unsigned)K_cap, 4), dim3(256), 0, as_stream(stream), right,
-                            n_img, H, W, margin, bound, out, status, K_dev);
-    return check_launch("resize_hwc_kernel");
+    return launch_resize_hwc(right, n_img, uniform_shapes(n_img, H / 32, W / 32, 0, H, W), margin, bound, K_cap, K_dev, out,
+                             status, as_stream(stream));
+}
+
+// ---- ragged batches: the same three kernels, each pair on its own grid and image (include/pats_amd.h) ----
+extern "C" int pats_compute_imgs_bounds_ragged_f32(const pats_pair_table_t* tab, const float* x_scale, const float* y_scale,
+                                                   const float* average_point, const uint8_t* if_nomatching, int64_t* bound5,
+                                                   int64_t* K_img, int64_t* K_total, float* x_scale_new, float* y_scale_new,
+                                                   float* average_new, pats_stream_t stream) {
+    PairShapes ps;
+    const int rc = ragged_shapes(tab, &ps, nullptr, "compute_imgs_bounds_ragged");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(ps.pairs <= 10000, "compute_imgs_bounds_ragged: more than 10000 images");
+    PATS_REQUIRE(x_scale && y_scale && average_point && if_nomatching && bound5 && K_img && x_scale_new && y_scale_new && average_new,
+                 "compute_imgs_bounds_ragged: null pointer");
+    hipLaunchKernelGGL(imgs_bounds_batch_kernel, dim3((unsigned)ps.pairs), dim3(1024), 0, as_stream(stream), x_scale, y_scale,
+                       average_point, if_nomatching, ps, bound5, K_img, K_total, x_scale_new, y_scale_new, average_new);
+    return check_launch("imgs_bounds_batch_kernel");
+}
+
+extern "C" int pats_left_crops_ragged_f32(const pats_pair_table_t* tab, const float* left, const int64_t* bound5, int64_t K_cap,
+                                          const int64_t* K_dev, float* out, pats_stream_t stream) {
+    PairShapes ps;
+    const int rc = ragged_shapes(tab, &ps, nullptr, "left_crops_ragged");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(K_cap >= 0 && K_cap < (1ll << 31), "left_crops_ragged: bad K_cap");
+    if (K_cap == 0) return PATS_OK;
+    PATS_REQUIRE(left && bound5 && out && K_dev, "left_crops_ragged: null pointer");
+    return launch_left_crops(left, (int)ps.pairs, ps, bound5, K_cap, K_dev, out, as_stream(stream));
+}
+
+extern "C" int pats_tensor_resize_hwc_ragged_f32(const pats_pair_table_t* tab, const float* right, int margin, const int64_t* bound5,
+                                                 int64_t K_cap, const int64_t* K_dev, float* out, int32_t* status,
+                                                 pats_stream_t stream) {
+    PairShapes ps;
+    const int rc = ragged_shapes(tab, &ps, nullptr, "tensor_resize_hwc_ragged");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(K_cap >= 0 && K_cap < (1ll << 31) && margin >= 0, "tensor_resize_hwc_ragged: bad shape");
+    if (K_cap == 0) return PATS_OK;
+    PATS_REQUIRE(right && bound5 && out && K_dev, "tensor_resize_hwc_ragged: null pointer");
+    return launch_resize_hwc(right, (int)ps.pairs, ps, margin, bound5, K_cap, K_dev, out, status, as_stream(stream));
 }

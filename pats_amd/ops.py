@@ -892,9 +892,49 @@ def get_result(batch_size, if_nomatching, average_point, scale, patch_size, left
 # throughput mode: the chunk loop of PATS.forward for a batch of pairs, no host read (csrc/batch.hip)
 # ------------------------------------------------------------------------------------------------
 class ChunkRows:
-    """The row table pats_chunk_rows_device builds (include/pats_amd.h): device tensors only."""
+    """The row table pats_chunk_rows_device / pats_chunk_rows_ragged build (include/pats_amd.h): device tensors only.
+    row_pair [rows_cap] (pair of the row, -1 past the total) and cell_base [pairs + 1] (pair p owns the packed cells
+    cell_base[p] .. cell_base[p + 1]) serve both kinds of batch; `table` is the PairTable of a ragged batch (h = w = None
+    there) and None for a uniform one."""
     __slots__ = ("pairs", "h", "w", "Cmax", "rows_cap", "sum_cycle", "cycle_num", "second", "third", "masks", "chunk_base",
-                 "crop_base", "row_cell", "row_forced", "row_crop", "row_slot", "status")
+                 "crop_base", "row_cell", "row_forced", "row_crop", "row_slot", "status", "table", "_row_pair", "_cell_base")
+
+    @property
+    def row_pair(self):
+        if getattr(self, "_row_pair", None) is None:          # uniform table: row_cell // N, formed on first use
+            N = self.h * self.w
+            self._row_pair = torch.where(self.row_cell >= 0, torch.div(self.row_cell, N, rounding_mode="floor"),
+                                         torch.full_like(self.row_cell, -1))
+        return self._row_pair
+
+    @property
+    def cell_base(self):
+        if getattr(self, "_cell_base", None) is None:
+            self._cell_base = torch.arange(self.pairs + 1, dtype=torch.int64, device=self.row_cell.device) * (self.h * self.w)
+        return self._cell_base
+
+
+class PairTable:
+    """The shapes of a ragged batch (pats_pair_table_t): grids (h_p, w_p) in batch order, packed cell ranges and the offsets
+    of the pairs' [32 h_p, 32 w_p, 3] images in a flat store - host copies (validated by every call) and device tensors."""
+
+    def __init__(self, shapes, device):
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.pairs = len(self.shapes)
+        self.shape_host = np.ascontiguousarray(np.array(self.shapes, np.int32).reshape(self.pairs, 2))
+        n = self.shape_host[:, 0].astype(np.int64) * self.shape_host[:, 1]
+        self.cell_base_host = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        self.img_base_host = np.concatenate([[0], np.cumsum(n * 1024 * 3)])[:-1].astype(np.int64)
+        self.cells = int(self.cell_base_host[-1])
+        self.hmax = int(self.shape_host[:, 0].max()) if self.pairs else 0
+        self.shape = torch.from_numpy(self.shape_host).to(device)
+        self.cell_base = torch.from_numpy(self.cell_base_host).to(device)
+        self.img_base = torch.from_numpy(self.img_base_host).to(device)
+        self.ct = _lib.PairTable(self.pairs, self.shape_host.ctypes.data, self.cell_base_host.ctypes.data, self.shape.data_ptr(),
+                                 self.cell_base.data_ptr(), self.img_base.data_ptr())
+
+    def ref(self):
+        return ctypes.byref(self.ct)
 
 
 def max_chunks(height, width, max_once_used):
@@ -911,6 +951,7 @@ def chunk_rows(if_nomatching1, height, width, max_once_used, Cmax=None, rows_cap
     if f.numel() != pairs * N:
         raise RuntimeError("chunk_rows: if_nomatching1 must be [pairs, height*width]")
     r = ChunkRows()
+    r.table = None
     r.pairs, r.h, r.w = pairs, int(height), int(width)
     r.Cmax = max_chunks(height, width, max_once_used) if Cmax is None else int(Cmax)
     r.rows_cap = pairs * (N + (r.Cmax - 1) * width) if rows_cap is None else int(rows_cap)
@@ -946,6 +987,8 @@ def merge_patches_batch(merge_new, rows, trust_score, original_image_shape, if_n
         raise RuntimeError("merge_patches_batch: trust_score must be a contiguous float32 GPU tensor (it is updated in place)")
     if if_nomatching1_L2.dtype != torch.bool or not if_nomatching1_L2.is_contiguous():
         raise RuntimeError("merge_patches_batch: if_nomatching1_L2 must be a contiguous bool tensor (it is updated in place)")
+    if rows.table is not None:
+        return _merge_patches_ragged(merge_new, rows, trust_score, if_nomatching1_L2, scores_back)
     H, W = int(original_image_shape[0]), int(original_image_shape[1])
     if trust_score.numel() != rows.rows_cap * 144 or if_nomatching1_L2.numel() != rows.rows_cap * 144 or \
             H // 32 != rows.h or W // 32 != rows.w:
@@ -1085,6 +1128,8 @@ def get_result_chunks(rows, if_nomatching16, pts_new, pts16, scales, patch_size=
     if_nomatching16 [rows_cap,2304] from refine_scatter.  No host read.  Returns (matches_l [cap,2], matches_r [cap,2],
     match_row [cap] int32, M [1] int64 device): the first M rows are valid, match_row -> rows.row_cell // N = pair."""
     f16 = _as_flags(if_nomatching16, "if_nomatching16")
+    if rows.table is not None:
+        return _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size)
     z0 = [int(patch_size[0][0]), rows.h, rows.w]
     z1 = [int(v) for v in patch_size[1]]
     n1 = z1[1] * z1[2]
@@ -1125,6 +1170,14 @@ def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None):
         raise RuntimeError("matches_by_pair: pair_off must be a contiguous int64 tensor of %d entries" % n_off)
     nws = _L().pats_matches_by_pair_workspace_bytes(rows.Cmax, rows.pairs)
     ws = _workspace(nws, dev)
+    if rows.table is not None:                  # ragged: the pair of a row is row_pair[row] (there is no global N)
+        # without P the call writes the pairs + 1 offsets only (null status): the buffer above holds no more
+        summary = P is not None
+        _check(_L().pats_matches_by_row_pair_summary_f32(_ptr(matches_l), _ptr(matches_r), _ptr(match_row), _ptr(M), _ptr(rows.row_pair),
+                                                         _ptr(rows.chunk_base), rows.Cmax, rows.pairs, _ptr(ol), _ptr(orr), _ptr(off),
+                                                         _ptr(_dev(P, "P", torch.int64)) if summary else None,
+                                                         _ptr(rows.status) if summary else None, _ptr(ws), nws, _stream()), "matches_by_pair")
+        return (ol, orr, off) if P is None else (ol, orr, off[:rows.pairs + 1], off)
     if P is None:
         _check(_L().pats_matches_by_pair_f32(_ptr(matches_l), _ptr(matches_r), _ptr(match_row), _ptr(M), _ptr(rows.row_cell),
                                              _ptr(rows.chunk_base), rows.Cmax, rows.pairs, rows.h * rows.w, _ptr(ol), _ptr(orr), _ptr(off),
@@ -1135,6 +1188,129 @@ def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None):
                                                  _ptr(off), _ptr(_dev(P, "P", torch.int64)), _ptr(rows.status), _ptr(ws), nws, _stream()),
            "matches_by_pair")
     return ol, orr, off[:rows.pairs + 1], off
+
+
+# ------------------------------------------------------------------------------------------------
+# ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
+# ------------------------------------------------------------------------------------------------
+def chunk_rows_ragged(if_nomatching1, table, if_local=True, Cmax=None, rows_cap=None):
+    """chunk_rows for a ragged batch: if_nomatching1 = the pairs' [N_p] flags packed [sum N] (batch order); each pair is planned on
+    its own grid with the chunk cap of first_layer.py:131-135.  Cmax / rows_cap default to the worst case of the batch."""
+    f = _as_flags(if_nomatching1, "if_nomatching1").reshape(-1)
+    if f.numel() != table.cells:
+        raise RuntimeError("chunk_rows_ragged: if_nomatching1 must hold the %d packed cells of the table" % table.cells)
+    caps = [(2 * w if if_local else 512) for _, w in table.shapes]
+    cm = [max_chunks(h, w, c) for (h, w), c in zip(table.shapes, caps)]
+    r = ChunkRows()
+    r.table, r.pairs, r.h, r.w = table, table.pairs, None, None
+    r.Cmax = max(cm) if Cmax is None else int(Cmax)
+    r.rows_cap = sum(h * w + (c - 1) * w for (h, w), c in zip(table.shapes, cm)) if rows_cap is None else int(rows_cap)
+    dev = f.device
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+    pairs, cells = table.pairs, table.cells
+    r.sum_cycle = torch.empty((cells,), dtype=i32, device=dev)
+    r.cycle_num = torch.empty((pairs,), dtype=i32, device=dev)
+    r.second = torch.empty((pairs, table.hmax + 1, 2), dtype=i64, device=dev)
+    r.third = torch.empty((pairs, table.hmax + 1, 2), dtype=i64, device=dev)
+    r.masks = torch.empty((r.Cmax, cells), dtype=torch.bool, device=dev)
+    r.chunk_base = torch.empty((r.Cmax + 1,), dtype=i64, device=dev)
+    r.crop_base = torch.empty((pairs + 1,), dtype=i64, device=dev)
+    r.row_cell = torch.empty((r.rows_cap,), dtype=i32, device=dev)
+    r._row_pair = torch.empty((r.rows_cap,), dtype=i32, device=dev)
+    r._cell_base = table.cell_base
+    r.row_forced = torch.empty((r.rows_cap,), dtype=u8, device=dev)
+    r.row_crop = torch.empty((r.rows_cap,), dtype=i32, device=dev)
+    r.row_slot = torch.empty((r.Cmax, cells), dtype=i32, device=dev)
+    r.status = torch.empty((1,), dtype=i32, device=dev)
+    nws = _L().pats_chunk_rows_workspace_bytes(pairs, r.Cmax)
+    ws = _workspace(nws, dev)
+    _check(_L().pats_chunk_rows_ragged(table.ref(), _ptr(f), int(bool(if_local)), r.Cmax, r.rows_cap, _ptr(r.sum_cycle),
+                                       _ptr(r.cycle_num), _ptr(r.second), _ptr(r.third), _ptr(r.masks.view(u8)), _ptr(r.chunk_base),
+                                       _ptr(r.crop_base), _ptr(r.row_cell), _ptr(r._row_pair), _ptr(r.row_forced), _ptr(r.row_crop),
+                                       _ptr(r.row_slot), _ptr(r.status), _ptr(ws), nws, _stream()), "chunk_rows_ragged")
+    return r
+
+
+def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_store, right_store, table, margin=128):
+    """Compute_imgs_ex(known_count="device") for a ragged batch: the per-cell inputs packed [sum N] ([sum N, 2] for the point),
+    left_store / right_store the flat HWC stores the table's img_base points into.  Returns (new_left, new_right [sum N,96,96,3],
+    xsn, ysn, avn [sum N,2], bound5 [sum N,5], K_img [pairs], K_total [1]) - device tensors, the first K_total crops valid."""
+    if margin != 128:
+        raise RuntimeError("Compute_imgs_ragged: margin=128 is what the path uses")
+    cells = table.cells
+    xs = _dev(x_scale.float(), "x_scale").reshape(-1)
+    ys = _dev(y_scale.float(), "y_scale").reshape(-1)
+    ap = _dev(average_point.float(), "average_point").reshape(-1)
+    ifn = _as_flags(if_nomatching, "if_nomatching").reshape(-1)
+    if xs.numel() != cells or ys.numel() != cells or ap.numel() != 2 * cells or ifn.numel() != cells:
+        raise RuntimeError("Compute_imgs_ragged: per-cell inputs must hold the %d packed cells of the table" % cells)
+    lf, rt = _dev(left_store, "left_store"), _dev(right_store, "right_store")
+    need = int(table.img_base_host[-1]) + table.shapes[-1][0] * table.shapes[-1][1] * 1024 * 3 if table.pairs else 0
+    if lf.numel() < need or rt.numel() < need:
+        raise RuntimeError("Compute_imgs_ragged: the image stores hold %d / %d floats, the table needs %d" % (lf.numel(), rt.numel(), need))
+    dev = xs.device
+    bound5 = torch.empty((cells, 5), dtype=torch.int64, device=dev)
+    Kd = torch.empty((table.pairs,), dtype=torch.int64, device=dev)
+    Kt = torch.empty((1,), dtype=torch.int64, device=dev)
+    xsn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
+    ysn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
+    avn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
+    _check(_L().pats_compute_imgs_bounds_ragged_f32(table.ref(), _ptr(xs), _ptr(ys), _ptr(ap), _ptr(ifn), _ptr(bound5), _ptr(Kd),
+                                                    _ptr(Kt), _ptr(xsn), _ptr(ysn), _ptr(avn), _stream()), "Compute_imgs_ragged(bounds)")
+    new_left = torch.empty((cells, 96, 96, 3), dtype=torch.float32, device=dev)
+    new_right = torch.empty((cells, 96, 96, 3), dtype=torch.float32, device=dev)
+    _check(_L().pats_left_crops_ragged_f32(table.ref(), _ptr(lf), _ptr(bound5), cells, _ptr(Kt), _ptr(new_left), _stream()),
+           "Compute_imgs_ragged(left)")
+    _check(_L().pats_tensor_resize_hwc_ragged_f32(table.ref(), _ptr(rt), margin, _ptr(bound5), cells, _ptr(Kt), _ptr(new_right), None,
+                                                  _stream()), "Compute_imgs_ragged(right)")
+    return new_left, new_right, xsn, ysn, avn, bound5, Kd, Kt
+
+
+def _merge_patches_ragged(merge_new, rows, trust_score, if_nomatching1_L2, scores_back):
+    table = rows.table
+    if trust_score.numel() != rows.rows_cap * 144 or if_nomatching1_L2.numel() != rows.rows_cap * 144:
+        raise RuntimeError("merge_patches_batch: tensors must be [rows_cap,144]")
+    dev = trust_score.device
+    fresh = scores_back is None
+    if fresh:
+        scores_back = torch.empty((table.cells, 16, 9), dtype=torch.float64, device=dev)            # cleared by the call
+    elif scores_back.dtype != torch.float64 or not scores_back.is_contiguous() or scores_back.numel() != table.cells * 144:
+        raise RuntimeError("merge_patches_batch: scores_back must be a contiguous float64 [sum N, 16, 9] tensor")
+    out = torch.empty((rows.rows_cap, 144), dtype=torch.bool, device=dev)
+    nws = _L().pats_merge_ragged_workspace_bytes(table.cells)
+    ws = _workspace(nws, dev)
+    _check(_L().pats_merge_patches_ragged(table.ref(), 1 if merge_new else 0, rows.Cmax, rows.rows_cap, _ptr(rows.chunk_base),
+                                          _ptr(rows.row_cell), _ptr(rows.row_pair), _ptr(rows.row_slot), _ptr(rows.row_forced),
+                                          _ptr(trust_score), _ptr(if_nomatching1_L2.view(torch.uint8)), _ptr(scores_back), int(fresh),
+                                          _ptr(out.view(torch.uint8)), _ptr(ws), nws, _stream()), "merge_patches_ragged")
+    return out
+
+
+def _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size):
+    table = rows.table
+    z1 = [int(v) for v in patch_size[1]]
+    n1 = z1[1] * z1[2]
+    if int(patch_size[0][0]) != 32:
+        raise RuntimeError("get_result_chunks: the level-0 patch size of the path is 32")
+    if f16.numel() != rows.rows_cap * n1:
+        raise RuntimeError("get_result_chunks: if_nomatching16 must be [rows_cap, %d]" % n1)
+    a0, a1, s0 = _dev(pts_new, "pts_new"), _dev(pts16, "pts16"), _dev(scales, "scales")
+    if a0.numel() != table.cells * 2 or s0.numel() != table.cells * 2 or a1.numel() != rows.rows_cap * n1 * 2:
+        raise RuntimeError("get_result_chunks: pts_new / scales must be [sum N,2], pts16 [rows_cap,%d,2]" % n1)
+    dev = a0.device
+    cap = rows.rows_cap * n1
+    ml = torch.empty((cap, 2), dtype=torch.float32, device=dev)
+    mr = torch.empty((cap, 2), dtype=torch.float32, device=dev)
+    mrow = torch.empty((cap,), dtype=torch.int32, device=dev)
+    cnt = torch.empty((1,), dtype=torch.int64, device=dev)
+    nws = _L().pats_get_result_workspace_bytes(rows.Cmax * table.cells, rows.rows_cap, n1)
+    ws = _workspace(nws, dev)
+    ps1 = (ctypes.c_int * 3)(*z1)
+    _check(_L().pats_get_result_chunks_ragged_f32(table.ref(), rows.Cmax, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
+                                                  _ptr(a0), _ptr(a1), _ptr(s0), ps1, _ptr(_ones(rows.Cmax * rows.pairs, dev)),
+                                                  _ptr(_ones(rows.rows_cap, dev)), _ptr(ml), _ptr(mr), _ptr(mrow), cap, _ptr(cnt),
+                                                  _ptr(ws), nws, _stream()), "get_result_chunks_ragged")
+    return ml, mr, mrow, cnt
 
 
 def masked_stream(cus):
