@@ -43,7 +43,7 @@ const char* pats_version(void);
  * `row_nomatch` to pats_iterative_expand_f32 under the same symbol: a caller built against the older header would pass
  * its stream where the new pointer goes).  A C consumer checks `pats_abi_version() == PATS_ABI_VERSION` once after
  * loading the library; pats_amd/_lib.py does.  New arguments now come with new entry points instead. */
-#define PATS_ABI_VERSION 7
+#define PATS_ABI_VERSION 8
 int pats_abi_version(void);
 const char* pats_last_error(void);
 /* number of HIP devices visible (0 on a CPU-only box; never fails) */
@@ -326,6 +326,24 @@ int pats_third_descriptors_nhwc_f32(const float* feat_f0, const float* feat_f1, 
                                     const float* rubbish, int64_t P_cap, const int64_t* P_dev, int64_t B,
                                     float* out0, float* out1, int64_t* p_s_out, int64_t* p_t_out,
                                     pats_stream_t stream);
+
+/* a15 / a16 on maps of a given element type (ABI 8).  A backbone run in bf16 / fp16 hands over half-precision maps; the
+ * kernels widen every element to fp32 EXACTLY at the load and compute everything after it as the fp32 kernels do, in the
+ * same order: desc / out0 / out1 / p_s_out / p_t_out are bit-identical to the fp32 entry points' outputs on the widened maps,
+ * and stay float32.  feat* point to `dtype` elements in NCHW (channels_last == 0) or channels-last memory order, shapes as
+ * above; title, rubbish, kenc, the points and the outputs are float32 / int64 as for the _f32 entry points.  B_dev / P_dev
+ * may be NULL (then B_cap / P_cap rows exist); with a count, rows past it are left untouched.  PATS_MAP_F32 dispatches to
+ * the fp32 kernels.  Refused before any launch (PATS_ERR_INVALID): an unknown dtype, a NULL pointer, and maps not aligned
+ * to the kernels' loads - 4 bytes for NCHW maps, 16 bytes for channels-last half maps and for the fine gather's
+ * channels-last maps and desc (channels-last fp32 third-level maps: 4 bytes). */
+typedef enum { PATS_MAP_F32 = 0, PATS_MAP_F16 = 1, PATS_MAP_BF16 = 2 } pats_map_dtype_t;
+int pats_fine_descriptors_typed(const void* feat0, const void* feat1, const void* feat2, pats_map_dtype_t dtype,
+                                int channels_last, const float* title, const float* rubbish, int64_t B_cap,
+                                const int64_t* B_dev, float* desc, pats_stream_t stream);
+int pats_third_descriptors_typed(const void* feat_f0, const void* feat_f1, pats_map_dtype_t dtype, int channels_last,
+                                 const float* mkpts0_c, const float* mkpts1_c, const int64_t* b_ids, const float* kenc,
+                                 const float* rubbish, int64_t P_cap, const int64_t* P_dev, int64_t B, float* out0,
+                                 float* out1, int64_t* p_s_out, int64_t* p_t_out, pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The steps either side of the OT path.  bool tensors are 1 byte, 0 / 1.

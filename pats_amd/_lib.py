@@ -17,7 +17,7 @@ if os.environ.get("PATS_AMD_DIAG_LIB", "") not in ("", "0"):
 c_void_p, c_int, c_i64, c_f, c_size = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
                                        ctypes.c_size_t)
 
-ABI_VERSION = 7      # include/pats_amd.h PATS_ABI_VERSION
+ABI_VERSION = 8      # include/pats_amd.h PATS_ABI_VERSION
 
 
 
@@ -107,6 +107,10 @@ SIGNATURES = {
     "pats_fine_descriptors_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "pats_third_descriptors_nhwc_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pats_fine_descriptors_typed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p,
+                                            c_void_p, c_void_p]),
+    "pats_third_descriptors_typed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pats_third_level_counted_f32": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),

@@ -24,7 +24,8 @@ the caller when it fetches the matches.  Rows of the table that no chunk uses (p
 a network callback may do the same with ops.fine_descriptors(count=...)) and are "no match" at the merge; rows that are left
 without a cell are not compacted (pats.py:40-52) - they emit nothing, exactly as in pipeline.forward_path.
 
-Network callbacks (`nets`, the out-of-scope backbones + heads; GPU float32 tensors, no host read required of them):
+Network callbacks (`nets`, the out-of-scope backbones + heads; they return GPU float32 tensors, no host read required of them -
+the backbone maps they gather from with ops.fine_descriptors / ops.third_descriptors may be float16 / bfloat16):
   nets.coarse(lefts, rights) -> mdesc0 [pairs,D,N], mdesc1 [pairs,D,N], scale [pairs,1,N], alpha
   nets.fine(rows, new_left, new_right) -> mdesc0 [rows_cap,264,145], mdesc1, scale_x [rows_cap,1,144], scale_y
       [, scale_x * scale_y] (what ops.scale_head hands out; formed here if absent)

@@ -357,6 +357,335 @@ fine_desc_nhwc_kernel(const float* __restrict__ f0, const float* __restrict__ f1
     fine_tile_pass<1, POL>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
 }
 
+// ---- the same four gathers on HALF-PRECISION maps (float16 / bfloat16) ---------------------------------------------------
+// A backbone run in bf16 / fp16 hands over maps of 2-byte elements.  Each element is widened to fp32 EXACTLY at the load
+// (every f16 / bf16 value, subnormals, infinities and NaNs included, is a float); from there on every output element is
+// formed by the fp32 kernels' operations in their order - the AvgPool2d(2,1,1) sum (((a + b) + c) + d) / 4, the kenc add,
+// the dustbin column - so the outputs are the fp32 kernels' outputs on maps.float(), bit for bit, and stay float32.  Only
+// the access shapes change with the element size: map 0's pooled taps become 4-byte pairs at 2-byte alignment, a
+// third-level window row becomes 16 contiguous bytes (4 lanes x 2 cells instead of 8 lanes x 1 cell), and a 16-byte load of
+// a channels-last pixel carries 8 channels instead of 4 (new lane -> (node, channel) maps, still whole lines per load).
+// DT = PATS_MAP_F16 or PATS_MAP_BF16 (include/pats_amd.h); maps 4-byte aligned (NCHW) / 16-byte aligned (channels-last).
+template <int DT>
+__device__ __forceinline__ float widen(uint32_t h) {          // the low 16 bits of h
+    if (DT == PATS_MAP_BF16) return __uint_as_float(h << 16);
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
+}
+template <int DT>
+__device__ __forceinline__ float widen_hi(uint32_t h) {       // the high 16 bits of h
+    if (DT == PATS_MAP_BF16) return __uint_as_float(h & 0xffff0000u);
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(h >> 16));
+}
+// two neighbouring halves as ONE 4-byte access at 2-byte alignment (map 0's pooled taps start at an odd element)
+typedef uint32_t u32u __attribute__((aligned(2)));
+template <int POL>
+__device__ __forceinline__ uint32_t ldh2(const uint16_t* p) {
+    const u32u* q = reinterpret_cast<const u32u*>(p);
+    if (POL & 1) return __builtin_nontemporal_load(q);
+    return *q;
+}
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef float f2s __attribute__((ext_vector_type(2), aligned(4)));
+template <int POL>
+__device__ __forceinline__ void stm2(float* p, f2s v) {      // two neighbouring floats as ONE 8-byte store at 4-byte alignment
+    f2s* q = reinterpret_cast<f2s*>(p);
+    if (POL & 2) __builtin_nontemporal_store(v, q);
+    else *q = v;
+}
+
+// fine level, NCHW: fine_desc_kernel's lane -> point map and channel loops; the taps of a pooled sample are two 4-byte pairs
+template <int DT, int POL>
+__global__ void __launch_bounds__(256)
+fine_desc_half_kernel(const uint16_t* __restrict__ f0, const uint16_t* __restrict__ f1,
+                      const uint16_t* __restrict__ f2, const float* __restrict__ title,
+                      const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
+                      const int64_t* __restrict__ B_live) {
+    const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
+    const int64_t b = n % B;
+    if (B_live && b >= *B_live) return;        // counted launch: rows past the device-side total are padding
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* o = desc + n * 264 * 145;
+    int pt[3], off0[3], off1[3];
+    bool live[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+        const int p = lane + 64 * g;
+        live[g] = p < 145;
+        pt[g] = p < 144 ? p : 0;                               // positions (k // 12, k % 12); the dustbin column reads nothing
+        const int r = pt[g] / 12, c = pt[g] - r * 12;
+        off0[g] = (4 * r + 1) * 48 + 4 * c + 1;                // map 0: avgpool(2,1,1) -> 49x49, sample (4r+2, 4c+2)   :73-79
+        off1[g] = (2 * r) * 24 + 2 * c;                        // map 1: avgpool -> 25x25, sample (2r+1, 2c+1)
+    }
+    const bool dust = lane == 16;                              // group 2 of lane 16 is point 144: the dustbin feature column
+    auto put = [&](int ch, float v0, float v1, float v2) {
+        float* row = o + ch * 145;
+        stm<POL>(row + lane, v0);
+        stm<POL>(row + lane + 64, v1);
+        if (live[2]) stm<POL>(row + lane + 128, dust ? rubbish[b * 264 + ch] : v2);           // second_layer.py:83,85
+    };
+    auto pool = [](uint32_t a, uint32_t c2) {
+        return (((widen<DT>(a) + widen_hi<DT>(a)) + widen<DT>(c2)) + widen_hi<DT>(c2)) / 4.0f;
+    };
+    for (int ch = wave; ch < 8; ch += 4) {                     // the 8-channel "title"                         :82,84
+        const float v = title[b * 8 + ch];
+        put(ch, v, v, v);
+    }
+#pragma unroll 2
+    for (int ch = 8 + wave; ch < 72; ch += 4) {                // map 0: [.,64,48,48]
+        const uint16_t* m = f0 + (n * 64 + (ch - 8)) * 48 * 48;
+        float v[3];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) v[g] = pool(ldh2<POL>(m + off0[g]), ldh2<POL>(m + off0[g] + 48));
+        put(ch, v[0], v[1], v[2]);
+    }
+#pragma unroll 2
+    for (int ch = 72 + wave; ch < 136; ch += 4) {              // map 1: [.,64,24,24]
+        const uint16_t* m = f1 + (n * 64 + (ch - 72)) * 24 * 24;
+        float v[3];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) v[g] = pool(ldh2<POL>(m + off1[g]), ldh2<POL>(m + off1[g] + 24));
+        put(ch, v[0], v[1], v[2]);
+    }
+#pragma unroll 4
+    for (int ch = 136 + wave; ch < 264; ch += 4) {             // map 2: [.,128,12,12], no pooling, sample (r, c)
+        const uint16_t* m = f2 + (n * 128 + (ch - 136)) * 144;
+        put(ch, widen<DT>(ldm<POL>(m + pt[0])), widen<DT>(ldm<POL>(m + pt[1])), widen<DT>(ldm<POL>(m + pt[2])));
+    }
+}
+
+// The third-level index arithmetic of third_desc_kernel / third_desc_nhwc_kernel for point p (third_layer.py:124-133,
+// 141-144): the rounded points (written by thread 0 when side 0), the NHWC-view row of window cell (0, 0) of each side, and
+// the dustbin feature's (image, cell).
+struct third_point {
+    long long i00[2], bb2, i2;
+};
+__device__ __forceinline__ third_point third_point_at(const float* __restrict__ mk0, const float* __restrict__ mk1,
+                                                      int64_t p, int64_t b, int64_t B, bool write,
+                                                      int64_t* __restrict__ ps_out, int64_t* __restrict__ pt_out) {
+    constexpr int W = 8, M = 52;
+    const long long s0 = round_half_even_div(mk0[p * 2 + 0], 4.0f) * 4, s1 = round_half_even_div(mk0[p * 2 + 1], 4.0f) * 4;   // :124
+    float t0 = mk1[p * 2 + 0], t1 = mk1[p * 2 + 1];                                                                          // :128-130
+    t0 = t0 >= 96.f ? 96.f : t0; t1 = t1 >= 96.f ? 96.f : t1;
+    t0 = t0 <= 0.f ? 0.f : t0;   t1 = t1 <= 0.f ? 0.f : t1;
+    const long long q0 = round_half_even_div(t0, 4.0f) * 4, q1 = round_half_even_div(t1, 4.0f) * 4;
+    if (write) {
+        if (ps_out) { ps_out[p * 2] = s0; ps_out[p * 2 + 1] = s1; }
+        if (pt_out) { pt_out[p * 2] = q0; pt_out[p * 2 + 1] = q1; }
+    }
+    auto fdiv2 = [](long long v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };      // python floor division
+    third_point r;
+    r.i00[0] = b * M * M + (fdiv2(s1) - W / 2 + 2) * M + (fdiv2(s0) - W / 2 + 2);     // :125-127,131-133
+    r.i00[1] = b * M * M + (fdiv2(q1) - W / 2 + 2) * M + (fdiv2(q0) - W / 2 + 2);
+    long long i2 = b * 144 + round_half_even_div((float)s1, 8.0f) * 12 + round_half_even_div((float)s0, 8.0f);
+    i2 = i2 < 0 ? 0 : (i2 > B * 144 - 1 ? B * 144 - 1 : i2);      // a row of the flattened [B*144, 128] view, see third_desc_kernel
+    r.bb2 = i2 / 144;
+    r.i2 = i2 - r.bb2 * 144;
+    return r;
+}
+
+// third level, NCHW: a window row of 8 cells is 16 contiguous bytes of a map row, so a lane takes TWO neighbouring cells as
+// one 4-byte pair - lanes 0..31 one channel's 8x8 window, lanes 32..63 the next channel's - and stores them as one 8-byte
+// write.  A pair starts at an even row i of the NHWC view (s0, q0 are multiples of 4, M is even), so it never straddles two
+// images, and the clamp of third_desc_kernel treats both cells alike: a pair below row 0 reads row 0 twice, one past the
+// last row reads the last row twice.  Wave w handles channels 32w .. 32w+31, sixteen at a time (eight pairs per side in
+// flight, then sixteen stores); XCD-aware order and the dustbin column as in third_desc_kernel.
+template <int DT, int POL>
+__global__ void __launch_bounds__(256)
+third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restrict__ ff1,
+                       const float* __restrict__ mk0, const float* __restrict__ mk1,
+                       const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
+                       const float* __restrict__ rubbish, int64_t P, int64_t B,
+                       float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                       int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
+    constexpr int M = 52, C = 128;
+    int64_t live = P;
+    if (P_dev) { const int64_t n = *P_dev; live = n < P ? n : P; }
+    const int64_t per = (live + 7) >> 3, p = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if ((int64_t)(blockIdx.x >> 3) >= per || p >= live) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cp = lane & 31, sub = lane >> 5;                 // cells 2 cp, 2 cp + 1 (row cp / 4) of channel c0 + 2 k + sub
+    const int64_t b = b_ids[p];
+    const third_point tp = third_point_at(mk0, mk1, p, b, B, threadIdx.x == 0, ps_out, pt_out);
+    const long long lim = B * M * M - 1;
+    const uint16_t* src[2];
+    bool below[2], above[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const long long i = tp.i00[s] + (cp >> 2) * M + 2 * (cp & 3);
+        below[s] = i < 0;
+        above[s] = i > lim;
+        const long long j = below[s] ? 0 : (above[s] ? lim - 1 : i);
+        const long long bb = j / (M * M);
+        src[s] = (s ? ff1 : ff0) + bb * C * (M * M) + (j - bb * (M * M));
+    }
+    auto fix = [](uint32_t u, bool lo, bool hi) {              // a clamped pair: both cells read the one row it clamps to
+        u = lo ? (u & 0xffffu) * 0x10001u : u;
+        return hi ? (u >> 16) * 0x10001u : u;
+    };
+    float* o0 = out0 + p * C * 65 + 2 * cp;
+    float* o1 = out1 + p * C * 65 + 2 * cp;
+#pragma unroll 1
+    for (int c0 = 32 * wave + sub; c0 < 32 * wave + 32; c0 += 16) {
+        uint32_t a[8], c[8];
+        f2s ke[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            a[k] = ldm<POL>(reinterpret_cast<const uint32_t*>(src[0] + (int64_t)(c0 + 2 * k) * (M * M)));
+            c[k] = ldm<POL>(reinterpret_cast<const uint32_t*>(src[1] + (int64_t)(c0 + 2 * k) * (M * M)));
+            ke[k] = *reinterpret_cast<const f2s*>(kenc + (c0 + 2 * k) * 64 + 2 * cp);        // + self.kenc(kpts)   :139-140
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t u = fix(a[k], below[0], above[0]), v = fix(c[k], below[1], above[1]);
+            f2s x, y;
+            x.x = widen<DT>(u) + ke[k].x; x.y = widen_hi<DT>(u) + ke[k].y;
+            y.x = widen<DT>(v) + ke[k].x; y.y = widen_hi<DT>(v) + ke[k].y;
+            stm2<POL>(o0 + (c0 + 2 * k) * 65, x);
+            stm2<POL>(o1 + (c0 + 2 * k) * 65, y);
+        }
+    }
+    if (lane < 32) {
+        const int ch = 32 * wave + lane;
+        const float rb = rubbish[(tp.bb2 * C + ch) * 144 + tp.i2];
+        out0[p * C * 65 + ch * 65 + 64] = rb;                                     // :145-146
+        out1[p * C * 65 + ch * 65 + 64] = rb;
+    }
+}
+
+// third level, channels-last: one workgroup per (point, side) as third_desc_nhwc_kernel.  A pixel's 128 channels are 256
+// bytes = 16 lanes x 16 bytes; lane l of wave w loads channels 8 (l / 4) .. +7 of window cells 16 j + 4 w + l % 4 (j < 4):
+// each load instruction reads four whole pixels, and the LDS writes of a half-wave hit 16 banks twice at most.
+template <int DT, int POL>
+__global__ void __launch_bounds__(256)
+third_desc_nhwc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restrict__ ff1,
+                            const float* __restrict__ mk0, const float* __restrict__ mk1,
+                            const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
+                            const float* __restrict__ rubbish, int64_t P, int64_t B,
+                            float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                            int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
+    constexpr int M = 52, C = 128, NT = 65;
+    __shared__ __attribute__((aligned(16))) float tile[C * NT];
+    int64_t live = P;
+    if (P_dev) { const int64_t n = *P_dev; live = n < P ? n : P; }
+    const unsigned k = blockIdx.x >> 3;
+    const int side = k & 1;
+    const int64_t per = (live + 7) >> 3, p = (int64_t)(blockIdx.x & 7) * per + (k >> 1);
+    if ((int64_t)(k >> 1) >= per || p >= live) return;
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int64_t b = b_ids[p];
+    const third_point tp = third_point_at(mk0, mk1, p, b, B, t == 0 && side == 0, ps_out, pt_out);
+    const long long lim = B * M * M - 1;
+    const uint16_t* __restrict__ ff = side ? ff1 : ff0;
+    float rb = 0.f;
+    if (t < C) rb = rubbish[(tp.bb2 * C + t) * 144 + tp.i2];
+    const int cg = lane >> 2;
+    u4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int cell = 16 * j + 4 * wave + (lane & 3);
+        long long i = (side ? tp.i00[1] : tp.i00[0]) + (cell >> 3) * M + (cell & 7);
+        i = i < 0 ? 0 : (i > lim ? lim : i);          // memory safety (torch.gather would raise out of range)
+        v[j] = ldm<POL>(reinterpret_cast<const u4*>(ff + i * C + 8 * cg));
+    }
+    float ke[33];                                     // + self.kenc(kpts) rides on the way out, as in third_desc_nhwc_kernel
+#pragma unroll
+    for (int r = 0; r < 33; ++r) {
+        const int e = t + 256 * r, c = e / NT, n = e - c * NT;
+        ke[r] = kenc[(e < C * NT && n < 64) ? c * 64 + n : 0];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int cell = 16 * j + 4 * wave + (lane & 3);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            tile[(8 * cg + 2 * h) * NT + cell] = widen<DT>(v[j][h]);
+            tile[(8 * cg + 2 * h + 1) * NT + cell] = widen_hi<DT>(v[j][h]);
+        }
+    }
+    if (t < C) tile[t * NT + 64] = rb;                                                                      // :145-146
+    wg_barrier();
+    float* o = (side ? out1 : out0) + p * C * NT;
+#pragma unroll
+    for (int r = 0; r < 33; ++r) {
+        const int e = t + 256 * r, c = e / NT, n = e - c * NT;
+        if (e < C * NT) stm<POL>(o + e, n < 64 ? tile[e] + ke[r] : tile[e]);
+    }
+}
+
+// fine level, channels-last: the four 64-channel tiles of fine_desc_nhwc_kernel.  64 half channels of a pixel are 128 bytes
+// = 8 lanes x 16 bytes: lane = (node % 8, eight channels), a wave takes 8 nodes, the workgroup 32 per group, 4.5 groups of
+// the 144 nodes (waves 2 and 3 sit out the last one).  Every load instruction reads 8 whole 128-byte lines.
+template <int DT, int TAPS, int POL>
+__device__ __forceinline__ void fine_tile_pass_half(const uint16_t* __restrict__ img, int cpp, int ch0, int rowpix, int step,
+                                                    int first, float* tile, float* __restrict__ o,
+                                                    const float* __restrict__ rub, int t) {
+    constexpr int NP = 145;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const int lane = t & 63, wave = t >> 6, cg = lane & 7, sub = lane >> 3;
+    float dust = 0.f;
+    if (t < 64) dust = rub[t];                                                                   // second_layer.py:83,85
+    u4 q[5][TAPS];
+#pragma unroll
+    for (int g = 0; g < 5; ++g) {
+        const int nd = 32 * g + 8 * wave + sub, r = nd / 12, c = nd - 12 * r;                   // positions (k // 12, k % 12)
+        if (g < 4 || wave < 2) {
+            const uint16_t* px = img + ((step * r + first) * rowpix + step * c + first) * cpp + ch0 + 8 * cg;
+#pragma unroll
+            for (int tap = 0; tap < TAPS; ++tap)
+                q[g][tap] = ldm<POL>(reinterpret_cast<const u4*>(px + ((tap >> 1) * rowpix + (tap & 1)) * cpp));
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 5; ++g) {
+        const int nd = 32 * g + 8 * wave + sub;
+        if (g < 4 || wave < 2) {
+#pragma unroll
+            for (int h = 0; h < 8; ++h) {
+                float v;
+                if (TAPS == 4) {                                                                 // AvgPool2d(2, 1, 1)  :73-79
+                    float x[4];
+#pragma unroll
+                    for (int tap = 0; tap < 4; ++tap) x[tap] = h & 1 ? widen_hi<DT>(q[g][tap][h >> 1]) : widen<DT>(q[g][tap][h >> 1]);
+                    v = (((x[0] + x[1]) + x[2]) + x[3]) / 4.0f;
+                } else {
+                    v = h & 1 ? widen_hi<DT>(q[g][0][h >> 1]) : widen<DT>(q[g][0][h >> 1]);
+                }
+                tile[(8 * cg + h) * NP + nd] = v;
+            }
+        }
+    }
+    if (t < 64) tile[t * NP + 144] = dust;
+    wg_barrier();
+    const f4* src = reinterpret_cast<const f4*>(tile);
+    f4* dst = reinterpret_cast<f4*>(o);
+    for (int e = t; e < 64 * NP / 4; e += 256) stm<POL>(dst + e, src[e]);
+    wg_barrier();
+}
+
+template <int DT, int POL>
+__global__ void __launch_bounds__(256)
+fine_desc_nhwc_half_kernel(const uint16_t* __restrict__ f0, const uint16_t* __restrict__ f1,
+                           const uint16_t* __restrict__ f2, const float* __restrict__ title,
+                           const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
+                           const int64_t* __restrict__ B_live) {
+    constexpr int NP = 145;
+    __shared__ __attribute__((aligned(16))) float tile[64 * NP];
+    const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
+    const int64_t b = n % B;
+    if (B_live && b >= *B_live) return;        // counted launch: rows past the device-side total are padding
+    const int t = threadIdx.x;
+    float* o = desc + n * 264 * NP;
+    const float* rub = rubbish + b * 264;
+    for (int e = t; e < 8 * NP; e += 256) {                    // the 8-channel "title"                         :82,84
+        const int ch = e / NP, p = e - ch * NP;
+        o[e] = p == 144 ? rub[ch] : title[b * 8 + ch];
+    }
+    fine_tile_pass_half<DT, 4, POL>(f0 + n * 48 * 48 * 64, 64, 0, 48, 4, 1, tile, o + 8 * NP, rub + 8, t);      // map 0
+    fine_tile_pass_half<DT, 4, POL>(f1 + n * 24 * 24 * 64, 64, 0, 24, 2, 0, tile, o + 72 * NP, rub + 72, t);    // map 1
+    fine_tile_pass_half<DT, 1, POL>(f2 + n * 144 * 128, 128, 0, 12, 1, 0, tile, o + 136 * NP, rub + 136, t);    // map 2
+    fine_tile_pass_half<DT, 1, POL>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
+}
+
 // PATS_GATHER_NT = 0..3 (see ldm / stm above), read once per process; without it 0 on NCHW maps, 3 on channels-last maps
 static int gather_policy(bool channels_last) {
     static const int pol = [] { const char* e = env_switch("PATS_GATHER_NT"); return e ? (atoi(e) & 3) : -1; }();
@@ -369,6 +698,17 @@ static int gather_policy(bool channels_last) {
         case 2: hipLaunchKernelGGL((KERNEL<2>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                  \
         default: hipLaunchKernelGGL((KERNEL<3>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                 \
     }
+// the half-map kernels, instantiated for f16 and bf16 under the same policies and defaults
+#define GATHER_LAUNCH_HALF(KERNEL, DT, NHWC, grid, ...)                                                                       \
+    switch (gather_policy(NHWC)) {                                                                                           \
+        case 0: hipLaunchKernelGGL((KERNEL<DT, 0>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;              \
+        case 1: hipLaunchKernelGGL((KERNEL<DT, 1>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;              \
+        case 2: hipLaunchKernelGGL((KERNEL<DT, 2>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;              \
+        default: hipLaunchKernelGGL((KERNEL<DT, 3>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;             \
+    }
+#define GATHER_LAUNCH_TYPED(KERNEL, DTYPE, NHWC, grid, ...)                                                                   \
+    if ((DTYPE) == PATS_MAP_F16) { GATHER_LAUNCH_HALF(KERNEL, PATS_MAP_F16, NHWC, grid, __VA_ARGS__) }                        \
+    else { GATHER_LAUNCH_HALF(KERNEL, PATS_MAP_BF16, NHWC, grid, __VA_ARGS__) }
 
 }  // namespace pats
 
@@ -458,4 +798,79 @@ extern "C" int pats_third_descriptors_nhwc_f32(const float* feat_f0, const float
     GATHER_LAUNCH(third_desc_nhwc_kernel, true, dim3((unsigned)((P_cap + 7) / 8 * 16)), feat_f0,
                        feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
     return check_launch("third_desc_nhwc_kernel");
+}
+
+
+// a15 / a16 on maps of any pats_map_dtype_t, either memory format, with or without the device-side count.  F32 takes the
+// kernels above (the launches of pats_fine_descriptors_*_f32 / pats_third_descriptors_*_f32); F16 / BF16 their half-map twins.
+// Every refusal comes before any launch.
+extern "C" int pats_fine_descriptors_typed(const void* feat0, const void* feat1, const void* feat2, pats_map_dtype_t dtype,
+                                           int channels_last, const float* title, const float* rubbish, int64_t B_cap,
+                                           const int64_t* B_dev, float* desc, pats_stream_t stream) {
+    PATS_REQUIRE(dtype == PATS_MAP_F32 || dtype == PATS_MAP_F16 || dtype == PATS_MAP_BF16,
+                 "fine_descriptors_typed: unknown map dtype %d", (int)dtype);
+    PATS_REQUIRE(B_cap >= 0, "fine_descriptors_typed: bad shape");
+    if (B_cap == 0) return PATS_OK;
+    PATS_REQUIRE(feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors_typed: null pointer");
+    const uintptr_t maps = (uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)feat2;
+    if (channels_last)      // 16-byte map loads, 16-byte stores of desc
+        PATS_REQUIRE((maps | (uintptr_t)desc) % 16 == 0, "fine_descriptors_typed: channels-last maps and desc must be 16-byte aligned");
+    else                    // 4-byte pair / float loads (f32: 8-byte pairs at 4-byte alignment)
+        PATS_REQUIRE(maps % 4 == 0, "fine_descriptors_typed: NCHW maps must be 4-byte aligned");
+    const dim3 grid((unsigned)(2 * B_cap));
+    if (dtype == PATS_MAP_F32) {
+        const float *f0 = (const float*)feat0, *f1 = (const float*)feat1, *f2 = (const float*)feat2;
+        if (channels_last) {
+            GATHER_LAUNCH(fine_desc_nhwc_kernel, true, grid, f0, f1, f2, title, rubbish, B_cap, desc, B_dev);
+            return check_launch("fine_desc_nhwc_kernel");
+        }
+        GATHER_LAUNCH(fine_desc_kernel, false, grid, f0, f1, f2, title, rubbish, B_cap, desc, B_dev);
+        return check_launch("fine_desc_kernel");
+    }
+    const uint16_t *h0 = (const uint16_t*)feat0, *h1 = (const uint16_t*)feat1, *h2 = (const uint16_t*)feat2;
+    if (channels_last) {
+        GATHER_LAUNCH_TYPED(fine_desc_nhwc_half_kernel, dtype, true, grid, h0, h1, h2, title, rubbish, B_cap, desc, B_dev);
+        return check_launch("fine_desc_nhwc_half_kernel");
+    }
+    GATHER_LAUNCH_TYPED(fine_desc_half_kernel, dtype, false, grid, h0, h1, h2, title, rubbish, B_cap, desc, B_dev);
+    return check_launch("fine_desc_half_kernel");
+}
+
+extern "C" int pats_third_descriptors_typed(const void* feat_f0, const void* feat_f1, pats_map_dtype_t dtype, int channels_last,
+                                            const float* mkpts0_c, const float* mkpts1_c, const int64_t* b_ids,
+                                            const float* kenc, const float* rubbish, int64_t P_cap, const int64_t* P_dev,
+                                            int64_t B, float* out0, float* out1, int64_t* p_s_out, int64_t* p_t_out,
+                                            pats_stream_t stream) {
+    PATS_REQUIRE(dtype == PATS_MAP_F32 || dtype == PATS_MAP_F16 || dtype == PATS_MAP_BF16,
+                 "third_descriptors_typed: unknown map dtype %d", (int)dtype);
+    PATS_REQUIRE(P_cap >= 0 && B > 0, "third_descriptors_typed: bad shape");
+    if (P_cap == 0) return PATS_OK;
+    PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
+                 "third_descriptors_typed: null pointer");
+    const uintptr_t maps = (uintptr_t)feat_f0 | (uintptr_t)feat_f1;
+    if (channels_last)      // 16-byte loads of half pixels (f32: 4-byte loads, aligned as the NCHW rule)
+        PATS_REQUIRE(maps % (dtype == PATS_MAP_F32 ? 4 : 16) == 0, "third_descriptors_typed: channels-last maps must be %d-byte aligned",
+                     dtype == PATS_MAP_F32 ? 4 : 16);
+    else                    // 4-byte float / cell-pair loads
+        PATS_REQUIRE(maps % 4 == 0, "third_descriptors_typed: NCHW maps must be 4-byte aligned");
+    if (dtype == PATS_MAP_F32) {
+        const float *f0 = (const float*)feat_f0, *f1 = (const float*)feat_f1;
+        if (channels_last) {
+            GATHER_LAUNCH(third_desc_nhwc_kernel, true, dim3((unsigned)((P_cap + 7) / 8 * 16)), f0, f1, mkpts0_c, mkpts1_c, b_ids,
+                          kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+            return check_launch("third_desc_nhwc_kernel");
+        }
+        GATHER_LAUNCH(third_desc_kernel, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), f0, f1, mkpts0_c, mkpts1_c, b_ids,
+                      kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+        return check_launch("third_desc_kernel");
+    }
+    const uint16_t *h0 = (const uint16_t*)feat_f0, *h1 = (const uint16_t*)feat_f1;
+    if (channels_last) {
+        GATHER_LAUNCH_TYPED(third_desc_nhwc_half_kernel, dtype, true, dim3((unsigned)((P_cap + 7) / 8 * 16)), h0, h1, mkpts0_c,
+                            mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+        return check_launch("third_desc_nhwc_half_kernel");
+    }
+    GATHER_LAUNCH_TYPED(third_desc_half_kernel, dtype, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), h0, h1, mkpts0_c, mkpts1_c,
+                        b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+    return check_launch("third_desc_half_kernel");
 }

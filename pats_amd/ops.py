@@ -65,6 +65,36 @@ def _map(t, name, dtype=torch.float32):
     return t.contiguous(), False
 
 
+# element types the descriptor gathers take their maps in (include/pats_amd.h pats_map_dtype_t)
+_MAP_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _maps_any(tensors, names):
+    """The maps of ONE gather call in float32, float16 or bfloat16 -> (maps as _map returns them, pats_map_dtype_t code, or
+    None when they are float32 and the _f32 entry points take them exactly as before).  Half maps are widened to fp32 exactly
+    in the kernels; the cases those kernels do not take fall back to .float() copies, which give the same bits: maps of
+    different dtypes in one call, mixed memory formats, and data pointers off the kernels' alignment (4 bytes NCHW,
+    16 bytes channels-last)."""
+    for t, name in zip(tensors, names):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype not in _MAP_DTYPES:
+            raise RuntimeError("pats_amd: %s must be float32, float16 or bfloat16, got %s" % (name, t.dtype))
+    dtypes = {t.dtype for t in tensors}
+    if dtypes == {torch.float32}:
+        return [_map(t, n) for t, n in zip(tensors, names)], None
+    if len(dtypes) != 1:
+        return [_map(t.float(), n) for t, n in zip(tensors, names)], None
+    dt = tensors[0].dtype
+    maps = [_map(t, n, dt) for t, n in zip(tensors, names)]
+    if len({cl for _, cl in maps}) != 1:
+        maps = [(t.contiguous(), False) for t, _ in maps]
+    align = 16 if maps[0][1] else 4
+    if any(t.data_ptr() % align for t, _ in maps):
+        return [_map(t.float(), n) for t, n in zip(tensors, names)], None
+    return maps, _MAP_DTYPES[dt]
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -660,12 +690,19 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
     return (m0, m1, label, ifm.bool(), Z) if return_plan else (m0, m1, label, ifm.bool())
 
 
+def _widen(t):
+    """title / rubbish / kenc in half precision: small, widened here (exactly) to the float32 the kernels read."""
+    return t.float() if isinstance(t, torch.Tensor) and t.dtype in (torch.float16, torch.bfloat16) else t
+
+
 def fine_descriptors(desc0_, title, rubbish, out=None, count=None):
     """second_layer.py:71-86: desc0_ = the three maps of ResNet2.forward2 on the stacked crops
     ([2B,64,48,48], [2B,64,24,24], [2B,128,12,12]); title [B,8] = compress_1(desc_l); rubbish [B,264]
     = compress_2(desc_l).  Returns desc [2,B,264,145] (desc[0], desc[1] feed the GNN).
-    Maps in torch.channels_last memory format (all three) take the channels-last gather: same bits, 0.67x the HBM bytes."""
-    maps = [_map(t, "desc0_[%d]" % i) for i, t in enumerate(desc0_)]
+    Maps in torch.channels_last memory format (all three) take the channels-last gather: same bits, 0.67x the HBM bytes.
+    Maps in float16 / bfloat16 are widened to fp32 exactly in the kernel: desc is float32 and bit-identical to the call on
+    [m.float() for m in desc0_]; title / rubbish may be half too (widened here)."""
+    maps, dtype = _maps_any(list(desc0_), ["desc0_[%d]" % i for i in range(len(desc0_))])
     if len({cl for _, cl in maps}) != 1:       # mixed formats: fall back to the NCHW kernel on contiguous copies
         maps = [(t.contiguous(), False) for t, _ in maps]
     (f0, nhwc), (f1, _), (f2, _) = maps
@@ -673,11 +710,16 @@ def fine_descriptors(desc0_, title, rubbish, out=None, count=None):
     if tuple(f0.shape[1:]) != (64, 48, 48) or tuple(f1.shape) != (2 * B, 64, 24, 24) or \
             tuple(f2.shape) != (2 * B, 128, 12, 12):
         raise RuntimeError("fine_descriptors: unexpected feature-map shapes")
-    ti = _dev(title, "title").reshape(B, 8)
-    ru = _dev(rubbish, "rubbish").reshape(B, 264)
+    ti = _dev(_widen(title), "title").reshape(B, 8)
+    ru = _dev(_widen(rubbish), "rubbish").reshape(B, 264)
     desc = torch.empty((2, B, 264, 145), dtype=torch.float32, device=f0.device) if out is None else _dev(out, "out")
     if tuple(desc.shape) != (2, B, 264, 145) or (out is not None and desc.data_ptr() != out.data_ptr()):
         raise RuntimeError("fine_descriptors: out must be a contiguous [2,B,264,145] tensor")
+    if dtype is not None:
+        cnt = _dev(count, "count", torch.int64) if count is not None else None
+        _check(_L().pats_fine_descriptors_typed(_ptr(f0), _ptr(f1), _ptr(f2), dtype, int(bool(nhwc)), _ptr(ti), _ptr(ru), B,
+                                                _ptr(cnt), _ptr(desc), _stream()), "fine_descriptors")
+        return desc
     if count is not None:      # device-side row count: the tensors are a capacity (throughput mode)
         _check(_L().pats_fine_descriptors_counted_f32(_ptr(f0), _ptr(f1), _ptr(f2), _ptr(ti), _ptr(ru), B,
                                                       _ptr(_dev(count, "count", torch.int64)), int(bool(nhwc)), _ptr(desc),
@@ -693,8 +735,10 @@ def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish
     mkpts1_c [P,2] int64 rounded to the 4-px lattice as the reference reassigns them).
     count: DEVICE int64 [1], the number of points that exist (the tensors are a capacity; rows past it are not written);
     out: optional (o0, o1) to write into.
-    Maps in torch.channels_last memory format take the channels-last gather: same bits, under half the HBM bytes."""
-    (f0, nhwc), (f1, nhwc1) = _map(feat_f0, "feat_f0"), _map(feat_f1, "feat_f1")
+    Maps in torch.channels_last memory format take the channels-last gather: same bits, under half the HBM bytes.
+    Maps in float16 / bfloat16 are widened to fp32 exactly in the kernel: the outputs are float32 and bit-identical to the
+    call on feat_f0.float(), feat_f1.float(); kenc / rubbish may be half too (widened here)."""
+    ((f0, nhwc), (f1, nhwc1)), dtype = _maps_any([feat_f0, feat_f1], ["feat_f0", "feat_f1"])
     if nhwc != nhwc1:
         f0, f1, nhwc = f0.contiguous(), f1.contiguous(), False
     B = f0.shape[0]
@@ -704,8 +748,8 @@ def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish
     m1 = _dev(mkpts1_c.float(), "mkpts1_c").reshape(-1, 2)
     P = m0.shape[0]
     bi = _dev(b_ids.to(torch.int64), "b_ids", torch.int64).reshape(P)
-    ke = _dev(kenc, "kenc").reshape(128, 64)
-    ru = _dev(rubbish, "rubbish").reshape(B, 128, 144)
+    ke = _dev(_widen(kenc), "kenc").reshape(128, 64)
+    ru = _dev(_widen(rubbish), "rubbish").reshape(B, 128, 144)
     dev = f0.device
     if out is not None:
         o0, o1 = _dev(out[0], "out[0]"), _dev(out[1], "out[1]")
@@ -717,6 +761,11 @@ def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish
     ps = torch.empty((P, 2), dtype=torch.int64, device=dev)
     pt = torch.empty((P, 2), dtype=torch.int64, device=dev)
     cnt = _dev(count, "count", torch.int64).reshape(1) if count is not None else None
+    if dtype is not None:
+        _check(_L().pats_third_descriptors_typed(_ptr(f0), _ptr(f1), dtype, int(bool(nhwc)), _ptr(m0), _ptr(m1), _ptr(bi),
+                                                 _ptr(ke), _ptr(ru), P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt),
+                                                 _stream()), "third_descriptors")
+        return o0, o1, ps, pt
     if nhwc:
         _check(_L().pats_third_descriptors_nhwc_f32(_ptr(f0), _ptr(f1), _ptr(m0), _ptr(m1), _ptr(bi), _ptr(ke), _ptr(ru),
                                                     P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt), _stream()),
