@@ -527,7 +527,7 @@ typedef struct pats_pair_table {
     const int64_t* cell_base_host;   /* [pairs + 1], host memory */
     const int32_t* shape;            /* the same two arrays in device memory */
     const int64_t* cell_base;
-    const int64_t* img_base;         /* [pairs] device: offset in floats of pair p's image in the flat left / right stores */
+    const int64_t* img_base;         /* [pairs] device: offset in elements of pair p's image in the flat left / right stores */
 } pats_pair_table_t;
 
 /* pats_chunk_rows_device for a ragged batch: each pair is planned on its own grid with the chunk cap of first_layer.py:131-135
@@ -550,6 +550,38 @@ int pats_left_crops_ragged_f32(const pats_pair_table_t* tab, const float* left, 
                                const int64_t* K_dev, float* out, pats_stream_t stream);
 int pats_tensor_resize_hwc_ragged_f32(const pats_pair_table_t* tab, const float* right, int margin, const int64_t* bound5,
                                       int64_t K_cap, const int64_t* K_dev, float* out, int32_t* status, pats_stream_t stream);
+
+/* ---- a13 / a14 on images of any element type, crops in the backbone's format --------------------------------------------
+ * The images (left / right HWC stores, tensor_resize's NCHW input) hold `dtype` elements.  Each element is widened to fp32
+ * EXACTLY at the load, and the crop is computed as the _f32 kernels compute it, in the same order: an fp32 crop is
+ * bit-identical to the _f32 entry points' crop of the images converted to float32.  The format then applies per element,
+ * in fp32: with `normalize`, (x - mean[c]) / std[c] (a subtraction, then an IEEE division: torchvision's Normalize), then ONE
+ * rounding to `dtype` (round-to-nearest-even).  layout hwc = [K,96,96,3], chw = [K,3,96,96] ([K,C,96,96] for tensor_resize,
+ * whose output is always chw).  PATS_IMG_U8 output: left crops of uint8 images only, not normalised (exact copies).  A crop
+ * that tensor_resize refuses (status) is written as the format's value of a zero pixel.
+ * tab: a ragged batch (n_img, H, W, height, width are then unused), or NULL for n_img uniform images.  K_dev: NULL = K_cap
+ * crops; else the crops run over the capacity K_cap and rows >= *K_dev are left untouched.  Refused before any launch
+ * (PATS_ERR_INVALID): an unknown image dtype, output dtype or layout; uint8 output for right crops / tensor_resize, of other
+ * images or with normalisation; with normalisation, a non-finite mean / std or std == 0 (tensor_resize: also C != 3); NULL
+ * pointers; images not aligned to their element size; out not 16-byte aligned.  PATS_CROPS_NT applies to every format. */
+typedef enum { PATS_IMG_F32 = 0, PATS_IMG_F16 = 1, PATS_IMG_BF16 = 2, PATS_IMG_U8 = 3 } pats_img_dtype_t;
+typedef enum { PATS_CROP_HWC = 0, PATS_CROP_CHW = 1 } pats_crop_layout_t;
+typedef struct pats_crop_format {
+    int32_t dtype;        /* pats_img_dtype_t of the crops */
+    int32_t layout;       /* pats_crop_layout_t */
+    int32_t normalize;    /* 0 / 1 */
+    float mean[3];
+    float std[3];
+} pats_crop_format_t;
+int pats_left_crops_typed(const pats_pair_table_t* tab, const void* left, pats_img_dtype_t dtype, int n_img, int H, int W,
+                          int height, int width, const int64_t* bound5, int64_t K_cap, const int64_t* K_dev,
+                          const pats_crop_format_t* fmt, void* out, pats_stream_t stream);
+int pats_tensor_resize_hwc_typed(const pats_pair_table_t* tab, const void* right, pats_img_dtype_t dtype, int n_img, int H, int W,
+                                 int margin, const int64_t* bound5, int64_t K_cap, const int64_t* K_dev,
+                                 const pats_crop_format_t* fmt, void* out, int32_t* status, pats_stream_t stream);
+int pats_tensor_resize_typed(const void* input, pats_img_dtype_t dtype, int n_img, int C, int Hp, int Wp, const int64_t* bound,
+                             int64_t K_cap, const int64_t* K_dev, const pats_crop_format_t* fmt, void* out, int32_t* status,
+                             pats_stream_t stream);
 /* pats_merge_patches_batch for a ragged batch (row table of pats_chunk_rows_ragged; scores_back packed [sum N, 16, 9]). */
 size_t pats_merge_ragged_workspace_bytes(int64_t total_cells);
 int pats_merge_patches_ragged(const pats_pair_table_t* tab, int merge_new, int Cmax, int64_t rows_cap, const int64_t* chunk_base,

@@ -29,6 +29,15 @@ class PairTable(ctypes.Structure):
 
 _TAB = ctypes.POINTER(PairTable)
 
+
+class CropFormat(ctypes.Structure):
+    """pats_crop_format_t (include/pats_amd.h): the crops' dtype (pats_img_dtype_t), layout (0 hwc, 1 chw), normalisation."""
+    _fields_ = [("dtype", ctypes.c_int32), ("layout", ctypes.c_int32), ("normalize", ctypes.c_int32),
+                ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
+
+
+_FMT = ctypes.POINTER(CropFormat)
+
 # name -> (restype, argtypes); must list every symbol include/pats_amd.h declares
 SIGNATURES = {
     "pats_version": (ctypes.c_char_p, []),
@@ -167,6 +176,12 @@ SIGNATURES = {
     "pats_compute_imgs_bounds_ragged_f32": (c_int, [_TAB] + [c_void_p] * 10 + [c_void_p]),
     "pats_left_crops_ragged_f32": (c_int, [_TAB, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
     "pats_tensor_resize_hwc_ragged_f32": (c_int, [_TAB, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pats_left_crops_typed": (c_int, [_TAB, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p,
+                                      _FMT, c_void_p, c_void_p]),
+    "pats_tensor_resize_hwc_typed": (c_int, [_TAB, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, _FMT,
+                                             c_void_p, c_void_p, c_void_p]),
+    "pats_tensor_resize_typed": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, _FMT, c_void_p,
+                                         c_void_p, c_void_p]),
     "pats_merge_ragged_workspace_bytes": (c_size, [c_i64]),
     "pats_merge_patches_ragged": (c_int, [_TAB, c_int, c_int, c_i64] + [c_void_p] * 8 + [c_int, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_get_result_chunks_ragged_f32": (c_int, [_TAB, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,

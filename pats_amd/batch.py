@@ -30,6 +30,9 @@ the backbone maps they gather from with ops.fine_descriptors / ops.third_descrip
   nets.fine(rows, new_left, new_right) -> mdesc0 [rows_cap,264,145], mdesc1, scale_x [rows_cap,1,144], scale_y
       [, scale_x * scale_y] (what ops.scale_head hands out; formed here if absent)
       rows: ops.ChunkRows (row r shows crop rows.row_crop[r] of new_left / new_right [pairs*N,96,96,3])
+      The crops are float32 HWC unless forward_pairs / forward_pairs_mixed get a crop_format (ops.CropFormat): then both
+      come in that format - e.g. CropFormat.backbone(torch.bfloat16): [pairs*N,3,96,96] bf16, normalised, the backbone's
+      input as it stands (a uint8 format: uint8 left crops, float32 right crops).
   nets.third(rows, mkpts0_c [P_cap,2], mkpts1_c [P_cap,2], b_ids [P_cap], P_dev [1]) ->
       feat0 [P_cap,128,65], feat1 [P_cap,128,65], scale [P_cap,1,64] [, p_s, p_t [P_cap,2] int64: the points rounded to
       the 4-px lattice as ops.third_descriptors returns them; formed here if absent]      (b_ids = row of the table)
@@ -83,7 +86,7 @@ class MixedCapacities:
 class MixedPack:
     """What pack_pairs returns.  Pairs are sorted stably by grid into SLOTS, so every shape group is a contiguous slot range:
         shapes          (h, w) per slot;  slot_of / caller_of: caller index -> slot, slot -> caller index
-        left, right     the flat HWC image stores (slot order; pair s at table.img_base[s] floats)
+        left, right     the flat HWC image stores (slot order; pair s at table.img_base[s] elements)
         table           ops.PairTable of the slots (grids, packed cell ranges, image offsets)
         groups          [(slot_lo, slot_hi, h, w, lefts [g,32h,32w,3], rights)] - views into the stores, for nets.coarse"""
 
@@ -94,9 +97,11 @@ def slot_order(shapes):
     return sorted(range(len(shapes)), key=lambda i: tuple(shapes[i]))
 
 
-def pack_pairs(pairs):
-    """pairs: [(left, right)] HWC float32 GPU tensors, each [H_p, W_p, 3] or [1, H_p, W_p, 3] with H_p, W_p multiples of 32 (the two
-    images of a pair the same size).  Returns a MixedPack for forward_pairs_mixed."""
+def pack_pairs(pairs, keep_dtype=False):
+    """pairs: [(left, right)] HWC GPU tensors, each [H_p, W_p, 3] or [1, H_p, W_p, 3] with H_p, W_p multiples of 32 (the two
+    images of a pair the same size).  Returns a MixedPack for forward_pairs_mixed.  The stores are float32 (.float() of every
+    image) - or, with keep_dtype=True, the pairs' own dtype, which must be one of float32, float16, bfloat16 and uint8 and the
+    same for every image (nets.coarse then gets views in that dtype; the crops widen it exactly, ops.Compute_imgs_ragged)."""
     if not pairs:
         raise ValueError("pack_pairs: no pairs")
     imgs, shapes = [], []
@@ -105,8 +110,13 @@ def pack_pairs(pairs):
         r = r[0] if r.dim() == 4 else r
         if l.dim() != 3 or l.shape[2] != 3 or l.shape != r.shape or l.shape[0] % 32 or l.shape[1] % 32 or not l.is_cuda:
             raise ValueError("pack_pairs: pair %d must be two equal [H,W,3] GPU images with H, W multiples of 32" % i)
-        imgs.append((l.float(), r.float()))
+        imgs.append((l, r) if keep_dtype else (l.float(), r.float()))
         shapes.append((int(l.shape[0]) // 32, int(l.shape[1]) // 32))
+    if keep_dtype:
+        dts = {t.dtype for pr in imgs for t in pr}
+        if len(dts) != 1 or next(iter(dts)) not in (torch.float32, torch.float16, torch.bfloat16, torch.uint8):
+            raise ValueError("pack_pairs: keep_dtype needs every image in one of float32, float16, bfloat16, uint8, got %s"
+                             % sorted(str(d) for d in dts))
     caller_of = slot_order(shapes)
     pk = MixedPack()
     pk.caller_of = caller_of
@@ -150,7 +160,7 @@ def _round4(x, clamp96):
     return torch.round(x / 4.0).long() * 4
 
 
-def coarse_stage(lefts, rights, nets, cap, iters=100, fine_inputs=True):
+def coarse_stage(lefts, rights, nets, cap, iters=100, fine_inputs=True, crop_format=None):
     """(fine_inputs="rows_only": stop after the row table - capacity planning.)
     The first layer's tail for all pairs + the chunk plan / row table + the crops (first_layer.py:110-146,
     utils.py:1343-1393) and - fine_inputs=True - the second layer's descriptors for those rows (nets.fine: backbone on the
@@ -167,7 +177,7 @@ def coarse_stage(lefts, rights, nets, cap, iters=100, fine_inputs=True):
     if fine_inputs == "rows_only":
         return {"rows": rows, "ifn1": ifn1}
     new_left, new_right, xsn, ysn, avn, bound5, K_img, K_tot = ops.Compute_imgs_ex(
-        xs, ys, pts, ifn1, lefts, rights, width=w, height=h, known_count="device")
+        xs, ys, pts, ifn1, lefts, rights, width=w, height=h, known_count="device", crop_format=crop_format)
     co = {"rows": rows, "new_left": new_left, "new_right": new_right, "xsn": xsn, "avn": avn, "K_img": K_img,
           "ifn1": ifn1, "H": H, "W": W}
     if fine_inputs:
@@ -247,19 +257,21 @@ def fine_third_stage(co, nets, cap, if_outdoor=True, merge_new=True, iters=100, 
     return third_stage(fs, nets, cap, if_outdoor, iters, events)
 
 
-def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None):
-    """lefts / rights [pairs,H,W,3] float32 HWC.  Returns a dict of DEVICE tensors:
+def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None):
+    """lefts / rights [pairs,H,W,3] HWC, float32 (or float16 / bfloat16 / uint8: nets.coarse gets them as they are, the crops
+    widen them exactly).  crop_format: the ops.CropFormat nets.fine receives the crops in (None: float32 HWC).
+    Returns a dict of DEVICE tensors:
         matches_l, matches_r [M_cap,2]   the first M rows valid, reference order inside every pair (chunk, patch, sub-cell)
         match_row [M_cap] int32          row of the table per match;  rows.row_cell[match_row] // N = pair
         M, P [1] int64, status [1] int32 match count, third-level problem count (P > cap.P_cap = overflow), table status
         rows                             the ops.ChunkRows table
         stages                           the intermediate tensors (parity checks; nothing reads them here)
     No host read happens in here."""
-    co = coarse_stage(lefts, rights, nets, cap, iters, fine_inputs=False)
+    co = coarse_stage(lefts, rights, nets, cap, iters, fine_inputs=False, crop_format=crop_format)
     return fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
 
 
-def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True):
+def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True, crop_format=None):
     """coarse_stage for a MixedPack: the first layer's tail once per shape group (the coarse solvers are chosen by size, so a
     group is one launch set on one grid - bits independent of the batch), its per-cell outputs packed over the slots, then the
     row table and the crops in ONE launch set over the whole batch (ops.chunk_rows_ragged, ops.Compute_imgs_ragged)."""
@@ -278,20 +290,21 @@ def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True):
     xs, ys, pts = (xs[0], ys[0], pts[0]) if one else (torch.cat(xs), torch.cat(ys), torch.cat(pts))
     rows = ops.chunk_rows_ragged(ifn1, pack.table, if_local, Cmax=cap.Cmax, rows_cap=cap.rows_cap)
     new_left, new_right, xsn, ysn, avn, bound5, K_img, K_tot = ops.Compute_imgs_ragged(xs, ys, pts, ifn1, pack.left, pack.right,
-                                                                                       pack.table)
+                                                                                       pack.table, crop_format=crop_format)
     return {"rows": rows, "new_left": new_left, "new_right": new_right, "xsn": xsn, "avn": avn, "K_img": K_img, "ifn1": ifn1,
             "H": None, "W": None}
 
 
-def forward_pairs_mixed(pack, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None):
+def forward_pairs_mixed(pack, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None):
     """forward_pairs for pairs of different grids (pack_pairs): the coarse level once per shape group, everything from the row
     table on ONE launch set over the whole batch, no host read.  Same result dict, in SLOT order (rows.row_pair = the slot;
     pack.caller_of[slot] = the caller's index); split_by_pair(out, cap) hands the per-pair lists back in the caller's order.
     Every pair's matches are bit-identical to forward_pairs / pipeline.forward_path on that pair alone.  nets.coarse is called
-    once per group with its [g, 32h, 32w, 3] views; nets.fine / nets.third find a row's pair through rows.row_pair."""
+    once per group with its [g, 32h, 32w, 3] views; nets.fine / nets.third find a row's pair through rows.row_pair.
+    crop_format: as for forward_pairs."""
     if cap.pairs != pack.table.pairs or sorted(cap.shapes) != sorted(pack.shapes):
         raise ValueError("forward_pairs_mixed: the capacities were made for other shapes than the pack holds")
-    co = coarse_stage_mixed(pack, nets, cap, iters, cap.if_local)
+    co = coarse_stage_mixed(pack, nets, cap, iters, cap.if_local, crop_format=crop_format)
     out = fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
     out["caller_of"] = pack.caller_of
     return out

@@ -3,8 +3,8 @@
 // definition :92-93, built by setup/setup.py:107-118, imported at utils/utils.py:17, called at utils/utils.py:1385).
 //
 // This file is the libtorch / pybind11 side only: it checks the tensors, allocates the result, and hands raw device
-// pointers + the caller's current HIP stream to the C-ABI `pats_tensor_resize_f32` of libpats_amd.so
-// (include/pats_amd.h), where the gather kernel lives (csrc/resize.hip).  There is no host path: a CPU tensor raises.
+// pointers + the caller's current HIP stream to the C-ABI `pats_tensor_resize_f32` (`pats_tensor_resize_typed` for half
+// inputs) of libpats_amd.so (include/pats_amd.h), where the gather kernel lives (csrc/resize.hip).  There is no host path: a CPU tensor raises.
 #include <torch/extension.h>
 // PyTorch-ROCm keeps the device type named `cuda` (torch.device("cuda") IS the MI355X), so the guard and the stream
 // come from the HIP implementations registered under that name; the plain c10::hip::HIPGuard refuses such a device.
@@ -22,8 +22,11 @@ torch::Tensor resize(const torch::Tensor& input_tensor, const torch::Tensor& bou
               "tensor_resize: input must live on the GPU (pats_amd has no CPU fallback), got ", input_tensor.device());
   TORCH_CHECK(bound.device() == input_tensor.device(), "tensor_resize: bound is on ", bound.device(),
               ", input on ", input_tensor.device());
-  TORCH_CHECK(input_tensor.scalar_type() == torch::kFloat, "tensor_resize: input must be float32, got ",
-              input_tensor.scalar_type());
+  // library.cpp:50-62 resizes a half input and writes it into a kFloat result: float16 / bfloat16 inputs are widened to
+  // fp32 exactly in the kernel and give the float32 result of the call on input.float(), bit for bit
+  const auto st = input_tensor.scalar_type();
+  TORCH_CHECK(st == torch::kFloat || st == torch::kHalf || st == torch::kBFloat16,
+              "tensor_resize: input must be float32, float16 or bfloat16, got ", st);
   TORCH_CHECK(bound.scalar_type() == torch::kLong, "tensor_resize: bound must be int64, got ", bound.scalar_type());
   TORCH_CHECK(input_tensor.dim() == 4, "tensor_resize: input must be [n,C,H,W], got ", input_tensor.dim(), " dims");
   TORCH_CHECK(bound.dim() == 2 && bound.size(1) == 5, "tensor_resize: bound must be [K,5] (y0,y1,x0,x1,seq)");
@@ -34,7 +37,7 @@ torch::Tensor resize(const torch::Tensor& input_tensor, const torch::Tensor& bou
   const auto in = input_tensor.contiguous();      // borrowed; a strided view is packed, never written
   const auto bnd = bound.contiguous();
   const int64_t K = bnd.size(0);
-  auto out = torch::empty({K, in.size(1), kOut, kOut}, in.options());
+  auto out = torch::empty({K, in.size(1), kOut, kOut}, in.options().dtype(torch::kFloat));
   if (K == 0) return out;                          // nothing matched: the reference's loop body never runs
 
   // library.cpp:56-60: narrow() beyond the tensor and upsample of an empty crop are c10::Error there.  The kernel is
@@ -42,10 +45,18 @@ torch::Tensor resize(const torch::Tensor& input_tensor, const torch::Tensor& bou
   // (the reference makes five per crop).
   auto status = torch::zeros({1}, bnd.options().dtype(torch::kInt));
   const auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(input_tensor.device().index());
-  const int rc = pats_tensor_resize_f32(in.data_ptr<float>(), static_cast<int>(in.size(0)), static_cast<int>(in.size(1)),
-                                        static_cast<int>(in.size(2)), static_cast<int>(in.size(3)),
-                                        bnd.data_ptr<int64_t>(), K, out.data_ptr<float>(), status.data_ptr<int32_t>(),
-                                        static_cast<pats_stream_t>(stream.stream()));
+  int rc;
+  if (st == torch::kFloat) {
+    rc = pats_tensor_resize_f32(in.data_ptr<float>(), static_cast<int>(in.size(0)), static_cast<int>(in.size(1)),
+                                static_cast<int>(in.size(2)), static_cast<int>(in.size(3)), bnd.data_ptr<int64_t>(), K,
+                                out.data_ptr<float>(), status.data_ptr<int32_t>(), static_cast<pats_stream_t>(stream.stream()));
+  } else {
+    const pats_crop_format_t fmt = {PATS_IMG_F32, PATS_CROP_CHW, 0, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};
+    rc = pats_tensor_resize_typed(in.data_ptr(), st == torch::kHalf ? PATS_IMG_F16 : PATS_IMG_BF16, static_cast<int>(in.size(0)),
+                                  static_cast<int>(in.size(1)), static_cast<int>(in.size(2)), static_cast<int>(in.size(3)),
+                                  bnd.data_ptr<int64_t>(), K, nullptr, &fmt, out.data_ptr(), status.data_ptr<int32_t>(),
+                                  static_cast<pats_stream_t>(stream.stream()));
+  }
   TORCH_CHECK(rc == 0, "tensor_resize: ", pats_last_error());
   TORCH_CHECK(status.item<int32_t>() == 0, "tensor_resize: a crop is empty or outside the ", in.size(2), "x", in.size(3),
               " input (start/length out of range, or image index >= ", in.size(0), ")");

@@ -512,11 +512,129 @@ def split_patches_device(sum_cycle, height, width, max_once_used=350):
 # ------------------------------------------------------------------------------------------------
 # subdivision gather
 # ------------------------------------------------------------------------------------------------
+# element types the crops take images in and write crops in (include/pats_amd.h pats_img_dtype_t)
+_IMG_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}
+_LAYOUTS = {"hwc": 0, "chw": 1}
+
+
+class CropFormat:
+    """The format the subdivision gather writes its crops in (pats_crop_format_t).
+        dtype   torch.float32 / float16 / bfloat16, or torch.uint8 for the left crops of uint8 images (exact copies; the
+                right crops then come out float32, like the reference's new_left / new_right, utils.py:1352-1385)
+        layout  "hwc" [K,96,96,3] or "chw" [K,3,96,96] (= crops.permute(0,3,1,2).contiguous())
+        mean, std  three floats each, or None: per-channel (x - mean[c]) / std[c] in fp32 (torchvision's Normalize)
+    Every crop is computed in fp32 as the float32 kernels compute it, then normalised, then rounded ONCE to dtype
+    (round-to-nearest-even).  CropFormat() is today's output: float32 HWC, not normalised."""
+
+    BACKBONE_MEAN = (0.485, 0.456, 0.406)          # second_layer.py:56
+    BACKBONE_STD = (0.229, 0.224, 0.225)
+
+    def __init__(self, dtype=torch.float32, layout="hwc", mean=None, std=None):
+        if dtype not in _IMG_DTYPES:
+            raise ValueError("CropFormat: dtype must be float32, float16, bfloat16 or uint8, got %r" % (dtype,))
+        if layout not in _LAYOUTS:
+            raise ValueError("CropFormat: layout must be 'hwc' or 'chw', got %r" % (layout,))
+        if (mean is None) != (std is None):
+            raise ValueError("CropFormat: mean and std go together")
+        if mean is not None:
+            mean, std = tuple(float(m) for m in mean), tuple(float(v) for v in std)
+            if len(mean) != 3 or len(std) != 3:
+                raise ValueError("CropFormat: mean and std need 3 values each, got %d and %d" % (len(mean), len(std)))
+            if not all(np.isfinite(mean)) or not all(np.isfinite(std)) or any(v == 0.0 for v in std):
+                raise ValueError("CropFormat: mean and std must be finite and std non-zero")
+            if dtype == torch.uint8:
+                raise ValueError("CropFormat: uint8 crops cannot be normalised")
+        self.dtype, self.layout, self.mean, self.std = dtype, layout, mean, std
+
+    @classmethod
+    def backbone(cls, dtype=torch.float32):
+        """What the reference's fine backbone reads (second_layer.py:56,66-68): chw, Normalize(mean, std) of the 0..255 values."""
+        return cls(dtype, "chw", cls.BACKBONE_MEAN, cls.BACKBONE_STD)
+
+    @property
+    def normalize(self):
+        return self.mean is not None
+
+    def is_default(self):
+        return self.dtype == torch.float32 and self.layout == "hwc" and not self.normalize
+
+    def shape(self, rows):
+        return (rows, 96, 96, 3) if self.layout == "hwc" else (rows, 3, 96, 96)
+
+    def _c(self):
+        f = _lib.CropFormat()
+        f.dtype, f.layout, f.normalize = _IMG_DTYPES[self.dtype], _LAYOUTS[self.layout], int(self.normalize)
+        for c in range(3):
+            f.mean[c] = self.mean[c] if self.normalize else 0.0
+            f.std[c] = self.std[c] if self.normalize else 1.0
+        return f
+
+    def __eq__(self, other):
+        return isinstance(other, CropFormat) and (self.dtype, self.layout, self.mean, self.std) == \
+            (other.dtype, other.layout, other.mean, other.std)
+
+    def __repr__(self):
+        return "CropFormat(dtype=%s, layout=%r, mean=%r, std=%r)" % (self.dtype, self.layout, self.mean, self.std)
+
+
+def _crop_images(left, right, names):
+    """The images of ONE crop call -> (left, right, pats_img_dtype_t code).  float32 / float16 / bfloat16 / uint8 images of
+    one dtype go to the kernels as they are (a non-contiguous view is made contiguous, in its dtype); images of other dtypes,
+    or of two different dtypes, take the float32 path on .float() copies, as every crop call did before the typed kernels."""
+    for t, n in zip((left, right), names):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % n)
+    if left.dtype == right.dtype and left.dtype in _IMG_DTYPES:
+        return _dev(left, names[0], left.dtype), _dev(right, names[1], right.dtype), _IMG_DTYPES[left.dtype]
+    return _dev(left.float(), names[0]), _dev(right.float(), names[1]), 0
+
+
+def _crop_formats(crop_format, code, left_dtype=None):
+    """(left format, right format, dtype to convert the left crops to afterwards or None).  crop_format None: float32 HWC -
+    except the host-count path of Compute_imgs (left_dtype given), whose new_left keeps left.dtype as it always did."""
+    if crop_format is None:
+        lf = rf = CropFormat()
+        if left_dtype is not None and left_dtype != torch.float32:
+            if left_dtype in _IMG_DTYPES and (left_dtype != torch.uint8 or code == 3):
+                lf = CropFormat(left_dtype)
+            else:
+                return lf, rf, left_dtype
+        return lf, rf, None
+    if not isinstance(crop_format, CropFormat):
+        raise TypeError("crop_format must be an ops.CropFormat or None")
+    if crop_format.dtype == torch.uint8:
+        if code != 3:
+            raise RuntimeError("Compute_imgs: uint8 crops need uint8 images")
+        return crop_format, CropFormat(torch.float32, crop_format.layout), None
+    return crop_format, crop_format, None
+
+
+def _crop_out(t, fmt, rows, name, device):
+    """A crop output: allocated, or the caller's tensor (dtype and per-crop shape of the format, >= rows crops, contiguous,
+    16-byte aligned) cut to `rows` crops."""
+    if t is None:
+        return torch.empty(fmt.shape(rows), dtype=fmt.dtype, device=device)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+        raise RuntimeError("Compute_imgs: %s must be a GPU tensor on %s" % (name, device))
+    if t.dtype != fmt.dtype or tuple(t.shape[1:]) != fmt.shape(rows)[1:] or t.shape[0] < rows:
+        raise RuntimeError("Compute_imgs: %s must be %s of shape [>= %d, %s], got %s %s" % (
+            name, fmt.dtype, rows, ",".join(str(d) for d in fmt.shape(rows)[1:]), t.dtype, tuple(t.shape)))
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise RuntimeError("Compute_imgs: %s must be contiguous and 16-byte aligned" % name)
+    return t[:rows]
+
+
 def tensor_resize(input_tensor, bound, validate=True):
     """tensor_resize.tensor_resize(input, bound)  (setup/library.cpp:47-66,92-93).
     input [n,C,Hp,Wp] float32, bound [K,5] int64 -> new [K,C,96,96] float32 on input.device.
+    A float16 / bfloat16 input is widened to fp32 exactly in the kernel (library.cpp:50-62 resizes a half input into a
+    float32 result): the result is float32 and bit-identical to the call on input.float().
     Raises RuntimeError for an empty or out-of-range crop like the reference (validate=True)."""
-    inp = _dev(input_tensor, "input_tensor")
+    if not isinstance(input_tensor, torch.Tensor):
+        raise TypeError("input_tensor must be a torch.Tensor")
+    if input_tensor.dtype not in _MAP_DTYPES:
+        raise RuntimeError("pats_amd: input_tensor must be float32, float16 or bfloat16, got %s" % input_tensor.dtype)
+    inp = _dev(input_tensor, "input_tensor", input_tensor.dtype)
     bnd = _dev(bound, "bound", torch.int64)
     if inp.dim() != 4 or bnd.dim() != 2 or bnd.shape[1] != 5:
         raise RuntimeError("tensor_resize: expected input [n,C,H,W] and bound [K,5]")
@@ -524,8 +642,13 @@ def tensor_resize(input_tensor, bound, validate=True):
     K = bnd.shape[0]
     out = torch.empty((K, C, 96, 96), dtype=torch.float32, device=inp.device)
     status = torch.zeros((1,), dtype=torch.int32, device=inp.device) if validate else None
-    _check(_L().pats_tensor_resize_f32(_ptr(inp), n_img, C, Hp, Wp, _ptr(bnd), K, _ptr(out),
-                                       _ptr(status), _stream()), "tensor_resize")
+    if inp.dtype == torch.float32:
+        _check(_L().pats_tensor_resize_f32(_ptr(inp), n_img, C, Hp, Wp, _ptr(bnd), K, _ptr(out),
+                                           _ptr(status), _stream()), "tensor_resize")
+    else:
+        fmt = CropFormat(torch.float32, "chw")._c()
+        _check(_L().pats_tensor_resize_typed(_ptr(inp), _IMG_DTYPES[inp.dtype], n_img, C, Hp, Wp, _ptr(bnd), K, None,
+                                             ctypes.byref(fmt), _ptr(out), _ptr(status), _stream()), "tensor_resize")
     if validate and K > 0 and int(status.item()) != 0:
         # library.cpp:56-60: narrow() outside the tensor / an empty crop into upsample_bilinear2d is a
         # c10::Error there (RuntimeError / IndexError in Python).  One host read per call (the reference
@@ -537,15 +660,16 @@ def tensor_resize(input_tensor, bound, validate=True):
 
 def Compute_imgs(x_scale, y_scale, average_point, if_nomatching, left, right, sequence_num=0,
                  output_path=None, if_view=False, margin=128, width=20, height=15, patch_scale=32, known_count=None,
-                 validate=False):
+                 validate=False, crop_format=None, out=None):
     """utils/utils.py:1343-1393 - same 5-tuple as the reference."""
     return Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right, sequence_num,
-                           output_path, if_view, margin, width, height, patch_scale, known_count, validate)[:5]
+                           output_path, if_view, margin, width, height, patch_scale, known_count, validate,
+                           crop_format, out)[:5]
 
 
 def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right, sequence_num=0,
                     output_path=None, if_view=False, margin=128, width=20, height=15, patch_scale=32,
-                    known_count=None, validate=False):
+                    known_count=None, validate=False, crop_format=None, out=None):
     """Compute_imgs plus the [K,5] bound tensor the reference hands to tensor_resize (utils.py:1382).
     utils/utils.py:1343-1393, any batch of images (PATS.forward uses 1, first_layer.py:135; a batch
     yields the crops of all images in (image, patch) order - `sequence = img * 10000 + patch`, :1374-1377).
@@ -555,7 +679,15 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
     (`known_count`, e.g. the last entry of the cumsum it fetched for split_patches): then no sync;
     validate=True checks those counts against the device-side ones (one host read).
     known_count="device" never touches the host: outputs are sized for the capacity n_img*N, only the first
-    K_total rows are written, and the tuple gains (K_img [n_img], K_total [1]) int64 DEVICE tensors."""
+    K_total rows are written, and the tuple gains (K_img [n_img], K_total [1]) int64 DEVICE tensors.
+    Images: float32, float16, bfloat16 or uint8 (the loaders' cv2 images), left and right of one dtype, are read as they are
+    and widened to fp32 exactly in the kernels - the crops equal those of images.float() bit for bit; images of other dtypes
+    or of two dtypes are converted with .float() first, as before.
+    crop_format: an ops.CropFormat for both sides' crops (dtype, hwc / chw, normalisation; CropFormat.backbone(dtype) is the
+    fine backbone's input).  None: float32 HWC - on the host-count path new_left keeps left.dtype, as it always did.
+    out: optional (left_out, right_out), either may be None - tensors of the format's dtype and per-crop shape with at least
+    as many crops as the call writes (K, or the capacity n_img*N with known_count="device"); the crops are written into them
+    (e.g. buf[0], buf[1] of one [2, cap, 3, 96, 96] buffer whose view(2 * cap, 3, 96, 96) the backbone reads)."""
     if margin != 128 or patch_scale != 32:
         raise RuntimeError("Compute_imgs: margin=128 / patch_scale=32 are what the path uses")
     nb = left.shape[0]                          # images in the batch; crops come out ordered (image, patch)
@@ -565,10 +697,12 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
     ys = _dev(y_scale.float(), "y_scale").reshape(nb, Np)
     ap = _dev(average_point.float(), "average_point").reshape(nb, Np, 2)
     ifn = _as_flags(if_nomatching, "if_nomatching").reshape(nb, Np)         # bool viewed as bytes: no copy kernel
-    leftf = _dev(left.float(), "left")
-    rightf = _dev(right.float(), "right")
+    leftf, rightf, code = _crop_images(left, right, ("left", "right"))
     H, W = leftf.shape[1], leftf.shape[2]
     on_device = isinstance(known_count, str) and known_count == "device"
+    lfmt, rfmt, left_to = _crop_formats(crop_format, code, None if on_device else left.dtype)
+    typed = code != 0 or not lfmt.is_default() or not rfmt.is_default()
+    lout, rout = (None, None) if out is None else out
     counts = None
     if known_count is not None and not on_device:
         if isinstance(known_count, torch.Tensor):
@@ -589,12 +723,16 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
     status = torch.zeros((1,), dtype=torch.int32, device=dev) if validate else None
     if on_device:
         cap = nb * Np
-        new_left = torch.empty((cap, 96, 96, 3), dtype=torch.float32, device=dev)
-        new_right = torch.empty((cap, 96, 96, 3), dtype=torch.float32, device=dev)
-        _check(_L().pats_left_crops_counted_f32(_ptr(leftf), nb, H, W, _ptr(bound5), cap, _ptr(Kt), height, width,
-                                                _ptr(new_left), _stream()), "Compute_imgs(left)")
-        _check(_L().pats_tensor_resize_hwc_counted_f32(_ptr(rightf), nb, H, W, margin, _ptr(bound5), cap, _ptr(Kt),
-                                                       _ptr(new_right), _ptr(status), _stream()), "Compute_imgs(right)")
+        new_left = _crop_out(lout, lfmt, cap, "out[0]", dev)
+        new_right = _crop_out(rout, rfmt, cap, "out[1]", dev)
+        if typed:
+            _typed_crops(None, leftf, rightf, code, nb, H, W, height, width, margin, bound5, cap, Kt, lfmt, rfmt, new_left,
+                         new_right, status)
+        else:
+            _check(_L().pats_left_crops_counted_f32(_ptr(leftf), nb, H, W, _ptr(bound5), cap, _ptr(Kt), height, width,
+                                                    _ptr(new_left), _stream()), "Compute_imgs(left)")
+            _check(_L().pats_tensor_resize_hwc_counted_f32(_ptr(rightf), nb, H, W, margin, _ptr(bound5), cap, _ptr(Kt),
+                                                           _ptr(new_right), _ptr(status), _stream()), "Compute_imgs(right)")
         if validate and int(status.item()) != 0:
             raise RuntimeError("Compute_imgs: a right crop is empty or outside the padded image")
         return new_left, new_right, xsn, ysn, avn, bound5, Kd, Kt
@@ -605,17 +743,35 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
         if got != counts:
             raise RuntimeError("Compute_imgs: known_count %s does not match the matched patches per image %s" % (counts, got))
     K = sum(counts)
-    new_left = torch.empty((K, 96, 96, 3), dtype=torch.float32, device=dev)
-    new_right = torch.empty((K, 96, 96, 3), dtype=torch.float32, device=dev)
-    _check(_L().pats_left_crops_f32(_ptr(leftf), nb, H, W, _ptr(bound5), K, height, width, _ptr(new_left),
-                                    _stream()), "Compute_imgs(left)")
-    _check(_L().pats_tensor_resize_hwc_f32(_ptr(rightf), nb, H, W, margin, _ptr(bound5), K,
-                                           _ptr(new_right), _ptr(status), _stream()),
-           "Compute_imgs(right)")
+    new_left = _crop_out(lout if left_to is None else None, lfmt, K, "out[0]", dev)
+    new_right = _crop_out(rout, rfmt, K, "out[1]", dev)
+    if typed:
+        _typed_crops(None, leftf, rightf, code, nb, H, W, height, width, margin, bound5, K, None, lfmt, rfmt, new_left, new_right,
+                     status)
+    else:
+        _check(_L().pats_left_crops_f32(_ptr(leftf), nb, H, W, _ptr(bound5), K, height, width, _ptr(new_left),
+                                        _stream()), "Compute_imgs(left)")
+        _check(_L().pats_tensor_resize_hwc_f32(_ptr(rightf), nb, H, W, margin, _ptr(bound5), K,
+                                               _ptr(new_right), _ptr(status), _stream()),
+               "Compute_imgs(right)")
     if validate and K > 0 and int(status.item()) != 0:
         raise RuntimeError("Compute_imgs: a right crop is empty or outside the padded image")
-    new_left = new_left.to(left.dtype) if left.dtype != torch.float32 else new_left
+    if left_to is not None:                 # a left image of another dtype (e.g. float64): converted back, as before
+        new_left = new_left.to(left_to)
+        if lout is not None:
+            new_left = _crop_out(lout, CropFormat(left_to), K, "out[0]", dev).copy_(new_left)
     return new_left, new_right, xsn, ysn, avn, bound5[:K]
+
+
+def _typed_crops(table, left, right, code, nb, H, W, height, width, margin, bound5, rows, K_dev, lfmt, rfmt, new_left, new_right,
+                 status):
+    """Both sides' crops through the typed entry points (table: a PairTable, or None for nb uniform images)."""
+    tab = table.ref() if table is not None else None
+    lc, rc = lfmt._c(), rfmt._c()
+    _check(_L().pats_left_crops_typed(tab, _ptr(left), code, nb, H, W, height, width, _ptr(bound5), rows, _ptr(K_dev),
+                                      ctypes.byref(lc), _ptr(new_left), _stream()), "Compute_imgs(left)")
+    _check(_L().pats_tensor_resize_hwc_typed(tab, _ptr(right), code, nb, H, W, margin, _ptr(bound5), rows, _ptr(K_dev),
+                                             ctypes.byref(rc), _ptr(new_right), _ptr(status), _stream()), "Compute_imgs(right)")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1280,10 +1436,13 @@ def chunk_rows_ragged(if_nomatching1, table, if_local=True, Cmax=None, rows_cap=
     return r
 
 
-def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_store, right_store, table, margin=128):
+def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_store, right_store, table, margin=128,
+                        crop_format=None, out=None):
     """Compute_imgs_ex(known_count="device") for a ragged batch: the per-cell inputs packed [sum N] ([sum N, 2] for the point),
-    left_store / right_store the flat HWC stores the table's img_base points into.  Returns (new_left, new_right [sum N,96,96,3],
-    xsn, ysn, avn [sum N,2], bound5 [sum N,5], K_img [pairs], K_total [1]) - device tensors, the first K_total crops valid."""
+    left_store / right_store the flat HWC stores the table's img_base points into (img_base counts elements, so the stores may
+    hold any of the images' dtypes of Compute_imgs_ex).  Returns (new_left, new_right [sum N,96,96,3], xsn, ysn, avn [sum N,2],
+    bound5 [sum N,5], K_img [pairs], K_total [1]) - device tensors, the first K_total crops valid.  crop_format / out: as for
+    Compute_imgs_ex (None: float32 HWC)."""
     if margin != 128:
         raise RuntimeError("Compute_imgs_ragged: margin=128 is what the path uses")
     cells = table.cells
@@ -1293,10 +1452,12 @@ def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_sto
     ifn = _as_flags(if_nomatching, "if_nomatching").reshape(-1)
     if xs.numel() != cells or ys.numel() != cells or ap.numel() != 2 * cells or ifn.numel() != cells:
         raise RuntimeError("Compute_imgs_ragged: per-cell inputs must hold the %d packed cells of the table" % cells)
-    lf, rt = _dev(left_store, "left_store"), _dev(right_store, "right_store")
+    lf, rt, code = _crop_images(left_store, right_store, ("left_store", "right_store"))
+    lfmt, rfmt, _ = _crop_formats(crop_format, code)
+    lout, rout = (None, None) if out is None else out
     need = int(table.img_base_host[-1]) + table.shapes[-1][0] * table.shapes[-1][1] * 1024 * 3 if table.pairs else 0
     if lf.numel() < need or rt.numel() < need:
-        raise RuntimeError("Compute_imgs_ragged: the image stores hold %d / %d floats, the table needs %d" % (lf.numel(), rt.numel(), need))
+        raise RuntimeError("Compute_imgs_ragged: the image stores hold %d / %d elements, the table needs %d" % (lf.numel(), rt.numel(), need))
     dev = xs.device
     bound5 = torch.empty((cells, 5), dtype=torch.int64, device=dev)
     Kd = torch.empty((table.pairs,), dtype=torch.int64, device=dev)
@@ -1306,8 +1467,11 @@ def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_sto
     avn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
     _check(_L().pats_compute_imgs_bounds_ragged_f32(table.ref(), _ptr(xs), _ptr(ys), _ptr(ap), _ptr(ifn), _ptr(bound5), _ptr(Kd),
                                                     _ptr(Kt), _ptr(xsn), _ptr(ysn), _ptr(avn), _stream()), "Compute_imgs_ragged(bounds)")
-    new_left = torch.empty((cells, 96, 96, 3), dtype=torch.float32, device=dev)
-    new_right = torch.empty((cells, 96, 96, 3), dtype=torch.float32, device=dev)
+    new_left = _crop_out(lout, lfmt, cells, "out[0]", dev)
+    new_right = _crop_out(rout, rfmt, cells, "out[1]", dev)
+    if code != 0 or not lfmt.is_default() or not rfmt.is_default():
+        _typed_crops(table, lf, rt, code, 0, 0, 0, 0, 0, margin, bound5, cells, Kt, lfmt, rfmt, new_left, new_right, None)
+        return new_left, new_right, xsn, ysn, avn, bound5, Kd, Kt
     _check(_L().pats_left_crops_ragged_f32(table.ref(), _ptr(lf), _ptr(bound5), cells, _ptr(Kt), _ptr(new_left), _stream()),
            "Compute_imgs_ragged(left)")
     _check(_L().pats_tensor_resize_hwc_ragged_f32(table.ref(), _ptr(rt), margin, _ptr(bound5), cells, _ptr(Kt), _ptr(new_right), None,
