@@ -57,6 +57,11 @@ int pats_set_sinkhorn_mode(int mode);
  * previous setting; PATS_FINE_FUSED=1 in the environment sets the initial one. */
 int pats_set_fine_fused(int on);
 
+/* Which kernel takes the fp32 third-level gather on NCHW maps (pats_third_descriptors_f32, _counted_f32 and the fp32 NCHW route of
+ * pats_third_descriptors_typed): 0 (default) the point-tiled third_desc_kernel, 1 the per-point third_desc_point_kernel.  Same
+ * bits either way.  Returns the previous setting; any other argument leaves it unchanged.  Process-wide. */
+int pats_set_third_gather(int mode);
+
 /* Number of problems (on the current device, since the last reset) whose linear-domain solve left the
  * guard band and was re-solved with log-sum-exp sweeps.  Results are the same either way; a high rate
  * only costs time.  Synchronises the whole device (hipDeviceSynchronize) before the read and after the

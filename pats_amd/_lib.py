@@ -46,6 +46,7 @@ SIGNATURES = {
     "pats_device_count": (c_int, []),
     "pats_set_sinkhorn_mode": (c_int, [c_int]),
     "pats_set_fine_fused": (c_int, [c_int]),
+    "pats_set_third_gather": (c_int, [c_int]),
     "pats_sinkhorn_fallbacks": (c_int, [ctypes.POINTER(ctypes.c_int64), c_int]),
     "pats_set_gnn_redo_mode": (c_int, [c_int]),
     "pats_gnn_overflows": (c_int, [ctypes.POINTER(ctypes.c_int64), c_int]),

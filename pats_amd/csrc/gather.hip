@@ -121,12 +121,13 @@ __device__ __forceinline__ long long round_half_even_div(float x, float d) {
     return (long long)rintf(x / d);      // torch.round = round half to even = rintf in the default mode
 }
 
-// one workgroup (256 threads = 4 waves) per point; wave w handles channels 32w .. 32w+31, eight at a time (sixteen
-// window loads in flight, then sixteen stores); lane = window cell.  The dustbin feature column is written once per wave
-// by 32 lanes (one channel each) instead of by lane 0 inside the channel loop.
+// The per-point kernel (the default until round 7; pats_set_third_gather(1) selects it): one workgroup (256 threads = 4 waves)
+// per point; wave w handles channels 32w .. 32w+31, eight at a time (sixteen window loads in flight, then sixteen stores);
+// lane = window cell.  The dustbin feature column is written once per wave by 32 lanes (one channel each) instead of by
+// lane 0 inside the channel loop.
 template <int POL>
 __global__ void __launch_bounds__(256)
-third_desc_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
+third_desc_point_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
                   const float* __restrict__ mk0, const float* __restrict__ mk1,
                   const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
                   const float* __restrict__ rubbish, int64_t P, int64_t B,
@@ -483,6 +484,96 @@ __device__ __forceinline__ third_point third_point_at(const float* __restrict__ 
     return r;
 }
 
+constexpr int THIRD_TILE = 8;      // points per workgroup of third_desc_kernel
+
+// third level, NCHW, point-tiled (the default): one workgroup per tile of T = 8 consecutive points, wave w owns points
+// 8 tile + 2w and 8 tile + 2w + 1.  third_inputs_kernel emits the points of a fine row consecutively (8 per row on average
+// at the bench's workload) and the windows of neighbouring cells overlap by half, so the CHANNEL loop is outermost: the four
+// waves read the same eight channel planes of neighbouring windows at about the same time and the shared 128-byte lines are
+// hit in the CU's L1 / the XCD's L2 instead of being fetched again by another workgroup later (tools/third_gather_lines.py
+// counts the lines: profiles/r07_third_gather_lines.txt).  Lane = window cell as in third_desc_point_kernel, 32 window loads
+// in flight per chunk.  Each (point, side, chunk) of 8 x 65 outputs - the dustbin value in column 64 - is staged in a
+// wave-private LDS slice and leaves as ONE linear span of 2 080 bytes (130 float4; 16-byte aligned: p * 33 280 +
+// chunk * 2 080 from an aligned base, which the launcher checks), instead of 4-byte stores into rows of 65 floats.  Every
+// element is the same a + ke add (or the same copied dustbin value) as in the per-point kernel: bit-identical by
+// construction.  Points past the count in the last tile re-read the last live point and store nothing.  Tiles of 4 and 16
+// points and a workgroup barrier per chunk measured within 2 % of this (profiles/r07_third_gather_ab.txt).
+template <int POL>
+__global__ void __launch_bounds__(256)
+third_desc_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
+                  const float* __restrict__ mk0, const float* __restrict__ mk1,
+                  const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
+                  const float* __restrict__ rubbish, int64_t P, int64_t B,
+                  float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                  int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
+    constexpr int PW = THIRD_TILE / 4;
+    constexpr int M = 52, C = 128, NT = 65, T = THIRD_TILE, SPAN = 8 * NT;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) float stage[4 * PW * SPAN];
+    int64_t live = P;
+    if (P_dev) { const int64_t n = *P_dev; live = n < P ? n : P; }
+    // XCD-aware tile order as in third_desc_point_kernel: tiles k and k + 1 run on the same XCD one after the other
+    const int64_t tiles = (live + T - 1) / T, per = (tiles + 7) >> 3, tile = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if ((int64_t)(blockIdx.x >> 3) >= per || tile >= tiles) return;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long lim = B * M * M - 1;
+    int64_t pp[PW];
+    bool on[PW];
+    const float* src[PW][2];
+    const float* rub[PW];
+#pragma unroll
+    for (int j = 0; j < PW; ++j) {
+        const int64_t p = tile * T + wave * PW + j;
+        on[j] = p < live;
+        pp[j] = on[j] ? p : live - 1;
+        const int64_t b = b_ids[pp[j]];
+        const third_point tp = third_point_at(mk0, mk1, pp[j], b, B, on[j] && lane == 0, ps_out, pt_out);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            long long i = tp.i00[s] + (lane >> 3) * M + (lane & 7);
+            i = i < 0 ? 0 : (i > lim ? lim : i);      // memory safety (torch.gather would raise out of range)
+            const long long bb = i / (M * M);
+            src[j][s] = (s ? ff1 : ff0) + bb * C * (M * M) + (i - bb * (M * M));
+        }
+        rub[j] = rubbish + tp.bb2 * C * 144 + tp.i2;
+    }
+    float* slice = stage + wave * PW * SPAN;
+#pragma unroll 1
+    for (int c0 = 0; c0 < C; c0 += 8) {
+        float a[PW][2][8], ke[8], rb[PW];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+#pragma unroll
+            for (int j = 0; j < PW; ++j) {
+                a[j][0][k] = ldm<POL>(src[j][0] + (int64_t)(c0 + k) * (M * M));
+                a[j][1][k] = ldm<POL>(src[j][1] + (int64_t)(c0 + k) * (M * M));
+            }
+            ke[k] = kenc[(c0 + k) * 64 + lane];                                      // + self.kenc(kpts)   :139-140
+        }
+#pragma unroll
+        for (int j = 0; j < PW; ++j) rb[j] = lane < 8 ? rub[j][(c0 + lane) * 144] : 0.f;      // :141-146
+#pragma unroll
+        for (int j = 0; j < PW; ++j) {
+            float* sl = slice + j * SPAN;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) sl[k * NT + lane] = a[j][s][k] + ke[k];
+                if (lane < 8) sl[lane * NT + 64] = rb[j];
+                wave_lds_sync();
+                const f4* v = reinterpret_cast<const f4*>(sl);
+                f4* o = reinterpret_cast<f4*>((s ? out1 : out0) + pp[j] * (C * NT) + c0 * NT);
+                if (on[j]) {
+                    stm<POL>(o + lane, v[lane]);
+                    stm<POL>(o + lane + 64, v[lane + 64]);
+                    if (lane < SPAN / 4 - 128) stm<POL>(o + lane + 128, v[lane + 128]);
+                }
+                wave_lds_sync();                      // the next writes of the slice come after these reads
+            }
+        }
+    }
+}
+
 // third level, NCHW: a window row of 8 cells is 16 contiguous bytes of a map row, so a lane takes TWO neighbouring cells as
 // one 4-byte pair - lanes 0..31 one channel's 8x8 window, lanes 32..63 the next channel's - and stores them as one 8-byte
 // write.  A pair starts at an even row i of the NHWC view (s0, q0 are multiples of 4, M is even), so it never straddles two
@@ -710,9 +801,33 @@ static int gather_policy(bool channels_last) {
     if ((DTYPE) == PATS_MAP_F16) { GATHER_LAUNCH_HALF(KERNEL, PATS_MAP_F16, NHWC, grid, __VA_ARGS__) }                        \
     else { GATHER_LAUNCH_HALF(KERNEL, PATS_MAP_BF16, NHWC, grid, __VA_ARGS__) }
 
+// The NCHW fp32 third-level gather: the point-tiled third_desc_kernel, or - pats_set_third_gather(1), or outputs that are
+// not 16-byte aligned - third_desc_point_kernel.  Same store policy default as the other NCHW gathers: non-temporal stores
+// measured within 1 % of plain ones here (profiles/r07_third_gather_ab.txt).
+static int g_third_gather = 0;
+static int launch_third_nchw_f32(const float* f0, const float* f1, const float* mkpts0_c, const float* mkpts1_c,
+                                 const int64_t* b_ids, const float* kenc, const float* rubbish, int64_t P_cap, const int64_t* P_dev,
+                                 int64_t B, float* out0, float* out1, int64_t* p_s_out, int64_t* p_t_out, pats_stream_t stream) {
+    if (g_third_gather == 1 || ((uintptr_t)out0 | (uintptr_t)out1) % 16 != 0) {
+        GATHER_LAUNCH(third_desc_point_kernel, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), f0, f1, mkpts0_c, mkpts1_c, b_ids,
+                      kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+        return check_launch("third_desc_point_kernel");
+    }
+    const int64_t tiles = (P_cap + THIRD_TILE - 1) / THIRD_TILE;
+    GATHER_LAUNCH(third_desc_kernel, false, dim3((unsigned)((tiles + 7) / 8 * 8)), f0, f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish,
+                  P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+    return check_launch("third_desc_kernel");
+}
+
 }  // namespace pats
 
 using namespace pats;
+
+extern "C" int pats_set_third_gather(int mode) {
+    const int prev = g_third_gather;
+    if (mode == 0 || mode == 1) g_third_gather = mode;
+    return prev;
+}
 
 extern "C" int pats_fine_descriptors_f32(const float* feat0, const float* feat1, const float* feat2,
                                          const float* title, const float* rubbish, int64_t B,
@@ -754,9 +869,8 @@ extern "C" int pats_third_descriptors_f32(const float* feat_f0, const float* fea
     if (P == 0) return PATS_OK;
     PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors: null pointer");
-    GATHER_LAUNCH(third_desc_kernel, false, dim3((unsigned)((P + 7) / 8 * 8)), feat_f0, feat_f1,
-                       mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P, B, out0, out1, p_s_out, p_t_out, (const int64_t*)nullptr);
-    return check_launch("third_desc_kernel");
+    return launch_third_nchw_f32(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P, nullptr, B, out0, out1, p_s_out,
+                                 p_t_out, stream);
 }
 
 extern "C" int pats_third_descriptors_counted_f32(const float* feat_f0, const float* feat_f1,
@@ -768,9 +882,8 @@ extern "C" int pats_third_descriptors_counted_f32(const float* feat_f0, const fl
     if (P_cap == 0) return PATS_OK;
     PATS_REQUIRE(P_dev && feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors_counted: null pointer");
-    GATHER_LAUNCH(third_desc_kernel, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), feat_f0, feat_f1,
-                       mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-    return check_launch("third_desc_kernel");
+    return launch_third_nchw_f32(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0, out1, p_s_out,
+                                 p_t_out, stream);
 }
 
 extern "C" int pats_fine_descriptors_nhwc_f32(const float* feat0, const float* feat1, const float* feat2,
@@ -860,9 +973,8 @@ extern "C" int pats_third_descriptors_typed(const void* feat_f0, const void* fea
                           kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
             return check_launch("third_desc_nhwc_kernel");
         }
-        GATHER_LAUNCH(third_desc_kernel, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), f0, f1, mkpts0_c, mkpts1_c, b_ids,
-                      kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-        return check_launch("third_desc_kernel");
+        return launch_third_nchw_f32(f0, f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0, out1, p_s_out,
+                                     p_t_out, stream);
     }
     const uint16_t *h0 = (const uint16_t*)feat_f0, *h1 = (const uint16_t*)feat_f1;
     if (channels_last) {

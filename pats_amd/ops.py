@@ -152,6 +152,16 @@ def set_fine_fused(on):
     return bool(_L().pats_set_fine_fused(1 if on else 0))
 
 
+def set_third_gather(mode):
+    """Kernel of the fp32 third-level gather on NCHW maps: "tile" (default, third_desc_kernel: a tile of neighbouring points per
+    workgroup) or "point" (third_desc_point_kernel: one point per workgroup).  Same bits; returns the previous setting."""
+    modes = {"tile": 0, "point": 1}
+    if mode not in modes:
+        raise ValueError("set_third_gather: mode must be 'tile' or 'point'")
+    prev = _L().pats_set_third_gather(modes[mode])
+    return {v: k for k, v in modes.items()}.get(prev, "tile")
+
+
 def sinkhorn_fallbacks(reset=True):
     """Problems on the current device whose linear-domain solve left the guard band and were redone
     with log-sum-exp sweeps since the last reset (pats_sinkhorn_fallbacks; synchronises)."""
