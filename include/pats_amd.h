@@ -691,9 +691,12 @@ int pats_attentional_propagation_packed_f32(const float* x, const float* source,
  * device-side flag; the per-layer compositions queued behind, gated on it, redo the stack (no host read).  PATS_GNN_FINE=0
  * switches the kernel off (both entry points take the round-4 kernels).
  * live (may be NULL): a device-side row count - throughput mode's row total; rows >= clamp(*live - live_off, 0, batch) of both
- * descriptor sets are not processed (their output rows hold whatever the conversion of the inputs left there).
- * pats_attentional_propagation_packed_counted_f32: one packed layer over a capacity with such a count (honoured by the one-kernel
- * layers at the third and the fine level's shapes in eval mode; ignored otherwise). */
+ * descriptor sets are not processed and their output rows are written as zeros (also when the redo chain ran; it copies the live
+ * rows only).
+ * pats_attentional_propagation_packed_counted_f32: one packed layer over a capacity with such a count, honoured by the one-kernel
+ * layers in eval mode - output rows past the count are zeros at the fine level's shape and left untouched at the third level's,
+ * also when the gated composition redoes the call (it computes into the workspace and copies the live rows out); ignored at any
+ * other shape.  bn_train != 0 with a count is refused (PATS_ERR_INVALID, nothing launched). */
 size_t pats_attentional_gnn_packed_workspace_bytes(int64_t batch, int C, int heads, int n);
 int pats_attentional_gnn_packed_f32(const float* desc0, const float* desc1, int64_t batch, const int64_t* live, int64_t live_off,
                                     int C, int heads, int n, int layers,

@@ -671,6 +671,34 @@ int launch_fine_attn(const char* qkv, int64_t shift, char* tf_att, int64_t P, co
                      int64_t live_off);
 int launch_fine_mlp(const char* tf_x, const char* tf_att, int residual, const void* section, char* tf_out, const void* next_section, char* qkv,
                     int64_t P, int* flag, const int* gate, hipStream_t st, int sets, const int64_t* live, int64_t live_off);
+
+// The copy behind a gated redo over a capacity: dst = src for the rows below clamp(*live - live_off, 0, rows) (every row without a
+// count), nothing at all unless *gate != 0.  Rows past the count are NOT copied: the redo computed them from padding inputs, and
+// what the fast path left there (zeros / untouched) must survive it (round-5 advice).
+template <typename T>
+__global__ void __launch_bounds__(256) gated_copy_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t n, const int* __restrict__ gate,
+                                                         int64_t row, const int64_t* __restrict__ live, int64_t live_off) {
+    if (*gate == 0) return;
+    int64_t lim = n;
+    if (live) {
+        int64_t rows = *live - live_off;
+        rows = rows < 0 ? 0 : rows;
+        lim = rows * row < n ? rows * row : n;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < lim; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
+}
+// elems floats in rows of row_elems; 16-byte accesses where both pointers allow them.  max_grid: the launch normally leaves at its
+// gate, so its size is what it costs then.
+static int launch_gated_copy(const float* src, float* dst, size_t elems, int64_t row_elems, const int* gate, const int64_t* live,
+                             int64_t live_off, int64_t max_grid, hipStream_t st) {
+    const bool v4 = ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0 && elems % 4 == 0 && row_elems % 4 == 0;
+    const int64_t n = v4 ? (int64_t)(elems / 4) : (int64_t)elems;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, max_grid));
+    if (v4) hipLaunchKernelGGL((gated_copy_kernel<float4>), dim3(grid), dim3(256), 0, st, (const float4*)src, (float4*)dst, n, gate, row_elems / 4,
+                               live, live_off);
+    else hipLaunchKernelGGL((gated_copy_kernel<float>), dim3(grid), dim3(256), 0, st, src, dst, n, gate, row_elems, live, live_off);
+    return check_launch("gated_copy_kernel");
+}
 }
 
 static int propagation_impl(const float* x, const float* source, int64_t batch, int C, int heads, int n, int m,
@@ -702,13 +730,16 @@ extern "C" int pats_attentional_propagation_packed_f32(const float* x, const flo
 
 // The packed layer over a CAPACITY with the problem count on the device (throughput mode: the third level's P, the fine level's row
 // total): problems >= clamp(*live - live_off, 0, batch) are skipped by the one-kernel layers (third and fine level's shapes, eval
-// mode); their output rows are left untouched.  Any other shape / bn_train: the count is ignored, every problem is computed.
+// mode); their output rows are left untouched (third level) / zeros (fine level: the conversion out writes them), also when the
+// gated composition redoes the call.  Any other shape: the count is ignored, every problem is computed.  bn_train: refused.
 extern "C" int pats_attentional_propagation_packed_counted_f32(const float* x, const float* source, int64_t batch, const int64_t* live,
                                                                int64_t live_off, int C, int heads, int n, int m,
                                                                const pats_propagation_weights* w, const void* packed, int bn_train,
                                                                float bn_eps, const float* residual, float* out, void* workspace,
                                                                size_t workspace_bytes, pats_stream_t stream) {
     PATS_REQUIRE(packed, "attentional_propagation_packed_counted: null packed weights");
+    PATS_REQUIRE(!(live && bn_train), "attentional_propagation_packed_counted: bn_train with a device-side count is not supported "
+                                      "(the batch statistics would take in the rows past the count)");
     return propagation_impl(x, source, batch, C, heads, n, m, w, bn_train, bn_eps, residual, out, workspace, workspace_bytes, stream,
                             packed, nullptr, live, live_off);
 }
@@ -751,6 +782,10 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
     int rc;
     const int* gate = ext_gate;
     if (ext_gate) packed = nullptr;
+    // set when a one-kernel layer below honoured the device-side count: the gated composition behind it runs over the whole
+    // capacity, so it writes into the workspace and only the rows below the count are copied out - the rows past it keep what
+    // the one-kernel layer left there (zeros at the fine level, untouched at the third)
+    bool counted = false;
     if (packed && !bn_train && fine_layer_supported(C, heads, n, m) && gnn_fold_enabled() && !(residual && residual == out)) {
         // The fine level (round 5, gnn_fine.hip): the whole layer in one kernel on (fp32 blocked, TF image) descriptors.  This
         // single-layer entry converts on the way in and out (pats_attentional_gnn_packed_f32 keeps a stack in that form); the
@@ -769,6 +804,7 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
             if ((rc = launch_fine_out(tf_out, batch, out, st, live, live_off, residual && residual != x ? residual : nullptr))) return rc;
             if (deferred) return PATS_OK;
             gate = flag;         // the composition below runs only if the kernel raised it
+            counted = live != nullptr;
         } else if (rc != PATS_ERR_UNSUPPORTED) {
             return rc;
         }
@@ -789,6 +825,7 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
             }
             if (deferred) return PATS_OK;
             gate = flag;         // the composition below runs only if the fused kernel raised it
+            counted = live != nullptr && !bn_train;
         } else if (rc != PATS_ERR_UNSUPPORTED) {
             return rc;
         }
@@ -856,7 +893,11 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
         sc = bsc; sh = bsh;
     }
     // mlp[2] ReLU + mlp[3] Conv1d(2C, C), BN affine + ReLU applied while staging; optional residual (desc + delta, :133)
-    return launch_conv(ConvArgs{w->w2_t, hid, nullptr, 2 * C, 0, C, n, batch * n, sc, sh, w->b2, residual, out}, gate ? nullptr : redo + 5, st, gate);
+    // (counted: into the message buffer - dead once mlp[0] has read it - and the live rows from there)
+    float* const y = counted ? msg : out;
+    if ((rc = launch_conv(ConvArgs{w->w2_t, hid, nullptr, 2 * C, 0, C, n, batch * n, sc, sh, w->b2, residual, y}, gate ? nullptr : redo + 5, st, gate)))
+        return rc;
+    return counted ? launch_gated_copy(y, out, (size_t)batch * C * n, (int64_t)C * n, gate, live, live_off, 256, st) : PATS_OK;
 }
 
 // ---- AttentionalGNN.forward (modules.py:127-134) at the fine level's shape, descriptors kept in the one-kernel layer's own form ----
@@ -867,21 +908,7 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
 // scale / shift given at pack time).  If any layer meets a non-finite value (an activation beyond the fp16 range of the split
 // operands) a device flag is raised and the chain of per-layer compositions queued behind - every kernel gated on that flag -
 // recomputes the whole stack from the inputs.
-namespace pats {
-// (rows past the device-side count are NOT copied: the redo chain recomputes them from padding inputs, and the fast path's contract -
-//  gnn_fine_out_kernel leaves zeros there - must survive a redo; round-5 advice)
-__global__ void __launch_bounds__(256) gated_copy_kernel(const float4* __restrict__ src, float4* __restrict__ dst, int64_t n4, const int* __restrict__ gate,
-                                                         int64_t row4, const int64_t* __restrict__ live, int64_t live_off) {
-    if (*gate == 0) return;
-    int64_t lim = n4;
-    if (live) {
-        int64_t rows = *live - live_off;
-        rows = rows < 0 ? 0 : rows;
-        lim = rows * row4 < n4 ? rows * row4 : n4;
-    }
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < lim; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
-}
-}
+// (the gated copy out leaves rows past the device-side count alone: gnn_fine_out_kernel's zeros survive a redo)
 extern "C" size_t pats_attentional_gnn_packed_workspace_bytes(int64_t batch, int C, int heads, int n) {
     if (batch <= 0 || !fine_layer_supported(C, heads, n, n)) return 0;
     const int64_t P = 2 * batch;
@@ -945,12 +972,8 @@ extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* 
         if ((rc = propagation_impl(c1, s1, batch, C, heads, n, n, weights[l], 0, bn_eps, c1, n1, cws, cws_b, stream, nullptr, flag))) return rc;
         c0 = n0; c1 = n1;
     }
-    const int64_t n4 = (int64_t)(elems / 4);
-    const unsigned cg = (unsigned)std::min<int64_t>((n4 + 255) / 256, 4096);
-    const int64_t row4 = (int64_t)C * n / 4;            // (C n is a multiple of four at the one supported shape: 264 x 145)
-    hipLaunchKernelGGL(gated_copy_kernel, dim3(cg), dim3(256), 0, st, (const float4*)c0, (float4*)out0, n4, (const int*)flag, row4, live, live_off);
-    hipLaunchKernelGGL(gated_copy_kernel, dim3(cg), dim3(256), 0, st, (const float4*)c1, (float4*)out1, n4, (const int*)flag, row4, live, live_off);
-    return check_launch("gated_copy_kernel");
+    if ((rc = launch_gated_copy(c0, out0, elems, (int64_t)C * n, flag, live, live_off, 4096, st))) return rc;
+    return launch_gated_copy(c1, out1, elems, (int64_t)C * n, flag, live, live_off, 4096, st);
 }
 
 // ---- the building blocks on their own: Conv1d(kernel_size = 1) and the BatchNorm1d + ReLU that follows it in MLP ------

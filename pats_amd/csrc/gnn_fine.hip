@@ -256,7 +256,8 @@ gnn_fine_out_kernel(const char* __restrict__ tf, int64_t P, float* __restrict__ 
     const int64_t p = gid / (33 * FN);
     const int r = (int)(gid - p * (33 * FN)), cg = r / FN, tok = r - cg * FN;
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (!live || p < *live - live_off) {
+    const bool on = !live || p < *live - live_off;
+    if (on) {
         const int ks = cg >> 2, kq = cg & 3, t = tok >> 4, j = tok & 15;
         const char* img = tf + p * TF_BYTES;
         const int off = tf_off(ks == 8, t, kq * 16 + j);
@@ -265,7 +266,8 @@ gnn_fine_out_kernel(const char* __restrict__ tf, int64_t P, float* __restrict__ 
         for (int e = 0; e < 8; ++e) v[e] = ((float)hi[e] + (float)lo[e]) * (1.0f / PRE);
     }
     float* d = y + (p * FC + cg * 8) * FN + tok;
-    if (add) {                 // a residual that is neither null nor the layer's own x (the single-layer entry): added here, in fp32
+    if (add && on) {           // a residual that is neither null nor the layer's own x (the single-layer entry): added here, in fp32
+                               // (not to the rows past the count: zeros there whatever the residual)
         const float* a_ = add + (p * FC + cg * 8) * FN + tok;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += a_[e * FN];

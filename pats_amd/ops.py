@@ -1637,7 +1637,14 @@ class PropagationParams:
 def attentional_propagation(x, source, params, heads=4, bn_train=False, residual=None, count=None, out=None, count_off=0):
     """AttentionalPropagation.forward(x, source) (modules.py:114-117) -> delta [b,C,n]; with `residual` (= x in
     AttentionalGNN.forward, :131-133) the sum residual + delta.  bn_train: BatchNorm on batch statistics - what the
-    third layer's GNN does under PATS.eval() (pats.py:112-120).  Six GEMM launches + the attention kernel."""
+    third layer's GNN does under PATS.eval() (pats.py:112-120).  Six GEMM launches + the attention kernel.
+    count: optional device int64 [1]; rows >= clamp(count - count_off, 0, b) are not problems.  Honoured by the one-kernel layers
+    (the fine level's [b, 264, 145] and the third level's [b, 128, 65], eval mode), also when an overflow sends the call to the
+    gated composition: rows past it are zeros (fine) / left untouched (third).  Any other shape: ignored, every row is computed.
+    bn_train with a count is refused (the batch statistics would take in the padding rows)."""
+    if bn_train and count is not None:
+        raise RuntimeError("attentional_propagation: bn_train=True with a device-side count is not supported "
+                           "(the batch statistics would take in the rows past the count)")
     x, source = _dev(x, "x"), _dev(source, "source")
     b, C, n = x.shape
     m = source.shape[2]
@@ -1713,8 +1720,12 @@ def attentional_gnn(desc0, desc1, layers, names, heads=4, bn_train=False, count=
     form (pats_attentional_gnn_packed_f32); any other shape: layer by layer (eval mode: in blocks of GNN_LAYER_ROWS rows - rows are
     independent problems, a cross layer couples row i of one set with row i of the other only).
     count: optional device int64 [1] - only rows < count are problems (throughput mode: the launches cover a capacity); honoured
-    by the one-kernel layers (fine and third level's shapes, eval mode), rows past it are zeros (fine) / left untouched (third).
+    by the one-kernel layers (fine and third level's shapes, eval mode), rows past it are zeros (fine) / left untouched (third),
+    also after an overflow redo; any other shape ignores it.  bn_train with a count is refused.
     out: optional (out0, out1), contiguous float32 GPU tensors shaped like the inputs."""
+    if bn_train and count is not None:
+        raise RuntimeError("attentional_gnn: bn_train=True with a device-side count is not supported "
+                           "(the batch statistics would take in the rows past the count)")
     layers, names = list(layers), list(names)
     desc0, desc1 = _dev(desc0, "desc0"), _dev(desc1, "desc1")
     if out is not None and (len(out) != 2 or any(tuple(o.shape) != tuple(desc0.shape) or not o.is_contiguous() for o in out)):
