@@ -14,6 +14,7 @@
 #include "common.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace pats {
 
@@ -47,15 +48,73 @@ __device__ __forceinline__ f2u ldm2(const float* p) {
     return *q;
 }
 
+// ---- map element types ---------------------------------------------------------------------------------------------------
+// Every kernel takes its maps in one pats_map_dtype_t DT (include/pats_amd.h): float32, or float16 / bfloat16 from a backbone
+// run in half precision, held as their raw 16 bits.  A half element is widened to fp32 EXACTLY at the load (every f16 / bf16
+// value, subnormals, infinities and NaNs included, is a float); from there on every output element is formed by the same
+// operations in the same order - the AvgPool2d(2,1,1) sum (((a + b) + c) + d) / 4, the kenc add, the dustbin column - so the
+// outputs on half maps are the outputs on maps.float(), bit for bit, and stay float32.  Only the access shapes change with the
+// element size: map 0's pooled taps become 4-byte pairs at 2-byte alignment, a third-level window row becomes 16 contiguous
+// bytes (4 lanes x 2 cells instead of 8 lanes x 1 cell), and a 16-byte load of a channels-last pixel carries 8 channels
+// instead of 4 (other lane -> (node, channel) maps, still whole lines per load).  Maps 4-byte aligned (NCHW) / 16-byte aligned
+// (channels-last half maps; channels-last fp32: the fine level 16, the third level 4).
+template <int DT> struct map_elem { using type = uint16_t; };
+template <> struct map_elem<PATS_MAP_F32> { using type = float; };
+template <int DT> using map_t = typename map_elem<DT>::type;
+
+template <int DT>
+__device__ __forceinline__ float widen(uint32_t h) {          // the low 16 bits of h
+    if (DT == PATS_MAP_BF16) return __uint_as_float(h << 16);
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
+}
+template <int DT>
+__device__ __forceinline__ float widen_hi(uint32_t h) {       // the high 16 bits of h
+    if (DT == PATS_MAP_BF16) return __uint_as_float(h & 0xffff0000u);
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(h >> 16));
+}
+// two neighbouring halves as ONE 4-byte access at 2-byte alignment (map 0's pooled taps start at an odd element)
+typedef uint32_t u32u __attribute__((aligned(2)));
+template <int POL>
+__device__ __forceinline__ uint32_t ldh2(const uint16_t* p) {
+    const u32u* q = reinterpret_cast<const u32u*>(p);
+    if (POL & 1) return __builtin_nontemporal_load(q);
+    return *q;
+}
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+typedef float f2s __attribute__((ext_vector_type(2), aligned(4)));
+template <int POL>
+__device__ __forceinline__ void stm2(float* p, f2s v) {      // two neighbouring floats as ONE 8-byte store at 4-byte alignment
+    f2s* q = reinterpret_cast<f2s*>(p);
+    if (POL & 2) __builtin_nontemporal_store(v, q);
+    else *q = v;
+}
+
 // ---- fine level ------------------------------------------------------------------------------
+// the AvgPool2d(2,1,1) sample over the taps q, q + 1 (one pair load) and q + row, q + row + 1             second_layer.py:73-79
+template <int DT, int POL>
+__device__ __forceinline__ float pooled_tap(const map_t<DT>* q, int row) {
+    if constexpr (DT == PATS_MAP_F32) {
+        const f2u a = ldm2<POL>(q), c2 = ldm2<POL>(q + row);
+        return (((a.x + a.y) + c2.x) + c2.y) / 4.0f;
+    } else {
+        const uint32_t a = ldh2<POL>(q), c2 = ldh2<POL>(q + row);
+        return (((widen<DT>(a) + widen_hi<DT>(a)) + widen<DT>(c2)) + widen_hi<DT>(c2)) / 4.0f;
+    }
+}
+template <int DT, int POL>
+__device__ __forceinline__ float single_tap(const map_t<DT>* q) {
+    if constexpr (DT == PATS_MAP_F32) return ldm<POL>(q);
+    else return widen<DT>(ldm<POL>(q));
+}
+
 // One 256-thread workgroup per stacked image n = s * B + b (left crops first).  Wave w takes channels w, w + 4, ...;
 // a lane owns the points l, l + 64, l + 128 (< 145) of every channel it visits, so the source offsets of the three maps are
 // computed ONCE per lane (no division in the channel loop) and a channel's 145 outputs leave as three coalesced stores.
 // The channel loop is split by source (title / map 0 / map 1 / map 2): wave-uniform, branch-free bodies.
-template <int POL>
+template <int DT, int POL>
 __global__ void __launch_bounds__(256)
-fine_desc_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
-                 const float* __restrict__ f2, const float* __restrict__ title,
+fine_desc_kernel(const map_t<DT>* __restrict__ f0, const map_t<DT>* __restrict__ f1,
+                 const map_t<DT>* __restrict__ f2, const float* __restrict__ title,
                  const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
                  const int64_t* __restrict__ B_live) {
     const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
@@ -87,38 +146,65 @@ fine_desc_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
     }
 #pragma unroll 2
     for (int ch = 8 + wave; ch < 72; ch += 4) {                // map 0: [.,64,48,48]
-        const float* m = f0 + (n * 64 + (ch - 8)) * 48 * 48;
+        const map_t<DT>* m = f0 + (n * 64 + (ch - 8)) * 48 * 48;
         float v[3];
 #pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            const float* q = m + off0[g];
-            const f2u a = ldm2<POL>(q), c2 = ldm2<POL>(q + 48);
-            v[g] = (((a.x + a.y) + c2.x) + c2.y) / 4.0f;
-        }
+        for (int g = 0; g < 3; ++g) v[g] = pooled_tap<DT, POL>(m + off0[g], 48);
         put(ch, v[0], v[1], v[2]);
     }
 #pragma unroll 2
     for (int ch = 72 + wave; ch < 136; ch += 4) {              // map 1: [.,64,24,24]
-        const float* m = f1 + (n * 64 + (ch - 72)) * 24 * 24;
+        const map_t<DT>* m = f1 + (n * 64 + (ch - 72)) * 24 * 24;
         float v[3];
 #pragma unroll
-        for (int g = 0; g < 3; ++g) {
-            const float* q = m + off1[g];
-            const f2u a = ldm2<POL>(q), c2 = ldm2<POL>(q + 24);
-            v[g] = (((a.x + a.y) + c2.x) + c2.y) / 4.0f;
-        }
+        for (int g = 0; g < 3; ++g) v[g] = pooled_tap<DT, POL>(m + off1[g], 24);
         put(ch, v[0], v[1], v[2]);
     }
 #pragma unroll 4
     for (int ch = 136 + wave; ch < 264; ch += 4) {             // map 2: [.,128,12,12], no pooling, sample (r, c)
-        const float* m = f2 + (n * 128 + (ch - 136)) * 144;
-        put(ch, ldm<POL>(m + pt[0]), ldm<POL>(m + pt[1]), ldm<POL>(m + pt[2]));
+        const map_t<DT>* m = f2 + (n * 128 + (ch - 136)) * 144;
+        put(ch, single_tap<DT, POL>(m + pt[0]), single_tap<DT, POL>(m + pt[1]), single_tap<DT, POL>(m + pt[2]));
     }
 }
 
 // ---- third level -----------------------------------------------------------------------------
 __device__ __forceinline__ long long round_half_even_div(float x, float d) {
     return (long long)rintf(x / d);      // torch.round = round half to even = rintf in the default mode
+}
+
+// The third-level index arithmetic of every third-level kernel for point p (third_layer.py:124-133, 141-144): the rounded
+// points (written when `write`), the NHWC-view row of window cell (0, 0) of each side, and the dustbin feature's (image, cell).
+struct third_point {
+    long long i00[2], bb2, i2;
+};
+__device__ __forceinline__ third_point third_point_at(const float* __restrict__ mk0, const float* __restrict__ mk1,
+                                                      int64_t p, int64_t b, int64_t B, bool write,
+                                                      int64_t* __restrict__ ps_out, int64_t* __restrict__ pt_out) {
+    constexpr int W = 8, M = 52;
+    // mkpts0_c = round(mkpts0_c / 4) * 4                                                                                 :124
+    const long long s0 = round_half_even_div(mk0[p * 2 + 0], 4.0f) * 4, s1 = round_half_even_div(mk0[p * 2 + 1], 4.0f) * 4;
+    // mkpts1_c clamped to [0, 96] then rounded the same way                                                              :128-130
+    float t0 = mk1[p * 2 + 0], t1 = mk1[p * 2 + 1];
+    t0 = t0 >= 96.f ? 96.f : t0; t1 = t1 >= 96.f ? 96.f : t1;
+    t0 = t0 <= 0.f ? 0.f : t0;   t1 = t1 <= 0.f ? 0.f : t1;
+    const long long q0 = round_half_even_div(t0, 4.0f) * 4, q1 = round_half_even_div(t1, 4.0f) * 4;
+    if (write) {
+        if (ps_out) { ps_out[p * 2] = s0; ps_out[p * 2 + 1] = s1; }
+        if (pt_out) { pt_out[p * 2] = q0; pt_out[p * 2 + 1] = q1; }
+    }
+    auto fdiv2 = [](long long v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };      // python floor division
+    // row of the NHWC view of window cell (0, 0): b M M + (y // 2 - W/2 + 2) M + (x // 2 - W/2 + 2)      :125-127,131-133
+    third_point r;
+    r.i00[0] = b * M * M + (fdiv2(s1) - W / 2 + 2) * M + (fdiv2(s0) - W / 2 + 2);
+    r.i00[1] = b * M * M + (fdiv2(q1) - W / 2 + 2) * M + (fdiv2(q0) - W / 2 + 2);
+    // dustbin feature: rubbish[b, :, y2*12 + x2], x2 = round(mk0x / 8), y2 = round(mk0y / 8)   :141-144
+    // as a row of the flattened [B*144, 128] view, like the reference: cell 11 of a patch (round(92 / 8) = 12) reads the NEXT
+    // patch's feature (PATS itself never sends the border ring here: second_layer.py:140-149,176-184)
+    long long i2 = b * 144 + round_half_even_div((float)s1, 8.0f) * 12 + round_half_even_div((float)s0, 8.0f);
+    i2 = i2 < 0 ? 0 : (i2 > B * 144 - 1 ? B * 144 - 1 : i2);      // memory safety (torch.gather would raise out of range)
+    r.bb2 = i2 / 144;
+    r.i2 = i2 - r.bb2 * 144;
+    return r;
 }
 
 // The per-point kernel (the default until round 7; pats_set_third_gather(1) selects it): one workgroup (256 threads = 4 waves)
@@ -145,34 +231,12 @@ third_desc_point_kernel(const float* __restrict__ ff0, const float* __restrict__
     if ((int64_t)(blockIdx.x >> 3) >= per || p >= live) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t b = b_ids[p];
-    // mkpts0_c = round(mkpts0_c / 4) * 4                                    third_layer.py:124
-    const long long s0 = round_half_even_div(mk0[p * 2 + 0], 4.0f) * 4, s1 = round_half_even_div(mk0[p * 2 + 1], 4.0f) * 4;
-    // mkpts1_c clamped to [0, 96] then rounded the same way                  :128-130
-    float t0 = mk1[p * 2 + 0], t1 = mk1[p * 2 + 1];
-    t0 = t0 >= 96.f ? 96.f : t0; t1 = t1 >= 96.f ? 96.f : t1;
-    t0 = t0 <= 0.f ? 0.f : t0;   t1 = t1 <= 0.f ? 0.f : t1;
-    const long long q0 = round_half_even_div(t0, 4.0f) * 4, q1 = round_half_even_div(t1, 4.0f) * 4;
-    if (threadIdx.x == 0) {
-        if (ps_out) { ps_out[p * 2] = s0; ps_out[p * 2 + 1] = s1; }
-        if (pt_out) { pt_out[p * 2] = q0; pt_out[p * 2 + 1] = q1; }
-    }
+    const third_point tp = third_point_at(mk0, mk1, p, b, B, threadIdx.x == 0, ps_out, pt_out);
     const int wx = lane % W, wy = lane / W;
-    auto fdiv2 = [](long long v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };      // python floor division
-    // x = mk[:,0] // 2 + wx - W/2 + 2 ; y = mk[:,1] // 2 + wy - W/2 + 2     :125-126,131-132
-    long long x0 = fdiv2(s0) + wx - W / 2 + 2, y0 = fdiv2(s1) + wy - W / 2 + 2;
-    long long x1 = fdiv2(q0) + wx - W / 2 + 2, y1 = fdiv2(q1) + wy - W / 2 + 2;
-    long long i0 = b * M * M + y0 * M + x0, i1 = b * M * M + y1 * M + x1;    // :127,133 (rows of the NHWC view)
+    long long i0 = tp.i00[0] + wy * M + wx, i1 = tp.i00[1] + wy * M + wx;       // rows of the NHWC view
     const long long lim = B * M * M - 1;
     i0 = i0 < 0 ? 0 : (i0 > lim ? lim : i0);      // memory safety (torch.gather would raise out of range)
     i1 = i1 < 0 ? 0 : (i1 > lim ? lim : i1);
-    // dustbin feature: rubbish[b, :, y2*12 + x2], x2 = round(mk0x / 8), y2 = round(mk0y / 8)   :141-144
-    // as a row of the flattened [B*144, 128] view, like the reference: cell 11 of a patch (round(92 / 8) = 12) reads the NEXT
-    // patch's feature (PATS itself never sends the border ring here: second_layer.py:140-149,176-184)
-    long long x2 = round_half_even_div((float)s0, 8.0f), y2 = round_half_even_div((float)s1, 8.0f);
-    long long i2 = b * 144 + y2 * 12 + x2;
-    i2 = i2 < 0 ? 0 : (i2 > B * 144 - 1 ? B * 144 - 1 : i2);      // memory safety (torch.gather would raise out of range)
-    const long long bb2 = i2 / 144;
-    i2 -= bb2 * 144;
     // NHWC row index -> (batch, y, x) of the NCHW map
     const long long bb0 = i0 / (M * M), r0 = i0 - bb0 * (M * M);
     const long long bb1 = i1 / (M * M), r1 = i1 - bb1 * (M * M);
@@ -197,291 +261,10 @@ third_desc_point_kernel(const float* __restrict__ ff0, const float* __restrict__
     }
     if (lane < 32) {
         const int ch = 32 * wave + lane;
-        const float rb = rubbish[(bb2 * C + ch) * 144 + i2];
+        const float rb = rubbish[(tp.bb2 * C + ch) * 144 + tp.i2];
         o0[ch * 65 + 64] = rb;                                                   // :145-146
         o1[ch * 65 + 64] = rb;
     }
-}
-
-
-// ---- the same two gathers on CHANNELS-LAST maps ----------------------------------------------------------------------
-// The reference gathers from `feat.permute(0, 2, 3, 1).reshape(-1, C)` (third_layer.py:139-140) and samples single pixels
-// of AvgPool'd maps (second_layer.py:73-79): per-PIXEL reads of all channels.  On the NCHW tensors a torch conv emits by
-// default a pixel's channels lie H*W*4 bytes apart - a third-level window row is 32 bytes of every 208-byte map row (2.75
-// 64-byte HBM granules fetched per 32 bytes used, measured), the stride-4 samples of the 48x48 map touch half of its
-// granules for a sixteenth of its pixels.  A backbone run in torch.channels_last (MIOpen's native layout; the logical
-// shape stays [B,C,H,W]) puts a pixel's channels in ONE contiguous run of 256 / 512 bytes: every granule fetched is
-// used in full.  Lanes then run over channels while the outputs want lanes over nodes ([C, nodes] rows for the MFMA cost
-// builds), so the tile turns through LDS and leaves as one linear, 16-byte-vectorised copy.  Same values, same
-// operation order per element as the NCHW kernels: bit-identical outputs (tests/test_gpu_parity.py).
-
-// one workgroup per (point, side): 64 pixels x 128 channels = 32 KB in, [128, 65] out
-template <int POL>
-__global__ void __launch_bounds__(256)
-third_desc_nhwc_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
-                       const float* __restrict__ mk0, const float* __restrict__ mk1,
-                       const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
-                       const float* __restrict__ rubbish, int64_t P, int64_t B,
-                       float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
-                       int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
-    constexpr int W = 8, M = 52, C = 128, NT = 65;
-    __shared__ __attribute__((aligned(16))) float tile[C * NT];
-    int64_t live = P;
-    if (P_dev) { const int64_t n = *P_dev; live = n < P ? n : P; }
-    // XCD-aware order as in third_desc_kernel; the two sides of a point follow each other on the same XCD (they share
-    // the dustbin feature's lines)
-    const unsigned k = blockIdx.x >> 3;
-    const int side = k & 1;
-    const int64_t per = (live + 7) >> 3, p = (int64_t)(blockIdx.x & 7) * per + (k >> 1);
-    if ((int64_t)(k >> 1) >= per || p >= live) return;
-    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int64_t b = b_ids[p];
-    const long long s0 = round_half_even_div(mk0[p * 2 + 0], 4.0f) * 4, s1 = round_half_even_div(mk0[p * 2 + 1], 4.0f) * 4;   // :124
-    float t0 = mk1[p * 2 + 0], t1 = mk1[p * 2 + 1];                                                                          // :128-130
-    t0 = t0 >= 96.f ? 96.f : t0; t1 = t1 >= 96.f ? 96.f : t1;
-    t0 = t0 <= 0.f ? 0.f : t0;   t1 = t1 <= 0.f ? 0.f : t1;
-    const long long q0 = round_half_even_div(t0, 4.0f) * 4, q1 = round_half_even_div(t1, 4.0f) * 4;
-    if (t == 0 && side == 0) {
-        if (ps_out) { ps_out[p * 2] = s0; ps_out[p * 2 + 1] = s1; }
-        if (pt_out) { pt_out[p * 2] = q0; pt_out[p * 2 + 1] = q1; }
-    }
-    auto fdiv2 = [](long long v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };      // python floor division
-    // row of the NHWC view of window cell (0, 0): b M M + (y // 2 - W/2 + 2) M + (x // 2 - W/2 + 2)      :125-127,131-133
-    const long long i00 = b * M * M + (fdiv2(side ? q1 : s1) - W / 2 + 2) * M + (fdiv2(side ? q0 : s0) - W / 2 + 2);
-    const long long lim = B * M * M - 1;
-    const float* __restrict__ ff = side ? ff1 : ff0;
-    // dustbin feature: rubbish[b, :, y2*12 + x2]                                                           :141-144
-    long long i2 = b * 144 + round_half_even_div((float)s1, 8.0f) * 12 + round_half_even_div((float)s0, 8.0f);
-    i2 = i2 < 0 ? 0 : (i2 > B * 144 - 1 ? B * 144 - 1 : i2);      // a row of the flattened [B*144, 128] view, see third_desc_kernel
-    const long long bb2 = i2 / 144;
-    i2 -= bb2 * 144;
-    float rb = 0.f;
-    if (t < C) rb = rubbish[(bb2 * C + t) * 144 + i2];
-    // wave w brings window cells 16w .. 16w+15, lane l channels l and l + 64 of each: 32 loads of 256 contiguous bytes in flight
-    float v0[16], v1[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        long long i = i00 + (2 * wave + (j >> 3)) * M + (j & 7);
-        i = i < 0 ? 0 : (i > lim ? lim : i);          // memory safety (torch.gather would raise out of range)
-        const float* src = ff + i * C;
-        v0[j] = ldm<POL>(src + lane);
-        v1[j] = ldm<POL>(src + lane + 64);
-    }
-    // + self.kenc(kpts) rides on the way out: element e = c * 65 + n of the output takes kenc[c, n]       :139-140
-    float ke[33];
-#pragma unroll
-    for (int r = 0; r < 33; ++r) {
-        const int e = t + 256 * r, c = e / NT, n = e - c * NT;
-        ke[r] = kenc[(e < C * NT && n < 64) ? c * 64 + n : 0];
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        tile[lane * NT + 16 * wave + j] = v0[j];
-        tile[(lane + 64) * NT + 16 * wave + j] = v1[j];
-    }
-    if (t < C) tile[t * NT + 64] = rb;                                                                      // :145-146
-    wg_barrier();
-    float* o = (side ? out1 : out0) + p * C * NT;
-#pragma unroll
-    for (int r = 0; r < 33; ++r) {
-        const int e = t + 256 * r, c = e / NT, n = e - c * NT;
-        if (e < C * NT) stm<POL>(o + e, n < 64 ? tile[e] + ke[r] : tile[e]);
-    }
-}
-
-// one workgroup per stacked image; the 264 output channels leave in four 64-channel tiles (map 0, map 1, the two halves of
-// map 2), each gathered with 16-byte loads - lane = (node % 4, four channels) - pooled in registers, turned in LDS and
-// copied out as float4.  `cpp` = channels per pixel of the map, `ch0` = first of the 64 channels this pass takes.
-template <int TAPS, int POL>
-__device__ __forceinline__ void fine_tile_pass(const float* __restrict__ img, int cpp, int ch0, int rowpix, int step, int first,
-                                               float* tile, float* __restrict__ o, const float* __restrict__ rub, int t) {
-    constexpr int NP = 145;
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const int lane = t & 63, wave = t >> 6, cg = lane & 15, sub = lane >> 4;
-    constexpr int GR = TAPS == 1 ? 9 : 3;          // node groups per round: 9 or 12 loads of 16 bytes in flight per lane
-    float dust = 0.f;
-    if (t < 64) dust = rub[t];                                                                   // second_layer.py:83,85
-#pragma unroll 1
-    for (int g0 = 0; g0 < 9; g0 += GR) {
-        f4 q[GR][TAPS];
-#pragma unroll
-        for (int g = 0; g < GR; ++g) {
-            const int nd = 16 * (g0 + g) + 4 * wave + sub, r = nd / 12, c = nd - 12 * r;       // positions (k // 12, k % 12)
-            const float* px = img + ((step * r + first) * rowpix + step * c + first) * cpp + ch0 + 4 * cg;
-#pragma unroll
-            for (int tap = 0; tap < TAPS; ++tap)
-                q[g][tap] = ldm<POL>(reinterpret_cast<const f4*>(px + ((tap >> 1) * rowpix + (tap & 1)) * cpp));
-        }
-#pragma unroll
-        for (int g = 0; g < GR; ++g) {
-            const int nd = 16 * (g0 + g) + 4 * wave + sub;
-            f4 v = q[g][0];
-            if (TAPS == 4) v = (((q[g][0] + q[g][1]) + q[g][2]) + q[g][3]) / 4.0f;              // AvgPool2d(2, 1, 1)  :73-79
-            tile[(4 * cg + 0) * NP + nd] = v.x;
-            tile[(4 * cg + 1) * NP + nd] = v.y;
-            tile[(4 * cg + 2) * NP + nd] = v.z;
-            tile[(4 * cg + 3) * NP + nd] = v.w;
-        }
-    }
-    if (t < 64) tile[t * NP + 144] = dust;
-    wg_barrier();
-    const f4* src = reinterpret_cast<const f4*>(tile);
-    f4* dst = reinterpret_cast<f4*>(o);
-    for (int e = t; e < 64 * NP / 4; e += 256) stm<POL>(dst + e, src[e]);
-    wg_barrier();
-}
-
-template <int POL>
-__global__ void __launch_bounds__(256)
-fine_desc_nhwc_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
-                      const float* __restrict__ f2, const float* __restrict__ title,
-                      const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
-                      const int64_t* __restrict__ B_live) {
-    constexpr int NP = 145;
-    __shared__ __attribute__((aligned(16))) float tile[64 * NP];
-    const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
-    const int64_t b = n % B;
-    if (B_live && b >= *B_live) return;        // counted launch: rows past the device-side total are padding
-    const int t = threadIdx.x;
-    float* o = desc + n * 264 * NP;
-    const float* rub = rubbish + b * 264;
-    for (int e = t; e < 8 * NP; e += 256) {                    // the 8-channel "title"                         :82,84
-        const int ch = e / NP, p = e - ch * NP;
-        o[e] = p == 144 ? rub[ch] : title[b * 8 + ch];
-    }
-    // map 0 [.,48,48,64]: avgpool(2,1,1) -> 49x49, sample (4r+2, 4c+2) = mean of pixels (4r+1.., 4c+1..)
-    fine_tile_pass<4, POL>(f0 + n * 48 * 48 * 64, 64, 0, 48, 4, 1, tile, o + 8 * NP, rub + 8, t);
-    // map 1 [.,24,24,64]: avgpool -> 25x25, sample (2r+1, 2c+1) = mean of pixels (2r.., 2c..)
-    fine_tile_pass<4, POL>(f1 + n * 24 * 24 * 64, 64, 0, 24, 2, 0, tile, o + 72 * NP, rub + 72, t);
-    // map 2 [.,12,12,128]: no pooling, sample (r, c)
-    fine_tile_pass<1, POL>(f2 + n * 144 * 128, 128, 0, 12, 1, 0, tile, o + 136 * NP, rub + 136, t);
-    fine_tile_pass<1, POL>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
-}
-
-// ---- the same four gathers on HALF-PRECISION maps (float16 / bfloat16) ---------------------------------------------------
-// A backbone run in bf16 / fp16 hands over maps of 2-byte elements.  Each element is widened to fp32 EXACTLY at the load
-// (every f16 / bf16 value, subnormals, infinities and NaNs included, is a float); from there on every output element is
-// formed by the fp32 kernels' operations in their order - the AvgPool2d(2,1,1) sum (((a + b) + c) + d) / 4, the kenc add,
-// the dustbin column - so the outputs are the fp32 kernels' outputs on maps.float(), bit for bit, and stay float32.  Only
-// the access shapes change with the element size: map 0's pooled taps become 4-byte pairs at 2-byte alignment, a
-// third-level window row becomes 16 contiguous bytes (4 lanes x 2 cells instead of 8 lanes x 1 cell), and a 16-byte load of
-// a channels-last pixel carries 8 channels instead of 4 (new lane -> (node, channel) maps, still whole lines per load).
-// DT = PATS_MAP_F16 or PATS_MAP_BF16 (include/pats_amd.h); maps 4-byte aligned (NCHW) / 16-byte aligned (channels-last).
-template <int DT>
-__device__ __forceinline__ float widen(uint32_t h) {          // the low 16 bits of h
-    if (DT == PATS_MAP_BF16) return __uint_as_float(h << 16);
-    return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
-}
-template <int DT>
-__device__ __forceinline__ float widen_hi(uint32_t h) {       // the high 16 bits of h
-    if (DT == PATS_MAP_BF16) return __uint_as_float(h & 0xffff0000u);
-    return (float)__builtin_bit_cast(_Float16, (uint16_t)(h >> 16));
-}
-// two neighbouring halves as ONE 4-byte access at 2-byte alignment (map 0's pooled taps start at an odd element)
-typedef uint32_t u32u __attribute__((aligned(2)));
-template <int POL>
-__device__ __forceinline__ uint32_t ldh2(const uint16_t* p) {
-    const u32u* q = reinterpret_cast<const u32u*>(p);
-    if (POL & 1) return __builtin_nontemporal_load(q);
-    return *q;
-}
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-typedef float f2s __attribute__((ext_vector_type(2), aligned(4)));
-template <int POL>
-__device__ __forceinline__ void stm2(float* p, f2s v) {      // two neighbouring floats as ONE 8-byte store at 4-byte alignment
-    f2s* q = reinterpret_cast<f2s*>(p);
-    if (POL & 2) __builtin_nontemporal_store(v, q);
-    else *q = v;
-}
-
-// fine level, NCHW: fine_desc_kernel's lane -> point map and channel loops; the taps of a pooled sample are two 4-byte pairs
-template <int DT, int POL>
-__global__ void __launch_bounds__(256)
-fine_desc_half_kernel(const uint16_t* __restrict__ f0, const uint16_t* __restrict__ f1,
-                      const uint16_t* __restrict__ f2, const float* __restrict__ title,
-                      const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
-                      const int64_t* __restrict__ B_live) {
-    const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
-    const int64_t b = n % B;
-    if (B_live && b >= *B_live) return;        // counted launch: rows past the device-side total are padding
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* o = desc + n * 264 * 145;
-    int pt[3], off0[3], off1[3];
-    bool live[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int p = lane + 64 * g;
-        live[g] = p < 145;
-        pt[g] = p < 144 ? p : 0;                               // positions (k // 12, k % 12); the dustbin column reads nothing
-        const int r = pt[g] / 12, c = pt[g] - r * 12;
-        off0[g] = (4 * r + 1) * 48 + 4 * c + 1;                // map 0: avgpool(2,1,1) -> 49x49, sample (4r+2, 4c+2)   :73-79
-        off1[g] = (2 * r) * 24 + 2 * c;                        // map 1: avgpool -> 25x25, sample (2r+1, 2c+1)
-    }
-    const bool dust = lane == 16;                              // group 2 of lane 16 is point 144: the dustbin feature column
-    auto put = [&](int ch, float v0, float v1, float v2) {
-        float* row = o + ch * 145;
-        stm<POL>(row + lane, v0);
-        stm<POL>(row + lane + 64, v1);
-        if (live[2]) stm<POL>(row + lane + 128, dust ? rubbish[b * 264 + ch] : v2);           // second_layer.py:83,85
-    };
-    auto pool = [](uint32_t a, uint32_t c2) {
-        return (((widen<DT>(a) + widen_hi<DT>(a)) + widen<DT>(c2)) + widen_hi<DT>(c2)) / 4.0f;
-    };
-    for (int ch = wave; ch < 8; ch += 4) {                     // the 8-channel "title"                         :82,84
-        const float v = title[b * 8 + ch];
-        put(ch, v, v, v);
-    }
-#pragma unroll 2
-    for (int ch = 8 + wave; ch < 72; ch += 4) {                // map 0: [.,64,48,48]
-        const uint16_t* m = f0 + (n * 64 + (ch - 8)) * 48 * 48;
-        float v[3];
-#pragma unroll
-        for (int g = 0; g < 3; ++g) v[g] = pool(ldh2<POL>(m + off0[g]), ldh2<POL>(m + off0[g] + 48));
-        put(ch, v[0], v[1], v[2]);
-    }
-#pragma unroll 2
-    for (int ch = 72 + wave; ch < 136; ch += 4) {              // map 1: [.,64,24,24]
-        const uint16_t* m = f1 + (n * 64 + (ch - 72)) * 24 * 24;
-        float v[3];
-#pragma unroll
-        for (int g = 0; g < 3; ++g) v[g] = pool(ldh2<POL>(m + off1[g]), ldh2<POL>(m + off1[g] + 24));
-        put(ch, v[0], v[1], v[2]);
-    }
-#pragma unroll 4
-    for (int ch = 136 + wave; ch < 264; ch += 4) {             // map 2: [.,128,12,12], no pooling, sample (r, c)
-        const uint16_t* m = f2 + (n * 128 + (ch - 136)) * 144;
-        put(ch, widen<DT>(ldm<POL>(m + pt[0])), widen<DT>(ldm<POL>(m + pt[1])), widen<DT>(ldm<POL>(m + pt[2])));
-    }
-}
-
-// The third-level index arithmetic of third_desc_kernel / third_desc_nhwc_kernel for point p (third_layer.py:124-133,
-// 141-144): the rounded points (written by thread 0 when side 0), the NHWC-view row of window cell (0, 0) of each side, and
-// the dustbin feature's (image, cell).
-struct third_point {
-    long long i00[2], bb2, i2;
-};
-__device__ __forceinline__ third_point third_point_at(const float* __restrict__ mk0, const float* __restrict__ mk1,
-                                                      int64_t p, int64_t b, int64_t B, bool write,
-                                                      int64_t* __restrict__ ps_out, int64_t* __restrict__ pt_out) {
-    constexpr int W = 8, M = 52;
-    const long long s0 = round_half_even_div(mk0[p * 2 + 0], 4.0f) * 4, s1 = round_half_even_div(mk0[p * 2 + 1], 4.0f) * 4;   // :124
-    float t0 = mk1[p * 2 + 0], t1 = mk1[p * 2 + 1];                                                                          // :128-130
-    t0 = t0 >= 96.f ? 96.f : t0; t1 = t1 >= 96.f ? 96.f : t1;
-    t0 = t0 <= 0.f ? 0.f : t0;   t1 = t1 <= 0.f ? 0.f : t1;
-    const long long q0 = round_half_even_div(t0, 4.0f) * 4, q1 = round_half_even_div(t1, 4.0f) * 4;
-    if (write) {
-        if (ps_out) { ps_out[p * 2] = s0; ps_out[p * 2 + 1] = s1; }
-        if (pt_out) { pt_out[p * 2] = q0; pt_out[p * 2 + 1] = q1; }
-    }
-    auto fdiv2 = [](long long v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };      // python floor division
-    third_point r;
-    r.i00[0] = b * M * M + (fdiv2(s1) - W / 2 + 2) * M + (fdiv2(s0) - W / 2 + 2);     // :125-127,131-133
-    r.i00[1] = b * M * M + (fdiv2(q1) - W / 2 + 2) * M + (fdiv2(q0) - W / 2 + 2);
-    long long i2 = b * 144 + round_half_even_div((float)s1, 8.0f) * 12 + round_half_even_div((float)s0, 8.0f);
-    i2 = i2 < 0 ? 0 : (i2 > B * 144 - 1 ? B * 144 - 1 : i2);      // a row of the flattened [B*144, 128] view, see third_desc_kernel
-    r.bb2 = i2 / 144;
-    r.i2 = i2 - r.bb2 * 144;
-    return r;
 }
 
 constexpr int THIRD_TILE = 8;      // points per workgroup of third_desc_kernel
@@ -574,12 +357,12 @@ third_desc_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
     }
 }
 
-// third level, NCHW: a window row of 8 cells is 16 contiguous bytes of a map row, so a lane takes TWO neighbouring cells as
-// one 4-byte pair - lanes 0..31 one channel's 8x8 window, lanes 32..63 the next channel's - and stores them as one 8-byte
-// write.  A pair starts at an even row i of the NHWC view (s0, q0 are multiples of 4, M is even), so it never straddles two
-// images, and the clamp of third_desc_kernel treats both cells alike: a pair below row 0 reads row 0 twice, one past the
+// third level, NCHW, half maps: a window row of 8 cells is 16 contiguous bytes of a map row, so a lane takes TWO neighbouring
+// cells as one 4-byte pair - lanes 0..31 one channel's 8x8 window, lanes 32..63 the next channel's - and stores them as one
+// 8-byte write.  A pair starts at an even row i of the NHWC view (s0, q0 are multiples of 4, M is even), so it never straddles
+// two images, and the clamp of third_desc_kernel treats both cells alike: a pair below row 0 reads row 0 twice, one past the
 // last row reads the last row twice.  Wave w handles channels 32w .. 32w+31, sixteen at a time (eight pairs per side in
-// flight, then sixteen stores); XCD-aware order and the dustbin column as in third_desc_kernel.
+// flight, then sixteen stores); XCD-aware order and the dustbin column as in third_desc_point_kernel.
 template <int DT, int POL>
 __global__ void __launch_bounds__(256)
 third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restrict__ ff1,
@@ -643,21 +426,34 @@ third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restr
     }
 }
 
-// third level, channels-last: one workgroup per (point, side) as third_desc_nhwc_kernel.  A pixel's 128 channels are 256
-// bytes = 16 lanes x 16 bytes; lane l of wave w loads channels 8 (l / 4) .. +7 of window cells 16 j + 4 w + l % 4 (j < 4):
-// each load instruction reads four whole pixels, and the LDS writes of a half-wave hit 16 banks twice at most.
+
+// ---- the same two gathers on CHANNELS-LAST maps ----------------------------------------------------------------------
+// The reference gathers from `feat.permute(0, 2, 3, 1).reshape(-1, C)` (third_layer.py:139-140) and samples single pixels
+// of AvgPool'd maps (second_layer.py:73-79): per-PIXEL reads of all channels.  On the NCHW tensors a torch conv emits by
+// default a pixel's channels lie H*W*4 bytes apart - a third-level window row is 32 bytes of every 208-byte map row (2.75
+// 64-byte HBM granules fetched per 32 bytes used, measured), the stride-4 samples of the 48x48 map touch half of its
+// granules for a sixteenth of its pixels.  A backbone run in torch.channels_last (MIOpen's native layout; the logical
+// shape stays [B,C,H,W]) puts a pixel's channels in ONE contiguous run of 256 / 512 bytes: every granule fetched is
+// used in full.  Lanes then run over channels while the outputs want lanes over nodes ([C, nodes] rows for the MFMA cost
+// builds), so the tile turns through LDS and leaves as one linear, 16-byte-vectorised copy.  Same values, same
+// operation order per element as the NCHW kernels: bit-identical outputs (tests/test_gpu_parity.py).
+
+// one workgroup per (point, side): 64 pixels x 128 channels in, [128, 65] out.  Only the stage that brings the window into
+// LDS depends on the element type.
 template <int DT, int POL>
 __global__ void __launch_bounds__(256)
-third_desc_nhwc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restrict__ ff1,
-                            const float* __restrict__ mk0, const float* __restrict__ mk1,
-                            const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
-                            const float* __restrict__ rubbish, int64_t P, int64_t B,
-                            float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
-                            int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
+third_desc_nhwc_kernel(const map_t<DT>* __restrict__ ff0, const map_t<DT>* __restrict__ ff1,
+                       const float* __restrict__ mk0, const float* __restrict__ mk1,
+                       const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
+                       const float* __restrict__ rubbish, int64_t P, int64_t B,
+                       float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                       int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
     constexpr int M = 52, C = 128, NT = 65;
     __shared__ __attribute__((aligned(16))) float tile[C * NT];
     int64_t live = P;
     if (P_dev) { const int64_t n = *P_dev; live = n < P ? n : P; }
+    // XCD-aware order as in third_desc_point_kernel; the two sides of a point follow each other on the same XCD (they share
+    // the dustbin feature's lines)
     const unsigned k = blockIdx.x >> 3;
     const int side = k & 1;
     const int64_t per = (live + 7) >> 3, p = (int64_t)(blockIdx.x & 7) * per + (k >> 1);
@@ -666,31 +462,56 @@ third_desc_nhwc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __
     const int64_t b = b_ids[p];
     const third_point tp = third_point_at(mk0, mk1, p, b, B, t == 0 && side == 0, ps_out, pt_out);
     const long long lim = B * M * M - 1;
-    const uint16_t* __restrict__ ff = side ? ff1 : ff0;
+    const map_t<DT>* __restrict__ ff = side ? ff1 : ff0;
     float rb = 0.f;
     if (t < C) rb = rubbish[(tp.bb2 * C + t) * 144 + tp.i2];
+    // the window's registers: fp32 lanes hold channels l and l + 64 of 16 cells, half lanes channels 8 cg .. 8 cg + 7 of 4 cells
     const int cg = lane >> 2;
-    u4 v[4];
+    std::conditional_t<DT == PATS_MAP_F32, float[2][16], u4[4]> v;
+    if constexpr (DT == PATS_MAP_F32) {
+        // wave w brings window cells 16w .. 16w+15, lane l channels l and l + 64 of each: 32 loads of 256 contiguous bytes in flight
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int cell = 16 * j + 4 * wave + (lane & 3);
-        long long i = (side ? tp.i00[1] : tp.i00[0]) + (cell >> 3) * M + (cell & 7);
-        i = i < 0 ? 0 : (i > lim ? lim : i);          // memory safety (torch.gather would raise out of range)
-        v[j] = ldm<POL>(reinterpret_cast<const u4*>(ff + i * C + 8 * cg));
+        for (int j = 0; j < 16; ++j) {
+            long long i = (side ? tp.i00[1] : tp.i00[0]) + (2 * wave + (j >> 3)) * M + (j & 7);
+            i = i < 0 ? 0 : (i > lim ? lim : i);          // memory safety (torch.gather would raise out of range)
+            const float* src = ff + i * C;
+            v[0][j] = ldm<POL>(src + lane);
+            v[1][j] = ldm<POL>(src + lane + 64);
+        }
+    } else {
+        // a pixel's 128 channels are 256 bytes = 16 lanes x 16 bytes; lane l of wave w loads channels 8 (l / 4) .. +7 of window
+        // cells 16 j + 4 w + l % 4 (j < 4): each load instruction reads four whole pixels, and the LDS writes of a half-wave hit
+        // 16 banks twice at most
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int cell = 16 * j + 4 * wave + (lane & 3);
+            long long i = (side ? tp.i00[1] : tp.i00[0]) + (cell >> 3) * M + (cell & 7);
+            i = i < 0 ? 0 : (i > lim ? lim : i);          // memory safety (torch.gather would raise out of range)
+            v[j] = ldm<POL>(reinterpret_cast<const u4*>(ff + i * C + 8 * cg));
+        }
     }
-    float ke[33];                                     // + self.kenc(kpts) rides on the way out, as in third_desc_nhwc_kernel
+    // + self.kenc(kpts) rides on the way out: element e = c * 65 + n of the output takes kenc[c, n]       :139-140
+    float ke[33];
 #pragma unroll
     for (int r = 0; r < 33; ++r) {
         const int e = t + 256 * r, c = e / NT, n = e - c * NT;
         ke[r] = kenc[(e < C * NT && n < 64) ? c * 64 + n : 0];
     }
+    if constexpr (DT == PATS_MAP_F32) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int cell = 16 * j + 4 * wave + (lane & 3);
+        for (int j = 0; j < 16; ++j) {
+            tile[lane * NT + 16 * wave + j] = v[0][j];
+            tile[(lane + 64) * NT + 16 * wave + j] = v[1][j];
+        }
+    } else {
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            tile[(8 * cg + 2 * h) * NT + cell] = widen<DT>(v[j][h]);
-            tile[(8 * cg + 2 * h + 1) * NT + cell] = widen_hi<DT>(v[j][h]);
+        for (int j = 0; j < 4; ++j) {
+            const int cell = 16 * j + 4 * wave + (lane & 3);
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                tile[(8 * cg + 2 * h) * NT + cell] = widen<DT>(v[j][h]);
+                tile[(8 * cg + 2 * h + 1) * NT + cell] = widen_hi<DT>(v[j][h]);
+            }
         }
     }
     if (t < C) tile[t * NT + 64] = rb;                                                                      // :145-146
@@ -703,45 +524,78 @@ third_desc_nhwc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __
     }
 }
 
-// fine level, channels-last: the four 64-channel tiles of fine_desc_nhwc_kernel.  64 half channels of a pixel are 128 bytes
-// = 8 lanes x 16 bytes: lane = (node % 8, eight channels), a wave takes 8 nodes, the workgroup 32 per group, 4.5 groups of
-// the 144 nodes (waves 2 and 3 sit out the last one).  Every load instruction reads 8 whole 128-byte lines.
+// one workgroup per stacked image; the 264 output channels leave in four 64-channel tiles (map 0, map 1, the two halves of
+// map 2), each gathered with 16-byte loads, pooled in registers, turned in LDS and copied out as float4.  `cpp` = channels
+// per pixel of the map, `ch0` = first of the 64 channels this pass takes.  The gather into LDS has one lane map per element
+// size:
+//   fp32  lane = (node % 4, four channels); 9 or 12 loads of 16 bytes in flight per lane
+//   half  64 channels of a pixel are 128 bytes = 8 lanes x 16 bytes: lane = (node % 8, eight channels), a wave takes 8 nodes,
+//         the workgroup 32 per group, 4.5 groups of the 144 nodes (waves 2 and 3 sit out the last one).  Every load
+//         instruction reads 8 whole 128-byte lines.
 template <int DT, int TAPS, int POL>
-__device__ __forceinline__ void fine_tile_pass_half(const uint16_t* __restrict__ img, int cpp, int ch0, int rowpix, int step,
-                                                    int first, float* tile, float* __restrict__ o,
-                                                    const float* __restrict__ rub, int t) {
+__device__ __forceinline__ void fine_tile_pass(const map_t<DT>* __restrict__ img, int cpp, int ch0, int rowpix, int step,
+                                               int first, float* tile, float* __restrict__ o, const float* __restrict__ rub,
+                                               int t) {
     constexpr int NP = 145;
     typedef float f4 __attribute__((ext_vector_type(4)));
-    const int lane = t & 63, wave = t >> 6, cg = lane & 7, sub = lane >> 3;
     float dust = 0.f;
     if (t < 64) dust = rub[t];                                                                   // second_layer.py:83,85
-    u4 q[5][TAPS];
+    if constexpr (DT == PATS_MAP_F32) {
+        const int lane = t & 63, wave = t >> 6, cg = lane & 15, sub = lane >> 4;
+        constexpr int GR = TAPS == 1 ? 9 : 3;          // node groups per round
+#pragma unroll 1
+        for (int g0 = 0; g0 < 9; g0 += GR) {
+            f4 q[GR][TAPS];
 #pragma unroll
-    for (int g = 0; g < 5; ++g) {
-        const int nd = 32 * g + 8 * wave + sub, r = nd / 12, c = nd - 12 * r;                   // positions (k // 12, k % 12)
-        if (g < 4 || wave < 2) {
-            const uint16_t* px = img + ((step * r + first) * rowpix + step * c + first) * cpp + ch0 + 8 * cg;
+            for (int g = 0; g < GR; ++g) {
+                const int nd = 16 * (g0 + g) + 4 * wave + sub, r = nd / 12, c = nd - 12 * r;   // positions (k // 12, k % 12)
+                const float* px = img + ((step * r + first) * rowpix + step * c + first) * cpp + ch0 + 4 * cg;
 #pragma unroll
-            for (int tap = 0; tap < TAPS; ++tap)
-                q[g][tap] = ldm<POL>(reinterpret_cast<const u4*>(px + ((tap >> 1) * rowpix + (tap & 1)) * cpp));
+                for (int tap = 0; tap < TAPS; ++tap)
+                    q[g][tap] = ldm<POL>(reinterpret_cast<const f4*>(px + ((tap >> 1) * rowpix + (tap & 1)) * cpp));
+            }
+#pragma unroll
+            for (int g = 0; g < GR; ++g) {
+                const int nd = 16 * (g0 + g) + 4 * wave + sub;
+                f4 v = q[g][0];
+                if (TAPS == 4) v = (((q[g][0] + q[g][1]) + q[g][2]) + q[g][3]) / 4.0f;          // AvgPool2d(2, 1, 1)  :73-79
+                tile[(4 * cg + 0) * NP + nd] = v.x;
+                tile[(4 * cg + 1) * NP + nd] = v.y;
+                tile[(4 * cg + 2) * NP + nd] = v.z;
+                tile[(4 * cg + 3) * NP + nd] = v.w;
+            }
         }
-    }
+    } else {
+        const int lane = t & 63, wave = t >> 6, cg = lane & 7, sub = lane >> 3;
+        u4 q[5][TAPS];
 #pragma unroll
-    for (int g = 0; g < 5; ++g) {
-        const int nd = 32 * g + 8 * wave + sub;
-        if (g < 4 || wave < 2) {
+        for (int g = 0; g < 5; ++g) {
+            const int nd = 32 * g + 8 * wave + sub, r = nd / 12, c = nd - 12 * r;               // positions (k // 12, k % 12)
+            if (g < 4 || wave < 2) {
+                const uint16_t* px = img + ((step * r + first) * rowpix + step * c + first) * cpp + ch0 + 8 * cg;
 #pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                float v;
-                if (TAPS == 4) {                                                                 // AvgPool2d(2, 1, 1)  :73-79
-                    float x[4];
+                for (int tap = 0; tap < TAPS; ++tap)
+                    q[g][tap] = ldm<POL>(reinterpret_cast<const u4*>(px + ((tap >> 1) * rowpix + (tap & 1)) * cpp));
+            }
+        }
 #pragma unroll
-                    for (int tap = 0; tap < 4; ++tap) x[tap] = h & 1 ? widen_hi<DT>(q[g][tap][h >> 1]) : widen<DT>(q[g][tap][h >> 1]);
-                    v = (((x[0] + x[1]) + x[2]) + x[3]) / 4.0f;
-                } else {
-                    v = h & 1 ? widen_hi<DT>(q[g][0][h >> 1]) : widen<DT>(q[g][0][h >> 1]);
+        for (int g = 0; g < 5; ++g) {
+            const int nd = 32 * g + 8 * wave + sub;
+            if (g < 4 || wave < 2) {
+#pragma unroll
+                for (int h = 0; h < 8; ++h) {
+                    float v;
+                    if (TAPS == 4) {                                                             // AvgPool2d(2, 1, 1)  :73-79
+                        float x[4];
+#pragma unroll
+                        for (int tap = 0; tap < 4; ++tap)
+                            x[tap] = h & 1 ? widen_hi<DT>(q[g][tap][h >> 1]) : widen<DT>(q[g][tap][h >> 1]);
+                        v = (((x[0] + x[1]) + x[2]) + x[3]) / 4.0f;
+                    } else {
+                        v = h & 1 ? widen_hi<DT>(q[g][0][h >> 1]) : widen<DT>(q[g][0][h >> 1]);
+                    }
+                    tile[(8 * cg + h) * NP + nd] = v;
                 }
-                tile[(8 * cg + h) * NP + nd] = v;
             }
         }
     }
@@ -755,10 +609,10 @@ __device__ __forceinline__ void fine_tile_pass_half(const uint16_t* __restrict__
 
 template <int DT, int POL>
 __global__ void __launch_bounds__(256)
-fine_desc_nhwc_half_kernel(const uint16_t* __restrict__ f0, const uint16_t* __restrict__ f1,
-                           const uint16_t* __restrict__ f2, const float* __restrict__ title,
-                           const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
-                           const int64_t* __restrict__ B_live) {
+fine_desc_nhwc_kernel(const map_t<DT>* __restrict__ f0, const map_t<DT>* __restrict__ f1,
+                      const map_t<DT>* __restrict__ f2, const float* __restrict__ title,
+                      const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
+                      const int64_t* __restrict__ B_live) {
     constexpr int NP = 145;
     __shared__ __attribute__((aligned(16))) float tile[64 * NP];
     const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
@@ -771,10 +625,13 @@ fine_desc_nhwc_half_kernel(const uint16_t* __restrict__ f0, const uint16_t* __re
         const int ch = e / NP, p = e - ch * NP;
         o[e] = p == 144 ? rub[ch] : title[b * 8 + ch];
     }
-    fine_tile_pass_half<DT, 4, POL>(f0 + n * 48 * 48 * 64, 64, 0, 48, 4, 1, tile, o + 8 * NP, rub + 8, t);      // map 0
-    fine_tile_pass_half<DT, 4, POL>(f1 + n * 24 * 24 * 64, 64, 0, 24, 2, 0, tile, o + 72 * NP, rub + 72, t);    // map 1
-    fine_tile_pass_half<DT, 1, POL>(f2 + n * 144 * 128, 128, 0, 12, 1, 0, tile, o + 136 * NP, rub + 136, t);    // map 2
-    fine_tile_pass_half<DT, 1, POL>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
+    // map 0 [.,48,48,64]: avgpool(2,1,1) -> 49x49, sample (4r+2, 4c+2) = mean of pixels (4r+1.., 4c+1..)
+    fine_tile_pass<DT, 4, POL>(f0 + n * 48 * 48 * 64, 64, 0, 48, 4, 1, tile, o + 8 * NP, rub + 8, t);
+    // map 1 [.,24,24,64]: avgpool -> 25x25, sample (2r+1, 2c+1) = mean of pixels (2r.., 2c..)
+    fine_tile_pass<DT, 4, POL>(f1 + n * 24 * 24 * 64, 64, 0, 24, 2, 0, tile, o + 72 * NP, rub + 72, t);
+    // map 2 [.,12,12,128]: no pooling, sample (r, c)
+    fine_tile_pass<DT, 1, POL>(f2 + n * 144 * 128, 128, 0, 12, 1, 0, tile, o + 136 * NP, rub + 136, t);
+    fine_tile_pass<DT, 1, POL>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
 }
 
 // PATS_GATHER_NT = 0..3 (see ldm / stm above), read once per process; without it 0 on NCHW maps, 3 on channels-last maps
@@ -782,41 +639,70 @@ static int gather_policy(bool channels_last) {
     static const int pol = [] { const char* e = env_switch("PATS_GATHER_NT"); return e ? (atoi(e) & 3) : -1; }();
     return pol >= 0 ? pol : (channels_last ? 3 : 0);
 }
-#define GATHER_LAUNCH(KERNEL, NHWC, grid, ...)                                                                                \
-    switch (gather_policy(NHWC)) {                                                                                           \
-        case 0: hipLaunchKernelGGL((KERNEL<0>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                  \
-        case 1: hipLaunchKernelGGL((KERNEL<1>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                  \
-        case 2: hipLaunchKernelGGL((KERNEL<2>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                  \
-        default: hipLaunchKernelGGL((KERNEL<3>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;                 \
-    }
-// the half-map kernels, instantiated for f16 and bf16 under the same policies and defaults
-#define GATHER_LAUNCH_HALF(KERNEL, DT, NHWC, grid, ...)                                                                       \
-    switch (gather_policy(NHWC)) {                                                                                           \
-        case 0: hipLaunchKernelGGL((KERNEL<DT, 0>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;              \
-        case 1: hipLaunchKernelGGL((KERNEL<DT, 1>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;              \
-        case 2: hipLaunchKernelGGL((KERNEL<DT, 2>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;              \
-        default: hipLaunchKernelGGL((KERNEL<DT, 3>), grid, dim3(256), 0, as_stream(stream), __VA_ARGS__); break;             \
-    }
-#define GATHER_LAUNCH_TYPED(KERNEL, DTYPE, NHWC, grid, ...)                                                                   \
-    if ((DTYPE) == PATS_MAP_F16) { GATHER_LAUNCH_HALF(KERNEL, PATS_MAP_F16, NHWC, grid, __VA_ARGS__) }                        \
-    else { GATHER_LAUNCH_HALF(KERNEL, PATS_MAP_BF16, NHWC, grid, __VA_ARGS__) }
 
-// The NCHW fp32 third-level gather: the point-tiled third_desc_kernel, or - pats_set_third_gather(1), or outputs that are
-// not 16-byte aligned - third_desc_point_kernel.  Same store policy default as the other NCHW gathers: non-temporal stores
-// measured within 1 % of plain ones here (profiles/r07_third_gather_ab.txt).
-static int g_third_gather = 0;
-static int launch_third_nchw_f32(const float* f0, const float* f1, const float* mkpts0_c, const float* mkpts1_c,
-                                 const int64_t* b_ids, const float* kenc, const float* rubbish, int64_t P_cap, const int64_t* P_dev,
-                                 int64_t B, float* out0, float* out1, int64_t* p_s_out, int64_t* p_t_out, pats_stream_t stream) {
-    if (g_third_gather == 1 || ((uintptr_t)out0 | (uintptr_t)out1) % 16 != 0) {
-        GATHER_LAUNCH(third_desc_point_kernel, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), f0, f1, mkpts0_c, mkpts1_c, b_ids,
-                      kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-        return check_launch("third_desc_point_kernel");
+template <int V> using int_c = std::integral_constant<int, V>;
+// f(int_c<DT>, int_c<POL>) for a pats_map_dtype_t (validated before) and the store policy of the maps' layout
+template <typename F>
+static void with_gather(int dt, bool channels_last, F&& f) {
+    auto pol = [&](auto d) {
+        switch (gather_policy(channels_last)) {
+            case 0: f(d, int_c<0>{}); break;
+            case 1: f(d, int_c<1>{}); break;
+            case 2: f(d, int_c<2>{}); break;
+            default: f(d, int_c<3>{}); break;
+        }
+    };
+    switch (dt) {
+        case PATS_MAP_F16: pol(int_c<PATS_MAP_F16>{}); break;
+        case PATS_MAP_BF16: pol(int_c<PATS_MAP_BF16>{}); break;
+        default: pol(int_c<PATS_MAP_F32>{}); break;
     }
-    const int64_t tiles = (P_cap + THIRD_TILE - 1) / THIRD_TILE;
-    GATHER_LAUNCH(third_desc_kernel, false, dim3((unsigned)((tiles + 7) / 8 * 8)), f0, f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish,
-                  P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-    return check_launch("third_desc_kernel");
+}
+
+// a15 over B stacked-image pairs (2 B workgroups); B_dev: the device-side row count of a counted launch, or null
+static int launch_fine(const void* f0, const void* f1, const void* f2, int dt, bool channels_last, const float* title,
+                       const float* rubbish, int64_t B, const int64_t* B_dev, float* desc, pats_stream_t stream) {
+    with_gather(dt, channels_last, [&](auto d, auto pol) {
+        constexpr int DT = decltype(d)::value, POL = decltype(pol)::value;
+        using T = map_t<DT>;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(2 * B)), dim3(256), 0, as_stream(stream), (const T*)f0, (const T*)f1,
+                               (const T*)f2, title, rubbish, B, desc, B_dev);
+        };
+        if (channels_last) go(fine_desc_nhwc_kernel<DT, POL>);
+        else go(fine_desc_kernel<DT, POL>);
+    });
+    return check_launch(channels_last ? "fine_desc_nhwc_kernel" : "fine_desc_kernel");
+}
+
+// a16 over a capacity of P points; P_dev: the device-side point count, or null.  The NCHW fp32 maps take the point-tiled
+// third_desc_kernel, or - pats_set_third_gather(1), or outputs that are not 16-byte aligned - third_desc_point_kernel.  Same
+// store policy default as the other NCHW gathers: non-temporal stores measured within 1 % of plain ones here
+// (profiles/r07_third_gather_ab.txt).
+static int g_third_gather = 0;
+static int launch_third(const void* f0, const void* f1, int dt, bool channels_last, const float* mkpts0_c,
+                        const float* mkpts1_c, const int64_t* b_ids, const float* kenc, const float* rubbish, int64_t P_cap,
+                        const int64_t* P_dev, int64_t B, float* out0, float* out1, int64_t* p_s_out, int64_t* p_t_out,
+                        pats_stream_t stream) {
+    const char* name = "third_desc_nhwc_kernel";
+    with_gather(dt, channels_last, [&](auto d, auto pol) {
+        constexpr int DT = decltype(d)::value, POL = decltype(pol)::value;
+        using T = map_t<DT>;
+        auto go = [&](auto kernel, const char* kname, int64_t blocks) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const T*)f0, (const T*)f1,
+                               mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+            name = kname;
+        };
+        if (channels_last)
+            go(third_desc_nhwc_kernel<DT, POL>, "third_desc_nhwc_kernel", (P_cap + 7) / 8 * 16);
+        else if constexpr (DT != PATS_MAP_F32)
+            go(third_desc_half_kernel<DT, POL>, "third_desc_half_kernel", (P_cap + 7) / 8 * 8);
+        else if (g_third_gather == 1 || ((uintptr_t)out0 | (uintptr_t)out1) % 16 != 0)
+            go(third_desc_point_kernel<POL>, "third_desc_point_kernel", (P_cap + 7) / 8 * 8);
+        else
+            go(third_desc_kernel<POL>, "third_desc_kernel", ((P_cap + THIRD_TILE - 1) / THIRD_TILE + 7) / 8 * 8);
+    });
+    return check_launch(name);
 }
 
 }  // namespace pats
@@ -835,9 +721,7 @@ extern "C" int pats_fine_descriptors_f32(const float* feat0, const float* feat1,
     PATS_REQUIRE(B >= 0, "fine_descriptors: bad shape");
     if (B == 0) return PATS_OK;
     PATS_REQUIRE(feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors: null pointer");
-    GATHER_LAUNCH(fine_desc_kernel, false, dim3((unsigned)(2 * B)), feat0, feat1,
-                       feat2, title, rubbish, B, desc, (const int64_t*)nullptr);
-    return check_launch("fine_desc_kernel");
+    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, false, title, rubbish, B, nullptr, desc, stream);
 }
 
 // a15 launched over a CAPACITY of B_cap rows with the number of rows in use on the device (throughput mode: the fine level's
@@ -848,16 +732,10 @@ extern "C" int pats_fine_descriptors_counted_f32(const float* feat0, const float
     PATS_REQUIRE(B_cap >= 0, "fine_descriptors_counted: bad shape");
     if (B_cap == 0) return PATS_OK;
     PATS_REQUIRE(B_dev && feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors_counted: null pointer");
-    if (channels_last) {
+    if (channels_last)
         PATS_REQUIRE(((uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)feat2 | (uintptr_t)desc) % 16 == 0,
                      "fine_descriptors_counted: channels-last maps and desc must be 16-byte aligned");
-        GATHER_LAUNCH(fine_desc_nhwc_kernel, true, dim3((unsigned)(2 * B_cap)), feat0, feat1,
-                           feat2, title, rubbish, B_cap, desc, B_dev);
-        return check_launch("fine_desc_nhwc_kernel");
-    }
-    GATHER_LAUNCH(fine_desc_kernel, false, dim3((unsigned)(2 * B_cap)), feat0, feat1,
-                       feat2, title, rubbish, B_cap, desc, B_dev);
-    return check_launch("fine_desc_kernel");
+    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, channels_last, title, rubbish, B_cap, B_dev, desc, stream);
 }
 
 extern "C" int pats_third_descriptors_f32(const float* feat_f0, const float* feat_f1,
@@ -869,8 +747,8 @@ extern "C" int pats_third_descriptors_f32(const float* feat_f0, const float* fea
     if (P == 0) return PATS_OK;
     PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors: null pointer");
-    return launch_third_nchw_f32(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P, nullptr, B, out0, out1, p_s_out,
-                                 p_t_out, stream);
+    return launch_third(feat_f0, feat_f1, PATS_MAP_F32, false, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P, nullptr, B, out0,
+                        out1, p_s_out, p_t_out, stream);
 }
 
 extern "C" int pats_third_descriptors_counted_f32(const float* feat_f0, const float* feat_f1,
@@ -882,8 +760,8 @@ extern "C" int pats_third_descriptors_counted_f32(const float* feat_f0, const fl
     if (P_cap == 0) return PATS_OK;
     PATS_REQUIRE(P_dev && feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors_counted: null pointer");
-    return launch_third_nchw_f32(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0, out1, p_s_out,
-                                 p_t_out, stream);
+    return launch_third(feat_f0, feat_f1, PATS_MAP_F32, false, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
+                        out1, p_s_out, p_t_out, stream);
 }
 
 extern "C" int pats_fine_descriptors_nhwc_f32(const float* feat0, const float* feat1, const float* feat2,
@@ -894,9 +772,7 @@ extern "C" int pats_fine_descriptors_nhwc_f32(const float* feat0, const float* f
     PATS_REQUIRE(feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors_nhwc: null pointer");
     PATS_REQUIRE(((uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)feat2 | (uintptr_t)desc) % 16 == 0,
                  "fine_descriptors_nhwc: maps and desc must be 16-byte aligned");
-    GATHER_LAUNCH(fine_desc_nhwc_kernel, true, dim3((unsigned)(2 * B)), feat0, feat1,
-                       feat2, title, rubbish, B, desc, (const int64_t*)nullptr);
-    return check_launch("fine_desc_nhwc_kernel");
+    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, true, title, rubbish, B, nullptr, desc, stream);
 }
 
 extern "C" int pats_third_descriptors_nhwc_f32(const float* feat_f0, const float* feat_f1,
@@ -908,15 +784,13 @@ extern "C" int pats_third_descriptors_nhwc_f32(const float* feat_f0, const float
     if (P_cap == 0) return PATS_OK;
     PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors_nhwc: null pointer");
-    GATHER_LAUNCH(third_desc_nhwc_kernel, true, dim3((unsigned)((P_cap + 7) / 8 * 16)), feat_f0,
-                       feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-    return check_launch("third_desc_nhwc_kernel");
+    return launch_third(feat_f0, feat_f1, PATS_MAP_F32, true, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
+                        out1, p_s_out, p_t_out, stream);
 }
 
 
-// a15 / a16 on maps of any pats_map_dtype_t, either memory format, with or without the device-side count.  F32 takes the
-// kernels above (the launches of pats_fine_descriptors_*_f32 / pats_third_descriptors_*_f32); F16 / BF16 their half-map twins.
-// Every refusal comes before any launch.
+// a15 / a16 on maps of any pats_map_dtype_t, either memory format, with or without the device-side count.  Every refusal comes
+// before any launch.
 extern "C" int pats_fine_descriptors_typed(const void* feat0, const void* feat1, const void* feat2, pats_map_dtype_t dtype,
                                            int channels_last, const float* title, const float* rubbish, int64_t B_cap,
                                            const int64_t* B_dev, float* desc, pats_stream_t stream) {
@@ -930,23 +804,7 @@ extern "C" int pats_fine_descriptors_typed(const void* feat0, const void* feat1,
         PATS_REQUIRE((maps | (uintptr_t)desc) % 16 == 0, "fine_descriptors_typed: channels-last maps and desc must be 16-byte aligned");
     else                    // 4-byte pair / float loads (f32: 8-byte pairs at 4-byte alignment)
         PATS_REQUIRE(maps % 4 == 0, "fine_descriptors_typed: NCHW maps must be 4-byte aligned");
-    const dim3 grid((unsigned)(2 * B_cap));
-    if (dtype == PATS_MAP_F32) {
-        const float *f0 = (const float*)feat0, *f1 = (const float*)feat1, *f2 = (const float*)feat2;
-        if (channels_last) {
-            GATHER_LAUNCH(fine_desc_nhwc_kernel, true, grid, f0, f1, f2, title, rubbish, B_cap, desc, B_dev);
-            return check_launch("fine_desc_nhwc_kernel");
-        }
-        GATHER_LAUNCH(fine_desc_kernel, false, grid, f0, f1, f2, title, rubbish, B_cap, desc, B_dev);
-        return check_launch("fine_desc_kernel");
-    }
-    const uint16_t *h0 = (const uint16_t*)feat0, *h1 = (const uint16_t*)feat1, *h2 = (const uint16_t*)feat2;
-    if (channels_last) {
-        GATHER_LAUNCH_TYPED(fine_desc_nhwc_half_kernel, dtype, true, grid, h0, h1, h2, title, rubbish, B_cap, desc, B_dev);
-        return check_launch("fine_desc_nhwc_half_kernel");
-    }
-    GATHER_LAUNCH_TYPED(fine_desc_half_kernel, dtype, false, grid, h0, h1, h2, title, rubbish, B_cap, desc, B_dev);
-    return check_launch("fine_desc_half_kernel");
+    return launch_fine(feat0, feat1, feat2, dtype, channels_last, title, rubbish, B_cap, B_dev, desc, stream);
 }
 
 extern "C" int pats_third_descriptors_typed(const void* feat_f0, const void* feat_f1, pats_map_dtype_t dtype, int channels_last,
@@ -966,23 +824,6 @@ extern "C" int pats_third_descriptors_typed(const void* feat_f0, const void* fea
                      dtype == PATS_MAP_F32 ? 4 : 16);
     else                    // 4-byte float / cell-pair loads
         PATS_REQUIRE(maps % 4 == 0, "third_descriptors_typed: NCHW maps must be 4-byte aligned");
-    if (dtype == PATS_MAP_F32) {
-        const float *f0 = (const float*)feat_f0, *f1 = (const float*)feat_f1;
-        if (channels_last) {
-            GATHER_LAUNCH(third_desc_nhwc_kernel, true, dim3((unsigned)((P_cap + 7) / 8 * 16)), f0, f1, mkpts0_c, mkpts1_c, b_ids,
-                          kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-            return check_launch("third_desc_nhwc_kernel");
-        }
-        return launch_third_nchw_f32(f0, f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0, out1, p_s_out,
-                                     p_t_out, stream);
-    }
-    const uint16_t *h0 = (const uint16_t*)feat_f0, *h1 = (const uint16_t*)feat_f1;
-    if (channels_last) {
-        GATHER_LAUNCH_TYPED(third_desc_nhwc_half_kernel, dtype, true, dim3((unsigned)((P_cap + 7) / 8 * 16)), h0, h1, mkpts0_c,
-                            mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-        return check_launch("third_desc_nhwc_half_kernel");
-    }
-    GATHER_LAUNCH_TYPED(third_desc_half_kernel, dtype, false, dim3((unsigned)((P_cap + 7) / 8 * 8)), h0, h1, mkpts0_c, mkpts1_c,
-                        b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
-    return check_launch("third_desc_half_kernel");
+    return launch_third(feat_f0, feat_f1, dtype, channels_last, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
+                        out1, p_s_out, p_t_out, stream);
 }

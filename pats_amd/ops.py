@@ -70,11 +70,10 @@ _MAP_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 def _maps_any(tensors, names):
-    """The maps of ONE gather call in float32, float16 or bfloat16 -> (maps as _map returns them, pats_map_dtype_t code, or
-    None when they are float32 and the _f32 entry points take them exactly as before).  Half maps are widened to fp32 exactly
-    in the kernels; the cases those kernels do not take fall back to .float() copies, which give the same bits: maps of
-    different dtypes in one call, mixed memory formats, and data pointers off the kernels' alignment (4 bytes NCHW,
-    16 bytes channels-last)."""
+    """The maps of ONE gather call in float32, float16 or bfloat16 -> (maps as _map returns them, pats_map_dtype_t code).
+    Half maps are widened to fp32 exactly in the kernels; the cases those kernels do not take fall back to .float() copies,
+    which give the same bits: maps of different dtypes in one call, mixed memory formats, and data pointers off the kernels'
+    alignment (4 bytes NCHW, 16 bytes channels-last)."""
     for t, name in zip(tensors, names):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor" % name)
@@ -82,16 +81,16 @@ def _maps_any(tensors, names):
             raise RuntimeError("pats_amd: %s must be float32, float16 or bfloat16, got %s" % (name, t.dtype))
     dtypes = {t.dtype for t in tensors}
     if dtypes == {torch.float32}:
-        return [_map(t, n) for t, n in zip(tensors, names)], None
+        return [_map(t, n) for t, n in zip(tensors, names)], _MAP_DTYPES[torch.float32]
     if len(dtypes) != 1:
-        return [_map(t.float(), n) for t, n in zip(tensors, names)], None
+        return [_map(t.float(), n) for t, n in zip(tensors, names)], _MAP_DTYPES[torch.float32]
     dt = tensors[0].dtype
     maps = [_map(t, n, dt) for t, n in zip(tensors, names)]
     if len({cl for _, cl in maps}) != 1:
         maps = [(t.contiguous(), False) for t, _ in maps]
     align = 16 if maps[0][1] else 4
     if any(t.data_ptr() % align for t, _ in maps):
-        return [_map(t.float(), n) for t, n in zip(tensors, names)], None
+        return [_map(t.float(), n) for t, n in zip(tensors, names)], _MAP_DTYPES[torch.float32]
     return maps, _MAP_DTYPES[dt]
 
 
@@ -881,18 +880,9 @@ def fine_descriptors(desc0_, title, rubbish, out=None, count=None):
     desc = torch.empty((2, B, 264, 145), dtype=torch.float32, device=f0.device) if out is None else _dev(out, "out")
     if tuple(desc.shape) != (2, B, 264, 145) or (out is not None and desc.data_ptr() != out.data_ptr()):
         raise RuntimeError("fine_descriptors: out must be a contiguous [2,B,264,145] tensor")
-    if dtype is not None:
-        cnt = _dev(count, "count", torch.int64) if count is not None else None
-        _check(_L().pats_fine_descriptors_typed(_ptr(f0), _ptr(f1), _ptr(f2), dtype, int(bool(nhwc)), _ptr(ti), _ptr(ru), B,
-                                                _ptr(cnt), _ptr(desc), _stream()), "fine_descriptors")
-        return desc
-    if count is not None:      # device-side row count: the tensors are a capacity (throughput mode)
-        _check(_L().pats_fine_descriptors_counted_f32(_ptr(f0), _ptr(f1), _ptr(f2), _ptr(ti), _ptr(ru), B,
-                                                      _ptr(_dev(count, "count", torch.int64)), int(bool(nhwc)), _ptr(desc),
-                                                      _stream()), "fine_descriptors")
-        return desc
-    fn = _L().pats_fine_descriptors_nhwc_f32 if nhwc else _L().pats_fine_descriptors_f32
-    _check(fn(_ptr(f0), _ptr(f1), _ptr(f2), _ptr(ti), _ptr(ru), B, _ptr(desc), _stream()), "fine_descriptors")
+    cnt = _dev(count, "count", torch.int64) if count is not None else None      # device-side row count: B is a capacity
+    _check(_L().pats_fine_descriptors_typed(_ptr(f0), _ptr(f1), _ptr(f2), dtype, int(bool(nhwc)), _ptr(ti), _ptr(ru), B,
+                                            _ptr(cnt), _ptr(desc), _stream()), "fine_descriptors")
     return desc
 
 
@@ -927,23 +917,8 @@ def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish
     ps = torch.empty((P, 2), dtype=torch.int64, device=dev)
     pt = torch.empty((P, 2), dtype=torch.int64, device=dev)
     cnt = _dev(count, "count", torch.int64).reshape(1) if count is not None else None
-    if dtype is not None:
-        _check(_L().pats_third_descriptors_typed(_ptr(f0), _ptr(f1), dtype, int(bool(nhwc)), _ptr(m0), _ptr(m1), _ptr(bi),
-                                                 _ptr(ke), _ptr(ru), P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt),
-                                                 _stream()), "third_descriptors")
-        return o0, o1, ps, pt
-    if nhwc:
-        _check(_L().pats_third_descriptors_nhwc_f32(_ptr(f0), _ptr(f1), _ptr(m0), _ptr(m1), _ptr(bi), _ptr(ke), _ptr(ru),
-                                                    P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt), _stream()),
-               "third_descriptors")
-        return o0, o1, ps, pt
-    if count is not None:
-        _check(_L().pats_third_descriptors_counted_f32(_ptr(f0), _ptr(f1), _ptr(m0), _ptr(m1), _ptr(bi), _ptr(ke), _ptr(ru),
-                                                       P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt), _stream()),
-               "third_descriptors")
-        return o0, o1, ps, pt
-    _check(_L().pats_third_descriptors_f32(_ptr(f0), _ptr(f1), _ptr(m0), _ptr(m1), _ptr(bi), _ptr(ke), _ptr(ru),
-                                           P, B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt), _stream()),
+    _check(_L().pats_third_descriptors_typed(_ptr(f0), _ptr(f1), dtype, int(bool(nhwc)), _ptr(m0), _ptr(m1), _ptr(bi), _ptr(ke),
+                                             _ptr(ru), P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt), _stream()),
            "third_descriptors")
     return o0, o1, ps, pt
 
