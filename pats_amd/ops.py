@@ -813,8 +813,23 @@ def Compute_result(scores, W, T, scale_x, scale_y, p_s, p_t, device=None, outdoo
     return m0, m1, wl, label, ifm.bool()
 
 
+def _third_out(out, P, dev):
+    """The four output tensors of third_level: fresh ones, or the caller's `out` checked (if_matching1 as uint8 storage)."""
+    if out is None:
+        return (torch.empty((P, 16, 2), dtype=torch.float32, device=dev), torch.empty((P, 16, 2), dtype=torch.float32, device=dev),
+                torch.empty((P * 16, 2), dtype=torch.float32, device=dev), torch.empty((P, 16), dtype=torch.uint8, device=dev))
+    if len(out) != 4:
+        raise RuntimeError("third_level: out must be (mkpts0_f, mkpts1_f, label, if_matching1)")
+    m0, m1, label = (_dev(t, "out[%d]" % i) for i, t in enumerate(out[:3]))
+    ifm = _as_flags(out[3], "out[3]")
+    shapes = ((P, 16, 2), (P, 16, 2), (P * 16, 2), (P, 16))
+    if any(tuple(t.shape) != s or t.data_ptr() != o.data_ptr() for t, o, s in zip((m0, m1, label, ifm), out, shapes)):
+        raise RuntimeError("third_level: out must be contiguous [P,16,2], [P,16,2], [P*16,2] float32 and [P,16] uint8 / bool tensors")
+    return m0, m1, label, ifm
+
+
 def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdoor=True, iters=100,
-                return_plan=False, count=None):
+                return_plan=False, count=None, out=None):
     """The third layer's whole OT step in one launch (third_layer.py:153-170):
         scale_x = scale_y = sqrt(scale + 1e-8)
         scores  = exp(log_optimal_transport2(0.1 * einsum(f0, f1) / 128**.5, 1, scale, 100))
@@ -822,7 +837,9 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
         label / if_matching1 as :161-170
     Returns (mkpts0_f, mkpts1_f, label, if_matching1[, Z]).  The 65x65 plans stay on chip.
     count: a DEVICE int64 [1] holding the number of problems that exist (throughput mode: the tensors are sized for a
-    capacity, nothing is read back); rows past it are not written, and sqrt(scale + 1e-8) is formed in the kernel."""
+    capacity, nothing is read back); rows past it are not written, and sqrt(scale + 1e-8) is formed in the kernel.
+    out: optional (mkpts0_f [P,16,2], mkpts1_f [P,16,2], label [P*16,2], if_matching1 [P,16] uint8 or bool) to write into; the same
+    four tensors are returned, if_matching1 as it was given."""
     f0, f1 = _dev(feat_f0_unfold, "feat_f0_unfold"), _dev(feat_f1_unfold, "feat_f1_unfold")
     P, D, n = f0.shape
     if n != 65 or tuple(f1.shape) != (P, D, 65):
@@ -835,24 +852,19 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
         if return_plan:
             raise RuntimeError("third_level: return_plan is not available with a device-side count")
         cnt = _dev(count, "count", torch.int64).reshape(1)
-        m0 = torch.empty((P, 16, 2), dtype=torch.float32, device=dev)
-        m1 = torch.empty((P, 16, 2), dtype=torch.float32, device=dev)
-        label = torch.empty((P * 16, 2), dtype=torch.float32, device=dev)
-        ifm = torch.empty((P, 16), dtype=torch.uint8, device=dev)
+        m0, m1, label, ifm = _third_out(out, P, dev)
         _check(_L().pats_third_level_counted_f32(_ptr(f0), _ptr(f1), P, _ptr(cnt), D, _ptr(sc), _ptr(None), _ptr(None), _ptr(ps),
                                                  _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
                                                  _ptr(ifm), _stream()), "third_level")
-        return m0, m1, label, ifm.view(torch.bool)
+        return (m0, m1, label, ifm.view(torch.bool)) if out is None else tuple(out)
     sxy = torch.sqrt(sc + 1e-8)
-    m0 = torch.empty((P, 16, 2), dtype=torch.float32, device=dev)
-    m1 = torch.empty((P, 16, 2), dtype=torch.float32, device=dev)
-    label = torch.empty((P * 16, 2), dtype=torch.float32, device=dev)
-    ifm = torch.empty((P, 16), dtype=torch.uint8, device=dev)
+    m0, m1, label, ifm = _third_out(out, P, dev)
     Z = torch.empty((P, 65, 65), dtype=torch.float32, device=dev) if return_plan else None
     _check(_L().pats_third_level_f32(_ptr(f0), _ptr(f1), P, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps),
                                      _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1),
                                      _ptr(label), _ptr(ifm), _ptr(Z), _stream()), "third_level")
-    return (m0, m1, label, ifm.bool(), Z) if return_plan else (m0, m1, label, ifm.bool())
+    res = (m0, m1, label, ifm.bool()) if out is None else tuple(out)
+    return res + (Z,) if return_plan else res
 
 
 def _widen(t):

@@ -4,7 +4,7 @@
 Draws random shapes / seeds for every op of the path and compares the C-ABI result with
 oracle/pats_oracle.c under the gates of tests/test_gpu_parity.py.  Prints one line per failing case
 (op, seed, shape) and a summary; exit code 1 if anything failed.
-usage: fuzz_parity.py [--seconds 120] [--seed 0] [--ops gnn,gnn_fine,scale,conv,attention,sinkhorn,ot,ot2,cost,expand,resize,merge,result,third]
+usage: fuzz_parity.py [--seconds 120] [--seed 0] [--ops gnn,gnn_fine,scale,conv,attention,sinkhorn,ot,ot2,cost,expand,resize,merge,result,third,third_wild]
 """
 import argparse
 import os
@@ -258,6 +258,58 @@ def op_third(rng):
     return "P=%d D=%d outdoor=%d" % (P, D, outdoor)
 
 
+def op_third_wild(rng):
+    """The third level with about a quarter of the problems beyond the guard band, on both sides of the 6144 workgroups of
+    the redo walk (tests/test_third_redo_walk_gpu.py), with and without a device-side count.  The launch is an index vector
+    into 48 base problems, so the oracle solves 48 problems whatever P is."""
+    from pats_amd import synth
+    K, REDO, NAN_BITS = 48, 0xEE, 0x7FC00000
+    P = int(rng.integers(6145, 13001)) if rng.integers(0, 2) else int(rng.integers(1, 201))
+    inp = synth.third_inputs(seed=int(rng.integers(0, 1 << 30)), P=K)
+    wild = np.sort(rng.permutation(K)[:K // 4])
+    amp = rng.choice([5.0, 9.0, 14.0], size=len(wild)).astype(np.float32)
+    d0, d1 = inp["d0"].copy(), inp["d1"].copy()
+    d0[wild] *= amp[:, None, None]
+    d1[wild] *= amp[:, None, None]
+    idx = rng.permutation(K)[:P] if P <= K else rng.integers(0, K, P)
+    count = int(rng.integers(0, P + 2)) if rng.integers(0, 2) else None
+    live = P if count is None else min(count, P)
+    # reference for the base set; the near-tie mask may leave out 2 % of the wild centre rows at most
+    Zr = oracle.log_optimal_transport2(oracle.cost(d0, d1), 1.0, inp["scale"], 100)
+    sq = np.sqrt(inp["scale"] + np.float32(1e-8)).astype(np.float32)
+    r0, r1, rwl, rlabel, rifm = oracle.compute_result(np.exp(Zr), sq, sq, inp["p_s"], inp["p_t"], True)
+    S = np.exp(Zr)[wild][:, :-1, :].reshape(len(wild), 8, 8, 65)[:, 2:6, 2:6, :].reshape(len(wild), 16, 65)
+    top = np.sort(S, axis=2)[:, :, -2:]
+    clear = (top[:, :, 1] - top[:, :, 0]) > 1e-3 * top[:, :, 1]
+    assert 1.0 - clear.mean() <= 0.02, "near-tie mask leaves out %.1f %% of the wild centre rows" % (100 * (1 - clear.mean()))
+    sel = cu(idx)
+    nan = lambda *s: torch.full(s, NAN_BITS, dtype=torch.int32, device="cuda").view(torch.float32)     # noqa: E731
+    out = (nan(P, 16, 2), nan(P, 16, 2), nan(P * 16, 2), torch.full((P, 16), REDO, dtype=torch.uint8, device="cuda"))
+    ops.third_level(*(torch.index_select(cu(a), 0, sel) for a in (d0, d1, inp["scale"], inp["p_s"], inp["p_t"])), outdoor=True,
+                    out=out, count=None if count is None else torch.tensor([count], dtype=torch.int64, device="cuda"))
+    m0, m1, label, ifm = (t.cpu().numpy() for t in out)
+    label = label.reshape(P, 16, 2)
+    for name, a in (("mkpts0_f", m0), ("mkpts1_f", m1), ("label", label)):
+        assert (a[live:].view(np.uint32) == NAN_BITS).all(), "%s: a row at or past the count was written" % name
+    assert (ifm[live:] == REDO).all(), "if_matching1: a row at or past the count was written"
+    m0, m1, label, ifm, idx = m0[:live], m1[:live], label[:live], ifm[:live], idx[:live]
+    assert set(np.unique(ifm)) <= {0, 1}, "if_matching1 holds %s" % np.unique(ifm)
+    assert np.array_equal(m0, r0[idx])
+    is_wild = np.isin(idx, wild)
+    tame = ~is_wild
+    assert np.array_equal(label[tame], rlabel.reshape(K, 16, 2)[idx[tame]])
+    assert np.array_equal(ifm.astype(bool)[tame], rifm.astype(bool)[idx[tame]])
+    if tame.any():
+        d = np.abs(m1[tame] - r1[idx[tame]]).max()
+        assert d <= 3e-4 * 8, "mkpts1 of a tame problem differs by %g" % d
+    clear_all = np.ones((K, 16), bool)
+    clear_all[wild] = clear
+    ok = clear_all[idx[is_wild]]
+    assert np.array_equal(ifm.astype(bool)[is_wild][ok], rifm.astype(bool)[idx[is_wild]][ok])
+    assert np.isfinite(m1).all() and np.isfinite(label).all()
+    return "P=%d count=%s wild=%d" % (P, count, int(is_wild.sum()))
+
+
 def op_attention(rng):
     pick = rng.integers(0, 4)
     if pick == 0:
@@ -422,7 +474,7 @@ def op_gnn_fine(rng):
 
 
 OPS = {"gnn": op_gnn, "gnn_fine": op_gnn_fine, "scale": op_scale, "conv": op_conv, "attention": op_attention, "sinkhorn": op_sinkhorn, "ot": op_ot, "ot2": op_ot2, "cost": op_cost, "expand": op_expand,
-       "resize": op_resize, "merge": op_merge, "result": op_result, "third": op_third}
+       "resize": op_resize, "merge": op_merge, "result": op_result, "third": op_third, "third_wild": op_third_wild}
 
 
 def main():
