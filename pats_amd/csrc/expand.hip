@@ -239,10 +239,13 @@ expand_kernel(ExpandArgs a) {
     // no rectangle of the wave's four rows reaches adds exact zeros to every accumulator and is skipped as a whole
     const int q16 = 16 / a.w, r16 = 16 - q16 * a.w;
     int pyi = t / a.w, pxi = t - pyi * a.w;
+    // a start cell off the grid (limitation[3] != w) can leave a rectangle that holds NO cell: its centroid and scale are then
+    // the sums of the 1e-14 fill-ins over every cell (:1256-1273), so nothing may be skipped for it
+    const bool no_cell = up > (n - 1) / a.w || left > a.w - 1;
     for (int p = t; p < n; p += 16, pyi += q16, pxi += r16) {
         if (pxi >= a.w) { pxi -= a.w; ++pyi; }
         const bool crit = pyi >= up && pyi <= down && pxi >= left && pxi <= right;
-        if (!__any(crit)) continue;
+        if (!__any(crit || no_cell)) continue;
         const float fx = sx[p], fy = sy[p];
         float ox = ZERO_F, oy = ZERO_F;
         if (crit) {                                                 // the rectangle is a few cells: most passes skip the sqrt and the two divisions

@@ -130,12 +130,16 @@ def op_expand(rng):
     for bi in range(b):
         tgt = rng.integers(0, N, N)
         base[bi, np.arange(N), tgt] += rng.uniform(3, 9, N)
+        # a share of rows whose dustbin entry dominates: the `if_nomatching` branch (whole_cost / core_cost zeroed)
+        dusty = np.nonzero(rng.random(N) < 0.15)[0]
+        base[bi, dusty, N] = base[bi, dusty, :].max(1) + rng.uniform(0.5, 4.0, len(dusty))
     P = np.exp(base - base.max(2, keepdims=True)).astype(np.float32)
     P /= P.sum(2, keepdims=True).astype(np.float32)
     sc = np.exp(rng.uniform(-1.0, 1.0, (b, N))).astype(np.float32)
-    want = oracle.iterative_expand(P, sc, sc, w, h, w, lb, it)                        # lim3 = limitation[3] = w
+    scy = np.exp(rng.uniform(-1.0, 1.0, (b, N))).astype(np.float32)                    # drawn independently of scalex
+    want = oracle.iterative_expand(P, sc, scy, w, h, w, lb, it)                       # lim3 = limitation[3] = w
     positions, ranges = ops.Compute_positions_and_ranges(h, w, "cuda")
-    got = ops.Iterative_expand_matrix(cu(P), cu(sc).reshape(b, -1, 1), cu(sc).reshape(b, -1, 1), [0, h, 0, w], ranges,
+    got = ops.Iterative_expand_matrix(cu(P), cu(sc).reshape(b, -1, 1), cu(scy).reshape(b, -1, 1), [0, h, 0, w], ranges,
                                       positions, lower_bound=lb, iter_num=it, width=w, height=h)
     gb = got[5].cpu().numpy()
     bad_rows = np.argwhere((gb != want[5]).any(-1))
@@ -147,15 +151,17 @@ def op_expand(rng):
         flips = set()
         for _ in range(6):
             Pn = (P * (1.0 + 1e-7 * rng.standard_normal(P.shape))).astype(np.float32)
-            wn = oracle.iterative_expand(Pn, sc, sc, w, h, w, lb, it)[5]
+            wn = oracle.iterative_expand(Pn, sc, scy, w, h, w, lb, it)[5]
             flips |= {tuple(r) for r in np.argwhere((wn != want[5]).any(-1))}
         assert all(tuple(r) in flips for r in bad_rows), "bounds differ (no near-tie)"
         global NEAR_TIES
         NEAR_TIES += len(bad_rows)
         return "near tie"
     np.testing.assert_allclose(got[0].cpu().numpy(), want[0], atol=3e-6, rtol=5e-5)
+    np.testing.assert_allclose(got[1].cpu().numpy(), want[1], atol=3e-6, rtol=5e-4)     # core_cost: test_coarse_level's gate
     np.testing.assert_allclose(got[2].cpu().numpy(), want[2], atol=2e-4, rtol=2e-5)
     np.testing.assert_allclose(got[3].cpu().numpy(), want[3], atol=1e-5, rtol=5e-5)
+    np.testing.assert_allclose(got[4].cpu().numpy(), want[4], atol=1e-5, rtol=5e-5)
     return "b=%d grid %dx%d it=%d lb=%g" % (b, h, w, it, lb)
 
 
