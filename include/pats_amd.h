@@ -350,6 +350,33 @@ int pats_third_descriptors_typed(const void* feat_f0, const void* feat_f1, pats_
                                  const float* rubbish, int64_t P_cap, const int64_t* P_dev, int64_t B, float* out0,
                                  float* out1, int64_t* p_s_out, int64_t* p_t_out, pats_stream_t stream);
 
+/* The cost builds and the descriptor -> plan entry points on DESCRIPTORS of a given element type (pats_map_dtype_t; ABI 8,
+ * new symbols).  Networks run under autocast hand over mdesc0 / mdesc1 and feat_f*_unfold in float16 / bfloat16; the cost
+ * builds widen every element to fp32 EXACTLY at the load (subnormals, signed zeros, infinities, NaNs included) and everything
+ * behind the load is the fp32 code in its order (prescale and fp16 hi + lo split, the MFMA passes, the in-kernel fp32 redo,
+ * `/ sqrt(D)` then `* 0.1`, the solvers and their re-solves, the epilogues).  Every output is float32 / uint8 as for the _f32
+ * entry points and bit-identical to theirs on the widened descriptors.  (Not reproduced: the reference under autocast runs
+ * the einsum itself in half precision.)  scalar, ns, scale* and all outputs stay float32.  PATS_MAP_F32 runs the kernels
+ * the _f32 entry points launch.  Refused before any launch (PATS_ERR_INVALID): an unknown dtype, a NULL pointer, a descriptor
+ * pointer that is not aligned to its element size (all the kernels' loads need).  batch == 0 / P_cap == 0: PATS_OK, no
+ * pointer is looked at.
+ *   pats_cost_typed         pats_cost_f32.
+ *   pats_cost_ot_typed      pats_cost_ot_f32 (col_nomatch == NULL), pats_cost_ot_flags_f32 (col_nomatch, variant 2) and
+ *                           pats_cost_ot_flags_counted_f32 (batch_dev != NULL: fine level only, needs col_nomatch); workspace
+ *                           as pats_cost_ot_workspace_bytes says.  Half descriptors at the fine level always take the
+ *                           two-kernel path (the fused fine-level kernel reads float32 only; same bits).
+ *   pats_third_level_typed  P_dev == NULL: pats_third_level_f32 (scale_x, scale_y required; Z may be NULL);
+ *                           P_dev != NULL: pats_third_level_counted_f32 (scale_x = scale_y = NULL allowed; Z must be NULL). */
+int pats_cost_typed(const void* d0, const void* d1, pats_map_dtype_t dtype, int64_t batch, int D, int n, int m, float* out,
+                    pats_stream_t stream);
+int pats_cost_ot_typed(const void* d0, const void* d1, pats_map_dtype_t dtype, int64_t batch_cap, const int64_t* batch_dev,
+                       int D, int n, int m, int variant, const float* scalar, const float* ns, int iters, float bias_k,
+                       float* Z, uint8_t* col_nomatch, void* workspace, size_t workspace_bytes, pats_stream_t stream);
+int pats_third_level_typed(const void* feat0, const void* feat1, pats_map_dtype_t dtype, int64_t P_cap, const int64_t* P_dev,
+                           int D, const float* scale, const float* scale_x, const float* scale_y, const int64_t* p_s,
+                           const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f, float* label,
+                           uint8_t* if_matching1, float* Z, pats_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * The steps either side of the OT path.  bool tensors are 1 byte, 0 / 1.
  * ---------------------------------------------------------------------------------------- */

@@ -124,6 +124,12 @@ SIGNATURES = {
     "pats_third_level_counted_f32": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
+    # descriptors in any pats_map_dtype_t (0 float32, 1 float16, 2 bfloat16); outputs as the _f32 entries'
+    "pats_cost_typed": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "pats_cost_ot_typed": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_int, c_f, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_third_level_typed": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pats_chunk_rows_workspace_bytes": (c_size, [c_i64, c_int]),
     "pats_chunk_rows_device": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_i64] + [c_void_p] * 13 +
                                [c_size, c_void_p]),

@@ -24,7 +24,8 @@ the caller when it fetches the matches.  Rows of the table that no chunk uses (p
 a network callback may do the same with ops.fine_descriptors(count=...)) and are "no match" at the merge; rows that are left
 without a cell are not compacted (pats.py:40-52) - they emit nothing, exactly as in pipeline.forward_path.
 
-Network callbacks (`nets`, the out-of-scope backbones + heads; they return GPU float32 tensors, no host read required of them -
+Network callbacks (`nets`, the out-of-scope backbones + heads; they return GPU tensors - the descriptors mdesc0 / mdesc1, feat0 / feat1 in float32,
+float16 or bfloat16 (ops.cost_ot / ops.third_level read them as they are), everything else float32 - no host read required of them;
 the backbone maps they gather from with ops.fine_descriptors / ops.third_descriptors may be float16 / bfloat16):
   nets.coarse(lefts, rights) -> mdesc0 [pairs,D,N], mdesc1 [pairs,D,N], scale [pairs,1,N], alpha
   nets.fine(rows, new_left, new_right) -> mdesc0 [rows_cap,264,145], mdesc1, scale_x [rows_cap,1,144], scale_y
@@ -260,6 +261,8 @@ def fine_third_stage(co, nets, cap, if_outdoor=True, merge_new=True, iters=100, 
 def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None):
     """lefts / rights [pairs,H,W,3] HWC, float32 (or float16 / bfloat16 / uint8: nets.coarse gets them as they are, the crops
     widen them exactly).  crop_format: the ops.CropFormat nets.fine receives the crops in (None: float32 HWC).
+    nets.coarse / nets.fine / nets.third may return their descriptors in float32, float16 or bfloat16 (ops.cost_ot / ops.third_level
+    read them as they are: same matches as on .float() copies); scales and points stay float32.
     Returns a dict of DEVICE tensors:
         matches_l, matches_r [M_cap,2]   the first M rows valid, reference order inside every pair (chunk, patch, sub-cell)
         match_row [M_cap] int32          row of the table per match;  rows.row_cell[match_row] // N = pair

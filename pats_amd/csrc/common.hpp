@@ -172,6 +172,31 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
     }
 }
 
+// ---- 2-byte element types of inputs the kernels widen at the load ------------------------------------------------------------
+// float16 is the compiler's _Float16; bfloat16 is held as its raw 16 bits.  Every value of either type is a float, so the
+// widening is exact (subnormals, signed zeros, infinities and NaNs included) and the fp32 code behind the load sees what it
+// would see on `.float()` copies.  Used by the crops (resize.hip: images) and by the cost builds (mfma_tile.hpp,
+// cost65_device.hpp: descriptors).
+struct bf16_t { uint16_t bits; };
+
+template <typename T> __device__ __forceinline__ float widen_px(const T* p) { return (float)*p; }      // float, uint8
+template <> __device__ __forceinline__ float widen_px<_Float16>(const _Float16* p) { return (float)*p; }
+template <> __device__ __forceinline__ float widen_px<bf16_t>(const bf16_t* p) { return __uint_as_float((uint32_t)p->bits << 16); }
+
+
+// f(tag<T>) for the element type a validated pats_map_dtype_t names: the one dtype switch of the typed cost builds
+template <typename T> struct elem_tag { typedef T type; };
+template <class F>
+inline int for_elem_type(int dtype, F&& f) {
+    switch (dtype) {
+        case PATS_MAP_F16: return f(elem_tag<_Float16>{});
+        case PATS_MAP_BF16: return f(elem_tag<bf16_t>{});
+        default: return f(elem_tag<float>{});
+    }
+}
+inline bool known_elem_type(int dtype) { return dtype == PATS_MAP_F32 || dtype == PATS_MAP_F16 || dtype == PATS_MAP_BF16; }
+inline size_t desc_elem_bytes(int dtype) { return dtype == PATS_MAP_F32 ? 4 : 2; }
+
 // raw transcendental units (v_exp_f32 = 2^x, v_log_f32 = log2 x): no denormal range fix-up code.
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }

@@ -34,9 +34,11 @@ struct CostColsT {
 
 }  // namespace
 
-template <bool SPLIT, bool STREAM = false>
+// T: the descriptors' element type (float, _Float16, bf16_t), widened to fp32 at the operand source's loads; <.., float> is
+// the kernel the fp32 entry points always launched
+template <bool SPLIT, bool STREAM = false, typename T = float>
 __global__ void __launch_bounds__(256, 2)
-cost_mfma_kernel(const float* __restrict__ d0, const float* __restrict__ d1, int D, int n, int m,
+cost_mfma_kernel(const T* __restrict__ d0, const T* __restrict__ d1, int D, int n, int m,
                  float rsqrtD, float sqrtD, float* __restrict__ out, const int64_t* __restrict__ live) {
     __shared__ mt::Lds lds;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -47,12 +49,13 @@ cost_mfma_kernel(const float* __restrict__ d0, const float* __restrict__ d1, int
     const int tt = (int)(blockIdx.x - b * tiles);
     const int i0 = (tt / tiles_j) * mt::CT, j0 = (tt % tiles_j) * mt::CT;
     typedef CostColsT<STREAM> CostCols;
+    typedef mt::CmSrc<CostCols, T> Src;
     const CostCols cols{n, m, i0, j0};
-    mt::CmSrc<CostCols> src(d0 + b * (int64_t)D * n, n, d1 + b * (int64_t)D * m, m, D, cols, t);
+    Src src(d0 + b * (int64_t)D * n, n, d1 + b * (int64_t)D * m, m, D, cols, t);
     float* O = out + b * (int64_t)n * m;
 
     mt::f32x16 acc[7];
-    const float unscale = mt::tile<SPLIT, true>(src, (mt::CmSrc<CostCols>*)nullptr, lds, acc, true, t, wave);
+    const float unscale = mt::tile<SPLIT, true>(src, (Src*)nullptr, lds, acc, true, t, wave);
 
     // C/D layout of 32x32: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     auto store_tile = [&](const mt::f32x16& cacc, int ti, int tj) {
@@ -74,27 +77,35 @@ cost_mfma_kernel(const float* __restrict__ d0, const float* __restrict__ d1, int
 
 }  // namespace pats
 
-namespace pats { int launch_cost65(const float*, const float*, int, int64_t, float*, hipStream_t); }
-using namespace pats;
-
 namespace pats {
+template <typename T> int launch_cost65(const T*, const T*, int, int64_t, float*, hipStream_t);      // sinkhorn.hip
 int launch_cost(const float* d0, const float* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
                 const int64_t* live);
+int launch_cost_typed(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, float* out,
+                      pats_stream_t stream, const int64_t* live);
 }
+using namespace pats;
 
 extern "C" int pats_cost_f32(const float* d0, const float* d1, int64_t batch, int D, int n, int m,
                              float* out, pats_stream_t stream) {
     return launch_cost(d0, d1, batch, D, n, m, out, stream, nullptr);
 }
 
+// pats_cost_f32 on descriptors of any pats_map_dtype_t: same kernels, the elements widened to fp32 at the load
+extern "C" int pats_cost_typed(const void* d0, const void* d1, pats_map_dtype_t dtype, int64_t batch, int D, int n, int m,
+                               float* out, pats_stream_t stream) {
+    return launch_cost_typed(d0, d1, (int)dtype, batch, D, n, m, out, stream, nullptr);
+}
+
 // live: optional device-side problem count (<= batch) - the MFMA-tile kernel's workgroups past it return at once
-int pats::launch_cost(const float* d0, const float* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
-                      const int64_t* live) {
+template <typename T>
+static int launch_cost_t(const T* d0, const T* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
+                         const int64_t* live) {
     PATS_REQUIRE(batch >= 0 && D > 0 && n > 0 && m > 0, "cost: bad shape");
     if (batch == 0) return PATS_OK;
     PATS_REQUIRE(d0 && d1 && out, "cost: null pointer");
     if (n == 65 && m == 65 && (D % 32) == 0 && D <= 512)      // third level: one wave per problem, see sinkhorn.hip
-        return launch_cost65(d0, d1, D, batch, out, as_stream(stream));
+        return launch_cost65<T>(d0, d1, D, batch, out, as_stream(stream));
     const int64_t tiles = (int64_t)((n + mt::CT - 1) / mt::CT) * ((m + mt::CT - 1) / mt::CT);
     PATS_REQUIRE(tiles * batch < (1ll << 31), "cost: grid too large (split the call)");
     const bool fp32_only = cost_f32_only();
@@ -102,10 +113,32 @@ int pats::launch_cost(const float* d0, const float* d1, int64_t batch, int D, in
     const dim3 grid((unsigned)(tiles * batch)), block(256);
     static const bool nt = [] { const char* e = diag_env("PATS_COST_NT"); return e && atoi(e) != 0; }();
     if (fp32_only)
-        hipLaunchKernelGGL(cost_mfma_kernel<false>, grid, block, 0, as_stream(stream), d0, d1, D, n, m, 1.0f / sq, sq, out, live);
+        hipLaunchKernelGGL((cost_mfma_kernel<false, false, T>), grid, block, 0, as_stream(stream), d0, d1, D, n, m, 1.0f / sq, sq, out, live);
     else if (nt)
-        hipLaunchKernelGGL((cost_mfma_kernel<true, true>), grid, block, 0, as_stream(stream), d0, d1, D, n, m, 1.0f / sq, sq, out, live);
+        hipLaunchKernelGGL((cost_mfma_kernel<true, true, T>), grid, block, 0, as_stream(stream), d0, d1, D, n, m, 1.0f / sq, sq, out, live);
     else
-        hipLaunchKernelGGL(cost_mfma_kernel<true>, grid, block, 0, as_stream(stream), d0, d1, D, n, m, 1.0f / sq, sq, out, live);
+        hipLaunchKernelGGL((cost_mfma_kernel<true, false, T>), grid, block, 0, as_stream(stream), d0, d1, D, n, m, 1.0f / sq, sq, out, live);
     return check_launch("cost_mfma_kernel");
+}
+
+int pats::launch_cost(const float* d0, const float* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
+                      const int64_t* live) {
+    return launch_cost_t<float>(d0, d1, batch, D, n, m, out, stream, live);
+}
+
+// Descriptors of a pats_map_dtype_t: an unknown dtype and a descriptor pointer off its element size are refused before any
+// launch (the 65-wide build loads a lane's pair of 2-byte elements as one dword at 2-byte alignment, the fp32 build its pair
+// of floats as one 8-byte load at 4-byte alignment: the element size is all either needs)
+int pats::launch_cost_typed(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, float* out,
+                            pats_stream_t stream, const int64_t* live) {
+    PATS_REQUIRE(known_elem_type(dtype), "cost: unknown descriptor dtype %d", dtype);
+    PATS_REQUIRE(batch >= 0 && D > 0 && n > 0 && m > 0, "cost: bad shape");
+    if (batch == 0) return PATS_OK;
+    PATS_REQUIRE(d0 && d1 && out, "cost: null pointer");
+    PATS_REQUIRE((uintptr_t)d0 % desc_elem_bytes(dtype) == 0 && (uintptr_t)d1 % desc_elem_bytes(dtype) == 0,
+                 "cost: descriptors must be aligned to their element size (%d bytes)", (int)desc_elem_bytes(dtype));
+    return for_elem_type(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        return launch_cost_t<T>((const T*)d0, (const T*)d1, batch, D, n, m, out, stream, live);
+    });
 }

@@ -28,8 +28,38 @@ struct Cost65Acc {
 // products; cost65_scale applies the reference's `/ D**.5` then `0.1 *`.
 // `ld` = elements between consecutive descriptor rows (65 for [D,65] descriptors; heads*65 for one
 // head of a [dim,heads,65] attention operand).
-template <bool NO_MFMA = false>     // NO_MFMA: timing ablation only (loads and edge chains stay, the four MFMAs become one add)
-__device__ __forceinline__ void cost65_accumulate(const float* __restrict__ A, const float* __restrict__ B,
+//
+// T = the descriptors' element type.  float: the lane's pair (2 li, 2 li + 1) of a row is one 8-byte load at 4-byte
+// alignment (f2u).  _Float16 / bf16_t (common.hpp): a [D,65] descriptor has 130-byte rows, so the pair of an odd row is only
+// 2-byte aligned; it is ONE 4-byte load declared at 2-byte alignment (Pair65<T>::raw - hipcc emits a single
+// global_load_dword for it on gfx950, whose global loads take any alignment: docs/kernels.md has the instruction counts),
+// held as its raw 32 bits in the prefetch ring (half the ring's registers) and widened to the two floats it stands for -
+// exactly - where the fp32 build reads its pair.  The dustbin column is a plain typed load.  Everything behind the widening
+// is the fp32 code, in its order.
+typedef unsigned u1u __attribute__((aligned(2)));
+template <typename T> struct Pair65;
+template <> struct Pair65<float> {
+    typedef f2u raw;
+    static __device__ __forceinline__ raw load(const float* p) { return *reinterpret_cast<const f2u*>(p); }
+    static __device__ __forceinline__ f2u widen(raw v) { return v; }
+};
+template <> struct Pair65<_Float16> {
+    typedef unsigned raw;
+    static __device__ __forceinline__ raw load(const _Float16* p) { return *reinterpret_cast<const u1u*>(p); }
+    static __device__ __forceinline__ f2u widen(raw v) {
+        typedef _Float16 h2w __attribute__((ext_vector_type(2)));
+        const h2w h = __builtin_bit_cast(h2w, v);
+        return f2u{(float)h.x, (float)h.y};
+    }
+};
+template <> struct Pair65<bf16_t> {
+    typedef unsigned raw;
+    static __device__ __forceinline__ raw load(const bf16_t* p) { return *reinterpret_cast<const u1u*>(p); }
+    static __device__ __forceinline__ f2u widen(raw v) { return f2u{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)}; }
+};
+
+template <bool NO_MFMA = false, typename T = float>     // NO_MFMA: timing ablation only (loads and edge chains stay, the four MFMAs become one add)
+__device__ __forceinline__ void cost65_accumulate(const T* __restrict__ A, const T* __restrict__ B,
                                                   int D, float* edge_lds, int lane, Cost65Acc& o,
                                                   int ld = C65_NT) {
     const int li = lane & 31, lk = lane >> 5;
@@ -41,28 +71,29 @@ __device__ __forceinline__ void cost65_accumulate(const float* __restrict__ A, c
     float* eA = edge_lds;
     float* eB = edge_lds + 512;
     for (int k = lane; k < D; k += 64) {
-        eA[k] = A[k * ld + NB];
-        eB[k] = B[k * ld + NB];
+        eA[k] = widen_px(&A[k * ld + NB]);
+        eB[k] = widen_px(&B[k * ld + NB]);
     }
-    const float* pa = A + lk * ld + 2 * li;
-    const float* pb = B + lk * ld + 2 * li;
+    const T* pa = A + lk * ld + 2 * li;
+    const T* pb = B + lk * ld + 2 * li;
     // explicit software pipeline over blocks of KB = 4 k-steps (8 descriptor rows): a ring of four
     // named register buffers keeps three blocks of loads in flight ahead of the MFMAs (deeper rings
     // were measured slower: the phase is HBM-bandwidth-bound, and the extra registers spill)
     constexpr int KB = 4;
-    struct Blk { f2u a[KB], b[KB]; };
+    typedef Pair65<T> Pair;
+    struct Blk { typename Pair::raw a[KB], b[KB]; };
     auto load_blk = [&](int k0, Blk& q) {
 #pragma unroll
         for (int s_ = 0; s_ < KB; ++s_) {
             const int k = k0 + 2 * s_;                    // D % 32 == 0: whole rings only
-            q.a[s_] = *reinterpret_cast<const f2u*>(pa + k * ld);
-            q.b[s_] = *reinterpret_cast<const f2u*>(pb + k * ld);
+            q.a[s_] = Pair::load(pa + k * ld);
+            q.b[s_] = Pair::load(pb + k * ld);
         }
     };
     auto compute_blk = [&](int k0, const Blk& q) {
 #pragma unroll
         for (int s_ = 0; s_ < KB; ++s_) {
-            const f2u av = q.a[s_], bv = q.b[s_];
+            const f2u av = Pair::widen(q.a[s_]), bv = Pair::widen(q.b[s_]);
             const float ea = eA[k0 + 2 * s_ + lk], eb = eB[k0 + 2 * s_ + lk];
             if (NO_MFMA) {
                 c00[s_ & 15] += av.x * bv.x + av.y * bv.y;
@@ -234,12 +265,12 @@ struct Cost65Scale {
 __device__ __forceinline__ float cost65_scale(float x, const Cost65Scale& k) { return 0.1f * div_invariant(x, k.d, k.rd); }
 
 // accumulate + write the scaled 65x65 matrix into a row-major LDS tile (row stride 65)
-template <bool F16 = false>
-__device__ __forceinline__ void cost65_to_tile(const float* __restrict__ A, const float* __restrict__ B,
+template <bool F16 = false, typename T = float>
+__device__ __forceinline__ void cost65_to_tile(const T* __restrict__ A, const T* __restrict__ B,
                                                int D, float* tile, int lane) {
     constexpr int NT = C65_NT, NB = C65_NB;
     Cost65Acc c;
-    if (F16) cost65_accumulate_f16x2(A, B, D, tile, lane, c);
+    if constexpr (F16) cost65_accumulate_f16x2(A, B, D, tile, lane, c);      // diagnostic builds, float descriptors only
     else cost65_accumulate(A, B, D, tile, lane, c);
     const int li = lane & 31, lk = lane >> 5;
     const Cost65Scale sq(D);

@@ -8,7 +8,7 @@
 using namespace pats;
 
 namespace pats {
-int launch_cost_ot65(const float*, const float*, int64_t, int, const float*, const float*, int, float, float*,
+int launch_cost_ot65(const void*, const void*, int dtype, int64_t, int, const float*, const float*, int, float, float*,
                      pats_stream_t);
 int launch_col_flags(const float* Z, int64_t batch, int M, int N, uint8_t* col_nomatch, const int* only_if,
                      hipStream_t st);
@@ -20,6 +20,8 @@ int launch_fine145_fused(const float* d0, const float* d1, int D, int64_t batch,
                          const int64_t* live);
 int launch_cost(const float* d0, const float* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
                 const int64_t* live);
+int launch_cost_typed(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, float* out,
+                      pats_stream_t stream, const int64_t* live);
 int ot2_flags_live(const float* scores, int64_t batch, int m, int n, const float* one, const float* ns, int iters, float bias_k,
                    float* Z, uint8_t* col_nomatch, void* workspace, size_t workspace_bytes, pats_stream_t stream,
                    const int64_t* live);
@@ -43,7 +45,8 @@ extern "C" size_t pats_cost_ot_workspace_bytes(int64_t batch, int D, int n, int 
     return scores + (variant == 1 ? pats_ot_workspace_bytes(batch, M, N) : pats_ot2_workspace_bytes(batch, M, N));
 }
 
-static int cost_ot_impl(const float* d0, const float* d1, int64_t batch, int D, int n, int m, int variant,
+// d0 / d1: descriptors of `dtype` elements (pats_map_dtype_t)
+static int cost_ot_impl(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, int variant,
                         const float* scalar, const float* ns, int iters, float bias_k, float* Z, uint8_t* col_nomatch,
                         void* workspace, size_t workspace_bytes, pats_stream_t stream, const int64_t* live = nullptr);
 
@@ -51,7 +54,7 @@ extern "C" int pats_cost_ot_f32(const float* d0, const float* d1, int64_t batch,
                                 int variant, const float* scalar, const float* ns, int iters,
                                 float bias_k, float* Z, void* workspace, size_t workspace_bytes,
                                 pats_stream_t stream) {
-    return cost_ot_impl(d0, d1, batch, D, n, m, variant, scalar, ns, iters, bias_k, Z, nullptr, workspace,
+    return cost_ot_impl(d0, d1, PATS_MAP_F32, batch, D, n, m, variant, scalar, ns, iters, bias_k, Z, nullptr, workspace,
                         workspace_bytes, stream);
 }
 
@@ -62,7 +65,7 @@ extern "C" int pats_cost_ot_flags_f32(const float* d0, const float* d1, int64_t 
                                       size_t workspace_bytes, pats_stream_t stream) {
     PATS_REQUIRE(variant == 2, "cost_ot_flags: column flags come from the log_optimal_transport2 epilogue (variant 2); "
                                "for variant 1 use pats_colmass_flags_f32, which the coarse level needs anyway");
-    return cost_ot_impl(d0, d1, batch, D, n, m, variant, scalar, ns, iters, bias_k, Z, col_nomatch, workspace,
+    return cost_ot_impl(d0, d1, PATS_MAP_F32, batch, D, n, m, variant, scalar, ns, iters, bias_k, Z, col_nomatch, workspace,
                         workspace_bytes, stream);
 }
 
@@ -75,11 +78,31 @@ extern "C" int pats_cost_ot_flags_counted_f32(const float* d0, const float* d1, 
                                               size_t workspace_bytes, pats_stream_t stream) {
     PATS_REQUIRE(variant == 2 && n == 145 && m == 145, "cost_ot_flags_counted: the fine level only (variant 2, 145 x 145)");
     PATS_REQUIRE(batch_dev, "cost_ot_flags_counted: null count");
-    return cost_ot_impl(d0, d1, batch_cap, D, n, m, variant, scalar, ns, iters, bias_k, Z, col_nomatch, workspace,
+    return cost_ot_impl(d0, d1, PATS_MAP_F32, batch_cap, D, n, m, variant, scalar, ns, iters, bias_k, Z, col_nomatch, workspace,
                         workspace_bytes, stream, batch_dev);
 }
 
-static int cost_ot_impl(const float* d0, const float* d1, int64_t batch, int D, int n, int m, int variant,
+// The three entries above in one, on descriptors of any pats_map_dtype_t (widened to fp32 at the cost build's loads: same
+// bits as on .float() copies).  col_nomatch (nullable): the variant-2 column flags; batch_dev (nullable): the fine level's
+// device-side row count.  Half descriptors at the fine level take the two-kernel path whatever pats_set_fine_fused says.
+extern "C" int pats_cost_ot_typed(const void* d0, const void* d1, pats_map_dtype_t dtype, int64_t batch_cap,
+                                  const int64_t* batch_dev, int D, int n, int m, int variant, const float* scalar,
+                                  const float* ns, int iters, float bias_k, float* Z, uint8_t* col_nomatch, void* workspace,
+                                  size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(known_elem_type((int)dtype), "cost_ot_typed: unknown descriptor dtype %d", (int)dtype);
+    PATS_REQUIRE(!col_nomatch || variant == 2, "cost_ot_typed: column flags come from the log_optimal_transport2 epilogue (variant 2)");
+    PATS_REQUIRE(!batch_dev || (variant == 2 && n == 145 && m == 145 && col_nomatch),
+                 "cost_ot_typed: a device-side count is taken at the fine level only (variant 2, 145 x 145, with column flags)");
+    if (batch_cap > 0) {
+        PATS_REQUIRE(d0 && d1 && ns && Z, "cost_ot_typed: null pointer");
+        PATS_REQUIRE((uintptr_t)d0 % desc_elem_bytes((int)dtype) == 0 && (uintptr_t)d1 % desc_elem_bytes((int)dtype) == 0,
+                     "cost_ot_typed: descriptors must be aligned to their element size (%d bytes)", (int)desc_elem_bytes((int)dtype));
+    }
+    return cost_ot_impl(d0, d1, (int)dtype, batch_cap, D, n, m, variant, scalar, ns, iters, bias_k, Z, col_nomatch, workspace,
+                        workspace_bytes, stream, batch_dev);
+}
+
+static int cost_ot_impl(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, int variant,
                         const float* scalar, const float* ns, int iters, float bias_k, float* Z, uint8_t* col_nomatch,
                         void* workspace, size_t workspace_bytes, pats_stream_t stream, const int64_t* live) {
     // the handle is consumed by THIS call whatever path it takes (fused kernel, 65-wide kernel, an error): left armed it would be
@@ -91,7 +114,7 @@ static int cost_ot_impl(const float* d0, const float* d1, int64_t batch, int D, 
     if (batch == 0) return PATS_OK;
     if (variant == 2 && n == 65 && m == 65 && (D % 32) == 0 && D <= 512) {
         PATS_REQUIRE(d0 && d1 && ns && Z, "cost_ot: null pointer");
-        int rc = launch_cost_ot65(d0, d1, batch, D, scalar, ns, iters, bias_k, Z, stream);
+        int rc = launch_cost_ot65(d0, d1, dtype, batch, D, scalar, ns, iters, bias_k, Z, stream);
         if (!rc && col_nomatch) rc = launch_col_flags(Z, batch, n, m, col_nomatch, nullptr, (hipStream_t)stream);
         return rc;
     }
@@ -100,16 +123,19 @@ static int cost_ot_impl(const float* d0, const float* d1, int64_t batch, int D, 
     float* scores = (float*)workspace;
     const size_t off = align256((size_t)batch * n * m * sizeof(float));
     void* ws2 = (char*)workspace + off;
-    if (variant == 2 && n == 145 && m == 145) {
+    if (variant == 2 && n == 145 && m == 145 && dtype == PATS_MAP_F32) {
         // the fine level: cost build and OT in ONE kernel, the score matrix never reaches HBM (sinkhorn_blk.hip, FUSED);
-        // the guard flags sit where the unfused path keeps them
+        // the guard flags sit where the unfused path keeps them.  (float32 descriptors only: half ones take the two kernels
+        // below, which the fused kernel is held to bit for bit.)
         PATS_REQUIRE(d0 && d1 && ns && Z, "cost_ot: null pointer");
         bool applied = false;
-        int rc = launch_fine145_fused(d0, d1, D, batch, ns, scalar, iters, bias_k, Z, (int*)ws2, col_nomatch, (hipStream_t)stream,
+        int rc = launch_fine145_fused((const float*)d0, (const float*)d1, D, batch, ns, scalar, iters, bias_k, Z, (int*)ws2, col_nomatch, (hipStream_t)stream,
                                       &applied, live);
         if (rc || applied) return rc;
     }
-    int rc = launch_cost(d0, d1, batch, D, n, m, scores, stream, live);
+    // float32: the call the _f32 entries always made; half types: validated by pats_cost_ot_typed
+    int rc = dtype == PATS_MAP_F32 ? launch_cost((const float*)d0, (const float*)d1, batch, D, n, m, scores, stream, live)
+                                   : launch_cost_typed(d0, d1, dtype, batch, D, n, m, scores, stream, live);
     if (rc) return rc;
     if (mid_event && hipEventRecord(mid_event, (hipStream_t)stream) != hipSuccess) return check_launch("cost_ot mid event");
     if (variant == 1) {

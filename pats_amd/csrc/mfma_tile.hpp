@@ -239,16 +239,25 @@ __device__ __forceinline__ bool split_finite(const Src& src, const f32x16 (&acc)
 // A[cols.a_off(c) + k * ldA], of side B  B[cols.b_off(c) + k * ldB]; optionally x <- max(0, x * scale[k] + shift[k]) on
 // side B while staging.  `Cols` also says which tile rows / columns are stored.  Running pointers, advanced per chunk;
 // only a ragged last chunk takes the zero-filling fetch (a valid channel is read, then zeroed: no predicated loads).
-template <class Cols>
+// T = element type of both operands: float, or _Float16 / bf16_t (common.hpp) widened to fp32 exactly at the load - the two
+// fetches are the only code that sees T; what they hand to the split and to the fp32 slabs is the float the operand stands for.
+template <bool STREAM, typename T>
+__device__ __forceinline__ float cm_load(const T* p) {
+    if constexpr (!STREAM) return widen_px(p);
+    else if constexpr (__is_same(T, bf16_t)) return __uint_as_float((uint32_t)__builtin_nontemporal_load(&p->bits) << 16);
+    else return (float)__builtin_nontemporal_load(p);
+}
+
+template <class Cols, typename T = float>
 struct CmSrc {
-    const float *A, *B;
+    const T *A, *B;
     int ldA, ldB, K, t;
     const Cols& cols;
     const float *scale, *shift;
-    const float* p[SQ];                // split items, or side-A slab elements of the fp32 path
-    const float* pq[CPT];              // side-B slab elements of the fp32 path
+    const T* p[SQ];                    // split items, or side-A slab elements of the fp32 path
+    const T* pq[CPT];                  // side-B slab elements of the fp32 path
 
-    __device__ __forceinline__ CmSrc(const float* A_, int ldA_, const float* B_, int ldB_, int K_, const Cols& c, int t_,
+    __device__ __forceinline__ CmSrc(const T* A_, int ldA_, const T* B_, int ldB_, int K_, const Cols& c, int t_,
                                      const float* scale_ = nullptr, const float* shift_ = nullptr)
         : A(A_), B(B_), ldA(ldA_), ldB(ldB_), K(K_), t(t_), cols(c), scale(scale_), shift(shift_) {}
     __device__ __forceinline__ bool row_stored(int r) const { return cols.row_stored(r); }
@@ -267,8 +276,8 @@ struct CmSrc {
         for (int q = 0; q < CPT; ++q) {
             const int k = k0 + f32_row(t, q);
             const bool kin = k0 + KC <= K || k < K;
-            ra[q] = kin ? *p[q] : 0.f;
-            float x = kin ? *pq[q] : 0.f;
+            ra[q] = kin ? widen_px(p[q]) : 0.f;
+            float x = kin ? widen_px(pq[q]) : 0.f;
             if (scale && kin) x = affine(x, k);
             rb[q] = x;
             p[q] += (int64_t)KC * ldA;
@@ -291,14 +300,14 @@ struct CmSrc {
 #pragma unroll
             for (int q = 0; q < SQ; ++q)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) r[q][e] = Cols::stream ? __builtin_nontemporal_load(p[q] + e * ld[q]) : p[q][e * ld[q]];
+                for (int e = 0; e < 4; ++e) r[q][e] = cm_load<Cols::stream>(p[q] + e * ld[q]);
         } else {
 #pragma unroll
             for (int q = 0; q < SQ; ++q)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int k = k0 + 4 * item_quad(t, q) + e, back = min(k, K - 1) - (k - e);
-                    const float v = p[q][back * ld[q]];
+                    const float v = widen_px(p[q] + back * ld[q]);
                     r[q][e] = k < K ? v : 0.f;
                 }
         }

@@ -136,13 +136,7 @@ imgs_bounds_batch_kernel(const float* __restrict__ x_scale, const float* __restr
 // (x - mean[c]) / std[c] - a subtraction, then an IEEE division (torchvision's Normalize: sub_, then div_) - and ONE
 // rounding to the output type at the store (round-to-nearest-even; plain conversions, v_cvt_pk_bf16_f32 for bf16).
 // Layout hwc = [K,96,96,3], chw = [K,3,96,96].  The default format (fp32, hwc, no normalisation) on fp32 images is the
-// instantiation the _f32 entry points launch; its code is the code those kernels always had.
-struct bf16_t { uint16_t bits; };
-
-template <typename T> __device__ __forceinline__ float widen_px(const T* p) { return (float)*p; }      // float, uint8
-template <> __device__ __forceinline__ float widen_px<_Float16>(const _Float16* p) { return (float)*p; }
-template <> __device__ __forceinline__ float widen_px<bf16_t>(const bf16_t* p) { return __uint_as_float((uint32_t)p->bits << 16); }
-
+// instantiation the _f32 entry points launch; its code is the code those kernels always had.  bf16_t / widen_px: common.hpp.
 template <typename T> __device__ __forceinline__ uint32_t narrow_bits(float v);                      // 2-byte outputs
 template <> __device__ __forceinline__ uint32_t narrow_bits<_Float16>(float v) {
     return __builtin_bit_cast(uint16_t, (_Float16)v);

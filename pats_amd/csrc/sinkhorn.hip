@@ -132,7 +132,7 @@ __device__ __forceinline__ float dot64(const float (&k)[64], const float* bc) {
 
 struct Ot65Args {
     const float* Zin;        // SRC 0: [P,65,65] couplings
-    const float* d0;         // SRC 1: [P,D,65] descriptors
+    const float* d0;         // SRC 1: [P,D,65] descriptors; the kernel reads them as (const TD*), its element type
     const float* d1;
     int D;
     int64_t P;
@@ -158,7 +158,8 @@ struct Ot65Args {
 // MODE 0: log_mu/log_nu given (a6)      MODE 2: ns given, log_optimal_transport2 marginals (a5)
 // SRC  0: couplings from HBM            SRC  1: cost build from descriptors (a3 fused)
 // EPI  0: write the log-plan            EPI  1: Compute_result + label from the LDS-resident plan
-template <int MODE, int SRC, int EPI>
+// TD (SRC 1): the descriptors' element type - float, or _Float16 / bf16_t widened at the cost build's loads (cost65_device.hpp)
+template <int MODE, int SRC, int EPI, typename TD = float>
 __global__ void __launch_bounds__(64, 2)     // 2 waves/SIMD: VGPR + AGPR (MFMA accumulators) <= 256
 sinkhorn65_kernel(Ot65Args g) {
     __shared__ Wave65Lds lds;
@@ -188,7 +189,7 @@ sinkhorn65_kernel(Ot65Args g) {
         for (int k = 0; k < 66; ++k) lds.tile[k * 64 + lane] = Zp[k * 64 + lane];
         if (lane == 0) lds.tile[TILE - 1] = Zp[TILE - 1];
     } else {
-        cost65_to_tile(g.d0 + p * (int64_t)g.D * NT, g.d1 + p * (int64_t)g.D * NT, g.D, lds.tile, lane);
+        cost65_to_tile((const TD*)g.d0 + p * (int64_t)g.D * NT, (const TD*)g.d1 + p * (int64_t)g.D * NT, g.D, lds.tile, lane);
     }
 
     // ---- marginals -----------------------------------------------------------------------
@@ -362,15 +363,15 @@ sinkhorn65_kernel(Ot65Args g) {
 }
 
 // standalone cost build for 65-wide problems (pats_cost_f32 fast path): one wave per problem
-template <bool F16>
+template <bool F16, typename T = float>
 __global__ void __launch_bounds__(64)
-cost65_kernel(const float* __restrict__ d0, const float* __restrict__ d1, int D, int64_t P,
+cost65_kernel(const T* __restrict__ d0, const T* __restrict__ d1, int D, int64_t P,
               float* __restrict__ out) {
     __shared__ float tile[TILE + 3];
     const int lane = threadIdx.x;
     const int64_t p = blockIdx.x;
     if (p >= P) return;
-    cost65_to_tile<F16>(d0 + p * (int64_t)D * NT, d1 + p * (int64_t)D * NT, D, tile, lane);
+    cost65_to_tile<F16, T>(d0 + p * (int64_t)D * NT, d1 + p * (int64_t)D * NT, D, tile, lane);
     wg_barrier();
     float* Op = out + p * TILE;
 #pragma unroll 11
@@ -378,12 +379,21 @@ cost65_kernel(const float* __restrict__ d0, const float* __restrict__ d1, int D,
     if (lane == 0) Op[TILE - 1] = tile[TILE - 1];
 }
 
-int launch_cost65(const float* d0, const float* d1, int D, int64_t P, float* out, hipStream_t st) {
-    static const bool f16 = diag_env("PATS_COST65_F16") != nullptr;      // diagnostic: the fp16-split contraction of the fused kernel
-    if (f16) hipLaunchKernelGGL(cost65_kernel<true>, dim3((unsigned)P), dim3(64), 0, st, d0, d1, D, P, out);
-    else hipLaunchKernelGGL(cost65_kernel<false>, dim3((unsigned)P), dim3(64), 0, st, d0, d1, D, P, out);
+template <typename T>
+int launch_cost65(const T* d0, const T* d1, int D, int64_t P, float* out, hipStream_t st) {
+    if constexpr (sizeof(T) == 4) {
+        static const bool f16 = diag_env("PATS_COST65_F16") != nullptr;      // diagnostic: the fp16-split contraction of the fused kernel
+        if (f16) {
+            hipLaunchKernelGGL(cost65_kernel<true>, dim3((unsigned)P), dim3(64), 0, st, d0, d1, D, P, out);
+            return check_launch("cost65_kernel");
+        }
+    }
+    hipLaunchKernelGGL((cost65_kernel<false, T>), dim3((unsigned)P), dim3(64), 0, st, d0, d1, D, P, out);
     return check_launch("cost65_kernel");
 }
+template int launch_cost65<float>(const float*, const float*, int, int64_t, float*, hipStream_t);
+template int launch_cost65<_Float16>(const _Float16*, const _Float16*, int, int64_t, float*, hipStream_t);
+template int launch_cost65<bf16_t>(const bf16_t*, const bf16_t*, int, int64_t, float*, hipStream_t);
 
 // ------------------------------------------------------------------------------------------
 // N x N with N <= 192 (the fine level: 145 x 145), one 384-thread workgroup per problem
@@ -1486,13 +1496,16 @@ static int ot2_impl(const float* scores, int64_t batch, int m, int n, const floa
 
 // descriptors -> log-plan for 65x65 problems in one launch (cost build + OT2), used by pats_cost_ot_f32
 namespace pats {
-int launch_cost_ot65(const float* d0, const float* d1, int64_t batch, int D, const float* one,
+int launch_cost_ot65(const void* d0, const void* d1, int dtype, int64_t batch, int D, const float* one,
                      const float* ns, int iters, float bias_k, float* Z, pats_stream_t stream) {
     Ot65Args g{};
     g.fallbacks = fallback_counter();
-    g.d0 = d0; g.d1 = d1; g.D = D; g.P = batch; g.ns = ns; g.one = one; g.iters = iters;
+    g.d0 = (const float*)d0; g.d1 = (const float*)d1; g.D = D; g.P = batch; g.ns = ns; g.one = one; g.iters = iters;
     g.bias_k = bias_k; g.linear = use_linear(); g.out = Z;
-    hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0>), dim3((unsigned)batch), dim3(64), 0, as_stream(stream), g);
+    const dim3 grid((unsigned)batch), block(64);
+    if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0, _Float16>), grid, block, 0, as_stream(stream), g);
+    else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0, bf16_t>), grid, block, 0, as_stream(stream), g);
+    else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0>), grid, block, 0, as_stream(stream), g);
     return check_launch("sinkhorn65_kernel<2,1,0>");
 }
 }  // namespace pats
@@ -1500,6 +1513,11 @@ int launch_cost_ot65(const float* d0, const float* d1, int64_t batch, int D, con
 
 // third-level step of a batch whose problem count lives on the device (throughput mode: no host read between the merge
 // that decides P and this launch): the grid covers the capacity P_cap, waves past *P_dev leave at once
+static int third_level_impl(const void* feat0, const void* feat1, int dtype, int64_t P, const int64_t* P_dev, int D,
+                            const float* scale, const float* scale_x, const float* scale_y, const int64_t* p_s,
+                            const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f, float* label,
+                            uint8_t* if_matching1, float* Z_out, pats_stream_t stream);
+
 extern "C" int pats_third_level_counted_f32(const float* feat0, const float* feat1, int64_t P_cap, const int64_t* P_dev, int D,
                                             const float* scale, const float* scale_x, const float* scale_y,
                                             const int64_t* p_s, const int64_t* p_t, int iters, int outdoor,
@@ -1510,9 +1528,8 @@ extern "C" int pats_third_level_counted_f32(const float* feat0, const float* fea
     if (P_cap == 0) return PATS_OK;
     PATS_REQUIRE(P_dev && feat0 && feat1 && scale && p_s && p_t && mkpts0_f && mkpts1_f && label && if_matching1 &&
                      ((scale_x == nullptr) == (scale_y == nullptr)), "third_level_counted: null pointer");
-    Fused65Args f{feat0, feat1, D, P_cap, scale, nullptr, iters, 1, scale_x, scale_y, p_s, p_t, outdoor,
-                  ComputeResultOut{mkpts0_f, mkpts1_f, nullptr, label, if_matching1, nullptr}, 0, nullptr, 0, P_dev};
-    return launch_third_fused(f, as_stream(stream));
+    return third_level_impl(feat0, feat1, PATS_MAP_F32, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
+                            mkpts0_f, mkpts1_f, label, if_matching1, nullptr, stream);
 }
 
 extern "C" int pats_third_level_f32(const float* feat0, const float* feat1, int64_t P, int D,
@@ -1525,15 +1542,47 @@ extern "C" int pats_third_level_f32(const float* feat0, const float* feat1, int6
     if (P == 0) return PATS_OK;
     PATS_REQUIRE(feat0 && feat1 && scale && scale_x && scale_y && p_s && p_t && mkpts0_f && mkpts1_f &&
                      label && if_matching1, "third_level: null pointer");
+    return third_level_impl(feat0, feat1, PATS_MAP_F32, P, nullptr, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
+                            mkpts0_f, mkpts1_f, label, if_matching1, Z_out, stream);
+}
+
+// Both of the above on descriptors of any pats_map_dtype_t: P_dev == NULL is pats_third_level_f32 (scale_x / scale_y required,
+// Z optional), a count is pats_third_level_counted_f32 (scale_x / scale_y both NULL or both given, no Z).
+extern "C" int pats_third_level_typed(const void* feat0, const void* feat1, pats_map_dtype_t dtype, int64_t P_cap,
+                                      const int64_t* P_dev, int D, const float* scale, const float* scale_x,
+                                      const float* scale_y, const int64_t* p_s, const int64_t* p_t, int iters, int outdoor,
+                                      float* mkpts0_f, float* mkpts1_f, float* label, uint8_t* if_matching1, float* Z,
+                                      pats_stream_t stream) {
+    PATS_REQUIRE(known_elem_type((int)dtype), "third_level_typed: unknown descriptor dtype %d", (int)dtype);
+    PATS_REQUIRE(P_cap >= 0 && D > 0 && (D % 32) == 0 && D <= 512 && iters >= 0,
+                 "third_level_typed: bad shape (D must be a multiple of 32, at most 512)");
+    if (P_cap == 0) return PATS_OK;
+    PATS_REQUIRE(feat0 && feat1 && scale && p_s && p_t && mkpts0_f && mkpts1_f && label && if_matching1 &&
+                     (P_dev ? (scale_x == nullptr) == (scale_y == nullptr) : scale_x && scale_y),
+                 "third_level_typed: null pointer");
+    PATS_REQUIRE(!(P_dev && Z), "third_level_typed: the plan is not available with a device-side count");
+    PATS_REQUIRE((uintptr_t)feat0 % desc_elem_bytes((int)dtype) == 0 && (uintptr_t)feat1 % desc_elem_bytes((int)dtype) == 0,
+                 "third_level_typed: descriptors must be aligned to their element size (%d bytes)", (int)desc_elem_bytes((int)dtype));
+    return third_level_impl(feat0, feat1, (int)dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
+                            mkpts0_f, mkpts1_f, label, if_matching1, Z, stream);
+}
+
+// validated arguments.  P_dev: throughput mode - no host read between the merge that decides P and this launch: the grid
+// covers the capacity P, waves past *P_dev leave at once
+static int third_level_impl(const void* feat0, const void* feat1, int dtype, int64_t P, const int64_t* P_dev, int D,
+                            const float* scale, const float* scale_x, const float* scale_y, const int64_t* p_s,
+                            const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f, float* label,
+                            uint8_t* if_matching1, float* Z_out, pats_stream_t stream) {
     static const bool v1_only = diag_env("PATS_THIRD_V1") != nullptr;     // A/B switch for benchmarking
-    if (!Z_out && !v1_only) {      // no plan requested: the 8x8 register-block kernel (third_fused.hip)
-        Fused65Args f{feat0, feat1, D, P, scale, nullptr, iters, 1, scale_x, scale_y, p_s, p_t, outdoor,
-                      ComputeResultOut{mkpts0_f, mkpts1_f, nullptr, label, if_matching1, nullptr}, 0, nullptr};
+    if (P_dev || (!Z_out && !v1_only)) {      // no plan requested: the 8x8 register-block kernel (third_fused.hip)
+        Fused65Args f{(const float*)feat0, (const float*)feat1, D, P, scale, nullptr, iters, 1, scale_x, scale_y, p_s, p_t, outdoor,
+                      ComputeResultOut{mkpts0_f, mkpts1_f, nullptr, label, if_matching1, nullptr}, 0, nullptr, 0, P_dev};
+        f.dtype = dtype;
         return launch_third_fused(f, as_stream(stream));
     }
     Ot65Args g{};
     g.fallbacks = fallback_counter();
-    g.d0 = feat0; g.d1 = feat1; g.D = D; g.P = P; g.ns = scale; g.iters = iters;
+    g.d0 = (const float*)feat0; g.d1 = (const float*)feat1; g.D = D; g.P = P; g.ns = scale; g.iters = iters;
     g.linear = use_linear(); g.out = Z_out;
     g.scale_x = scale_x; g.scale_y = scale_y; g.p_s = p_s; g.p_t = p_t; g.outdoor = outdoor;
     g.cr = ComputeResultOut{mkpts0_f, mkpts1_f, nullptr, label, if_matching1, nullptr};
@@ -1542,6 +1591,9 @@ extern "C" int pats_third_level_f32(const float* feat0, const float* feat1, int6
     // (measured on MI355X: unit 1-3 all give ~-11 %, larger units lose it again)
     if (P >= 8192) g.stagger = (int)((30.0f + 0.6f * (float)iters) / 16.0f / 3.4f);
     if (const char* e = diag_env("PATS_STAGGER")) g.stagger = atoi(e);
-    hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1>), dim3((unsigned)P), dim3(64), 0, as_stream(stream), g);
+    const dim3 grid((unsigned)P), block(64);
+    if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, _Float16>), grid, block, 0, as_stream(stream), g);
+    else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, bf16_t>), grid, block, 0, as_stream(stream), g);
+    else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1>), grid, block, 0, as_stream(stream), g);
     return check_launch("sinkhorn65_kernel<2,1,1>");
 }

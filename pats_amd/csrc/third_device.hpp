@@ -18,8 +18,8 @@ struct ComputeResultOut {
 
 // arguments of the register-block fused third-level kernel (third_fused.hip)
 struct Fused65Args {
-    const float* d0;
-    const float* d1;
+    const float* d0;             // [P,D,65] descriptors of `dtype` elements: a kernel instantiated for the element type T
+    const float* d1;             // reads them as (const T*)
     int D;
     int64_t P;
     const float* ns;             // [P,64] target areas
@@ -39,6 +39,7 @@ struct Fused65Args {
     int lds_poison_on;               // libpats_amd_diag.so only: fill the workgroup's LDS with lds_poison first
     unsigned lds_poison;
     int reverse_blocks;              // libpats_amd_diag.so only: workgroup b solves problem P - 1 - b (round-6 first-launch experiment)
+    int dtype;                       // pats_map_dtype_t of d0 / d1 (0 = float32): picks the instantiation, no kernel reads it
 };
 // number of problems that exist: min(capacity, device-side count)
 __device__ __forceinline__ int64_t live_problems(const Fused65Args& g) {

@@ -48,6 +48,7 @@ struct __attribute__((aligned(16))) BlkLds {
 __device__ __forceinline__ float lse_fin(float s, float mI) { return (fast_log2(s) + mI) * LN2; }
 __device__ __forceinline__ float uni(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
+template <typename T>      // the descriptors' element type (cost65_device.hpp): only the cost build's loads see it
 __device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int64_t p, BlkLds& lds, const int lane) {
     const int I = lane >> 3, J = lane & 7;
     const int colj = 8 * J + I;              // the column this lane owns in the column half-sweep
@@ -74,7 +75,7 @@ __device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int
         // ---- cost build (MFMA) and redistribution: fragment layout -> 8x8 blocks ----------------
         {
             Cost65Acc c;
-            cost65_accumulate(g.d0 + p * (int64_t)g.D * 65, g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
+            cost65_accumulate((const T*)g.d0 + p * (int64_t)g.D * 65, (const T*)g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
             const int li = lane & 31, lk = lane >> 5;
             const Cost65Scale sq(g.D);
 #pragma unroll
@@ -353,6 +354,7 @@ __device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int
 // consecutive): with contiguous blocks of 64 per workgroup - round 3 - one wave re-solved a whole run serially while the rest
 // of the GPU idled (9.1 ms per step for 8 000 flagged problems, profiles/r04_wild10_step_kernel_stats.md); interleaved, a
 // run of 64 goes to 64 different waves.
+template <typename T = float>       // the descriptors' element type
 __global__ void __launch_bounds__(64, 3)
 third_fused_kernel(Fused65Args g) {
     __shared__ BlkLds lds;
@@ -365,7 +367,7 @@ third_fused_kernel(Fused65Args g) {
             const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
             for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
         }
-        third_v2_problem(g, p, lds, lane);
+        third_v2_problem<T>(g, p, lds, lane);
         return;
     }
     const int64_t W = gridDim.x, live = live_problems(g);
@@ -377,9 +379,14 @@ third_fused_kernel(Fused65Args g) {
             const int k = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
             wg_barrier();
-            third_v2_problem(g, first + (int64_t)k * W, lds, lane);
+            third_v2_problem<T>(g, first + (int64_t)k * W, lds, lane);
         }
     }
+}
+static void launch_v2(const Fused65Args& g, dim3 grid, hipStream_t st) {
+    if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused_kernel<_Float16>, grid, dim3(64), 0, st, g);
+    else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused_kernel<bf16_t>, grid, dim3(64), 0, st, g);
+    else hipLaunchKernelGGL(third_fused_kernel<float>, grid, dim3(64), 0, st, g);
 }
 
 int launch_third_fused3(const Fused65Args& g0, hipStream_t st);      // third_fused3.hip
@@ -397,12 +404,12 @@ int launch_third_fused(const Fused65Args& g0, hipStream_t st) {
         g.linear = 0;
         g.scan = 1;
         const int64_t waves = g.P < 6144 ? g.P : 6144;            // two rounds of the 3 072 wave slots: flagged runs spread out
-        hipLaunchKernelGGL(third_fused_kernel, dim3((unsigned)(waves > 0 ? waves : 1)), dim3(64), 0, st, g);
+        launch_v2(g, dim3((unsigned)(waves > 0 ? waves : 1)), st);
         return check_launch("third_fused_kernel(scan)");
     }
     if (g.P >= 8192) g.stagger = (int)((30.0f + 0.6f * (float)g.iters) / 16.0f / 3.4f);
     if (const char* e = diag_env("PATS_STAGGER")) g.stagger = atoi(e);
-    hipLaunchKernelGGL(third_fused_kernel, dim3((unsigned)g.P), dim3(64), 0, st, g);
+    launch_v2(g, dim3((unsigned)g.P), st);
     return check_launch("third_fused_kernel");
 }
 

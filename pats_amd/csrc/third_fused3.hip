@@ -246,7 +246,8 @@ __device__ __forceinline__ unsigned fbits(float x) { return __builtin_bit_cast(u
 // that has drifted out of [2^-20, 2^20] is absorbed into the kernel matrix (K_ij <- a_i K_ij b_j, a = b = 1: the plan K a b is
 // unchanged, the iterate is the same Sinkhorn iterate) and the sweeps go on; only a scaling that leaves fp32 within ONE sweep
 // (-inf scores, ranges beyond 2^127) still goes to the log-sum-exp kernel.  A problem that never drifts runs bit-identically to ST = 0.
-template <int CR, int DB, int CF, int ST>
+// T = the descriptors' element type (cost65_device.hpp); only build_scores' descriptor loads see it.
+template <int CR, int DB, int CF, int ST, typename T = float>
 __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64_t p, Blk3Lds& lds, const int lane) {
     const int I = lane >> 3, J = lane & 7;
     const int colj = 8 * J + I;              // the column this lane owns in the column half-sweep
@@ -272,11 +273,11 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
             for (int r = 0; r < 16; ++r) { c.c00[r] = (float)(lane + r) * 0.01f; c.c01[r] = -c.c00[r]; c.c10[r] = c.c00[r] * 0.5f; c.c11[r] = 0.25f; }
             c.er0 = c.er1 = c.ec0 = c.ec1 = c.cn = 0.f;
         } else if (DB == 7) {   // timing ablation only: descriptor loads without the MFMAs
-            cost65_accumulate<true>(g.d0 + p * (int64_t)g.D * 65, g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
-        } else if (CF == 1) {   // fp16-split operands, three exact-product MFMA passes (cost65_device.hpp)
+            cost65_accumulate<true>((const T*)g.d0 + p * (int64_t)g.D * 65, (const T*)g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
+        } else if (CF == 1) {   // fp16-split operands, three exact-product MFMA passes (cost65_device.hpp; float descriptors only)
             cost65_accumulate_f16x2(g.d0 + p * (int64_t)g.D * 65, g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
         } else
-        cost65_accumulate(g.d0 + p * (int64_t)g.D * 65, g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
+        cost65_accumulate((const T*)g.d0 + p * (int64_t)g.D * 65, (const T*)g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
         const int li = lane & 31, lk = lane >> 5;
         const Cost65Scale sq(g.D);
         // LDS offsets of this lane's eight register rows: matrix row 8I + rho(s, J), columns 4J..4J+3 of the parity
@@ -635,8 +636,25 @@ third_fused3_kernel(Fused65Args g) {
     third3_problem<CR, DB, CF, 0>(g, p, lds, lane);
 }
 
+// The production instantiation (fp32-MFMA cost build, <3, 0, 0>) for float16 / bfloat16 descriptors.  A kernel of its own name:
+// third_fused3_kernel<3, 0, 0, 0> stays the one instantiation of that template in the production library.
+template <typename T>
+__global__ void __launch_bounds__(64, 3)
+third_fused3_typed_kernel(Fused65Args g) {
+    __shared__ Blk3Lds lds;
+    const int lane = threadIdx.x;
+    const int64_t p = blockIdx.x;
+    if (p >= live_problems(g)) return;
+    if (g.stagger > 0 && blockIdx.x < 8192u) {      // de-phase the first wave-front, as above
+        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
+        for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
+    }
+    third3_problem<0, 0, 0, 0, T>(g, p, lds, lane);
+}
+
 // The stabilised solve over the problems the launch above flagged: the W workgroups share the problems interleaved, as
 // third_fused_kernel's scan mode does (third_fused.hip) - which runs behind this one for what is still flagged.
+template <typename T = float>       // the descriptors' element type
 __global__ void __launch_bounds__(64, 2)
 third_fused3_stab_kernel(Fused65Args g) {
     __shared__ Blk3Lds lds;
@@ -650,7 +668,7 @@ third_fused3_stab_kernel(Fused65Args g) {
             const int k = __ffsll((long long)todo) - 1;
             todo &= todo - 1;
             wg_barrier();
-            third3_problem<0, 0, 0, 1>(g, first + (int64_t)k * W, lds, lane);
+            third3_problem<0, 0, 0, 1, T>(g, first + (int64_t)k * W, lds, lane);
         }
     }
 }
@@ -683,8 +701,11 @@ int launch_third_fused3(const Fused65Args& g0, hipStream_t st) {
     PATS_REQUIRE(variant == 300,
                  "PATS_THIRD_VARIANT=%d is a diagnostic build: it is compiled into libpats_amd_diag.so only "
                  "(python -m pats_amd.build --diag; PATS_AMD_DIAG_LIB=1)", variant);
-    hipLaunchKernelGGL((third_fused3_kernel<3, 0, 0>), grid, block, 0, st, g);       // fp32 MFMA cost build
+    if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_typed_kernel<_Float16>, grid, block, 0, st, g);
+    else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_typed_kernel<bf16_t>, grid, block, 0, st, g);
+    else hipLaunchKernelGGL((third_fused3_kernel<3, 0, 0>), grid, block, 0, st, g);       // fp32 MFMA cost build
 #else
+    PATS_REQUIRE(g.dtype == PATS_MAP_F32, "third_level: the diagnostic library's sweep-loop variants take float32 descriptors only");
     // last digit (dustbin sums) 6..9 = diagnostic / timing-ablation builds whose RESULTS ARE NOT the solve: never by accident
     static const bool ablation_ok = diag_env("PATS_THIRD_ABLATION") != nullptr;
     PATS_REQUIRE(ablation_ok || variant % 10 < 6,
@@ -725,7 +746,10 @@ int launch_third_fused3(const Fused65Args& g0, hipStream_t st) {
     static const bool no_stab = [] { const char* e = env_switch("PATS_THIRD_STAB"); return e && atoi(e) == 0; }();      // A/B switch
     if (!no_stab && g.iters > 0) {
         const int64_t waves = g.P < 6144 ? g.P : 6144;            // two rounds of the 3 072 wave slots: flagged runs spread out
-        hipLaunchKernelGGL(third_fused3_stab_kernel, dim3((unsigned)(waves > 0 ? waves : 1)), dim3(64), 0, st, g);
+        const dim3 sgrid((unsigned)(waves > 0 ? waves : 1));
+        if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_stab_kernel<_Float16>, sgrid, dim3(64), 0, st, g);
+        else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_stab_kernel<bf16_t>, sgrid, dim3(64), 0, st, g);
+        else hipLaunchKernelGGL(third_fused3_stab_kernel<float>, sgrid, dim3(64), 0, st, g);
         rc = check_launch("third_fused3_stab_kernel");
     }
     return rc;

@@ -94,6 +94,26 @@ def _maps_any(tensors, names):
     return maps, _MAP_DTYPES[dt]
 
 
+def _descs_any(tensors, names):
+    """The two descriptor sets of ONE cost / cost_ot / third_level call in float32, float16 or bfloat16 -> (contiguous tensors,
+    pats_map_dtype_t code).  Both sets in the same half dtype go to the typed entry points as they lie: the cost builds widen
+    every element to fp32 exactly at the load, so every output has the bits of the same call on .float() copies.  Two different
+    dtypes in one call, or a data pointer off the element size (all the kernels' loads need), fall back to .float() copies and
+    the fp32 entry: same bits."""
+    for t, name in zip(tensors, names):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype not in _MAP_DTYPES:
+            raise RuntimeError("pats_amd: %s must be float32, float16 or bfloat16, got %s" % (name, t.dtype))
+    dtypes = {t.dtype for t in tensors}
+    if len(dtypes) == 1 and torch.float32 not in dtypes:
+        dt = tensors[0].dtype
+        descs = [_dev(t, n, dt) for t, n in zip(tensors, names)]
+        if not any(t.data_ptr() % t.element_size() for t in descs):
+            return descs, _MAP_DTYPES[dt]
+    return [_dev(t.float(), n) for t, n in zip(tensors, names)], _MAP_DTYPES[torch.float32]
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -195,8 +215,10 @@ def gnn_overflows(reset=True):
 # ------------------------------------------------------------------------------------------------
 def cost(mdesc0, mdesc1, out=None):
     """0.1 * (einsum('bdn,bdm->bnm', mdesc0, mdesc1) / D**.5)   (first_layer.py:110-114).
-    out: optional preallocated [b, n, m] float32 result (as torch's `out=`)."""
-    d0, d1 = _dev(mdesc0, "mdesc0"), _dev(mdesc1, "mdesc1")
+    out: optional preallocated [b, n, m] float32 result (as torch's `out=`).
+    mdesc0 / mdesc1: float32, float16 or bfloat16 (see _descs_any); the result is float32 with the bits of the call on
+    .float() copies."""
+    (d0, d1), code = _descs_any([mdesc0, mdesc1], ["mdesc0", "mdesc1"])
     b, D, n = d0.shape
     if d1.shape[0] != b or d1.shape[1] != D:
         raise RuntimeError("cost: descriptor shapes %s / %s do not match" % (tuple(d0.shape), tuple(d1.shape)))
@@ -205,7 +227,10 @@ def cost(mdesc0, mdesc1, out=None):
         out = torch.empty((b, n, m), dtype=torch.float32, device=d0.device)
     elif tuple(out.shape) != (b, n, m) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != d0.device:
         raise RuntimeError("cost: out must be a contiguous float32 [%d, %d, %d] tensor on %s" % (b, n, m, d0.device))
-    _check(_L().pats_cost_f32(_ptr(d0), _ptr(d1), b, D, n, m, _ptr(out), _stream()), "cost")
+    if code:
+        _check(_L().pats_cost_typed(_ptr(d0), _ptr(d1), code, b, D, n, m, _ptr(out), _stream()), "cost")
+    else:
+        _check(_L().pats_cost_f32(_ptr(d0), _ptr(d1), b, D, n, m, _ptr(out), _stream()), "cost")
     return out
 
 
@@ -272,11 +297,13 @@ def cost_ot(mdesc0, mdesc1, variant, scalar, ns, iters: int, bias_k: float = 0.0
     return_flags (variant 2): also est_position's if_nomatching2 [b, m-1] (bool) from the OT epilogue ->
     (Z, col_nomatch); hand it to est_position_second(col_nomatch=...).
     count (fine level, with return_flags): DEVICE int64 [1] - the tensors are a capacity, only the first `count` problems are
-    solved (the rows of the others are left as allocated)."""
-    d0, d1 = _dev(mdesc0, "mdesc0"), _dev(mdesc1, "mdesc1")
+    solved (the rows of the others are left as allocated).
+    mdesc0 / mdesc1: float32, float16 or bfloat16 (see _descs_any; Z is float32 with the bits of the call on .float() copies);
+    a half `scalar` / `ns` is widened here."""
+    (d0, d1), code = _descs_any([mdesc0, mdesc1], ["mdesc0", "mdesc1"])
     b, D, n = d0.shape
     m = d1.shape[2]
-    ns = _dev(ns, "ns").reshape(b, m if variant == 1 else m - 1)
+    ns = _dev(_widen(ns), "ns").reshape(b, m if variant == 1 else m - 1)
     s = _scalar_dev(scalar, d0.device)
     shape = (b, n + 1, m + 1) if variant == 1 else (b, n, m)
     Z = torch.empty(shape, dtype=torch.float32, device=d0.device)
@@ -286,8 +313,13 @@ def cost_ot(mdesc0, mdesc1, variant, scalar, ns, iters: int, bias_k: float = 0.0
         if variant != 2:
             raise RuntimeError("cost_ot: return_flags needs variant 2 (the coarse level gets them from colmass_sqrt)")
         flags = torch.empty((b, m - 1), dtype=torch.bool, device=d0.device)
+        cnt = _dev(count, "count", torch.int64) if count is not None else None
+        if code:
+            _check(_L().pats_cost_ot_typed(_ptr(d0), _ptr(d1), code, b, _ptr(cnt) if cnt is not None else None, D, n, m,
+                                           int(variant), _ptr(s), _ptr(ns), int(iters), float(bias_k), _ptr(Z),
+                                           _ptr(flags.view(torch.uint8)), _ptr(ws), nb, _stream()), "cost_ot")
+            return Z, flags
         if count is not None:
-            cnt = _dev(count, "count", torch.int64)
             _check(_L().pats_cost_ot_flags_counted_f32(_ptr(d0), _ptr(d1), b, _ptr(cnt), D, n, m, int(variant), _ptr(s), _ptr(ns),
                                                        int(iters), float(bias_k), _ptr(Z), _ptr(flags.view(torch.uint8)), _ptr(ws),
                                                        nb, _stream()), "cost_ot")
@@ -298,6 +330,10 @@ def cost_ot(mdesc0, mdesc1, variant, scalar, ns, iters: int, bias_k: float = 0.0
         return Z, flags
     if count is not None:
         raise RuntimeError("cost_ot: count needs return_flags=True (the fine level's counted launch)")
+    if code:
+        _check(_L().pats_cost_ot_typed(_ptr(d0), _ptr(d1), code, b, None, D, n, m, int(variant), _ptr(s), _ptr(ns), int(iters),
+                                       float(bias_k), _ptr(Z), None, _ptr(ws), nb, _stream()), "cost_ot")
+        return Z
     _check(_L().pats_cost_ot_f32(_ptr(d0), _ptr(d1), b, D, n, m, int(variant), _ptr(s), _ptr(ns),
                                  int(iters), float(bias_k), _ptr(Z), _ptr(ws), nb, _stream()), "cost_ot")
     return Z
@@ -839,12 +875,14 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
     count: a DEVICE int64 [1] holding the number of problems that exist (throughput mode: the tensors are sized for a
     capacity, nothing is read back); rows past it are not written, and sqrt(scale + 1e-8) is formed in the kernel.
     out: optional (mkpts0_f [P,16,2], mkpts1_f [P,16,2], label [P*16,2], if_matching1 [P,16] uint8 or bool) to write into; the same
-    four tensors are returned, if_matching1 as it was given."""
-    f0, f1 = _dev(feat_f0_unfold, "feat_f0_unfold"), _dev(feat_f1_unfold, "feat_f1_unfold")
+    four tensors are returned, if_matching1 as it was given.
+    feat_f*_unfold: float32, float16 or bfloat16 (see _descs_any); every output is float32 / bool with the bits of the call on
+    .float() copies.  A half `scale` is widened here."""
+    (f0, f1), code = _descs_any([feat_f0_unfold, feat_f1_unfold], ["feat_f0_unfold", "feat_f1_unfold"])
     P, D, n = f0.shape
     if n != 65 or tuple(f1.shape) != (P, D, 65):
         raise RuntimeError("third_level: descriptors must be [P,D,65]")
-    sc = _dev(scale, "scale").reshape(P, 64)
+    sc = _dev(_widen(scale), "scale").reshape(P, 64)
     ps = _dev(mkpts0_c.to(torch.int64), "mkpts0_c", torch.int64).reshape(P, 2)
     pt = _dev(mkpts1_c.to(torch.int64), "mkpts1_c", torch.int64).reshape(P, 2)
     dev = f0.device
@@ -853,6 +891,11 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
             raise RuntimeError("third_level: return_plan is not available with a device-side count")
         cnt = _dev(count, "count", torch.int64).reshape(1)
         m0, m1, label, ifm = _third_out(out, P, dev)
+        if code:
+            _check(_L().pats_third_level_typed(_ptr(f0), _ptr(f1), code, P, _ptr(cnt), D, _ptr(sc), None, None, _ptr(ps), _ptr(pt),
+                                               int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label), _ptr(ifm), None,
+                                               _stream()), "third_level")
+            return (m0, m1, label, ifm.view(torch.bool)) if out is None else tuple(out)
         _check(_L().pats_third_level_counted_f32(_ptr(f0), _ptr(f1), P, _ptr(cnt), D, _ptr(sc), _ptr(None), _ptr(None), _ptr(ps),
                                                  _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
                                                  _ptr(ifm), _stream()), "third_level")
@@ -860,9 +903,14 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
     sxy = torch.sqrt(sc + 1e-8)
     m0, m1, label, ifm = _third_out(out, P, dev)
     Z = torch.empty((P, 65, 65), dtype=torch.float32, device=dev) if return_plan else None
-    _check(_L().pats_third_level_f32(_ptr(f0), _ptr(f1), P, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps),
-                                     _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1),
-                                     _ptr(label), _ptr(ifm), _ptr(Z), _stream()), "third_level")
+    if code:
+        _check(_L().pats_third_level_typed(_ptr(f0), _ptr(f1), code, P, None, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps), _ptr(pt),
+                                           int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label), _ptr(ifm),
+                                           _ptr(Z) if Z is not None else None, _stream()), "third_level")
+    else:
+        _check(_L().pats_third_level_f32(_ptr(f0), _ptr(f1), P, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps),
+                                         _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1),
+                                         _ptr(label), _ptr(ifm), _ptr(Z), _stream()), "third_level")
     res = (m0, m1, label, ifm.bool()) if out is None else tuple(out)
     return res + (Z,) if return_plan else res
 
@@ -1256,8 +1304,9 @@ def chunk_fine_tail(f0, f1, one, ns, scale_x, scale_y, iters, bias_k, merge_new,
     the capacity 144 B).  Returns (merged [B,144] bool, points [B,144,2], mkpts0_c [144 B,2], mkpts1_c, b_ids [144 B], P [1] int64
     on the device); the log plan, flags and the other expansion outputs stay internal.
     wait_before_merge / record_after_merge: torch.cuda.Event objects (already recorded once, so that their handles exist) - the
-    stream waits for the first right before the merge and re-records the second right behind it."""
-    d0, d1 = _dev(f0, "f0"), _dev(f1, "f1")
+    stream waits for the first right before the merge and re-records the second right behind it.
+    float16 / bfloat16 descriptors are widened with .float() here (the chunk walk's C entry reads float32 only)."""
+    d0, d1 = _dev(_widen(f0), "f0"), _dev(_widen(f1), "f1")
     B = d0.shape[0]
     if tuple(d0.shape) != (B, 264, 145) or d1.shape != d0.shape:
         raise RuntimeError("chunk_fine_tail: descriptors must be [B,264,145]")
@@ -1289,8 +1338,9 @@ def chunk_third_tail(feat0, feat1, P, scale, p_s, p_t, iters, outdoor, merged, p
     """Everything behind the third network callback for ONE chunk, in one C call (pats_chunk_third_tail_f32): third_layer.py:153-170
     over the capacity 144 B with the count P on the device, pats.py:59-67 (scatter onto the sub-cell grid) and :68-78 (get_result with
     the chunk's mask [h w] as the level-0 flags; pts_new / scales = Compute_imgs' [1, h w, 2] tensors).  Returns (matches_l, matches_r
-    [2304 B, 2], M [1] int64 on the device): the first M rows are the chunk's matches in the reference's order."""
-    a, b = _dev(feat0, "feat0"), _dev(feat1, "feat1")
+    [2304 B, 2], M [1] int64 on the device): the first M rows are the chunk's matches in the reference's order.
+    float16 / bfloat16 descriptors are widened with .float() here (the chunk walk's C entry reads float32 only)."""
+    a, b = _dev(_widen(feat0), "feat0"), _dev(_widen(feat1), "feat1")
     Pc = a.shape[0]
     B = merged.shape[0]
     if tuple(a.shape) != (Pc, 128, 65) or b.shape != a.shape or Pc != B * 144:

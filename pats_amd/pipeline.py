@@ -14,7 +14,9 @@ What changes against the reference's Python, and why it is equivalent:
     (tests/test_gpu_parity.py::test_pipeline_chain compares with the reference's own functions run in
     its own order on the same callbacks).
 
-Callbacks (`nets`), all returning float32 GPU tensors (the backbone maps they gather from may be float16 / bfloat16):
+Callbacks (`nets`), returning GPU tensors: the descriptors (mdesc0 / mdesc1, feat0 / feat1) in float32, float16 or bfloat16 - heads run
+under autocast hand them over as they come, ops.cost_ot / ops.third_level widen them exactly at the load - everything else in
+float32 (the backbone maps they gather from may be float16 / bfloat16 too):
   nets.coarse(left, right) -> mdesc0 [1,D,N], mdesc1 [1,D,N], scale [1,1,N], alpha (0-d / float)
       N = (H/32)*(W/32); what FirstLayer computes up to first_layer.py:107.
   nets.fine(num, new_left, new_right, chunk_mask) -> mdesc0 [B,264,145], mdesc1 [B,264,145],
