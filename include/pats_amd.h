@@ -350,6 +350,29 @@ int pats_third_descriptors_typed(const void* feat_f0, const void* feat_f1, pats_
                                  const float* rubbish, int64_t P_cap, const int64_t* P_dev, int64_t B, float* out0,
                                  float* out1, int64_t* p_s_out, int64_t* p_t_out, pats_stream_t stream);
 
+/* The two typed gathers with the OUTPUT element type selectable as well (ABI 8, new symbols): desc / out0 / out1 point to
+ * `out_dtype` elements - float32, or float16 / bfloat16 for the typed cost builds below - independent of the maps' dtype and
+ * memory order.  Semantics: every output element is the float32 value pats_*_descriptors_typed writes there, rounded ONCE to
+ * out_dtype, round-to-nearest-even, as tensor.to(dtype) rounds: for float16 magnitudes above 65520 become +-inf, subnormal
+ * results are produced (not flushed), +-0 and +-inf pass through; for bfloat16 RNE on the upper 16 bits; a NaN stays a NaN
+ * (payload unspecified).  Everything before the store is the fp32 code in its order - the widening at the load, the
+ * (((a + b) + c) + d) / 4 pool, the + kenc add, the dustbin column - so the half outputs are bit-identical to the float32
+ * outputs converted afterwards, and pats_cost_ot_typed / pats_third_level_typed on them to those calls on the converted
+ * descriptors.  p_s_out / p_t_out do not change; with a count, rows past it are left untouched in every output type.
+ * out_dtype == PATS_MAP_F32 dispatches to what the _typed entry points launch.  Half outputs of NCHW fp32 third-level maps
+ * are always written by the per-point kernel (pats_set_third_gather does not apply to them).  Refused before any launch
+ * (PATS_ERR_INVALID): an unknown out_dtype, what the _typed entry points refuse, and half outputs not aligned to what the
+ * kernel stores - 2 bytes for NCHW maps, 16 bytes for channels-last maps.  B_cap == 0 / P_cap == 0: PATS_OK, no pointer is
+ * looked at. */
+int pats_fine_descriptors_typed_out(const void* feat0, const void* feat1, const void* feat2, pats_map_dtype_t dtype,
+                                    int channels_last, const float* title, const float* rubbish, int64_t B_cap,
+                                    const int64_t* B_dev, void* desc, pats_map_dtype_t out_dtype, pats_stream_t stream);
+int pats_third_descriptors_typed_out(const void* feat_f0, const void* feat_f1, pats_map_dtype_t dtype, int channels_last,
+                                     const float* mkpts0_c, const float* mkpts1_c, const int64_t* b_ids, const float* kenc,
+                                     const float* rubbish, int64_t P_cap, const int64_t* P_dev, int64_t B, void* out0,
+                                     void* out1, pats_map_dtype_t out_dtype, int64_t* p_s_out, int64_t* p_t_out,
+                                     pats_stream_t stream);
+
 /* The cost builds and the descriptor -> plan entry points on DESCRIPTORS of a given element type (pats_map_dtype_t; ABI 8,
  * new symbols).  Networks run under autocast hand over mdesc0 / mdesc1 and feat_f*_unfold in float16 / bfloat16; the cost
  * builds widen every element to fp32 EXACTLY at the load (subnormals, signed zeros, infinities, NaNs included) and everything

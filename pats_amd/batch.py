@@ -26,7 +26,8 @@ without a cell are not compacted (pats.py:40-52) - they emit nothing, exactly as
 
 Network callbacks (`nets`, the out-of-scope backbones + heads; they return GPU tensors - the descriptors mdesc0 / mdesc1, feat0 / feat1 in float32,
 float16 or bfloat16 (ops.cost_ot / ops.third_level read them as they are), everything else float32 - no host read required of them;
-the backbone maps they gather from with ops.fine_descriptors / ops.third_descriptors may be float16 / bfloat16):
+the backbone maps they gather from with ops.fine_descriptors / ops.third_descriptors may be float16 / bfloat16, and those two
+write half descriptors themselves with out_dtype= or a half out=: the float32 values rounded once at the store, no .to() pass):
   nets.coarse(lefts, rights) -> mdesc0 [pairs,D,N], mdesc1 [pairs,D,N], scale [pairs,1,N], alpha
   nets.fine(rows, new_left, new_right) -> mdesc0 [rows_cap,264,145], mdesc1, scale_x [rows_cap,1,144], scale_y
       [, scale_x * scale_y] (what ops.scale_head hands out; formed here if absent)

@@ -89,6 +89,44 @@ __device__ __forceinline__ void stm2(float* p, f2s v) {      // two neighbouring
     else *q = v;
 }
 
+// ---- output element types -------------------------------------------------------------------------------------------------
+// Every kernel writes its descriptors in one pats_map_dtype_t OT, independent of DT and of the maps' layout: float32, or
+// float16 / bfloat16 as their raw 16 bits.  The float32 value the fp32-output kernel would have stored exists in a register
+// (NCHW kernels) or in the fp32 LDS tile (channels-last kernels) and is rounded ONCE, to nearest even, where it leaves - what
+// tensor.to(dtype) does: fp16 overflows to inf above 65 520 and keeps its subnormals, +-0 / +-inf pass, a NaN stays a NaN.  The
+// casts below are the hardware's RNE conversions (v_cvt_f16_f32 / v_cvt_pk_f16_f32, v_cvt_pk_bf16_f32), never the packed
+// round-toward-zero one.  OT == PATS_MAP_F32 compiles to the code there was before the parameter existed.  Only the store
+// shapes change with the element size: rows of 145 / 65 halves start at 2 mod 4 bytes on every other channel, so the NCHW
+// kernels' pairs are 4-byte stores at 2-byte alignment, and the channels-last kernels' linear copies carry 8 elements per 16
+// bytes (every block - 8 x 145, 64 x 145, 128 x 65 halves - is still a multiple of 16 bytes).
+template <int OT> using out_t = map_t<OT>;
+template <int OT>
+__device__ __forceinline__ out_t<OT> narrow(float v) {
+    if constexpr (OT == PATS_MAP_F32) return v;
+    else if constexpr (OT == PATS_MAP_F16) return __builtin_bit_cast(uint16_t, (_Float16)v);
+    else return __builtin_bit_cast(uint16_t, (__bf16)v);
+}
+template <int OT>
+__device__ __forceinline__ uint32_t narrow2(float lo, float hi) {      // two neighbouring half outputs as one 32-bit word
+    return (uint32_t)narrow<OT>(lo) | ((uint32_t)narrow<OT>(hi) << 16);
+}
+template <int POL>
+__device__ __forceinline__ void sth2(uint16_t* p, uint32_t v) {        // ... stored as ONE 4-byte write at 2-byte alignment
+    u32u* q = reinterpret_cast<u32u*>(p);
+    if (POL & 2) __builtin_nontemporal_store(v, q);
+    else *q = v;
+}
+// eight consecutive floats of a 32-byte aligned LDS tile -> eight half outputs, one 16-byte word of the linear copy
+template <int OT>
+__device__ __forceinline__ u4 narrow8(const float* t) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 a = *reinterpret_cast<const f4*>(t), b = *reinterpret_cast<const f4*>(t + 4);
+    u4 r;
+    r.x = narrow2<OT>(a.x, a.y); r.y = narrow2<OT>(a.z, a.w);
+    r.z = narrow2<OT>(b.x, b.y); r.w = narrow2<OT>(b.z, b.w);
+    return r;
+}
+
 // ---- fine level ------------------------------------------------------------------------------
 // the AvgPool2d(2,1,1) sample over the taps q, q + 1 (one pair load) and q + row, q + row + 1             second_layer.py:73-79
 template <int DT, int POL>
@@ -111,22 +149,24 @@ __device__ __forceinline__ float single_tap(const map_t<DT>* q) {
 // a lane owns the points l, l + 64, l + 128 (< 145) of every channel it visits, so the source offsets of the three maps are
 // computed ONCE per lane (no division in the channel loop) and a channel's 145 outputs leave as three coalesced stores.
 // The channel loop is split by source (title / map 0 / map 1 / map 2): wave-uniform, branch-free bodies.
-template <int DT, int POL>
+// Half output: a lane owns the NEIGHBOURING points 2l, 2l + 1 (< 128) and 128 + l (< 145) instead, so that a channel leaves as
+// one 4-byte pair store per lane (at 2-byte alignment in the odd channels) and one 2-byte store of 17 lanes.
+template <int DT, int POL, int OT>
 __global__ void __launch_bounds__(256)
 fine_desc_kernel(const map_t<DT>* __restrict__ f0, const map_t<DT>* __restrict__ f1,
                  const map_t<DT>* __restrict__ f2, const float* __restrict__ title,
-                 const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
+                 const float* __restrict__ rubbish, int64_t B, out_t<OT>* __restrict__ desc,
                  const int64_t* __restrict__ B_live) {
     const int64_t n = blockIdx.x;              // s * B + b : index into the stacked maps
     const int64_t b = n % B;
     if (B_live && b >= *B_live) return;        // counted launch: rows past the device-side total are padding
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* o = desc + n * 264 * 145;
+    out_t<OT>* o = desc + n * 264 * 145;
     int pt[3], off0[3], off1[3];
     bool live[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
-        const int p = lane + 64 * g;
+        const int p = OT == PATS_MAP_F32 ? lane + 64 * g : (g < 2 ? 2 * lane + g : 128 + lane);
         live[g] = p < 145;
         pt[g] = p < 144 ? p : 0;                               // positions (k // 12, k % 12); the dustbin column reads nothing
         const int r = pt[g] / 12, c = pt[g] - r * 12;
@@ -135,10 +175,15 @@ fine_desc_kernel(const map_t<DT>* __restrict__ f0, const map_t<DT>* __restrict__
     }
     const bool dust = lane == 16;                              // group 2 of lane 16 is point 144: the dustbin feature column
     auto put = [&](int ch, float v0, float v1, float v2) {
-        float* row = o + ch * 145;
-        stm<POL>(row + lane, v0);
-        stm<POL>(row + lane + 64, v1);
-        if (live[2]) stm<POL>(row + lane + 128, dust ? rubbish[b * 264 + ch] : v2);           // second_layer.py:83,85
+        out_t<OT>* row = o + ch * 145;
+        if constexpr (OT == PATS_MAP_F32) {
+            stm<POL>(row + lane, v0);
+            stm<POL>(row + lane + 64, v1);
+            if (live[2]) stm<POL>(row + lane + 128, dust ? rubbish[b * 264 + ch] : v2);       // second_layer.py:83,85
+        } else {
+            sth2<POL>(row + 2 * lane, narrow2<OT>(v0, v1));
+            if (live[2]) stm<POL>(row + lane + 128, narrow<OT>(dust ? rubbish[b * 264 + ch] : v2));
+        }
     };
     for (int ch = wave; ch < 8; ch += 4) {                     // the 8-channel "title"                         :82,84
         const float v = title[b * 8 + ch];
@@ -210,14 +255,15 @@ __device__ __forceinline__ third_point third_point_at(const float* __restrict__ 
 // The per-point kernel (the default until round 7; pats_set_third_gather(1) selects it): one workgroup (256 threads = 4 waves)
 // per point; wave w handles channels 32w .. 32w+31, eight at a time (sixteen window loads in flight, then sixteen stores);
 // lane = window cell.  The dustbin feature column is written once per wave by 32 lanes (one channel each) instead of by
-// lane 0 inside the channel loop.
-template <int POL>
+// lane 0 inside the channel loop.  Half output on NCHW fp32 maps is this kernel's (the point-tiled one stays float32 only): a
+// lane's window cell is one 2-byte store, which any half output's alignment takes.
+template <int POL, int OT>
 __global__ void __launch_bounds__(256)
 third_desc_point_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
                   const float* __restrict__ mk0, const float* __restrict__ mk1,
                   const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
                   const float* __restrict__ rubbish, int64_t P, int64_t B,
-                  float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                  out_t<OT>* __restrict__ out0, out_t<OT>* __restrict__ out1, int64_t* __restrict__ ps_out,
                   int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
     constexpr int W = 8, M = 52, C = 128;
     // throughput mode: the launch covers the capacity, the count is on the device.
@@ -240,8 +286,8 @@ third_desc_point_kernel(const float* __restrict__ ff0, const float* __restrict__
     // NHWC row index -> (batch, y, x) of the NCHW map
     const long long bb0 = i0 / (M * M), r0 = i0 - bb0 * (M * M);
     const long long bb1 = i1 / (M * M), r1 = i1 - bb1 * (M * M);
-    float* o0 = out0 + p * C * 65;
-    float* o1 = out1 + p * C * 65;
+    out_t<OT>* o0 = out0 + p * C * 65;
+    out_t<OT>* o1 = out1 + p * C * 65;
     const float* src0 = ff0 + bb0 * C * (M * M) + r0;
     const float* src1 = ff1 + bb1 * C * (M * M) + r1;
 #pragma unroll 1
@@ -255,15 +301,15 @@ third_desc_point_kernel(const float* __restrict__ ff0, const float* __restrict__
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            stm<POL>(o0 + (c0 + k) * 65 + lane, a[k] + ke[k]);
-            stm<POL>(o1 + (c0 + k) * 65 + lane, c[k] + ke[k]);
+            stm<POL>(o0 + (c0 + k) * 65 + lane, narrow<OT>(a[k] + ke[k]));
+            stm<POL>(o1 + (c0 + k) * 65 + lane, narrow<OT>(c[k] + ke[k]));
         }
     }
     if (lane < 32) {
         const int ch = 32 * wave + lane;
         const float rb = rubbish[(tp.bb2 * C + ch) * 144 + tp.i2];
-        o0[ch * 65 + 64] = rb;                                                   // :145-146
-        o1[ch * 65 + 64] = rb;
+        o0[ch * 65 + 64] = narrow<OT>(rb);                                       // :145-146
+        o1[ch * 65 + 64] = narrow<OT>(rb);
     }
 }
 
@@ -362,14 +408,15 @@ third_desc_kernel(const float* __restrict__ ff0, const float* __restrict__ ff1,
 // 8-byte write.  A pair starts at an even row i of the NHWC view (s0, q0 are multiples of 4, M is even), so it never straddles
 // two images, and the clamp of third_desc_kernel treats both cells alike: a pair below row 0 reads row 0 twice, one past the
 // last row reads the last row twice.  Wave w handles channels 32w .. 32w+31, sixteen at a time (eight pairs per side in
-// flight, then sixteen stores); XCD-aware order and the dustbin column as in third_desc_point_kernel.
-template <int DT, int POL>
+// flight, then sixteen stores); XCD-aware order and the dustbin column as in third_desc_point_kernel.  Half output: the pair
+// leaves as one 4-byte write at 2-byte alignment (rows of 65 halves), the dustbin store stays scalar.
+template <int DT, int POL, int OT>
 __global__ void __launch_bounds__(256)
 third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restrict__ ff1,
                        const float* __restrict__ mk0, const float* __restrict__ mk1,
                        const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
                        const float* __restrict__ rubbish, int64_t P, int64_t B,
-                       float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                       out_t<OT>* __restrict__ out0, out_t<OT>* __restrict__ out1, int64_t* __restrict__ ps_out,
                        int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
     constexpr int M = 52, C = 128;
     int64_t live = P;
@@ -396,8 +443,8 @@ third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restr
         u = lo ? (u & 0xffffu) * 0x10001u : u;
         return hi ? (u >> 16) * 0x10001u : u;
     };
-    float* o0 = out0 + p * C * 65 + 2 * cp;
-    float* o1 = out1 + p * C * 65 + 2 * cp;
+    out_t<OT>* o0 = out0 + p * C * 65 + 2 * cp;
+    out_t<OT>* o1 = out1 + p * C * 65 + 2 * cp;
 #pragma unroll 1
     for (int c0 = 32 * wave + sub; c0 < 32 * wave + 32; c0 += 16) {
         uint32_t a[8], c[8];
@@ -414,15 +461,20 @@ third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restr
             f2s x, y;
             x.x = widen<DT>(u) + ke[k].x; x.y = widen_hi<DT>(u) + ke[k].y;
             y.x = widen<DT>(v) + ke[k].x; y.y = widen_hi<DT>(v) + ke[k].y;
-            stm2<POL>(o0 + (c0 + 2 * k) * 65, x);
-            stm2<POL>(o1 + (c0 + 2 * k) * 65, y);
+            if constexpr (OT == PATS_MAP_F32) {
+                stm2<POL>(o0 + (c0 + 2 * k) * 65, x);
+                stm2<POL>(o1 + (c0 + 2 * k) * 65, y);
+            } else {
+                sth2<POL>(o0 + (c0 + 2 * k) * 65, narrow2<OT>(x.x, x.y));
+                sth2<POL>(o1 + (c0 + 2 * k) * 65, narrow2<OT>(y.x, y.y));
+            }
         }
     }
     if (lane < 32) {
         const int ch = 32 * wave + lane;
         const float rb = rubbish[(tp.bb2 * C + ch) * 144 + tp.i2];
-        out0[p * C * 65 + ch * 65 + 64] = rb;                                     // :145-146
-        out1[p * C * 65 + ch * 65 + 64] = rb;
+        out0[p * C * 65 + ch * 65 + 64] = narrow<OT>(rb);                         // :145-146
+        out1[p * C * 65 + ch * 65 + 64] = narrow<OT>(rb);
     }
 }
 
@@ -439,14 +491,15 @@ third_desc_half_kernel(const uint16_t* __restrict__ ff0, const uint16_t* __restr
 // operation order per element as the NCHW kernels: bit-identical outputs (tests/test_gpu_parity.py).
 
 // one workgroup per (point, side): 64 pixels x 128 channels in, [128, 65] out.  Only the stage that brings the window into
-// LDS depends on the element type.
-template <int DT, int POL>
+// LDS depends on the map element type.  Half output: the fp32 tile leaves as 1 040 words of 16 bytes, eight elements each
+// rounded after their kenc add (out0 / out1 16-byte aligned then; a point's block is 16 640 bytes).
+template <int DT, int POL, int OT>
 __global__ void __launch_bounds__(256)
 third_desc_nhwc_kernel(const map_t<DT>* __restrict__ ff0, const map_t<DT>* __restrict__ ff1,
                        const float* __restrict__ mk0, const float* __restrict__ mk1,
                        const int64_t* __restrict__ b_ids, const float* __restrict__ kenc,
                        const float* __restrict__ rubbish, int64_t P, int64_t B,
-                       float* __restrict__ out0, float* __restrict__ out1, int64_t* __restrict__ ps_out,
+                       out_t<OT>* __restrict__ out0, out_t<OT>* __restrict__ out1, int64_t* __restrict__ ps_out,
                        int64_t* __restrict__ pt_out, const int64_t* __restrict__ P_dev) {
     constexpr int M = 52, C = 128, NT = 65;
     __shared__ __attribute__((aligned(16))) float tile[C * NT];
@@ -491,11 +544,24 @@ third_desc_nhwc_kernel(const map_t<DT>* __restrict__ ff0, const map_t<DT>* __res
         }
     }
     // + self.kenc(kpts) rides on the way out: element e = c * 65 + n of the output takes kenc[c, n]       :139-140
-    float ke[33];
+    constexpr int KE = OT == PATS_MAP_F32 ? 33 : 40;       // half output: lane t takes elements 8 (t + 256 r) .. + 7, r < 5
+    float ke[KE];
+    if constexpr (OT == PATS_MAP_F32) {
 #pragma unroll
-    for (int r = 0; r < 33; ++r) {
-        const int e = t + 256 * r, c = e / NT, n = e - c * NT;
-        ke[r] = kenc[(e < C * NT && n < 64) ? c * 64 + n : 0];
+        for (int r = 0; r < 33; ++r) {
+            const int e = t + 256 * r, c = e / NT, n = e - c * NT;
+            ke[r] = kenc[(e < C * NT && n < 64) ? c * 64 + n : 0];
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+#pragma unroll
+            for (int h = 0; h < 8; ++h) {
+                const int e0 = 8 * (t + 256 * r), c0 = e0 / NT, n0 = e0 - c0 * NT + h;      // a word spans two rows at most
+                const int c = n0 < NT ? c0 : c0 + 1, n = n0 < NT ? n0 : n0 - NT;
+                ke[8 * r + h] = kenc[(e0 < C * NT && n < 64) ? c * 64 + n : 0];
+            }
+        }
     }
     if constexpr (DT == PATS_MAP_F32) {
 #pragma unroll
@@ -516,11 +582,29 @@ third_desc_nhwc_kernel(const map_t<DT>* __restrict__ ff0, const map_t<DT>* __res
     }
     if (t < C) tile[t * NT + 64] = rb;                                                                      // :145-146
     wg_barrier();
-    float* o = (side ? out1 : out0) + p * C * NT;
+    out_t<OT>* o = (side ? out1 : out0) + p * C * NT;
+    if constexpr (OT == PATS_MAP_F32) {
 #pragma unroll
-    for (int r = 0; r < 33; ++r) {
-        const int e = t + 256 * r, c = e / NT, n = e - c * NT;
-        if (e < C * NT) stm<POL>(o + e, n < 64 ? tile[e] + ke[r] : tile[e]);
+        for (int r = 0; r < 33; ++r) {
+            const int e = t + 256 * r, c = e / NT, n = e - c * NT;
+            if (e < C * NT) stm<POL>(o + e, n < 64 ? tile[e] + ke[r] : tile[e]);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int q = t + 256 * r;
+            if (q < C * NT / 8) {
+                float x[8];
+                const int n0 = (8 * q) % NT;
+#pragma unroll
+                for (int h = 0; h < 8; ++h)           // column n0 + h (mod 65) of its row: 64 is the dustbin value
+                    x[h] = n0 + h != 64 ? tile[8 * q + h] + ke[8 * r + h] : tile[8 * q + h];
+                u4 w;
+                w.x = narrow2<OT>(x[0], x[1]); w.y = narrow2<OT>(x[2], x[3]);
+                w.z = narrow2<OT>(x[4], x[5]); w.w = narrow2<OT>(x[6], x[7]);
+                stm<POL>(reinterpret_cast<u4*>(o) + q, w);
+            }
+        }
     }
 }
 
@@ -532,10 +616,11 @@ third_desc_nhwc_kernel(const map_t<DT>* __restrict__ ff0, const map_t<DT>* __res
 //   half  64 channels of a pixel are 128 bytes = 8 lanes x 16 bytes: lane = (node % 8, eight channels), a wave takes 8 nodes,
 //         the workgroup 32 per group, 4.5 groups of the 144 nodes (waves 2 and 3 sit out the last one).  Every load
 //         instruction reads 8 whole 128-byte lines.
-template <int DT, int TAPS, int POL>
+// The LDS tile is float32 for every output type; half output is rounded in the copy (eight elements per 16-byte word).
+template <int DT, int TAPS, int POL, int OT>
 __device__ __forceinline__ void fine_tile_pass(const map_t<DT>* __restrict__ img, int cpp, int ch0, int rowpix, int step,
-                                               int first, float* tile, float* __restrict__ o, const float* __restrict__ rub,
-                                               int t) {
+                                               int first, float* tile, out_t<OT>* __restrict__ o,
+                                               const float* __restrict__ rub, int t) {
     constexpr int NP = 145;
     typedef float f4 __attribute__((ext_vector_type(4)));
     float dust = 0.f;
@@ -601,17 +686,22 @@ __device__ __forceinline__ void fine_tile_pass(const map_t<DT>* __restrict__ img
     }
     if (t < 64) tile[t * NP + 144] = dust;
     wg_barrier();
-    const f4* src = reinterpret_cast<const f4*>(tile);
-    f4* dst = reinterpret_cast<f4*>(o);
-    for (int e = t; e < 64 * NP / 4; e += 256) stm<POL>(dst + e, src[e]);
+    if constexpr (OT == PATS_MAP_F32) {
+        const f4* src = reinterpret_cast<const f4*>(tile);
+        f4* dst = reinterpret_cast<f4*>(o);
+        for (int e = t; e < 64 * NP / 4; e += 256) stm<POL>(dst + e, src[e]);
+    } else {
+        u4* dst = reinterpret_cast<u4*>(o);
+        for (int e = t; e < 64 * NP / 8; e += 256) stm<POL>(dst + e, narrow8<OT>(tile + 8 * e));
+    }
     wg_barrier();
 }
 
-template <int DT, int POL>
+template <int DT, int POL, int OT>
 __global__ void __launch_bounds__(256)
 fine_desc_nhwc_kernel(const map_t<DT>* __restrict__ f0, const map_t<DT>* __restrict__ f1,
                       const map_t<DT>* __restrict__ f2, const float* __restrict__ title,
-                      const float* __restrict__ rubbish, int64_t B, float* __restrict__ desc,
+                      const float* __restrict__ rubbish, int64_t B, out_t<OT>* __restrict__ desc,
                       const int64_t* __restrict__ B_live) {
     constexpr int NP = 145;
     __shared__ __attribute__((aligned(16))) float tile[64 * NP];
@@ -619,19 +709,19 @@ fine_desc_nhwc_kernel(const map_t<DT>* __restrict__ f0, const map_t<DT>* __restr
     const int64_t b = n % B;
     if (B_live && b >= *B_live) return;        // counted launch: rows past the device-side total are padding
     const int t = threadIdx.x;
-    float* o = desc + n * 264 * NP;
+    out_t<OT>* o = desc + n * 264 * NP;
     const float* rub = rubbish + b * 264;
     for (int e = t; e < 8 * NP; e += 256) {                    // the 8-channel "title"                         :82,84
         const int ch = e / NP, p = e - ch * NP;
-        o[e] = p == 144 ? rub[ch] : title[b * 8 + ch];
+        o[e] = narrow<OT>(p == 144 ? rub[ch] : title[b * 8 + ch]);
     }
     // map 0 [.,48,48,64]: avgpool(2,1,1) -> 49x49, sample (4r+2, 4c+2) = mean of pixels (4r+1.., 4c+1..)
-    fine_tile_pass<DT, 4, POL>(f0 + n * 48 * 48 * 64, 64, 0, 48, 4, 1, tile, o + 8 * NP, rub + 8, t);
+    fine_tile_pass<DT, 4, POL, OT>(f0 + n * 48 * 48 * 64, 64, 0, 48, 4, 1, tile, o + 8 * NP, rub + 8, t);
     // map 1 [.,24,24,64]: avgpool -> 25x25, sample (2r+1, 2c+1) = mean of pixels (2r.., 2c..)
-    fine_tile_pass<DT, 4, POL>(f1 + n * 24 * 24 * 64, 64, 0, 24, 2, 0, tile, o + 72 * NP, rub + 72, t);
+    fine_tile_pass<DT, 4, POL, OT>(f1 + n * 24 * 24 * 64, 64, 0, 24, 2, 0, tile, o + 72 * NP, rub + 72, t);
     // map 2 [.,12,12,128]: no pooling, sample (r, c)
-    fine_tile_pass<DT, 1, POL>(f2 + n * 144 * 128, 128, 0, 12, 1, 0, tile, o + 136 * NP, rub + 136, t);
-    fine_tile_pass<DT, 1, POL>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
+    fine_tile_pass<DT, 1, POL, OT>(f2 + n * 144 * 128, 128, 0, 12, 1, 0, tile, o + 136 * NP, rub + 136, t);
+    fine_tile_pass<DT, 1, POL, OT>(f2 + n * 144 * 128, 128, 64, 12, 1, 0, tile, o + 200 * NP, rub + 200, t);
 }
 
 // PATS_GATHER_NT = 0..3 (see ldm / stm above), read once per process; without it 0 on NCHW maps, 3 on channels-last maps
@@ -641,36 +731,45 @@ static int gather_policy(bool channels_last) {
 }
 
 template <int V> using int_c = std::integral_constant<int, V>;
-// f(int_c<DT>, int_c<POL>) for a pats_map_dtype_t (validated before) and the store policy of the maps' layout
+// f(int_c<DT>, int_c<POL>, int_c<OT>) for the maps' and the outputs' pats_map_dtype_t (validated before) and the store policy of
+// the maps' layout
 template <typename F>
-static void with_gather(int dt, bool channels_last, F&& f) {
-    auto pol = [&](auto d) {
+static void with_gather(int dt, int ot, bool channels_last, F&& f) {
+    auto pol = [&](auto d, auto o) {
         switch (gather_policy(channels_last)) {
-            case 0: f(d, int_c<0>{}); break;
-            case 1: f(d, int_c<1>{}); break;
-            case 2: f(d, int_c<2>{}); break;
-            default: f(d, int_c<3>{}); break;
+            case 0: f(d, int_c<0>{}, o); break;
+            case 1: f(d, int_c<1>{}, o); break;
+            case 2: f(d, int_c<2>{}, o); break;
+            default: f(d, int_c<3>{}, o); break;
+        }
+    };
+    auto out = [&](auto d) {
+        switch (ot) {
+            case PATS_MAP_F16: pol(d, int_c<PATS_MAP_F16>{}); break;
+            case PATS_MAP_BF16: pol(d, int_c<PATS_MAP_BF16>{}); break;
+            default: pol(d, int_c<PATS_MAP_F32>{}); break;
         }
     };
     switch (dt) {
-        case PATS_MAP_F16: pol(int_c<PATS_MAP_F16>{}); break;
-        case PATS_MAP_BF16: pol(int_c<PATS_MAP_BF16>{}); break;
-        default: pol(int_c<PATS_MAP_F32>{}); break;
+        case PATS_MAP_F16: out(int_c<PATS_MAP_F16>{}); break;
+        case PATS_MAP_BF16: out(int_c<PATS_MAP_BF16>{}); break;
+        default: out(int_c<PATS_MAP_F32>{}); break;
     }
 }
 
-// a15 over B stacked-image pairs (2 B workgroups); B_dev: the device-side row count of a counted launch, or null
+// a15 over B stacked-image pairs (2 B workgroups); B_dev: the device-side row count of a counted launch, or null; desc in
+// elements of `ot`
 static int launch_fine(const void* f0, const void* f1, const void* f2, int dt, bool channels_last, const float* title,
-                       const float* rubbish, int64_t B, const int64_t* B_dev, float* desc, pats_stream_t stream) {
-    with_gather(dt, channels_last, [&](auto d, auto pol) {
-        constexpr int DT = decltype(d)::value, POL = decltype(pol)::value;
+                       const float* rubbish, int64_t B, const int64_t* B_dev, void* desc, int ot, pats_stream_t stream) {
+    with_gather(dt, ot, channels_last, [&](auto d, auto pol, auto o) {
+        constexpr int DT = decltype(d)::value, POL = decltype(pol)::value, OT = decltype(o)::value;
         using T = map_t<DT>;
         auto go = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3((unsigned)(2 * B)), dim3(256), 0, as_stream(stream), (const T*)f0, (const T*)f1,
-                               (const T*)f2, title, rubbish, B, desc, B_dev);
+                               (const T*)f2, title, rubbish, B, (out_t<OT>*)desc, B_dev);
         };
-        if (channels_last) go(fine_desc_nhwc_kernel<DT, POL>);
-        else go(fine_desc_kernel<DT, POL>);
+        if (channels_last) go(fine_desc_nhwc_kernel<DT, POL, OT>);
+        else go(fine_desc_kernel<DT, POL, OT>);
     });
     return check_launch(channels_last ? "fine_desc_nhwc_kernel" : "fine_desc_kernel");
 }
@@ -678,29 +777,34 @@ static int launch_fine(const void* f0, const void* f1, const void* f2, int dt, b
 // a16 over a capacity of P points; P_dev: the device-side point count, or null.  The NCHW fp32 maps take the point-tiled
 // third_desc_kernel, or - pats_set_third_gather(1), or outputs that are not 16-byte aligned - third_desc_point_kernel.  Same
 // store policy default as the other NCHW gathers: non-temporal stores measured within 1 % of plain ones here
-// (profiles/r07_third_gather_ab.txt).
+// (profiles/r07_third_gather_ab.txt).  out0 / out1 in elements of `ot`; half output on these maps is always the per-point
+// kernel's (2-byte stores: whatever alignment a half output has, and whatever pats_set_third_gather says).
 static int g_third_gather = 0;
 static int launch_third(const void* f0, const void* f1, int dt, bool channels_last, const float* mkpts0_c,
                         const float* mkpts1_c, const int64_t* b_ids, const float* kenc, const float* rubbish, int64_t P_cap,
-                        const int64_t* P_dev, int64_t B, float* out0, float* out1, int64_t* p_s_out, int64_t* p_t_out,
+                        const int64_t* P_dev, int64_t B, void* out0, void* out1, int ot, int64_t* p_s_out, int64_t* p_t_out,
                         pats_stream_t stream) {
     const char* name = "third_desc_nhwc_kernel";
-    with_gather(dt, channels_last, [&](auto d, auto pol) {
-        constexpr int DT = decltype(d)::value, POL = decltype(pol)::value;
+    with_gather(dt, ot, channels_last, [&](auto d, auto pol, auto o) {
+        constexpr int DT = decltype(d)::value, POL = decltype(pol)::value, OT = decltype(o)::value;
         using T = map_t<DT>;
-        auto go = [&](auto kernel, const char* kname, int64_t blocks) {
+        auto go = [&](auto kernel, const char* kname, int64_t blocks, auto* o0, auto* o1) {
             hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const T*)f0, (const T*)f1,
-                               mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, B, out0, out1, p_s_out, p_t_out, P_dev);
+                               mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, B, o0, o1, p_s_out, p_t_out, P_dev);
             name = kname;
         };
+        out_t<OT>* const o0 = (out_t<OT>*)out0;
+        out_t<OT>* const o1 = (out_t<OT>*)out1;
         if (channels_last)
-            go(third_desc_nhwc_kernel<DT, POL>, "third_desc_nhwc_kernel", (P_cap + 7) / 8 * 16);
+            go(third_desc_nhwc_kernel<DT, POL, OT>, "third_desc_nhwc_kernel", (P_cap + 7) / 8 * 16, o0, o1);
         else if constexpr (DT != PATS_MAP_F32)
-            go(third_desc_half_kernel<DT, POL>, "third_desc_half_kernel", (P_cap + 7) / 8 * 8);
+            go(third_desc_half_kernel<DT, POL, OT>, "third_desc_half_kernel", (P_cap + 7) / 8 * 8, o0, o1);
+        else if constexpr (OT != PATS_MAP_F32)
+            go(third_desc_point_kernel<POL, OT>, "third_desc_point_kernel", (P_cap + 7) / 8 * 8, o0, o1);
         else if (g_third_gather == 1 || ((uintptr_t)out0 | (uintptr_t)out1) % 16 != 0)
-            go(third_desc_point_kernel<POL>, "third_desc_point_kernel", (P_cap + 7) / 8 * 8);
+            go(third_desc_point_kernel<POL, OT>, "third_desc_point_kernel", (P_cap + 7) / 8 * 8, o0, o1);
         else
-            go(third_desc_kernel<POL>, "third_desc_kernel", ((P_cap + THIRD_TILE - 1) / THIRD_TILE + 7) / 8 * 8);
+            go(third_desc_kernel<POL>, "third_desc_kernel", ((P_cap + THIRD_TILE - 1) / THIRD_TILE + 7) / 8 * 8, o0, o1);
     });
     return check_launch(name);
 }
@@ -721,7 +825,7 @@ extern "C" int pats_fine_descriptors_f32(const float* feat0, const float* feat1,
     PATS_REQUIRE(B >= 0, "fine_descriptors: bad shape");
     if (B == 0) return PATS_OK;
     PATS_REQUIRE(feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors: null pointer");
-    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, false, title, rubbish, B, nullptr, desc, stream);
+    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, false, title, rubbish, B, nullptr, desc, PATS_MAP_F32, stream);
 }
 
 // a15 launched over a CAPACITY of B_cap rows with the number of rows in use on the device (throughput mode: the fine level's
@@ -735,7 +839,7 @@ extern "C" int pats_fine_descriptors_counted_f32(const float* feat0, const float
     if (channels_last)
         PATS_REQUIRE(((uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)feat2 | (uintptr_t)desc) % 16 == 0,
                      "fine_descriptors_counted: channels-last maps and desc must be 16-byte aligned");
-    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, channels_last, title, rubbish, B_cap, B_dev, desc, stream);
+    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, channels_last, title, rubbish, B_cap, B_dev, desc, PATS_MAP_F32, stream);
 }
 
 extern "C" int pats_third_descriptors_f32(const float* feat_f0, const float* feat_f1,
@@ -748,7 +852,7 @@ extern "C" int pats_third_descriptors_f32(const float* feat_f0, const float* fea
     PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors: null pointer");
     return launch_third(feat_f0, feat_f1, PATS_MAP_F32, false, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P, nullptr, B, out0,
-                        out1, p_s_out, p_t_out, stream);
+                        out1, PATS_MAP_F32, p_s_out, p_t_out, stream);
 }
 
 extern "C" int pats_third_descriptors_counted_f32(const float* feat_f0, const float* feat_f1,
@@ -761,7 +865,7 @@ extern "C" int pats_third_descriptors_counted_f32(const float* feat_f0, const fl
     PATS_REQUIRE(P_dev && feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors_counted: null pointer");
     return launch_third(feat_f0, feat_f1, PATS_MAP_F32, false, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
-                        out1, p_s_out, p_t_out, stream);
+                        out1, PATS_MAP_F32, p_s_out, p_t_out, stream);
 }
 
 extern "C" int pats_fine_descriptors_nhwc_f32(const float* feat0, const float* feat1, const float* feat2,
@@ -772,7 +876,7 @@ extern "C" int pats_fine_descriptors_nhwc_f32(const float* feat0, const float* f
     PATS_REQUIRE(feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors_nhwc: null pointer");
     PATS_REQUIRE(((uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)feat2 | (uintptr_t)desc) % 16 == 0,
                  "fine_descriptors_nhwc: maps and desc must be 16-byte aligned");
-    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, true, title, rubbish, B, nullptr, desc, stream);
+    return launch_fine(feat0, feat1, feat2, PATS_MAP_F32, true, title, rubbish, B, nullptr, desc, PATS_MAP_F32, stream);
 }
 
 extern "C" int pats_third_descriptors_nhwc_f32(const float* feat_f0, const float* feat_f1,
@@ -785,7 +889,7 @@ extern "C" int pats_third_descriptors_nhwc_f32(const float* feat_f0, const float
     PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
                  "third_descriptors_nhwc: null pointer");
     return launch_third(feat_f0, feat_f1, PATS_MAP_F32, true, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
-                        out1, p_s_out, p_t_out, stream);
+                        out1, PATS_MAP_F32, p_s_out, p_t_out, stream);
 }
 
 
@@ -804,7 +908,7 @@ extern "C" int pats_fine_descriptors_typed(const void* feat0, const void* feat1,
         PATS_REQUIRE((maps | (uintptr_t)desc) % 16 == 0, "fine_descriptors_typed: channels-last maps and desc must be 16-byte aligned");
     else                    // 4-byte pair / float loads (f32: 8-byte pairs at 4-byte alignment)
         PATS_REQUIRE(maps % 4 == 0, "fine_descriptors_typed: NCHW maps must be 4-byte aligned");
-    return launch_fine(feat0, feat1, feat2, dtype, channels_last, title, rubbish, B_cap, B_dev, desc, stream);
+    return launch_fine(feat0, feat1, feat2, dtype, channels_last, title, rubbish, B_cap, B_dev, desc, PATS_MAP_F32, stream);
 }
 
 extern "C" int pats_third_descriptors_typed(const void* feat_f0, const void* feat_f1, pats_map_dtype_t dtype, int channels_last,
@@ -825,5 +929,63 @@ extern "C" int pats_third_descriptors_typed(const void* feat_f0, const void* fea
     else                    // 4-byte float / cell-pair loads
         PATS_REQUIRE(maps % 4 == 0, "third_descriptors_typed: NCHW maps must be 4-byte aligned");
     return launch_third(feat_f0, feat_f1, dtype, channels_last, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
-                        out1, p_s_out, p_t_out, stream);
+                        out1, PATS_MAP_F32, p_s_out, p_t_out, stream);
+}
+
+
+// The two entries above with the OUTPUT element type selectable too: each element is the float32 value the fp32-output kernel
+// stores, rounded once to `out_dtype` (nearest even) at the store.  PATS_MAP_F32 is the call above.
+extern "C" int pats_fine_descriptors_typed_out(const void* feat0, const void* feat1, const void* feat2, pats_map_dtype_t dtype,
+                                               int channels_last, const float* title, const float* rubbish, int64_t B_cap,
+                                               const int64_t* B_dev, void* desc, pats_map_dtype_t out_dtype,
+                                               pats_stream_t stream) {
+    PATS_REQUIRE(out_dtype == PATS_MAP_F32 || out_dtype == PATS_MAP_F16 || out_dtype == PATS_MAP_BF16,
+                 "fine_descriptors_typed_out: unknown output dtype %d", (int)out_dtype);
+    if (out_dtype == PATS_MAP_F32)
+        return pats_fine_descriptors_typed(feat0, feat1, feat2, dtype, channels_last, title, rubbish, B_cap, B_dev, (float*)desc,
+                                           stream);
+    PATS_REQUIRE(dtype == PATS_MAP_F32 || dtype == PATS_MAP_F16 || dtype == PATS_MAP_BF16,
+                 "fine_descriptors_typed_out: unknown map dtype %d", (int)dtype);
+    PATS_REQUIRE(B_cap >= 0, "fine_descriptors_typed_out: bad shape");
+    if (B_cap == 0) return PATS_OK;
+    PATS_REQUIRE(feat0 && feat1 && feat2 && title && rubbish && desc, "fine_descriptors_typed_out: null pointer");
+    const uintptr_t maps = (uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)feat2;
+    if (channels_last) {    // 16-byte map loads, 16-byte stores of desc
+        PATS_REQUIRE((maps | (uintptr_t)desc) % 16 == 0,
+                     "fine_descriptors_typed_out: channels-last maps and desc must be 16-byte aligned");
+    } else {                // 4-byte pair / float loads; pair stores at 2-byte alignment
+        PATS_REQUIRE(maps % 4 == 0, "fine_descriptors_typed_out: NCHW maps must be 4-byte aligned");
+        PATS_REQUIRE((uintptr_t)desc % 2 == 0, "fine_descriptors_typed_out: a half desc must be 2-byte aligned");
+    }
+    return launch_fine(feat0, feat1, feat2, dtype, channels_last, title, rubbish, B_cap, B_dev, desc, out_dtype, stream);
+}
+
+extern "C" int pats_third_descriptors_typed_out(const void* feat_f0, const void* feat_f1, pats_map_dtype_t dtype,
+                                                int channels_last, const float* mkpts0_c, const float* mkpts1_c,
+                                                const int64_t* b_ids, const float* kenc, const float* rubbish, int64_t P_cap,
+                                                const int64_t* P_dev, int64_t B, void* out0, void* out1,
+                                                pats_map_dtype_t out_dtype, int64_t* p_s_out, int64_t* p_t_out,
+                                                pats_stream_t stream) {
+    PATS_REQUIRE(out_dtype == PATS_MAP_F32 || out_dtype == PATS_MAP_F16 || out_dtype == PATS_MAP_BF16,
+                 "third_descriptors_typed_out: unknown output dtype %d", (int)out_dtype);
+    if (out_dtype == PATS_MAP_F32)
+        return pats_third_descriptors_typed(feat_f0, feat_f1, dtype, channels_last, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap,
+                                            P_dev, B, (float*)out0, (float*)out1, p_s_out, p_t_out, stream);
+    PATS_REQUIRE(dtype == PATS_MAP_F32 || dtype == PATS_MAP_F16 || dtype == PATS_MAP_BF16,
+                 "third_descriptors_typed_out: unknown map dtype %d", (int)dtype);
+    PATS_REQUIRE(P_cap >= 0 && B > 0, "third_descriptors_typed_out: bad shape");
+    if (P_cap == 0) return PATS_OK;
+    PATS_REQUIRE(feat_f0 && feat_f1 && mkpts0_c && mkpts1_c && b_ids && kenc && rubbish && out0 && out1,
+                 "third_descriptors_typed_out: null pointer");
+    const uintptr_t maps = (uintptr_t)feat_f0 | (uintptr_t)feat_f1, outs = (uintptr_t)out0 | (uintptr_t)out1;
+    if (channels_last) {    // 16-byte loads of half pixels (f32: 4-byte loads); 16-byte stores of the half outputs
+        PATS_REQUIRE(maps % (dtype == PATS_MAP_F32 ? 4 : 16) == 0,
+                     "third_descriptors_typed_out: channels-last maps must be %d-byte aligned", dtype == PATS_MAP_F32 ? 4 : 16);
+        PATS_REQUIRE(outs % 16 == 0, "third_descriptors_typed_out: half outputs of channels-last maps must be 16-byte aligned");
+    } else {                // 4-byte float / cell-pair loads; 2-byte stores or pair stores at 2-byte alignment
+        PATS_REQUIRE(maps % 4 == 0, "third_descriptors_typed_out: NCHW maps must be 4-byte aligned");
+        PATS_REQUIRE(outs % 2 == 0, "third_descriptors_typed_out: half outputs must be 2-byte aligned");
+    }
+    return launch_third(feat_f0, feat_f1, dtype, channels_last, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, P_cap, P_dev, B, out0,
+                        out1, out_dtype, p_s_out, p_t_out, stream);
 }

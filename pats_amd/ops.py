@@ -920,13 +920,33 @@ def _widen(t):
     return t.float() if isinstance(t, torch.Tensor) and t.dtype in (torch.float16, torch.bfloat16) else t
 
 
-def fine_descriptors(desc0_, title, rubbish, out=None, count=None):
+def _out_dtype(outs, out_dtype, who):
+    """The element type a gather writes: that of `out` when given (all of `outs` must agree, and out_dtype must not
+    contradict them), else out_dtype, else float32."""
+    if out_dtype is not None and not isinstance(out_dtype, torch.dtype):
+        raise TypeError("%s: out_dtype must be a torch.dtype" % who)
+    dts = {t.dtype for t in outs if isinstance(t, torch.Tensor)}
+    if len(dts) > 1:
+        raise RuntimeError("%s: out[0] and out[1] must have one dtype, got %s" % (who, " and ".join(sorted(map(str, dts)))))
+    dt = dts.pop() if dts else (out_dtype if out_dtype is not None else torch.float32)
+    if out_dtype is not None and out_dtype != dt:
+        raise RuntimeError("%s: out_dtype %s conflicts with out's dtype %s" % (who, out_dtype, dt))
+    if dt not in _MAP_DTYPES:
+        raise RuntimeError("%s: the output must be float32, float16 or bfloat16, got %s" % (who, dt))
+    return dt
+
+
+def fine_descriptors(desc0_, title, rubbish, out=None, count=None, out_dtype=None):
     """second_layer.py:71-86: desc0_ = the three maps of ResNet2.forward2 on the stacked crops
     ([2B,64,48,48], [2B,64,24,24], [2B,128,12,12]); title [B,8] = compress_1(desc_l); rubbish [B,264]
     = compress_2(desc_l).  Returns desc [2,B,264,145] (desc[0], desc[1] feed the GNN).
     Maps in torch.channels_last memory format (all three) take the channels-last gather: same bits, 0.67x the HBM bytes.
     Maps in float16 / bfloat16 are widened to fp32 exactly in the kernel: desc is float32 and bit-identical to the call on
-    [m.float() for m in desc0_]; title / rubbish may be half too (widened here)."""
+    [m.float() for m in desc0_]; title / rubbish may be half too (widened here).
+    out_dtype (or the dtype of `out`, which decides when given): torch.float32 (default), float16 or bfloat16.  A half desc is
+    the float32 desc rounded once, to nearest even, at the kernel's store - bit-identical to fine_descriptors(...).to(dtype)
+    without the pass over it - and is what cost_ot takes as it lies."""
+    odt = _out_dtype([out] if out is not None else [], out_dtype, "fine_descriptors")
     maps, dtype = _maps_any(list(desc0_), ["desc0_[%d]" % i for i in range(len(desc0_))])
     if len({cl for _, cl in maps}) != 1:       # mixed formats: fall back to the NCHW kernel on contiguous copies
         maps = [(t.contiguous(), False) for t, _ in maps]
@@ -937,23 +957,32 @@ def fine_descriptors(desc0_, title, rubbish, out=None, count=None):
         raise RuntimeError("fine_descriptors: unexpected feature-map shapes")
     ti = _dev(_widen(title), "title").reshape(B, 8)
     ru = _dev(_widen(rubbish), "rubbish").reshape(B, 264)
-    desc = torch.empty((2, B, 264, 145), dtype=torch.float32, device=f0.device) if out is None else _dev(out, "out")
+    desc = torch.empty((2, B, 264, 145), dtype=odt, device=f0.device) if out is None else _dev(out, "out", odt)
     if tuple(desc.shape) != (2, B, 264, 145) or (out is not None and desc.data_ptr() != out.data_ptr()):
         raise RuntimeError("fine_descriptors: out must be a contiguous [2,B,264,145] tensor")
     cnt = _dev(count, "count", torch.int64) if count is not None else None      # device-side row count: B is a capacity
-    _check(_L().pats_fine_descriptors_typed(_ptr(f0), _ptr(f1), _ptr(f2), dtype, int(bool(nhwc)), _ptr(ti), _ptr(ru), B,
-                                            _ptr(cnt), _ptr(desc), _stream()), "fine_descriptors")
+    if odt == torch.float32:
+        _check(_L().pats_fine_descriptors_typed(_ptr(f0), _ptr(f1), _ptr(f2), dtype, int(bool(nhwc)), _ptr(ti), _ptr(ru), B,
+                                                _ptr(cnt), _ptr(desc), _stream()), "fine_descriptors")
+    else:
+        _check(_L().pats_fine_descriptors_typed_out(_ptr(f0), _ptr(f1), _ptr(f2), dtype, int(bool(nhwc)), _ptr(ti), _ptr(ru), B,
+                                                    _ptr(cnt), _ptr(desc), _MAP_DTYPES[odt], _stream()), "fine_descriptors")
     return desc
 
 
-def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, count=None, out=None):
+def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish, count=None, out=None, out_dtype=None):
     """third_layer.py:121-146.  Returns (feat_f0_unfold, feat_f1_unfold [P,128,65], mkpts0_c,
     mkpts1_c [P,2] int64 rounded to the 4-px lattice as the reference reassigns them).
     count: DEVICE int64 [1], the number of points that exist (the tensors are a capacity; rows past it are not written);
     out: optional (o0, o1) to write into.
     Maps in torch.channels_last memory format take the channels-last gather: same bits, under half the HBM bytes.
     Maps in float16 / bfloat16 are widened to fp32 exactly in the kernel: the outputs are float32 and bit-identical to the
-    call on feat_f0.float(), feat_f1.float(); kenc / rubbish may be half too (widened here)."""
+    call on feat_f0.float(), feat_f1.float(); kenc / rubbish may be half too (widened here).
+    out_dtype (or the dtype of out[0] and out[1], which must agree and decide when given): torch.float32 (default), float16 or
+    bfloat16.  Half outputs are the float32 outputs rounded once, to nearest even, at the kernel's store - bit-identical to
+    converting them afterwards - and are what third_level takes as they lie; the rounded points do not change.  Half outputs
+    of channels-last maps must be 16-byte aligned (fresh tensors are); NCHW ones may sit at any element offset."""
+    odt = _out_dtype(list(out) if out is not None else [], out_dtype, "third_descriptors")
     ((f0, nhwc), (f1, nhwc1)), dtype = _maps_any([feat_f0, feat_f1], ["feat_f0", "feat_f1"])
     if nhwc != nhwc1:
         f0, f1, nhwc = f0.contiguous(), f1.contiguous(), False
@@ -968,18 +997,23 @@ def third_descriptors(feat_f0, feat_f1, mkpts0_c, mkpts1_c, b_ids, kenc, rubbish
     ru = _dev(_widen(rubbish), "rubbish").reshape(B, 128, 144)
     dev = f0.device
     if out is not None:
-        o0, o1 = _dev(out[0], "out[0]"), _dev(out[1], "out[1]")
+        o0, o1 = _dev(out[0], "out[0]", odt), _dev(out[1], "out[1]", odt)
         if tuple(o0.shape) != (P, 128, 65) or o1.shape != o0.shape or o0.data_ptr() != out[0].data_ptr():
             raise RuntimeError("third_descriptors: out must be two contiguous [P,128,65] tensors")
     else:
-        o0 = torch.empty((P, 128, 65), dtype=torch.float32, device=dev)
-        o1 = torch.empty((P, 128, 65), dtype=torch.float32, device=dev)
+        o0 = torch.empty((P, 128, 65), dtype=odt, device=dev)
+        o1 = torch.empty((P, 128, 65), dtype=odt, device=dev)
     ps = torch.empty((P, 2), dtype=torch.int64, device=dev)
     pt = torch.empty((P, 2), dtype=torch.int64, device=dev)
     cnt = _dev(count, "count", torch.int64).reshape(1) if count is not None else None
-    _check(_L().pats_third_descriptors_typed(_ptr(f0), _ptr(f1), dtype, int(bool(nhwc)), _ptr(m0), _ptr(m1), _ptr(bi), _ptr(ke),
-                                             _ptr(ru), P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt), _stream()),
-           "third_descriptors")
+    if odt == torch.float32:
+        _check(_L().pats_third_descriptors_typed(_ptr(f0), _ptr(f1), dtype, int(bool(nhwc)), _ptr(m0), _ptr(m1), _ptr(bi),
+                                                 _ptr(ke), _ptr(ru), P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _ptr(ps), _ptr(pt),
+                                                 _stream()), "third_descriptors")
+    else:
+        _check(_L().pats_third_descriptors_typed_out(_ptr(f0), _ptr(f1), dtype, int(bool(nhwc)), _ptr(m0), _ptr(m1), _ptr(bi),
+                                                     _ptr(ke), _ptr(ru), P, _ptr(cnt), B, _ptr(o0), _ptr(o1), _MAP_DTYPES[odt],
+                                                     _ptr(ps), _ptr(pt), _stream()), "third_descriptors")
     return o0, o1, ps, pt
 
 
