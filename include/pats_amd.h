@@ -657,6 +657,60 @@ int pats_matches_by_row_pair_summary_f32(const float* matches_l, const float* ma
                                          int64_t pairs, float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev,
                                          const int32_t* status, void* workspace, size_t workspace_bytes, pats_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-match confidence (ABI 8, symbols added).  For third-level problem p and centre source cell k in 0..15 (row r of the 8x8
+ * grid inside [2:6, 2:6], in Compute_result's order), with S = exp(Z) the [65,65] plan:
+ *     rowmass = sum of S[r, :] over all 65 columns, dustbin included           (first term of third_layer.py:213)
+ *     winmass = sum of S[r, c] over the 5x5 window around argmax_c S[r, :64], zero outside the 8x8 grid   (:212)
+ *     conf[p,k] = winmass / rowmass        float32, at most 1; computed for all 16 cells whatever label / if_matching1 say
+ * The reference folds rowmass - winmass into a training loss; nothing else of it is kept.  Every entry below is the entry it is
+ * named after with the extra pointer(s): it refuses a null or not 4-byte aligned confidence pointer before any launch
+ * (pats_last_error names the argument), then runs the same implementation with the confidence instantiation of the same kernel
+ * - every other output has the bits of the plain call.  Workspaces are those of the plain entries.
+ *   pats_third_level_typed_conf          conf [P_cap,16] beside mkpts1_f (rows past *P_dev not written); a problem the guard
+ *                                        sends to a re-solve gets the confidence of the re-solved plan
+ *   pats_compute_result_ws_conf_f32      conf [P,16] from a plan in memory
+ *   pats_refine_scatter_conf_f32         conf [P,16] -> conf16 [B,2304] by pts16's permutation; 0 where if_nomatching16 is set.
+ *                                        conf may be null when P == 0
+ *   pats_get_result_chunks(_ragged)_conf_f32   conf16 [rows_cap,n1] -> match_conf [capacity], the slots of matches_l / matches_r
+ *   pats_matches_by_(row_)pair_summary_conf_f32   match_conf [M] -> out_conf, regrouped with the matches.  status may be null in
+ *                                        both: pair_off then holds the pairs + 1 offsets only and P_dev is ignored */
+int pats_third_level_typed_conf(const void* feat0, const void* feat1, pats_map_dtype_t dtype, int64_t P_cap, const int64_t* P_dev,
+                                int D, const float* scale, const float* scale_x, const float* scale_y, const int64_t* p_s,
+                                const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f, float* label,
+                                uint8_t* if_matching1, float* Z, float* conf, pats_stream_t stream);
+int pats_compute_result_ws_conf_f32(const float* scores, int input_is_log, int64_t P, const float* scale_x,
+                                    const float* scale_y, const int64_t* p_s, const int64_t* p_t, int outdoor,
+                                    float* mkpts0_f, float* mkpts1_f, float* whole_loss, float* label,
+                                    uint8_t* if_matching1, float* conf, void* workspace, size_t workspace_bytes,
+                                    pats_stream_t stream);
+int pats_refine_scatter_conf_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f, const float* label,
+                                 int label_stride, const float* conf, int64_t B, int64_t P, uint8_t* if_nomatching16,
+                                 float* pts16, float* conf16, void* workspace, size_t workspace_bytes, pats_stream_t stream);
+int pats_get_result_chunks_conf_f32(int Cmax, int64_t pairs, const uint8_t* masks, const uint8_t* if_nomatching16,
+                                    int64_t rows_cap, const float* pts_new, const float* pts16, const float* scales,
+                                    const float* conf16, const int* patch_size0, const int* patch_size1,
+                                    const uint8_t* left_choice0, const uint8_t* left_choice1, float* matches_l,
+                                    float* matches_r, float* match_conf, int32_t* match_row, int64_t capacity,
+                                    int64_t* count, void* workspace, size_t workspace_bytes, pats_stream_t stream);
+int pats_get_result_chunks_ragged_conf_f32(const pats_pair_table_t* tab, int Cmax, const uint8_t* masks,
+                                           const uint8_t* if_nomatching16, int64_t rows_cap, const float* pts_new,
+                                           const float* pts16, const float* scales, const float* conf16,
+                                           const int* patch_size1, const uint8_t* left_choice0, const uint8_t* left_choice1,
+                                           float* matches_l, float* matches_r, float* match_conf, int32_t* match_row,
+                                           int64_t capacity, int64_t* count, void* workspace, size_t workspace_bytes,
+                                           pats_stream_t stream);
+int pats_matches_by_pair_summary_conf_f32(const float* matches_l, const float* matches_r, const float* match_conf,
+                                          const int32_t* match_row, const int64_t* M_dev, const int32_t* row_cell,
+                                          const int64_t* chunk_base, int Cmax, int64_t pairs, int N, float* out_l, float* out_r,
+                                          float* out_conf, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
+                                          void* workspace, size_t workspace_bytes, pats_stream_t stream);
+int pats_matches_by_row_pair_summary_conf_f32(const float* matches_l, const float* matches_r, const float* match_conf,
+                                              const int32_t* match_row, const int64_t* M_dev, const int32_t* row_pair,
+                                              const int64_t* chunk_base, int Cmax, int64_t pairs, float* out_l, float* out_r,
+                                              float* out_conf, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
+                                              void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the
  * keys, out = prob v.  query [batch,dim,heads,n], key / value [batch,dim,heads,m] (the view

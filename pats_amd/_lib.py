@@ -202,6 +202,27 @@ SIGNATURES = {
                                                   c_void_p, c_void_p, c_size, c_void_p]),
     "pats_matches_by_row_pair_summary_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64,
                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-match confidence: the entries they are named after with the confidence pointer(s) added
+    "pats_third_level_typed_conf": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "pats_compute_result_ws_conf_f32": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_size, c_void_p]),
+    "pats_refine_scatter_conf_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_get_result_chunks_conf_f32": (c_int, [c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_get_result_chunks_ragged_conf_f32": (c_int, [_TAB, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_i64, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_matches_by_pair_summary_conf_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                      c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_size, c_void_p]),
+    "pats_matches_by_row_pair_summary_conf_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_size, c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -237,11 +237,23 @@ def fine_stage(co, nets, cap, if_outdoor=True, merge_new=True, iters=100, events
     return third_gather_stage(fine_solve_stage(co, nets, cap, if_outdoor, merge_new, iters, events), nets, cap)
 
 
-def third_stage(fs, nets, cap, if_outdoor=True, iters=100, events=None):
+def third_stage(fs, nets, cap, if_outdoor=True, iters=100, events=None, confidence=False):
     """third_layer.py:153-170 over the capacity with the count on the device, then pats.py:59-78: the scatter onto the
-    sub-cell grid and get_result for every chunk of every pair."""
+    sub-cell grid and get_result for every chunk of every pair.  confidence: the result gains match_conf [M_cap] float32, the
+    third level's per-match confidence (ops.third_level) carried through the scatter and the compaction beside matches_r."""
     co, rows, P = fs["co"], fs["co"]["rows"], fs["P"]
     e = _timed(events, "third")
+    if confidence:
+        m0f, m1f, label, ifm, conf = ops.third_level(fs["feat0"], fs["feat1"], fs["scale3"], fs["p_s"], fs["p_t"], outdoor=if_outdoor,
+                                                     iters=iters, count=P, return_confidence=True)
+        if e is not None:
+            e.record()
+        ifn16, pts16, conf16 = ops.refine_scatter(fs["merged"], fs["pts2"], m1f, label, conf=conf)
+        ml, mr, mrow, M, mconf = ops.get_result_chunks(rows, ifn16, co["avn"], pts16, co["xsn"], conf16=conf16)
+        stages = dict(fs["stages"], m0f=m0f, m1f=m1f, label=label, ifm=ifm, pts16=pts16, conf=conf, conf16=conf16)
+        return {"matches_l": ml, "matches_r": mr, "match_row": mrow, "match_conf": mconf, "M": M, "P": P, "status": rows.status,
+                "rows": rows, "if_nomatching16": ifn16, "merged": fs["merged"], "K_img": co["K_img"],
+                "crops": (co["new_left"], co["new_right"]), "coarse": co, "stages": stages}
     m0f, m1f, label, ifm = ops.third_level(fs["feat0"], fs["feat1"], fs["scale3"], fs["p_s"], fs["p_t"], outdoor=if_outdoor,
                                            iters=iters, count=P)
     if e is not None:
@@ -254,12 +266,15 @@ def third_stage(fs, nets, cap, if_outdoor=True, iters=100, events=None):
             "coarse": co, "stages": stages}
 
 
-def fine_third_stage(co, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None):
+def fine_third_stage(co, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, confidence=False):
     fs = fine_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
+    if confidence:
+        return third_stage(fs, nets, cap, if_outdoor, iters, events, confidence=True)
     return third_stage(fs, nets, cap, if_outdoor, iters, events)
 
 
-def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None):
+def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None,
+                  confidence=False):
     """lefts / rights [pairs,H,W,3] HWC, float32 (or float16 / bfloat16 / uint8: nets.coarse gets them as they are, the crops
     widen them exactly).  crop_format: the ops.CropFormat nets.fine receives the crops in (None: float32 HWC).
     nets.coarse / nets.fine / nets.third may return their descriptors in float32, float16 or bfloat16 (ops.cost_ot / ops.third_level
@@ -267,12 +282,14 @@ def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, ite
     Returns a dict of DEVICE tensors:
         matches_l, matches_r [M_cap,2]   the first M rows valid, reference order inside every pair (chunk, patch, sub-cell)
         match_row [M_cap] int32          row of the table per match;  rows.row_cell[match_row] // N = pair
+        match_conf [M_cap] float32       confidence=True only: the third level's per-match confidence (ops.third_level), aligned
+                                         with matches_l / matches_r; group_by_pair / split_by_pair then carry it along
         M, P [1] int64, status [1] int32 match count, third-level problem count (P > cap.P_cap = overflow), table status
         rows                             the ops.ChunkRows table
         stages                           the intermediate tensors (parity checks; nothing reads them here)
     No host read happens in here."""
     co = coarse_stage(lefts, rights, nets, cap, iters, fine_inputs=False, crop_format=crop_format)
-    return fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
+    return fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events, confidence)
 
 
 def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True, crop_format=None):
@@ -299,26 +316,36 @@ def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True, crop_format=No
             "H": None, "W": None}
 
 
-def forward_pairs_mixed(pack, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None):
+def forward_pairs_mixed(pack, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None,
+                        confidence=False):
     """forward_pairs for pairs of different grids (pack_pairs): the coarse level once per shape group, everything from the row
     table on ONE launch set over the whole batch, no host read.  Same result dict, in SLOT order (rows.row_pair = the slot;
     pack.caller_of[slot] = the caller's index); split_by_pair(out, cap) hands the per-pair lists back in the caller's order.
     Every pair's matches are bit-identical to forward_pairs / pipeline.forward_path on that pair alone.  nets.coarse is called
     once per group with its [g, 32h, 32w, 3] views; nets.fine / nets.third find a row's pair through rows.row_pair.
-    crop_format: as for forward_pairs."""
+    crop_format, confidence: as for forward_pairs."""
     if cap.pairs != pack.table.pairs or sorted(cap.shapes) != sorted(pack.shapes):
         raise ValueError("forward_pairs_mixed: the capacities were made for other shapes than the pack holds")
     co = coarse_stage_mixed(pack, nets, cap, iters, cap.if_local, crop_format=crop_format)
-    out = fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
+    out = fine_third_stage(co, nets, cap, if_outdoor, merge_new, iters, events, confidence)
     out["caller_of"] = pack.caller_of
     return out
 
 
-def group_by_pair(out, cap, buffers=None):
+def group_by_pair(out, cap, buffers=None, confidence=False):
     """Device side of the hand-over: the batch's matches regrouped by pair (ops.matches_by_pair), no host read.  Adds
     `by_pair` = (matches_l, matches_r, pair_off) and `summary` (int64 [pairs + 4]: the pairs + 1 offsets, then M, P, table status -
     everything the host reads of a step, in ONE buffer) to the result; a caller in a loop passes `buffers` (out_l, out_r,
-    summary-sized pair_off) to reuse the outputs."""
+    summary-sized pair_off) to reuse the outputs.
+    confidence (or a result that holds match_conf): match_conf is regrouped with the matches, by_pair = (matches_l, matches_r,
+    pair_off, conf) and `buffers` may carry conf's destination as a fourth tensor."""
+    if confidence and "match_conf" not in out:
+        raise ValueError("group_by_pair: confidence=True needs a result made with confidence=True")
+    if "match_conf" in out:
+        ml, mr, off, summary, mc = ops.matches_by_pair(out["rows"], out["matches_l"], out["matches_r"], out["match_row"], out["M"],
+                                                       out=buffers, P=out["P"], match_conf=out["match_conf"])
+        out["by_pair"], out["summary"] = (ml, mr, off, mc), summary
+        return out["by_pair"]
     ml, mr, off, summary = ops.matches_by_pair(out["rows"], out["matches_l"], out["matches_r"], out["match_row"], out["M"], out=buffers,
                                                P=out["P"])
     out["by_pair"], out["summary"] = (ml, mr, off), summary
@@ -326,7 +353,8 @@ def group_by_pair(out, cap, buffers=None):
 
 
 def split_by_pair(out, cap):
-    """Host side, AFTER the step: per-pair (matches_l, matches_r) lists from a forward_pairs (or forward_pairs_mixed: in the
+    """Host side, AFTER the step: per-pair (matches_l, matches_r) lists - (matches_l, matches_r, conf) for a result made with
+    confidence=True - from a forward_pairs (or forward_pairs_mixed: in the
     caller's order) result, in the reference's order.  Reads the counts back (the one synchronisation of a batch) and raises on a capacity overflow."""
     if "summary" not in out:
         group_by_pair(out, cap)
@@ -338,8 +366,12 @@ def split_by_pair(out, cap):
         raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
     if P > cap.P_cap:
         raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
-    ml, mr, _ = out["by_pair"]
-    per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]]) for p in range(cap.pairs)]
+    if len(out["by_pair"]) > 3:
+        ml, mr, _, mc = out["by_pair"]
+        per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]], mc[o[p]:o[p + 1]]) for p in range(cap.pairs)]
+    else:
+        ml, mr, _ = out["by_pair"]
+        per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]]) for p in range(cap.pairs)]
     if "caller_of" not in out:
         return per_slot
     per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order

@@ -472,10 +472,13 @@ third_inputs_kernel(const uint8_t* __restrict__ ifn2, const float* __restrict__ 
 }
 
 // ---- result scatter, pats.py:59-67 -------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-refine_scatter_kernel(const uint8_t* __restrict__ ifn2, const float* __restrict__ pts, const float* __restrict__ mkpts1,
-                      const float* __restrict__ label, int label_stride, int64_t P_rows, int64_t n16, Scan sc,
-                      uint8_t* __restrict__ ifn16, float* __restrict__ pts16) {
+// CONF: conf [P,16] goes to conf16 [B,2304] by the permutation pts16 gets; a sub-cell whose flag is set gets 0
+template <int CONF>
+__device__ __forceinline__ void refine_scatter_body(const uint8_t* __restrict__ ifn2, const float* __restrict__ pts,
+                                                    const float* __restrict__ mkpts1, const float* __restrict__ label, int label_stride,
+                                                    int64_t P_rows, int64_t n16, const Scan& sc, uint8_t* __restrict__ ifn16,
+                                                    float* __restrict__ pts16, const float* __restrict__ conf,
+                                                    float* __restrict__ conf16) {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;       // output index, [B,12,4,12,4] order
     if (o >= n16) return;
     const int64_t b = o / 2304;
@@ -484,17 +487,33 @@ refine_scatter_kernel(const uint8_t* __restrict__ ifn2, const float* __restrict_
     const int64_t e = b * 144 + cell;
     float py = pts[e * 2], px = pts[e * 2 + 1];
     uint8_t f = 1;
+    float cf = 0.0f;
     if (!ifn2[e]) {
         const int64_t P = sc.at(e);
         if (P < P_rows) {
             py = mkpts1[(P * 16 + sub) * 2];
             px = mkpts1[(P * 16 + sub) * 2 + 1];
             f = label[(P * 16 + sub) * (int64_t)label_stride] < -9.9f;
+            if (CONF) cf = conf[P * 16 + sub];
         }
     }
     pts16[o * 2] = py;
     pts16[o * 2 + 1] = px;
     ifn16[o] = f;
+    if (CONF) conf16[o] = f ? 0.0f : cf;
+}
+__global__ void __launch_bounds__(256)
+refine_scatter_kernel(const uint8_t* __restrict__ ifn2, const float* __restrict__ pts, const float* __restrict__ mkpts1,
+                      const float* __restrict__ label, int label_stride, int64_t P_rows, int64_t n16, Scan sc,
+                      uint8_t* __restrict__ ifn16, float* __restrict__ pts16) {
+    refine_scatter_body<0>(ifn2, pts, mkpts1, label, label_stride, P_rows, n16, sc, ifn16, pts16, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256)
+refine_scatter_conf_kernel(const uint8_t* __restrict__ ifn2, const float* __restrict__ pts, const float* __restrict__ mkpts1,
+                           const float* __restrict__ label, int label_stride, int64_t P_rows, int64_t n16, Scan sc,
+                           uint8_t* __restrict__ ifn16, float* __restrict__ pts16, const float* __restrict__ conf,
+                           float* __restrict__ conf16) {
+    refine_scatter_body<1>(ifn2, pts, mkpts1, label, label_stride, P_rows, n16, sc, ifn16, pts16, conf, conf16);
 }
 
 // ---- get_result (layer_num = 2), utils.py:189-213 -----------------------------------------------------
@@ -575,6 +594,19 @@ get_result_kernel(ResultArgs g, const int32_t* __restrict__ row_cell, Scan sc1) 
         g.ml[M * 2 + d] = l0 + (c1 ? dl1 : dr1);
         g.mr[M * 2 + d] = r0 + (c1 ? dr1 : dl1);
     }
+}
+// The sub-cells' confidences into the matches' slots: match_conf[M] = conf16[f] for every sub-cell f get_result_kernel emits, by
+// the same scan, the same row bound and the same capacity - one thread per sub-cell, one 4-byte store per match.  A kernel of
+// its own beside get_result_kernel (which stays what it was): the compaction reads nothing of the points and scales.
+__global__ void __launch_bounds__(256)
+match_conf_kernel(const uint8_t* __restrict__ ifn1, int64_t n, unsigned n1, const int64_t* __restrict__ rows0_dev, int64_t capacity,
+                  Scan sc1, const float* __restrict__ conf16, float* __restrict__ match_conf) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= n || ifn1[f]) return;
+    if (f / n1 >= *rows0_dev) return;
+    const int64_t M = sc1.at(f);
+    if (M >= capacity) return;
+    match_conf[M] = conf16[f];
 }
 
 }  // namespace pats
@@ -835,6 +867,16 @@ __global__ void __launch_bounds__(256) bypair_copy_kernel(ByPairArgs g) {
         reinterpret_cast<float2*>(g.out_r)[d] = reinterpret_cast<const float2*>(g.mr)[i];
     }
 }
+// the same copy with the matches' confidences beside them
+__global__ void __launch_bounds__(256) bypair_copy_conf_kernel(ByPairArgs g, const float* __restrict__ conf, float* __restrict__ out_conf) {
+    const int64_t M = *g.M;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
+        const int64_t k = bypair_key(g, i), d = g.seg_dst[k] + (i - g.seg_lo[k]);
+        reinterpret_cast<float2*>(g.out_l)[d] = reinterpret_cast<const float2*>(g.ml)[i];
+        reinterpret_cast<float2*>(g.out_r)[d] = reinterpret_cast<const float2*>(g.mr)[i];
+        out_conf[d] = conf[i];
+    }
+}
 }  // namespace pats
 
 extern "C" size_t pats_matches_by_pair_workspace_bytes(int Cmax, int64_t pairs) {
@@ -844,7 +886,8 @@ extern "C" size_t pats_matches_by_pair_workspace_bytes(int Cmax, int64_t pairs) 
 static int matches_by_pair_impl(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                 const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                 float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
-                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair = nullptr);
+                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair = nullptr,
+                                const float* match_conf = nullptr, float* out_conf = nullptr);
 extern "C" int pats_matches_by_pair_f32(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                         const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                         float* out_l, float* out_r, int64_t* pair_off, void* workspace, size_t workspace_bytes,
@@ -871,10 +914,38 @@ extern "C" int pats_matches_by_row_pair_summary_f32(const float* matches_l, cons
     return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, nullptr, chunk_base, Cmax, pairs, 1, out_l, out_r, pair_off, P_dev,
                                 status, workspace, workspace_bytes, stream, row_pair);
 }
+// the regroup entries that carry the matches' confidences along: match_conf [cap] in, out_conf [cap] out, in the slots of
+// matches_l / out_l.  status may be null for both (pair_off then holds the pairs + 1 offsets only, P_dev is ignored).
+#define PATS_CONF_PAIR(who, in, out)                                                                      \
+    PATS_REQUIRE((in) && (out), who ": null match_conf / out_conf");                                      \
+    PATS_REQUIRE((uintptr_t)(in) % 4 == 0 && (uintptr_t)(out) % 4 == 0, who ": match_conf / out_conf must be 4-byte aligned")
+extern "C" int pats_matches_by_pair_summary_conf_f32(const float* matches_l, const float* matches_r, const float* match_conf,
+                                                     const int32_t* match_row, const int64_t* M_dev, const int32_t* row_cell,
+                                                     const int64_t* chunk_base, int Cmax, int64_t pairs, int N, float* out_l,
+                                                     float* out_r, float* out_conf, int64_t* pair_off, const int64_t* P_dev,
+                                                     const int32_t* status, void* workspace, size_t workspace_bytes,
+                                                     pats_stream_t stream) {
+    PATS_CONF_PAIR("matches_by_pair_summary_conf", match_conf, out_conf);
+    PATS_REQUIRE(row_cell, "matches_by_pair_summary_conf: null row_cell");
+    return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, row_cell, chunk_base, Cmax, pairs, N, out_l, out_r, pair_off, P_dev,
+                                status, workspace, workspace_bytes, stream, nullptr, match_conf, out_conf);
+}
+extern "C" int pats_matches_by_row_pair_summary_conf_f32(const float* matches_l, const float* matches_r, const float* match_conf,
+                                                         const int32_t* match_row, const int64_t* M_dev, const int32_t* row_pair,
+                                                         const int64_t* chunk_base, int Cmax, int64_t pairs, float* out_l,
+                                                         float* out_r, float* out_conf, int64_t* pair_off, const int64_t* P_dev,
+                                                         const int32_t* status, void* workspace, size_t workspace_bytes,
+                                                         pats_stream_t stream) {
+    PATS_CONF_PAIR("matches_by_row_pair_summary_conf", match_conf, out_conf);
+    PATS_REQUIRE(row_pair, "matches_by_row_pair_summary_conf: null row_pair");
+    return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, nullptr, chunk_base, Cmax, pairs, 1, out_l, out_r, pair_off, P_dev,
+                                status, workspace, workspace_bytes, stream, row_pair, match_conf, out_conf);
+}
 static int matches_by_pair_impl(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                 const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                 float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
-                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair) {
+                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair,
+                                const float* match_conf, float* out_conf) {
     PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && N >= 1, "matches_by_pair: bad shape");
     PATS_REQUIRE(matches_l && matches_r && match_row && M_dev && (row_cell || row_pair) && chunk_base && out_l && out_r && pair_off,
                  "matches_by_pair: null pointer");
@@ -887,7 +958,8 @@ static int matches_by_pair_impl(const float* matches_l, const float* matches_r, 
                  ws + 2 * nseg, P_dev, status, row_pair};
     hipLaunchKernelGGL(bypair_runs_kernel, dim3(2048), dim3(256), 0, st, g);
     hipLaunchKernelGGL(bypair_offsets_kernel, dim3(1), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(bypair_copy_kernel, dim3(2048), dim3(256), 0, st, g);
+    if (out_conf) hipLaunchKernelGGL(bypair_copy_conf_kernel, dim3(2048), dim3(256), 0, st, g, match_conf, out_conf);
+    else hipLaunchKernelGGL(bypair_copy_kernel, dim3(2048), dim3(256), 0, st, g);
     return check_launch("matches_by_pair kernels");
 }
 
@@ -910,10 +982,32 @@ extern "C" int pats_third_inputs_f32(const uint8_t* if_nomatching, const float* 
     return check_launch("third_inputs_kernel");
 }
 
+static int refine_scatter_impl(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f, const float* label,
+                               int label_stride, int64_t B, int64_t P, uint8_t* if_nomatching16, float* pts16, void* workspace,
+                               size_t workspace_bytes, pats_stream_t stream, const float* conf, float* conf16);
 extern "C" int pats_refine_scatter_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f,
                                        const float* label, int label_stride, int64_t B, int64_t P,
                                        uint8_t* if_nomatching16, float* pts16, void* workspace,
                                        size_t workspace_bytes, pats_stream_t stream) {
+    return refine_scatter_impl(if_nomatching, pts, mkpts1_f, label, label_stride, B, P, if_nomatching16, pts16, workspace,
+                               workspace_bytes, stream, nullptr, nullptr);
+}
+// pats_refine_scatter_f32 that also scatters conf [P,16] onto conf16 [B,2304] (0 where if_nomatching16 is set).  conf may be
+// null when P == 0, as mkpts1_f.
+extern "C" int pats_refine_scatter_conf_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f,
+                                            const float* label, int label_stride, const float* conf, int64_t B, int64_t P,
+                                            uint8_t* if_nomatching16, float* pts16, float* conf16, void* workspace,
+                                            size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(B >= 0 && P >= 0 && label_stride >= 1, "refine_scatter_conf: bad shape");
+    if (B == 0) return PATS_OK;
+    PATS_REQUIRE(conf16 && (P == 0 || conf), "refine_scatter_conf: null conf / conf16");
+    PATS_REQUIRE((uintptr_t)conf % 4 == 0 && (uintptr_t)conf16 % 4 == 0, "refine_scatter_conf: conf / conf16 must be 4-byte aligned");
+    return refine_scatter_impl(if_nomatching, pts, mkpts1_f, label, label_stride, B, P, if_nomatching16, pts16, workspace,
+                               workspace_bytes, stream, conf, conf16);
+}
+static int refine_scatter_impl(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f, const float* label,
+                               int label_stride, int64_t B, int64_t P, uint8_t* if_nomatching16, float* pts16, void* workspace,
+                               size_t workspace_bytes, pats_stream_t stream, const float* conf, float* conf16) {
     PATS_REQUIRE(B >= 0 && P >= 0 && label_stride >= 1, "refine_scatter: bad shape");
     if (B == 0) return PATS_OK;
     PATS_REQUIRE(if_nomatching && pts && if_nomatching16 && pts16 && (P == 0 || (mkpts1_f && label)), "refine_scatter: null pointer");
@@ -923,8 +1017,12 @@ extern "C" int pats_refine_scatter_f32(const uint8_t* if_nomatching, const float
     Scan sc;
     int rc = run_scan(if_nomatching, n, nullptr, &ws, &sc, as_stream(stream));
     if (rc != PATS_OK) return rc;
-    hipLaunchKernelGGL(refine_scatter_kernel, dim3(blocks256(B * 2304)), dim3(256), 0, as_stream(stream), if_nomatching, pts,
-                       mkpts1_f, label, label_stride, P, B * 2304, sc, if_nomatching16, pts16);
+    if (conf16)
+        hipLaunchKernelGGL(refine_scatter_conf_kernel, dim3(blocks256(B * 2304)), dim3(256), 0, as_stream(stream), if_nomatching, pts,
+                           mkpts1_f, label, label_stride, P, B * 2304, sc, if_nomatching16, pts16, conf, conf16);
+    else
+        hipLaunchKernelGGL(refine_scatter_kernel, dim3(blocks256(B * 2304)), dim3(256), 0, as_stream(stream), if_nomatching, pts,
+                           mkpts1_f, label, label_stride, P, B * 2304, sc, if_nomatching16, pts16);
     return check_launch("refine_scatter_kernel");
 }
 
@@ -940,7 +1038,7 @@ static int get_result_impl(int batch_size, const uint8_t* if_nomatching0, const 
                                    const uint8_t* left_choice1, float* matches_l, float* matches_r,
                                    int64_t capacity, int64_t* count, void* workspace, size_t workspace_bytes,
                                    pats_stream_t stream, int64_t period0, float ap0_div, float ap1_div, int32_t* match_row,
-                                   const PairShapes* ragged) {
+                                   const PairShapes* ragged, const float* conf16 = nullptr, float* match_conf = nullptr) {
     PATS_REQUIRE(batch_size >= 1 && rows1 >= 0 && capacity >= 0 && patch_size0 && patch_size1, "get_result: bad shape");
     PATS_REQUIRE(scale1_cell_stride == 0 || scale1_cell_stride == 2, "get_result: scale1_cell_stride must be 0 or 2");
     PATS_REQUIRE(count, "get_result: null count");
@@ -969,6 +1067,9 @@ static int get_result_impl(int batch_size, const uint8_t* if_nomatching0, const 
     const int64_t blocks = rows1 * (((int64_t)n1 + 255) / 256);
     PATS_REQUIRE(blocks < (1ll << 31), "get_result: grid too large (split the batch)");
     hipLaunchKernelGGL(get_result_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, row_cell, s1);
+    if (match_conf)
+        hipLaunchKernelGGL(match_conf_kernel, dim3(blocks256(rows1 * n1)), dim3(256), 0, st, if_nomatching1, rows1 * n1, (unsigned)n1,
+                           rows0_dev, capacity, s1, conf16, match_conf);
     return check_launch("get_result_kernel");
 }
 
@@ -1017,4 +1118,43 @@ extern "C" int pats_get_result_chunks_ragged_f32(const pats_pair_table_t* tab, i
     return get_result_impl((int)(Cmax * ps.pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0, ps0,
                            patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count, workspace, workspace_bytes,
                            stream, ps.cells, 32.0f, 2.0f, match_row, &ps);
+}
+
+// The two entries above with the sub-cells' confidences compacted beside the matches: match_conf[M] = conf16 of the sub-cell
+// whose match went to matches_l[M] / matches_r[M] (the same scan, the same slots).  conf16 [rows_cap, n1], match_conf [capacity].
+extern "C" int pats_get_result_chunks_conf_f32(int Cmax, int64_t pairs, const uint8_t* masks, const uint8_t* if_nomatching16,
+                                               int64_t rows_cap, const float* pts_new, const float* pts16, const float* scales,
+                                               const float* conf16, const int* patch_size0, const int* patch_size1,
+                                               const uint8_t* left_choice0, const uint8_t* left_choice1, float* matches_l,
+                                               float* matches_r, float* match_conf, int32_t* match_row, int64_t capacity,
+                                               int64_t* count, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(conf16 && match_conf, "get_result_chunks_conf: null conf16 / match_conf");
+    PATS_REQUIRE((uintptr_t)conf16 % 4 == 0 && (uintptr_t)match_conf % 4 == 0, "get_result_chunks_conf: conf16 / match_conf must be 4-byte aligned");
+    PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && patch_size0, "get_result_chunks_conf: bad shape");
+    PATS_REQUIRE((int64_t)Cmax * pairs < (1ll << 31), "get_result_chunks_conf: batch too large");
+    const int64_t period0 = pairs * (int64_t)patch_size0[1] * patch_size0[2];
+    return get_result_impl((int)(Cmax * pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0,
+                           patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count,
+                           workspace, workspace_bytes, stream, period0, 32.0f, 2.0f, match_row, nullptr, conf16, match_conf);
+}
+
+extern "C" int pats_get_result_chunks_ragged_conf_f32(const pats_pair_table_t* tab, int Cmax, const uint8_t* masks,
+                                                      const uint8_t* if_nomatching16, int64_t rows_cap, const float* pts_new,
+                                                      const float* pts16, const float* scales, const float* conf16,
+                                                      const int* patch_size1, const uint8_t* left_choice0,
+                                                      const uint8_t* left_choice1, float* matches_l, float* matches_r,
+                                                      float* match_conf, int32_t* match_row, int64_t capacity, int64_t* count,
+                                                      void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(conf16 && match_conf, "get_result_chunks_ragged_conf: null conf16 / match_conf");
+    PATS_REQUIRE((uintptr_t)conf16 % 4 == 0 && (uintptr_t)match_conf % 4 == 0,
+                 "get_result_chunks_ragged_conf: conf16 / match_conf must be 4-byte aligned");
+    PairShapes ps;
+    int hmax = 0;
+    const int rc = ragged_shapes(tab, &ps, &hmax, "get_result_chunks_ragged_conf");
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && ps.cells * Cmax < (1ll << 31), "get_result_chunks_ragged_conf: bad shape");
+    const int ps0[3] = {32, 1, 1};
+    return get_result_impl((int)(Cmax * ps.pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0, ps0,
+                           patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count, workspace, workspace_bytes,
+                           stream, ps.cells, 32.0f, 2.0f, match_row, &ps, conf16, match_conf);
 }

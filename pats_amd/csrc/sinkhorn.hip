@@ -153,11 +153,13 @@ struct Ot65Args {
     ComputeResultOut cr;
     int stagger;             // first-wave-front start delay unit, in s_sleep(127) periods (0 = off)
     unsigned long long* fallbacks;   // guard-trip counter or null
+    float* conf;             // EPI 2: [P,16] per-match confidence (last member: the other instantiations' offsets stay)
 };
 
 // MODE 0: log_mu/log_nu given (a6)      MODE 2: ns given, log_optimal_transport2 marginals (a5)
 // SRC  0: couplings from HBM            SRC  1: cost build from descriptors (a3 fused)
 // EPI  0: write the log-plan            EPI  1: Compute_result + label from the LDS-resident plan
+// EPI  2: EPI 1 + the per-match confidence (third_device.hpp)
 // TD (SRC 1): the descriptors' element type - float, or _Float16 / bf16_t widened at the cost build's loads (cost65_device.hpp)
 template <int MODE, int SRC, int EPI, typename TD = float>
 __global__ void __launch_bounds__(64, 2)     // 2 waves/SIMD: VGPR + AGPR (MFMA accumulators) <= 256
@@ -356,9 +358,9 @@ sinkhorn65_kernel(Ot65Args g) {
             for (int k = 0; k < 66; ++k) Op[k * 64 + lane] = Tw[k * 64 + lane];
             if (lane == 0) Op[TILE - 1] = Tw[TILE - 1];
         }
-        compute_result_problem(Tw, 1, p, g.scale_x + p * 64, g.scale_y + p * 64,
-                               (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2],
-                               (float)g.p_t[p * 2 + 1], g.outdoor, g.cr, lane);
+        compute_result_problem<EPI == 2>(Tw, 1, p, g.scale_x + p * 64, g.scale_y + p * 64,
+                                         (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2],
+                                         (float)g.p_t[p * 2 + 1], g.outdoor, g.cr, lane, 0, false, g.conf);
     }
 }
 
@@ -1516,7 +1518,7 @@ int launch_cost_ot65(const void* d0, const void* d1, int dtype, int64_t batch, i
 static int third_level_impl(const void* feat0, const void* feat1, int dtype, int64_t P, const int64_t* P_dev, int D,
                             const float* scale, const float* scale_x, const float* scale_y, const int64_t* p_s,
                             const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f, float* label,
-                            uint8_t* if_matching1, float* Z_out, pats_stream_t stream);
+                            uint8_t* if_matching1, float* Z_out, pats_stream_t stream, float* conf = nullptr);
 
 extern "C" int pats_third_level_counted_f32(const float* feat0, const float* feat1, int64_t P_cap, const int64_t* P_dev, int D,
                                             const float* scale, const float* scale_x, const float* scale_y,
@@ -1567,18 +1569,41 @@ extern "C" int pats_third_level_typed(const void* feat0, const void* feat1, pats
                             mkpts0_f, mkpts1_f, label, if_matching1, Z, stream);
 }
 
+// pats_third_level_typed that also writes the per-match confidence conf [P_cap,16] (rows past *P_dev are not written): the same
+// checks, the same launches with the confidence instantiations in the plain ones' places.
+extern "C" int pats_third_level_typed_conf(const void* feat0, const void* feat1, pats_map_dtype_t dtype, int64_t P_cap,
+                                           const int64_t* P_dev, int D, const float* scale, const float* scale_x,
+                                           const float* scale_y, const int64_t* p_s, const int64_t* p_t, int iters, int outdoor,
+                                           float* mkpts0_f, float* mkpts1_f, float* label, uint8_t* if_matching1, float* Z,
+                                           float* conf, pats_stream_t stream) {
+    PATS_REQUIRE(known_elem_type((int)dtype), "third_level_typed_conf: unknown descriptor dtype %d", (int)dtype);
+    PATS_REQUIRE(P_cap >= 0 && D > 0 && (D % 32) == 0 && D <= 512 && iters >= 0,
+                 "third_level_typed_conf: bad shape (D must be a multiple of 32, at most 512)");
+    if (P_cap == 0) return PATS_OK;
+    PATS_REQUIRE(conf, "third_level_typed_conf: null conf");
+    PATS_REQUIRE((uintptr_t)conf % 4 == 0, "third_level_typed_conf: conf must be 4-byte aligned");
+    PATS_REQUIRE(feat0 && feat1 && scale && p_s && p_t && mkpts0_f && mkpts1_f && label && if_matching1 &&
+                     (P_dev ? (scale_x == nullptr) == (scale_y == nullptr) : scale_x && scale_y),
+                 "third_level_typed_conf: null pointer");
+    PATS_REQUIRE(!(P_dev && Z), "third_level_typed_conf: the plan is not available with a device-side count");
+    PATS_REQUIRE((uintptr_t)feat0 % desc_elem_bytes((int)dtype) == 0 && (uintptr_t)feat1 % desc_elem_bytes((int)dtype) == 0,
+                 "third_level_typed_conf: descriptors must be aligned to their element size (%d bytes)", (int)desc_elem_bytes((int)dtype));
+    return third_level_impl(feat0, feat1, (int)dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
+                            mkpts0_f, mkpts1_f, label, if_matching1, Z, stream, conf);
+}
+
 // validated arguments.  P_dev: throughput mode - no host read between the merge that decides P and this launch: the grid
 // covers the capacity P, waves past *P_dev leave at once
 static int third_level_impl(const void* feat0, const void* feat1, int dtype, int64_t P, const int64_t* P_dev, int D,
                             const float* scale, const float* scale_x, const float* scale_y, const int64_t* p_s,
                             const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f, float* label,
-                            uint8_t* if_matching1, float* Z_out, pats_stream_t stream) {
+                            uint8_t* if_matching1, float* Z_out, pats_stream_t stream, float* conf) {
     static const bool v1_only = diag_env("PATS_THIRD_V1") != nullptr;     // A/B switch for benchmarking
     if (P_dev || (!Z_out && !v1_only)) {      // no plan requested: the 8x8 register-block kernel (third_fused.hip)
         Fused65Args f{(const float*)feat0, (const float*)feat1, D, P, scale, nullptr, iters, 1, scale_x, scale_y, p_s, p_t, outdoor,
                       ComputeResultOut{mkpts0_f, mkpts1_f, nullptr, label, if_matching1, nullptr}, 0, nullptr, 0, P_dev};
         f.dtype = dtype;
-        return launch_third_fused(f, as_stream(stream));
+        return launch_third_fused(f, as_stream(stream), conf);
     }
     Ot65Args g{};
     g.fallbacks = fallback_counter();
@@ -1592,6 +1617,13 @@ static int third_level_impl(const void* feat0, const void* feat1, int dtype, int
     if (P >= 8192) g.stagger = (int)((30.0f + 0.6f * (float)iters) / 16.0f / 3.4f);
     if (const char* e = diag_env("PATS_STAGGER")) g.stagger = atoi(e);
     const dim3 grid((unsigned)P), block(64);
+    if (conf) {
+        g.conf = conf;
+        if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2, _Float16>), grid, block, 0, as_stream(stream), g);
+        else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2, bf16_t>), grid, block, 0, as_stream(stream), g);
+        else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2>), grid, block, 0, as_stream(stream), g);
+        return check_launch("sinkhorn65_kernel<2,1,2>");
+    }
     if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, _Float16>), grid, block, 0, as_stream(stream), g);
     else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, bf16_t>), grid, block, 0, as_stream(stream), g);
     else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1>), grid, block, 0, as_stream(stream), g);

@@ -27,6 +27,20 @@ compute_result_kernel(const float* __restrict__ scores, int input_is_log, int64_
                            (float)p_t[p * 2], (float)p_t[p * 2 + 1], outdoor, o, lane);
 }
 
+// the same with the per-match confidence conf [P,16] (third_device.hpp) beside the matches
+__global__ void __launch_bounds__(256)
+compute_result_conf_kernel(const float* __restrict__ scores, int input_is_log, int64_t P,
+                           const float* __restrict__ scale_x, const float* __restrict__ scale_y,
+                           const int64_t* __restrict__ p_s, const int64_t* __restrict__ p_t, int outdoor,
+                           ComputeResultOut o, float* __restrict__ conf) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t p = (int64_t)blockIdx.x * 4 + wave;
+    if (p >= P) return;
+    compute_result_problem<1>(scores + p * (int64_t)65 * 65, input_is_log, p, scale_x + p * 64,
+                              scale_y + p * 64, (float)p_s[p * 2], (float)p_s[p * 2 + 1],
+                              (float)p_t[p * 2], (float)p_t[p * 2 + 1], outdoor, o, lane, 0, false, conf);
+}
+
 // whole_loss = where(wl >= 1e-2, wl, 0) / (count + 10) / 10        (:215)
 __global__ void __launch_bounds__(256)
 whole_loss_finish_kernel(float* __restrict__ wl, int64_t n, const int* __restrict__ count) {
@@ -43,11 +57,16 @@ using namespace pats;
 
 static int compute_result_impl(const float* scores, int input_is_log, int64_t P, const float* scale_x, const float* scale_y,
                                const int64_t* p_s, const int64_t* p_t, int outdoor, float* mkpts0_f, float* mkpts1_f,
-                               float* whole_loss, float* label, uint8_t* if_matching1, int* count, hipStream_t st) {
+                               float* whole_loss, float* label, uint8_t* if_matching1, int* count, hipStream_t st,
+                               float* conf = nullptr) {
     if (whole_loss && fill_bytes(count, 0, sizeof(int), st)) return PATS_ERR_LAUNCH;
-    hipLaunchKernelGGL(compute_result_kernel, dim3((unsigned)ceil_div(P, 4)), dim3(256), 0, st, scores,
-                       input_is_log, P, scale_x, scale_y, p_s, p_t, outdoor,
-                       ComputeResultOut{mkpts0_f, mkpts1_f, whole_loss, label, if_matching1, whole_loss ? count : nullptr});
+    const ComputeResultOut o{mkpts0_f, mkpts1_f, whole_loss, label, if_matching1, whole_loss ? count : nullptr};
+    if (conf)
+        hipLaunchKernelGGL(compute_result_conf_kernel, dim3((unsigned)ceil_div(P, 4)), dim3(256), 0, st, scores,
+                           input_is_log, P, scale_x, scale_y, p_s, p_t, outdoor, o, conf);
+    else
+        hipLaunchKernelGGL(compute_result_kernel, dim3((unsigned)ceil_div(P, 4)), dim3(256), 0, st, scores,
+                           input_is_log, P, scale_x, scale_y, p_s, p_t, outdoor, o);
     int rc = check_launch("compute_result_kernel");
     if (whole_loss && rc == PATS_OK) {
         hipLaunchKernelGGL(whole_loss_finish_kernel, dim3((unsigned)ceil_div(P * 16, 256)), dim3(256),
@@ -72,6 +91,24 @@ extern "C" int pats_compute_result_ws_f32(const float* scores, int input_is_log,
     PATS_REQUIRE(!whole_loss || (workspace && workspace_bytes >= sizeof(int)), "compute_result: whole_loss needs 4 bytes of workspace");
     return compute_result_impl(scores, input_is_log, P, scale_x, scale_y, p_s, p_t, outdoor, mkpts0_f, mkpts1_f, whole_loss, label,
                                if_matching1, static_cast<int*>(workspace), as_stream(stream));
+}
+
+// pats_compute_result_ws_f32 that also writes the per-match confidence conf [P,16]
+extern "C" int pats_compute_result_ws_conf_f32(const float* scores, int input_is_log, int64_t P,
+                                               const float* scale_x, const float* scale_y,
+                                               const int64_t* p_s, const int64_t* p_t, int outdoor,
+                                               float* mkpts0_f, float* mkpts1_f, float* whole_loss,
+                                               float* label, uint8_t* if_matching1, float* conf, void* workspace,
+                                               size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(P >= 0, "compute_result_conf: bad shape");
+    if (P == 0) return PATS_OK;
+    PATS_REQUIRE(conf, "compute_result_conf: null conf");
+    PATS_REQUIRE((uintptr_t)conf % 4 == 0, "compute_result_conf: conf must be 4-byte aligned");
+    PATS_REQUIRE(scores && scale_x && scale_y && p_s && p_t && mkpts0_f && mkpts1_f && label &&
+                     if_matching1, "compute_result_conf: null pointer");
+    PATS_REQUIRE(!whole_loss || (workspace && workspace_bytes >= sizeof(int)), "compute_result_conf: whole_loss needs 4 bytes of workspace");
+    return compute_result_impl(scores, input_is_log, P, scale_x, scale_y, p_s, p_t, outdoor, mkpts0_f, mkpts1_f, whole_loss, label,
+                               if_matching1, static_cast<int*>(workspace), as_stream(stream), conf);
 }
 
 // The round-1 signature, kept for callers built against it: without a workspace argument the count is a 4-byte

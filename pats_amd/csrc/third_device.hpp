@@ -48,7 +48,9 @@ __device__ __forceinline__ int64_t live_problems(const Fused65Args& g) {
     return n < g.P ? n : g.P;
 }
 constexpr uint8_t THIRD_REDO = 0xEE; // if_matching1[p*16] of a problem the log-domain kernel must redo
-int launch_third_fused(const Fused65Args& g, hipStream_t st);
+// conf: [P,16] per-match confidence or null.  Not a member of Fused65Args: the *_conf_kernel instantiations take it as a kernel
+// argument of their own, so the plain kernels' argument block - and with it their code - stays what it was.
+int launch_third_fused(const Fused65Args& g, hipStream_t st, float* conf = nullptr);
 
 // row-level (16-lane) all-reduces: 4 DPP steps, no LDS traffic
 __device__ __forceinline__ float row16_sum(float v) {
@@ -71,17 +73,28 @@ __device__ __forceinline__ void row16_argmax(float& v, int& i) {
     argmax_step<DPP_ROW_MIRROR>(v, i);
 }
 
+// winmass / rowmass, at most 1 (the two fp32 sums are taken in different orders: a window that holds the whole row's mass may
+// come out an ulp above it); a NaN or a 0 / 0 stays what the division gives
+__device__ __forceinline__ float confidence_ratio(float winmass, float rowmass) {
+    const float c = winmass / rowmass;
+    return c > 1.0f ? 1.0f : c;
+}
+
 // One wave, one problem.  The 16 centre rows are processed four at a time: each 16-lane DPP row
 // of the wave owns one centre row (lane t of the group holds targets t, t+16, t+32, t+48), so the
 // argmax / sums are 4-step row-level DPP reductions and the 5x5 taps are two per lane, gathered
 // from the plan by address.  sx / sy are indexable [64] scale vectors (global or LDS).
 // `compact_stride` == 0: Sp is the full 65 x 65 matrix (row stride 65); > 0: Sp holds only the 16
 // centre rows, row q at Sp + q * compact_stride; < 0: see below.
+// CONF: conf[p*16 + q] = (plan mass inside the 5x5 window) / (mass of the whole row, dustbin included) - the two terms of
+// third_layer.py:212-213 as a ratio; both sums exist here for whole_loss.  CONF = 0 compiles to what it was.
+template <int CONF = 0>
 __device__ __forceinline__ void compute_result_problem(const float* Sp, int input_is_log, int64_t p,
                                                        const float* sx, const float* sy, float ps0,
                                                        float ps1, float pt0, float pt1, int outdoor,
                                                        const ComputeResultOut& o, int lane,
-                                                       int compact_stride = 0, bool scale_is_area = false) {
+                                                       int compact_stride = 0, bool scale_is_area = false,
+                                                       float* conf = nullptr) {
     constexpr int W = 8, T = 5, NN = 65;
     const int grp = lane >> 4, t = lane & 15;
     int local_count = 0;
@@ -153,6 +166,7 @@ __device__ __forceinline__ void compute_result_problem(const float* Sp, int inpu
             o.mk0[oo + 1] = ps1 + (float)(q / 4) * 2.0f - 3.0f;
             const float wl = rowsum - unfold;                                           // :213
             if (o.wl_raw) o.wl_raw[p * 16 + q] = wl;
+            if (CONF) conf[p * 16 + q] = confidence_ratio(unfold, rowsum);
             if (wl >= 1e-2f) local_count += 1;
             o.ifm[p * 16 + q] = matching ? 1 : 0;
             float l0 = 1e8f;                                                            // :161

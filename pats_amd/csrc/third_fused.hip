@@ -48,8 +48,10 @@ struct __attribute__((aligned(16))) BlkLds {
 __device__ __forceinline__ float lse_fin(float s, float mI) { return (fast_log2(s) + mI) * LN2; }
 __device__ __forceinline__ float uni(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
-template <typename T>      // the descriptors' element type (cost65_device.hpp): only the cost build's loads see it
-__device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int64_t p, BlkLds& lds, const int lane) {
+// CONF: the per-match confidence conf [P,16] is written beside the matches (third_device.hpp)
+template <typename T, int CONF = 0>      // T: the descriptors' element type (cost65_device.hpp): only the cost build's loads see it
+__device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int64_t p, BlkLds& lds, const int lane,
+                                                 float* conf = nullptr) {
     const int I = lane >> 3, J = lane & 7;
     const int colj = 8 * J + I;              // the column this lane owns in the column half-sweep
     // ---- marginals of log_optimal_transport2 (modules.py:169-179) --------------------------------
@@ -343,9 +345,9 @@ __device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int
     wg_barrier();
     // scale_x == NULL: scale_x = scale_y = sqrt(ns + 1e-8) (third_layer.py:153-154) is formed in the kernel
     const bool area = g.scale_x == nullptr;
-    compute_result_problem(rows16, 0, p, (area ? g.ns : g.scale_x) + p * 64, (area ? g.ns : g.scale_y) + p * 64,
-                           (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2], (float)g.p_t[p * 2 + 1],
-                           g.outdoor, g.cr, lane, 66, area);
+    compute_result_problem<CONF>(rows16, 0, p, (area ? g.ns : g.scale_x) + p * 64, (area ? g.ns : g.scale_y) + p * 64,
+                                 (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2], (float)g.p_t[p * 2 + 1],
+                                 g.outdoor, g.cr, lane, 66, area, conf);
 }
 
 // direct mode: one workgroup per problem.  scan mode (g.scan): the W workgroups of the launch share the problems INTERLEAVED -
@@ -383,15 +385,51 @@ third_fused_kernel(Fused65Args g) {
         }
     }
 }
-static void launch_v2(const Fused65Args& g, dim3 grid, hipStream_t st) {
+// The same with the per-match confidence conf [P,16]: a kernel of its own name and with its own copy of the walk (as
+// third_fused3_stab_kernel has), so that the plain one stays what it was, instruction for instruction.
+template <typename T>
+__global__ void __launch_bounds__(64, 3)
+third_fused_conf_kernel(Fused65Args g, float* conf) {
+    __shared__ BlkLds lds;
+    const int lane = threadIdx.x;
+    if (!g.scan) {
+        const int64_t p = blockIdx.x;
+        if (p >= live_problems(g)) return;
+        if (g.stagger > 0 && blockIdx.x < 8192u) {
+            const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
+            for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
+        }
+        third_v2_problem<T, 1>(g, p, lds, lane, conf);
+        return;
+    }
+    const int64_t W = gridDim.x, live = live_problems(g);
+    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
+        const int64_t cand = first + (int64_t)lane * W;
+        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
+        unsigned long long todo = __ballot(redo);
+        while (todo) {
+            const int k = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            wg_barrier();
+            third_v2_problem<T, 1>(g, first + (int64_t)k * W, lds, lane, conf);
+        }
+    }
+}
+static void launch_v2(const Fused65Args& g, dim3 grid, hipStream_t st, float* conf) {
+    if (conf) {
+        if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused_conf_kernel<_Float16>, grid, dim3(64), 0, st, g, conf);
+        else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused_conf_kernel<bf16_t>, grid, dim3(64), 0, st, g, conf);
+        else hipLaunchKernelGGL(third_fused_conf_kernel<float>, grid, dim3(64), 0, st, g, conf);
+        return;
+    }
     if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused_kernel<_Float16>, grid, dim3(64), 0, st, g);
     else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused_kernel<bf16_t>, grid, dim3(64), 0, st, g);
     else hipLaunchKernelGGL(third_fused_kernel<float>, grid, dim3(64), 0, st, g);
 }
 
-int launch_third_fused3(const Fused65Args& g0, hipStream_t st);      // third_fused3.hip
+int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf);      // third_fused3.hip
 
-int launch_third_fused(const Fused65Args& g0, hipStream_t st) {
+int launch_third_fused(const Fused65Args& g0, hipStream_t st, float* conf) {
     Fused65Args g = g0;
     g.linear = sinkhorn_mode() != PATS_SINKHORN_LOG;
     g.fallbacks = fallback_counter();
@@ -399,17 +437,17 @@ int launch_third_fused(const Fused65Args& g0, hipStream_t st) {
     if (g.linear && g.iters > 0 && !v2_only) {
         // linear-domain solve by the third-generation kernel; it flags the problems that leave the guard
         // band, and this file's kernel re-solves exactly those with log-sum-exp sweeps (scan mode)
-        int rc = launch_third_fused3(g, st);
+        int rc = launch_third_fused3(g, st, conf);
         if (rc) return rc;
         g.linear = 0;
         g.scan = 1;
         const int64_t waves = g.P < 6144 ? g.P : 6144;            // two rounds of the 3 072 wave slots: flagged runs spread out
-        launch_v2(g, dim3((unsigned)(waves > 0 ? waves : 1)), st);
+        launch_v2(g, dim3((unsigned)(waves > 0 ? waves : 1)), st, conf);
         return check_launch("third_fused_kernel(scan)");
     }
     if (g.P >= 8192) g.stagger = (int)((30.0f + 0.6f * (float)g.iters) / 16.0f / 3.4f);
     if (const char* e = diag_env("PATS_STAGGER")) g.stagger = atoi(e);
-    launch_v2(g, dim3((unsigned)g.P), st);
+    launch_v2(g, dim3((unsigned)g.P), st, conf);
     return check_launch("third_fused_kernel");
 }
 

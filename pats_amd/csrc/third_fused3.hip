@@ -155,19 +155,23 @@ __device__ __forceinline__ float reduce8_strided_pk(f2v q01, f2v q23, f2v q45, f
 // whole_loss (third_layer.py:213) is not produced here: nothing reads it at inference (the standalone
 // pats_compute_result_f32 still returns it).  sqrt and the two quotients use v_sqrt_f32 / v_rcp_f32 with one
 // Newton step instead of the IEEE sequences: <= 1 ulp, against a 3e-4 px gate.
+// CONF: the two SUMS of that line are kept as a ratio, conf[p*16 + q] = (mass of the 5x5 window) / (mass of the row, dustbin
+// included): lane u adds the 16 entries it scanned for the argmax and the taps it takes anyway, two quad-level DPP steps each,
+// one IEEE division per row.  CONF = 0 compiles to what it was.
 constexpr int RS3 = 68;                  // row stride of the plan rows (floats): 16-byte aligned rows
 __device__ __forceinline__ float fast_div(float x, float d) {
     const float r = __builtin_amdgcn_rcpf(d), q = x * r;
     return fmaf(fmaf(-q, d, x), r, q);
 }
+template <int CONF = 0>
 __device__ __forceinline__ void compute_result16(const float* rows, const float* sxl, const float* syl, int64_t p,
                                                  float ps0, float ps1, float pt0, float pt1, int outdoor,
-                                                 const ComputeResultOut& o, int lane) {
+                                                 const ComputeResultOut& o, int lane, float* conf = nullptr) {
     constexpr int W = 8, T = 5;
     const int q = lane >> 2, u = lane & 3;
     const int qy = (q >> 2) + 2, qx = (q & 3) + 2;                   // [:, 2:6, 2:6]  (:186,188)
     const float* row = rows + ((qy - 2) * 8 + qx) * RS3;
-    float bv;
+    float bv, rowmass = 0.f, winmass = 0.f;
     int bi;
     {
         const f4v* r4 = reinterpret_cast<const f4v*>(row + 16 * u);
@@ -178,6 +182,8 @@ __device__ __forceinline__ void compute_result16(const float* rows, const float*
 #pragma unroll
         for (int k = 1; k < 16; ++k)
             if (x[k] > bv) { bv = x[k]; bi = 16 * u + k; }
+        if (CONF) rowmass = (((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]))) +
+                            (((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15])));
     }
     argmax_step<DPP_QUAD_XOR1>(bv, bi);                             // lower index wins ties: first index over the row
     argmax_step<DPP_QUAD_XOR2>(bv, bi);
@@ -203,7 +209,12 @@ __device__ __forceinline__ void compute_result16(const float* rows, const float*
             wpy = fmaf(fy, (float)ty * 2.0f - (float)(T - 1), wpy);
             sumx += fx;
             sumy += fy;
+            if (CONF) winmass += sbv;
         }
+    }
+    if (CONF) {
+        rowmass += dpp_f<DPP_QUAD_XOR1>(rowmass); winmass += dpp_f<DPP_QUAD_XOR1>(winmass);
+        rowmass += dpp_f<DPP_QUAD_XOR2>(rowmass); winmass += dpp_f<DPP_QUAD_XOR2>(winmass);
     }
     wpx += dpp_f<DPP_QUAD_XOR1>(wpx); wpy += dpp_f<DPP_QUAD_XOR1>(wpy);
     sumx += dpp_f<DPP_QUAD_XOR1>(sumx); sumy += dpp_f<DPP_QUAD_XOR1>(sumy);
@@ -217,6 +228,7 @@ __device__ __forceinline__ void compute_result16(const float* rows, const float*
         *reinterpret_cast<f2v*>(o.mk0 + oo) = f2v{ps0 + (float)(q % 4) * 2.0f - 3.0f,        // :209-210
                                                   ps1 + (float)(q / 4) * 2.0f - 3.0f};
         o.ifm[p * 16 + q] = matching ? 1 : 0;
+        if (CONF) conf[p * 16 + q] = confidence_ratio(winmass, rowmass + xd);                // the two sums of :212-213
         float l0 = 1e8f;                                                                     // :161
         if (!outdoor) {
             const bool select = (q == 5 || q == 15 || q == 7 || q == 13);                    // :163-166
@@ -247,8 +259,10 @@ __device__ __forceinline__ unsigned fbits(float x) { return __builtin_bit_cast(u
 // unchanged, the iterate is the same Sinkhorn iterate) and the sweeps go on; only a scaling that leaves fp32 within ONE sweep
 // (-inf scores, ranges beyond 2^127) still goes to the log-sum-exp kernel.  A problem that never drifts runs bit-identically to ST = 0.
 // T = the descriptors' element type (cost65_device.hpp); only build_scores' descriptor loads see it.
-template <int CR, int DB, int CF, int ST, typename T = float>
-__device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64_t p, Blk3Lds& lds, const int lane) {
+// CONF: compute_result16 also writes the per-match confidence conf [P,16].
+template <int CR, int DB, int CF, int ST, typename T = float, int CONF = 0>
+__device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64_t p, Blk3Lds& lds, const int lane,
+                                               float* conf = nullptr) {
     const int I = lane >> 3, J = lane & 7;
     const int colj = 8 * J + I;              // the column this lane owns in the column half-sweep
     // ---- marginals of log_optimal_transport2 (modules.py:169-179); wave-uniform values in SGPRs -------
@@ -593,8 +607,8 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
     }
     wg_barrier();
     if (DB == 8) { if (lane == 0) g.cr.ifm[p * 16] = 0; return; }      // timing ablation only: no Compute_result
-    compute_result16(rows, lds.erow, lds.ecol, p, (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2],
-                     (float)g.p_t[p * 2 + 1], g.outdoor, g.cr, lane);
+    compute_result16<CONF>(rows, lds.erow, lds.ecol, p, (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2],
+                           (float)g.p_t[p * 2 + 1], g.outdoor, g.cr, lane, conf);
 #ifdef PATS_DIAG
     wg_barrier();
     if (lane == 0 && g.fingerprint) {
@@ -652,6 +666,22 @@ third_fused3_typed_kernel(Fused65Args g) {
     third3_problem<0, 0, 0, 0, T>(g, p, lds, lane);
 }
 
+// The production instantiation with the per-match confidence written beside mkpts1_f (conf [P,16]), for the three descriptor element
+// types.  Kernels of their own names, as above: the plain instantiations stay what they were, instruction for instruction.
+template <typename T>
+__global__ void __launch_bounds__(64, 3)
+third_fused3_conf_kernel(Fused65Args g, float* conf) {
+    __shared__ Blk3Lds lds;
+    const int lane = threadIdx.x;
+    const int64_t p = blockIdx.x;
+    if (p >= live_problems(g)) return;
+    if (g.stagger > 0 && blockIdx.x < 8192u) {      // de-phase the first wave-front, as above
+        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
+        for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
+    }
+    third3_problem<0, 0, 0, 0, T, 1>(g, p, lds, lane, conf);
+}
+
 // The stabilised solve over the problems the launch above flagged: the W workgroups share the problems interleaved, as
 // third_fused_kernel's scan mode does (third_fused.hip) - which runs behind this one for what is still flagged.
 template <typename T = float>       // the descriptors' element type
@@ -672,8 +702,27 @@ third_fused3_stab_kernel(Fused65Args g) {
         }
     }
 }
+// ... and with the confidence of the re-solved plan
+template <typename T>
+__global__ void __launch_bounds__(64, 2)
+third_fused3_stab_conf_kernel(Fused65Args g, float* conf) {
+    __shared__ Blk3Lds lds;
+    const int lane = threadIdx.x;
+    const int64_t W = gridDim.x, live = live_problems(g);
+    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
+        const int64_t cand = first + (int64_t)lane * W;
+        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
+        unsigned long long todo = __ballot(redo);
+        while (todo) {
+            const int k = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            wg_barrier();
+            third3_problem<0, 0, 0, 1, T, 1>(g, first + (int64_t)k * W, lds, lane, conf);
+        }
+    }
+}
 
-int launch_third_fused3(const Fused65Args& g0, hipStream_t st) {
+int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf) {
     Fused65Args g = g0;
     g.linear = 1;
     g.fallbacks = fallback_counter();
@@ -701,11 +750,17 @@ int launch_third_fused3(const Fused65Args& g0, hipStream_t st) {
     PATS_REQUIRE(variant == 300,
                  "PATS_THIRD_VARIANT=%d is a diagnostic build: it is compiled into libpats_amd_diag.so only "
                  "(python -m pats_amd.build --diag; PATS_AMD_DIAG_LIB=1)", variant);
-    if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_typed_kernel<_Float16>, grid, block, 0, st, g);
+    if (conf) {
+        if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_conf_kernel<_Float16>, grid, block, 0, st, g, conf);
+        else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_conf_kernel<bf16_t>, grid, block, 0, st, g, conf);
+        else hipLaunchKernelGGL(third_fused3_conf_kernel<float>, grid, block, 0, st, g, conf);
+    }
+    else if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_typed_kernel<_Float16>, grid, block, 0, st, g);
     else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_typed_kernel<bf16_t>, grid, block, 0, st, g);
     else hipLaunchKernelGGL((third_fused3_kernel<3, 0, 0>), grid, block, 0, st, g);       // fp32 MFMA cost build
 #else
     PATS_REQUIRE(g.dtype == PATS_MAP_F32, "third_level: the diagnostic library's sweep-loop variants take float32 descriptors only");
+    PATS_REQUIRE(!conf, "third_level: the diagnostic library's sweep-loop variants do not write the confidence");
     // last digit (dustbin sums) 6..9 = diagnostic / timing-ablation builds whose RESULTS ARE NOT the solve: never by accident
     static const bool ablation_ok = diag_env("PATS_THIRD_ABLATION") != nullptr;
     PATS_REQUIRE(ablation_ok || variant % 10 < 6,
@@ -747,7 +802,12 @@ int launch_third_fused3(const Fused65Args& g0, hipStream_t st) {
     if (!no_stab && g.iters > 0) {
         const int64_t waves = g.P < 6144 ? g.P : 6144;            // two rounds of the 3 072 wave slots: flagged runs spread out
         const dim3 sgrid((unsigned)(waves > 0 ? waves : 1));
-        if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_stab_kernel<_Float16>, sgrid, dim3(64), 0, st, g);
+        if (conf) {
+            if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_stab_conf_kernel<_Float16>, sgrid, dim3(64), 0, st, g, conf);
+            else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_stab_conf_kernel<bf16_t>, sgrid, dim3(64), 0, st, g, conf);
+            else hipLaunchKernelGGL(third_fused3_stab_conf_kernel<float>, sgrid, dim3(64), 0, st, g, conf);
+        }
+        else if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_stab_kernel<_Float16>, sgrid, dim3(64), 0, st, g);
         else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_stab_kernel<bf16_t>, sgrid, dim3(64), 0, st, g);
         else hipLaunchKernelGGL(third_fused3_stab_kernel<float>, sgrid, dim3(64), 0, st, g);
         rc = check_launch("third_fused3_stab_kernel");

@@ -823,9 +823,10 @@ def _typed_crops(table, left, right, code, nb, H, W, height, width, margin, boun
 # third level
 # ------------------------------------------------------------------------------------------------
 def Compute_result(scores, W, T, scale_x, scale_y, p_s, p_t, device=None, outdoor=True,
-                   input_is_log=False):
+                   input_is_log=False, return_confidence=False):
     """ThirdLayer.Compute_result (third_layer.py:184-217) + the label rule (:161-170).
-    Returns (mkpts0_f, mkpts1_f, whole_loss, label, if_matching1)."""
+    Returns (mkpts0_f, mkpts1_f, whole_loss, label, if_matching1[, conf]).  return_confidence: conf [P,16] float32, the plan
+    mass inside each centre cell's 5x5 window over the mass of its whole row (third_level has the definition)."""
     if W != 8 or T != 5:
         raise RuntimeError("Compute_result: the path uses W=8, T=5 (third_layer.py:108-111)")
     S = _dev(scores, "scores")
@@ -843,14 +844,33 @@ def Compute_result(scores, W, T, scale_x, scale_y, p_s, p_t, device=None, outdoo
     label = torch.empty((P * 16, 2), dtype=torch.float32, device=dev)
     ifm = torch.empty((P, 16), dtype=torch.uint8, device=dev)
     ws = torch.empty((1,), dtype=torch.int32, device=dev)          # whole_loss' cross-problem count: no allocation in the call
+    if return_confidence:
+        conf = torch.empty((P, 16), dtype=torch.float32, device=dev)
+        _check(_L().pats_compute_result_ws_conf_f32(_ptr(S), int(bool(input_is_log)), P, _ptr(sx), _ptr(sy), _ptr(ps),
+                                                    _ptr(pt), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(wl),
+                                                    _ptr(label), _ptr(ifm), _ptr(conf), _ptr(ws), 4, _stream()), "Compute_result")
+        return m0, m1, wl, label, ifm.bool(), conf
     _check(_L().pats_compute_result_ws_f32(_ptr(S), int(bool(input_is_log)), P, _ptr(sx), _ptr(sy), _ptr(ps),
                                            _ptr(pt), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(wl),
                                            _ptr(label), _ptr(ifm), _ptr(ws), 4, _stream()), "Compute_result")
     return m0, m1, wl, label, ifm.bool()
 
 
-def _third_out(out, P, dev):
-    """The four output tensors of third_level: fresh ones, or the caller's `out` checked (if_matching1 as uint8 storage)."""
+def _third_conf(out, P, dev):
+    """third_level's conf [P,16]: a fresh tensor, or the fifth tensor of the caller's `out` checked."""
+    if out is None or len(out) == 4:
+        return torch.empty((P, 16), dtype=torch.float32, device=dev)
+    c = _dev(out[4], "out[4]")
+    if tuple(c.shape) != (P, 16) or c.data_ptr() != out[4].data_ptr():
+        raise RuntimeError("third_level: out[4] (conf) must be a contiguous [P,16] float32 tensor")
+    return c
+
+
+def _third_out(out, P, dev, n=4):
+    """The four output tensors of third_level: fresh ones, or the caller's `out` checked (if_matching1 as uint8 storage).
+    n = 5: `out` may carry conf as a fifth tensor (_third_conf checks it)."""
+    if out is not None and n == 5 and len(out) == 5:
+        return _third_out(tuple(out[:4]), P, dev)
     if out is None:
         return (torch.empty((P, 16, 2), dtype=torch.float32, device=dev), torch.empty((P, 16, 2), dtype=torch.float32, device=dev),
                 torch.empty((P * 16, 2), dtype=torch.float32, device=dev), torch.empty((P, 16), dtype=torch.uint8, device=dev))
@@ -865,13 +885,18 @@ def _third_out(out, P, dev):
 
 
 def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdoor=True, iters=100,
-                return_plan=False, count=None, out=None):
+                return_plan=False, count=None, out=None, return_confidence=False):
     """The third layer's whole OT step in one launch (third_layer.py:153-170):
         scale_x = scale_y = sqrt(scale + 1e-8)
         scores  = exp(log_optimal_transport2(0.1 * einsum(f0, f1) / 128**.5, 1, scale, 100))
         mkpts0_f, mkpts1_f, _ = Compute_result(scores, 8, 5, scale_x, scale_y, mkpts0_c, mkpts1_c)
         label / if_matching1 as :161-170
-    Returns (mkpts0_f, mkpts1_f, label, if_matching1[, Z]).  The 65x65 plans stay on chip.
+    Returns (mkpts0_f, mkpts1_f, label, if_matching1[, Z][, conf]).  The 65x65 plans stay on chip.
+    return_confidence: conf [P,16] float32 is appended (behind Z).  For problem p and centre cell k (row r of the plan
+    S = exp(Z)): conf = (sum of S[r, c] over the 5x5 window around argmax_c S[r, :64], zero outside the 8x8 grid) / (sum of
+    S[r, :] over all 65 columns) - the two terms of third_layer.py:212-213 - for all 16 cells, whatever label / if_matching1
+    say; a problem the guard sends to a re-solve gets the confidence of the re-solved plan.  The other outputs keep their bits;
+    `out` may carry conf as a fifth tensor; with `count`, rows past it are not written.
     count: a DEVICE int64 [1] holding the number of problems that exist (throughput mode: the tensors are sized for a
     capacity, nothing is read back); rows past it are not written, and sqrt(scale + 1e-8) is formed in the kernel.
     out: optional (mkpts0_f [P,16,2], mkpts1_f [P,16,2], label [P*16,2], if_matching1 [P,16] uint8 or bool) to write into; the same
@@ -890,6 +915,13 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
         if return_plan:
             raise RuntimeError("third_level: return_plan is not available with a device-side count")
         cnt = _dev(count, "count", torch.int64).reshape(1)
+        if return_confidence:
+            m0, m1, label, ifm = _third_out(out, P, dev, 5)
+            conf = _third_conf(out, P, dev)
+            _check(_L().pats_third_level_typed_conf(_ptr(f0), _ptr(f1), code, P, _ptr(cnt), D, _ptr(sc), None, None, _ptr(ps),
+                                                    _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
+                                                    _ptr(ifm), None, _ptr(conf), _stream()), "third_level")
+            return (m0, m1, label, ifm.view(torch.bool), conf) if out is None else tuple(out[:4]) + (conf,)
         m0, m1, label, ifm = _third_out(out, P, dev)
         if code:
             _check(_L().pats_third_level_typed(_ptr(f0), _ptr(f1), code, P, _ptr(cnt), D, _ptr(sc), None, None, _ptr(ps), _ptr(pt),
@@ -901,8 +933,17 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
                                                  _ptr(ifm), _stream()), "third_level")
         return (m0, m1, label, ifm.view(torch.bool)) if out is None else tuple(out)
     sxy = torch.sqrt(sc + 1e-8)
-    m0, m1, label, ifm = _third_out(out, P, dev)
     Z = torch.empty((P, 65, 65), dtype=torch.float32, device=dev) if return_plan else None
+    if return_confidence:
+        m0, m1, label, ifm = _third_out(out, P, dev, 5)
+        conf = _third_conf(out, P, dev)
+        _check(_L().pats_third_level_typed_conf(_ptr(f0), _ptr(f1), code, P, None, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps),
+                                                _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
+                                                _ptr(ifm), _ptr(Z) if Z is not None else None, _ptr(conf), _stream()),
+               "third_level")
+        res = (m0, m1, label, ifm.bool()) if out is None else tuple(out[:4])
+        return res + ((Z, conf) if return_plan else (conf,))
+    m0, m1, label, ifm = _third_out(out, P, dev)
     if code:
         _check(_L().pats_third_level_typed(_ptr(f0), _ptr(f1), code, P, None, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps), _ptr(pt),
                                            int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label), _ptr(ifm),
@@ -1103,9 +1144,11 @@ def third_inputs(if_nomatching, pts, capacity=None, sync=True):
     return mk0[:P], mk1[:P], bi[:P]
 
 
-def refine_scatter(if_nomatching, pts, mkpts1_f, label):
+def refine_scatter(if_nomatching, pts, mkpts1_f, label, conf=None):
     """pats.py:59-67: (if_nomatching16 [B,2304] bool, pts16 [B,2304,2]) on the 48x48 sub-cell grid.
-    `label` is ThirdLayer's [P*16,2] tensor (column 0 is read) or a 1-D [P*16] tensor."""
+    `label` is ThirdLayer's [P*16,2] tensor (column 0 is read) or a 1-D [P*16] tensor.
+    conf (third_level's [P,16] confidence): a third element conf16 [B,2304] float32 is returned, scattered by the permutation
+    pts16 gets, 0 where if_nomatching16 is set."""
     f = _as_flags(if_nomatching, "if_nomatching")
     B = f.shape[0]
     p = _dev(pts, "pts").reshape(B, 144, 2)
@@ -1120,6 +1163,15 @@ def refine_scatter(if_nomatching, pts, mkpts1_f, label):
     p16 = torch.empty((B, 2304, 2), dtype=torch.float32, device=dev)
     nws = _L().pats_compact_workspace_bytes(B * 144)
     ws = _workspace(nws, dev)
+    if conf is not None:
+        cf = _dev(conf, "conf")
+        if cf.numel() != P * 16:
+            raise RuntimeError("refine_scatter: conf must be [P,16]")
+        c16 = torch.empty((B, 2304), dtype=torch.float32, device=dev)
+        _check(_L().pats_refine_scatter_conf_f32(_ptr(f), _ptr(p), _ptr(mk), _ptr(lb), stride, _ptr(cf), B, P,
+                                                 _ptr(f16.view(torch.uint8)), _ptr(p16), _ptr(c16), _ptr(ws), nws, _stream()),
+               "refine_scatter")
+        return f16, p16, c16
     _check(_L().pats_refine_scatter_f32(_ptr(f), _ptr(p), _ptr(mk), _ptr(lb), stride, B, P, _ptr(f16.view(torch.uint8)),
                                         _ptr(p16), _ptr(ws), nws, _stream()), "refine_scatter")
     return f16, p16
@@ -1408,14 +1460,19 @@ def _ones(n, device):
     return t
 
 
-def get_result_chunks(rows, if_nomatching16, pts_new, pts16, scales, patch_size=((32, None, None), (2, 48, 48))):
+def get_result_chunks(rows, if_nomatching16, pts_new, pts16, scales, patch_size=((32, None, None), (2, 48, 48)), conf16=None):
     """get_result (utils.py:189-213) for every (chunk, pair) of a ChunkRows table in one call, as PATS.forward issues it per
     chunk (pats.py:68-73): pts_new / scales = Compute_imgs' per-pair [pairs,N,2] tensors, pts16 [rows_cap,2304,2] /
     if_nomatching16 [rows_cap,2304] from refine_scatter.  No host read.  Returns (matches_l [cap,2], matches_r [cap,2],
-    match_row [cap] int32, M [1] int64 device): the first M rows are valid, match_row -> rows.row_cell // N = pair."""
+    match_row [cap] int32, M [1] int64 device): the first M rows are valid, match_row -> rows.row_cell // N = pair.
+    conf16 (refine_scatter's [rows_cap,2304]): a fifth element match_conf [cap] float32, compacted into the matches' slots."""
     f16 = _as_flags(if_nomatching16, "if_nomatching16")
+    if conf16 is not None:
+        conf16 = _dev(conf16, "conf16")
+        if conf16.numel() != f16.numel():
+            raise RuntimeError("get_result_chunks: conf16 must have if_nomatching16's shape")
     if rows.table is not None:
-        return _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size)
+        return _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size, conf16)
     z0 = [int(patch_size[0][0]), rows.h, rows.w]
     z1 = [int(v) for v in patch_size[1]]
     n1 = z1[1] * z1[2]
@@ -1434,6 +1491,14 @@ def get_result_chunks(rows, if_nomatching16, pts_new, pts16, scales, patch_size=
     nws = _L().pats_get_result_workspace_bytes(rows.Cmax * rows.pairs * N, rows.rows_cap, n1)
     ws = _workspace(nws, dev)
     ps0, ps1 = (ctypes.c_int * 3)(*z0), (ctypes.c_int * 3)(*z1)
+    if conf16 is not None:
+        mc = torch.empty((cap,), dtype=torch.float32, device=dev)
+        _check(_L().pats_get_result_chunks_conf_f32(rows.Cmax, rows.pairs, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
+                                                    _ptr(a0), _ptr(a1), _ptr(s0), _ptr(conf16), ps0, ps1,
+                                                    _ptr(_ones(rows.Cmax * rows.pairs, dev)), _ptr(_ones(rows.rows_cap, dev)),
+                                                    _ptr(ml), _ptr(mr), _ptr(mc), _ptr(mrow), cap, _ptr(cnt), _ptr(ws), nws,
+                                                    _stream()), "get_result_chunks")
+        return ml, mr, mrow, cnt, mc
     _check(_L().pats_get_result_chunks_f32(rows.Cmax, rows.pairs, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
                                            _ptr(a0), _ptr(a1), _ptr(s0), ps0, ps1, _ptr(_ones(rows.Cmax * rows.pairs, dev)),
                                            _ptr(_ones(rows.rows_cap, dev)), _ptr(ml), _ptr(mr), _ptr(mrow), cap, _ptr(cnt),
@@ -1441,12 +1506,14 @@ def get_result_chunks(rows, if_nomatching16, pts_new, pts16, scales, patch_size=
     return ml, mr, mrow, cnt
 
 
-def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None):
+def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None, match_conf=None):
     """The matches of a batch (get_result_chunks) grouped by pair ON THE DEVICE: (matches_l, matches_r) with every pair's
     list contiguous in the reference's order, and pair_off [pairs + 1] int64 (pair p = rows pair_off[p] .. pair_off[p + 1]).
     What batch.split_by_pair reads back is then only pair_off.  out: optional (out_l, out_r, pair_off) to write into.
     P (device int64 [1], the step's third-level problem count): pair_off is then the first pairs + 1 entries of a pairs + 4
-    buffer whose tail is (M, P, table status) - returned as a fourth element: the whole hand-over in ONE device-to-host copy."""
+    buffer whose tail is (M, P, table status) - returned as a fourth element: the whole hand-over in ONE device-to-host copy.
+    match_conf (get_result_chunks' fifth element): regrouped with the matches and returned as the LAST element; out may then
+    carry its destination as a fourth tensor (out_l, out_r, pair_off, conf)."""
     dev = matches_l.device
     n_off = rows.pairs + 1 + (3 if P is not None else 0)
     if out is None:
@@ -1456,6 +1523,25 @@ def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None):
         raise RuntimeError("matches_by_pair: pair_off must be a contiguous int64 tensor of %d entries" % n_off)
     nws = _L().pats_matches_by_pair_workspace_bytes(rows.Cmax, rows.pairs)
     ws = _workspace(nws, dev)
+    if match_conf is not None:
+        mc = _dev(match_conf, "match_conf").reshape(-1)
+        oc = out[3] if len(out) > 3 else torch.empty_like(mc)
+        if mc.numel() != matches_l.shape[0] or oc.numel() != mc.numel() or oc.dtype != torch.float32 or not oc.is_contiguous():
+            raise RuntimeError("matches_by_pair: match_conf and its destination must be contiguous float32 [cap] tensors")
+        summary = P is not None
+        Pp = _ptr(_dev(P, "P", torch.int64)) if summary else None
+        sp = _ptr(rows.status) if summary else None
+        if rows.table is not None:
+            _check(_L().pats_matches_by_row_pair_summary_conf_f32(_ptr(matches_l), _ptr(matches_r), _ptr(mc), _ptr(match_row), _ptr(M),
+                                                                  _ptr(rows.row_pair), _ptr(rows.chunk_base), rows.Cmax, rows.pairs,
+                                                                  _ptr(ol), _ptr(orr), _ptr(oc), _ptr(off), Pp, sp, _ptr(ws), nws,
+                                                                  _stream()), "matches_by_pair")
+        else:
+            _check(_L().pats_matches_by_pair_summary_conf_f32(_ptr(matches_l), _ptr(matches_r), _ptr(mc), _ptr(match_row), _ptr(M),
+                                                              _ptr(rows.row_cell), _ptr(rows.chunk_base), rows.Cmax, rows.pairs,
+                                                              rows.h * rows.w, _ptr(ol), _ptr(orr), _ptr(oc), _ptr(off), Pp, sp,
+                                                              _ptr(ws), nws, _stream()), "matches_by_pair")
+        return (ol, orr, off, oc) if P is None else (ol, orr, off[:rows.pairs + 1], off, oc)
     if rows.table is not None:                  # ragged: the pair of a row is row_pair[row] (there is no global N)
         # without P the call writes the pairs + 1 offsets only (null status): the buffer above holds no more
         summary = P is not None
@@ -1580,7 +1666,7 @@ def _merge_patches_ragged(merge_new, rows, trust_score, if_nomatching1_L2, score
     return out
 
 
-def _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size):
+def _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size, conf16=None):
     table = rows.table
     z1 = [int(v) for v in patch_size[1]]
     n1 = z1[1] * z1[2]
@@ -1600,6 +1686,14 @@ def _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size):
     nws = _L().pats_get_result_workspace_bytes(rows.Cmax * table.cells, rows.rows_cap, n1)
     ws = _workspace(nws, dev)
     ps1 = (ctypes.c_int * 3)(*z1)
+    if conf16 is not None:
+        mc = torch.empty((cap,), dtype=torch.float32, device=dev)
+        _check(_L().pats_get_result_chunks_ragged_conf_f32(table.ref(), rows.Cmax, _ptr(rows.masks.view(torch.uint8)), _ptr(f16),
+                                                           rows.rows_cap, _ptr(a0), _ptr(a1), _ptr(s0), _ptr(conf16), ps1,
+                                                           _ptr(_ones(rows.Cmax * rows.pairs, dev)), _ptr(_ones(rows.rows_cap, dev)),
+                                                           _ptr(ml), _ptr(mr), _ptr(mc), _ptr(mrow), cap, _ptr(cnt), _ptr(ws), nws,
+                                                           _stream()), "get_result_chunks_ragged")
+        return ml, mr, mrow, cnt, mc
     _check(_L().pats_get_result_chunks_ragged_f32(table.ref(), rows.Cmax, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
                                                   _ptr(a0), _ptr(a1), _ptr(s0), ps1, _ptr(_ones(rows.Cmax * rows.pairs, dev)),
                                                   _ptr(_ones(rows.rows_cap, dev)), _ptr(ml), _ptr(mr), _ptr(mrow), cap, _ptr(cnt),

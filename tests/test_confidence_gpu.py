@@ -1,0 +1,341 @@
+"""-m gpu: the per-match confidence of the third level, from the kernels to the batch hand-over.
+
+    conf[p,k] = (mass of plan row r inside the 5x5 window around argmax_c S[r, :64], zero outside the 8x8 grid)
+                / (mass of the whole row, dustbin column included)            S = exp(Z), r = the k-th centre row
+
+(third_layer.py:212-213's two sums as a ratio).  Values are compared with that definition evaluated in float64 numpy on the Z
+the SAME call returned, under 1e-4 - the project's element-wise gate on transport mass taken as the ceiling;
+what differs is fp32 sums of <= 65 non-negative terms and the exp of a stored log.  Everything else the calls return must keep
+its bits.  The kernel that solves without writing a plan (the throughput path) has no Z to compare with: it is checked against
+the plan-returning call under 1e-3, on rows whose argmax is not a near-tie - both are the same 100 Sinkhorn sweeps in fp32 in
+different summation orders, 100 sweeps x 2 half-sweeps x ~70 roundings of 2^-24 each add up to 8e-4 relative in the worst case.
+Measured maxima are printed by every test and recorded in docs/kernels.md."""
+import numpy as np
+import pytest
+import torch
+
+from pats_amd import synth
+from test_batch_gpu import _BatchNets, cu
+
+pytestmark = pytest.mark.gpu
+
+BOUND = 1e-4            # tests 1, 2, 6: against the definition on the call's own Z
+CROSS = 1e-3            # the plan-free kernels against the plan-returning call (see above)
+SENTINEL = -7.25        # no confidence is negative
+AMPS = np.array([0.35, 0.6, 1.0, 1.6, 2.2], np.float32)       # flat to peaked plans
+P_FULL = 67
+
+
+def conf_def(Z):
+    """The definition, float64: (conf [P,16], argmax [P,16], dustbin entry / largest real entry [P,16])."""
+    S = np.exp(Z.astype(np.float64))
+    P = S.shape[0]
+    rows = S[:, :64, :].reshape(P, 8, 8, 65)[:, 2:6, 2:6, :].reshape(P, 16, 65)
+    am = rows[:, :, :64].argmax(2)                                  # first index on ties
+    pad = np.zeros((P, 16, 12, 12))
+    pad[:, :, 2:10, 2:10] = rows[:, :, :64].reshape(P, 16, 8, 8)    # ZeroPad2d(2)
+    win = np.zeros((P, 16))
+    for dy in range(5):
+        for dx in range(5):
+            win += np.take_along_axis(pad.reshape(P, 16, 144), ((am // 8 + dy) * 12 + am % 8 + dx)[:, :, None], 2)[:, :, 0]
+    return win / rows.sum(2), am, rows[:, :, 64] / rows[:, :, :64].max(2)
+
+
+def clear_rows(Z):
+    """centre rows whose two largest real entries differ by more than 1e-3 relative: the argmax is the same in every solve"""
+    S = np.exp(Z.astype(np.float64))
+    P = S.shape[0]
+    top = np.sort(S[:, :64, :64].reshape(P, 8, 8, 64)[:, 2:6, 2:6, :].reshape(P, 16, 64), axis=2)[:, :, -2:]
+    return (top[:, :, 1] - top[:, :, 0]) > 1e-3 * top[:, :, 1]
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from pats_amd import ops
+    return ops
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    """67 seeded problems, descriptors scaled per problem from flat to peaked; problem 0 alone already has a corner and an
+    edge argmax, a dustbin row, a confidence below 0.5 and one above 0.99 (asserted on the returned Z in test 1)."""
+    inp = synth.third_inputs(seed=synth.SEED + 903, P=P_FULL)
+    amps = np.resize(AMPS, P_FULL)
+    d0, d1 = inp["d0"] * amps[:, None, None], inp["d1"] * amps[:, None, None]
+    order = np.arange(P_FULL)
+    order[[0, 13]] = [13, 0]
+    return tuple(cu(a[order]) for a in (d0, d1, inp["scale"], inp["p_s"], inp["p_t"]))
+
+
+def run(ops, inp, P, **kw):
+    return ops.third_level(*(t[:P] for t in inp), outdoor=True, **kw)
+
+
+_PLAN = {}
+
+
+def plan_call(ops, inputs, P):
+    """ONE plan-returning confidence call per size, shared by the tests (left unchanged)."""
+    if P not in _PLAN:
+        _PLAN[P] = run(ops, inputs, P, return_plan=True, return_confidence=True)
+    return _PLAN[P]
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a,
+                                                                     b.view(torch.int32) if b.dtype == torch.float32 else b)
+
+
+@pytest.mark.parametrize("P", [1, 3, P_FULL])
+def test_value_against_the_definition_on_the_returned_plan(ops, inputs, P):
+    out = plan_call(ops, inputs, P)
+    assert len(out) == 6 and out[4].shape == (P, 65, 65) and out[5].shape == (P, 16) and out[5].dtype == torch.float32
+    Z, conf = out[4].cpu().numpy(), out[5].cpu().numpy()
+    want, am, ratio = conf_def(Z)
+    mx, my = am % 8, am // 8
+    assert ((mx % 7 == 0) & (my % 7 == 0)).any() and ((mx % 7 == 0) ^ (my % 7 == 0)).any(), "no clipped window"
+    ifm = out[3].cpu().numpy()
+    assert (ratio > 1.001).any() and not ifm[ratio > 1.001].any() and ifm[ratio < 0.999].all(), "dustbin rows / if_matching1"
+    assert (want < 0.5).any() and (want > 0.99).any()
+    err = np.abs(conf - want).max()
+    print("P=%d: max |conf - definition| = %.3g (range %.3f .. %.6f)" % (P, err, conf.min(), conf.max()))
+    assert np.isfinite(conf).all() and conf.min() >= 0.0 and conf.max() <= 1.0
+    assert err <= BOUND
+    # 3: nothing else moved
+    plain = run(ops, inputs, P, return_plan=True)
+    assert len(plain) == 5 and all(same_bits(a, b) for a, b in zip(plain, out[:5]))
+
+
+def test_plan_free_kernels_agree_and_leave_the_other_outputs_alone(ops, inputs):
+    """The throughput path's kernels (no plan in memory): every other output keeps its bits, conf agrees with the plan call."""
+    got = run(ops, inputs, P_FULL, return_confidence=True)
+    plain = run(ops, inputs, P_FULL)
+    assert len(got) == 5 and len(plain) == 4 and all(same_bits(a, b) for a, b in zip(plain, got[:4]))
+    ref = plan_call(ops, inputs, P_FULL)
+    clear = clear_rows(ref[4].cpu().numpy())
+    assert clear.mean() > 0.95
+    d = np.abs(got[4].cpu().numpy() - ref[5].cpu().numpy())[clear].max()
+    print("plan-free kernel against the plan call: max |conf difference| = %.3g over %d rows" % (d, clear.sum()))
+    assert d <= CROSS
+    # out= may carry conf as a fifth tensor
+    bufs = tuple(torch.empty_like(t) for t in got[:3]) + (torch.empty((P_FULL, 16), dtype=torch.uint8, device="cuda"),
+                                                          torch.full((P_FULL, 16), SENTINEL, device="cuda"))
+    back = run(ops, inputs, P_FULL, return_confidence=True, out=bufs)
+    assert back[4].data_ptr() == bufs[4].data_ptr() and same_bits(bufs[4], got[4]) and same_bits(bufs[1], got[1])
+
+
+@pytest.fixture(scope="module")
+def wild():
+    """tests/test_third_redo_walk_gpu.py's recipe at its base size: 96 problems, the first 32 scaled out of the guard band."""
+    inp = synth.third_inputs(seed=synth.SEED + 64, P=96)
+    amps = np.tile(np.array([3.0, 5.0, 9.0, 14.0], np.float32), 8)
+    d0, d1 = inp["d0"].copy(), inp["d1"].copy()
+    d0[:32] *= amps[:, None, None]
+    d1[:32] *= amps[:, None, None]
+    return tuple(cu(a) for a in (d0, d1, inp["scale"], inp["p_s"], inp["p_t"]))
+
+
+def test_resolved_problems_get_the_confidence_of_the_resolved_plan(ops, wild):
+    ops.sinkhorn_fallbacks(reset=True)
+    out = run(ops, wild, 96, return_plan=True, return_confidence=True)
+    trips = ops.sinkhorn_fallbacks(reset=True)
+    assert trips >= 8, "only %d guard trips" % trips
+    Z, conf = out[4].cpu().numpy(), out[5].cpu().numpy()
+    assert np.isfinite(Z).all()
+    want, _, _ = conf_def(Z)
+    err = np.abs(conf - want)
+    print("guard-trip launch (%d trips): max |conf - definition| = %.3g wild, %.3g tame" % (trips, err[:32].max(), err[32:].max()))
+    assert err.max() <= BOUND
+    plain = run(ops, wild, 96, return_plan=True)
+    assert all(same_bits(a, b) for a, b in zip(plain, out[:5]))
+    # the redo walk (third_fused3 -> stabilised -> log-domain scan): flagged problems get a confidence, the rest keeps its bits
+    ops.sinkhorn_fallbacks(reset=True)
+    conf_buf = torch.full((96, 16), SENTINEL, device="cuda")
+    got = run(ops, wild, 96, return_confidence=True,
+              out=tuple(torch.empty_like(t) for t in out[:3]) + (torch.empty((96, 16), dtype=torch.uint8, device="cuda"), conf_buf))
+    walk_trips = ops.sinkhorn_fallbacks(reset=True)
+    assert walk_trips >= 8
+    plain = run(ops, wild, 96)
+    assert all(same_bits(a, b) for a, b in zip(plain[:3], got[:3])) and torch.equal(plain[3], got[3].bool())
+    c = got[4].cpu().numpy()
+    assert np.isfinite(c).all() and c.min() >= 0.0 and c.max() <= 1.0, "a re-solved problem kept the sentinel or left [0, 1]"
+    clear = clear_rows(Z)
+    d = np.abs(c - conf)[clear]
+    print("redo walk (%d trips) against the plan call: max |conf difference| = %.3g over %d rows" % (walk_trips, d.max(), clear.sum()))
+    assert d.max() <= CROSS
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+def test_half_descriptors_give_the_bits_of_the_float_copies(ops, inputs, wild, dt):
+    for inp, P in ((inputs, P_FULL), (wild, 96)):
+        half = (inp[0].to(dt), inp[1].to(dt)) + inp[2:]
+        wide = (half[0].float(), half[1].float()) + inp[2:]
+        for kw in ({}, {"return_plan": True}):
+            a = run(ops, half, P, return_confidence=True, **kw)
+            b = run(ops, wide, P, return_confidence=True, **kw)
+            assert all(same_bits(x, y) for x, y in zip(a, b)), (dt, P, kw)
+            plain = run(ops, half, P, **kw)                      # the plain half call (guard trips included) keeps its bits
+            assert len(plain) == len(a) - 1 and all(same_bits(x, y) for x, y in zip(plain, a)), (dt, P, kw)
+
+
+@pytest.mark.parametrize("count", [0, 1, 66, 67])
+def test_counted_launch_writes_the_rows_below_the_count_only(ops, inputs, wild, count):
+    full = run(ops, inputs, P_FULL, return_confidence=True)
+    cnt = torch.tensor([count], dtype=torch.int64, device="cuda")
+    for dt in (torch.float32, torch.float16, torch.bfloat16):
+        inp = (inputs[0].to(dt), inputs[1].to(dt)) + inputs[2:]
+        want = full if dt == torch.float32 else run(ops, (inp[0].float(), inp[1].float()) + inp[2:], P_FULL, return_confidence=True)
+        bufs = (torch.empty((P_FULL, 16, 2), device="cuda"), torch.empty((P_FULL, 16, 2), device="cuda"),
+                torch.empty((P_FULL * 16, 2), device="cuda"), torch.empty((P_FULL, 16), dtype=torch.uint8, device="cuda"),
+                torch.full((P_FULL, 16), SENTINEL, device="cuda"))
+        got = run(ops, inp, P_FULL, return_confidence=True, count=cnt, out=bufs)
+        assert len(got) == 5 and got[4].data_ptr() == bufs[4].data_ptr()
+        assert same_bits(bufs[4][:count], want[4][:count]) and same_bits(bufs[1][:count], want[1][:count]), (dt, count)
+        assert bool((bufs[4][count:] == SENTINEL).all()), (dt, count)
+        plain = run(ops, inp, P_FULL, count=cnt)
+        assert len(plain) == 4 and same_bits(plain[1][:count], bufs[1][:count])
+    # flagged problems on both sides of the count
+    c96 = torch.tensor([17], dtype=torch.int64, device="cuda")
+    ref = run(ops, wild, 96, return_confidence=True)
+    buf = torch.full((96, 16), SENTINEL, device="cuda")
+    run(ops, wild, 96, return_confidence=True, count=c96,
+        out=tuple(torch.empty_like(t) for t in ref[:3]) + (torch.empty((96, 16), dtype=torch.uint8, device="cuda"), buf))
+    assert same_bits(buf[:17], ref[4][:17]) and bool((buf[17:] == SENTINEL).all())
+
+
+def test_standalone_compute_result(ops, inputs):
+    ref = plan_call(ops, inputs, P_FULL)
+    Z = ref[4]
+    sxy = torch.sqrt(inputs[2].reshape(P_FULL, 64) + 1e-8)
+    want, _, _ = conf_def(Z.cpu().numpy())
+    for S, is_log in ((torch.exp(Z), False), (Z, True)):
+        out = ops.Compute_result(S, 8, 5, sxy, sxy, inputs[3], inputs[4], outdoor=True, input_is_log=is_log, return_confidence=True)
+        plain = ops.Compute_result(S, 8, 5, sxy, sxy, inputs[3], inputs[4], outdoor=True, input_is_log=is_log)
+        assert len(out) == 6 and len(plain) == 5 and all(same_bits(a, b) for a, b in zip(plain, out[:5]))
+        err = np.abs(out[5].cpu().numpy() - want).max()
+        print("Compute_result(input_is_log=%s): max |conf - definition| = %.3g" % (is_log, err))
+        assert err <= BOUND
+
+
+def test_scatter_follows_the_permutation_of_pts16(ops):
+    B = 3
+    rng = np.random.default_rng(5)
+    ifn = rng.random((B, 144)) < 0.4
+    ifn[1] = True                                             # one fully masked row
+    P = int((~ifn).sum())
+    pts = rng.random((B, 144, 2)).astype(np.float32) * 24
+    mk1 = rng.random((P, 16, 2)).astype(np.float32) * 96
+    label = np.where(rng.random((P * 16, 2)) < 0.3, -10.0, 1e8).astype(np.float32)
+    conf = (rng.permutation(P * 16) + 1).astype(np.float32).reshape(P, 16)       # distinct integers below 2^24
+    f16, p16, c16 = ops.refine_scatter(cu(ifn), cu(pts), cu(mk1), cu(label), conf=cu(conf))
+    f16p, p16p = ops.refine_scatter(cu(ifn), cu(pts), cu(mk1), cu(label))
+    assert same_bits(f16, f16p) and same_bits(p16, p16p) and c16.shape == (B, 2304) and c16.dtype == torch.float32
+    # pats.py:64-71 restated: per-cell values repeated over the 16 sub-cells, the surviving cells' filled in compaction order
+    cell = np.zeros((B, 144, 16), np.float32)
+    cell[~ifn] = conf
+    lab = np.zeros((B, 144, 16), np.float32)
+    lab[~ifn] = label[:, 0].reshape(P, 16)
+    no = ifn[:, :, None].repeat(16, 2) | (lab < -9.9)
+    perm = lambda a: a.reshape(B, 12, 12, 4, 4).transpose(0, 1, 3, 2, 4).reshape(B, 2304)       # noqa: E731
+    assert np.array_equal(f16.cpu().numpy(), perm(no))
+    assert np.array_equal(c16.cpu().numpy(), np.where(perm(no), 0.0, perm(cell)).astype(np.float32))
+    assert (c16[1] == 0).all() and int((c16 > 0).sum()) == int((~perm(no)).sum()) > 0
+
+
+def _small_batch(mixed):
+    """Two pairs at the smallest grids the batch tests use, run once with confidence and once without."""
+    from pats_amd import batch
+    if mixed:
+        from test_mixed_batch_gpu import _MixedNets
+        nets = [synth.SynthNets(seed=synth.SEED + 4040, h=6, w=9), synth.SynthNets(seed=synth.SEED + 40, h=5, w=6)]
+        imgs = [tuple(cu(x) for x in n.images()) for n in nets]
+        pack = batch.pack_pairs(imgs)
+        cap = batch.MixedCapacities([(n.h, n.w) for n in nets])
+        runs = [batch.forward_pairs_mixed(pack, _MixedNets(nets, pack), cap, confidence=c) for c in (True, False)]
+    else:
+        nets = [synth.SynthNets(seed=synth.SEED + 40, h=5, w=6), synth.SynthNets(seed=synth.SEED + 1040, h=5, w=6)]
+        imgs = [n.images() for n in nets]
+        lefts, rights = cu(np.concatenate([i[0] for i in imgs])), cu(np.concatenate([i[1] for i in imgs]))
+        cap = batch.Capacities(2, 5, 6)
+        runs = [batch.forward_pairs(lefts, rights, _BatchNets(nets), cap, confidence=c) for c in (True, False)]
+    return nets, cap, runs[0], runs[1]
+
+
+@pytest.mark.parametrize("mixed", [False, True])
+def test_compaction_and_regroup_carry_the_confidence_in_the_matches_slots(ops, mixed):
+    nets, cap, out, _ = _small_batch(mixed)
+    rows, co, ifn16 = out["rows"], out["coarse"], out["if_nomatching16"]
+    ids = torch.arange(1, ifn16.numel() + 1, dtype=torch.float32, device="cuda").reshape(ifn16.shape)     # below 2^24
+    ml, mr, mrow, M, mc = ops.get_result_chunks(rows, ifn16, co["avn"], out["stages"]["pts16"], co["xsn"], conf16=ids)
+    plain = ops.get_result_chunks(rows, ifn16, co["avn"], out["stages"]["pts16"], co["xsn"])
+    n = int(M.item())
+    live = int(rows.chunk_base[-1].item())
+    keep = ~ifn16.clone()
+    keep[live:] = False                                        # rows past the table's total emit nothing
+    assert n == int(keep.sum()) > 100 and int(plain[3].item()) == n
+    assert torch.equal(mc[:n], ids[keep]) and torch.equal(mrow[:n].long(), torch.nonzero(keep)[:, 0])
+    assert same_bits(ml[:n], plain[0][:n]) and same_bits(mr[:n], plain[1][:n]) and torch.equal(mrow[:n], plain[2][:n])
+    for P in (None, out["P"]):                                 # without and with the summary tail
+        got = ops.matches_by_pair(rows, ml, mr, mrow, M, P=P, match_conf=mc)
+        want = ops.matches_by_pair(rows, ml, mr, mrow, M, P=P)
+        assert len(got) == len(want) + 1 and same_bits(got[0][:n], want[0][:n]) and same_bits(got[1][:n], want[1][:n])
+        assert all(torch.equal(a, b) for a, b in zip(got[2:-1], want[2:]))            # pair_off and the summary tail
+        off = got[2].cpu().tolist()
+        pair_of_row = (rows.row_pair if mixed else rows.row_cell // (rows.h * rows.w))[:live].long()
+        sel_row = torch.nonzero(keep)[:, 0]
+        for p in range(cap.pairs):
+            assert torch.equal(got[-1][off[p]:off[p + 1]], ids[keep][pair_of_row[sel_row] == p]), p
+        assert off[cap.pairs] == n
+    # M = 0: every sub-cell masked
+    none = torch.ones_like(ifn16)
+    ml0, mr0, mrow0, M0, mc0 = ops.get_result_chunks(rows, none, co["avn"], out["stages"]["pts16"], co["xsn"], conf16=ids)
+    assert int(M0.item()) == 0
+    g0 = ops.matches_by_pair(rows, ml0, mr0, mrow0, M0, match_conf=mc0)
+    assert g0[2].cpu().tolist() == [0] * (cap.pairs + 1)
+
+
+@pytest.mark.parametrize("mixed", [False, True])
+def test_end_to_end_confidence_rides_with_every_match(mixed):
+    from pats_amd import batch
+    nets, cap, out, plain = _small_batch(mixed)
+    per_pair = batch.split_by_pair(out, cap)
+    per_plain = batch.split_by_pair(plain, cap)
+    assert "match_conf" in out and "match_conf" not in plain and len(out["by_pair"]) == 4 and len(plain["by_pair"]) == 3
+    M = int(out["M"].item())
+    assert M == int(plain["M"].item()) and same_bits(out["matches_l"][:M], plain["matches_l"][:M]) and \
+        same_bits(out["matches_r"][:M], plain["matches_r"][:M]) and torch.equal(out["summary"], plain["summary"])
+    for p, n in enumerate(nets):
+        l, r, c = per_pair[p]
+        assert len(per_plain[p]) == 2 and same_bits(l, per_plain[p][0]) and same_bits(r, per_plain[p][1])
+        left, right = [cu(x) for x in n.images()]
+        cap1 = batch.Capacities(1, n.h, n.w)
+        alone = batch.forward_pairs(left, right, _BatchNets([n]), cap1, confidence=True)
+        (l1, r1, c1), = batch.split_by_pair(alone, cap1)
+        assert l.shape[0] > 100 and c.shape == (l.shape[0],) and c.dtype == torch.float32
+        assert same_bits(l, l1) and same_bits(r, r1) and same_bits(c, c1), p
+        assert bool(((c > 0) & (c <= 1)).all())
+        print("pair %d: %d matches, confidence %.3f .. %.3f, median %.3f" % (p, c.shape[0], c.min(), c.max(), c.median()))
+
+
+def test_entries_refuse_bad_confidence_pointers_before_any_launch(ops, inputs):
+    """On the device, with every other argument valid: a null or misaligned confidence pointer is refused, nothing is written."""
+    import ctypes
+    from pats_amd import _lib
+    lib = _lib.lib()
+    d0, d1, sc, ps, pt = (t[:3].contiguous() for t in inputs)
+    sxy = torch.sqrt(sc.reshape(3, 64) + 1e-8)
+    m0 = torch.full((3, 16, 2), SENTINEL, device="cuda")
+    m1, label, ifm = m0.clone(), torch.full((48, 2), SENTINEL, device="cuda"), torch.full((3, 16), 0x5A, dtype=torch.uint8, device="cuda")
+    conf = torch.full((3, 16), SENTINEL, device="cuda")
+    q = lambda t: ctypes.c_void_p(t.data_ptr())       # noqa: E731
+    for bad in (None, ctypes.c_void_p(conf.data_ptr() + 2), ctypes.c_void_p(conf.data_ptr() + 1)):
+        rc = lib.pats_third_level_typed_conf(q(d0), q(d1), 0, 3, None, 128, q(sc), q(sxy), q(sxy), q(ps), q(pt), 100, 1, q(m0), q(m1),
+                                             q(label), q(ifm), None, bad, None)
+        assert rc != 0 and b"conf" in lib.pats_last_error()
+        S = torch.rand((3, 65, 65), device="cuda")
+        rc = lib.pats_compute_result_ws_conf_f32(q(S), 0, 3, q(sxy), q(sxy), q(ps), q(pt), 1, q(m0), q(m1), None, q(label), q(ifm), bad,
+                                                 None, 0, None)
+        assert rc != 0 and b"conf" in lib.pats_last_error()
+    torch.cuda.synchronize()
+    assert bool((m0 == SENTINEL).all()) and bool((m1 == SENTINEL).all()) and bool((label == SENTINEL).all()) and \
+        bool((ifm == 0x5A).all()) and bool((conf == SENTINEL).all())
