@@ -711,6 +711,34 @@ int pats_matches_by_row_pair_summary_conf_f32(const float* matches_l, const floa
                                               float* out_conf, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
                                               void* workspace, size_t workspace_bytes, pats_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pair top-K (ABI 8, symbols added): each pair's K most confident matches out of the regrouped hand-over
+ * (pats_matches_by_(row_)pair_summary_conf_f32: matches_l / matches_r [cap,2], conf [cap], pair_off [pairs + 1] - a longer buffer
+ * with the summary behind the offsets is fine), exact and deterministic, ONE launch for the whole batch, no host read.
+ * For pair p: lo = pair_off[p], hi = pair_off[p + 1] (both clamped to [0, cap] on the device; hi <= lo is an empty pair - a stale
+ * pair_off never causes a read outside the arrays), n = hi - lo, i in 0..n-1 the position inside the pair's list.
+ *   key(i)      = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000), b = the 32 bits of conf[lo + i]: the order-preserving map of float32
+ *                 onto uint32.  On [0, 1] a larger key is a larger confidence; +inf and a positive NaN rank ABOVE every number
+ *                 (a broken confidence shows up first instead of vanishing), negative values and negative NaNs below 0.0
+ *   eligible    use_min_conf == 0, or key(i) >= key(min_conf) - for finite non-negative values conf >= min_conf, inclusive
+ *   ranking     eligible matches by key descending, ties by i ascending (a stable descending sort)
+ *   top_count   [pairs] int64: min(K, number of eligible matches)
+ *   j <  count  top_idx[p,j] = the i of rank j; top_l[p,j], top_r[p,j], top_conf[p,j] = matches_l[lo+i], matches_r[lo+i],
+ *               conf[lo+i], bit for bit
+ *   j >= count  top_idx = -1, top_l = top_r = top_conf = 0.0: every call defines every byte of every output
+ * top_l, top_r [pairs,K,2] float32, top_conf [pairs,K] float32, top_idx [pairs,K] int32.  1 <= K <= pats_topk_by_pair_max_k()
+ * (8192: the composites of one pair are sorted in 64 KB of LDS).  cap = the rows the input arrays hold (cap == 0: every pair
+ * empty, outputs defined).  Refused before any launch (pats_last_error names the argument): a null pointer; matches_l / matches_r /
+ * top_l / top_r off 8 bytes (read and written as float2), conf / top_conf / top_idx off 4, pair_off / top_count off 8; pairs < 1,
+ * cap < 0 (or >= 2^31 - 1: top_idx is int32), K < 1, K > max_k; use_min_conf with a NaN or negative min_conf; a workspace smaller
+ * than pats_topk_by_pair_workspace_bytes (0 today: the kernel keeps everything in LDS; workspace may then be null). */
+int64_t pats_topk_by_pair_max_k(void);
+size_t pats_topk_by_pair_workspace_bytes(int64_t pairs, int64_t K);
+int pats_topk_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                          int64_t pairs, int64_t cap, int64_t K, int use_min_conf, float min_conf, float* top_l, float* top_r,
+                          float* top_conf, int32_t* top_idx, int64_t* top_count, void* workspace, size_t workspace_bytes,
+                          pats_stream_t stream);
+
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the
  * keys, out = prob v.  query [batch,dim,heads,n], key / value [batch,dim,heads,m] (the view

@@ -223,6 +223,11 @@ SIGNATURES = {
     "pats_matches_by_row_pair_summary_conf_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                           c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                           c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair top-K over the regrouped matches (csrc/topk.hip)
+    "pats_topk_by_pair_max_k": (c_i64, []),
+    "pats_topk_by_pair_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_topk_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_f, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

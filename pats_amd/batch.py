@@ -378,3 +378,65 @@ def split_by_pair(out, cap):
     for s_, i in enumerate(out["caller_of"]):
         per_caller[i] = per_slot[s_]
     return per_caller
+
+
+def topk_by_pair(out, cap, K, min_conf=None):
+    """Device side, after (or instead of) group_by_pair: each pair's K most confident matches (ops.topk_by_pair: one launch over
+    all pairs, no host read; confidence descending, ties by the position in the pair's list; min_conf keeps conf >= min_conf).
+    Needs a result made with confidence=True.  Adds `topk` = (top_l [pairs,K,2], top_r [pairs,K,2], top_conf [pairs,K],
+    top_idx [pairs,K] int32, top_count [pairs] int64) to the result and returns it; rows in SLOT order for a mixed pack
+    (split_topk_by_pair hands them back in the caller's).  If the result is not regrouped yet this does it, with ONE int64 buffer
+    of (pairs + 4) + pairs entries - group_by_pair's summary, then top_count - kept as `topk_summary`: the whole hand-over is then
+    still one device-to-host copy.  After a group_by_pair of the caller's own, top_count is a tensor of its own.  Nothing is
+    removed from the full lists: this is a selection by the third level's confidence alone - no mutual check, no suppression."""
+    if "match_conf" not in out:
+        raise ValueError("topk_by_pair: needs a result made with confidence=True")
+    top_count = None
+    if "by_pair" not in out:
+        ml, mr, mc = out["matches_l"], out["matches_r"], out["match_conf"]
+        both = torch.empty((2 * cap.pairs + 4,), dtype=torch.int64, device=ml.device)
+        group_by_pair(out, cap, buffers=(torch.empty_like(ml), torch.empty_like(mr), both[:cap.pairs + 4], torch.empty_like(mc)))
+        out["topk_summary"] = both
+    if "topk_summary" in out:                       # still the buffer behind `summary`?  (a regroup of the caller's own since then
+        if out["topk_summary"].data_ptr() == out["summary"].data_ptr():             # has its summary elsewhere)
+            top_count = out["topk_summary"][cap.pairs + 4:]
+        else:
+            del out["topk_summary"]
+    ml, mr, _, mc = out["by_pair"]
+    dest = None
+    if top_count is not None:
+        dev, K = ml.device, int(K)
+        dest = (torch.empty((cap.pairs, K, 2), dtype=torch.float32, device=dev), torch.empty((cap.pairs, K, 2), dtype=torch.float32, device=dev),
+                torch.empty((cap.pairs, K), dtype=torch.float32, device=dev), torch.empty((cap.pairs, K), dtype=torch.int32, device=dev),
+                top_count)
+    out["topk"] = ops.topk_by_pair(ml, mr, mc, out["summary"], K, min_conf=min_conf, out=dest, pairs=cap.pairs)
+    return out["topk"]
+
+
+def split_topk_by_pair(out, cap):
+    """Host side, AFTER the step: per-pair (l [c,2], r [c,2], conf [c], idx [c]) slices of a topk_by_pair result, c = the pair's
+    top_count, in the caller's order for a forward_pairs_mixed result.  Raises on the capacity overflows split_by_pair raises on.
+    Device-to-host copies: ONE when topk_by_pair did the regroup itself (`topk_summary`: offsets, M, P, status and the counts in
+    one buffer), TWO otherwise (`summary`, then top_count)."""
+    if "topk" not in out:
+        raise ValueError("split_topk_by_pair: run topk_by_pair first")
+    tl, tr, tc, ti, tn = out["topk"]
+    if "topk_summary" in out:
+        o = out["topk_summary"].cpu().tolist()            # the one synchronisation of a batch
+        o, counts = o[:cap.pairs + 4], o[cap.pairs + 4:]
+    else:
+        o, counts = out["summary"].cpu().tolist(), tn.cpu().tolist()
+    M, P, status = o[cap.pairs + 1:]
+    if status & 1:
+        raise RuntimeError("pats_amd.batch: a pair needed more than Cmax = %d chunks" % cap.Cmax)
+    if status & 2:
+        raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
+    if P > cap.P_cap:
+        raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
+    per_slot = [(tl[p, :counts[p]], tr[p, :counts[p]], tc[p, :counts[p]], ti[p, :counts[p]]) for p in range(cap.pairs)]
+    if "caller_of" not in out:
+        return per_slot
+    per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order
+    for s_, i in enumerate(out["caller_of"]):
+        per_caller[i] = per_slot[s_]
+    return per_caller

@@ -111,4 +111,15 @@ __device__ __forceinline__ float wave_sum_xbar(float v, int lane) {
     return v;
 }
 
+// inclusive prefix sum of an integer over the 64 lanes (lane l gets v[0] + ... + v[l]): six steps on the LDS crossbar.  Counts
+// need every bit, so this does not go through the float helpers above.
+__device__ __forceinline__ uint32_t wave_scan_inclusive_u32(uint32_t v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane - off) & 63) << 2, (int)v);      // lane < off: wraps, discarded
+        v += lane >= off ? up : 0u;
+    }
+    return v;
+}
+
 }  // namespace pats

@@ -1562,6 +1562,57 @@ def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None, 
     return ol, orr, off[:rows.pairs + 1], off
 
 
+def topk_max_k():
+    """The largest K topk_by_pair takes (pats_topk_by_pair_max_k)."""
+    return int(_L().pats_topk_by_pair_max_k())
+
+
+def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=None, pairs=None):
+    """Each pair's K most confident matches out of matches_by_pair's regrouped lists, ON THE DEVICE: one launch for the whole
+    batch, no host read (pats_topk_by_pair_f32; include/pats_amd.h holds the definition).  matches_l / matches_r [cap,2], conf
+    [cap] float32, pair_off the [pairs + 1] int64 view matches_by_pair returns - or, with pairs= given, a longer buffer that
+    starts with those offsets (the summary buffer).  min_conf: keep only matches with conf >= min_conf (inclusive).
+    Returns (top_l [pairs,K,2], top_r [pairs,K,2], top_conf [pairs,K], top_idx [pairs,K] int32, top_count [pairs] int64): rank j
+    of pair p is the match at position top_idx[p,j] of the pair's list, by confidence descending, ties by position ascending
+    (+inf and a positive NaN rank first); past top_count[p] top_idx is -1 and the rest 0.0.  out: the five destinations."""
+    for t, name in ((matches_l, "matches_l"), (matches_r, "matches_r"), (conf, "conf"), (pair_off, "pair_off")):
+        if isinstance(t, torch.Tensor) and t.is_cuda and not t.is_contiguous():
+            raise RuntimeError("topk_by_pair: %s must be contiguous" % name)
+    ml, mr, cf = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r"), _dev(conf, "conf").reshape(-1)
+    pair_off = _dev(pair_off, "pair_off", torch.int64)
+    if pair_off.dim() != 1:
+        raise RuntimeError("topk_by_pair: pair_off must be an int64 vector")
+    if pairs is None:
+        pairs = pair_off.numel() - 1
+    pairs, K, cap = int(pairs), int(K), int(cf.numel())
+    if pairs < 1 or pair_off.numel() < pairs + 1:
+        raise RuntimeError("topk_by_pair: pair_off holds %d entries, %d pairs need %d" % (pair_off.numel(), pairs, pairs + 1))
+    if ml.dim() != 2 or ml.shape[1] != 2 or ml.shape != mr.shape or ml.shape[0] != cap:
+        raise RuntimeError("topk_by_pair: matches_l / matches_r must be [cap,2] and conf [cap]")
+    if not 1 <= K <= topk_max_k():
+        raise RuntimeError("topk_by_pair: K = %d, must lie in 1 .. %d" % (K, topk_max_k()))
+    dev = ml.device
+    if out is None:
+        out = (torch.empty((pairs, K, 2), dtype=torch.float32, device=dev), torch.empty((pairs, K, 2), dtype=torch.float32, device=dev),
+               torch.empty((pairs, K), dtype=torch.float32, device=dev), torch.empty((pairs, K), dtype=torch.int32, device=dev),
+               torch.empty((pairs,), dtype=torch.int64, device=dev))
+    if len(out) != 5:
+        raise RuntimeError("topk_by_pair: out must be (top_l, top_r, top_conf, top_idx, top_count)")
+    want = (("top_l", torch.float32, (pairs, K, 2)), ("top_r", torch.float32, (pairs, K, 2)), ("top_conf", torch.float32, (pairs, K)),
+            ("top_idx", torch.int32, (pairs, K)), ("top_count", torch.int64, (pairs,)))
+    for t, (name, dt, shape) in zip(out, want):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("topk_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    nws = _L().pats_topk_by_pair_workspace_bytes(pairs, K)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:                                # empty tensors have no address; the call is valid and reads none of the three
+        ml = mr = cf = torch.empty((2,), dtype=torch.float32, device=dev)
+    _check(_L().pats_topk_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(cf), _ptr(pair_off), pairs, cap, K, 0 if min_conf is None else 1,
+                                      0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                      _ptr(out[3]), _ptr(out[4]), _ptr(ws), nws, _stream()), "topk_by_pair")
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------------
 # ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
 # ------------------------------------------------------------------------------------------------
