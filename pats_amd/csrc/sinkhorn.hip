@@ -989,8 +989,9 @@ sinkhorn_cu_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
 //   * the cross-wave column sums are formed ONCE (thread j < 320 adds the 16 partials of column j
 //     in the old order and publishes b_j) instead of by every wave for itself: 16 + 5 LDS reads a
 //     lane of five waves instead of 80 a lane of all sixteen, at the price of a second barrier.
-// sinkhorn_cu_kernel stays as the A/B partner (diagnostic library: PATS_CU_V1=1); the GPU test
-// holds the two to torch.equal.
+// sinkhorn_cu_kernel stays as the A/B partner (diagnostic library: PATS_CU_V1=1); tools/cu2_ab.py
+// holds the two to bit equality.  The diagnostic library is built on request only, so no test of
+// the suite can: tests/test_coarse_solver_edges_gpu.py holds THIS kernel to a float64 reference.
 // ------------------------------------------------------------------------------------------
 template <int RPW, int CPL>
 __global__ void __launch_bounds__(1024)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """sinkhorn_cu2_kernel against sinkhorn_cu_kernel (diagnostic library: PATS_CU_V1=1 selects the first version): the coarse level's
-log-plans of 48 + 1 problems at 301x301 and a ragged 250x290 case must be BIT-IDENTICAL (the packed row pass and the once-formed
+log-plans of 48 + 1 problems at 301x301, a ragged 251x291 case and the solver shapes (304, 320), (289, 257), (160, 64), (29, 320)
+and (304, 31) must be BIT-IDENTICAL (the packed row pass and the once-formed
 column sums keep every operand and every summation order), and the time per solve is printed.  Run with PATS_AMD_DIAG_LIB=1; the
 script re-runs itself as two child processes (the switch is read once per process)."""
 import os, subprocess, sys, time
@@ -13,7 +14,12 @@ if len(sys.argv) > 1:
     from pats_amd import ops
     g = torch.Generator(device="cuda"); g.manual_seed(5)
     outs = {}
-    for name, (b, M, N) in {"coarse48": (48, 300, 300), "one": (1, 300, 300), "ragged": (3, 250, 290)}.items():
+    # (b, m, n) of the descriptors; the solver sees [m + 1, n + 1].  The last five are shape edges of tests/coarse_cases.py: every
+    # row slot and column slice full, slot 18 / slice 4 held by one wave / lane, every pair's second half padding, fewer rows
+    # than two per wave, fewer columns than lanes
+    shapes = {"coarse48": (48, 300, 300), "one": (1, 300, 300), "ragged": (3, 250, 290), "full": (3, 303, 319),
+              "one_wave_one_lane": (3, 288, 256), "half_pairs": (3, 159, 63), "few_rows": (3, 28, 319), "few_columns": (3, 303, 30)}
+    for name, (b, M, N) in shapes.items():
         base = torch.randn((b, 448, max(M, N)), device="cuda", generator=g)
         d0 = 3.0 * (base[:, :, :M] + 0.3 * torch.randn((b, 448, M), device="cuda", generator=g))
         d1 = 3.0 * (base[:, :, :N] + 0.3 * torch.randn((b, 448, N), device="cuda", generator=g))

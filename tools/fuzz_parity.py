@@ -41,7 +41,15 @@ def mass_close(got, want):
 
 def rand_shape(rng):
     """OT shapes: the resident ones, their neighbours, ragged ones, a few large."""
-    pick = rng.integers(0, 10)
+    pick = rng.integers(0, 11)
+    if pick == 10:
+        # the dispatch edges of the coarse solvers (csrc/sinkhorn.hip: cu_shape, stream_shape, the wg kernel's thread switch),
+        # redrawn until M + N fits the general kernel's LDS bound (launch_wg: (M + N) floats in 64 KiB)
+        while True:
+            M = int(rng.choice([29, 30, 31, 95, 96, 97, 303, 304, 305]))
+            N = int(rng.choice([30, 31, 32, 319, 320, 321]))
+            if (M + N) * 4 <= 64 * 1024:
+                return M, N
     if pick == 0:
         return 65, 65
     if pick == 1:
