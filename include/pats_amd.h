@@ -739,6 +739,60 @@ int pats_topk_by_pair_f32(const float* matches_l, const float* matches_r, const 
                           float* top_conf, int32_t* top_idx, int64_t* top_count, void* workspace, size_t workspace_bytes,
                           pats_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pair model verification (ABI 8, symbols added): H candidate epipolar models per pair tested against every match of the
+ * pair, the model with the most inliers, its inlier mask and - on request - the moment matrix of its inliers.  The O(H M) step
+ * of a hypothesise-and-verify search on the hand-over (or on a per-pair top-K of it), on the device, no host read; generating the
+ * hypotheses and everything after the mask (cheirality, pose) stay with the caller.
+ * Inputs
+ *   matches_l, matches_r [cap,2] float32, the stored (c0, c1) of the hand-over taken as they lie; conf [cap] float32 (optional)
+ *   the segment of pair p, in exactly ONE of two forms (both or neither: refused)
+ *     ragged   pair_off: int64, pairs + 1 entries (a longer buffer that starts with them - the summary buffer - is fine):
+ *              lo = pair_off[p], hi = pair_off[p + 1], both clamped to [0, cap] on the device, hi <= lo is an empty pair: a stale
+ *              table never causes a read outside the arrays.  (Where the segments of a corrupt table overlap, a row's mask is
+ *              that of one of its pairs.)  stride is ignored.
+ *     strided  counts_in [pairs] int64 and stride (the layout of the top-K outputs top_l / top_r / top_count): the segment starts
+ *              at p * stride and holds min(max(counts_in[p], 0), stride) rows; cap >= pairs * stride
+ *   models [pairs,H,3,3] float32, contiguous, row-major E; 1 <= H <= pats_epipolar_max_h() (65536: what the grid of the score
+ *              kernel and an int32 index carry comfortably; the kernel itself walks the models in chunks of 256)
+ *   thr [pairs] float32.  It lives on the device and cannot be refused: a pair whose thr is NaN or negative has NO inliers
+ *              (counts 0, best 0, best_count 0, mask 0, moments 0); the other pairs are unaffected
+ *   norm [pairs,8] float32 (optional) = (c0_l, c1_l, s0_l, s1_l, c0_r, c1_r, s0_r, s1_r): a point p becomes
+ *              x = ((p0 - c0) * s0, (p1 - c1) * s1, 1) - in float32 one subtract, then one multiply, never contracted, so a host
+ *              reproduces x bit for bit.  Without norm x = (p0, p1, 1)
+ *   use_min_conf, min_conf: a match PARTICIPATES iff use_min_conf == 0 or conf >= min_conf (inclusive; a NaN confidence does not
+ *              participate) - and iff its four coordinates, after norm, are finite
+ * The test of match i against model E:
+ *   a = E x_l,  b = E^T x_r,  r = x_r . a,  den = a0^2 + a1^2 + b0^2 + b1^2
+ *   inlier iff the match participates and den > 0 and r^2 <= thr^2 den
+ * - the squared Sampson error against thr^2 without the division.  A NaN anywhere makes it a non-inlier; an all-zero model has
+ * den = 0 and so no inliers: zero models may pad H.  The device evaluates it in float32 with fused multiply-adds (a0 =
+ * fma(E00, x0, fma(E01, x1, E02)), ..., den = fma(a0, a0, fma(a1, a1, fma(b0, b0, b1 b1)))); a verdict whose r^2 lies within a few
+ * float32 roundings of thr^2 den may differ from a float64 evaluation (docs/parity.md quantifies the band), but the counts, the
+ * winner and the mask of one call always agree with each other: one arithmetic serves all three.
+ * Outputs - every call defines every byte of every output
+ *   counts [pairs,H] int32      the inliers of every model
+ *   best [pairs] int32          the lowest index with the largest count;  best_count [pairs] int64 that count
+ *   inlier [cap] uint8          aligned with the input lists: 1 where the match is an inlier of its pair's best model, 0 everywhere
+ *                               else - rows outside every segment and the slack of strided rows included
+ *   moments [pairs,9,9] float64 (null: skipped) sum over the best model's inliers of q q^T, q = vec(x_r x_l^T) - the nine products
+ *                               in row-major order, formed in float64 from the float32 x (exact).  The summation order is fixed:
+ *                               two calls are bit-identical.  The eigenvector of the smallest eigenvalue is the least-squares refit
+ * cap == 0 is a valid call (counts 0, outputs defined; the match pointers must still be non-null).  Refused before any launch
+ * (pats_last_error names the argument): a null matches_l / matches_r / models / thr / counts / best / best_count / inlier;
+ * matches_l / matches_r off 8 bytes (read as float2), models / thr / norm / conf / counts / best off 4, pair_off / counts_in /
+ * best_count / moments off 8; both segment forms or neither; pairs < 1; H < 1 or H > max_h; cap < 0 or cap >= 2^31 - 1; in the strided
+ * form stride < 1 or pairs * stride > cap; use_min_conf without conf or with a NaN or negative min_conf; a grid of 2^31 workgroups
+ * or more (ceil(longest / 2048) * pairs * ceil(H / 256), longest = cap or stride); a workspace smaller than
+ * pats_epipolar_workspace_bytes (0 today: the counts are accumulated in the output; workspace may then be null). */
+int64_t pats_epipolar_max_h(void);
+size_t pats_epipolar_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                    int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                    int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                    int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                    void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the
  * keys, out = prob v.  query [batch,dim,heads,n], key / value [batch,dim,heads,m] (the view

@@ -440,3 +440,81 @@ def split_topk_by_pair(out, cap):
     for s_, i in enumerate(out["caller_of"]):
         per_caller[i] = per_slot[s_]
     return per_caller
+
+
+def _overflow_check(o, cap):
+    M, P, status = o[cap.pairs + 1:cap.pairs + 4]
+    if status & 1:
+        raise RuntimeError("pats_amd.batch: a pair needed more than Cmax = %d chunks" % cap.Cmax)
+    if status & 2:
+        raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
+    if P > cap.P_cap:
+        raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
+
+
+def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
+    """Device side, after the matching (and after topk_by_pair for on="topk"): every pair's H candidate epipolar models
+    (models [pairs,H,3,3], thr [pairs], norm [pairs,8] or None - all float32 GPU tensors in the CALLER's pair order) tested against
+    the pair's matches (ops.epipolar_score_by_pair: no host read).  on="all": the regrouped full lists (regroups first if the
+    result is not grouped yet, as topk_by_pair does); on="topk": the rows of a prior topk_by_pair result, in strided form.
+    min_conf (needs a result made with confidence=True): only matches with conf >= min_conf take part.
+    Adds `verified` = (counts [pairs,H] int32, best [pairs] int32, best_count [pairs] int64, inlier uint8 aligned with the lists
+    that were scored - [M_cap] for "all", [pairs*K] for "topk" - [, moments [pairs,9,9] float64]) to the result and returns it; rows
+    in SLOT order for a mixed pack (models / thr / norm are permuted to it on the device; split_verified_by_pair hands the pairs
+    back in the caller's order).  The matches, the regrouped lists and a top-K of the same step are not touched."""
+    if on not in ("all", "topk"):
+        raise ValueError("verify_by_pair: on must be \"all\" or \"topk\", got %r" % (on,))
+    if on == "topk" and "topk" not in out:
+        raise ValueError("verify_by_pair: on=\"topk\" needs a topk_by_pair result")
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("verify_by_pair: min_conf needs a result made with confidence=True")
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        if "caller_of_dev" not in out:
+            out["caller_of_dev"] = torch.tensor(out["caller_of"], dtype=torch.int64, device=models.device)
+        idx = out["caller_of_dev"]
+        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    if on == "topk":
+        tl, tr, tc, _, tn = out["topk"]
+        ver = ops.epipolar_score_by_pair(tl, tr, models, thr, stride=int(tl.shape[1]), counts=tn, conf=tc if min_conf is not None else None,
+                                         min_conf=min_conf, norm=norm, moments=moments)
+    else:
+        if "by_pair" not in out:
+            group_by_pair(out, cap)
+        bp = out["by_pair"]
+        ver = ops.epipolar_score_by_pair(bp[0], bp[1], models, thr, pair_off=out["summary"], conf=bp[3] if min_conf is not None else None,
+                                         min_conf=min_conf, norm=norm, moments=moments, pairs=cap.pairs)
+    out["verified"], out["verified_on"] = ver, on
+    return ver
+
+
+def split_verified_by_pair(out, cap):
+    """Host side, AFTER the step: per-pair (l [c,2], r [c,2], inlier [c] bool, best, best_count) of a verify_by_pair result - the
+    lists that were scored (the pair's full list for on="all", its top_count top-K rows for on="topk") with the best model's inlier
+    mask, views of the device tensors; best / best_count are 0-d device views (their values are not read here).  In the caller's
+    order for a forward_pairs_mixed result.  Raises on the capacity overflows split_by_pair raises on.  Device-to-host copies: ONE
+    (`summary`; for on="topk" `topk_summary` when topk_by_pair did the regroup itself), TWO for on="topk" otherwise."""
+    if "verified" not in out:
+        raise ValueError("split_verified_by_pair: run verify_by_pair first")
+    best, best_count, inl = out["verified"][1:4]
+    if out["verified_on"] == "topk":
+        tl, tr, _, _, tn = out["topk"]
+        if "topk_summary" in out:
+            o = out["topk_summary"].cpu().tolist()            # the one synchronisation of a batch
+            o, counts = o[:cap.pairs + 4], o[cap.pairs + 4:]
+        else:
+            o, counts = out["summary"].cpu().tolist(), tn.cpu().tolist()
+        _overflow_check(o, cap)
+        mask = inl.view(cap.pairs, -1)
+        per_slot = [(tl[p, :counts[p]], tr[p, :counts[p]], mask[p, :counts[p]].bool(), best[p], best_count[p]) for p in range(cap.pairs)]
+    else:
+        o = out["summary"].cpu().tolist()                     # the one synchronisation of a batch
+        _overflow_check(o, cap)
+        ml, mr = out["by_pair"][:2]
+        per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]], inl[o[p]:o[p + 1]].bool(), best[p], best_count[p]) for p in range(cap.pairs)]
+    if "caller_of" not in out:
+        return per_slot
+    per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order
+    for s_, i in enumerate(out["caller_of"]):
+        per_caller[i] = per_slot[s_]
+    return per_caller

@@ -1,0 +1,341 @@
+// Per-pair verification of candidate epipolar models against the hand-over's matches: for every pair of a batch H 3x3 models are
+// tested against every match of the pair's segment (squared Sampson error against thr^2, without the division), the model with the
+// most inliers wins (lowest index on a tie), its inlier mask is written beside the match lists and - on request - the 9x9 moment
+// matrix of its inliers, the input of a least-squares refit.  No host read.  include/pats_amd.h states the definition;
+// docs/kernels.md 4.7 the design.
+//
+//   score   grid = tiles x pairs x model chunks, 256 threads.  A thread keeps EPI_R = 8 matches (normalised once, as four packed
+//           pairs of float2 lanes) in registers and walks the EPI_CHUNK = 256 models of its chunk; a model is nine wave-uniform floats
+//           (scalar loads, one model ahead).  Per model: v_pk_fma_f32 on the four pairs, the verdicts as wave ballots, their
+//           popcounts added on the scalar unit and kept by lane h % 64 in a counter register; every 64 models the
+//           register goes to LDS, at the end the four waves' counters are added and ONE integer atomic per workgroup and model with a
+//           non-zero count goes to counts[p, h] (integer adds: the order does not matter).  Blocks past a segment's end return.
+//   argmax  one workgroup per pair over counts[p, :]: the largest count, the lowest index that holds it
+//   mask    one workgroup per pair: the winner's verdict for every match of the segment with the arithmetic of the score kernel
+//           (same device function: the mask and the winner's count agree exactly), the moments in float64 in a fixed order
+//           (thread-local in index order, an xor tree over the wave, the waves in order)
+// A match that does not participate (outside the segment, gated by min_conf, a non-finite coordinate) carries a NaN x_l: every
+// comparison with it is false, the inner loop needs no mask.
+#include "common.hpp"
+
+namespace pats {
+
+constexpr int EPI_THREADS = 256;
+constexpr int EPI_WAVES = EPI_THREADS / WAVE;
+constexpr int EPI_R = 8;                               // matches per thread
+constexpr int EPI_TILE = EPI_THREADS * EPI_R;          // matches per workgroup
+constexpr int EPI_CHUNK = 256;                         // models per workgroup
+constexpr int EPI_MAX_H = 65536;
+constexpr int EPI_MASK_THREADS = 512;
+constexpr int EPI_MASK_WAVES = EPI_MASK_THREADS / WAVE;
+constexpr int EPI_MOM = 45;                            // upper triangle of the 9x9 moment matrix
+
+typedef float e2f __attribute__((ext_vector_type(2)));
+
+// the segment of pair p: ragged (pair_off) or strided (stride, counts_in); always inside [0, cap]
+__device__ __forceinline__ void epi_segment(const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride,
+                                            int64_t cap, int64_t p, int64_t& lo, uint32_t& n) {
+    if (counts_in) {                                    // pairs * stride <= cap (checked on the host)
+        int64_t c = counts_in[p];
+        c = c < 0 ? 0 : (c > stride ? stride : c);
+        lo = p * stride;
+        n = (uint32_t)c;
+    } else {
+        int64_t a = pair_off[p], b = pair_off[p + 1];
+        a = a < 0 ? 0 : (a > cap ? cap : a);
+        b = b < 0 ? 0 : (b > cap ? cap : b);
+        lo = a;
+        n = b > a ? (uint32_t)(b - a) : 0u;             // cap < 2^31 (checked on the host)
+    }
+}
+
+struct EpiNorm { float c0l, c1l, s0l, s1l, c0r, c1r, s0r, s1r; };
+
+__device__ __forceinline__ EpiNorm epi_norm(const float* __restrict__ norm, int64_t p) {
+    EpiNorm m{0.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f, 1.0f, 1.0f};
+    if (norm) {
+        const float* q = norm + p * 8;
+        m = EpiNorm{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
+    }
+    return m;
+}
+
+// match i of the segment as (x_l, x_r); l0 = NaN unless the match participates
+__device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const float2* __restrict__ mr, const float* __restrict__ conf,
+                                         uint32_t i, uint32_t n, bool has_norm, const EpiNorm& nm, bool gate, float min_conf,
+                                         float& l0, float& l1, float& r0, float& r1) {
+    l0 = __builtin_nanf("");
+    l1 = r0 = r1 = 0.0f;
+    if (i >= n) return;
+    float2 a = ml[i], b = mr[i];
+    if (has_norm) {                                     // one subtract, one multiply (no contraction: -ffp-contract=off)
+        a.x = (a.x - nm.c0l) * nm.s0l; a.y = (a.y - nm.c1l) * nm.s1l;
+        b.x = (b.x - nm.c0r) * nm.s0r; b.y = (b.y - nm.c1r) * nm.s1r;
+    }
+    bool ok = __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(b.x) && __builtin_isfinite(b.y);
+    if (gate) ok = ok && conf[i] >= min_conf;           // false for a NaN confidence
+    l1 = a.y; r0 = b.x; r1 = b.y;
+    if (ok) l0 = a.x;
+}
+
+__device__ __forceinline__ e2f epi_fma(e2f a, e2f b, e2f c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ e2f epi_splat(float v) { return e2f{v, v}; }
+
+// two matches against one model: r^2, thr^2 den and den.  THE arithmetic of the test - the score and the mask kernel both call it;
+// match k is an inlier iff den[k] > 0 and r2[k] <= lim[k].
+__device__ __forceinline__ void epi_test2(const float (&e)[9], float t2, e2f l0, e2f l1, e2f r0, e2f r1, e2f& r2, e2f& lim, e2f& den) {
+    const e2f a0 = epi_fma(epi_splat(e[0]), l0, epi_fma(epi_splat(e[1]), l1, epi_splat(e[2])));
+    const e2f a1 = epi_fma(epi_splat(e[3]), l0, epi_fma(epi_splat(e[4]), l1, epi_splat(e[5])));
+    const e2f a2 = epi_fma(epi_splat(e[6]), l0, epi_fma(epi_splat(e[7]), l1, epi_splat(e[8])));
+    const e2f b0 = epi_fma(epi_splat(e[0]), r0, epi_fma(epi_splat(e[3]), r1, epi_splat(e[6])));
+    const e2f b1 = epi_fma(epi_splat(e[1]), r0, epi_fma(epi_splat(e[4]), r1, epi_splat(e[7])));
+    const e2f r = epi_fma(r0, a0, epi_fma(r1, a1, a2));
+    den = epi_fma(a0, a0, epi_fma(a1, a1, epi_fma(b0, b0, b1 * b1)));
+    r2 = r * r;
+    lim = epi_splat(t2) * den;
+}
+
+__device__ __forceinline__ void epi_model(const float* __restrict__ m, float (&e)[9]) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) e[k] = m[k];
+}
+
+__global__ void __launch_bounds__(EPI_THREADS)
+epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
+                      const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
+                      int pairs, int chunks, const float* __restrict__ models, int H, const float* __restrict__ thr,
+                      const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts) {
+    __shared__ int wave_cnt[EPI_WAVES][EPI_CHUNK];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // block -> (tile, pair, chunk), the tile slowest: the blocks that find work come first
+    const uint32_t b = blockIdx.x;
+    const int chunk = (int)(b % (uint32_t)chunks);
+    const int64_t p = (int64_t)((b / (uint32_t)chunks) % (uint32_t)pairs);
+    const uint32_t tile = b / ((uint32_t)chunks * (uint32_t)pairs);
+    int64_t lo;
+    uint32_t n;
+    epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
+    const uint64_t i0 = (uint64_t)tile * EPI_TILE;
+    if (i0 >= n) return;                                // workgroup-uniform
+    const float t = thr[p];
+    if (!(t >= 0.0f)) return;                           // NaN or negative threshold: the pair has no inliers (counts are zeroed)
+    const float t2 = t * t;
+
+    const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
+    const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
+    const float* conf = conf_ ? conf_ + lo : nullptr;
+    const EpiNorm nm = epi_norm(norm, p);
+    e2f l0[EPI_R / 2], l1[EPI_R / 2], r0[EPI_R / 2], r1[EPI_R / 2];
+#pragma unroll
+    for (int k = 0; k < EPI_R / 2; ++k) {
+        float a0, a1, a2, a3, c0, c1, c2, c3;
+        epi_load(ml, mr, conf, (uint32_t)i0 + (uint32_t)((2 * k) * EPI_THREADS + tid), n, norm != nullptr, nm, gate != 0, min_conf, a0, a1, a2, a3);
+        epi_load(ml, mr, conf, (uint32_t)i0 + (uint32_t)((2 * k + 1) * EPI_THREADS + tid), n, norm != nullptr, nm, gate != 0, min_conf, c0, c1, c2, c3);
+        l0[k] = e2f{a0, c0}; l1[k] = e2f{a1, c1}; r0[k] = e2f{a2, c2}; r1[k] = e2f{a3, c3};
+    }
+
+    const int h_lo = chunk * EPI_CHUNK;
+    const int nmod = H - h_lo < EPI_CHUNK ? H - h_lo : EPI_CHUNK;             // >= 1: chunks = ceil(H / EPI_CHUNK)
+    const float* m = models + ((int64_t)p * H + h_lo) * 9;
+    float e[9];
+    epi_model(m, e);
+    for (int h0 = 0; h0 < nmod; h0 += WAVE) {
+        const int jn = nmod - h0 < WAVE ? nmod - h0 : WAVE;
+        int acc = 0;
+        for (int j = 0; j < jn; ++j) {
+            float en[9];
+            const int hn = h0 + j + 1 < nmod ? h0 + j + 1 : h0 + j;            // one model ahead (the last one again: in bounds)
+            epi_model(m + (int64_t)hn * 9, en);
+            int cnt = 0;
+#pragma unroll
+            for (int k = 0; k < EPI_R / 2; ++k) {
+                e2f r2, lim, den;
+                epi_test2(e, t2, l0[k], l1[k], r0[k], r1[k], r2, lim, den);
+                // the two comparisons as ballots of their own, combined on the scalar unit
+                cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(den.x > 0.0f) & __builtin_amdgcn_ballot_w64(r2.x <= lim.x)) +
+                       __builtin_popcountll(__builtin_amdgcn_ballot_w64(den.y > 0.0f) & __builtin_amdgcn_ballot_w64(r2.y <= lim.y));
+            }
+            acc = lane == j ? cnt : acc;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) e[k] = en[k];
+        }
+        wave_cnt[wave][h0 + lane] = acc;                // h0 + lane < EPI_CHUNK; lanes past jn hold 0
+    }
+    wg_barrier();
+    if (tid < nmod) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < EPI_WAVES; ++w) s += wave_cnt[w][tid];
+        if (s) atomicAdd(&counts[(int64_t)p * H + h_lo + tid], s);
+    }
+}
+
+// one workgroup per pair: the largest count of counts[p, :], the lowest index that holds it
+__global__ void __launch_bounds__(256) epipolar_argmax_kernel(const int32_t* __restrict__ counts, int H, int32_t* __restrict__ best,
+                                                               int64_t* __restrict__ best_count) {
+    __shared__ int sv[256], si[256];
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int32_t* c = counts + p * H;
+    int v = -1, idx = 0x7fffffff;
+    for (int h = tid; h < H; h += 256) {                // ascending h: a later equal count does not replace an earlier one
+        const int x = c[h];
+        if (x > v) { v = x; idx = h; }
+    }
+    sv[tid] = v; si[tid] = idx;
+    wg_barrier();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int ov = sv[tid + s], oi = si[tid + s];
+            if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
+        }
+        wg_barrier();
+    }
+    if (tid == 0) { best[p] = si[0]; best_count[p] = (int64_t)sv[0]; }
+}
+
+// one workgroup per pair: the winner's inlier mask (the rows outside the segments were zeroed before) and the moments
+__global__ void __launch_bounds__(EPI_MASK_THREADS)
+epipolar_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
+                     const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
+                     const float* __restrict__ models, int H, const float* __restrict__ thr, const float* __restrict__ norm, int gate,
+                     float min_conf, const int32_t* __restrict__ best, const int64_t* __restrict__ best_count,
+                     uint8_t* __restrict__ inlier, double* __restrict__ moments) {
+    __shared__ double part[EPI_MASK_WAVES][EPI_MOM];
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t lo;
+    uint32_t n;
+    epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
+    const float t = thr[p];
+    const bool live = t >= 0.0f && best_count[p] > 0;  // otherwise no match is an inlier: the mask stays zero, the moments are zero
+    double acc[EPI_MOM];
+#pragma unroll
+    for (int k = 0; k < EPI_MOM; ++k) acc[k] = 0.0;
+    if (live) {                                         // workgroup-uniform
+        const float t2 = t * t;
+        int h = best[p];
+        h = h < 0 ? 0 : (h >= H ? H - 1 : h);
+        float e[9];
+        epi_model(models + ((int64_t)p * H + h) * 9, e);
+        const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
+        const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
+        const float* conf = conf_ ? conf_ + lo : nullptr;
+        const EpiNorm nm = epi_norm(norm, p);
+        for (uint32_t i0 = 0; i0 < n; i0 += EPI_MASK_THREADS) {
+            const uint32_t i = i0 + tid;
+            float xl0, xl1, xr0, xr1;
+            epi_load(ml, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, xl0, xl1, xr0, xr1);
+            e2f r2, lim, den;
+            epi_test2(e, t2, epi_splat(xl0), epi_splat(xl1), epi_splat(xr0), epi_splat(xr1), r2, lim, den);
+            const bool in0 = den.x > 0.0f && r2.x <= lim.x;
+            if (i < n) inlier[lo + i] = in0 ? 1 : 0;
+            if (moments && in0) {
+                const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
+                const double q[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};       // vec(x_r x_l^T): exact products
+                int k = 0;
+#pragma unroll
+                for (int u = 0; u < 9; ++u)
+#pragma unroll
+                    for (int v = u; v < 9; ++v) acc[k++] += q[u] * q[v];
+            }
+        }
+    }
+    if (!moments) return;
+#pragma unroll
+    for (int k = 0; k < EPI_MOM; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) part[wave][k] = v;
+    }
+    wg_barrier();
+    if (tid < EPI_MOM) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < EPI_MASK_WAVES; ++w) s += part[w][tid];
+        int u = 0, k = tid;                             // entry tid of the upper triangle -> (u, v)
+        while (k >= 9 - u) { k -= 9 - u; ++u; }
+        const int v = u + k;
+        double* mo = moments + p * 81;
+        mo[u * 9 + v] = s;
+        mo[v * 9 + u] = s;
+    }
+}
+
+}  // namespace pats
+
+using namespace pats;
+
+extern "C" int64_t pats_epipolar_max_h(void) { return EPI_MAX_H; }
+
+extern "C" size_t pats_epipolar_workspace_bytes(int64_t pairs, int64_t H, int64_t cap) {
+    (void)pairs; (void)H; (void)cap;
+    return 0;                                           // the counts are accumulated in the output itself
+}
+
+extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                               int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                               int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                               int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                               void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    (void)workspace;
+#define PATS_EPI_ALIGNED(ptr, align) \
+    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "epipolar_score_by_pair: " #ptr " must be " #align "-byte aligned")
+#define PATS_EPI_PTR(ptr, align)                                                        \
+    PATS_REQUIRE(ptr, "epipolar_score_by_pair: null " #ptr);                            \
+    PATS_EPI_ALIGNED(ptr, align)
+    PATS_EPI_PTR(matches_l, 8);
+    PATS_EPI_PTR(matches_r, 8);
+    PATS_EPI_PTR(models, 4);
+    PATS_EPI_PTR(thr, 4);
+    PATS_EPI_PTR(counts, 4);
+    PATS_EPI_PTR(best, 4);
+    PATS_EPI_PTR(best_count, 8);
+    PATS_REQUIRE(inlier, "epipolar_score_by_pair: null inlier");
+    PATS_EPI_ALIGNED(conf, 4);                          // optional pointers: null is aligned
+    PATS_EPI_ALIGNED(norm, 4);
+    PATS_EPI_ALIGNED(pair_off, 8);
+    PATS_EPI_ALIGNED(counts_in, 8);
+    PATS_EPI_ALIGNED(moments, 8);
+#undef PATS_EPI_PTR
+#undef PATS_EPI_ALIGNED
+    PATS_REQUIRE((pair_off != nullptr) != (counts_in != nullptr),
+                 "epipolar_score_by_pair: exactly one of pair_off (ragged segments) and counts_in (strided segments) must be given");
+    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "epipolar_score_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
+    PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "epipolar_score_by_pair: H = %lld (1 .. max_h = %lld)", (long long)H,
+                 (long long)pats_epipolar_max_h());
+    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "epipolar_score_by_pair: cap = %lld (0 .. 2^31 - 2)", (long long)cap);
+    if (counts_in) {
+        PATS_REQUIRE(stride >= 1, "epipolar_score_by_pair: stride = %lld must be at least 1", (long long)stride);
+        PATS_REQUIRE(stride <= cap && pairs <= cap / stride, "epipolar_score_by_pair: pairs * stride = %lld * %lld exceeds cap = %lld",
+                     (long long)pairs, (long long)stride, (long long)cap);
+    }
+    PATS_REQUIRE(!use_min_conf || conf, "epipolar_score_by_pair: min_conf needs conf");
+    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "epipolar_score_by_pair: min_conf = %g must be a non-negative number", (double)min_conf);
+    PATS_REQUIRE(workspace_bytes >= pats_epipolar_workspace_bytes(pairs, H, cap), "epipolar_score_by_pair: workspace too small");
+    const int64_t longest = counts_in ? stride : cap;   // the grid comes from the sizes alone: no host read of the counts
+    const int64_t tiles = ceil_div(longest, EPI_TILE), chunks = ceil_div(H, EPI_CHUNK);
+    PATS_REQUIRE(tiles * chunks <= 0x7fffffff / pairs, "epipolar_score_by_pair: pairs = %lld gives a grid of %lld x %lld x %lld workgroups (< 2^31)",
+                 (long long)pairs, (long long)tiles, (long long)pairs, (long long)chunks);
+    hipStream_t st = as_stream(stream);
+    int rc = fill_bytes(counts, 0, (size_t)pairs * (size_t)H * sizeof(int32_t), st);
+    if (rc != PATS_OK) return rc;
+    rc = fill_bytes(inlier, 0, (size_t)cap, st);
+    if (rc != PATS_OK) return rc;
+    const float* cf = use_min_conf ? conf : nullptr;    // without a threshold the confidence is not read
+    if (tiles > 0) {
+        hipLaunchKernelGGL(epipolar_score_kernel, dim3((unsigned)(tiles * pairs * chunks)), dim3(EPI_THREADS), 0, st, matches_l, matches_r,
+                           cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm, use_min_conf, min_conf,
+                           counts);
+        rc = check_launch("epipolar_score kernel");
+        if (rc != PATS_OK) return rc;
+    }
+    hipLaunchKernelGGL(epipolar_argmax_kernel, dim3((unsigned)pairs), dim3(256), 0, st, counts, (int)H, best, best_count);
+    rc = check_launch("epipolar_argmax kernel");
+    if (rc != PATS_OK) return rc;
+    hipLaunchKernelGGL(epipolar_mask_kernel, dim3((unsigned)pairs), dim3(EPI_MASK_THREADS), 0, st, matches_l, matches_r, cf, pair_off,
+                       counts_in, stride, cap, models, (int)H, thr, norm, use_min_conf, min_conf, best, best_count, inlier, moments);
+    return check_launch("epipolar_mask kernel");
+}

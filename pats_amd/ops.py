@@ -1613,6 +1613,102 @@ def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=Non
     return tuple(out)
 
 
+def epipolar_max_h():
+    """The largest number of models per pair epipolar_score_by_pair takes (pats_epipolar_max_h)."""
+    return int(_L().pats_epipolar_max_h())
+
+
+def epipolar_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None,
+                           norm=None, moments=False, out=None, pairs=None):
+    """H candidate epipolar models per pair against every match of the pair, ON THE DEVICE, no host read
+    (pats_epipolar_score_by_pair_f32; include/pats_amd.h holds the definition): match i is an inlier of the 3x3 model E iff
+    r^2 <= thr^2 den with a = E x_l, b = E^T x_r, r = x_r . a, den = a0^2 + a1^2 + b0^2 + b1^2 > 0 (squared Sampson error).
+    matches_l / matches_r [cap,2] float32 (also [pairs,K,2]: top-K outputs are taken as the flat [pairs*K,2] lists they are),
+    models [pairs,H,3,3], thr [pairs] float32.  The pairs' segments in exactly one of two forms: pair_off (int64 [pairs + 1] - or,
+    with pairs= given, a longer buffer that starts with the offsets) or stride + counts (int64 [pairs]: pair p = rows
+    p * stride .. + counts[p], the layout of topk_by_pair's outputs).  norm [pairs,8] = (c0_l, c1_l, s0_l, s1_l, c0_r, c1_r, s0_r,
+    s1_r): x = ((p0 - c0) * s0, (p1 - c1) * s1, 1); without it x = (p0, p1, 1).  min_conf (needs conf [cap]): only matches with
+    conf >= min_conf take part.  A pair whose thr is NaN or negative has no inliers.
+    Returns (counts [pairs,H] int32, best [pairs] int32 - the lowest index of the largest count -, best_count [pairs] int64,
+    inlier [cap] uint8 - 1 where the match is an inlier of its pair's best model, 0 everywhere else) and, with moments=True,
+    moments [pairs,9,9] float64 = the sum of q q^T over those inliers, q = vec(x_r x_l^T): torch.linalg.eigh of it is the
+    least-squares refit.  out: the four (five) destinations."""
+    named = [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
+             (counts, "counts"), (conf, "conf"), (norm, "norm")]
+    i64 = ("pair_off", "counts")
+    for t, name in named:                       # layout and type first: refused the same way with or without a GPU
+        if isinstance(t, torch.Tensor) and not t.is_contiguous():
+            raise RuntimeError("epipolar_score_by_pair: %s must be contiguous" % name)
+        if isinstance(t, torch.Tensor) and t.dtype != (torch.int64 if name in i64 else torch.float32):
+            raise RuntimeError("epipolar_score_by_pair: %s must be %s, got %s" % (name, "int64" if name in i64 else "float32", t.dtype))
+    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
+        raise RuntimeError("epipolar_score_by_pair: give either pair_off, or stride and counts")
+    if min_conf is not None and conf is None:
+        raise RuntimeError("epipolar_score_by_pair: min_conf needs conf")
+    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
+    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
+        raise RuntimeError("epipolar_score_by_pair: matches_l / matches_r must be [cap,2]")
+    ml, mr = ml.reshape(-1, 2), mr.reshape(-1, 2)
+    cap = int(ml.shape[0])
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
+        raise RuntimeError("epipolar_score_by_pair: models must be [pairs,H,3,3]")
+    H = int(models.shape[1])
+    if pair_off is not None:
+        seg = _dev(pair_off, "pair_off", torch.int64)
+        if seg.dim() != 1:
+            raise RuntimeError("epipolar_score_by_pair: pair_off must be an int64 vector")
+        pairs = seg.numel() - 1 if pairs is None else int(pairs)
+        if pairs < 1 or seg.numel() < pairs + 1:
+            raise RuntimeError("epipolar_score_by_pair: pair_off holds %d entries, %d pairs need %d" % (seg.numel(), pairs, pairs + 1))
+        stride = 0
+    else:
+        seg = _dev(counts, "counts", torch.int64).reshape(-1)
+        pairs = seg.numel() if pairs is None else int(pairs)
+        stride = int(stride)
+        if pairs < 1 or seg.numel() != pairs:
+            raise RuntimeError("epipolar_score_by_pair: counts must hold one int64 per pair")
+        if stride < 1 or pairs * stride > cap:
+            raise RuntimeError("epipolar_score_by_pair: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (stride, cap))
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("epipolar_score_by_pair: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % pairs)
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("epipolar_score_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("epipolar_score_by_pair: conf must be [cap]")
+    if norm is not None:
+        norm = _dev(norm, "norm")
+        if tuple(norm.shape) != (pairs, 8):
+            raise RuntimeError("epipolar_score_by_pair: norm must be [pairs,8]")
+    dev = ml.device
+    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
+            ("inlier", torch.uint8, (cap,))]
+    if moments:
+        want.append(("moments", torch.float64, (pairs, 9, 9)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
+    if len(out) != len(want):
+        raise RuntimeError("epipolar_score_by_pair: out must be (%s)" % ", ".join(n for n, _, _ in want))
+    for t, (name, dt, shape) in zip(out, want):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("epipolar_score_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    nws = _L().pats_epipolar_workspace_bytes(pairs, H, cap)
+    ws = _workspace(nws, dev) if nws else None
+    inl = out[3]
+    if cap == 0:                                # empty tensors have no address; the call is valid and touches none of these
+        ml = mr = torch.empty((2,), dtype=torch.float32, device=dev)
+        inl = torch.empty((8,), dtype=torch.uint8, device=dev)
+        conf = None if conf is None else ml
+    _check(_L().pats_epipolar_score_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(conf), _ptr(seg) if pair_off is not None else None, stride,
+                                                _ptr(seg) if pair_off is None else None, pairs, cap, _ptr(models), H, _ptr(thr),
+                                                _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
+                                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
+                                                _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream()), "epipolar_score_by_pair")
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------------
 # ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
 # ------------------------------------------------------------------------------------------------
