@@ -742,8 +742,9 @@ int pats_topk_by_pair_f32(const float* matches_l, const float* matches_r, const 
 /* ------------------------------------------------------------------------------------------
  * Per-pair model verification (ABI 8, symbols added): H candidate epipolar models per pair tested against every match of the
  * pair, the model with the most inliers, its inlier mask and - on request - the moment matrix of its inliers.  The O(H M) step
- * of a hypothesise-and-verify search on the hand-over (or on a per-pair top-K of it), on the device, no host read; generating the
- * hypotheses and everything after the mask (cheirality, pose) stay with the caller.
+ * of a hypothesise-and-verify search on the hand-over (or on a per-pair top-K of it), on the device, no host read; everything
+ * after the mask (cheirality, pose) stays with the caller, and the hypotheses are the caller's own or those of
+ * pats_epipolar_hypotheses_by_pair_f32 below.
  * Inputs
  *   matches_l, matches_r [cap,2] float32, the stored (c0, c1) of the hand-over taken as they lie; conf [cap] float32 (optional)
  *   the segment of pair p, in exactly ONE of two forms (both or neither: refused)
@@ -792,6 +793,57 @@ int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches
                                     int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
                                     int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
                                     void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair hypotheses (ABI 8, symbols added): the H candidate models pats_epipolar_score_by_pair_f32 tests, generated on the
+ * device - for every pair p and every h in 0 .. H-1 eight distinct matches of the pair are drawn and the unit null vector of their
+ * 8x9 epipolar constraint matrix (the 8-point algorithm's linear step) is written as a row-major 3x3 model.  One launch, no host
+ * read, deterministic: the draws come from a counter-based generator that a host reproduces exactly.  Not here: 5- and 7-point
+ * minimal solvers, the rank-2 / essential projection of a hypothesis, cheirality and pose, local optimisation, adaptive termination.
+ * Inputs
+ *   matches_l, matches_r [cap,2] float32 and the segment of pair p - ragged (pair_off) or strided (stride, counts_in), exactly ONE
+ *              of the two forms (both or neither: refused) - as for pats_epipolar_score_by_pair_f32, with the same clamping:
+ *              ragged   lo = pair_off[p], hi = pair_off[p + 1], both clamped to [0, cap] on the device, hi <= lo is an empty pair
+ *              strided  the segment starts at p * stride and holds min(max(counts_in[p], 0), stride) rows; cap >= pairs * stride
+ *              n = the pair's count, lo = its first row
+ *   norm [pairs,8] float32 (optional): x = ((p0 - c0) * s0, (p1 - c1) * s1, 1), the verification's rule - in float32 one subtract,
+ *              then one multiply, never contracted.  Without norm x = (p0, p1, 1)
+ *   pair_seed [pairs] int64, on the device; progressive: 0 or 1; 1 <= H <= pats_epipolar_max_h()
+ * The pool of hypothesis h: m_h = n for progressive == 0, otherwise m_h = max(8, (n (h + 1) + H - 1) / H) in int64 arithmetic - on a
+ * list sorted by confidence (a per-pair top-K) the early hypotheses draw from the most confident matches, the last one from all.
+ * The sampler - all arithmetic uint32, wrapping:
+ *   mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   s_lo, s_hi = the low and the high 32 bits of pair_seed[p];  k = mix(mix(mix(s_lo) ^ s_hi) + h)
+ *   u_t = mix(k + 0x9e3779b9 * (t + 1)),  j_t = (uint64(u_t) * (m_h - t)) >> 32          for t = 0 .. 7
+ *   draw t is the j_t-th index (from 0) of 0 .. m_h - 1 that no earlier draw took - equivalently: walk the earlier draws in ascending
+ *   order and add 1 to j for each one that is <= j.  sample_idx[p,h,t] is that position inside the pair's list, in draw order.
+ * The eight indices are distinct and < m_h; there is no rejection loop.
+ * The model: A [8,9] has row t = vec(x_r x_l^T) of draw t - q[3i + j] = x_r[i] x_l[j], the q of `moments` above.  models[p,h] is a
+ * float32 vector e with A e = 0 and Frobenius norm 1, its sign such that the component of largest magnitude is positive (the lowest
+ * index among equals, judged on the values written).  No component is pinned: a null vector with e[8] = 0 (a sideways translation)
+ * is found like any other.
+ * The ZERO model - nine exact zeros, the padding the verification ignores - is written
+ *   for every h of a pair with n < 8; sample_idx is then -1 for every h and t
+ *   for a sample one of whose 32 coordinates is not finite after norm; sample_idx is still written
+ *   for a sample whose solve does not end finite (coordinates whose squares leave the float32 range)
+ * A rank-deficient sample (duplicated matches, ...) gives the zero model or a finite unit vector of the null space, never a NaN or
+ * an infinity.
+ * Accuracy: the solve is float32.  The contract is a backward error, not an algorithm: with the written e promoted to float64 and
+ * A formed exactly from the float32 x,  |A e|_2 <= B eps32 |A|_F  and  | |e| - 1 | <= 1e-5  for every nonzero model; the tests hold B
+ * to 8 times what LAPACK's float32 SVD reaches on the same samples (docs/parity.md has the measured values).
+ * Outputs - every call defines every byte of both
+ *   models [pairs,H,3,3] float32;  sample_idx [pairs,H,8] int32 (optional: null skips it)
+ * cap == 0 is a valid call (every model zero; the match pointers must still be non-null).  Refused before any launch
+ * (pats_last_error names the argument): a null matches_l / matches_r / pair_seed / models; matches_l / matches_r off 8 bytes (read
+ * as float2), models / norm / sample_idx off 4, pair_off / counts_in / pair_seed off 8; both segment forms or neither; pairs < 1;
+ * H < 1 or H > max_h; cap < 0 or cap >= 2^31 - 1; in the strided form stride < 1 or pairs * stride > cap; progressive not 0 or 1;
+ * a grid of 2^31 workgroups or more (pairs * ceil(H / 64)); a workspace smaller than pats_epipolar_hypotheses_workspace_bytes
+ * (0 today: a hypothesis lives in its thread's registers; workspace may then be null). */
+size_t pats_epipolar_hypotheses_workspace_bytes(int64_t pairs, int64_t H);
+int pats_epipolar_hypotheses_by_pair_f32(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                         const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
+                                         const float* norm, int progressive, float* models, int32_t* sample_idx, void* workspace,
+                                         size_t workspace_bytes, pats_stream_t stream);
 
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the

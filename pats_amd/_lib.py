@@ -234,6 +234,10 @@ SIGNATURES = {
     "pats_epipolar_score_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
                                                 c_void_p, c_void_p, c_int, c_f, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_size, c_void_p]),
+    # per-pair 8-point hypotheses for that verification (csrc/hypotheses.hip)
+    "pats_epipolar_hypotheses_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_epipolar_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
+                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

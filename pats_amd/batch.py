@@ -442,6 +442,55 @@ def split_topk_by_pair(out, cap):
     return per_caller
 
 
+def hypothesize_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
+    """Device side, after the matching: H 8-point hypotheses per pair (ops.epipolar_hypotheses_by_pair: one launch, no host read) -
+    the `models` of verify_by_pair.  on="topk": drawn from the rows of a prior topk_by_pair result (strided form); on="all": from
+    the regrouped full lists (regroups first if the result is not grouped yet, as verify_by_pair does).  progressive (default: on ==
+    "topk"): hypothesis h draws from the first max(8, ceil(n (h + 1) / H)) matches of the pair's list, the most confident ones of a
+    top-K.  seed: a Python int; pair i of the CALLER's order gets pair_seed = seed + i (int64, wrapping), built on the device once
+    per seed and kept in the result - a pair's hypotheses do not depend on its slot in a mixed pack.  norm [pairs,8] or None, in the
+    caller's order (permuted to slot order on the device, as verify_by_pair does).
+    Returns models [pairs,H,3,3] float32 - or (models, sample_idx [pairs,H,8] int32) with samples=True - in the CALLER's order: they
+    go straight into verify_by_pair(out, cap, models, thr, norm=norm, on=...).  Adds `hypotheses` (what is returned) to the result;
+    the matches, the regrouped lists and a top-K of the same step are not touched."""
+    if on not in ("all", "topk"):
+        raise ValueError("hypothesize_by_pair: on must be \"all\" or \"topk\", got %r" % (on,))
+    if on == "topk" and "topk" not in out:
+        raise ValueError("hypothesize_by_pair: on=\"topk\" needs a topk_by_pair result")
+    if progressive is None:
+        progressive = on == "topk"
+    dev = out["matches_l"].device
+    seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)              # the int64 the bits of `seed` spell
+    mixed = "caller_of" in out
+    if mixed and "caller_of_dev" not in out:                              # slot s holds the caller's pair caller_of[s]
+        out["caller_of_dev"] = torch.tensor(out["caller_of"], dtype=torch.int64, device=dev)
+    if out.get("pair_seed", (None,))[0] != seed:
+        ids = out["caller_of_dev"] if mixed else torch.arange(cap.pairs, dtype=torch.int64, device=dev)
+        out["pair_seed"] = (seed, ids + seed)                             # slot order
+    pair_seed = out["pair_seed"][1]
+    if mixed and norm is not None:
+        norm = norm.index_select(0, out["caller_of_dev"])
+    if on == "topk":
+        tl, tr, _, _, tn = out["topk"]
+        hyp = ops.epipolar_hypotheses_by_pair(tl, tr, H, pair_seed, stride=int(tl.shape[1]), counts=tn, norm=norm, progressive=progressive,
+                                              return_samples=samples)
+    else:
+        if "by_pair" not in out:
+            group_by_pair(out, cap)
+        bp = out["by_pair"]
+        hyp = ops.epipolar_hypotheses_by_pair(bp[0], bp[1], H, pair_seed, pair_off=out["summary"], norm=norm, progressive=progressive,
+                                              return_samples=samples, pairs=cap.pairs)
+    if mixed:                                                             # slots back to the caller's order
+        if "slot_of_dev" not in out:
+            slot_of = [0] * cap.pairs
+            for s_, i in enumerate(out["caller_of"]):
+                slot_of[i] = s_
+            out["slot_of_dev"] = torch.tensor(slot_of, dtype=torch.int64, device=dev)
+        hyp = tuple(t.index_select(0, out["slot_of_dev"]) for t in hyp) if samples else hyp.index_select(0, out["slot_of_dev"])
+    out["hypotheses"] = hyp
+    return hyp
+
+
 def _overflow_check(o, cap):
     M, P, status = o[cap.pairs + 1:cap.pairs + 4]
     if status & 1:

@@ -17,6 +17,7 @@
 // A match that does not participate (outside the segment, gated by min_conf, a non-finite coordinate) carries a NaN x_l: every
 // comparison with it is false, the inner loop needs no mask.
 #include "common.hpp"
+#include "epipolar.hpp"
 
 namespace pats {
 
@@ -31,34 +32,6 @@ constexpr int EPI_MASK_WAVES = EPI_MASK_THREADS / WAVE;
 constexpr int EPI_MOM = 45;                            // upper triangle of the 9x9 moment matrix
 
 typedef float e2f __attribute__((ext_vector_type(2)));
-
-// the segment of pair p: ragged (pair_off) or strided (stride, counts_in); always inside [0, cap]
-__device__ __forceinline__ void epi_segment(const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride,
-                                            int64_t cap, int64_t p, int64_t& lo, uint32_t& n) {
-    if (counts_in) {                                    // pairs * stride <= cap (checked on the host)
-        int64_t c = counts_in[p];
-        c = c < 0 ? 0 : (c > stride ? stride : c);
-        lo = p * stride;
-        n = (uint32_t)c;
-    } else {
-        int64_t a = pair_off[p], b = pair_off[p + 1];
-        a = a < 0 ? 0 : (a > cap ? cap : a);
-        b = b < 0 ? 0 : (b > cap ? cap : b);
-        lo = a;
-        n = b > a ? (uint32_t)(b - a) : 0u;             // cap < 2^31 (checked on the host)
-    }
-}
-
-struct EpiNorm { float c0l, c1l, s0l, s1l, c0r, c1r, s0r, s1r; };
-
-__device__ __forceinline__ EpiNorm epi_norm(const float* __restrict__ norm, int64_t p) {
-    EpiNorm m{0.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f, 1.0f, 1.0f};
-    if (norm) {
-        const float* q = norm + p * 8;
-        m = EpiNorm{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
-    }
-    return m;
-}
 
 // match i of the segment as (x_l, x_r); l0 = NaN unless the match participates
 __device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const float2* __restrict__ mr, const float* __restrict__ conf,

@@ -1709,6 +1709,84 @@ def epipolar_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, str
     return tuple(out)
 
 
+def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
+                                return_samples=False, out=None, pairs=None):
+    """H 8-point hypotheses per pair, ON THE DEVICE, one launch, no host read (pats_epipolar_hypotheses_by_pair_f32;
+    include/pats_amd.h holds the definition): for every pair and every h eight distinct matches of the pair are drawn by a
+    counter-based generator and the unit null vector of their 8x9 constraint matrix is written as a row-major 3x3 model - the input
+    of epipolar_score_by_pair.  matches_l / matches_r [cap,2] float32 (also [pairs,K,2]: top-K outputs are taken as the flat lists
+    they are); the pairs' segments in exactly one of two forms, as for epipolar_score_by_pair: pair_off (int64 [pairs + 1] - or,
+    with pairs= given, a longer buffer that starts with the offsets) or stride + counts (int64 [pairs]).  seed: int64 GPU tensor
+    [pairs], one generator seed per pair.  norm [pairs,8]: the verification's normalisation.  progressive: hypothesis h draws from
+    the first max(8, ceil(n (h + 1) / H)) matches of the pair's list (a confidence-sorted top-K) instead of all n.
+    Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 8 matches and for a sample with a non-finite
+    coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,8] int32: the draws as positions inside the pair's
+    list, -1 for a pair with fewer than 8 matches).  out: the destination(s), a tensor or a tuple."""
+    named = [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")]
+    i64 = ("pair_off", "counts", "seed")
+    for t, name in named:                       # layout and type first: refused the same way with or without a GPU
+        if isinstance(t, torch.Tensor) and not t.is_contiguous():
+            raise RuntimeError("epipolar_hypotheses_by_pair: %s must be contiguous" % name)
+        if isinstance(t, torch.Tensor) and t.dtype != (torch.int64 if name in i64 else torch.float32):
+            raise RuntimeError("epipolar_hypotheses_by_pair: %s must be %s, got %s" % (name, "int64" if name in i64 else "float32", t.dtype))
+    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
+        raise RuntimeError("epipolar_hypotheses_by_pair: give either pair_off, or stride and counts")
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("epipolar_hypotheses_by_pair: seed must be an int64 GPU tensor [pairs]")
+    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
+    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
+        raise RuntimeError("epipolar_hypotheses_by_pair: matches_l / matches_r must be [cap,2]")
+    ml, mr = ml.reshape(-1, 2), mr.reshape(-1, 2)
+    cap, H = int(ml.shape[0]), int(H)
+    seed = _dev(seed, "seed", torch.int64).reshape(-1)
+    if pair_off is not None:
+        seg = _dev(pair_off, "pair_off", torch.int64)
+        if seg.dim() != 1:
+            raise RuntimeError("epipolar_hypotheses_by_pair: pair_off must be an int64 vector")
+        pairs = seg.numel() - 1 if pairs is None else int(pairs)
+        if pairs < 1 or seg.numel() < pairs + 1:
+            raise RuntimeError("epipolar_hypotheses_by_pair: pair_off holds %d entries, %d pairs need %d" % (seg.numel(), pairs, pairs + 1))
+        stride = 0
+    else:
+        seg = _dev(counts, "counts", torch.int64).reshape(-1)
+        pairs = seg.numel() if pairs is None else int(pairs)
+        stride = int(stride)
+        if pairs < 1 or seg.numel() != pairs:
+            raise RuntimeError("epipolar_hypotheses_by_pair: counts must hold one int64 per pair")
+        if stride < 1 or pairs * stride > cap:
+            raise RuntimeError("epipolar_hypotheses_by_pair: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (stride, cap))
+    if seed.numel() != pairs:
+        raise RuntimeError("epipolar_hypotheses_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("epipolar_hypotheses_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    if norm is not None:
+        norm = _dev(norm, "norm")
+        if tuple(norm.shape) != (pairs, 8):
+            raise RuntimeError("epipolar_hypotheses_by_pair: norm must be [pairs,8]")
+    dev = ml.device
+    want = [("models", torch.float32, (pairs, H, 3, 3))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, 8)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
+    elif isinstance(out, torch.Tensor):
+        out = (out,)
+    if len(out) != len(want):
+        raise RuntimeError("epipolar_hypotheses_by_pair: out must be (%s)" % ", ".join(n for n, _, _ in want))
+    for t, (name, dt, shape) in zip(out, want):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("epipolar_hypotheses_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    nws = _L().pats_epipolar_hypotheses_workspace_bytes(pairs, H)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:                                # empty tensors have no address; the call is valid and reads neither
+        ml = mr = torch.empty((2,), dtype=torch.float32, device=dev)
+    _check(_L().pats_epipolar_hypotheses_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(seg) if pair_off is not None else None, stride,
+                                                     _ptr(seg) if pair_off is None else None, pairs, cap, H, _ptr(seed), _ptr(norm),
+                                                     1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
+                                                     _ptr(ws), nws, _stream()), "epipolar_hypotheses_by_pair")
+    return tuple(out) if return_samples else out[0]
+
+
 # ------------------------------------------------------------------------------------------------
 # ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
 # ------------------------------------------------------------------------------------------------
