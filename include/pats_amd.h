@@ -743,8 +743,8 @@ int pats_topk_by_pair_f32(const float* matches_l, const float* matches_r, const 
  * Per-pair model verification (ABI 8, symbols added): H candidate epipolar models per pair tested against every match of the
  * pair, the model with the most inliers, its inlier mask and - on request - the moment matrix of its inliers.  The O(H M) step
  * of a hypothesise-and-verify search on the hand-over (or on a per-pair top-K of it), on the device, no host read; everything
- * after the mask (cheirality, pose) stays with the caller, and the hypotheses are the caller's own or those of
- * pats_epipolar_hypotheses_by_pair_f32 below.
+ * after the mask (cheirality, pose) is pats_epipolar_pose_by_pair_f64 below, and the hypotheses are the caller's own or those of
+ * pats_epipolar_hypotheses_by_pair_f32.
  * Inputs
  *   matches_l, matches_r [cap,2] float32, the stored (c0, c1) of the hand-over taken as they lie; conf [cap] float32 (optional)
  *   the segment of pair p, in exactly ONE of two forms (both or neither: refused)
@@ -844,6 +844,73 @@ int pats_epipolar_hypotheses_by_pair_f32(const float* matches_l, const float* ma
                                          const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
                                          const float* norm, int progressive, float* models, int32_t* sample_idx, void* workspace,
                                          size_t workspace_bytes, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair relative pose (ABI 8, symbols added): from the inliers pats_epipolar_score_by_pair_f32 marked to (R, t) per pair - the
+ * least-squares refit of the winner's moments, its projection onto the essential matrices, the four decompositions and the
+ * cheirality vote that picks one.  What findEssentialMat's last step and recoverPose do after a hypothesise-and-verify search, on
+ * the device, no host read.  The returned E, cast to float32, is a valid unit model: fed back as an H = 1 model it gives the local-
+ * optimisation round (pose -> verify -> moments -> pose).
+ * What it is not: there is no distance threshold on the triangulated points (the reference passes 1e9 to recoverPose: effectively
+ * none), no 5-point solver, no pose-error metric, and nothing in pipeline.forward_* or the drop-in calls it.
+ * Inputs
+ *   matches_l, matches_r [cap,2] float32, the segment of pair p - ragged (pair_off) or strided (stride, counts_in), exactly ONE of
+ *              the two forms - and norm [pairs,8] float32 (optional): as for pats_epipolar_score_by_pair_f32, with the same clamping
+ *   inlier [cap] uint8        the mask the verification wrote beside those lists
+ *   best_count [pairs] int64  the verification's; a pair with best_count < 8 has no pose
+ *   the refit's source: moments [pairs,9,9] float64 (the verification's; the upper triangle is read), or - when moments is null -
+ *              models [pairs,H,3,3] float32 with best [pairs] int32 (clamped to 0 .. H-1).  With moments given, models and best
+ *              are not read
+ *   swapped    0 or 1, see below
+ * Definition, per pair
+ *   x           the verification's point, formed exactly as there (float32: one subtract, one multiply; (p0, p1, 1) without norm)
+ *   used        inlier[i] != 0 and the four coordinates of x finite
+ *   e_refit     [pairs,9] float64 (optional output).  With moments: a unit eigenvector of moments[p] for its smallest eigenvalue
+ *               (float64 throughout; the lowest index among equal eigenvalues, either sign).  Without: models[p, best[p]] promoted
+ *               to float64.  Nine zeros for a pair without a pose because of best_count or a non-finite value
+ *   E           [pairs,3,3] float64: the essential matrix nearest to e_refit, E = U diag(s, s, 0) V^T from e_refit =
+ *               U diag(s1, s2, s3) V^T, rescaled to Frobenius norm 1 (s = 1/sqrt 2).  The component of largest magnitude is positive
+ *               (the lowest index among equals): the hypotheses' convention.  Cast to float32 it is a valid model for
+ *               pats_epipolar_score_by_pair_f32
+ *   candidates  det U, det V > 0;  W = [[0,-1,0],[1,0,0],[0,0,1]];  R1 = U W V^T,  R2 = U W^T V^T,  u = U[:,2]
+ *               order: (R1, u), (R2, u), (R1, -u), (R2, -u).  (The SVD leaves U and V free up to a joint rotation of the first two
+ *               columns and joint signs; the SET of four is unique, which of its members is R1 is not.)
+ *               convention: x_r ~ R x_l + t, so E ~ [t]x R - OpenCV's
+ *   in front    for a used match and candidate (R, t), with R and t rounded to float32 and float32 arithmetic:
+ *                 a = R x_l,  b = x_r,  c = a x b
+ *                 in front  iff  c.c > 0  and  c.(b x t) > 0  and  c.(a x t) > 0
+ *               - the signs of the two depths of the least-squares intersection of the rays, without a division:
+ *                 lambda_l = c.(b x t) / c.c,   lambda_r = c.(a x t) / c.c
+ *               A verdict whose dot product lies within a few float32 roundings of zero may differ from a float64 evaluation
+ *               (docs/parity.md quantifies the band); the counts, the choice and the mask of one call always agree: one device
+ *               function serves all three
+ *   no pose     best_count[p] < 8, a non-finite moment or e_refit, or s2 == 0 (e_refit of rank below 2):
+ *               E = 0, R = I, t = 0, all counts 0, choice 0, front 0.  Never a NaN or an infinity in any output
+ *   swapped     with 1 the points are in the hand-over's (c0, c1) = (y, x) order.  Everything is computed in that frame and written
+ *               in the reference's:  R_out = P R P,  t_out = P t,  E_out = P E P (sign rule applied after the permutation),
+ *               P = [[0,1,0],[1,0,0],[0,0,1]] - X' = P X turns X_r = R X_l + t into X_r' = (P R P) X_l' + P t with the depths
+ *               unchanged.  front_counts, choice and front do not depend on it; e_refit stays in the input frame
+ * Outputs - every call defines every byte of every output
+ *   E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64: the chosen candidate, |t| = 1
+ *   front_counts [pairs,4] int32   used matches in front, per candidate
+ *   choice [pairs] int32           the lowest candidate index with the largest count;  front_count [pairs] int64 that count
+ *   front [cap] uint8 (optional)   1 where a used match is in front under the chosen candidate, 0 everywhere else - rows outside
+ *                                  every segment and the slack of strided rows included.  Its sum over a segment is front_count
+ *   e_refit [pairs,9] float64 (optional)
+ * cap == 0 is a valid call that defines every per-pair output (the match pointers and inlier must still be non-null).  Refused
+ * before any launch (pats_last_error names the argument): a null matches_l / matches_r / inlier / best_count / E / R / t /
+ * front_counts / choice / front_count; matches_l / matches_r off 8 bytes (read as float2), moments / E / R / t / e_refit / pair_off /
+ * counts_in / best_count / front_count off 8, models / best / norm / front_counts / choice off 4; both segment forms or neither;
+ * pairs < 1; cap < 0 or cap >= 2^31 - 1; in the strided form stride < 1 or pairs * stride > cap; swapped not 0 or 1; neither moments
+ * nor (models and best); with models given H < 1 or H > max_h; a workspace smaller than
+ * pats_epipolar_pose_workspace_bytes (0 today: the solve lives in LDS and registers; workspace may then be null). */
+size_t pats_epipolar_pose_workspace_bytes(int64_t pairs, int64_t cap);
+int pats_epipolar_pose_by_pair_f64(const float* matches_l, const float* matches_r, const uint8_t* inlier, const int64_t* pair_off,
+                                   int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const int64_t* best_count,
+                                   const double* moments, const float* models, int64_t H, const int32_t* best, const float* norm,
+                                   int swapped, double* E, double* R, double* t, int32_t* front_counts, int32_t* choice,
+                                   int64_t* front_count, uint8_t* front, double* e_refit, void* workspace, size_t workspace_bytes,
+                                   pats_stream_t stream);
 
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the

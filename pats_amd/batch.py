@@ -534,6 +534,7 @@ def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", mo
         ver = ops.epipolar_score_by_pair(bp[0], bp[1], models, thr, pair_off=out["summary"], conf=bp[3] if min_conf is not None else None,
                                          min_conf=min_conf, norm=norm, moments=moments, pairs=cap.pairs)
     out["verified"], out["verified_on"] = ver, on
+    out["verified_models"] = models                   # slot order: pose_by_pair's source when no moments were asked for
     return ver
 
 
@@ -567,3 +568,51 @@ def split_verified_by_pair(out, cap):
     for s_, i in enumerate(out["caller_of"]):
         per_caller[i] = per_slot[s_]
     return per_caller
+
+
+def pose_by_pair(out, cap, norm=None, swapped=False, front=False):
+    """Device side, after verify_by_pair: each pair's relative pose from its verified inliers (ops.epipolar_pose_by_pair: no host
+    read) - the refit of `verified`'s moments if the verification produced them, otherwise its winning model; the nearest
+    essential matrix, its four decompositions and the cheirality vote over the lists that verification scored ("all" or "topk").
+    norm [pairs,8] or None in the CALLER's order - pass what verify_by_pair was given.  swapped: the lists are in the hand-over's
+    (y, x) order and the pose is wanted in the reference's (x, y) frame.
+    Returns (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64, front_counts [pairs,4] int32,
+    choice [pairs] int32) in the CALLER's order - with front=True followed by front (uint8, aligned with the scored lists like
+    `verified`'s inlier mask: slot order) - and stores them as `pose`.  E.float() goes straight back into verify_by_pair as an
+    H = 1 model: the local-optimisation round."""
+    if "verified" not in out:
+        raise ValueError("pose_by_pair: run verify_by_pair first")
+    ver, on = out["verified"], out["verified_on"]
+    best, best_count, inl = ver[1:4]
+    mixed = "caller_of" in out
+    if mixed and norm is not None:
+        norm = norm.index_select(0, out["caller_of_dev"])                 # verify_by_pair made the index
+    src = {"moments": ver[4]} if len(ver) > 4 else {"models": out["verified_models"], "best": best}
+    if on == "topk":
+        tl, tr, _, _, tn = out["topk"]
+        res = ops.epipolar_pose_by_pair(tl, tr, inl, best_count, stride=int(tl.shape[1]), counts=tn, norm=norm, swapped=swapped,
+                                        return_front=front, **src)
+    else:
+        bp = out["by_pair"]
+        res = ops.epipolar_pose_by_pair(bp[0], bp[1], inl, best_count, pair_off=out["summary"], norm=norm, swapped=swapped,
+                                        return_front=front, pairs=cap.pairs, **src)
+    if mixed:                                                             # slots back to the caller's order
+        if "slot_of_dev" not in out:
+            slot_of = [0] * cap.pairs
+            for s_, i in enumerate(out["caller_of"]):
+                slot_of[i] = s_
+            out["slot_of_dev"] = torch.tensor(slot_of, dtype=torch.int64, device=inl.device)
+        res = tuple(t.index_select(0, out["slot_of_dev"]) for t in res[:6]) + tuple(res[6:])
+    out["pose"] = res
+    return res
+
+
+def split_pose_by_pair(out, cap):
+    """Host side, AFTER the step: per-pair (R [3,3], t [3], E [3,3], front_count) of a pose_by_pair result, views of the device
+    tensors (their values are not read here), in the caller's order.  Raises on the capacity overflows split_verified_by_pair
+    raises on, after the same device-to-host copies and no further one."""
+    if "pose" not in out:
+        raise ValueError("split_pose_by_pair: run pose_by_pair first")
+    split_verified_by_pair(out, cap)                  # the overflow checks, with the copies that function makes
+    E, R, t, front_count = out["pose"][:4]
+    return [(R[i], t[i], E[i], front_count[i]) for i in range(cap.pairs)]

@@ -1,5 +1,5 @@
-// What the per-pair epipolar stages share (epipolar.hip: verification; hypotheses.hip: the 8-point hypotheses): how a pair's segment
-// of the match lists and its normalisation are read.  include/pats_amd.h states both.
+// What the per-pair epipolar stages share (epipolar.hip: verification; hypotheses.hip: the 8-point hypotheses; pose.hip: the pose):
+// how a pair's segment of the match lists, its normalisation and a match's point are read.  include/pats_amd.h states both.
 #pragma once
 #include "common.hpp"
 
@@ -31,6 +31,24 @@ __device__ __forceinline__ EpiNorm epi_norm(const float* __restrict__ norm, int6
         m = EpiNorm{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]};
     }
     return m;
+}
+
+// match i of the segment as (x_l, x_r); l0 = NaN unless the match participates
+__device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const float2* __restrict__ mr, const float* __restrict__ conf,
+                                         uint32_t i, uint32_t n, bool has_norm, const EpiNorm& nm, bool gate, float min_conf,
+                                         float& l0, float& l1, float& r0, float& r1) {
+    l0 = __builtin_nanf("");
+    l1 = r0 = r1 = 0.0f;
+    if (i >= n) return;
+    float2 a = ml[i], b = mr[i];
+    if (has_norm) {                                     // one subtract, one multiply (no contraction: -ffp-contract=off)
+        a.x = (a.x - nm.c0l) * nm.s0l; a.y = (a.y - nm.c1l) * nm.s1l;
+        b.x = (b.x - nm.c0r) * nm.s0r; b.y = (b.y - nm.c1r) * nm.s1r;
+    }
+    bool ok = __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(b.x) && __builtin_isfinite(b.y);
+    if (gate) ok = ok && conf[i] >= min_conf;           // false for a NaN confidence
+    l1 = a.y; r0 = b.x; r1 = b.y;
+    if (ok) l0 = a.x;
 }
 
 }  // namespace pats

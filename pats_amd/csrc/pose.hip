@@ -1,0 +1,441 @@
+// Per-pair relative pose from the verified inliers: for every pair of a batch the least-squares refit of the winner's moments (the
+// eigenvector of the 9x9 moment matrix for its smallest eigenvalue - or the winning model itself), its projection onto the essential
+// matrices, the four (R, t) decompositions and the cheirality vote of the pair's inliers that picks one of them.  One launch (after
+// the fill of the optional mask), no host read.  include/pats_amd.h states the definition; docs/kernels.md 4.9 the design.
+//
+//   one workgroup per pair, POSE_THREADS = 256 threads, decided by the sizes alone
+//   solve   float64.  The 9x9 matrix A and the accumulated rotations V live in LDS; wave 0 runs a cyclic Jacobi in the round-robin
+//           order: a sweep is nine rounds of four disjoint rotations (p, q) = ((r + i) % 9, (r - i) % 9), i = 1 .. 4 - sixteen
+//           lanes per rotation, lane k of a group updates row / column entry k.  A rotation whose off-diagonal entry no longer
+//           changes either diagonal entry when added to it is replaced by setting that entry to zero; a sweep without a rotation
+//           ends the loop, POSE_SWEEPS caps it.  Thread 0 then holds everything else in registers, all indices static: the
+//           eigenvector, G^T G of it as a 3x3 G, a 3x3 Jacobi for the right singular vectors, u_i = G v_i (Gram-Schmidt), u_3 =
+//           u_1 x u_2, v_3 = v_1 x v_2 (det U = det V = +1 by construction), E, R1, R2, u.  They go to LDS in float64 and float32.
+//   vote    the workgroup walks the segment with epi_load; a match that is not used carries a NaN x_l.  pose_front4 gives the four
+//           verdicts of a match as bits (R1 and R2 share everything up to the two signs); ballots + popcounts per wave, the waves
+//           added in LDS by thread 0 (integer adds: no order), which picks the candidate and writes the per-pair outputs.
+//   mask    a second walk with the same device function writes the chosen candidate's bit: front.sum() == front_count exactly.
+#include "common.hpp"
+#include "epipolar.hpp"
+
+namespace pats {
+
+constexpr int POSE_THREADS = 256;
+constexpr int POSE_WAVES = POSE_THREADS / WAVE;
+constexpr int POSE_SWEEPS = 16;                        // cap of both Jacobi loops (a sweep without a rotation ends them: the 7th or 8th)
+constexpr int POSE_MIN_INLIERS = 8;
+
+// the rotation that annihilates apq: J = [[c, s], [-s, c]] on (p, q), B = J^T A J  (apq != 0)
+__device__ __forceinline__ void pose_cs(double app, double aqq, double apq, double& c, double& s) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (__builtin_fabs(theta) + __builtin_sqrt(theta * theta + 1.0));   // 0 for a huge theta
+    c = 1.0 / __builtin_sqrt(t * t + 1.0);
+    s = t * c;
+}
+
+// apq is too small to change either diagonal entry
+__device__ __forceinline__ bool pose_negligible(double app, double aqq, double g) {
+    return __builtin_fabs(app) + g == __builtin_fabs(app) && __builtin_fabs(aqq) + g == __builtin_fabs(aqq);
+}
+
+template <int P, int Q>
+__device__ __forceinline__ bool pose_rot3(double (&B)[3][3], double (&W)[3][3]) {
+    const double g = __builtin_fabs(B[P][Q]);
+    if (g == 0.0) return false;
+    if (pose_negligible(B[P][P], B[Q][Q], g)) {
+        B[P][Q] = B[Q][P] = 0.0;
+        return false;
+    }
+    double c, s;
+    pose_cs(B[P][P], B[Q][Q], B[P][Q], c, s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = B[k][P], y = B[k][Q];
+        B[k][P] = c * x - s * y; B[k][Q] = s * x + c * y;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = B[P][k], y = B[Q][k];
+        B[P][k] = c * x - s * y; B[Q][k] = s * x + c * y;
+    }
+    B[P][Q] = B[Q][P] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = W[k][P], y = W[k][Q];
+        W[k][P] = c * x - s * y; W[k][Q] = s * x + c * y;
+    }
+    return true;
+}
+
+// columns a and b of W and their eigenvalues exchanged if la < lb
+template <int A_, int B_>
+__device__ __forceinline__ void pose_order(double (&l)[3], double (&W)[3][3]) {
+    const bool sw = l[A_] < l[B_];
+    const double la = l[A_], lb = l[B_];
+    l[A_] = sw ? lb : la; l[B_] = sw ? la : lb;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = W[k][A_], y = W[k][B_];
+        W[k][A_] = sw ? y : x; W[k][B_] = sw ? x : y;
+    }
+}
+
+__device__ __forceinline__ void pose_cross(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// e (a 3x3 G, row-major) -> E = U diag(s, s, 0) V^T with |E|_F = 1, R1 = U W V^T, R2 = U W^T V^T, u = U[:,2]; false: no pose
+__device__ __forceinline__ bool pose_decompose(const double (&e)[9], double (&E)[9], double (&R1)[9], double (&R2)[9], double (&u3)[3]) {
+    double G[3][3], B[3][3], W[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { G[i][j] = e[3 * i + j]; W[i][j] = i == j ? 1.0 : 0.0; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[i][j] = G[0][i] * G[0][j] + G[1][i] * G[1][j] + G[2][i] * G[2][j];
+    for (int sweep = 0; sweep < POSE_SWEEPS; ++sweep) {
+        bool any = pose_rot3<0, 1>(B, W);
+        any = pose_rot3<0, 2>(B, W) || any;
+        any = pose_rot3<1, 2>(B, W) || any;
+        if (!any) break;
+    }
+    double l[3] = {B[0][0], B[1][1], B[2][2]};
+    pose_order<0, 1>(l, W);                             // descending: the columns of W become v_1, v_2, (v_3)
+    pose_order<1, 2>(l, W);
+    pose_order<0, 1>(l, W);
+    double v1[3], v2[3], v3[3], u1[3], u2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v1[k] = W[k][0]; v2[k] = W[k][1]; }
+    pose_cross(v1, v2, v3);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        u1[i] = G[i][0] * v1[0] + G[i][1] * v1[1] + G[i][2] * v1[2];
+        u2[i] = G[i][0] * v2[0] + G[i][1] * v2[1] + G[i][2] * v2[2];
+    }
+    const double s1 = __builtin_sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+    if (!(s1 > 0.0)) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u1[i] /= s1;
+    const double d = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u2[i] -= d * u1[i];
+    const double s2 = __builtin_sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+    if (!(s2 > 0.0)) return false;                      // rank below 2: no essential matrix is nearest
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u2[i] /= s2;
+    pose_cross(u1, u2, u3);
+    const double h = 0.70710678118654752440;            // 1 / sqrt 2
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double a = u1[i] * v1[j] + u2[i] * v2[j], b = u2[i] * v1[j] - u1[i] * v2[j], c = u3[i] * v3[j];
+            E[3 * i + j] = a * h;
+            R1[3 * i + j] = b + c;                      // U W V^T,  W = [[0,-1,0],[1,0,0],[0,0,1]]
+            R2[3 * i + j] = c - b;                      // U W^T V^T
+            ok = ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c);
+        }
+    return ok;
+}
+
+// THE cheirality test - the vote and the mask both call it.  Bit k: the match lies in front of both cameras under candidate k of
+// (R1, u), (R2, u), (R1, -u), (R2, -u).  A NaN l0 (a match that is not used) gives 0.
+__device__ __forceinline__ unsigned pose_front4(const float (&R)[2][9], const float (&u)[3], float l0, float l1, float r0, float r1) {
+    // b x t, b = (r0, r1, 1)
+    const float bt0 = __builtin_fmaf(r1, u[2], -u[1]), bt1 = __builtin_fmaf(-r0, u[2], u[0]), bt2 = __builtin_fmaf(r0, u[1], -(r1 * u[0]));
+    unsigned bits = 0u;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const float a0 = __builtin_fmaf(R[j][0], l0, __builtin_fmaf(R[j][1], l1, R[j][2]));
+        const float a1 = __builtin_fmaf(R[j][3], l0, __builtin_fmaf(R[j][4], l1, R[j][5]));
+        const float a2 = __builtin_fmaf(R[j][6], l0, __builtin_fmaf(R[j][7], l1, R[j][8]));
+        const float c0 = __builtin_fmaf(-a2, r1, a1), c1 = __builtin_fmaf(a2, r0, -a0), c2 = __builtin_fmaf(a0, r1, -(a1 * r0));   // a x b
+        const float at0 = __builtin_fmaf(a1, u[2], -(a2 * u[1])), at1 = __builtin_fmaf(a2, u[0], -(a0 * u[2])),
+                    at2 = __builtin_fmaf(a0, u[1], -(a1 * u[0]));                                                              // a x t
+        const float cc = __builtin_fmaf(c0, c0, __builtin_fmaf(c1, c1, c2 * c2));
+        const float dl = __builtin_fmaf(c0, bt0, __builtin_fmaf(c1, bt1, c2 * bt2));
+        const float dr = __builtin_fmaf(c0, at0, __builtin_fmaf(c1, at1, c2 * at2));
+        if (cc > 0.0f && dl > 0.0f && dr > 0.0f) bits |= 1u << j;
+        if (cc > 0.0f && dl < 0.0f && dr < 0.0f) bits |= 4u << j;      // -u: both signs turn
+    }
+    return bits;
+}
+
+__global__ void __launch_bounds__(POSE_THREADS)
+epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const uint8_t* __restrict__ inlier,
+                     const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
+                     const int64_t* __restrict__ best_count, const double* __restrict__ moments, const float* __restrict__ models, int H,
+                     const int32_t* __restrict__ best, const float* __restrict__ norm, int swapped, double* __restrict__ E_out,
+                     double* __restrict__ R_out, double* __restrict__ t_out, int32_t* __restrict__ front_counts,
+                     int32_t* __restrict__ choice_out, int64_t* __restrict__ front_count, uint8_t* __restrict__ front,
+                     double* __restrict__ e_refit) {
+    __shared__ double sA[9][9], sV[9][9];
+    __shared__ double sE[9], sR[2][9], sU[3];
+    __shared__ float sRf[2][9], sUf[3];
+    __shared__ int s_cnt[POSE_WAVES][4];
+    __shared__ int s_bad, s_rot, s_ok, s_choice;
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int64_t lo;
+    uint32_t n;
+    epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
+    const bool live = best_count[p] >= POSE_MIN_INLIERS;  // workgroup-uniform
+    if (tid == 0) { s_bad = 0; s_rot = 0; s_ok = 0; s_choice = 0; }
+    wg_barrier();
+
+    // ---- solve ------------------------------------------------------------------------------------------------------------------
+    if (live && moments) {                              // workgroup-uniform
+        if (tid < 81) {
+            const int i = tid / 9, j = tid - 9 * i;
+            const double v = moments[p * 81 + (i < j ? i * 9 + j : j * 9 + i)];    // the upper triangle: symmetric whatever is stored
+            sA[i][j] = v;
+            sV[i][j] = i == j ? 1.0 : 0.0;
+            if (!__builtin_isfinite(v)) s_bad = 1;      // the same value from every writer
+        }
+        wg_barrier();
+        const bool bad = s_bad != 0;
+        const int grp = tid >> 4, k = tid & 15;         // rotation grp of a round, entry k
+        const bool mine = tid < 64 && k < 9;
+        for (int sweep = 0; sweep < POSE_SWEEPS && !bad; ++sweep) {
+            for (int r = 0; r < 9; ++r) {
+                int pp = (r + grp + 1) % 9, qq = (r + 8 - grp) % 9;
+                if (pp > qq) { const int x_ = pp; pp = qq; qq = x_; }
+                double c = 1.0, s = 0.0, x = 0.0, y = 0.0, vx = 0.0, vy = 0.0;
+                bool rot = false, zero = false;
+                if (mine) {
+                    const double app = sA[pp][pp], aqq = sA[qq][qq], apq = sA[pp][qq];
+                    const double g = __builtin_fabs(apq);
+                    if (g != 0.0) {
+                        if (pose_negligible(app, aqq, g)) {
+                            zero = k == 0;
+                        } else {
+                            rot = true;
+                            pose_cs(app, aqq, apq, c, s);
+                        }
+                    }
+                    x = sA[k][pp]; y = sA[k][qq];
+                    vx = sV[k][pp]; vy = sV[k][qq];
+                }
+                wg_barrier();                           // every lane has read the round's entries
+                if (zero) { sA[pp][qq] = 0.0; sA[qq][pp] = 0.0; }       // no other lane touches the two in this round
+                if (rot) {                              // A <- A J, V <- V J: the columns p and q
+                    sA[k][pp] = c * x - s * y; sA[k][qq] = s * x + c * y;
+                    sV[k][pp] = c * vx - s * vy; sV[k][qq] = s * vx + c * vy;
+                    s_rot = 1;
+                }
+                wg_barrier();
+                if (rot) {                              // A <- J^T A: the rows p and q; the annihilated pair is set, not computed
+                    x = sA[pp][k]; y = sA[qq][k];
+                    sA[pp][k] = k == qq ? 0.0 : c * x - s * y;
+                    sA[qq][k] = k == pp ? 0.0 : s * x + c * y;
+                }
+                wg_barrier();
+            }
+            const bool again = s_rot != 0;
+            wg_barrier();
+            if (tid == 0) s_rot = 0;
+            if (!again) break;
+        }
+    }
+    if (tid == 0) {
+        double e[9];
+        bool ok = live && s_bad == 0;
+        if (ok && moments) {
+            int m = 0;
+            double lmin = sA[0][0];
+            for (int k = 1; k < 9; ++k) {               // the smallest eigenvalue, the lowest index among equals
+                const double l = sA[k][k];
+                if (l < lmin) { lmin = l; m = k; }
+            }
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { e[k] = sV[k][m]; s += e[k] * e[k]; }
+            const double inv = 1.0 / __builtin_sqrt(s);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) e[k] *= inv;
+        } else if (ok) {
+            int h = best[p];
+            h = h < 0 ? 0 : (h >= H ? H - 1 : h);
+            const float* m = models + (p * H + h) * 9;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) e[k] = (double)m[k];
+        }
+        if (ok) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) ok = ok && __builtin_isfinite(e[k]);
+        }
+        if (e_refit) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) e_refit[p * 9 + k] = ok ? e[k] : 0.0;
+        }
+        double E[9], R1[9], R2[9], u[3];
+        if (ok) ok = pose_decompose(e, E, R1, R2, u);
+        if (ok) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                sE[k] = E[k]; sR[0][k] = R1[k]; sR[1][k] = R2[k];
+                sRf[0][k] = (float)R1[k]; sRf[1][k] = (float)R2[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { sU[k] = u[k]; sUf[k] = (float)u[k]; }
+            s_ok = 1;
+        }
+    }
+    wg_barrier();
+    const bool ok = s_ok != 0;                          // workgroup-uniform
+
+    // ---- vote -------------------------------------------------------------------------------------------------------------------
+    const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
+    const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
+    const uint8_t* inl = inlier + lo;
+    const EpiNorm nm = epi_norm(norm, p);
+    float Rf[2][9], uf[3];
+    int cnt[4] = {0, 0, 0, 0};
+    if (ok) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { Rf[0][k] = sRf[0][k]; Rf[1][k] = sRf[1][k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) uf[k] = sUf[k];
+        for (uint32_t i0 = 0; i0 < n; i0 += POSE_THREADS) {
+            const uint32_t i = i0 + tid;
+            float l0, l1, r0, r1;
+            epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
+            if (i < n && inl[i] == 0) l0 = __builtin_nanf("");          // not an inlier of the verification: not used
+            const unsigned bits = pose_front4(Rf, uf, l0, l1, r0, r1);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) cnt[c] += __builtin_popcountll(__builtin_amdgcn_ballot_w64((bits >> c) & 1u));
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s_cnt[wave][c] = cnt[c];
+        }
+    }
+    wg_barrier();
+    if (tid == 0) {
+        int tot[4] = {0, 0, 0, 0};
+        int ch = 0, top = 0;
+        if (ok) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                for (int w = 0; w < POSE_WAVES; ++w) tot[c] += s_cnt[w][c];
+            }
+            top = tot[0];
+#pragma unroll
+            for (int c = 1; c < 4; ++c)
+                if (tot[c] > top) { top = tot[c]; ch = c; }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) front_counts[p * 4 + c] = tot[c];
+        choice_out[p] = ch;
+        front_count[p] = (int64_t)top;
+        s_choice = ch;
+    }
+    wg_barrier();
+    const int ch = s_choice;
+    if (tid < 9) {                                      // the pose in the reference's frame: rows and columns 0 and 1 exchanged
+        const int i = tid / 3, j = tid - 3 * i;
+        const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
+        R_out[p * 9 + tid] = ok ? sR[ch & 1][si * 3 + sj] : (i == j ? 1.0 : 0.0);
+        if (j == 0) t_out[p * 3 + i] = ok ? ((ch & 2) ? -sU[si] : sU[si]) : 0.0;
+    }
+    if (tid == 64) {                                    // E, its sign judged on the values written
+        double big = -1.0, at = 0.0;
+        for (int k = 0; k < 9; ++k) {
+            const int i = k / 3, j = k - 3 * i;
+            const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
+            const double v = ok ? sE[si * 3 + sj] : 0.0;
+            if (__builtin_fabs(v) > big) { big = __builtin_fabs(v); at = v; }
+        }
+        const bool flip = at < 0.0;
+        for (int k = 0; k < 9; ++k) {
+            const int i = k / 3, j = k - 3 * i;
+            const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
+            const double v = ok ? sE[si * 3 + sj] : 0.0;
+            E_out[p * 9 + k] = flip ? -v : v;
+        }
+    }
+
+    // ---- mask -------------------------------------------------------------------------------------------------------------------
+    if (!front || !ok) return;                          // the mask was zeroed before the launch
+    for (uint32_t i0 = 0; i0 < n; i0 += POSE_THREADS) {
+        const uint32_t i = i0 + tid;
+        float l0, l1, r0, r1;
+        epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
+        if (i < n && inl[i] == 0) l0 = __builtin_nanf("");
+        const unsigned bits = pose_front4(Rf, uf, l0, l1, r0, r1);
+        if (i < n) front[lo + i] = (uint8_t)((bits >> ch) & 1u);
+    }
+}
+
+}  // namespace pats
+
+using namespace pats;
+
+extern "C" size_t pats_epipolar_pose_workspace_bytes(int64_t pairs, int64_t cap) {
+    (void)pairs; (void)cap;
+    return 0;                                           // the solve lives in LDS and registers, the mask is a second walk
+}
+
+extern "C" int pats_epipolar_pose_by_pair_f64(const float* matches_l, const float* matches_r, const uint8_t* inlier, const int64_t* pair_off,
+                                              int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap,
+                                              const int64_t* best_count, const double* moments, const float* models, int64_t H,
+                                              const int32_t* best, const float* norm, int swapped, double* E, double* R, double* t,
+                                              int32_t* front_counts, int32_t* choice, int64_t* front_count, uint8_t* front,
+                                              double* e_refit, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    (void)workspace;
+#define PATS_POSE_ALIGNED(ptr, align) \
+    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "epipolar_pose_by_pair: " #ptr " must be " #align "-byte aligned")
+#define PATS_POSE_PTR(ptr, align)                                                       \
+    PATS_REQUIRE(ptr, "epipolar_pose_by_pair: null " #ptr);                             \
+    PATS_POSE_ALIGNED(ptr, align)
+    PATS_POSE_PTR(matches_l, 8);
+    PATS_POSE_PTR(matches_r, 8);
+    PATS_REQUIRE(inlier, "epipolar_pose_by_pair: null inlier");
+    PATS_POSE_PTR(best_count, 8);
+    PATS_POSE_PTR(E, 8);
+    PATS_POSE_PTR(R, 8);
+    PATS_POSE_PTR(t, 8);
+    PATS_POSE_PTR(front_counts, 4);
+    PATS_POSE_PTR(choice, 4);
+    PATS_POSE_PTR(front_count, 8);
+    PATS_POSE_ALIGNED(moments, 8);                      // optional pointers: null is aligned
+    PATS_POSE_ALIGNED(models, 4);
+    PATS_POSE_ALIGNED(best, 4);
+    PATS_POSE_ALIGNED(norm, 4);
+    PATS_POSE_ALIGNED(pair_off, 8);
+    PATS_POSE_ALIGNED(counts_in, 8);
+    PATS_POSE_ALIGNED(e_refit, 8);
+#undef PATS_POSE_PTR
+#undef PATS_POSE_ALIGNED
+    PATS_REQUIRE((pair_off != nullptr) != (counts_in != nullptr),
+                 "epipolar_pose_by_pair: exactly one of pair_off (ragged segments) and counts_in (strided segments) must be given");
+    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "epipolar_pose_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
+    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "epipolar_pose_by_pair: cap = %lld (0 .. 2^31 - 2)", (long long)cap);
+    if (counts_in) {
+        PATS_REQUIRE(stride >= 1, "epipolar_pose_by_pair: stride = %lld must be at least 1", (long long)stride);
+        PATS_REQUIRE(stride <= cap && pairs <= cap / stride, "epipolar_pose_by_pair: pairs * stride = %lld * %lld exceeds cap = %lld",
+                     (long long)pairs, (long long)stride, (long long)cap);
+    }
+    PATS_REQUIRE(swapped == 0 || swapped == 1, "epipolar_pose_by_pair: swapped = %d must be 0 or 1", swapped);
+    PATS_REQUIRE(moments || (models && best), "epipolar_pose_by_pair: the refit needs moments, or models and best (the winning model)");
+    if (models)
+        PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "epipolar_pose_by_pair: H = %lld (1 .. max_h = %lld)", (long long)H,
+                     (long long)pats_epipolar_max_h());
+    PATS_REQUIRE(workspace_bytes >= pats_epipolar_pose_workspace_bytes(pairs, cap), "epipolar_pose_by_pair: workspace too small");
+    hipStream_t st = as_stream(stream);
+    if (front) {
+        const int rc = fill_bytes(front, 0, (size_t)cap, st);
+        if (rc != PATS_OK) return rc;
+    }
+    hipLaunchKernelGGL(epipolar_pose_kernel, dim3((unsigned)pairs), dim3(POSE_THREADS), 0, st, matches_l, matches_r, inlier, pair_off,
+                       counts_in, stride, cap, best_count, moments, moments ? nullptr : models, moments ? 1 : (int)H, best, norm, swapped, E,
+                       R, t, front_counts, choice, front_count, front, e_refit);
+    return check_launch("epipolar_pose kernel");
+}

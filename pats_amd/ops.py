@@ -1787,6 +1787,107 @@ def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, st
     return tuple(out) if return_samples else out[0]
 
 
+def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
+                          counts=None, norm=None, swapped=False, return_front=False, return_refit=False, out=None, pairs=None):
+    """Each pair's relative pose from its verified inliers, ON THE DEVICE, no host read (pats_epipolar_pose_by_pair_f64;
+    include/pats_amd.h holds the definition): the least-squares refit of `moments` (its eigenvector for the smallest eigenvalue;
+    without moments the winning model models[p, best[p]]), the nearest essential matrix E, the four (R, t) decompositions and the
+    cheirality vote of the pair's used matches - inlier != 0, finite - that picks one.  matches_l / matches_r [cap,2] float32 (also
+    [pairs,K,2]), the segments (pair_off, or stride + counts) and norm exactly as epipolar_score_by_pair took them; inlier [cap]
+    uint8, best_count [pairs] int64 and moments [pairs,9,9] float64 (or best [pairs] int32 with the models) are its outputs.
+    swapped: the points are in the hand-over's (y, x) order; R, t, E come back in the reference's (x, y) frame.
+    Returns (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64, front_counts [pairs,4] int32,
+    choice [pairs] int32), then front [cap] uint8 with return_front=True, then e_refit [pairs,9] float64 with return_refit=True.
+    A pair without a pose (best_count < 8, a non-finite moment, a refit of rank below 2) has E = 0, R = I, t = 0 and no count.
+    out: the destinations, in that order."""
+    named = [(matches_l, "matches_l"), (matches_r, "matches_r"), (inlier, "inlier"), (best_count, "best_count"), (moments, "moments"),
+             (models, "models"), (best, "best"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")]
+    types = {"inlier": torch.uint8, "best_count": torch.int64, "moments": torch.float64, "best": torch.int32, "pair_off": torch.int64,
+             "counts": torch.int64}
+    for t, name in named:                       # layout and type first: refused the same way with or without a GPU
+        if isinstance(t, torch.Tensor) and not t.is_contiguous():
+            raise RuntimeError("epipolar_pose_by_pair: %s must be contiguous" % name)
+        want_t = types.get(name, torch.float32)
+        if isinstance(t, torch.Tensor) and t.dtype != want_t:
+            raise RuntimeError("epipolar_pose_by_pair: %s must be %s, got %s" % (name, str(want_t).replace("torch.", ""), t.dtype))
+    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
+        raise RuntimeError("epipolar_pose_by_pair: give either pair_off, or stride and counts")
+    if moments is None and (models is None or best is None):
+        raise RuntimeError("epipolar_pose_by_pair: give moments, or models and best")
+    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
+    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
+        raise RuntimeError("epipolar_pose_by_pair: matches_l / matches_r must be [cap,2]")
+    ml, mr = ml.reshape(-1, 2), mr.reshape(-1, 2)
+    cap = int(ml.shape[0])
+    inl = _dev(inlier, "inlier", torch.uint8).reshape(-1)
+    if inl.numel() != cap:
+        raise RuntimeError("epipolar_pose_by_pair: inlier must be [cap]")
+    bc = _dev(best_count, "best_count", torch.int64).reshape(-1)
+    if pair_off is not None:
+        seg = _dev(pair_off, "pair_off", torch.int64)
+        if seg.dim() != 1:
+            raise RuntimeError("epipolar_pose_by_pair: pair_off must be an int64 vector")
+        pairs = seg.numel() - 1 if pairs is None else int(pairs)
+        if pairs < 1 or seg.numel() < pairs + 1:
+            raise RuntimeError("epipolar_pose_by_pair: pair_off holds %d entries, %d pairs need %d" % (seg.numel(), pairs, pairs + 1))
+        stride = 0
+    else:
+        seg = _dev(counts, "counts", torch.int64).reshape(-1)
+        pairs = seg.numel() if pairs is None else int(pairs)
+        stride = int(stride)
+        if pairs < 1 or seg.numel() != pairs:
+            raise RuntimeError("epipolar_pose_by_pair: counts must hold one int64 per pair")
+        if stride < 1 or pairs * stride > cap:
+            raise RuntimeError("epipolar_pose_by_pair: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (stride, cap))
+    if bc.numel() != pairs:
+        raise RuntimeError("epipolar_pose_by_pair: best_count must hold one int64 per pair (%d), got %d" % (pairs, bc.numel()))
+    H = 1
+    if moments is not None:
+        moments = _dev(moments, "moments", torch.float64)
+        if tuple(moments.shape) != (pairs, 9, 9):
+            raise RuntimeError("epipolar_pose_by_pair: moments must be [pairs,9,9]")
+        models = best = None
+    else:
+        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
+        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
+            raise RuntimeError("epipolar_pose_by_pair: models must be [pairs,H,3,3] and best [pairs]")
+        H = int(models.shape[1])
+        if not 1 <= H <= epipolar_max_h():
+            raise RuntimeError("epipolar_pose_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    if norm is not None:
+        norm = _dev(norm, "norm")
+        if tuple(norm.shape) != (pairs, 8):
+            raise RuntimeError("epipolar_pose_by_pair: norm must be [pairs,8]")
+    dev = ml.device
+    want = [("E", torch.float64, (pairs, 3, 3)), ("R", torch.float64, (pairs, 3, 3)), ("t", torch.float64, (pairs, 3)),
+            ("front_count", torch.int64, (pairs,)), ("front_counts", torch.int32, (pairs, 4)), ("choice", torch.int32, (pairs,))]
+    if return_front:
+        want.append(("front", torch.uint8, (cap,)))
+    if return_refit:
+        want.append(("e_refit", torch.float64, (pairs, 9)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
+    if len(out) != len(want):
+        raise RuntimeError("epipolar_pose_by_pair: out must be (%s)" % ", ".join(n for n, _, _ in want))
+    for t, (name, dt, shape) in zip(out, want):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("epipolar_pose_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    nws = _L().pats_epipolar_pose_workspace_bytes(pairs, cap)
+    ws = _workspace(nws, dev) if nws else None
+    front = out[6] if return_front else None
+    refit = out[-1] if return_refit else None
+    if cap == 0:                                # empty tensors have no address; the call is valid and touches none of these
+        ml = mr = torch.empty((2,), dtype=torch.float32, device=dev)
+        inl = torch.empty((8,), dtype=torch.uint8, device=dev)
+        front = None
+    _check(_L().pats_epipolar_pose_by_pair_f64(_ptr(ml), _ptr(mr), _ptr(inl), _ptr(seg) if pair_off is not None else None, stride,
+                                               _ptr(seg) if pair_off is None else None, pairs, cap, _ptr(bc), _ptr(moments), _ptr(models),
+                                               H, _ptr(best), _ptr(norm), 1 if swapped else 0, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                               _ptr(out[4]), _ptr(out[5]), _ptr(out[3]), _ptr(front), _ptr(refit), _ptr(ws), nws,
+                                               _stream()), "epipolar_pose_by_pair")
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------------
 # ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
 # ------------------------------------------------------------------------------------------------
