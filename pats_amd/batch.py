@@ -352,6 +352,73 @@ def group_by_pair(out, cap, buffers=None, confidence=False):
     return out["by_pair"]
 
 
+# ---- what the hand-over functions below share; a new per-pair stage calls these instead of copying a neighbour ----
+def _overflow_check(o, cap):
+    """o = the summary's host copy: raises on the capacity overflows of a step."""
+    M, P, status = o[cap.pairs + 1:cap.pairs + 4]
+    if status & 1:
+        raise RuntimeError("pats_amd.batch: a pair needed more than Cmax = %d chunks" % cap.Cmax)
+    if status & 2:
+        raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
+    if P > cap.P_cap:
+        raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
+
+
+def _read_topk_summary(out, cap):
+    """(summary, top_count) of a topk_by_pair result as host lists.  Device-to-host copies: ONE when topk_by_pair did the regroup
+    itself (`topk_summary` holds both), TWO otherwise."""
+    if "topk_summary" in out:
+        o = out["topk_summary"].cpu().tolist()            # the one synchronisation of a batch
+        return o[:cap.pairs + 4], o[cap.pairs + 4:]
+    return out["summary"].cpu().tolist(), out["topk"][4].cpu().tolist()
+
+
+def _caller_order(out, cap, per_slot):
+    """per_slot in the caller's order (forward_pairs_mixed: slot s holds the caller's pair caller_of[s])."""
+    if "caller_of" not in out:
+        return per_slot
+    per_caller = [None] * cap.pairs
+    for s_, i in enumerate(out["caller_of"]):
+        per_caller[i] = per_slot[s_]
+    return per_caller
+
+
+def _caller_of_dev(out, dev):
+    """caller_of on the device (made once, kept in the result): index_select with it takes caller order to slot order."""
+    if "caller_of_dev" not in out:
+        out["caller_of_dev"] = torch.tensor(out["caller_of"], dtype=torch.int64, device=dev)
+    return out["caller_of_dev"]
+
+
+def _slot_of_dev(out, cap, dev):
+    """The inverse of caller_of on the device (made once, kept in the result): slot order back to caller order."""
+    if "slot_of_dev" not in out:
+        slot_of = [0] * cap.pairs
+        for s_, i in enumerate(out["caller_of"]):
+            slot_of[i] = s_
+        out["slot_of_dev"] = torch.tensor(slot_of, dtype=torch.int64, device=dev)
+    return out["slot_of_dev"]
+
+
+def _check_on(fn, out, on):
+    if on not in ("all", "topk"):
+        raise ValueError("%s: on must be \"all\" or \"topk\", got %r" % (fn, on))
+    if on == "topk" and "topk" not in out:
+        raise ValueError("%s: on=\"topk\" needs a topk_by_pair result" % fn)
+
+
+def _lists_on(out, cap, on):
+    """The lists a device-side stage works on -> (matches_l, matches_r, conf or None, the segment keywords of the ops call):
+    "topk" = the rows of the topk_by_pair result, strided; "all" = the regrouped full lists (regrouped here if they are not yet)."""
+    if on == "topk":
+        tl, tr, tc, _, tn = out["topk"]
+        return tl, tr, tc, {"stride": int(tl.shape[1]), "counts": tn}
+    if "by_pair" not in out:
+        group_by_pair(out, cap)
+    bp = out["by_pair"]
+    return bp[0], bp[1], bp[3] if len(bp) > 3 else None, {"pair_off": out["summary"], "pairs": cap.pairs}
+
+
 def split_by_pair(out, cap):
     """Host side, AFTER the step: per-pair (matches_l, matches_r) lists - (matches_l, matches_r, conf) for a result made with
     confidence=True - from a forward_pairs (or forward_pairs_mixed: in the
@@ -359,25 +426,14 @@ def split_by_pair(out, cap):
     if "summary" not in out:
         group_by_pair(out, cap)
     o = out["summary"].cpu().tolist()                 # the one synchronisation of a batch: offsets, M, P, status in one copy
-    M, P, status = o[cap.pairs + 1:]
-    if status & 1:
-        raise RuntimeError("pats_amd.batch: a pair needed more than Cmax = %d chunks" % cap.Cmax)
-    if status & 2:
-        raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
-    if P > cap.P_cap:
-        raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
+    _overflow_check(o, cap)
     if len(out["by_pair"]) > 3:
         ml, mr, _, mc = out["by_pair"]
         per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]], mc[o[p]:o[p + 1]]) for p in range(cap.pairs)]
     else:
         ml, mr, _ = out["by_pair"]
         per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]]) for p in range(cap.pairs)]
-    if "caller_of" not in out:
-        return per_slot
-    per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order
-    for s_, i in enumerate(out["caller_of"]):
-        per_caller[i] = per_slot[s_]
-    return per_caller
+    return _caller_order(out, cap, per_slot)
 
 
 def topk_by_pair(out, cap, K, min_conf=None):
@@ -420,26 +476,11 @@ def split_topk_by_pair(out, cap):
     one buffer), TWO otherwise (`summary`, then top_count)."""
     if "topk" not in out:
         raise ValueError("split_topk_by_pair: run topk_by_pair first")
-    tl, tr, tc, ti, tn = out["topk"]
-    if "topk_summary" in out:
-        o = out["topk_summary"].cpu().tolist()            # the one synchronisation of a batch
-        o, counts = o[:cap.pairs + 4], o[cap.pairs + 4:]
-    else:
-        o, counts = out["summary"].cpu().tolist(), tn.cpu().tolist()
-    M, P, status = o[cap.pairs + 1:]
-    if status & 1:
-        raise RuntimeError("pats_amd.batch: a pair needed more than Cmax = %d chunks" % cap.Cmax)
-    if status & 2:
-        raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
-    if P > cap.P_cap:
-        raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
+    tl, tr, tc, ti, _ = out["topk"]
+    o, counts = _read_topk_summary(out, cap)
+    _overflow_check(o, cap)
     per_slot = [(tl[p, :counts[p]], tr[p, :counts[p]], tc[p, :counts[p]], ti[p, :counts[p]]) for p in range(cap.pairs)]
-    if "caller_of" not in out:
-        return per_slot
-    per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order
-    for s_, i in enumerate(out["caller_of"]):
-        per_caller[i] = per_slot[s_]
-    return per_caller
+    return _caller_order(out, cap, per_slot)
 
 
 def hypothesize_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
@@ -453,52 +494,25 @@ def hypothesize_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=N
     Returns models [pairs,H,3,3] float32 - or (models, sample_idx [pairs,H,8] int32) with samples=True - in the CALLER's order: they
     go straight into verify_by_pair(out, cap, models, thr, norm=norm, on=...).  Adds `hypotheses` (what is returned) to the result;
     the matches, the regrouped lists and a top-K of the same step are not touched."""
-    if on not in ("all", "topk"):
-        raise ValueError("hypothesize_by_pair: on must be \"all\" or \"topk\", got %r" % (on,))
-    if on == "topk" and "topk" not in out:
-        raise ValueError("hypothesize_by_pair: on=\"topk\" needs a topk_by_pair result")
+    _check_on("hypothesize_by_pair", out, on)
     if progressive is None:
         progressive = on == "topk"
     dev = out["matches_l"].device
     seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)              # the int64 the bits of `seed` spell
-    mixed = "caller_of" in out
-    if mixed and "caller_of_dev" not in out:                              # slot s holds the caller's pair caller_of[s]
-        out["caller_of_dev"] = torch.tensor(out["caller_of"], dtype=torch.int64, device=dev)
+    mixed = "caller_of" in out                                            # slot s holds the caller's pair caller_of[s]
     if out.get("pair_seed", (None,))[0] != seed:
-        ids = out["caller_of_dev"] if mixed else torch.arange(cap.pairs, dtype=torch.int64, device=dev)
+        ids = _caller_of_dev(out, dev) if mixed else torch.arange(cap.pairs, dtype=torch.int64, device=dev)
         out["pair_seed"] = (seed, ids + seed)                             # slot order
     pair_seed = out["pair_seed"][1]
     if mixed and norm is not None:
-        norm = norm.index_select(0, out["caller_of_dev"])
-    if on == "topk":
-        tl, tr, _, _, tn = out["topk"]
-        hyp = ops.epipolar_hypotheses_by_pair(tl, tr, H, pair_seed, stride=int(tl.shape[1]), counts=tn, norm=norm, progressive=progressive,
-                                              return_samples=samples)
-    else:
-        if "by_pair" not in out:
-            group_by_pair(out, cap)
-        bp = out["by_pair"]
-        hyp = ops.epipolar_hypotheses_by_pair(bp[0], bp[1], H, pair_seed, pair_off=out["summary"], norm=norm, progressive=progressive,
-                                              return_samples=samples, pairs=cap.pairs)
+        norm = norm.index_select(0, _caller_of_dev(out, dev))
+    ml, mr, _, seg = _lists_on(out, cap, on)
+    hyp = ops.epipolar_hypotheses_by_pair(ml, mr, H, pair_seed, norm=norm, progressive=progressive, return_samples=samples, **seg)
     if mixed:                                                             # slots back to the caller's order
-        if "slot_of_dev" not in out:
-            slot_of = [0] * cap.pairs
-            for s_, i in enumerate(out["caller_of"]):
-                slot_of[i] = s_
-            out["slot_of_dev"] = torch.tensor(slot_of, dtype=torch.int64, device=dev)
-        hyp = tuple(t.index_select(0, out["slot_of_dev"]) for t in hyp) if samples else hyp.index_select(0, out["slot_of_dev"])
+        back = _slot_of_dev(out, cap, dev)
+        hyp = tuple(t.index_select(0, back) for t in hyp) if samples else hyp.index_select(0, back)
     out["hypotheses"] = hyp
     return hyp
-
-
-def _overflow_check(o, cap):
-    M, P, status = o[cap.pairs + 1:cap.pairs + 4]
-    if status & 1:
-        raise RuntimeError("pats_amd.batch: a pair needed more than Cmax = %d chunks" % cap.Cmax)
-    if status & 2:
-        raise RuntimeError("pats_amd.batch: the row table overflowed rows_cap = %d" % cap.rows_cap)
-    if P > cap.P_cap:
-        raise RuntimeError("pats_amd.batch: %d third-level problems exceed P_cap = %d" % (P, cap.P_cap))
 
 
 def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
@@ -511,28 +525,16 @@ def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", mo
     that were scored - [M_cap] for "all", [pairs*K] for "topk" - [, moments [pairs,9,9] float64]) to the result and returns it; rows
     in SLOT order for a mixed pack (models / thr / norm are permuted to it on the device; split_verified_by_pair hands the pairs
     back in the caller's order).  The matches, the regrouped lists and a top-K of the same step are not touched."""
-    if on not in ("all", "topk"):
-        raise ValueError("verify_by_pair: on must be \"all\" or \"topk\", got %r" % (on,))
-    if on == "topk" and "topk" not in out:
-        raise ValueError("verify_by_pair: on=\"topk\" needs a topk_by_pair result")
+    _check_on("verify_by_pair", out, on)
     if min_conf is not None and "match_conf" not in out:
         raise ValueError("verify_by_pair: min_conf needs a result made with confidence=True")
     if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
-        if "caller_of_dev" not in out:
-            out["caller_of_dev"] = torch.tensor(out["caller_of"], dtype=torch.int64, device=models.device)
-        idx = out["caller_of_dev"]
+        idx = _caller_of_dev(out, models.device)
         models, thr = models.index_select(0, idx), thr.index_select(0, idx)
         norm = None if norm is None else norm.index_select(0, idx)
-    if on == "topk":
-        tl, tr, tc, _, tn = out["topk"]
-        ver = ops.epipolar_score_by_pair(tl, tr, models, thr, stride=int(tl.shape[1]), counts=tn, conf=tc if min_conf is not None else None,
-                                         min_conf=min_conf, norm=norm, moments=moments)
-    else:
-        if "by_pair" not in out:
-            group_by_pair(out, cap)
-        bp = out["by_pair"]
-        ver = ops.epipolar_score_by_pair(bp[0], bp[1], models, thr, pair_off=out["summary"], conf=bp[3] if min_conf is not None else None,
-                                         min_conf=min_conf, norm=norm, moments=moments, pairs=cap.pairs)
+    ml, mr, conf, seg = _lists_on(out, cap, on)
+    ver = ops.epipolar_score_by_pair(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm,
+                                     moments=moments, **seg)
     out["verified"], out["verified_on"] = ver, on
     out["verified_models"] = models                   # slot order: pose_by_pair's source when no moments were asked for
     return ver
@@ -548,12 +550,8 @@ def split_verified_by_pair(out, cap):
         raise ValueError("split_verified_by_pair: run verify_by_pair first")
     best, best_count, inl = out["verified"][1:4]
     if out["verified_on"] == "topk":
-        tl, tr, _, _, tn = out["topk"]
-        if "topk_summary" in out:
-            o = out["topk_summary"].cpu().tolist()            # the one synchronisation of a batch
-            o, counts = o[:cap.pairs + 4], o[cap.pairs + 4:]
-        else:
-            o, counts = out["summary"].cpu().tolist(), tn.cpu().tolist()
+        tl, tr = out["topk"][:2]
+        o, counts = _read_topk_summary(out, cap)
         _overflow_check(o, cap)
         mask = inl.view(cap.pairs, -1)
         per_slot = [(tl[p, :counts[p]], tr[p, :counts[p]], mask[p, :counts[p]].bool(), best[p], best_count[p]) for p in range(cap.pairs)]
@@ -562,12 +560,7 @@ def split_verified_by_pair(out, cap):
         _overflow_check(o, cap)
         ml, mr = out["by_pair"][:2]
         per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]], inl[o[p]:o[p + 1]].bool(), best[p], best_count[p]) for p in range(cap.pairs)]
-    if "caller_of" not in out:
-        return per_slot
-    per_caller = [None] * cap.pairs                   # forward_pairs_mixed: slots back to the caller's order
-    for s_, i in enumerate(out["caller_of"]):
-        per_caller[i] = per_slot[s_]
-    return per_caller
+    return _caller_order(out, cap, per_slot)
 
 
 def pose_by_pair(out, cap, norm=None, swapped=False, front=False):
@@ -586,23 +579,13 @@ def pose_by_pair(out, cap, norm=None, swapped=False, front=False):
     best, best_count, inl = ver[1:4]
     mixed = "caller_of" in out
     if mixed and norm is not None:
-        norm = norm.index_select(0, out["caller_of_dev"])                 # verify_by_pair made the index
+        norm = norm.index_select(0, _caller_of_dev(out, inl.device))
     src = {"moments": ver[4]} if len(ver) > 4 else {"models": out["verified_models"], "best": best}
-    if on == "topk":
-        tl, tr, _, _, tn = out["topk"]
-        res = ops.epipolar_pose_by_pair(tl, tr, inl, best_count, stride=int(tl.shape[1]), counts=tn, norm=norm, swapped=swapped,
-                                        return_front=front, **src)
-    else:
-        bp = out["by_pair"]
-        res = ops.epipolar_pose_by_pair(bp[0], bp[1], inl, best_count, pair_off=out["summary"], norm=norm, swapped=swapped,
-                                        return_front=front, pairs=cap.pairs, **src)
+    ml, mr, _, seg = _lists_on(out, cap, on)
+    res = ops.epipolar_pose_by_pair(ml, mr, inl, best_count, norm=norm, swapped=swapped, return_front=front, **src, **seg)
     if mixed:                                                             # slots back to the caller's order
-        if "slot_of_dev" not in out:
-            slot_of = [0] * cap.pairs
-            for s_, i in enumerate(out["caller_of"]):
-                slot_of[i] = s_
-            out["slot_of_dev"] = torch.tensor(slot_of, dtype=torch.int64, device=inl.device)
-        res = tuple(t.index_select(0, out["slot_of_dev"]) for t in res[:6]) + tuple(res[6:])
+        back = _slot_of_dev(out, cap, inl.device)
+        res = tuple(t.index_select(0, back) for t in res[:6]) + tuple(res[6:])
     out["pose"] = res
     return res
 

@@ -48,6 +48,14 @@ int* gnn_overflow_flag();
         }                                     \
     } while (0)
 
+// A pointer argument of the entry point `fn` (a string literal): non-null and aligned, or - an optional one, null is aligned -
+// only aligned.  Macros, because the message names the argument.
+#define PATS_REQUIRE_ALIGNED(fn, ptr, align) \
+    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, fn ": " #ptr " must be " #align "-byte aligned")
+#define PATS_REQUIRE_PTR(fn, ptr, align)     \
+    PATS_REQUIRE(ptr, fn ": null " #ptr);    \
+    PATS_REQUIRE_ALIGNED(fn, ptr, align)
+
 // ---- wave-level reductions: 4 DPP steps inside each 16-lane row, then two half-swaps -------
 // Every lane ends up with the full 64-lane result (all-reduce).
 template <int CTRL>

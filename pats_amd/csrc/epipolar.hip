@@ -236,37 +236,23 @@ extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const flo
                                                int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
                                                void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-#define PATS_EPI_ALIGNED(ptr, align) \
-    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "epipolar_score_by_pair: " #ptr " must be " #align "-byte aligned")
-#define PATS_EPI_PTR(ptr, align)                                                        \
-    PATS_REQUIRE(ptr, "epipolar_score_by_pair: null " #ptr);                            \
-    PATS_EPI_ALIGNED(ptr, align)
-    PATS_EPI_PTR(matches_l, 8);
-    PATS_EPI_PTR(matches_r, 8);
-    PATS_EPI_PTR(models, 4);
-    PATS_EPI_PTR(thr, 4);
-    PATS_EPI_PTR(counts, 4);
-    PATS_EPI_PTR(best, 4);
-    PATS_EPI_PTR(best_count, 8);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", matches_l, 8);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", matches_r, 8);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", models, 4);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", thr, 4);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", counts, 4);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", best, 4);
+    PATS_REQUIRE_PTR("epipolar_score_by_pair", best_count, 8);
     PATS_REQUIRE(inlier, "epipolar_score_by_pair: null inlier");
-    PATS_EPI_ALIGNED(conf, 4);                          // optional pointers: null is aligned
-    PATS_EPI_ALIGNED(norm, 4);
-    PATS_EPI_ALIGNED(pair_off, 8);
-    PATS_EPI_ALIGNED(counts_in, 8);
-    PATS_EPI_ALIGNED(moments, 8);
-#undef PATS_EPI_PTR
-#undef PATS_EPI_ALIGNED
-    PATS_REQUIRE((pair_off != nullptr) != (counts_in != nullptr),
-                 "epipolar_score_by_pair: exactly one of pair_off (ragged segments) and counts_in (strided segments) must be given");
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "epipolar_score_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "epipolar_score_by_pair: H = %lld (1 .. max_h = %lld)", (long long)H,
-                 (long long)pats_epipolar_max_h());
-    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "epipolar_score_by_pair: cap = %lld (0 .. 2^31 - 2)", (long long)cap);
-    if (counts_in) {
-        PATS_REQUIRE(stride >= 1, "epipolar_score_by_pair: stride = %lld must be at least 1", (long long)stride);
-        PATS_REQUIRE(stride <= cap && pairs <= cap / stride, "epipolar_score_by_pair: pairs * stride = %lld * %lld exceeds cap = %lld",
-                     (long long)pairs, (long long)stride, (long long)cap);
-    }
+    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", conf, 4);     // optional pointers: null is aligned
+    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", norm, 4);
+    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", pair_off, 8);
+    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", counts_in, 8);
+    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", moments, 8);
+    int rc = epi_check_segments("epipolar_score_by_pair", pair_off, counts_in, stride, pairs, cap);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_h("epipolar_score_by_pair", H);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(!use_min_conf || conf, "epipolar_score_by_pair: min_conf needs conf");
     PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "epipolar_score_by_pair: min_conf = %g must be a non-negative number", (double)min_conf);
     PATS_REQUIRE(workspace_bytes >= pats_epipolar_workspace_bytes(pairs, H, cap), "epipolar_score_by_pair: workspace too small");
@@ -275,7 +261,7 @@ extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const flo
     PATS_REQUIRE(tiles * chunks <= 0x7fffffff / pairs, "epipolar_score_by_pair: pairs = %lld gives a grid of %lld x %lld x %lld workgroups (< 2^31)",
                  (long long)pairs, (long long)tiles, (long long)pairs, (long long)chunks);
     hipStream_t st = as_stream(stream);
-    int rc = fill_bytes(counts, 0, (size_t)pairs * (size_t)H * sizeof(int32_t), st);
+    rc = fill_bytes(counts, 0, (size_t)pairs * (size_t)H * sizeof(int32_t), st);
     if (rc != PATS_OK) return rc;
     rc = fill_bytes(inlier, 0, (size_t)cap, st);
     if (rc != PATS_OK) return rc;

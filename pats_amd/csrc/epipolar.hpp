@@ -51,4 +51,27 @@ __device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const fl
     if (ok) l0 = a.x;
 }
 
+// ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name) ------
+// exactly one segment form, and sizes the kernels' 32-bit indices and epi_segment's clamps rely on
+inline int epi_check_segments(const char* what, const int64_t* pair_off, const int64_t* counts_in, int64_t stride, int64_t pairs,
+                              int64_t cap) {
+    PATS_REQUIRE((pair_off != nullptr) != (counts_in != nullptr),
+                 "%s: exactly one of pair_off (ragged segments) and counts_in (strided segments) must be given", what);
+    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "%s: pairs = %lld (1 .. 2^31 - 1)", what, (long long)pairs);
+    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "%s: cap = %lld (0 .. 2^31 - 2)", what, (long long)cap);
+    if (counts_in) {
+        PATS_REQUIRE(stride >= 1, "%s: stride = %lld must be at least 1", what, (long long)stride);
+        PATS_REQUIRE(stride <= cap && pairs <= cap / stride, "%s: pairs * stride = %lld * %lld exceeds cap = %lld", what,
+                     (long long)pairs, (long long)stride, (long long)cap);
+    }
+    return PATS_OK;
+}
+
+// the number of models per pair
+inline int epi_check_h(const char* what, int64_t H) {
+    PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "%s: H = %lld (1 .. max_h = %lld)", what, (long long)H,
+                 (long long)pats_epipolar_max_h());
+    return PATS_OK;
+}
+
 }  // namespace pats

@@ -212,32 +212,18 @@ extern "C" int pats_epipolar_hypotheses_by_pair_f32(const float* matches_l, cons
                                                     const int64_t* pair_seed, const float* norm, int progressive, float* models,
                                                     int32_t* sample_idx, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-#define PATS_HYP_ALIGNED(ptr, align) \
-    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "epipolar_hypotheses_by_pair: " #ptr " must be " #align "-byte aligned")
-#define PATS_HYP_PTR(ptr, align)                                                        \
-    PATS_REQUIRE(ptr, "epipolar_hypotheses_by_pair: null " #ptr);                       \
-    PATS_HYP_ALIGNED(ptr, align)
-    PATS_HYP_PTR(matches_l, 8);
-    PATS_HYP_PTR(matches_r, 8);
-    PATS_HYP_PTR(pair_seed, 8);
-    PATS_HYP_PTR(models, 4);
-    PATS_HYP_ALIGNED(norm, 4);                          // optional pointers: null is aligned
-    PATS_HYP_ALIGNED(sample_idx, 4);
-    PATS_HYP_ALIGNED(pair_off, 8);
-    PATS_HYP_ALIGNED(counts_in, 8);
-#undef PATS_HYP_PTR
-#undef PATS_HYP_ALIGNED
-    PATS_REQUIRE((pair_off != nullptr) != (counts_in != nullptr),
-                 "epipolar_hypotheses_by_pair: exactly one of pair_off (ragged segments) and counts_in (strided segments) must be given");
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "epipolar_hypotheses_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "epipolar_hypotheses_by_pair: H = %lld (1 .. max_h = %lld)", (long long)H,
-                 (long long)pats_epipolar_max_h());
-    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "epipolar_hypotheses_by_pair: cap = %lld (0 .. 2^31 - 2)", (long long)cap);
-    if (counts_in) {
-        PATS_REQUIRE(stride >= 1, "epipolar_hypotheses_by_pair: stride = %lld must be at least 1", (long long)stride);
-        PATS_REQUIRE(stride <= cap && pairs <= cap / stride, "epipolar_hypotheses_by_pair: pairs * stride = %lld * %lld exceeds cap = %lld",
-                     (long long)pairs, (long long)stride, (long long)cap);
-    }
+    PATS_REQUIRE_PTR("epipolar_hypotheses_by_pair", matches_l, 8);
+    PATS_REQUIRE_PTR("epipolar_hypotheses_by_pair", matches_r, 8);
+    PATS_REQUIRE_PTR("epipolar_hypotheses_by_pair", pair_seed, 8);
+    PATS_REQUIRE_PTR("epipolar_hypotheses_by_pair", models, 4);
+    PATS_REQUIRE_ALIGNED("epipolar_hypotheses_by_pair", norm, 4);     // optional pointers: null is aligned
+    PATS_REQUIRE_ALIGNED("epipolar_hypotheses_by_pair", sample_idx, 4);
+    PATS_REQUIRE_ALIGNED("epipolar_hypotheses_by_pair", pair_off, 8);
+    PATS_REQUIRE_ALIGNED("epipolar_hypotheses_by_pair", counts_in, 8);
+    int rc = epi_check_segments("epipolar_hypotheses_by_pair", pair_off, counts_in, stride, pairs, cap);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_h("epipolar_hypotheses_by_pair", H);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(progressive == 0 || progressive == 1, "epipolar_hypotheses_by_pair: progressive = %d must be 0 or 1", progressive);
     PATS_REQUIRE(workspace_bytes >= pats_epipolar_hypotheses_workspace_bytes(pairs, H), "epipolar_hypotheses_by_pair: workspace too small");
     const int64_t chunks = ceil_div(H, HYP_THREADS);

@@ -390,48 +390,35 @@ extern "C" int pats_epipolar_pose_by_pair_f64(const float* matches_l, const floa
                                               int32_t* front_counts, int32_t* choice, int64_t* front_count, uint8_t* front,
                                               double* e_refit, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-#define PATS_POSE_ALIGNED(ptr, align) \
-    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "epipolar_pose_by_pair: " #ptr " must be " #align "-byte aligned")
-#define PATS_POSE_PTR(ptr, align)                                                       \
-    PATS_REQUIRE(ptr, "epipolar_pose_by_pair: null " #ptr);                             \
-    PATS_POSE_ALIGNED(ptr, align)
-    PATS_POSE_PTR(matches_l, 8);
-    PATS_POSE_PTR(matches_r, 8);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", matches_l, 8);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", matches_r, 8);
     PATS_REQUIRE(inlier, "epipolar_pose_by_pair: null inlier");
-    PATS_POSE_PTR(best_count, 8);
-    PATS_POSE_PTR(E, 8);
-    PATS_POSE_PTR(R, 8);
-    PATS_POSE_PTR(t, 8);
-    PATS_POSE_PTR(front_counts, 4);
-    PATS_POSE_PTR(choice, 4);
-    PATS_POSE_PTR(front_count, 8);
-    PATS_POSE_ALIGNED(moments, 8);                      // optional pointers: null is aligned
-    PATS_POSE_ALIGNED(models, 4);
-    PATS_POSE_ALIGNED(best, 4);
-    PATS_POSE_ALIGNED(norm, 4);
-    PATS_POSE_ALIGNED(pair_off, 8);
-    PATS_POSE_ALIGNED(counts_in, 8);
-    PATS_POSE_ALIGNED(e_refit, 8);
-#undef PATS_POSE_PTR
-#undef PATS_POSE_ALIGNED
-    PATS_REQUIRE((pair_off != nullptr) != (counts_in != nullptr),
-                 "epipolar_pose_by_pair: exactly one of pair_off (ragged segments) and counts_in (strided segments) must be given");
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "epipolar_pose_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "epipolar_pose_by_pair: cap = %lld (0 .. 2^31 - 2)", (long long)cap);
-    if (counts_in) {
-        PATS_REQUIRE(stride >= 1, "epipolar_pose_by_pair: stride = %lld must be at least 1", (long long)stride);
-        PATS_REQUIRE(stride <= cap && pairs <= cap / stride, "epipolar_pose_by_pair: pairs * stride = %lld * %lld exceeds cap = %lld",
-                     (long long)pairs, (long long)stride, (long long)cap);
-    }
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", best_count, 8);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", E, 8);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", R, 8);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", t, 8);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", front_counts, 4);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", choice, 4);
+    PATS_REQUIRE_PTR("epipolar_pose_by_pair", front_count, 8);
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", moments, 8);     // optional pointers: null is aligned
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", models, 4);
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", best, 4);
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", norm, 4);
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", pair_off, 8);
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", counts_in, 8);
+    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", e_refit, 8);
+    int rc = epi_check_segments("epipolar_pose_by_pair", pair_off, counts_in, stride, pairs, cap);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(swapped == 0 || swapped == 1, "epipolar_pose_by_pair: swapped = %d must be 0 or 1", swapped);
     PATS_REQUIRE(moments || (models && best), "epipolar_pose_by_pair: the refit needs moments, or models and best (the winning model)");
-    if (models)
-        PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "epipolar_pose_by_pair: H = %lld (1 .. max_h = %lld)", (long long)H,
-                     (long long)pats_epipolar_max_h());
+    if (models) {
+        rc = epi_check_h("epipolar_pose_by_pair", H);
+        if (rc != PATS_OK) return rc;
+    }
     PATS_REQUIRE(workspace_bytes >= pats_epipolar_pose_workspace_bytes(pairs, cap), "epipolar_pose_by_pair: workspace too small");
     hipStream_t st = as_stream(stream);
     if (front) {
-        const int rc = fill_bytes(front, 0, (size_t)cap, st);
+        rc = fill_bytes(front, 0, (size_t)cap, st);
         if (rc != PATS_OK) return rc;
     }
     hipLaunchKernelGGL(epipolar_pose_kernel, dim3((unsigned)pairs), dim3(POSE_THREADS), 0, st, matches_l, matches_r, inlier, pair_off,

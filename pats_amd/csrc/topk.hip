@@ -196,19 +196,15 @@ extern "C" int pats_topk_by_pair_f32(const float* matches_l, const float* matche
                                      float* top_r, float* top_conf, int32_t* top_idx, int64_t* top_count, void* workspace,
                                      size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-#define PATS_TOPK_PTR(ptr, align)                                                       \
-    PATS_REQUIRE(ptr, "topk_by_pair: null " #ptr);                                      \
-    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "topk_by_pair: " #ptr " must be " #align "-byte aligned")
-    PATS_TOPK_PTR(matches_l, 8);
-    PATS_TOPK_PTR(matches_r, 8);
-    PATS_TOPK_PTR(conf, 4);
-    PATS_TOPK_PTR(pair_off, 8);
-    PATS_TOPK_PTR(top_l, 8);
-    PATS_TOPK_PTR(top_r, 8);
-    PATS_TOPK_PTR(top_conf, 4);
-    PATS_TOPK_PTR(top_idx, 4);
-    PATS_TOPK_PTR(top_count, 8);
-#undef PATS_TOPK_PTR
+    PATS_REQUIRE_PTR("topk_by_pair", matches_l, 8);
+    PATS_REQUIRE_PTR("topk_by_pair", matches_r, 8);
+    PATS_REQUIRE_PTR("topk_by_pair", conf, 4);
+    PATS_REQUIRE_PTR("topk_by_pair", pair_off, 8);
+    PATS_REQUIRE_PTR("topk_by_pair", top_l, 8);
+    PATS_REQUIRE_PTR("topk_by_pair", top_r, 8);
+    PATS_REQUIRE_PTR("topk_by_pair", top_conf, 4);
+    PATS_REQUIRE_PTR("topk_by_pair", top_idx, 4);
+    PATS_REQUIRE_PTR("topk_by_pair", top_count, 8);
     PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "topk_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
     PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "topk_by_pair: cap = %lld (0 .. 2^31 - 2: top_idx is int32)", (long long)cap);
     PATS_REQUIRE(K >= 1 && K <= pats_topk_by_pair_max_k(), "topk_by_pair: K = %lld (1 .. max_k = %lld)", (long long)K,

@@ -1562,6 +1562,89 @@ def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None, 
     return ol, orr, off[:rows.pairs + 1], off
 
 
+# ---- what the per-pair hand-over stages below (top-K, epipolar score / hypotheses / pose) check alike; fn = the public
+# function's name, the prefix of every message.  A new per-pair stage calls these instead of copying a neighbour. ----
+def _bp_layout(fn, named, types=()):
+    """Contiguity and dtype of the (tensor, name) pairs that are tensors - float32 unless `types` {name: dtype} says otherwise.
+    The FIRST check of a stage: a bad layout or type is refused the same way with or without a GPU."""
+    types = dict(types)
+    for t, name in named:
+        if not isinstance(t, torch.Tensor):
+            continue
+        if not t.is_contiguous():
+            raise RuntimeError("%s: %s must be contiguous" % (fn, name))
+        want = types.get(name, torch.float32)
+        if t.dtype != want:
+            raise RuntimeError("%s: %s must be %s, got %s" % (fn, name, str(want).replace("torch.", ""), t.dtype))
+
+
+def _bp_one_form(fn, pair_off, stride, counts):
+    """Exactly one segment form: pair_off (ragged), or stride and counts (strided)."""
+    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
+        raise RuntimeError("%s: give either pair_off, or stride and counts" % fn)
+
+
+def _bp_matches(fn, matches_l, matches_r):
+    """The match lists ([cap,2], or top-K's [pairs,K,2]) as flat GPU [cap,2] lists -> (ml, mr, cap)."""
+    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
+    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
+        raise RuntimeError("%s: matches_l / matches_r must be [cap,2]" % fn)
+    ml = ml.reshape(-1, 2)
+    return ml, mr.reshape(-1, 2), int(ml.shape[0])
+
+
+def _bp_segments(fn, pair_off, stride, counts, pairs, cap):
+    """The pairs' segments (one form: _bp_one_form) -> (seg, pairs, stride, pair_off pointer, counts pointer): seg is the GPU int64
+    tensor behind the one pointer that is not null; stride is 0 for the ragged form.  pairs=None: as many as seg describes."""
+    if counts is None:
+        seg = _dev(pair_off, "pair_off", torch.int64)
+        if seg.dim() != 1:
+            raise RuntimeError("%s: pair_off must be an int64 vector" % fn)
+        pairs = seg.numel() - 1 if pairs is None else int(pairs)
+        if pairs < 1 or seg.numel() < pairs + 1:
+            raise RuntimeError("%s: pair_off holds %d entries, %d pairs need %d" % (fn, seg.numel(), pairs, pairs + 1))
+        return seg, pairs, 0, _ptr(seg), None
+    seg = _dev(counts, "counts", torch.int64).reshape(-1)
+    pairs = seg.numel() if pairs is None else int(pairs)
+    stride = int(stride)
+    if pairs < 1 or seg.numel() != pairs:
+        raise RuntimeError("%s: counts must hold one int64 per pair" % fn)
+    if stride < 1 or pairs * stride > cap:
+        raise RuntimeError("%s: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (fn, stride, cap))
+    return seg, pairs, stride, None, _ptr(seg)
+
+
+def _bp_norm(fn, norm, pairs):
+    """The optional normalisation as a GPU [pairs,8] tensor, or None."""
+    if norm is None:
+        return None
+    norm = _dev(norm, "norm")
+    if tuple(norm.shape) != (pairs, 8):
+        raise RuntimeError("%s: norm must be [pairs,8]" % fn)
+    return norm
+
+
+def _bp_outputs(fn, want, out, dev, lone=False):
+    """The destinations `want` = [(name, dtype, shape)] describes: allocated when out is None, else out checked against it.
+    lone: a tensor is taken as the 1-tuple of it."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
+    if lone and isinstance(out, torch.Tensor):
+        out = (out,)
+    if len(out) != len(want):
+        raise RuntimeError("%s: out must be (%s)" % (fn, ", ".join(n for n, _, _ in want)))
+    for t, (name, dt, shape) in zip(out, want):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("%s: %s must be a contiguous GPU %s tensor of shape %s" % (fn, name, dt, list(shape)))
+    return tuple(out)
+
+
+def _bp_placeholder(dev, dtype=torch.float32):
+    """Empty tensors have no address: with cap == 0 a stage passes these 8 bytes for its [cap] arguments (the call is valid and
+    touches none of them)."""
+    return torch.empty((8 // dtype.itemsize,), dtype=dtype, device=dev)
+
+
 def topk_max_k():
     """The largest K topk_by_pair takes (pats_topk_by_pair_max_k)."""
     return int(_L().pats_topk_by_pair_max_k())
@@ -1575,42 +1658,29 @@ def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=Non
     Returns (top_l [pairs,K,2], top_r [pairs,K,2], top_conf [pairs,K], top_idx [pairs,K] int32, top_count [pairs] int64): rank j
     of pair p is the match at position top_idx[p,j] of the pair's list, by confidence descending, ties by position ascending
     (+inf and a positive NaN rank first); past top_count[p] top_idx is -1 and the rest 0.0.  out: the five destinations."""
+    fn = "topk_by_pair"
     for t, name in ((matches_l, "matches_l"), (matches_r, "matches_r"), (conf, "conf"), (pair_off, "pair_off")):
         if isinstance(t, torch.Tensor) and t.is_cuda and not t.is_contiguous():
             raise RuntimeError("topk_by_pair: %s must be contiguous" % name)
     ml, mr, cf = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r"), _dev(conf, "conf").reshape(-1)
-    pair_off = _dev(pair_off, "pair_off", torch.int64)
-    if pair_off.dim() != 1:
-        raise RuntimeError("topk_by_pair: pair_off must be an int64 vector")
-    if pairs is None:
-        pairs = pair_off.numel() - 1
-    pairs, K, cap = int(pairs), int(K), int(cf.numel())
-    if pairs < 1 or pair_off.numel() < pairs + 1:
-        raise RuntimeError("topk_by_pair: pair_off holds %d entries, %d pairs need %d" % (pair_off.numel(), pairs, pairs + 1))
+    K, cap = int(K), int(cf.numel())
+    pair_off, pairs, _, off_p, _ = _bp_segments(fn, pair_off, None, None, pairs, cap)
     if ml.dim() != 2 or ml.shape[1] != 2 or ml.shape != mr.shape or ml.shape[0] != cap:
         raise RuntimeError("topk_by_pair: matches_l / matches_r must be [cap,2] and conf [cap]")
     if not 1 <= K <= topk_max_k():
         raise RuntimeError("topk_by_pair: K = %d, must lie in 1 .. %d" % (K, topk_max_k()))
     dev = ml.device
-    if out is None:
-        out = (torch.empty((pairs, K, 2), dtype=torch.float32, device=dev), torch.empty((pairs, K, 2), dtype=torch.float32, device=dev),
-               torch.empty((pairs, K), dtype=torch.float32, device=dev), torch.empty((pairs, K), dtype=torch.int32, device=dev),
-               torch.empty((pairs,), dtype=torch.int64, device=dev))
-    if len(out) != 5:
-        raise RuntimeError("topk_by_pair: out must be (top_l, top_r, top_conf, top_idx, top_count)")
     want = (("top_l", torch.float32, (pairs, K, 2)), ("top_r", torch.float32, (pairs, K, 2)), ("top_conf", torch.float32, (pairs, K)),
             ("top_idx", torch.int32, (pairs, K)), ("top_count", torch.int64, (pairs,)))
-    for t, (name, dt, shape) in zip(out, want):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RuntimeError("topk_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    out = _bp_outputs(fn, want, out, dev)
     nws = _L().pats_topk_by_pair_workspace_bytes(pairs, K)
     ws = _workspace(nws, dev) if nws else None
-    if cap == 0:                                # empty tensors have no address; the call is valid and reads none of the three
-        ml = mr = cf = torch.empty((2,), dtype=torch.float32, device=dev)
-    _check(_L().pats_topk_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(cf), _ptr(pair_off), pairs, cap, K, 0 if min_conf is None else 1,
+    if cap == 0:
+        ml = mr = cf = _bp_placeholder(dev)
+    _check(_L().pats_topk_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(cf), off_p, pairs, cap, K, 0 if min_conf is None else 1,
                                       0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                      _ptr(out[3]), _ptr(out[4]), _ptr(ws), nws, _stream()), "topk_by_pair")
-    return tuple(out)
+                                      _ptr(out[3]), _ptr(out[4]), _ptr(ws), nws, _stream()), fn)
+    return out
 
 
 def epipolar_max_h():
@@ -1633,43 +1703,18 @@ def epipolar_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, str
     inlier [cap] uint8 - 1 where the match is an inlier of its pair's best model, 0 everywhere else) and, with moments=True,
     moments [pairs,9,9] float64 = the sum of q q^T over those inliers, q = vec(x_r x_l^T): torch.linalg.eigh of it is the
     least-squares refit.  out: the four (five) destinations."""
-    named = [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
-             (counts, "counts"), (conf, "conf"), (norm, "norm")]
-    i64 = ("pair_off", "counts")
-    for t, name in named:                       # layout and type first: refused the same way with or without a GPU
-        if isinstance(t, torch.Tensor) and not t.is_contiguous():
-            raise RuntimeError("epipolar_score_by_pair: %s must be contiguous" % name)
-        if isinstance(t, torch.Tensor) and t.dtype != (torch.int64 if name in i64 else torch.float32):
-            raise RuntimeError("epipolar_score_by_pair: %s must be %s, got %s" % (name, "int64" if name in i64 else "float32", t.dtype))
-    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
-        raise RuntimeError("epipolar_score_by_pair: give either pair_off, or stride and counts")
+    fn = "epipolar_score_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
+                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
     if min_conf is not None and conf is None:
         raise RuntimeError("epipolar_score_by_pair: min_conf needs conf")
-    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
-    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
-        raise RuntimeError("epipolar_score_by_pair: matches_l / matches_r must be [cap,2]")
-    ml, mr = ml.reshape(-1, 2), mr.reshape(-1, 2)
-    cap = int(ml.shape[0])
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
     models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
     if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
         raise RuntimeError("epipolar_score_by_pair: models must be [pairs,H,3,3]")
     H = int(models.shape[1])
-    if pair_off is not None:
-        seg = _dev(pair_off, "pair_off", torch.int64)
-        if seg.dim() != 1:
-            raise RuntimeError("epipolar_score_by_pair: pair_off must be an int64 vector")
-        pairs = seg.numel() - 1 if pairs is None else int(pairs)
-        if pairs < 1 or seg.numel() < pairs + 1:
-            raise RuntimeError("epipolar_score_by_pair: pair_off holds %d entries, %d pairs need %d" % (seg.numel(), pairs, pairs + 1))
-        stride = 0
-    else:
-        seg = _dev(counts, "counts", torch.int64).reshape(-1)
-        pairs = seg.numel() if pairs is None else int(pairs)
-        stride = int(stride)
-        if pairs < 1 or seg.numel() != pairs:
-            raise RuntimeError("epipolar_score_by_pair: counts must hold one int64 per pair")
-        if stride < 1 or pairs * stride > cap:
-            raise RuntimeError("epipolar_score_by_pair: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (stride, cap))
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if models.shape[0] != pairs or thr.numel() != pairs:
         raise RuntimeError("epipolar_score_by_pair: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % pairs)
     if not 1 <= H <= epipolar_max_h():
@@ -1678,35 +1723,25 @@ def epipolar_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, str
         conf = _dev(conf, "conf").reshape(-1)
         if conf.numel() != cap:
             raise RuntimeError("epipolar_score_by_pair: conf must be [cap]")
-    if norm is not None:
-        norm = _dev(norm, "norm")
-        if tuple(norm.shape) != (pairs, 8):
-            raise RuntimeError("epipolar_score_by_pair: norm must be [pairs,8]")
+    norm = _bp_norm(fn, norm, pairs)
     dev = ml.device
     want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
             ("inlier", torch.uint8, (cap,))]
     if moments:
         want.append(("moments", torch.float64, (pairs, 9, 9)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
-    if len(out) != len(want):
-        raise RuntimeError("epipolar_score_by_pair: out must be (%s)" % ", ".join(n for n, _, _ in want))
-    for t, (name, dt, shape) in zip(out, want):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RuntimeError("epipolar_score_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    out = _bp_outputs(fn, want, out, dev)
     nws = _L().pats_epipolar_workspace_bytes(pairs, H, cap)
     ws = _workspace(nws, dev) if nws else None
     inl = out[3]
-    if cap == 0:                                # empty tensors have no address; the call is valid and touches none of these
-        ml = mr = torch.empty((2,), dtype=torch.float32, device=dev)
-        inl = torch.empty((8,), dtype=torch.uint8, device=dev)
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
         conf = None if conf is None else ml
-    _check(_L().pats_epipolar_score_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(conf), _ptr(seg) if pair_off is not None else None, stride,
-                                                _ptr(seg) if pair_off is None else None, pairs, cap, _ptr(models), H, _ptr(thr),
-                                                _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
-                                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
-                                                _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream()), "epipolar_score_by_pair")
-    return tuple(out)
+    _check(_L().pats_epipolar_score_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H,
+                                                _ptr(thr), _ptr(norm), 0 if min_conf is None else 1,
+                                                0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                                _ptr(inl), _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream()), fn)
+    return out
 
 
 def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
@@ -1722,69 +1757,34 @@ def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, st
     Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 8 matches and for a sample with a non-finite
     coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,8] int32: the draws as positions inside the pair's
     list, -1 for a pair with fewer than 8 matches).  out: the destination(s), a tensor or a tuple."""
-    named = [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")]
-    i64 = ("pair_off", "counts", "seed")
-    for t, name in named:                       # layout and type first: refused the same way with or without a GPU
-        if isinstance(t, torch.Tensor) and not t.is_contiguous():
-            raise RuntimeError("epipolar_hypotheses_by_pair: %s must be contiguous" % name)
-        if isinstance(t, torch.Tensor) and t.dtype != (torch.int64 if name in i64 else torch.float32):
-            raise RuntimeError("epipolar_hypotheses_by_pair: %s must be %s, got %s" % (name, "int64" if name in i64 else "float32", t.dtype))
-    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
-        raise RuntimeError("epipolar_hypotheses_by_pair: give either pair_off, or stride and counts")
+    fn = "epipolar_hypotheses_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
     if not isinstance(seed, torch.Tensor):
         raise RuntimeError("epipolar_hypotheses_by_pair: seed must be an int64 GPU tensor [pairs]")
-    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
-    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
-        raise RuntimeError("epipolar_hypotheses_by_pair: matches_l / matches_r must be [cap,2]")
-    ml, mr = ml.reshape(-1, 2), mr.reshape(-1, 2)
-    cap, H = int(ml.shape[0]), int(H)
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    H = int(H)
     seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    if pair_off is not None:
-        seg = _dev(pair_off, "pair_off", torch.int64)
-        if seg.dim() != 1:
-            raise RuntimeError("epipolar_hypotheses_by_pair: pair_off must be an int64 vector")
-        pairs = seg.numel() - 1 if pairs is None else int(pairs)
-        if pairs < 1 or seg.numel() < pairs + 1:
-            raise RuntimeError("epipolar_hypotheses_by_pair: pair_off holds %d entries, %d pairs need %d" % (seg.numel(), pairs, pairs + 1))
-        stride = 0
-    else:
-        seg = _dev(counts, "counts", torch.int64).reshape(-1)
-        pairs = seg.numel() if pairs is None else int(pairs)
-        stride = int(stride)
-        if pairs < 1 or seg.numel() != pairs:
-            raise RuntimeError("epipolar_hypotheses_by_pair: counts must hold one int64 per pair")
-        if stride < 1 or pairs * stride > cap:
-            raise RuntimeError("epipolar_hypotheses_by_pair: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (stride, cap))
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if seed.numel() != pairs:
         raise RuntimeError("epipolar_hypotheses_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
     if not 1 <= H <= epipolar_max_h():
         raise RuntimeError("epipolar_hypotheses_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
-    if norm is not None:
-        norm = _dev(norm, "norm")
-        if tuple(norm.shape) != (pairs, 8):
-            raise RuntimeError("epipolar_hypotheses_by_pair: norm must be [pairs,8]")
+    norm = _bp_norm(fn, norm, pairs)
     dev = ml.device
     want = [("models", torch.float32, (pairs, H, 3, 3))]
     if return_samples:
         want.append(("sample_idx", torch.int32, (pairs, H, 8)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
-    elif isinstance(out, torch.Tensor):
-        out = (out,)
-    if len(out) != len(want):
-        raise RuntimeError("epipolar_hypotheses_by_pair: out must be (%s)" % ", ".join(n for n, _, _ in want))
-    for t, (name, dt, shape) in zip(out, want):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RuntimeError("epipolar_hypotheses_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    out = _bp_outputs(fn, want, out, dev, lone=True)
     nws = _L().pats_epipolar_hypotheses_workspace_bytes(pairs, H)
     ws = _workspace(nws, dev) if nws else None
-    if cap == 0:                                # empty tensors have no address; the call is valid and reads neither
-        ml = mr = torch.empty((2,), dtype=torch.float32, device=dev)
-    _check(_L().pats_epipolar_hypotheses_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(seg) if pair_off is not None else None, stride,
-                                                     _ptr(seg) if pair_off is None else None, pairs, cap, H, _ptr(seed), _ptr(norm),
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+    _check(_L().pats_epipolar_hypotheses_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
                                                      1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
-                                                     _ptr(ws), nws, _stream()), "epipolar_hypotheses_by_pair")
-    return tuple(out) if return_samples else out[0]
+                                                     _ptr(ws), nws, _stream()), fn)
+    return out if return_samples else out[0]
 
 
 def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
@@ -1800,45 +1800,20 @@ def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None
     choice [pairs] int32), then front [cap] uint8 with return_front=True, then e_refit [pairs,9] float64 with return_refit=True.
     A pair without a pose (best_count < 8, a non-finite moment, a refit of rank below 2) has E = 0, R = I, t = 0 and no count.
     out: the destinations, in that order."""
-    named = [(matches_l, "matches_l"), (matches_r, "matches_r"), (inlier, "inlier"), (best_count, "best_count"), (moments, "moments"),
-             (models, "models"), (best, "best"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")]
-    types = {"inlier": torch.uint8, "best_count": torch.int64, "moments": torch.float64, "best": torch.int32, "pair_off": torch.int64,
-             "counts": torch.int64}
-    for t, name in named:                       # layout and type first: refused the same way with or without a GPU
-        if isinstance(t, torch.Tensor) and not t.is_contiguous():
-            raise RuntimeError("epipolar_pose_by_pair: %s must be contiguous" % name)
-        want_t = types.get(name, torch.float32)
-        if isinstance(t, torch.Tensor) and t.dtype != want_t:
-            raise RuntimeError("epipolar_pose_by_pair: %s must be %s, got %s" % (name, str(want_t).replace("torch.", ""), t.dtype))
-    if (pair_off is None) == (counts is None) or (stride is None) != (counts is None):
-        raise RuntimeError("epipolar_pose_by_pair: give either pair_off, or stride and counts")
+    fn = "epipolar_pose_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (inlier, "inlier"), (best_count, "best_count"),
+                    (moments, "moments"), (models, "models"), (best, "best"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")],
+               {"inlier": torch.uint8, "best_count": torch.int64, "moments": torch.float64, "best": torch.int32, "pair_off": torch.int64,
+                "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
     if moments is None and (models is None or best is None):
         raise RuntimeError("epipolar_pose_by_pair: give moments, or models and best")
-    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
-    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
-        raise RuntimeError("epipolar_pose_by_pair: matches_l / matches_r must be [cap,2]")
-    ml, mr = ml.reshape(-1, 2), mr.reshape(-1, 2)
-    cap = int(ml.shape[0])
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
     inl = _dev(inlier, "inlier", torch.uint8).reshape(-1)
     if inl.numel() != cap:
         raise RuntimeError("epipolar_pose_by_pair: inlier must be [cap]")
     bc = _dev(best_count, "best_count", torch.int64).reshape(-1)
-    if pair_off is not None:
-        seg = _dev(pair_off, "pair_off", torch.int64)
-        if seg.dim() != 1:
-            raise RuntimeError("epipolar_pose_by_pair: pair_off must be an int64 vector")
-        pairs = seg.numel() - 1 if pairs is None else int(pairs)
-        if pairs < 1 or seg.numel() < pairs + 1:
-            raise RuntimeError("epipolar_pose_by_pair: pair_off holds %d entries, %d pairs need %d" % (seg.numel(), pairs, pairs + 1))
-        stride = 0
-    else:
-        seg = _dev(counts, "counts", torch.int64).reshape(-1)
-        pairs = seg.numel() if pairs is None else int(pairs)
-        stride = int(stride)
-        if pairs < 1 or seg.numel() != pairs:
-            raise RuntimeError("epipolar_pose_by_pair: counts must hold one int64 per pair")
-        if stride < 1 or pairs * stride > cap:
-            raise RuntimeError("epipolar_pose_by_pair: stride = %d: pairs * stride must lie in 1 .. cap = %d" % (stride, cap))
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if bc.numel() != pairs:
         raise RuntimeError("epipolar_pose_by_pair: best_count must hold one int64 per pair (%d), got %d" % (pairs, bc.numel()))
     H = 1
@@ -1854,10 +1829,7 @@ def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None
         H = int(models.shape[1])
         if not 1 <= H <= epipolar_max_h():
             raise RuntimeError("epipolar_pose_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
-    if norm is not None:
-        norm = _dev(norm, "norm")
-        if tuple(norm.shape) != (pairs, 8):
-            raise RuntimeError("epipolar_pose_by_pair: norm must be [pairs,8]")
+    norm = _bp_norm(fn, norm, pairs)
     dev = ml.device
     want = [("E", torch.float64, (pairs, 3, 3)), ("R", torch.float64, (pairs, 3, 3)), ("t", torch.float64, (pairs, 3)),
             ("front_count", torch.int64, (pairs,)), ("front_counts", torch.int32, (pairs, 4)), ("choice", torch.int32, (pairs,))]
@@ -1865,27 +1837,20 @@ def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None
         want.append(("front", torch.uint8, (cap,)))
     if return_refit:
         want.append(("e_refit", torch.float64, (pairs, 9)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dt, device=dev) for _, dt, shape in want)
-    if len(out) != len(want):
-        raise RuntimeError("epipolar_pose_by_pair: out must be (%s)" % ", ".join(n for n, _, _ in want))
-    for t, (name, dt, shape) in zip(out, want):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RuntimeError("epipolar_pose_by_pair: %s must be a contiguous GPU %s tensor of shape %s" % (name, dt, list(shape)))
+    out = _bp_outputs(fn, want, out, dev)
     nws = _L().pats_epipolar_pose_workspace_bytes(pairs, cap)
     ws = _workspace(nws, dev) if nws else None
     front = out[6] if return_front else None
     refit = out[-1] if return_refit else None
-    if cap == 0:                                # empty tensors have no address; the call is valid and touches none of these
-        ml = mr = torch.empty((2,), dtype=torch.float32, device=dev)
-        inl = torch.empty((8,), dtype=torch.uint8, device=dev)
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
         front = None
-    _check(_L().pats_epipolar_pose_by_pair_f64(_ptr(ml), _ptr(mr), _ptr(inl), _ptr(seg) if pair_off is not None else None, stride,
-                                               _ptr(seg) if pair_off is None else None, pairs, cap, _ptr(bc), _ptr(moments), _ptr(models),
-                                               H, _ptr(best), _ptr(norm), 1 if swapped else 0, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                               _ptr(out[4]), _ptr(out[5]), _ptr(out[3]), _ptr(front), _ptr(refit), _ptr(ws), nws,
-                                               _stream()), "epipolar_pose_by_pair")
-    return tuple(out)
+    _check(_L().pats_epipolar_pose_by_pair_f64(_ptr(ml), _ptr(mr), _ptr(inl), off_p, stride, counts_p, pairs, cap, _ptr(bc),
+                                               _ptr(moments), _ptr(models), H, _ptr(best), _ptr(norm), 1 if swapped else 0, _ptr(out[0]),
+                                               _ptr(out[1]), _ptr(out[2]), _ptr(out[4]), _ptr(out[5]), _ptr(out[3]), _ptr(front),
+                                               _ptr(refit), _ptr(ws), nws, _stream()), fn)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
