@@ -798,8 +798,9 @@ int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches
  * Per-pair hypotheses (ABI 8, symbols added): the H candidate models pats_epipolar_score_by_pair_f32 tests, generated on the
  * device - for every pair p and every h in 0 .. H-1 eight distinct matches of the pair are drawn and the unit null vector of their
  * 8x9 epipolar constraint matrix (the 8-point algorithm's linear step) is written as a row-major 3x3 model.  One launch, no host
- * read, deterministic: the draws come from a counter-based generator that a host reproduces exactly.  Not here: 5- and 7-point
- * minimal solvers, the rank-2 / essential projection of a hypothesis, cheirality and pose, local optimisation, adaptive termination.
+ * read, deterministic: the draws come from a counter-based generator that a host reproduces exactly.  Not here: a 7-point solver
+ * (the 5-point one is pats_epipolar_hypotheses5_by_pair_f32 below), the rank-2 / essential projection of a hypothesis, cheirality and
+ * pose, local optimisation, adaptive termination.
  * Inputs
  *   matches_l, matches_r [cap,2] float32 and the segment of pair p - ragged (pair_off) or strided (stride, counts_in), exactly ONE
  *              of the two forms (both or neither: refused) - as for pats_epipolar_score_by_pair_f32, with the same clamping:
@@ -846,13 +847,64 @@ int pats_epipolar_hypotheses_by_pair_f32(const float* matches_l, const float* ma
                                          size_t workspace_bytes, pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pair 5-point hypotheses (ABI 8, symbols added): the calibrated sibling of the per-pair hypotheses above - for every pair p and
+ * every sample h in 0 .. H-1 FIVE distinct matches of the pair are drawn and the real essential matrices through them, at most ten,
+ * are written as row-major 3x3 models.  What cv2.findEssentialMat's RANSAC solves per sample.  One launch, no host read, no
+ * workspace, deterministic.  The points must be calibrated: norm carries the intrinsics ((c, s) = (principal point, 1 / focal
+ * length) per side); without norm the solver runs on (p0, p1, 1) as if those were calibrated coordinates.
+ * What it is not: a 7-point solver, cheirality and pose (pats_epipolar_pose_by_pair_f64), local optimisation, adaptive termination.
+ *   x          the verification's point, formed exactly as there: ((p0 - c0) * s0, (p1 - c1) * s1, 1) in float32 - one subtract,
+ *              then one multiply, never contracted - or (p0, p1, 1) without norm.  The segment of pair p (n rows from lo on) in the
+ *              same two forms, ragged (pair_off) or strided (stride, counts_in), with the same clamping as above
+ *   pool       m_h = n (progressive == 0)  or  max(5, (n (h + 1) + H - 1) / H)  in int64 arithmetic
+ *   sampler    the one above with five draws: k = mix(mix(mix(s_lo) ^ s_hi) + h),  u_t = mix(k + 0x9e3779b9 (t + 1)),
+ *              j_t = (uint64(u_t) (m_h - t)) >> 32,  t = 0 .. 4,  draw t = the j_t-th index of 0 .. m_h - 1 not drawn before
+ *   sample_idx [pairs,H,5] int32 (optional: null skips it), the draws in draw order;  -1 for n < 5
+ *   solutions  A5 [5,9], row t = vec(x_r x_l^T) of draw t (q[3i + j] = x_r[i] x_l[j]).  A solution is a 3x3 E, |E|_F = 1, with
+ *              A5 vec(E) = 0 and 2 E E^T E - tr(E E^T) E = 0 (hence det E = 0): the real essential matrices through the five
+ *              matches, at most 10
+ *   models     [pairs,H,10,3,3] float32, row-major.  The solutions found occupy the lowest slots of their sample, every other slot
+ *              is nine exact zeros.  Each non-zero model has the component of largest magnitude positive (the lowest index among
+ *              equals, judged on the values written: the hypotheses' convention).  The non-zero models of a sample are pairwise
+ *              distinct, 1 - |<a, b>| > 1e-6: where two roots lie closer (a sample at the edge between k and k + 2 real
+ *              solutions) one model stands for both.  The order among the non-zero slots is unspecified but identical from call to
+ *              call.  Viewed as [pairs, 10 H, 3, 3] it is a `models` argument of pats_epipolar_score_by_pair_f32 as it stands
+ *   n_models   [pairs,H] int32 (optional: null skips it): the number of non-zero slots
+ *   zero       all ten slots zero (n_models 0): n < 5 (sample_idx -1);  a sample with a non-finite coordinate after norm (sample_idx
+ *              still written);  a degenerate sample (a pivot of the elimination that is zero or not finite, a polynomial without a
+ *              leading term);  a sample without a real solution.  Never a NaN or an infinity
+ *   contract   every non-zero model e, promoted to float64, with A5 formed exactly from the float32 points:
+ *                | |e| - 1 | <= 1e-5
+ *                |A5 e|_2                      <= B_epi eps32 |A5|_F
+ *                |2 E E^T E - tr(E E^T) E|_F   <= B_ess eps32
+ *              The solve is float64 (null space by Householder QR, Gauss-Jordan with partial pivoting on the ten cubic
+ *              constraints, the degree-10 polynomial in z, a Sturm chain, bisection and Newton steps with fixed caps); the kernel
+ *              evaluates the third residual itself, in float64 on the float32 values it is about to store, and writes NOTHING for
+ *              a root whose residual exceeds 4 eps32 (rounding an exact solution to float32 costs at most 3): an ill-conditioned
+ *              root is dropped, never emitted.  So every non-zero model is a solution of the sample's problem to working accuracy;
+ *              completeness is a tested share (docs/parity.md), not a pointwise promise.  The tests hold B_epi and B_ess to 8
+ *              times what a float64 LAPACK solve, rounded to float32, reaches on the same samples
+ *   limits     1 <= H and 10 H <= pats_epipolar_max_h()
+ * Outputs - every call defines every byte of all three.  cap == 0 is a valid call (every model zero; the match pointers must still
+ * be non-null).  Refused before any launch (pats_last_error names the argument): what pats_epipolar_hypotheses_by_pair_f32 refuses,
+ * n_models off 4 bytes, 10 H > max_h (the message names H), a grid of 2^31 workgroups or more (pairs * ceil(H / 64)); a workspace
+ * smaller than pats_epipolar_hypotheses5_workspace_bytes (0 today: a sample lives in its thread's registers and 1888 bytes of LDS;
+ * workspace may then be null).  PATS_ERR_UNSUPPORTED if the device does not grant a workgroup its 120832 bytes of LDS. */
+size_t pats_epipolar_hypotheses5_workspace_bytes(int64_t pairs, int64_t H);
+int pats_epipolar_hypotheses5_by_pair_f32(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                          const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
+                                          const float* norm, int progressive, float* models, int32_t* sample_idx, int32_t* n_models,
+                                          void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pair relative pose (ABI 8, symbols added): from the inliers pats_epipolar_score_by_pair_f32 marked to (R, t) per pair - the
  * least-squares refit of the winner's moments, its projection onto the essential matrices, the four decompositions and the
  * cheirality vote that picks one.  What findEssentialMat's last step and recoverPose do after a hypothesise-and-verify search, on
  * the device, no host read.  The returned E, cast to float32, is a valid unit model: fed back as an H = 1 model it gives the local-
  * optimisation round (pose -> verify -> moments -> pose).
  * What it is not: there is no distance threshold on the triangulated points (the reference passes 1e9 to recoverPose: effectively
- * none), no 5-point solver, no pose-error metric, and nothing in pipeline.forward_* or the drop-in calls it.
+ * none), no minimal solver (the 5-point hypotheses are pats_epipolar_hypotheses5_by_pair_f32 above), no pose-error metric, and
+ * nothing in pipeline.forward_* or the drop-in calls it.
  * Inputs
  *   matches_l, matches_r [cap,2] float32, the segment of pair p - ragged (pair_off) or strided (stride, counts_in), exactly ONE of
  *              the two forms - and norm [pairs,8] float32 (optional): as for pats_epipolar_score_by_pair_f32, with the same clamping

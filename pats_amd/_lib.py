@@ -238,6 +238,10 @@ SIGNATURES = {
     "pats_epipolar_hypotheses_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pats_epipolar_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
                                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair 5-point hypotheses: up to ten essential matrices per sample (csrc/hypotheses5.hip)
+    "pats_epipolar_hypotheses5_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_epipolar_hypotheses5_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
+                                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     # per-pair relative pose from the verified inliers (csrc/pose.hip)
     "pats_epipolar_pose_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pats_epipolar_pose_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,

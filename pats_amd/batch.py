@@ -483,18 +483,11 @@ def split_topk_by_pair(out, cap):
     return _caller_order(out, cap, per_slot)
 
 
-def hypothesize_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
-    """Device side, after the matching: H 8-point hypotheses per pair (ops.epipolar_hypotheses_by_pair: one launch, no host read) -
-    the `models` of verify_by_pair.  on="topk": drawn from the rows of a prior topk_by_pair result (strided form); on="all": from
-    the regrouped full lists (regroups first if the result is not grouped yet, as verify_by_pair does).  progressive (default: on ==
-    "topk"): hypothesis h draws from the first max(8, ceil(n (h + 1) / H)) matches of the pair's list, the most confident ones of a
-    top-K.  seed: a Python int; pair i of the CALLER's order gets pair_seed = seed + i (int64, wrapping), built on the device once
-    per seed and kept in the result - a pair's hypotheses do not depend on its slot in a mixed pack.  norm [pairs,8] or None, in the
-    caller's order (permuted to slot order on the device, as verify_by_pair does).
-    Returns models [pairs,H,3,3] float32 - or (models, sample_idx [pairs,H,8] int32) with samples=True - in the CALLER's order: they
-    go straight into verify_by_pair(out, cap, models, thr, norm=norm, on=...).  Adds `hypotheses` (what is returned) to the result;
-    the matches, the regrouped lists and a top-K of the same step are not touched."""
-    _check_on("hypothesize_by_pair", out, on)
+def _sample_by_pair(fn, generate, out, cap, H, seed, norm, on, progressive, samples):
+    """What hypothesize_by_pair and hypothesize5_by_pair share: the order handling, the per-pair seeds (pair i of the CALLER's order
+    gets seed + i, built on the device once per seed and kept in the result), the permutation of norm to slot order and of the
+    results back to the caller's.  generate = the ops function."""
+    _check_on(fn, out, on)
     if progressive is None:
         progressive = on == "topk"
     dev = out["matches_l"].device
@@ -507,11 +500,41 @@ def hypothesize_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=N
     if mixed and norm is not None:
         norm = norm.index_select(0, _caller_of_dev(out, dev))
     ml, mr, _, seg = _lists_on(out, cap, on)
-    hyp = ops.epipolar_hypotheses_by_pair(ml, mr, H, pair_seed, norm=norm, progressive=progressive, return_samples=samples, **seg)
+    hyp = generate(ml, mr, H, pair_seed, norm=norm, progressive=progressive, return_samples=samples, **seg)
     if mixed:                                                             # slots back to the caller's order
         back = _slot_of_dev(out, cap, dev)
         hyp = tuple(t.index_select(0, back) for t in hyp) if samples else hyp.index_select(0, back)
+    return hyp
+
+
+def hypothesize_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
+    """Device side, after the matching: H 8-point hypotheses per pair (ops.epipolar_hypotheses_by_pair: one launch, no host read) -
+    the `models` of verify_by_pair.  on="topk": drawn from the rows of a prior topk_by_pair result (strided form); on="all": from
+    the regrouped full lists (regroups first if the result is not grouped yet, as verify_by_pair does).  progressive (default: on ==
+    "topk"): hypothesis h draws from the first max(8, ceil(n (h + 1) / H)) matches of the pair's list, the most confident ones of a
+    top-K.  seed: a Python int; pair i of the CALLER's order gets pair_seed = seed + i (int64, wrapping), built on the device once
+    per seed and kept in the result - a pair's hypotheses do not depend on its slot in a mixed pack.  norm [pairs,8] or None, in the
+    caller's order (permuted to slot order on the device, as verify_by_pair does).
+    Returns models [pairs,H,3,3] float32 - or (models, sample_idx [pairs,H,8] int32) with samples=True - in the CALLER's order: they
+    go straight into verify_by_pair(out, cap, models, thr, norm=norm, on=...).  Adds `hypotheses` (what is returned) to the result;
+    the matches, the regrouped lists and a top-K of the same step are not touched."""
+    hyp = _sample_by_pair("hypothesize_by_pair", ops.epipolar_hypotheses_by_pair, out, cap, H, seed, norm, on, progressive, samples)
     out["hypotheses"] = hyp
+    return hyp
+
+
+def hypothesize5_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
+    """Device side, after the matching: H 5-point samples per pair, each solved for the up to ten essential matrices through it
+    (ops.epipolar_hypotheses5_by_pair: one launch, no host read).  on, progressive (the pool's minimum is 5 here), seed and norm
+    exactly as hypothesize_by_pair takes them - and norm must carry the intrinsics: the solver works in calibrated coordinates.
+    Returns models [pairs,10*H,3,3] float32 - or (models, sample_idx [pairs,H,5] int32) with samples=True - in the CALLER's order:
+    sample h owns rows 10 h .. 10 h + 9, its solutions first, zero models (which verification ignores) behind.  They go straight
+    into verify_by_pair(out, cap, models, thr, norm=norm, on=...).  Adds `hypotheses5` (what is returned) to the result;
+    `hypotheses`, the matches, the regrouped lists and a top-K of the same step are not touched."""
+    hyp = _sample_by_pair("hypothesize5_by_pair", ops.epipolar_hypotheses5_by_pair, out, cap, H, seed, norm, on, progressive, samples)
+    flat = (hyp[0] if samples else hyp).flatten(1, 2)                     # [pairs,H,10,3,3] -> [pairs,10 H,3,3]: a view
+    hyp = (flat, hyp[1]) if samples else flat
+    out["hypotheses5"] = hyp
     return hyp
 
 

@@ -1,5 +1,6 @@
-// What the per-pair epipolar stages share (epipolar.hip: verification; hypotheses.hip: the 8-point hypotheses; pose.hip: the pose):
-// how a pair's segment of the match lists, its normalisation and a match's point are read.  include/pats_amd.h states both.
+// What the per-pair epipolar stages share (epipolar.hip: verification; hypotheses.hip: the 8-point hypotheses; hypotheses5.hip: the
+// 5-point hypotheses; pose.hip: the pose): how a pair's segment of the match lists, its normalisation and a match's point are read,
+// and the hypotheses' sampler.  include/pats_amd.h states all of it.
 #pragma once
 #include "common.hpp"
 
@@ -49,6 +50,37 @@ __device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const fl
     if (gate) ok = ok && conf[i] >= min_conf;           // false for a NaN confidence
     l1 = a.y; r0 = b.x; r1 = b.y;
     if (ok) l0 = a.x;
+}
+
+// ---- the hypotheses' sampler (include/pats_amd.h, "Per-pair hypotheses"): uint32 arithmetic that wraps ------------------------
+__device__ __forceinline__ uint32_t epi_mix(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// K draws of hypothesis h out of 0 .. m - 1 (K <= m) without replacement and without a rejection loop, in draw order: draw t takes
+// the j_t-th index not drawn before, found by walking the earlier draws in ascending order (a sorted register array kept by
+// insertion; every index below is a constant once the loops are unrolled)
+template <int K>
+__device__ __forceinline__ void epi_draw(uint64_t seed, uint32_t h, uint32_t m, uint32_t (&idx)[K]) {
+    const uint32_t key = epi_mix(epi_mix(epi_mix((uint32_t)seed) ^ (uint32_t)(seed >> 32)) + h);
+    uint32_t srt[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const uint32_t u = epi_mix(key + 0x9e3779b9u * (uint32_t)(t + 1));
+        uint32_t j = (uint32_t)(((uint64_t)u * (uint64_t)(m - (uint32_t)t)) >> 32);        // < m - t
+#pragma unroll
+        for (int i = 0; i < t; ++i) j += srt[i] <= j ? 1u : 0u;                            // the j-th index not drawn before: < m
+        idx[t] = j;
+        srt[t] = j;
+#pragma unroll
+        for (int i = t - 1; i >= 0; --i) {
+            const uint32_t lo_ = srt[i] < srt[i + 1] ? srt[i] : srt[i + 1], hi_ = srt[i] < srt[i + 1] ? srt[i + 1] : srt[i];
+            srt[i] = lo_; srt[i + 1] = hi_;
+        }
+    }
 }
 
 // ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name) ------

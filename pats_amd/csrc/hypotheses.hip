@@ -5,8 +5,7 @@
 //
 //   one THREAD per hypothesis, 64 threads per workgroup, grid = pairs x ceil(H / 64).  Everything a thread holds is indexed
 //   statically (every loop below is unrolled to constants), so the 9x8 matrix lives in registers: no scratch, no LDS.
-//   sampler  eight draws without replacement and without a rejection loop: draw t takes the j_t-th index not drawn before, found by
-//            walking the earlier draws in ascending order (a sorted register array kept by insertion)
+//   sampler  eight draws without replacement and without a rejection loop (epi_draw of epipolar.hpp, shared with hypotheses5.hip)
 //   solve    Householder QR of A^T (9x8, column t = vec(x_r x_l^T) of draw t), no pivoting: the reflectors stay below the
 //            diagonal, R on and above it.  The null vector is the last column of Q = H_0 .. H_7 e_8 - orthogonal to every column of
 //            A^T whatever its rank, so a degenerate sample still gives a finite unit vector.  No component is pinned
@@ -21,13 +20,6 @@
 namespace pats {
 
 constexpr int HYP_THREADS = 64;                        // hypotheses per workgroup: one wave
-
-__device__ __forceinline__ uint32_t hyp_mix(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
 
 // z <- H_0 H_1 .. H_7 z with the reflectors H_k = I - tau_k v_k v_k^T, v_k = (1, M[k+1..8][k]) on rows k .. 8
 __device__ __forceinline__ void hyp_apply_q(const float (&M)[9][8], const float (&tau)[8], float (&z)[9]) {
@@ -86,23 +78,8 @@ epipolar_hypotheses_kernel(const float* __restrict__ ml_, const float* __restric
         const int64_t q = ((int64_t)n * (h + 1) + H - 1) / H;
         m = q < 8 ? 8u : (q > (int64_t)n ? n : (uint32_t)q);
     }
-    const uint64_t seed = (uint64_t)pair_seed[p];
-    const uint32_t key = hyp_mix(hyp_mix(hyp_mix((uint32_t)seed) ^ (uint32_t)(seed >> 32)) + (uint32_t)h);
-    uint32_t idx[8], srt[8];                            // the draws in draw order and in ascending order
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const uint32_t u = hyp_mix(key + 0x9e3779b9u * (uint32_t)(t + 1));
-        uint32_t j = (uint32_t)(((uint64_t)u * (uint64_t)(m - (uint32_t)t)) >> 32);        // < m - t
-#pragma unroll
-        for (int i = 0; i < t; ++i) j += srt[i] <= j ? 1u : 0u;                            // the j-th index not drawn before: < m
-        idx[t] = j;
-        srt[t] = j;
-#pragma unroll
-        for (int i = t - 1; i >= 0; --i) {
-            const uint32_t lo_ = srt[i] < srt[i + 1] ? srt[i] : srt[i + 1], hi_ = srt[i] < srt[i + 1] ? srt[i + 1] : srt[i];
-            srt[i] = lo_; srt[i + 1] = hi_;
-        }
-    }
+    uint32_t idx[8];                                    // the draws in draw order (epipolar.hpp: the sampler)
+    epi_draw<8>((uint64_t)pair_seed[p], (uint32_t)h, m, idx);
     if (so) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) so[t] = (int32_t)idx[t];

@@ -1787,6 +1787,51 @@ def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, st
     return out if return_samples else out[0]
 
 
+def epipolar_hypotheses5_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
+                                 return_samples=False, return_counts=False, out=None, pairs=None):
+    """H 5-point samples per pair, ON THE DEVICE, one launch, no host read (pats_epipolar_hypotheses5_by_pair_f32;
+    include/pats_amd.h holds the definition): for every pair and every h five distinct matches of the pair are drawn by the
+    hypotheses' counter-based generator and the real essential matrices through them - at most ten - are written as row-major 3x3
+    unit models into the sample's lowest slots, exact zeros behind them.  The arguments are those of epipolar_hypotheses_by_pair;
+    10 * H may not exceed epipolar_max_h().  The models live in the frame of the normalised points: norm must carry the intrinsics.
+    progressive: sample h draws from the first max(5, ceil(n (h + 1) / H)) matches of the pair's list instead of all n.
+    Returns models [pairs,H,10,3,3] float32 - models.view(pairs, 10 * H, 3, 3) is a `models` of epipolar_score_by_pair; all ten
+    slots zero for a pair with fewer than 5 matches, a sample with a non-finite coordinate and a degenerate sample - or a tuple
+    (models[, sample_idx [pairs,H,5] int32 with return_samples=True: the draws as positions inside the pair's list, -1 for a pair
+    with fewer than 5 matches][, n_models [pairs,H] int32 with return_counts=True: the non-zero slots]).  out: the destination(s), a
+    tensor or a tuple in that order."""
+    fn = "epipolar_hypotheses5_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("epipolar_hypotheses5_by_pair: seed must be an int64 GPU tensor [pairs]")
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    H = int(H)
+    seed = _dev(seed, "seed", torch.int64).reshape(-1)
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if seed.numel() != pairs:
+        raise RuntimeError("epipolar_hypotheses5_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h() // 10:
+        raise RuntimeError("epipolar_hypotheses5_by_pair: H = %d, must lie in 1 .. %d (10 H models)" % (H, epipolar_max_h() // 10))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("models", torch.float32, (pairs, H, 10, 3, 3))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, 5)))
+    if return_counts:
+        want.append(("n_models", torch.int32, (pairs, H)))
+    out = _bp_outputs(fn, want, out, dev, lone=True)
+    nws = _L().pats_epipolar_hypotheses5_workspace_bytes(pairs, H)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+    _check(_L().pats_epipolar_hypotheses5_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
+                                                      1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
+                                                      _ptr(out[-1]) if return_counts else None, _ptr(ws), nws, _stream()), fn)
+    return out if len(out) > 1 else out[0]
+
+
 def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
                           counts=None, norm=None, swapped=False, return_front=False, return_refit=False, out=None, pairs=None):
     """Each pair's relative pose from its verified inliers, ON THE DEVICE, no host read (pats_epipolar_pose_by_pair_f64;
