@@ -162,6 +162,15 @@ def _round4(x, clamp96):
     return torch.round(x / 4.0).long() * 4
 
 
+def _coarse_tail(lefts, rights, nets, iters, H, W):
+    """The first layer's tail (first_layer.py:110-127) for pairs of ONE grid: nets.coarse, cost + OT, column mass, area expansion
+    -> est_position_first's (trust, pts, xs, ys, ifn1, ifn2)."""
+    mdesc0, mdesc1, scale, alpha = nets.coarse(lefts, rights)
+    Z = ops.cost_ot(mdesc0, mdesc1, 1, alpha, scale, iters)
+    scales, cflag = ops.colmass_sqrt(Z, return_flags=True)
+    return ops.est_position_first(Z, scales, (H, W), 32, col_nomatch=cflag)
+
+
 def coarse_stage(lefts, rights, nets, cap, iters=100, fine_inputs=True, crop_format=None):
     """(fine_inputs="rows_only": stop after the row table - capacity planning.)
     The first layer's tail for all pairs + the chunk plan / row table + the crops (first_layer.py:110-146,
@@ -171,10 +180,7 @@ def coarse_stage(lefts, rights, nets, cap, iters=100, fine_inputs=True, crop_for
     H, W = int(lefts.shape[1]), int(lefts.shape[2])
     h, w = cap.h, cap.w
     assert (H // 32, W // 32) == (h, w) and lefts.shape[0] == cap.pairs
-    mdesc0, mdesc1, scale, alpha = nets.coarse(lefts, rights)
-    Z = ops.cost_ot(mdesc0, mdesc1, 1, alpha, scale, iters)
-    scales, cflag = ops.colmass_sqrt(Z, return_flags=True)
-    trust, pts, xs, ys, ifn1, ifn2 = ops.est_position_first(Z, scales, (H, W), 32, col_nomatch=cflag)
+    trust, pts, xs, ys, ifn1, ifn2 = _coarse_tail(lefts, rights, nets, iters, H, W)
     rows = ops.chunk_rows(ifn1, h, w, cap.chunk_cap, Cmax=cap.Cmax, rows_cap=cap.rows_cap)
     if fine_inputs == "rows_only":
         return {"rows": rows, "ifn1": ifn1}
@@ -243,34 +249,29 @@ def third_stage(fs, nets, cap, if_outdoor=True, iters=100, events=None, confiden
     third level's per-match confidence (ops.third_level) carried through the scatter and the compaction beside matches_r."""
     co, rows, P = fs["co"], fs["co"]["rows"], fs["P"]
     e = _timed(events, "third")
-    if confidence:
-        m0f, m1f, label, ifm, conf = ops.third_level(fs["feat0"], fs["feat1"], fs["scale3"], fs["p_s"], fs["p_t"], outdoor=if_outdoor,
-                                                     iters=iters, count=P, return_confidence=True)
-        if e is not None:
-            e.record()
-        ifn16, pts16, conf16 = ops.refine_scatter(fs["merged"], fs["pts2"], m1f, label, conf=conf)
-        ml, mr, mrow, M, mconf = ops.get_result_chunks(rows, ifn16, co["avn"], pts16, co["xsn"], conf16=conf16)
-        stages = dict(fs["stages"], m0f=m0f, m1f=m1f, label=label, ifm=ifm, pts16=pts16, conf=conf, conf16=conf16)
-        return {"matches_l": ml, "matches_r": mr, "match_row": mrow, "match_conf": mconf, "M": M, "P": P, "status": rows.status,
-                "rows": rows, "if_nomatching16": ifn16, "merged": fs["merged"], "K_img": co["K_img"],
-                "crops": (co["new_left"], co["new_right"]), "coarse": co, "stages": stages}
-    m0f, m1f, label, ifm = ops.third_level(fs["feat0"], fs["feat1"], fs["scale3"], fs["p_s"], fs["p_t"], outdoor=if_outdoor,
-                                           iters=iters, count=P)
+    # one sequence: with confidence the calls return one tensor more (conf, conf16, match_conf), handed on to the next
+    level = ops.third_level(fs["feat0"], fs["feat1"], fs["scale3"], fs["p_s"], fs["p_t"], outdoor=if_outdoor, iters=iters, count=P,
+                            return_confidence=bool(confidence))
+    m0f, m1f, label, ifm = level[:4]
     if e is not None:
         e.record()
-    ifn16, pts16 = ops.refine_scatter(fs["merged"], fs["pts2"], m1f, label)
-    ml, mr, mrow, M = ops.get_result_chunks(rows, ifn16, co["avn"], pts16, co["xsn"])
+    scattered = ops.refine_scatter(fs["merged"], fs["pts2"], m1f, label, conf=level[4] if confidence else None)
+    ifn16, pts16 = scattered[:2]
+    result = ops.get_result_chunks(rows, ifn16, co["avn"], pts16, co["xsn"], conf16=scattered[2] if confidence else None)
+    ml, mr, mrow, M = result[:4]
     stages = dict(fs["stages"], m0f=m0f, m1f=m1f, label=label, ifm=ifm, pts16=pts16)
-    return {"matches_l": ml, "matches_r": mr, "match_row": mrow, "M": M, "P": P, "status": rows.status, "rows": rows,
-            "if_nomatching16": ifn16, "merged": fs["merged"], "K_img": co["K_img"], "crops": (co["new_left"], co["new_right"]),
-            "coarse": co, "stages": stages}
+    out = {"matches_l": ml, "matches_r": mr, "match_row": mrow}
+    if confidence:
+        stages.update(conf=level[4], conf16=scattered[2])
+        out["match_conf"] = result[4]
+    out.update(M=M, P=P, status=rows.status, rows=rows, if_nomatching16=ifn16, merged=fs["merged"], K_img=co["K_img"],
+               crops=(co["new_left"], co["new_right"]), coarse=co, stages=stages)
+    return out
 
 
 def fine_third_stage(co, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, confidence=False):
     fs = fine_stage(co, nets, cap, if_outdoor, merge_new, iters, events)
-    if confidence:
-        return third_stage(fs, nets, cap, if_outdoor, iters, events, confidence=True)
-    return third_stage(fs, nets, cap, if_outdoor, iters, events)
+    return third_stage(fs, nets, cap, if_outdoor, iters, events, confidence)
 
 
 def forward_pairs(lefts, rights, nets, cap, if_outdoor=True, merge_new=True, iters=100, events=None, crop_format=None,
@@ -298,10 +299,7 @@ def coarse_stage_mixed(pack, nets, cap, iters=100, if_local=True, crop_format=No
     row table and the crops in ONE launch set over the whole batch (ops.chunk_rows_ragged, ops.Compute_imgs_ragged)."""
     ifn1, xs, ys, pts = [], [], [], []
     for lo, hi, h, w, lefts, rights in pack.groups:
-        mdesc0, mdesc1, scale, alpha = nets.coarse(lefts, rights)
-        Z = ops.cost_ot(mdesc0, mdesc1, 1, alpha, scale, iters)
-        scales, cflag = ops.colmass_sqrt(Z, return_flags=True)
-        _, p_, x_, y_, f_, _ = ops.est_position_first(Z, scales, (32 * h, 32 * w), 32, col_nomatch=cflag)
+        _, p_, x_, y_, f_, _ = _coarse_tail(lefts, rights, nets, iters, 32 * h, 32 * w)
         ifn1.append(f_.reshape(-1))
         xs.append(x_.reshape(-1))
         ys.append(y_.reshape(-1))
@@ -341,14 +339,9 @@ def group_by_pair(out, cap, buffers=None, confidence=False):
     pair_off, conf) and `buffers` may carry conf's destination as a fourth tensor."""
     if confidence and "match_conf" not in out:
         raise ValueError("group_by_pair: confidence=True needs a result made with confidence=True")
-    if "match_conf" in out:
-        ml, mr, off, summary, mc = ops.matches_by_pair(out["rows"], out["matches_l"], out["matches_r"], out["match_row"], out["M"],
-                                                       out=buffers, P=out["P"], match_conf=out["match_conf"])
-        out["by_pair"], out["summary"] = (ml, mr, off, mc), summary
-        return out["by_pair"]
-    ml, mr, off, summary = ops.matches_by_pair(out["rows"], out["matches_l"], out["matches_r"], out["match_row"], out["M"], out=buffers,
-                                               P=out["P"])
-    out["by_pair"], out["summary"] = (ml, mr, off), summary
+    got = ops.matches_by_pair(out["rows"], out["matches_l"], out["matches_r"], out["match_row"], out["M"], out=buffers, P=out["P"],
+                              match_conf=out.get("match_conf"))
+    out["by_pair"], out["summary"] = got[:3] + got[4:], got[3]          # got = (matches_l, matches_r, pair_off, summary[, conf])
     return out["by_pair"]
 
 
@@ -427,12 +420,8 @@ def split_by_pair(out, cap):
         group_by_pair(out, cap)
     o = out["summary"].cpu().tolist()                 # the one synchronisation of a batch: offsets, M, P, status in one copy
     _overflow_check(o, cap)
-    if len(out["by_pair"]) > 3:
-        ml, mr, _, mc = out["by_pair"]
-        per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]], mc[o[p]:o[p + 1]]) for p in range(cap.pairs)]
-    else:
-        ml, mr, _ = out["by_pair"]
-        per_slot = [(ml[o[p]:o[p + 1]], mr[o[p]:o[p + 1]]) for p in range(cap.pairs)]
+    lists = out["by_pair"][:2] + out["by_pair"][3:]           # (matches_l, matches_r[, conf]): pair_off left out
+    per_slot = [tuple(t[o[p]:o[p + 1]] for t in lists) for p in range(cap.pairs)]
     return _caller_order(out, cap, per_slot)
 
 

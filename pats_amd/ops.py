@@ -746,7 +746,6 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
     H, W = leftf.shape[1], leftf.shape[2]
     on_device = isinstance(known_count, str) and known_count == "device"
     lfmt, rfmt, left_to = _crop_formats(crop_format, code, None if on_device else left.dtype)
-    typed = code != 0 or not lfmt.is_default() or not rfmt.is_default()
     lout, rout = (None, None) if out is None else out
     counts = None
     if known_count is not None and not on_device:
@@ -755,29 +754,12 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
         counts = [int(k) for k in np.atleast_1d(np.asarray(known_count)).ravel()]
         if len(counts) != nb:
             raise RuntimeError("Compute_imgs: known_count needs one entry per image")
-    bound5 = torch.empty((nb * Np, 5), dtype=torch.int64, device=dev)
-    Kd = torch.empty((nb,), dtype=torch.int64, device=dev)
-    Kt = torch.empty((1,), dtype=torch.int64, device=dev)
-    xsn = torch.empty((nb, Np, 2), dtype=torch.float32, device=dev)
-    ysn = torch.empty((nb, Np, 2), dtype=torch.float32, device=dev)
-    avn = torch.empty((nb, Np, 2), dtype=torch.float32, device=dev)
     # all images in one launch: block i offsets its compacted bounds by the matches of the images before it
-    _check(_L().pats_compute_imgs_bounds_batch_f32(_ptr(xs), _ptr(ys), _ptr(ap), _ptr(ifn), nb, Np, height, width,
-                                                   _ptr(bound5), _ptr(Kd), _ptr(Kt), _ptr(xsn), _ptr(ysn), _ptr(avn),
-                                                   _stream()), "Compute_imgs(bounds)")
+    bound5, Kd, Kt, xsn, ysn, avn = _imgs_bounds(None, xs, ys, ap, ifn, nb, (nb, Np), height, width)
     status = torch.zeros((1,), dtype=torch.int32, device=dev) if validate else None
     if on_device:
-        cap = nb * Np
-        new_left = _crop_out(lout, lfmt, cap, "out[0]", dev)
-        new_right = _crop_out(rout, rfmt, cap, "out[1]", dev)
-        if typed:
-            _typed_crops(None, leftf, rightf, code, nb, H, W, height, width, margin, bound5, cap, Kt, lfmt, rfmt, new_left,
-                         new_right, status)
-        else:
-            _check(_L().pats_left_crops_counted_f32(_ptr(leftf), nb, H, W, _ptr(bound5), cap, _ptr(Kt), height, width,
-                                                    _ptr(new_left), _stream()), "Compute_imgs(left)")
-            _check(_L().pats_tensor_resize_hwc_counted_f32(_ptr(rightf), nb, H, W, margin, _ptr(bound5), cap, _ptr(Kt),
-                                                           _ptr(new_right), _ptr(status), _stream()), "Compute_imgs(right)")
+        new_left, new_right = _crops(None, leftf, rightf, code, nb, H, W, height, width, margin, bound5, nb * Np, Kt, lfmt, rfmt,
+                                     lout, rout, status)
         if validate and int(status.item()) != 0:
             raise RuntimeError("Compute_imgs: a right crop is empty or outside the padded image")
         return new_left, new_right, xsn, ysn, avn, bound5, Kd, Kt
@@ -788,17 +770,8 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
         if got != counts:
             raise RuntimeError("Compute_imgs: known_count %s does not match the matched patches per image %s" % (counts, got))
     K = sum(counts)
-    new_left = _crop_out(lout if left_to is None else None, lfmt, K, "out[0]", dev)
-    new_right = _crop_out(rout, rfmt, K, "out[1]", dev)
-    if typed:
-        _typed_crops(None, leftf, rightf, code, nb, H, W, height, width, margin, bound5, K, None, lfmt, rfmt, new_left, new_right,
-                     status)
-    else:
-        _check(_L().pats_left_crops_f32(_ptr(leftf), nb, H, W, _ptr(bound5), K, height, width, _ptr(new_left),
-                                        _stream()), "Compute_imgs(left)")
-        _check(_L().pats_tensor_resize_hwc_f32(_ptr(rightf), nb, H, W, margin, _ptr(bound5), K,
-                                               _ptr(new_right), _ptr(status), _stream()),
-               "Compute_imgs(right)")
+    new_left, new_right = _crops(None, leftf, rightf, code, nb, H, W, height, width, margin, bound5, K, None, lfmt, rfmt,
+                                 lout if left_to is None else None, rout, status)
     if validate and K > 0 and int(status.item()) != 0:
         raise RuntimeError("Compute_imgs: a right crop is empty or outside the padded image")
     if left_to is not None:                 # a left image of another dtype (e.g. float64): converted back, as before
@@ -808,15 +781,57 @@ def Compute_imgs_ex(x_scale, y_scale, average_point, if_nomatching, left, right,
     return new_left, new_right, xsn, ysn, avn, bound5[:K]
 
 
-def _typed_crops(table, left, right, code, nb, H, W, height, width, margin, bound5, rows, K_dev, lfmt, rfmt, new_left, new_right,
-                 status):
-    """Both sides' crops through the typed entry points (table: a PairTable, or None for nb uniform images)."""
+def _imgs_bounds(table, xs, ys, ap, ifn, pairs, cell_ext, height=0, width=0):
+    """The crop bounds of a batch - what Compute_imgs_ex and Compute_imgs_ragged share: (bound5 [cells,5], K_img [pairs], K_total
+    [1], xsn, ysn, avn [cell_ext, 2]) allocated and written.  cell_ext: (nb, Np) for nb uniform images, (sum N,) for a PairTable."""
+    dev = xs.device
+    bound5 = torch.empty((xs.numel(), 5), dtype=torch.int64, device=dev)
+    Kd = torch.empty((pairs,), dtype=torch.int64, device=dev)
+    Kt = torch.empty((1,), dtype=torch.int64, device=dev)
+    xsn = torch.empty(cell_ext + (2,), dtype=torch.float32, device=dev)
+    ysn = torch.empty(cell_ext + (2,), dtype=torch.float32, device=dev)
+    avn = torch.empty(cell_ext + (2,), dtype=torch.float32, device=dev)
+    if table is None:
+        entry, head, grid, what = "pats_compute_imgs_bounds_batch_f32", (), (cell_ext[0], cell_ext[1], height, width), "Compute_imgs(bounds)"
+    else:
+        entry, head, grid, what = "pats_compute_imgs_bounds_ragged_f32", (table.ref(),), (), "Compute_imgs_ragged(bounds)"
+    _check(getattr(_L(), entry)(*head, _ptr(xs), _ptr(ys), _ptr(ap), _ptr(ifn), *grid, _ptr(bound5), _ptr(Kd), _ptr(Kt), _ptr(xsn),
+                                _ptr(ysn), _ptr(avn), _stream()), what)
+    return bound5, Kd, Kt, xsn, ysn, avn
+
+
+# the crop entries (left, right, what a failure names) of the float32 HWC forms; every other image dtype or format is "typed"
+_CROPS = {"typed": ("pats_left_crops_typed", "pats_tensor_resize_hwc_typed", "Compute_imgs(left)", "Compute_imgs(right)"),
+          "host": ("pats_left_crops_f32", "pats_tensor_resize_hwc_f32", "Compute_imgs(left)", "Compute_imgs(right)"),
+          "counted": ("pats_left_crops_counted_f32", "pats_tensor_resize_hwc_counted_f32", "Compute_imgs(left)", "Compute_imgs(right)"),
+          "ragged": ("pats_left_crops_ragged_f32", "pats_tensor_resize_hwc_ragged_f32", "Compute_imgs_ragged(left)",
+                     "Compute_imgs_ragged(right)")}
+
+
+def _crops(table, left, right, code, nb, H, W, height, width, margin, bound5, rows, K_dev, lfmt, rfmt, lout, rout, status):
+    """Both sides' crops of `rows` bounds (K_dev: the device count of those that exist, or None) into fresh tensors or the
+    caller's lout / rout -> (new_left, new_right).  table: a PairTable, or None for nb uniform images."""
+    dev = bound5.device
+    new_left = _crop_out(lout, lfmt, rows, "out[0]", dev)
+    new_right = _crop_out(rout, rfmt, rows, "out[1]", dev)
     tab = table.ref() if table is not None else None
-    lc, rc = lfmt._c(), rfmt._c()
-    _check(_L().pats_left_crops_typed(tab, _ptr(left), code, nb, H, W, height, width, _ptr(bound5), rows, _ptr(K_dev),
-                                      ctypes.byref(lc), _ptr(new_left), _stream()), "Compute_imgs(left)")
-    _check(_L().pats_tensor_resize_hwc_typed(tab, _ptr(right), code, nb, H, W, margin, _ptr(bound5), rows, _ptr(K_dev),
-                                             ctypes.byref(rc), _ptr(new_right), _ptr(status), _stream()), "Compute_imgs(right)")
+    if code != 0 or not lfmt.is_default() or not rfmt.is_default():
+        form, lc, rc = "typed", lfmt._c(), rfmt._c()
+        largs = (tab, _ptr(left), code, nb, H, W, height, width, _ptr(bound5), rows, _ptr(K_dev), ctypes.byref(lc), _ptr(new_left))
+        rargs = (tab, _ptr(right), code, nb, H, W, margin, _ptr(bound5), rows, _ptr(K_dev), ctypes.byref(rc), _ptr(new_right),
+                 _ptr(status))
+    elif table is not None:
+        form = "ragged"
+        largs = (tab, _ptr(left), _ptr(bound5), rows, _ptr(K_dev), _ptr(new_left))
+        rargs = (tab, _ptr(right), margin, _ptr(bound5), rows, _ptr(K_dev), _ptr(new_right), _ptr(status))
+    else:
+        form, count_arg = ("counted", (_ptr(K_dev),)) if K_dev is not None else ("host", ())
+        largs = (_ptr(left), nb, H, W, _ptr(bound5), rows, *count_arg, height, width, _ptr(new_left))
+        rargs = (_ptr(right), nb, H, W, margin, _ptr(bound5), rows, *count_arg, _ptr(new_right), _ptr(status))
+    lentry, rentry, lwhat, rwhat = _CROPS[form]
+    _check(getattr(_L(), lentry)(*largs, _stream()), lwhat)
+    _check(getattr(_L(), rentry)(*rargs, _stream()), rwhat)
+    return new_left, new_right
 
 
 # ------------------------------------------------------------------------------------------------
@@ -911,49 +926,44 @@ def third_level(feat_f0_unfold, feat_f1_unfold, scale, mkpts0_c, mkpts1_c, outdo
     ps = _dev(mkpts0_c.to(torch.int64), "mkpts0_c", torch.int64).reshape(P, 2)
     pt = _dev(mkpts1_c.to(torch.int64), "mkpts1_c", torch.int64).reshape(P, 2)
     dev = f0.device
-    if count is not None:
+    counted = count is not None
+    if counted:                     # the kernel forms sqrt(scale + 1e-8) itself and writes no plan
         if return_plan:
             raise RuntimeError("third_level: return_plan is not available with a device-side count")
-        cnt = _dev(count, "count", torch.int64).reshape(1)
-        if return_confidence:
-            m0, m1, label, ifm = _third_out(out, P, dev, 5)
-            conf = _third_conf(out, P, dev)
-            _check(_L().pats_third_level_typed_conf(_ptr(f0), _ptr(f1), code, P, _ptr(cnt), D, _ptr(sc), None, None, _ptr(ps),
-                                                    _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
-                                                    _ptr(ifm), None, _ptr(conf), _stream()), "third_level")
-            return (m0, m1, label, ifm.view(torch.bool), conf) if out is None else tuple(out[:4]) + (conf,)
-        m0, m1, label, ifm = _third_out(out, P, dev)
-        if code:
-            _check(_L().pats_third_level_typed(_ptr(f0), _ptr(f1), code, P, _ptr(cnt), D, _ptr(sc), None, None, _ptr(ps), _ptr(pt),
-                                               int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label), _ptr(ifm), None,
-                                               _stream()), "third_level")
-            return (m0, m1, label, ifm.view(torch.bool)) if out is None else tuple(out)
-        _check(_L().pats_third_level_counted_f32(_ptr(f0), _ptr(f1), P, _ptr(cnt), D, _ptr(sc), _ptr(None), _ptr(None), _ptr(ps),
-                                                 _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
-                                                 _ptr(ifm), _stream()), "third_level")
-        return (m0, m1, label, ifm.view(torch.bool)) if out is None else tuple(out)
-    sxy = torch.sqrt(sc + 1e-8)
-    Z = torch.empty((P, 65, 65), dtype=torch.float32, device=dev) if return_plan else None
-    if return_confidence:
-        m0, m1, label, ifm = _third_out(out, P, dev, 5)
-        conf = _third_conf(out, P, dev)
-        _check(_L().pats_third_level_typed_conf(_ptr(f0), _ptr(f1), code, P, None, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps),
-                                                _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
-                                                _ptr(ifm), _ptr(Z) if Z is not None else None, _ptr(conf), _stream()),
-               "third_level")
-        res = (m0, m1, label, ifm.bool()) if out is None else tuple(out[:4])
-        return res + ((Z, conf) if return_plan else (conf,))
-    m0, m1, label, ifm = _third_out(out, P, dev)
-    if code:
-        _check(_L().pats_third_level_typed(_ptr(f0), _ptr(f1), code, P, None, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps), _ptr(pt),
-                                           int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label), _ptr(ifm),
-                                           _ptr(Z) if Z is not None else None, _stream()), "third_level")
+        cnt, sxy, Z = _dev(count, "count", torch.int64).reshape(1), None, None
     else:
-        _check(_L().pats_third_level_f32(_ptr(f0), _ptr(f1), P, D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps),
-                                         _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1),
-                                         _ptr(label), _ptr(ifm), _ptr(Z), _stream()), "third_level")
-    res = (m0, m1, label, ifm.bool()) if out is None else tuple(out)
-    return res + (Z,) if return_plan else res
+        cnt, sxy = None, torch.sqrt(sc + 1e-8)
+        Z = torch.empty((P, 65, 65), dtype=torch.float32, device=dev) if return_plan else None
+    m0, m1, label, ifm = _third_out(out, P, dev, 5 if return_confidence else 4)
+    conf = _third_conf(out, P, dev) if return_confidence else None
+    # one argument list; the form picks the entry and splices in what only it takes (dtype code, count, plan, conf)
+    entry = _THIRD_LEVEL[2 if return_confidence else 1 if code else 0][counted]
+    args = [_ptr(f0), _ptr(f1)]
+    if return_confidence or code:
+        args += (code, P, _ptr(cnt))
+    elif counted:
+        args += (P, _ptr(cnt))
+    else:
+        args.append(P)
+    args += (D, _ptr(sc), _ptr(sxy), _ptr(sxy), _ptr(ps), _ptr(pt), int(iters), int(bool(outdoor)), _ptr(m0), _ptr(m1), _ptr(label),
+             _ptr(ifm))
+    if entry != "pats_third_level_counted_f32":
+        args.append(_ptr(Z))
+    if return_confidence:
+        args.append(_ptr(conf))
+    _check(getattr(_L(), entry)(*args, _stream()), "third_level")
+    if out is not None:
+        res = tuple(out[:4])
+    else:                           # the counted form hands out a view of the flags, the other a bool copy, as they always did
+        res = (m0, m1, label, ifm.view(torch.bool) if counted else ifm.bool())
+    if return_plan:
+        res += (Z,)
+    return res + (conf,) if return_confidence else res
+
+
+# third_level's entry by (0 fp32 / 1 typed / 2 typed with confidence) and [no count, device count]
+_THIRD_LEVEL = (("pats_third_level_f32", "pats_third_level_counted_f32"), ("pats_third_level_typed",) * 2,
+                ("pats_third_level_typed_conf",) * 2)
 
 
 def _widen(t):
@@ -1163,18 +1173,16 @@ def refine_scatter(if_nomatching, pts, mkpts1_f, label, conf=None):
     p16 = torch.empty((B, 2304, 2), dtype=torch.float32, device=dev)
     nws = _L().pats_compact_workspace_bytes(B * 144)
     ws = _workspace(nws, dev)
-    if conf is not None:
+    entry, cf_arg, c16_arg, res = "pats_refine_scatter_f32", (), (), (f16, p16)
+    if conf is not None:            # the confidence form: conf behind the label's stride, conf16 behind pts16
         cf = _dev(conf, "conf")
         if cf.numel() != P * 16:
             raise RuntimeError("refine_scatter: conf must be [P,16]")
         c16 = torch.empty((B, 2304), dtype=torch.float32, device=dev)
-        _check(_L().pats_refine_scatter_conf_f32(_ptr(f), _ptr(p), _ptr(mk), _ptr(lb), stride, _ptr(cf), B, P,
-                                                 _ptr(f16.view(torch.uint8)), _ptr(p16), _ptr(c16), _ptr(ws), nws, _stream()),
-               "refine_scatter")
-        return f16, p16, c16
-    _check(_L().pats_refine_scatter_f32(_ptr(f), _ptr(p), _ptr(mk), _ptr(lb), stride, B, P, _ptr(f16.view(torch.uint8)),
-                                        _ptr(p16), _ptr(ws), nws, _stream()), "refine_scatter")
-    return f16, p16
+        entry, cf_arg, c16_arg, res = "pats_refine_scatter_conf_f32", (_ptr(cf),), (_ptr(c16),), (f16, p16, c16)
+    _check(getattr(_L(), entry)(_ptr(f), _ptr(p), _ptr(mk), _ptr(lb), stride, *cf_arg, B, P, _ptr(f16.view(torch.uint8)), _ptr(p16),
+                                *c16_arg, _ptr(ws), nws, _stream()), "refine_scatter")
+    return res
 
 
 def get_result(batch_size, if_nomatching, average_point, scale, patch_size, left_choice, layer_num=2, validate=True,
@@ -1279,6 +1287,43 @@ def max_chunks(height, width, max_once_used):
     return min(height + 1, (height * width - 1) // int(max_once_used) + 1)
 
 
+def _chunk_rows_table(table, pairs, h, w, hmax, cell_ext, Cmax, rows_cap, dev):
+    """A ChunkRows with every tensor the planner writes allocated - what chunk_rows and chunk_rows_ragged share.  cell_ext: the
+    extents of a per-cell tensor, (pairs, N) for a uniform batch and (sum N,) for a ragged one (`table` its PairTable)."""
+    r = ChunkRows()
+    r.table, r.pairs, r.h, r.w, r.Cmax, r.rows_cap = table, pairs, h, w, Cmax, rows_cap
+    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
+    r.sum_cycle = torch.empty(cell_ext, dtype=i32, device=dev)
+    r.cycle_num = torch.empty((pairs,), dtype=i32, device=dev)
+    r.second = torch.empty((pairs, hmax + 1, 2), dtype=i64, device=dev)
+    r.third = torch.empty((pairs, hmax + 1, 2), dtype=i64, device=dev)
+    r.masks = torch.empty((Cmax,) + cell_ext, dtype=torch.bool, device=dev)
+    r.chunk_base = torch.empty((Cmax + 1,), dtype=i64, device=dev)
+    r.crop_base = torch.empty((pairs + 1,), dtype=i64, device=dev)
+    r.row_cell = torch.empty((rows_cap,), dtype=i32, device=dev)
+    # a ragged table is told each row's pair; a uniform one forms row_cell // N and the cell ranges on first use (ChunkRows)
+    r._row_pair = torch.empty((rows_cap,), dtype=i32, device=dev) if table is not None else None
+    r._cell_base = table.cell_base if table is not None else None
+    r.row_forced = torch.empty((rows_cap,), dtype=u8, device=dev)
+    r.row_crop = torch.empty((rows_cap,), dtype=i32, device=dev)
+    r.row_slot = torch.empty((Cmax, r.sum_cycle.numel()), dtype=i32, device=dev)
+    r.status = torch.empty((1,), dtype=i32, device=dev)
+    return r
+
+
+def _chunk_rows_plan(r, head, what):
+    """The planner's call on a _chunk_rows_table: `head` = the arguments in front of the outputs; r.row_pair goes behind row_cell
+    for a ragged table."""
+    entry, pair_arg = ("pats_chunk_rows_device", ()) if r.table is None else ("pats_chunk_rows_ragged", (_ptr(r._row_pair),))
+    dev = r.status.device
+    nws = _L().pats_chunk_rows_workspace_bytes(r.pairs, r.Cmax)
+    ws = _workspace(nws, dev)
+    _check(getattr(_L(), entry)(*head, r.Cmax, r.rows_cap, _ptr(r.sum_cycle), _ptr(r.cycle_num), _ptr(r.second), _ptr(r.third),
+                                _ptr(r.masks.view(torch.uint8)), _ptr(r.chunk_base), _ptr(r.crop_base), _ptr(r.row_cell), *pair_arg,
+                                _ptr(r.row_forced), _ptr(r.row_crop), _ptr(r.row_slot), _ptr(r.status), _ptr(ws), nws, _stream()), what)
+    return r
+
+
 def chunk_rows(if_nomatching1, height, width, max_once_used, Cmax=None, rows_cap=None):
     """first_layer.py:130-146 + pats.py:33-39 for a batch of pairs on the device: cumulative match counts, chunk plans,
     chunk masks and the fine level's row table in (chunk, pair, cell) order.  if_nomatching1 [pairs, h*w] bool."""
@@ -1286,33 +1331,10 @@ def chunk_rows(if_nomatching1, height, width, max_once_used, Cmax=None, rows_cap
     pairs, N = f.shape[0], height * width
     if f.numel() != pairs * N:
         raise RuntimeError("chunk_rows: if_nomatching1 must be [pairs, height*width]")
-    r = ChunkRows()
-    r.table = None
-    r.pairs, r.h, r.w = pairs, int(height), int(width)
-    r.Cmax = max_chunks(height, width, max_once_used) if Cmax is None else int(Cmax)
-    r.rows_cap = pairs * (N + (r.Cmax - 1) * width) if rows_cap is None else int(rows_cap)
-    dev = f.device
-    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
-    r.sum_cycle = torch.empty((pairs, N), dtype=i32, device=dev)
-    r.cycle_num = torch.empty((pairs,), dtype=i32, device=dev)
-    r.second = torch.empty((pairs, height + 1, 2), dtype=i64, device=dev)
-    r.third = torch.empty((pairs, height + 1, 2), dtype=i64, device=dev)
-    r.masks = torch.empty((r.Cmax, pairs, N), dtype=torch.bool, device=dev)
-    r.chunk_base = torch.empty((r.Cmax + 1,), dtype=i64, device=dev)
-    r.crop_base = torch.empty((pairs + 1,), dtype=i64, device=dev)
-    r.row_cell = torch.empty((r.rows_cap,), dtype=i32, device=dev)
-    r.row_forced = torch.empty((r.rows_cap,), dtype=u8, device=dev)
-    r.row_crop = torch.empty((r.rows_cap,), dtype=i32, device=dev)
-    r.row_slot = torch.empty((r.Cmax, pairs * N), dtype=i32, device=dev)
-    r.status = torch.empty((1,), dtype=i32, device=dev)
-    nws = _L().pats_chunk_rows_workspace_bytes(pairs, r.Cmax)
-    ws = _workspace(nws, dev)
-    _check(_L().pats_chunk_rows_device(_ptr(f), pairs, int(height), int(width), int(max_once_used), r.Cmax, r.rows_cap,
-                                       _ptr(r.sum_cycle), _ptr(r.cycle_num), _ptr(r.second), _ptr(r.third),
-                                       _ptr(r.masks.view(u8)), _ptr(r.chunk_base), _ptr(r.crop_base), _ptr(r.row_cell),
-                                       _ptr(r.row_forced), _ptr(r.row_crop), _ptr(r.row_slot), _ptr(r.status), _ptr(ws), nws,
-                                       _stream()), "chunk_rows")
-    return r
+    Cmax = max_chunks(height, width, max_once_used) if Cmax is None else int(Cmax)
+    rows_cap = pairs * (N + (Cmax - 1) * width) if rows_cap is None else int(rows_cap)
+    r = _chunk_rows_table(None, pairs, int(height), int(width), height, (pairs, N), Cmax, rows_cap, f.device)
+    return _chunk_rows_plan(r, (_ptr(f), pairs, int(height), int(width), int(max_once_used)), "chunk_rows")
 
 
 def merge_patches_batch(merge_new, rows, trust_score, original_image_shape, if_nomatching1_L2, scores_back=None):
@@ -1323,26 +1345,31 @@ def merge_patches_batch(merge_new, rows, trust_score, original_image_shape, if_n
         raise RuntimeError("merge_patches_batch: trust_score must be a contiguous float32 GPU tensor (it is updated in place)")
     if if_nomatching1_L2.dtype != torch.bool or not if_nomatching1_L2.is_contiguous():
         raise RuntimeError("merge_patches_batch: if_nomatching1_L2 must be a contiguous bool tensor (it is updated in place)")
-    if rows.table is not None:
-        return _merge_patches_ragged(merge_new, rows, trust_score, if_nomatching1_L2, scores_back)
-    H, W = int(original_image_shape[0]), int(original_image_shape[1])
-    if trust_score.numel() != rows.rows_cap * 144 or if_nomatching1_L2.numel() != rows.rows_cap * 144 or \
-            H // 32 != rows.h or W // 32 != rows.w:
-        raise RuntimeError("merge_patches_batch: tensors must be [rows_cap,144] on the table's grid")
+    table = rows.table
+    if table is None:
+        H, W = int(original_image_shape[0]), int(original_image_shape[1])
+        on_grid, cells, sb_shape = H // 32 == rows.h and W // 32 == rows.w, rows.pairs * rows.h * rows.w, (rows.pairs, rows.h * rows.w, 16, 9)
+        entry, what, sizer, size_args = "pats_merge_patches_batch", "merge_patches_batch", "pats_merge_batch_workspace_bytes", (rows.pairs, H, W)
+        head, pair_arg = (1 if merge_new else 0, rows.Cmax, rows.pairs, H, W, rows.rows_cap), ()
+    else:                           # ragged: the table carries the grids (original_image_shape is not read), row_pair the rows' pairs
+        on_grid, cells, sb_shape = True, table.cells, (table.cells, 16, 9)
+        entry, what, sizer, size_args = "pats_merge_patches_ragged", "merge_patches_ragged", "pats_merge_ragged_workspace_bytes", (cells,)
+        head, pair_arg = (table.ref(), 1 if merge_new else 0, rows.Cmax, rows.rows_cap), (_ptr(rows.row_pair),)
+    if trust_score.numel() != rows.rows_cap * 144 or if_nomatching1_L2.numel() != rows.rows_cap * 144 or not on_grid:
+        raise RuntimeError("merge_patches_batch: tensors must be [rows_cap,144]" + (" on the table's grid" if table is None else ""))
     dev = trust_score.device
     fresh = scores_back is None
     if fresh:
-        scores_back = torch.empty((rows.pairs, rows.h * rows.w, 16, 9), dtype=torch.float64, device=dev)   # cleared by the call
-    elif scores_back.dtype != torch.float64 or not scores_back.is_contiguous() or \
-            scores_back.numel() != rows.pairs * rows.h * rows.w * 144:
-        raise RuntimeError("merge_patches_batch: scores_back must be a contiguous float64 [pairs, N, 16, 9] tensor")
+        scores_back = torch.empty(sb_shape, dtype=torch.float64, device=dev)            # cleared by the call
+    elif scores_back.dtype != torch.float64 or not scores_back.is_contiguous() or scores_back.numel() != cells * 144:
+        raise RuntimeError("merge_patches_batch: scores_back must be a contiguous float64 [%s, 16, 9] tensor"
+                           % ("pairs, N" if table is None else "sum N"))
     out = torch.empty((rows.rows_cap, 144), dtype=torch.bool, device=dev)
-    nws = _L().pats_merge_batch_workspace_bytes(rows.pairs, H, W)
+    nws = getattr(_L(), sizer)(*size_args)
     ws = _workspace(nws, dev)
-    _check(_L().pats_merge_patches_batch(1 if merge_new else 0, rows.Cmax, rows.pairs, H, W, rows.rows_cap,
-                                         _ptr(rows.chunk_base), _ptr(rows.row_cell), _ptr(rows.row_slot), _ptr(rows.row_forced),
-                                         _ptr(trust_score), _ptr(if_nomatching1_L2.view(torch.uint8)), _ptr(scores_back),
-                                         int(fresh), _ptr(out.view(torch.uint8)), _ptr(ws), nws, _stream()), "merge_patches_batch")
+    _check(getattr(_L(), entry)(*head, _ptr(rows.chunk_base), _ptr(rows.row_cell), *pair_arg, _ptr(rows.row_slot), _ptr(rows.row_forced),
+                                _ptr(trust_score), _ptr(if_nomatching1_L2.view(torch.uint8)), _ptr(scores_back), int(fresh),
+                                _ptr(out.view(torch.uint8)), _ptr(ws), nws, _stream()), what)
     return out
 
 
@@ -1471,39 +1498,47 @@ def get_result_chunks(rows, if_nomatching16, pts_new, pts16, scales, patch_size=
         conf16 = _dev(conf16, "conf16")
         if conf16.numel() != f16.numel():
             raise RuntimeError("get_result_chunks: conf16 must have if_nomatching16's shape")
-    if rows.table is not None:
-        return _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size, conf16)
-    z0 = [int(patch_size[0][0]), rows.h, rows.w]
+    table = rows.table
     z1 = [int(v) for v in patch_size[1]]
     n1 = z1[1] * z1[2]
+    if table is not None and int(patch_size[0][0]) != 32:
+        raise RuntimeError("get_result_chunks: the level-0 patch size of the path is 32")
     if f16.numel() != rows.rows_cap * n1:
         raise RuntimeError("get_result_chunks: if_nomatching16 must be [rows_cap, %d]" % n1)
     a0, a1, s0 = _dev(pts_new, "pts_new"), _dev(pts16, "pts16"), _dev(scales, "scales")
-    N = rows.h * rows.w
-    if a0.numel() != rows.pairs * N * 2 or s0.numel() != rows.pairs * N * 2 or a1.numel() != rows.rows_cap * n1 * 2:
-        raise RuntimeError("get_result_chunks: pts_new / scales must be [pairs,N,2], pts16 [rows_cap,%d,2]" % n1)
+    cells = table.cells if table is not None else rows.pairs * rows.h * rows.w
+    if a0.numel() != cells * 2 or s0.numel() != cells * 2 or a1.numel() != rows.rows_cap * n1 * 2:
+        raise RuntimeError("get_result_chunks: pts_new / scales must be [%s,2], pts16 [rows_cap,%d,2]"
+                           % ("sum N" if table is not None else "pairs,N", n1))
     dev = a0.device
     cap = rows.rows_cap * n1
     ml = torch.empty((cap, 2), dtype=torch.float32, device=dev)
     mr = torch.empty((cap, 2), dtype=torch.float32, device=dev)
     mrow = torch.empty((cap,), dtype=torch.int32, device=dev)
     cnt = torch.empty((1,), dtype=torch.int64, device=dev)
-    nws = _L().pats_get_result_workspace_bytes(rows.Cmax * rows.pairs * N, rows.rows_cap, n1)
+    nws = _L().pats_get_result_workspace_bytes(rows.Cmax * cells, rows.rows_cap, n1)
     ws = _workspace(nws, dev)
-    ps0, ps1 = (ctypes.c_int * 3)(*z0), (ctypes.c_int * 3)(*z1)
+    ps1 = (ctypes.c_int * 3)(*z1)
+    if table is None:               # the uniform entries take the pair count and the level-0 patch size, the ragged ones the table
+        head, sizes, what = (rows.Cmax, rows.pairs), ((ctypes.c_int * 3)(int(patch_size[0][0]), rows.h, rows.w), ps1), "get_result_chunks"
+    else:
+        head, sizes, what = (table.ref(), rows.Cmax), (ps1,), "get_result_chunks_ragged"
+    conf_arg, mc_arg, res = (), (), (ml, mr, mrow, cnt)
     if conf16 is not None:
         mc = torch.empty((cap,), dtype=torch.float32, device=dev)
-        _check(_L().pats_get_result_chunks_conf_f32(rows.Cmax, rows.pairs, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
-                                                    _ptr(a0), _ptr(a1), _ptr(s0), _ptr(conf16), ps0, ps1,
-                                                    _ptr(_ones(rows.Cmax * rows.pairs, dev)), _ptr(_ones(rows.rows_cap, dev)),
-                                                    _ptr(ml), _ptr(mr), _ptr(mc), _ptr(mrow), cap, _ptr(cnt), _ptr(ws), nws,
-                                                    _stream()), "get_result_chunks")
-        return ml, mr, mrow, cnt, mc
-    _check(_L().pats_get_result_chunks_f32(rows.Cmax, rows.pairs, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
-                                           _ptr(a0), _ptr(a1), _ptr(s0), ps0, ps1, _ptr(_ones(rows.Cmax * rows.pairs, dev)),
-                                           _ptr(_ones(rows.rows_cap, dev)), _ptr(ml), _ptr(mr), _ptr(mrow), cap, _ptr(cnt),
-                                           _ptr(ws), nws, _stream()), "get_result_chunks")
-    return ml, mr, mrow, cnt
+        conf_arg, mc_arg, res = (_ptr(conf16),), (_ptr(mc),), (ml, mr, mrow, cnt, mc)
+    entry = _GET_RESULT_CHUNKS[table is not None][conf16 is not None]
+    _check(getattr(_L(), entry)(*head, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap, _ptr(a0), _ptr(a1), _ptr(s0), *conf_arg,
+                                *sizes, _ptr(_ones(rows.Cmax * rows.pairs, dev)), _ptr(_ones(rows.rows_cap, dev)), _ptr(ml), _ptr(mr),
+                                *mc_arg, _ptr(mrow), cap, _ptr(cnt), _ptr(ws), nws, _stream()), what)
+    return res
+
+
+# the entries of get_result_chunks and matches_by_pair by [ragged][confidence]
+_GET_RESULT_CHUNKS = (("pats_get_result_chunks_f32", "pats_get_result_chunks_conf_f32"),
+                      ("pats_get_result_chunks_ragged_f32", "pats_get_result_chunks_ragged_conf_f32"))
+_MATCHES_BY_PAIR = (("pats_matches_by_pair_summary_f32", "pats_matches_by_pair_summary_conf_f32"),
+                    ("pats_matches_by_row_pair_summary_f32", "pats_matches_by_row_pair_summary_conf_f32"))
 
 
 def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None, match_conf=None):
@@ -1523,43 +1558,25 @@ def matches_by_pair(rows, matches_l, matches_r, match_row, M, out=None, P=None, 
         raise RuntimeError("matches_by_pair: pair_off must be a contiguous int64 tensor of %d entries" % n_off)
     nws = _L().pats_matches_by_pair_workspace_bytes(rows.Cmax, rows.pairs)
     ws = _workspace(nws, dev)
+    mc_arg, oc_arg, res = (), (), ((ol, orr, off) if P is None else (ol, orr, off[:rows.pairs + 1], off))
     if match_conf is not None:
         mc = _dev(match_conf, "match_conf").reshape(-1)
         oc = out[3] if len(out) > 3 else torch.empty_like(mc)
         if mc.numel() != matches_l.shape[0] or oc.numel() != mc.numel() or oc.dtype != torch.float32 or not oc.is_contiguous():
             raise RuntimeError("matches_by_pair: match_conf and its destination must be contiguous float32 [cap] tensors")
-        summary = P is not None
-        Pp = _ptr(_dev(P, "P", torch.int64)) if summary else None
-        sp = _ptr(rows.status) if summary else None
-        if rows.table is not None:
-            _check(_L().pats_matches_by_row_pair_summary_conf_f32(_ptr(matches_l), _ptr(matches_r), _ptr(mc), _ptr(match_row), _ptr(M),
-                                                                  _ptr(rows.row_pair), _ptr(rows.chunk_base), rows.Cmax, rows.pairs,
-                                                                  _ptr(ol), _ptr(orr), _ptr(oc), _ptr(off), Pp, sp, _ptr(ws), nws,
-                                                                  _stream()), "matches_by_pair")
-        else:
-            _check(_L().pats_matches_by_pair_summary_conf_f32(_ptr(matches_l), _ptr(matches_r), _ptr(mc), _ptr(match_row), _ptr(M),
-                                                              _ptr(rows.row_cell), _ptr(rows.chunk_base), rows.Cmax, rows.pairs,
-                                                              rows.h * rows.w, _ptr(ol), _ptr(orr), _ptr(oc), _ptr(off), Pp, sp,
-                                                              _ptr(ws), nws, _stream()), "matches_by_pair")
-        return (ol, orr, off, oc) if P is None else (ol, orr, off[:rows.pairs + 1], off, oc)
-    if rows.table is not None:                  # ragged: the pair of a row is row_pair[row] (there is no global N)
-        # without P the call writes the pairs + 1 offsets only (null status): the buffer above holds no more
-        summary = P is not None
-        _check(_L().pats_matches_by_row_pair_summary_f32(_ptr(matches_l), _ptr(matches_r), _ptr(match_row), _ptr(M), _ptr(rows.row_pair),
-                                                         _ptr(rows.chunk_base), rows.Cmax, rows.pairs, _ptr(ol), _ptr(orr), _ptr(off),
-                                                         _ptr(_dev(P, "P", torch.int64)) if summary else None,
-                                                         _ptr(rows.status) if summary else None, _ptr(ws), nws, _stream()), "matches_by_pair")
-        return (ol, orr, off) if P is None else (ol, orr, off[:rows.pairs + 1], off)
-    if P is None:
-        _check(_L().pats_matches_by_pair_f32(_ptr(matches_l), _ptr(matches_r), _ptr(match_row), _ptr(M), _ptr(rows.row_cell),
-                                             _ptr(rows.chunk_base), rows.Cmax, rows.pairs, rows.h * rows.w, _ptr(ol), _ptr(orr), _ptr(off),
-                                             _ptr(ws), nws, _stream()), "matches_by_pair")
-        return ol, orr, off
-    _check(_L().pats_matches_by_pair_summary_f32(_ptr(matches_l), _ptr(matches_r), _ptr(match_row), _ptr(M), _ptr(rows.row_cell),
-                                                 _ptr(rows.chunk_base), rows.Cmax, rows.pairs, rows.h * rows.w, _ptr(ol), _ptr(orr),
-                                                 _ptr(off), _ptr(_dev(P, "P", torch.int64)), _ptr(rows.status), _ptr(ws), nws, _stream()),
-           "matches_by_pair")
-    return ol, orr, off[:rows.pairs + 1], off
+        mc_arg, oc_arg, res = (_ptr(mc),), (_ptr(oc),), res + (oc,)
+    # the pair of a row: row_pair[row] in a ragged batch (there is no global N), row_cell[row] // N in a uniform one
+    pair_args = (_ptr(rows.row_pair),) if rows.table is not None else (_ptr(rows.row_cell),)
+    grid_arg = () if rows.table is not None else (rows.h * rows.w,)
+    if P is None and match_conf is None and rows.table is None:
+        entry, tail = "pats_matches_by_pair_f32", ()                # the one entry without the summary's two pointers
+    else:                           # without P the call writes the pairs + 1 offsets only (null status): the buffer holds no more
+        entry = _MATCHES_BY_PAIR[rows.table is not None][match_conf is not None]
+        tail = (_ptr(_dev(P, "P", torch.int64)), _ptr(rows.status)) if P is not None else (None, None)
+    _check(getattr(_L(), entry)(_ptr(matches_l), _ptr(matches_r), *mc_arg, _ptr(match_row), _ptr(M), *pair_args, _ptr(rows.chunk_base),
+                                rows.Cmax, rows.pairs, *grid_arg, _ptr(ol), _ptr(orr), *oc_arg, _ptr(off), *tail, _ptr(ws), nws,
+                                _stream()), "matches_by_pair")
+    return res
 
 
 # ---- what the per-pair hand-over stages below (top-K, epipolar score / hypotheses / pose) check alike; fn = the public
@@ -1909,34 +1926,10 @@ def chunk_rows_ragged(if_nomatching1, table, if_local=True, Cmax=None, rows_cap=
         raise RuntimeError("chunk_rows_ragged: if_nomatching1 must hold the %d packed cells of the table" % table.cells)
     caps = [(2 * w if if_local else 512) for _, w in table.shapes]
     cm = [max_chunks(h, w, c) for (h, w), c in zip(table.shapes, caps)]
-    r = ChunkRows()
-    r.table, r.pairs, r.h, r.w = table, table.pairs, None, None
-    r.Cmax = max(cm) if Cmax is None else int(Cmax)
-    r.rows_cap = sum(h * w + (c - 1) * w for (h, w), c in zip(table.shapes, cm)) if rows_cap is None else int(rows_cap)
-    dev = f.device
-    i32, i64, u8 = torch.int32, torch.int64, torch.uint8
-    pairs, cells = table.pairs, table.cells
-    r.sum_cycle = torch.empty((cells,), dtype=i32, device=dev)
-    r.cycle_num = torch.empty((pairs,), dtype=i32, device=dev)
-    r.second = torch.empty((pairs, table.hmax + 1, 2), dtype=i64, device=dev)
-    r.third = torch.empty((pairs, table.hmax + 1, 2), dtype=i64, device=dev)
-    r.masks = torch.empty((r.Cmax, cells), dtype=torch.bool, device=dev)
-    r.chunk_base = torch.empty((r.Cmax + 1,), dtype=i64, device=dev)
-    r.crop_base = torch.empty((pairs + 1,), dtype=i64, device=dev)
-    r.row_cell = torch.empty((r.rows_cap,), dtype=i32, device=dev)
-    r._row_pair = torch.empty((r.rows_cap,), dtype=i32, device=dev)
-    r._cell_base = table.cell_base
-    r.row_forced = torch.empty((r.rows_cap,), dtype=u8, device=dev)
-    r.row_crop = torch.empty((r.rows_cap,), dtype=i32, device=dev)
-    r.row_slot = torch.empty((r.Cmax, cells), dtype=i32, device=dev)
-    r.status = torch.empty((1,), dtype=i32, device=dev)
-    nws = _L().pats_chunk_rows_workspace_bytes(pairs, r.Cmax)
-    ws = _workspace(nws, dev)
-    _check(_L().pats_chunk_rows_ragged(table.ref(), _ptr(f), int(bool(if_local)), r.Cmax, r.rows_cap, _ptr(r.sum_cycle),
-                                       _ptr(r.cycle_num), _ptr(r.second), _ptr(r.third), _ptr(r.masks.view(u8)), _ptr(r.chunk_base),
-                                       _ptr(r.crop_base), _ptr(r.row_cell), _ptr(r._row_pair), _ptr(r.row_forced), _ptr(r.row_crop),
-                                       _ptr(r.row_slot), _ptr(r.status), _ptr(ws), nws, _stream()), "chunk_rows_ragged")
-    return r
+    Cmax = max(cm) if Cmax is None else int(Cmax)
+    rows_cap = sum(h * w + (c - 1) * w for (h, w), c in zip(table.shapes, cm)) if rows_cap is None else int(rows_cap)
+    r = _chunk_rows_table(table, table.pairs, None, None, table.hmax, (table.cells,), Cmax, rows_cap, f.device)
+    return _chunk_rows_plan(r, (table.ref(), _ptr(f), int(bool(if_local))), "chunk_rows_ragged")
 
 
 def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_store, right_store, table, margin=128,
@@ -1961,80 +1954,9 @@ def Compute_imgs_ragged(x_scale, y_scale, average_point, if_nomatching, left_sto
     need = int(table.img_base_host[-1]) + table.shapes[-1][0] * table.shapes[-1][1] * 1024 * 3 if table.pairs else 0
     if lf.numel() < need or rt.numel() < need:
         raise RuntimeError("Compute_imgs_ragged: the image stores hold %d / %d elements, the table needs %d" % (lf.numel(), rt.numel(), need))
-    dev = xs.device
-    bound5 = torch.empty((cells, 5), dtype=torch.int64, device=dev)
-    Kd = torch.empty((table.pairs,), dtype=torch.int64, device=dev)
-    Kt = torch.empty((1,), dtype=torch.int64, device=dev)
-    xsn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
-    ysn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
-    avn = torch.empty((cells, 2), dtype=torch.float32, device=dev)
-    _check(_L().pats_compute_imgs_bounds_ragged_f32(table.ref(), _ptr(xs), _ptr(ys), _ptr(ap), _ptr(ifn), _ptr(bound5), _ptr(Kd),
-                                                    _ptr(Kt), _ptr(xsn), _ptr(ysn), _ptr(avn), _stream()), "Compute_imgs_ragged(bounds)")
-    new_left = _crop_out(lout, lfmt, cells, "out[0]", dev)
-    new_right = _crop_out(rout, rfmt, cells, "out[1]", dev)
-    if code != 0 or not lfmt.is_default() or not rfmt.is_default():
-        _typed_crops(table, lf, rt, code, 0, 0, 0, 0, 0, margin, bound5, cells, Kt, lfmt, rfmt, new_left, new_right, None)
-        return new_left, new_right, xsn, ysn, avn, bound5, Kd, Kt
-    _check(_L().pats_left_crops_ragged_f32(table.ref(), _ptr(lf), _ptr(bound5), cells, _ptr(Kt), _ptr(new_left), _stream()),
-           "Compute_imgs_ragged(left)")
-    _check(_L().pats_tensor_resize_hwc_ragged_f32(table.ref(), _ptr(rt), margin, _ptr(bound5), cells, _ptr(Kt), _ptr(new_right), None,
-                                                  _stream()), "Compute_imgs_ragged(right)")
+    bound5, Kd, Kt, xsn, ysn, avn = _imgs_bounds(table, xs, ys, ap, ifn, table.pairs, (cells,))
+    new_left, new_right = _crops(table, lf, rt, code, 0, 0, 0, 0, 0, margin, bound5, cells, Kt, lfmt, rfmt, lout, rout, None)
     return new_left, new_right, xsn, ysn, avn, bound5, Kd, Kt
-
-
-def _merge_patches_ragged(merge_new, rows, trust_score, if_nomatching1_L2, scores_back):
-    table = rows.table
-    if trust_score.numel() != rows.rows_cap * 144 or if_nomatching1_L2.numel() != rows.rows_cap * 144:
-        raise RuntimeError("merge_patches_batch: tensors must be [rows_cap,144]")
-    dev = trust_score.device
-    fresh = scores_back is None
-    if fresh:
-        scores_back = torch.empty((table.cells, 16, 9), dtype=torch.float64, device=dev)            # cleared by the call
-    elif scores_back.dtype != torch.float64 or not scores_back.is_contiguous() or scores_back.numel() != table.cells * 144:
-        raise RuntimeError("merge_patches_batch: scores_back must be a contiguous float64 [sum N, 16, 9] tensor")
-    out = torch.empty((rows.rows_cap, 144), dtype=torch.bool, device=dev)
-    nws = _L().pats_merge_ragged_workspace_bytes(table.cells)
-    ws = _workspace(nws, dev)
-    _check(_L().pats_merge_patches_ragged(table.ref(), 1 if merge_new else 0, rows.Cmax, rows.rows_cap, _ptr(rows.chunk_base),
-                                          _ptr(rows.row_cell), _ptr(rows.row_pair), _ptr(rows.row_slot), _ptr(rows.row_forced),
-                                          _ptr(trust_score), _ptr(if_nomatching1_L2.view(torch.uint8)), _ptr(scores_back), int(fresh),
-                                          _ptr(out.view(torch.uint8)), _ptr(ws), nws, _stream()), "merge_patches_ragged")
-    return out
-
-
-def _get_result_chunks_ragged(rows, f16, pts_new, pts16, scales, patch_size, conf16=None):
-    table = rows.table
-    z1 = [int(v) for v in patch_size[1]]
-    n1 = z1[1] * z1[2]
-    if int(patch_size[0][0]) != 32:
-        raise RuntimeError("get_result_chunks: the level-0 patch size of the path is 32")
-    if f16.numel() != rows.rows_cap * n1:
-        raise RuntimeError("get_result_chunks: if_nomatching16 must be [rows_cap, %d]" % n1)
-    a0, a1, s0 = _dev(pts_new, "pts_new"), _dev(pts16, "pts16"), _dev(scales, "scales")
-    if a0.numel() != table.cells * 2 or s0.numel() != table.cells * 2 or a1.numel() != rows.rows_cap * n1 * 2:
-        raise RuntimeError("get_result_chunks: pts_new / scales must be [sum N,2], pts16 [rows_cap,%d,2]" % n1)
-    dev = a0.device
-    cap = rows.rows_cap * n1
-    ml = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-    mr = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-    mrow = torch.empty((cap,), dtype=torch.int32, device=dev)
-    cnt = torch.empty((1,), dtype=torch.int64, device=dev)
-    nws = _L().pats_get_result_workspace_bytes(rows.Cmax * table.cells, rows.rows_cap, n1)
-    ws = _workspace(nws, dev)
-    ps1 = (ctypes.c_int * 3)(*z1)
-    if conf16 is not None:
-        mc = torch.empty((cap,), dtype=torch.float32, device=dev)
-        _check(_L().pats_get_result_chunks_ragged_conf_f32(table.ref(), rows.Cmax, _ptr(rows.masks.view(torch.uint8)), _ptr(f16),
-                                                           rows.rows_cap, _ptr(a0), _ptr(a1), _ptr(s0), _ptr(conf16), ps1,
-                                                           _ptr(_ones(rows.Cmax * rows.pairs, dev)), _ptr(_ones(rows.rows_cap, dev)),
-                                                           _ptr(ml), _ptr(mr), _ptr(mc), _ptr(mrow), cap, _ptr(cnt), _ptr(ws), nws,
-                                                           _stream()), "get_result_chunks_ragged")
-        return ml, mr, mrow, cnt, mc
-    _check(_L().pats_get_result_chunks_ragged_f32(table.ref(), rows.Cmax, _ptr(rows.masks.view(torch.uint8)), _ptr(f16), rows.rows_cap,
-                                                  _ptr(a0), _ptr(a1), _ptr(s0), ps1, _ptr(_ones(rows.Cmax * rows.pairs, dev)),
-                                                  _ptr(_ones(rows.rows_cap, dev)), _ptr(ml), _ptr(mr), _ptr(mrow), cap, _ptr(cnt),
-                                                  _ptr(ws), nws, _stream()), "get_result_chunks_ragged")
-    return ml, mr, mrow, cnt
 
 
 def masked_stream(cus):
