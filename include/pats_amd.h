@@ -964,6 +964,101 @@ int pats_epipolar_pose_by_pair_f64(const float* matches_l, const float* matches_
                                    int64_t* front_count, uint8_t* front, double* e_refit, void* workspace, size_t workspace_bytes,
                                    pats_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pair homographies (ABI 8, symbols added): the planar sibling of the three epipolar stages above - 4-point hypotheses, their
+ * verification and the least-squares refit of the winner - for pairs whose geometry no epipolar model describes (a wall, a floor or a
+ * facade filling both images; a camera that mostly rotates) and for callers without intrinsics who want to align two views.  All on
+ * the device, no host read.  A caller runs both branches on the same lists and compares the two best_count; the choice is the
+ * caller's.
+ * What it is not: no symmetric or backward transfer error (the test is the forward one), no orientation test on a2, no decision
+ * between E and H, no decomposition of H into (R, t, n), no adaptive termination, and nothing in pipeline.forward_* or the drop-in
+ * calls it.
+ * Shared by the three entry points, per pair p with the n rows of its segment from lo on:
+ *   segment     ragged (pair_off) or strided (stride, counts_in), exactly ONE of the two forms, with the clamping of
+ *               pats_epipolar_score_by_pair_f32;  norm [pairs,8] float32 (optional) as there
+ *   x           the verification's point, formed exactly as there: ((p0 - c0) * s0, (p1 - c1) * s1, 1) in float32 - one subtract, then
+ *               one multiply, never contracted - or (p0, p1, 1) without norm;  r = (r0, r1) the first two coordinates of x_r
+ *   model       a row-major 3x3 H with x_r ~ H x_l, |H|_F = 1, the component of largest magnitude positive (the lowest index among
+ *               equals, judged on the values written).  Nine exact zeros pad H and score nothing
+ *   rows        of match i, for h = vec(H):  A_i = [ -x_l^T, 0 0 0, r0 x_l^T ],  B_i = [ 0 0 0, -x_l^T, r1 x_l^T ]   (A_i h = r0 a2 - a0,
+ *               B_i h = r1 a2 - a1 with a = H x_l)
+ *
+ * 1. Hypotheses: pats_homography_hypotheses_by_pair_f32 - the arguments, in order and meaning, of
+ *    pats_epipolar_hypotheses_by_pair_f32.  For every pair and every h in 0 .. H-1 FOUR distinct matches are drawn by the sampler
+ *    defined there with four draws: k = mix(mix(mix(s_lo) ^ s_hi) + h),  u_t = mix(k + 0x9e3779b9 (t + 1)),
+ *    j_t = (uint64(u_t) (m_h - t)) >> 32,  t = 0 .. 3,  draw t = the j_t-th index of 0 .. m_h - 1 not drawn before;
+ *    pool m_h = n (progressive == 0) or max(4, (n (h + 1) + H - 1) / H) in int64 arithmetic.
+ *      sample_idx [pairs,H,4] int32 (optional: null skips it), the draws in draw order;  -1 for n < 4
+ *      models     [pairs,H,3,3] float32: the unit null vector of the 8x9 matrix A whose rows 2t and 2t + 1 are A_i and B_i of draw t
+ *      zero       the zero model is written for every h of a pair with n < 4 (sample_idx -1), for a sample one of whose 16
+ *                 coordinates is not finite after norm (sample_idx still written) and for a solve that does not end finite.  A rank-
+ *                 deficient sample (three collinear points, repeated matches) gives the zero model or a finite unit vector, never
+ *                 a NaN or an infinity
+ *      contract   the solve is float32 (Householder QR of A^T, one refinement step).  With the written e promoted to float64 and A
+ *                 formed exactly from the float32 x:  |A e|_2 <= B eps32 |A|_F  and  | |e| - 1 | <= 1e-5  for every non-zero model; the
+ *                 tests hold B to 8 times what LAPACK's float32 SVD reaches on the same samples (docs/parity.md has the values)
+ *    Every call defines every byte of both outputs; cap == 0 is a valid call (every model zero; the match pointers must still be
+ *    non-null).  Refused before any launch (pats_last_error names the argument): what pats_epipolar_hypotheses_by_pair_f32 refuses,
+ *    in the same order and wording; the workspace is pats_homography_hypotheses_workspace_bytes (0 today).
+ *
+ * 2. Verification: pats_homography_score_by_pair_f32 - the arguments, in order and meaning, of pats_epipolar_score_by_pair_f32
+ *    (models [pairs,H,3,3] float32, 1 <= H <= pats_epipolar_max_h(); thr [pairs] float32 on the device; use_min_conf / min_conf and the
+ *    finite rule decide whether a match PARTICIPATES exactly as there).  The test of match i against model H:
+ *      a = H x_l,   d0 = a0 - r0 a2,   d1 = a1 - r1 a2
+ *      inlier iff the match participates and a2^2 > 0 and d0^2 + d1^2 <= thr[p]^2 a2^2
+ *    - the squared forward transfer error |r - a / a2|^2 against thr^2 without the division.  A NaN anywhere makes it a non-inlier;
+ *    an all-zero model has a2 = 0 and so no inliers.  The device evaluates it in float32 with fused multiply-adds:
+ *      a0 = fma(H00, l0, fma(H01, l1, H02)), a1 and a2 alike;  d0 = fma(-r0, a2, a0);  d1 = fma(-r1, a2, a1);
+ *      s = fma(d0, d0, d1 d1);  w = a2 a2;  inlier iff w > 0 and s <= (thr thr) w
+ *    A verdict whose s lies within a few float32 roundings of thr^2 a2^2 may differ from a float64 evaluation (docs/parity.md
+ *    quantifies the band); the counts, the winner and the mask of one call always agree: one device function serves all three.
+ *    Outputs, every byte defined by every call, with the shapes and rules of the epipolar verification:
+ *      counts [pairs,H] int32;  best [pairs] int32 (the lowest index of the largest count);  best_count [pairs] int64
+ *      inlier [cap] uint8       1 where the match is an inlier of its pair's best model, 0 everywhere else - rows outside every
+ *                               segment and the slack of strided rows included.  Its sum over a segment is best_count exactly
+ *      moments [pairs,9,9] float64 (null: skipped) the sum over the best model's inliers of A_i^T A_i + B_i^T B_i, the rows formed in
+ *                               float64 from the float32 x (exact).  The summation order is fixed: two calls are byte-identical.
+ *    A pair whose thr is NaN or negative has NO inliers (counts 0, best 0, best_count 0, mask 0, moments 0).  cap == 0 is a valid
+ *    call.  Refused before any launch: what pats_epipolar_score_by_pair_f32 refuses, in the same order and wording; the workspace is
+ *    pats_homography_score_workspace_bytes (0 today).
+ *
+ * 3. Refit: pats_homography_refit_by_pair_f64 - one small launch, float64 throughout.  It reads no match: there is no cap.
+ *    Inputs: best_count [pairs] int64 (the verification's); moments [pairs,9,9] float64 (the verification's; the upper triangle is
+ *    read) or - when moments is null - models [pairs,H,3,3] float32 with best [pairs] int32 (clamped to 0 .. H-1; with moments given
+ *    they are not read); norm [pairs,8] float32 (optional); swapped 0 or 1.
+ *      h_refit     a unit eigenvector of moments[p] for its smallest eigenvalue (the lowest index among equal eigenvalues);  without
+ *                  moments: models[p, best[p]] promoted to float64 as it is
+ *      H           [pairs,3,3] float64 = h_refit, |H|_F = 1 (to float32 accuracy without moments), with the hypotheses' sign rule:
+ *                  cast to float32 it is a model for the verification (the local-optimisation round: refit -> verify -> refit)
+ *      H_px        [pairs,3,3] float64 (optional: null skips it) = N_r^-1 H N_l rescaled to Frobenius norm 1, same sign rule;
+ *                  N = [[s0, 0, -c0 s0], [0, s1, -c1 s1], [0, 0, 1]] per side from norm[p] read as float32 and widened exactly: the
+ *                  homography of the stored (c0, c1) coordinates.  Without norm H_px = H
+ *      eig         [pairs,2] float64: the two smallest eigenvalues of moments[p], ascending - the caller's degeneracy measure (a
+ *                  second one near the first: the inliers do not pin H down);  0, 0 without moments
+ *      no model    best_count[p] < 4, a non-finite moment or model, or an all-zero winning model:  H = H_px = 0, eig = 0.  A
+ *                  non-finite H_px (a zero scale in norm) is written as zeros on its own.  Never a NaN or an infinity
+ *      swapped     with 1 the points are in the hand-over's (c0, c1) = (y, x) order; everything is computed in that frame and H and
+ *                  H_px are written as P H P, P = [[0,1,0],[1,0,0],[0,0,1]], the sign rule applied after the permutation
+ *    Refused before any launch (pats_last_error names the argument): a null best_count / H_out / eig; best_count / moments / H_out /
+ *    H_px / eig off 8 bytes, models / best / norm off 4; pairs < 1; swapped not 0 or 1; neither moments nor (models and best); with models
+ *    given H < 1 or H > max_h; a workspace smaller than pats_homography_refit_workspace_bytes (0 today: the solve lives in LDS and
+ *    registers; workspace may then be null). */
+size_t pats_homography_hypotheses_workspace_bytes(int64_t pairs, int64_t H);
+int pats_homography_hypotheses_by_pair_f32(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                           const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
+                                           const float* norm, int progressive, float* models, int32_t* sample_idx, void* workspace,
+                                           size_t workspace_bytes, pats_stream_t stream);
+size_t pats_homography_score_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_homography_score_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                      int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                      int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                      int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                      void* workspace, size_t workspace_bytes, pats_stream_t stream);
+size_t pats_homography_refit_workspace_bytes(int64_t pairs);
+int pats_homography_refit_by_pair_f64(const int64_t* best_count, const double* moments, const float* models, int64_t H,
+                                      const int32_t* best, const float* norm, int64_t pairs, int swapped, double* H_out, double* H_px,
+                                      double* eig, void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the
  * keys, out = prob v.  query [batch,dim,heads,n], key / value [batch,dim,heads,m] (the view

@@ -611,3 +611,63 @@ def split_pose_by_pair(out, cap):
     split_verified_by_pair(out, cap)                  # the overflow checks, with the copies that function makes
     E, R, t, front_count = out["pose"][:4]
     return [(R[i], t[i], E[i], front_count[i]) for i in range(cap.pairs)]
+
+
+def hypothesize_h_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
+    """Device side, after the matching: H 4-point HOMOGRAPHY hypotheses per pair (ops.homography_hypotheses_by_pair: one launch, no
+    host read) - the `models` of verify_h_by_pair, for pairs that look at a plane or whose camera mostly rotates.  on, progressive
+    (the pool's minimum is 4 here), seed and norm exactly as hypothesize_by_pair takes them; the same seed gives a pair the same
+    generator key in both branches.
+    Returns models [pairs,H,3,3] float32 - or (models, sample_idx [pairs,H,4] int32) with samples=True - in the CALLER's order.  Adds
+    `hypotheses_h` (what is returned) to the result; `hypotheses`, `hypotheses5`, the matches, the regrouped lists and a top-K of the
+    same step are not touched."""
+    hyp = _sample_by_pair("hypothesize_h_by_pair", ops.homography_hypotheses_by_pair, out, cap, H, seed, norm, on, progressive, samples)
+    out["hypotheses_h"] = hyp
+    return hyp
+
+
+def verify_h_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
+    """Device side: every pair's H candidate HOMOGRAPHIES (models [pairs,H,3,3], thr [pairs], norm [pairs,8] or None - float32 GPU
+    tensors in the CALLER's pair order) tested against the pair's matches by the forward transfer error
+    (ops.homography_score_by_pair: no host read).  on and min_conf as verify_by_pair takes them.
+    Adds `verified_h` = (counts [pairs,H] int32, best [pairs] int32, best_count [pairs] int64, inlier uint8 aligned with the lists that
+    were scored [, moments [pairs,9,9] float64]) to the result and returns it; rows in SLOT order for a mixed pack, as
+    `verified`'s.  `verified_h_on` and `verified_h_models` go with it.  `verified` and `pose` are never touched: a caller runs
+    both branches on one result and compares best_count of the two - choosing between the models stays with the caller."""
+    _check_on("verify_h_by_pair", out, on)
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("verify_h_by_pair: min_conf needs a result made with confidence=True")
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        idx = _caller_of_dev(out, models.device)
+        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    ml, mr, conf, seg = _lists_on(out, cap, on)
+    ver = ops.homography_score_by_pair(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm,
+                                       moments=moments, **seg)
+    out["verified_h"], out["verified_h_on"] = ver, on
+    out["verified_h_models"] = models                 # slot order: homography_by_pair's source when no moments were asked for
+    return ver
+
+
+def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
+    """Device side, after verify_h_by_pair: each pair's homography refitted to its verified inliers (ops.homography_refit_by_pair:
+    one launch, float64, no host read) - the smallest eigenvector of `verified_h`'s moments if the verification produced them,
+    otherwise its winning model.  norm [pairs,8] or None in the CALLER's order - pass what verify_h_by_pair was given.  swapped: the
+    lists are in the hand-over's (y, x) order and H is wanted in the reference's (x, y) frame.
+    Returns (H [pairs,3,3] float64, eig [pairs,2] float64: the two smallest eigenvalues of the moments) in the CALLER's order - with
+    pixel=True followed by H_px [pairs,3,3]: the homography of the stored coordinates - and stores them as `homography`.  H.float()
+    goes straight back into verify_h_by_pair as an H = 1 model: the local-optimisation round."""
+    if "verified_h" not in out:
+        raise ValueError("homography_by_pair: run verify_h_by_pair first")
+    ver = out["verified_h"]
+    best, best_count = ver[1:3]
+    mixed = "caller_of" in out
+    if mixed and norm is not None:
+        norm = norm.index_select(0, _caller_of_dev(out, best.device))
+    src = {"moments": ver[4]} if len(ver) > 4 else {"models": out["verified_h_models"], "best": best}
+    res = ops.homography_refit_by_pair(best_count, norm=norm, swapped=swapped, return_pixel=pixel, **src)
+    if mixed:                                                             # slots back to the caller's order
+        back = _slot_of_dev(out, cap, best.device)
+        res = tuple(t.index_select(0, back) for t in res)
+    out["homography"] = res
+    return res

@@ -1915,6 +1915,145 @@ def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None
     return out
 
 
+def homography_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
+                                  return_samples=False, out=None, pairs=None):
+    """H 4-point homography hypotheses per pair, ON THE DEVICE, one launch, no host read (pats_homography_hypotheses_by_pair_f32;
+    include/pats_amd.h, "Per-pair homographies", holds the definition): for every pair and every h four distinct matches of the pair
+    are drawn by the hypotheses' counter-based generator and the unit null vector of their 8x9 DLT matrix is written as a row-major
+    3x3 model H, x_r ~ H x_l - the input of homography_score_by_pair.  The arguments are those of epipolar_hypotheses_by_pair.
+    progressive: hypothesis h draws from the first max(4, ceil(n (h + 1) / H)) matches of the pair's list instead of all n.
+    Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 4 matches and for a sample with a non-finite
+    coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,4] int32: the draws as positions inside the pair's
+    list, -1 for a pair with fewer than 4 matches).  out: the destination(s), a tensor or a tuple."""
+    fn = "homography_hypotheses_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("homography_hypotheses_by_pair: seed must be an int64 GPU tensor [pairs]")
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    H = int(H)
+    seed = _dev(seed, "seed", torch.int64).reshape(-1)
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if seed.numel() != pairs:
+        raise RuntimeError("homography_hypotheses_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("homography_hypotheses_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("models", torch.float32, (pairs, H, 3, 3))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, 4)))
+    out = _bp_outputs(fn, want, out, dev, lone=True)
+    nws = _L().pats_homography_hypotheses_workspace_bytes(pairs, H)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+    _check(_L().pats_homography_hypotheses_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
+                                                       1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
+                                                       _ptr(ws), nws, _stream()), fn)
+    return out if return_samples else out[0]
+
+
+def homography_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None,
+                             norm=None, moments=False, out=None, pairs=None):
+    """H candidate homographies per pair against every match of the pair, ON THE DEVICE, no host read
+    (pats_homography_score_by_pair_f32; include/pats_amd.h, "Per-pair homographies", holds the definition): match i is an inlier of
+    the 3x3 model H iff d0^2 + d1^2 <= thr^2 a2^2 with a = H x_l, d = (a0 - r0 a2, a1 - r1 a2), a2^2 > 0 - the squared forward
+    transfer error against thr^2 without the division.  The arguments, the segment forms, norm, min_conf and thr are those of
+    epipolar_score_by_pair; an all-zero model has no inliers.
+    Returns (counts [pairs,H] int32, best [pairs] int32 - the lowest index of the largest count -, best_count [pairs] int64,
+    inlier [cap] uint8 - 1 where the match is an inlier of its pair's best model, 0 everywhere else) and, with moments=True,
+    moments [pairs,9,9] float64 = the sum of A_i^T A_i + B_i^T B_i over those inliers (the two DLT rows of a match): the input of
+    homography_refit_by_pair.  out: the four (five) destinations."""
+    fn = "homography_score_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
+                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("homography_score_by_pair: min_conf needs conf")
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
+        raise RuntimeError("homography_score_by_pair: models must be [pairs,H,3,3]")
+    H = int(models.shape[1])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("homography_score_by_pair: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % pairs)
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("homography_score_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("homography_score_by_pair: conf must be [cap]")
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
+            ("inlier", torch.uint8, (cap,))]
+    if moments:
+        want.append(("moments", torch.float64, (pairs, 9, 9)))
+    out = _bp_outputs(fn, want, out, dev)
+    nws = _L().pats_homography_score_workspace_bytes(pairs, H, cap)
+    ws = _workspace(nws, dev) if nws else None
+    inl = out[3]
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else ml
+    _check(_L().pats_homography_score_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H,
+                                                  _ptr(thr), _ptr(norm), 0 if min_conf is None else 1,
+                                                  0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                                  _ptr(inl), _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream()), fn)
+    return out
+
+
+def homography_refit_by_pair(best_count, moments=None, models=None, best=None, norm=None, swapped=False, return_pixel=False, out=None):
+    """Each pair's homography refitted to its verified inliers, ON THE DEVICE, one launch, float64, no host read
+    (pats_homography_refit_by_pair_f64; include/pats_amd.h, "Per-pair homographies", holds the definition): the unit eigenvector of
+    `moments` for its smallest eigenvalue - without moments the winning model models[p, best[p]] promoted.  best_count [pairs] int64
+    and moments [pairs,9,9] float64 (or best [pairs] int32 with the models [pairs,H,3,3] float32) are homography_score_by_pair's
+    outputs; norm [pairs,8] what it was given.  swapped: the points are in the hand-over's (y, x) order; H and H_px come back in the
+    reference's (x, y) frame.
+    Returns (H [pairs,3,3] float64 - Frobenius norm 1, the component of largest magnitude positive: H.float() is a model for
+    homography_score_by_pair -, eig [pairs,2] float64: the two smallest eigenvalues of the moments, ascending; 0 without moments),
+    then H_px [pairs,3,3] float64 with return_pixel=True: the homography of the stored coordinates, N_r^-1 H N_l rescaled (H itself
+    without norm).  A pair without a model (best_count < 4, a non-finite moment) has zeros everywhere.  out: the destinations."""
+    fn = "homography_refit_by_pair"
+    _bp_layout(fn, [(best_count, "best_count"), (moments, "moments"), (models, "models"), (best, "best"), (norm, "norm")],
+               {"best_count": torch.int64, "moments": torch.float64, "best": torch.int32})
+    if moments is None and (models is None or best is None):
+        raise RuntimeError("homography_refit_by_pair: give moments, or models and best")
+    bc = _dev(best_count, "best_count", torch.int64).reshape(-1)
+    pairs = int(bc.numel())
+    if pairs < 1:
+        raise RuntimeError("homography_refit_by_pair: best_count must hold one int64 per pair")
+    H = 1
+    if moments is not None:
+        moments = _dev(moments, "moments", torch.float64)
+        if tuple(moments.shape) != (pairs, 9, 9):
+            raise RuntimeError("homography_refit_by_pair: moments must be [pairs,9,9]")
+        models = best = None
+    else:
+        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
+        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
+            raise RuntimeError("homography_refit_by_pair: models must be [pairs,H,3,3] and best [pairs]")
+        H = int(models.shape[1])
+        if not 1 <= H <= epipolar_max_h():
+            raise RuntimeError("homography_refit_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = bc.device
+    want = [("H", torch.float64, (pairs, 3, 3)), ("eig", torch.float64, (pairs, 2))]
+    if return_pixel:
+        want.append(("H_px", torch.float64, (pairs, 3, 3)))
+    out = _bp_outputs(fn, want, out, dev)
+    nws = _L().pats_homography_refit_workspace_bytes(pairs)
+    ws = _workspace(nws, dev) if nws else None
+    _check(_L().pats_homography_refit_by_pair_f64(_ptr(bc), _ptr(moments), _ptr(models), H, _ptr(best), _ptr(norm), pairs,
+                                                  1 if swapped else 0, _ptr(out[0]), _ptr(out[2]) if return_pixel else None, _ptr(out[1]),
+                                                  _ptr(ws), nws, _stream()), fn)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
 # ------------------------------------------------------------------------------------------------
