@@ -1059,6 +1059,58 @@ int pats_homography_refit_by_pair_f64(const int64_t* best_count, const double* m
                                       const int32_t* best, const float* norm, int64_t pairs, int swapped, double* H_out, double* H_px,
                                       double* eig, void* workspace, size_t workspace_bytes, pats_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pair adaptive verification (ABI 8, symbols added): the two verifications above with plain RANSAC's stopping rule - a pair's
+ * models are tested in rounds of round_models, and the pair stops as soon as the probability of having missed an all-inlier sample
+ * falls below 1 - confidence.  On the device, on the caller's stream, no host read and no synchronisation: after two fills,
+ * 2 ceil(H / round_models) launches and the mask launch (rounds after every pair has stopped still launch; their workgroups
+ * return at once).  The hypotheses are still all generated up front; only their verification stops early.
+ * pats_epipolar_score_adaptive_by_pair_f32 and pats_homography_score_adaptive_by_pair_f32 take the arguments of
+ * pats_epipolar_score_by_pair_f32 / pats_homography_score_by_pair_f32 in their order and meaning - the segment, norm, min_conf, thr
+ * and the models models[p, 0..H-1] are exactly what those take - and then
+ *   confidence         double, strictly between 0 and 1
+ *   sample_size s      1 .. 16: the matches one sample draws (8, 5 or 4 for the three samplers)
+ *   models_per_sample g  1 .. 16: the models one sample yields (10 for the 5-point models, otherwise 1)
+ *   round_models B     a positive multiple of 64; ceil(H / B) is at most 256
+ *   used, participating [pairs] int32 outputs, required
+ * The rule.  All its arithmetic is IEEE float64, no contraction, no transcendental function: a host reproduces it bit for bit.
+ *   participating[p]  int32: matches of the segment that take part (the verification's finite / min_conf rule). 0 when thr[p] is NaN or negative
+ *   round r           tests models [r B, min(H, (r+1) B)) of every pair that has not stopped.  T_r = min(H, (r+1) B)
+ *   after round r     c = the largest count over models [0, T_r), lowest index among equals (running best: a later equal count never replaces it)
+ *                     k = T_r / g (integer division);  eta = 1.0 - confidence
+ *                     w = (double)c / (double)participating[p]   (0 when participating is 0)
+ *                     ws = w multiplied by itself s - 1 times, left to right;  q = 1.0 - ws
+ *                     miss = q^k by square-and-multiply from k's most significant bit (start 1.0; per bit: square, then multiply by q if the bit is set); k = 0 gives 1.0
+ *                     the pair stops iff miss <= eta
+ *   used[p]           int32: T_r of the round after which the pair stopped; H if it never did
+ *   counts[p, h]      as the existing verification for h < used[p]; exactly 0 for h >= used[p]
+ *   best, best_count, inlier, moments
+ *                     bit for bit what the existing verification returns for the same call with models[p, used[p]:] replaced by zero models
+ * A pair with no inliers has q = 1 and never stops: used = H.  It still costs next to nothing - the score workgroups return on a
+ * bad thr and on empty tiles.  The criterion is plain RANSAC's, also on progressive samples (it is not PROSAC's).
+ * cap == 0 is a valid call and defines every per-pair output: used = H, participating = 0.
+ * Refused before any launch (pats_last_error names the argument): everything the fixed-budget entries refuse (the grid is
+ * ceil(longest / 2048) * pairs * ceil(min(B, H) / 256) workgroups per round); a confidence not strictly between 0 and 1 (NaN included);
+ * sample_size or models_per_sample outside 1 .. 16; a round_models that is not a positive multiple of 64; more than 256 rounds; a null
+ * used / participating or one off 4 bytes; a workspace smaller than pats_*_score_adaptive_workspace_bytes (one int32 per pair: the
+ * stopped flags; the running best lives in best / best_count), null or off 4 bytes. */
+size_t pats_epipolar_score_adaptive_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_epipolar_score_adaptive_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                             int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                             int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                             int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                             void* workspace, size_t workspace_bytes, pats_stream_t stream, double confidence,
+                                             int sample_size, int models_per_sample, int64_t round_models, int32_t* used,
+                                             int32_t* participating);
+size_t pats_homography_score_adaptive_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_homography_score_adaptive_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                               int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                               int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                               int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                               void* workspace, size_t workspace_bytes, pats_stream_t stream, double confidence,
+                                               int sample_size, int models_per_sample, int64_t round_models, int32_t* used,
+                                               int32_t* participating);
+
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the
  * keys, out = prob v.  query [batch,dim,heads,n], key / value [batch,dim,heads,m] (the view

@@ -38,6 +38,11 @@ class CropFormat(ctypes.Structure):
 
 _FMT = ctypes.POINTER(CropFormat)
 
+# the 22 arguments of a fixed-budget score entry, and what an adaptive one appends to them
+_SCORE_ARGS = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_f,
+               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]
+_ADAPTIVE_ARGS = [ctypes.c_double, c_int, c_int, c_i64, c_void_p, c_void_p]
+
 # name -> (restype, argtypes); must list every symbol include/pats_amd.h declares
 SIGNATURES = {
     "pats_version": (ctypes.c_char_p, []),
@@ -258,6 +263,12 @@ SIGNATURES = {
     "pats_homography_refit_workspace_bytes": (c_size, [c_i64]),
     "pats_homography_refit_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p,
                                                   c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair adaptive verification, both branches (csrc/adaptive.hip): the fixed-budget arguments, then confidence, sample_size,
+    # models_per_sample, round_models, used, participating
+    "pats_epipolar_score_adaptive_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "pats_epipolar_score_adaptive_by_pair_f32": (c_int, _SCORE_ARGS + _ADAPTIVE_ARGS),
+    "pats_homography_score_adaptive_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "pats_homography_score_adaptive_by_pair_f32": (c_int, _SCORE_ARGS + _ADAPTIVE_ARGS),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -671,3 +671,49 @@ def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
         res = tuple(t.index_select(0, back) for t in res)
     out["homography"] = res
     return res
+
+
+def _verify_adaptive(fn, score, key, out, cap, models, thr, confidence, sample_size, models_per_sample, round_models, norm, min_conf, on,
+                     moments):
+    """What verify_adaptive_by_pair and verify_h_adaptive_by_pair share; score = the ops function, key = "verified" / "verified_h"."""
+    if not 0.0 < float(confidence) < 1.0:             # false for a NaN; before any device work
+        raise ValueError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
+    _check_on(fn, out, on)
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
+    if round_models is None:
+        round_models = 320 if models_per_sample == 10 else 256
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        idx = _caller_of_dev(out, models.device)
+        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    ml, mr, conf, seg = _lists_on(out, cap, on)
+    res = score(ml, mr, models, thr, confidence, sample_size, models_per_sample=models_per_sample, round_models=round_models,
+                conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, moments=moments, **seg)
+    out[key], out[key + "_on"] = res[:-2], on
+    out[key + "_models"] = models                     # slot order, as the fixed-budget functions keep them
+    out[key + "_used"] = res[-2:]
+    return res
+
+
+def verify_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,
+                            min_conf=None, on="all", moments=False):
+    """verify_by_pair that stops each pair at a RANSAC confidence, on the device (ops.epipolar_score_adaptive_by_pair: no host
+    read): the pair's models are tested in rounds of round_models (None: 320 with models_per_sample == 10, else 256) and a pair
+    stops once (1 - w^sample_size)^(models seen // models_per_sample) <= 1 - confidence, w = its best inlier ratio so far.
+    sample_size = 8 for hypothesize_by_pair's models, 5 with models_per_sample = 10 for hypothesize5_by_pair's.  Everything else -
+    the caller's pair order, the slot order of a mixed pack, on, min_conf - as verify_by_pair.
+    Stores verify_by_pair's tuple as `verified` (with `verified_on`, `verified_models`): pose_by_pair and split_verified_by_pair
+    work on it unchanged; counts are 0 from used[p] on.  Also stores `verified_used` = (used [pairs] int32, participating [pairs]
+    int32) and returns the tuple followed by those two, in SLOT order like counts.  A confidence outside (0, 1) raises ValueError."""
+    return _verify_adaptive("verify_adaptive_by_pair", ops.epipolar_score_adaptive_by_pair, "verified", out, cap, models, thr, confidence,
+                            sample_size, models_per_sample, round_models, norm, min_conf, on, moments)
+
+
+def verify_h_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,
+                              min_conf=None, on="all", moments=False):
+    """verify_h_by_pair with the stopping rule of verify_adaptive_by_pair (ops.homography_score_adaptive_by_pair); sample_size = 4
+    for hypothesize_h_by_pair's models.  Stores `verified_h` (with `verified_h_on`, `verified_h_models`: homography_by_pair works
+    on it unchanged) and `verified_h_used` = (used, participating); returns the tuple followed by those two."""
+    return _verify_adaptive("verify_h_adaptive_by_pair", ops.homography_score_adaptive_by_pair, "verified_h", out, cap, models, thr,
+                            confidence, sample_size, models_per_sample, round_models, norm, min_conf, on, moments)

@@ -10,6 +10,8 @@
 //           popcounts added on the scalar unit and kept by lane h % 64 in a counter register; every 64 models the
 //           register goes to LDS, at the end the four waves' counters are added and ONE integer atomic per workgroup and model with a
 //           non-zero count goes to counts[p, h] (integer adds: the order does not matter).  Blocks past a segment's end return.
+//           A template on ROUND: <false> is this fixed budget; <true> is one round of the adaptive verification (adaptive.hip) - the
+//           models [h_begin, h_stop) only, and the workgroups of a pair that has stopped return on its flag.
 //   argmax  one workgroup per pair over counts[p, :]: the largest count, the lowest index that holds it
 //   mask    one workgroup per pair: the winner's verdict for every match of the segment with the arithmetic of the score kernel
 //           (same device function: the mask and the winner's count agree exactly), the moments in float64 in a fixed order
@@ -55,11 +57,16 @@ __device__ __forceinline__ void epi_model(const float* __restrict__ m, float (&e
     for (int k = 0; k < 9; ++k) e[k] = m[k];
 }
 
+// ROUND = false: the fixed budget - models [0, H) in `chunks` chunks; h_begin, h_stop and stopped are not read.  ROUND = true: a round
+// of the adaptive verification (adaptive.hip issues them) - models [h_begin, h_stop) in `chunks` chunks, and the workgroups of a
+// pair whose stopped flag is set return at once
+template <bool ROUND>
 __global__ void __launch_bounds__(EPI_THREADS)
 epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
                       const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
                       int pairs, int chunks, const float* __restrict__ models, int H, const float* __restrict__ thr,
-                      const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts) {
+                      const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts, int h_begin, int h_stop,
+                      const int32_t* __restrict__ stopped) {
     __shared__ int wave_cnt[EPI_WAVES][EPI_CHUNK];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -68,6 +75,7 @@ epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ m
     const int chunk = (int)(b % (uint32_t)chunks);
     const int64_t p = (int64_t)((b / (uint32_t)chunks) % (uint32_t)pairs);
     const uint32_t tile = b / ((uint32_t)chunks * (uint32_t)pairs);
+    if (ROUND && stopped[p]) return;                    // workgroup-uniform: the pair has met its confidence
     int64_t lo;
     uint32_t n;
     epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
@@ -90,8 +98,9 @@ epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ m
         l0[k] = e2f{a0, c0}; l1[k] = e2f{a1, c1}; r0[k] = e2f{a2, c2}; r1[k] = e2f{a3, c3};
     }
 
-    const int h_lo = chunk * EPI_CHUNK;
-    const int nmod = H - h_lo < EPI_CHUNK ? H - h_lo : EPI_CHUNK;             // >= 1: chunks = ceil(H / EPI_CHUNK)
+    const int h_lo = (ROUND ? h_begin : 0) + chunk * EPI_CHUNK;              // the fixed budget: every model, [0, H)
+    const int h_end = ROUND ? h_stop : H;
+    const int nmod = h_end - h_lo < EPI_CHUNK ? h_end - h_lo : EPI_CHUNK;     // >= 1: chunks = ceil((h_end - h_begin) / EPI_CHUNK)
     const float* m = models + ((int64_t)p * H + h_lo) * 9;
     float e[9];
     epi_model(m, e);
@@ -267,9 +276,9 @@ extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const flo
     if (rc != PATS_OK) return rc;
     const float* cf = use_min_conf ? conf : nullptr;    // without a threshold the confidence is not read
     if (tiles > 0) {
-        hipLaunchKernelGGL(epipolar_score_kernel, dim3((unsigned)(tiles * pairs * chunks)), dim3(EPI_THREADS), 0, st, matches_l, matches_r,
-                           cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm, use_min_conf, min_conf,
-                           counts);
+        hipLaunchKernelGGL(epipolar_score_kernel<false>, dim3((unsigned)(tiles * pairs * chunks)), dim3(EPI_THREADS), 0, st, matches_l,
+                           matches_r, cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm, use_min_conf, min_conf,
+                           counts, 0, (int)H, nullptr);
         rc = check_launch("epipolar_score kernel");
         if (rc != PATS_OK) return rc;
     }
@@ -279,4 +288,39 @@ extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const flo
     hipLaunchKernelGGL(epipolar_mask_kernel, dim3((unsigned)pairs), dim3(EPI_MASK_THREADS), 0, st, matches_l, matches_r, cf, pair_off,
                        counts_in, stride, cap, models, (int)H, thr, norm, use_min_conf, min_conf, best, best_count, inlier, moments);
     return check_launch("epipolar_mask kernel");
+}
+
+// ---- adaptive verification: this branch's two launchers for adaptive.hip's host side ------------------------------------------------
+static_assert(EPI_TILE == ADAPTIVE_TILE && EPI_CHUNK == ADAPTIVE_CHUNK, "adaptive.hip sizes the rounds' grids");
+
+static int epi_adaptive_round(const AdaptiveCall& c, const float* conf, int tiles, int h_lo, int h_hi, const int32_t* stopped,
+                              hipStream_t st) {
+    const int64_t chunks = ceil_div(h_hi - h_lo, EPI_CHUNK);
+    hipLaunchKernelGGL(epipolar_score_kernel<true>, dim3((unsigned)(tiles * c.pairs * chunks)), dim3(EPI_THREADS), 0, st, c.matches_l,
+                       c.matches_r, conf, c.pair_off, c.counts_in, c.stride, c.cap, (int)c.pairs, (int)chunks, c.models, (int)c.H, c.thr,
+                       c.norm, c.use_min_conf, c.min_conf, c.counts, h_lo, h_hi, stopped);
+    return check_launch("epipolar_score kernel (a round)");
+}
+
+static int epi_adaptive_mask(const AdaptiveCall& c, const float* conf, hipStream_t st) {
+    hipLaunchKernelGGL(epipolar_mask_kernel, dim3((unsigned)c.pairs), dim3(EPI_MASK_THREADS), 0, st, c.matches_l, c.matches_r, conf,
+                       c.pair_off, c.counts_in, c.stride, c.cap, c.models, (int)c.H, c.thr, c.norm, c.use_min_conf, c.min_conf, c.best,
+                       c.best_count, c.inlier, c.moments);
+    return check_launch("epipolar_mask kernel");
+}
+
+extern "C" size_t pats_epipolar_score_adaptive_workspace_bytes(int64_t pairs, int64_t H, int64_t cap) {
+    (void)H; (void)cap;
+    return adaptive_workspace_bytes(pairs);
+}
+
+extern "C" int pats_epipolar_score_adaptive_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf,
+        const int64_t* pair_off, int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t H,
+        const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts, int32_t* best, int64_t* best_count,
+        uint8_t* inlier, double* moments, void* workspace, size_t workspace_bytes, pats_stream_t stream, double confidence,
+        int sample_size, int models_per_sample, int64_t round_models, int32_t* used, int32_t* participating) {
+    const AdaptiveCall c{matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap, models, H, thr, norm, use_min_conf, min_conf,
+                         counts, best, best_count, inlier, moments, workspace, workspace_bytes, stream, confidence, sample_size,
+                         models_per_sample, round_models, used, participating};
+    return adaptive_score_by_pair("epipolar_score_adaptive_by_pair", c, epi_adaptive_round, epi_adaptive_mask);
 }

@@ -106,4 +106,38 @@ inline int epi_check_h(const char* what, int64_t H) {
     return PATS_OK;
 }
 
+// ---- adaptive verification (adaptive.hip): the arguments of pats_*_score_adaptive_by_pair_f32 and the two launchers a branch hands
+// to the shared host side - its score kernel restricted to the models [h_lo, h_hi) of pairs that have not stopped, and its mask kernel
+struct AdaptiveCall {
+    const float *matches_l, *matches_r, *conf;
+    const int64_t* pair_off;
+    int64_t stride;
+    const int64_t* counts_in;
+    int64_t pairs, cap;
+    const float* models;
+    int64_t H;
+    const float *thr, *norm;
+    int use_min_conf;
+    float min_conf;
+    int32_t *counts, *best;
+    int64_t* best_count;
+    uint8_t* inlier;
+    double* moments;
+    void* workspace;
+    size_t workspace_bytes;
+    pats_stream_t stream;
+    double confidence;
+    int sample_size, models_per_sample;
+    int64_t round_models;
+    int32_t *used, *participating;
+};
+constexpr int ADAPTIVE_TILE = 2048;                    // matches per score workgroup and models per score workgroup: both branches'
+constexpr int ADAPTIVE_CHUNK = 256;
+// conf = the confidence list if it gates, else null; tiles = ceil(longest segment / ADAPTIVE_TILE) >= 1
+typedef int (*AdaptiveScoreRound)(const AdaptiveCall& c, const float* conf, int tiles, int h_lo, int h_hi, const int32_t* stopped,
+                                  hipStream_t st);
+typedef int (*AdaptiveMask)(const AdaptiveCall& c, const float* conf, hipStream_t st);
+size_t adaptive_workspace_bytes(int64_t pairs);
+int adaptive_score_by_pair(const char* who, const AdaptiveCall& c, AdaptiveScoreRound score_round, AdaptiveMask mask);
+
 }  // namespace pats

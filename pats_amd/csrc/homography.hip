@@ -10,7 +10,7 @@
 //   score       grid = tiles x pairs x model chunks, 256 threads - epipolar_score_kernel's plan: HOM_R = 8 matches per thread in
 //               registers (four packed pairs), a model as nine wave-uniform floats loaded one model ahead, v_pk_fma_f32 per pair,
 //               the verdicts as wave ballots counted on the scalar unit, lane h % 64 keeps the count of model h, ONE integer
-//               atomic per workgroup and model with a non-zero sum
+//               atomic per workgroup and model with a non-zero sum;  <true>: one round of the adaptive verification (adaptive.hip)
 //   argmax      one workgroup per pair: the largest count, the lowest index that holds it
 //   mask        one workgroup per pair: the winner's verdicts with hom_test2 (the score kernel's device function: the mask's
 //               population is best_count exactly) and the 9x9 moments in float64 in a fixed order
@@ -221,11 +221,16 @@ __device__ __forceinline__ void hom_model(const float* __restrict__ m, float (&e
     for (int k = 0; k < 9; ++k) e[k] = m[k];
 }
 
+// ROUND = false: the fixed budget - models [0, H) in `chunks` chunks; h_begin, h_stop and stopped are not read.  ROUND = true: a round
+// of the adaptive verification (adaptive.hip issues them) - models [h_begin, h_stop) in `chunks` chunks, and the workgroups of a
+// pair whose stopped flag is set return at once
+template <bool ROUND>
 __global__ void __launch_bounds__(HOM_THREADS)
 homography_score_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
                         const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
                         int pairs, int chunks, const float* __restrict__ models, int H, const float* __restrict__ thr,
-                        const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts) {
+                        const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts, int h_begin, int h_stop,
+                        const int32_t* __restrict__ stopped) {
     __shared__ int wave_cnt[HOM_WAVES][HOM_CHUNK];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -234,6 +239,7 @@ homography_score_kernel(const float* __restrict__ ml_, const float* __restrict__
     const int chunk = (int)(b % (uint32_t)chunks);
     const int64_t p = (int64_t)((b / (uint32_t)chunks) % (uint32_t)pairs);
     const uint32_t tile = b / ((uint32_t)chunks * (uint32_t)pairs);
+    if (ROUND && stopped[p]) return;                    // workgroup-uniform: the pair has met its confidence
     int64_t lo;
     uint32_t n;
     epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
@@ -256,8 +262,9 @@ homography_score_kernel(const float* __restrict__ ml_, const float* __restrict__
         l0[k] = h2f{a0, c0}; l1[k] = h2f{a1, c1}; r0[k] = h2f{a2, c2}; r1[k] = h2f{a3, c3};
     }
 
-    const int h_lo = chunk * HOM_CHUNK;
-    const int nmod = H - h_lo < HOM_CHUNK ? H - h_lo : HOM_CHUNK;             // >= 1: chunks = ceil(H / HOM_CHUNK)
+    const int h_lo = (ROUND ? h_begin : 0) + chunk * HOM_CHUNK;              // the fixed budget: every model, [0, H)
+    const int h_end = ROUND ? h_stop : H;
+    const int nmod = h_end - h_lo < HOM_CHUNK ? h_end - h_lo : HOM_CHUNK;     // >= 1: chunks = ceil((h_end - h_begin) / HOM_CHUNK)
     const float* m = models + ((int64_t)p * H + h_lo) * 9;
     float e[9];
     hom_model(m, e);
@@ -642,9 +649,9 @@ extern "C" int pats_homography_score_by_pair_f32(const float* matches_l, const f
     if (rc != PATS_OK) return rc;
     const float* cf = use_min_conf ? conf : nullptr;    // without a threshold the confidence is not read
     if (tiles > 0) {
-        hipLaunchKernelGGL(homography_score_kernel, dim3((unsigned)(tiles * pairs * chunks)), dim3(HOM_THREADS), 0, st, matches_l, matches_r,
-                           cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm, use_min_conf, min_conf,
-                           counts);
+        hipLaunchKernelGGL(homography_score_kernel<false>, dim3((unsigned)(tiles * pairs * chunks)), dim3(HOM_THREADS), 0, st, matches_l,
+                           matches_r, cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm, use_min_conf, min_conf,
+                           counts, 0, (int)H, nullptr);
         rc = check_launch("homography_score kernel");
         if (rc != PATS_OK) return rc;
     }
@@ -654,6 +661,41 @@ extern "C" int pats_homography_score_by_pair_f32(const float* matches_l, const f
     hipLaunchKernelGGL(homography_mask_kernel, dim3((unsigned)pairs), dim3(HOM_MASK_THREADS), 0, st, matches_l, matches_r, cf, pair_off,
                        counts_in, stride, cap, models, (int)H, thr, norm, use_min_conf, min_conf, best, best_count, inlier, moments);
     return check_launch("homography_mask kernel");
+}
+
+// ---- adaptive verification: this branch's two launchers for adaptive.hip's host side ------------------------------------------------
+static_assert(HOM_TILE == ADAPTIVE_TILE && HOM_CHUNK == ADAPTIVE_CHUNK, "adaptive.hip sizes the rounds' grids");
+
+static int hom_adaptive_round(const AdaptiveCall& c, const float* conf, int tiles, int h_lo, int h_hi, const int32_t* stopped,
+                              hipStream_t st) {
+    const int64_t chunks = ceil_div(h_hi - h_lo, HOM_CHUNK);
+    hipLaunchKernelGGL(homography_score_kernel<true>, dim3((unsigned)(tiles * c.pairs * chunks)), dim3(HOM_THREADS), 0, st, c.matches_l,
+                       c.matches_r, conf, c.pair_off, c.counts_in, c.stride, c.cap, (int)c.pairs, (int)chunks, c.models, (int)c.H, c.thr,
+                       c.norm, c.use_min_conf, c.min_conf, c.counts, h_lo, h_hi, stopped);
+    return check_launch("homography_score kernel (a round)");
+}
+
+static int hom_adaptive_mask(const AdaptiveCall& c, const float* conf, hipStream_t st) {
+    hipLaunchKernelGGL(homography_mask_kernel, dim3((unsigned)c.pairs), dim3(HOM_MASK_THREADS), 0, st, c.matches_l, c.matches_r, conf,
+                       c.pair_off, c.counts_in, c.stride, c.cap, c.models, (int)c.H, c.thr, c.norm, c.use_min_conf, c.min_conf, c.best,
+                       c.best_count, c.inlier, c.moments);
+    return check_launch("homography_mask kernel");
+}
+
+extern "C" size_t pats_homography_score_adaptive_workspace_bytes(int64_t pairs, int64_t H, int64_t cap) {
+    (void)H; (void)cap;
+    return adaptive_workspace_bytes(pairs);
+}
+
+extern "C" int pats_homography_score_adaptive_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf,
+        const int64_t* pair_off, int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t H,
+        const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts, int32_t* best, int64_t* best_count,
+        uint8_t* inlier, double* moments, void* workspace, size_t workspace_bytes, pats_stream_t stream, double confidence,
+        int sample_size, int models_per_sample, int64_t round_models, int32_t* used, int32_t* participating) {
+    const AdaptiveCall c{matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap, models, H, thr, norm, use_min_conf, min_conf,
+                         counts, best, best_count, inlier, moments, workspace, workspace_bytes, stream, confidence, sample_size,
+                         models_per_sample, round_models, used, participating};
+    return adaptive_score_by_pair("homography_score_adaptive_by_pair", c, hom_adaptive_round, hom_adaptive_mask);
 }
 
 extern "C" size_t pats_homography_refit_workspace_bytes(int64_t pairs) {

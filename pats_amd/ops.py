@@ -2054,6 +2054,87 @@ def homography_refit_by_pair(best_count, moments=None, models=None, best=None, n
     return out
 
 
+def _score_adaptive_by_pair(fn, branch, matches_l, matches_r, models, thr, confidence, sample_size, models_per_sample, round_models,
+                            pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs):
+    """What the two adaptive verifications share - everything but the C entry (branch = "epipolar" or "homography")."""
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
+                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("%s: min_conf needs conf" % fn)
+    confidence, s, g, B = float(confidence), int(sample_size), int(models_per_sample), int(round_models)
+    if not 0.0 < confidence < 1.0:                    # false for a NaN
+        raise RuntimeError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
+    if not (1 <= s <= 16 and 1 <= g <= 16):
+        raise RuntimeError("%s: sample_size = %d and models_per_sample = %d must lie in 1 .. 16" % (fn, s, g))
+    if B < 64 or B % 64:
+        raise RuntimeError("%s: round_models = %d must be a positive multiple of 64" % (fn, B))
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
+        raise RuntimeError("%s: models must be [pairs,H,3,3]" % fn)
+    H = int(models.shape[1])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("%s: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % (fn, pairs))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    if -(-H // B) > 256:
+        raise RuntimeError("%s: round_models = %d gives %d rounds for H = %d (at most 256)" % (fn, B, -(-H // B), H))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("%s: conf must be [cap]" % fn)
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
+            ("inlier", torch.uint8, (cap,))]
+    if moments:
+        want.append(("moments", torch.float64, (pairs, 9, 9)))
+    want += [("used", torch.int32, (pairs,)), ("participating", torch.int32, (pairs,))]
+    out = _bp_outputs(fn, want, out, dev)
+    nws = getattr(_L(), "pats_%s_score_adaptive_workspace_bytes" % branch)(pairs, H, cap)
+    ws = _workspace(nws, dev)
+    inl = out[3]
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else ml
+    _check(getattr(_L(), "pats_%s_score_adaptive_by_pair_f32" % branch)(
+        _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H, _ptr(thr), _ptr(norm),
+        0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
+        _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream(), confidence, s, g, B, _ptr(out[-2]), _ptr(out[-1])), fn)
+    return out
+
+
+def epipolar_score_adaptive_by_pair(matches_l, matches_r, models, thr, confidence, sample_size, models_per_sample=1, round_models=256,
+                                    pair_off=None, stride=None, counts=None, conf=None, min_conf=None, norm=None, moments=False,
+                                    out=None, pairs=None):
+    """epipolar_score_by_pair with plain RANSAC's stopping rule, ON THE DEVICE, no host read
+    (pats_epipolar_score_adaptive_by_pair_f32; include/pats_amd.h, "Per-pair adaptive verification", holds the definition): a
+    pair's models are tested in rounds of round_models (a positive multiple of 64, at most 256 rounds); after round r, with c the
+    largest count so far, k = T_r // models_per_sample samples seen and w = c / participating, the pair stops iff
+    (1 - w^sample_size)^k <= 1 - confidence - float64, a fixed order of multiplications, reproducible on the host bit for bit.
+    sample_size: 8, 5 or 4 for the three samplers; models_per_sample: 10 for the 5-point models.  Every other argument as
+    epipolar_score_by_pair takes it.
+    Returns epipolar_score_by_pair's tuple - counts are exactly 0 from used[p] on; best, best_count, inlier and moments are what the
+    fixed budget gives with models[p, used[p]:] zeroed - followed by used [pairs] int32 (the models tested; H for a pair that never
+    stopped) and participating [pairs] int32 (the matches that took part).  out: the six (seven) destinations."""
+    return _score_adaptive_by_pair("epipolar_score_adaptive_by_pair", "epipolar", matches_l, matches_r, models, thr, confidence, sample_size,
+                                   models_per_sample, round_models, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs)
+
+
+def homography_score_adaptive_by_pair(matches_l, matches_r, models, thr, confidence, sample_size, models_per_sample=1, round_models=256,
+                                      pair_off=None, stride=None, counts=None, conf=None, min_conf=None, norm=None, moments=False,
+                                      out=None, pairs=None):
+    """homography_score_by_pair with the stopping rule of epipolar_score_adaptive_by_pair
+    (pats_homography_score_adaptive_by_pair_f32): the same arguments, the same rule, the same outputs, the forward transfer error as
+    the test.  sample_size is 4 for the 4-point hypotheses."""
+    return _score_adaptive_by_pair("homography_score_adaptive_by_pair", "homography", matches_l, matches_r, models, thr, confidence,
+                                   sample_size, models_per_sample, round_models, pair_off, stride, counts, conf, min_conf, norm, moments,
+                                   out, pairs)
+
+
 # ------------------------------------------------------------------------------------------------
 # ragged batches: pairs of different grids in one throughput batch (PairTable; per-cell tensors packed over cells)
 # ------------------------------------------------------------------------------------------------
