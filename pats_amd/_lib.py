@@ -252,7 +252,7 @@ SIGNATURES = {
     "pats_epipolar_pose_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
                                                c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
-    # per-pair homographies: 4-point hypotheses, verification, refit (csrc/homography.hip)
+    # per-pair homographies: 4-point hypotheses (csrc/hypotheses.hip), verification (csrc/epipolar.hip), refit (csrc/homography.hip)
     "pats_homography_hypotheses_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pats_homography_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
                                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),

@@ -527,6 +527,34 @@ def hypothesize5_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=
     return hyp
 
 
+def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, moments, adaptive=None):
+    """What the four verify functions share; score = the ops function, key = "verified" / "verified_h".  adaptive: None for the fixed
+    budget, else (confidence, sample_size, models_per_sample, round_models) - `key`_used is stored too."""
+    more = {}
+    if adaptive is not None:
+        confidence, sample_size, models_per_sample, round_models = adaptive
+        if not 0.0 < float(confidence) < 1.0:         # false for a NaN; before any device work
+            raise ValueError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
+        if round_models is None:
+            round_models = 320 if models_per_sample == 10 else 256
+        more = {"confidence": confidence, "sample_size": sample_size, "models_per_sample": models_per_sample, "round_models": round_models}
+    _check_on(fn, out, on)
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        idx = _caller_of_dev(out, models.device)
+        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    ml, mr, conf, seg = _lists_on(out, cap, on)
+    res = score(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, moments=moments, **more,
+                **seg)
+    out[key], out[key + "_on"] = (res if adaptive is None else res[:-2]), on
+    out[key + "_models"] = models                     # slot order: the refit's source when no moments were asked for
+    if adaptive is not None:
+        out[key + "_used"] = res[-2:]
+    return res
+
+
 def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
     """Device side, after the matching (and after topk_by_pair for on="topk"): every pair's H candidate epipolar models
     (models [pairs,H,3,3], thr [pairs], norm [pairs,8] or None - all float32 GPU tensors in the CALLER's pair order) tested against
@@ -537,19 +565,7 @@ def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", mo
     that were scored - [M_cap] for "all", [pairs*K] for "topk" - [, moments [pairs,9,9] float64]) to the result and returns it; rows
     in SLOT order for a mixed pack (models / thr / norm are permuted to it on the device; split_verified_by_pair hands the pairs
     back in the caller's order).  The matches, the regrouped lists and a top-K of the same step are not touched."""
-    _check_on("verify_by_pair", out, on)
-    if min_conf is not None and "match_conf" not in out:
-        raise ValueError("verify_by_pair: min_conf needs a result made with confidence=True")
-    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
-        idx = _caller_of_dev(out, models.device)
-        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
-        norm = None if norm is None else norm.index_select(0, idx)
-    ml, mr, conf, seg = _lists_on(out, cap, on)
-    ver = ops.epipolar_score_by_pair(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm,
-                                     moments=moments, **seg)
-    out["verified"], out["verified_on"] = ver, on
-    out["verified_models"] = models                   # slot order: pose_by_pair's source when no moments were asked for
-    return ver
+    return _verify("verify_by_pair", ops.epipolar_score_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, moments)
 
 
 def split_verified_by_pair(out, cap):
@@ -634,19 +650,7 @@ def verify_h_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", 
     were scored [, moments [pairs,9,9] float64]) to the result and returns it; rows in SLOT order for a mixed pack, as
     `verified`'s.  `verified_h_on` and `verified_h_models` go with it.  `verified` and `pose` are never touched: a caller runs
     both branches on one result and compares best_count of the two - choosing between the models stays with the caller."""
-    _check_on("verify_h_by_pair", out, on)
-    if min_conf is not None and "match_conf" not in out:
-        raise ValueError("verify_h_by_pair: min_conf needs a result made with confidence=True")
-    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
-        idx = _caller_of_dev(out, models.device)
-        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
-        norm = None if norm is None else norm.index_select(0, idx)
-    ml, mr, conf, seg = _lists_on(out, cap, on)
-    ver = ops.homography_score_by_pair(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm,
-                                       moments=moments, **seg)
-    out["verified_h"], out["verified_h_on"] = ver, on
-    out["verified_h_models"] = models                 # slot order: homography_by_pair's source when no moments were asked for
-    return ver
+    return _verify("verify_h_by_pair", ops.homography_score_by_pair, "verified_h", out, cap, models, thr, norm, min_conf, on, moments)
 
 
 def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
@@ -673,29 +677,6 @@ def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
     return res
 
 
-def _verify_adaptive(fn, score, key, out, cap, models, thr, confidence, sample_size, models_per_sample, round_models, norm, min_conf, on,
-                     moments):
-    """What verify_adaptive_by_pair and verify_h_adaptive_by_pair share; score = the ops function, key = "verified" / "verified_h"."""
-    if not 0.0 < float(confidence) < 1.0:             # false for a NaN; before any device work
-        raise ValueError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
-    _check_on(fn, out, on)
-    if min_conf is not None and "match_conf" not in out:
-        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
-    if round_models is None:
-        round_models = 320 if models_per_sample == 10 else 256
-    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
-        idx = _caller_of_dev(out, models.device)
-        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
-        norm = None if norm is None else norm.index_select(0, idx)
-    ml, mr, conf, seg = _lists_on(out, cap, on)
-    res = score(ml, mr, models, thr, confidence, sample_size, models_per_sample=models_per_sample, round_models=round_models,
-                conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, moments=moments, **seg)
-    out[key], out[key + "_on"] = res[:-2], on
-    out[key + "_models"] = models                     # slot order, as the fixed-budget functions keep them
-    out[key + "_used"] = res[-2:]
-    return res
-
-
 def verify_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,
                             min_conf=None, on="all", moments=False):
     """verify_by_pair that stops each pair at a RANSAC confidence, on the device (ops.epipolar_score_adaptive_by_pair: no host
@@ -706,8 +687,8 @@ def verify_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, mode
     Stores verify_by_pair's tuple as `verified` (with `verified_on`, `verified_models`): pose_by_pair and split_verified_by_pair
     work on it unchanged; counts are 0 from used[p] on.  Also stores `verified_used` = (used [pairs] int32, participating [pairs]
     int32) and returns the tuple followed by those two, in SLOT order like counts.  A confidence outside (0, 1) raises ValueError."""
-    return _verify_adaptive("verify_adaptive_by_pair", ops.epipolar_score_adaptive_by_pair, "verified", out, cap, models, thr, confidence,
-                            sample_size, models_per_sample, round_models, norm, min_conf, on, moments)
+    return _verify("verify_adaptive_by_pair", ops.epipolar_score_adaptive_by_pair, "verified", out, cap, models, thr, norm, min_conf, on,
+                   moments, adaptive=(confidence, sample_size, models_per_sample, round_models))
 
 
 def verify_h_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,
@@ -715,5 +696,5 @@ def verify_h_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, mo
     """verify_h_by_pair with the stopping rule of verify_adaptive_by_pair (ops.homography_score_adaptive_by_pair); sample_size = 4
     for hypothesize_h_by_pair's models.  Stores `verified_h` (with `verified_h_on`, `verified_h_models`: homography_by_pair works
     on it unchanged) and `verified_h_used` = (used, participating); returns the tuple followed by those two."""
-    return _verify_adaptive("verify_h_adaptive_by_pair", ops.homography_score_adaptive_by_pair, "verified_h", out, cap, models, thr,
-                            confidence, sample_size, models_per_sample, round_models, norm, min_conf, on, moments)
+    return _verify("verify_h_adaptive_by_pair", ops.homography_score_adaptive_by_pair, "verified_h", out, cap, models, thr, norm, min_conf,
+                   on, moments, adaptive=(confidence, sample_size, models_per_sample, round_models))

@@ -1,7 +1,7 @@
 // Per-pair adaptive verification - what the epipolar and the homography branch share: the stopping rule, the per-pair update kernel
 // that applies it after every round of models, and the host side that checks the arguments and issues the rounds.  The score and
-// the mask kernels are the branches' own (epipolar.hip, homography.hip: the fixed-budget kernels, restricted to a round's models);
-// they reach this file as two launchers.  include/pats_amd.h states the definition ("Per-pair adaptive verification");
+// the mask kernels are epipolar.hip's (the fixed-budget kernels of the branch's family, restricted to a round's models); they reach
+// this file as two launchers.  include/pats_amd.h states the definition ("Per-pair adaptive verification");
 // docs/kernels.md 4.12 the design.
 //
 //   update  one workgroup per pair after round r, 256 threads: the argmax of counts[p, r B .. T_r) (the lowest index among equals)

@@ -1,21 +1,28 @@
-// Per-pair verification of candidate epipolar models against the hand-over's matches: for every pair of a batch H 3x3 models are
-// tested against every match of the pair's segment (squared Sampson error against thr^2, without the division), the model with the
-// most inliers wins (lowest index on a tie), its inlier mask is written beside the match lists and - on request - the 9x9 moment
-// matrix of its inliers, the input of a least-squares refit.  No host read.  include/pats_amd.h states the definition;
-// docs/kernels.md 4.7 the design.
+// Per-pair verification of candidate models against the hand-over's matches, written once for both model families: for every pair of
+// a batch H 3x3 models are tested against every match of the pair's segment, the model with the most inliers wins (lowest index on a
+// tie), its inlier mask is written beside the match lists and - on request - the 9x9 moment matrix of its inliers, the input of a
+// least-squares refit.  No host read.  include/pats_amd.h states the definitions; docs/kernels.md 4.7 the design (4.11: the
+// homographies, 4.12: the adaptive rounds).
+// The file and the EPI_ constants are named like epipolar.hpp's epi_ helpers, which the homography branch shares as well.
 //
-//   score   grid = tiles x pairs x model chunks, 256 threads.  A thread keeps EPI_R = 8 matches (normalised once, as four packed
-//           pairs of float2 lanes) in registers and walks the EPI_CHUNK = 256 models of its chunk; a model is nine wave-uniform floats
-//           (scalar loads, one model ahead).  Per model: v_pk_fma_f32 on the four pairs, the verdicts as wave ballots, their
-//           popcounts added on the scalar unit and kept by lane h % 64 in a counter register; every 64 models the
-//           register goes to LDS, at the end the four waves' counters are added and ONE integer atomic per workgroup and model with a
-//           non-zero count goes to counts[p, h] (integer adds: the order does not matter).  Blocks past a segment's end return.
-//           A template on ROUND: <false> is this fixed budget; <true> is one round of the adaptive verification (adaptive.hip) - the
+// A family is a struct with the two things that differ: test2, THE arithmetic of its test (two matches against one model), and
+// accumulate, a match's contribution to the moments.
+//   Epipolar    squared Sampson error against thr^2, without the division; the moments of q = vec(x_r x_l^T)
+//   Homography  squared forward transfer error against thr^2, without the division; the moments of the two DLT rows A_i, B_i
+//
+//   score   verify_score_kernel<T, ROUND>: grid = tiles x pairs x model chunks, 256 threads.  A thread keeps EPI_R = 8 matches
+//           (normalised once, as four packed pairs of float2 lanes) in registers and walks the EPI_CHUNK = 256 models of its chunk;
+//           a model is nine wave-uniform floats (scalar loads, one model ahead).  Per model: v_pk_fma_f32 on the four pairs, the
+//           verdicts as wave ballots, their popcounts added on the scalar unit and kept by lane h % 64 in a counter register; every
+//           64 models the register goes to LDS, at the end the four waves' counters are added and ONE integer atomic per workgroup
+//           and model with a non-zero count goes to counts[p, h] (integer adds: the order does not matter).  Blocks past a segment's
+//           end return.  ROUND: <false> is the fixed budget; <true> is one round of the adaptive verification (adaptive.hip) - the
 //           models [h_begin, h_stop) only, and the workgroups of a pair that has stopped return on its flag.
-//   argmax  one workgroup per pair over counts[p, :]: the largest count, the lowest index that holds it
-//   mask    one workgroup per pair: the winner's verdict for every match of the segment with the arithmetic of the score kernel
-//           (same device function: the mask and the winner's count agree exactly), the moments in float64 in a fixed order
-//           (thread-local in index order, an xor tree over the wave, the waves in order)
+//   argmax  verify_argmax_kernel, one for both families: one workgroup per pair over counts[p, :], the largest count, the lowest
+//           index that holds it
+//   mask    verify_mask_kernel<T>: one workgroup per pair, the winner's verdict for every match of the segment with the arithmetic of
+//           the score kernel (same device function: the mask and the winner's count agree exactly), the moments in float64 in a fixed
+//           order (thread-local in index order, an xor tree over the wave, the waves in order)
 // A match that does not participate (outside the segment, gated by min_conf, a non-finite coordinate) carries a NaN x_l: every
 // comparison with it is false, the inner loop needs no mask.
 #include "common.hpp"
@@ -25,34 +32,77 @@ namespace pats {
 
 constexpr int EPI_THREADS = 256;
 constexpr int EPI_WAVES = EPI_THREADS / WAVE;
-constexpr int EPI_R = 8;                               // matches per thread
-constexpr int EPI_TILE = EPI_THREADS * EPI_R;          // matches per workgroup
-constexpr int EPI_CHUNK = 256;                         // models per workgroup
+constexpr int EPI_R = 8;                            // matches per thread
+constexpr int EPI_TILE = EPI_THREADS * EPI_R; // matches per workgroup
+constexpr int EPI_CHUNK = 256;                      // models per workgroup
 constexpr int EPI_MAX_H = 65536;
 constexpr int EPI_MASK_THREADS = 512;
 constexpr int EPI_MASK_WAVES = EPI_MASK_THREADS / WAVE;
-constexpr int EPI_MOM = 45;                            // upper triangle of the 9x9 moment matrix
+constexpr int EPI_MOM = 45;                         // upper triangle of the 9x9 moment matrix
+static_assert(EPI_TILE == ADAPTIVE_TILE && EPI_CHUNK == ADAPTIVE_CHUNK, "adaptive.hip sizes the rounds' grids");
 
-typedef float e2f __attribute__((ext_vector_type(2)));
+typedef float v2f __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ e2f epi_fma(e2f a, e2f b, e2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ e2f epi_splat(float v) { return e2f{v, v}; }
+__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ v2f pk_splat(float v) { return v2f{v, v}; }
 
-// two matches against one model: r^2, thr^2 den and den.  THE arithmetic of the test - the score and the mask kernel both call it;
-// match k is an inlier iff den[k] > 0 and r2[k] <= lim[k].
-__device__ __forceinline__ void epi_test2(const float (&e)[9], float t2, e2f l0, e2f l1, e2f r0, e2f r1, e2f& r2, e2f& lim, e2f& den) {
-    const e2f a0 = epi_fma(epi_splat(e[0]), l0, epi_fma(epi_splat(e[1]), l1, epi_splat(e[2])));
-    const e2f a1 = epi_fma(epi_splat(e[3]), l0, epi_fma(epi_splat(e[4]), l1, epi_splat(e[5])));
-    const e2f a2 = epi_fma(epi_splat(e[6]), l0, epi_fma(epi_splat(e[7]), l1, epi_splat(e[8])));
-    const e2f b0 = epi_fma(epi_splat(e[0]), r0, epi_fma(epi_splat(e[3]), r1, epi_splat(e[6])));
-    const e2f b1 = epi_fma(epi_splat(e[1]), r0, epi_fma(epi_splat(e[4]), r1, epi_splat(e[7])));
-    const e2f r = epi_fma(r0, a0, epi_fma(r1, a1, a2));
-    den = epi_fma(a0, a0, epi_fma(a1, a1, epi_fma(b0, b0, b1 * b1)));
-    r2 = r * r;
-    lim = epi_splat(t2) * den;
-}
+// The families.  test2: two matches against one model - match k is an inlier iff w[k] > 0 and s[k] <= lim[k]; the score and the mask
+// kernel both call it.  accumulate: an inlier's 45 products in float64 (the products of two float32 are exact).  The strings are the
+// names the launch checks report.
+struct Epipolar {
+    static constexpr const char *SCORE = "epipolar_score kernel", *ROUND = "epipolar_score kernel (a round)",
+                                *ARGMAX = "epipolar_argmax kernel", *MASK = "epipolar_mask kernel";
+    // s = r^2, lim = thr^2 den, w = den
+    static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
+        const v2f a0 = pk_fma(pk_splat(e[0]), l0, pk_fma(pk_splat(e[1]), l1, pk_splat(e[2])));
+        const v2f a1 = pk_fma(pk_splat(e[3]), l0, pk_fma(pk_splat(e[4]), l1, pk_splat(e[5])));
+        const v2f a2 = pk_fma(pk_splat(e[6]), l0, pk_fma(pk_splat(e[7]), l1, pk_splat(e[8])));
+        const v2f b0 = pk_fma(pk_splat(e[0]), r0, pk_fma(pk_splat(e[3]), r1, pk_splat(e[6])));
+        const v2f b1 = pk_fma(pk_splat(e[1]), r0, pk_fma(pk_splat(e[4]), r1, pk_splat(e[7])));
+        const v2f r = pk_fma(r0, a0, pk_fma(r1, a1, a2));
+        w = pk_fma(a0, a0, pk_fma(a1, a1, pk_fma(b0, b0, b1 * b1)));
+        s = r * r;
+        lim = pk_splat(t2) * w;
+    }
+    static __device__ __forceinline__ void accumulate(float xl0, float xl1, float xr0, float xr1, double (&acc)[EPI_MOM]) {
+        const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
+        const double q[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};       // vec(x_r x_l^T): exact products
+        int k = 0;
+#pragma unroll
+        for (int u = 0; u < 9; ++u)
+#pragma unroll
+            for (int v = u; v < 9; ++v) acc[k++] += q[u] * q[v];
+    }
+};
 
-__device__ __forceinline__ void epi_model(const float* __restrict__ m, float (&e)[9]) {
+struct Homography {
+    static constexpr const char *SCORE = "homography_score kernel", *ROUND = "homography_score kernel (a round)",
+                                *ARGMAX = "homography_argmax kernel", *MASK = "homography_mask kernel";
+    // s = d0^2 + d1^2, lim = thr^2 a2^2, w = a2^2
+    static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
+        const v2f a0 = pk_fma(pk_splat(e[0]), l0, pk_fma(pk_splat(e[1]), l1, pk_splat(e[2])));
+        const v2f a1 = pk_fma(pk_splat(e[3]), l0, pk_fma(pk_splat(e[4]), l1, pk_splat(e[5])));
+        const v2f a2 = pk_fma(pk_splat(e[6]), l0, pk_fma(pk_splat(e[7]), l1, pk_splat(e[8])));
+        const v2f d0 = pk_fma(-r0, a2, a0);
+        const v2f d1 = pk_fma(-r1, a2, a1);
+        s = pk_fma(d0, d0, d1 * d1);
+        w = a2 * a2;
+        lim = pk_splat(t2) * w;
+    }
+    static __device__ __forceinline__ void accumulate(float xl0, float xl1, float xr0, float xr1, double (&acc)[EPI_MOM]) {
+        const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
+        // the rows A_i and B_i: the products of two float32 are exact in float64
+        const double qa[9] = {-a0, -a1, -1.0, 0.0, 0.0, 0.0, b0 * a0, b0 * a1, b0};
+        const double qb[9] = {0.0, 0.0, 0.0, -a0, -a1, -1.0, b1 * a0, b1 * a1, b1};
+        int k = 0;
+#pragma unroll
+        for (int u = 0; u < 9; ++u)
+#pragma unroll
+            for (int v = u; v < 9; ++v) acc[k++] += qa[u] * qa[v] + qb[u] * qb[v];
+    }
+};
+
+__device__ __forceinline__ void verify_model(const float* __restrict__ m, float (&e)[9]) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) e[k] = m[k];
 }
@@ -60,13 +110,13 @@ __device__ __forceinline__ void epi_model(const float* __restrict__ m, float (&e
 // ROUND = false: the fixed budget - models [0, H) in `chunks` chunks; h_begin, h_stop and stopped are not read.  ROUND = true: a round
 // of the adaptive verification (adaptive.hip issues them) - models [h_begin, h_stop) in `chunks` chunks, and the workgroups of a
 // pair whose stopped flag is set return at once
-template <bool ROUND>
+template <class T, bool ROUND>
 __global__ void __launch_bounds__(EPI_THREADS)
-epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
-                      const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
-                      int pairs, int chunks, const float* __restrict__ models, int H, const float* __restrict__ thr,
-                      const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts, int h_begin, int h_stop,
-                      const int32_t* __restrict__ stopped) {
+verify_score_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
+                    const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
+                    int pairs, int chunks, const float* __restrict__ models, int H, const float* __restrict__ thr,
+                    const float* __restrict__ norm, int gate, float min_conf, int32_t* __restrict__ counts, int h_begin, int h_stop,
+                    const int32_t* __restrict__ stopped) {
     __shared__ int wave_cnt[EPI_WAVES][EPI_CHUNK];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -89,36 +139,36 @@ epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ m
     const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
     const float* conf = conf_ ? conf_ + lo : nullptr;
     const EpiNorm nm = epi_norm(norm, p);
-    e2f l0[EPI_R / 2], l1[EPI_R / 2], r0[EPI_R / 2], r1[EPI_R / 2];
+    v2f l0[EPI_R / 2], l1[EPI_R / 2], r0[EPI_R / 2], r1[EPI_R / 2];
 #pragma unroll
     for (int k = 0; k < EPI_R / 2; ++k) {
         float a0, a1, a2, a3, c0, c1, c2, c3;
         epi_load(ml, mr, conf, (uint32_t)i0 + (uint32_t)((2 * k) * EPI_THREADS + tid), n, norm != nullptr, nm, gate != 0, min_conf, a0, a1, a2, a3);
         epi_load(ml, mr, conf, (uint32_t)i0 + (uint32_t)((2 * k + 1) * EPI_THREADS + tid), n, norm != nullptr, nm, gate != 0, min_conf, c0, c1, c2, c3);
-        l0[k] = e2f{a0, c0}; l1[k] = e2f{a1, c1}; r0[k] = e2f{a2, c2}; r1[k] = e2f{a3, c3};
+        l0[k] = v2f{a0, c0}; l1[k] = v2f{a1, c1}; r0[k] = v2f{a2, c2}; r1[k] = v2f{a3, c3};
     }
 
-    const int h_lo = (ROUND ? h_begin : 0) + chunk * EPI_CHUNK;              // the fixed budget: every model, [0, H)
+    const int h_lo = (ROUND ? h_begin : 0) + chunk * EPI_CHUNK;           // the fixed budget: every model, [0, H)
     const int h_end = ROUND ? h_stop : H;
     const int nmod = h_end - h_lo < EPI_CHUNK ? h_end - h_lo : EPI_CHUNK;     // >= 1: chunks = ceil((h_end - h_begin) / EPI_CHUNK)
     const float* m = models + ((int64_t)p * H + h_lo) * 9;
     float e[9];
-    epi_model(m, e);
+    verify_model(m, e);
     for (int h0 = 0; h0 < nmod; h0 += WAVE) {
         const int jn = nmod - h0 < WAVE ? nmod - h0 : WAVE;
         int acc = 0;
         for (int j = 0; j < jn; ++j) {
             float en[9];
             const int hn = h0 + j + 1 < nmod ? h0 + j + 1 : h0 + j;            // one model ahead (the last one again: in bounds)
-            epi_model(m + (int64_t)hn * 9, en);
+            verify_model(m + (int64_t)hn * 9, en);
             int cnt = 0;
 #pragma unroll
             for (int k = 0; k < EPI_R / 2; ++k) {
-                e2f r2, lim, den;
-                epi_test2(e, t2, l0[k], l1[k], r0[k], r1[k], r2, lim, den);
+                v2f s, lim, w;
+                T::test2(e, t2, l0[k], l1[k], r0[k], r1[k], s, lim, w);
                 // the two comparisons as ballots of their own, combined on the scalar unit
-                cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(den.x > 0.0f) & __builtin_amdgcn_ballot_w64(r2.x <= lim.x)) +
-                       __builtin_popcountll(__builtin_amdgcn_ballot_w64(den.y > 0.0f) & __builtin_amdgcn_ballot_w64(r2.y <= lim.y));
+                cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(w.x > 0.0f) & __builtin_amdgcn_ballot_w64(s.x <= lim.x)) +
+                       __builtin_popcountll(__builtin_amdgcn_ballot_w64(w.y > 0.0f) & __builtin_amdgcn_ballot_w64(s.y <= lim.y));
             }
             acc = lane == j ? cnt : acc;
 #pragma unroll
@@ -136,8 +186,8 @@ epipolar_score_kernel(const float* __restrict__ ml_, const float* __restrict__ m
 }
 
 // one workgroup per pair: the largest count of counts[p, :], the lowest index that holds it
-__global__ void __launch_bounds__(256) epipolar_argmax_kernel(const int32_t* __restrict__ counts, int H, int32_t* __restrict__ best,
-                                                               int64_t* __restrict__ best_count) {
+__global__ void __launch_bounds__(256) verify_argmax_kernel(const int32_t* __restrict__ counts, int H, int32_t* __restrict__ best,
+                                                             int64_t* __restrict__ best_count) {
     __shared__ int sv[256], si[256];
     const int64_t p = blockIdx.x;
     const int tid = threadIdx.x;
@@ -160,12 +210,13 @@ __global__ void __launch_bounds__(256) epipolar_argmax_kernel(const int32_t* __r
 }
 
 // one workgroup per pair: the winner's inlier mask (the rows outside the segments were zeroed before) and the moments
+template <class T>
 __global__ void __launch_bounds__(EPI_MASK_THREADS)
-epipolar_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
-                     const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
-                     const float* __restrict__ models, int H, const float* __restrict__ thr, const float* __restrict__ norm, int gate,
-                     float min_conf, const int32_t* __restrict__ best, const int64_t* __restrict__ best_count,
-                     uint8_t* __restrict__ inlier, double* __restrict__ moments) {
+verify_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, const float* __restrict__ conf_,
+                   const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
+                   const float* __restrict__ models, int H, const float* __restrict__ thr, const float* __restrict__ norm, int gate,
+                   float min_conf, const int32_t* __restrict__ best, const int64_t* __restrict__ best_count,
+                   uint8_t* __restrict__ inlier, double* __restrict__ moments) {
     __shared__ double part[EPI_MASK_WAVES][EPI_MOM];
     const int64_t p = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -182,7 +233,7 @@ epipolar_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
         int h = best[p];
         h = h < 0 ? 0 : (h >= H ? H - 1 : h);
         float e[9];
-        epi_model(models + ((int64_t)p * H + h) * 9, e);
+        verify_model(models + ((int64_t)p * H + h) * 9, e);
         const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
         const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
         const float* conf = conf_ ? conf_ + lo : nullptr;
@@ -191,19 +242,11 @@ epipolar_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
             const uint32_t i = i0 + tid;
             float xl0, xl1, xr0, xr1;
             epi_load(ml, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, xl0, xl1, xr0, xr1);
-            e2f r2, lim, den;
-            epi_test2(e, t2, epi_splat(xl0), epi_splat(xl1), epi_splat(xr0), epi_splat(xr1), r2, lim, den);
-            const bool in0 = den.x > 0.0f && r2.x <= lim.x;
+            v2f s, lim, w;
+            T::test2(e, t2, pk_splat(xl0), pk_splat(xl1), pk_splat(xr0), pk_splat(xr1), s, lim, w);
+            const bool in0 = w.x > 0.0f && s.x <= lim.x;
             if (i < n) inlier[lo + i] = in0 ? 1 : 0;
-            if (moments && in0) {
-                const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
-                const double q[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};       // vec(x_r x_l^T): exact products
-                int k = 0;
-#pragma unroll
-                for (int u = 0; u < 9; ++u)
-#pragma unroll
-                    for (int v = u; v < 9; ++v) acc[k++] += q[u] * q[v];
-            }
+            if (moments && in0) T::accumulate(xl0, xl1, xr0, xr1, acc);
         }
     }
     if (!moments) return;
@@ -232,42 +275,34 @@ epipolar_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
 
 using namespace pats;
 
-extern "C" int64_t pats_epipolar_max_h(void) { return EPI_MAX_H; }
-
-extern "C" size_t pats_epipolar_workspace_bytes(int64_t pairs, int64_t H, int64_t cap) {
-    (void)pairs; (void)H; (void)cap;
-    return 0;                                           // the counts are accumulated in the output itself
-}
-
-extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
-                                               int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
-                                               int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
-                                               int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
-                                               void* workspace, size_t workspace_bytes, pats_stream_t stream) {
-    (void)workspace;
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", matches_l, 8);
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", matches_r, 8);
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", models, 4);
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", thr, 4);
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", counts, 4);
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", best, 4);
-    PATS_REQUIRE_PTR("epipolar_score_by_pair", best_count, 8);
-    PATS_REQUIRE(inlier, "epipolar_score_by_pair: null inlier");
-    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", conf, 4);     // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", norm, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", pair_off, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", counts_in, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_score_by_pair", moments, 8);
-    int rc = epi_check_segments("epipolar_score_by_pair", pair_off, counts_in, stride, pairs, cap);
+// the fixed budget of family T; `who` = the entry point's name.  No workspace: the counts are accumulated in the output itself
+template <class T>
+static int verify_score_by_pair(const char* who, const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t H,
+                                const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts, int32_t* best,
+                                int64_t* best_count, uint8_t* inlier, double* moments, pats_stream_t stream) {
+    EPI_REQUIRE_PTR(matches_l, 8);
+    EPI_REQUIRE_PTR(matches_r, 8);
+    EPI_REQUIRE_PTR(models, 4);
+    EPI_REQUIRE_PTR(thr, 4);
+    EPI_REQUIRE_PTR(counts, 4);
+    EPI_REQUIRE_PTR(best, 4);
+    EPI_REQUIRE_PTR(best_count, 8);
+    PATS_REQUIRE(inlier, "%s: null inlier", who);
+    EPI_REQUIRE_ALIGNED(conf, 4);                    // optional pointers: null is aligned
+    EPI_REQUIRE_ALIGNED(norm, 4);
+    EPI_REQUIRE_ALIGNED(pair_off, 8);
+    EPI_REQUIRE_ALIGNED(counts_in, 8);
+    EPI_REQUIRE_ALIGNED(moments, 8);
+    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h("epipolar_score_by_pair", H);
+    rc = epi_check_h(who, H);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(!use_min_conf || conf, "epipolar_score_by_pair: min_conf needs conf");
-    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "epipolar_score_by_pair: min_conf = %g must be a non-negative number", (double)min_conf);
-    PATS_REQUIRE(workspace_bytes >= pats_epipolar_workspace_bytes(pairs, H, cap), "epipolar_score_by_pair: workspace too small");
+    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
+    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
     const int64_t longest = counts_in ? stride : cap;   // the grid comes from the sizes alone: no host read of the counts
     const int64_t tiles = ceil_div(longest, EPI_TILE), chunks = ceil_div(H, EPI_CHUNK);
-    PATS_REQUIRE(tiles * chunks <= 0x7fffffff / pairs, "epipolar_score_by_pair: pairs = %lld gives a grid of %lld x %lld x %lld workgroups (< 2^31)",
+    PATS_REQUIRE(tiles * chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld x %lld workgroups (< 2^31)", who,
                  (long long)pairs, (long long)tiles, (long long)pairs, (long long)chunks);
     hipStream_t st = as_stream(stream);
     rc = fill_bytes(counts, 0, (size_t)pairs * (size_t)H * sizeof(int32_t), st);
@@ -276,42 +311,64 @@ extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const flo
     if (rc != PATS_OK) return rc;
     const float* cf = use_min_conf ? conf : nullptr;    // without a threshold the confidence is not read
     if (tiles > 0) {
-        hipLaunchKernelGGL(epipolar_score_kernel<false>, dim3((unsigned)(tiles * pairs * chunks)), dim3(EPI_THREADS), 0, st, matches_l,
-                           matches_r, cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm, use_min_conf, min_conf,
-                           counts, 0, (int)H, nullptr);
-        rc = check_launch("epipolar_score kernel");
+        hipLaunchKernelGGL((verify_score_kernel<T, false>), dim3((unsigned)(tiles * pairs * chunks)), dim3(EPI_THREADS), 0, st,
+                           matches_l, matches_r, cf, pair_off, counts_in, stride, cap, (int)pairs, (int)chunks, models, (int)H, thr, norm,
+                           use_min_conf, min_conf, counts, 0, (int)H, nullptr);
+        rc = check_launch(T::SCORE);
         if (rc != PATS_OK) return rc;
     }
-    hipLaunchKernelGGL(epipolar_argmax_kernel, dim3((unsigned)pairs), dim3(256), 0, st, counts, (int)H, best, best_count);
-    rc = check_launch("epipolar_argmax kernel");
+    hipLaunchKernelGGL(verify_argmax_kernel, dim3((unsigned)pairs), dim3(256), 0, st, counts, (int)H, best, best_count);
+    rc = check_launch(T::ARGMAX);
     if (rc != PATS_OK) return rc;
-    hipLaunchKernelGGL(epipolar_mask_kernel, dim3((unsigned)pairs), dim3(EPI_MASK_THREADS), 0, st, matches_l, matches_r, cf, pair_off,
+    hipLaunchKernelGGL(verify_mask_kernel<T>, dim3((unsigned)pairs), dim3(EPI_MASK_THREADS), 0, st, matches_l, matches_r, cf, pair_off,
                        counts_in, stride, cap, models, (int)H, thr, norm, use_min_conf, min_conf, best, best_count, inlier, moments);
-    return check_launch("epipolar_mask kernel");
+    return check_launch(T::MASK);
 }
 
-// ---- adaptive verification: this branch's two launchers for adaptive.hip's host side ------------------------------------------------
-static_assert(EPI_TILE == ADAPTIVE_TILE && EPI_CHUNK == ADAPTIVE_CHUNK, "adaptive.hip sizes the rounds' grids");
-
-static int epi_adaptive_round(const AdaptiveCall& c, const float* conf, int tiles, int h_lo, int h_hi, const int32_t* stopped,
-                              hipStream_t st) {
+// the two launchers of family T for adaptive.hip's host side
+template <class T>
+static int verify_adaptive_round(const AdaptiveCall& c, const float* conf, int tiles, int h_lo, int h_hi, const int32_t* stopped,
+                                 hipStream_t st) {
     const int64_t chunks = ceil_div(h_hi - h_lo, EPI_CHUNK);
-    hipLaunchKernelGGL(epipolar_score_kernel<true>, dim3((unsigned)(tiles * c.pairs * chunks)), dim3(EPI_THREADS), 0, st, c.matches_l,
-                       c.matches_r, conf, c.pair_off, c.counts_in, c.stride, c.cap, (int)c.pairs, (int)chunks, c.models, (int)c.H, c.thr,
-                       c.norm, c.use_min_conf, c.min_conf, c.counts, h_lo, h_hi, stopped);
-    return check_launch("epipolar_score kernel (a round)");
+    hipLaunchKernelGGL((verify_score_kernel<T, true>), dim3((unsigned)(tiles * c.pairs * chunks)), dim3(EPI_THREADS), 0, st,
+                       c.matches_l, c.matches_r, conf, c.pair_off, c.counts_in, c.stride, c.cap, (int)c.pairs, (int)chunks, c.models,
+                       (int)c.H, c.thr, c.norm, c.use_min_conf, c.min_conf, c.counts, h_lo, h_hi, stopped);
+    return check_launch(T::ROUND);
 }
 
-static int epi_adaptive_mask(const AdaptiveCall& c, const float* conf, hipStream_t st) {
-    hipLaunchKernelGGL(epipolar_mask_kernel, dim3((unsigned)c.pairs), dim3(EPI_MASK_THREADS), 0, st, c.matches_l, c.matches_r, conf,
+template <class T>
+static int verify_adaptive_mask(const AdaptiveCall& c, const float* conf, hipStream_t st) {
+    hipLaunchKernelGGL(verify_mask_kernel<T>, dim3((unsigned)c.pairs), dim3(EPI_MASK_THREADS), 0, st, c.matches_l, c.matches_r, conf,
                        c.pair_off, c.counts_in, c.stride, c.cap, c.models, (int)c.H, c.thr, c.norm, c.use_min_conf, c.min_conf, c.best,
                        c.best_count, c.inlier, c.moments);
-    return check_launch("epipolar_mask kernel");
+    return check_launch(T::MASK);
 }
 
-extern "C" size_t pats_epipolar_score_adaptive_workspace_bytes(int64_t pairs, int64_t H, int64_t cap) {
-    (void)H; (void)cap;
-    return adaptive_workspace_bytes(pairs);
+// ---- the entry points (include/pats_amd.h) ---------------------------------------------------------------------------------------
+extern "C" int64_t pats_epipolar_max_h(void) { return EPI_MAX_H; }
+
+// the fixed budget needs no workspace (the counts are accumulated in the output itself), the adaptive one the stopped flags
+extern "C" size_t pats_epipolar_workspace_bytes(int64_t, int64_t, int64_t) { return 0; }
+extern "C" size_t pats_homography_score_workspace_bytes(int64_t, int64_t, int64_t) { return 0; }
+extern "C" size_t pats_epipolar_score_adaptive_workspace_bytes(int64_t pairs, int64_t, int64_t) { return adaptive_workspace_bytes(pairs); }
+extern "C" size_t pats_homography_score_adaptive_workspace_bytes(int64_t pairs, int64_t, int64_t) { return adaptive_workspace_bytes(pairs); }
+
+extern "C" int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                               int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                               int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                               int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                               void*, size_t, pats_stream_t stream) {
+    return verify_score_by_pair<Epipolar>("epipolar_score_by_pair", matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap,
+                                          models, H, thr, norm, use_min_conf, min_conf, counts, best, best_count, inlier, moments, stream);
+}
+
+extern "C" int pats_homography_score_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                                 int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                                 int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                                 int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                                 void*, size_t, pats_stream_t stream) {
+    return verify_score_by_pair<Homography>("homography_score_by_pair", matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap,
+                                            models, H, thr, norm, use_min_conf, min_conf, counts, best, best_count, inlier, moments, stream);
 }
 
 extern "C" int pats_epipolar_score_adaptive_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf,
@@ -322,5 +379,16 @@ extern "C" int pats_epipolar_score_adaptive_by_pair_f32(const float* matches_l, 
     const AdaptiveCall c{matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap, models, H, thr, norm, use_min_conf, min_conf,
                          counts, best, best_count, inlier, moments, workspace, workspace_bytes, stream, confidence, sample_size,
                          models_per_sample, round_models, used, participating};
-    return adaptive_score_by_pair("epipolar_score_adaptive_by_pair", c, epi_adaptive_round, epi_adaptive_mask);
+    return adaptive_score_by_pair("epipolar_score_adaptive_by_pair", c, verify_adaptive_round<Epipolar>, verify_adaptive_mask<Epipolar>);
+}
+
+extern "C" int pats_homography_score_adaptive_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf,
+        const int64_t* pair_off, int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t H,
+        const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts, int32_t* best, int64_t* best_count,
+        uint8_t* inlier, double* moments, void* workspace, size_t workspace_bytes, pats_stream_t stream, double confidence,
+        int sample_size, int models_per_sample, int64_t round_models, int32_t* used, int32_t* participating) {
+    const AdaptiveCall c{matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap, models, H, thr, norm, use_min_conf, min_conf,
+                         counts, best, best_count, inlier, moments, workspace, workspace_bytes, stream, confidence, sample_size,
+                         models_per_sample, round_models, used, participating};
+    return adaptive_score_by_pair("homography_score_adaptive_by_pair", c, verify_adaptive_round<Homography>, verify_adaptive_mask<Homography>);
 }

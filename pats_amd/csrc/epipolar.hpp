@@ -1,6 +1,6 @@
-// What the per-pair epipolar stages share (epipolar.hip: verification; hypotheses.hip: the 8-point hypotheses; hypotheses5.hip: the
-// 5-point hypotheses; pose.hip: the pose): how a pair's segment of the match lists, its normalisation and a match's point are read,
-// and the hypotheses' sampler.  include/pats_amd.h states all of it.
+// What the per-pair stages share (epipolar.hip: verification; hypotheses.hip: the 8-point and 4-point hypotheses; hypotheses5.hip: the
+// 5-point hypotheses; pose.hip: the pose; homography.hip: the refit): how a pair's segment of the match lists, its normalisation and
+// a match's point are read, and the hypotheses' sampler.  include/pats_amd.h states all of it.
 #pragma once
 #include "common.hpp"
 
@@ -84,6 +84,12 @@ __device__ __forceinline__ void epi_draw(uint64_t seed, uint32_t h, uint32_t m, 
 }
 
 // ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name) ------
+// PATS_REQUIRE_PTR / PATS_REQUIRE_ALIGNED for a host function that serves several entry points: `who` is a variable in scope
+#define EPI_REQUIRE_ALIGNED(ptr, align) PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "%s: " #ptr " must be " #align "-byte aligned", who)
+#define EPI_REQUIRE_PTR(ptr, align)            \
+    PATS_REQUIRE(ptr, "%s: null " #ptr, who);  \
+    EPI_REQUIRE_ALIGNED(ptr, align)
+
 // exactly one segment form, and sizes the kernels' 32-bit indices and epi_segment's clamps rely on
 inline int epi_check_segments(const char* what, const int64_t* pair_off, const int64_t* counts_in, int64_t stride, int64_t pairs,
                               int64_t cap) {
@@ -131,7 +137,7 @@ struct AdaptiveCall {
     int64_t round_models;
     int32_t *used, *participating;
 };
-constexpr int ADAPTIVE_TILE = 2048;                    // matches per score workgroup and models per score workgroup: both branches'
+constexpr int ADAPTIVE_TILE = 2048;                    // matches per score workgroup and models per score workgroup (epipolar.hip asserts it)
 constexpr int ADAPTIVE_CHUNK = 256;
 // conf = the confidence list if it gates, else null; tiles = ceil(longest segment / ADAPTIVE_TILE) >= 1
 typedef int (*AdaptiveScoreRound)(const AdaptiveCall& c, const float* conf, int tiles, int h_lo, int h_hi, const int32_t* stopped,

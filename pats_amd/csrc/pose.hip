@@ -4,19 +4,18 @@
 // the fill of the optional mask), no host read.  include/pats_amd.h states the definition; docs/kernels.md 4.9 the design.
 //
 //   one workgroup per pair, POSE_THREADS = 256 threads, decided by the sizes alone
-//   solve   float64.  The 9x9 matrix A and the accumulated rotations V live in LDS; wave 0 runs a cyclic Jacobi in the round-robin
-//           order: a sweep is nine rounds of four disjoint rotations (p, q) = ((r + i) % 9, (r - i) % 9), i = 1 .. 4 - sixteen
-//           lanes per rotation, lane k of a group updates row / column entry k.  A rotation whose off-diagonal entry no longer
-//           changes either diagonal entry when added to it is replaced by setting that entry to zero; a sweep without a rotation
-//           ends the loop, POSE_SWEEPS caps it.  Thread 0 then holds everything else in registers, all indices static: the
-//           eigenvector, G^T G of it as a 3x3 G, a 3x3 Jacobi for the right singular vectors, u_i = G v_i (Gram-Schmidt), u_3 =
-//           u_1 x u_2, v_3 = v_1 x v_2 (det U = det V = +1 by construction), E, R1, R2, u.  They go to LDS in float64 and float32.
+//   solve   float64.  The 9x9 matrix A and the accumulated rotations V live in LDS; wave 0 runs the round-robin cyclic Jacobi of
+//           jacobi9.hpp (shared with the homography refit), POSE_SWEEPS caps it.  Thread 0 then holds everything else in registers,
+//           all indices static: the eigenvector, G^T G of it as a 3x3 G, a 3x3 Jacobi for the right singular vectors, u_i = G v_i
+//           (Gram-Schmidt), u_3 = u_1 x u_2, v_3 = v_1 x v_2 (det U = det V = +1 by construction), E, R1, R2, u.  They go to LDS in
+//           float64 and float32.
 //   vote    the workgroup walks the segment with epi_load; a match that is not used carries a NaN x_l.  pose_front4 gives the four
 //           verdicts of a match as bits (R1 and R2 share everything up to the two signs); ballots + popcounts per wave, the waves
 //           added in LDS by thread 0 (integer adds: no order), which picks the candidate and writes the per-pair outputs.
 //   mask    a second walk with the same device function writes the chosen candidate's bit: front.sum() == front_count exactly.
 #include "common.hpp"
 #include "epipolar.hpp"
+#include "jacobi9.hpp"
 
 namespace pats {
 
@@ -25,29 +24,16 @@ constexpr int POSE_WAVES = POSE_THREADS / WAVE;
 constexpr int POSE_SWEEPS = 16;                        // cap of both Jacobi loops (a sweep without a rotation ends them: the 7th or 8th)
 constexpr int POSE_MIN_INLIERS = 8;
 
-// the rotation that annihilates apq: J = [[c, s], [-s, c]] on (p, q), B = J^T A J  (apq != 0)
-__device__ __forceinline__ void pose_cs(double app, double aqq, double apq, double& c, double& s) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (__builtin_fabs(theta) + __builtin_sqrt(theta * theta + 1.0));   // 0 for a huge theta
-    c = 1.0 / __builtin_sqrt(t * t + 1.0);
-    s = t * c;
-}
-
-// apq is too small to change either diagonal entry
-__device__ __forceinline__ bool pose_negligible(double app, double aqq, double g) {
-    return __builtin_fabs(app) + g == __builtin_fabs(app) && __builtin_fabs(aqq) + g == __builtin_fabs(aqq);
-}
-
 template <int P, int Q>
 __device__ __forceinline__ bool pose_rot3(double (&B)[3][3], double (&W)[3][3]) {
     const double g = __builtin_fabs(B[P][Q]);
     if (g == 0.0) return false;
-    if (pose_negligible(B[P][P], B[Q][Q], g)) {
+    if (jacobi_negligible(B[P][P], B[Q][Q], g)) {
         B[P][Q] = B[Q][P] = 0.0;
         return false;
     }
     double c, s;
-    pose_cs(B[P][P], B[Q][Q], B[P][Q], c, s);
+    jacobi_cs(B[P][P], B[Q][Q], B[P][Q], c, s);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const double x = B[k][P], y = B[k][Q];
@@ -199,49 +185,7 @@ epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
             if (!__builtin_isfinite(v)) s_bad = 1;      // the same value from every writer
         }
         wg_barrier();
-        const bool bad = s_bad != 0;
-        const int grp = tid >> 4, k = tid & 15;         // rotation grp of a round, entry k
-        const bool mine = tid < 64 && k < 9;
-        for (int sweep = 0; sweep < POSE_SWEEPS && !bad; ++sweep) {
-            for (int r = 0; r < 9; ++r) {
-                int pp = (r + grp + 1) % 9, qq = (r + 8 - grp) % 9;
-                if (pp > qq) { const int x_ = pp; pp = qq; qq = x_; }
-                double c = 1.0, s = 0.0, x = 0.0, y = 0.0, vx = 0.0, vy = 0.0;
-                bool rot = false, zero = false;
-                if (mine) {
-                    const double app = sA[pp][pp], aqq = sA[qq][qq], apq = sA[pp][qq];
-                    const double g = __builtin_fabs(apq);
-                    if (g != 0.0) {
-                        if (pose_negligible(app, aqq, g)) {
-                            zero = k == 0;
-                        } else {
-                            rot = true;
-                            pose_cs(app, aqq, apq, c, s);
-                        }
-                    }
-                    x = sA[k][pp]; y = sA[k][qq];
-                    vx = sV[k][pp]; vy = sV[k][qq];
-                }
-                wg_barrier();                           // every lane has read the round's entries
-                if (zero) { sA[pp][qq] = 0.0; sA[qq][pp] = 0.0; }       // no other lane touches the two in this round
-                if (rot) {                              // A <- A J, V <- V J: the columns p and q
-                    sA[k][pp] = c * x - s * y; sA[k][qq] = s * x + c * y;
-                    sV[k][pp] = c * vx - s * vy; sV[k][qq] = s * vx + c * vy;
-                    s_rot = 1;
-                }
-                wg_barrier();
-                if (rot) {                              // A <- J^T A: the rows p and q; the annihilated pair is set, not computed
-                    x = sA[pp][k]; y = sA[qq][k];
-                    sA[pp][k] = k == qq ? 0.0 : c * x - s * y;
-                    sA[qq][k] = k == pp ? 0.0 : s * x + c * y;
-                }
-                wg_barrier();
-            }
-            const bool again = s_rot != 0;
-            wg_barrier();
-            if (tid == 0) s_rot = 0;
-            if (!again) break;
-        }
+        jacobi9_sweeps(sA, sV, s_rot, tid, tid < 64 && (tid & 15) < 9, s_bad != 0, POSE_SWEEPS);
     }
     if (tid == 0) {
         double e[9];

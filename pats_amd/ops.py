@@ -1700,6 +1700,94 @@ def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=Non
     return out
 
 
+def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out,
+                   pairs, adaptive=None):
+    """What the four verifications share - everything but the C entry and its workspace query (the library's functions; looked up by
+    the callers, by plain attribute: these calls take microseconds and a formatted name would show).  adaptive: None for
+    the fixed budget, else (confidence, sample_size, models_per_sample, round_models) - four more arguments, two more outputs."""
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
+                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("%s: min_conf needs conf" % fn)
+    if adaptive is not None:
+        confidence, s, g, B = float(adaptive[0]), int(adaptive[1]), int(adaptive[2]), int(adaptive[3])
+        if not 0.0 < confidence < 1.0:                    # false for a NaN
+            raise RuntimeError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
+        if not (1 <= s <= 16 and 1 <= g <= 16):
+            raise RuntimeError("%s: sample_size = %d and models_per_sample = %d must lie in 1 .. 16" % (fn, s, g))
+        if B < 64 or B % 64:
+            raise RuntimeError("%s: round_models = %d must be a positive multiple of 64" % (fn, B))
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
+        raise RuntimeError("%s: models must be [pairs,H,3,3]" % fn)
+    H = int(models.shape[1])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("%s: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % (fn, pairs))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    if adaptive is not None and -(-H // B) > 256:
+        raise RuntimeError("%s: round_models = %d gives %d rounds for H = %d (at most 256)" % (fn, B, -(-H // B), H))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("%s: conf must be [cap]" % fn)
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
+            ("inlier", torch.uint8, (cap,))]
+    if moments:
+        want.append(("moments", torch.float64, (pairs, 9, 9)))
+    if adaptive is not None:
+        want += [("used", torch.int32, (pairs,)), ("participating", torch.int32, (pairs,))]
+    out = _bp_outputs(fn, want, out, dev)
+    nws = workspace_bytes(pairs, H, cap)
+    ws = _workspace(nws, dev) if nws else None
+    inl = out[3]
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else ml
+    more = () if adaptive is None else (confidence, s, g, B, _ptr(out[-2]), _ptr(out[-1]))
+    _check(entry(
+        _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H, _ptr(thr), _ptr(norm),
+        0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
+        _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream(), *more), fn)
+    return out
+
+
+def _hypotheses_by_pair(fn, K, entry, workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm, progressive, return_samples, out, pairs):
+    """What the 8-point and the 4-point generator share - everything but the sample size K, the C entry and its workspace query."""
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("%s: seed must be an int64 GPU tensor [pairs]" % fn)
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    H = int(H)
+    seed = _dev(seed, "seed", torch.int64).reshape(-1)
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if seed.numel() != pairs:
+        raise RuntimeError("%s: seed must hold one int64 per pair (%d), got %d" % (fn, pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("models", torch.float32, (pairs, H, 3, 3))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, K)))
+    out = _bp_outputs(fn, want, out, dev, lone=True)
+    nws = workspace_bytes(pairs, H)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+    _check(entry(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0, _ptr(out[0]),
+                 _ptr(out[1]) if return_samples else None, _ptr(ws), nws, _stream()), fn)
+    return out if return_samples else out[0]
+
+
 def epipolar_max_h():
     """The largest number of models per pair epipolar_score_by_pair takes (pats_epipolar_max_h)."""
     return int(_L().pats_epipolar_max_h())
@@ -1720,45 +1808,8 @@ def epipolar_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, str
     inlier [cap] uint8 - 1 where the match is an inlier of its pair's best model, 0 everywhere else) and, with moments=True,
     moments [pairs,9,9] float64 = the sum of q q^T over those inliers, q = vec(x_r x_l^T): torch.linalg.eigh of it is the
     least-squares refit.  out: the four (five) destinations."""
-    fn = "epipolar_score_by_pair"
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
-                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if min_conf is not None and conf is None:
-        raise RuntimeError("epipolar_score_by_pair: min_conf needs conf")
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
-        raise RuntimeError("epipolar_score_by_pair: models must be [pairs,H,3,3]")
-    H = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("epipolar_score_by_pair: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % pairs)
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("epipolar_score_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("epipolar_score_by_pair: conf must be [cap]")
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
-            ("inlier", torch.uint8, (cap,))]
-    if moments:
-        want.append(("moments", torch.float64, (pairs, 9, 9)))
-    out = _bp_outputs(fn, want, out, dev)
-    nws = _L().pats_epipolar_workspace_bytes(pairs, H, cap)
-    ws = _workspace(nws, dev) if nws else None
-    inl = out[3]
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else ml
-    _check(_L().pats_epipolar_score_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H,
-                                                _ptr(thr), _ptr(norm), 0 if min_conf is None else 1,
-                                                0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                                _ptr(inl), _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream()), fn)
-    return out
+    return _score_by_pair("epipolar_score_by_pair", _L().pats_epipolar_score_by_pair_f32, _L().pats_epipolar_workspace_bytes, matches_l,
+                          matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs)
 
 
 def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
@@ -1774,34 +1825,9 @@ def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, st
     Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 8 matches and for a sample with a non-finite
     coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,8] int32: the draws as positions inside the pair's
     list, -1 for a pair with fewer than 8 matches).  out: the destination(s), a tensor or a tuple."""
-    fn = "epipolar_hypotheses_by_pair"
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
-                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if not isinstance(seed, torch.Tensor):
-        raise RuntimeError("epipolar_hypotheses_by_pair: seed must be an int64 GPU tensor [pairs]")
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    H = int(H)
-    seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if seed.numel() != pairs:
-        raise RuntimeError("epipolar_hypotheses_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("epipolar_hypotheses_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("models", torch.float32, (pairs, H, 3, 3))]
-    if return_samples:
-        want.append(("sample_idx", torch.int32, (pairs, H, 8)))
-    out = _bp_outputs(fn, want, out, dev, lone=True)
-    nws = _L().pats_epipolar_hypotheses_workspace_bytes(pairs, H)
-    ws = _workspace(nws, dev) if nws else None
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-    _check(_L().pats_epipolar_hypotheses_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
-                                                     1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
-                                                     _ptr(ws), nws, _stream()), fn)
-    return out if return_samples else out[0]
+    return _hypotheses_by_pair("epipolar_hypotheses_by_pair", 8, _L().pats_epipolar_hypotheses_by_pair_f32,
+                               _L().pats_epipolar_hypotheses_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
+                               progressive, return_samples, out, pairs)
 
 
 def epipolar_hypotheses5_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
@@ -1925,34 +1951,9 @@ def homography_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, 
     Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 4 matches and for a sample with a non-finite
     coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,4] int32: the draws as positions inside the pair's
     list, -1 for a pair with fewer than 4 matches).  out: the destination(s), a tensor or a tuple."""
-    fn = "homography_hypotheses_by_pair"
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
-                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if not isinstance(seed, torch.Tensor):
-        raise RuntimeError("homography_hypotheses_by_pair: seed must be an int64 GPU tensor [pairs]")
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    H = int(H)
-    seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if seed.numel() != pairs:
-        raise RuntimeError("homography_hypotheses_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("homography_hypotheses_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("models", torch.float32, (pairs, H, 3, 3))]
-    if return_samples:
-        want.append(("sample_idx", torch.int32, (pairs, H, 4)))
-    out = _bp_outputs(fn, want, out, dev, lone=True)
-    nws = _L().pats_homography_hypotheses_workspace_bytes(pairs, H)
-    ws = _workspace(nws, dev) if nws else None
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-    _check(_L().pats_homography_hypotheses_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
-                                                       1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
-                                                       _ptr(ws), nws, _stream()), fn)
-    return out if return_samples else out[0]
+    return _hypotheses_by_pair("homography_hypotheses_by_pair", 4, _L().pats_homography_hypotheses_by_pair_f32,
+                               _L().pats_homography_hypotheses_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
+                               progressive, return_samples, out, pairs)
 
 
 def homography_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None,
@@ -1966,45 +1967,8 @@ def homography_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, s
     inlier [cap] uint8 - 1 where the match is an inlier of its pair's best model, 0 everywhere else) and, with moments=True,
     moments [pairs,9,9] float64 = the sum of A_i^T A_i + B_i^T B_i over those inliers (the two DLT rows of a match): the input of
     homography_refit_by_pair.  out: the four (five) destinations."""
-    fn = "homography_score_by_pair"
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
-                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if min_conf is not None and conf is None:
-        raise RuntimeError("homography_score_by_pair: min_conf needs conf")
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
-        raise RuntimeError("homography_score_by_pair: models must be [pairs,H,3,3]")
-    H = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("homography_score_by_pair: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % pairs)
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("homography_score_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("homography_score_by_pair: conf must be [cap]")
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
-            ("inlier", torch.uint8, (cap,))]
-    if moments:
-        want.append(("moments", torch.float64, (pairs, 9, 9)))
-    out = _bp_outputs(fn, want, out, dev)
-    nws = _L().pats_homography_score_workspace_bytes(pairs, H, cap)
-    ws = _workspace(nws, dev) if nws else None
-    inl = out[3]
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else ml
-    _check(_L().pats_homography_score_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H,
-                                                  _ptr(thr), _ptr(norm), 0 if min_conf is None else 1,
-                                                  0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                                  _ptr(inl), _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream()), fn)
-    return out
+    return _score_by_pair("homography_score_by_pair", _L().pats_homography_score_by_pair_f32, _L().pats_homography_score_workspace_bytes,
+                          matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs)
 
 
 def homography_refit_by_pair(best_count, moments=None, models=None, best=None, norm=None, swapped=False, return_pixel=False, out=None):
@@ -2054,59 +2018,6 @@ def homography_refit_by_pair(best_count, moments=None, models=None, best=None, n
     return out
 
 
-def _score_adaptive_by_pair(fn, branch, matches_l, matches_r, models, thr, confidence, sample_size, models_per_sample, round_models,
-                            pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs):
-    """What the two adaptive verifications share - everything but the C entry (branch = "epipolar" or "homography")."""
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
-                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if min_conf is not None and conf is None:
-        raise RuntimeError("%s: min_conf needs conf" % fn)
-    confidence, s, g, B = float(confidence), int(sample_size), int(models_per_sample), int(round_models)
-    if not 0.0 < confidence < 1.0:                    # false for a NaN
-        raise RuntimeError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
-    if not (1 <= s <= 16 and 1 <= g <= 16):
-        raise RuntimeError("%s: sample_size = %d and models_per_sample = %d must lie in 1 .. 16" % (fn, s, g))
-    if B < 64 or B % 64:
-        raise RuntimeError("%s: round_models = %d must be a positive multiple of 64" % (fn, B))
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
-        raise RuntimeError("%s: models must be [pairs,H,3,3]" % fn)
-    H = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("%s: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % (fn, pairs))
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
-    if -(-H // B) > 256:
-        raise RuntimeError("%s: round_models = %d gives %d rounds for H = %d (at most 256)" % (fn, B, -(-H // B), H))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("%s: conf must be [cap]" % fn)
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
-            ("inlier", torch.uint8, (cap,))]
-    if moments:
-        want.append(("moments", torch.float64, (pairs, 9, 9)))
-    want += [("used", torch.int32, (pairs,)), ("participating", torch.int32, (pairs,))]
-    out = _bp_outputs(fn, want, out, dev)
-    nws = getattr(_L(), "pats_%s_score_adaptive_workspace_bytes" % branch)(pairs, H, cap)
-    ws = _workspace(nws, dev)
-    inl = out[3]
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else ml
-    _check(getattr(_L(), "pats_%s_score_adaptive_by_pair_f32" % branch)(
-        _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H, _ptr(thr), _ptr(norm),
-        0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
-        _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream(), confidence, s, g, B, _ptr(out[-2]), _ptr(out[-1])), fn)
-    return out
-
-
 def epipolar_score_adaptive_by_pair(matches_l, matches_r, models, thr, confidence, sample_size, models_per_sample=1, round_models=256,
                                     pair_off=None, stride=None, counts=None, conf=None, min_conf=None, norm=None, moments=False,
                                     out=None, pairs=None):
@@ -2120,8 +2031,10 @@ def epipolar_score_adaptive_by_pair(matches_l, matches_r, models, thr, confidenc
     Returns epipolar_score_by_pair's tuple - counts are exactly 0 from used[p] on; best, best_count, inlier and moments are what the
     fixed budget gives with models[p, used[p]:] zeroed - followed by used [pairs] int32 (the models tested; H for a pair that never
     stopped) and participating [pairs] int32 (the matches that took part).  out: the six (seven) destinations."""
-    return _score_adaptive_by_pair("epipolar_score_adaptive_by_pair", "epipolar", matches_l, matches_r, models, thr, confidence, sample_size,
-                                   models_per_sample, round_models, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs)
+    return _score_by_pair("epipolar_score_adaptive_by_pair", _L().pats_epipolar_score_adaptive_by_pair_f32,
+                          _L().pats_epipolar_score_adaptive_workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf,
+                          min_conf, norm, moments, out, pairs,
+                          adaptive=(confidence, sample_size, models_per_sample, round_models))
 
 
 def homography_score_adaptive_by_pair(matches_l, matches_r, models, thr, confidence, sample_size, models_per_sample=1, round_models=256,
@@ -2130,9 +2043,10 @@ def homography_score_adaptive_by_pair(matches_l, matches_r, models, thr, confide
     """homography_score_by_pair with the stopping rule of epipolar_score_adaptive_by_pair
     (pats_homography_score_adaptive_by_pair_f32): the same arguments, the same rule, the same outputs, the forward transfer error as
     the test.  sample_size is 4 for the 4-point hypotheses."""
-    return _score_adaptive_by_pair("homography_score_adaptive_by_pair", "homography", matches_l, matches_r, models, thr, confidence,
-                                   sample_size, models_per_sample, round_models, pair_off, stride, counts, conf, min_conf, norm, moments,
-                                   out, pairs)
+    return _score_by_pair("homography_score_adaptive_by_pair", _L().pats_homography_score_adaptive_by_pair_f32,
+                          _L().pats_homography_score_adaptive_workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf,
+                          min_conf, norm, moments, out, pairs,
+                          adaptive=(confidence, sample_size, models_per_sample, round_models))
 
 
 # ------------------------------------------------------------------------------------------------

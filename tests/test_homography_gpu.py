@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 PAD = 64
 SENT = {torch.int32: -123456, torch.int64: -123456, torch.uint8: 0xA5, torch.float64: -777.25, torch.float32: -777.25}
-T, C = 2048, 256        # the score kernel's match tile (HOM_THREADS * HOM_R) and model chunk (HOM_CHUNK): asserted against the source
+T, C = 2048, 256        # the score kernel's match tile (EPI_THREADS * EPI_R) and model chunk (EPI_CHUNK): asserted against the source
 NORM = np.array([[0.02, -0.01, 1.25, 1.2, -0.03, 0.015, 1.1, 1.3]], np.float32)      # scales between 1 and 1.3
 
 
@@ -30,9 +30,9 @@ def test_the_tile_constants_are_the_kernels():
     import os
     import re
     from conftest import REPO
-    src = open(os.path.join(REPO, "pats_amd", "csrc", "homography.hip")).read()
+    src = open(os.path.join(REPO, "pats_amd", "csrc", "epipolar.hip")).read()
     k = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))       # noqa: E731
-    assert k("HOM_THREADS") * k("HOM_R") == T and k("HOM_CHUNK") == C
+    assert k("EPI_THREADS") * k("EPI_R") == T and k("EPI_CHUNK") == C
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-pair homographies (ops.homography_{hypotheses,score,refit}_by_pair, csrc/homography.hip) at the verification bench's shape:
+"""Per-pair homographies (ops.homography_{hypotheses,score,refit}_by_pair: csrc/hypotheses.hip, csrc/epipolar.hip, csrc/homography.hip) at the verification bench's shape:
 default workload, 48 pairs per step, confidence=True, H = 1024 hypotheses per pair, on="all" (every match) and on="topk" (K = 2048).
 
 Without --measure this is the driver: ONE GPU step, a child process under its own `timeout -k 10`:
