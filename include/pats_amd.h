@@ -800,7 +800,7 @@ int pats_epipolar_score_by_pair_f32(const float* matches_l, const float* matches
  * 8x9 epipolar constraint matrix (the 8-point algorithm's linear step) is written as a row-major 3x3 model.  One launch, no host
  * read, deterministic: the draws come from a counter-based generator that a host reproduces exactly.  Not here: a 7-point solver
  * (the 5-point one is pats_epipolar_hypotheses5_by_pair_f32 below), the rank-2 / essential projection of a hypothesis, cheirality and
- * pose, local optimisation, adaptive termination.
+ * pose, local optimisation (pats_epipolar_polish_by_pair_f32 below), adaptive termination.
  * Inputs
  *   matches_l, matches_r [cap,2] float32 and the segment of pair p - ragged (pair_off) or strided (stride, counts_in), exactly ONE
  *              of the two forms (both or neither: refused) - as for pats_epipolar_score_by_pair_f32, with the same clamping:
@@ -852,7 +852,8 @@ int pats_epipolar_hypotheses_by_pair_f32(const float* matches_l, const float* ma
  * are written as row-major 3x3 models.  What cv2.findEssentialMat's RANSAC solves per sample.  One launch, no host read, no
  * workspace, deterministic.  The points must be calibrated: norm carries the intrinsics ((c, s) = (principal point, 1 / focal
  * length) per side); without norm the solver runs on (p0, p1, 1) as if those were calibrated coordinates.
- * What it is not: a 7-point solver, cheirality and pose (pats_epipolar_pose_by_pair_f64), local optimisation, adaptive termination.
+ * What it is not: a 7-point solver, cheirality and pose (pats_epipolar_pose_by_pair_f64), local optimisation
+ * (pats_epipolar_polish_by_pair_f32), adaptive termination.
  *   x          the verification's point, formed exactly as there: ((p0 - c0) * s0, (p1 - c1) * s1, 1) in float32 - one subtract,
  *              then one multiply, never contracted - or (p0, p1, 1) without norm.  The segment of pair p (n rows from lo on) in the
  *              same two forms, ragged (pair_off) or strided (stride, counts_in), with the same clamping as above
@@ -1110,6 +1111,66 @@ int pats_homography_score_adaptive_by_pair_f32(const float* matches_l, const flo
                                                void* workspace, size_t workspace_bytes, pats_stream_t stream, double confidence,
                                                int sample_size, int models_per_sample, int64_t round_models, int32_t* used,
                                                int32_t* participating);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair local optimisation (ABI 8, symbols added): the rounds "refit the winner's inliers, verify the refit" that follow a
+ * verification - LO-RANSAC's inner loop in its simplest form - walked by ONE launch per call with the pair's matches resident on
+ * chip, and the BEST round kept: the result never has less support than the model it started from.  No new numerics: every value
+ * returned is one the entry points above produce, and a caller who chains them gets the same bits.  On the device, no host read.
+ * What it is not: no essential projection for uncalibrated callers (a plain F refit without rank 2), no shrinking threshold, no
+ * inner RANSAC on the inlier set, no PROSAC rule, and nothing in pipeline.forward_* or the drop-in calls it.
+ * pats_epipolar_polish_by_pair_f32 (family F = Epipolar, min_F = 8) and pats_homography_polish_by_pair_f32 (F = Homography,
+ * min_F = 4) take the verification's match, segment, thr, norm and min_conf arguments - the same two segment forms, the same
+ * clamping, the same rule for a match that participates - and then
+ *   models [pairs,H,3,3] float32, 1 <= H <= pats_epipolar_max_h(), and best [pairs] int32 (clamped to 0 .. H-1; null is allowed
+ *              with H == 1 only): the verification's models and winner - the start of the walk.  The models are expected finite
+ *   rounds     T, 1 <= T <= 16
+ * Definition, per pair p
+ *   support(m)   (c, M, mask): the count, the 9x9 float64 moments and the inlier bytes that pats_{epipolar,homography}_score_by_pair_f32
+ *                returns for pair p when m is its one model (H = 1, moments requested) - bit for bit, the moments in that kernel's
+ *                fixed order (thread-local in index order over a 512-thread walk, the xor tree over the wave, the waves in order)
+ *   refit_E(M, c)  float32 cast (round to nearest even) of the E that pats_epipolar_pose_by_pair_f64 returns for (moments = M,
+ *                best_count = c, swapped = 0): smallest eigenvector, nearest essential matrix, |E|_F = 1, sign rule.  "No pose"
+ *                there (c < 8, non-finite, s2 == 0) gives the zero model
+ *   refit_H(M, c)  float32 cast of the H that pats_homography_refit_by_pair_f64 returns for (moments = M, best_count = c,
+ *                swapped = 0); "no model" there gives the zero model
+ *   m_0          models[p, clamp(best[p], 0, H-1)]                      (c_0, M_0, mask_0) = support(m_0)
+ *   round r = 1 .. T:   m_r = refit_F(M_{r-1}, c_{r-1});   (c_r, M_r, mask_r) = support(m_r)
+ *                a zero m_r has support 0, so every later round is zero as well: the walk ends there
+ *   b            the lowest r in 0 .. T with the largest c_r       (round 0 is the input: the result never has less support than it)
+ * A NaN or negative thr[p] gives c_r = 0 for all r, b = 0 and model = m_0.  When m_r equals m_{r-1} bit for bit every later round
+ * repeats it; the kernel stops there and copies the count into the rest of counts[p, :] - the definition cannot tell the difference.
+ * There is no other early exit.  No output ever holds a NaN or an infinity.
+ * Outputs - every call defines every byte of every output
+ *   model [pairs,3,3] float32      m_b: a model for the verification, the pose and the refit as it stands
+ *   best_count [pairs] int64       c_b
+ *   inlier [cap] uint8             mask_b; 0 outside every segment and in the slack of strided rows.  Its sum over a segment is c_b
+ *   moments [pairs,9,9] float64    M_b: with best_count the input of pats_epipolar_pose_by_pair_f64 / pats_homography_refit_by_pair_f64
+ *   best_round [pairs] int32       b
+ *   counts [pairs, T+1] int32      c_0 .. c_T
+ * cap == 0 is a valid call that defines every per-pair output (the match pointers and inlier must still be non-null).  Refused
+ * before any launch (pats_last_error names the argument), in the verification's wording and order: a null matches_l / matches_r /
+ * models / thr / model / best_count / inlier / moments / best_round / counts; matches_l / matches_r off 8 bytes (read as float2),
+ * models / thr / model / best_round / counts / conf / norm / best off 4, best_count / moments / pair_off / counts_in off 8; both
+ * segment forms or neither; pairs < 1; cap < 0 or cap >= 2^31 - 1; in the strided form stride < 1 or pairs * stride > cap; H < 1 or
+ * H > max_h; use_min_conf without conf; a negative or NaN min_conf; rounds outside 1 .. 16; a null best with H > 1.  The workspace is
+ * pats_*_polish_workspace_bytes (0 today: a pair's walk lives in its workgroup's LDS and registers; workspace may be null).
+ * PATS_ERR_UNSUPPORTED if the device does not grant a workgroup 131072 bytes of dynamic LDS (the staging of 8192 matches; a longer
+ * segment is legal and is walked in global memory instead, with the same results). */
+size_t pats_epipolar_polish_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_epipolar_polish_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                     int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* thr,
+                                     const float* norm, int use_min_conf, float min_conf, const float* models, int64_t H,
+                                     const int32_t* best, int rounds, float* model, int64_t* best_count, uint8_t* inlier,
+                                     double* moments, int32_t* best_round, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                     pats_stream_t stream);
+size_t pats_homography_polish_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_homography_polish_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                       int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* thr,
+                                       const float* norm, int use_min_conf, float min_conf, const float* models, int64_t H,
+                                       const int32_t* best, int rounds, float* model, int64_t* best_count, uint8_t* inlier,
+                                       double* moments, int32_t* best_round, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                       pats_stream_t stream);
 
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the

@@ -42,6 +42,8 @@ _FMT = ctypes.POINTER(CropFormat)
 _SCORE_ARGS = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_f,
                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]
 _ADAPTIVE_ARGS = [ctypes.c_double, c_int, c_int, c_i64, c_void_p, c_void_p]
+_POLISH_ARGS = [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_f, c_void_p, c_i64,
+                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]
 
 # name -> (restype, argtypes); must list every symbol include/pats_amd.h declares
 SIGNATURES = {
@@ -269,6 +271,12 @@ SIGNATURES = {
     "pats_epipolar_score_adaptive_by_pair_f32": (c_int, _SCORE_ARGS + _ADAPTIVE_ARGS),
     "pats_homography_score_adaptive_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
     "pats_homography_score_adaptive_by_pair_f32": (c_int, _SCORE_ARGS + _ADAPTIVE_ARGS),
+    # per-pair local optimisation, both branches (csrc/polish.hip): the verification's match, segment, thr, norm and min_conf
+    # arguments, then models, H, best, rounds, the six outputs, workspace, stream
+    "pats_epipolar_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "pats_epipolar_polish_by_pair_f32": (c_int, _POLISH_ARGS),
+    "pats_homography_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "pats_homography_polish_by_pair_f32": (c_int, _POLISH_ARGS),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -600,7 +600,7 @@ def pose_by_pair(out, cap, norm=None, swapped=False, front=False):
     Returns (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64, front_counts [pairs,4] int32,
     choice [pairs] int32) in the CALLER's order - with front=True followed by front (uint8, aligned with the scored lists like
     `verified`'s inlier mask: slot order) - and stores them as `pose`.  E.float() goes straight back into verify_by_pair as an
-    H = 1 model: the local-optimisation round."""
+    H = 1 model: the local-optimisation round, which polish_by_pair runs `rounds` times in one launch, keeping the best."""
     if "verified" not in out:
         raise ValueError("pose_by_pair: run verify_by_pair first")
     ver, on = out["verified"], out["verified_on"]
@@ -660,7 +660,8 @@ def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
     lists are in the hand-over's (y, x) order and H is wanted in the reference's (x, y) frame.
     Returns (H [pairs,3,3] float64, eig [pairs,2] float64: the two smallest eigenvalues of the moments) in the CALLER's order - with
     pixel=True followed by H_px [pairs,3,3]: the homography of the stored coordinates - and stores them as `homography`.  H.float()
-    goes straight back into verify_h_by_pair as an H = 1 model: the local-optimisation round."""
+    goes straight back into verify_h_by_pair as an H = 1 model: the local-optimisation round, which polish_h_by_pair runs `rounds`
+    times in one launch, keeping the best."""
     if "verified_h" not in out:
         raise ValueError("homography_by_pair: run verify_h_by_pair first")
     ver = out["verified_h"]
@@ -675,6 +676,46 @@ def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
         res = tuple(t.index_select(0, back) for t in res)
     out["homography"] = res
     return res
+
+
+def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf):
+    """What polish_by_pair and polish_h_by_pair share; polish = the ops function, key = "verified" / "verified_h"."""
+    if key not in out:
+        raise ValueError("%s: run %s first" % (fn, "verify_by_pair" if key == "verified" else "verify_h_by_pair"))
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
+    on, best = out[key + "_on"], out[key][1]
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        idx = _caller_of_dev(out, thr.device)
+        thr = thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    ml, mr, conf, seg = _lists_on(out, cap, on)
+    model, best_count, inl, moments, best_round, counts = polish(
+        ml, mr, out[key + "_models"], thr, best=best, rounds=rounds, conf=conf if min_conf is not None else None, min_conf=min_conf,
+        norm=norm, **seg)
+    out["polished" if key == "verified" else "polished_h"] = (model, best_round, counts)
+    out[key] = (best_count.to(torch.int32)[:, None], torch.zeros_like(best), best_count, inl, moments)
+    out[key + "_models"] = model[:, None]
+    return out[key]
+
+
+def polish_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
+    """Device side, after any of verify_by_pair / verify_adaptive_by_pair: the local optimisation of each pair's winning model
+    (ops.epipolar_polish_by_pair: ONE launch for all rounds, no host read) - `rounds` times "refit the inliers, verify the refit" on
+    the lists that verification scored (`verified_on`), starting from `verified_models` and its `best`, and the round with the most
+    inliers kept (round 0 is the verified winner: the result never has less support).  thr [pairs], norm [pairs,8] or None in the
+    CALLER's order and min_conf - pass what the verification was given; they are permuted to slot order on the device as there.
+    Stores `polished` = (model [pairs,3,3] float32, best_round [pairs] int32, counts [pairs, rounds + 1] int32) and REPLACES
+    `verified` by the standard tuple of the polished model - (counts [pairs,1] int32, best = 0, best_count, inlier, moments) - and
+    `verified_models` by model[:, None], all in SLOT order like the verification's: pose_by_pair and split_verified_by_pair work on
+    the polished result unchanged and hand the pairs back in the caller's order.  Returns the new `verified`."""
+    return _polish("polish_by_pair", ops.epipolar_polish_by_pair, "verified", out, cap, thr, rounds, norm, min_conf)
+
+
+def polish_h_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
+    """polish_by_pair for the homography branch, after verify_h_by_pair / verify_h_adaptive_by_pair (ops.homography_polish_by_pair):
+    stores `polished_h` and replaces `verified_h` and `verified_h_models` - homography_by_pair works on the result unchanged."""
+    return _polish("polish_h_by_pair", ops.homography_polish_by_pair, "verified_h", out, cap, thr, rounds, norm, min_conf)
 
 
 def verify_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,

@@ -5,8 +5,8 @@
 // homographies, 4.12: the adaptive rounds).
 // The file and the EPI_ constants are named like epipolar.hpp's epi_ helpers, which the homography branch shares as well.
 //
-// A family is a struct with the two things that differ: test2, THE arithmetic of its test (two matches against one model), and
-// accumulate, a match's contribution to the moments.
+// A family (verify.hpp, shared with polish.hip) is a struct with the two things that differ: test2, THE arithmetic of its test (two
+// matches against one model), and accumulate, a match's contribution to the moments.
 //   Epipolar    squared Sampson error against thr^2, without the division; the moments of q = vec(x_r x_l^T)
 //   Homography  squared forward transfer error against thr^2, without the division; the moments of the two DLT rows A_i, B_i
 //
@@ -27,6 +27,7 @@
 // comparison with it is false, the inner loop needs no mask.
 #include "common.hpp"
 #include "epipolar.hpp"
+#include "verify.hpp"
 
 namespace pats {
 
@@ -36,76 +37,7 @@ constexpr int EPI_R = 8;                            // matches per thread
 constexpr int EPI_TILE = EPI_THREADS * EPI_R; // matches per workgroup
 constexpr int EPI_CHUNK = 256;                      // models per workgroup
 constexpr int EPI_MAX_H = 65536;
-constexpr int EPI_MASK_THREADS = 512;
-constexpr int EPI_MASK_WAVES = EPI_MASK_THREADS / WAVE;
-constexpr int EPI_MOM = 45;                         // upper triangle of the 9x9 moment matrix
 static_assert(EPI_TILE == ADAPTIVE_TILE && EPI_CHUNK == ADAPTIVE_CHUNK, "adaptive.hip sizes the rounds' grids");
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ v2f pk_splat(float v) { return v2f{v, v}; }
-
-// The families.  test2: two matches against one model - match k is an inlier iff w[k] > 0 and s[k] <= lim[k]; the score and the mask
-// kernel both call it.  accumulate: an inlier's 45 products in float64 (the products of two float32 are exact).  The strings are the
-// names the launch checks report.
-struct Epipolar {
-    static constexpr const char *SCORE = "epipolar_score kernel", *ROUND = "epipolar_score kernel (a round)",
-                                *ARGMAX = "epipolar_argmax kernel", *MASK = "epipolar_mask kernel";
-    // s = r^2, lim = thr^2 den, w = den
-    static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
-        const v2f a0 = pk_fma(pk_splat(e[0]), l0, pk_fma(pk_splat(e[1]), l1, pk_splat(e[2])));
-        const v2f a1 = pk_fma(pk_splat(e[3]), l0, pk_fma(pk_splat(e[4]), l1, pk_splat(e[5])));
-        const v2f a2 = pk_fma(pk_splat(e[6]), l0, pk_fma(pk_splat(e[7]), l1, pk_splat(e[8])));
-        const v2f b0 = pk_fma(pk_splat(e[0]), r0, pk_fma(pk_splat(e[3]), r1, pk_splat(e[6])));
-        const v2f b1 = pk_fma(pk_splat(e[1]), r0, pk_fma(pk_splat(e[4]), r1, pk_splat(e[7])));
-        const v2f r = pk_fma(r0, a0, pk_fma(r1, a1, a2));
-        w = pk_fma(a0, a0, pk_fma(a1, a1, pk_fma(b0, b0, b1 * b1)));
-        s = r * r;
-        lim = pk_splat(t2) * w;
-    }
-    static __device__ __forceinline__ void accumulate(float xl0, float xl1, float xr0, float xr1, double (&acc)[EPI_MOM]) {
-        const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
-        const double q[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};       // vec(x_r x_l^T): exact products
-        int k = 0;
-#pragma unroll
-        for (int u = 0; u < 9; ++u)
-#pragma unroll
-            for (int v = u; v < 9; ++v) acc[k++] += q[u] * q[v];
-    }
-};
-
-struct Homography {
-    static constexpr const char *SCORE = "homography_score kernel", *ROUND = "homography_score kernel (a round)",
-                                *ARGMAX = "homography_argmax kernel", *MASK = "homography_mask kernel";
-    // s = d0^2 + d1^2, lim = thr^2 a2^2, w = a2^2
-    static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
-        const v2f a0 = pk_fma(pk_splat(e[0]), l0, pk_fma(pk_splat(e[1]), l1, pk_splat(e[2])));
-        const v2f a1 = pk_fma(pk_splat(e[3]), l0, pk_fma(pk_splat(e[4]), l1, pk_splat(e[5])));
-        const v2f a2 = pk_fma(pk_splat(e[6]), l0, pk_fma(pk_splat(e[7]), l1, pk_splat(e[8])));
-        const v2f d0 = pk_fma(-r0, a2, a0);
-        const v2f d1 = pk_fma(-r1, a2, a1);
-        s = pk_fma(d0, d0, d1 * d1);
-        w = a2 * a2;
-        lim = pk_splat(t2) * w;
-    }
-    static __device__ __forceinline__ void accumulate(float xl0, float xl1, float xr0, float xr1, double (&acc)[EPI_MOM]) {
-        const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
-        // the rows A_i and B_i: the products of two float32 are exact in float64
-        const double qa[9] = {-a0, -a1, -1.0, 0.0, 0.0, 0.0, b0 * a0, b0 * a1, b0};
-        const double qb[9] = {0.0, 0.0, 0.0, -a0, -a1, -1.0, b1 * a0, b1 * a1, b1};
-        int k = 0;
-#pragma unroll
-        for (int u = 0; u < 9; ++u)
-#pragma unroll
-            for (int v = u; v < 9; ++v) acc[k++] += qa[u] * qa[v] + qb[u] * qb[v];
-    }
-};
-
-__device__ __forceinline__ void verify_model(const float* __restrict__ m, float (&e)[9]) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) e[k] = m[k];
-}
 
 // ROUND = false: the fixed budget - models [0, H) in `chunks` chunks; h_begin, h_stop and stopped are not read.  ROUND = true: a round
 // of the adaptive verification (adaptive.hip issues them) - models [h_begin, h_stop) in `chunks` chunks, and the workgroups of a
@@ -250,21 +182,10 @@ verify_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_,
         }
     }
     if (!moments) return;
-#pragma unroll
-    for (int k = 0; k < EPI_MOM; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == 0) part[wave][k] = v;
-    }
-    wg_barrier();
+    const double s = verify_moments_sum(acc, part, tid, lane, wave);
     if (tid < EPI_MOM) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < EPI_MASK_WAVES; ++w) s += part[w][tid];
-        int u = 0, k = tid;                             // entry tid of the upper triangle -> (u, v)
-        while (k >= 9 - u) { k -= 9 - u; ++u; }
-        const int v = u + k;
+        int u, v;
+        verify_triangle(tid, u, v);
         double* mo = moments + p * 81;
         mo[u * 9 + v] = s;
         mo[v * 9 + u] = s;

@@ -1,5 +1,5 @@
 // What the per-pair stages share (epipolar.hip: verification; hypotheses.hip: the 8-point and 4-point hypotheses; hypotheses5.hip: the
-// 5-point hypotheses; pose.hip: the pose; homography.hip: the refit): how a pair's segment of the match lists, its normalisation and
+// 5-point hypotheses; pose.hip: the pose; homography.hip: the refit; polish.hip: the local optimisation): how a pair's segment of the match lists, its normalisation and
 // a match's point are read, and the hypotheses' sampler.  include/pats_amd.h states all of it.
 #pragma once
 #include "common.hpp"

@@ -4,37 +4,16 @@
 // family.  No host read anywhere.  include/pats_amd.h states the definition ("Per-pair homographies"); docs/kernels.md 4.11 the design.
 //
 //   refit       one wave per pair, float64: the round-robin cyclic Jacobi of jacobi9.hpp on the moments in LDS (shared with pose.hip),
-//               the two smallest eigenvalues, the eigenvector, the sign rule, the denormalisation and the permutation
+//               the two smallest eigenvalues, the eigenvector, the sign rule (refit.hpp, shared with polish.hip), the denormalisation
+//               and the permutation
 #include "common.hpp"
 #include "epipolar.hpp"
 #include "jacobi9.hpp"
+#include "refit.hpp"
 
 namespace pats {
 
 constexpr int HOM_REFIT_THREADS = 64;
-constexpr int HOM_SWEEPS = 16;                         // cap of the Jacobi loop (a sweep without a rotation ends it)
-constexpr int HOM_MIN_INLIERS = 4;
-
-// k -> P k for the permutation P = [[0,1,0],[1,0,0],[0,0,1]] applied to rows and columns of a row-major 3x3
-__device__ __forceinline__ int hom_perm(int k, int swapped) {
-    const int i = k / 3, j = k - 3 * i;
-    const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
-    return si * 3 + sj;
-}
-
-// out[k] = +-v[P k]: the permutation, then the sign rule judged on the values written (the lowest index among equals)
-__device__ __forceinline__ void hom_write(const double (&v)[9], bool ok, int swapped, double* __restrict__ out) {
-    double big = -1.0, at = 0.0;
-    for (int k = 0; k < 9; ++k) {
-        const double x = ok ? v[hom_perm(k, swapped)] : 0.0;
-        if (__builtin_fabs(x) > big) { big = __builtin_fabs(x); at = x; }
-    }
-    const bool flip = at < 0.0;
-    for (int k = 0; k < 9; ++k) {
-        const double x = ok ? v[hom_perm(k, swapped)] : 0.0;
-        out[k] = flip ? -x : x;
-    }
-}
 
 __global__ void __launch_bounds__(HOM_REFIT_THREADS)
 homography_refit_kernel(const int64_t* __restrict__ best_count, const double* __restrict__ moments, const float* __restrict__ models,
@@ -63,25 +42,10 @@ homography_refit_kernel(const int64_t* __restrict__ best_count, const double* __
     double e[9], ev[2] = {0.0, 0.0};
     bool ok = live && s_bad == 0;
     if (ok && moments) {
-        int m = 0;
-        double lmin = sA[0][0];
-        for (int k = 1; k < 9; ++k) {                   // the smallest eigenvalue, the lowest index among equals
-            const double l = sA[k][k];
-            if (l < lmin) { lmin = l; m = k; }
-        }
-        int m2 = m == 0 ? 1 : 0;
-        double lsec = sA[m2][m2];
-        for (int k = m2 + 1; k < 9; ++k) {              // the second smallest
-            const double l = sA[k][k];
-            if (k != m && l < lsec) { lsec = l; m2 = k; }
-        }
+        double lmin;
+        const int m = refit_eigvec(sA, sV, e, lmin);
+        const double lsec = refit_second(sA, m);
         ev[0] = lmin; ev[1] = lsec;
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { e[k] = sV[k][m]; s += e[k] * e[k]; }
-        const double inv = 1.0 / __builtin_sqrt(s);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) e[k] *= inv;
         ok = __builtin_isfinite(lmin) && __builtin_isfinite(lsec);
     } else if (ok) {
         int h = best[p];

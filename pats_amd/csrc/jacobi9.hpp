@@ -1,5 +1,5 @@
-// The float64 cyclic Jacobi of a symmetric 9x9 matrix in LDS - the eigen-solve of the pose (pose.hip) and of the homography refit
-// (homography.hip) - and its rotation, which pose.hip's 3x3 Jacobi in registers shares.
+// The float64 cyclic Jacobi of a symmetric 9x9 matrix in LDS - the eigen-solve of the pose (pose.hip), of the homography refit
+// (homography.hip) and of the local optimisation's refits (polish.hip) - and its rotation, which refit.hpp's 3x3 Jacobi in registers shares.
 //   order   round-robin: a sweep is nine rounds of four disjoint rotations (p, q) = ((r + i) % 9, (r - i) % 9), i = 1 .. 4 - sixteen
 //           lanes per rotation (the first 64 threads of the workgroup), lane k < 9 of a group updates row / column entry k
 //   stop    a rotation whose off-diagonal entry no longer changes either diagonal entry when added to it is replaced by setting that

@@ -6,9 +6,9 @@
 //   one workgroup per pair, POSE_THREADS = 256 threads, decided by the sizes alone
 //   solve   float64.  The 9x9 matrix A and the accumulated rotations V live in LDS; wave 0 runs the round-robin cyclic Jacobi of
 //           jacobi9.hpp (shared with the homography refit), POSE_SWEEPS caps it.  Thread 0 then holds everything else in registers,
-//           all indices static: the eigenvector, G^T G of it as a 3x3 G, a 3x3 Jacobi for the right singular vectors, u_i = G v_i
-//           (Gram-Schmidt), u_3 = u_1 x u_2, v_3 = v_1 x v_2 (det U = det V = +1 by construction), E, R1, R2, u.  They go to LDS in
-//           float64 and float32.
+//           all indices static (refit.hpp, shared with polish.hip): the eigenvector, G^T G of it as a 3x3 G, a 3x3 Jacobi for the
+//           right singular vectors, u_i = G v_i (Gram-Schmidt), u_3 = u_1 x u_2, v_3 = v_1 x v_2 (det U = det V = +1 by
+//           construction), E, R1, R2, u.  They go to LDS in float64 and float32.
 //   vote    the workgroup walks the segment with epi_load; a match that is not used carries a NaN x_l.  pose_front4 gives the four
 //           verdicts of a match as bits (R1 and R2 share everything up to the two signs); ballots + popcounts per wave, the waves
 //           added in LDS by thread 0 (integer adds: no order), which picks the candidate and writes the per-pair outputs.
@@ -16,118 +16,12 @@
 #include "common.hpp"
 #include "epipolar.hpp"
 #include "jacobi9.hpp"
+#include "refit.hpp"
 
 namespace pats {
 
 constexpr int POSE_THREADS = 256;
 constexpr int POSE_WAVES = POSE_THREADS / WAVE;
-constexpr int POSE_SWEEPS = 16;                        // cap of both Jacobi loops (a sweep without a rotation ends them: the 7th or 8th)
-constexpr int POSE_MIN_INLIERS = 8;
-
-template <int P, int Q>
-__device__ __forceinline__ bool pose_rot3(double (&B)[3][3], double (&W)[3][3]) {
-    const double g = __builtin_fabs(B[P][Q]);
-    if (g == 0.0) return false;
-    if (jacobi_negligible(B[P][P], B[Q][Q], g)) {
-        B[P][Q] = B[Q][P] = 0.0;
-        return false;
-    }
-    double c, s;
-    jacobi_cs(B[P][P], B[Q][Q], B[P][Q], c, s);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = B[k][P], y = B[k][Q];
-        B[k][P] = c * x - s * y; B[k][Q] = s * x + c * y;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = B[P][k], y = B[Q][k];
-        B[P][k] = c * x - s * y; B[Q][k] = s * x + c * y;
-    }
-    B[P][Q] = B[Q][P] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = W[k][P], y = W[k][Q];
-        W[k][P] = c * x - s * y; W[k][Q] = s * x + c * y;
-    }
-    return true;
-}
-
-// columns a and b of W and their eigenvalues exchanged if la < lb
-template <int A_, int B_>
-__device__ __forceinline__ void pose_order(double (&l)[3], double (&W)[3][3]) {
-    const bool sw = l[A_] < l[B_];
-    const double la = l[A_], lb = l[B_];
-    l[A_] = sw ? lb : la; l[B_] = sw ? la : lb;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = W[k][A_], y = W[k][B_];
-        W[k][A_] = sw ? y : x; W[k][B_] = sw ? x : y;
-    }
-}
-
-__device__ __forceinline__ void pose_cross(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// e (a 3x3 G, row-major) -> E = U diag(s, s, 0) V^T with |E|_F = 1, R1 = U W V^T, R2 = U W^T V^T, u = U[:,2]; false: no pose
-__device__ __forceinline__ bool pose_decompose(const double (&e)[9], double (&E)[9], double (&R1)[9], double (&R2)[9], double (&u3)[3]) {
-    double G[3][3], B[3][3], W[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { G[i][j] = e[3 * i + j]; W[i][j] = i == j ? 1.0 : 0.0; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) B[i][j] = G[0][i] * G[0][j] + G[1][i] * G[1][j] + G[2][i] * G[2][j];
-    for (int sweep = 0; sweep < POSE_SWEEPS; ++sweep) {
-        bool any = pose_rot3<0, 1>(B, W);
-        any = pose_rot3<0, 2>(B, W) || any;
-        any = pose_rot3<1, 2>(B, W) || any;
-        if (!any) break;
-    }
-    double l[3] = {B[0][0], B[1][1], B[2][2]};
-    pose_order<0, 1>(l, W);                             // descending: the columns of W become v_1, v_2, (v_3)
-    pose_order<1, 2>(l, W);
-    pose_order<0, 1>(l, W);
-    double v1[3], v2[3], v3[3], u1[3], u2[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { v1[k] = W[k][0]; v2[k] = W[k][1]; }
-    pose_cross(v1, v2, v3);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        u1[i] = G[i][0] * v1[0] + G[i][1] * v1[1] + G[i][2] * v1[2];
-        u2[i] = G[i][0] * v2[0] + G[i][1] * v2[1] + G[i][2] * v2[2];
-    }
-    const double s1 = __builtin_sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-    if (!(s1 > 0.0)) return false;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u1[i] /= s1;
-    const double d = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u2[i] -= d * u1[i];
-    const double s2 = __builtin_sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-    if (!(s2 > 0.0)) return false;                      // rank below 2: no essential matrix is nearest
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u2[i] /= s2;
-    pose_cross(u1, u2, u3);
-    const double h = 0.70710678118654752440;            // 1 / sqrt 2
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double a = u1[i] * v1[j] + u2[i] * v2[j], b = u2[i] * v1[j] - u1[i] * v2[j], c = u3[i] * v3[j];
-            E[3 * i + j] = a * h;
-            R1[3 * i + j] = b + c;                      // U W V^T,  W = [[0,-1,0],[1,0,0],[0,0,1]]
-            R2[3 * i + j] = c - b;                      // U W^T V^T
-            ok = ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c);
-        }
-    return ok;
-}
 
 // THE cheirality test - the vote and the mask both call it.  Bit k: the match lies in front of both cameras under candidate k of
 // (R1, u), (R2, u), (R1, -u), (R2, -u).  A NaN l0 (a match that is not used) gives 0.
@@ -191,18 +85,8 @@ epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
         double e[9];
         bool ok = live && s_bad == 0;
         if (ok && moments) {
-            int m = 0;
-            double lmin = sA[0][0];
-            for (int k = 1; k < 9; ++k) {               // the smallest eigenvalue, the lowest index among equals
-                const double l = sA[k][k];
-                if (l < lmin) { lmin = l; m = k; }
-            }
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) { e[k] = sV[k][m]; s += e[k] * e[k]; }
-            const double inv = 1.0 / __builtin_sqrt(s);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) e[k] *= inv;
+            double lmin;
+            refit_eigvec(sA, sV, e, lmin);
         } else if (ok) {
             int h = best[p];
             h = h < 0 ? 0 : (h >= H ? H - 1 : h);

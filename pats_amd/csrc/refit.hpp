@@ -1,0 +1,170 @@
+// What the least-squares refits share (pose.hip: the pose; homography.hip: the homography refit; polish.hip: the local optimisation's
+// refit of either family): the pick of the eigenvector behind jacobi9.hpp's sweeps, the projection onto the essential matrices with
+// its decompositions, and the homography's permutation and sign rule.  include/pats_amd.h states the definitions.
+#pragma once
+#include "common.hpp"
+#include "jacobi9.hpp"
+
+namespace pats {
+
+constexpr int POSE_SWEEPS = 16;                        // cap of both Jacobi loops (a sweep without a rotation ends them: the 7th or 8th)
+constexpr int POSE_MIN_INLIERS = 8;
+constexpr int HOM_SWEEPS = 16;                         // cap of the Jacobi loop (a sweep without a rotation ends it)
+constexpr int HOM_MIN_INLIERS = 4;
+
+// behind jacobi9_sweeps: e = the unit eigenvector (column of V) of the smallest eigenvalue lmin (diagonal of A), the lowest index
+// among equals; returns that index
+__device__ __forceinline__ int refit_eigvec(const double (&sA)[9][9], const double (&sV)[9][9], double (&e)[9], double& lmin) {
+    int m = 0;
+    lmin = sA[0][0];
+    for (int k = 1; k < 9; ++k) {                       // the smallest eigenvalue, the lowest index among equals
+        const double l = sA[k][k];
+        if (l < lmin) { lmin = l; m = k; }
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { e[k] = sV[k][m]; s += e[k] * e[k]; }
+    const double inv = 1.0 / __builtin_sqrt(s);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) e[k] *= inv;
+    return m;
+}
+
+// the second smallest eigenvalue: the smallest over the indices other than m
+__device__ __forceinline__ double refit_second(const double (&sA)[9][9], int m) {
+    int m2 = m == 0 ? 1 : 0;
+    double lsec = sA[m2][m2];
+    for (int k = m2 + 1; k < 9; ++k) {                  // the second smallest
+        const double l = sA[k][k];
+        if (k != m && l < lsec) { lsec = l; m2 = k; }
+    }
+    return lsec;
+}
+
+template <int P, int Q>
+__device__ __forceinline__ bool pose_rot3(double (&B)[3][3], double (&W)[3][3]) {
+    const double g = __builtin_fabs(B[P][Q]);
+    if (g == 0.0) return false;
+    if (jacobi_negligible(B[P][P], B[Q][Q], g)) {
+        B[P][Q] = B[Q][P] = 0.0;
+        return false;
+    }
+    double c, s;
+    jacobi_cs(B[P][P], B[Q][Q], B[P][Q], c, s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = B[k][P], y = B[k][Q];
+        B[k][P] = c * x - s * y; B[k][Q] = s * x + c * y;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = B[P][k], y = B[Q][k];
+        B[P][k] = c * x - s * y; B[Q][k] = s * x + c * y;
+    }
+    B[P][Q] = B[Q][P] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = W[k][P], y = W[k][Q];
+        W[k][P] = c * x - s * y; W[k][Q] = s * x + c * y;
+    }
+    return true;
+}
+
+// columns a and b of W and their eigenvalues exchanged if la < lb
+template <int A_, int B_>
+__device__ __forceinline__ void pose_order(double (&l)[3], double (&W)[3][3]) {
+    const bool sw = l[A_] < l[B_];
+    const double la = l[A_], lb = l[B_];
+    l[A_] = sw ? lb : la; l[B_] = sw ? la : lb;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = W[k][A_], y = W[k][B_];
+        W[k][A_] = sw ? y : x; W[k][B_] = sw ? x : y;
+    }
+}
+
+__device__ __forceinline__ void pose_cross(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// e (a 3x3 G, row-major) -> E = U diag(s, s, 0) V^T with |E|_F = 1, R1 = U W V^T, R2 = U W^T V^T, u = U[:,2]; false: no pose
+__device__ __forceinline__ bool pose_decompose(const double (&e)[9], double (&E)[9], double (&R1)[9], double (&R2)[9], double (&u3)[3]) {
+    double G[3][3], B[3][3], W[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { G[i][j] = e[3 * i + j]; W[i][j] = i == j ? 1.0 : 0.0; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[i][j] = G[0][i] * G[0][j] + G[1][i] * G[1][j] + G[2][i] * G[2][j];
+    for (int sweep = 0; sweep < POSE_SWEEPS; ++sweep) {
+        bool any = pose_rot3<0, 1>(B, W);
+        any = pose_rot3<0, 2>(B, W) || any;
+        any = pose_rot3<1, 2>(B, W) || any;
+        if (!any) break;
+    }
+    double l[3] = {B[0][0], B[1][1], B[2][2]};
+    pose_order<0, 1>(l, W);                             // descending: the columns of W become v_1, v_2, (v_3)
+    pose_order<1, 2>(l, W);
+    pose_order<0, 1>(l, W);
+    double v1[3], v2[3], v3[3], u1[3], u2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v1[k] = W[k][0]; v2[k] = W[k][1]; }
+    pose_cross(v1, v2, v3);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        u1[i] = G[i][0] * v1[0] + G[i][1] * v1[1] + G[i][2] * v1[2];
+        u2[i] = G[i][0] * v2[0] + G[i][1] * v2[1] + G[i][2] * v2[2];
+    }
+    const double s1 = __builtin_sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+    if (!(s1 > 0.0)) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u1[i] /= s1;
+    const double d = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u2[i] -= d * u1[i];
+    const double s2 = __builtin_sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+    if (!(s2 > 0.0)) return false;                      // rank below 2: no essential matrix is nearest
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u2[i] /= s2;
+    pose_cross(u1, u2, u3);
+    const double h = 0.70710678118654752440;            // 1 / sqrt 2
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double a = u1[i] * v1[j] + u2[i] * v2[j], b = u2[i] * v1[j] - u1[i] * v2[j], c = u3[i] * v3[j];
+            E[3 * i + j] = a * h;
+            R1[3 * i + j] = b + c;                      // U W V^T,  W = [[0,-1,0],[1,0,0],[0,0,1]]
+            R2[3 * i + j] = c - b;                      // U W^T V^T
+            ok = ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c);
+        }
+    return ok;
+}
+
+// k -> P k for the permutation P = [[0,1,0],[1,0,0],[0,0,1]] applied to rows and columns of a row-major 3x3
+__device__ __forceinline__ int hom_perm(int k, int swapped) {
+    const int i = k / 3, j = k - 3 * i;
+    const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
+    return si * 3 + sj;
+}
+
+// out[k] = +-v[P k]: the permutation, then the sign rule judged on the values written (the lowest index among equals)
+__device__ __forceinline__ void hom_write(const double (&v)[9], bool ok, int swapped, double* __restrict__ out) {
+    double big = -1.0, at = 0.0;
+    for (int k = 0; k < 9; ++k) {
+        const double x = ok ? v[hom_perm(k, swapped)] : 0.0;
+        if (__builtin_fabs(x) > big) { big = __builtin_fabs(x); at = x; }
+    }
+    const bool flip = at < 0.0;
+    for (int k = 0; k < 9; ++k) {
+        const double x = ok ? v[hom_perm(k, swapped)] : 0.0;
+        out[k] = flip ? -x : x;
+    }
+}
+
+}  // namespace pats

@@ -1,0 +1,111 @@
+// The two model families of the per-pair verification and the mask kernel's moment reduction - what epipolar.hip's kernels and
+// polish.hip's local optimisation both run, written once.  include/pats_amd.h states the definitions; docs/kernels.md 4.7 / 4.11 the
+// design.
+//
+// A family is a struct with the two things that differ: test2, THE arithmetic of its test (two matches against one model), and
+// accumulate, a match's contribution to the moments.
+//   Epipolar    squared Sampson error against thr^2, without the division; the moments of q = vec(x_r x_l^T)
+//   Homography  squared forward transfer error against thr^2, without the division; the moments of the two DLT rows A_i, B_i
+#pragma once
+#include "common.hpp"
+
+namespace pats {
+
+constexpr int EPI_MASK_THREADS = 512;               // the walk whose order fixes the moments' bits
+constexpr int EPI_MASK_WAVES = EPI_MASK_THREADS / WAVE;
+constexpr int EPI_MOM = 45;                         // upper triangle of the 9x9 moment matrix
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ v2f pk_splat(float v) { return v2f{v, v}; }
+
+// The families.  test2: two matches against one model - match k is an inlier iff w[k] > 0 and s[k] <= lim[k]; the score and the mask
+// kernel both call it.  accumulate: an inlier's 45 products in float64 (the products of two float32 are exact).  The strings are the
+// names the launch checks report.
+struct Epipolar {
+    static constexpr const char *SCORE = "epipolar_score kernel", *ROUND = "epipolar_score kernel (a round)",
+                                *ARGMAX = "epipolar_argmax kernel", *MASK = "epipolar_mask kernel", *POLISH = "epipolar_polish kernel";
+    // s = r^2, lim = thr^2 den, w = den
+    static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
+        const v2f a0 = pk_fma(pk_splat(e[0]), l0, pk_fma(pk_splat(e[1]), l1, pk_splat(e[2])));
+        const v2f a1 = pk_fma(pk_splat(e[3]), l0, pk_fma(pk_splat(e[4]), l1, pk_splat(e[5])));
+        const v2f a2 = pk_fma(pk_splat(e[6]), l0, pk_fma(pk_splat(e[7]), l1, pk_splat(e[8])));
+        const v2f b0 = pk_fma(pk_splat(e[0]), r0, pk_fma(pk_splat(e[3]), r1, pk_splat(e[6])));
+        const v2f b1 = pk_fma(pk_splat(e[1]), r0, pk_fma(pk_splat(e[4]), r1, pk_splat(e[7])));
+        const v2f r = pk_fma(r0, a0, pk_fma(r1, a1, a2));
+        w = pk_fma(a0, a0, pk_fma(a1, a1, pk_fma(b0, b0, b1 * b1)));
+        s = r * r;
+        lim = pk_splat(t2) * w;
+    }
+    static __device__ __forceinline__ void accumulate(float xl0, float xl1, float xr0, float xr1, double (&acc)[EPI_MOM]) {
+        const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
+        const double q[9] = {b0 * a0, b0 * a1, b0, b1 * a0, b1 * a1, b1, a0, a1, 1.0};       // vec(x_r x_l^T): exact products
+        int k = 0;
+#pragma unroll
+        for (int u = 0; u < 9; ++u)
+#pragma unroll
+            for (int v = u; v < 9; ++v) acc[k++] += q[u] * q[v];
+    }
+};
+
+struct Homography {
+    static constexpr const char *SCORE = "homography_score kernel", *ROUND = "homography_score kernel (a round)",
+                                *ARGMAX = "homography_argmax kernel", *MASK = "homography_mask kernel", *POLISH = "homography_polish kernel";
+    // s = d0^2 + d1^2, lim = thr^2 a2^2, w = a2^2
+    static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
+        const v2f a0 = pk_fma(pk_splat(e[0]), l0, pk_fma(pk_splat(e[1]), l1, pk_splat(e[2])));
+        const v2f a1 = pk_fma(pk_splat(e[3]), l0, pk_fma(pk_splat(e[4]), l1, pk_splat(e[5])));
+        const v2f a2 = pk_fma(pk_splat(e[6]), l0, pk_fma(pk_splat(e[7]), l1, pk_splat(e[8])));
+        const v2f d0 = pk_fma(-r0, a2, a0);
+        const v2f d1 = pk_fma(-r1, a2, a1);
+        s = pk_fma(d0, d0, d1 * d1);
+        w = a2 * a2;
+        lim = pk_splat(t2) * w;
+    }
+    static __device__ __forceinline__ void accumulate(float xl0, float xl1, float xr0, float xr1, double (&acc)[EPI_MOM]) {
+        const double a0 = (double)xl0, a1 = (double)xl1, b0 = (double)xr0, b1 = (double)xr1;
+        // the rows A_i and B_i: the products of two float32 are exact in float64
+        const double qa[9] = {-a0, -a1, -1.0, 0.0, 0.0, 0.0, b0 * a0, b0 * a1, b0};
+        const double qb[9] = {0.0, 0.0, 0.0, -a0, -a1, -1.0, b1 * a0, b1 * a1, b1};
+        int k = 0;
+#pragma unroll
+        for (int u = 0; u < 9; ++u)
+#pragma unroll
+            for (int v = u; v < 9; ++v) acc[k++] += qa[u] * qa[v] + qb[u] * qb[v];
+    }
+};
+
+__device__ __forceinline__ void verify_model(const float* __restrict__ m, float (&e)[9]) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) e[k] = m[k];
+}
+
+// The moments' fixed order behind the thread-local sums of an EPI_MASK_THREADS walk: an xor tree over the wave, then the waves in
+// order.  EVERY thread of the workgroup calls this (one barrier inside); thread k < EPI_MOM gets entry k of the upper triangle.
+__device__ __forceinline__ double verify_moments_sum(const double (&acc)[EPI_MOM], double (&part)[EPI_MASK_WAVES][EPI_MOM], int tid, int lane,
+                                                     int wave) {
+#pragma unroll
+    for (int k = 0; k < EPI_MOM; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) part[wave][k] = v;
+    }
+    wg_barrier();
+    double s = 0.0;
+    if (tid < EPI_MOM) {
+#pragma unroll
+        for (int w = 0; w < EPI_MASK_WAVES; ++w) s += part[w][tid];
+    }
+    return s;
+}
+
+// entry k of the upper triangle -> (u, v), u <= v
+__device__ __forceinline__ void verify_triangle(int k, int& u, int& v) {
+    u = 0;
+    while (k >= 9 - u) { k -= 9 - u; ++u; }
+    v = u + k;
+}
+
+}  // namespace pats

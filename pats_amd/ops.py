@@ -2487,3 +2487,82 @@ def scale_head(desc1, height, width, weights, biases, return_heads=False):
     if return_heads:
         return out, [per[:, i:i + 1, :] for i in range(heads)]
     return out
+
+
+def _polish_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride, counts, conf, min_conf,
+                    norm, out, pairs):
+    """What the two local optimisations share - everything but the C entry and its workspace query (looked up by the callers, as for
+    _score_by_pair)."""
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (best, "best"),
+                    (pair_off, "pair_off"), (counts, "counts"), (conf, "conf"), (norm, "norm")],
+               {"best": torch.int32, "pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("%s: min_conf needs conf" % fn)
+    rounds = int(rounds)
+    if not 1 <= rounds <= 16:
+        raise RuntimeError("%s: rounds = %d, must lie in 1 .. 16" % (fn, rounds))
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
+        raise RuntimeError("%s: models must be [pairs,H,3,3]" % fn)
+    H = int(models.shape[1])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("%s: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % (fn, pairs))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    if best is None:
+        if H != 1:
+            raise RuntimeError("%s: best may be left out with H == 1 only, got H = %d" % (fn, H))
+    else:
+        best = _dev(best, "best", torch.int32).reshape(-1)
+        if best.numel() != pairs:
+            raise RuntimeError("%s: best must hold one int32 per pair (%d), got %d" % (fn, pairs, best.numel()))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("%s: conf must be [cap]" % fn)
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("model", torch.float32, (pairs, 3, 3)), ("best_count", torch.int64, (pairs,)), ("inlier", torch.uint8, (cap,)),
+            ("moments", torch.float64, (pairs, 9, 9)), ("best_round", torch.int32, (pairs,)), ("counts", torch.int32, (pairs, rounds + 1))]
+    out = _bp_outputs(fn, want, out, dev)
+    nws = workspace_bytes(pairs, H, cap)
+    ws = _workspace(nws, dev) if nws else None
+    inl = out[2]
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else ml
+    _check(entry(
+        _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(thr), _ptr(norm), 0 if min_conf is None else 1,
+        0.0 if min_conf is None else float(min_conf), _ptr(models), H, _ptr(best), rounds, _ptr(out[0]), _ptr(out[1]), _ptr(inl),
+        _ptr(out[3]), _ptr(out[4]), _ptr(out[5]), _ptr(ws), nws, _stream()), fn)
+    return out
+
+
+def epipolar_polish_by_pair(matches_l, matches_r, models, thr, best=None, rounds=4, pair_off=None, stride=None, counts=None, conf=None,
+                            min_conf=None, norm=None, out=None, pairs=None):
+    """Local optimisation of each pair's winning epipolar model, ON THE DEVICE, one launch, no host read
+    (pats_epipolar_polish_by_pair_f32; include/pats_amd.h, "Per-pair local optimisation", holds the definition): starting from
+    m_0 = models[p, best[p]], `rounds` times "refit the current model's inliers (epipolar_pose_by_pair's E, cast to float32), verify the
+    refit (epipolar_score_by_pair with that one model)", and the round with the most inliers - the lowest among equals, round 0 being
+    the input - is returned.  Every value equals what that chain of calls gives, bit for bit.  matches_l / matches_r, the segment
+    forms (pair_off, or stride + counts), conf / min_conf, norm and thr exactly as epipolar_score_by_pair takes them; models
+    [pairs,H,3,3] float32 and best [pairs] int32 are its input and output (best may be left out with H == 1); 1 <= rounds <= 16.
+    Returns (model [pairs,3,3] float32, best_count [pairs] int64, inlier [cap] uint8, moments [pairs,9,9] float64 - the best round's,
+    what epipolar_pose_by_pair takes -, best_round [pairs] int32, counts [pairs, rounds + 1] int32: the support of every round, a walk
+    that stopped early on a repeated model padded with its count).  out: the six destinations."""
+    return _polish_by_pair("epipolar_polish_by_pair", _L().pats_epipolar_polish_by_pair_f32, _L().pats_epipolar_polish_workspace_bytes,
+                           matches_l, matches_r, models, thr, best, rounds, pair_off, stride, counts, conf, min_conf, norm, out, pairs)
+
+
+def homography_polish_by_pair(matches_l, matches_r, models, thr, best=None, rounds=4, pair_off=None, stride=None, counts=None, conf=None,
+                              min_conf=None, norm=None, out=None, pairs=None):
+    """epipolar_polish_by_pair for homographies (pats_homography_polish_by_pair_f32): the same arguments, the same outputs, the
+    forward transfer error of homography_score_by_pair as the test and homography_refit_by_pair's H, cast to float32, as the refit;
+    moments and best_count are what homography_refit_by_pair takes."""
+    return _polish_by_pair("homography_polish_by_pair", _L().pats_homography_polish_by_pair_f32,
+                           _L().pats_homography_polish_workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride,
+                           counts, conf, min_conf, norm, out, pairs)
