@@ -852,8 +852,8 @@ int pats_epipolar_hypotheses_by_pair_f32(const float* matches_l, const float* ma
  * are written as row-major 3x3 models.  What cv2.findEssentialMat's RANSAC solves per sample.  One launch, no host read, no
  * workspace, deterministic.  The points must be calibrated: norm carries the intrinsics ((c, s) = (principal point, 1 / focal
  * length) per side); without norm the solver runs on (p0, p1, 1) as if those were calibrated coordinates.
- * What it is not: a 7-point solver, cheirality and pose (pats_epipolar_pose_by_pair_f64), local optimisation
- * (pats_epipolar_polish_by_pair_f32), adaptive termination.
+ * What it is not: cheirality and pose (pats_epipolar_pose_by_pair_f64), local optimisation (pats_epipolar_polish_by_pair_f32),
+ * adaptive termination; the uncalibrated sibling is pats_epipolar_hypotheses7_by_pair_f32.
  *   x          the verification's point, formed exactly as there: ((p0 - c0) * s0, (p1 - c1) * s1, 1) in float32 - one subtract,
  *              then one multiply, never contracted - or (p0, p1, 1) without norm.  The segment of pair p (n rows from lo on) in the
  *              same two forms, ragged (pair_off) or strided (stride, counts_in), with the same clamping as above
@@ -1117,8 +1117,8 @@ int pats_homography_score_adaptive_by_pair_f32(const float* matches_l, const flo
  * verification - LO-RANSAC's inner loop in its simplest form - walked by ONE launch per call with the pair's matches resident on
  * chip, and the BEST round kept: the result never has less support than the model it started from.  No new numerics: every value
  * returned is one the entry points above produce, and a caller who chains them gets the same bits.  On the device, no host read.
- * What it is not: no essential projection for uncalibrated callers (a plain F refit without rank 2), no shrinking threshold, no
- * inner RANSAC on the inlier set, no PROSAC rule, and nothing in pipeline.forward_* or the drop-in calls it.
+ * What it is not: no shrinking threshold, no inner RANSAC on the inlier set, no PROSAC rule, and nothing in pipeline.forward_* or
+ * the drop-in calls it.  Uncalibrated callers use pats_fundamental_polish_by_pair_f32 ("Per-pair fundamental matrices" below).
  * pats_epipolar_polish_by_pair_f32 (family F = Epipolar, min_F = 8) and pats_homography_polish_by_pair_f32 (F = Homography,
  * min_F = 4) take the verification's match, segment, thr, norm and min_conf arguments - the same two segment forms, the same
  * clamping, the same rule for a match that participates - and then
@@ -1171,6 +1171,111 @@ int pats_homography_polish_by_pair_f32(const float* matches_l, const float* matc
                                        const int32_t* best, int rounds, float* model, int64_t* best_count, uint8_t* inlier,
                                        double* moments, int32_t* best_round, int32_t* counts, void* workspace, size_t workspace_bytes,
                                        pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair 7-point hypotheses (ABI 8, symbols added): the uncalibrated sibling of the per-pair hypotheses - for every pair p and every
+ * sample h in 0 .. H-1 SEVEN distinct matches of the pair are drawn and the real fundamental matrices through them, at most three,
+ * are written as row-major 3x3 models: rank 2 by construction, the cheapest epipolar sample RANSAC can use.  What
+ * cv2.findFundamentalMat's RANSAC solves per sample.  One launch, no host read, no workspace, deterministic.  No calibration is
+ * needed: norm is the verification's normalisation, whatever it is (advice for uncalibrated callers: INTEGRATION.md).
+ * What it is not: a plane-and-parallax (DEGENSAC) check, epipoles, rectification, self-calibration.
+ *   x          the verification's point, formed exactly as there: ((p0 - c0) * s0, (p1 - c1) * s1, 1) in float32 - one subtract,
+ *              then one multiply, never contracted - or (p0, p1, 1) without norm.  The segment of pair p (n rows from lo on) in the
+ *              same two forms, ragged (pair_off) or strided (stride, counts_in), with the same clamping as above
+ *   pool       m_h = n (progressive == 0)  or  max(7, (n (h + 1) + H - 1) / H)  in int64 arithmetic
+ *   sampler    the hypotheses' with seven draws: k = mix(mix(mix(s_lo) ^ s_hi) + h),  u_t = mix(k + 0x9e3779b9 (t + 1)),
+ *              j_t = (uint64(u_t) (m_h - t)) >> 32,  t = 0 .. 6,  draw t = the j_t-th index of 0 .. m_h - 1 not drawn before: the
+ *              first seven draws of the 8-point sample with the same seed, h and pool
+ *   sample_idx [pairs,H,7] int32 (optional: null skips it), the draws in draw order;  -1 for n < 7
+ *   A7         [7,9] float64, row t = vec(x_r x_l^T) of draw t (q[3i + j] = x_r[i] x_l[j]; exact products of the float32 points)
+ *   basis      F1, F2: an orthonormal basis of the null space of A7 (the last two columns of Q of a Householder QR of A7^T: two
+ *              orthonormal vectors orthogonal to every row whatever the rank)
+ *   solutions  every real (a : b) with det(a F1 + b F2) = 0 - a binary cubic, one or three real roots; a vanishing leading
+ *              coefficient is a root at infinity of b / a and the root 0 of a / b, never a division by zero.  F = a F1 + b F2
+ *              scaled to |F|_F = 1, the component of largest magnitude positive (the lowest index among equals, judged on the
+ *              float32 values written); at most 3
+ *   models     [pairs,H,3,3,3] float32, row-major (= [pairs, 3 H, 3, 3]: a `models` argument of pats_epipolar_score_by_pair_f32 as
+ *              it stands).  The solutions found occupy the lowest slots of their sample, every other slot is nine exact zeros.
+ *              Order: first the roots with |b / a| <= 1 by ascending b / a, then those with |a / b| <= 1 by ascending a / b.  A
+ *              solution within 1 - |<a, b>| <= 2e-6 of one already stored for its sample is not stored again (a double root; a
+ *              root with |a| = |b|, which both ranges hold)
+ *   n_models   [pairs,H] int32 (optional: null skips it): the number of non-zero slots
+ *   zero       all three slots zero (n_models 0): n < 7 (sample_idx -1);  a sample with a non-finite coordinate after norm
+ *              (sample_idx still written);  a cubic that vanishes identically or has a non-finite coefficient.  A rank-deficient
+ *              sample (seven copies of one match) gives zeros or finite unit models.  Never a NaN or an infinity
+ *   contract   every non-zero model e, promoted to float64, with A7 formed exactly from the float32 points:
+ *                | |e| - 1 | <= 1e-5
+ *                |A7 e|_2    <= B_epi eps32 |A7|_F
+ *                |det F|     <= B_det eps32
+ *              The solve is float64 throughout (null space by Householder QR, the cubic's coefficients from the cofactors, its
+ *              critical points from one square root, a bracketed Newton iteration of at most 64 steps per monotone piece: no
+ *              closed form with acos or cbrt).  Rounding a rank-2 unit matrix to float32 moves its determinant by at most
+ *              eps32 / 4.  Completeness is a tested share (docs/parity.md), not a pointwise promise.  The tests hold B_epi and
+ *              B_det to 8 times what a float64 LAPACK solve, rounded to float32, reaches on the same samples
+ *   limits     1 <= H and 3 H <= pats_epipolar_max_h()
+ * Adaptive verification of these models needs nothing new: pats_epipolar_score_adaptive_by_pair_f32 with sample_size = 7,
+ * models_per_sample = 3 and round_models a multiple of 64 - 192 keeps the rounds on sample boundaries.
+ * Outputs - every call defines every byte of all three.  cap == 0 is a valid call (every model zero; the match pointers must still
+ * be non-null).  Refused before any launch (pats_last_error names the argument), in the wording and order of
+ * pats_epipolar_hypotheses5_by_pair_f32: what that refuses, with 3 H > max_h in place of 10 H > max_h; a workspace smaller than
+ * pats_epipolar_hypotheses7_workspace_bytes (0 today: a sample lives in its thread's registers; workspace may then be null).  The
+ * kernel uses no LDS: there is no PATS_ERR_UNSUPPORTED case. */
+size_t pats_epipolar_hypotheses7_workspace_bytes(int64_t pairs, int64_t H);
+int pats_epipolar_hypotheses7_by_pair_f32(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                          const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
+                                          const float* norm, int progressive, float* models, int32_t* sample_idx, int32_t* n_models,
+                                          void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair fundamental matrices (ABI 8, symbols added): the result of the epipolar stages for a caller without intrinsics - the
+ * least-squares refit of the winner's moments truncated to rank 2, taken back to the stored coordinates the way the homography
+ * refit does, and the local optimisation that refits with it.  The sibling of pats_homography_refit_by_pair_f64: the same launch
+ * shape (one wave per pair), the same Jacobi, the same arguments with two outputs more.  On the device, float64, no host read.
+ * What it is not: epipoles, rectification, a plane-and-parallax check, self-calibration from F.
+ * pats_fundamental_refit_by_pair_f64 - best_count [pairs] int64 and moments [pairs,9,9] float64 (or, moments null, models
+ * [pairs,H,3,3] float32 with best [pairs] int32) as pats_epipolar_score_by_pair_f32 or a local optimisation returned them; norm
+ * [pairs,8] float32 or null, what the verification was given; swapped 0 or 1.  Per pair p
+ *   f_refit   [pairs,9] float64 (optional output: null skips it): the unit eigenvector of moments[p] for its smallest eigenvalue,
+ *             the lowest index among equals (only the upper triangle of moments[p] is read); without moments
+ *             models[p, clamp(best[p], 0, H-1)] promoted, as it stands
+ *   sigma     [pairs,3] float64: the singular values of f_refit as a row-major 3x3, descending
+ *   F         [pairs,3,3] float64 = U diag(s1, s2, 0) V^T of f_refit, rescaled to |F|_F = 1, the component of largest magnitude
+ *             positive (the lowest index among equals: the homography refit's sign rule).  Cast to float32 it is a model for
+ *             pats_epipolar_score_by_pair_f32
+ *   F_px      [pairs,3,3] float64 (optional output: null skips it) = N_r^T F N_l rescaled to Frobenius norm 1, the same sign rule,
+ *             N = [[s0, 0, -c0 s0], [0, s1, -c1 s1], [0, 0, 1]] per side from norm[p] (float32 widened exactly): the fundamental
+ *             matrix of the stored (c0, c1) coordinates, x_r^T F_px x_l = 0 on them.  F itself without norm
+ *   eig       [pairs,2] float64: the two smallest eigenvalues of moments[p], ascending (0, 0 without moments)
+ *   no model  best_count[p] < 8, a non-finite moment (upper triangle) or a non-finite f_refit, s2 == 0 (rank below 2; the zero
+ *             model): zeros in F, F_px, eig, sigma and f_refit.  F_px alone is zero as well when the denormalisation is not
+ *             finite or a scale of norm[p] is zero (N is then singular: no change of coordinates).  Never a NaN or an infinity
+ *   swapped   1: the points were in (y, x) order - F and F_px are returned as P F P, P = [[0,1,0],[1,0,0],[0,0,1]], with the sign
+ *             rule applied after the permutation; sigma, eig and f_refit do not change
+ * Accuracy, as the tests hold it: | |F| - 1 | and |det F| <= 64 eps64; F within 64 eps64 / (sigma2 - sigma3) (Wedin) of LAPACK's
+ * truncated SVD of the same f_refit; sigma within 64 eps64; eig and the eigen-residual of f_refit as for the homography refit.
+ * Refused before any launch, in the wording and order of pats_homography_refit_by_pair_f64: a null best_count / F / eig / sigma;
+ * best_count / moments / F / F_px / eig / sigma / f_refit off 8 bytes, models / best / norm off 4; pairs < 1; swapped not 0 or 1;
+ * neither moments nor (models and best); with models H < 1 or H > max_h; a workspace smaller than
+ * pats_fundamental_refit_workspace_bytes (0 today; workspace may be null).
+ * pats_fundamental_polish_by_pair_f32 - "Per-pair local optimisation" above with family F = Fundamental, min_F = 8: the Epipolar
+ * family's support (the same Sampson test, the same moments) and
+ *   refit_F(M, c)  float32 cast (round to nearest even) of the F that pats_fundamental_refit_by_pair_f64 returns for (moments = M,
+ *                best_count = c, swapped = 0); "no model" there gives the zero model
+ * Arguments, outputs, refusals and wording are those of pats_epipolar_polish_by_pair_f32; moments and best_count are the input of
+ * pats_fundamental_refit_by_pair_f64.  A caller who chains pats_epipolar_score_by_pair_f32 (H = 1, moments) and
+ * pats_fundamental_refit_by_pair_f64 round for round gets the same bits. */
+size_t pats_fundamental_refit_workspace_bytes(int64_t pairs);
+int pats_fundamental_refit_by_pair_f64(const int64_t* best_count, const double* moments, const float* models, int64_t H,
+                                       const int32_t* best, const float* norm, int64_t pairs, int swapped, double* F, double* F_px,
+                                       double* eig, double* sigma, double* f_refit, void* workspace, size_t workspace_bytes,
+                                       pats_stream_t stream);
+size_t pats_fundamental_polish_workspace_bytes(int64_t pairs, int64_t H, int64_t cap);
+int pats_fundamental_polish_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                        int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* thr,
+                                        const float* norm, int use_min_conf, float min_conf, const float* models, int64_t H,
+                                        const int32_t* best, int rounds, float* model, int64_t* best_count, uint8_t* inlier,
+                                        double* moments, int32_t* best_round, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                        pats_stream_t stream);
 
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the

@@ -277,6 +277,16 @@ SIGNATURES = {
     "pats_epipolar_polish_by_pair_f32": (c_int, _POLISH_ARGS),
     "pats_homography_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
     "pats_homography_polish_by_pair_f32": (c_int, _POLISH_ARGS),
+    # the uncalibrated branch: 7-point hypotheses, up to three fundamental matrices per sample (csrc/hypotheses7.hip), the rank-2
+    # refit (csrc/fundamental.hip: the homography refit's arguments with sigma and f_refit behind eig) and its local optimisation
+    "pats_epipolar_hypotheses7_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_epipolar_hypotheses7_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
+                                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_fundamental_refit_workspace_bytes": (c_size, [c_i64]),
+    "pats_fundamental_refit_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_fundamental_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "pats_fundamental_polish_by_pair_f32": (c_int, _POLISH_ARGS),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -473,7 +473,7 @@ def split_topk_by_pair(out, cap):
 
 
 def _sample_by_pair(fn, generate, out, cap, H, seed, norm, on, progressive, samples):
-    """What hypothesize_by_pair and hypothesize5_by_pair share: the order handling, the per-pair seeds (pair i of the CALLER's order
+    """What hypothesize_by_pair, hypothesize5_by_pair and hypothesize7_by_pair share: the order handling, the per-pair seeds (pair i of the CALLER's order
     gets seed + i, built on the device once per seed and kept in the result), the permutation of norm to slot order and of the
     results back to the caller's.  generate = the ops function."""
     _check_on(fn, out, on)
@@ -524,6 +524,19 @@ def hypothesize5_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=
     flat = (hyp[0] if samples else hyp).flatten(1, 2)                     # [pairs,H,10,3,3] -> [pairs,10 H,3,3]: a view
     hyp = (flat, hyp[1]) if samples else flat
     out["hypotheses5"] = hyp
+    return hyp
+
+
+def hypothesize7_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
+    """Device side, after the matching: H 7-point samples per pair, each solved for the up to three fundamental matrices through
+    it (ops.epipolar_hypotheses7_by_pair: one launch, no host read) - the branch of a caller without intrinsics.  on, progressive
+    (the pool's minimum is 7 here), seed and norm exactly as hypothesize_by_pair takes them; norm need not carry any calibration.
+    Returns models [pairs,H,3,3,3] float32 - or (models, sample_idx [pairs,H,7] int32) with samples=True - in the CALLER's order:
+    models.reshape(pairs, -1, 3, 3) goes straight into verify_by_pair(out, cap, ..., thr, norm=norm, on=...), sample h owning rows
+    3 h .. 3 h + 2, its solutions first, zero models (which verification ignores) behind.  Adds `hypotheses7` (what is returned) to
+    the result; `hypotheses`, `hypotheses5`, the matches, the regrouped lists and a top-K of the same step are not touched."""
+    hyp = _sample_by_pair("hypothesize7_by_pair", ops.epipolar_hypotheses7_by_pair, out, cap, H, seed, norm, on, progressive, samples)
+    out["hypotheses7"] = hyp
     return hyp
 
 
@@ -678,8 +691,9 @@ def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
     return res
 
 
-def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf):
-    """What polish_by_pair and polish_h_by_pair share; polish = the ops function, key = "verified" / "verified_h"."""
+def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf, store=None):
+    """What polish_by_pair, polish_h_by_pair and polish_f_by_pair share; polish = the ops function, key = "verified" / "verified_h",
+    store = the name the walk is stored under (default: "polished" / "polished_h")."""
     if key not in out:
         raise ValueError("%s: run %s first" % (fn, "verify_by_pair" if key == "verified" else "verify_h_by_pair"))
     if min_conf is not None and "match_conf" not in out:
@@ -693,7 +707,7 @@ def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf):
     model, best_count, inl, moments, best_round, counts = polish(
         ml, mr, out[key + "_models"], thr, best=best, rounds=rounds, conf=conf if min_conf is not None else None, min_conf=min_conf,
         norm=norm, **seg)
-    out["polished" if key == "verified" else "polished_h"] = (model, best_round, counts)
+    out[store or ("polished" if key == "verified" else "polished_h")] = (model, best_round, counts)
     out[key] = (best_count.to(torch.int32)[:, None], torch.zeros_like(best), best_count, inl, moments)
     out[key + "_models"] = model[:, None]
     return out[key]
@@ -716,6 +730,39 @@ def polish_h_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
     """polish_by_pair for the homography branch, after verify_h_by_pair / verify_h_adaptive_by_pair (ops.homography_polish_by_pair):
     stores `polished_h` and replaces `verified_h` and `verified_h_models` - homography_by_pair works on the result unchanged."""
     return _polish("polish_h_by_pair", ops.homography_polish_by_pair, "verified_h", out, cap, thr, rounds, norm, min_conf)
+
+
+def polish_f_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
+    """polish_by_pair for uncalibrated callers, after verify_by_pair / verify_adaptive_by_pair (ops.fundamental_polish_by_pair): the
+    refit of every round is fundamental_by_pair's rank-2 F instead of the pose's essential matrix.  Stores `polished_f` and replaces
+    `verified` and `verified_models` as polish_by_pair does - fundamental_by_pair works on the result unchanged."""
+    return _polish("polish_f_by_pair", ops.fundamental_polish_by_pair, "verified", out, cap, thr, rounds, norm, min_conf, store="polished_f")
+
+
+def fundamental_by_pair(out, cap, norm=None, swapped=False, pixel=False):
+    """Device side, after verify_by_pair (or polish_f_by_pair): each pair's fundamental matrix from its verified inliers
+    (ops.fundamental_refit_by_pair: one launch, float64, no host read) - the smallest eigenvector of `verified`'s moments if the
+    verification produced them, otherwise its winning model, truncated to rank 2.  It picks its inputs exactly as pose_by_pair does
+    and needs no intrinsics.  norm [pairs,8] or None in the CALLER's order - pass what verify_by_pair was given.  swapped: the lists
+    are in the hand-over's (y, x) order and F is wanted in the reference's (x, y) frame.
+    Returns (F [pairs,3,3] float64, eig [pairs,2] float64: the two smallest eigenvalues of the moments, sigma [pairs,3] float64: the
+    refit's singular values before the truncation) in the CALLER's order - with pixel=True followed by F_px [pairs,3,3]: the
+    fundamental matrix of the stored coordinates - and stores them as `fundamental`.  F.float() goes straight back into
+    verify_by_pair as an H = 1 model: the local-optimisation round, which polish_f_by_pair runs `rounds` times in one launch."""
+    if "verified" not in out:
+        raise ValueError("fundamental_by_pair: run verify_by_pair first")
+    ver = out["verified"]
+    best, best_count = ver[1:3]
+    mixed = "caller_of" in out
+    if mixed and norm is not None:
+        norm = norm.index_select(0, _caller_of_dev(out, best.device))
+    src = {"moments": ver[4]} if len(ver) > 4 else {"models": out["verified_models"], "best": best}
+    res = ops.fundamental_refit_by_pair(best_count, norm=norm, swapped=swapped, return_pixel=pixel, **src)
+    if mixed:                                                             # slots back to the caller's order
+        back = _slot_of_dev(out, cap, best.device)
+        res = tuple(t.index_select(0, back) for t in res)
+    out["fundamental"] = res
+    return res
 
 
 def verify_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,

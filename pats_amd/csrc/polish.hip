@@ -1,7 +1,7 @@
 // Per-pair local optimisation: the rounds "refit the winner's inliers, verify the refit" that follow a verification, walked by ONE
 // launch with the pair's matches resident in LDS, the best round kept.  Every value is one the existing entry points produce - the
-// support of a model is the verification's (H = 1, moments), the refit the pose's E or the homography refit's H cast to float32 - so
-// the result equals that chain of calls bit for bit.  include/pats_amd.h states the definition ("Per-pair local optimisation");
+// support of a model is the verification's (H = 1, moments), the refit the pose's E, the fundamental refit's F or the homography
+// refit's H cast to float32 - so the result equals that chain of calls bit for bit.  include/pats_amd.h states the definition ("Per-pair local optimisation");
 // docs/kernels.md 4.13 the design.
 //
 //   verify_polish_kernel<T>: one workgroup per pair, EPI_MASK_THREADS = 512 threads (the walk whose order fixes the moments' bits),
@@ -31,8 +31,8 @@ constexpr int POLISH_STAGE = 8192;                     // matches a workgroup ke
 constexpr int POLISH_MAX_ROUNDS = 16;
 constexpr int POLISH_LDS = POLISH_STAGE * (int)sizeof(float4);
 
-// the families' refits, on one thread behind jacobi9_sweeps: what pats_epipolar_pose_by_pair_f64 / pats_homography_refit_by_pair_f64
-// return for (moments, best_count, swapped = 0), cast to float32.  live: the count reaches the family's minimum; bad: a non-finite moment
+// the families' refits, on one thread behind jacobi9_sweeps: what pats_epipolar_pose_by_pair_f64 / pats_homography_refit_by_pair_f64 /
+// pats_fundamental_refit_by_pair_f64 return for (moments, best_count, swapped = 0), cast to float32.  live: the count reaches the family's minimum; bad: a non-finite moment
 template <class T> struct PolishRefit;
 
 template <> struct PolishRefit<Epipolar> {
@@ -69,6 +69,17 @@ template <> struct PolishRefit<Homography> {
             ok = ok && any;                             // the zero model is no model
         }
         hom_write(e, ok, 0, out);
+    }
+};
+
+// pats_fundamental_refit_by_pair_f64's F: the refit truncated to rank 2 instead of projected onto the essential matrices
+template <> struct PolishRefit<Fundamental> {
+    static constexpr int MIN_INLIERS = FUND_MIN_INLIERS, SWEEPS = FUND_SWEEPS;
+    static __device__ __forceinline__ void refit(const double (&sA)[9][9], const double (&sV)[9][9], bool live, bool bad, double (&out)[9]) {
+        double e[9], F[9], sig[3], ev[2];
+        bool ok = live && !bad;
+        if (ok) ok = fund_from_moments(sA, sV, e, ev, F, sig);
+        hom_write(F, ok, 0, out);
     }
 };
 
@@ -298,6 +309,7 @@ static int verify_polish_by_pair(const char* who, const float* matches_l, const 
 // ---- the entry points (include/pats_amd.h) ---------------------------------------------------------------------------------------
 extern "C" size_t pats_epipolar_polish_workspace_bytes(int64_t, int64_t, int64_t) { return 0; }
 extern "C" size_t pats_homography_polish_workspace_bytes(int64_t, int64_t, int64_t) { return 0; }
+extern "C" size_t pats_fundamental_polish_workspace_bytes(int64_t, int64_t, int64_t) { return 0; }
 
 extern "C" int pats_epipolar_polish_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
                                                 int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* thr,
@@ -317,4 +329,14 @@ extern "C" int pats_homography_polish_by_pair_f32(const float* matches_l, const 
     return verify_polish_by_pair<Homography>("homography_polish_by_pair", matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap,
                                              thr, norm, use_min_conf, min_conf, models, H, best, rounds, model, best_count, inlier, moments,
                                              best_round, counts, stream);
+}
+
+extern "C" int pats_fundamental_polish_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                                   int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* thr,
+                                                   const float* norm, int use_min_conf, float min_conf, const float* models, int64_t H,
+                                                   const int32_t* best, int rounds, float* model, int64_t* best_count, uint8_t* inlier,
+                                                   double* moments, int32_t* best_round, int32_t* counts, void*, size_t, pats_stream_t stream) {
+    return verify_polish_by_pair<Fundamental>("fundamental_polish_by_pair", matches_l, matches_r, conf, pair_off, stride, counts_in, pairs, cap,
+                                              thr, norm, use_min_conf, min_conf, models, H, best, rounds, model, best_count, inlier, moments,
+                                              best_round, counts, stream);
 }

@@ -1,6 +1,7 @@
-// What the least-squares refits share (pose.hip: the pose; homography.hip: the homography refit; polish.hip: the local optimisation's
-// refit of either family): the pick of the eigenvector behind jacobi9.hpp's sweeps, the projection onto the essential matrices with
-// its decompositions, and the homography's permutation and sign rule.  include/pats_amd.h states the definitions.
+// What the least-squares refits share (pose.hip: the pose; homography.hip: the homography refit; fundamental.hip: the rank-2 refit;
+// polish.hip: the local optimisation's refit of every family): the pick of the eigenvector behind jacobi9.hpp's sweeps, the projection
+// onto the essential matrices with its decompositions, the rank-2 truncation, and the homography's permutation and sign rule.
+// include/pats_amd.h states the definitions.
 #pragma once
 #include "common.hpp"
 #include "jacobi9.hpp"
@@ -11,6 +12,8 @@ constexpr int POSE_SWEEPS = 16;                        // cap of both Jacobi loo
 constexpr int POSE_MIN_INLIERS = 8;
 constexpr int HOM_SWEEPS = 16;                         // cap of the Jacobi loop (a sweep without a rotation ends it)
 constexpr int HOM_MIN_INLIERS = 4;
+constexpr int FUND_SWEEPS = 16;                        // cap of both Jacobi loops of the fundamental refit
+constexpr int FUND_MIN_INLIERS = 8;
 
 // behind jacobi9_sweeps: e = the unit eigenvector (column of V) of the smallest eigenvalue lmin (diagonal of A), the lowest index
 // among equals; returns that index
@@ -144,6 +147,78 @@ __device__ __forceinline__ bool pose_decompose(const double (&e)[9], double (&E)
             ok = ok && __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c);
         }
     return ok;
+}
+
+// e (a 3x3 G, row-major) -> F = U diag(s1, s2, 0) V^T rescaled to |F|_F = 1 and sig = the singular values of G, descending - the
+// route of pose_decompose with both singular values kept and the third term dropped; false: rank below 2, no fundamental matrix
+__device__ __forceinline__ bool fund_project(const double (&e)[9], double (&F)[9], double (&sig)[3]) {
+    double G[3][3], B[3][3], W[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { G[i][j] = e[3 * i + j]; W[i][j] = i == j ? 1.0 : 0.0; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[i][j] = G[0][i] * G[0][j] + G[1][i] * G[1][j] + G[2][i] * G[2][j];
+    for (int sweep = 0; sweep < FUND_SWEEPS; ++sweep) {
+        bool any = pose_rot3<0, 1>(B, W);
+        any = pose_rot3<0, 2>(B, W) || any;
+        any = pose_rot3<1, 2>(B, W) || any;
+        if (!any) break;
+    }
+    double l[3] = {B[0][0], B[1][1], B[2][2]};
+    pose_order<0, 1>(l, W);                             // descending: the columns of W become v_1, v_2, (v_3)
+    pose_order<1, 2>(l, W);
+    pose_order<0, 1>(l, W);
+    double v1[3], v2[3], v3[3], u1[3], u2[3], u3[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v1[k] = W[k][0]; v2[k] = W[k][1]; }
+    pose_cross(v1, v2, v3);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        u1[i] = G[i][0] * v1[0] + G[i][1] * v1[1] + G[i][2] * v1[2];
+        u2[i] = G[i][0] * v2[0] + G[i][1] * v2[1] + G[i][2] * v2[2];
+        u3[i] = G[i][0] * v3[0] + G[i][1] * v3[1] + G[i][2] * v3[2];
+    }
+    const double s1 = __builtin_sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+    if (!(s1 > 0.0)) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u1[i] /= s1;
+    const double d = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u2[i] -= d * u1[i];
+    const double s2 = __builtin_sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+    if (!(s2 > 0.0)) return false;                      // rank below 2: no fundamental matrix is nearest
+    sig[0] = s1; sig[1] = s2;
+    sig[2] = __builtin_sqrt(u3[0] * u3[0] + u3[1] * u3[1] + u3[2] * u3[2]);               // |G v_3|: second order in the error of v_3
+    double nn = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            F[3 * i + j] = s1 * (u1[i] * v1[j]) + u2[i] * v2[j];                           // u2 still carries s2
+            nn += F[3 * i + j] * F[3 * i + j];
+        }
+    const double inv = 1.0 / __builtin_sqrt(nn);
+    bool ok = nn > 0.0 && __builtin_isfinite(sig[2]);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { F[k] *= inv; ok = ok && __builtin_isfinite(F[k]); }
+    return ok;
+}
+
+// behind jacobi9_sweeps, on one thread: e = the refit of the moments, ev = their two smallest eigenvalues, F and sig = fund_project
+// of e - what the fundamental refit (fundamental.hip) and the local optimisation's refit of that family (polish.hip) both return
+__device__ __forceinline__ bool fund_from_moments(const double (&sA)[9][9], const double (&sV)[9][9], double (&e)[9], double (&ev)[2],
+                                                  double (&F)[9], double (&sig)[3]) {
+    double lmin;
+    const int m = refit_eigvec(sA, sV, e, lmin);
+    const double lsec = refit_second(sA, m);
+    ev[0] = lmin; ev[1] = lsec;
+    bool ok = __builtin_isfinite(lmin) && __builtin_isfinite(lsec);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ok = ok && __builtin_isfinite(e[k]);
+    return ok && fund_project(e, F, sig);
 }
 
 // k -> P k for the permutation P = [[0,1,0],[1,0,0],[0,0,1]] applied to rows and columns of a row-major 3x3

@@ -49,6 +49,11 @@ struct Epipolar {
     }
 };
 
+// the uncalibrated branch: the Epipolar test and moments, its own refit in the local optimisation (polish.hip)
+struct Fundamental : Epipolar {
+    static constexpr const char* POLISH = "fundamental_polish kernel";
+};
+
 struct Homography {
     static constexpr const char *SCORE = "homography_score kernel", *ROUND = "homography_score kernel (a round)",
                                 *ARGMAX = "homography_argmax kernel", *MASK = "homography_mask kernel", *POLISH = "homography_polish kernel";

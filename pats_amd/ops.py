@@ -1875,6 +1875,52 @@ def epipolar_hypotheses5_by_pair(matches_l, matches_r, H, seed, pair_off=None, s
     return out if len(out) > 1 else out[0]
 
 
+def epipolar_hypotheses7_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
+                                 return_samples=False, return_counts=False, out=None, pairs=None):
+    """H 7-point samples per pair, ON THE DEVICE, one launch, no host read (pats_epipolar_hypotheses7_by_pair_f32;
+    include/pats_amd.h, "Per-pair 7-point hypotheses", holds the definition): for every pair and every h seven distinct matches of
+    the pair are drawn by the hypotheses' counter-based generator and the real fundamental matrices through them - at most three,
+    rank 2 by construction - are written as row-major 3x3 unit models into the sample's lowest slots, exact zeros behind them.  The
+    arguments are those of epipolar_hypotheses_by_pair; 3 * H may not exceed epipolar_max_h().  No calibration is needed: norm is
+    the verification's normalisation, whatever it is.  progressive: sample h draws from the first max(7, ceil(n (h + 1) / H))
+    matches of the pair's list instead of all n.
+    Returns models [pairs,H,3,3,3] float32 - models.view(pairs, 3 * H, 3, 3) is a `models` of epipolar_score_by_pair; all three
+    slots zero for a pair with fewer than 7 matches and a sample with a non-finite coordinate - or a tuple (models[, sample_idx
+    [pairs,H,7] int32 with return_samples=True: the draws as positions inside the pair's list, -1 for a pair with fewer than 7
+    matches][, n_models [pairs,H] int32 with return_counts=True: the non-zero slots]).  out: the destination(s), a tensor or a tuple
+    in that order."""
+    fn = "epipolar_hypotheses7_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("epipolar_hypotheses7_by_pair: seed must be an int64 GPU tensor [pairs]")
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    H = int(H)
+    seed = _dev(seed, "seed", torch.int64).reshape(-1)
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if seed.numel() != pairs:
+        raise RuntimeError("epipolar_hypotheses7_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h() // 3:
+        raise RuntimeError("epipolar_hypotheses7_by_pair: H = %d, must lie in 1 .. %d (3 H models)" % (H, epipolar_max_h() // 3))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = ml.device
+    want = [("models", torch.float32, (pairs, H, 3, 3, 3))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, 7)))
+    if return_counts:
+        want.append(("n_models", torch.int32, (pairs, H)))
+    out = _bp_outputs(fn, want, out, dev, lone=True)
+    nws = _L().pats_epipolar_hypotheses7_workspace_bytes(pairs, H)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+    _check(_L().pats_epipolar_hypotheses7_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
+                                                      1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
+                                                      _ptr(out[-1]) if return_counts else None, _ptr(ws), nws, _stream()), fn)
+    return out if len(out) > 1 else out[0]
+
+
 def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
                           counts=None, norm=None, swapped=False, return_front=False, return_refit=False, out=None, pairs=None):
     """Each pair's relative pose from its verified inliers, ON THE DEVICE, no host read (pats_epipolar_pose_by_pair_f64;
@@ -2015,6 +2061,58 @@ def homography_refit_by_pair(best_count, moments=None, models=None, best=None, n
     _check(_L().pats_homography_refit_by_pair_f64(_ptr(bc), _ptr(moments), _ptr(models), H, _ptr(best), _ptr(norm), pairs,
                                                   1 if swapped else 0, _ptr(out[0]), _ptr(out[2]) if return_pixel else None, _ptr(out[1]),
                                                   _ptr(ws), nws, _stream()), fn)
+    return out
+
+
+def fundamental_refit_by_pair(best_count, moments=None, models=None, best=None, norm=None, swapped=False, return_pixel=False,
+                              return_refit=False, out=None):
+    """Each pair's fundamental matrix from its verified inliers, ON THE DEVICE, one launch, float64, no host read
+    (pats_fundamental_refit_by_pair_f64; include/pats_amd.h, "Per-pair fundamental matrices", holds the definition): the unit
+    eigenvector of `moments` for its smallest eigenvalue - without moments the winning model models[p, best[p]] promoted -
+    truncated to rank 2, F = U diag(s1, s2, 0) V^T, rescaled to Frobenius norm 1.  best_count [pairs] int64 and moments [pairs,9,9]
+    float64 (or best [pairs] int32 with the models [pairs,H,3,3] float32) are epipolar_score_by_pair's outputs; norm [pairs,8] what
+    it was given.  swapped: the points are in the hand-over's (y, x) order; F and F_px come back in the reference's (x, y) frame.
+    Returns (F [pairs,3,3] float64 - the component of largest magnitude positive: F.float() is a model for epipolar_score_by_pair -,
+    eig [pairs,2] float64: the two smallest eigenvalues of the moments, ascending; 0 without moments -, sigma [pairs,3] float64: the
+    singular values of the refit before the truncation, descending), then F_px [pairs,3,3] float64 with return_pixel=True: the
+    fundamental matrix of the stored coordinates, N_r^T F N_l rescaled (F itself without norm), then f_refit [pairs,9] float64 with
+    return_refit=True: the refit before the truncation.  A pair without a model (best_count < 8, a non-finite moment, a refit of
+    rank below 2) has zeros everywhere.  out: the destinations, in that order."""
+    fn = "fundamental_refit_by_pair"
+    _bp_layout(fn, [(best_count, "best_count"), (moments, "moments"), (models, "models"), (best, "best"), (norm, "norm")],
+               {"best_count": torch.int64, "moments": torch.float64, "best": torch.int32})
+    if moments is None and (models is None or best is None):
+        raise RuntimeError("fundamental_refit_by_pair: give moments, or models and best")
+    bc = _dev(best_count, "best_count", torch.int64).reshape(-1)
+    pairs = int(bc.numel())
+    if pairs < 1:
+        raise RuntimeError("fundamental_refit_by_pair: best_count must hold one int64 per pair")
+    H = 1
+    if moments is not None:
+        moments = _dev(moments, "moments", torch.float64)
+        if tuple(moments.shape) != (pairs, 9, 9):
+            raise RuntimeError("fundamental_refit_by_pair: moments must be [pairs,9,9]")
+        models = best = None
+    else:
+        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
+        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
+            raise RuntimeError("fundamental_refit_by_pair: models must be [pairs,H,3,3] and best [pairs]")
+        H = int(models.shape[1])
+        if not 1 <= H <= epipolar_max_h():
+            raise RuntimeError("fundamental_refit_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = bc.device
+    want = [("F", torch.float64, (pairs, 3, 3)), ("eig", torch.float64, (pairs, 2)), ("sigma", torch.float64, (pairs, 3))]
+    if return_pixel:
+        want.append(("F_px", torch.float64, (pairs, 3, 3)))
+    if return_refit:
+        want.append(("f_refit", torch.float64, (pairs, 9)))
+    out = _bp_outputs(fn, want, out, dev)
+    nws = _L().pats_fundamental_refit_workspace_bytes(pairs)
+    ws = _workspace(nws, dev) if nws else None
+    _check(_L().pats_fundamental_refit_by_pair_f64(_ptr(bc), _ptr(moments), _ptr(models), H, _ptr(best), _ptr(norm), pairs,
+                                                   1 if swapped else 0, _ptr(out[0]), _ptr(out[3]) if return_pixel else None, _ptr(out[1]),
+                                                   _ptr(out[2]), _ptr(out[-1]) if return_refit else None, _ptr(ws), nws, _stream()), fn)
     return out
 
 
@@ -2491,7 +2589,7 @@ def scale_head(desc1, height, width, weights, biases, return_heads=False):
 
 def _polish_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride, counts, conf, min_conf,
                     norm, out, pairs):
-    """What the two local optimisations share - everything but the C entry and its workspace query (looked up by the callers, as for
+    """What the three local optimisations share - everything but the C entry and its workspace query (looked up by the callers, as for
     _score_by_pair)."""
     _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (best, "best"),
                     (pair_off, "pair_off"), (counts, "counts"), (conf, "conf"), (norm, "norm")],
@@ -2565,4 +2663,14 @@ def homography_polish_by_pair(matches_l, matches_r, models, thr, best=None, roun
     moments and best_count are what homography_refit_by_pair takes."""
     return _polish_by_pair("homography_polish_by_pair", _L().pats_homography_polish_by_pair_f32,
                            _L().pats_homography_polish_workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride,
+                           counts, conf, min_conf, norm, out, pairs)
+
+
+def fundamental_polish_by_pair(matches_l, matches_r, models, thr, best=None, rounds=4, pair_off=None, stride=None, counts=None, conf=None,
+                               min_conf=None, norm=None, out=None, pairs=None):
+    """epipolar_polish_by_pair for uncalibrated callers (pats_fundamental_polish_by_pair_f32): the same arguments, the same outputs,
+    the same Sampson test, and fundamental_refit_by_pair's F - the refit truncated to rank 2, not projected onto the essential
+    matrices -, cast to float32, as the refit; moments and best_count are what fundamental_refit_by_pair takes."""
+    return _polish_by_pair("fundamental_polish_by_pair", _L().pats_fundamental_polish_by_pair_f32,
+                           _L().pats_fundamental_polish_workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride,
                            counts, conf, min_conf, norm, out, pairs)
