@@ -68,6 +68,12 @@ int pats_set_third_gather(int mode);
  * reset, so launches on any stream are counted and none races with the reset.  No reference counterpart. */
 int pats_sinkhorn_fallbacks(int64_t* count, int reset);
 
+/* Of those, the 145 x 145 problems whose STABILISED linear re-solve (sinkhorn_rc_kernel, linear == 2) failed its final guard as
+ * well and were solved by the log-sum-exp sweeps behind it, in the same launch: problems with non-finite scores, or whose
+ * scalings run away within a single sweep.  The plan is the same either way, so nothing else shows that the stabilised form
+ * stopped working.  Same synchronisation and reset as pats_sinkhorn_fallbacks, a counter of its own.  No reference counterpart. */
+int pats_sinkhorn_tail_solves(int64_t* count, int reset);
+
 /* ---- a1-a3: cost build -------------------------------------------------------------------
  * out[b,i,j] = 0.1f * ( (sum_d d0[b,d,i] * d1[b,d,j]) / sqrtf(D) )
  * replaces  scores = einsum('bdn,bdm->bnm', mdesc0, mdesc1) / D**.5 ; 0.1 * scores

@@ -55,6 +55,7 @@ SIGNATURES = {
     "pats_set_fine_fused": (c_int, [c_int]),
     "pats_set_third_gather": (c_int, [c_int]),
     "pats_sinkhorn_fallbacks": (c_int, [ctypes.POINTER(ctypes.c_int64), c_int]),
+    "pats_sinkhorn_tail_solves": (c_int, [ctypes.POINTER(ctypes.c_int64), c_int]),
     "pats_set_gnn_redo_mode": (c_int, [c_int]),
     "pats_gnn_overflows": (c_int, [ctypes.POINTER(ctypes.c_int64), c_int]),
     "pats_cost_f32": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -12,7 +12,10 @@ namespace pats {
 
 constexpr int WAVE = 64;
 constexpr float LOG2E = 1.4426950408889634f;
+constexpr float LOG2E_LO = 1.925963033500011e-08f;     // log2(e) - (double)LOG2E: what the fp32 constant leaves out, 1.3e-8 of it
 constexpr float LN2 = 0.6931471805599453f;
+constexpr float LN2_HI = 0.693145751953125f;           // ln 2 in two parts, the first with 15 significant bits
+constexpr float LN2_LO = 1.42860682030941723212e-6f;
 constexpr float ZERO_F = 1e-14f;  // the reference's `zero` (utils/utils.py:1201)
 
 // ---- environment switches -----------------------------------------------------------------------------------------------------

@@ -59,7 +59,8 @@ unsigned long long* fallback_counter() {
     std::lock_guard<std::mutex> lock(g_fallbacks_mu);           // first use may race between host threads
     if (!g_fallbacks[dev]) {
         unsigned long long* p = nullptr;
-        if (hipMalloc((void**)&p, sizeof(*p)) != hipSuccess || hipMemset(p, 0, sizeof(*p)) != hipSuccess) {
+        // two words: [0] the problems that left the guard, [1] those of them whose stabilised re-solve failed too (tail_counter)
+        if (hipMalloc((void**)&p, 2 * sizeof(*p)) != hipSuccess || hipMemset(p, 0, 2 * sizeof(*p)) != hipSuccess) {
             (void)hipGetLastError();
             return nullptr;
         }
@@ -176,6 +177,19 @@ extern "C" int pats_sinkhorn_fallbacks(int64_t* count, int reset) {
     if (hipMemcpy(&v, p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return check_launch("sinkhorn_fallbacks");
     if (reset && (hipMemset(p, 0, sizeof(v)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
         return check_launch("sinkhorn_fallbacks");
+    *count = (int64_t)v;
+    return PATS_OK;
+}
+
+extern "C" int pats_sinkhorn_tail_solves(int64_t* count, int reset) {
+    PATS_REQUIRE(count, "sinkhorn_tail_solves: null pointer");
+    unsigned long long* p = fallback_counter();
+    PATS_REQUIRE(p, "sinkhorn_tail_solves: no counter on this device");
+    unsigned long long v = 0;
+    if (hipDeviceSynchronize() != hipSuccess) return check_launch("sinkhorn_tail_solves");       // as pats_sinkhorn_fallbacks
+    if (hipMemcpy(&v, p + 1, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return check_launch("sinkhorn_tail_solves");
+    if (reset && (hipMemset(p + 1, 0, sizeof(v)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+        return check_launch("sinkhorn_tail_solves");
     *count = (int64_t)v;
     return PATS_OK;
 }

@@ -582,6 +582,9 @@ sinkhorn_rc_kernel(const float* Zin, int64_t P, const float* __restrict__ log_mu
 
     if (!solved) {      // workgroup-uniform: max-subtracted log-sum-exp sweeps on Z itself.
         if (linear == 1 && t == 0 && fallbacks) atomicAdd(fallbacks, 1ull);      // (a re-solve pass has counted its problem on entry)
+        // the stabilised re-solve failed its guard too: counted apart (pats_sinkhorn_tail_solves), because the sweeps below hide
+        // it - they return the right plan whatever the re-base did, at several times the cost
+        if (linear == 2 && t == 0 && fallbacks) atomicAdd(fallbacks + 1, 1ull);
         // Rare path (guard tripped, or PATS_SINKHORN_LOG): Z is read from the LDS tile each time
         // rather than held in registers, so it does not raise the kernel's VGPR budget.
         const int zstride = colw ? N_ : 1;
@@ -600,10 +603,18 @@ sinkhorn_rc_kernel(const float* Zin, int64_t P, const float* __restrict__ log_mu
                     if (m == -INFINITY || m == INFINITY) m = 0.f;
                     const float mI = ceilf(m * LOG2E);
                     float sacc = 0.f;
+                    // log2(e) in two parts: x * LOG2E alone is off by 1.3e-8 |x|, and |x| = |Z + dual| reaches hundreds of nats
+                    // in exactly the problems that come here - 1.4e-6 in the exponent at |x| = 73, which put a problem with
+                    // 8-fold scaled columns at 2.25 of its mass gate under bias 3, where the corner carries nine times its
+                    // mass (tests/test_fine_solver_edges_gpu.py in log mode; docs/kernels.md 4.1)
 #pragma unroll 8
-                    for (int q = 0; q < N_; ++q)
-                        sacc += fast_exp2(fmaf(zbase[q * zstride] + other[q], LOG2E, -mI));
-                    dual = lmarg - lse_finish(sacc, mI);
+                    for (int q = 0; q < N_; ++q) {
+                        const float x = zbase[q * zstride] + other[q];
+                        sacc += fast_exp2(fmaf(x, LOG2E_LO, fmaf(x, LOG2E, -mI)));
+                    }
+                    // ... and ln 2 in two parts on the way back (Cody-Waite: mI * LN2_HI is exact up to |mI| = 512): the sum
+                    // log2(s) + mI of lse_finish() rounds the fraction at ulp(mI), 3e-5 at mI = 300
+                    dual = lmarg - fmaf(mI, LN2_HI, fmaf(mI, LN2_LO, fast_log2(sacc) * LN2));
                     if (act) (h == 0 ? lds.bc0 : lds.bc1)[tl] = dual;
                 }
             }

@@ -192,6 +192,14 @@ def sinkhorn_fallbacks(reset=True):
     return int(n.value)
 
 
+def sinkhorn_tail_solves(reset=True):
+    """Of sinkhorn_fallbacks(), the 145 x 145 problems whose stabilised linear re-solve failed its guard as well and ended in the
+    log-sum-exp sweeps of the same launch (pats_sinkhorn_tail_solves; synchronises; a counter of its own)."""
+    n = ctypes.c_int64(0)
+    _check(_L().pats_sinkhorn_tail_solves(ctypes.byref(n), 1 if reset else 0), "sinkhorn_tail_solves")
+    return int(n.value)
+
+
 def set_gnn_redo(mode):
     """'inline' (default) | 'deferred' (include/pats_amd.h pats_set_gnn_redo_mode): in deferred mode the GNN layers queue no gated
     fp32 redo chain; an activation beyond the fp16 range raises a sticky device flag instead and the outputs of that call are not

@@ -370,8 +370,15 @@ def test_third_level(ops, oracle, name):
 
 def test_wide_dynamic_range_trips_guard_and_falls_back(ops, oracle, sinkhorn_mode):
     """Scores spanning +-150 nats: exp(Z - r - c) underflows for most entries and the scaling
-    vectors leave the 2^30 guard, so the linear-domain path must hand the problem to the
-    log-sum-exp sweeps (which ATen's logsumexp-based reference handles natively)."""
+    vectors leave the 2^30 guard, so the plain linear-domain solve must hand the problem on.
+    Which path takes it depends on the size: the 65-wide problems re-solve themselves with the
+    log-sum-exp sweeps inside sinkhorn65_kernel; the 145-wide ones are flagged by the block kernel
+    and re-solved by sinkhorn_rc_kernel's STABILISED LINEAR sweeps (linear == 2: several
+    re-bases each at this spread; none of them reaches the log-sum-exp sweeps behind it - those
+    take a 145-wide problem only when its scores are not finite or its scalings run away within
+    one sweep).  In the forced log domain every problem is solved by log-sum-exp sweeps (which
+    ATen's logsumexp-based reference handles natively).  tests/test_fine_solver_edges_gpu.py
+    holds the 145-wide paths to float64 and counts which one was taken."""
     rng = np.random.default_rng(21)
     for n, P in ((65, 6), (145, 3)):
         Z = (60.0 * rng.standard_normal((P, n, n))).astype(np.float32)
