@@ -972,6 +972,67 @@ int pats_epipolar_pose_by_pair_f64(const float* matches_l, const float* matches_
                                    pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pair triangulation (ABI 8, symbols added): from a pair's pose and a mask over its matches to 3-D points - for every masked
+ * match the midpoint of the common perpendicular of its two rays, the two depths, the squared reprojection error and the cosine of
+ * the triangulation angle, and per pair the number of valid points and the sum of their errors.  What two-view initialisation,
+ * keyframe selection, depth seeding and a filter by reprojection error or parallax start from, on the device, no host read.
+ * What it is not: the optimal (Hartley-Sturm) correction - this is the midpoint; no bundle adjustment; the scale is the baseline's
+ * (|t| = 1); calibrated coordinates only (the uncalibrated branch, pats_fundamental_refit_by_pair_f64, has no triangulation); and
+ * nothing in pipeline.forward_* or the drop-in calls it.
+ * Inputs
+ *   matches_l, matches_r [cap,2] float32, the segment of pair p - ragged (pair_off) or strided (stride, counts_in), exactly ONE of
+ *              the two forms - and norm [pairs,8] float32 (optional): as for pats_epipolar_score_by_pair_f32, with the same clamping
+ *   mask [cap] uint8          aligned with the lists: the pose's front, or the verification's inlier
+ *   R [pairs,3,3], t [pairs,3] float64, as pats_epipolar_pose_by_pair_f64 wrote them (with the same swapped)
+ *   swapped    0 or 1: what pats_epipolar_pose_by_pair_f64 was given
+ *   max_reproj [pairs] float32 (optional), max_cos [pairs] float32 (optional): the limits below
+ * Definition, per match i of pair p
+ *   x          the verification's point, formed exactly as there (float32: one subtract, one multiply; (p0, p1, 1) without norm);
+ *              then promoted to float64
+ *   used       mask[i] != 0 and the four coordinates of x finite
+ *   R_p, t_p   swapped ? (P R P, P t) : (R, t),  P = [[0,1,0],[1,0,0],[0,0,1]] - the pose in the frame of the points; float64, NOT
+ *              rounded to float32.  A pair with a non-finite entry in R or t, or t = 0 (the pose's "no pose"), has no valid match
+ *   a = R_p x_l,  b = x_r = (r0, r1, 1),  c = a x b,  cc = c.c
+ *   lambda = c.(b x t_p) / cc,   mu = c.(a x t_p) / cc     the depths in the left / right camera (x has third component 1)
+ *   X_r = (lambda a + t_p + mu b) / 2                      the midpoint of the common perpendicular, right camera frame
+ *   X   = R_p^T (X_r - t_p)                                the same point in the LEFT camera frame: the output frame
+ *   e2  = |pi(X) - x_l|^2 + |pi(R_p X + t_p) - x_r|^2,  pi(v) = (v0 / v2, v1 / v2)    squared reprojection error, the points' units
+ *   cosp = a.b / (|a| |b|)                                 cosine of the triangulation angle
+ *   valid      used and cc > 0 and lambda > 0 and mu > 0 and X[2] > 0 and (R_p X + t_p)[2] > 0 and every value above finite -
+ *              X, lambda, mu, e2 and cosp of magnitude at most FLT_MAX, so that their float32 roundings are finite too -
+ *              and (max_reproj null or e2 <= (double)max_reproj[p]^2) and (max_cos null or cosp <= (double)max_cos[p])
+ *              (a NaN limit makes every comparison false: nothing valid)
+ * All arithmetic after the point is formed is float64, no contraction, in this order (sums left to right, brackets first):
+ *   a_i = (R_p[i,0] l0 + R_p[i,1] l1) + R_p[i,2];  the cross products by components, u x v = (u1 v2 - u2 v1, u2 v0 - u0 v2,
+ *   u0 v1 - u1 v0) with b2 = 1 not multiplied;  every dot product (u0 v0 + u1 v1) + u2 v2;  X_r - t_p by components as
+ *   ((lambda a_i + t_i) + mu b_i) * 0.5 - t_i;  X_j = (R_p[0,j] q0 + R_p[1,j] q1) + R_p[2,j] q2;  (R_p X + t_p)_i =
+ *   ((R_p[i,0] X0 + R_p[i,1] X1) + R_p[i,2] X2) + t_i;  e2 = (d0^2 + d1^2) + (d2^2 + d3^2), left differences first;
+ *   cosp = a.b / (sqrt(a.a) sqrt(b.b)).  A float64 restatement that orders them differently agrees far below a float32 step.
+ * Outputs - every call defines every byte of every output; a row that is not valid (not used, in no segment, the slack of a strided
+ * row, behind a camera, over a limit, degenerate) holds exact zeros in every per-match output.  Never a NaN or an infinity
+ *   points [cap,3] float32          X rounded once; with swapped = 1 in the reference's frame (P X: the first two components exchanged)
+ *   depths [cap,2] float32 (optional)   (lambda, mu)
+ *   reproj [cap] float32 (optional)     e2
+ *   cos_parallax [cap] float32 (optional)   cosp
+ *   valid [cap] uint8               1 where the match is valid, else 0
+ *   tri_count [pairs] int64         the valid matches of the pair: valid's sum over the segment, exactly
+ *   reproj_sum [pairs] float64      the sum of e2 (float64, before the rounding) over the pair's valid matches, added in an order the
+ *                                   sizes alone fix: two calls give the same bits
+ * cap == 0 is a valid call that defines every per-pair output (the match pointers, mask, points and valid must still be non-null).
+ * Refused before any launch (pats_last_error names the argument): a null matches_l / matches_r / mask / R / t / points / valid /
+ * tri_count / reproj_sum; matches_l / matches_r off 8 bytes (read as float2), R / t / tri_count / reproj_sum / pair_off / counts_in
+ * off 8, norm / max_reproj / max_cos / points / depths / reproj / cos_parallax off 4; both segment forms or neither; pairs < 1;
+ * cap < 0 or cap >= 2^31 - 1; in the strided form stride < 1 or pairs * stride > cap; swapped not 0 or 1; a workspace smaller than
+ * pats_epipolar_triangulate_workspace_bytes (0 today: everything lives in LDS and registers; workspace may then be null). */
+size_t pats_epipolar_triangulate_workspace_bytes(int64_t pairs, int64_t cap);
+int pats_epipolar_triangulate_by_pair_f64(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                          const int64_t* counts_in, int64_t pairs, int64_t cap, const uint8_t* mask, const float* norm,
+                                          const double* R, const double* t, int swapped, const float* max_reproj, const float* max_cos,
+                                          float* points, float* depths, float* reproj, float* cos_parallax, uint8_t* valid,
+                                          int64_t* tri_count, double* reproj_sum, void* workspace, size_t workspace_bytes,
+                                          pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pair homographies (ABI 8, symbols added): the planar sibling of the three epipolar stages above - 4-point hypotheses, their
  * verification and the least-squares refit of the winner - for pairs whose geometry no epipolar model describes (a wall, a floor or a
  * facade filling both images; a camera that mostly rotates) and for callers without intrinsics who want to align two views.  All on

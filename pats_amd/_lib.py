@@ -255,6 +255,11 @@ SIGNATURES = {
     "pats_epipolar_pose_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
                                                c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair triangulation of the posed matches (csrc/triangulate.hip)
+    "pats_epipolar_triangulate_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_epipolar_triangulate_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     # per-pair homographies: 4-point hypotheses (csrc/hypotheses.hip), verification (csrc/epipolar.hip), refit (csrc/homography.hip)
     "pats_homography_hypotheses_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pats_homography_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,

@@ -642,6 +642,65 @@ def split_pose_by_pair(out, cap):
     return [(R[i], t[i], E[i], front_count[i]) for i in range(cap.pairs)]
 
 
+def triangulate_by_pair(out, cap, norm=None, swapped=False, max_reproj=None, max_cos=None, mask="front", depths=False, reproj=False,
+                        cos=False):
+    """Device side, after pose_by_pair: each pair's masked matches triangulated under its pose (ops.epipolar_triangulate_by_pair:
+    no host read) - the midpoint of the two rays' common perpendicular in the LEFT camera's frame, over the lists that verification
+    scored ("all" or "topk").  mask="front": the matches the pose's cheirality vote kept (needs pose_by_pair(..., front=True));
+    mask="inlier": the verification's inliers.  norm [pairs,8] or None, max_reproj / max_cos [pairs] float32 or None, all in the
+    CALLER's order - pass the norm that verify_by_pair and pose_by_pair were given, and the swapped that pose_by_pair was given: the
+    pose is in the reference's frame only because of it, and the points come back in that frame the same way.  A match is valid only
+    with a squared reprojection error <= max_reproj^2 and a cosine of its triangulation angle <= max_cos.
+    Returns (points float32 [n,3], valid uint8 [n], tri_count [pairs] int64, reproj_sum [pairs] float64) - followed by depths
+    [n,2], reproj [n], cos_parallax [n] (float32) for depths / reproj / cos = True - and stores them as `points`.  tri_count and
+    reproj_sum are in the CALLER's order; the per-match outputs are aligned with the scored lists like `verified`'s inlier mask and the
+    pose's front (slot order; split_points_by_pair hands the pairs back in the caller's).  `verified`, `pose`, the lists and a top-K
+    of the same step are not touched."""
+    if "pose" not in out:
+        raise ValueError("triangulate_by_pair: run pose_by_pair first")
+    if mask not in ("front", "inlier"):
+        raise ValueError("triangulate_by_pair: mask must be \"front\" or \"inlier\", got %r" % (mask,))
+    pose, on = out["pose"], out["verified_on"]
+    if mask == "front" and len(pose) < 7:
+        raise ValueError("triangulate_by_pair: mask=\"front\" needs pose_by_pair(..., front=True)")
+    used = pose[6] if mask == "front" else out["verified"][3]
+    R, t = pose[1], pose[2]
+    mixed = "caller_of" in out
+    if mixed:                                                             # the pose is in the caller's order: back to slots
+        idx = _caller_of_dev(out, used.device)
+        R, t = R.index_select(0, idx), t.index_select(0, idx)
+        norm, max_reproj, max_cos = (None if v is None else v.index_select(0, idx) for v in (norm, max_reproj, max_cos))
+    ml, mr, _, seg = _lists_on(out, cap, on)
+    res = ops.epipolar_triangulate_by_pair(ml, mr, used, R, t, norm=norm, swapped=swapped, max_reproj=max_reproj, max_cos=max_cos,
+                                           return_depths=depths, return_reproj=reproj, return_cos=cos, **seg)
+    if mixed:                                                             # slots back to the caller's order
+        back = _slot_of_dev(out, cap, used.device)
+        res = res[:2] + tuple(v.index_select(0, back) for v in res[2:4]) + tuple(res[4:])
+    out["points"] = res
+    return res
+
+
+def split_points_by_pair(out, cap):
+    """Host side, AFTER the step: per-pair (X [c,3], valid [c] bool, tri_count, reproj_sum) of a triangulate_by_pair result - the
+    points of the lists that were scored (the pair's full list for on="all", its top_count top-K rows for on="topk"), views of the
+    device tensors; tri_count / reproj_sum are 0-d device views (their values are not read here).  In the caller's order.  Raises on
+    the capacity overflows split_verified_by_pair raises on, after the device-to-host copies that function makes and no further one."""
+    if "points" not in out:
+        raise ValueError("split_points_by_pair: run triangulate_by_pair first")
+    if out["verified_on"] == "topk":                  # (lo, hi) per slot in the flat numbering of the scored lists
+        K = int(out["topk"][0].shape[1])
+        o, counts = _read_topk_summary(out, cap)
+        _overflow_check(o, cap)
+        ext = [(p * K, p * K + counts[p]) for p in range(cap.pairs)]
+    else:
+        o = out["summary"].cpu().tolist()             # the one synchronisation of a batch
+        _overflow_check(o, cap)
+        ext = [(o[p], o[p + 1]) for p in range(cap.pairs)]
+    X, valid, tri_count, reproj_sum = out["points"][:4]
+    per_slot = [(X[lo:hi], valid[lo:hi].bool()) for lo, hi in ext]
+    return [xv + (tri_count[i], reproj_sum[i]) for i, xv in enumerate(_caller_order(out, cap, per_slot))]
+
+
 def hypothesize_h_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
     """Device side, after the matching: H 4-point HOMOGRAPHY hypotheses per pair (ops.homography_hypotheses_by_pair: one launch, no
     host read) - the `models` of verify_h_by_pair, for pairs that look at a plane or whose camera mostly rotates.  on, progressive

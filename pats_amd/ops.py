@@ -1995,6 +1995,66 @@ def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None
     return out
 
 
+def epipolar_triangulate_by_pair(matches_l, matches_r, mask, R, t, pair_off=None, stride=None, counts=None, norm=None, swapped=False,
+                                 max_reproj=None, max_cos=None, return_depths=False, return_reproj=False, return_cos=False, out=None,
+                                 pairs=None):
+    """Each pair's masked matches triangulated under its pose, ON THE DEVICE, no host read (pats_epipolar_triangulate_by_pair_f64;
+    include/pats_amd.h holds the definition): the midpoint of the common perpendicular of a match's two rays in the LEFT camera's
+    frame, the two depths, the squared reprojection error and the cosine of the triangulation angle, float64 throughout.
+    matches_l / matches_r [cap,2] float32 (also [pairs,K,2]), the segments (pair_off, or stride + counts) and norm exactly as
+    epipolar_pose_by_pair took them; mask [cap] uint8 - its front, or the verification's inlier; R [pairs,3,3], t [pairs,3]
+    float64 its outputs, with the `swapped` it was given.  max_reproj / max_cos [pairs] float32: a match is valid only with
+    e2 <= max_reproj^2 and cos <= max_cos (a NaN limit: no valid match in that pair).
+    Returns (points [cap,3] float32, valid [cap] uint8, tri_count [pairs] int64, reproj_sum [pairs] float64), then depths [cap,2]
+    with return_depths=True, reproj [cap] with return_reproj=True, cos_parallax [cap] with return_cos=True (float32).  A row that is
+    not valid holds zeros everywhere; a pair without a pose (t = 0) or with a non-finite one has no valid match.
+    out: the destinations, in that order."""
+    fn = "epipolar_triangulate_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (mask, "mask"), (R, "R"), (t, "t"), (pair_off, "pair_off"),
+                    (counts, "counts"), (norm, "norm"), (max_reproj, "max_reproj"), (max_cos, "max_cos")],
+               {"mask": torch.uint8, "R": torch.float64, "t": torch.float64, "pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    msk = _dev(mask, "mask", torch.uint8).reshape(-1)
+    if msk.numel() != cap:
+        raise RuntimeError("epipolar_triangulate_by_pair: mask must be [cap]")
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    R, t = _dev(R, "R", torch.float64), _dev(t, "t", torch.float64)
+    if tuple(R.shape) != (pairs, 3, 3) or tuple(t.shape) != (pairs, 3):
+        raise RuntimeError("epipolar_triangulate_by_pair: R must be [pairs,3,3] and t [pairs,3]")
+    norm = _bp_norm(fn, norm, pairs)
+    lims = []
+    for lim, name in ((max_reproj, "max_reproj"), (max_cos, "max_cos")):
+        if lim is not None:
+            lim = _dev(lim, name).reshape(-1)
+            if lim.numel() != pairs:
+                raise RuntimeError("epipolar_triangulate_by_pair: %s must hold one float32 per pair (%d), got %d" % (name, pairs, lim.numel()))
+        lims.append(lim)
+    dev = ml.device
+    want = [("points", torch.float32, (cap, 3)), ("valid", torch.uint8, (cap,)), ("tri_count", torch.int64, (pairs,)),
+            ("reproj_sum", torch.float64, (pairs,))]
+    more = {}
+    for flag, name, shape in ((return_depths, "depths", (cap, 2)), (return_reproj, "reproj", (cap,)), (return_cos, "cos_parallax", (cap,))):
+        if flag:
+            more[name] = len(want)
+            want.append((name, torch.float32, shape))
+    out = _bp_outputs(fn, want, out, dev)
+    nws = _L().pats_epipolar_triangulate_workspace_bytes(pairs, cap)
+    ws = _workspace(nws, dev) if nws else None
+    points, valid = out[0], out[1]
+    per_match = {name: out[k] for name, k in more.items()}
+    if cap == 0:
+        ml = mr = points = _bp_placeholder(dev)
+        msk = valid = _bp_placeholder(dev, torch.uint8)
+        per_match = {}
+    _check(_L().pats_epipolar_triangulate_by_pair_f64(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, _ptr(msk), _ptr(norm), _ptr(R),
+                                                      _ptr(t), 1 if swapped else 0, _ptr(lims[0]), _ptr(lims[1]), _ptr(points),
+                                                      _ptr(per_match.get("depths")), _ptr(per_match.get("reproj")),
+                                                      _ptr(per_match.get("cos_parallax")), _ptr(valid), _ptr(out[2]), _ptr(out[3]), _ptr(ws),
+                                                      nws, _stream()), fn)
+    return out
+
+
 def homography_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
                                   return_samples=False, out=None, pairs=None):
     """H 4-point homography hypotheses per pair, ON THE DEVICE, one launch, no host read (pats_homography_hypotheses_by_pair_f32;
