@@ -1033,6 +1033,73 @@ int pats_epipolar_triangulate_by_pair_f64(const float* matches_l, const float* m
                                           pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pair pose error and AUC (ABI 8, symbols added): what the reference's evaluation does with a pose - the rotation error and the
+ * translation error of every pair against the ground truth (utils/metrics.py:56-66: angle_error_mat, angle_error_vec and the fold of
+ * the translation angle at 90 degrees), and the AUC of the recall curve over a data set's worth of them (metrics.py:70-96: error_auc
+ * under aggregate_metrics) - on the device, no host read.  What it is not: an estimator (the pose comes from
+ * pats_epipolar_pose_by_pair_f64); a match-precision metric (the verification with the ground truth's essential matrix as the one
+ * model gives that); and nothing in pipeline.forward_*, the drop-in or bench.py calls it.
+ *
+ * pats_pose_error_by_pair_f64 - one launch for the batch, float64 throughout
+ * Inputs
+ *   R [pairs,3,3], t [pairs,3] float64   the estimate, as pats_epipolar_pose_by_pair_f64 wrote it.  Estimate and ground truth must be
+ *              in the SAME frame - there is no swapped here: with the data set's extrinsics as the ground truth the pose stage is
+ *              called with swapped = 1 (the reference's (x, y) frame)
+ *   T1 [pairs,4,4] float64, row-major    only the upper 3 x 4 is read: (R1 | t1)
+ *   T0 [pairs,4,4] float64 (optional)    only the upper 3 x 4 is read: (R0 | t0)
+ *   counts [pairs] int64 (optional)      the pair's number of matches (the reference's kp1.shape[0])
+ *   min_matches  the reference's 15;  min_gt_t >= 0, 0 for the reference's behaviour wherever that is defined
+ * Definition, per pair p (float64, no contraction, sums left to right, brackets first)
+ *   ground truth   without T0: R_gt = R1, t_gt = t1.  With T0 the rigid form of the reference's T1 inv(T0):
+ *              R_gt[i][j] = (R1[i][0] R0[j][0] + R1[i][1] R0[j][1]) + R1[i][2] R0[j][2]                    (R1 R0^T)
+ *              t_gt[i] = t1[i] - ((R_gt[i][0] t0[0] + R_gt[i][1] t0[1]) + R_gt[i][2] t0[2])
+ *              The reference inverts T0 by a general LU factorisation: for a rigid T0 the two differ by rounding only
+ *   err_R      s = R[0][0] R_gt[0][0], then s = s + R[i][j] R_gt[i][j] for the other eight entries in row-major order;
+ *              c = (s - 1) / 2, clipped to [-1, 1];  err_R = acos(c) * 57.29577951308232 (180 / pi)       angle_error_mat
+ *   err_t      d = (t[0] t_gt[0] + t[1] t_gt[1]) + t[2] t_gt[2];  |v| = sqrt((v[0]^2 + v[1]^2) + v[2]^2);  c = d / (|t| |t_gt|),
+ *              clipped;  e = acos(c) * 57.29577951308232;  err_t = min(e, 180 - e)      angle_error_vec and the fold of metrics.py:63
+ *              If |t_gt| <= min_gt_t the direction of t_gt carries no information and err_t = 0 - a stated departure: for t_gt = 0
+ *              the reference produces a NaN
+ *   err        max(err_R, err_t): what aggregate_metrics feeds the AUC
+ *   status     the lowest number that applies:
+ *              0 evaluated;  1 counts given and counts[p] < min_matches;  2 no pose: an entry of R or t that is not finite, or
+ *              t = 0 (pats_epipolar_pose_by_pair_f64's "no pose");  3 an entry that is not finite in the ground truth that was read
+ *              (the upper 3 x 4 of T1, and of T0 if given)
+ *   For status != 0 all three errors are +inf: the reference's value for a pair it cannot score.  A NaN that arises in the
+ *   arithmetic of an evaluated pair (an overflow of finite inputs) is written as +inf as well.  Unlike every other stage of this
+ *   library +inf is therefore a legitimate VALUE of these outputs; a NaN never is.
+ * Outputs - every call defines every byte
+ *   err_R, err_t, err [pairs] float64 (degrees), status [pairs] int32
+ * Refused before the launch (pats_last_error names the argument): a null R / t / T1 / err_R / err_t / err / status; R / t / T1 / T0 /
+ * counts / err_R / err_t / err off 8 bytes, status off 4; pairs < 1; min_matches < 0; min_gt_t negative or a NaN.
+ *
+ * pats_pose_auc_f64 - one workgroup, one launch
+ * Inputs
+ *   errors [n] float64 on the device, 0 <= n <= pats_pose_auc_max_n() (16384: the keys live in LDS); a NaN counts as +inf and
+ *              -0.0 as +0.0 (the stage above never writes either)
+ *   thresholds   n_thr HOST doubles, 1 <= n_thr <= 8, each finite and > 0 (the reference's are 5, 10, 20)
+ * Definition, per threshold thr
+ *   e_(1) <= ... <= e_(n)   the errors sorted ascending (as order-preserving 64-bit keys, bitonic; equal keys are equal values)
+ *   k = the number of errors STRICTLY below thr (searchsorted's left side: an error equal to the threshold is out)
+ *   x_0 = 0, x_i = e_(i);  y_i = i * (1 / n)
+ *   area = sum over i < k of ((x_{i+1} - x_i) * (y_i + y_{i+1})) * 0.5, plus (thr - x_k) * y_k;  auc = area / thr
+ *   This is error_auc's np.trapz over [0] + sorted(errors) with the recall np.linspace(0, 1, n + 1), cut at thr (the reference
+ *   ignores its thresholds argument and always uses 5, 10, 20; this function uses what it is given).  n = 0: auc = 0, below = 0.
+ *   The sum runs in an order n alone fixes - thread j of 1024 adds the terms j, j + 1024, ... in that order, lane l of a wave then
+ *   takes lane l + 32, + 16, ... + 1, the sixteen waves are added in index order, then the last term - so two calls give the same bits.
+ * Outputs
+ *   auc [n_thr] float64, below [n_thr] int64 (k), sorted [n] float64 (optional): the sorted list, NaN replaced by +inf and
+ *   -0.0 by +0.0
+ * Refused before the launch: a null errors / thresholds / auc / below (errors also for n = 0); errors / auc / below / sorted off 8
+ * bytes; n < 0 or n > pats_pose_auc_max_n(); n_thr < 1 or > 8; a threshold that is not finite and positive. */
+int pats_pose_error_by_pair_f64(const double* R, const double* t, const double* T1, const double* T0, const int64_t* counts,
+                                int64_t pairs, int64_t min_matches, double min_gt_t, double* err_R, double* err_t, double* err,
+                                int32_t* status, pats_stream_t stream);
+int64_t pats_pose_auc_max_n(void);
+int pats_pose_auc_f64(const double* errors, int64_t n, const double* thresholds, int64_t n_thr, double* auc, int64_t* below,
+                      double* sorted, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pair homographies (ABI 8, symbols added): the planar sibling of the three epipolar stages above - 4-point hypotheses, their
  * verification and the least-squares refit of the winner - for pairs whose geometry no epipolar model describes (a wall, a floor or a
  * facade filling both images; a camera that mostly rotates) and for callers without intrinsics who want to align two views.  All on

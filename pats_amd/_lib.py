@@ -260,6 +260,11 @@ SIGNATURES = {
     "pats_epipolar_triangulate_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
                                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair pose error against the ground truth and the AUC over accumulated errors (csrc/pose_error.hip)
+    "pats_pose_error_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, ctypes.c_double, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pats_pose_auc_max_n": (c_i64, []),
+    "pats_pose_auc_f64": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
     # per-pair homographies: 4-point hypotheses (csrc/hypotheses.hip), verification (csrc/epipolar.hip), refit (csrc/homography.hip)
     "pats_homography_hypotheses_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pats_homography_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,

@@ -701,6 +701,41 @@ def split_points_by_pair(out, cap):
     return [xv + (tri_count[i], reproj_sum[i]) for i, xv in enumerate(_caller_order(out, cap, per_slot))]
 
 
+def pose_error_by_pair(out, cap, T1, T0=None, min_matches=15, min_gt_t=0.0, into=None):
+    """Device side, after pose_by_pair: each pair's rotation and translation error against the ground truth
+    (ops.pose_error_by_pair: one launch, no host read) - the reference's compute_pose_error behind its estimator.  T1 [pairs,4,4]
+    float64 holds the ground truth (R_gt | t_gt), or with T0 the two extrinsics (ground truth T1 inv(T0)); both in the CALLER's
+    order, like the pose.  The pose must be in the ground truth's frame: for a data set's extrinsics that is
+    pose_by_pair(..., swapped=True).  A pair whose FULL regrouped match list (the reference's kp1.shape[0], not a top-K count) is
+    shorter than min_matches is not scored: the lengths are the differences of `summary`, taken on the device (the lists are
+    regrouped here if they are not yet).
+    Returns (err_R, err_t, err [pairs] float64 in degrees, status [pairs] int32) in the CALLER's order and stores them as
+    `pose_error`.  into=(buffer, offset): err is written into buffer[offset:offset + pairs] (float64, on the device) and is that
+    view - a data set accumulates over its steps and ops.pose_auc(buffer[:total]) is the one aggregate.  `verified`, `pose`,
+    `points`, the lists and a top-K of the same step are not touched."""
+    if "pose" not in out:
+        raise ValueError("pose_error_by_pair: run pose_by_pair first")
+    R, t = out["pose"][1], out["pose"][2]
+    if "summary" not in out:
+        group_by_pair(out, cap)
+    off = out["summary"][:cap.pairs + 1]
+    counts = off[1:] - off[:-1]                                           # slot order
+    if "caller_of" in out:
+        counts = counts.index_select(0, _slot_of_dev(out, cap, counts.device))
+    dest = None
+    if into is not None:
+        buf, at = into[0], int(into[1])
+        if (not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dim() != 1 or not buf.is_contiguous() or buf.dtype != torch.float64
+                or at < 0 or at + cap.pairs > buf.numel()):
+            raise ValueError("pose_error_by_pair: into must be (contiguous float64 vector on the device, offset) with offset + pairs <= its length")
+        f64 = dict(dtype=torch.float64, device=R.device)
+        dest = (torch.empty(cap.pairs, **f64), torch.empty(cap.pairs, **f64), buf[at:at + cap.pairs],
+                torch.empty(cap.pairs, dtype=torch.int32, device=R.device))
+    res = ops.pose_error_by_pair(R, t, T1, T0=T0, counts=counts, min_matches=min_matches, min_gt_t=min_gt_t, out=dest)
+    out["pose_error"] = res
+    return res
+
+
 def hypothesize_h_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=None, samples=False):
     """Device side, after the matching: H 4-point HOMOGRAPHY hypotheses per pair (ops.homography_hypotheses_by_pair: one launch, no
     host read) - the `models` of verify_h_by_pair, for pairs that look at a plane or whose camera mostly rotates.  on, progressive

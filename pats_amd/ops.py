@@ -2055,6 +2055,79 @@ def epipolar_triangulate_by_pair(matches_l, matches_r, mask, R, t, pair_off=None
     return out
 
 
+def pose_error_by_pair(R, t, T1, T0=None, counts=None, min_matches=15, min_gt_t=0.0, out=None):
+    """Each pair's rotation and translation error against the ground truth, ON THE DEVICE, one launch, no host read
+    (pats_pose_error_by_pair_f64; include/pats_amd.h holds the definition): the reference's angle_error_mat, angle_error_vec with the
+    fold at 90 degrees and their maximum, in degrees, float64.  R [pairs,3,3], t [pairs,3] float64 as epipolar_pose_by_pair returns
+    them; T1 [pairs,4,4] float64 the ground truth (R_gt | t_gt) in its upper 3 x 4 - or, with T0 [pairs,4,4] given, the two
+    extrinsics, and the ground truth is the rigid T1 inv(T0).  Estimate and ground truth must be in the SAME frame: with a data
+    set's extrinsics call epipolar_pose_by_pair(..., swapped=True).  counts [pairs] int64: a pair with fewer than min_matches matches
+    is not scored.  min_gt_t: a ground-truth translation of at most this length has no direction, err_t = 0.
+    Returns (err_R, err_t, err [pairs] float64, status [pairs] int32): status 0 evaluated, 1 too few matches, 2 no pose (t = 0 or a
+    non-finite entry), 3 a non-finite ground truth - the lowest that applies; for status != 0 the errors are +inf, the reference's
+    value for a pair it cannot score.  No output ever holds a NaN.  out: the four destinations - views are fine, so `err` can be a
+    slice of a running buffer that pose_auc aggregates."""
+    fn = "pose_error_by_pair"
+    f64 = torch.float64
+    _bp_layout(fn, [(R, "R"), (t, "t"), (T1, "T1"), (T0, "T0"), (counts, "counts")], {"R": f64, "t": f64, "T1": f64, "T0": f64, "counts": torch.int64})
+    R, t, T1 = _dev(R, "R", f64), _dev(t, "t", f64), _dev(T1, "T1", f64)
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] < 1:
+        raise RuntimeError("pose_error_by_pair: R must be [pairs,3,3] with pairs >= 1")
+    pairs = int(R.shape[0])
+    if tuple(t.shape) != (pairs, 3):
+        raise RuntimeError("pose_error_by_pair: t must be [pairs,3]")
+    if tuple(T1.shape) != (pairs, 4, 4):
+        raise RuntimeError("pose_error_by_pair: T1 must be [pairs,4,4]")
+    if T0 is not None:
+        T0 = _dev(T0, "T0", f64)
+        if tuple(T0.shape) != (pairs, 4, 4):
+            raise RuntimeError("pose_error_by_pair: T0 must be [pairs,4,4]")
+    if counts is not None:
+        counts = _dev(counts, "counts", torch.int64)
+        if tuple(counts.shape) != (pairs,):
+            raise RuntimeError("pose_error_by_pair: counts must hold one int64 per pair (%d)" % pairs)
+    want = [("err_R", f64, (pairs,)), ("err_t", f64, (pairs,)), ("err", f64, (pairs,)), ("status", torch.int32, (pairs,))]
+    out = _bp_outputs(fn, want, out, R.device)
+    _check(_L().pats_pose_error_by_pair_f64(_ptr(R), _ptr(t), _ptr(T1), _ptr(T0), _ptr(counts), pairs, int(min_matches), float(min_gt_t),
+                                            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _stream()), fn)
+    return out
+
+
+def pose_auc_max_n():
+    """The longest error list pose_auc takes (pats_pose_auc_max_n)."""
+    return int(_L().pats_pose_auc_max_n())
+
+
+def pose_auc(errors, thresholds=(5.0, 10.0, 20.0), return_sorted=False, out=None):
+    """The AUC of the recall curve over a list of pose errors at each threshold, ON THE DEVICE, one launch, no host read
+    (pats_pose_auc_f64; include/pats_amd.h holds the definition): the reference's error_auc - sorted errors behind a leading 0,
+    recall i / n, the trapezoids up to the threshold, divided by it.  errors [n] float64, 0 <= n <= pose_auc_max_n() - the `err` of
+    pose_error_by_pair accumulated over a data set; +inf (a pair that was not scored) never counts, a NaN is taken as +inf, -0.0 as +0.0.
+    thresholds: 1 .. 8 finite positive numbers (host values).
+    Returns (auc [n_thr] float64, below [n_thr] int64: the errors strictly below each threshold), followed by sorted [n] float64 -
+    the sorted list - with return_sorted=True.  out: the destinations, in that order."""
+    fn = "pose_auc"
+    _bp_layout(fn, [(errors, "errors")], {"errors": torch.float64})
+    errors = _dev(errors, "errors", torch.float64)
+    if errors.dim() != 1:
+        raise RuntimeError("pose_auc: errors must be a float64 vector")
+    n = int(errors.numel())
+    thr = [float(v) for v in thresholds]
+    n_thr = len(thr)
+    want = [("auc", torch.float64, (n_thr,)), ("below", torch.int64, (n_thr,))]
+    if return_sorted:
+        want.append(("sorted", torch.float64, (n,)))
+    if n_thr < 1:
+        raise RuntimeError("pose_auc: thresholds must hold 1 .. 8 numbers")
+    out = _bp_outputs(fn, want, out, errors.device)
+    srt = out[2] if return_sorted and n > 0 else None
+    if n == 0:
+        errors = _bp_placeholder(errors.device, torch.float64)
+    _check(_L().pats_pose_auc_f64(_ptr(errors), n, (ctypes.c_double * n_thr)(*thr), n_thr, _ptr(out[0]), _ptr(out[1]), _ptr(srt),
+                                  _stream()), fn)
+    return out
+
+
 def homography_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
                                   return_samples=False, out=None, pairs=None):
     """H 4-point homography hypotheses per pair, ON THE DEVICE, one launch, no host read (pats_homography_hypotheses_by_pair_f32;
