@@ -1105,9 +1105,9 @@ int pats_pose_auc_f64(const double* errors, int64_t n, const double* thresholds,
  * facade filling both images; a camera that mostly rotates) and for callers without intrinsics who want to align two views.  All on
  * the device, no host read.  A caller runs both branches on the same lists and compares the two best_count; the choice is the
  * caller's.
- * What it is not: no symmetric or backward transfer error (the test is the forward one), no orientation test on a2, no decision
- * between E and H, no decomposition of H into (R, t, n), no adaptive termination, and nothing in pipeline.forward_* or the drop-in
- * calls it.
+ * What it is not: no symmetric or backward transfer error (the test is the forward one), no orientation test on a2, no adaptive
+ * termination, and nothing in pipeline.forward_* or the drop-in calls it.  The decomposition of H into (R, t, n) and the decision
+ * between E and H are "Per-pair pose from a homography and the E-or-H decision" below.
  * Shared by the three entry points, per pair p with the n rows of its segment from lo on:
  *   segment     ragged (pair_off) or strided (stride, counts_in), exactly ONE of the two forms, with the clamping of
  *               pats_epipolar_score_by_pair_f32;  norm [pairs,8] float32 (optional) as there
@@ -1193,6 +1193,99 @@ size_t pats_homography_refit_workspace_bytes(int64_t pairs);
 int pats_homography_refit_by_pair_f64(const int64_t* best_count, const double* moments, const float* models, int64_t H,
                                       const int32_t* best, const float* norm, int64_t pairs, int swapped, double* H_out, double* H_px,
                                       double* eig, void* workspace, size_t workspace_bytes, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair pose from a homography and the E-or-H decision (ABI 8, symbols added): what closes the planar branch the way
+ * pats_epipolar_pose_by_pair_f64 closes the epipolar one - the verified homography decomposed into (R, t, n) per pair, the candidate
+ * picked by the pair's matches - and the per-pair choice between the two poses, with the chosen branch's masks handed on.  On the
+ * device, no host read; the triangulation, the pose error and the AUC take either result as they take the epipolar pose.
+ * The decomposition is the eigenvector form of the four-solution algorithm (Ma, Soatto, Kosecka, Sastry, An Invitation to 3-D Vision,
+ * section 5.3).
+ * What it is not: no nonlinear refinement of H or of the pose, no symmetric transfer error, no prior on the normal (the candidates
+ * are returned for a caller who has one), calibrated coordinates only, and nothing in pipeline.forward_* or the drop-in calls it.
+ *
+ * 1. pats_homography_pose_by_pair_f64.  Inputs: matches_l, matches_r, the segment forms with their clamping, norm, the refit's source
+ *    (moments, or models + best with H) and swapped exactly as pats_epipolar_pose_by_pair_f64 takes them; inlier [cap] uint8 and
+ *    best_count [pairs] int64 are those of pats_homography_score_by_pair_f32; thr [pairs] float32 (optional); min_baseline a double
+ *    >= 0.  Definition, per pair; float64 on one thread unless stated otherwise:
+ *      x, used     as for the pose stage: the verification's float32 point;  used = inlier[i] != 0 and four finite coordinates
+ *      G           h_refit of the homography refit (a unit eigenvector of moments[p] for its smallest eigenvalue, or
+ *                  models[p, best[p]] promoted) as a row-major 3x3 in the frame of the points:  x_r ~ G x_l
+ *      no pose     best_count[p] < 4, a non-finite moment or h_refit, lambda2 <= 0, (rotation only and l3 <= 0), or a value of the
+ *                  decomposition that is not finite (a t_k of length 0 included).  Then R = I, t = n = 0, E = 0, baseline = 0, all
+ *                  counts 0, choice 0, status 0, front 0, cand_R = I, cand_t = cand_n = 0.  Never a NaN or an infinity in any output
+ *      spectrum    S = G^T G = V diag(lambda1 >= lambda2 >= lambda3) V^T by cyclic Jacobi, v3 = v1 x v2 so det V = +1.
+ *                  G' = G / sqrt(lambda2),  l1 = max(lambda1 / lambda2, 1),  l3 = min(max(lambda3 / lambda2, 0), 1)  (the inner
+ *                  max: the Jacobi may leave the zero eigenvalue of a singular S a rounding below zero)
+ *      sign        workgroup, float32, G' rounded to float32.  For a used match:  a_i = fma(G'_i0, l0, fma(G'_i1, l1, G'_i2)),
+ *                  q = fma(r0, a0, fma(r1, a1, a2)) = x_r . (G' x_l);  pos = #(q > 0), neg = #(q < 0);  if neg > pos then G' = -G'
+ *      baseline    sqrt(l1) - sqrt(l3): |t| / d of H = R + t n^T / d, the same for all candidates
+ *      rotation    l1 - l3 <= 0, or baseline <= min_baseline.  Then R = G' V diag(1/sqrt(l1), 1, 1/sqrt(l3)) V^T, t = n = 0, E = 0,
+ *                  status 2, vis[k] = the used count for all k, sup = 0, choice 0, front = used, cand_R = R twice, cand_t = cand_n = 0
+ *      candidates  otherwise (status 1), for s = +1 (k = 0) and s = -1 (k = 1):
+ *                    u = (sqrt(1 - l3) v1 + s sqrt(l1 - 1) v3) / sqrt(l1 - l3)
+ *                    U = [v2, u, v2 x u]     W = [G' v2, G' u, (G' v2) x (G' u)]
+ *                    R_k = W U^T             n_k = v2 x u             t_k = (G' - R_k) n_k
+ *                  k = 2, 3: (R_0, -t_0, -n_0), (R_1, -t_1, -n_1).  The written t is t_k / |t_k|; cand_t is t_k itself (|t_k| =
+ *                  baseline).  Convention x_r ~ R x_l + t, n in the left camera's frame, n . X = d > 0 on the plane.  Which
+ *                  member of the set is k = 0 depends on the signs the Jacobi gives v1 and v2 (they permute the four as
+ *                  k -> k ^ m, m in 0 .. 3); the SET of four is unique
+ *      E_k         [t_k / |t_k|]x R_k scaled to Frobenius norm 1; E is written with the hypotheses' sign rule
+ *      vis         workgroup, float32, n_k rounded to float32:  d = fma(n0, l0, fma(n1, l1, n2));  vis[k] = # used matches with d > 0
+ *                  for k = 0, 1 and with d < 0 for k = 2, 3 (one dot product serves two candidates)
+ *      sup         only with thr: over ALL matches of the segment with four finite coordinates, sup[k] = # with the epipolar
+ *                  verification's test (pats_epipolar_score_by_pair_f32) of float32(E_k) against thr[p]^2: w > 0 and s <= lim;
+ *                  sup[2] = sup[0], sup[3] = sup[1].  A NaN or negative thr gives 0.  Without thr: 0
+ *      choice      the lowest k with the lexicographically largest (vis[k], sup[k]);  front_count = vis[choice].  Two candidates
+ *                  often see every plane point in front - the known two-fold ambiguity; the matches off the plane decide through sup
+ *      front       [cap] uint8, optional: 1 where a used match is on the visible side of n_choice, 0 everywhere else.  Every byte is
+ *                  written; its sum over a segment is front_count exactly (one device function serves the counts and the mask)
+ *      swapped     as in the pose stage:  R -> P R P,  t -> P t,  n -> P n,  E -> P E P (sign rule after the permutation), the
+ *                  candidates alike;  vis, sup, choice, status, baseline and front do not depend on it
+ *    A float32 verdict within a few roundings of zero (sign, vis) or of the limit (sup) may differ from a float64 evaluation;
+ *    docs/parity.md quantifies the band.
+ *    Outputs - every call defines every byte of every output:  E, R [pairs,3,3], t, n [pairs,3], baseline [pairs] float64;  vis, sup
+ *    [pairs,4], choice, status [pairs] int32;  front_count [pairs] int64;  optional (null skips them; the three cand_* together)
+ *    cand_R [pairs,2,3,3], cand_t, cand_n [pairs,2,3] float64 and front [cap] uint8.
+ *    cap == 0 is a valid call that defines every per-pair output (the match pointers and inlier must still be non-null).  Refused
+ *    before any launch (pats_last_error names the argument), in the wording and order of the pose stage: a null matches_l / matches_r /
+ *    inlier / best_count / E / R / t / n / baseline / vis / sup / choice / status / front_count; matches_l / matches_r off 8 bytes, the
+ *    float64 and int64 arrays, pair_off and counts_in off 8, models / best / norm / thr / vis / sup / choice / status off 4; some but not
+ *    all of cand_R, cand_t, cand_n; both segment forms or neither; pairs < 1; cap < 0 or cap >= 2^31 - 1; in the strided form stride < 1 or
+ *    pairs * stride > cap; swapped not 0 or 1; neither moments nor (models and best); with models given H < 1 or H > max_h; a NaN or
+ *    negative min_baseline; a workspace smaller than pats_homography_pose_workspace_bytes (0 today; workspace may then be null).
+ *
+ * 2. pats_pose_select_by_pair: one launch, one workgroup per pair.  Inputs: the segments (as above); R_e [pairs,3,3], t_e [pairs,3],
+ *    E_e [pairs,3,3] float64, front_count_e [pairs] int64, front_e [cap] uint8 (optional) of the epipolar pose with the
+ *    verification's best_count_e [pairs] int64 and inlier_e [cap] uint8; the same of the planar pose (_h) with its status_h [pairs]
+ *    int32; ratio [pairs] float32.
+ *      epi_ok    = best_count_e >= 8
+ *      planar_ok = status_h != 0
+ *      branch    = planar_ok and (not epi_ok or double(best_count_h) >= double(ratio[p]) * double(best_count_e))
+ *                    ? (status_h == 2 ? 3 : 2)  :  (epi_ok ? 1 : 0)
+ *    - 0 no pose, 1 epipolar, 2 planar, 3 planar without a baseline (rotation only).  A NaN ratio chooses the epipolar branch when it
+ *    is ok.  Outputs, every byte defined by every call: R, t, E, front_count of the chosen branch, copied as they are (branch 0: the
+ *    identity, zeros and 0); branch [pairs] int32; inlier_sel [cap] uint8 and front_sel [cap] uint8 (optional; needs front_e and
+ *    front_h): the chosen branch's bytes over the pair's segment, 0 everywhere else.
+ *    cap == 0 is a valid call.  Refused before any launch: a null required pointer, a misaligned one, front_sel without both fronts,
+ *    both segment forms or neither, pairs < 1, cap out of range, a bad stride, a workspace smaller than
+ *    pats_pose_select_workspace_bytes (0 today). */
+size_t pats_homography_pose_workspace_bytes(int64_t pairs, int64_t cap);
+int pats_homography_pose_by_pair_f64(const float* matches_l, const float* matches_r, const uint8_t* inlier, const int64_t* pair_off,
+                                     int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const int64_t* best_count,
+                                     const double* moments, const float* models, int64_t H, const int32_t* best, const float* norm,
+                                     const float* thr, int swapped, double min_baseline, double* E, double* R, double* t, double* n,
+                                     double* baseline, int32_t* vis, int32_t* sup, int32_t* choice, int32_t* status,
+                                     int64_t* front_count, double* cand_R, double* cand_t, double* cand_n, uint8_t* front,
+                                     void* workspace, size_t workspace_bytes, pats_stream_t stream);
+size_t pats_pose_select_workspace_bytes(int64_t pairs, int64_t cap);
+int pats_pose_select_by_pair(const int64_t* pair_off, int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap,
+                             const double* R_e, const double* t_e, const double* E_e, const int64_t* front_count_e,
+                             const uint8_t* front_e, const int64_t* best_count_e, const uint8_t* inlier_e, const double* R_h,
+                             const double* t_h, const double* E_h, const int64_t* front_count_h, const uint8_t* front_h,
+                             const int32_t* status_h, const int64_t* best_count_h, const uint8_t* inlier_h, const float* ratio,
+                             double* R, double* t, double* E, int64_t* front_count, int32_t* branch, uint8_t* inlier_sel,
+                             uint8_t* front_sel, void* workspace, size_t workspace_bytes, pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-pair adaptive verification (ABI 8, symbols added): the two verifications above with plain RANSAC's stopping rule - a pair's

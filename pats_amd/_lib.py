@@ -276,6 +276,13 @@ SIGNATURES = {
     "pats_homography_refit_workspace_bytes": (c_size, [c_i64]),
     "pats_homography_refit_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p,
                                                   c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair pose from a verified homography and the per-pair E-or-H decision (csrc/pose_h.hip)
+    "pats_homography_pose_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_homography_pose_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
+                                                 c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 14 +
+                                         [c_void_p, c_size, c_void_p]),
+    "pats_pose_select_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_pose_select_by_pair": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64] + [c_void_p] * 23 + [c_void_p, c_size, c_void_p]),
     # per-pair adaptive verification, both branches (csrc/adaptive.hip): the fixed-budget arguments, then confidence, sample_size,
     # models_per_sample, round_models, used, participating
     "pats_epipolar_score_adaptive_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),

@@ -785,6 +785,118 @@ def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
     return res
 
 
+def pose_h_by_pair(out, cap, thr=None, norm=None, swapped=False, front=False, candidates=False, min_baseline=0.0):
+    """Device side, after verify_h_by_pair: each pair's pose from its verified homography (ops.homography_pose_by_pair: no host
+    read) - the refit of `verified_h`'s moments if the verification produced them, otherwise its winning model, decomposed into its
+    four (R, t, n) candidates, one picked by the matches of the lists that verification scored: how many inliers lie on the visible
+    side of the plane and - with thr [pairs] float32 - how many matches of the whole list support the candidate's essential matrix
+    (the matches off the plane: what resolves the two-fold ambiguity).  thr, norm [pairs,8] in the CALLER's order - pass the norm
+    that verify_h_by_pair was given; swapped as pose_by_pair takes it.  min_baseline: a pair with |t| / d at most this only rotates.
+    Returns and stores as `pose_h` (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64, vis [pairs,4]
+    int32, choice [pairs] int32) in the CALLER's order - with front=True followed by front (uint8, aligned with the scored lists: slot
+    order): the layout of `pose`, so triangulate_by_pair, pose_error_by_pair and split_pose_by_pair read it through
+    pose_branch(out, "planar").
+    `pose_h_extra` = (n [pairs,3], baseline [pairs] float64, sup [pairs,4] int32, status [pairs] int32: 0 no pose, 1 a pose, 2
+    rotation only) - with candidates=True followed by cand_R [pairs,2,3,3], cand_t, cand_n [pairs,2,3] - in the CALLER's order.
+    `verified`, `pose` and `homography` are not touched."""
+    if "verified_h" not in out:
+        raise ValueError("pose_h_by_pair: run verify_h_by_pair first")
+    ver, on = out["verified_h"], out["verified_h_on"]
+    best, best_count, inl = ver[1:4]
+    mixed = "caller_of" in out
+    if mixed:
+        idx = _caller_of_dev(out, inl.device)
+        norm, thr = (None if v is None else v.index_select(0, idx) for v in (norm, thr))
+    src = {"moments": ver[4]} if len(ver) > 4 else {"models": out["verified_h_models"], "best": best}
+    ml, mr, _, seg = _lists_on(out, cap, on)
+    res = ops.homography_pose_by_pair(ml, mr, inl, best_count, norm=norm, thr=thr, swapped=swapped, min_baseline=min_baseline,
+                                      return_candidates=candidates, return_front=front, **src, **seg)
+    per_pair, per_match = res[:13 if candidates else 10], res[13 if candidates else 10:]
+    if mixed:                                                             # slots back to the caller's order
+        back = _slot_of_dev(out, cap, inl.device)
+        per_pair = tuple(t.index_select(0, back) for t in per_pair)
+    out["pose_h"] = per_pair[:6] + tuple(per_match)
+    out["pose_h_extra"] = per_pair[6:]
+    return out["pose_h"]
+
+
+def select_pose_by_pair(out, cap, ratio=0.8):
+    """Device side, after pose_by_pair and pose_h_by_pair on the same lists: each pair's choice between its epipolar and its planar
+    pose (ops.pose_select_by_pair: one launch, no host read) - the planar one when it exists and the homography's best_count is at
+    least ratio times the epipolar best_count, or when fewer than 8 epipolar inliers leave no other.  ratio: a float, or a [pairs]
+    float32 tensor in the CALLER's order.
+    Returns and stores as `pose_selected` (E, R, t, front_count, front_counts [pairs,4], choice [pairs]) of the chosen branch in the
+    CALLER's order, zeros / the identity for a pair without a pose - followed by front_sel (uint8, slot order) when both poses were made
+    with front=True: the layout of `pose`, read by the consumers through pose_branch(out, "selected").  `pose_selected_extra` =
+    (branch [pairs] int32 in the CALLER's order: 0 no pose, 1 epipolar, 2 planar, 3 planar and rotation only; inlier_sel uint8, slot
+    order: the chosen branch's inlier mask).  `verified_selected` = (None, best, best_count, inlier_sel) of the chosen branch in
+    `verified`'s layout and slot order (0 for a pair without a pose).  `verified`, `verified_h`, `pose` and `pose_h` are not touched."""
+    if "pose" not in out or "pose_h" not in out:
+        raise ValueError("select_pose_by_pair: run pose_by_pair and pose_h_by_pair first")
+    if out["verified_on"] != out["verified_h_on"]:
+        raise ValueError("select_pose_by_pair: verified_on = %r and verified_h_on = %r: both branches must have scored the same lists"
+                         % (out["verified_on"], out["verified_h_on"]))
+    pe, ph_, status = out["pose"], out["pose_h"], out["pose_h_extra"][3]
+    bce, ie = out["verified"][2:4]
+    bch, ih = out["verified_h"][2:4]
+    dev = ie.device
+    if not isinstance(ratio, torch.Tensor):
+        ratio = torch.full((cap.pairs,), float(ratio), dtype=torch.float32, device=dev)
+    per_e, per_h = pe[:4], ph_[:4]
+    mixed = "caller_of" in out
+    if mixed:                                                             # the poses are in the caller's order: back to slots
+        idx = _caller_of_dev(out, dev)
+        per_e, per_h = (tuple(t.index_select(0, idx) for t in per) for per in (per_e, per_h))
+        status, ratio = status.index_select(0, idx), ratio.index_select(0, idx)
+    with_front = len(pe) > 6 and len(ph_) > 6
+    _, _, _, seg = _lists_on(out, cap, out["verified_on"])
+    res = ops.pose_select_by_pair(per_e + ((pe[6],) if with_front else ()), bce, ie, per_h + ((ph_[6],) if with_front else ()), status,
+                                  bch, ih, ratio, **seg)
+    E, R, t, front_count, branch = res[:5]
+    if mixed:
+        back = _slot_of_dev(out, cap, dev)
+        E, R, t, front_count, branch = (v.index_select(0, back) for v in (E, R, t, front_count, branch))
+    planar, none = (branch >= 2), (branch == 0)                           # caller order, like pose[4:6] and pose_h[4:6]
+    counts = torch.where(planar[:, None], ph_[4], pe[4]).masked_fill(none[:, None], 0)
+    choice = torch.where(planar, ph_[5], pe[5]).masked_fill(none, 0)
+    out["pose_selected"] = (E, R, t, front_count, counts, choice) + tuple(res[6:])
+    out["pose_selected_extra"] = (branch, res[5])
+    planar_s, none_s = res[4] >= 2, res[4] == 0                           # slot order, like the verifications' results
+    out["verified_selected"] = (None, torch.where(planar_s, out["verified_h"][1], out["verified"][1]).masked_fill(none_s, 0),
+                                torch.where(planar_s, bch, bce).masked_fill(none_s, 0), res[5])
+    return out["pose_selected"]
+
+
+_BRANCHES = {"planar": ("pose_h", "verified_h", "pose_h_by_pair"), "selected": ("pose_selected", "verified_selected", "select_pose_by_pair")}
+
+
+def pose_branch(out, branch):
+    """The result seen through one branch: a shallow copy of `out` whose `pose` and `verified` (with `verified_on` and
+    `verified_models`) are those of branch = "epipolar" (as they are), "planar" (`pose_h`, `verified_h`) or "selected"
+    (`pose_selected`, `verified_selected`).  Every consumer of a pose - triangulate_by_pair (mask="front": the branch's front,
+    "inlier": its inlier mask), pose_error_by_pair, split_pose_by_pair, split_points_by_pair - then works on the view as it stands:
+    the three poses share one layout, so there is no second code path.  What a consumer stores (`points`, `pose_error`) goes into the
+    view; `out` and the default branch's `points` and `pose_error` are never touched (a view does not inherit them either).  The
+    tensors are shared, nothing is copied or launched.  Raises ValueError for an unknown branch and for a branch that has not been
+    computed."""
+    if branch != "epipolar" and branch not in _BRANCHES:
+        raise ValueError("pose_branch: branch must be \"epipolar\", \"planar\" or \"selected\", got %r" % (branch,))
+    view = dict(out)
+    view.pop("points", None)
+    view.pop("pose_error", None)
+    if branch == "epipolar":
+        if "pose" not in out:
+            raise ValueError("pose_branch: branch=\"epipolar\": run pose_by_pair first")
+        return view
+    pose_key, ver_key, maker = _BRANCHES[branch]
+    if pose_key not in out:
+        raise ValueError("pose_branch: branch=%r: run %s first" % (branch, maker))
+    view["pose"], view["verified"] = out[pose_key], out[ver_key]
+    view["verified_on"] = out["verified_h_on"]                           # for "selected" both branches scored the same lists
+    view["verified_models"] = out["verified_h_models"] if branch == "planar" else None
+    return view
+
+
 def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf, store=None):
     """What polish_by_pair, polish_h_by_pair and polish_f_by_pair share; polish = the ops function, key = "verified" / "verified_h",
     store = the name the walk is stored under (default: "polished" / "polished_h")."""

@@ -242,4 +242,123 @@ __device__ __forceinline__ void hom_write(const double (&v)[9], bool ok, int swa
     }
 }
 
+// ---- the pose behind a homography (pose_h.hip; include/pats_amd.h, "Per-pair pose from a homography") ----------------------------
+constexpr int HPOSE_SWEEPS = 16;                       // cap of the 3x3 Jacobi loop
+
+// e (a 3x3 G, row-major) -> G^T G = V diag(lam) V^T, lam descending, the columns of V = v_1, v_2, v_1 x v_2;  Gp = G / sqrt(lam_2),
+// l1 = max(lam_1 / lam_2, 1), l3 = min(max(lam_3 / lam_2, 0), 1);  false: lam_2 <= 0 or a value that is not finite
+__device__ __forceinline__ bool hom_spectrum(const double (&e)[9], double (&Gp)[9], double (&V)[3][3], double& l1, double& l3) {
+    double B[3][3], W[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            B[i][j] = e[i] * e[j] + e[3 + i] * e[3 + j] + e[6 + i] * e[6 + j];
+            W[i][j] = i == j ? 1.0 : 0.0;
+        }
+    for (int sweep = 0; sweep < HPOSE_SWEEPS; ++sweep) {
+        bool any = pose_rot3<0, 1>(B, W);
+        any = pose_rot3<0, 2>(B, W) || any;
+        any = pose_rot3<1, 2>(B, W) || any;
+        if (!any) break;
+    }
+    double l[3] = {B[0][0], B[1][1], B[2][2]};
+    pose_order<0, 1>(l, W);                             // descending: the columns of W become v_1, v_2, (v_3)
+    pose_order<1, 2>(l, W);
+    pose_order<0, 1>(l, W);
+    if (!(l[1] > 0.0) || !__builtin_isfinite(l[0]) || !__builtin_isfinite(l[1]) || !__builtin_isfinite(l[2])) return false;
+    double v1[3], v2[3], v3[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v1[k] = W[k][0]; v2[k] = W[k][1]; }
+    pose_cross(v1, v2, v3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { V[k][0] = v1[k]; V[k][1] = v2[k]; V[k][2] = v3[k]; }
+    const double inv = 1.0 / __builtin_sqrt(l[1]);
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { Gp[k] = e[k] * inv; ok = ok && __builtin_isfinite(Gp[k]); }
+    const double a = l[0] / l[1], c = l[2] / l[1];
+    l1 = a > 1.0 ? a : 1.0;
+    l3 = c < 1.0 ? (c > 0.0 ? c : 0.0) : 1.0;
+    return ok && __builtin_isfinite(l1);
+}
+
+// y = G x for a row-major 3x3
+__device__ __forceinline__ void hom_apply(const double (&G)[9], const double (&x)[3], double (&y)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) y[i] = G[3 * i] * x[0] + G[3 * i + 1] * x[1] + G[3 * i + 2] * x[2];
+}
+
+// the rotation of a homography without a baseline: R = Gp V diag(1/sqrt(l1), 1, 1/sqrt(l3)) V^T (l3 > 0);  false: not finite
+__device__ __forceinline__ bool hom_rotation(const double (&Gp)[9], const double (&V)[3][3], double l1, double l3, double (&R)[9]) {
+    const double d[3] = {1.0 / __builtin_sqrt(l1), 1.0, 1.0 / __builtin_sqrt(l3)};
+    double gv[3][3];                                    // gv[c] = Gp v_c
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double v[3] = {V[0][c], V[1][c], V[2][c]};
+        hom_apply(Gp, v, gv[c]);
+    }
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            R[3 * i + j] = gv[0][i] * d[0] * V[j][0] + gv[1][i] * d[1] * V[j][1] + gv[2][i] * d[2] * V[j][2];
+            ok = ok && __builtin_isfinite(R[3 * i + j]);
+        }
+    return ok;
+}
+
+// The two candidates s = +1, -1 of Gp = R + t n^T with Gp^T Gp = V diag(l1, 1, l3) V^T and l1 - l3 > 0 (the eigenvector form of the
+// four-solution algorithm; the other two are (R_k, -t_k, -n_k)):
+//   u = (sqrt(1 - l3) v1 + s sqrt(l1 - 1) v3) / sqrt(l1 - l3),  U = [v2, u, v2 x u],  W = [Gp v2, Gp u, (Gp v2) x (Gp u)]
+//   R = W U^T,  n = v2 x u,  t = (Gp - R) n (not normalised),  E = [t / |t|]x R scaled to Frobenius norm 1
+// false: a value that is not finite, or t = 0
+__device__ __forceinline__ bool hom_decompose(const double (&Gp)[9], const double (&V)[3][3], double l1, double l3, double (&R)[2][9],
+                                              double (&t)[2][3], double (&n)[2][3], double (&E)[2][9]) {
+    const double a = __builtin_sqrt(1.0 - l3), b = __builtin_sqrt(l1 - 1.0), inv = 1.0 / __builtin_sqrt(l1 - l3);
+    const double v2[3] = {V[0][1], V[1][1], V[2][1]};
+    double w0[3];
+    hom_apply(Gp, v2, w0);
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double sb = k == 0 ? b : -b;
+        double u[3], w1[3], w2[3], nn[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) u[i] = (a * V[i][0] + sb * V[i][2]) * inv;
+        pose_cross(v2, u, nn);
+        hom_apply(Gp, u, w1);
+        pose_cross(w0, w1, w2);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) R[k][3 * i + j] = w0[i] * v2[j] + w1[i] * u[j] + w2[i] * nn[j];
+        double gn[3], rn[3], tt[3];
+        hom_apply(Gp, nn, gn);
+        hom_apply(R[k], nn, rn);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { tt[i] = gn[i] - rn[i]; t[k][i] = tt[i]; n[k][i] = nn[i]; }
+        const double tn = __builtin_sqrt(tt[0] * tt[0] + tt[1] * tt[1] + tt[2] * tt[2]);
+        ok = ok && tn > 0.0 && __builtin_isfinite(tn);
+        const double q[3] = {tt[0] / tn, tt[1] / tn, tt[2] / tn};
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {                   // [q]x R by rows
+            E[k][j] = q[1] * R[k][6 + j] - q[2] * R[k][3 + j];
+            E[k][3 + j] = q[2] * R[k][j] - q[0] * R[k][6 + j];
+            E[k][6 + j] = q[0] * R[k][3 + j] - q[1] * R[k][j];
+        }
+#pragma unroll
+        for (int j = 0; j < 9; ++j) s += E[k][j] * E[k][j];
+        const double es = 1.0 / __builtin_sqrt(s);
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            E[k][j] *= es;
+            ok = ok && __builtin_isfinite(E[k][j]) && __builtin_isfinite(R[k][j]);
+        }
+    }
+    return ok;
+}
+
 }  // namespace pats

@@ -2205,6 +2205,157 @@ def homography_refit_by_pair(best_count, moments=None, models=None, best=None, n
     return out
 
 
+def homography_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
+                            counts=None, norm=None, thr=None, swapped=False, min_baseline=0.0, return_candidates=False,
+                            return_front=False, out=None, pairs=None):
+    """Each pair's pose from its verified homography, ON THE DEVICE, no host read (pats_homography_pose_by_pair_f64;
+    include/pats_amd.h, "Per-pair pose from a homography and the E-or-H decision", holds the definition): the homography refit's
+    G = h_refit (the smallest eigenvector of `moments`; without moments the winning model models[p, best[p]]) decomposed into its
+    four (R, t, n) candidates, one picked by the pair's matches - how many used matches (inlier != 0, finite) lie on the visible side
+    of the plane, then, with thr [pairs] float32 given, how many matches of the whole segment support the candidate's essential
+    matrix.  matches_l / matches_r [cap,2] float32 (also [pairs,K,2]), the segments (pair_off, or stride + counts) and norm exactly as
+    homography_score_by_pair took them; inlier [cap] uint8, best_count [pairs] int64 and moments [pairs,9,9] float64 (or best [pairs]
+    int32 with the models) are its outputs.  swapped as epipolar_pose_by_pair takes it.  min_baseline: a pair whose baseline
+    |t| / d is at most this is taken as rotating only.
+    Returns (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64, vis [pairs,4] int32, choice [pairs] int32,
+    n [pairs,3], baseline [pairs] float64, sup [pairs,4] int32, status [pairs] int32: 0 no pose, 1 a pose, 2 rotation only (t = n = 0)),
+    then cand_R [pairs,2,3,3], cand_t, cand_n [pairs,2,3] float64 with return_candidates=True, then front [cap] uint8 with
+    return_front=True.  A pair without a pose has E = 0, R = I, t = n = 0 and no count.  out: the destinations, in that order."""
+    fn = "homography_pose_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (inlier, "inlier"), (best_count, "best_count"),
+                    (moments, "moments"), (models, "models"), (best, "best"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm"),
+                    (thr, "thr")],
+               {"inlier": torch.uint8, "best_count": torch.int64, "moments": torch.float64, "best": torch.int32, "pair_off": torch.int64,
+                "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if moments is None and (models is None or best is None):
+        raise RuntimeError("homography_pose_by_pair: give moments, or models and best")
+    min_baseline = float(min_baseline)
+    if not min_baseline >= 0.0:                       # false for a NaN
+        raise RuntimeError("homography_pose_by_pair: min_baseline = %r must be a number >= 0" % min_baseline)
+    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    inl = _dev(inlier, "inlier", torch.uint8).reshape(-1)
+    if inl.numel() != cap:
+        raise RuntimeError("homography_pose_by_pair: inlier must be [cap]")
+    bc = _dev(best_count, "best_count", torch.int64).reshape(-1)
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if bc.numel() != pairs:
+        raise RuntimeError("homography_pose_by_pair: best_count must hold one int64 per pair (%d), got %d" % (pairs, bc.numel()))
+    H = 1
+    if moments is not None:
+        moments = _dev(moments, "moments", torch.float64)
+        if tuple(moments.shape) != (pairs, 9, 9):
+            raise RuntimeError("homography_pose_by_pair: moments must be [pairs,9,9]")
+        models = best = None
+    else:
+        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
+        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
+            raise RuntimeError("homography_pose_by_pair: models must be [pairs,H,3,3] and best [pairs]")
+        H = int(models.shape[1])
+        if not 1 <= H <= epipolar_max_h():
+            raise RuntimeError("homography_pose_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    norm = _bp_norm(fn, norm, pairs)
+    if thr is not None:
+        thr = _dev(thr, "thr").reshape(-1)
+        if thr.numel() != pairs:
+            raise RuntimeError("homography_pose_by_pair: thr must hold one float32 per pair (%d), got %d" % (pairs, thr.numel()))
+    dev = ml.device
+    f64, i32 = torch.float64, torch.int32
+    want = [("E", f64, (pairs, 3, 3)), ("R", f64, (pairs, 3, 3)), ("t", f64, (pairs, 3)), ("front_count", torch.int64, (pairs,)),
+            ("vis", i32, (pairs, 4)), ("choice", i32, (pairs,)), ("n", f64, (pairs, 3)), ("baseline", f64, (pairs,)),
+            ("sup", i32, (pairs, 4)), ("status", i32, (pairs,))]
+    if return_candidates:
+        want += [("cand_R", f64, (pairs, 2, 3, 3)), ("cand_t", f64, (pairs, 2, 3)), ("cand_n", f64, (pairs, 2, 3))]
+    if return_front:
+        want.append(("front", torch.uint8, (cap,)))
+    out = _bp_outputs(fn, want, out, dev)
+    nws = _L().pats_homography_pose_workspace_bytes(pairs, cap)
+    ws = _workspace(nws, dev) if nws else None
+    cand = out[10:13] if return_candidates else (None, None, None)
+    front = out[-1] if return_front else None
+    if cap == 0:
+        ml = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        front = None
+    _check(_L().pats_homography_pose_by_pair_f64(_ptr(ml), _ptr(mr), _ptr(inl), off_p, stride, counts_p, pairs, cap, _ptr(bc),
+                                                 _ptr(moments), _ptr(models), H, _ptr(best), _ptr(norm), _ptr(thr), 1 if swapped else 0,
+                                                 min_baseline, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[6]), _ptr(out[7]),
+                                                 _ptr(out[4]), _ptr(out[8]), _ptr(out[5]), _ptr(out[9]), _ptr(out[3]), _ptr(cand[0]),
+                                                 _ptr(cand[1]), _ptr(cand[2]), _ptr(front), _ptr(ws), nws, _stream()), fn)
+    return out
+
+
+def pose_select_by_pair(pose_e, best_count_e, inlier_e, pose_h, status_h, best_count_h, inlier_h, ratio, pair_off=None, stride=None,
+                        counts=None, out=None, pairs=None):
+    """Each pair's choice between its epipolar and its planar pose, ON THE DEVICE, one launch, no host read
+    (pats_pose_select_by_pair; include/pats_amd.h, "Per-pair pose from a homography and the E-or-H decision", holds the rule).
+    pose_e = (E, R, t, front_count[, front]) of epipolar_pose_by_pair with the verification's best_count_e [pairs] int64 and
+    inlier_e [cap] uint8; pose_h the same of homography_pose_by_pair with its status_h [pairs] int32, best_count_h and inlier_h;
+    ratio [pairs] float32; the segments (pair_off, or stride + counts) as both stages took them.  The planar pose is chosen when it
+    exists and best_count_h >= ratio * best_count_e, or when fewer than 8 epipolar inliers leave no other.
+    Returns (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64, branch [pairs] int32: 0 no pose,
+    1 epipolar, 2 planar, 3 planar and rotation only, inlier_sel [cap] uint8), then front_sel [cap] uint8 when both poses carry a
+    front: the chosen branch's values, its mask bytes over each pair's segment and 0 elsewhere.  out: the destinations, in that order."""
+    fn = "pose_select_by_pair"
+    if len(pose_e) not in (4, 5) or len(pose_h) not in (4, 5):
+        raise RuntimeError("pose_select_by_pair: pose_e and pose_h must be (E, R, t, front_count[, front])")
+    with_front = len(pose_e) == 5 and len(pose_h) == 5
+    names_e = ("E_e", "R_e", "t_e", "front_count_e", "front_e")[:len(pose_e)]
+    names_h = ("E_h", "R_h", "t_h", "front_count_h", "front_h")[:len(pose_h)]
+    named = list(zip(pose_e, names_e)) + list(zip(pose_h, names_h)) + [
+        (best_count_e, "best_count_e"), (inlier_e, "inlier_e"), (status_h, "status_h"), (best_count_h, "best_count_h"),
+        (inlier_h, "inlier_h"), (ratio, "ratio"), (pair_off, "pair_off"), (counts, "counts")]
+    types = {"front_count_e": torch.int64, "front_count_h": torch.int64, "front_e": torch.uint8, "front_h": torch.uint8,
+             "best_count_e": torch.int64, "best_count_h": torch.int64, "inlier_e": torch.uint8, "inlier_h": torch.uint8,
+             "status_h": torch.int32, "pair_off": torch.int64, "counts": torch.int64}
+    types.update({n: torch.float64 for n in ("E_e", "R_e", "t_e", "E_h", "R_h", "t_h")})
+    _bp_layout(fn, named, types)
+    _bp_one_form(fn, pair_off, stride, counts)
+    ie, ih = _dev(inlier_e, "inlier_e", torch.uint8).reshape(-1), _dev(inlier_h, "inlier_h", torch.uint8).reshape(-1)
+    cap = int(ie.numel())
+    if ih.numel() != cap:
+        raise RuntimeError("pose_select_by_pair: inlier_e and inlier_h must both be [cap]")
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    per_pair = {"E": (pairs, 3, 3), "R": (pairs, 3, 3), "t": (pairs, 3), "front_count": (pairs,), "front": (cap,)}
+    got = {}
+    for tensors, names in ((pose_e, names_e), (pose_h, names_h)):
+        for x, name in zip(tensors, names):
+            x = _dev(x, name, types[name])
+            if name.startswith("front_") and not name.startswith("front_count"):
+                x = x.reshape(-1)
+            if tuple(x.shape) != per_pair[name[:-2]]:
+                raise RuntimeError("pose_select_by_pair: %s must be %s" % (name, list(per_pair[name[:-2]])))
+            got[name] = x
+    vec = {}
+    for x, name, dt in ((best_count_e, "best_count_e", torch.int64), (best_count_h, "best_count_h", torch.int64),
+                        (status_h, "status_h", torch.int32), (ratio, "ratio", torch.float32)):
+        x = _dev(x, name, dt).reshape(-1)
+        if x.numel() != pairs:
+            raise RuntimeError("pose_select_by_pair: %s must hold one value per pair (%d), got %d" % (name, pairs, x.numel()))
+        vec[name] = x
+    dev = ie.device
+    want = [("E", torch.float64, (pairs, 3, 3)), ("R", torch.float64, (pairs, 3, 3)), ("t", torch.float64, (pairs, 3)),
+            ("front_count", torch.int64, (pairs,)), ("branch", torch.int32, (pairs,)), ("inlier_sel", torch.uint8, (cap,))]
+    if with_front:
+        want.append(("front_sel", torch.uint8, (cap,)))
+    out = _bp_outputs(fn, want, out, dev)
+    nws = _L().pats_pose_select_workspace_bytes(pairs, cap)
+    ws = _workspace(nws, dev) if nws else None
+    fe, fh, sel, fsel = got.get("front_e"), got.get("front_h"), out[5], out[6] if with_front else None
+    if not with_front:
+        fe = fh = None
+    if cap == 0:
+        ie = ih = sel = _bp_placeholder(dev, torch.uint8)
+        fe = fh = fsel = None
+    _check(_L().pats_pose_select_by_pair(off_p, stride, counts_p, pairs, cap, _ptr(got["R_e"]), _ptr(got["t_e"]), _ptr(got["E_e"]),
+                                         _ptr(got["front_count_e"]), _ptr(fe), _ptr(vec["best_count_e"]), _ptr(ie), _ptr(got["R_h"]),
+                                         _ptr(got["t_h"]), _ptr(got["E_h"]), _ptr(got["front_count_h"]), _ptr(fh), _ptr(vec["status_h"]),
+                                         _ptr(vec["best_count_h"]), _ptr(ih), _ptr(vec["ratio"]), _ptr(out[1]), _ptr(out[2]),
+                                         _ptr(out[0]), _ptr(out[3]), _ptr(out[4]), _ptr(out[5] if cap else sel), _ptr(fsel), _ptr(ws),
+                                         nws, _stream()), fn)
+    return out
+
+
 def fundamental_refit_by_pair(best_count, moments=None, models=None, best=None, norm=None, swapped=False, return_pixel=False,
                               return_refit=False, out=None):
     """Each pair's fundamental matrix from its verified inliers, ON THE DEVICE, one launch, float64, no host read
