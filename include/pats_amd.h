@@ -1340,6 +1340,52 @@ int pats_homography_score_adaptive_by_pair_f32(const float* matches_l, const flo
                                                int32_t* participating);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pair MSAC scoring (ABI 8, symbols added): the two fixed-budget verifications with the winner chosen by how well its inliers
+ * fit, not only by how many it has - the MSAC gain, sum over the inliers of 1 - e^2 / thr^2 (e^2 the squared Sampson error or the
+ * squared forward transfer error).  Two models with the same support are told apart, and with a threshold a few times the noise a
+ * slightly wrong model that collects an inlier or two more than the right one no longer wins.  On the device, no host read.
+ * pats_epipolar_score_msac_by_pair_f32 and pats_homography_score_msac_by_pair_f32 take the arguments of
+ * pats_epipolar_score_by_pair_f32 / pats_homography_score_by_pair_f32 in their order and meaning through `stream` - the matches, the
+ * two segment forms and their clamping, norm, min_conf, thr, models [pairs,H,3,3], H <= pats_epipolar_max_h(), the "participates"
+ * rule - and then gains and best_gain.  The verdict is the family's: inlier iff w > 0 and s <= lim, by the device function the count
+ * entries run (Epipolar: s = r^2, w = den, lim = thr^2 den;  Homography: s = d0^2 + d1^2, w = a2^2, lim = thr^2 a2^2).
+ * Per pair p, model h and match i
+ *   a non-inlier   g_i = 0: a match that does not participate, a NaN anywhere, a zero model, a NaN or negative thr
+ *   an inlier      u = s / lim for lim > 0, u = 0 for lim == 0 (thr == 0: an inlier has s == 0), in float32 and in ONE form for every
+ *                  cell: u = s * rcp(lim), rcp the device's reciprocal instruction (v_rcp_f32: within 1 ulp of 1 / lim), then one
+ *                  rounded multiply.  Against the exact quotient of the float32 s and lim that is a relative error of at most
+ *                  3 * 2^-24.  (A lim below the smallest normal float32 may give rcp = +inf; u = 0 * inf = NaN counts as u = 1.)
+ *                  q = min((uint32)floor(u * 2^20), 2^20),  g_i = 2^20 - q    (u * 2^20 is exact)
+ *   gains[p, h]    int64 = sum over i of g_i.  Integer adds are order-independent: a call is bit-reproducible and a pair's gains do not
+ *                  depend on where its segment lies.  pats_msac_gain_one() returns 1 << 20: gains / 2^20 ~ sum over the inliers of
+ *                  1 - e^2 / thr^2, and participating - gains / 2^20 is the MSAC cost
+ *   best[p]        int32: the lowest index with the largest gain; 0 when every gain is 0
+ *   best_gain[p]   int64 = gains[p, best[p]];  best_count[p] int64 = counts[p, best[p]]
+ *   counts [pairs,H] int32   bit for bit what the count entry returns for the same call
+ *   inlier, moments          the count entries' mask kernel run on the MSAC winner: bit for bit what the count entry returns when
+ *                  models[p, best[p]] is the pair's only model
+ * A pair whose thr is NaN or negative has gains 0, best 0, best_gain 0, best_count 0, mask 0, moments 0.  Every call defines every
+ * byte of every output, cap == 0 included (gains 0, best 0).  Like the count entries' verdicts, a gain is evaluated in float32 with
+ * fused multiply-adds: docs/parity.md ("MSAC scoring") bounds its distance from a float64 evaluation per cell.
+ * Refused before any launch: everything the count entries refuse, in their wording (under the MSAC entry's name) and order; then a
+ * null gains / best_gain or one off 8 bytes.  Workspace: that of the count sibling (0 today; workspace may be null).
+ * The adaptive entries and the local optimisation still rank by count: their stopping rule and their choice of round are defined on
+ * it. */
+int64_t pats_msac_gain_one(void);
+int pats_epipolar_score_msac_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                         int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                         int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                         int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                         void* workspace, size_t workspace_bytes, pats_stream_t stream, int64_t* gains,
+                                         int64_t* best_gain);
+int pats_homography_score_msac_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                           int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                           int64_t H, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                           int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, double* moments,
+                                           void* workspace, size_t workspace_bytes, pats_stream_t stream, int64_t* gains,
+                                           int64_t* best_gain);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pair local optimisation (ABI 8, symbols added): the rounds "refit the winner's inliers, verify the refit" that follow a
  * verification - LO-RANSAC's inner loop in its simplest form - walked by ONE launch per call with the pair's matches resident on
  * chip, and the BEST round kept: the result never has less support than the model it started from.  No new numerics: every value

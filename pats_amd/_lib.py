@@ -289,6 +289,10 @@ SIGNATURES = {
     "pats_epipolar_score_adaptive_by_pair_f32": (c_int, _SCORE_ARGS + _ADAPTIVE_ARGS),
     "pats_homography_score_adaptive_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
     "pats_homography_score_adaptive_by_pair_f32": (c_int, _SCORE_ARGS + _ADAPTIVE_ARGS),
+    # per-pair MSAC scoring, both branches (csrc/epipolar.hip): the fixed-budget arguments, then gains, best_gain
+    "pats_msac_gain_one": (c_i64, []),
+    "pats_epipolar_score_msac_by_pair_f32": (c_int, _SCORE_ARGS + [c_void_p, c_void_p]),
+    "pats_homography_score_msac_by_pair_f32": (c_int, _SCORE_ARGS + [c_void_p, c_void_p]),
     # per-pair local optimisation, both branches (csrc/polish.hip): the verification's match, segment, thr, norm and min_conf
     # arguments, then models, H, best, rounds, the six outputs, workspace, stream
     "pats_epipolar_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),

@@ -540,9 +540,10 @@ def hypothesize7_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=
     return hyp
 
 
-def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, moments, adaptive=None):
-    """What the four verify functions share; score = the ops function, key = "verified" / "verified_h".  adaptive: None for the fixed
-    budget, else (confidence, sample_size, models_per_sample, round_models) - `key`_used is stored too."""
+def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, moments, adaptive=None, msac=False):
+    """What the six verify functions share; score = the ops function, key = "verified" / "verified_h".  adaptive: None for the fixed
+    budget, else (confidence, sample_size, models_per_sample, round_models) - `key`_used is stored too.  msac: score is an MSAC
+    entry - `key` keeps the standard tuple, `key`_gain = (gains, best_gain) and `key`_score = "msac" are stored too."""
     more = {}
     if adaptive is not None:
         confidence, sample_size, models_per_sample, round_models = adaptive
@@ -561,8 +562,12 @@ def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, moments, 
     ml, mr, conf, seg = _lists_on(out, cap, on)
     res = score(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, moments=moments, **more,
                 **seg)
-    out[key], out[key + "_on"] = (res if adaptive is None else res[:-2]), on
+    out[key], out[key + "_on"] = (res[:-2] if adaptive is not None or msac else res), on
     out[key + "_models"] = models                     # slot order: the refit's source when no moments were asked for
+    out.pop(key + "_gain", None)                      # a count verification after an MSAC one leaves no stale gains
+    out.pop(key + "_score", None)
+    if msac:
+        out[key + "_gain"], out[key + "_score"] = res[-2:], "msac"
     if adaptive is not None:
         out[key + "_used"] = res[-2:]
     return res
@@ -579,6 +584,17 @@ def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", mo
     in SLOT order for a mixed pack (models / thr / norm are permuted to it on the device; split_verified_by_pair hands the pairs
     back in the caller's order).  The matches, the regrouped lists and a top-K of the same step are not touched."""
     return _verify("verify_by_pair", ops.epipolar_score_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, moments)
+
+
+def verify_msac_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
+    """verify_by_pair with the winner chosen by MSAC gain instead of by count (ops.epipolar_score_msac_by_pair: no host read) - the
+    same arguments.  `verified` keeps verify_by_pair's tuple - counts as there; best, best_count, inlier and moments of the MSAC
+    winner - so pose_by_pair, polish_by_pair, fundamental_by_pair and split_verified_by_pair work on it unchanged;
+    `verified_gain` = (gains [pairs,H] int64, best_gain [pairs] int64; rows in slot order like `verified`'s) and
+    `verified_score` = "msac" are added (a later verify_by_pair on the same result removes the two).  Returns the tuple followed by
+    gains, best_gain."""
+    return _verify("verify_msac_by_pair", ops.epipolar_score_msac_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, moments,
+                   msac=True)
 
 
 def split_verified_by_pair(out, cap):
@@ -758,6 +774,14 @@ def verify_h_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", 
     `verified`'s.  `verified_h_on` and `verified_h_models` go with it.  `verified` and `pose` are never touched: a caller runs
     both branches on one result and compares best_count of the two - choosing between the models stays with the caller."""
     return _verify("verify_h_by_pair", ops.homography_score_by_pair, "verified_h", out, cap, models, thr, norm, min_conf, on, moments)
+
+
+def verify_h_msac_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
+    """verify_h_by_pair with the winner chosen by MSAC gain (ops.homography_score_msac_by_pair), as verify_msac_by_pair is to
+    verify_by_pair: `verified_h` keeps the standard tuple for the MSAC winner - homography_by_pair, polish_h_by_pair and
+    pose_h_by_pair work on it unchanged -, `verified_h_gain` = (gains, best_gain) and `verified_h_score` = "msac" are added."""
+    return _verify("verify_h_msac_by_pair", ops.homography_score_msac_by_pair, "verified_h", out, cap, models, thr, norm, min_conf, on,
+                   moments, msac=True)
 
 
 def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):

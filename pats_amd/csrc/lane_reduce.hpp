@@ -122,4 +122,17 @@ __device__ __forceinline__ uint32_t wave_scan_inclusive_u32(uint32_t v, int lane
     return v;
 }
 
+// 64-lane sum of an integer into every lane: wave_sum_xbar's steps (four in-row DPP adds, lane ^ 16 by ds_swizzle_b32, lane ^ 32 by
+// ds_bpermute_b32) with integer adds - exact and the same in every lane as long as the sum fits 32 bits.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v, int lane) {
+    int x = (int)v;
+    x += dpp_i<DPP_QUAD_XOR1>(x);
+    x += dpp_i<DPP_QUAD_XOR2>(x);
+    x += dpp_i<DPP_ROW_HALF_MIRROR>(x);
+    x += dpp_i<DPP_ROW_MIRROR>(x);
+    x += __builtin_amdgcn_ds_swizzle(x, (16 << 10) | 0x1f);
+    x += __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, x);
+    return (uint32_t)x;
+}
+
 }  // namespace pats

@@ -24,7 +24,7 @@ __device__ __forceinline__ v2f pk_splat(float v) { return v2f{v, v}; }
 // kernel both call it.  accumulate: an inlier's 45 products in float64 (the products of two float32 are exact).  The strings are the
 // names the launch checks report.
 struct Epipolar {
-    static constexpr const char *SCORE = "epipolar_score kernel", *ROUND = "epipolar_score kernel (a round)",
+    static constexpr const char *SCORE = "epipolar_score kernel", *SCORE_MSAC = "epipolar_score kernel (MSAC)", *ROUND = "epipolar_score kernel (a round)",
                                 *ARGMAX = "epipolar_argmax kernel", *MASK = "epipolar_mask kernel", *POLISH = "epipolar_polish kernel";
     // s = r^2, lim = thr^2 den, w = den
     static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
@@ -55,7 +55,7 @@ struct Fundamental : Epipolar {
 };
 
 struct Homography {
-    static constexpr const char *SCORE = "homography_score kernel", *ROUND = "homography_score kernel (a round)",
+    static constexpr const char *SCORE = "homography_score kernel", *SCORE_MSAC = "homography_score kernel (MSAC)", *ROUND = "homography_score kernel (a round)",
                                 *ARGMAX = "homography_argmax kernel", *MASK = "homography_mask kernel", *POLISH = "homography_polish kernel";
     // s = d0^2 + d1^2, lim = thr^2 a2^2, w = a2^2
     static __device__ __forceinline__ void test2(const float (&e)[9], float t2, v2f l0, v2f l1, v2f r0, v2f r1, v2f& s, v2f& lim, v2f& w) {
@@ -80,6 +80,18 @@ struct Homography {
             for (int v = u; v < 9; ++v) acc[k++] += qa[u] * qa[v] + qb[u] * qb[v];
     }
 };
+
+// The MSAC gain of one cell from what test2 returned (include/pats_amd.h, "Per-pair MSAC scoring"): 2^20 - q for an inlier,
+// q = min(floor(u 2^20), 2^20), u = s / lim as ONE hardware reciprocal (v_rcp_f32, 1 ulp) and one multiply; 0 for every other cell.
+// The scaling by 2^20 is exact, the conversion truncates (u >= 0), and fminf drops a NaN u (0 x inf: s = 0 against a lim so small
+// that its reciprocal overflows) in favour of 2^20: that cell gains nothing.
+constexpr int MSAC_GAIN_BITS = 20;
+__device__ __forceinline__ uint32_t verify_gain(bool inlier, float s, float lim) {
+    constexpr float ONE = (float)(1u << MSAC_GAIN_BITS);
+    const float u = lim > 0.0f ? s * __builtin_amdgcn_rcpf(lim) : 0.0f;
+    const uint32_t q = (uint32_t)fminf(u * ONE, ONE);
+    return inlier ? (1u << MSAC_GAIN_BITS) - q : 0u;
+}
 
 __device__ __forceinline__ void verify_model(const float* __restrict__ m, float (&e)[9]) {
 #pragma unroll

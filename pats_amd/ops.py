@@ -1709,10 +1709,11 @@ def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=Non
 
 
 def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out,
-                   pairs, adaptive=None):
-    """What the four verifications share - everything but the C entry and its workspace query (the library's functions; looked up by
+                   pairs, adaptive=None, msac=False):
+    """What the six verifications share - everything but the C entry and its workspace query (the library's functions; looked up by
     the callers, by plain attribute: these calls take microseconds and a formatted name would show).  adaptive: None for
-    the fixed budget, else (confidence, sample_size, models_per_sample, round_models) - four more arguments, two more outputs."""
+    the fixed budget, else (confidence, sample_size, models_per_sample, round_models) - four more arguments, two more outputs.
+    msac: the MSAC entries - two more outputs, gains and best_gain."""
     _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
                     (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
     _bp_one_form(fn, pair_off, stride, counts)
@@ -1750,6 +1751,8 @@ def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr
         want.append(("moments", torch.float64, (pairs, 9, 9)))
     if adaptive is not None:
         want += [("used", torch.int32, (pairs,)), ("participating", torch.int32, (pairs,))]
+    if msac:
+        want += [("gains", torch.int64, (pairs, H)), ("best_gain", torch.int64, (pairs,))]
     out = _bp_outputs(fn, want, out, dev)
     nws = workspace_bytes(pairs, H, cap)
     ws = _workspace(nws, dev) if nws else None
@@ -1759,6 +1762,8 @@ def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr
         inl = _bp_placeholder(dev, torch.uint8)
         conf = None if conf is None else ml
     more = () if adaptive is None else (confidence, s, g, B, _ptr(out[-2]), _ptr(out[-1]))
+    if msac:
+        more = (_ptr(out[-2]), _ptr(out[-1]))
     _check(entry(
         _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H, _ptr(thr), _ptr(norm),
         0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
@@ -1818,6 +1823,24 @@ def epipolar_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, str
     least-squares refit.  out: the four (five) destinations."""
     return _score_by_pair("epipolar_score_by_pair", _L().pats_epipolar_score_by_pair_f32, _L().pats_epipolar_workspace_bytes, matches_l,
                           matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs)
+
+
+def msac_gain_one():
+    """The gain of a perfect inlier in the units of epipolar_score_msac_by_pair's gains (pats_msac_gain_one: 1 << 20)."""
+    return int(_L().pats_msac_gain_one())
+
+
+def epipolar_score_msac_by_pair(matches_l, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None,
+                                norm=None, moments=False, out=None, pairs=None):
+    """epipolar_score_by_pair with the winner chosen by MSAC gain, ON THE DEVICE, no host read
+    (pats_epipolar_score_msac_by_pair_f32; include/pats_amd.h, "Per-pair MSAC scoring", holds the definition): an inlier of model h
+    adds 2^20 - min(floor(2^20 r^2 / (thr^2 den)), 2^20) to gains[p, h], every other match 0; best is the lowest index of the largest
+    gain.  The arguments are epipolar_score_by_pair's.
+    Returns epipolar_score_by_pair's tuple - counts bit for bit its counts; best, best_count, inlier and moments those of the MSAC
+    winner - followed by gains [pairs,H] int64 and best_gain [pairs] int64 (gains / msac_gain_one() ~ the sum over the inliers of
+    1 - e^2 / thr^2).  out: the six (seven) destinations."""
+    return _score_by_pair("epipolar_score_msac_by_pair", _L().pats_epipolar_score_msac_by_pair_f32, _L().pats_epipolar_workspace_bytes,
+                          matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs, msac=True)
 
 
 def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
@@ -2156,6 +2179,15 @@ def homography_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, s
     homography_refit_by_pair.  out: the four (five) destinations."""
     return _score_by_pair("homography_score_by_pair", _L().pats_homography_score_by_pair_f32, _L().pats_homography_score_workspace_bytes,
                           matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out, pairs)
+
+
+def homography_score_msac_by_pair(matches_l, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None,
+                                  norm=None, moments=False, out=None, pairs=None):
+    """homography_score_by_pair with the winner chosen by MSAC gain (pats_homography_score_msac_by_pair_f32): the arguments and the
+    outputs of epipolar_score_msac_by_pair, the squared forward transfer error d0^2 + d1^2 against thr^2 a2^2 as the test."""
+    return _score_by_pair("homography_score_msac_by_pair", _L().pats_homography_score_msac_by_pair_f32,
+                          _L().pats_homography_score_workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf,
+                          min_conf, norm, moments, out, pairs, msac=True)
 
 
 def homography_refit_by_pair(best_count, moments=None, models=None, best=None, norm=None, swapped=False, return_pixel=False, out=None):
