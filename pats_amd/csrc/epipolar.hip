@@ -219,10 +219,8 @@ verify_mask_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_,
     for (int k = 0; k < EPI_MOM; ++k) acc[k] = 0.0;
     if (live) {                                         // workgroup-uniform
         const float t2 = t * t;
-        int h = best[p];
-        h = h < 0 ? 0 : (h >= H ? H - 1 : h);
         float e[9];
-        verify_model(models + ((int64_t)p * H + h) * 9, e);
+        verify_model(epi_winner(models, H, best, p), e);
         const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
         const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
         const float* conf = conf_ ? conf_ + lo : nullptr;

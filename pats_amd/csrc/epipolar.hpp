@@ -1,6 +1,8 @@
-// What the per-pair stages share (epipolar.hip: verification; hypotheses.hip: the 8-point and 4-point hypotheses; hypotheses5.hip: the
-// 5-point hypotheses; pose.hip: the pose; homography.hip: the refit; polish.hip: the local optimisation): how a pair's segment of the match lists, its normalisation and
-// a match's point are read, and the hypotheses' sampler.  include/pats_amd.h states all of it.
+// What the per-pair stages share (epipolar.hip: verification; hypotheses.hip, hypotheses5.hip, hypotheses7.hip: the 8-, 4-, 5- and
+// 7-point hypotheses; pose.hip, pose_h.hip: the poses; homography.hip, fundamental.hip: the refits; polish.hip: the local optimisation):
+// how a pair's segment of the match lists, its normalisation, a match's point and the winning model are read, the hypotheses' sampler
+// with the front end of every minimal-sample kernel, and the host checks of the generators and of the refit source.
+// include/pats_amd.h states all of it.
 #pragma once
 #include "common.hpp"
 
@@ -52,6 +54,15 @@ __device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const fl
     if (ok) l0 = a.x;
 }
 
+// the winner of pair p among its H models: model h clamped into 0 .. H - 1, h = best[p]
+__device__ __forceinline__ const float* epi_winner(const float* __restrict__ models, int H, int h, int64_t p) {
+    h = h < 0 ? 0 : (h >= H ? H - 1 : h);
+    return models + (p * H + h) * 9;
+}
+__device__ __forceinline__ const float* epi_winner(const float* __restrict__ models, int H, const int32_t* __restrict__ best, int64_t p) {
+    return epi_winner(models, H, best[p], p);
+}
+
 // ---- the hypotheses' sampler (include/pats_amd.h, "Per-pair hypotheses"): uint32 arithmetic that wraps ------------------------
 __device__ __forceinline__ uint32_t epi_mix(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du;
@@ -83,6 +94,60 @@ __device__ __forceinline__ void epi_draw(uint64_t seed, uint32_t h, uint32_t m, 
     }
 }
 
+// The front end of a minimal-sample kernel, one thread per sample h of pair p: the K draws of the pair's pool (progressive: the first
+// max(K, ceil(n (h + 1) / H)) matches) go to the sample's row of sample_idx (if given) and their points, normalised if norm is given,
+// to l0 .. r1.  EPI_SAMPLE_SHORT: the pair has fewer than K matches (workgroup-uniform), the row is -1 and nothing was drawn
+enum EpiSample { EPI_SAMPLE_SHORT, EPI_SAMPLE_NOT_FINITE, EPI_SAMPLE_READY };
+
+template <int K, class T>
+__device__ __forceinline__ EpiSample epi_sample(const float* __restrict__ ml_, const float* __restrict__ mr_,
+                                                const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride,
+                                                int64_t cap, const int64_t* __restrict__ pair_seed, const float* __restrict__ norm,
+                                                int progressive, int32_t* __restrict__ sample_idx, int64_t p, int h, int H, T (&l0)[K],
+                                                T (&l1)[K], T (&r0)[K], T (&r1)[K]) {
+    int64_t lo;
+    uint32_t n;
+    epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
+    int32_t* so = sample_idx ? sample_idx + (p * H + h) * K : nullptr;
+    if (n < K) {
+        if (so) {
+#pragma unroll
+            for (int t = 0; t < K; ++t) so[t] = -1;
+        }
+        return EPI_SAMPLE_SHORT;
+    }
+    uint32_t m = n;                                     // the pool: K <= m <= n
+    if (progressive) {
+        const int64_t q = ((int64_t)n * (h + 1) + H - 1) / H;
+        m = q < K ? (uint32_t)K : (q > (int64_t)n ? n : (uint32_t)q);
+    }
+    uint32_t idx[K];                                    // the draws in draw order
+    epi_draw<K>((uint64_t)pair_seed[p], (uint32_t)h, m, idx);
+    if (so) {
+#pragma unroll
+        for (int t = 0; t < K; ++t) so[t] = (int32_t)idx[t];
+    }
+    const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
+    const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
+    const EpiNorm nm = epi_norm(norm, p);
+    float2 xl[K], xr[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) { xl[t] = ml[idx[t]]; xr[t] = mr[idx[t]]; }    // idx < m <= n: inside the segment
+    __builtin_amdgcn_sched_barrier(0);                  // all 2 K loads are in flight before the first is waited for
+    bool finite = true;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        float2 a = xl[t], c = xr[t];
+        if (norm) {                                     // one subtract, one multiply (no contraction: -ffp-contract=off)
+            a.x = (a.x - nm.c0l) * nm.s0l; a.y = (a.y - nm.c1l) * nm.s1l;
+            c.x = (c.x - nm.c0r) * nm.s0r; c.y = (c.y - nm.c1r) * nm.s1r;
+        }
+        finite = finite && __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(c.x) && __builtin_isfinite(c.y);
+        l0[t] = (T)a.x; l1[t] = (T)a.y; r0[t] = (T)c.x; r1[t] = (T)c.y;
+    }
+    return finite ? EPI_SAMPLE_READY : EPI_SAMPLE_NOT_FINITE;
+}
+
 // ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name) ------
 // PATS_REQUIRE_PTR / PATS_REQUIRE_ALIGNED for a host function that serves several entry points: `who` is a variable in scope
 #define EPI_REQUIRE_ALIGNED(ptr, align) PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "%s: " #ptr " must be " #align "-byte aligned", who)
@@ -109,6 +174,47 @@ inline int epi_check_segments(const char* what, const int64_t* pair_off, const i
 inline int epi_check_h(const char* what, int64_t H) {
     PATS_REQUIRE(H >= 1 && H <= pats_epipolar_max_h(), "%s: H = %lld (1 .. max_h = %lld)", what, (long long)H,
                  (long long)pats_epipolar_max_h());
+    return PATS_OK;
+}
+
+// what the minimal-sample generators check alike (models_per_sample = 1, 10 or 3 slots; n_models is null where the entry has none);
+// chunks = the workgroups of `threads` samples per pair
+inline int epi_check_hypotheses(const char* who, const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed, const float* norm,
+                                int progressive, const float* models, const int32_t* sample_idx, const int32_t* n_models,
+                                int models_per_sample, int threads, int64_t& chunks) {
+    EPI_REQUIRE_PTR(matches_l, 8);
+    EPI_REQUIRE_PTR(matches_r, 8);
+    EPI_REQUIRE_PTR(pair_seed, 8);
+    EPI_REQUIRE_PTR(models, 4);
+    EPI_REQUIRE_ALIGNED(norm, 4);                       // optional pointers: null is aligned
+    EPI_REQUIRE_ALIGNED(sample_idx, 4);
+    EPI_REQUIRE_ALIGNED(n_models, 4);
+    EPI_REQUIRE_ALIGNED(pair_off, 8);
+    EPI_REQUIRE_ALIGNED(counts_in, 8);
+    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_h(who, H);
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(H <= pats_epipolar_max_h() / models_per_sample, "%s: H = %lld gives %d H = %lld models (<= max_h = %lld)", who,
+                 (long long)H, models_per_sample, (long long)(H * models_per_sample), (long long)pats_epipolar_max_h());
+    PATS_REQUIRE(progressive == 0 || progressive == 1, "%s: progressive = %d must be 0 or 1", who, progressive);
+    chunks = ceil_div(H, threads);
+    PATS_REQUIRE(chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld workgroups (< 2^31)", who, (long long)pairs,
+                 (long long)pairs, (long long)chunks);
+    return PATS_OK;
+}
+
+// the source of a refit - moments, or models and best - and its frame flag.  With moments the kernels get no models: models is
+// nulled and H set to 1, the launch's arguments
+inline int epi_check_refit_source(const char* who, const double* moments, const float*& models, const int32_t* best, int64_t& H, int swapped) {
+    PATS_REQUIRE(swapped == 0 || swapped == 1, "%s: swapped = %d must be 0 or 1", who, swapped);
+    PATS_REQUIRE(moments || (models && best), "%s: the refit needs moments, or models and best (the winning model)", who);
+    if (models) {
+        const int rc = epi_check_h(who, H);
+        if (rc != PATS_OK) return rc;
+    }
+    if (moments) { models = nullptr; H = 1; }
     return PATS_OK;
 }
 

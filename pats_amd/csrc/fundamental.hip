@@ -28,31 +28,15 @@ fundamental_refit_kernel(const int64_t* __restrict__ best_count, const double* _
     const bool live = best_count[p] >= FUND_MIN_INLIERS;    // workgroup-uniform
     if (tid == 0) { s_bad = 0; s_rot = 0; }
     wg_barrier();
-    if (live && moments) {                              // workgroup-uniform
-        for (int q = tid; q < 81; q += FUND_REFIT_THREADS) {
-            const int i = q / 9, j = q - 9 * i;
-            const double v = moments[p * 81 + (i < j ? i * 9 + j : j * 9 + i)];    // the upper triangle: symmetric whatever is stored
-            sA[i][j] = v;
-            sV[i][j] = i == j ? 1.0 : 0.0;
-            if (!__builtin_isfinite(v)) s_bad = 1;      // the same value from every writer
-        }
-        wg_barrier();
-        jacobi9_sweeps(sA, sV, s_rot, tid, (tid & 15) < 9, s_bad != 0, FUND_SWEEPS);
-    }
+    if (live && moments)                                // workgroup-uniform
+        refit_solve<FUND_REFIT_THREADS>(moments, p, sA, sV, s_bad, s_rot, tid, (tid & 15) < 9, FUND_SWEEPS);
     wg_barrier();
     if (tid != 0) return;
-    double e[9] = {}, F[9] = {}, sig[3] = {}, ev[2] = {0.0, 0.0};
-    bool ok = live && s_bad == 0;
-    if (ok && moments) {
-        ok = fund_from_moments(sA, sV, e, ev, F, sig);
-    } else if (ok) {
-        int h = best[p];
-        h = h < 0 ? 0 : (h >= H ? H - 1 : h);
-        const float* m = models + (p * H + h) * 9;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { e[k] = (double)m[k]; ok = ok && __builtin_isfinite(e[k]); }
-        ok = ok && fund_project(e, F, sig);             // the zero model has rank 0: no model
-    }
+    double e[9] = {}, F[9] = {}, sig[3] = {}, ev[2] = {0.0, 0.0}, lmin;
+    int m;
+    bool ok = refit_source(live && s_bad == 0, moments, sA, sV, models, H, best, p, e, m, lmin);
+    if (ok && moments) ok = refit_spectrum(sA, m, lmin, ev);
+    ok = ok && fund_project(e, F, sig);                 // the zero model has rank 0: no model
     hom_write(F, ok, swapped, F_out + p * 9);
     eig_out[p * 2] = ok ? ev[0] : 0.0;
     eig_out[p * 2 + 1] = ok ? ev[1] : 0.0;
@@ -67,29 +51,18 @@ fundamental_refit_kernel(const int64_t* __restrict__ best_count, const double* _
     bool okp = ok;
     if (ok) {
         const EpiNorm nm = epi_norm(norm, p);           // float32, widened exactly; the identity without norm
-        const double c0l = nm.c0l, c1l = nm.c1l, s0l = nm.s0l, s1l = nm.s1l, c0r = nm.c0r, c1r = nm.c1r, s0r = nm.s0r, s1r = nm.s1r;
+        const double s0l = nm.s0l, s1l = nm.s1l, c0r = nm.c0r, c1r = nm.c1r, s0r = nm.s0r, s1r = nm.s1r;
         if (norm) {
             double q[9];                                // F N_l
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                q[3 * i] = F[3 * i] * s0l;
-                q[3 * i + 1] = F[3 * i + 1] * s1l;
-                q[3 * i + 2] = F[3 * i + 2] - (F[3 * i] * (c0l * s0l) + F[3 * i + 1] * (c1l * s1l));
-            }
+            refit_times_nl(F, nm.c0l, nm.c1l, s0l, s1l, q);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {               // N_r^T (F N_l),  N_r^T = [[s0, 0, 0], [0, s1, 0], [-c0 s0, -c1 s1, 1]]
                 g[j] = s0r * q[j];
                 g[3 + j] = s1r * q[3 + j];
                 g[6 + j] = q[6 + j] - ((c0r * s0r) * q[j] + (c1r * s1r) * q[3 + j]);
             }
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) s += g[k] * g[k];
-            const double inv = 1.0 / __builtin_sqrt(s);
             // a zero scale makes N singular: not a change of coordinates, no F_px
-            okp = s > 0.0 && s0l != 0.0 && s1l != 0.0 && s0r != 0.0 && s1r != 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) { g[k] *= inv; okp = okp && __builtin_isfinite(g[k]); }
+            okp = refit_unit(g) && s0l != 0.0 && s1l != 0.0 && s0r != 0.0 && s1r != 0.0;
         } else {
 #pragma unroll
             for (int k = 0; k < 9; ++k) g[k] = F[k];
@@ -123,14 +96,10 @@ extern "C" int pats_fundamental_refit_by_pair_f64(const int64_t* best_count, con
     PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", F_px, 8);
     PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", f_refit, 8);
     PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "fundamental_refit_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(swapped == 0 || swapped == 1, "fundamental_refit_by_pair: swapped = %d must be 0 or 1", swapped);
-    PATS_REQUIRE(moments || (models && best), "fundamental_refit_by_pair: the refit needs moments, or models and best (the winning model)");
-    if (models) {
-        const int rc = epi_check_h("fundamental_refit_by_pair", H);
-        if (rc != PATS_OK) return rc;
-    }
+    const int rc = epi_check_refit_source("fundamental_refit_by_pair", moments, models, best, H, swapped);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(workspace_bytes >= pats_fundamental_refit_workspace_bytes(pairs), "fundamental_refit_by_pair: workspace too small");
     hipLaunchKernelGGL(fundamental_refit_kernel, dim3((unsigned)pairs), dim3(FUND_REFIT_THREADS), 0, as_stream(stream), best_count, moments,
-                       moments ? nullptr : models, moments ? 1 : (int)H, best, norm, swapped, F, F_px, eig, sigma, f_refit);
+                       models, (int)H, best, norm, swapped, F, F_px, eig, sigma, f_refit);
     return check_launch("fundamental_refit kernel");
 }

@@ -26,34 +26,14 @@ homography_refit_kernel(const int64_t* __restrict__ best_count, const double* __
     const bool live = best_count[p] >= HOM_MIN_INLIERS; // workgroup-uniform
     if (tid == 0) { s_bad = 0; s_rot = 0; }
     wg_barrier();
-    if (live && moments) {                              // workgroup-uniform
-        for (int q = tid; q < 81; q += HOM_REFIT_THREADS) {
-            const int i = q / 9, j = q - 9 * i;
-            const double v = moments[p * 81 + (i < j ? i * 9 + j : j * 9 + i)];    // the upper triangle: symmetric whatever is stored
-            sA[i][j] = v;
-            sV[i][j] = i == j ? 1.0 : 0.0;
-            if (!__builtin_isfinite(v)) s_bad = 1;      // the same value from every writer
-        }
-        wg_barrier();
-        jacobi9_sweeps(sA, sV, s_rot, tid, (tid & 15) < 9, s_bad != 0, HOM_SWEEPS);
-    }
+    if (live && moments)                                // workgroup-uniform
+        refit_solve<HOM_REFIT_THREADS>(moments, p, sA, sV, s_bad, s_rot, tid, (tid & 15) < 9, HOM_SWEEPS);
     wg_barrier();
     if (tid != 0) return;
-    double e[9], ev[2] = {0.0, 0.0};
-    bool ok = live && s_bad == 0;
-    if (ok && moments) {
-        double lmin;
-        const int m = refit_eigvec(sA, sV, e, lmin);
-        const double lsec = refit_second(sA, m);
-        ev[0] = lmin; ev[1] = lsec;
-        ok = __builtin_isfinite(lmin) && __builtin_isfinite(lsec);
-    } else if (ok) {
-        int h = best[p];
-        h = h < 0 ? 0 : (h >= H ? H - 1 : h);
-        const float* m = models + (p * H + h) * 9;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) e[k] = (double)m[k];
-    }
+    double e[9], ev[2] = {0.0, 0.0}, lmin;
+    int m;
+    bool ok = refit_source(live && s_bad == 0, moments, sA, sV, models, H, best, p, e, m, lmin);
+    if (ok && moments) ok = refit_spectrum(sA, m, lmin, ev);
     if (ok) {
         bool any = false;
 #pragma unroll
@@ -68,28 +48,17 @@ homography_refit_kernel(const int64_t* __restrict__ best_count, const double* __
     bool okp = ok;
     if (ok) {
         const EpiNorm nm = epi_norm(norm, p);           // float32, widened exactly; the identity without norm
-        const double c0l = nm.c0l, c1l = nm.c1l, s0l = nm.s0l, s1l = nm.s1l, c0r = nm.c0r, c1r = nm.c1r, s0r = nm.s0r, s1r = nm.s1r;
+        const double c0r = nm.c0r, c1r = nm.c1r, s0r = nm.s0r, s1r = nm.s1r;
         if (norm) {
             double q[9];                                // H N_l
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                q[3 * i] = e[3 * i] * s0l;
-                q[3 * i + 1] = e[3 * i + 1] * s1l;
-                q[3 * i + 2] = e[3 * i + 2] - (e[3 * i] * (c0l * s0l) + e[3 * i + 1] * (c1l * s1l));
-            }
+            refit_times_nl(e, nm.c0l, nm.c1l, nm.s0l, nm.s1l, q);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {               // N_r^-1 (H N_l),  N_r^-1 = [[1/s0, 0, c0], [0, 1/s1, c1], [0, 0, 1]]
                 g[j] = q[j] / s0r + c0r * q[6 + j];
                 g[3 + j] = q[3 + j] / s1r + c1r * q[6 + j];
                 g[6 + j] = q[6 + j];
             }
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) s += g[k] * g[k];
-            const double inv = 1.0 / __builtin_sqrt(s);
-            okp = s > 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) { g[k] *= inv; okp = okp && __builtin_isfinite(g[k]); }
+            okp = refit_unit(g);
         } else {
 #pragma unroll
             for (int k = 0; k < 9; ++k) g[k] = e[k];
@@ -121,14 +90,10 @@ extern "C" int pats_homography_refit_by_pair_f64(const int64_t* best_count, cons
     PATS_REQUIRE_ALIGNED("homography_refit_by_pair", norm, 4);
     PATS_REQUIRE_ALIGNED("homography_refit_by_pair", H_px, 8);
     PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "homography_refit_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(swapped == 0 || swapped == 1, "homography_refit_by_pair: swapped = %d must be 0 or 1", swapped);
-    PATS_REQUIRE(moments || (models && best), "homography_refit_by_pair: the refit needs moments, or models and best (the winning model)");
-    if (models) {
-        const int rc = epi_check_h("homography_refit_by_pair", H);
-        if (rc != PATS_OK) return rc;
-    }
+    const int rc = epi_check_refit_source("homography_refit_by_pair", moments, models, best, H, swapped);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(workspace_bytes >= pats_homography_refit_workspace_bytes(pairs), "homography_refit_by_pair: workspace too small");
     hipLaunchKernelGGL(homography_refit_kernel, dim3((unsigned)pairs), dim3(HOM_REFIT_THREADS), 0, as_stream(stream), best_count, moments,
-                       moments ? nullptr : models, moments ? 1 : (int)H, best, norm, swapped, H_out, H_px, eig);
+                       models, (int)H, best, norm, swapped, H_out, H_px, eig);
     return check_launch("homography_refit kernel");
 }

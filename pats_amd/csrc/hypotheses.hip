@@ -5,7 +5,7 @@
 //
 //   one THREAD per hypothesis, 64 threads per workgroup, grid = pairs x ceil(H / 64).  Everything a thread holds is indexed
 //   statically (every loop below is unrolled to constants), so the 9x8 matrix lives in registers: no scratch, no LDS.
-//   sampler  K draws without replacement and without a rejection loop (epi_draw of epipolar.hpp, shared with hypotheses5.hip)
+//   sampler  K draws without replacement and without a rejection loop (epi_sample of epipolar.hpp, the front end of every generator)
 //   solve    null_vector_9x8 of nullvec9x8.hpp: Householder QR of A^T and one step of iterative refinement.  The plain QR vector
 //            alone sits at ~1.1 eps32 |A|_F in the worst of 2100 8-point samples; with the step at ~0.2 (docs/parity.md)
 //   family   a struct with the sample size K, fill (A^T from the draws) and residual (column j of A^T times z through the factored
@@ -81,55 +81,18 @@ hypotheses_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_, 
     const int64_t p = (int64_t)(b / (uint32_t)chunks);
     const int h = (int)(b % (uint32_t)chunks) * HYP_THREADS + (int)threadIdx.x;
     if (h >= H) return;
-    int64_t lo;
-    uint32_t n;
-    epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
     float* mo = models + (p * H + h) * 9;
-    int32_t* so = sample_idx ? sample_idx + (p * H + h) * K : nullptr;
-    if (n < K) {                                        // workgroup-uniform: the zero model, no sample
-#pragma unroll
-        for (int k = 0; k < 9; ++k) mo[k] = 0.0f;
-        if (so) {
-#pragma unroll
-            for (int t = 0; t < K; ++t) so[t] = -1;
-        }
-        return;
-    }
-    uint32_t m = n;                                     // the pool: K <= m <= n
-    if (progressive) {
-        const int64_t q = ((int64_t)n * (h + 1) + H - 1) / H;
-        m = q < K ? (uint32_t)K : (q > (int64_t)n ? n : (uint32_t)q);
-    }
-    uint32_t idx[K];                                    // the draws in draw order (epipolar.hpp: the sampler)
-    epi_draw<K>((uint64_t)pair_seed[p], (uint32_t)h, m, idx);
-    if (so) {
-#pragma unroll
-        for (int t = 0; t < K; ++t) so[t] = (int32_t)idx[t];
-    }
-
-    const float2* ml = reinterpret_cast<const float2*>(ml_) + lo;
-    const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
-    const EpiNorm nm = epi_norm(norm, p);
     float l0[K], l1[K], r0[K], r1[K];
-    bool finite = true;
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-        float2 a = ml[idx[t]], c = mr[idx[t]];          // idx < m <= n: inside the segment
-        if (norm) {                                     // one subtract, one multiply (no contraction: -ffp-contract=off)
-            a.x = (a.x - nm.c0l) * nm.s0l; a.y = (a.y - nm.c1l) * nm.s1l;
-            c.x = (c.x - nm.c0r) * nm.s0r; c.y = (c.y - nm.c1r) * nm.s1r;
-        }
-        finite = finite && __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(c.x) && __builtin_isfinite(c.y);
-        l0[t] = a.x; l1[t] = a.y; r0[t] = c.x; r1[t] = c.y;
-    }
+    const EpiSample drawn = epi_sample<K>(ml_, mr_, pair_off, counts_in, stride, cap, pair_seed, norm, progressive, sample_idx, p, h, H, l0,
+                                          l1, r0, r1);
     float e[9];
     bool ok = false;
-    if (finite) {
+    if (drawn == EPI_SAMPLE_READY) {
         float M[9][8];
         F::fill(M, l0, l1, r0, r1);
         ok = null_vector_9x8(M, [&](const float (&z)[9], int j) { return F::residual(z, l0, l1, r0, r1, j); }, e);
     }
-    if (!ok) {
+    if (!ok) {                                          // a short pair, a non-finite coordinate or vector: the zero model
 #pragma unroll
         for (int k = 0; k < 9; ++k) mo[k] = 0.0f;
         return;
@@ -154,22 +117,10 @@ template <class F>
 static int hypotheses_by_pair(const char* who, const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
                               const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed, const float* norm,
                               int progressive, float* models, int32_t* sample_idx, pats_stream_t stream) {
-    EPI_REQUIRE_PTR(matches_l, 8);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(pair_seed, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_ALIGNED(norm, 4);                       // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(sample_idx, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int64_t chunks;
+    const int rc = epi_check_hypotheses(who, matches_l, matches_r, pair_off, stride, counts_in, pairs, cap, H, pair_seed, norm, progressive,
+                                        models, sample_idx, nullptr, 1, HYP_THREADS, chunks);
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, H);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(progressive == 0 || progressive == 1, "%s: progressive = %d must be 0 or 1", who, progressive);
-    const int64_t chunks = ceil_div(H, HYP_THREADS);
-    PATS_REQUIRE(chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld workgroups (< 2^31)", who, (long long)pairs,
-                 (long long)pairs, (long long)chunks);
     hipLaunchKernelGGL(hypotheses_kernel<F>, dim3((unsigned)(pairs * chunks)), dim3(HYP_THREADS), 0, as_stream(stream), matches_l,
                        matches_r, pair_off, counts_in, stride, cap, (int)chunks, (int)H, pair_seed, norm, progressive, models, sample_idx);
     return check_launch(F::KERNEL);

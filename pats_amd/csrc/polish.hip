@@ -139,11 +139,7 @@ verify_polish_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
             polish_stage[i] = float4{l0, l1, r0, r1};
         }
     }
-    if (tid < 9) {
-        int h = best ? best[p] : 0;
-        h = h < 0 ? 0 : (h >= H ? H - 1 : h);
-        s_model[tid] = models[(p * H + h) * 9 + tid];
-    }
+    if (tid < 9) s_model[tid] = epi_winner(models, H, best ? best[p] : 0, p)[tid];     // a null best: H == 1
     wg_barrier();
 
     int best_c = -1, best_r = 0;                        // workgroup-uniform: every thread computes every count

@@ -53,34 +53,12 @@ homography_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ 
     wg_barrier();
 
     // ---- solve: the refit and its spectrum -----------------------------------------------------------------------------------------
-    if (live && moments) {                              // workgroup-uniform
-        if (tid < 81) {
-            const int i = tid / 9, j = tid - 9 * i;
-            const double v = moments[p * 81 + (i < j ? i * 9 + j : j * 9 + i)];    // the upper triangle: symmetric whatever is stored
-            sA[i][j] = v;
-            sV[i][j] = i == j ? 1.0 : 0.0;
-            if (!__builtin_isfinite(v)) s_bad = 1;      // the same value from every writer
-        }
-        wg_barrier();
-        jacobi9_sweeps(sA, sV, s_rot, tid, tid < 64 && (tid & 15) < 9, s_bad != 0, HOM_SWEEPS);
-    }
+    if (live && moments)                                // workgroup-uniform
+        refit_solve<HPOSE_THREADS>(moments, p, sA, sV, s_bad, s_rot, tid, tid < 64 && (tid & 15) < 9, HOM_SWEEPS);
     if (tid == 0) {
-        double e[9];
-        bool ok = live && s_bad == 0;
-        if (ok && moments) {
-            double lmin;
-            refit_eigvec(sA, sV, e, lmin);
-        } else if (ok) {
-            int h = best[p];
-            h = h < 0 ? 0 : (h >= H ? H - 1 : h);
-            const float* m = models + (p * H + h) * 9;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) e[k] = (double)m[k];
-        }
-        if (ok) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) ok = ok && __builtin_isfinite(e[k]);
-        }
+        double e[9], lmin;
+        int m;
+        bool ok = refit_source(live && s_bad == 0, moments, sA, sV, models, H, best, p, e, m, lmin);
         double Gp[9], V[3][3], l1 = 1.0, l3 = 1.0;
         if (ok) ok = hom_spectrum(e, Gp, V, l1, l3);
         if (ok) {
@@ -370,12 +348,8 @@ extern "C" int pats_homography_pose_by_pair_f64(const float* matches_l, const fl
                  "homography_pose_by_pair: cand_R, cand_t and cand_n must be given together");
     int rc = epi_check_segments("homography_pose_by_pair", pair_off, counts_in, stride, pairs, cap);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(swapped == 0 || swapped == 1, "homography_pose_by_pair: swapped = %d must be 0 or 1", swapped);
-    PATS_REQUIRE(moments || (models && best), "homography_pose_by_pair: the refit needs moments, or models and best (the winning model)");
-    if (models) {
-        rc = epi_check_h("homography_pose_by_pair", H);
-        if (rc != PATS_OK) return rc;
-    }
+    rc = epi_check_refit_source("homography_pose_by_pair", moments, models, best, H, swapped);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(min_baseline >= 0.0, "homography_pose_by_pair: min_baseline = %g must be a number >= 0", min_baseline);     // false for a NaN
     PATS_REQUIRE(workspace_bytes >= pats_homography_pose_workspace_bytes(pairs, cap), "homography_pose_by_pair: workspace too small");
     hipStream_t st = as_stream(stream);
@@ -384,7 +358,7 @@ extern "C" int pats_homography_pose_by_pair_f64(const float* matches_l, const fl
         if (rc != PATS_OK) return rc;
     }
     hipLaunchKernelGGL(homography_pose_kernel, dim3((unsigned)pairs), dim3(HPOSE_THREADS), 0, st, matches_l, matches_r, inlier, pair_off,
-                       counts_in, stride, cap, best_count, moments, moments ? nullptr : models, moments ? 1 : (int)H, best, norm, thr, swapped,
+                       counts_in, stride, cap, best_count, moments, models, (int)H, best, norm, thr, swapped,
                        min_baseline, E, R, t, n, baseline, vis, sup, choice, status, front_count, cand_R, cand_t, cand_n, front);
     return check_launch("homography_pose kernel");
 }

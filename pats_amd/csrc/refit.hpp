@@ -1,9 +1,11 @@
-// What the least-squares refits share (pose.hip: the pose; homography.hip: the homography refit; fundamental.hip: the rank-2 refit;
-// polish.hip: the local optimisation's refit of every family): the pick of the eigenvector behind jacobi9.hpp's sweeps, the projection
-// onto the essential matrices with its decompositions, the rank-2 truncation, and the homography's permutation and sign rule.
-// include/pats_amd.h states the definitions.
+// What the least-squares refits share (pose.hip, pose_h.hip: the poses; homography.hip: the homography refit; fundamental.hip: the
+// rank-2 refit; polish.hip: the local optimisation's refit of every family): the refit source - the eigenvector of a pair's moments
+// behind jacobi9.hpp's sweeps, or the winning model -, the projection onto the essential matrices with its decompositions, the rank-2
+// truncation, the denormalisation's shared steps, and the homography's permutation and sign rule.  include/pats_amd.h states the
+// definitions.
 #pragma once
 #include "common.hpp"
+#include "epipolar.hpp"
 #include "jacobi9.hpp"
 
 namespace pats {
@@ -42,6 +44,73 @@ __device__ __forceinline__ double refit_second(const double (&sA)[9][9], int m) 
         if (k != m && l < lsec) { lsec = l; m2 = k; }
     }
     return lsec;
+}
+
+// the two smallest eigenvalues behind refit_eigvec (its index m and lmin); false: one of them is not finite
+__device__ __forceinline__ bool refit_spectrum(const double (&sA)[9][9], int m, double lmin, double (&ev)[2]) {
+    ev[0] = lmin; ev[1] = refit_second(sA, m);
+    return __builtin_isfinite(ev[0]) && __builtin_isfinite(ev[1]);
+}
+
+// ---- the refit source of pose.hip, pose_h.hip, homography.hip and fundamental.hip: moments, or models and best ------------------
+// The workgroup's part: moments[p] (its upper triangle: symmetric whatever is stored) into sA, sV = I, s_bad raised by a moment that
+// is not finite, then the sweeps.  EVERY thread of the THREADS of the workgroup calls it, under a workgroup-uniform condition and
+// behind the barrier that follows the clearing of s_bad and s_rot; mine and sweeps are jacobi9_sweeps'
+template <int THREADS>
+__device__ __forceinline__ void refit_solve(const double* __restrict__ moments, int64_t p, double (&sA)[9][9], double (&sV)[9][9], int& s_bad,
+                                            int& s_rot, int tid, bool mine, int sweeps) {
+    for (int q = tid; q < 81; q += THREADS) {
+        const int i = q / 9, j = q - 9 * i;
+        const double v = moments[p * 81 + (i < j ? i * 9 + j : j * 9 + i)];
+        sA[i][j] = v;
+        sV[i][j] = i == j ? 1.0 : 0.0;
+        if (!__builtin_isfinite(v)) s_bad = 1;          // the same value from every writer
+    }
+    wg_barrier();
+    jacobi9_sweeps(sA, sV, s_rot, tid, mine, s_bad != 0, sweeps);
+}
+
+// One thread's part, behind refit_solve and a barrier: e = the refit of the moments (m and lmin: refit_eigvec's, for refit_spectrum) or,
+// without moments, the winner of models promoted.  ok: the pair is live and no moment was bad; returns ok and nine finite values
+__device__ __forceinline__ bool refit_source(bool ok, const double* __restrict__ moments, const double (&sA)[9][9], const double (&sV)[9][9],
+                                             const float* __restrict__ models, int H, const int32_t* __restrict__ best, int64_t p,
+                                             double (&e)[9], int& m, double& lmin) {
+    m = 0;
+    lmin = 0.0;
+    if (ok && moments) {
+        m = refit_eigvec(sA, sV, e, lmin);
+    } else if (ok) {
+        const float* w = epi_winner(models, H, best, p);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) e[k] = (double)w[k];
+    }
+    if (ok) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) ok = ok && __builtin_isfinite(e[k]);
+    }
+    return ok;
+}
+
+// q = X N_l for a row-major 3x3 X and the left points' normalisation N_l = [[s0, 0, -c0 s0], [0, s1, -c1 s1], [0, 0, 1]]
+__device__ __forceinline__ void refit_times_nl(const double (&x)[9], double c0l, double c1l, double s0l, double s1l, double (&q)[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        q[3 * i] = x[3 * i] * s0l;
+        q[3 * i + 1] = x[3 * i + 1] * s1l;
+        q[3 * i + 2] = x[3 * i + 2] - (x[3 * i] * (c0l * s0l) + x[3 * i + 1] * (c1l * s1l));
+    }
+}
+
+// g rescaled to Frobenius norm 1; false: g is zero or a value is not finite - no model
+__device__ __forceinline__ bool refit_unit(double (&g)[9]) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s += g[k] * g[k];
+    const double inv = 1.0 / __builtin_sqrt(s);
+    bool ok = s > 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { g[k] *= inv; ok = ok && __builtin_isfinite(g[k]); }
+    return ok;
 }
 
 template <int P, int Q>

@@ -1649,6 +1649,23 @@ def _bp_norm(fn, norm, pairs):
     return norm
 
 
+def _bp_refit_source(fn, pairs, moments, models, best):
+    """The source of a refit -> (moments, models, best, H): moments as a GPU [pairs,9,9] float64 tensor and no models (H = 1), or,
+    without moments, models [pairs,H,3,3] and best [pairs]."""
+    if moments is not None:
+        moments = _dev(moments, "moments", torch.float64)
+        if tuple(moments.shape) != (pairs, 9, 9):
+            raise RuntimeError("%s: moments must be [pairs,9,9]" % fn)
+        return moments, None, None, 1
+    models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
+        raise RuntimeError("%s: models must be [pairs,H,3,3] and best [pairs]" % fn)
+    H = int(models.shape[1])
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    return moments, models, best, H
+
+
 def _bp_outputs(fn, want, out, dev, lone=False):
     """The destinations `want` = [(name, dtype, shape)] describes: allocated when out is None, else out checked against it.
     lone: a tensor is taken as the 1-tuple of it."""
@@ -1771,8 +1788,10 @@ def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr
     return out
 
 
-def _hypotheses_by_pair(fn, K, entry, workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm, progressive, return_samples, out, pairs):
-    """What the 8-point and the 4-point generator share - everything but the sample size K, the C entry and its workspace query."""
+def _hypotheses_by_pair(fn, K, slots, entry, workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm, progressive,
+                        return_samples, return_counts, out, pairs):
+    """What the minimal-sample generators share - everything but the sample size K, the model slots per sample (1, or the 10 and 3
+    of the 5- and 7-point generators, whose entries also take n_models), the C entry and its workspace query."""
     _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
                     (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
     _bp_one_form(fn, pair_off, stride, counts)
@@ -1784,21 +1803,28 @@ def _hypotheses_by_pair(fn, K, entry, workspace_bytes, matches_l, matches_r, H, 
     seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if seed.numel() != pairs:
         raise RuntimeError("%s: seed must hold one int64 per pair (%d), got %d" % (fn, pairs, seed.numel()))
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    if not 1 <= H <= epipolar_max_h() // slots:
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d%s" % (fn, H, epipolar_max_h() // slots, " (%d H models)" % slots if slots > 1 else ""))
     norm = _bp_norm(fn, norm, pairs)
     dev = ml.device
-    want = [("models", torch.float32, (pairs, H, 3, 3))]
+    want = [("models", torch.float32, (pairs, H, 3, 3) if slots == 1 else (pairs, H, slots, 3, 3))]
     if return_samples:
         want.append(("sample_idx", torch.int32, (pairs, H, K)))
+    if return_counts:
+        want.append(("n_models", torch.int32, (pairs, H)))
     out = _bp_outputs(fn, want, out, dev, lone=True)
     nws = workspace_bytes(pairs, H)
     ws = _workspace(nws, dev) if nws else None
     if cap == 0:
         ml = mr = _bp_placeholder(dev)
-    _check(entry(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0, _ptr(out[0]),
-                 _ptr(out[1]) if return_samples else None, _ptr(ws), nws, _stream()), fn)
-    return out if return_samples else out[0]
+    samples = _ptr(out[1]) if return_samples else None
+    if slots == 1:                                        # the 8- and 4-point entries have no n_models
+        _check(entry(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0,
+                     _ptr(out[0]), samples, _ptr(ws), nws, _stream()), fn)
+    else:
+        _check(entry(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0,
+                     _ptr(out[0]), samples, _ptr(out[-1]) if return_counts else None, _ptr(ws), nws, _stream()), fn)
+    return out if len(out) > 1 else out[0]
 
 
 def epipolar_max_h():
@@ -1856,9 +1882,9 @@ def epipolar_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, st
     Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 8 matches and for a sample with a non-finite
     coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,8] int32: the draws as positions inside the pair's
     list, -1 for a pair with fewer than 8 matches).  out: the destination(s), a tensor or a tuple."""
-    return _hypotheses_by_pair("epipolar_hypotheses_by_pair", 8, _L().pats_epipolar_hypotheses_by_pair_f32,
+    return _hypotheses_by_pair("epipolar_hypotheses_by_pair", 8, 1, _L().pats_epipolar_hypotheses_by_pair_f32,
                                _L().pats_epipolar_hypotheses_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
-                               progressive, return_samples, out, pairs)
+                               progressive, return_samples, False, out, pairs)
 
 
 def epipolar_hypotheses5_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
@@ -1874,36 +1900,9 @@ def epipolar_hypotheses5_by_pair(matches_l, matches_r, H, seed, pair_off=None, s
     (models[, sample_idx [pairs,H,5] int32 with return_samples=True: the draws as positions inside the pair's list, -1 for a pair
     with fewer than 5 matches][, n_models [pairs,H] int32 with return_counts=True: the non-zero slots]).  out: the destination(s), a
     tensor or a tuple in that order."""
-    fn = "epipolar_hypotheses5_by_pair"
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
-                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if not isinstance(seed, torch.Tensor):
-        raise RuntimeError("epipolar_hypotheses5_by_pair: seed must be an int64 GPU tensor [pairs]")
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    H = int(H)
-    seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if seed.numel() != pairs:
-        raise RuntimeError("epipolar_hypotheses5_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
-    if not 1 <= H <= epipolar_max_h() // 10:
-        raise RuntimeError("epipolar_hypotheses5_by_pair: H = %d, must lie in 1 .. %d (10 H models)" % (H, epipolar_max_h() // 10))
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("models", torch.float32, (pairs, H, 10, 3, 3))]
-    if return_samples:
-        want.append(("sample_idx", torch.int32, (pairs, H, 5)))
-    if return_counts:
-        want.append(("n_models", torch.int32, (pairs, H)))
-    out = _bp_outputs(fn, want, out, dev, lone=True)
-    nws = _L().pats_epipolar_hypotheses5_workspace_bytes(pairs, H)
-    ws = _workspace(nws, dev) if nws else None
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-    _check(_L().pats_epipolar_hypotheses5_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
-                                                      1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
-                                                      _ptr(out[-1]) if return_counts else None, _ptr(ws), nws, _stream()), fn)
-    return out if len(out) > 1 else out[0]
+    return _hypotheses_by_pair("epipolar_hypotheses5_by_pair", 5, 10, _L().pats_epipolar_hypotheses5_by_pair_f32,
+                               _L().pats_epipolar_hypotheses5_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
+                               progressive, return_samples, return_counts, out, pairs)
 
 
 def epipolar_hypotheses7_by_pair(matches_l, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
@@ -1920,36 +1919,9 @@ def epipolar_hypotheses7_by_pair(matches_l, matches_r, H, seed, pair_off=None, s
     [pairs,H,7] int32 with return_samples=True: the draws as positions inside the pair's list, -1 for a pair with fewer than 7
     matches][, n_models [pairs,H] int32 with return_counts=True: the non-zero slots]).  out: the destination(s), a tensor or a tuple
     in that order."""
-    fn = "epipolar_hypotheses7_by_pair"
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
-                    (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if not isinstance(seed, torch.Tensor):
-        raise RuntimeError("epipolar_hypotheses7_by_pair: seed must be an int64 GPU tensor [pairs]")
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    H = int(H)
-    seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if seed.numel() != pairs:
-        raise RuntimeError("epipolar_hypotheses7_by_pair: seed must hold one int64 per pair (%d), got %d" % (pairs, seed.numel()))
-    if not 1 <= H <= epipolar_max_h() // 3:
-        raise RuntimeError("epipolar_hypotheses7_by_pair: H = %d, must lie in 1 .. %d (3 H models)" % (H, epipolar_max_h() // 3))
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("models", torch.float32, (pairs, H, 3, 3, 3))]
-    if return_samples:
-        want.append(("sample_idx", torch.int32, (pairs, H, 7)))
-    if return_counts:
-        want.append(("n_models", torch.int32, (pairs, H)))
-    out = _bp_outputs(fn, want, out, dev, lone=True)
-    nws = _L().pats_epipolar_hypotheses7_workspace_bytes(pairs, H)
-    ws = _workspace(nws, dev) if nws else None
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-    _check(_L().pats_epipolar_hypotheses7_by_pair_f32(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
-                                                      1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
-                                                      _ptr(out[-1]) if return_counts else None, _ptr(ws), nws, _stream()), fn)
-    return out if len(out) > 1 else out[0]
+    return _hypotheses_by_pair("epipolar_hypotheses7_by_pair", 7, 3, _L().pats_epipolar_hypotheses7_by_pair_f32,
+                               _L().pats_epipolar_hypotheses7_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
+                               progressive, return_samples, return_counts, out, pairs)
 
 
 def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
@@ -1981,19 +1953,7 @@ def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None
     seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if bc.numel() != pairs:
         raise RuntimeError("epipolar_pose_by_pair: best_count must hold one int64 per pair (%d), got %d" % (pairs, bc.numel()))
-    H = 1
-    if moments is not None:
-        moments = _dev(moments, "moments", torch.float64)
-        if tuple(moments.shape) != (pairs, 9, 9):
-            raise RuntimeError("epipolar_pose_by_pair: moments must be [pairs,9,9]")
-        models = best = None
-    else:
-        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
-        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
-            raise RuntimeError("epipolar_pose_by_pair: models must be [pairs,H,3,3] and best [pairs]")
-        H = int(models.shape[1])
-        if not 1 <= H <= epipolar_max_h():
-            raise RuntimeError("epipolar_pose_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    moments, models, best, H = _bp_refit_source(fn, pairs, moments, models, best)
     norm = _bp_norm(fn, norm, pairs)
     dev = ml.device
     want = [("E", torch.float64, (pairs, 3, 3)), ("R", torch.float64, (pairs, 3, 3)), ("t", torch.float64, (pairs, 3)),
@@ -2161,9 +2121,9 @@ def homography_hypotheses_by_pair(matches_l, matches_r, H, seed, pair_off=None, 
     Returns models [pairs,H,3,3] float32 - exact zeros for a pair with fewer than 4 matches and for a sample with a non-finite
     coordinate - or, with return_samples=True, (models, sample_idx [pairs,H,4] int32: the draws as positions inside the pair's
     list, -1 for a pair with fewer than 4 matches).  out: the destination(s), a tensor or a tuple."""
-    return _hypotheses_by_pair("homography_hypotheses_by_pair", 4, _L().pats_homography_hypotheses_by_pair_f32,
+    return _hypotheses_by_pair("homography_hypotheses_by_pair", 4, 1, _L().pats_homography_hypotheses_by_pair_f32,
                                _L().pats_homography_hypotheses_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
-                               progressive, return_samples, out, pairs)
+                               progressive, return_samples, False, out, pairs)
 
 
 def homography_score_by_pair(matches_l, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None,
@@ -2210,19 +2170,7 @@ def homography_refit_by_pair(best_count, moments=None, models=None, best=None, n
     pairs = int(bc.numel())
     if pairs < 1:
         raise RuntimeError("homography_refit_by_pair: best_count must hold one int64 per pair")
-    H = 1
-    if moments is not None:
-        moments = _dev(moments, "moments", torch.float64)
-        if tuple(moments.shape) != (pairs, 9, 9):
-            raise RuntimeError("homography_refit_by_pair: moments must be [pairs,9,9]")
-        models = best = None
-    else:
-        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
-        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
-            raise RuntimeError("homography_refit_by_pair: models must be [pairs,H,3,3] and best [pairs]")
-        H = int(models.shape[1])
-        if not 1 <= H <= epipolar_max_h():
-            raise RuntimeError("homography_refit_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    moments, models, best, H = _bp_refit_source(fn, pairs, moments, models, best)
     norm = _bp_norm(fn, norm, pairs)
     dev = bc.device
     want = [("H", torch.float64, (pairs, 3, 3)), ("eig", torch.float64, (pairs, 2))]
@@ -2273,19 +2221,7 @@ def homography_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=No
     seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if bc.numel() != pairs:
         raise RuntimeError("homography_pose_by_pair: best_count must hold one int64 per pair (%d), got %d" % (pairs, bc.numel()))
-    H = 1
-    if moments is not None:
-        moments = _dev(moments, "moments", torch.float64)
-        if tuple(moments.shape) != (pairs, 9, 9):
-            raise RuntimeError("homography_pose_by_pair: moments must be [pairs,9,9]")
-        models = best = None
-    else:
-        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
-        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
-            raise RuntimeError("homography_pose_by_pair: models must be [pairs,H,3,3] and best [pairs]")
-        H = int(models.shape[1])
-        if not 1 <= H <= epipolar_max_h():
-            raise RuntimeError("homography_pose_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    moments, models, best, H = _bp_refit_source(fn, pairs, moments, models, best)
     norm = _bp_norm(fn, norm, pairs)
     if thr is not None:
         thr = _dev(thr, "thr").reshape(-1)
@@ -2411,19 +2347,7 @@ def fundamental_refit_by_pair(best_count, moments=None, models=None, best=None, 
     pairs = int(bc.numel())
     if pairs < 1:
         raise RuntimeError("fundamental_refit_by_pair: best_count must hold one int64 per pair")
-    H = 1
-    if moments is not None:
-        moments = _dev(moments, "moments", torch.float64)
-        if tuple(moments.shape) != (pairs, 9, 9):
-            raise RuntimeError("fundamental_refit_by_pair: moments must be [pairs,9,9]")
-        models = best = None
-    else:
-        models, best = _dev(models, "models"), _dev(best, "best", torch.int32).reshape(-1)
-        if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3) or models.shape[0] != pairs or best.numel() != pairs:
-            raise RuntimeError("fundamental_refit_by_pair: models must be [pairs,H,3,3] and best [pairs]")
-        H = int(models.shape[1])
-        if not 1 <= H <= epipolar_max_h():
-            raise RuntimeError("fundamental_refit_by_pair: H = %d, must lie in 1 .. %d" % (H, epipolar_max_h()))
+    moments, models, best, H = _bp_refit_source(fn, pairs, moments, models, best)
     norm = _bp_norm(fn, norm, pairs)
     dev = bc.device
     want = [("F", torch.float64, (pairs, 3, 3)), ("eig", torch.float64, (pairs, 2)), ("sigma", torch.float64, (pairs, 3))]
