@@ -535,7 +535,14 @@ int pats_refine_scatter_f32(const uint8_t* if_nomatching, const float* pts, cons
  * scale1_cell_stride = 2: scale1 is [rows1, n1, 2] as the reference materialises it; 0: scale1 is
  * [rows1, 2], one scale per row (what pats.py:70 repeats).  Output order = reference (row, sub-cell);
  * at most `capacity` rows are written, *count (device int64) receives M.  fp32, operation order of the
- * reference.  Workspace: pats_get_result_workspace_bytes(batch_size*n0, rows1, n1). */
+ * reference.  Workspace: pats_get_result_workspace_bytes(batch_size*n0, rows1, n1).
+ * rows1 may exceed the number of surviving level-0 cells K (a capacity-sized tensor): rows K .. rows1 - 1 emit
+ * nothing, and the first M_true slots (the unflagged sub-cells of rows 0 .. K - 1) are the matches.  *count is
+ * the total of the level-1 flag scan over ALL rows1 rows: it equals M_true only when the rows past K are fully
+ * flagged (what pats_refine_scatter_f32 / the batch merge leave there).  Otherwise *count = M_true + their
+ * unflagged sub-cells, and the slots M_true .. *count - 1 stay unwritten - a caller that cannot guarantee the
+ * flags must not read them.  The same holds for the pats_get_result_chunks_* entries and their match_row /
+ * match_conf. */
 size_t pats_get_result_workspace_bytes(int64_t cells0, int64_t rows1, int64_t cells1);
 int pats_get_result_f32(int batch_size, const uint8_t* if_nomatching0, const uint8_t* if_nomatching1,
                         int64_t rows1, const float* average_point0, const float* average_point1,
