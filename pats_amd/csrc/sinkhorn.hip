@@ -22,6 +22,7 @@
 #include "third_device.hpp"
 #include "cost65_device.hpp"
 #include <stdlib.h>
+#include <utility>
 
 namespace pats {
 
@@ -741,7 +742,21 @@ __global__ void sinkhorn_wg_kernel(SrcView src, int M, int N, const float* __res
 // Column pass: 95 FMAs per lane into 5 partial column sums, combined across the 16 waves through a
 // double-buffered 20 KB LDS array (one barrier per sweep).  Z is re-read from L2 for the epilogue.
 // A problem whose scalings leave the guard sets fail[b]; sinkhorn_wg_kernel re-solves only those.
+//
+// Two generations share everything but the storage of K and the sweep loop: sinkhorn_cu2_kernel (production) and
+// sinkhorn_cu_kernel (diagnostic library only).  The shared phases are the cu_* functions below, in the order a kernel calls them:
+// cu_load, cu_row_max, cu_col_max, cu_exp_k, cu_marginals, (the kernel's sweeps), cu_guard, cu_epilogue.  A kernel hands them its
+// storage as two accessors, kget(s, c) and kset(s, c, v), whose row slot s is a compile-time value (slot_c): where a slot lives -
+// a register, half of a register pair, LDS - is an `if constexpr`, never an index computed at run time.
 typedef float f2p __attribute__((ext_vector_type(2)));
+constexpr int CU_NW = 16;                        // waves of the workgroup
+
+template <int V> using slot_c = std::integral_constant<int, V>;
+template <class F, int... I>
+__device__ __forceinline__ void for_slots_impl(F& f, std::integer_sequence<int, I...>) { (f(slot_c<I>{}), ...); }
+// f(slot_c<0>{}), ..., f(slot_c<N - 1>{}), in that order
+template <int N, class F>
+__device__ __forceinline__ void for_slots(F f) { for_slots_impl(f, std::make_integer_sequence<int, N>{}); }
 
 template <int RPW, class Op>
 struct RowReduce {
@@ -753,164 +768,269 @@ struct RowReduce {
     }
     // slot held by register i in 16-lane group g (may be >= RPW: padding)
     __device__ static int slot_of(int i, int g) { return i + N2 * (g & 1) + N1 * (g >> 1); }
+    // slot s's reduced value, as a wave-uniform scalar
+    __device__ static float at(const float (&red)[N2], int s) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, red[slot_reg(s)]), 16 * slot_grp(s)));
+    }
 
-    // pf(s) yields this lane's partial for slot s; it is evaluated right before the swap that
+    // first exchange level: this lane's partials of slots i (lo) and i + N1 (hi; the identity past RPW) across the wave halves
+    __device__ static float level1(float lo, float hi, Op op) {
+        unsigned x = __builtin_bit_cast(unsigned, lo), y = __builtin_bit_cast(unsigned, hi);
+        lane_swap32(x, y);
+        return op(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
+    }
+    // second exchange level across the 16-lane rows, then four DPP steps inside them
+    __device__ static void finish(const float (&a1)[N1], float (&red)[N2], Op op, float identity) {
+#pragma unroll
+        for (int i = 0; i < N2; ++i) {
+            unsigned x = __builtin_bit_cast(unsigned, a1[i]);
+            unsigned y = __builtin_bit_cast(unsigned, (i + N2 < N1) ? a1[i + N2] : identity);
+            lane_swap16(x, y);
+            float v = op(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
+            v = op(v, dpp_f<DPP_QUAD_XOR1>(v));
+            v = op(v, dpp_f<DPP_QUAD_XOR2>(v));
+            v = op(v, dpp_f<DPP_ROW_HALF_MIRROR>(v));
+            v = op(v, dpp_f<DPP_ROW_MIRROR>(v));
+            red[i] = v;
+        }
+    }
+
+    // pf(slot_c<s>) yields this lane's partial for slot s; it is evaluated right before the swap that
     // consumes it so the RPW partials are never all live at once
     template <class PF>
     __device__ static void run(PF pf, float (&red)[N2], Op op, float identity) {
         float a1[N1];
-#pragma unroll
-        for (int i = 0; i < N1; ++i) {
-            unsigned x = __builtin_bit_cast(unsigned, pf(i));
-            unsigned y = __builtin_bit_cast(unsigned, (i + N1 < RPW) ? pf(i + N1 < RPW ? i + N1 : 0) : identity);
-            lane_swap32(x, y);
-            a1[i] = op(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
-        }
-#pragma unroll
-        for (int i = 0; i < N2; ++i) {
-            unsigned x = __builtin_bit_cast(unsigned, a1[i]);
-            unsigned y = __builtin_bit_cast(unsigned, (i + N2 < N1) ? a1[i + N2] : identity);
-            lane_swap16(x, y);
-            float v = op(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
-            v = op(v, dpp_f<DPP_QUAD_XOR1>(v));
-            v = op(v, dpp_f<DPP_QUAD_XOR2>(v));
-            v = op(v, dpp_f<DPP_ROW_HALF_MIRROR>(v));
-            v = op(v, dpp_f<DPP_ROW_MIRROR>(v));
-            red[i] = v;
-        }
+        for_slots<N1>([&](auto i) {
+            constexpr int I = decltype(i)::value;
+            const float lo = pf(i);
+            float hi = identity;
+            if constexpr (I + N1 < RPW) hi = pf(slot_c<I + N1>{});
+            a1[I] = level1(lo, hi, op);
+        });
+        finish(a1, red, op, identity);
     }
 
-    // the same reduction fed PAIR-wise: pf2(i) yields this lane's partials of slots i and i + N1 together (one packed FMA chain
-    // over a register pair, sinkhorn_cu2_kernel) - exactly the two values the first exchange level consumes side by side
+    // the same reduction fed PAIR-wise: pf2(slot_c<i>) yields this lane's partials of slots i and i + N1 together (one packed FMA
+    // chain over a register pair, sinkhorn_cu2_kernel) - exactly the two values the first exchange level consumes side by side
     template <class PF2>
     __device__ static void run_pairs(PF2 pf2, float (&red)[N2], Op op, float identity) {
         float a1[N1];
-#pragma unroll
-        for (int i = 0; i < N1; ++i) {
+        for_slots<N1>([&](auto i) {
+            constexpr int I = decltype(i)::value;
             const f2p pr = pf2(i);
-            unsigned x = __builtin_bit_cast(unsigned, pr.x);
-            unsigned y = __builtin_bit_cast(unsigned, (i + N1 < RPW) ? pr.y : identity);
-            lane_swap32(x, y);
-            a1[i] = op(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
-        }
-#pragma unroll
-        for (int i = 0; i < N2; ++i) {
-            unsigned x = __builtin_bit_cast(unsigned, a1[i]);
-            unsigned y = __builtin_bit_cast(unsigned, (i + N2 < N1) ? a1[i + N2] : identity);
-            lane_swap16(x, y);
-            float v = op(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
-            v = op(v, dpp_f<DPP_QUAD_XOR1>(v));
-            v = op(v, dpp_f<DPP_QUAD_XOR2>(v));
-            v = op(v, dpp_f<DPP_ROW_HALF_MIRROR>(v));
-            v = op(v, dpp_f<DPP_ROW_MIRROR>(v));
-            red[i] = v;
-        }
+            a1[I] = level1(pr.x, (I + N1 < RPW) ? pr.y : identity, op);
+        });
+        finish(a1, red, op, identity);
     }
 };
 
+// where a lane sits in the problem: wave w owns rows w + 16 s, lane l owns columns l + 64 c
+template <int CPL>
+struct CuLane {
+    int lane, wave, grp;        // grp: the lane's 16-lane group, which selects its slots of the reduced layout (RowReduce::slot_of)
+    int M, N;
+    bool cval[CPL];             // column slice c holds a column of the matrix
+    __device__ CuLane(int M_, int N_) : lane(threadIdx.x & 63), wave(threadIdx.x >> 6), grp(lane >> 4), M(M_), N(N_) {
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) cval[c] = lane + 64 * c < N;
+    }
+    __device__ bool row(int s) const { return wave + CU_NW * s < M; }       // row slot s holds a row of the matrix
+};
+
+// ---- load Z block (rows wave + 16 s, columns lane + 64 c); -inf outside the matrix --------------
+template <int RPW, int CPL, class KSet>
+__device__ __forceinline__ void cu_load(const CuLane<CPL>& q, const SrcView& src, const float* sb, KSet kset) {
+    for_slots<RPW>([&](auto s) {
+        const int i = q.wave + CU_NW * s;
+#pragma unroll
+        for (int c = 0; c < CPL; ++c)
+            kset(s, c, (i < q.M && q.cval[c]) ? src_at(src, sb, i, q.lane + 64 * c) : -INFINITY);
+    });
+}
+
+// ---- r_i = max_j Z_ij (transposed wave reduction) into rsave[wave][slot] -------------------------
+template <int RPW, int CPL, class KGet>
+__device__ __forceinline__ void cu_row_max(const CuLane<CPL>& q, KGet kget, float (&rsave)[CU_NW][RPW + 1]) {
+    using RMax = RowReduce<RPW, OpMax>;
+    float rred[RMax::N2];
+    RMax::run([&](auto s) {
+        float m = kget(s, 0);
+#pragma unroll
+        for (int c = 1; c < CPL; ++c) m = fmaxf(m, kget(s, c));
+        return m; }, rred, OpMax(), -INFINITY);
+    // keep one scalar per row slot: slot s sits in register slot_reg(s), 16-lane group slot_grp(s)
+#pragma unroll
+    for (int i = 0; i < RMax::N2; ++i)
+        if ((q.lane & 15) == 0 && RMax::slot_of(i, q.grp) < RPW) rsave[q.wave][RMax::slot_of(i, q.grp)] = rred[i];
+}
+
+// ---- c_j = max_i (Z_ij - r_i): per-wave partial, then across waves through LDS (part: [16][64 CPL]) ---
+// Leaves c_j in bsc and, from wave 0, in csave.  rs = rsave[wave], which this same wave wrote: LDS operations of one wave complete
+// in order - and wave_lds_sync() tells the compiler, to which the reads below do not depend on another lane's store (round 5
+// audit, tools/lds_handover_audit.py)
+template <int RPW, int CPL, class KGet>
+__device__ __forceinline__ void cu_col_max(const CuLane<CPL>& q, KGet kget, const float* rs, float (*part)[CPL * 64], float* csave,
+                                           float (&bsc)[CPL]) {
+    wave_lds_sync();
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+        float m = -INFINITY;
+        for_slots<RPW>([&](auto s) {
+            if (s * CU_NW < q.M) m = fmaxf(m, q.row(s) ? kget(s, c) - rs[s] : -INFINITY);
+        });
+        part[q.wave][q.lane + 64 * c] = m;
+    }
+    wg_barrier();
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+        float m = part[0][q.lane + 64 * c];
+#pragma unroll
+        for (int w = 1; w < CU_NW; ++w) m = fmaxf(m, part[w][q.lane + 64 * c]);
+        m = q.cval[c] ? m : 0.f;
+        if (q.wave == 0) csave[q.lane + 64 * c] = m;
+        bsc[c] = m;                                     // temporarily the stabiliser c_j
+    }
+}
+
+// ---- K = exp(Z - r - c), zero outside the matrix -------------------------------------------------
+template <int RPW, int CPL, class KGet, class KSet>
+__device__ __forceinline__ void cu_exp_k(const CuLane<CPL>& q, KGet kget, KSet kset, const float* rs, const float (&bsc)[CPL]) {
+    for_slots<RPW>([&](auto s) {
+        const float r_s = rs[s];
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+            const bool v = q.row(s) && q.cval[c];
+            kset(s, c, v ? fast_exp2(((kget(s, c) - r_s) - bsc[c]) * LOG2E) : 0.f);
+        }
+    });
+}
+
+// ---- b starts at exp(c_j); mu in the reduced layout (register i, group g <-> slot), a at 0 -----------
+template <int RPW, int CPL, int N2>
+__device__ __forceinline__ void cu_marginals(const CuLane<CPL>& q, const float* lmu, float (&bsc)[CPL], float (&mured)[N2],
+                                             float (&ared)[N2]) {
+    using RSum = RowReduce<RPW, OpSum>;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) bsc[c] = q.cval[c] ? expf(bsc[c]) : 0.f;
+#pragma unroll
+    for (int i = 0; i < N2; ++i) {
+        const int row = q.wave + CU_NW * RSum::slot_of(i, q.grp);
+        mured[i] = (RSum::slot_of(i, q.grp) < RPW && row < q.M) ? expf(lmu[row]) : 0.f;
+        ared[i] = 0.f;
+    }
+}
+
+// ---- guard: every scaling of the matrix in (0, 2^30], and at least one sweep; writes *fail_b -----------
+template <int RPW, int CPL, int N2>
+__device__ __forceinline__ bool cu_guard(const CuLane<CPL>& q, const float (&ared)[N2], const float (&bsc)[CPL], int iters,
+                                         int (&ok_s)[CU_NW], int* fail_b) {
+    using RSum = RowReduce<RPW, OpSum>;
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) ok = ok && (!q.cval[c] || scaling_ok(bsc[c]));
+#pragma unroll
+    for (int i = 0; i < N2; ++i) {
+        const int sl = RSum::slot_of(i, q.grp);
+        ok = ok && (!(sl < RPW && q.row(sl)) || scaling_ok(ared[i]));
+    }
+    const bool okw = __all(ok);
+    wg_barrier();
+    if (q.lane == 0) ok_s[q.wave] = okw ? 1 : 0;
+    wg_barrier();
+    bool all_ok = iters > 0;
+#pragma unroll
+    for (int w = 0; w < CU_NW; ++w) all_ok = all_ok && ok_s[w] != 0;
+    if (threadIdx.x == 0) *fail_b = all_ok ? 0 : 1;
+    return all_ok;
+}
+
+// ---- duals and epilogue: ((Z + u) + v) - norm, Z re-read from the source ---------------------------
+template <int RPW, int CPL, int N2>
+__device__ __forceinline__ void cu_epilogue(const CuLane<CPL>& q, const SrcView& src, const float* sb, const float (&ared)[N2],
+                                            const float (&bsc)[CPL], const float (&rsave)[CU_NW][RPW + 1], const float* csave,
+                                            const float* norm_b, float* ob) {
+    using RSum = RowReduce<RPW, OpSum>;
+    float ured[N2], vs[CPL];
+#pragma unroll
+    for (int i = 0; i < N2; ++i) {
+        const int sl = RSum::slot_of(i, q.grp);
+        ured[i] = logf(ared[i]) - rsave[q.wave][sl < RPW ? sl : RPW];
+    }
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) vs[c] = logf(bsc[c]) - csave[q.lane + 64 * c];
+    const float norm = norm_b ? *norm_b : 0.f;
+#pragma unroll
+    for (int s_ = 0; s_ < RPW; ++s_) {
+        const int i = q.wave + CU_NW * s_;
+        const float u_s = RSum::at(ured, s_);
+        if (i < q.M) {
+#pragma unroll
+            for (int c = 0; c < CPL; ++c)
+                if (q.cval[c]) {
+                    const int j = q.lane + 64 * c;
+                    float z = (src_at(src, sb, i, j) + u_s) + vs[c];
+                    if (norm_b) z = z - norm;
+                    ob[(int64_t)i * q.N + j] = z;
+                }
+        }
+    }
+}
+
+#ifdef PATS_DIAG
+// ------------------------------------------------------------------------------------------
+// sinkhorn_cu_kernel: the first generation, in the diagnostic library only (PATS_CU_V1=1) as the A/B partner of
+// sinkhorn_cu2_kernel; tools/cu2_ab.py holds the two to bit equality.  Its own: the last LSLOTS row slots of K in LDS as single
+// floats, a scalar row pass, and column sums that every wave forms for itself from a double-buffered `part` (one barrier a sweep).
+// ------------------------------------------------------------------------------------------
 template <int RPW, int CPL, int LSLOTS>
 __global__ void __launch_bounds__(1024)
 sinkhorn_cu_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
                    const float* __restrict__ log_nu, const float* __restrict__ norm_in, int iters,
                    float* __restrict__ out, int* __restrict__ fail) {
-    constexpr int NW = 16, CW = CPL * 64, RREG = RPW - LSLOTS;
+    constexpr int NW = CU_NW, CW = CPL * 64, RREG = RPW - LSLOTS;
     using RSum = RowReduce<RPW, OpSum>;
-    using RMax = RowReduce<RPW, OpMax>;
     constexpr int N2 = RSum::N2;
     __shared__ float part[2][NW][CW];       // cross-wave column partials (double-buffered)
     __shared__ float kl[LSLOTS][NW][CW];    // the last LSLOTS row-slots of K (register budget: 128)
     __shared__ float rsave[NW][RPW + 1];    // row stabilisers r_i per (wave, slot)
     __shared__ float csave[CW];             // column stabilisers
     __shared__ int ok_s[NW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
+    const CuLane<CPL> q(M, N);
+    const int lane = q.lane, wave = q.wave;
     const int b = blockIdx.x;
     const float* sb = src.base + (int64_t)b * src.stride;
     const float* lmu = log_mu + (int64_t)b * M;
     const float* lnu = log_nu + (int64_t)b * N;
 
     float K[RREG][CPL];
-#define KREF(s_, c) (*((s_) < RREG ? &K[(s_) < RREG ? (s_) : 0][c] : &kl[(s_) >= RREG ? (s_) - RREG : 0][wave][lane + 64 * (c)]))
-    bool cval[CPL];
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) cval[c] = lane + 64 * c < N;
+    auto kget = [&](auto s, int c) -> float {
+        constexpr int S = decltype(s)::value;
+        if constexpr (S < RREG) return K[S][c];
+        else return kl[S - RREG][wave][lane + 64 * c];
+    };
+    auto kset = [&](auto s, int c, float v) {
+        constexpr int S = decltype(s)::value;
+        if constexpr (S < RREG) K[S][c] = v;
+        else kl[S - RREG][wave][lane + 64 * c] = v;
+    };
 
-    // ---- load Z block (rows wave + 16 s, columns lane + 64 c); -inf outside the matrix ----------
+    float bsc[CPL], nu[CPL], mured[N2], ared[N2];
+    cu_load<RPW>(q, src, sb, kset);
+    cu_row_max<RPW>(q, kget, rsave);
+    cu_col_max<RPW>(q, kget, rsave[wave], part[0], csave, bsc);
+    cu_exp_k<RPW>(q, kget, kset, rsave[wave], bsc);
 #pragma unroll
-    for (int s_ = 0; s_ < RPW; ++s_) {
-        const int i = wave + NW * s_;
-#pragma unroll
-        for (int c = 0; c < CPL; ++c)
-            KREF(s_, c) = (i < M && cval[c]) ? src_at(src, sb, i, lane + 64 * c) : -INFINITY;
-    }
-    // ---- r_i = max_j Z_ij (transposed wave reduction) ------------------------------------------
-    {
-        float rred[N2];
-        RMax::run([&](int s_) {
-            float m = KREF(s_, 0);
-#pragma unroll
-            for (int c = 1; c < CPL; ++c) m = fmaxf(m, KREF(s_, c));
-            return m; }, rred, OpMax(), -INFINITY);
-        // keep one scalar per row slot: slot s sits in register slot_reg(s), 16-lane group slot_grp(s)
-#pragma unroll
-        for (int i = 0; i < N2; ++i)
-            if ((lane & 15) == 0 && RSum::slot_of(i, grp) < RPW) rsave[wave][RSum::slot_of(i, grp)] = rred[i];
-    }
-    // ---- c_j = max_i (Z_ij - r_i): per-wave partial, then across waves through LDS ---------------
-    // (same wave wrote rsave: LDS operations of one wave complete in order - and wave_lds_sync() tells the compiler, to which the
-    //  reads below do not depend on another lane's store; round 5 audit, tools/lds_handover_audit.py)
-    wave_lds_sync();
-#define RS(s_) (rsave[wave][s_])
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        float m = -INFINITY;
-#pragma unroll
-        for (int s_ = 0; s_ < RPW; ++s_)
-            if (s_ * NW < M) m = fmaxf(m, (wave + NW * s_ < M) ? KREF(s_, c) - RS(s_) : -INFINITY);
-        part[0][wave][lane + 64 * c] = m;
-    }
-    wg_barrier();
-    float bsc[CPL];
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        float m = part[0][0][lane + 64 * c];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) m = fmaxf(m, part[0][w][lane + 64 * c]);
-        m = cval[c] ? m : 0.f;
-        if (wave == 0) csave[lane + 64 * c] = m;
-        bsc[c] = m;                                     // temporarily the stabiliser c_j
-    }
-    // ---- K = exp(Z - r - c), zero outside the matrix -------------------------------------------
-#pragma unroll
-    for (int s_ = 0; s_ < RPW; ++s_) {
-        const float r_s = RS(s_);
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) {
-            const bool v = (wave + NW * s_ < M) && cval[c];
-            KREF(s_, c) = v ? fast_exp2(((KREF(s_, c) - r_s) - bsc[c]) * LOG2E) : 0.f;
-        }
-    }
-    // marginals: nu per owned column; mu in the reduced layout (register i, group g <-> slot)
-    float nu[CPL], mured[N2], ared[N2];
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        nu[c] = cval[c] ? expf(lnu[lane + 64 * c]) : 0.f;
-        bsc[c] = cval[c] ? expf(bsc[c]) : 0.f;          // b starts at exp(c_j)
-    }
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int row = wave + NW * RSum::slot_of(i, grp);
-        mured[i] = (RSum::slot_of(i, grp) < RPW && row < M) ? expf(lmu[row]) : 0.f;
-        ared[i] = 0.f;
-    }
+    for (int c = 0; c < CPL; ++c) nu[c] = q.cval[c] ? expf(lnu[lane + 64 * c]) : 0.f;       // nu per owned column
+    cu_marginals<RPW>(q, lmu, bsc, mured, ared);
     wg_barrier();        // part[0] is free again
 
     for (int it = 0; it < iters; ++it) {
         // ---- a_i = mu_i / sum_j K_ij b_j ----------------------------------------------------------
         float sred[N2];
-        RSum::run([&](int s_) {
-            float acc = KREF(s_, 0) * bsc[0];
+        RSum::run([&](auto s) {
+            float acc = kget(s, 0) * bsc[0];
 #pragma unroll
-            for (int c = 1; c < CPL; ++c) acc = fmaf(KREF(s_, c), bsc[c], acc);
+            for (int c = 1; c < CPL; ++c) acc = fmaf(kget(s, c), bsc[c], acc);
             return acc; }, sred, OpSum(), 0.f);
 #pragma unroll
         for (int i = 0; i < N2; ++i) ared[i] = mured[i] * fast_rcp(sred[i]);   // padding slots: never read
@@ -918,14 +1038,12 @@ sinkhorn_cu_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
         float t[CPL];
 #pragma unroll
         for (int c = 0; c < CPL; ++c) t[c] = 0.f;
+        for_slots<RPW>([&](auto s) {
+            const float a_s = RSum::at(ared, s);        // read in every lane: a select, not a branch around the lane read
+            const float a_u = q.row(s) ? a_s : 0.f;
 #pragma unroll
-        for (int s_ = 0; s_ < RPW; ++s_) {
-            const float a_s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(
-                __builtin_bit_cast(int, ared[RSum::slot_reg(s_)]), 16 * RSum::slot_grp(s_)));
-            const float a_u = (wave + NW * s_ < M) ? a_s : 0.f;
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) t[c] = fmaf(KREF(s_, c), a_u, t[c]);
-        }
+            for (int c = 0; c < CPL; ++c) t[c] = fmaf(kget(s, c), a_u, t[c]);
+        });
         float (*pb)[CW] = part[it & 1];
 #pragma unroll
         for (int c = 0; c < CPL; ++c) pb[wave][lane + 64 * c] = t[c];
@@ -935,59 +1053,14 @@ sinkhorn_cu_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
             float tot = 0.f;
 #pragma unroll
             for (int w = 0; w < NW; ++w) tot += pb[w][lane + 64 * c];
-            bsc[c] = cval[c] ? nu[c] * fast_rcp(tot) : 0.f;
+            bsc[c] = q.cval[c] ? nu[c] * fast_rcp(tot) : 0.f;
         }
     }
 
-    // ---- guard -------------------------------------------------------------------------------
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) ok = ok && (!cval[c] || scaling_ok(bsc[c]));
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int sl = RSum::slot_of(i, grp);
-        ok = ok && (!(sl < RPW && wave + NW * sl < M) || scaling_ok(ared[i]));
-    }
-    const bool okw = __all(ok);
-    wg_barrier();
-    if (lane == 0) ok_s[wave] = okw ? 1 : 0;
-    wg_barrier();
-    bool all_ok = iters > 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) all_ok = all_ok && ok_s[w] != 0;
-    if (threadIdx.x == 0) fail[b] = all_ok ? 0 : 1;
-    if (!all_ok) return;            // sinkhorn_wg_kernel will solve this problem
-
-    // ---- duals and epilogue: ((Z + u) + v) - norm ----------------------------------------------
-    float ured[N2], vs[CPL];
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int sl = RSum::slot_of(i, grp);
-        ured[i] = logf(ared[i]) - rsave[wave][sl < RPW ? sl : RPW];
-    }
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) vs[c] = logf(bsc[c]) - csave[lane + 64 * c];
-    const float norm = norm_in ? norm_in[b] : 0.f;
-    float* ob = out + (int64_t)b * M * N;
-#pragma unroll
-    for (int s_ = 0; s_ < RPW; ++s_) {
-        const int i = wave + NW * s_;
-        const float u_s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(
-            __builtin_bit_cast(int, ured[RSum::slot_reg(s_)]), 16 * RSum::slot_grp(s_)));
-        if (i < M) {
-#pragma unroll
-            for (int c = 0; c < CPL; ++c)
-                if (cval[c]) {
-                    const int j = lane + 64 * c;
-                    float z = (src_at(src, sb, i, j) + u_s) + vs[c];
-                    if (norm_in) z = z - norm;
-                    ob[(int64_t)i * N + j] = z;
-                }
-        }
-    }
-#undef KREF
-#undef RS
+    if (!cu_guard<RPW>(q, ared, bsc, iters, ok_s, fail + b)) return;            // sinkhorn_wg_kernel will solve this problem
+    cu_epilogue<RPW>(q, src, sb, ared, bsc, rsave, csave, norm_in ? norm_in + b : nullptr, out + (int64_t)b * M * N);
 }
+#endif  // PATS_DIAG
 
 // ------------------------------------------------------------------------------------------
 // sinkhorn_cu2_kernel (round 6): the same solve, the same bits, ~25 % fewer instructions a sweep.
@@ -1000,18 +1073,18 @@ sinkhorn_cu_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
 //   * the cross-wave column sums are formed ONCE (thread j < 320 adds the 16 partials of column j
 //     in the old order and publishes b_j) instead of by every wave for itself: 16 + 5 LDS reads a
 //     lane of five waves instead of 80 a lane of all sixteen, at the price of a second barrier.
-// sinkhorn_cu_kernel stays as the A/B partner (diagnostic library: PATS_CU_V1=1); tools/cu2_ab.py
-// holds the two to bit equality.  The diagnostic library is built on request only, so no test of
-// the suite can: tests/test_coarse_solver_edges_gpu.py holds THIS kernel to a float64 reference.
+// Its own: the LDS declarations, the paired storage behind kget / kset, and the sweep loop.  Load, stabilisers, K, marginals,
+// guard and epilogue are the cu_* functions above, shared with sinkhorn_cu_kernel.  The diagnostic library is built on request
+// only, so no test of the suite can compare the two: tests/test_coarse_solver_edges_gpu.py holds THIS kernel to a float64
+// reference.
 // ------------------------------------------------------------------------------------------
 template <int RPW, int CPL>
 __global__ void __launch_bounds__(1024)
 sinkhorn_cu2_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
                     const float* __restrict__ log_nu, const float* __restrict__ norm_in, int iters,
                     float* __restrict__ out, int* __restrict__ fail) {
-    constexpr int NW = 16, CW = CPL * 64;
+    constexpr int NW = CU_NW, CW = CPL * 64;
     using RSum = RowReduce<RPW, OpSum>;
-    using RMax = RowReduce<RPW, OpMax>;
     constexpr int N1 = RSum::N1, N2 = RSum::N2;
     constexpr int PREG = 7;                       // pairs (i, i + N1), i < PREG, in registers
     constexpr int PLDS = N1 - 1 - PREG;           // pairs PREG .. N1 - 2 in LDS; slot N1 - 1 is single (RPW odd)
@@ -1023,90 +1096,37 @@ sinkhorn_cu2_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
     __shared__ float rsave[NW][RPW + 1];
     __shared__ float csave[CW];
     __shared__ int ok_s[NW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 4;
+    const CuLane<CPL> q(M, N);
+    const int lane = q.lane, wave = q.wave;
     const int b = blockIdx.x;
     const float* sb = src.base + (int64_t)b * src.stride;
     const float* lmu = log_mu + (int64_t)b * M;
     const float* lnu = log_nu + (int64_t)b * N;
 
     f2p K2[PREG][CPL];
-    // element (slot s_, column slice c) of this lane's block
-#define KPI(s_) ((s_) < N1 ? (s_) : (s_) - N1)
-#define KPH(s_) ((s_) < N1 ? 0 : 1)
-#define KGET(s_, c) (KPI(s_) < PREG ? K2[KPI(s_) < PREG ? KPI(s_) : 0][c][KPH(s_)] \
-                     : KPI(s_) < N1 - 1 ? klp[KPI(s_) < N1 - 1 && KPI(s_) >= PREG ? KPI(s_) - PREG : 0][wave][lane + 64 * (c)][KPH(s_)] \
-                     : kls[wave][lane + 64 * (c)])
-#define KSET(s_, c, v_) do { const float kv_ = (v_); \
-        if (KPI(s_) < PREG) K2[KPI(s_) < PREG ? KPI(s_) : 0][c][KPH(s_)] = kv_; \
-        else if (KPI(s_) < N1 - 1) klp[KPI(s_) < N1 - 1 && KPI(s_) >= PREG ? KPI(s_) - PREG : 0][wave][lane + 64 * (c)][KPH(s_)] = kv_; \
-        else kls[wave][lane + 64 * (c)] = kv_; } while (0)
-    bool cval[CPL];
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) cval[c] = lane + 64 * c < N;
+    // element (slot s, column slice c) of this lane's block: half s / N1 of pair s mod N1
+    auto kget = [&](auto s, int c) -> float {
+        constexpr int P = decltype(s)::value % N1, H = decltype(s)::value / N1;
+        if constexpr (P < PREG) return K2[P][c][H];
+        else if constexpr (P < N1 - 1) return klp[P - PREG][wave][lane + 64 * c][H];
+        else return kls[wave][lane + 64 * c];
+    };
+    auto kset = [&](auto s, int c, float v) {
+        constexpr int P = decltype(s)::value % N1, H = decltype(s)::value / N1;
+        if constexpr (P < PREG) K2[P][c][H] = v;
+        else if constexpr (P < N1 - 1) klp[P - PREG][wave][lane + 64 * c][H] = v;
+        else kls[wave][lane + 64 * c] = v;
+    };
 
-    // ---- load Z block (rows wave + 16 s, columns lane + 64 c); -inf outside the matrix ----------
-#pragma unroll
-    for (int s_ = 0; s_ < RPW; ++s_) {
-        const int i = wave + NW * s_;
-#pragma unroll
-        for (int c = 0; c < CPL; ++c)
-            KSET(s_, c, (i < M && cval[c]) ? src_at(src, sb, i, lane + 64 * c) : -INFINITY);
-    }
-    // ---- r_i = max_j Z_ij (transposed wave reduction) ------------------------------------------
-    {
-        float rred[N2];
-        RMax::run([&](int s_) {
-            float m = KGET(s_, 0);
-#pragma unroll
-            for (int c = 1; c < CPL; ++c) m = fmaxf(m, KGET(s_, c));
-            return m; }, rred, OpMax(), -INFINITY);
-#pragma unroll
-        for (int i = 0; i < N2; ++i)
-            if ((lane & 15) == 0 && RSum::slot_of(i, grp) < RPW) rsave[wave][RSum::slot_of(i, grp)] = rred[i];
-    }
-    wave_lds_sync();
-#define RS(s_) (rsave[wave][s_])
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        float m = -INFINITY;
-#pragma unroll
-        for (int s_ = 0; s_ < RPW; ++s_)
-            if (s_ * NW < M) m = fmaxf(m, (wave + NW * s_ < M) ? KGET(s_, c) - RS(s_) : -INFINITY);
-        part[wave][lane + 64 * c] = m;
-    }
-    wg_barrier();
-    float bsc[CPL];
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        float m = part[0][lane + 64 * c];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) m = fmaxf(m, part[w][lane + 64 * c]);
-        m = cval[c] ? m : 0.f;
-        if (wave == 0) csave[lane + 64 * c] = m;
-        bsc[c] = m;                                     // temporarily the stabiliser c_j
-    }
-    // ---- K = exp(Z - r - c), zero outside the matrix -------------------------------------------
-#pragma unroll
-    for (int s_ = 0; s_ < RPW; ++s_) {
-        const float r_s = RS(s_);
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) {
-            const bool v = (wave + NW * s_ < M) && cval[c];
-            KSET(s_, c, v ? fast_exp2(((KGET(s_, c) - r_s) - bsc[c]) * LOG2E) : 0.f);
-        }
-    }
-    // marginals: nu of the column this THREAD reduces (j = threadIdx.x < CW); mu in the reduced layout
+    float bsc[CPL], mured[N2], ared[N2];
+    cu_load<RPW>(q, src, sb, kset);
+    cu_row_max<RPW>(q, kget, rsave);
+    cu_col_max<RPW>(q, kget, rsave[wave], part, csave, bsc);
+    cu_exp_k<RPW>(q, kget, kset, rsave[wave], bsc);
+    // nu of the column this THREAD reduces (j = threadIdx.x < CW)
     const int jb = threadIdx.x;
     const float nu_b = (jb < CW && jb < N) ? expf(lnu[jb < N ? jb : 0]) : 0.f;
-    float mured[N2], ared[N2];
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) bsc[c] = cval[c] ? expf(bsc[c]) : 0.f;          // b starts at exp(c_j)
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int row = wave + NW * RSum::slot_of(i, grp);
-        mured[i] = (RSum::slot_of(i, grp) < RPW && row < M) ? expf(lmu[row]) : 0.f;
-        ared[i] = 0.f;
-    }
+    cu_marginals<RPW>(q, lmu, bsc, mured, ared);
     wg_barrier();        // part is free again
 
     for (int it = 0; it < iters; ++it) {
@@ -1115,38 +1135,36 @@ sinkhorn_cu2_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
 #pragma unroll
         for (int c = 0; c < CPL; ++c) bb[c] = f2p{bsc[c], bsc[c]};
         float sred[N2];
-        RSum::run_pairs([&](int i) {
-            if (i < PREG) {
-                f2p acc = K2[i < PREG ? i : 0][0] * bb[0];
+        RSum::run_pairs([&](auto i) {
+            constexpr int I = decltype(i)::value;
+            if constexpr (I < PREG) {
+                f2p acc = K2[I][0] * bb[0];
 #pragma unroll
-                for (int c = 1; c < CPL; ++c) acc = __builtin_elementwise_fma(K2[i < PREG ? i : 0][c], bb[c], acc);
+                for (int c = 1; c < CPL; ++c) acc = __builtin_elementwise_fma(K2[I][c], bb[c], acc);
                 return acc;
-            }
-            if (i < N1 - 1) {
-                const int q = i >= PREG && i < N1 - 1 ? i - PREG : 0;
-                f2p acc = klp[q][wave][lane] * bb[0];
+            } else if constexpr (I < N1 - 1) {
+                f2p acc = klp[I - PREG][wave][lane] * bb[0];
 #pragma unroll
-                for (int c = 1; c < CPL; ++c) acc = __builtin_elementwise_fma(klp[q][wave][lane + 64 * c], bb[c], acc);
+                for (int c = 1; c < CPL; ++c) acc = __builtin_elementwise_fma(klp[I - PREG][wave][lane + 64 * c], bb[c], acc);
                 return acc;
-            }
-            float acc = kls[wave][lane] * bsc[0];
+            } else {
+                float acc = kls[wave][lane] * bsc[0];
 #pragma unroll
-            for (int c = 1; c < CPL; ++c) acc = fmaf(kls[wave][lane + 64 * c], bsc[c], acc);
-            return f2p{acc, 0.f}; }, sred, OpSum(), 0.f);
+                for (int c = 1; c < CPL; ++c) acc = fmaf(kls[wave][lane + 64 * c], bsc[c], acc);
+                return f2p{acc, 0.f};
+            } }, sred, OpSum(), 0.f);
 #pragma unroll
         for (int i = 0; i < N2; ++i) ared[i] = mured[i] * fast_rcp(sred[i]);   // padding slots: never read
         // ---- b_j = nu_j / sum_i K_ij a_i: per-wave partials in the old row order ... ------------------
         float t[CPL];
 #pragma unroll
         for (int c = 0; c < CPL; ++c) t[c] = 0.f;
+        for_slots<RPW>([&](auto s) {
+            const float a_s = RSum::at(ared, s);        // read in every lane: a select, not a branch around the lane read
+            const float a_u = q.row(s) ? a_s : 0.f;
 #pragma unroll
-        for (int s_ = 0; s_ < RPW; ++s_) {
-            const float a_s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(
-                __builtin_bit_cast(int, ared[RSum::slot_reg(s_)]), 16 * RSum::slot_grp(s_)));
-            const float a_u = (wave + NW * s_ < M) ? a_s : 0.f;
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) t[c] = fmaf(KGET(s_, c), a_u, t[c]);
-        }
+            for (int c = 0; c < CPL; ++c) t[c] = fmaf(kget(s, c), a_u, t[c]);
+        });
 #pragma unroll
         for (int c = 0; c < CPL; ++c) part[wave][lane + 64 * c] = t[c];
         wg_barrier();
@@ -1162,57 +1180,8 @@ sinkhorn_cu2_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
         for (int c = 0; c < CPL; ++c) bsc[c] = bl[lane + 64 * c];
     }
 
-    // ---- guard -------------------------------------------------------------------------------
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) ok = ok && (!cval[c] || scaling_ok(bsc[c]));
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int sl = RSum::slot_of(i, grp);
-        ok = ok && (!(sl < RPW && wave + NW * sl < M) || scaling_ok(ared[i]));
-    }
-    const bool okw = __all(ok);
-    wg_barrier();
-    if (lane == 0) ok_s[wave] = okw ? 1 : 0;
-    wg_barrier();
-    bool all_ok = iters > 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) all_ok = all_ok && ok_s[w] != 0;
-    if (threadIdx.x == 0) fail[b] = all_ok ? 0 : 1;
-    if (!all_ok) return;            // sinkhorn_wg_kernel will solve this problem
-
-    // ---- duals and epilogue: ((Z + u) + v) - norm ----------------------------------------------
-    float ured[N2], vs[CPL];
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int sl = RSum::slot_of(i, grp);
-        ured[i] = logf(ared[i]) - rsave[wave][sl < RPW ? sl : RPW];
-    }
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) vs[c] = logf(bsc[c]) - csave[lane + 64 * c];
-    const float norm = norm_in ? norm_in[b] : 0.f;
-    float* ob = out + (int64_t)b * M * N;
-#pragma unroll
-    for (int s_ = 0; s_ < RPW; ++s_) {
-        const int i = wave + NW * s_;
-        const float u_s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(
-            __builtin_bit_cast(int, ured[RSum::slot_reg(s_)]), 16 * RSum::slot_grp(s_)));
-        if (i < M) {
-#pragma unroll
-            for (int c = 0; c < CPL; ++c)
-                if (cval[c]) {
-                    const int j = lane + 64 * c;
-                    float z = (src_at(src, sb, i, j) + u_s) + vs[c];
-                    if (norm_in) z = z - norm;
-                    ob[(int64_t)i * N + j] = z;
-                }
-        }
-    }
-#undef KPI
-#undef KPH
-#undef KGET
-#undef KSET
-#undef RS
+    if (!cu_guard<RPW>(q, ared, bsc, iters, ok_s, fail + b)) return;            // sinkhorn_wg_kernel will solve this problem
+    cu_epilogue<RPW>(q, src, sb, ared, bsc, rsave, csave, norm_in ? norm_in + b : nullptr, out + (int64_t)b * M * N);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1221,6 +1190,7 @@ sinkhorn_cu2_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t stream_workspace_bytes(int64_t batch, int M, int N);
 static inline size_t al256_fwd(int64_t batch, int M, int N) { return align256(stream_workspace_bytes(batch, M, N)); }
+static inline bool stream_shape(int M, int N) { return (int64_t)M * N > 304 * 320 && N <= 512 * 9; }
 
 struct OtWorkspace {
     float *log_mu, *log_nu, *norm, *Zw, *Zt;
@@ -1241,7 +1211,7 @@ static OtWorkspace carve(void* ws, int64_t batch, int M, int N, bool marginals, 
     w.fail = (int*)take((size_t)batch);
     if (zw) w.Zw = take((size_t)batch * M * N);
     w.Zt = take((size_t)batch * M * N);
-    if ((int64_t)M * N > 304 * 320 && N <= 512 * 9) {       // streaming solver's K / partials / vectors
+    if (stream_shape(M, N)) {                               // streaming solver's K / partials / vectors
         w.stream = base + off;
         off += al256_fwd(batch, M, N);
     }
@@ -1260,13 +1230,11 @@ static int launch_wg(const SrcView& src, int64_t batch, int M, int N, const floa
     return check_launch("sinkhorn_wg_kernel");
 }
 
-size_t stream_workspace_bytes(int64_t batch, int M, int N);
 int launch_stream(const float* base, int64_t stride, int ld, int rows, int cols, const float* alpha,
                   int64_t batch, int M, int N, const float* log_mu, const float* log_nu, const float* norm,
                   int iters, float* out, void* ws, int* fail, hipStream_t st);
-static inline bool stream_shape(int M, int N) { return (int64_t)M * N > 304 * 320 && N <= 512 * 9; }
 
-constexpr int CU_RPW = 19, CU_CPL = 5, CU_LSLOTS = 5;            // 16 * 19 = 304 rows, 64 * 5 = 320 columns
+constexpr int CU_RPW = 19, CU_CPL = 5;            // 16 * 19 = 304 rows, 64 * 5 = 320 columns
 static inline bool cu_shape(int M, int N) { return M <= 16 * CU_RPW && N <= 64 * CU_CPL && M * N >= 96 * 96; }
 
 // one-CU linear-domain kernel, then the log-domain kernel on the problems it flagged
@@ -1274,12 +1242,15 @@ static int launch_cu_then_fallback(const SrcView& src, int64_t batch, int M, int
                                    const float* log_nu, const float* norm, int iters, float* out,
                                    const OtWorkspace& w, hipStream_t st) {
     // sinkhorn_cu2_kernel: the same bits in ~25 % fewer instructions (packed row pass, column sums formed once); the first
-    // version stays selectable in the diagnostic library (PATS_CU_V1=1) as its A/B partner
-    static const bool v1 = [] { const char* e = diag_env("PATS_CU_V1"); return e && atoi(e) != 0; }();
-    if (v1) hipLaunchKernelGGL((sinkhorn_cu_kernel<CU_RPW, CU_CPL, CU_LSLOTS>), dim3((unsigned)batch), dim3(1024), 0, st, src, M,
+    // version exists and is selectable in the diagnostic library only (PATS_CU_V1=1), as its A/B partner
+#ifdef PATS_DIAG
+    static const bool v1 = [] { const char* e = diag_env("PATS_CU_V1"); return e && atoi(e) != 0; }();      // (5: its row slots in LDS)
+    if (v1) hipLaunchKernelGGL((sinkhorn_cu_kernel<CU_RPW, CU_CPL, 5>), dim3((unsigned)batch), dim3(1024), 0, st, src, M,
                                N, log_mu, log_nu, norm, iters, out, w.fail);
-    else hipLaunchKernelGGL((sinkhorn_cu2_kernel<CU_RPW, CU_CPL>), dim3((unsigned)batch), dim3(1024), 0, st, src, M,
-                            N, log_mu, log_nu, norm, iters, out, w.fail);
+    else
+#endif
+    hipLaunchKernelGGL((sinkhorn_cu2_kernel<CU_RPW, CU_CPL>), dim3((unsigned)batch), dim3(1024), 0, st, src, M,
+                       N, log_mu, log_nu, norm, iters, out, w.fail);
     int rc = check_launch("sinkhorn_cu_kernel");
     if (rc) return rc;
     return launch_wg(src, batch, M, N, log_mu, log_nu, norm, iters, 0.f, out, w.Zw, w.Zt, st, w.fail);
@@ -1383,6 +1354,22 @@ extern "C" size_t pats_ot2_workspace_bytes(int64_t batch, int m, int n) {
     return pats_ot_workspace_bytes(batch, m, n);
 }
 
+// The shape ladder of the shapes without a resident kernel, for both entry points below: the one-CU kernel, else the streaming
+// solver, each followed by the redo pass over the problems it flagged, else the one-workgroup kernel for everything.  w is the
+// carved workspace (w.fail / w.stream are carved for every shape; w.Zw is null unless the source is augmented).
+static int launch_by_shape(const SrcView& src, int64_t batch, int M, int N, const float* log_mu, const float* log_nu,
+                           const float* norm, int iters, float* out, const OtWorkspace& w, hipStream_t st) {
+    if (use_linear() && cu_shape(M, N))
+        return launch_cu_then_fallback(src, batch, M, N, log_mu, log_nu, norm, iters, out, w, st);
+    if (use_linear() && stream_shape(M, N) && batch <= 65535) {
+        int rc = launch_stream(src.base, src.stride, src.ld, src.rows, src.cols, src.alpha, batch, M, N, log_mu, log_nu, norm,
+                               iters, out, w.stream, w.fail, st);
+        if (rc) return rc;
+        return launch_wg(src, batch, M, N, log_mu, log_nu, norm, iters, 0.f, out, w.Zw, w.Zt, st, w.fail);
+    }
+    return launch_wg(src, batch, M, N, log_mu, log_nu, norm, iters, 0.f, out, w.Zw, w.Zt, st);
+}
+
 extern "C" int pats_sinkhorn_f32(const float* Z, int64_t batch, int M, int N, const float* log_mu,
                                  const float* log_nu, int iters, float* out, void* workspace,
                                  size_t workspace_bytes, pats_stream_t stream) {
@@ -1406,16 +1393,8 @@ extern "C" int pats_sinkhorn_f32(const float* Z, int64_t batch, int M, int N, co
     PATS_REQUIRE(workspace && workspace_bytes >= pats_sinkhorn_workspace_bytes(batch, M, N),
                  "sinkhorn: workspace too small");
     OtWorkspace w = carve(workspace, batch, M, N, false, false);
-    SrcView src{Z, (int64_t)M * N, N, M, N, nullptr};   // (w.fail / w.stream are carved for every shape)
-    if (use_linear() && cu_shape(M, N))
-        return launch_cu_then_fallback(src, batch, M, N, log_mu, log_nu, nullptr, iters, out, w, st);
-    if (use_linear() && stream_shape(M, N) && batch <= 65535) {
-        int rc = launch_stream(Z, (int64_t)M * N, N, M, N, nullptr, batch, M, N, log_mu, log_nu, nullptr, iters,
-                               out, w.stream, w.fail, st);
-        if (rc) return rc;
-        return launch_wg(src, batch, M, N, log_mu, log_nu, nullptr, iters, 0.f, out, nullptr, w.Zt, st, w.fail);
-    }
-    return launch_wg(src, batch, M, N, log_mu, log_nu, nullptr, iters, 0.f, out, nullptr, w.Zt, st);
+    SrcView src{Z, (int64_t)M * N, N, M, N, nullptr};
+    return launch_by_shape(src, batch, M, N, log_mu, log_nu, nullptr, iters, out, w, st);
 }
 
 extern "C" int pats_log_optimal_transport_f32(const float* scores, int64_t batch, int m, int n,
@@ -1435,15 +1414,7 @@ extern "C" int pats_log_optimal_transport_f32(const float* scores, int64_t batch
     int rc = check_launch("ot_prep_kernel");
     if (rc) return rc;
     SrcView src{scores, (int64_t)m * n, n, m, n, alpha};
-    if (use_linear() && cu_shape(M, N))
-        return launch_cu_then_fallback(src, batch, M, N, w.log_mu, w.log_nu, w.norm, iters, Z, w, st);
-    if (use_linear() && stream_shape(M, N) && batch <= 65535) {
-        rc = launch_stream(scores, (int64_t)m * n, n, m, n, alpha, batch, M, N, w.log_mu, w.log_nu, w.norm, iters,
-                           Z, w.stream, w.fail, st);
-        if (rc) return rc;
-        return launch_wg(src, batch, M, N, w.log_mu, w.log_nu, w.norm, iters, 0.f, Z, w.Zw, w.Zt, st, w.fail);
-    }
-    return launch_wg(src, batch, M, N, w.log_mu, w.log_nu, w.norm, iters, 0.f, Z, w.Zw, w.Zt, st);
+    return launch_by_shape(src, batch, M, N, w.log_mu, w.log_nu, w.norm, iters, Z, w, st);
 }
 
 static int ot2_impl(const float* scores, int64_t batch, int m, int n, const float* one, const float* ns, int iters,
