@@ -7,8 +7,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpats_amd.so")
-# diagnostic twin: the same objects, third_fused3.hip compiled with -DPATS_DIAG (every sweep-loop variant and the timing
-# ablations whose results are wrong by design).  Built on request only (`--diag`); never loaded unless PATS_AMD_DIAG_LIB=1.
+# diagnostic twin: every source compiled with -DPATS_DIAG (third_fused3.hip then holds the four PATS_THIRD_VARIANT builds 300,
+# 350, 1300, 1350, the stage fingerprints and the LDS poison).  Built on request only (`--diag`); never loaded unless
+# PATS_AMD_DIAG_LIB=1.
 LIB_DIAG = os.path.join(HERE, "libpats_amd_diag.so")
 DIAG_SOURCES = None      # every source, each with -DPATS_DIAG=1 (set below SOURCES): diag_env() (csrc/common.hpp) is live in that library only
 SOURCES = ["host.cpp", "sinkhorn.hip", "sinkhorn_stream.hip", "sinkhorn_blk.hip", "sinkhorn_blk2w.hip", "cost.hip", "post.hip", "expand.hip", "resize.hip", "third.hip", "third_fused.hip", "third_fused3.hip", "gather.hip", "merge.hip", "attention.hip", "attention145.hip", "gnn.hip", "gnn_fused.hip", "gnn_fine.hip", "conv_pk.hip",

@@ -58,7 +58,7 @@ template <> struct Pair65<bf16_t> {
     static __device__ __forceinline__ f2u widen(raw v) { return f2u{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)}; }
 };
 
-template <bool NO_MFMA = false, typename T = float>     // NO_MFMA: timing ablation only (loads and edge chains stay, the four MFMAs become one add)
+template <typename T = float>
 __device__ __forceinline__ void cost65_accumulate(const T* __restrict__ A, const T* __restrict__ B,
                                                   int D, float* edge_lds, int lane, Cost65Acc& o,
                                                   int ld = C65_NT) {
@@ -95,14 +95,10 @@ __device__ __forceinline__ void cost65_accumulate(const T* __restrict__ A, const
         for (int s_ = 0; s_ < KB; ++s_) {
             const f2u av = Pair::widen(q.a[s_]), bv = Pair::widen(q.b[s_]);
             const float ea = eA[k0 + 2 * s_ + lk], eb = eB[k0 + 2 * s_ + lk];
-            if (NO_MFMA) {
-                c00[s_ & 15] += av.x * bv.x + av.y * bv.y;
-            } else {
             c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, c00, 0, 0, 0);
             c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.y, c01, 0, 0, 0);
             c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.x, c10, 0, 0, 0);
             c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, c11, 0, 0, 0);
-            }
             er0 = fmaf(ea, bv.x, er0);
             er1 = fmaf(ea, bv.y, er1);
             ec0 = fmaf(av.x, eb, ec0);

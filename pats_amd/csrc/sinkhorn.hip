@@ -176,15 +176,7 @@ sinkhorn65_kernel(Ot65Args g) {
     const int iters = g.iters, linear = g.linear;
     const float bias_k = g.bias_k;
 
-    // Every problem takes the same time, so without this all resident waves stay phase-locked: the
-    // chip alternates between "everyone streams descriptors" (HBM-bound, VALU idle) and "everyone
-    // sweeps" (VALU/LDS-bound, HBM idle) and the phase times ADD.  A hashed one-off start delay for
-    // the first wave-front spreads the phases; later blocks inherit the spread from the slot they
-    // take over.  Purely a scheduling aid - no effect on results.
-    if (g.stagger > 0 && blockIdx.x < 4096u) {
-        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;         // 0..7
-        for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
-    }
+    dephase_first_front<4096>(g.stagger);        // third_device.hpp
     if (SRC == 0) {
         // ---- coalesced load of the 4225 floats into LDS ----------------------------------------
         const float* Zp = g.Zin + p * TILE;
@@ -1488,10 +1480,10 @@ int launch_cost_ot65(const void* d0, const void* d1, int dtype, int64_t batch, i
     g.d0 = (const float*)d0; g.d1 = (const float*)d1; g.D = D; g.P = batch; g.ns = ns; g.one = one; g.iters = iters;
     g.bias_k = bias_k; g.linear = use_linear(); g.out = Z;
     const dim3 grid((unsigned)batch), block(64);
-    if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0, _Float16>), grid, block, 0, as_stream(stream), g);
-    else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0, bf16_t>), grid, block, 0, as_stream(stream), g);
-    else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0>), grid, block, 0, as_stream(stream), g);
-    return check_launch("sinkhorn65_kernel<2,1,0>");
+    return for_elem_type(dtype, [&](auto tag) {
+        hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 0, typename decltype(tag)::type>), grid, block, 0, as_stream(stream), g);
+        return check_launch("sinkhorn65_kernel<2,1,0>");
+    });
 }
 }  // namespace pats
 
@@ -1600,15 +1592,11 @@ static int third_level_impl(const void* feat0, const void* feat1, int dtype, int
     if (P >= 8192) g.stagger = (int)((30.0f + 0.6f * (float)iters) / 16.0f / 3.4f);
     if (const char* e = diag_env("PATS_STAGGER")) g.stagger = atoi(e);
     const dim3 grid((unsigned)P), block(64);
-    if (conf) {
-        g.conf = conf;
-        if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2, _Float16>), grid, block, 0, as_stream(stream), g);
-        else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2, bf16_t>), grid, block, 0, as_stream(stream), g);
-        else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2>), grid, block, 0, as_stream(stream), g);
-        return check_launch("sinkhorn65_kernel<2,1,2>");
-    }
-    if (dtype == PATS_MAP_F16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, _Float16>), grid, block, 0, as_stream(stream), g);
-    else if (dtype == PATS_MAP_BF16) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, bf16_t>), grid, block, 0, as_stream(stream), g);
-    else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1>), grid, block, 0, as_stream(stream), g);
-    return check_launch("sinkhorn65_kernel<2,1,1>");
+    g.conf = conf;
+    return for_elem_type(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (conf) hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 2, T>), grid, block, 0, as_stream(stream), g);
+        else hipLaunchKernelGGL((sinkhorn65_kernel<2, 1, 1, T>), grid, block, 0, as_stream(stream), g);
+        return check_launch(conf ? "sinkhorn65_kernel<2,1,2>" : "sinkhorn65_kernel<2,1,1>");
+    });
 }

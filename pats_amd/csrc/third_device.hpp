@@ -52,6 +52,50 @@ constexpr uint8_t THIRD_REDO = 0xEE; // if_matching1[p*16] of a problem the log-
 // argument of their own, so the plain kernels' argument block - and with it their code - stays what it was.
 int launch_third_fused(const Fused65Args& g, hipStream_t st, float* conf = nullptr);
 
+// ---- shared by the two register-block files (third_fused.hip, third_fused3.hip) ---------------------------------------------
+constexpr int SST = 36;                 // staging row stride (floats): 16-byte aligned rows
+constexpr float GUARD = 1073741824.0f;  // 2^30
+__device__ __forceinline__ bool sc_ok(float x) { return x <= GUARD && x > 0.f; }
+__device__ __forceinline__ float uni(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
+
+// Every problem takes the same time, so without this all resident waves stay phase-locked: the
+// chip alternates between "everyone streams descriptors" (HBM-bound, VALU idle) and "everyone
+// sweeps" (VALU/LDS-bound, HBM idle) and the phase times ADD.  A hashed one-off start delay for
+// the first wave-front (the first FRONT workgroups) spreads the phases; later blocks inherit the
+// spread from the slot they take over.  Purely a scheduling aid - no effect on results.
+// stagger: the delay unit in s_sleep(127) periods (0 = off).
+template <unsigned FRONT>
+__device__ __forceinline__ void dephase_first_front(int stagger) {
+    if (stagger > 0 && blockIdx.x < FRONT) {
+        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;         // 0..7
+        for (unsigned q = 0; q < slots * (unsigned)stagger; ++q) __builtin_amdgcn_s_sleep(127);
+    }
+}
+
+// The re-solve walk of the kernels that run behind third_fused3_kernel: the W workgroups of the launch share the problems
+// INTERLEAVED - workgroup w looks at w, w + W, w + 2 W, ... (64 candidates per ballot) and calls solve(p) for those whose
+// if_matching1 slot carries THIRD_REDO (left there by third_fused3_kernel's guard).  Flagged problems come in runs (the points
+// of one wild fine row are consecutive): with contiguous blocks of 64 per workgroup - round 3 - one wave re-solved a whole run
+// serially while the rest of the GPU idled (9.1 ms per step for 8 000 flagged problems, profiles/r04_wild10_step_kernel_stats.md);
+// interleaved, a run of 64 goes to 64 different waves.  tests/test_third_redo_walk_gpu.py models this loop.
+template <class Solve>
+__device__ __forceinline__ void third_redo_walk(const Fused65Args& g, int lane, Solve&& solve) {
+    const int64_t W = gridDim.x, live = live_problems(g);
+    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
+        const int64_t cand = first + (int64_t)lane * W;
+        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
+        unsigned long long todo = __ballot(redo);
+        while (todo) {
+            const int k = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            wg_barrier();
+            solve(first + (int64_t)k * W);
+        }
+    }
+}
+// the walk's grid: two rounds of the 3 072 wave slots, so that flagged runs spread out; at least one workgroup
+inline unsigned third_walk_grid(int64_t P) { return (unsigned)(P < 1 ? 1 : P < 6144 ? P : 6144); }
+
 // row-level (16-lane) all-reduces: 4 DPP steps, no LDS traffic
 __device__ __forceinline__ float row16_sum(float v) {
     v += dpp_f<DPP_QUAD_XOR1>(v);

@@ -32,10 +32,6 @@ int sinkhorn_mode();
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-constexpr int SST = 36;                 // staging row stride (floats): 16-byte aligned rows
-constexpr float GUARD = 1073741824.0f;  // 2^30
-__device__ __forceinline__ bool sc_ok(float x) { return x <= GUARD && x > 0.f; }
-
 struct __attribute__((aligned(16))) BlkLds {
     float va[72];                // row-indexed vector (r, then a / u); [64] = dustbin row's value
     float vb[72];                // column-indexed vector (c, then b / v); [64] = dustbin column's value
@@ -46,7 +42,6 @@ struct __attribute__((aligned(16))) BlkLds {
 
 
 __device__ __forceinline__ float lse_fin(float s, float mI) { return (fast_log2(s) + mI) * LN2; }
-__device__ __forceinline__ float uni(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
 // CONF: the per-match confidence conf [P,16] is written beside the matches (third_device.hpp)
 template <typename T, int CONF = 0>      // T: the descriptors' element type (cost65_device.hpp): only the cost build's loads see it
@@ -350,12 +345,8 @@ __device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int
                                  g.outdoor, g.cr, lane, 66, area, conf);
 }
 
-// direct mode: one workgroup per problem.  scan mode (g.scan): the W workgroups of the launch share the problems INTERLEAVED -
-// workgroup w looks at w, w + W, w + 2 W, ... (64 candidates per ballot) and re-solves those whose if_matching1 slot carries
-// THIRD_REDO (left there by third_fused3_kernel's guard).  Flagged problems come in runs (the points of one wild fine row are
-// consecutive): with contiguous blocks of 64 per workgroup - round 3 - one wave re-solved a whole run serially while the rest
-// of the GPU idled (9.1 ms per step for 8 000 flagged problems, profiles/r04_wild10_step_kernel_stats.md); interleaved, a
-// run of 64 goes to 64 different waves.
+// direct mode: one workgroup per problem.  scan mode (g.scan): the re-solve walk (third_redo_walk, third_device.hpp) over the
+// problems third_fused3_kernel's guard flagged.
 template <typename T = float>       // the descriptors' element type
 __global__ void __launch_bounds__(64, 3)
 third_fused_kernel(Fused65Args g) {
@@ -364,29 +355,14 @@ third_fused_kernel(Fused65Args g) {
     if (!g.scan) {
         const int64_t p = blockIdx.x;
         if (p >= live_problems(g)) return;
-        // de-phase the first wave-front (see sinkhorn65_kernel)
-        if (g.stagger > 0 && blockIdx.x < 8192u) {
-            const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
-            for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
-        }
+        dephase_first_front<8192>(g.stagger);
         third_v2_problem<T>(g, p, lds, lane);
         return;
     }
-    const int64_t W = gridDim.x, live = live_problems(g);
-    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
-        const int64_t cand = first + (int64_t)lane * W;
-        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
-        unsigned long long todo = __ballot(redo);
-        while (todo) {
-            const int k = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            wg_barrier();
-            third_v2_problem<T>(g, first + (int64_t)k * W, lds, lane);
-        }
-    }
+    third_redo_walk(g, lane, [&](int64_t p) { third_v2_problem<T>(g, p, lds, lane); });
 }
-// The same with the per-match confidence conf [P,16]: a kernel of its own name and with its own copy of the walk (as
-// third_fused3_stab_kernel has), so that the plain one stays what it was, instruction for instruction.
+// The same with the per-match confidence conf [P,16]: a kernel of its own name, so that the plain one's argument block - and
+// with it its code - stays what it was.
 template <typename T>
 __global__ void __launch_bounds__(64, 3)
 third_fused_conf_kernel(Fused65Args g, float* conf) {
@@ -395,36 +371,19 @@ third_fused_conf_kernel(Fused65Args g, float* conf) {
     if (!g.scan) {
         const int64_t p = blockIdx.x;
         if (p >= live_problems(g)) return;
-        if (g.stagger > 0 && blockIdx.x < 8192u) {
-            const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
-            for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
-        }
+        dephase_first_front<8192>(g.stagger);
         third_v2_problem<T, 1>(g, p, lds, lane, conf);
         return;
     }
-    const int64_t W = gridDim.x, live = live_problems(g);
-    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
-        const int64_t cand = first + (int64_t)lane * W;
-        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
-        unsigned long long todo = __ballot(redo);
-        while (todo) {
-            const int k = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            wg_barrier();
-            third_v2_problem<T, 1>(g, first + (int64_t)k * W, lds, lane, conf);
-        }
-    }
+    third_redo_walk(g, lane, [&](int64_t p) { third_v2_problem<T, 1>(g, p, lds, lane, conf); });
 }
 static void launch_v2(const Fused65Args& g, dim3 grid, hipStream_t st, float* conf) {
-    if (conf) {
-        if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused_conf_kernel<_Float16>, grid, dim3(64), 0, st, g, conf);
-        else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused_conf_kernel<bf16_t>, grid, dim3(64), 0, st, g, conf);
-        else hipLaunchKernelGGL(third_fused_conf_kernel<float>, grid, dim3(64), 0, st, g, conf);
-        return;
-    }
-    if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused_kernel<_Float16>, grid, dim3(64), 0, st, g);
-    else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused_kernel<bf16_t>, grid, dim3(64), 0, st, g);
-    else hipLaunchKernelGGL(third_fused_kernel<float>, grid, dim3(64), 0, st, g);
+    for_elem_type(g.dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (conf) hipLaunchKernelGGL(third_fused_conf_kernel<T>, grid, dim3(64), 0, st, g, conf);
+        else hipLaunchKernelGGL(third_fused_kernel<T>, grid, dim3(64), 0, st, g);
+        return 0;
+    });
 }
 
 int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf);      // third_fused3.hip
@@ -441,8 +400,7 @@ int launch_third_fused(const Fused65Args& g0, hipStream_t st, float* conf) {
         if (rc) return rc;
         g.linear = 0;
         g.scan = 1;
-        const int64_t waves = g.P < 6144 ? g.P : 6144;            // two rounds of the 3 072 wave slots: flagged runs spread out
-        launch_v2(g, dim3((unsigned)(waves > 0 ? waves : 1)), st, conf);
+        launch_v2(g, dim3(third_walk_grid(g.P)), st, conf);
         return check_launch("third_fused_kernel(scan)");
     }
     if (g.P >= 8192) g.stagger = (int)((30.0f + 0.6f * (float)g.iters) / 16.0f / 3.4f);

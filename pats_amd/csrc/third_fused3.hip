@@ -16,17 +16,16 @@
 //    with v_pk_fma_f32's op_sel both half-sweeps accumulate straight into {row 2i, row 2i+1} resp.
 //    {col 2j, col 2j+1} pairs - no horizontal x + y adds (8 instructions), and the column reduction's
 //    adds become v_pk_add_f32.
-//  * everything that crosses 16-lane rows goes through LDS instead of v_permlane*_swap / row broadcasts: the
-//    column reduction posts its eight partials and reads back two b128 (six swaps + selects -> seven adds),
-//    the two 64-lane dustbin dot products finish with one ds_write_b32 + one broadcast ds_read_b128.  LDS
-//    instructions are issued beside the VALU; tools/valu_cost.hip has the measured instruction costs this
-//    layout was chosen by (v_pk_fma_f32 2.05 ns per SIMD, plain fp32 add/mul/fma 1.05, DPP add / select /
-//    v_pk_add 1.75, rcp and permlane swaps 3.4, and the fp32 MFMA occupies the same FMA lanes: 13.4).
+//  * what crosses 16-lane rows stays on the VALU: the column reduction takes six v_permlane*_swap and one row rotate
+//    (reduce8_strided_pk), the two 64-lane dustbin dot products end in DPP row broadcasts (wave_sum_uniform).  Sending either
+//    through LDS or the MFMA was measured and not adopted (docs/kernels.md 4.2, 4.18).  tools/valu_cost.hip has the measured
+//    instruction costs this layout was chosen by (v_pk_fma_f32 2.05 ns per SIMD, plain fp32 add/mul/fma 1.05, DPP add /
+//    select / v_pk_add 1.75, rcp and permlane swaps 3.4, and the fp32 MFMA occupies the same FMA lanes: 13.4).
 //
-//  * the cost build splits every fp32 descriptor element into two fp16 halves and runs three exact-product passes of
-//    v_mfma_f32_32x32x16_f16 per tile instead of the fp32 MFMA (cost65_device.hpp: 96 matrix instructions of 32 cycles
-//    instead of 256 of 64; measured error against float64 below the fp32 fma chain's own).  PATS_THIRD_VARIANT=300
-//    selects the fp32-MFMA build of the same kernel.
+//  * the cost build is the fp32 MFMA's (cost65_device.hpp).  The diagnostic library also holds the build that splits every fp32
+//    descriptor element into two fp16 halves and runs three exact-product passes of v_mfma_f32_32x32x16_f16 per tile (96 matrix
+//    instructions of 32 cycles instead of 256 of 64; measured error against float64 below the fp32 fma chain's own): faster, but
+//    its first launch in a process is not bit-reproducible (launch_third_fused3 below).
 //
 // The solve is the linear-domain one only.  A problem that trips the guard writes a sentinel into its
 // if_matching1 slot and is re-solved by third_fused_kernel (third_fused.hip, log-sum-exp sweeps) in
@@ -36,31 +35,19 @@
 #include "third_device.hpp"
 #include "cost65_device.hpp"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace pats {
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// experiment hook (diagnostic builds): wave priority up for the reduction tail of each half-sweep, as in sinkhorn_blk.hip
-#ifdef PATS_THIRD_PRIO
-#define THIRD_PRIO(n) __builtin_amdgcn_s_setprio((n) ? 1 : 0)
-#else
-#define THIRD_PRIO(n) do { } while (0)
-#endif
-
-constexpr int SST3 = 36;                 // staging row stride (floats): 16-byte aligned rows
-constexpr float GUARD3 = 1073741824.0f;  // 2^30
-__device__ __forceinline__ bool sc_ok3(float x) { return x <= GUARD3 && x > 0.f; }
-__device__ __forceinline__ float uni3(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
 struct __attribute__((aligned(16))) Blk3Lds {
     float vb[72];                // column-indexed vector (c, then b)
     float erow[72];              // Z[64][j]
     float ecol[72];              // Z[i][64]
-    float red[8];                // [0..3], [4..7]: the four 16-lane row totals of the two dustbin dot products
-    float stage[64 * SST3];      // one column parity of Z: [64 rows][32 cols]; first: cost edge columns;
+    float pad[8];                // not used: keeps `stage` at offset 896, so every LDS address is what it was (docs/kernels.md 4.18)
+    float stage[64 * SST];       // one column parity of Z: [64 rows][32 cols]; first: cost edge columns;
                                  // last: the plan rows of block rows 2..5, [32][RS3]
 };
 
@@ -80,57 +67,6 @@ __device__ __forceinline__ float reduce8_perm(const float (&p)[8], Op op) {
     for (int s = 0; s < 4; ++s) r[s] = op(p[s], dpp_f<DPP_ROW_HALF_MIRROR>(p[s + 4]));
     const float q0 = op(r[0], dpp_f<DPP_QUAD_XOR2>(r[2])), q1 = op(r[1], dpp_f<DPP_QUAD_XOR2>(r[3]));
     return op(q0, dpp_f<DPP_QUAD_XOR1>(q1));
-}
-
-// 64-lane sum into every lane: in-row DPP butterfly, then the four 16-lane row totals cross through LDS (one
-// ds_write_b32, one broadcast ds_read_b128: LDS instructions take no VALU issue time, and the fp32 MFMA that
-// could add the rows runs on the VALU's own FMA lanes - measured, tools/valu_cost.hip: 13 ns against 2).
-// `slot` = four floats of LDS, 16-byte aligned; one wave per workgroup, so program order is the only sync.
-__device__ __forceinline__ float wave_sum_lds(float v, float* slot, int lane) {
-    v += dpp_f<DPP_QUAD_XOR1>(v);
-    v += dpp_f<DPP_QUAD_XOR2>(v);
-    v += dpp_f<DPP_ROW_HALF_MIRROR>(v);
-    v += dpp_f<DPP_ROW_MIRROR>(v);
-    slot[lane >> 4] = v;
-    wg_barrier();
-    const f4v r = *reinterpret_cast<const f4v*>(slot);
-    return (r.x + r.y) + (r.z + r.w);
-}
-
-// A/B alternative: the four row totals added by one v_mfma_f32_16x16x4_f32 against a vector of ones
-__device__ __forceinline__ float wave_sum_mfma(float v) {
-    v += dpp_f<DPP_QUAD_XOR1>(v);
-    v += dpp_f<DPP_QUAD_XOR2>(v);
-    v += dpp_f<DPP_ROW_HALF_MIRROR>(v);
-    v += dpp_f<DPP_ROW_MIRROR>(v);
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x4f32(v, 1.0f, z, 0, 0, 0);
-    return d[0];
-}
-template <int DB>
-__device__ __forceinline__ float dustbin_sum(float v, float* slot, int lane) {
-    if (DB == 5) return wave_sum_xbar(v, lane);
-    if (DB == 0 || DB >= 4) return wave_sum_uniform(v);
-    if (DB == 2) return wave_sum_mfma(v);
-    return wave_sum_lds(v, slot, lane);
-}
-
-// Column partials {c0,c1},{c2,c3},{c4,c5},{c6,c7} (this lane's eight rows) summed over the 8 lanes that share J;
-// lane (I, J) ends with the total of column 8J + I.  The exchange crosses 16-lane rows, where the VALU only has
-// v_permlane*_swap (3.4 ns each, six of them): instead every lane posts its eight partials at T[J][c][I]
-// (J-stride 72 floats: a 2-way bank conflict, free for ds_write_b32) and collects column I's eight as two
-// ds_read_b128.  T = 8 * 72 floats.
-__device__ __forceinline__ float reduce8_strided_lds(const f2v (&q)[4], float* T, int I, int J) {
-    float* w = T + J * 72 + I;
-#pragma unroll
-    for (int cp = 0; cp < 4; ++cp) {
-        w[(2 * cp) * 8] = q[cp].x;
-        w[(2 * cp + 1) * 8] = q[cp].y;
-    }
-    wg_barrier();
-    const float* r = T + J * 72 + I * 8;
-    const f4v u = *reinterpret_cast<const f4v*>(r), v = *reinterpret_cast<const f4v*>(r + 4);
-    return ((u.x + u.y) + (u.z + u.w)) + ((v.x + v.y) + (v.z + v.w));
 }
 
 // column partials {c0,c1},{c2,c3},{c4,c5},{c6,c7} reduced over the 8 lanes that share J; lane (I, J)
@@ -240,11 +176,6 @@ __device__ __forceinline__ void compute_result16(const float* rows, const float*
     }
 }
 
-// WAVES = waves per SIMD the register budget is cut for; CR = column reduction (0 swaps, 1 LDS); CF = cost build
-// (0 fp32 MFMA, 1 fp16-split operands); DB = dustbin
-// sums (0 DPP row broadcasts, 1 LDS, 2 MFMA, 4 dustbin ROW as a ninth register row: every lane keeps K[64][8J..8J+7],
-// the sum over the row is four packed FMAs and a three-step butterfly over the 8 lanes that share I).  The defaults are what
-// measured fastest (launch_third_fused3).
 #ifdef PATS_DIAG
 __device__ __forceinline__ unsigned wave_xor_bits(unsigned v) {
 #pragma unroll
@@ -260,7 +191,9 @@ __device__ __forceinline__ unsigned fbits(float x) { return __builtin_bit_cast(u
 // (-inf scores, ranges beyond 2^127) still goes to the log-sum-exp kernel.  A problem that never drifts runs bit-identically to ST = 0.
 // T = the descriptors' element type (cost65_device.hpp); only build_scores' descriptor loads see it.
 // CONF: compute_result16 also writes the per-match confidence conf [P,16].
-template <int CR, int DB, int CF, int ST, typename T = float, int CONF = 0>
+// DB (dustbin sums) and CF (cost build) are the diagnostic library's: DB = 0 DPP row broadcasts, 5 the LDS crossbar, issued ahead of
+// the FMAs; CF = 0 fp32 MFMA, 1 fp16-split operands.  Production is <0, 0> (launch_third_fused3).
+template <int DB, int CF, int ST, typename T = float, int CONF = 0>
 __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64_t p, Blk3Lds& lds, const int lane,
                                                float* conf = nullptr) {
     const int I = lane >> 3, J = lane & 7;
@@ -279,25 +212,18 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
     // ---- cost build (MFMA), then fragment layout -> permuted diagonal-pair blocks through LDS -----------
     f2v Pa[4][4], Pb[4][4];                  // [row pair][column pair], see the header
     float zdrow, zdcol, zcorner;
-    float zr8[8];                            // DB == 4: Z[64][8J .. 8J+7]
-    f2v kdr[4];                              // DB == 4: the same as K, in column pairs
     auto build_scores = [&]() {              // (ST: called again whenever the stabilisers move)
         Cost65Acc c;
-        if (DB == 9) {      // timing ablation only: no cost build (results are garbage)
-            for (int r = 0; r < 16; ++r) { c.c00[r] = (float)(lane + r) * 0.01f; c.c01[r] = -c.c00[r]; c.c10[r] = c.c00[r] * 0.5f; c.c11[r] = 0.25f; }
-            c.er0 = c.er1 = c.ec0 = c.ec1 = c.cn = 0.f;
-        } else if (DB == 7) {   // timing ablation only: descriptor loads without the MFMAs
-            cost65_accumulate<true>((const T*)g.d0 + p * (int64_t)g.D * 65, (const T*)g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
-        } else if (CF == 1) {   // fp16-split operands, three exact-product MFMA passes (cost65_device.hpp; float descriptors only)
+        if (CF == 1)        // fp16-split operands, three exact-product MFMA passes (cost65_device.hpp; float descriptors only)
             cost65_accumulate_f16x2(g.d0 + p * (int64_t)g.D * 65, g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
-        } else
-        cost65_accumulate((const T*)g.d0 + p * (int64_t)g.D * 65, (const T*)g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
+        else
+            cost65_accumulate((const T*)g.d0 + p * (int64_t)g.D * 65, (const T*)g.d1 + p * (int64_t)g.D * 65, g.D, lds.stage, lane, c);
         const int li = lane & 31, lk = lane >> 5;
         const Cost65Scale sq(g.D);
         // LDS offsets of this lane's eight register rows: matrix row 8I + rho(s, J), columns 4J..4J+3 of the parity
         int roff[8];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) roff[s] = (8 * I + ((s ^ J) ^ (s >= 4 ? 3 : 0))) * SST3 + 4 * J;
+        for (int s = 0; s < 8; ++s) roff[s] = (8 * I + ((s ^ J) ^ (s >= 4 ? 3 : 0))) * SST + 4 * J;
 #pragma unroll
         for (int tj = 0; tj < 2; ++tj) {
             const f32x16& even = tj == 0 ? c.c00 : c.c01;        // tile (ti, tj): element [r] <-> matrix (2 rc + ti, 2 li + tj)
@@ -306,8 +232,8 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rc = (r & 3) + 8 * (r >> 2) + 4 * lk;
-                lds.stage[(2 * rc) * SST3 + li] = cost65_scale(even[r], sq);
-                lds.stage[(2 * rc + 1) * SST3 + li] = cost65_scale(odd[r], sq);
+                lds.stage[(2 * rc) * SST + li] = cost65_scale(even[r], sq);
+                lds.stage[(2 * rc + 1) * SST + li] = cost65_scale(odd[r], sq);
             }
             wg_barrier();
 #pragma unroll
@@ -332,10 +258,6 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
         wg_barrier();
         zdrow = lds.erow[colj];          // Z[64][8J+I]
         zdcol = lds.ecol[lane];          // Z[8I+J][64]
-        if (DB == 4) {
-            const f4v e0 = *reinterpret_cast<const f4v*>(&lds.erow[8 * J]), e1 = *reinterpret_cast<const f4v*>(&lds.erow[8 * J + 4]);
-            zr8[0] = e0.x; zr8[1] = e0.y; zr8[2] = e0.z; zr8[3] = e0.w; zr8[4] = e1.x; zr8[5] = e1.y; zr8[6] = e1.z; zr8[7] = e1.w;
-        }
         wg_barrier();
         lds.erow[lane] = sx_lane;                        // the epilogue's target scales wait in the freed edge buffers
         lds.ecol[lane] = sy_lane;
@@ -358,22 +280,6 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) score_bits ^= __shfl_xor(score_bits * 2654435761u, off);
 #endif
-    if (DB == 6) {      // diagnostic: checksums of the score matrix this wave built (no solve)
-        float sblk = 0.f, sabs = 0.f;
-#pragma unroll
-        for (int sp = 0; sp < 4; ++sp)
-#pragma unroll
-            for (int cp = 0; cp < 4; ++cp) {
-                sblk += (Pa[sp][cp].x + Pa[sp][cp].y) + (Pb[sp][cp].x + Pb[sp][cp].y);
-                sabs += (fabsf(Pa[sp][cp].x) + fabsf(Pa[sp][cp].y)) + (fabsf(Pb[sp][cp].x) + fabsf(Pb[sp][cp].y));
-            }
-        const float a0 = wave_sum(sblk), a1 = wave_sum(sabs), a2 = wave_sum(zdrow), a3 = wave_sum(zdcol);
-        if (lane == 0) {
-            g.cr.mk1[p * 32 + 0] = a0; g.cr.mk1[p * 32 + 1] = a1; g.cr.mk1[p * 32 + 2] = a2; g.cr.mk1[p * 32 + 3] = a3;
-            g.cr.mk1[p * 32 + 4] = zcorner; g.cr.ifm[p * 16] = 0;
-        }
-        return;
-    }
 
     // ---- stabilisers r_i = max_j Z_ij, c_j = max_i (Z_ij - r_i); K = exp(Z - r - c) -----------------------
     float part[8];
@@ -389,7 +295,7 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
         part[2 * sp + 1] = mo;
     }
     const float r_own = fmaxf(reduce8_perm(part, OpMax()), zdcol);
-    const float r64 = uni3(fmaxf(wave_max(zdrow), zcorner));
+    const float r64 = uni(fmaxf(wave_max(zdrow), zcorner));
     float rl[8];
     gather_rows(r_own, rl);
     f2v cm[4];
@@ -406,7 +312,7 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
     }
     const float cpart[8] = {cm[0].x, cm[0].y, cm[1].x, cm[1].y, cm[2].x, cm[2].y, cm[3].x, cm[3].y};
     const float c_own = fmaxf(reduce8_strided(cpart, OpMax(), lane), zdrow - r64);
-    const float c64 = uni3(fmaxf(wave_max(zdcol - r_own), zcorner - r64));
+    const float c64 = uni(fmaxf(wave_max(zdcol - r_own), zcorner - r64));
     float kdcol, kdrow, kcorner;             // K[8I+J][64], K[64][8J+I], K[64][64]
     // K = exp(Z - r - c) from the scores in Pa / Pb and the edge scores, in place; rs / r64s / cs / c64s: this lane's row, the dustbin
     // row, this lane's column, the dustbin column
@@ -426,24 +332,18 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
                 Pa[sp][cp] = f2v{fast_exp2(((Pa[sp][cp].x - r0) - c0) * LOG2E), fast_exp2(((Pa[sp][cp].y - r1) - c1) * LOG2E)};
                 Pb[sp][cp] = f2v{fast_exp2(((Pb[sp][cp].x - r1) - c0) * LOG2E), fast_exp2(((Pb[sp][cp].y - r0) - c1) * LOG2E)};
             }
-        if (DB == 4) {
-#pragma unroll
-            for (int cp = 0; cp < 4; ++cp)
-                kdr[cp] = f2v{fast_exp2(((zr8[2 * cp] - r64s) - cl[2 * cp]) * LOG2E),
-                              fast_exp2(((zr8[2 * cp + 1] - r64s) - cl[2 * cp + 1]) * LOG2E)};
-        }
         kdcol = fast_exp2(((zdcol - rs) - c64s) * LOG2E);
         kdrow = fast_exp2(((zdrow - r64s) - cs) * LOG2E);
-        kcorner = uni3(fast_exp2(((zcorner - r64s) - c64s) * LOG2E));
+        kcorner = uni(fast_exp2(((zcorner - r64s) - c64s) * LOG2E));
     };
     exp_kernel(r_own, r64, c_own, c64);
     float r_t = r_own, r64_t = r64, c_t = c_own, c64_t = c64;      // ST: the stabilisers as they move
-    const float ns_sum = uni3(wave_sum(ns_lane));
-    const float ms = uni3(64.0f * one_v);
-    const float norm = uni3(-logf(ms + ns_sum));
-    const float lmu = norm, lmu64 = uni3(logf(ns_sum) + norm);
-    const float lnu = logf(ns_own) + norm, lnu64 = uni3(logf(ms) + norm);
-    const float mu = uni3(expf(lmu)), mu64 = uni3(expf(lmu64)), nu = expf(lnu), nu64 = uni3(expf(lnu64));
+    const float ns_sum = uni(wave_sum(ns_lane));
+    const float ms = uni(64.0f * one_v);
+    const float norm = uni(-logf(ms + ns_sum));
+    const float lmu = norm, lmu64 = uni(logf(ns_sum) + norm);
+    const float lnu = logf(ns_own) + norm, lnu64 = uni(logf(ms) + norm);
+    const float mu = uni(expf(lmu)), mu64 = uni(expf(lmu64)), nu = expf(lnu), nu64 = uni(expf(lnu64));
     float a = 0.f, a64 = 0.f, b = expf(c_own), b64 = expf(c64);
 #ifdef PATS_DIAG
     unsigned k_bits = fbits(kdcol) ^ (fbits(kdrow) * 3u) ^ (fbits(kcorner) * 5u) ^ (fbits(nu) * 7u) ^ (fbits(b) * 11u) ^
@@ -465,13 +365,6 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
         wg_barrier();                                 // b visible
         {   // a_i = mu_i / sum_j K_ij b_j
             const f4v b0 = *reinterpret_cast<const f4v*>(&lds.vb[8 * J]), b1 = *reinterpret_cast<const f4v*>(&lds.vb[8 * J + 4]);
-#ifdef PATS_EXP_LGKM0
-            {   // experiment: the two LDS reads have landed before any crossbar operation (ds_swizzle / ds_bpermute) is issued
-                f4v t0 = b0, t1 = b1;
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t0), "+v"(t1));
-                const_cast<f4v&>(b0) = t0; const_cast<f4v&>(b1) = t1;
-            }
-#endif
             const f2v bp[4] = {b0.xy, b0.zw, b1.xy, b1.zw};
             float dsum = 0.f;
             if (DB == 5) dsum = wave_sum_xbar(kdrow * b, lane);      // first: its two crossbar trips run under the FMAs
@@ -488,28 +381,11 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
                 for (int sp = 0; sp < 4; ++sp) acc[sp] = __builtin_elementwise_fma(Pb[sp][cp].yx, bp[cp].yx, acc[sp]);
             }
             const float rp[8] = {acc[0].x, acc[0].y, acc[1].x, acc[1].y, acc[2].x, acc[2].y, acc[3].x, acc[3].y};
-            if (DB == 5) {
-            } else if (DB == 4) {
-                f2v d = kdr[0] * bp[0];
-#pragma unroll
-                for (int cp = 1; cp < 4; ++cp) d = __builtin_elementwise_fma(kdr[cp], bp[cp], d);
-                float x = d.x + d.y;
-                x += dpp_f<DPP_QUAD_XOR1>(x);
-                x += dpp_f<DPP_QUAD_XOR2>(x);
-                x += dpp_f<DPP_ROW_HALF_MIRROR>(x);          // the 8 lanes that share I cover all 64 columns
-                dsum = x;
-            } else {
-                dsum = dustbin_sum<DB>(kdrow * b, lds.red, lane);
-            }
-            THIRD_PRIO(1);
+            if (DB != 5) dsum = wave_sum_uniform(kdrow * b);
             const float s = fmaf(kdcol, b64, reduce8_perm(rp, OpSum()));
             float rs = __builtin_amdgcn_rcpf(s), rd = __builtin_amdgcn_rcpf(fmaf(kcorner, b64, dsum));
-#ifdef PATS_EXP_RCP_NOPS
-            asm volatile("s_nop 1" : "+v"(rs), "+v"(rd));
-#endif
             a = mu * rs;
             a64 = mu64 * rd;
-            THIRD_PRIO(0);
         }
         {   // b_j = nu_j / sum_i K_ij a_i
             float dsum = 0.f;
@@ -529,18 +405,12 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
 #pragma unroll
                 for (int cp = 0; cp < 4; ++cp) q[cp] = __builtin_elementwise_fma(Pb[sp][cp], ap[sp].yx, q[cp]);
             }
-            if (DB != 5) dsum = dustbin_sum<DB>(kdcol * a, lds.red + 4, lane);
-            THIRD_PRIO(1);
-            const float t = fmaf(kdrow, a64, CR ? reduce8_strided_lds(q, lds.stage, I, J)
-                                                : reduce8_strided_pk(q[0], q[1], q[2], q[3], lane));
+            if (DB != 5) dsum = wave_sum_uniform(kdcol * a);
+            const float t = fmaf(kdrow, a64, reduce8_strided_pk(q[0], q[1], q[2], q[3], lane));
             float rt = __builtin_amdgcn_rcpf(t), rd = __builtin_amdgcn_rcpf(fmaf(kcorner, a64, dsum));
-#ifdef PATS_EXP_RCP_NOPS
-            asm volatile("s_nop 1" : "+v"(rt), "+v"(rd));
-#endif
             b = nu * rt;
             b64 = nu64 * rd;
             lds.vb[colj] = b;
-            THIRD_PRIO(0);
         }
         if (ST) {
             auto band = [](float x) { return x >= 9.5367431640625e-07f && x <= 1048576.0f; };       // [2^-20, 2^20]
@@ -569,7 +439,7 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
 #ifdef PATS_DIAG
     const unsigned ab_bits = wave_xor_bits(fbits(a) ^ (fbits(b) * 3u) ^ (fbits(a64) * 5u) ^ (fbits(b64) * 7u));
 #endif
-    if (!(__all(sc_ok3(a) && sc_ok3(b)) && sc_ok3(a64) && sc_ok3(b64))) {
+    if (!(__all(sc_ok(a) && sc_ok(b)) && sc_ok(a64) && sc_ok(b64))) {
         // guard tripped: the stabilised instantiation of this solve, then third_fused_kernel (log-sum-exp sweeps), redo this problem
         // in scan mode (ST: the sentinel is already there and the trip already counted)
         if (!ST && lane == 0) {
@@ -606,7 +476,6 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
         rows[((I - 2) * 8 + J) * RS3 + 64] = (kdcol * (a * en)) * b64;     // dustbin entry of the row this lane owns
     }
     wg_barrier();
-    if (DB == 8) { if (lane == 0) g.cr.ifm[p * 16] = 0; return; }      // timing ablation only: no Compute_result
     compute_result16<CONF>(rows, lds.erow, lds.ecol, p, (float)g.p_s[p * 2], (float)g.p_s[p * 2 + 1], (float)g.p_t[p * 2],
                            (float)g.p_t[p * 2 + 1], g.outdoor, g.cr, lane, conf);
 #ifdef PATS_DIAG
@@ -622,8 +491,10 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
 #endif
 }
 
-template <int WAVES, int CR, int DB, int CF = 0>
-__global__ void __launch_bounds__(64, WAVES)
+// DB, CF: third3_problem's.  Production instantiates <0, 0> only; the typed and confidence kernels below are kernels of their own
+// names so that this one's code - and tests/test_host_abi.py's one symbol - stays what it is.
+template <int DB, int CF>
+__global__ void __launch_bounds__(64, 3)
 third_fused3_kernel(Fused65Args g) {
     __shared__ Blk3Lds lds;
     const int lane = threadIdx.x;
@@ -633,11 +504,7 @@ third_fused3_kernel(Fused65Args g) {
     const int64_t p = blockIdx.x;
 #endif
     if (p >= live_problems(g)) return;
-    // de-phase the first wave-front (see sinkhorn65_kernel)
-    if (g.stagger > 0 && blockIdx.x < 8192u) {
-        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
-        for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
-    }
+    dephase_first_front<8192>(g.stagger);
 #ifdef PATS_DIAG
     // diagnostic library only: every LDS word starts as a caller-chosen bit pattern - a result that changes with the
     // pattern has read LDS it never wrote (tools/third_determinism.py LDSPOISON=1)
@@ -647,11 +514,10 @@ third_fused3_kernel(Fused65Args g) {
         wg_barrier();
     }
 #endif
-    third3_problem<CR, DB, CF, 0>(g, p, lds, lane);
+    third3_problem<DB, CF, 0>(g, p, lds, lane);
 }
 
-// The production instantiation (fp32-MFMA cost build, <3, 0, 0>) for float16 / bfloat16 descriptors.  A kernel of its own name:
-// third_fused3_kernel<3, 0, 0, 0> stays the one instantiation of that template in the production library.
+// The production instantiation for float16 / bfloat16 descriptors
 template <typename T>
 __global__ void __launch_bounds__(64, 3)
 third_fused3_typed_kernel(Fused65Args g) {
@@ -659,15 +525,11 @@ third_fused3_typed_kernel(Fused65Args g) {
     const int lane = threadIdx.x;
     const int64_t p = blockIdx.x;
     if (p >= live_problems(g)) return;
-    if (g.stagger > 0 && blockIdx.x < 8192u) {      // de-phase the first wave-front, as above
-        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
-        for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
-    }
-    third3_problem<0, 0, 0, 0, T>(g, p, lds, lane);
+    dephase_first_front<8192>(g.stagger);
+    third3_problem<0, 0, 0, T>(g, p, lds, lane);
 }
 
-// The production instantiation with the per-match confidence written beside mkpts1_f (conf [P,16]), for the three descriptor element
-// types.  Kernels of their own names, as above: the plain instantiations stay what they were, instruction for instruction.
+// ... and with the per-match confidence written beside mkpts1_f (conf [P,16]), for the three descriptor element types
 template <typename T>
 __global__ void __launch_bounds__(64, 3)
 third_fused3_conf_kernel(Fused65Args g, float* conf) {
@@ -675,32 +537,18 @@ third_fused3_conf_kernel(Fused65Args g, float* conf) {
     const int lane = threadIdx.x;
     const int64_t p = blockIdx.x;
     if (p >= live_problems(g)) return;
-    if (g.stagger > 0 && blockIdx.x < 8192u) {      // de-phase the first wave-front, as above
-        const unsigned slots = (blockIdx.x * 2654435761u) >> 29;
-        for (unsigned q = 0; q < slots * (unsigned)g.stagger; ++q) __builtin_amdgcn_s_sleep(127);
-    }
-    third3_problem<0, 0, 0, 0, T, 1>(g, p, lds, lane, conf);
+    dephase_first_front<8192>(g.stagger);
+    third3_problem<0, 0, 0, T, 1>(g, p, lds, lane, conf);
 }
 
-// The stabilised solve over the problems the launch above flagged: the W workgroups share the problems interleaved, as
-// third_fused_kernel's scan mode does (third_fused.hip) - which runs behind this one for what is still flagged.
+// The stabilised solve over the problems the launch above flagged (third_redo_walk, third_device.hpp); third_fused_kernel's scan
+// mode (third_fused.hip) runs behind this one for what is still flagged.
 template <typename T = float>       // the descriptors' element type
 __global__ void __launch_bounds__(64, 2)
 third_fused3_stab_kernel(Fused65Args g) {
     __shared__ Blk3Lds lds;
     const int lane = threadIdx.x;
-    const int64_t W = gridDim.x, live = live_problems(g);
-    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
-        const int64_t cand = first + (int64_t)lane * W;
-        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
-        unsigned long long todo = __ballot(redo);
-        while (todo) {
-            const int k = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            wg_barrier();
-            third3_problem<0, 0, 0, 1, T>(g, first + (int64_t)k * W, lds, lane);
-        }
-    }
+    third_redo_walk(g, lane, [&](int64_t p) { third3_problem<0, 0, 1, T>(g, p, lds, lane); });
 }
 // ... and with the confidence of the re-solved plan
 template <typename T>
@@ -708,18 +556,7 @@ __global__ void __launch_bounds__(64, 2)
 third_fused3_stab_conf_kernel(Fused65Args g, float* conf) {
     __shared__ Blk3Lds lds;
     const int lane = threadIdx.x;
-    const int64_t W = gridDim.x, live = live_problems(g);
-    for (int64_t first = blockIdx.x; first < live; first += 64 * W) {
-        const int64_t cand = first + (int64_t)lane * W;
-        const bool redo = cand < live && g.cr.ifm[cand * 16] == THIRD_REDO;
-        unsigned long long todo = __ballot(redo);
-        while (todo) {
-            const int k = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            wg_barrier();
-            third3_problem<0, 0, 0, 1, T, 1>(g, first + (int64_t)k * W, lds, lane, conf);
-        }
-    }
+    third_redo_walk(g, lane, [&](int64_t p) { third3_problem<0, 0, 1, T, 1>(g, p, lds, lane, conf); });
 }
 
 int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf) {
@@ -741,75 +578,44 @@ int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf) {
     // clean), not the memory (a warm-up on COPIES of the inputs removes it, reading every input byte first does not), not the
     // first wave front's phase (any stagger) - but not to a cause, and one of 60 fresh processes had a problem 0.25 px off
     // (the parity gate is 2.4e-3 px).  The contract (bit-identical results from launch 0) decides: the production library
-    // holds the fp32-MFMA build ONLY; the fp16-split build lives in libpats_amd_diag.so with the other experiments.
+    // holds the fp32-MFMA build ONLY; the fp16-split build lives in libpats_amd_diag.so, for the study of that divergence.
     static const int variant = diag_env("PATS_THIRD_VARIANT") ? atoi(diag_env("PATS_THIRD_VARIANT")) : 300;
 #ifndef PATS_DIAG
-    // The production library carries exactly ONE instantiation: the fp32-MFMA cost build, reproducible from the first launch of
-    // a process.  The fp16-split cost build (1350), every other sweep-loop variant and every timing ablation (builds whose
-    // results are wrong by design) live in libpats_amd_diag.so only (`python -m pats_amd.build --diag`, PATS_AMD_DIAG_LIB=1).
+    // The production library carries exactly ONE instantiation of third_fused3_kernel: the fp32-MFMA cost build, reproducible from
+    // the first launch of a process.  The others live in libpats_amd_diag.so only (`python -m pats_amd.build --diag`,
+    // PATS_AMD_DIAG_LIB=1).
     PATS_REQUIRE(variant == 300,
                  "PATS_THIRD_VARIANT=%d is a diagnostic build: it is compiled into libpats_amd_diag.so only "
                  "(python -m pats_amd.build --diag; PATS_AMD_DIAG_LIB=1)", variant);
-    if (conf) {
-        if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_conf_kernel<_Float16>, grid, block, 0, st, g, conf);
-        else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_conf_kernel<bf16_t>, grid, block, 0, st, g, conf);
-        else hipLaunchKernelGGL(third_fused3_conf_kernel<float>, grid, block, 0, st, g, conf);
-    }
-    else if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_typed_kernel<_Float16>, grid, block, 0, st, g);
-    else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_typed_kernel<bf16_t>, grid, block, 0, st, g);
-    else hipLaunchKernelGGL((third_fused3_kernel<3, 0, 0>), grid, block, 0, st, g);       // fp32 MFMA cost build
+    for_elem_type(g.dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        if (conf) hipLaunchKernelGGL(third_fused3_conf_kernel<T>, grid, block, 0, st, g, conf);
+        else if constexpr (std::is_same<T, float>::value) hipLaunchKernelGGL((third_fused3_kernel<0, 0>), grid, block, 0, st, g);
+        else hipLaunchKernelGGL(third_fused3_typed_kernel<T>, grid, block, 0, st, g);
+        return 0;
+    });
 #else
     PATS_REQUIRE(g.dtype == PATS_MAP_F32, "third_level: the diagnostic library's sweep-loop variants take float32 descriptors only");
     PATS_REQUIRE(!conf, "third_level: the diagnostic library's sweep-loop variants do not write the confidence");
-    // last digit (dustbin sums) 6..9 = diagnostic / timing-ablation builds whose RESULTS ARE NOT the solve: never by accident
-    static const bool ablation_ok = diag_env("PATS_THIRD_ABLATION") != nullptr;
-    PATS_REQUIRE(ablation_ok || variant % 10 < 6,
-                 "PATS_THIRD_VARIANT=%d is a timing ablation (wrong results by design); set PATS_THIRD_ABLATION=1 to run it", variant);
-    // experiment: extra dynamic LDS per workgroup lowers the occupancy (12 workgroups per CU at 10 KB; 40 KB -> 4 = one wave per SIMD)
-    const unsigned lds_pad = diag_env("PATS_THIRD_LDS_PAD") ? (unsigned)atoi(diag_env("PATS_THIRD_LDS_PAD")) : 0u;
-    switch (variant) {          // digits: waves per SIMD, column reduction, dustbin sums
-        case 311: hipLaunchKernelGGL((third_fused3_kernel<3, 1, 1>), grid, block, lds_pad, st, g); break;
-        case 306: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 6, 0>), grid, block, lds_pad, st, g); break;
-        case 1306: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 6, 1>), grid, block, lds_pad, st, g); break;
-        case 1307: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 7, 1>), grid, block, lds_pad, st, g); break;
-        case 1308: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 8, 1>), grid, block, lds_pad, st, g); break;
-        case 1309: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 9, 1>), grid, block, lds_pad, st, g); break;
-        case 1340: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 4, 1>), grid, block, lds_pad, st, g); break;
-        case 350: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 5, 0>), grid, block, lds_pad, st, g); break;      // fp32 MFMA, LDS dustbin sums
-        case 1350: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 5, 1>), grid, block, lds_pad, st, g); break;
-        case 1400: hipLaunchKernelGGL((third_fused3_kernel<4, 0, 0, 1>), grid, block, lds_pad, st, g); break;
-        case 1301: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 1, 1>), grid, block, lds_pad, st, g); break;
-        case 1310: hipLaunchKernelGGL((third_fused3_kernel<3, 1, 0, 1>), grid, block, lds_pad, st, g); break;
-        case 1311: hipLaunchKernelGGL((third_fused3_kernel<3, 1, 1, 1>), grid, block, lds_pad, st, g); break;
-        case 301: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 1>), grid, block, lds_pad, st, g); break;
-        case 302: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 2>), grid, block, lds_pad, st, g); break;
-        case 307: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 7>), grid, block, lds_pad, st, g); break;
-        case 308: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 8>), grid, block, lds_pad, st, g); break;
-        case 309: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 9>), grid, block, lds_pad, st, g); break;
-        case 310: hipLaunchKernelGGL((third_fused3_kernel<3, 1, 0>), grid, block, lds_pad, st, g); break;
-        case 400: hipLaunchKernelGGL((third_fused3_kernel<4, 0, 0>), grid, block, lds_pad, st, g); break;
-        case 401: hipLaunchKernelGGL((third_fused3_kernel<4, 0, 1>), grid, block, lds_pad, st, g); break;
-        case 410: hipLaunchKernelGGL((third_fused3_kernel<4, 1, 0>), grid, block, lds_pad, st, g); break;
-        case 411: hipLaunchKernelGGL((third_fused3_kernel<4, 1, 1>), grid, block, lds_pad, st, g); break;
-        case 300: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 0>), grid, block, lds_pad, st, g); break;     // fp32 MFMA cost build
-        case 1300: hipLaunchKernelGGL((third_fused3_kernel<3, 0, 0, 1>), grid, block, lds_pad, st, g); break;    // row-broadcast dustbin sums
-        default:  hipLaunchKernelGGL((third_fused3_kernel<3, 0, 5, 1>), grid, block, lds_pad, st, g); break;
+    switch (variant) {          // thousands: cost build (0 fp32 MFMA, 1 fp16-split operands); tens: dustbin sums (0 row broadcasts, 5 LDS crossbar)
+        case 300: hipLaunchKernelGGL((third_fused3_kernel<0, 0>), grid, block, 0, st, g); break;
+        case 350: hipLaunchKernelGGL((third_fused3_kernel<5, 0>), grid, block, 0, st, g); break;
+        case 1300: hipLaunchKernelGGL((third_fused3_kernel<0, 1>), grid, block, 0, st, g); break;
+        case 1350: hipLaunchKernelGGL((third_fused3_kernel<5, 1>), grid, block, 0, st, g); break;
+        default: PATS_REQUIRE(false, "PATS_THIRD_VARIANT=%d: the diagnostic library holds 300, 350, 1300 and 1350", variant);
     }
 #endif
     int rc = check_launch("third_fused3_kernel");
     if (rc) return rc;
     static const bool no_stab = [] { const char* e = env_switch("PATS_THIRD_STAB"); return e && atoi(e) == 0; }();      // A/B switch
     if (!no_stab && g.iters > 0) {
-        const int64_t waves = g.P < 6144 ? g.P : 6144;            // two rounds of the 3 072 wave slots: flagged runs spread out
-        const dim3 sgrid((unsigned)(waves > 0 ? waves : 1));
-        if (conf) {
-            if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_stab_conf_kernel<_Float16>, sgrid, dim3(64), 0, st, g, conf);
-            else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_stab_conf_kernel<bf16_t>, sgrid, dim3(64), 0, st, g, conf);
-            else hipLaunchKernelGGL(third_fused3_stab_conf_kernel<float>, sgrid, dim3(64), 0, st, g, conf);
-        }
-        else if (g.dtype == PATS_MAP_F16) hipLaunchKernelGGL(third_fused3_stab_kernel<_Float16>, sgrid, dim3(64), 0, st, g);
-        else if (g.dtype == PATS_MAP_BF16) hipLaunchKernelGGL(third_fused3_stab_kernel<bf16_t>, sgrid, dim3(64), 0, st, g);
-        else hipLaunchKernelGGL(third_fused3_stab_kernel<float>, sgrid, dim3(64), 0, st, g);
+        const dim3 sgrid(third_walk_grid(g.P));
+        for_elem_type(g.dtype, [&](auto tag) {
+            typedef typename decltype(tag)::type T;
+            if (conf) hipLaunchKernelGGL(third_fused3_stab_conf_kernel<T>, sgrid, dim3(64), 0, st, g, conf);
+            else hipLaunchKernelGGL(third_fused3_stab_kernel<T>, sgrid, dim3(64), 0, st, g);
+            return 0;
+        });
         rc = check_launch("third_fused3_stab_kernel");
     }
     return rc;

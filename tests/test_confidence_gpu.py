@@ -178,6 +178,49 @@ def test_half_descriptors_give_the_bits_of_the_float_copies(ops, inputs, wild, d
             assert len(plain) == len(a) - 1 and all(same_bits(x, y) for x, y in zip(plain, a)), (dt, P, kw)
 
 
+@pytest.mark.parametrize("dt", [torch.float32, torch.float16])
+def test_confidence_kernels_walk_past_the_grid_and_on_upper_ballot_lanes(ops, wild, dt):
+    """The confidence kernels' re-solve walks (third_fused3_stab_conf_kernel, third_fused_conf_kernel in scan mode) at more
+    problems than the walk has workgroups: 6144 + 70 problems gathered from the 96-problem base set as
+    tests/test_half_desc_gpu.py::test_third_level_redo_walk_reads_half_descriptors gathers its launch, wild problems in the first
+    6144 and in the 70 beyond, where a workgroup's ballot has them in lane 1.  Problems are independent and results bit-identical
+    by contract, so every row must carry the bits of its base problem in the 96-problem launch, the confidence included."""
+    from test_third_redo_walk_gpu import K, NWILD, W, walk_slot
+    P = W + 70
+    rng = np.random.default_rng(23)
+    idx = rng.integers(NWILD, K, P)
+    idx[rng.choice(W, 400, replace=False)] = rng.integers(0, NWILD, 400)      # wild problems in the first 6144 ...
+    idx[W + 3:W + 67] = np.arange(64) % NWILD                                 # ... and beyond: each base problem twice
+    base = (wild[0].to(dt), wild[1].to(dt)) + wild[2:]
+    # which of the 32 wild base problems trip the guard, each launched alone
+    trips = np.zeros(K, np.int64)
+    for b in range(NWILD):
+        ops.sinkhorn_fallbacks(reset=True)
+        ops.third_level(*(t[b:b + 1] for t in base), outdoor=True, return_confidence=True)
+        trips[b] = ops.sinkhorn_fallbacks(reset=True)
+    assert trips[:NWILD].tolist() == [1] * NWILD, "every wild base problem must trip the guard once: %s" % trips[:NWILD]
+    # conditions of the test, on the CPU: a problem that trips beyond the grid, and one that a ballot lane above 0 claims
+    tripping = [p for p in range(P) if trips[idx[p]]]
+    assert any(p >= W for p in tripping) and any(walk_slot(p, P)[1] > 0 for p in tripping)
+    assert any(p < W for p in tripping) and all(walk_slot(p, P) == (p - W, 1, 0) for p in range(W, P))
+
+    ops.sinkhorn_fallbacks(reset=True)
+    ref = run(ops, base, K, return_confidence=True)
+    assert ops.sinkhorn_fallbacks(reset=True) == trips.sum()
+    sel = cu(idx.astype(np.int64))
+    ops.sinkhorn_fallbacks(reset=True)
+    got = ops.third_level(*(torch.index_select(t, 0, sel) for t in base), outdoor=True, return_confidence=True)
+    counted = ops.sinkhorn_fallbacks(reset=True)
+    assert len(got) == 5 and counted == int((idx < NWILD).sum()), "%d guard trips counted, %d wild problems gathered" % (
+        counted, (idx < NWILD).sum())
+    for name, g, r in zip(("mkpts0_f", "mkpts1_f", "label", "if_matching1", "conf"), got, ref):
+        if name == "label":
+            g, r = g.view(P, 16, 2), r.view(K, 16, 2)
+        assert same_bits(g, r[sel]), "%s (%s): a row differs from its base problem in the 96-problem launch" % (name, dt)
+    c = got[4]
+    assert bool(torch.isfinite(c).all()) and float(c.min()) >= 0.0 and float(c.max()) <= 1.0
+
+
 @pytest.mark.parametrize("count", [0, 1, 66, 67])
 def test_counted_launch_writes_the_rows_below_the_count_only(ops, inputs, wild, count):
     full = run(ops, inputs, P_FULL, return_confidence=True)
