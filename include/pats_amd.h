@@ -753,6 +753,45 @@ int pats_topk_by_pair_f32(const float* matches_l, const float* matches_r, const 
                           pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-pair spread top-K (ABI 8, symbols added): the sibling of the per-pair top-K that spreads the selection over the image.  A
+ * grid of square cells lies over the points of ONE side; every cell keeps its most confident eligible match, and the K most
+ * confident of these winners are the pair's selection, left in the form of the per-pair top-K: whatever reads that result reads
+ * this one.  Exact and deterministic, ONE launch for the whole batch, no host read.
+ * For pair p let lo, hi, n and i be as in "Per-pair top-K", and key(i) and eligible exactly as defined there.  Further arguments:
+ *   side         0 = cells over matches_l, 1 = cells over matches_r
+ *   cell         an integer number of pixels, 1 .. 65536
+ *   grid0, grid1 cells along component 0 and component 1 of the stored (c0, c1) points; both >= 1 and grid0 * grid1 <= max_cells
+ * Definition
+ *   u_a(i)     component a of the point of match i on the chosen side (float32)
+ *   q_a(i)     u_a > 0 ? (int)min(u_a, 16777216.0f) : 0: a NaN, a negative value and -inf give 0, +inf gives 2^24; the floor of a
+ *              float, exact
+ *   c_a(i)     min(q_a / cell, grid_a - 1): integer division; a point outside the grid falls into the edge cell
+ *   cellid(i)  c_0 * grid1 + c_1
+ *   winner(g)  among the ELIGIBLE matches with cellid == g: the largest key, ties by the lowest i; a cell without an eligible match
+ *              has none
+ *   ranking    the winners by key descending, ties by i ascending
+ *   occupied   [pairs] int64: the number of winners (cells with at least one eligible match)
+ *   top_count  [pairs] int64: min(K, occupied)
+ *   top_l, top_r, top_conf, top_idx: as in "Per-pair top-K" over that ranking - bit-for-bit copies for j < count, -1 / 0.0 behind it
+ * It follows that every call defines every byte of every output; that the result does not depend on any order of execution; that a
+ * batch in which no two eligible matches of a pair share a cell returns exactly what pats_topk_by_pair_f32 returns; and that
+ * grid0 = grid1 = 1 returns each pair's single best eligible match.  The selection is NOT a subset of the plain top-K.
+ * max_cells = pats_topk_spread_by_pair_max_cells() = 16384: the cell table of one pair lives in LDS at 8 bytes per cell (128 KiB
+ * of the 160 a workgroup may allocate; a launch asks for what its grid needs, rounded up to a power of two).  With K <= 8192 more
+ * cells buy nothing; a caller whose grid is larger takes a larger cell.
+ * Refused before any launch (pats_last_error names the argument), in this order: everything pats_topk_by_pair_f32 refuses; occupied
+ * null or off 8 bytes; side not 0 or 1; cell outside 1 .. 65536; grid0 < 1; grid1 < 1; grid0 * grid1 > max_cells.  cap == 0 is a
+ * valid call.  PATS_ERR_UNSUPPORTED if the device refuses the LDS a grid above 8192 cells needs.  The workspace query answers 0
+ * today (workspace may then be null). */
+int64_t pats_topk_spread_by_pair_max_cells(void);
+size_t pats_topk_spread_by_pair_workspace_bytes(int64_t pairs, int64_t K, int64_t grid0, int64_t grid1);
+int pats_topk_spread_by_pair_f32(const float* matches_l, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                 int64_t pairs, int64_t cap, int64_t K, int use_min_conf, float min_conf, int side, int64_t cell,
+                                 int64_t grid0, int64_t grid1, float* top_l, float* top_r, float* top_conf, int32_t* top_idx,
+                                 int64_t* top_count, int64_t* occupied, void* workspace, size_t workspace_bytes,
+                                 pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-pair model verification (ABI 8, symbols added): H candidate epipolar models per pair tested against every match of the
  * pair, the model with the most inliers, its inlier mask and - on request - the moment matrix of its inliers.  The O(H M) step
  * of a hypothesise-and-verify search on the hand-over (or on a per-pair top-K of it), on the device, no host read; everything

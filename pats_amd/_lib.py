@@ -236,6 +236,12 @@ SIGNATURES = {
     "pats_topk_by_pair_workspace_bytes": (c_size, [c_i64, c_i64]),
     "pats_topk_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_f, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # per-pair spread top-K: one winner per image cell, the K most confident winners (csrc/topk_spread.hip)
+    "pats_topk_spread_by_pair_max_cells": (c_i64, []),
+    "pats_topk_spread_by_pair_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_i64]),
+    "pats_topk_spread_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_f, c_int, c_i64,
+                                             c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_size, c_void_p]),
     # per-pair verification of candidate epipolar models (csrc/epipolar.hip)
     "pats_epipolar_max_h": (c_i64, []),
     "pats_epipolar_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),

@@ -425,17 +425,12 @@ def split_by_pair(out, cap):
     return _caller_order(out, cap, per_slot)
 
 
-def topk_by_pair(out, cap, K, min_conf=None):
-    """Device side, after (or instead of) group_by_pair: each pair's K most confident matches (ops.topk_by_pair: one launch over
-    all pairs, no host read; confidence descending, ties by the position in the pair's list; min_conf keeps conf >= min_conf).
-    Needs a result made with confidence=True.  Adds `topk` = (top_l [pairs,K,2], top_r [pairs,K,2], top_conf [pairs,K],
-    top_idx [pairs,K] int32, top_count [pairs] int64) to the result and returns it; rows in SLOT order for a mixed pack
-    (split_topk_by_pair hands them back in the caller's).  If the result is not regrouped yet this does it, with ONE int64 buffer
-    of (pairs + 4) + pairs entries - group_by_pair's summary, then top_count - kept as `topk_summary`: the whole hand-over is then
-    still one device-to-host copy.  After a group_by_pair of the caller's own, top_count is a tensor of its own.  Nothing is
-    removed from the full lists: this is a selection by the third level's confidence alone - no mutual check, no suppression."""
+def _topk_lists(fn, out, cap):
+    """What topk_by_pair and topk_spread_by_pair do in front of their launch -> (matches_l, matches_r, conf, top_count's place or
+    None): the regrouped lists, regrouped here if they are not yet - then with ONE int64 buffer of (pairs + 4) + pairs entries,
+    group_by_pair's summary and behind it top_count's place, kept as `topk_summary`.  None: the caller regrouped on its own."""
     if "match_conf" not in out:
-        raise ValueError("topk_by_pair: needs a result made with confidence=True")
+        raise ValueError("%s: needs a result made with confidence=True" % fn)
     top_count = None
     if "by_pair" not in out:
         ml, mr, mc = out["matches_l"], out["matches_r"], out["match_conf"]
@@ -448,13 +443,68 @@ def topk_by_pair(out, cap, K, min_conf=None):
         else:
             del out["topk_summary"]
     ml, mr, _, mc = out["by_pair"]
+    return ml, mr, mc, top_count
+
+
+def _topk_dest(cap, K, dev, top_count):
+    """topk_by_pair's five destinations around a top_count that lives in `topk_summary`."""
+    K = int(K)
+    return (torch.empty((cap.pairs, K, 2), dtype=torch.float32, device=dev), torch.empty((cap.pairs, K, 2), dtype=torch.float32, device=dev),
+            torch.empty((cap.pairs, K), dtype=torch.float32, device=dev), torch.empty((cap.pairs, K), dtype=torch.int32, device=dev),
+            top_count)
+
+
+def topk_by_pair(out, cap, K, min_conf=None):
+    """Device side, after (or instead of) group_by_pair: each pair's K most confident matches (ops.topk_by_pair: one launch over
+    all pairs, no host read; confidence descending, ties by the position in the pair's list; min_conf keeps conf >= min_conf).
+    Needs a result made with confidence=True.  Adds `topk` = (top_l [pairs,K,2], top_r [pairs,K,2], top_conf [pairs,K],
+    top_idx [pairs,K] int32, top_count [pairs] int64) to the result and returns it; rows in SLOT order for a mixed pack
+    (split_topk_by_pair hands them back in the caller's).  If the result is not regrouped yet this does it, with ONE int64 buffer
+    of (pairs + 4) + pairs entries - group_by_pair's summary, then top_count - kept as `topk_summary`: the whole hand-over is then
+    still one device-to-host copy.  After a group_by_pair of the caller's own, top_count is a tensor of its own.  Nothing is
+    removed from the full lists: this is a selection by the third level's confidence alone - no mutual check, no suppression."""
+    ml, mr, mc, top_count = _topk_lists("topk_by_pair", out, cap)
+    dest = None if top_count is None else _topk_dest(cap, K, ml.device, top_count)
+    out["topk"] = ops.topk_by_pair(ml, mr, mc, out["summary"], K, min_conf=min_conf, out=dest, pairs=cap.pairs)
+    out.pop("topk_spread", None)                    # the rows are no spread selection any more
+    return out["topk"]
+
+
+def _spread_grid(cap, cell):
+    """The grid of `cell`-pixel cells over the largest image of the batch, (ceil(32 h / cell), ceil(32 w / cell)) - for mixed shapes
+    the largest h and the largest w: smaller pairs leave cells empty.  ValueError if the kernel's table cannot hold it."""
+    if int(cell) != cell or not 1 <= cell <= 65536:
+        raise ValueError("topk_spread_by_pair: cell = %r must be an integer number of pixels, 1 .. 65536" % (cell,))
+    shapes = cap.shapes if hasattr(cap, "shapes") else [(cap.h, cap.w)]
+    H, W = 32 * max(h for h, _ in shapes), 32 * max(w for _, w in shapes)
+
+    def grid(c):
+        return -(-H // c), -(-W // c)
+
+    g, most = grid(int(cell)), ops.topk_spread_max_cells()
+    if g[0] * g[1] > most:
+        fits = next(c for c in range(int(cell) + 1, max(H, W) + 1) if grid(c)[0] * grid(c)[1] <= most)      # 1 x 1 at max(H, W)
+        raise ValueError("topk_spread_by_pair: cell = %d makes %d x %d cells on %d x %d pixels, more than max_cells = %d; the "
+                         "smallest cell that fits is %d" % (cell, g[0], g[1], H, W, most, fits))
+    return g
+
+
+def topk_spread_by_pair(out, cap, K, cell, min_conf=None, side="left"):
+    """topk_by_pair's sibling that spreads the selection over the image (ops.topk_spread_by_pair: one launch over all pairs, no host
+    read): a grid of `cell`-pixel cells over the `side` ("left" / "right") image, (ceil(32 h / cell), ceil(32 w / cell)) of them for
+    the batch's largest h and w; each cell keeps its most confident match with conf >= min_conf, each pair the K most confident of
+    these.  Needs a result made with confidence=True and regroups like topk_by_pair (`topk_summary`).  Stores `topk`, the same
+    five-tuple in the same order of the rows - split_topk_by_pair and every on="topk" stage work on it unchanged; top_count =
+    min(K, occupied) - and `topk_spread` = (occupied [pairs] int64, cell, (grid0, grid1), side); returns `topk`.  A later plain
+    topk_by_pair removes `topk_spread`.  Nothing is removed from the full lists.  ValueError for a grid above
+    ops.topk_spread_max_cells(): it names the smallest cell that fits."""
+    grid = _spread_grid(cap, cell)
+    ml, mr, mc, top_count = _topk_lists("topk_spread_by_pair", out, cap)
     dest = None
     if top_count is not None:
-        dev, K = ml.device, int(K)
-        dest = (torch.empty((cap.pairs, K, 2), dtype=torch.float32, device=dev), torch.empty((cap.pairs, K, 2), dtype=torch.float32, device=dev),
-                torch.empty((cap.pairs, K), dtype=torch.float32, device=dev), torch.empty((cap.pairs, K), dtype=torch.int32, device=dev),
-                top_count)
-    out["topk"] = ops.topk_by_pair(ml, mr, mc, out["summary"], K, min_conf=min_conf, out=dest, pairs=cap.pairs)
+        dest = _topk_dest(cap, K, ml.device, top_count) + (torch.empty((cap.pairs,), dtype=torch.int64, device=ml.device),)
+    got = ops.topk_spread_by_pair(ml, mr, mc, out["summary"], K, int(cell), grid, side=side, min_conf=min_conf, out=dest, pairs=cap.pairs)
+    out["topk"], out["topk_spread"] = got[:5], (got[5], int(cell), grid, side)
     return out["topk"]
 
 

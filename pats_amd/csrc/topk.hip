@@ -14,11 +14,10 @@
 //   write    rows 0 .. count - 1 gathered through the sorted indices, the tail filled (-1 / 0.0): every output byte is defined
 #include "common.hpp"
 #include "lane_reduce.hpp"
+#include "topk_shared.hpp"
 
 namespace pats {
 
-constexpr int TOPK_THREADS = 1024;
-constexpr int TOPK_WAVES = TOPK_THREADS / WAVE;
 constexpr int TOPK_SORT_CAP = 8192;             // composites the sort buffer holds = pats_topk_by_pair_max_k(): 64 KB of LDS
 constexpr int TOPK_WHOLE = 4096;                // segments up to this length are sorted whole (no select): 78 sort steps at most
 constexpr uint32_t TOPK_ALL = 0x7fffffffu;      // r = "every key equal to T" (a segment holds fewer rows than this)
@@ -28,8 +27,6 @@ struct TopkArgs {
     int64_t cap; int K; uint32_t thr;           // thr = key(min_conf), 0 without a threshold: every key is >= 0
     float* top_l; float* top_r; float* top_conf; int32_t* top_idx; int64_t* top_count;
 };
-
-__host__ __device__ __forceinline__ uint32_t topk_key(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
 
 // one radix pass: hist[d] = number of eligible keys of the segment that agree with `prefix` above `shift + 8` and have digit d at
 // `shift`.  Confidences cluster (most of a pair's share the exponent byte), so a wave whose active lanes all hold one digit adds
@@ -65,11 +62,7 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_by_pair_kernel(TopkArgs g) 
     const int64_t p = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t K = (uint32_t)g.K;
-    // a stale or corrupt pair_off never reaches outside the arrays: both ends clamped to [0, cap], hi <= lo = empty
-    int64_t lo = g.pair_off[p], hi = g.pair_off[p + 1];
-    lo = lo < 0 ? 0 : (lo > g.cap ? g.cap : lo);
-    hi = hi < 0 ? 0 : (hi > g.cap ? g.cap : hi);
-    const uint32_t n = hi > lo ? (uint32_t)(hi - lo) : 0u;    // cap < 2^31 (checked on the host)
+    PATS_TOPK_SEGMENT(g.pair_off, p, g.cap);                  // lo, n: the pair's rows, inside the arrays whatever pair_off holds
     const uint32_t* bits = reinterpret_cast<const uint32_t*>(g.conf) + lo;
 
     // ---- select: T and r ---------------------------------------------------------------------------------------------------
@@ -135,7 +128,7 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_by_pair_kernel(TopkArgs g) 
         if (gt || (eq && eq_before < r)) {                    // slot = selected rows in front: all the greater, the first r equal
             const uint32_t slot = gt_before + (eq_before < r ? eq_before : r);
             if (slot < (uint32_t)TOPK_SORT_CAP)               // holds by construction (at most TOPK_WHOLE or K rows are selected)
-                buf[slot] = ((unsigned long long)k << 32) | (unsigned long long)(0xFFFFFFFFu - i);
+                buf[slot] = topk_composite(k, i);
         }
         gt_run += gt_tile; eq_run += eq_tile;                 // the other buffer is written next: one barrier per tile
     }
@@ -196,21 +189,7 @@ extern "C" int pats_topk_by_pair_f32(const float* matches_l, const float* matche
                                      float* top_r, float* top_conf, int32_t* top_idx, int64_t* top_count, void* workspace,
                                      size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("topk_by_pair", matches_l, 8);
-    PATS_REQUIRE_PTR("topk_by_pair", matches_r, 8);
-    PATS_REQUIRE_PTR("topk_by_pair", conf, 4);
-    PATS_REQUIRE_PTR("topk_by_pair", pair_off, 8);
-    PATS_REQUIRE_PTR("topk_by_pair", top_l, 8);
-    PATS_REQUIRE_PTR("topk_by_pair", top_r, 8);
-    PATS_REQUIRE_PTR("topk_by_pair", top_conf, 4);
-    PATS_REQUIRE_PTR("topk_by_pair", top_idx, 4);
-    PATS_REQUIRE_PTR("topk_by_pair", top_count, 8);
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "topk_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(cap >= 0 && cap < 0x7fffffff, "topk_by_pair: cap = %lld (0 .. 2^31 - 2: top_idx is int32)", (long long)cap);
-    PATS_REQUIRE(K >= 1 && K <= pats_topk_by_pair_max_k(), "topk_by_pair: K = %lld (1 .. max_k = %lld)", (long long)K,
-                 (long long)pats_topk_by_pair_max_k());
-    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "topk_by_pair: min_conf = %g must be a non-negative number", (double)min_conf);
-    PATS_REQUIRE(workspace_bytes >= pats_topk_by_pair_workspace_bytes(pairs, K), "topk_by_pair: workspace too small");
+    PATS_TOPK_REQUIRE_ARGS("topk_by_pair", pats_topk_by_pair_workspace_bytes(pairs, K));
     TopkArgs g{matches_l, matches_r, conf, pair_off, cap, (int)K, use_min_conf ? topk_key(__builtin_bit_cast(uint32_t, min_conf)) : 0u,
                top_l, top_r, top_conf, top_idx, top_count};
     hipLaunchKernelGGL(topk_by_pair_kernel, dim3((unsigned)pairs), dim3(TOPK_THREADS), 0, as_stream(stream), g);

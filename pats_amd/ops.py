@@ -1692,6 +1692,24 @@ def topk_max_k():
     return int(_L().pats_topk_by_pair_max_k())
 
 
+def _topk_inputs(fn, matches_l, matches_r, conf, pair_off, K, pairs):
+    """What topk_by_pair and topk_spread_by_pair check of the arguments they share -> (matches_l, matches_r, conf as GPU tensors,
+    the pair_off tensor, its pointer, pairs, cap, K, the five outputs they share as _bp_outputs takes them)."""
+    for t, name in ((matches_l, "matches_l"), (matches_r, "matches_r"), (conf, "conf"), (pair_off, "pair_off")):
+        if isinstance(t, torch.Tensor) and t.is_cuda and not t.is_contiguous():
+            raise RuntimeError("%s: %s must be contiguous" % (fn, name))
+    ml, mr, cf = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r"), _dev(conf, "conf").reshape(-1)
+    K, cap = int(K), int(cf.numel())
+    pair_off, pairs, _, off_p, _ = _bp_segments(fn, pair_off, None, None, pairs, cap)
+    if ml.dim() != 2 or ml.shape[1] != 2 or ml.shape != mr.shape or ml.shape[0] != cap:
+        raise RuntimeError("%s: matches_l / matches_r must be [cap,2] and conf [cap]" % fn)
+    if not 1 <= K <= topk_max_k():
+        raise RuntimeError("%s: K = %d, must lie in 1 .. %d" % (fn, K, topk_max_k()))
+    want = (("top_l", torch.float32, (pairs, K, 2)), ("top_r", torch.float32, (pairs, K, 2)), ("top_conf", torch.float32, (pairs, K)),
+            ("top_idx", torch.int32, (pairs, K)), ("top_count", torch.int64, (pairs,)))
+    return ml, mr, cf, pair_off, off_p, pairs, cap, K, want
+
+
 def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=None, pairs=None):
     """Each pair's K most confident matches out of matches_by_pair's regrouped lists, ON THE DEVICE: one launch for the whole
     batch, no host read (pats_topk_by_pair_f32; include/pats_amd.h holds the definition).  matches_l / matches_r [cap,2], conf
@@ -1701,19 +1719,8 @@ def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=Non
     of pair p is the match at position top_idx[p,j] of the pair's list, by confidence descending, ties by position ascending
     (+inf and a positive NaN rank first); past top_count[p] top_idx is -1 and the rest 0.0.  out: the five destinations."""
     fn = "topk_by_pair"
-    for t, name in ((matches_l, "matches_l"), (matches_r, "matches_r"), (conf, "conf"), (pair_off, "pair_off")):
-        if isinstance(t, torch.Tensor) and t.is_cuda and not t.is_contiguous():
-            raise RuntimeError("topk_by_pair: %s must be contiguous" % name)
-    ml, mr, cf = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r"), _dev(conf, "conf").reshape(-1)
-    K, cap = int(K), int(cf.numel())
-    pair_off, pairs, _, off_p, _ = _bp_segments(fn, pair_off, None, None, pairs, cap)
-    if ml.dim() != 2 or ml.shape[1] != 2 or ml.shape != mr.shape or ml.shape[0] != cap:
-        raise RuntimeError("topk_by_pair: matches_l / matches_r must be [cap,2] and conf [cap]")
-    if not 1 <= K <= topk_max_k():
-        raise RuntimeError("topk_by_pair: K = %d, must lie in 1 .. %d" % (K, topk_max_k()))
+    ml, mr, cf, pair_off, off_p, pairs, cap, K, want = _topk_inputs(fn, matches_l, matches_r, conf, pair_off, K, pairs)
     dev = ml.device
-    want = (("top_l", torch.float32, (pairs, K, 2)), ("top_r", torch.float32, (pairs, K, 2)), ("top_conf", torch.float32, (pairs, K)),
-            ("top_idx", torch.int32, (pairs, K)), ("top_count", torch.int64, (pairs,)))
     out = _bp_outputs(fn, want, out, dev)
     nws = _L().pats_topk_by_pair_workspace_bytes(pairs, K)
     ws = _workspace(nws, dev) if nws else None
@@ -1722,6 +1729,45 @@ def topk_by_pair(matches_l, matches_r, conf, pair_off, K, min_conf=None, out=Non
     _check(_L().pats_topk_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(cf), off_p, pairs, cap, K, 0 if min_conf is None else 1,
                                       0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                       _ptr(out[3]), _ptr(out[4]), _ptr(ws), nws, _stream()), fn)
+    return out
+
+
+def topk_spread_max_cells():
+    """The largest grid0 * grid1 topk_spread_by_pair takes (pats_topk_spread_by_pair_max_cells)."""
+    return int(_L().pats_topk_spread_by_pair_max_cells())
+
+
+def topk_spread_by_pair(matches_l, matches_r, conf, pair_off, K, cell, grid, side="left", min_conf=None, out=None, pairs=None):
+    """topk_by_pair's sibling that spreads the selection over the image, ON THE DEVICE: a grid of grid = (grid0, grid1) square cells
+    of `cell` pixels lies over the points of one side ("left": matches_l, "right": matches_r; grid0 along component 0 of the stored
+    points), every cell keeps its most confident match with conf >= min_conf, and the K most confident of these winners are the
+    pair's selection (pats_topk_spread_by_pair_f32; include/pats_amd.h holds the definition).  One launch for the whole batch, no
+    host read.  The inputs are topk_by_pair's; grid0 * grid1 <= topk_spread_max_cells(), a point outside the grid counts for the
+    edge cell.  Returns topk_by_pair's five tensors - top_count = min(K, occupied) - and occupied [pairs] int64, the cells of each
+    pair that hold a match.  out: the six destinations."""
+    fn = "topk_spread_by_pair"
+    ml, mr, cf, pair_off, off_p, pairs, cap, K, want = _topk_inputs(fn, matches_l, matches_r, conf, pair_off, K, pairs)
+    if side not in ("left", "right"):
+        raise RuntimeError("topk_spread_by_pair: side must be \"left\" or \"right\", got %r" % (side,))
+    try:
+        grid0, grid1 = (int(x) for x in grid)
+        whole = (grid0, grid1) == tuple(grid)
+    except (TypeError, ValueError):
+        whole = False
+    if not whole or grid0 < 1 or grid1 < 1:
+        raise RuntimeError("topk_spread_by_pair: grid must be two positive integers (grid0, grid1), got %r" % (grid,))
+    if int(cell) != cell:
+        raise RuntimeError("topk_spread_by_pair: cell must be an integer number of pixels, got %r" % (cell,))
+    dev = ml.device
+    out = _bp_outputs(fn, want + (("occupied", torch.int64, (pairs,)),), out, dev)
+    nws = _L().pats_topk_spread_by_pair_workspace_bytes(pairs, K, grid0, grid1)
+    ws = _workspace(nws, dev) if nws else None
+    if cap == 0:
+        ml = mr = cf = _bp_placeholder(dev)
+    _check(_L().pats_topk_spread_by_pair_f32(_ptr(ml), _ptr(mr), _ptr(cf), off_p, pairs, cap, K, 0 if min_conf is None else 1,
+                                             0.0 if min_conf is None else float(min_conf), 0 if side == "left" else 1, int(cell),
+                                             grid0, grid1, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[4]),
+                                             _ptr(out[5]), _ptr(ws), nws, _stream()), fn)
     return out
 
 
