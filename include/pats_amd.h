@@ -671,6 +671,85 @@ int pats_matches_by_row_pair_summary_f32(const float* matches_l, const float* ma
                                          const int32_t* status, void* workspace, size_t workspace_bytes, pats_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image front end (ABI 8, symbols added): the step in FRONT of the throughput path - what the reference's data set classes do to a
+ * decoded image on the CPU (datasets/yfcc.py:33-60, datasets/scannet.py:40-55): the centre crop and resize of Resize_img
+ * (utils/utils.py:1118-1131), the zero pad of cv2.copyMakeBorder up to a canvas that is a multiple of 32 and common to the pair, and
+ * the matching change to the intrinsics.  One launch turns every raw uint8 [h0, w0, 3] image of a batch - each its own allocation,
+ * of any size - into its canvas inside the flat left / right stores of a ragged batch (pats_pair_table_t.img_base), pad included.
+ * What it is not: a decoder, a normalisation or a grayscale conversion (those belong to the backbone and pats_crop_format_t).
+ *
+ * WHAT HAS BEEN CHECKED.  The resampling below is written from a reading of OpenCV's portable (non-SIMD-specific) uint8 path of
+ * cv2.resize with INTER_LINEAR.  It has NOT been run against any OpenCV build, and some builds route cv2.resize through IPP or a
+ * HAL with other rounding: no bit parity with an installed OpenCV is claimed.  Checked on the CPU: a numpy restatement of the
+ * rules below stays within 0.80 grey levels of float64 bilinear interpolation (half-pixel centres, align_corners = False) on
+ * eight shapes from 2 x 2 to 480 x 640, up- and downscaling, and maps constant 0 and constant 255 images to themselves; the
+ * kernel's output is bit-equal to that restatement (tests/test_prepare_gpu.py).
+ *
+ * Per image, ON THE HOST, in Python floats (IEEE double) exactly as the reference's lines - int() truncates toward zero:
+ *   target     from `size`: s = size / max(h0, w0), w_t = int(w0 * s), h_t = int(h0 * s) (yfcc.py:35-37); or given as (w_t, h_t).
+ *              Both at least 1
+ *   window     if w0 / w_t < h0 / h_t:  gap = int((h0 - w0 / w_t * h_t) / 2), rows [gap, h0 - gap), all columns
+ *              otherwise:               gap = int((w0 - h0 / h_t * w_t) / 2), columns [gap, w0 - gap), all rows
+ *              its size is (h_c, w_c) (Resize_img's slices)
+ *   canvas     per image ceil32(h_t) x ceil32(w_t); per pair the maximum of its two images' in each axis (yfcc.py:43-60); or one
+ *              fixed (H, W) for all pairs (scannet.py:52-53), which every target must fit.  The image sits at the top left; the
+ *              rest of the canvas is zero
+ * ON THE DEVICE the window S [h_c, w_c, 3] is resampled to [h_t, w_t, 3]:
+ *   per axis   with sn source and dn destination samples:  inv = double(dn) / double(sn), scale = 1.0 / inv (the table's scale_x /
+ *              scale_y).  For destination sample d:
+ *                f = float32((d + 0.5) * scale - 0.5)      evaluated in float64 without contraction, then rounded once
+ *                s = floor(f), f = f - s (float32);  if s < 0: s = 0, f = 0;  if s >= sn - 1: s = sn - 1, f = 0
+ *                second tap t = min(s + 1, sn - 1)
+ *                a0 = rint((1.0f - f) * 2048.0f), a1 = rint(f * 2048.0f)      float32 operations, ties to even
+ *   passes     a = the x coefficients of column d, b = the y coefficients of row y (taps y0, y1), int32 arithmetic:
+ *                Hsum[r][d][c] = S[r][s][c] * a0 + S[r][t][c] * a1
+ *                out[y][d][c] = (((b0 * (Hsum[y0][d][c] >> 4)) >> 16) + ((b1 * (Hsum[y1][d][c] >> 4)) >> 16) + 2) >> 2, clamped
+ *                to [0, 255]
+ *   halving    if w_c == 2 w_t AND h_c == 2 h_t the 2 x 2 mean replaces bilinear:
+ *                out[y][x][c] = (S[2y][2x][c] + S[2y][2x+1][c] + S[2y+1][2x][c] + S[2y+1][2x+1][c] + 2) >> 2
+ *              A halving in one axis only stays bilinear
+ *   bgr        with bgr = 1 output channel c reads source channel 2 - c (the reference's [:, :, [2, 1, 0]])
+ *   dtype      the stores' element type: PATS_IMG_U8, _F32, _F16 or _BF16 - 0 .. 255 is exact in all four
+ * Intrinsics (host, numpy float64, the reference's operation order; pats_amd/ops.py prepare_intrinsics), K the 3 x 3 of the raw image:
+ *   "ratio"    yfcc.py:39-42 with Get_resize_ratio (utils.py:943-957) on (w0, h0) and (w_t, h_t) as floats:  h_w = h_t / w_t;
+ *              if w0 / w_t < h0 / h_t:  r = w_t / w0, add = (0, (h0 - w0 * h_w) / 2);  otherwise r = h_t / h0,
+ *              add = ((w0 - h0 / h_w) / 2, 0).  K' = r * K, K'[2][2] = 1, K'[0:2][2] -= add * r.  `add` is the reference's FLOAT gap,
+ *              not the integer gap of the crop
+ *   "axes"     scannet.py:54-55 with scale_intrinsics (utils/metrics.py:6-8):  K' = diag(1 / sx, 1 / sy, 1) K (a matrix product),
+ *              sx = float(w0) / w_t, sy = float(h0) / h_t
+ *   norm       [pairs,8] float32 = (cy_l, cx_l, 1 / fy_l, 1 / fx_l, cy_r, cx_r, 1 / fy_r, 1 / fx_r) of K'_l, K'_r - each formed in
+ *              float64 and rounded once to float32: the `norm` of the per-pair stages below
+ *   thr        [pairs] float32 = threshold / mean(K'_l[0][0], K'_r[1][1], K'_l[0][0], K'_r[1][1]) (metrics.py:36-37; numpy's mean of
+ *              the four, float64, rounded once)
+ *
+ * pats_prepare_images_u8 - one launch for all n_img images.  The table is handed over twice, as pats_pair_table_t is: images_host
+ * (host memory; validated before the launch, sizes it) and images (the same bytes in device memory; what the kernel reads).
+ * left / right: the stores, left_elems / right_elems elements of `dtype` long; image i's canvas [H, W, 3] is written - every
+ * element of it, pad included, nothing else - at element dst of the store `side` names.  No workspace, no host read, no allocation:
+ * the call can be captured in a graph.
+ * Refused before the launch (PATS_ERR_INVALID; pats_last_error names the image): a null images_host / images / left / right or a
+ * null src; images off 8 bytes, left / right off 16; an unknown dtype; n_img outside 1 .. 65535; a source or canvas side above
+ * pats_prepare_images_max_side() (16384); a window that is empty or leaves its source; a canvas side that is not a positive
+ * multiple of 32; a target below 1 or larger than its canvas; side or bgr not 0 / 1; scale_x / scale_y not the definition's
+ * double; a canvas that leaves its store or does not start on a 16-byte boundary. */
+typedef struct pats_prepare_image {
+    const uint8_t* src;      /* device: the raw image [h0, w0, 3] uint8, contiguous */
+    int64_t dst;             /* offset in ELEMENTS of the canvas in its store: pats_pair_table_t.img_base of the image's slot */
+    double scale_x;          /* 1.0 / (double(w_t) / double(w_c)) */
+    double scale_y;          /* 1.0 / (double(h_t) / double(h_c)) */
+    int32_t h0, w0;          /* the raw image */
+    int32_t y0, x0;          /* the window's first row and column */
+    int32_t h_c, w_c;        /* the window's size */
+    int32_t h_t, w_t;        /* the target */
+    int32_t H, W;            /* the canvas */
+    int32_t side;            /* 0: the left store, 1: the right store */
+    int32_t bgr;             /* 0 / 1 */
+} pats_prepare_image_t;
+int64_t pats_prepare_images_max_side(void);
+int pats_prepare_images_u8(const pats_prepare_image_t* images_host, const pats_prepare_image_t* images, int64_t n_img, void* left,
+                           int64_t left_elems, void* right, int64_t right_elems, pats_img_dtype_t dtype, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-match confidence (ABI 8, symbols added).  For third-level problem p and centre source cell k in 0..15 (row r of the 8x8
  * grid inside [2:6, 2:6], in Compute_result's order), with S = exp(Z) the [65,65] plan:
  *     rowmass = sum of S[r, :] over all 65 columns, dustbin included           (first term of third_layer.py:213)

@@ -210,6 +210,9 @@ SIGNATURES = {
                                                   c_void_p, c_void_p, c_size, c_void_p]),
     "pats_matches_by_row_pair_summary_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64,
                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    # the image front end (csrc/prepare.hip): the table in host and in device memory, n_img, left, left_elems, right, right_elems, dtype
+    "pats_prepare_images_max_side": (c_i64, []),
+    "pats_prepare_images_u8": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p]),
     # per-match confidence: the entries they are named after with the confidence pointer(s) added
     "pats_third_level_typed_conf": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

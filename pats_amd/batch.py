@@ -39,6 +39,7 @@ write half descriptors themselves with out_dtype= or a half out=: the float32 va
       feat0 [P_cap,128,65], feat1 [P_cap,128,65], scale [P_cap,1,64] [, p_s, p_t [P_cap,2] int64: the points rounded to
       the 4-px lattice as ops.third_descriptors returns them; formed here if absent]      (b_ids = row of the table)
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -141,6 +142,60 @@ def pack_pairs(pairs, keep_dtype=False):
         pk.groups.append((lo, hi, h, w, pk.left[o0:o0 + n].view(hi - lo, 32 * h, 32 * w, 3),
                           pk.right[o0:o0 + n].view(hi - lo, 32 * h, 32 * w, 3)))
         lo = hi
+    return pk
+
+
+def pack_raw_pairs(pairs, size=None, targets=None, canvas=None, dtype=torch.uint8, bgr=False, K=None, intrinsics="ratio", threshold=None):
+    """pack_pairs for RAW images: pairs = [(left, right)] decoded uint8 [h0, w0, 3] GPU tensors of any size, each its own tensor.
+    What the reference's data set classes do on the CPU - Resize_img's centre crop and resize, the zero pad to a canvas that is a
+    multiple of 32 and common to the pair (include/pats_amd.h, "Image front end") - happens in ONE launch that writes every canvas
+    straight into the flat stores in slot order (ops.prepare_images; no torch.cat pass).  size / targets / canvas as
+    ops.prepare_plan takes them; dtype: the stores' (uint8, float32, float16, bfloat16); bgr: swap the channel order.
+    Returns the MixedPack pack_pairs(prepared images, keep_dtype=True) would return, which also carries
+        plan                 the ops.PreparePlan (windows, targets, canvases; host)
+        K_left, K_right      [pairs,3,3] float64 host arrays: the intrinsics of the prepared images      } with K = [(K_l, K_r)], the raw
+        norm [pairs,8]       float32 on the GPU, caller order: the `norm` of verify_by_pair and the rest  } images' 3 x 3, and
+        thr [pairs]          float32 on the GPU: threshold / mean focal length; with `threshold` only     } intrinsics "ratio" or "axes"
+    (None without K).  ValueError: a canvas that does not hold a target, K without both matrices of every pair."""
+    if not pairs:
+        raise ValueError("pack_raw_pairs: no pairs")
+    for i, pr in enumerate(pairs):
+        if len(pr) != 2 or any(not isinstance(t, torch.Tensor) or t.dim() != 3 for t in pr):
+            raise ValueError("pack_raw_pairs: pair %d must be two [h, w, 3] tensors" % i)
+    plan = ops.prepare_plan([((l.shape[0], l.shape[1]), (r.shape[0], r.shape[1])) for l, r in pairs], size=size, targets=targets,
+                            canvas=canvas)
+    pk = MixedPack()
+    pk.plan, pk.K_left, pk.K_right, pk.norm, pk.thr = plan, None, None, None, None
+    if K is not None:
+        if len(K) != len(pairs) or any(k is None or len(k) != 2 or k[0] is None or k[1] is None for k in K):
+            raise ValueError("pack_raw_pairs: K must hold (K_left, K_right) for every pair")
+        prepared = [[ops.prepare_intrinsics(k[s], plan.h0[p, s], plan.w0[p, s], plan.w_t[p, s], plan.h_t[p, s], intrinsics)
+                     for p, k in enumerate(K)] for s in range(2)]
+        pk.K_left, pk.K_right = np.stack(prepared[0]), np.stack(prepared[1])
+    elif threshold is not None:
+        raise ValueError("pack_raw_pairs: a threshold needs K")
+    dev = pairs[0][0].device
+    pk.caller_of, pk.slot_of = list(plan.caller_of), list(plan.slot_of)
+    pk.shapes = [plan.shapes[i] for i in pk.caller_of]
+    pk.left = torch.empty(plan.elems, dtype=dtype, device=dev)
+    pk.right = torch.empty(plan.elems, dtype=dtype, device=dev)
+    ops.prepare_images(pairs, plan, pk.left, pk.right, bgr=bgr)
+    pk.table = ops.PairTable(pk.shapes, dev)
+    pk.groups = []
+    lo = 0
+    while lo < len(pk.shapes):
+        hi = lo
+        while hi < len(pk.shapes) and pk.shapes[hi] == pk.shapes[lo]:
+            hi += 1
+        h, w = pk.shapes[lo]
+        o0, n = int(pk.table.img_base_host[lo]), (hi - lo) * h * w * 1024 * 3
+        pk.groups.append((lo, hi, h, w, pk.left[o0:o0 + n].view(hi - lo, 32 * h, 32 * w, 3),
+                          pk.right[o0:o0 + n].view(hi - lo, 32 * h, 32 * w, 3)))
+        lo = hi
+    if K is not None:
+        pk.norm = torch.from_numpy(ops.prepare_norm(pk.K_left, pk.K_right)).to(dev)
+        if threshold is not None:
+            pk.thr = torch.from_numpy(ops.prepare_thr(pk.K_left, pk.K_right, threshold)).to(dev)
     return pk
 
 

@@ -2968,3 +2968,203 @@ def fundamental_polish_by_pair(matches_l, matches_r, models, thr, best=None, rou
     return _polish_by_pair("fundamental_polish_by_pair", _L().pats_fundamental_polish_by_pair_f32,
                            _L().pats_fundamental_polish_workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride,
                            counts, conf, min_conf, norm, out, pairs)
+
+
+# ---- the image front end (csrc/prepare.hip; include/pats_amd.h, "Image front end") ----------------------------------------------
+_IMG_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}        # pats_img_dtype_t
+# pats_prepare_image_t
+_PREPARE_IMAGE = np.dtype([("src", np.uint64), ("dst", np.int64), ("scale_x", np.float64), ("scale_y", np.float64)] +
+                          [(n, np.int32) for n in ("h0", "w0", "y0", "x0", "h_c", "w_c", "h_t", "w_t", "H", "W", "side", "bgr")], align=True)
+assert _PREPARE_IMAGE.itemsize == 80
+
+
+def prepare_images_max_side():
+    """The largest source or canvas side prepare_images takes (pats_prepare_images_max_side)."""
+    return int(_L().pats_prepare_images_max_side())
+
+
+def prepare_target(h0, w0, size):
+    """(w_t, h_t) of an [h0, w0] image whose longer side becomes `size`, with the reference's truncations (yfcc.py:35-37)."""
+    s = size / max(h0, w0)
+    return int(w0 * s), int(h0 * s)
+
+
+def prepare_window(h0, w0, w_t, h_t):
+    """The centre crop to the target's aspect (Resize_img's slices) -> (y0, x0, h_c, w_c)."""
+    if w0 / w_t < h0 / h_t:
+        gap = int((h0 - w0 / w_t * h_t) / 2)
+        return gap, 0, h0 - 2 * gap, w0
+    gap = int((w0 - h0 / h_t * w_t) / 2)
+    return 0, gap, h0, w0 - 2 * gap
+
+
+class PreparePlan:
+    """What prepare_plan returns - host data only, every array in CALLER order:
+        h0, w0, y0, x0, h_c, w_c, h_t, w_t   [pairs,2] int64 (left, right): the raw size, the crop window, the target
+        canvas                               [pairs,2] int64 (H, W): the pair's canvas;  shapes: its grid (H / 32, W / 32)
+        caller_of, slot_of                   the slots of the pack: caller indices sorted stably by grid (batch.slot_order)
+        dst                                  [pairs] int64: the offset in elements of the pair's canvas in either flat store
+                                             (PairTable.img_base of its slot);  elems: the length of a store"""
+
+
+def prepare_plan(sizes, size=None, targets=None, canvas=None):
+    """The host half of the image front end, no GPU: sizes = [((h0, w0) left, (h0, w0) right)] per pair.  Give either `size` (the
+    longer side of every target, prepare_target) or `targets`: one (w_t, h_t) for every image, or [((w_t, h_t), (w_t, h_t))] per
+    pair.  canvas: None = per pair the maximum of its images' ceil32 targets in each axis (yfcc.py:43-60), or one fixed (H, W) -
+    multiples of 32 - for all pairs (scannet.py:52-53); ValueError if a target does not fit it.  Returns a PreparePlan."""
+    if not sizes:
+        raise ValueError("prepare_plan: no pairs")
+    if (size is None) == (targets is None):
+        raise ValueError("prepare_plan: give either size or targets")
+    n = len(sizes)
+    if targets is not None and not isinstance(targets[0], (tuple, list)):
+        targets = [((int(targets[0]), int(targets[1])),) * 2] * n
+    if targets is not None and len(targets) != n:
+        raise ValueError("prepare_plan: %d targets for %d pairs" % (len(targets), n))
+    if canvas is not None and (canvas[0] < 32 or canvas[1] < 32 or canvas[0] % 32 or canvas[1] % 32):
+        raise ValueError("prepare_plan: the canvas (%d, %d) must be positive multiples of 32" % tuple(canvas))
+    pl = PreparePlan()
+    names = ("h0", "w0", "y0", "x0", "h_c", "w_c", "h_t", "w_t")
+    for name in names:
+        setattr(pl, name, np.zeros((n, 2), np.int64))
+    pl.canvas = np.zeros((n, 2), np.int64)
+    for p in range(n):
+        for side in range(2):
+            h0, w0 = int(sizes[p][side][0]), int(sizes[p][side][1])
+            if h0 < 1 or w0 < 1:
+                raise ValueError("prepare_plan: pair %d has an empty image" % p)
+            w_t, h_t = prepare_target(h0, w0, size) if targets is None else (int(targets[p][side][0]), int(targets[p][side][1]))
+            if w_t < 1 or h_t < 1:
+                raise ValueError("prepare_plan: pair %d: the target %d x %d (h x w) is empty" % (p, h_t, w_t))
+            for name, v in zip(names, (h0, w0) + prepare_window(h0, w0, w_t, h_t) + (h_t, w_t)):
+                getattr(pl, name)[p, side] = v
+        H, W = (-(-int(pl.h_t[p].max()) // 32) * 32, -(-int(pl.w_t[p].max()) // 32) * 32) if canvas is None else (int(canvas[0]), int(canvas[1]))
+        if pl.h_t[p].max() > H or pl.w_t[p].max() > W:
+            raise ValueError("prepare_plan: pair %d: the target %d x %d does not fit the canvas %d x %d"
+                             % (p, pl.h_t[p].max(), pl.w_t[p].max(), H, W))
+        pl.canvas[p] = (H, W)
+    pl.shapes = [(int(H) // 32, int(W) // 32) for H, W in pl.canvas]
+    pl.caller_of = sorted(range(n), key=lambda i: pl.shapes[i])        # batch.slot_order
+    pl.slot_of = [0] * n
+    pl.dst = np.zeros(n, np.int64)
+    off = 0
+    for s, i in enumerate(pl.caller_of):
+        pl.slot_of[i], pl.dst[i] = s, off
+        off += int(pl.canvas[i, 0] * pl.canvas[i, 1]) * 3
+    pl.elems = off
+    return pl
+
+
+def prepare_intrinsics(K, h0, w0, w_t, h_t, mode="ratio"):
+    """The raw image's K [3,3] -> K' float64 of the prepared image, in numpy float64 and the reference's operation order.
+    "ratio": Get_resize_ratio as yfcc.py:39-42 applies it (the float gap, not the crop's integer gap); "axes": scale_intrinsics as
+    scannet.py:54-55 applies it.  include/pats_amd.h, "Image front end", states both."""
+    K = np.array(K, np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("prepare_intrinsics: K must be 3 x 3")
+    if mode == "ratio":
+        w, h, w_new, h_new = float(w0), float(h0), float(w_t), float(h_t)
+        h_w = h_new / w_new
+        add = np.zeros(2, np.float64)
+        if w / w_new < h / h_new:
+            r = w_new / w
+            add[1] = (h - w * h_w) / 2
+        else:
+            r = h_new / h
+            add[0] = (w - h / h_w) / 2
+        K = r * K
+        K[2, 2] = 1
+        K[0:2, 2] -= add * r
+        return K
+    if mode == "axes":
+        return np.dot(np.diag([1.0 / (float(w0) / w_t), 1.0 / (float(h0) / h_t), 1.0]), K)
+    raise ValueError("prepare_intrinsics: mode must be \"ratio\" or \"axes\", got %r" % (mode,))
+
+
+def prepare_norm(K_left, K_right):
+    """K'_l, K'_r [pairs,3,3] float64 -> norm [pairs,8] float32 (cy_l, cx_l, 1 / fy_l, 1 / fx_l, cy_r, cx_r, 1 / fy_r, 1 / fx_r), each
+    formed in float64 and rounded once: the `norm` of the per-pair stages (a host array)."""
+    cols = []
+    for K in (np.asarray(K_left, np.float64), np.asarray(K_right, np.float64)):
+        cols += [K[:, 1, 2], K[:, 0, 2], 1.0 / K[:, 1, 1], 1.0 / K[:, 0, 0]]
+    return np.stack(cols, 1).astype(np.float32)
+
+
+def prepare_thr(K_left, K_right, threshold):
+    """thr [pairs] float32 = threshold / mean(K'_l[0,0], K'_r[1,1], K'_l[0,0], K'_r[1,1]) (metrics.py:36-37), a host array."""
+    K_left, K_right = np.asarray(K_left, np.float64), np.asarray(K_right, np.float64)
+    return np.array([threshold / np.mean([a[0, 0], b[1, 1], a[0, 0], b[1, 1]]) for a, b in zip(K_left, K_right)]).astype(np.float32)
+
+
+class PrepareTable:
+    """The per-image table of one prepare_images call (pats_prepare_image_t, 2 * pairs entries: pair p's left image at 2 p, its
+    right at 2 p + 1): `host` the numpy records, `dev` the same bytes on the GPU; `srcs` keeps the images it points to alive."""
+
+
+def prepare_table(srcs, plan, bgr=False):
+    """The table of prepare_images for these source tensors: srcs = [(left, right)] raw uint8 [h0, w0, 3] GPU tensors in the plan's
+    pair order, each its own tensor (no copy is made: the table holds their addresses).  Build it once and hand it to prepare_images
+    (table=) to call that without an allocation or an upload - under graph capture, say."""
+    fn = "prepare_images"
+    if len(srcs) != len(plan.dst):
+        raise RuntimeError("%s: %d source pairs for a plan of %d" % (fn, len(srcs), len(plan.dst)))
+    host = np.zeros(2 * len(srcs), _PREPARE_IMAGE)
+    dev = None
+    for p, pr in enumerate(srcs):
+        if len(pr) != 2:
+            raise RuntimeError("%s: pair %d must be (left, right)" % (fn, p))
+        for side, t in enumerate(pr):
+            name = "pair %d %s" % (p, ("left", "right")[side])
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s: %s must be a torch.Tensor" % (fn, name))
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:       # layout first: refused the same way without a GPU
+                raise RuntimeError("%s: %s must be a uint8 [h, w, 3] image, got %s %s" % (fn, name, t.dtype, list(t.shape)))
+            if not t.is_contiguous():
+                raise RuntimeError("%s: %s must be contiguous" % (fn, name))
+            if not t.is_cuda:
+                raise RuntimeError("pats_amd: %s is on %s; the HIP path needs a GPU tensor (no CPU fallback)" % (name, t.device))
+            if (int(t.shape[0]), int(t.shape[1])) != (int(plan.h0[p, side]), int(plan.w0[p, side])):
+                raise RuntimeError("%s: %s is %d x %d, the plan was made for %d x %d"
+                                   % (fn, name, t.shape[0], t.shape[1], plan.h0[p, side], plan.w0[p, side]))
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise RuntimeError("%s: %s is on %s, the others on %s" % (fn, name, t.device, dev))
+            e = host[2 * p + side]
+            e["src"], e["dst"], e["side"], e["bgr"] = t.data_ptr(), plan.dst[p], side, 1 if bgr else 0
+            for k in ("h0", "w0", "y0", "x0", "h_c", "w_c", "h_t", "w_t"):
+                e[k] = getattr(plan, k)[p, side]
+            e["H"], e["W"] = plan.canvas[p]
+            e["scale_x"] = 1.0 / (float(e["w_t"]) / float(e["w_c"]))
+            e["scale_y"] = 1.0 / (float(e["h_t"]) / float(e["h_c"]))
+    tab = PrepareTable()
+    tab.host, tab.srcs, tab.bgr = host, srcs, bool(bgr)
+    tab.dev = torch.from_numpy(host.view(np.uint8)).to(dev)
+    return tab
+
+
+def prepare_images(srcs, plan, left, right, bgr=False, table=None):
+    """The device half of the image front end, ONE launch (pats_prepare_images_u8; include/pats_amd.h, "Image front end", holds the
+    definition): every raw image of srcs = [(left, right)] (uint8 [h0, w0, 3] GPU tensors of any size, each its own tensor) is
+    cropped to the plan's window, resampled to its target with OpenCV's fixed-point bilinear arithmetic (the 2 x 2 mean at an exact
+    halving) and written with its zero pad as the pair's canvas into the flat stores left / right at plan.dst - every element of
+    every canvas, so the stores may be torch.empty.  left / right: contiguous GPU tensors of at least plan.elems elements, both
+    uint8, float32, float16 or bfloat16.  bgr: output channel c reads source channel 2 - c.  table: a prepare_table(srcs, plan, bgr)
+    made earlier - the call then allocates and uploads nothing.  Returns (left, right)."""
+    fn = "prepare_images"
+    if table is None:
+        table = prepare_table(srcs, plan, bgr)
+    elif len(table.host) != 2 * len(plan.dst) or table.bgr != bool(bgr):
+        raise RuntimeError("%s: the table was made for another plan or bgr setting" % fn)
+    for t, name in ((left, "left"), (right, "right")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor" % (fn, name))
+        if not t.is_cuda:
+            raise RuntimeError("pats_amd: %s is on %s; the HIP path needs a GPU tensor (no CPU fallback)" % (name, t.device))
+        if t.dtype not in _IMG_DTYPES or t.dtype != left.dtype:
+            raise RuntimeError("%s: left and right must share one of float32, float16, bfloat16, uint8, got %s" % (fn, t.dtype))
+        if not t.is_contiguous() or t.numel() < plan.elems:
+            raise RuntimeError("%s: %s must be contiguous and hold at least %d elements" % (fn, name, plan.elems))
+    _check(_L().pats_prepare_images_u8(ctypes.c_void_p(table.host.ctypes.data), _ptr(table.dev), len(table.host), _ptr(left), left.numel(),
+                                       _ptr(right), right.numel(), _IMG_DTYPES[left.dtype], _stream()), fn)
+    return left, right
