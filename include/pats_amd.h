@@ -1814,6 +1814,79 @@ int pats_bn_fold_f32(const float* h, int64_t batch, int C, int n, const float* g
 int pats_scale_head_f32(const float* x, int64_t batch, int C, int ld, int h, int w, const float* weight,
                         const float* bias, int heads, float* out, float* per_head, pats_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-pair absolute pose from depth (ABI 8, symbols added): the left (database) image comes with a depth map, a match in it is
+ * LIFTED to a metric 3-D point, three lifted matches give the right (query) camera's absolute pose (P3P) and the candidates are
+ * verified by reprojection.  The result is a metric (R, t) - what the two-view stages cannot give.  Three entry points; each takes
+ * the per-pair segments in the two forms of pats_epipolar_score_by_pair_f32 (ragged pair_off, or stride with counts_in, exactly
+ * ONE of them, with the same clamping), issues a fixed number of launches for the whole batch and reads nothing back.
+ * What it is not: a refit of the winner on its inliers (linear or non-linear), MSAC, adaptive stopping, a local optimisation, a
+ * sampler that skips invalid matches; nothing in pipeline.forward_* or the drop-in calls it.
+ *
+ * 1. The lift.  Inputs
+ *   matches [cap,2] float32   ONE side's list in the hand-over's (c0, c1) = (y, x) order, un-normalised pixels of the map
+ *   norm [pairs,8] float32 (optional)   its LEFT half (c0, c1, s0, s1) normalises the point: x_k = (p_k - c_k) * s_k, one subtract and
+ *              one multiply in float32, as everywhere; without it x = p
+ *   depth_table [pairs,4] int64   per pair (address of a float32 map, h, w, row stride in elements): map axis 0 belongs to c0, axis 1
+ *              to c1, the centre of pixel (i, j) is at (c0, c1) = (i, j).  A null address, h < 1 or w < 1: every match of the pair is
+ *              invalid
+ *   max_depth [pairs] float32 (optional), interp (0 nearest, 1 bilinear), use_max_jump (0 or 1) with max_jump
+ * Definition, per match (p0, p1), float32 throughout, every operation rounded once, no contraction
+ *   nearest    i = rint(p0), j = rint(p1) (round half to even; still float32), the tap (i, j), d = depth[i, j]
+ *   bilinear   i0 = floor(p0), a = p0 - i0, j0 = floor(p1), b = p1 - j0.  The taps USED are (i0, j0), (i0, j0 + 1) if b > 0,
+ *              (i0 + 1, j0) if a > 0 and (i0 + 1, j0 + 1) if both: a tap whose weight is exactly zero is not read and enters the sum
+ *              as 0, so p0 = h - 1 with a = 0 is inside the map.  wa = 1 - a, wb = 1 - b, w00 = wa wb, w01 = wa b, w10 = a wb,
+ *              w11 = a b;  d = ((w00 d00 + w01 d01) + w10 d10) + w11 d11  - four products, then three sums left to right
+ *   invalid    iff a coordinate is not finite; a used tap lies outside [0, h) x [0, w); a used tap is not finite or <= 0; in the
+ *              bilinear form with use_max_jump, (max tap - min tap) > max_jump * min tap over the used taps (a depth edge; max_jump
+ *              is not looked at in the nearest form); max_depth given and d > max_depth[p] (a NaN limit does not limit); or the pair
+ *              has no map
+ *   point      X = (x0 d, x1 d, d): each product rounded once
+ * Outputs - every call defines every byte: rows of cap in no segment (and the slack of a strided row) hold exact zeros, as
+ * pats_epipolar_triangulate_by_pair_f64 leaves them; an invalid match of a segment holds three NaNs and valid = 0
+ *   points [cap,3] float32,  valid [cap] uint8,  lift_count [pairs] int64 = valid's sum over the segment, exactly
+ * Refused before any launch: a null matches / depth_table / points / valid / lift_count; matches, depth_table, lift_count, pair_off or
+ * counts_in off 8 bytes, norm, max_depth or points off 4; the segment rules of every per-pair stage (both forms or neither, pairs < 1,
+ * cap < 0 or cap >= 2^31 - 1, stride < 1 or pairs * stride > cap); interp or use_max_jump not 0 or 1.  cap == 0 is a valid call. */
+int pats_lift_by_pair_f32(const float* matches, const int64_t* pair_off, int64_t stride, const int64_t* counts_in, int64_t pairs,
+                          int64_t cap, const float* norm, const int64_t* depth_table, const float* max_depth, int interp,
+                          int use_max_jump, float max_jump, float* points, uint8_t* valid, int64_t* lift_count, pats_stream_t stream);
+
+/* 2. P3P hypotheses: H samples per pair, one thread each, every sample solved for the up to four (R, t) with x_r ~ R X + t.
+ *   points [cap,3] float32 (the lift's), matches_r [cap,2] float32 with norm's RIGHT half (optional) as the verification normalises
+ *   sampler    the one of pats_epipolar_hypotheses_by_pair_f32 with three draws: the pool is n, or with progressive
+ *              max(3, ceil(n (h + 1) / H)); pair_seed [pairs] int64; sample_idx [pairs,H,3] int32 (optional) gets the draws, -1 for a
+ *              pair with n < 3
+ *   solve      float64, Grunert's quartic in the ratio of two camera distances, its positive real roots bracketed by the roots of its
+ *              derivatives, the three distances polished on the law-of-cosines equations, the pose from the two triangles' frames
+ *   kept       a sample with a non-finite point (an invalid lift) or right point gives no model.  A solution is kept iff it is finite,
+ *              also as float32; the camera-frame depths of its three points are positive; and its largest reprojection residual on
+ *              its own three points, max_i |(Y_i0, Y_i1) / Y_i2 - x_r,i|_inf in float64, is <= 1e-8
+ *   models [pairs,H,4,3,4] float32   row-major [R | t] in the frame of the points, the kept solutions first by ascending camera
+ *              distance of the first sample point, exact zero models behind; n_models [pairs,H] int32 (optional) their number
+ * Refused before any launch: a null points / matches_r / pair_seed / models; matches_r, pair_seed, pair_off or counts_in off 8
+ * bytes, the others off 4; the segment rules; H < 1 or 4 H above pats_epipolar_max_h; progressive not 0 or 1. */
+int pats_absolute_hypotheses_by_pair_f32(const float* points, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                         const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
+                                         const float* norm, int progressive, float* models, int32_t* sample_idx, int32_t* n_models,
+                                         pats_stream_t stream);
+
+/* 3. Reprojection verification: M models [pairs,M,3,4] float32 per pair (M <= pats_epipolar_max_h) against every match.
+ *   takes part a match whose X and (normalised) x_r are finite and, with use_min_conf, whose conf >= min_conf (false for a NaN)
+ *   test       float32 FMAs in this order:  Y_k = fma(m[k,0], X0, fma(m[k,1], X1, fma(m[k,2], X2, m[k,3])));  d_k = fma(-r_k, Y2, Y_k)
+ *              for k = 0, 1;  s = fma(d0, d0, d1 * d1);  lim = (thr * thr) * (Y2 * Y2);  inlier iff the match takes part, Y2 > 0
+ *              and s <= lim - no division.  thr [pairs] float32 in normalised units; a NaN or negative thr: no inliers.  An all-zero
+ *              model has Y = 0: no inliers by construction
+ *   counts [pairs,M] int32;  best [pairs] int32 = the lowest index among the largest counts (0 when no model has an inlier),
+ *   best_count [pairs] int64;  inlier [cap] uint8 = the winner's verdicts, zero outside the segments: its sum is best_count exactly
+ * Integer sums only: two calls give the same bits.
+ * Refused before any launch: a null points / matches_r / models / thr / counts / best / best_count / inlier; the alignment and
+ * segment rules above; M outside 1 .. pats_epipolar_max_h; use_min_conf without conf, a negative or NaN min_conf. */
+int pats_absolute_score_by_pair_f32(const float* points, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                    int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t M,
+                                    const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts,
+                                    int32_t* best, int64_t* best_count, uint8_t* inlier, pats_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

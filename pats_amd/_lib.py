@@ -318,6 +318,13 @@ SIGNATURES = {
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_fundamental_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
     "pats_fundamental_polish_by_pair_f32": (c_int, _POLISH_ARGS),
+    # the absolute-pose branch (csrc/absolute.hip): the lift through a depth map, P3P hypotheses, reprojection verification
+    "pats_lift_by_pair_f32": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_f,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pats_absolute_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
+                                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pats_absolute_score_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
+                                                c_void_p, c_void_p, c_int, c_f, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -996,20 +996,23 @@ def select_pose_by_pair(out, cap, ratio=0.8):
     return out["pose_selected"]
 
 
-_BRANCHES = {"planar": ("pose_h", "verified_h", "pose_h_by_pair"), "selected": ("pose_selected", "verified_selected", "select_pose_by_pair")}
+# branch -> (its pose, its verification, the function that makes them, the key of the lists that were scored, the key of its models)
+_BRANCHES = {"planar": ("pose_h", "verified_h", "pose_h_by_pair", "verified_h_on", "verified_h_models"),
+             "selected": ("pose_selected", "verified_selected", "select_pose_by_pair", "verified_h_on", None),      # both branches scored the same lists
+             "absolute": ("pose_abs", "verified_abs", "pose_abs_by_pair", "verified_abs_on", None)}
 
 
 def pose_branch(out, branch):
     """The result seen through one branch: a shallow copy of `out` whose `pose` and `verified` (with `verified_on` and
-    `verified_models`) are those of branch = "epipolar" (as they are), "planar" (`pose_h`, `verified_h`) or "selected"
-    (`pose_selected`, `verified_selected`).  Every consumer of a pose - triangulate_by_pair (mask="front": the branch's front,
+    `verified_models`) are those of branch = "epipolar" (as they are), "planar" (`pose_h`, `verified_h`), "selected"
+    (`pose_selected`, `verified_selected`) or "absolute" (`pose_abs`, `verified_abs`: the metric pose of pose_abs_by_pair).  Every consumer of a pose - triangulate_by_pair (mask="front": the branch's front,
     "inlier": its inlier mask), pose_error_by_pair, split_pose_by_pair, split_points_by_pair - then works on the view as it stands:
-    the three poses share one layout, so there is no second code path.  What a consumer stores (`points`, `pose_error`) goes into the
+    the poses share one layout, so there is no second code path.  What a consumer stores (`points`, `pose_error`) goes into the
     view; `out` and the default branch's `points` and `pose_error` are never touched (a view does not inherit them either).  The
     tensors are shared, nothing is copied or launched.  Raises ValueError for an unknown branch and for a branch that has not been
     computed."""
     if branch != "epipolar" and branch not in _BRANCHES:
-        raise ValueError("pose_branch: branch must be \"epipolar\", \"planar\" or \"selected\", got %r" % (branch,))
+        raise ValueError("pose_branch: branch must be \"epipolar\", \"planar\", \"selected\" or \"absolute\", got %r" % (branch,))
     view = dict(out)
     view.pop("points", None)
     view.pop("pose_error", None)
@@ -1017,12 +1020,12 @@ def pose_branch(out, branch):
         if "pose" not in out:
             raise ValueError("pose_branch: branch=\"epipolar\": run pose_by_pair first")
         return view
-    pose_key, ver_key, maker = _BRANCHES[branch]
+    pose_key, ver_key, maker, on_key, models_key = _BRANCHES[branch]
     if pose_key not in out:
         raise ValueError("pose_branch: branch=%r: run %s first" % (branch, maker))
     view["pose"], view["verified"] = out[pose_key], out[ver_key]
-    view["verified_on"] = out["verified_h_on"]                           # for "selected" both branches scored the same lists
-    view["verified_models"] = out["verified_h_models"] if branch == "planar" else None
+    view["verified_on"] = out[on_key]
+    view["verified_models"] = out[models_key] if models_key else None
     return view
 
 
@@ -1121,3 +1124,124 @@ def verify_h_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, mo
     on it unchanged) and `verified_h_used` = (used, participating); returns the tuple followed by those two."""
     return _verify("verify_h_adaptive_by_pair", ops.homography_score_adaptive_by_pair, "verified_h", out, cap, models, thr, norm, min_conf,
                    on, moments, adaptive=(confidence, sample_size, models_per_sample, round_models))
+
+
+# ---- the absolute-pose branch: lift through depth, P3P, reprojection verification, the metric pose ----
+def lift_by_pair(out, cap, depths, norm, on="topk", interp="nearest", max_depth=None, max_jump=None):
+    """Device side, after the matching (and after topk_by_pair for on="topk"): each pair's LEFT matches lifted through the left
+    image's depth map to metric 3-D points (ops.lift_by_pair: one launch, no host read).  depths: one float32 GPU tensor [h, w] per
+    pair (or None), of any sizes, each its own tensor, possibly a strided view - in the CALLER's order, like norm [pairs,8] (or None:
+    the points stay in pixels) and max_depth [pairs] float32 (or None); for a mixed pack the table of addresses is permuted to slot
+    order on the device.  The map must be sampled where the matches live: axis 0 belongs to the stored component 0 (y), the centre of
+    pixel (i, j) lies at (i, j) - the depth of the prepared left image, at its resolution.  interp "nearest" or "bilinear"; max_jump
+    (bilinear): a match whose taps differ by more than max_jump times the smallest one lies on a depth edge and is invalid.
+    Stores `lifted` = (points [n,3] float32, valid [n] uint8, lift_count [pairs] int64, on) and returns it: the per-match outputs are
+    aligned with the lists (slot order, like `verified`'s inlier mask), lift_count is in the CALLER's order.  `verified`, `pose` and
+    the lists are not touched."""
+    fn = "lift_by_pair"
+    _check_on(fn, out, on)
+    if interp not in ("nearest", "bilinear"):
+        raise ValueError("%s: interp must be \"nearest\" or \"bilinear\", got %r" % (fn, interp))
+    if not isinstance(depths, (list, tuple)) or len(depths) != cap.pairs:
+        raise ValueError("%s: depths must be a list of %d maps, one per pair, got %s" %
+                         (fn, cap.pairs, len(depths) if isinstance(depths, (list, tuple)) else type(depths).__name__))
+    for i, d in enumerate(depths):
+        if d is not None and (not isinstance(d, torch.Tensor) or d.dtype != torch.float32 or d.dim() != 2):
+            raise ValueError("%s: depths[%d] must be a float32 [h, w] tensor or None, got %s" %
+                             (fn, i, "%s %s" % (d.dtype, list(d.shape)) if isinstance(d, torch.Tensor) else type(d).__name__))
+    ml, _, _, seg = _lists_on(out, cap, on)
+    table = ops.lift_table(depths, device=ml.device)
+    tab = table.dev
+    mixed = "caller_of" in out
+    if mixed:                                                             # caller order -> slot order
+        idx = _caller_of_dev(out, ml.device)
+        tab = tab.index_select(0, idx)
+        norm, max_depth = (None if v is None else v.index_select(0, idx) for v in (norm, max_depth))
+    points, valid, lift_count = ops.lift_by_pair(ml, None, norm=norm, max_depth=max_depth, interp=interp, max_jump=max_jump, table=tab, **seg)
+    if mixed:
+        lift_count = lift_count.index_select(0, _slot_of_dev(out, cap, ml.device))
+    out["lifted"], out["lifted_table"] = (points, valid, lift_count, on), table       # the table keeps the maps alive
+    return out["lifted"]
+
+
+def _need_lifted(fn, out):
+    if "lifted" not in out:
+        raise ValueError("%s: run lift_by_pair first" % fn)
+    return out["lifted"]
+
+
+def hypothesize_p3p_by_pair(out, cap, H, seed=0, norm=None, progressive=None, samples=False):
+    """Device side, after lift_by_pair: H 3-point samples per pair over the lists that were lifted, each solved for the up to four
+    absolute poses of the RIGHT camera (ops.absolute_hypotheses_by_pair: one launch, no host read).  seed, progressive (default: the
+    lift was on="topk"; the pool's minimum is 3) and norm - whose right half normalises the right points: pass what lift_by_pair was
+    given - exactly as hypothesize_by_pair takes them.  A sample that holds an invalid lift gives no model: the share of such samples
+    is 1 - (lift_count / n)^3.
+    Returns models [pairs,4*H,3,4] float32, a view - or (models, sample_idx [pairs,H,3] int32) with samples=True - in the CALLER's
+    order: sample h owns rows 4 h .. 4 h + 3, its solutions first, zero models (which verification ignores) behind.  They go
+    straight into verify_abs_by_pair.  Adds `hypotheses_p3p` (what is returned) to the result."""
+    fn = "hypothesize_p3p_by_pair"
+    points, _, _, on = _need_lifted(fn, out)
+
+    def generate(ml, mr, H, pair_seed, **kw):
+        return ops.absolute_hypotheses_by_pair(points, mr, H, pair_seed, **kw)
+
+    hyp = _sample_by_pair(fn, generate, out, cap, H, seed, norm, on, progressive, samples)
+    flat = (hyp[0] if samples else hyp).flatten(1, 2)                     # [pairs,H,4,3,4] -> [pairs,4 H,3,4]: a view
+    hyp = (flat, hyp[1]) if samples else flat
+    out["hypotheses_p3p"] = hyp
+    return hyp
+
+
+def verify_abs_by_pair(out, cap, models, thr, norm=None, min_conf=None):
+    """Device side, after lift_by_pair: every pair's M candidate absolute poses (models [pairs,M,3,4] float32, thr [pairs] in
+    normalised units, norm [pairs,8] or None - GPU tensors in the CALLER's order) tested by reprojection against the lifted matches
+    (ops.absolute_score_by_pair: no host read), over the lists that were lifted.  min_conf needs a result made with confidence=True.
+    Stores `verified_abs` = (counts [pairs,M] int32, best [pairs] int32, best_count [pairs] int64, inlier uint8 aligned with the
+    lists) - rows in SLOT order for a mixed pack, like `verified` -, `verified_abs_on` and `verified_abs_models`, and returns the
+    tuple.  `verified`, `verified_h` and `pose` are never touched."""
+    fn = "verify_abs_by_pair"
+    points, _, _, on = _need_lifted(fn, out)
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        idx = _caller_of_dev(out, models.device)
+        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    _, mr, conf, seg = _lists_on(out, cap, on)
+    res = ops.absolute_score_by_pair(points, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, **seg)
+    out["verified_abs"], out["verified_abs_on"], out["verified_abs_models"] = res, on, models
+    return res
+
+
+def pose_abs_by_pair(out, cap, swapped=False):
+    """Device side, after verify_abs_by_pair: each pair's METRIC pose - the winning P3P model widened exactly to float64 (index
+    operations on the device, no host read, no refit).  swapped: the lists are in the hand-over's (y, x) order and the pose is wanted
+    in the reference's (x, y) frame: R -> P R P, t -> P t, as pose_by_pair does.  E = [t]_x R scaled to |E|_F = 1.  A pair without an
+    inlier has no pose: E, R and t are zero (what every consumer reads as "no pose").
+    Stores `pose_abs` in the standard pose layout - (E [pairs,3,3], R [pairs,3,3], t [pairs,3] float64, front_count [pairs] int64 =
+    best_count, counts [pairs,4] int32 = (best_count, 0, 0, 0), choice [pairs] int32 = 0) in the CALLER's order, then front = the
+    winner's inlier mask (slot order) - and returns it; batch.pose_branch(out, "absolute") is the view every consumer of a pose
+    works on.  `pose`, `verified` and `verified_h` are never touched."""
+    if "verified_abs" not in out:
+        raise ValueError("pose_abs_by_pair: run verify_abs_by_pair first")
+    _, best, best_count, inlier = out["verified_abs"]
+    models = out["verified_abs_models"]                                   # slot order
+    pairs, M = int(models.shape[0]), int(models.shape[1])
+    rows = torch.arange(pairs, device=models.device)
+    win = models[rows, best.long().clamp(0, M - 1)].double()              # [pairs,3,4]: exact
+    none = (best_count <= 0).view(pairs, 1, 1)
+    R, t = win[:, :, :3].masked_fill(none, 0.0), win[:, :, 3].masked_fill(none.view(pairs, 1), 0.0)
+    if swapped:
+        perm = torch.tensor([1, 0, 2], device=models.device)
+        R, t = R.index_select(1, perm).index_select(2, perm), t.index_select(1, perm)
+    E = torch.linalg.cross(t.unsqueeze(2).expand(-1, -1, 3), R, dim=1)     # column j = t x R[:, j]: [t]_x R, element-wise work only
+    nrm = E.flatten(1).norm(dim=1).view(pairs, 1, 1)
+    E = torch.where(nrm > 0, E / torch.where(nrm > 0, nrm, torch.ones_like(nrm)), torch.zeros_like(E))
+    counts = torch.zeros((pairs, 4), dtype=torch.int32, device=models.device)
+    counts[:, 0] = best_count.to(torch.int32)
+    res = (E, R.contiguous(), t.contiguous(), best_count.clone(), counts, torch.zeros(pairs, dtype=torch.int32, device=models.device))
+    if "caller_of" in out:                                                # slots back to the caller's order
+        back = _slot_of_dev(out, cap, models.device)
+        res = tuple(v.index_select(0, back) for v in res)
+    out["pose_abs"] = res + (inlier,)
+    return out["pose_abs"]

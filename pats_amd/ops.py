@@ -3168,3 +3168,190 @@ def prepare_images(srcs, plan, left, right, bgr=False, table=None):
     _check(_L().pats_prepare_images_u8(ctypes.c_void_p(table.host.ctypes.data), _ptr(table.dev), len(table.host), _ptr(left), left.numel(),
                                        _ptr(right), right.numel(), _IMG_DTYPES[left.dtype], _stream()), fn)
     return left, right
+
+
+# ---- the absolute-pose branch (csrc/absolute.hip; include/pats_amd.h, "Per-pair absolute pose from depth") ----------------------
+_INTERP = {"nearest": 0, "bilinear": 1, 0: 0, 1: 1}
+
+
+class DepthTable:
+    """The per-pair table of one lift_by_pair call: `host` the numpy [pairs,4] int64 rows (address, h, w, row stride in elements),
+    `dev` the same on the GPU; `maps` keeps the depth maps it points to alive."""
+
+
+def lift_table(depths, device=None):
+    """The table of lift_by_pair for these depth maps: one float32 GPU tensor [h, w] per pair, of any sizes, each its own tensor -
+    a strided view is taken as it lies (its rows must be dense: stride(1) == 1) - or None for a pair without a map (every match of
+    it is invalid, as for a map with h or w = 0).  No copy is made: the table holds the addresses.  Build it once and hand it to
+    lift_by_pair (table=) to call that without an upload."""
+    fn = "lift_by_pair"
+    host = np.zeros((len(depths), 4), np.int64)
+    dev = device
+    for p, t in enumerate(depths):
+        if t is None:
+            continue
+        name = "depths[%d]" % p
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor or None" % (fn, name))
+        if t.dtype != torch.float32 or t.dim() != 2:                        # layout first: refused the same way without a GPU
+            raise RuntimeError("%s: %s must be a float32 [h, w] map, got %s %s" % (fn, name, t.dtype, list(t.shape)))
+        if not t.is_cuda:
+            raise RuntimeError("pats_amd: %s is on %s; the HIP path needs a GPU tensor (no CPU fallback)" % (name, t.device))
+        if dev is None:
+            dev = t.device
+        elif t.device != torch.device(dev):
+            raise RuntimeError("%s: %s is on %s, the others on %s" % (fn, name, t.device, dev))
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if h < 1 or w < 1:
+            continue                                                          # an empty map has no address
+        if (w > 1 and t.stride(1) != 1) or (h > 1 and t.stride(0) < w):
+            raise RuntimeError("%s: %s must have dense rows that do not overlap (strides %s)" % (fn, name, list(t.stride())))
+        host[p] = (t.data_ptr(), h, w, t.stride(0) if h > 1 else w)
+    if dev is None:
+        raise RuntimeError("%s: no depth map to take the device from; pass device=" % fn)
+    tab = DepthTable()
+    tab.host, tab.maps = host, list(depths)
+    tab.dev = torch.from_numpy(host).to(dev)
+    return tab
+
+
+def lift_by_pair(matches, depths, pair_off=None, stride=None, counts=None, norm=None, max_depth=None, interp="nearest", max_jump=None,
+                 out=None, pairs=None, table=None):
+    """One side's matches lifted through that image's depth map to metric 3-D points, ON THE DEVICE, one launch, no host read
+    (pats_lift_by_pair_f32; include/pats_amd.h holds the definition).  matches [cap,2] float32 (also [pairs,K,2]) in the hand-over's
+    (c0, c1) = (y, x) order, un-normalised pixels; the segments as every per-pair stage takes them (pair_off, or stride + counts);
+    depths: the per-pair maps as lift_table takes them - or None with table= a lift_table(...) made earlier (or its [pairs,4] int64
+    GPU tensor, rows in the order of the segments).  norm [pairs,8]: its left half normalises the point.  interp "nearest" or
+    "bilinear" (0 / 1); max_depth [pairs] float32 and max_jump (a float, bilinear only: (max tap - min tap) > max_jump * min tap marks
+    a depth edge) invalidate matches.
+    Returns (points [cap,3] float32 = (x0 d, x1 d, d), NaN for an invalid match and 0 outside the segments; valid [cap] uint8;
+    lift_count [pairs] int64).  out: the three destinations."""
+    fn = "lift_by_pair"
+    _bp_layout(fn, [(matches, "matches"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm"), (max_depth, "max_depth")],
+               {"pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if interp not in _INTERP or isinstance(interp, bool):
+        raise RuntimeError("%s: interp must be \"nearest\" (0) or \"bilinear\" (1), got %r" % (fn, interp))
+    ml = _dev(matches, "matches")
+    if ml.dim() < 2 or ml.shape[-1] != 2:
+        raise RuntimeError("%s: matches must be [cap,2]" % fn)
+    ml = ml.reshape(-1, 2)
+    cap = int(ml.shape[0])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    dev = ml.device
+    if table is None:
+        if depths is None or len(depths) != pairs:
+            raise RuntimeError("%s: depths must hold one map (or None) per pair (%d), got %s" % (fn, pairs, "None" if depths is None else len(depths)))
+        table = lift_table(depths, device=dev)
+    tab = table.dev if isinstance(table, DepthTable) else table
+    tab = _dev(tab, "table", torch.int64)
+    if tuple(tab.shape) != (pairs, 4):
+        raise RuntimeError("%s: the depth table must be [pairs,4] int64 (%d pairs), got %s" % (fn, pairs, list(tab.shape)))
+    norm = _bp_norm(fn, norm, pairs)
+    if max_depth is not None:
+        max_depth = _dev(max_depth, "max_depth").reshape(-1)
+        if max_depth.numel() != pairs:
+            raise RuntimeError("%s: max_depth must hold one float32 per pair (%d), got %d" % (fn, pairs, max_depth.numel()))
+    want = [("points", torch.float32, (cap, 3)), ("valid", torch.uint8, (cap,)), ("lift_count", torch.int64, (pairs,))]
+    out = _bp_outputs(fn, want, out, dev)
+    points, valid = out[0], out[1]
+    if cap == 0:
+        ml = points = _bp_placeholder(dev)
+        valid = _bp_placeholder(dev, torch.uint8)
+    _check(_L().pats_lift_by_pair_f32(_ptr(ml), off_p, stride, counts_p, pairs, cap, _ptr(norm), _ptr(tab), _ptr(max_depth), _INTERP[interp],
+                                      0 if max_jump is None else 1, 0.0 if max_jump is None else float(max_jump), _ptr(points),
+                                      _ptr(valid), _ptr(out[2]), _stream()), fn)
+    return out
+
+
+def _abs_lists(fn, points, matches_r):
+    """The lifted points ([cap,3], or [pairs,K,3]) and the right list as flat GPU lists -> (points, mr, cap)."""
+    X, mr = _dev(points, "points"), _dev(matches_r, "matches_r")
+    if X.dim() < 2 or X.shape[-1] != 3 or mr.dim() < 2 or mr.shape[-1] != 2 or X.numel() // 3 != mr.numel() // 2:
+        raise RuntimeError("%s: points must be [cap,3] and matches_r [cap,2]" % fn)
+    X = X.reshape(-1, 3)
+    return X, mr.reshape(-1, 2), int(X.shape[0])
+
+
+def absolute_hypotheses_by_pair(points, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
+                                return_samples=False, return_counts=False, out=None, pairs=None):
+    """H P3P samples per pair, each solved for the up to four absolute poses (R, t) with x_r ~ R X + t, ON THE DEVICE, one launch, no
+    host read (pats_absolute_hypotheses_by_pair_f32; include/pats_amd.h holds the definition).  points [cap,3] float32 = lift_by_pair's,
+    matches_r [cap,2] the right list (norm's right half normalises it), seed [pairs] int64, the segments and progressive as
+    epipolar_hypotheses_by_pair takes them (the pool's minimum is 3).  A sample with an invalid (NaN) point gives no model.
+    Returns models [pairs,H,4,3,4] float32 - row-major [R | t], the kept solutions first by ascending camera distance of the first
+    sample point, zero models behind - then sample_idx [pairs,H,3] int32 with return_samples=True and n_models [pairs,H] int32 with
+    return_counts=True.  out: the destinations, in that order."""
+    fn = "absolute_hypotheses_by_pair"
+    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")],
+               {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("%s: seed must be an int64 GPU tensor [pairs]" % fn)
+    X, mr, cap = _abs_lists(fn, points, matches_r)
+    H = int(H)
+    seed = _dev(seed, "seed", torch.int64).reshape(-1)
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if seed.numel() != pairs:
+        raise RuntimeError("%s: seed must hold one int64 per pair (%d), got %d" % (fn, pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h() // 4:
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d (4 H models)" % (fn, H, epipolar_max_h() // 4))
+    norm = _bp_norm(fn, norm, pairs)
+    dev = X.device
+    want = [("models", torch.float32, (pairs, H, 4, 3, 4))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, 3)))
+    if return_counts:
+        want.append(("n_models", torch.int32, (pairs, H)))
+    out = _bp_outputs(fn, want, out, dev, lone=True)
+    if cap == 0:
+        X = mr = _bp_placeholder(dev)
+    _check(_L().pats_absolute_hypotheses_by_pair_f32(_ptr(X), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
+                                                     1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
+                                                     _ptr(out[-1]) if return_counts else None, _stream()), fn)
+    return out if len(out) > 1 else out[0]
+
+
+def absolute_score_by_pair(points, matches_r, models, thr, pair_off=None, stride=None, counts=None, conf=None, min_conf=None, norm=None,
+                           out=None, pairs=None):
+    """M candidate absolute poses per pair against every lifted match of the pair by REPROJECTION, ON THE DEVICE, no host read
+    (pats_absolute_score_by_pair_f32; include/pats_amd.h holds the definition): with Y = R X + t a match is an inlier iff it takes
+    part (X and x_r finite, conf >= min_conf), Y2 > 0 and (Y0 - r0 Y2)^2 + (Y1 - r1 Y2)^2 <= thr^2 Y2^2.  points [cap,3] float32,
+    matches_r [cap,2], models [pairs,M,3,4] float32 (row-major [R | t]; M <= epipolar_max_h()), thr [pairs] float32 in normalised
+    units; the segments, conf / min_conf and norm (its right half) as epipolar_score_by_pair takes them.
+    Returns (counts [pairs,M] int32, best [pairs] int32 - the lowest index among the largest counts -, best_count [pairs] int64,
+    inlier [cap] uint8 = the winner's mask).  Bit-reproducible.  out: the four destinations."""
+    fn = "absolute_score_by_pair"
+    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"), (counts, "counts"),
+                    (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("%s: min_conf needs conf" % fn)
+    X, mr, cap = _abs_lists(fn, points, matches_r)
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 4):
+        raise RuntimeError("%s: models must be [pairs,M,3,4]" % fn)
+    M = int(models.shape[1])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("%s: models [pairs,M,3,4] and thr [pairs] must hold %d pairs" % (fn, pairs))
+    if not 1 <= M <= epipolar_max_h():
+        raise RuntimeError("%s: M = %d, must lie in 1 .. %d" % (fn, M, epipolar_max_h()))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("%s: conf must be [cap]" % fn)
+    norm = _bp_norm(fn, norm, pairs)
+    dev = X.device
+    want = [("counts", torch.int32, (pairs, M)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
+            ("inlier", torch.uint8, (cap,))]
+    out = _bp_outputs(fn, want, out, dev)
+    inl = out[3]
+    if cap == 0:
+        X = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else X
+    _check(_L().pats_absolute_score_by_pair_f32(_ptr(X), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), M, _ptr(thr),
+                                                _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
+                                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl), _stream()), fn)
+    return out
