@@ -1820,8 +1820,9 @@ int pats_scale_head_f32(const float* x, int64_t batch, int C, int ld, int h, int
  * verified by reprojection.  The result is a metric (R, t) - what the two-view stages cannot give.  Three entry points; each takes
  * the per-pair segments in the two forms of pats_epipolar_score_by_pair_f32 (ragged pair_off, or stride with counts_in, exactly
  * ONE of them, with the same clamping), issues a fixed number of launches for the whole batch and reads nothing back.
- * What it is not: a refit of the winner on its inliers (linear or non-linear), MSAC, adaptive stopping, a local optimisation, a
- * sampler that skips invalid matches; nothing in pipeline.forward_* or the drop-in calls it.
+ * The refit of the winner on its inliers and its local optimisation are "Per-pair absolute local optimisation" below.
+ * What it is not: MSAC, adaptive stopping, a sampler that skips invalid matches; nothing in pipeline.forward_* or the drop-in calls
+ * it.
  *
  * 1. The lift.  Inputs
  *   matches [cap,2] float32   ONE side's list in the hand-over's (c0, c1) = (y, x) order, un-normalised pixels of the map
@@ -1886,6 +1887,57 @@ int pats_absolute_score_by_pair_f32(const float* points, const float* matches_r,
                                     int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t M,
                                     const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts,
                                     int32_t* best, int64_t* best_count, uint8_t* inlier, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair absolute local optimisation (ABI 8, a symbol added): the rounds "refit the pose on the winner's inliers by Gauss-Newton on
+ * the reprojection error, verify the refit" that follow pats_absolute_score_by_pair_f32, walked by ONE launch for the whole batch -
+ * one workgroup per pair, the pair's matches resident in LDS, nothing read back, no workspace, no atomics - and the best round kept.
+ * The inputs up to min_conf are pats_absolute_score_by_pair_f32's, with its segments, normalisation and confidence gate; best [pairs]
+ * int32 is its output (null: M == 1); T = rounds (1 .. 16); G = steps (1 .. 8; the callers' default is 3).
+ *
+ *   support(m)   (c, mask): what pats_absolute_score_by_pair_f32 returns for pair p when m is its one model (M = 1), bit for bit -
+ *                the same loads and the same float32 test, so mask's sum is c exactly
+ *   sums(m, mask)  with R, t = m in float64, over the matches of mask in the FIXED order below:  Y = R X + t, each row
+ *                ((m_k0 X0 + m_k1 X1) + m_k2 X2) + m_k3;  iz = 1 / Y2,  u = Y0 iz,  v = Y1 iz;  e = (u - r0, v - r1);  the Jacobian of
+ *                e for a left perturbation Y -> Y + w x Y + tau, unknowns (w0, w1, w2, tau0, tau1, tau2), which is
+ *                [[1/Y2, 0, -u/Y2], [0, 1/Y2, -v/Y2]] [ -[Y]x | I ] written out:
+ *                    J0 = (-u v,  1 + u u,  -v,  iz,  0,  -u iz)        J1 = (-(1 + v v),  u v,  u,  0,  iz,  -v iz)
+ *                A = sum J^T J (the 21 entries of the upper triangle, row by row), b = sum J^T e (6), S = sum |e|^2 (1): 28 float64
+ *                sums, every product and sum rounded once, no contraction
+ *   step(m, mask)  A = L L^T in index order without pivoting; "no step" if a pivot p_k = A_kk - sum_q<k L_kq^2 is not finite or not
+ *                > 1e-12 A_kk;  d = -A^-1 b by the two triangular solves;  with w = d[0:3], tau = d[3:6], th = |w|:
+ *                exp([w]x) = I + (sin th / th) [w]x + (2 sin^2(th / 2) / th^2) [w]x^2 (the identity for th = 0);
+ *                R' = exp([w]x) R,  t' = exp([w]x) t + tau;  "no step" if an entry of (R', t') is not finite
+ *   refit(m, mask, c)  "no refit" if c < 4.  Otherwise G steps in float64, the first from m widened, ALL on the same mask (plain
+ *                Gauss-Newton: no damping, no line search); then R <- R + R (I - R^T R) / 2 - one Newton step towards the nearest
+ *                rotation: the steps carry the float32 input's R^T R along, eps32 off the identity, and this squares that distance,
+ *                so the cast leaves |R^T R - I|_max <= 4 eps32 after any number of rounds -; then the cast to float32 (round to
+ *                nearest even).  A "no step" at any of the G steps, or a cast that is not finite, is "no refit".  "No refit"
+ *                returns m itself
+ *   m_0          models[p, clamp(best[p], 0, M - 1)];   (c_0, mask_0) = support(m_0);   S_0 = S of sums(m_0, mask_0)
+ *   round r = 1 .. T   m_r = refit(m_{r-1}, mask_{r-1}, c_{r-1});   (c_r, mask_r) = support(m_r);   S_r likewise.  The first step of
+ *                round r + 1 uses the very sums whose S is S_r: one pass over the matches, not two
+ *                m_r equal to m_{r-1} bit for bit ends the walk: every later round would repeat it; c and S are copied into the rest
+ *   b            walking r = 0 .. T, round r replaces the best so far iff c_r is larger, or equal with S_r smaller (a NaN S_r never
+ *                is): the largest c_r, among those the smallest S_r, among those the lowest r.  Round 0 is the input: never less support
+ *   outputs      model [pairs,3,4] float32 = m_b;  best_count [pairs] int64 = c_b;  inlier [cap] uint8 = mask_b, every byte of cap
+ *                written (zeros outside the segments);  best_round [pairs] int32 = b;  counts [pairs,T+1] int32 = c_0 .. c_T;
+ *                cost [pairs,T+1] float64 = S_0 .. S_T
+ * A NaN or negative thr[p], or an empty segment: c_r = 0, S_r = 0, b = 0, model = m_0.  c_r = 0 gives S_r = 0 (an empty sum).
+ * The fixed order of the 28 sums, as "Per-pair local optimisation" fixes its moments': thread j of 512 adds the inliers among matches
+ * j, j + 512, j + 1024, ... of the segment in that order; the 64 sums of a wave are added by the xor tree (lane ^ 32, ^ 16, ^ 8, ^ 4,
+ * ^ 2, ^ 1); the 8 waves' sums are added in wave order starting from 0.0.  Two calls give the same bits in all six outputs; a change of
+ * the walk's width or of this order changes them and is a change of this definition.
+ * Refused before any launch: what pats_absolute_score_by_pair_f32 refuses of the shared arguments (a null points / matches_r / models
+ * / thr; here also a null model / best_count / inlier / best_round / counts / cost; best_count and cost off 8 bytes, best off 4; the
+ * segment rules; M outside 1 .. pats_epipolar_max_h; use_min_conf without conf, a negative or NaN min_conf), then rounds outside
+ * 1 .. 16, steps outside 1 .. 8, a null best with M > 1.  PATS_ERR_UNSUPPORTED if the device refuses the dynamic LDS.  cap == 0 is a
+ * valid call. */
+int pats_absolute_polish_by_pair_f32(const float* points, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                     int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models, int64_t M,
+                                     const float* thr, const float* norm, int use_min_conf, float min_conf, const int32_t* best, int rounds,
+                                     int steps, float* model, int64_t* best_count, uint8_t* inlier, int32_t* best_round, int32_t* counts,
+                                     double* cost, pats_stream_t stream);
 
 #ifdef __cplusplus
 }

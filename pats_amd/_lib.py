@@ -325,6 +325,10 @@ SIGNATURES = {
                                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pats_absolute_score_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
                                                 c_void_p, c_void_p, c_int, c_f, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ... and its local optimisation: the verification's arguments up to min_conf, then best, rounds, steps, the six outputs, stream
+    "pats_absolute_polish_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
+                                                 c_void_p, c_void_p, c_int, c_f, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -1213,6 +1213,39 @@ def verify_abs_by_pair(out, cap, models, thr, norm=None, min_conf=None):
     return res
 
 
+def polish_abs_by_pair(out, cap, thr, rounds=4, steps=3, norm=None, min_conf=None):
+    """Device side, after verify_abs_by_pair: the local optimisation of each pair's winning absolute pose
+    (ops.absolute_polish_by_pair: ONE launch for all rounds, no host read) - `rounds` times "refit the pose on its inliers by `steps`
+    Gauss-Newton steps on the reprojection error, verify the refit" on the lifted lists that verification scored, starting from
+    `verified_abs_models` and its `best`, the best round kept (round 0 is the verified winner: the result never has less support).
+    thr [pairs], norm [pairs,8] or None in the CALLER's order and min_conf - pass what verify_abs_by_pair was given; they are permuted
+    to slot order on the device as there.
+    Stores `polished_abs` = (model [pairs,3,4] float32, best_round [pairs] int32, counts [pairs, rounds + 1] int32, cost
+    [pairs, rounds + 1] float64) and REPLACES `verified_abs` by the standard tuple of the polished model - (counts [pairs,1] int32,
+    best = 0, best_count, inlier) - and `verified_abs_models` by model[:, None], all in SLOT order like the verification's:
+    pose_abs_by_pair and pose_branch(out, "absolute") work on the polished result unchanged and hand the pairs back in the caller's
+    order.  `verified`, `verified_h`, `pose` and `lifted` are never touched.  Returns the new `verified_abs`."""
+    fn = "polish_abs_by_pair"
+    if "verified_abs" not in out:
+        raise ValueError("%s: run verify_abs_by_pair first" % fn)
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
+    points = out["lifted"][0]
+    on, best = out["verified_abs_on"], out["verified_abs"][1]
+    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
+        idx = _caller_of_dev(out, thr.device)
+        thr = thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    _, mr, conf, seg = _lists_on(out, cap, on)
+    model, best_count, inl, best_round, counts, cost = ops.absolute_polish_by_pair(
+        points, mr, out["verified_abs_models"], thr, best=best, rounds=rounds, steps=steps, conf=conf if min_conf is not None else None,
+        min_conf=min_conf, norm=norm, **seg)
+    out["polished_abs"] = (model, best_round, counts, cost)
+    out["verified_abs"] = (best_count.to(torch.int32)[:, None], torch.zeros_like(best), best_count, inl)
+    out["verified_abs_models"] = model[:, None]
+    return out["verified_abs"]
+
+
 def pose_abs_by_pair(out, cap, swapped=False):
     """Device side, after verify_abs_by_pair: each pair's METRIC pose - the winning P3P model widened exactly to float64 (index
     operations on the device, no host read, no refit).  swapped: the lists are in the hand-over's (y, x) order and the pose is wanted

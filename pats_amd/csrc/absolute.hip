@@ -1,7 +1,8 @@
 // The absolute-pose branch of the per-pair stages: a match of the left (database) image is lifted through that image's depth map to a
-// metric 3-D point, the right (query) camera is hypothesised from three lifted matches (P3P) and verified by reprojection.  Three
-// entry points, each a fixed number of launches for the whole batch and no host read.  include/pats_amd.h states the definitions
-// ("Per-pair absolute pose from depth"); docs/kernels.md 4.21 the design.
+// metric 3-D point, the right (query) camera is hypothesised from three lifted matches (P3P) and verified by reprojection, and the
+// winner is refitted on its inliers.  Four entry points, each a fixed number of launches for the whole batch and no host read.
+// include/pats_amd.h states the definitions ("Per-pair absolute pose from depth", "Per-pair absolute local optimisation");
+// docs/kernels.md 4.21 and 4.22 the design.
 //
 //   lift        absolute_lift_kernel: one workgroup of ABS_LIFT_THREADS per pair walks the segment; abs_lift_one is the whole
 //               definition of one match (float32, no contraction).  Every row of the segment is stored (a point, or three NaNs), the
@@ -18,6 +19,15 @@
 //               global memory every pass instead: the same values
 //   argmax      absolute_argmax_kernel: the verification's rule - the largest count, the lowest index that holds it (0 for no inlier)
 //   mask        absolute_mask_kernel: the winner's verdict for every match with abs_test2, so the mask's sum is best_count exactly
+//   polish      absolute_polish_kernel ("Per-pair absolute local optimisation"; docs/kernels.md 4.22): one workgroup of
+//               ABS_POLISH_THREADS per pair walks ALL rounds "refit the winner on its inliers, verify the refit" in one launch.  The
+//               segment is staged once through abs_load into the score kernel's five planes (a longer one is walked in global memory:
+//               the same values).  A pass tests every match with abs_test2 against the round's float32 model - the count, and the
+//               mask of all the round's passes: recomputed, never stored - and adds an inlier's 28 float64 sums (J^T J, J^T e, |e|^2 of
+//               the reprojection error) at the float64 model the next Gauss-Newton step starts from; the sums are reduced in a FIXED
+//               order (thread-local in index order, the xor tree over the wave, the waves in order), thread 0 solves the 6 x 6 system
+//               by Cholesky and applies the Rodrigues update; behind the last step R is made orthonormal and the model cast to
+//               float32.  The best round's model stays in LDS; one last pass writes its mask.  No atomics, no workspace
 #include "common.hpp"
 #include "epipolar.hpp"
 #include "p3p.hpp"
@@ -369,17 +379,318 @@ absolute_mask_kernel(const float* __restrict__ points, const float* __restrict__
     }
 }
 
-// the staging can exceed the 64 KiB a launch gets unasked: raised once per device
-static bool abs_lds_ready() {
-    static int state[64] = {0};
+// ---- local optimisation (include/pats_amd.h, "Per-pair absolute local optimisation") ----------------------------------------------
+constexpr int ABS_POLISH_THREADS = 512;                 // the walk whose width fixes the sums' bits
+constexpr int ABS_POLISH_WAVES = ABS_POLISH_THREADS / WAVE;
+constexpr int ABS_POLISH_MAX_ROUNDS = 16;
+constexpr int ABS_POLISH_MAX_STEPS = 8;
+constexpr int ABS_POLISH_MIN_INLIERS = 4;
+constexpr int ABS_SUMS = 28;                            // A's upper triangle row by row (21), b (6), S (1)
+
+// match i of the segment as the passes see it: from the staged planes, or through abs_load (staged is workgroup-uniform)
+__device__ __forceinline__ void abs_fetch1(bool staged, const float* __restrict__ stage, int stage_n, const float* __restrict__ X_,
+                                           const float2* __restrict__ mr, const float* __restrict__ conf, uint32_t i, uint32_t n, bool has_norm,
+                                           const EpiNorm& nm, bool gate, float min_conf, float (&a)[5]) {
+    if (staged) {
+        a[0] = __builtin_nanf("");
+        a[1] = a[2] = a[3] = a[4] = 0.0f;
+        if (i < n) {                                    // n <= stage_n, the slots per plane the launch allocated
+#pragma unroll
+            for (int k = 0; k < 5; ++k) a[k] = stage[k * stage_n + i];
+        }
+    } else {
+        abs_load(X_, mr, conf, i, n, has_norm, nm, gate, min_conf, a[0], a[1], a[2], a[3], a[4]);
+    }
+}
+
+// THE sums of one inlier at the float64 model m = [R | t]: every sum and product rounded once, left to right
+__device__ __forceinline__ void abs_polish_accumulate(const double (&m)[12], const float (&a)[5], double (&acc)[ABS_SUMS]) {
+    const double X0 = (double)a[0], X1 = (double)a[1], X2 = (double)a[2];
+    const double Y0 = ((m[0] * X0 + m[1] * X1) + m[2] * X2) + m[3];
+    const double Y1 = ((m[4] * X0 + m[5] * X1) + m[6] * X2) + m[7];
+    const double Y2 = ((m[8] * X0 + m[9] * X1) + m[10] * X2) + m[11];
+    const double iz = 1.0 / Y2, u = Y0 * iz, v = Y1 * iz;
+    const double e0 = u - (double)a[3], e1 = v - (double)a[4];
+    const double uv = u * v;
+    const double J0[6] = {-uv, 1.0 + u * u, -v, iz, 0.0, -(u * iz)};
+    const double J1[6] = {-(1.0 + v * v), uv, u, 0.0, iz, -(v * iz)};
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) acc[k++] += J0[r] * J0[c] + J1[r] * J1[c];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) acc[21 + r] += J0[r] * e0 + J1[r] * e1;
+    acc[27] += e0 * e0 + e1 * e1;
+}
+
+// one Gauss-Newton step on the reduced sums s, on ONE thread: A = L L^T in index order without pivoting, d = -A^-1 b, the left
+// update by Rodrigues' formula.  false = "no step" (m is then not to be used)
+__device__ __forceinline__ bool abs_polish_step(const double (&s)[ABS_SUMS], double (&m)[12]) {
+    double A[6][6], L[6][6], y[6], d[6];
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 6; ++c) { A[r][c] = s[k]; A[c][r] = s[k]; ++k; }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double p = A[j][j];
+#pragma unroll
+        for (int q = 0; q < j; ++q) p -= L[j][q] * L[j][q];
+        ok = ok && __builtin_isfinite(p) && p > 1e-12 * A[j][j];
+        const double l = __builtin_sqrt(p);
+        L[j][j] = l;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double x = A[i][j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) x -= L[i][q] * L[j][q];
+            L[i][j] = x / l;
+        }
+    }
+    if (!ok) return false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {                       // L y = -b
+        double x = -s[21 + i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) x -= L[i][q] * y[q];
+        y[i] = x / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {                      // L^T d = y
+        double x = y[i];
+#pragma unroll
+        for (int q = i + 1; q < 6; ++q) x -= L[q][i] * d[q];
+        d[i] = x / L[i][i];
+    }
+    // exp([w]x) = I + a [w]x + b [w]x^2,  a = sin(th) / th,  b = 2 sin^2(th / 2) / th^2,  [w]x^2 = w w^T - th^2 I
+    const double w0 = d[0], w1 = d[1], w2 = d[2];
+    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
+    double E[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    if (th2 > 0.0) {
+        const double th = __builtin_sqrt(th2), sh = sin(0.5 * th);
+        const double a = sin(th) / th, b = 2.0 * (sh * sh) / th2;
+        E[0][0] = 1.0 + b * (w0 * w0 - th2); E[0][1] = b * (w0 * w1) - a * w2;     E[0][2] = b * (w0 * w2) + a * w1;
+        E[1][0] = b * (w0 * w1) + a * w2;     E[1][1] = 1.0 + b * (w1 * w1 - th2); E[1][2] = b * (w1 * w2) - a * w0;
+        E[2][0] = b * (w0 * w2) - a * w1;     E[2][1] = b * (w1 * w2) + a * w0;     E[2][2] = 1.0 + b * (w2 * w2 - th2);
+    }
+    double o[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[4 * r + c] = (E[r][0] * m[c] + E[r][1] * m[4 + c]) + E[r][2] * m[8 + c];
+        o[4 * r + 3] = ((E[r][0] * m[3] + E[r][1] * m[7]) + E[r][2] * m[11]) + d[3 + r];
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) { ok = ok && __builtin_isfinite(o[q]); m[q] = o[q]; }
+    return ok;
+}
+
+// R <- R + R (I - R^T R) / 2: one Newton step towards the nearest rotation.  The steps leave R^T R where the float32 input had it
+// (eps32 off the identity), the step squares that distance
+__device__ __forceinline__ void abs_polish_orthonormal(double (&m)[12]) {
+    double G[3][3], o[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[r][c] = (r == c ? 1.0 : 0.0) - ((m[r] * m[c] + m[4 + r] * m[4 + c]) + m[8 + r] * m[8 + c]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[3 * r + c] = m[4 * r + c] + 0.5 * ((m[4 * r] * G[0][c] + m[4 * r + 1] * G[1][c]) + m[4 * r + 2] * G[2][c]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m[4 * r + c] = o[3 * r + c];
+}
+
+// One workgroup per pair walks all rounds.  A round's passes over the segment: the first tests with m_r (abs_test2, the count) and sums
+// at m_r widened; passes 2 .. G sum at the stepped float64 model over the SAME matches - the mask is m_r's verdict again, not a copy.
+// Every pass reduces its ABS_SUMS thread-local sums (ascending i, stride ABS_POLISH_THREADS) by the xor tree over the wave, then the
+// waves in order; thread 0 takes the step.  stage_n = the slots per plane of dynamic LDS: min(longest possible segment, ABS_STAGE)
+__global__ void __launch_bounds__(ABS_POLISH_THREADS)
+absolute_polish_kernel(const float* __restrict__ points, const float* __restrict__ mr_, const float* __restrict__ conf_,
+                       const int64_t* __restrict__ pair_off, const int64_t* __restrict__ counts_in, int64_t stride, int64_t cap,
+                       const float* __restrict__ models, int M, const float* __restrict__ thr, const float* __restrict__ norm, int gate,
+                       float min_conf, const int32_t* __restrict__ best, int rounds, int steps, int stage_n, float* __restrict__ model_out,
+                       int64_t* __restrict__ best_count, uint8_t* __restrict__ inlier, int32_t* __restrict__ best_round,
+                       int32_t* __restrict__ counts_out, double* __restrict__ cost_out) {
+    extern __shared__ __attribute__((aligned(16))) float abs_polish_stage[];
+    __shared__ double part[ABS_POLISH_WAVES][ABS_SUMS];
+    __shared__ double s_sum[ABS_SUMS];
+    __shared__ double s_m64[12];
+    __shared__ float s_model[12], s_model_best[12];
+    __shared__ int s_wcnt[ABS_POLISH_WAVES];
+    __shared__ int s_state;                             // after a step: 0 = step on, 1 = a new model is in s_model, 2 = the walk has ended
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int64_t lo;
+    uint32_t n;
+    epi_segment(pair_off, counts_in, stride, cap, p, lo, n);
+    const float t = thr[p];
+    const bool live_t = t >= 0.0f;                      // NaN or negative threshold: no match is an inlier of any model
+    const float t2 = t * t;
+    const float* X_ = points + lo * 3;
+    const float2* mr = reinterpret_cast<const float2*>(mr_) + lo;
+    const float* conf = conf_ ? conf_ + lo : nullptr;
+    const EpiNorm nm = epi_norm(norm, p);
+    const bool staged = n <= (uint32_t)stage_n;         // workgroup-uniform
+
+    // ---- stage, and round 0's model -----------------------------------------------------------------------------------------
+    if (staged) {
+        for (uint32_t i = tid; i < n; i += ABS_POLISH_THREADS) {        // at most ABS_STAGE / ABS_POLISH_THREADS trips
+            float a[5];
+            abs_load(X_, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, a[0], a[1], a[2], a[3], a[4]);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) abs_polish_stage[k * stage_n + i] = a[k];
+        }
+    }
+    if (tid < 12) {
+        int h = best ? best[p] : 0;                     // a null best: M == 1
+        h = h < 0 ? 0 : (h >= M ? M - 1 : h);
+        s_model[tid] = models[((int64_t)p * M + h) * 12 + tid];
+    }
+    wg_barrier();
+
+    int best_c = -1, best_r = 0;                        // workgroup-uniform: every thread computes every count and cost
+    double best_S = 0.0, last_S = 0.0;
+    int last_r = 0, last_c = 0;
+#pragma unroll 1
+    for (int r = 0; r <= ABS_POLISH_MAX_ROUNDS; ++r) {
+        float e[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) e[k] = s_model[k];
+        const float mine_m = tid < 12 ? s_model[tid] : 0.0f;
+        bool ended = false;
+#pragma unroll 1
+        for (int g = 0; g < ABS_POLISH_MAX_STEPS; ++g) {
+            // ---- one pass: support(m_r) and the sums at the model the next step starts from -------------------------------------
+            double m[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) m[k] = g == 0 ? (double)e[k] : s_m64[k];
+            double acc[ABS_SUMS];
+#pragma unroll
+            for (int k = 0; k < ABS_SUMS; ++k) acc[k] = 0.0;
+            int wcnt = 0;
+            if (live_t) {                               // workgroup-uniform
+                for (uint32_t i0 = 0; i0 < n; i0 += ABS_POLISH_THREADS) {
+                    float a[5];
+                    abs_fetch1(staged, abs_polish_stage, stage_n, X_, mr, conf, i0 + tid, n, norm != nullptr, nm, gate != 0, min_conf, a);
+                    abs_v2f s, lim, y2;
+                    abs_test2(e, t2, abs_splat(a[0]), abs_splat(a[1]), abs_splat(a[2]), abs_splat(a[3]), abs_splat(a[4]), s, lim, y2);
+                    const bool in = y2.x > 0.0f && s.x <= lim.x;
+                    wcnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
+                    if (in) abs_polish_accumulate(m, a, acc);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < ABS_SUMS; ++k) {
+                double v = acc[k];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (lane == 0) part[wave][k] = v;
+            }
+            if (lane == 0) s_wcnt[wave] = wcnt;
+            wg_barrier();
+            if (tid < ABS_SUMS) {
+                double v = 0.0;
+#pragma unroll
+                for (int w = 0; w < ABS_POLISH_WAVES; ++w) v += part[w][tid];
+                s_sum[tid] = v;
+            }
+            wg_barrier();
+            int c = 0;
+#pragma unroll
+            for (int w = 0; w < ABS_POLISH_WAVES; ++w) c += s_wcnt[w];
+            if (g == 0) {                               // (c_r, S_r): the best rule, and the walk's end
+                const double S = s_sum[27];
+                if (tid == 0) { counts_out[p * (rounds + 1) + r] = c; cost_out[p * (rounds + 1) + r] = S; }
+                last_r = r; last_c = c; last_S = S;
+                if (c > best_c || (c == best_c && S < best_S)) {
+                    best_c = c; best_S = S; best_r = r;
+                    if (tid < 12) s_model_best[tid] = mine_m;
+                }
+                if (r >= rounds) { ended = true; break; }
+            }
+            // ---- thread 0: the step; behind the last one the cast, and whether the model repeats ------------------------------
+            if (tid == 0) {
+                double sm[ABS_SUMS], mm[12];
+#pragma unroll
+                for (int k = 0; k < ABS_SUMS; ++k) sm[k] = s_sum[k];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) mm[k] = m[k];
+                bool ok = c >= ABS_POLISH_MIN_INLIERS && abs_polish_step(sm, mm);
+                int state = 0;
+                if (ok && g + 1 < steps) {
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) s_m64[k] = mm[k];
+                } else {
+                    float f[12];
+                    if (ok) {
+                        abs_polish_orthonormal(mm);
+#pragma unroll
+                        for (int k = 0; k < 12; ++k) { f[k] = (float)mm[k]; ok = ok && __builtin_isfinite(f[k]); }
+                    }
+                    bool same = true;                   // "no refit" returns m_r itself
+                    if (ok) {
+#pragma unroll
+                        for (int k = 0; k < 12; ++k) {
+                            same = same && __float_as_uint(f[k]) == __float_as_uint(s_model[k]);
+                            s_model[k] = f[k];
+                        }
+                    }
+                    state = same ? 2 : 1;
+                }
+                s_state = state;
+            }
+            wg_barrier();
+            if (s_state != 0) { ended = s_state == 2; break; }
+        }
+        if (ended) break;
+    }
+    if (tid == 0) {                                     // a walk that ended early: every later round repeats the last one scored
+        for (int q = last_r + 1; q <= rounds; ++q) { counts_out[p * (rounds + 1) + q] = last_c; cost_out[p * (rounds + 1) + q] = last_S; }
+    }
+    wg_barrier();                                       // the best model is in LDS
+
+    // ---- outputs, and the best round's mask ----------------------------------------------------------------------------------
+    if (tid < 12) model_out[p * 12 + tid] = s_model_best[tid];
+    if (tid == 0) { best_count[p] = (int64_t)best_c; best_round[p] = best_r; }
+    if (!live_t || best_c <= 0) return;                 // the mask was zeroed before the launch
+    float e[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) e[k] = s_model_best[k];
+    for (uint32_t i0 = 0; i0 < n; i0 += ABS_POLISH_THREADS) {
+        const uint32_t i = i0 + tid;
+        float a[5];
+        abs_fetch1(staged, abs_polish_stage, stage_n, X_, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, a);
+        abs_v2f s, lim, y2;
+        abs_test2(e, t2, abs_splat(a[0]), abs_splat(a[1]), abs_splat(a[2]), abs_splat(a[3]), abs_splat(a[4]), s, lim, y2);
+        if (i < n) inlier[lo + i] = y2.x > 0.0f && s.x <= lim.x ? 1 : 0;
+    }
+}
+
+// the staging can exceed the 64 KiB a launch gets unasked: raised once per device and kernel
+static bool abs_lds_raise(const void* kernel, int (&state)[64]) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
     if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)absolute_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ABS_LDS) == hipSuccess;
+        const bool ok = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ABS_LDS) == hipSuccess;
         if (!ok) (void)hipGetLastError();
         state[dev] = ok ? 1 : -1;
     }
     return state[dev] == 1;
+}
+static bool abs_lds_ready() {
+    static int state[64] = {0};
+    return abs_lds_raise((const void*)absolute_score_kernel, state);
+}
+static bool abs_polish_lds_ready() {
+    static int state[64] = {0};
+    return abs_lds_raise((const void*)absolute_polish_kernel, state);
 }
 
 }  // namespace pats
@@ -491,4 +802,49 @@ extern "C" int pats_absolute_score_by_pair_f32(const float* points, const float*
     hipLaunchKernelGGL(absolute_mask_kernel, dim3((unsigned)pairs), dim3(ABS_MASK_THREADS), 0, st, points, matches_r, cf, pair_off, counts_in,
                        stride, cap, models, (int)M, thr, norm, use_min_conf, min_conf, best, best_count, inlier);
     return check_launch("absolute_mask kernel");
+}
+
+extern "C" int pats_absolute_polish_by_pair_f32(const float* points, const float* matches_r, const float* conf, const int64_t* pair_off,
+                                                int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, const float* models,
+                                                int64_t M, const float* thr, const float* norm, int use_min_conf, float min_conf,
+                                                const int32_t* best, int rounds, int steps, float* model, int64_t* best_count,
+                                                uint8_t* inlier, int32_t* best_round, int32_t* counts, double* cost, pats_stream_t stream) {
+    const char* who = "absolute_polish_by_pair";
+    EPI_REQUIRE_PTR(points, 4);
+    EPI_REQUIRE_PTR(matches_r, 8);
+    EPI_REQUIRE_PTR(models, 4);
+    EPI_REQUIRE_PTR(thr, 4);
+    EPI_REQUIRE_PTR(model, 4);
+    EPI_REQUIRE_PTR(best_count, 8);
+    PATS_REQUIRE(inlier, "%s: null inlier", who);
+    EPI_REQUIRE_PTR(best_round, 4);
+    EPI_REQUIRE_PTR(counts, 4);
+    EPI_REQUIRE_PTR(cost, 8);
+    EPI_REQUIRE_ALIGNED(conf, 4);                       // optional pointers: null is aligned
+    EPI_REQUIRE_ALIGNED(norm, 4);
+    EPI_REQUIRE_ALIGNED(pair_off, 8);
+    EPI_REQUIRE_ALIGNED(counts_in, 8);
+    EPI_REQUIRE_ALIGNED(best, 4);
+    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_h(who, M);
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
+    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
+    PATS_REQUIRE(rounds >= 1 && rounds <= ABS_POLISH_MAX_ROUNDS, "%s: rounds = %d (1 .. %d)", who, rounds, ABS_POLISH_MAX_ROUNDS);
+    PATS_REQUIRE(steps >= 1 && steps <= ABS_POLISH_MAX_STEPS, "%s: steps = %d (1 .. %d)", who, steps, ABS_POLISH_MAX_STEPS);
+    PATS_REQUIRE(best || M == 1, "%s: null best needs M == 1, got M = %lld", who, (long long)M);
+    const int64_t longest = counts_in ? stride : cap;   // the staging comes from the sizes alone: no host read of the counts
+    const int stage_n = (int)(longest < ABS_STAGE ? (longest < 1 ? 1 : longest) : ABS_STAGE);
+    if (!abs_polish_lds_ready()) {
+        set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, ABS_LDS);
+        return PATS_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = as_stream(stream);
+    rc = fill_bytes(inlier, 0, (size_t)cap, st);
+    if (rc != PATS_OK) return rc;
+    hipLaunchKernelGGL(absolute_polish_kernel, dim3((unsigned)pairs), dim3(ABS_POLISH_THREADS), (size_t)stage_n * 5 * sizeof(float), st, points,
+                       matches_r, use_min_conf ? conf : nullptr, pair_off, counts_in, stride, cap, models, (int)M, thr, norm, use_min_conf,
+                       min_conf, best, rounds, steps, stage_n, model, best_count, inlier, best_round, counts, cost);
+    return check_launch("absolute_polish kernel");
 }

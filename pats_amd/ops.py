@@ -3355,3 +3355,66 @@ def absolute_score_by_pair(points, matches_r, models, thr, pair_off=None, stride
                                                 _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl), _stream()), fn)
     return out
+
+
+def absolute_polish_by_pair(points, matches_r, models, thr, best=None, rounds=4, steps=3, pair_off=None, stride=None, counts=None, conf=None,
+                            min_conf=None, norm=None, out=None, pairs=None):
+    """Local optimisation of each pair's winning absolute pose, ON THE DEVICE, one launch, no host read
+    (pats_absolute_polish_by_pair_f32; include/pats_amd.h, "Per-pair absolute local optimisation", holds the definition): starting from
+    m_0 = models[p, best[p]], `rounds` times "refit the current model on its inliers - `steps` Gauss-Newton steps on the reprojection
+    error in float64, R made orthonormal, the result cast to float32 -, verify the refit (absolute_score_by_pair with that one
+    model)", and the round with the most inliers - among equals the smallest squared error, then the lowest round; round 0 is the
+    input - is returned.  points / matches_r, the segment forms (pair_off, or stride + counts), conf / min_conf, norm and thr exactly
+    as absolute_score_by_pair takes them; models [pairs,M,3,4] float32 and best [pairs] int32 are its input and output (best may be
+    left out with M == 1); 1 <= rounds <= 16, 1 <= steps <= 8.
+    Returns (model [pairs,3,4] float32, best_count [pairs] int64, inlier [cap] uint8, best_round [pairs] int32, counts
+    [pairs, rounds + 1] int32 and cost [pairs, rounds + 1] float64: the support and the inliers' summed squared reprojection error of
+    every round, a walk that stopped early on a repeated model padded with its last values).  Bit-reproducible.  out: the six
+    destinations."""
+    fn = "absolute_polish_by_pair"
+    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (best, "best"), (pair_off, "pair_off"),
+                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"best": torch.int32, "pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("%s: min_conf needs conf" % fn)
+    rounds, steps = int(rounds), int(steps)
+    if not 1 <= rounds <= 16:
+        raise RuntimeError("%s: rounds = %d, must lie in 1 .. 16" % (fn, rounds))
+    if not 1 <= steps <= 8:
+        raise RuntimeError("%s: steps = %d, must lie in 1 .. 8" % (fn, steps))
+    X, mr, cap = _abs_lists(fn, points, matches_r)
+    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
+    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 4):
+        raise RuntimeError("%s: models must be [pairs,M,3,4]" % fn)
+    M = int(models.shape[1])
+    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("%s: models [pairs,M,3,4] and thr [pairs] must hold %d pairs" % (fn, pairs))
+    if not 1 <= M <= epipolar_max_h():
+        raise RuntimeError("%s: M = %d, must lie in 1 .. %d" % (fn, M, epipolar_max_h()))
+    if best is None:
+        if M != 1:
+            raise RuntimeError("%s: best may be left out with M == 1 only, got M = %d" % (fn, M))
+    else:
+        best = _dev(best, "best", torch.int32).reshape(-1)
+        if best.numel() != pairs:
+            raise RuntimeError("%s: best must hold one int32 per pair (%d), got %d" % (fn, pairs, best.numel()))
+    if conf is not None:
+        conf = _dev(conf, "conf").reshape(-1)
+        if conf.numel() != cap:
+            raise RuntimeError("%s: conf must be [cap]" % fn)
+    norm = _bp_norm(fn, norm, pairs)
+    dev = X.device
+    want = [("model", torch.float32, (pairs, 3, 4)), ("best_count", torch.int64, (pairs,)), ("inlier", torch.uint8, (cap,)),
+            ("best_round", torch.int32, (pairs,)), ("counts", torch.int32, (pairs, rounds + 1)), ("cost", torch.float64, (pairs, rounds + 1))]
+    out = _bp_outputs(fn, want, out, dev)
+    inl = out[2]
+    if cap == 0:
+        X = mr = _bp_placeholder(dev)
+        inl = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else X
+    _check(_L().pats_absolute_polish_by_pair_f32(_ptr(X), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), M, _ptr(thr),
+                                                 _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
+                                                 _ptr(best), rounds, steps, _ptr(out[0]), _ptr(out[1]), _ptr(inl), _ptr(out[3]), _ptr(out[4]),
+                                                 _ptr(out[5]), _stream()), fn)
+    return out
