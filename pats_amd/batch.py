@@ -645,18 +645,18 @@ def hypothesize7_by_pair(out, cap, H, seed=0, norm=None, on="topk", progressive=
     return hyp
 
 
-def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, moments, adaptive=None, msac=False):
-    """What the six verify functions share; score = the ops function, key = "verified" / "verified_h".  adaptive: None for the fixed
-    budget, else (confidence, sample_size, models_per_sample, round_models) - `key`_used is stored too.  msac: score is an MSAC
-    entry - `key` keeps the standard tuple, `key`_gain = (gains, best_gain) and `key`_score = "msac" are stored too."""
-    more = {}
+def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, adaptive=None, msac=False, first=None, **more):
+    """What the verify functions share; score = the ops function, key = "verified" / "verified_h" / "verified_abs".  adaptive: None
+    for the fixed budget, else (confidence, sample_size, models_per_sample, round_models) - `key`_used is stored too.  msac: score is
+    an MSAC entry - `key` keeps the standard tuple, `key`_gain = (gains, best_gain) and `key`_score = "msac" are stored too.  first:
+    the result (`lifted`) whose first entry is scored in the place of matches_l.  more: what else score takes (moments=)."""
     if adaptive is not None:
         confidence, sample_size, models_per_sample, round_models = adaptive
         if not 0.0 < float(confidence) < 1.0:         # false for a NaN; before any device work
             raise ValueError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
         if round_models is None:
             round_models = 320 if models_per_sample == 10 else 256
-        more = {"confidence": confidence, "sample_size": sample_size, "models_per_sample": models_per_sample, "round_models": round_models}
+        more.update(confidence=confidence, sample_size=sample_size, models_per_sample=models_per_sample, round_models=round_models)
     _check_on(fn, out, on)
     if min_conf is not None and "match_conf" not in out:
         raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
@@ -665,8 +665,8 @@ def _verify(fn, score, key, out, cap, models, thr, norm, min_conf, on, moments, 
         models, thr = models.index_select(0, idx), thr.index_select(0, idx)
         norm = None if norm is None else norm.index_select(0, idx)
     ml, mr, conf, seg = _lists_on(out, cap, on)
-    res = score(ml, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, moments=moments, **more,
-                **seg)
+    res = score(ml if first is None else out[first][0], mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm,
+                **more, **seg)
     out[key], out[key + "_on"] = (res[:-2] if adaptive is not None or msac else res), on
     out[key + "_models"] = models                     # slot order: the refit's source when no moments were asked for
     out.pop(key + "_gain", None)                      # a count verification after an MSAC one leaves no stale gains
@@ -688,7 +688,7 @@ def verify_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", mo
     that were scored - [M_cap] for "all", [pairs*K] for "topk" - [, moments [pairs,9,9] float64]) to the result and returns it; rows
     in SLOT order for a mixed pack (models / thr / norm are permuted to it on the device; split_verified_by_pair hands the pairs
     back in the caller's order).  The matches, the regrouped lists and a top-K of the same step are not touched."""
-    return _verify("verify_by_pair", ops.epipolar_score_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, moments)
+    return _verify("verify_by_pair", ops.epipolar_score_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, moments=moments)
 
 
 def verify_msac_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
@@ -698,8 +698,8 @@ def verify_msac_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all
     `verified_gain` = (gains [pairs,H] int64, best_gain [pairs] int64; rows in slot order like `verified`'s) and
     `verified_score` = "msac" are added (a later verify_by_pair on the same result removes the two).  Returns the tuple followed by
     gains, best_gain."""
-    return _verify("verify_msac_by_pair", ops.epipolar_score_msac_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, moments,
-                   msac=True)
+    return _verify("verify_msac_by_pair", ops.epipolar_score_msac_by_pair, "verified", out, cap, models, thr, norm, min_conf, on, msac=True,
+                   moments=moments)
 
 
 def split_verified_by_pair(out, cap):
@@ -878,7 +878,7 @@ def verify_h_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", 
     were scored [, moments [pairs,9,9] float64]) to the result and returns it; rows in SLOT order for a mixed pack, as
     `verified`'s.  `verified_h_on` and `verified_h_models` go with it.  `verified` and `pose` are never touched: a caller runs
     both branches on one result and compares best_count of the two - choosing between the models stays with the caller."""
-    return _verify("verify_h_by_pair", ops.homography_score_by_pair, "verified_h", out, cap, models, thr, norm, min_conf, on, moments)
+    return _verify("verify_h_by_pair", ops.homography_score_by_pair, "verified_h", out, cap, models, thr, norm, min_conf, on, moments=moments)
 
 
 def verify_h_msac_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="all", moments=False):
@@ -886,7 +886,7 @@ def verify_h_msac_by_pair(out, cap, models, thr, norm=None, min_conf=None, on="a
     verify_by_pair: `verified_h` keeps the standard tuple for the MSAC winner - homography_by_pair, polish_h_by_pair and
     pose_h_by_pair work on it unchanged -, `verified_h_gain` = (gains, best_gain) and `verified_h_score` = "msac" are added."""
     return _verify("verify_h_msac_by_pair", ops.homography_score_msac_by_pair, "verified_h", out, cap, models, thr, norm, min_conf, on,
-                   moments, msac=True)
+                   msac=True, moments=moments)
 
 
 def homography_by_pair(out, cap, norm=None, swapped=False, pixel=False):
@@ -1029,11 +1029,13 @@ def pose_branch(out, branch):
     return view
 
 
-def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf, store=None):
-    """What polish_by_pair, polish_h_by_pair and polish_f_by_pair share; polish = the ops function, key = "verified" / "verified_h",
-    store = the name the walk is stored under (default: "polished" / "polished_h")."""
+def _polish(fn, polish, key, verify, store, out, cap, thr, rounds, norm, min_conf, moments=True, first=None, **more):
+    """What the polish functions share; polish = the ops function, key = "verified" / "verified_h" / "verified_abs", verify = the
+    function that makes it, store = the name the walk is stored under.  moments: polish returns them behind the mask (they join the
+    new `key`).  first: the result (`lifted`) whose first entry is walked in the place of matches_l.  more: what else polish takes
+    (steps=, with a cost behind counts)."""
     if key not in out:
-        raise ValueError("%s: run %s first" % (fn, "verify_by_pair" if key == "verified" else "verify_h_by_pair"))
+        raise ValueError("%s: run %s first" % (fn, verify))
     if min_conf is not None and "match_conf" not in out:
         raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
     on, best = out[key + "_on"], out[key][1]
@@ -1042,11 +1044,12 @@ def _polish(fn, polish, key, out, cap, thr, rounds, norm, min_conf, store=None):
         thr = thr.index_select(0, idx)
         norm = None if norm is None else norm.index_select(0, idx)
     ml, mr, conf, seg = _lists_on(out, cap, on)
-    model, best_count, inl, moments, best_round, counts = polish(
-        ml, mr, out[key + "_models"], thr, best=best, rounds=rounds, conf=conf if min_conf is not None else None, min_conf=min_conf,
-        norm=norm, **seg)
-    out[store or ("polished" if key == "verified" else "polished_h")] = (model, best_round, counts)
-    out[key] = (best_count.to(torch.int32)[:, None], torch.zeros_like(best), best_count, inl, moments)
+    res = polish(ml if first is None else out[first][0], mr, out[key + "_models"], thr, best=best, rounds=rounds,
+                 conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, **more, **seg)
+    model, best_count, inl = res[:3]
+    kept = res[3:4] if moments else ()                # the moments stay with the new `key`; behind them best_round, counts[, cost]
+    out[store] = (model,) + res[3 + len(kept):]
+    out[key] = (best_count.to(torch.int32)[:, None], torch.zeros_like(best), best_count, inl) + kept
     out[key + "_models"] = model[:, None]
     return out[key]
 
@@ -1061,20 +1064,22 @@ def polish_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
     `verified` by the standard tuple of the polished model - (counts [pairs,1] int32, best = 0, best_count, inlier, moments) - and
     `verified_models` by model[:, None], all in SLOT order like the verification's: pose_by_pair and split_verified_by_pair work on
     the polished result unchanged and hand the pairs back in the caller's order.  Returns the new `verified`."""
-    return _polish("polish_by_pair", ops.epipolar_polish_by_pair, "verified", out, cap, thr, rounds, norm, min_conf)
+    return _polish("polish_by_pair", ops.epipolar_polish_by_pair, "verified", "verify_by_pair", "polished", out, cap, thr, rounds, norm, min_conf)
 
 
 def polish_h_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
     """polish_by_pair for the homography branch, after verify_h_by_pair / verify_h_adaptive_by_pair (ops.homography_polish_by_pair):
     stores `polished_h` and replaces `verified_h` and `verified_h_models` - homography_by_pair works on the result unchanged."""
-    return _polish("polish_h_by_pair", ops.homography_polish_by_pair, "verified_h", out, cap, thr, rounds, norm, min_conf)
+    return _polish("polish_h_by_pair", ops.homography_polish_by_pair, "verified_h", "verify_h_by_pair", "polished_h", out, cap, thr, rounds, norm,
+                   min_conf)
 
 
 def polish_f_by_pair(out, cap, thr, rounds=4, norm=None, min_conf=None):
     """polish_by_pair for uncalibrated callers, after verify_by_pair / verify_adaptive_by_pair (ops.fundamental_polish_by_pair): the
     refit of every round is fundamental_by_pair's rank-2 F instead of the pose's essential matrix.  Stores `polished_f` and replaces
     `verified` and `verified_models` as polish_by_pair does - fundamental_by_pair works on the result unchanged."""
-    return _polish("polish_f_by_pair", ops.fundamental_polish_by_pair, "verified", out, cap, thr, rounds, norm, min_conf, store="polished_f")
+    return _polish("polish_f_by_pair", ops.fundamental_polish_by_pair, "verified", "verify_by_pair", "polished_f", out, cap, thr, rounds, norm,
+                   min_conf)
 
 
 def fundamental_by_pair(out, cap, norm=None, swapped=False, pixel=False):
@@ -1114,7 +1119,7 @@ def verify_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, mode
     work on it unchanged; counts are 0 from used[p] on.  Also stores `verified_used` = (used [pairs] int32, participating [pairs]
     int32) and returns the tuple followed by those two, in SLOT order like counts.  A confidence outside (0, 1) raises ValueError."""
     return _verify("verify_adaptive_by_pair", ops.epipolar_score_adaptive_by_pair, "verified", out, cap, models, thr, norm, min_conf, on,
-                   moments, adaptive=(confidence, sample_size, models_per_sample, round_models))
+                   adaptive=(confidence, sample_size, models_per_sample, round_models), moments=moments)
 
 
 def verify_h_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, models_per_sample=1, round_models=None, norm=None,
@@ -1123,7 +1128,7 @@ def verify_h_adaptive_by_pair(out, cap, models, thr, confidence, sample_size, mo
     for hypothesize_h_by_pair's models.  Stores `verified_h` (with `verified_h_on`, `verified_h_models`: homography_by_pair works
     on it unchanged) and `verified_h_used` = (used, participating); returns the tuple followed by those two."""
     return _verify("verify_h_adaptive_by_pair", ops.homography_score_adaptive_by_pair, "verified_h", out, cap, models, thr, norm, min_conf,
-                   on, moments, adaptive=(confidence, sample_size, models_per_sample, round_models))
+                   on, adaptive=(confidence, sample_size, models_per_sample, round_models), moments=moments)
 
 
 # ---- the absolute-pose branch: lift through depth, P3P, reprojection verification, the metric pose ----
@@ -1200,17 +1205,8 @@ def verify_abs_by_pair(out, cap, models, thr, norm=None, min_conf=None):
     lists) - rows in SLOT order for a mixed pack, like `verified` -, `verified_abs_on` and `verified_abs_models`, and returns the
     tuple.  `verified`, `verified_h` and `pose` are never touched."""
     fn = "verify_abs_by_pair"
-    points, _, _, on = _need_lifted(fn, out)
-    if min_conf is not None and "match_conf" not in out:
-        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
-    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
-        idx = _caller_of_dev(out, models.device)
-        models, thr = models.index_select(0, idx), thr.index_select(0, idx)
-        norm = None if norm is None else norm.index_select(0, idx)
-    _, mr, conf, seg = _lists_on(out, cap, on)
-    res = ops.absolute_score_by_pair(points, mr, models, thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm, **seg)
-    out["verified_abs"], out["verified_abs_on"], out["verified_abs_models"] = res, on, models
-    return res
+    on = _need_lifted(fn, out)[3]
+    return _verify(fn, ops.absolute_score_by_pair, "verified_abs", out, cap, models, thr, norm, min_conf, on, first="lifted")
 
 
 def polish_abs_by_pair(out, cap, thr, rounds=4, steps=3, norm=None, min_conf=None):
@@ -1225,25 +1221,8 @@ def polish_abs_by_pair(out, cap, thr, rounds=4, steps=3, norm=None, min_conf=Non
     best = 0, best_count, inlier) - and `verified_abs_models` by model[:, None], all in SLOT order like the verification's:
     pose_abs_by_pair and pose_branch(out, "absolute") work on the polished result unchanged and hand the pairs back in the caller's
     order.  `verified`, `verified_h`, `pose` and `lifted` are never touched.  Returns the new `verified_abs`."""
-    fn = "polish_abs_by_pair"
-    if "verified_abs" not in out:
-        raise ValueError("%s: run verify_abs_by_pair first" % fn)
-    if min_conf is not None and "match_conf" not in out:
-        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
-    points = out["lifted"][0]
-    on, best = out["verified_abs_on"], out["verified_abs"][1]
-    if "caller_of" in out:                            # mixed pack: slot s holds the caller's pair caller_of[s]
-        idx = _caller_of_dev(out, thr.device)
-        thr = thr.index_select(0, idx)
-        norm = None if norm is None else norm.index_select(0, idx)
-    _, mr, conf, seg = _lists_on(out, cap, on)
-    model, best_count, inl, best_round, counts, cost = ops.absolute_polish_by_pair(
-        points, mr, out["verified_abs_models"], thr, best=best, rounds=rounds, steps=steps, conf=conf if min_conf is not None else None,
-        min_conf=min_conf, norm=norm, **seg)
-    out["polished_abs"] = (model, best_round, counts, cost)
-    out["verified_abs"] = (best_count.to(torch.int32)[:, None], torch.zeros_like(best), best_count, inl)
-    out["verified_abs_models"] = model[:, None]
-    return out["verified_abs"]
+    return _polish("polish_abs_by_pair", ops.absolute_polish_by_pair, "verified_abs", "verify_abs_by_pair", "polished_abs", out, cap, thr, rounds,
+                   norm, min_conf, moments=False, first="lifted", steps=steps)
 
 
 def pose_abs_by_pair(out, cap, swapped=False):

@@ -17,7 +17,8 @@
 //               register goes to LDS, at the end the waves are added and counts[p, h] is STORED (a workgroup owns its models: no
 //               atomics, nothing to zero, the same bits every run).  A segment longer than ABS_STAGE is read through abs_load from
 //               global memory every pass instead: the same values
-//   argmax      absolute_argmax_kernel: the verification's rule - the largest count, the lowest index that holds it (0 for no inlier)
+//   argmax      verify_argmax_kernel (verify.hpp), the verification's own: the largest count, the lowest index that holds it (0 for no
+//               inlier)
 //   mask        absolute_mask_kernel: the winner's verdict for every match with abs_test2, so the mask's sum is best_count exactly
 //   polish      absolute_polish_kernel ("Per-pair absolute local optimisation"; docs/kernels.md 4.22): one workgroup of
 //               ABS_POLISH_THREADS per pair walks ALL rounds "refit the winner on its inliers, verify the refit" in one launch.  The
@@ -31,12 +32,9 @@
 #include "common.hpp"
 #include "epipolar.hpp"
 #include "p3p.hpp"
+#include "verify.hpp"
 
 namespace pats {
-
-typedef float abs_v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ abs_v2f abs_fma(abs_v2f a, abs_v2f b, abs_v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ abs_v2f abs_splat(float v) { return abs_v2f{v, v}; }
 
 // ---- lift ------------------------------------------------------------------------------------------------------------------------
 constexpr int ABS_LIFT_THREADS = 256;
@@ -210,20 +208,34 @@ __device__ __forceinline__ void abs_load(const float* __restrict__ X_, const flo
     if (ok) { X0 = a0; X1 = a1; X2 = a2; r0 = b.x; r1 = b.y; }
 }
 
-// THE arithmetic of the test, two matches against one model m = [R | t] row-major: Y_k = fma(m[4k], X0, fma(m[4k+1], X1,
-// fma(m[4k+2], X2, m[4k+3]))), d_k = fma(-r_k, Y2, Y_k), s = fma(d0, d0, d1 d1), lim = t2 (Y2 Y2); inlier iff Y2 > 0 and s <= lim
-__device__ __forceinline__ void abs_test2(const float (&m)[12], float t2, abs_v2f X0, abs_v2f X1, abs_v2f X2, abs_v2f r0, abs_v2f r1, abs_v2f& s,
-                                          abs_v2f& lim, abs_v2f& y2) {
-    const abs_v2f y0 = abs_fma(abs_splat(m[0]), X0, abs_fma(abs_splat(m[1]), X1, abs_fma(abs_splat(m[2]), X2, abs_splat(m[3]))));
-    const abs_v2f y1 = abs_fma(abs_splat(m[4]), X0, abs_fma(abs_splat(m[5]), X1, abs_fma(abs_splat(m[6]), X2, abs_splat(m[7]))));
-    y2 = abs_fma(abs_splat(m[8]), X0, abs_fma(abs_splat(m[9]), X1, abs_fma(abs_splat(m[10]), X2, abs_splat(m[11]))));
-    const abs_v2f d0 = abs_fma(-r0, y2, y0);
-    const abs_v2f d1 = abs_fma(-r1, y2, y1);
-    s = abs_fma(d0, d0, d1 * d1);
-    lim = abs_splat(t2) * (y2 * y2);
+// The workgroup of `threads` stages matches 0 .. count - 1 of the segment through abs_load into the five planes of stage_n slots each:
+// count = n, or - the score kernel's two-match trips - n rounded up to even, whose last slot then holds the NaN X0 of a match that
+// takes no part.  count <= stage_n; the caller's barrier follows
+__device__ __forceinline__ void abs_stage_segment(float* __restrict__ stage, int stage_n, uint32_t count, int tid, int threads,
+                                                  const float* __restrict__ X_, const float2* __restrict__ mr, const float* __restrict__ conf,
+                                                  uint32_t n, bool has_norm, const EpiNorm& nm, bool gate, float min_conf) {
+    for (uint32_t i = tid; i < count; i += threads) {
+        float a[5];
+        abs_load(X_, mr, conf, i, n, has_norm, nm, gate, min_conf, a[0], a[1], a[2], a[3], a[4]);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) stage[k * stage_n + i] = a[k];
+    }
 }
 
-__device__ __forceinline__ int abs_count2(abs_v2f s, abs_v2f lim, abs_v2f y2) {
+// THE arithmetic of the test, two matches against one model m = [R | t] row-major: Y_k = fma(m[4k], X0, fma(m[4k+1], X1,
+// fma(m[4k+2], X2, m[4k+3]))), d_k = fma(-r_k, Y2, Y_k), s = fma(d0, d0, d1 d1), lim = t2 (Y2 Y2); inlier iff Y2 > 0 and s <= lim
+__device__ __forceinline__ void abs_test2(const float (&m)[12], float t2, v2f X0, v2f X1, v2f X2, v2f r0, v2f r1, v2f& s,
+                                          v2f& lim, v2f& y2) {
+    const v2f y0 = pk_fma(pk_splat(m[0]), X0, pk_fma(pk_splat(m[1]), X1, pk_fma(pk_splat(m[2]), X2, pk_splat(m[3]))));
+    const v2f y1 = pk_fma(pk_splat(m[4]), X0, pk_fma(pk_splat(m[5]), X1, pk_fma(pk_splat(m[6]), X2, pk_splat(m[7]))));
+    y2 = pk_fma(pk_splat(m[8]), X0, pk_fma(pk_splat(m[9]), X1, pk_fma(pk_splat(m[10]), X2, pk_splat(m[11]))));
+    const v2f d0 = pk_fma(-r0, y2, y0);
+    const v2f d1 = pk_fma(-r1, y2, y1);
+    s = pk_fma(d0, d0, d1 * d1);
+    lim = pk_splat(t2) * (y2 * y2);
+}
+
+__device__ __forceinline__ int abs_count2(v2f s, v2f lim, v2f y2) {
     return __builtin_popcountll(__builtin_amdgcn_ballot_w64(y2.x > 0.0f) & __builtin_amdgcn_ballot_w64(s.x <= lim.x)) +
            __builtin_popcountll(__builtin_amdgcn_ballot_w64(y2.y > 0.0f) & __builtin_amdgcn_ballot_w64(s.y <= lim.y));
 }
@@ -236,17 +248,17 @@ __device__ __forceinline__ void abs_model(const float* __restrict__ m, float (&e
 // matches 2 q and 2 q + 1 of the segment (q = a trip's pair index) from the staged planes or through abs_load
 __device__ __forceinline__ void abs_fetch2(bool staged, const float* __restrict__ stage, int stage_n, const float* __restrict__ X_,
                                            const float2* __restrict__ mr, const float* __restrict__ conf, uint32_t q, uint32_t n, bool has_norm,
-                                           const EpiNorm& nm, bool gate, float min_conf, abs_v2f& X0, abs_v2f& X1, abs_v2f& X2, abs_v2f& r0,
-                                           abs_v2f& r1) {
+                                           const EpiNorm& nm, bool gate, float min_conf, v2f& X0, v2f& X1, v2f& X2, v2f& r0,
+                                           v2f& r1) {
     if (staged) {                                       // stage_n is even and the planes are padded with NaN X0 up to it: 2 q + 1 < stage_n
-        const abs_v2f* s2 = reinterpret_cast<const abs_v2f*>(stage);
+        const v2f* s2 = reinterpret_cast<const v2f*>(stage);
         const int half = stage_n / 2;
         X0 = s2[q]; X1 = s2[half + q]; X2 = s2[2 * half + q]; r0 = s2[3 * half + q]; r1 = s2[4 * half + q];
     } else {
         float a[5], c[5];
         abs_load(X_, mr, conf, 2 * q, n, has_norm, nm, gate, min_conf, a[0], a[1], a[2], a[3], a[4]);
         abs_load(X_, mr, conf, 2 * q + 1, n, has_norm, nm, gate, min_conf, c[0], c[1], c[2], c[3], c[4]);
-        X0 = abs_v2f{a[0], c[0]}; X1 = abs_v2f{a[1], c[1]}; X2 = abs_v2f{a[2], c[2]}; r0 = abs_v2f{a[3], c[3]}; r1 = abs_v2f{a[4], c[4]};
+        X0 = v2f{a[0], c[0]}; X1 = v2f{a[1], c[1]}; X2 = v2f{a[2], c[2]}; r0 = v2f{a[3], c[3]}; r1 = v2f{a[4], c[4]};
     }
 }
 
@@ -281,14 +293,7 @@ absolute_score_kernel(const float* __restrict__ points, const float* __restrict_
     const bool staged = n <= (uint32_t)stage_n;         // workgroup-uniform
     const uint32_t n2 = (n + 1) / 2;                    // pairs of matches
 
-    if (staged) {                                       // rows n .. 2 n2 - 1 (at most one) get the NaN X0 of a match that takes no part
-        for (uint32_t i = tid; i < 2 * n2; i += ABS_THREADS) {
-            float a[5];
-            abs_load(X_, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, a[0], a[1], a[2], a[3], a[4]);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) abs_stage[k * stage_n + i] = a[k];
-        }
-    }
+    if (staged) abs_stage_segment(abs_stage, stage_n, 2 * n2, tid, ABS_THREADS, X_, mr, conf, n, norm != nullptr, nm, gate != 0, min_conf);
     wg_barrier();
 
     const float* m = models + ((int64_t)p * M + h_lo) * 12;
@@ -303,9 +308,9 @@ absolute_score_kernel(const float* __restrict__ points, const float* __restrict_
             int ca = 0, cb = 0;
             for (uint32_t q0 = 0; q0 < n2; q0 += ABS_THREADS) {
                 const uint32_t q = q0 + tid;
-                abs_v2f X0 = abs_splat(__builtin_nanf("")), X1 = abs_splat(0.0f), X2 = X1, r0 = X1, r1 = X1;
+                v2f X0 = pk_splat(__builtin_nanf("")), X1 = pk_splat(0.0f), X2 = X1, r0 = X1, r1 = X1;
                 if (q < n2) abs_fetch2(staged, abs_stage, stage_n, X_, mr, conf, q, n, norm != nullptr, nm, gate != 0, min_conf, X0, X1, X2, r0, r1);
-                abs_v2f s, lim, y2;
+                v2f s, lim, y2;
                 abs_test2(ea, t2, X0, X1, X2, r0, r1, s, lim, y2);
                 ca += abs_count2(s, lim, y2);
                 abs_test2(eb, t2, X0, X1, X2, r0, r1, s, lim, y2);
@@ -322,30 +327,6 @@ absolute_score_kernel(const float* __restrict__ points, const float* __restrict_
         for (int w = 0; w < ABS_WAVES; ++w) s += wave_cnt[w][tid];
         out[tid] = s;
     }
-}
-
-// one workgroup per pair: the largest count of counts[p, :], the lowest index that holds it
-__global__ void __launch_bounds__(256) absolute_argmax_kernel(const int32_t* __restrict__ counts, int M, int32_t* __restrict__ best,
-                                                               int64_t* __restrict__ best_count) {
-    __shared__ int sv[256], si[256];
-    const int64_t p = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int32_t* c = counts + p * M;
-    int v = -1, idx = 0x7fffffff;
-    for (int h = tid; h < M; h += 256) {                // ascending h: a later equal count does not replace an earlier one
-        const int x = c[h];
-        if (x > v) { v = x; idx = h; }
-    }
-    sv[tid] = v; si[tid] = idx;
-    wg_barrier();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            const int ov = sv[tid + s], oi = si[tid + s];
-            if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
-        }
-        wg_barrier();
-    }
-    if (tid == 0) { best[p] = si[0]; best_count[p] = (int64_t)sv[0]; }
 }
 
 // one workgroup per pair: the winner's inlier mask (zeroed before the launch)
@@ -373,8 +354,8 @@ absolute_mask_kernel(const float* __restrict__ points, const float* __restrict__
     for (uint32_t i = tid; i < n; i += ABS_MASK_THREADS) {
         float a[5];
         abs_load(X_, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, a[0], a[1], a[2], a[3], a[4]);
-        abs_v2f s, lim, y2;
-        abs_test2(e, t2, abs_splat(a[0]), abs_splat(a[1]), abs_splat(a[2]), abs_splat(a[3]), abs_splat(a[4]), s, lim, y2);
+        v2f s, lim, y2;
+        abs_test2(e, t2, pk_splat(a[0]), pk_splat(a[1]), pk_splat(a[2]), pk_splat(a[3]), pk_splat(a[4]), s, lim, y2);
         inlier[lo + i] = y2.x > 0.0f && s.x <= lim.x ? 1 : 0;
     }
 }
@@ -540,14 +521,7 @@ absolute_polish_kernel(const float* __restrict__ points, const float* __restrict
     const bool staged = n <= (uint32_t)stage_n;         // workgroup-uniform
 
     // ---- stage, and round 0's model -----------------------------------------------------------------------------------------
-    if (staged) {
-        for (uint32_t i = tid; i < n; i += ABS_POLISH_THREADS) {        // at most ABS_STAGE / ABS_POLISH_THREADS trips
-            float a[5];
-            abs_load(X_, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, a[0], a[1], a[2], a[3], a[4]);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) abs_polish_stage[k * stage_n + i] = a[k];
-        }
-    }
+    if (staged) abs_stage_segment(abs_polish_stage, stage_n, n, tid, ABS_POLISH_THREADS, X_, mr, conf, n, norm != nullptr, nm, gate != 0, min_conf);
     if (tid < 12) {
         int h = best ? best[p] : 0;                     // a null best: M == 1
         h = h < 0 ? 0 : (h >= M ? M - 1 : h);
@@ -579,8 +553,8 @@ absolute_polish_kernel(const float* __restrict__ points, const float* __restrict
                 for (uint32_t i0 = 0; i0 < n; i0 += ABS_POLISH_THREADS) {
                     float a[5];
                     abs_fetch1(staged, abs_polish_stage, stage_n, X_, mr, conf, i0 + tid, n, norm != nullptr, nm, gate != 0, min_conf, a);
-                    abs_v2f s, lim, y2;
-                    abs_test2(e, t2, abs_splat(a[0]), abs_splat(a[1]), abs_splat(a[2]), abs_splat(a[3]), abs_splat(a[4]), s, lim, y2);
+                    v2f s, lim, y2;
+                    abs_test2(e, t2, pk_splat(a[0]), pk_splat(a[1]), pk_splat(a[2]), pk_splat(a[3]), pk_splat(a[4]), s, lim, y2);
                     const bool in = y2.x > 0.0f && s.x <= lim.x;
                     wcnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(in));
                     if (in) abs_polish_accumulate(m, a, acc);
@@ -667,30 +641,18 @@ absolute_polish_kernel(const float* __restrict__ points, const float* __restrict
         const uint32_t i = i0 + tid;
         float a[5];
         abs_fetch1(staged, abs_polish_stage, stage_n, X_, mr, conf, i, n, norm != nullptr, nm, gate != 0, min_conf, a);
-        abs_v2f s, lim, y2;
-        abs_test2(e, t2, abs_splat(a[0]), abs_splat(a[1]), abs_splat(a[2]), abs_splat(a[3]), abs_splat(a[4]), s, lim, y2);
+        v2f s, lim, y2;
+        abs_test2(e, t2, pk_splat(a[0]), pk_splat(a[1]), pk_splat(a[2]), pk_splat(a[3]), pk_splat(a[4]), s, lim, y2);
         if (i < n) inlier[lo + i] = y2.x > 0.0f && s.x <= lim.x ? 1 : 0;
     }
 }
 
-// the staging can exceed the 64 KiB a launch gets unasked: raised once per device and kernel
-static bool abs_lds_raise(const void* kernel, int (&state)[64]) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ABS_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1;
-}
-static bool abs_lds_ready() {
-    static int state[64] = {0};
-    return abs_lds_raise((const void*)absolute_score_kernel, state);
-}
-static bool abs_polish_lds_ready() {
-    static int state[64] = {0};
-    return abs_lds_raise((const void*)absolute_polish_kernel, state);
+// stage_n, the slots per plane of dynamic LDS a launch allocates: the longest possible segment - from the sizes alone: no host read of
+// the counts - rounded up to `granule` (2 for the score kernel's two-match trips), at least one granule and at most ABS_STAGE
+static int abs_stage_slots(const int64_t* counts_in, int64_t stride, int64_t cap, int granule) {
+    const int64_t longest = counts_in ? stride : cap;
+    const int64_t slots = (longest + granule - 1) / granule * granule;
+    return (int)(slots < ABS_STAGE ? (slots < granule ? granule : slots) : ABS_STAGE);
 }
 
 }  // namespace pats
@@ -728,26 +690,10 @@ extern "C" int pats_absolute_hypotheses_by_pair_f32(const float* points, const f
                                                     const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H,
                                                     const int64_t* pair_seed, const float* norm, int progressive, float* models,
                                                     int32_t* sample_idx, int32_t* n_models, pats_stream_t stream) {
-    const char* who = "absolute_hypotheses_by_pair";
-    EPI_REQUIRE_PTR(points, 4);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(pair_seed, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_ALIGNED(norm, 4);                       // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(sample_idx, 4);
-    EPI_REQUIRE_ALIGNED(n_models, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int64_t chunks;
+    const int rc = epi_check_hypotheses("absolute_hypotheses_by_pair", {"points", points, 4}, matches_r, pair_off, stride, counts_in, pairs, cap, H,
+                                        pair_seed, norm, progressive, models, sample_idx, n_models, ABS_SLOTS, ABS_HYP_THREADS, chunks);
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, H);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(H <= pats_epipolar_max_h() / ABS_SLOTS, "%s: H = %lld gives %d H = %lld models (<= max_h = %lld)", who, (long long)H,
-                 ABS_SLOTS, (long long)(H * ABS_SLOTS), (long long)pats_epipolar_max_h());
-    PATS_REQUIRE(progressive == 0 || progressive == 1, "%s: progressive = %d must be 0 or 1", who, progressive);
-    const int64_t chunks = ceil_div(H, ABS_HYP_THREADS);
-    PATS_REQUIRE(chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld workgroups (< 2^31)", who, (long long)pairs,
-                 (long long)pairs, (long long)chunks);
     hipLaunchKernelGGL(absolute_hypotheses_kernel, dim3((unsigned)(pairs * chunks)), dim3(ABS_HYP_THREADS), 0, as_stream(stream), points,
                        matches_r, pair_off, counts_in, stride, cap, (int)chunks, (int)H, pair_seed, norm, progressive, models, sample_idx,
                        n_models);
@@ -759,31 +705,15 @@ extern "C" int pats_absolute_score_by_pair_f32(const float* points, const float*
                                                int64_t M, const float* thr, const float* norm, int use_min_conf, float min_conf,
                                                int32_t* counts, int32_t* best, int64_t* best_count, uint8_t* inlier, pats_stream_t stream) {
     const char* who = "absolute_score_by_pair";
-    EPI_REQUIRE_PTR(points, 4);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_PTR(thr, 4);
-    EPI_REQUIRE_PTR(counts, 4);
-    EPI_REQUIRE_PTR(best, 4);
-    EPI_REQUIRE_PTR(best_count, 8);
-    PATS_REQUIRE(inlier, "%s: null inlier", who);
-    EPI_REQUIRE_ALIGNED(conf, 4);                       // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(norm, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int rc = epi_check_scored(who, {"points", points, 4}, matches_r, models, thr,
+                              {{"counts", counts, 4}, {"best", best, 4}, {"best_count", best_count, 8}, {"inlier", inlier, 1}}, conf, norm, pair_off,
+                              stride, counts_in, pairs, cap, M, use_min_conf, min_conf);
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, M);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
-    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
     const int64_t chunks = ceil_div(M, ABS_CHUNK);
     PATS_REQUIRE(chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld workgroups (< 2^31)", who, (long long)pairs,
                  (long long)pairs, (long long)chunks);
-    const int64_t longest = counts_in ? stride : cap;   // the staging comes from the sizes alone: no host read of the counts
-    const int64_t even = (longest + 1) / 2 * 2;
-    const int stage_n = (int)(even < ABS_STAGE ? (even < 2 ? 2 : even) : ABS_STAGE);
-    if (!abs_lds_ready()) {
+    const int stage_n = abs_stage_slots(counts_in, stride, cap, 2);
+    if (!epi_lds_raised<absolute_score_kernel>(ABS_LDS)) {
         set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, ABS_LDS);
         return PATS_ERR_UNSUPPORTED;
     }
@@ -796,7 +726,7 @@ extern "C" int pats_absolute_score_by_pair_f32(const float* points, const float*
                        stage_n, counts);
     rc = check_launch("absolute_score kernel");
     if (rc != PATS_OK) return rc;
-    hipLaunchKernelGGL(absolute_argmax_kernel, dim3((unsigned)pairs), dim3(256), 0, st, counts, (int)M, best, best_count);
+    hipLaunchKernelGGL(verify_argmax_kernel<ARGMAX_THREADS>, dim3((unsigned)pairs), dim3(ARGMAX_THREADS), 0, st, counts, (int)M, best, best_count);
     rc = check_launch("absolute_argmax kernel");
     if (rc != PATS_OK) return rc;
     hipLaunchKernelGGL(absolute_mask_kernel, dim3((unsigned)pairs), dim3(ABS_MASK_THREADS), 0, st, points, matches_r, cf, pair_off, counts_in,
@@ -810,33 +740,16 @@ extern "C" int pats_absolute_polish_by_pair_f32(const float* points, const float
                                                 const int32_t* best, int rounds, int steps, float* model, int64_t* best_count,
                                                 uint8_t* inlier, int32_t* best_round, int32_t* counts, double* cost, pats_stream_t stream) {
     const char* who = "absolute_polish_by_pair";
-    EPI_REQUIRE_PTR(points, 4);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_PTR(thr, 4);
-    EPI_REQUIRE_PTR(model, 4);
-    EPI_REQUIRE_PTR(best_count, 8);
-    PATS_REQUIRE(inlier, "%s: null inlier", who);
-    EPI_REQUIRE_PTR(best_round, 4);
-    EPI_REQUIRE_PTR(counts, 4);
-    EPI_REQUIRE_PTR(cost, 8);
-    EPI_REQUIRE_ALIGNED(conf, 4);                       // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(norm, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    EPI_REQUIRE_ALIGNED(best, 4);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int rc = epi_check_scored(who, {"points", points, 4}, matches_r, models, thr,
+                              {{"model", model, 4}, {"best_count", best_count, 8}, {"inlier", inlier, 1}, {"best_round", best_round, 4},
+                               {"counts", counts, 4}, {"cost", cost, 8}},
+                              conf, norm, pair_off, stride, counts_in, pairs, cap, M, use_min_conf, min_conf, {"best", best, 4});
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, M);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
-    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
     PATS_REQUIRE(rounds >= 1 && rounds <= ABS_POLISH_MAX_ROUNDS, "%s: rounds = %d (1 .. %d)", who, rounds, ABS_POLISH_MAX_ROUNDS);
     PATS_REQUIRE(steps >= 1 && steps <= ABS_POLISH_MAX_STEPS, "%s: steps = %d (1 .. %d)", who, steps, ABS_POLISH_MAX_STEPS);
     PATS_REQUIRE(best || M == 1, "%s: null best needs M == 1, got M = %lld", who, (long long)M);
-    const int64_t longest = counts_in ? stride : cap;   // the staging comes from the sizes alone: no host read of the counts
-    const int stage_n = (int)(longest < ABS_STAGE ? (longest < 1 ? 1 : longest) : ABS_STAGE);
-    if (!abs_polish_lds_ready()) {
+    const int stage_n = abs_stage_slots(counts_in, stride, cap, 1);
+    if (!epi_lds_raised<absolute_polish_kernel>(ABS_LDS)) {
         set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, ABS_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

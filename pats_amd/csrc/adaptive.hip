@@ -105,37 +105,17 @@ adaptive_update_kernel(const float* __restrict__ ml_, const float* __restrict__ 
 
 using namespace pats;
 
-#define ADP_REQUIRE_ALIGNED(ptr, align) PATS_REQUIRE((uintptr_t)(c.ptr) % (align) == 0, "%s: " #ptr " must be " #align "-byte aligned", who)
-#define ADP_REQUIRE_PTR(ptr, align)                    \
-    PATS_REQUIRE(c.ptr, "%s: null " #ptr, who);        \
-    ADP_REQUIRE_ALIGNED(ptr, align)
-
 size_t pats::adaptive_workspace_bytes(int64_t pairs) {
     return pairs > 0 ? (size_t)pairs * sizeof(int32_t) : 0;     // the stopped flag of every pair
 }
 
 int pats::adaptive_score_by_pair(const char* who, const AdaptiveCall& c, AdaptiveScoreRound score_round, AdaptiveMask mask) {
-    ADP_REQUIRE_PTR(matches_l, 8);
-    ADP_REQUIRE_PTR(matches_r, 8);
-    ADP_REQUIRE_PTR(models, 4);
-    ADP_REQUIRE_PTR(thr, 4);
-    ADP_REQUIRE_PTR(counts, 4);
-    ADP_REQUIRE_PTR(best, 4);
-    ADP_REQUIRE_PTR(best_count, 8);
-    PATS_REQUIRE(c.inlier, "%s: null inlier", who);
-    ADP_REQUIRE_PTR(used, 4);
-    ADP_REQUIRE_PTR(participating, 4);
-    ADP_REQUIRE_ALIGNED(conf, 4);                       // optional pointers: null is aligned
-    ADP_REQUIRE_ALIGNED(norm, 4);
-    ADP_REQUIRE_ALIGNED(pair_off, 8);
-    ADP_REQUIRE_ALIGNED(counts_in, 8);
-    ADP_REQUIRE_ALIGNED(moments, 8);
-    int rc = epi_check_segments(who, c.pair_off, c.counts_in, c.stride, c.pairs, c.cap);
+    int rc = epi_check_scored(who, {"matches_l", c.matches_l, 8}, c.matches_r, c.models, c.thr,
+                              {{"counts", c.counts, 4}, {"best", c.best, 4}, {"best_count", c.best_count, 8}, {"inlier", c.inlier, 1},
+                               {"used", c.used, 4}, {"participating", c.participating, 4}},
+                              c.conf, c.norm, c.pair_off, c.stride, c.counts_in, c.pairs, c.cap, c.H, c.use_min_conf, c.min_conf,
+                              {"moments", c.moments, 8});
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, c.H);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(!c.use_min_conf || c.conf, "%s: min_conf needs conf", who);
-    PATS_REQUIRE(!c.use_min_conf || c.min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)c.min_conf);
     PATS_REQUIRE(c.confidence > 0.0 && c.confidence < 1.0, "%s: confidence = %g must lie strictly between 0 and 1", who, c.confidence);
     PATS_REQUIRE(c.sample_size >= 1 && c.sample_size <= ADP_MAX_SAMPLE, "%s: sample_size = %d (1 .. %d)", who, c.sample_size, ADP_MAX_SAMPLE);
     PATS_REQUIRE(c.models_per_sample >= 1 && c.models_per_sample <= ADP_MAX_SAMPLE, "%s: models_per_sample = %d (1 .. %d)", who,
@@ -147,7 +127,7 @@ int pats::adaptive_score_by_pair(const char* who, const AdaptiveCall& c, Adaptiv
                  (long long)c.round_models, (long long)rounds, (long long)c.H, ADP_MAX_ROUNDS);
     const size_t need = adaptive_workspace_bytes(c.pairs);
     PATS_REQUIRE(c.workspace_bytes >= need, "%s: workspace too small", who);
-    ADP_REQUIRE_PTR(workspace, 4);
+    if ((rc = epi_check_args(who, {{"workspace", c.workspace, 4}}, true)) != PATS_OK) return rc;
     const int64_t longest = c.counts_in ? c.stride : c.cap;    // the grid comes from the sizes alone: no host read of the counts
     const int64_t span = c.round_models < c.H ? c.round_models : c.H;
     const int64_t tiles = ceil_div(longest, ADAPTIVE_TILE), chunks = ceil_div(span, ADAPTIVE_CHUNK);

@@ -23,8 +23,8 @@
 //           into integer gains (verify_gain), the 64-lane integer sum of a model is taken one model behind (its crossbar steps wait
 //           under the next model's arithmetic), lane h % 64 keeps it, and a second LDS array and ONE 64-bit integer atomic per
 //           workgroup and model with a non-zero gain carry it to gains[p, h].  The <T, ROUND, false> kernels hold none of this.
-//   argmax  verify_argmax_kernel, one for both families: one workgroup per pair over counts[p, :], the largest count, the lowest
-//           index that holds it
+//   argmax  verify_argmax_kernel (verify.hpp: the absolute branch launches it too), one for every family: one workgroup per pair over
+//           counts[p, :], the largest count, the lowest index that holds it
 //           verify_argmax_gain_kernel: the same over the int64 gains[p, :]; it reads counts[p, best] for best_count
 //   mask    verify_mask_kernel<T>: one workgroup per pair, the winner's verdict for every match of the segment with the arithmetic of
 //           the score kernel (same device function: the mask and the winner's count agree exactly), the moments in float64 in a fixed
@@ -146,30 +146,6 @@ verify_score_kernel(const float* __restrict__ ml_, const float* __restrict__ mr_
     }
 }
 
-// one workgroup per pair: the largest count of counts[p, :], the lowest index that holds it
-__global__ void __launch_bounds__(256) verify_argmax_kernel(const int32_t* __restrict__ counts, int H, int32_t* __restrict__ best,
-                                                             int64_t* __restrict__ best_count) {
-    __shared__ int sv[256], si[256];
-    const int64_t p = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int32_t* c = counts + p * H;
-    int v = -1, idx = 0x7fffffff;
-    for (int h = tid; h < H; h += 256) {                // ascending h: a later equal count does not replace an earlier one
-        const int x = c[h];
-        if (x > v) { v = x; idx = h; }
-    }
-    sv[tid] = v; si[tid] = idx;
-    wg_barrier();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            const int ov = sv[tid + s], oi = si[tid + s];
-            if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
-        }
-        wg_barrier();
-    }
-    if (tid == 0) { best[p] = si[0]; best_count[p] = (int64_t)sv[0]; }
-}
-
 // the MSAC sibling: the largest gain of gains[p, :], the lowest index that holds it (0 when every gain is 0), and that model's count
 __global__ void __launch_bounds__(256) verify_argmax_gain_kernel(const int64_t* __restrict__ gains, const int32_t* __restrict__ counts, int H,
                                                                   int32_t* __restrict__ best, int64_t* __restrict__ best_gain,
@@ -260,32 +236,16 @@ static int verify_score_by_pair(const char* who, const float* matches_l, const f
                                 const float* thr, const float* norm, int use_min_conf, float min_conf, int32_t* counts, int32_t* best,
                                 int64_t* best_count, uint8_t* inlier, double* moments, pats_stream_t stream, int64_t* gains,
                                 int64_t* best_gain) {
-    EPI_REQUIRE_PTR(matches_l, 8);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_PTR(thr, 4);
-    EPI_REQUIRE_PTR(counts, 4);
-    EPI_REQUIRE_PTR(best, 4);
-    EPI_REQUIRE_PTR(best_count, 8);
-    PATS_REQUIRE(inlier, "%s: null inlier", who);
-    EPI_REQUIRE_ALIGNED(conf, 4);                    // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(norm, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    EPI_REQUIRE_ALIGNED(moments, 8);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int rc = epi_check_scored(who, {"matches_l", matches_l, 8}, matches_r, models, thr,
+                              {{"counts", counts, 4}, {"best", best, 4}, {"best_count", best_count, 8}, {"inlier", inlier, 1}}, conf, norm, pair_off,
+                              stride, counts_in, pairs, cap, H, use_min_conf, min_conf, {"moments", moments, 8});
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, H);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
-    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
     const int64_t longest = counts_in ? stride : cap;   // the grid comes from the sizes alone: no host read of the counts
     const int64_t tiles = ceil_div(longest, EPI_TILE), chunks = ceil_div(H, EPI_CHUNK);
     PATS_REQUIRE(tiles * chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld x %lld workgroups (< 2^31)", who,
                  (long long)pairs, (long long)tiles, (long long)pairs, (long long)chunks);
     if (GAIN) {                                         // behind everything the count entries refuse, in their order
-        EPI_REQUIRE_PTR(gains, 8);
-        EPI_REQUIRE_PTR(best_gain, 8);
+        if ((rc = epi_check_args(who, {{"gains", gains, 8}, {"best_gain", best_gain, 8}}, true)) != PATS_OK) return rc;
     }
     hipStream_t st = as_stream(stream);
     rc = fill_bytes(counts, 0, (size_t)pairs * (size_t)H * sizeof(int32_t), st);
@@ -308,7 +268,8 @@ static int verify_score_by_pair(const char* who, const float* matches_l, const f
         hipLaunchKernelGGL(verify_argmax_gain_kernel, dim3((unsigned)pairs), dim3(256), 0, st, gains, counts, (int)H, best, best_gain,
                            best_count);
     else
-        hipLaunchKernelGGL(verify_argmax_kernel, dim3((unsigned)pairs), dim3(256), 0, st, counts, (int)H, best, best_count);
+        hipLaunchKernelGGL(verify_argmax_kernel<ARGMAX_THREADS>, dim3((unsigned)pairs), dim3(ARGMAX_THREADS), 0, st, counts, (int)H, best,
+                           best_count);
     rc = check_launch(T::ARGMAX);
     if (rc != PATS_OK) return rc;
     hipLaunchKernelGGL(verify_mask_kernel<T>, dim3((unsigned)pairs), dim3(EPI_MASK_THREADS), 0, st, matches_l, matches_r, cf, pair_off,

@@ -1,9 +1,12 @@
 // What the per-pair stages share (epipolar.hip: verification; hypotheses.hip, hypotheses5.hip, hypotheses7.hip: the 8-, 4-, 5- and
 // 7-point hypotheses; pose.hip, pose_h.hip: the poses; homography.hip, fundamental.hip: the refits; polish.hip: the local optimisation):
 // how a pair's segment of the match lists, its normalisation, a match's point and the winning model are read, the hypotheses' sampler
-// with the front end of every minimal-sample kernel, and the host checks of the generators and of the refit source.
+// with the front end of every minimal-sample kernel, and the host side: the checks of the generators, of the verifications and local
+// optimisations and of the refit source, and the raising of a kernel's dynamic LDS limit (absolute.hip is a caller of these too).
 // include/pats_amd.h states all of it.
 #pragma once
+#include <initializer_list>
+
 #include "common.hpp"
 
 namespace pats {
@@ -149,11 +152,26 @@ __device__ __forceinline__ EpiSample epi_sample(const float* __restrict__ ml_, c
 }
 
 // ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name) ------
-// PATS_REQUIRE_PTR / PATS_REQUIRE_ALIGNED for a host function that serves several entry points: `who` is a variable in scope
-#define EPI_REQUIRE_ALIGNED(ptr, align) PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, "%s: " #ptr " must be " #align "-byte aligned", who)
-#define EPI_REQUIRE_PTR(ptr, align)            \
-    PATS_REQUIRE(ptr, "%s: null " #ptr, who);  \
-    EPI_REQUIRE_ALIGNED(ptr, align)
+// PATS_REQUIRE_PTR / PATS_REQUIRE_ALIGNED for a host function that serves several entry points: a pointer comes with the name the
+// message gives it - the first list is matches_l for most entries and points for the absolute ones, the outputs differ from entry to
+// entry - and is non-null and aligned (required), or - an optional one: null is aligned - only aligned.  align = 1: any address (a
+// byte mask)
+struct EpiArg { const char* name; const void* ptr; unsigned align; };
+
+inline int epi_check_arg(const char* who, const EpiArg& a, bool required) {
+    PATS_REQUIRE(a.ptr || !required, "%s: null %s", who, a.name);
+    PATS_REQUIRE((uintptr_t)a.ptr % a.align == 0, "%s: %s must be %u-byte aligned", who, a.name, a.align);
+    return PATS_OK;
+}
+
+// the pointers of `args` in their order, all required or all optional
+inline int epi_check_args(const char* who, std::initializer_list<EpiArg> args, bool required) {
+    for (const EpiArg& a : args) {
+        const int rc = epi_check_arg(who, a, required);
+        if (rc != PATS_OK) return rc;
+    }
+    return PATS_OK;
+}
 
 // exactly one segment form, and sizes the kernels' 32-bit indices and epi_segment's clamps rely on
 inline int epi_check_segments(const char* what, const int64_t* pair_off, const int64_t* counts_in, int64_t stride, int64_t pairs,
@@ -177,22 +195,18 @@ inline int epi_check_h(const char* what, int64_t H) {
     return PATS_OK;
 }
 
-// what the minimal-sample generators check alike (models_per_sample = 1, 10 or 3 slots; n_models is null where the entry has none);
-// chunks = the workgroups of `threads` samples per pair
-inline int epi_check_hypotheses(const char* who, const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+// what the minimal-sample generators check alike (first = the first list, by its name: matches_l, or the absolute branch's points;
+// models_per_sample = 1, 10, 3 or 4 slots; n_models is null where the entry has none); chunks = the workgroups of `threads` samples per pair
+inline int epi_check_hypotheses(const char* who, const EpiArg& first, const float* matches_r, const int64_t* pair_off, int64_t stride,
                                 const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed, const float* norm,
                                 int progressive, const float* models, const int32_t* sample_idx, const int32_t* n_models,
                                 int models_per_sample, int threads, int64_t& chunks) {
-    EPI_REQUIRE_PTR(matches_l, 8);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(pair_seed, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_ALIGNED(norm, 4);                       // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(sample_idx, 4);
-    EPI_REQUIRE_ALIGNED(n_models, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int rc = epi_check_args(who, {first, {"matches_r", matches_r, 8}, {"pair_seed", pair_seed, 8}, {"models", models, 4}}, true);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_args(who, {{"norm", norm, 4}, {"sample_idx", sample_idx, 4}, {"n_models", n_models, 4}, {"pair_off", pair_off, 8},
+                              {"counts_in", counts_in, 8}}, false);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
     if (rc != PATS_OK) return rc;
     rc = epi_check_h(who, H);
     if (rc != PATS_OK) return rc;
@@ -203,6 +217,41 @@ inline int epi_check_hypotheses(const char* who, const float* matches_l, const f
     PATS_REQUIRE(chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld workgroups (< 2^31)", who, (long long)pairs,
                  (long long)pairs, (long long)chunks);
     return PATS_OK;
+}
+
+// What every verification and local optimisation checks alike before it launches, in this order: the required pointers - the first
+// list (by its name), matches_r, models, thr, then the entry's `outputs` in its own order -, the alignment of the optional ones (conf,
+// norm, pair_off, counts_in, then `optional`, the entry's own: moments, or best; null is aligned), the segments, the number of models
+// and the two rules of the confidence gate
+inline int epi_check_scored(const char* who, const EpiArg& first, const float* matches_r, const float* models, const float* thr,
+                            std::initializer_list<EpiArg> outputs, const float* conf, const float* norm, const int64_t* pair_off,
+                            int64_t stride, const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, int use_min_conf, float min_conf,
+                            const EpiArg& optional = {"", nullptr, 1}) {
+    int rc = epi_check_args(who, {first, {"matches_r", matches_r, 8}, {"models", models, 4}, {"thr", thr, 4}}, true);
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_args(who, outputs, true)) != PATS_OK) return rc;
+    rc = epi_check_args(who, {{"conf", conf, 4}, {"norm", norm, 4}, {"pair_off", pair_off, 8}, {"counts_in", counts_in, 8}, optional}, false);
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap)) != PATS_OK) return rc;
+    if ((rc = epi_check_h(who, H)) != PATS_OK) return rc;
+    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
+    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
+    return PATS_OK;
+}
+
+// A launch gets 64 KiB of LDS unasked; a kernel whose staging can exceed them has its limit of dynamic LDS raised to `bytes`, once
+// per device.  One instantiation, and with it one state, per kernel
+template <auto Kernel>
+inline bool epi_lds_raised(int bytes) {
+    static int state[64] = {0};                         // per device: 0 = not tried yet, 1 = raised, -1 = refused
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
+    if (state[dev] == 0) {
+        const bool ok = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        state[dev] = ok ? 1 : -1;
+    }
+    return state[dev] == 1;
 }
 
 // the source of a refit - moments, or models and best - and its frame flag.  With moments the kernels get no models: models is

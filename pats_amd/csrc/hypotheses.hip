@@ -118,7 +118,7 @@ static int hypotheses_by_pair(const char* who, const float* matches_l, const flo
                               const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed, const float* norm,
                               int progressive, float* models, int32_t* sample_idx, pats_stream_t stream) {
     int64_t chunks;
-    const int rc = epi_check_hypotheses(who, matches_l, matches_r, pair_off, stride, counts_in, pairs, cap, H, pair_seed, norm, progressive,
+    const int rc = epi_check_hypotheses(who, {"matches_l", matches_l, 8}, matches_r, pair_off, stride, counts_in, pairs, cap, H, pair_seed, norm, progressive,
                                         models, sample_idx, nullptr, 1, HYP_THREADS, chunks);
     if (rc != PATS_OK) return rc;
     hipLaunchKernelGGL(hypotheses_kernel<F>, dim3((unsigned)(pairs * chunks)), dim3(HYP_THREADS), 0, as_stream(stream), matches_l,

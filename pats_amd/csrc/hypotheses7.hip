@@ -53,8 +53,8 @@ extern "C" int pats_epipolar_hypotheses7_by_pair_f32(const float* matches_l, con
                                                      pats_stream_t stream) {
     (void)workspace;
     int64_t chunks;
-    const int rc = epi_check_hypotheses("epipolar_hypotheses7_by_pair", matches_l, matches_r, pair_off, stride, counts_in, pairs, cap, H, pair_seed, norm,
-                                        progressive, models, sample_idx, n_models, F7_MAX_MODELS, F7_THREADS, chunks);
+    const int rc = epi_check_hypotheses("epipolar_hypotheses7_by_pair", {"matches_l", matches_l, 8}, matches_r, pair_off, stride, counts_in, pairs, cap,
+                                        H, pair_seed, norm, progressive, models, sample_idx, n_models, F7_MAX_MODELS, F7_THREADS, chunks);
     if (rc != PATS_OK) return rc;
     PATS_REQUIRE(workspace_bytes >= pats_epipolar_hypotheses7_workspace_bytes(pairs, H), "epipolar_hypotheses7_by_pair: workspace too small");
     hipLaunchKernelGGL(epipolar_hypotheses7_kernel, dim3((unsigned)(pairs * chunks)), dim3(F7_THREADS), 0, as_stream(stream), matches_l,

@@ -239,20 +239,6 @@ verify_polish_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
     }
 }
 
-// the staging can exceed the 64 KiB a launch gets unasked: raised once per device and family
-template <class T>
-static bool polish_lds_ready() {
-    static int state[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)verify_polish_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, POLISH_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1;
-}
-
 }  // namespace pats
 
 using namespace pats;
@@ -264,32 +250,16 @@ static int verify_polish_by_pair(const char* who, const float* matches_l, const 
                                  int use_min_conf, float min_conf, const float* models, int64_t H, const int32_t* best, int rounds,
                                  float* model, int64_t* best_count, uint8_t* inlier, double* moments, int32_t* best_round, int32_t* counts,
                                  pats_stream_t stream) {
-    EPI_REQUIRE_PTR(matches_l, 8);
-    EPI_REQUIRE_PTR(matches_r, 8);
-    EPI_REQUIRE_PTR(models, 4);
-    EPI_REQUIRE_PTR(thr, 4);
-    EPI_REQUIRE_PTR(model, 4);
-    EPI_REQUIRE_PTR(best_count, 8);
-    PATS_REQUIRE(inlier, "%s: null inlier", who);
-    EPI_REQUIRE_PTR(moments, 8);
-    EPI_REQUIRE_PTR(best_round, 4);
-    EPI_REQUIRE_PTR(counts, 4);
-    EPI_REQUIRE_ALIGNED(conf, 4);                    // optional pointers: null is aligned
-    EPI_REQUIRE_ALIGNED(norm, 4);
-    EPI_REQUIRE_ALIGNED(pair_off, 8);
-    EPI_REQUIRE_ALIGNED(counts_in, 8);
-    EPI_REQUIRE_ALIGNED(best, 4);
-    int rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap);
+    int rc = epi_check_scored(who, {"matches_l", matches_l, 8}, matches_r, models, thr,
+                              {{"model", model, 4}, {"best_count", best_count, 8}, {"inlier", inlier, 1}, {"moments", moments, 8},
+                               {"best_round", best_round, 4}, {"counts", counts, 4}},
+                              conf, norm, pair_off, stride, counts_in, pairs, cap, H, use_min_conf, min_conf, {"best", best, 4});
     if (rc != PATS_OK) return rc;
-    rc = epi_check_h(who, H);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(!use_min_conf || conf, "%s: min_conf needs conf", who);
-    PATS_REQUIRE(!use_min_conf || min_conf >= 0.0f, "%s: min_conf = %g must be a non-negative number", who, (double)min_conf);
     PATS_REQUIRE(rounds >= 1 && rounds <= POLISH_MAX_ROUNDS, "%s: rounds = %d (1 .. %d)", who, rounds, POLISH_MAX_ROUNDS);
     PATS_REQUIRE(best || H == 1, "%s: null best needs H == 1, got H = %lld", who, (long long)H);
     const int64_t longest = counts_in ? stride : cap;   // the staging comes from the sizes alone: no host read of the counts
     const int stage_n = (int)(longest < POLISH_STAGE ? longest : POLISH_STAGE);
-    if (!polish_lds_ready<T>()) {
+    if (!epi_lds_raised<verify_polish_kernel<T>>(POLISH_LDS)) {          // the staging can exceed what a launch gets unasked
         set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, POLISH_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

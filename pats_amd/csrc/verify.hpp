@@ -1,6 +1,6 @@
-// The two model families of the per-pair verification and the mask kernel's moment reduction - what epipolar.hip's kernels and
-// polish.hip's local optimisation both run, written once.  include/pats_amd.h states the definitions; docs/kernels.md 4.7 / 4.11 the
-// design.
+// The two model families of the per-pair verification, the mask kernel's moment reduction and the count argmax - what epipolar.hip's
+// kernels and polish.hip's local optimisation both run, and what absolute.hip takes of it (the packed FMAs, the argmax), written once.
+// include/pats_amd.h states the definitions; docs/kernels.md 4.7 / 4.11 the design.
 //
 // A family is a struct with the two things that differ: test2, THE arithmetic of its test (two matches against one model), and
 // accumulate, a match's contribution to the moments.
@@ -96,6 +96,35 @@ __device__ __forceinline__ uint32_t verify_gain(bool inlier, float s, float lim)
 __device__ __forceinline__ void verify_model(const float* __restrict__ m, float (&e)[9]) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) e[k] = m[k];
+}
+
+// The winner by count, one kernel for every family (epipolar.hip and absolute.hip launch it): one workgroup of THREADS =
+// ARGMAX_THREADS per pair, the largest count of counts[p, :], the lowest index that holds it.  A template, so that each translation
+// unit that launches it carries its own copy
+constexpr int ARGMAX_THREADS = 256;
+
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) verify_argmax_kernel(const int32_t* __restrict__ counts, int H, int32_t* __restrict__ best,
+                                                                 int64_t* __restrict__ best_count) {
+    __shared__ int sv[THREADS], si[THREADS];
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int32_t* c = counts + p * H;
+    int v = -1, idx = 0x7fffffff;
+    for (int h = tid; h < H; h += THREADS) {            // ascending h: a later equal count does not replace an earlier one
+        const int x = c[h];
+        if (x > v) { v = x; idx = h; }
+    }
+    sv[tid] = v; si[tid] = idx;
+    wg_barrier();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int ov = sv[tid + s], oi = si[tid + s];
+            if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
+        }
+        wg_barrier();
+    }
+    if (tid == 0) { best[p] = si[0]; best_count[p] = (int64_t)sv[0]; }
 }
 
 // The moments' fixed order behind the thread-local sums of an EPI_MASK_THREADS walk: an xor tree over the wave, then the waves in

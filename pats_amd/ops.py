@@ -16,6 +16,7 @@ Reference call sites (paths relative to zju3dv/pats):
   Compute_imgs / tensor_resize     utils/utils.py:1343-1393  setup/library.cpp:47-66
   Compute_result / third label     models/third_layer.py:161-170,184-217
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -1609,13 +1610,36 @@ def _bp_one_form(fn, pair_off, stride, counts):
         raise RuntimeError("%s: give either pair_off, or stride and counts" % fn)
 
 
-def _bp_matches(fn, matches_l, matches_r):
-    """The match lists ([cap,2], or top-K's [pairs,K,2]) as flat GPU [cap,2] lists -> (ml, mr, cap)."""
-    ml, mr = _dev(matches_l, "matches_l"), _dev(matches_r, "matches_r")
-    if ml.dim() < 2 or ml.shape[-1] != 2 or ml.shape != mr.shape:
-        raise RuntimeError("%s: matches_l / matches_r must be [cap,2]" % fn)
-    ml = ml.reshape(-1, 2)
-    return ml, mr.reshape(-1, 2), int(ml.shape[0])
+# What tells the families of the hypothesis, verification and local-optimisation stages apart, as data: the name and width of the
+# first list; whether it and matches_r must have the same shape (else the same number of rows: lifted points are flat beside a top-K's
+# [pairs,K,2]) and what the refusal of the two says; the shape of a model, as a tuple and as the messages write it with
+# the family's letter for the model count; whether a local optimisation returns moments, or takes steps and returns cost.
+_Family = collections.namedtuple("_Family", "first width same_shape lists model models letter moments cost")
+_EPI = _Family("matches_l", 2, True, "matches_l / matches_r must be [cap,2]", (3, 3), "[pairs,H,3,3]", "H", True, False)
+_ABS = _Family("points", 3, False, "points must be [cap,3] and matches_r [cap,2]", (3, 4), "[pairs,M,3,4]", "M", False, True)
+
+
+def _bp_flat(t, width):
+    """A GPU list [cap,width] (or top-K's [pairs,K,width]) as the flat [cap,width] list it is - None for any other shape."""
+    shape = t.shape
+    if len(shape) < 2 or shape[-1] != width:
+        return None
+    return t if len(shape) == 2 else t.reshape(-1, width)             # a view costs a microsecond: these calls take few
+
+
+def _bp_vector(t, name, dtype=torch.float32):
+    """A per-pair (or per-match) GPU tensor as the vector of its elements; a [n] tensor as it is."""
+    t = _dev(t, name, dtype)
+    return t if t.dim() == 1 else t.reshape(-1)
+
+
+def _bp_matches(fn, first, matches_r, fam=_EPI):
+    """The family's first list and the right matches as flat GPU lists -> (first [cap,width], mr [cap,2], cap)."""
+    a, mr = _dev(first, fam.first), _dev(matches_r, "matches_r")
+    fa, fr = _bp_flat(a, fam.width), _bp_flat(mr, 2)
+    if fa is None or fr is None or (a.shape != mr.shape if fam.same_shape else fa.shape[0] != fr.shape[0]):
+        raise RuntimeError("%s: %s" % (fn, fam.lists))
+    return fa, fr, fa.shape[0]
 
 
 def _bp_segments(fn, pair_off, stride, counts, pairs, cap):
@@ -1647,6 +1671,41 @@ def _bp_norm(fn, norm, pairs):
     if tuple(norm.shape) != (pairs, 8):
         raise RuntimeError("%s: norm must be [pairs,8]" % fn)
     return norm
+
+
+def _bp_candidates(fn, fam, first, matches_r, models, thr, pair_off, stride, counts, pairs):
+    """The lists, the candidate models and the segments of a verification or a local optimisation, checked -> (first, mr, models, thr
+    as GPU tensors, H = the models per pair, seg = the C arguments (pair_off, stride, counts_in, pairs, cap))."""
+    a, mr, cap = _bp_matches(fn, first, matches_r, fam)
+    models, thr = _dev(models, "models"), _bp_vector(thr, "thr")
+    if models.dim() != 4 or tuple(models.shape[2:]) != fam.model:
+        raise RuntimeError("%s: models must be %s" % (fn, fam.models))
+    H = int(models.shape[1])
+    _, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if models.shape[0] != pairs or thr.numel() != pairs:
+        raise RuntimeError("%s: models %s and thr [pairs] must hold %d pairs" % (fn, fam.models, pairs))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: %s = %d, must lie in 1 .. %d" % (fn, fam.letter, H, epipolar_max_h()))
+    return a, mr, models, thr, H, (off_p, stride, counts_p, pairs, cap)
+
+
+def _bp_conf_norm(fn, conf, cap, norm, pairs):
+    """The optional confidence list as a flat GPU [cap] tensor and the optional normalisation -> (conf, norm)."""
+    if conf is not None:
+        conf = _bp_vector(conf, "conf")
+        if conf.numel() != cap:
+            raise RuntimeError("%s: conf must be [cap]" % fn)
+    return conf, _bp_norm(fn, norm, pairs)
+
+
+def _bp_gated_call(first, mr, conf, inlier, min_conf, cap):
+    """What a verification or a local optimisation hands to C for its per-match arguments and its gate -> ((first, matches_r, conf),
+    (use_min_conf, min_conf), inlier), pointers: with cap == 0 the placeholders stand in for the empty tensors."""
+    if cap == 0:
+        first = mr = _bp_placeholder(first.device)
+        inlier = _bp_placeholder(first.device, torch.uint8)
+        conf = None if conf is None else first
+    return (_ptr(first), _ptr(mr), _ptr(conf)), (0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf)), _ptr(inlier)
 
 
 def _bp_refit_source(fn, pairs, moments, models, best):
@@ -1771,43 +1830,29 @@ def topk_spread_by_pair(matches_l, matches_r, conf, pair_off, K, cell, grid, sid
     return out
 
 
-def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out,
-                   pairs, adaptive=None, msac=False):
-    """What the six verifications share - everything but the C entry and its workspace query (the library's functions; looked up by
-    the callers, by plain attribute: these calls take microseconds and a formatted name would show).  adaptive: None for
-    the fixed budget, else (confidence, sample_size, models_per_sample, round_models) - four more arguments, two more outputs.
-    msac: the MSAC entries - two more outputs, gains and best_gain."""
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
+def _score_checked(fn, fam, first, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, out, pairs, moments=False,
+                   adaptive=None, msac=False):
+    """What every verification checks and allocates; the caller lays out its own C call from what comes back -> (head, out, (pairs, H,
+    cap)): head = the C arguments every score entry starts with (the lists and conf, the segments, models, H, thr, norm, the gate,
+    counts, best, best_count, inlier), out = the destinations.  moments, adaptive, msac: the outputs they add, and adaptive's checks."""
+    _bp_layout(fn, [(first, fam.first), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"),
                     (counts, "counts"), (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
     _bp_one_form(fn, pair_off, stride, counts)
     if min_conf is not None and conf is None:
         raise RuntimeError("%s: min_conf needs conf" % fn)
     if adaptive is not None:
         confidence, s, g, B = float(adaptive[0]), int(adaptive[1]), int(adaptive[2]), int(adaptive[3])
-        if not 0.0 < confidence < 1.0:                    # false for a NaN
+        if not 0.0 < confidence < 1.0:                   # false for a NaN
             raise RuntimeError("%s: confidence = %r must lie strictly between 0 and 1" % (fn, confidence))
         if not (1 <= s <= 16 and 1 <= g <= 16):
             raise RuntimeError("%s: sample_size = %d and models_per_sample = %d must lie in 1 .. 16" % (fn, s, g))
         if B < 64 or B % 64:
             raise RuntimeError("%s: round_models = %d must be a positive multiple of 64" % (fn, B))
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
-        raise RuntimeError("%s: models must be [pairs,H,3,3]" % fn)
-    H = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("%s: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % (fn, pairs))
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    a, mr, models, thr, H, seg = _bp_candidates(fn, fam, first, matches_r, models, thr, pair_off, stride, counts, pairs)
+    pairs, cap = seg[3:]
     if adaptive is not None and -(-H // B) > 256:
         raise RuntimeError("%s: round_models = %d gives %d rounds for H = %d (at most 256)" % (fn, B, -(-H // B), H))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("%s: conf must be [cap]" % fn)
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
+    conf, norm = _bp_conf_norm(fn, conf, cap, norm, pairs)
     want = [("counts", torch.int32, (pairs, H)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
             ("inlier", torch.uint8, (cap,))]
     if moments:
@@ -1816,60 +1861,70 @@ def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr
         want += [("used", torch.int32, (pairs,)), ("participating", torch.int32, (pairs,))]
     if msac:
         want += [("gains", torch.int64, (pairs, H)), ("best_gain", torch.int64, (pairs,))]
-    out = _bp_outputs(fn, want, out, dev)
-    nws = workspace_bytes(pairs, H, cap)
-    ws = _workspace(nws, dev) if nws else None
-    inl = out[3]
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else ml
-    more = () if adaptive is None else (confidence, s, g, B, _ptr(out[-2]), _ptr(out[-1]))
-    if msac:
-        more = (_ptr(out[-2]), _ptr(out[-1]))
-    _check(entry(
-        _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), H, _ptr(thr), _ptr(norm),
-        0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl),
-        _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream(), *more), fn)
+    out = _bp_outputs(fn, want, out, a.device)
+    lists, gate, inl = _bp_gated_call(a, mr, conf, out[3], min_conf, cap)
+    return lists + seg + (_ptr(models), H, _ptr(thr), _ptr(norm)) + gate + (_ptr(out[0]), _ptr(out[1]), _ptr(out[2]), inl), out, (pairs, H, cap)
+
+
+def _score_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, moments, out,
+                   pairs, adaptive=None, msac=False):
+    """The C call of the six epipolar and homography verifications behind _score_checked's head: moments, the workspace, the stream
+    and what an adaptive or an MSAC entry appends.  entry and its workspace query are the library's functions, looked up by the
+    callers by plain attribute: these calls take microseconds and a formatted name would show.  adaptive: None for the fixed budget,
+    else (confidence, sample_size, models_per_sample, round_models) - four more arguments, two more outputs.  msac: the MSAC entries
+    - two more outputs, gains and best_gain."""
+    head, out, sizes = _score_checked(fn, _EPI, matches_l, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, out, pairs,
+                                      moments, adaptive, msac)
+    nws = workspace_bytes(*sizes)
+    ws = _workspace(nws, out[0].device) if nws else None
+    more = (_ptr(out[-2]), _ptr(out[-1])) if msac or adaptive is not None else ()
+    if adaptive is not None:
+        more = (float(adaptive[0]), int(adaptive[1]), int(adaptive[2]), int(adaptive[3])) + more
+    _check(entry(*head, _ptr(out[4]) if moments else None, _ptr(ws), nws, _stream(), *more), fn)
     return out
 
 
-def _hypotheses_by_pair(fn, K, slots, entry, workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm, progressive,
-                        return_samples, return_counts, out, pairs):
-    """What the minimal-sample generators share - everything but the sample size K, the model slots per sample (1, or the 10 and 3
-    of the 5- and 7-point generators, whose entries also take n_models), the C entry and its workspace query."""
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+def _hypotheses_checked(fn, fam, K, slots, first, matches_r, H, seed, pair_off, stride, counts, norm, progressive, return_samples,
+                        return_counts, out, pairs):
+    """What every minimal-sample generator checks and allocates - K = the sample size, slots = the models per sample (1, the 10 and 3
+    of the 5- and 7-point generators, P3P's 4) -; the caller lays out its own C call -> (head, out, (pairs, H)): head = the C arguments every
+    generator starts with (the lists, the segments, H, seed, norm, progressive, models, sample_idx - and n_models where slots > 1: the
+    one-model entries have none), out = the destinations."""
+    _bp_layout(fn, [(first, fam.first), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
                     (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
     _bp_one_form(fn, pair_off, stride, counts)
     if not isinstance(seed, torch.Tensor):
         raise RuntimeError("%s: seed must be an int64 GPU tensor [pairs]" % fn)
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    a, mr, cap = _bp_matches(fn, first, matches_r, fam)
     H = int(H)
-    seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    seed = _bp_vector(seed, "seed", torch.int64)
+    _, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     if seed.numel() != pairs:
         raise RuntimeError("%s: seed must hold one int64 per pair (%d), got %d" % (fn, pairs, seed.numel()))
     if not 1 <= H <= epipolar_max_h() // slots:
         raise RuntimeError("%s: H = %d, must lie in 1 .. %d%s" % (fn, H, epipolar_max_h() // slots, " (%d H models)" % slots if slots > 1 else ""))
     norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("models", torch.float32, (pairs, H, 3, 3) if slots == 1 else (pairs, H, slots, 3, 3))]
+    want = [("models", torch.float32, (pairs, H) + ((slots,) if slots > 1 else ()) + fam.model)]
     if return_samples:
         want.append(("sample_idx", torch.int32, (pairs, H, K)))
     if return_counts:
         want.append(("n_models", torch.int32, (pairs, H)))
-    out = _bp_outputs(fn, want, out, dev, lone=True)
-    nws = workspace_bytes(pairs, H)
-    ws = _workspace(nws, dev) if nws else None
+    out = _bp_outputs(fn, want, out, a.device, lone=True)
     if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-    samples = _ptr(out[1]) if return_samples else None
-    if slots == 1:                                        # the 8- and 4-point entries have no n_models
-        _check(entry(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0,
-                     _ptr(out[0]), samples, _ptr(ws), nws, _stream()), fn)
-    else:
-        _check(entry(_ptr(ml), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0,
-                     _ptr(out[0]), samples, _ptr(out[-1]) if return_counts else None, _ptr(ws), nws, _stream()), fn)
+        a = mr = _bp_placeholder(a.device)
+    n_models = (_ptr(out[-1]) if return_counts else None,) if slots > 1 else ()
+    return (_ptr(a), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm), 1 if progressive else 0, _ptr(out[0]),
+            _ptr(out[1]) if return_samples else None) + n_models, out, (pairs, H)
+
+
+def _hypotheses_by_pair(fn, K, slots, entry, workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm, progressive,
+                        return_samples, return_counts, out, pairs):
+    """The C call of the epipolar and homography generators behind _hypotheses_checked's head: the workspace and the stream."""
+    head, out, sizes = _hypotheses_checked(fn, _EPI, K, slots, matches_l, matches_r, H, seed, pair_off, stride, counts, norm, progressive,
+                                           return_samples, return_counts, out, pairs)
+    nws = workspace_bytes(*sizes)
+    ws = _workspace(nws, out[0].device) if nws else None
+    _check(entry(*head, _ptr(ws), nws, _stream()), fn)
     return out if len(out) > 1 else out[0]
 
 
@@ -2881,56 +2936,55 @@ def scale_head(desc1, height, width, weights, biases, return_heads=False):
     return out
 
 
-def _polish_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride, counts, conf, min_conf,
-                    norm, out, pairs):
-    """What the three local optimisations share - everything but the C entry and its workspace query (looked up by the callers, as for
-    _score_by_pair)."""
-    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (best, "best"),
+def _polish_checked(fn, fam, first, matches_r, models, thr, best, rounds, pair_off, stride, counts, conf, min_conf, norm, out, pairs,
+                    steps=None):
+    """What every local optimisation checks and allocates; the caller lays out its own C call from what comes back -> (lists, seg,
+    models, thr_norm, gate, walk, inlier, out): tuples of C arguments - (first, matches_r, conf), (pair_off, stride, counts_in, pairs,
+    cap), (models, H), (thr, norm), (use_min_conf, min_conf), (best, rounds) or, for a family with a cost, (best, rounds, steps) -, the
+    pointer of the mask, and the destinations."""
+    _bp_layout(fn, [(first, fam.first), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (best, "best"),
                     (pair_off, "pair_off"), (counts, "counts"), (conf, "conf"), (norm, "norm")],
                {"best": torch.int32, "pair_off": torch.int64, "counts": torch.int64})
     _bp_one_form(fn, pair_off, stride, counts)
     if min_conf is not None and conf is None:
         raise RuntimeError("%s: min_conf needs conf" % fn)
-    rounds = int(rounds)
+    walk = (int(rounds), int(steps)) if fam.cost else (int(rounds),)
+    rounds = walk[0]
     if not 1 <= rounds <= 16:
         raise RuntimeError("%s: rounds = %d, must lie in 1 .. 16" % (fn, rounds))
-    ml, mr, cap = _bp_matches(fn, matches_l, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 3):
-        raise RuntimeError("%s: models must be [pairs,H,3,3]" % fn)
-    H = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("%s: models [pairs,H,3,3] and thr [pairs] must hold %d pairs" % (fn, pairs))
-    if not 1 <= H <= epipolar_max_h():
-        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    if fam.cost and not 1 <= walk[1] <= 8:
+        raise RuntimeError("%s: steps = %d, must lie in 1 .. 8" % (fn, walk[1]))
+    a, mr, models, thr, H, seg = _bp_candidates(fn, fam, first, matches_r, models, thr, pair_off, stride, counts, pairs)
+    pairs, cap = seg[3:]
     if best is None:
         if H != 1:
-            raise RuntimeError("%s: best may be left out with H == 1 only, got H = %d" % (fn, H))
+            raise RuntimeError("%s: best may be left out with %s == 1 only, got %s = %d" % (fn, fam.letter, fam.letter, H))
     else:
-        best = _dev(best, "best", torch.int32).reshape(-1)
+        best = _bp_vector(best, "best", torch.int32)
         if best.numel() != pairs:
             raise RuntimeError("%s: best must hold one int32 per pair (%d), got %d" % (fn, pairs, best.numel()))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("%s: conf must be [cap]" % fn)
-    norm = _bp_norm(fn, norm, pairs)
-    dev = ml.device
-    want = [("model", torch.float32, (pairs, 3, 3)), ("best_count", torch.int64, (pairs,)), ("inlier", torch.uint8, (cap,)),
-            ("moments", torch.float64, (pairs, 9, 9)), ("best_round", torch.int32, (pairs,)), ("counts", torch.int32, (pairs, rounds + 1))]
-    out = _bp_outputs(fn, want, out, dev)
-    nws = workspace_bytes(pairs, H, cap)
-    ws = _workspace(nws, dev) if nws else None
-    inl = out[2]
-    if cap == 0:
-        ml = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else ml
-    _check(entry(
-        _ptr(ml), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(thr), _ptr(norm), 0 if min_conf is None else 1,
-        0.0 if min_conf is None else float(min_conf), _ptr(models), H, _ptr(best), rounds, _ptr(out[0]), _ptr(out[1]), _ptr(inl),
-        _ptr(out[3]), _ptr(out[4]), _ptr(out[5]), _ptr(ws), nws, _stream()), fn)
+    conf, norm = _bp_conf_norm(fn, conf, cap, norm, pairs)
+    want = [("model", torch.float32, (pairs,) + fam.model), ("best_count", torch.int64, (pairs,)), ("inlier", torch.uint8, (cap,))]
+    if fam.moments:
+        want.append(("moments", torch.float64, (pairs, 9, 9)))
+    want += [("best_round", torch.int32, (pairs,)), ("counts", torch.int32, (pairs, rounds + 1))]
+    if fam.cost:
+        want.append(("cost", torch.float64, (pairs, rounds + 1)))
+    out = _bp_outputs(fn, want, out, a.device)
+    lists, gate, inl = _bp_gated_call(a, mr, conf, out[2], min_conf, cap)
+    return lists, seg, (_ptr(models), H), (_ptr(thr), _ptr(norm)), gate, (_ptr(best),) + walk, inl, out
+
+
+def _polish_by_pair(fn, entry, workspace_bytes, matches_l, matches_r, models, thr, best, rounds, pair_off, stride, counts, conf, min_conf,
+                    norm, out, pairs):
+    """The C call of the three epipolar and homography local optimisations from _polish_checked's pieces (entry and its workspace
+    query are looked up by the callers, as for _score_by_pair)."""
+    lists, seg, models, thr_norm, gate, walk, inl, out = _polish_checked(fn, _EPI, matches_l, matches_r, models, thr, best, rounds, pair_off,
+                                                                         stride, counts, conf, min_conf, norm, out, pairs)
+    nws = workspace_bytes(seg[3], models[1], seg[4])    # pairs, H, cap
+    ws = _workspace(nws, out[0].device) if nws else None
+    _check(entry(*lists, *seg, *thr_norm, *gate, *models, *walk, _ptr(out[0]), _ptr(out[1]), inl, _ptr(out[3]), _ptr(out[4]),
+                 _ptr(out[5]), _ptr(ws), nws, _stream()), fn)
     return out
 
 
@@ -3232,10 +3286,9 @@ def lift_by_pair(matches, depths, pair_off=None, stride=None, counts=None, norm=
     _bp_one_form(fn, pair_off, stride, counts)
     if interp not in _INTERP or isinstance(interp, bool):
         raise RuntimeError("%s: interp must be \"nearest\" (0) or \"bilinear\" (1), got %r" % (fn, interp))
-    ml = _dev(matches, "matches")
-    if ml.dim() < 2 or ml.shape[-1] != 2:
+    ml = _bp_flat(_dev(matches, "matches"), 2)
+    if ml is None:
         raise RuntimeError("%s: matches must be [cap,2]" % fn)
-    ml = ml.reshape(-1, 2)
     cap = int(ml.shape[0])
     seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
     dev = ml.device
@@ -3264,15 +3317,6 @@ def lift_by_pair(matches, depths, pair_off=None, stride=None, counts=None, norm=
     return out
 
 
-def _abs_lists(fn, points, matches_r):
-    """The lifted points ([cap,3], or [pairs,K,3]) and the right list as flat GPU lists -> (points, mr, cap)."""
-    X, mr = _dev(points, "points"), _dev(matches_r, "matches_r")
-    if X.dim() < 2 or X.shape[-1] != 3 or mr.dim() < 2 or mr.shape[-1] != 2 or X.numel() // 3 != mr.numel() // 2:
-        raise RuntimeError("%s: points must be [cap,3] and matches_r [cap,2]" % fn)
-    X = X.reshape(-1, 3)
-    return X, mr.reshape(-1, 2), int(X.shape[0])
-
-
 def absolute_hypotheses_by_pair(points, matches_r, H, seed, pair_off=None, stride=None, counts=None, norm=None, progressive=False,
                                 return_samples=False, return_counts=False, out=None, pairs=None):
     """H P3P samples per pair, each solved for the up to four absolute poses (R, t) with x_r ~ R X + t, ON THE DEVICE, one launch, no
@@ -3283,32 +3327,9 @@ def absolute_hypotheses_by_pair(points, matches_r, H, seed, pair_off=None, strid
     sample point, zero models behind - then sample_idx [pairs,H,3] int32 with return_samples=True and n_models [pairs,H] int32 with
     return_counts=True.  out: the destinations, in that order."""
     fn = "absolute_hypotheses_by_pair"
-    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"), (norm, "norm")],
-               {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if not isinstance(seed, torch.Tensor):
-        raise RuntimeError("%s: seed must be an int64 GPU tensor [pairs]" % fn)
-    X, mr, cap = _abs_lists(fn, points, matches_r)
-    H = int(H)
-    seed = _dev(seed, "seed", torch.int64).reshape(-1)
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if seed.numel() != pairs:
-        raise RuntimeError("%s: seed must hold one int64 per pair (%d), got %d" % (fn, pairs, seed.numel()))
-    if not 1 <= H <= epipolar_max_h() // 4:
-        raise RuntimeError("%s: H = %d, must lie in 1 .. %d (4 H models)" % (fn, H, epipolar_max_h() // 4))
-    norm = _bp_norm(fn, norm, pairs)
-    dev = X.device
-    want = [("models", torch.float32, (pairs, H, 4, 3, 4))]
-    if return_samples:
-        want.append(("sample_idx", torch.int32, (pairs, H, 3)))
-    if return_counts:
-        want.append(("n_models", torch.int32, (pairs, H)))
-    out = _bp_outputs(fn, want, out, dev, lone=True)
-    if cap == 0:
-        X = mr = _bp_placeholder(dev)
-    _check(_L().pats_absolute_hypotheses_by_pair_f32(_ptr(X), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
-                                                     1 if progressive else 0, _ptr(out[0]), _ptr(out[1]) if return_samples else None,
-                                                     _ptr(out[-1]) if return_counts else None, _stream()), fn)
+    head, out, _ = _hypotheses_checked(fn, _ABS, 3, 4, points, matches_r, H, seed, pair_off, stride, counts, norm, progressive,
+                                       return_samples, return_counts, out, pairs)
+    _check(_L().pats_absolute_hypotheses_by_pair_f32(*head, _stream()), fn)
     return out if len(out) > 1 else out[0]
 
 
@@ -3322,38 +3343,8 @@ def absolute_score_by_pair(points, matches_r, models, thr, pair_off=None, stride
     Returns (counts [pairs,M] int32, best [pairs] int32 - the lowest index among the largest counts -, best_count [pairs] int64,
     inlier [cap] uint8 = the winner's mask).  Bit-reproducible.  out: the four destinations."""
     fn = "absolute_score_by_pair"
-    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (pair_off, "pair_off"), (counts, "counts"),
-                    (conf, "conf"), (norm, "norm")], {"pair_off": torch.int64, "counts": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if min_conf is not None and conf is None:
-        raise RuntimeError("%s: min_conf needs conf" % fn)
-    X, mr, cap = _abs_lists(fn, points, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 4):
-        raise RuntimeError("%s: models must be [pairs,M,3,4]" % fn)
-    M = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("%s: models [pairs,M,3,4] and thr [pairs] must hold %d pairs" % (fn, pairs))
-    if not 1 <= M <= epipolar_max_h():
-        raise RuntimeError("%s: M = %d, must lie in 1 .. %d" % (fn, M, epipolar_max_h()))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("%s: conf must be [cap]" % fn)
-    norm = _bp_norm(fn, norm, pairs)
-    dev = X.device
-    want = [("counts", torch.int32, (pairs, M)), ("best", torch.int32, (pairs,)), ("best_count", torch.int64, (pairs,)),
-            ("inlier", torch.uint8, (cap,))]
-    out = _bp_outputs(fn, want, out, dev)
-    inl = out[3]
-    if cap == 0:
-        X = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else X
-    _check(_L().pats_absolute_score_by_pair_f32(_ptr(X), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), M, _ptr(thr),
-                                                _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
-                                                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(inl), _stream()), fn)
+    head, out, _ = _score_checked(fn, _ABS, points, matches_r, models, thr, pair_off, stride, counts, conf, min_conf, norm, out, pairs)
+    _check(_L().pats_absolute_score_by_pair_f32(*head, _stream()), fn)
     return out
 
 
@@ -3372,49 +3363,8 @@ def absolute_polish_by_pair(points, matches_r, models, thr, best=None, rounds=4,
     every round, a walk that stopped early on a repeated model padded with its last values).  Bit-reproducible.  out: the six
     destinations."""
     fn = "absolute_polish_by_pair"
-    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (models, "models"), (thr, "thr"), (best, "best"), (pair_off, "pair_off"),
-                    (counts, "counts"), (conf, "conf"), (norm, "norm")], {"best": torch.int32, "pair_off": torch.int64, "counts": torch.int64})
-    _bp_one_form(fn, pair_off, stride, counts)
-    if min_conf is not None and conf is None:
-        raise RuntimeError("%s: min_conf needs conf" % fn)
-    rounds, steps = int(rounds), int(steps)
-    if not 1 <= rounds <= 16:
-        raise RuntimeError("%s: rounds = %d, must lie in 1 .. 16" % (fn, rounds))
-    if not 1 <= steps <= 8:
-        raise RuntimeError("%s: steps = %d, must lie in 1 .. 8" % (fn, steps))
-    X, mr, cap = _abs_lists(fn, points, matches_r)
-    models, thr = _dev(models, "models"), _dev(thr, "thr").reshape(-1)
-    if models.dim() != 4 or tuple(models.shape[2:]) != (3, 4):
-        raise RuntimeError("%s: models must be [pairs,M,3,4]" % fn)
-    M = int(models.shape[1])
-    seg, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
-    if models.shape[0] != pairs or thr.numel() != pairs:
-        raise RuntimeError("%s: models [pairs,M,3,4] and thr [pairs] must hold %d pairs" % (fn, pairs))
-    if not 1 <= M <= epipolar_max_h():
-        raise RuntimeError("%s: M = %d, must lie in 1 .. %d" % (fn, M, epipolar_max_h()))
-    if best is None:
-        if M != 1:
-            raise RuntimeError("%s: best may be left out with M == 1 only, got M = %d" % (fn, M))
-    else:
-        best = _dev(best, "best", torch.int32).reshape(-1)
-        if best.numel() != pairs:
-            raise RuntimeError("%s: best must hold one int32 per pair (%d), got %d" % (fn, pairs, best.numel()))
-    if conf is not None:
-        conf = _dev(conf, "conf").reshape(-1)
-        if conf.numel() != cap:
-            raise RuntimeError("%s: conf must be [cap]" % fn)
-    norm = _bp_norm(fn, norm, pairs)
-    dev = X.device
-    want = [("model", torch.float32, (pairs, 3, 4)), ("best_count", torch.int64, (pairs,)), ("inlier", torch.uint8, (cap,)),
-            ("best_round", torch.int32, (pairs,)), ("counts", torch.int32, (pairs, rounds + 1)), ("cost", torch.float64, (pairs, rounds + 1))]
-    out = _bp_outputs(fn, want, out, dev)
-    inl = out[2]
-    if cap == 0:
-        X = mr = _bp_placeholder(dev)
-        inl = _bp_placeholder(dev, torch.uint8)
-        conf = None if conf is None else X
-    _check(_L().pats_absolute_polish_by_pair_f32(_ptr(X), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(models), M, _ptr(thr),
-                                                 _ptr(norm), 0 if min_conf is None else 1, 0.0 if min_conf is None else float(min_conf),
-                                                 _ptr(best), rounds, steps, _ptr(out[0]), _ptr(out[1]), _ptr(inl), _ptr(out[3]), _ptr(out[4]),
-                                                 _ptr(out[5]), _stream()), fn)
+    lists, seg, models, thr_norm, gate, walk, inl, out = _polish_checked(fn, _ABS, points, matches_r, models, thr, best, rounds, pair_off, stride,
+                                                                         counts, conf, min_conf, norm, out, pairs, steps)
+    _check(_L().pats_absolute_polish_by_pair_f32(*lists, *seg, *models, *thr_norm, *gate, *walk, _ptr(out[0]),
+                                                 _ptr(out[1]), inl, _ptr(out[3]), _ptr(out[4]), _ptr(out[5]), _stream()), fn)
     return out
