@@ -1162,8 +1162,8 @@ int pats_epipolar_triangulate_by_pair_f64(const float* matches_l, const float* m
  * translation error of every pair against the ground truth (utils/metrics.py:56-66: angle_error_mat, angle_error_vec and the fold of
  * the translation angle at 90 degrees), and the AUC of the recall curve over a data set's worth of them (metrics.py:70-96: error_auc
  * under aggregate_metrics) - on the device, no host read.  What it is not: an estimator (the pose comes from
- * pats_epipolar_pose_by_pair_f64); a match-precision metric (the verification with the ground truth's essential matrix as the one
- * model gives that); and nothing in pipeline.forward_*, the drop-in or bench.py calls it.
+ * pats_epipolar_pose_by_pair_f64); a match-precision metric (pats_match_error_by_pair_f64 is that; the verification with the ground
+ * truth's essential matrix as the one model is its epipolar form); and nothing in pipeline.forward_*, the drop-in or bench.py calls it.
  *
  * pats_pose_error_by_pair_f64 - one launch for the batch, float64 throughout
  * Inputs
@@ -1938,6 +1938,83 @@ int pats_absolute_polish_by_pair_f32(const float* points, const float* matches_r
                                      const float* thr, const float* norm, int use_min_conf, float min_conf, const int32_t* best, int rounds,
                                      int steps, float* model, int64_t* best_count, uint8_t* inlier, int32_t* best_round, int32_t* counts,
                                      double* cost, pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair match error against ground truth (ABI 8, a symbol added): whether the MATCHES are right.  A left match lifted through the
+ * left depth map (pats_lift_by_pair_f32) is carried through the ground-truth relative pose into the right image, and the distance of
+ * the matched right point from that projection is the match's error in pixels - the reprojection form of the check the reference's
+ * Compute_depth_label (datasets/megadepth.py) and Compute_label (utils/utils.py) make, and the "matching precision" every matcher
+ * reports on ScanNet and MegaDepth.  The epipolar test of a verification with the ground truth's essential matrix lets a match slide
+ * along its epipolar line; this does not.  With the right image's depth map the match must also be covisible.  Per pair it counts
+ * the outcomes, the matches within each threshold, the same over a sweep of confidence floors (to choose min_conf, K and cell of the
+ * top-K stages) and the confusion against a mask (how many of a verification's inliers are true).  The segments come in the two
+ * forms of pats_epipolar_score_by_pair_f32 (ragged pair_off, or stride with counts_in, exactly ONE of them, with the same
+ * clamping).  Two fills and ONE launch for the whole batch, nothing read back, no workspace, no environment switch.
+ * What it is not: the right-to-left direction (call it with the sides exchanged and the inverse ground truth); a resampler - the depth
+ * maps must be given at the resolution the matches live at, as for the lift; the reference's grid labels themselves; and nothing in
+ * pipeline.forward_*, the drop-in, bench.py or the smoke run calls it.
+ *
+ * Inputs
+ *   points [cap,3] float32      pats_lift_by_pair_f32's output: X = (x0 d, x1 d, d); an invalid lift holds NaNs
+ *   matches_r [cap,2] float32   the right list, (c0, c1) = (y, x) un-normalised pixels: p = (p0, p1)
+ *   norm [pairs,8] float32 (optional)   only its RIGHT half (c0, c1, s0, s1) is used: it takes the projection back to pixels.  Pass
+ *              what the lift was given
+ *   T1 [pairs,4,4], T0 [pairs,4,4] float64 (T0 optional)   as pats_pose_error_by_pair_f64 takes them; R_gt, t_gt by exactly its formula
+ *   swapped (0 or 1)            1: the ground truth is in the reference's (x, y) frame and is conjugated into the frame of the points,
+ *              as the pose stages do: Rg = P R_gt P, tg = P t_gt, P exchanges the first two components (an index permutation: exact).
+ *              0: Rg = R_gt, tg = t_gt
+ *   depth_r_table [pairs,4] int64 (optional)   the RIGHT images' depth maps in the layout of the lift's depth_table (address of a
+ *              float32 map, h, w, row stride in elements).  A null address, h < 1 or w < 1: no covisibility test for that pair
+ *   occl_rel (float64, finite, > 0)   looked at only with depth_r_table
+ *   size_r [pairs,2] float32 (optional)   (h, w) of the right image's real content (the canvas minus its pad)
+ *   conf [cap] float32 (optional), use_min_conf with min_conf   the verification's gate.  A match TAKES PART iff p0 and p1 are finite
+ *              and, with use_min_conf, conf >= min_conf (false for a NaN)
+ *   thr        n_thr HOST doubles, 1 <= n_thr <= 8, each finite and > 0, strictly ascending, in pixels
+ *   edges (optional)   B HOST floats, 1 <= B <= 64, finite, strictly ascending: confidence floors.  Needs conf
+ *   mask [cap] uint8 (optional)   e.g. a verification's inlier mask; non-zero is "in"
+ * Definition, per match of a segment that takes part (float64, no contraction, sums left to right, brackets first; the float32
+ * inputs are widened exactly)
+ *   Y_i = ((Rg[i][0] X0 + Rg[i][1] X1) + Rg[i][2] X2) + tg[i]            i = 0, 1, 2
+ *   u_k = Y_k / Y_2;   q_k = u_k / s_k + c_k  (without norm q_k = u_k);   e_k = q_k - p_k            k = 0, 1
+ *   err = sqrt(e0 e0 + e1 e1)
+ *   status     the first rule that applies:
+ *              0  the row is in no segment, or the match does not take part
+ *              2  X is not finite (no depth)
+ *              3  Y_2 <= 0 or an entry of Y is not finite (behind the right camera; also a ground truth that is not finite)
+ *              4  size_r given and not (0 <= q0 <= h - 1 and 0 <= q1 <= w - 1)
+ *              5  the pair has a right map and the tap i = rint(q0), j = rint(q1) (round half to even, in float64) lies outside
+ *                 [0, h) x [0, w) of the map, or d1 = map[i, j] is not finite or <= 0
+ *              6  the pair has a right map and abs(Y_2 - d1) > occl_rel * d1 (not covisible)
+ *              1  scored
+ *   An err that is not finite (an overflow of finite inputs) is scored, lies within no threshold and makes err_sum not finite.
+ * Outputs - every call defines every byte; rows of cap in no segment (and the slack of a strided row) hold exact zeros
+ *   err [cap] float64           NaN for a row of a segment that is not scored
+ *   status [cap] uint8
+ *   tally [pairs,8] int64       the segment's rows per status value; slot 7 is zero
+ *   correct [pairs,n_thr] int64   the scored matches with err <= thr[k]
+ *   err_sum [pairs] float64     the sum of err over the scored matches (0 for none)
+ *   sweep [pairs,B,1+n_thr] int64 (with edges, and only then)   sweep[p,b,0] = the scored matches with conf >= edges[b], compared in
+ *              float32; sweep[p,b,1+k] = those of them with err <= thr[k].  A NaN conf is in no bin
+ *   confusion [pairs,4] int64 (with mask, and only then)   over the scored matches, good = err <= thr[0]:
+ *              (mask & good, mask & !good, !mask & good, !mask & !good)
+ * The fixed order of err_sum, as "Per-pair absolute local optimisation" fixes its 28 sums': thread j of 256 adds the scored matches
+ * among j, j + 256, j + 512, ... of the segment in that order, starting from 0.0; the 64 sums of a wave are added by the xor tree
+ * (lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1); the 4 waves' sums are added in wave order starting from 0.0.  Everything else is integer.
+ * Two calls give the same bits in all seven outputs; a change of the walk's width or of this order changes err_sum and is a change
+ * of this definition.
+ * Refused before any launch: a null points / matches_r / T1 / thr / err / status / tally / correct / err_sum; matches_r, pair_off,
+ * counts_in, T1, T0, depth_r_table, err, tally, correct, err_sum, sweep or confusion off 8 bytes, points, conf, norm or size_r off 4;
+ * the segment rules of every per-pair stage (both forms or neither, pairs < 1, cap < 0 or cap >= 2^31 - 1, stride < 1 or
+ * pairs * stride > cap); use_min_conf without conf, a negative or NaN min_conf; swapped not 0 or 1; with depth_r_table an occl_rel
+ * that is not finite and positive; n_thr outside 1 .. 8; a threshold that is not finite and positive or does not ascend; edges
+ * without sweep or sweep without edges, mask without confusion or confusion without mask; edges without conf; B outside 1 .. 64; an
+ * edge that is not finite or does not ascend.  cap == 0 is a valid call. */
+int pats_match_error_by_pair_f64(const float* points, const float* matches_r, const float* conf, const int64_t* pair_off, int64_t stride,
+                                 const int64_t* counts_in, int64_t pairs, int64_t cap, const float* norm, const double* T1,
+                                 const double* T0, int swapped, const int64_t* depth_r_table, double occl_rel, const float* size_r,
+                                 int use_min_conf, float min_conf, const double* thr, int64_t n_thr, const float* edges, int64_t B,
+                                 const uint8_t* mask, double* err, uint8_t* status, int64_t* tally, int64_t* correct, double* err_sum,
+                                 int64_t* sweep, int64_t* confusion, pats_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -329,6 +329,11 @@ SIGNATURES = {
     "pats_absolute_polish_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64,
                                                  c_void_p, c_void_p, c_int, c_f, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    # per-pair match error against depth-and-pose ground truth (csrc/match_error.hip): the lists and conf, the segments, norm, T1, T0,
+    # swapped, the right depth table, occl_rel, size_r, the gate, thr + n_thr and edges + B (host arrays), mask, the seven outputs, stream
+    "pats_match_error_by_pair_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_void_p, ctypes.c_double, c_void_p, c_int, c_f, c_void_p, c_i64, c_void_p,
+                                             c_i64, c_void_p] + [c_void_p] * 7 + [c_void_p]),
     "pats_conv1x1_workspace_bytes": (c_size, []),
     "pats_conv1x1_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size, c_void_p]),

@@ -1257,3 +1257,76 @@ def pose_abs_by_pair(out, cap, swapped=False):
         res = tuple(v.index_select(0, back) for v in res)
     out["pose_abs"] = res + (inlier,)
     return out["pose_abs"]
+
+
+# ---- the match-level yardstick: the lifted matches against depth-and-pose ground truth ----
+_MATCH_ERROR_MASKS = ("verified", "verified_abs", "verified_h")
+
+
+def match_error_by_pair(out, cap, T1, T0=None, thr=(1.0, 3.0, 5.0), norm=None, swapped=False, depths_r=None, occl_rel=0.2, size_r=None,
+                        min_conf=None, edges=None, mask=None):
+    """Device side, after lift_by_pair: every match of the lists that were lifted scored against the ground truth
+    (ops.match_error_by_pair: one launch, no host read) - the lifted point carried through the ground-truth pose into the right image,
+    err = the distance of the matched right point from it in pixels.  T1 [pairs,4,4] float64 (with T0: the two extrinsics, ground
+    truth T1 inv(T0)) as pose_error_by_pair takes them, swapped=True for a data set's extrinsics; norm [pairs,8] - pass what
+    lift_by_pair was given -, size_r [pairs,2] float32 (the right images' content) and depths_r (one float32 [h, w] GPU map or None per
+    pair: the RIGHT images' depth, for the covisibility test within occl_rel) - all in the CALLER's order; for a mixed pack they are
+    permuted to slot order on the device.  thr: ascending pixel thresholds; edges: ascending confidence floors for the sweep and
+    min_conf: the gate (both need a result made with confidence=True).  mask: "verified", "verified_abs" or "verified_h" - that
+    verification's inlier mask, which must have been computed on the lists that were lifted - or None.
+    Stores `match_error` = (err float64, status uint8 - aligned with the lists: slot order, like `lifted` -, tally [pairs,8],
+    correct [pairs,n_thr] int64, err_sum [pairs] float64, sweep [pairs,B,1+n_thr] int64 or None, confusion [pairs,4] int64 or None -
+    in the CALLER's order) and returns it.  No other entry of the result is touched."""
+    fn = "match_error_by_pair"
+    if "lifted" not in out:
+        raise ValueError("%s: run lift_by_pair first" % fn)
+    points, _, _, on = out["lifted"]
+    if mask is not None:
+        if mask not in _MATCH_ERROR_MASKS:
+            raise ValueError("%s: mask must be one of %s or None, got %r" % (fn, ", ".join("\"%s\"" % m for m in _MATCH_ERROR_MASKS), mask))
+        if mask not in out:
+            raise ValueError("%s: mask=\"%s\" needs that verification's result" % (fn, mask))
+        if out[mask + "_on"] != on:
+            raise ValueError("%s: `%s` was computed on=\"%s\", the lift on=\"%s\": the mask is not aligned with the lifted lists" %
+                             (fn, mask, out[mask + "_on"], on))
+    if (min_conf is not None or edges is not None) and "match_conf" not in out:
+        raise ValueError("%s: min_conf and edges need a result made with confidence=True" % fn)
+    if depths_r is not None and (not isinstance(depths_r, (list, tuple)) or len(depths_r) != cap.pairs):
+        raise ValueError("%s: depths_r must be a list of %d maps, one per pair" % (fn, cap.pairs))
+    _, mr, conf, seg = _lists_on(out, cap, on)
+    dev = points.device
+    tab = None if depths_r is None else ops.lift_table(depths_r, device=dev)          # keeps the maps alive until the call returns
+    tab_dev = None if tab is None else tab.dev
+    mixed = "caller_of" in out
+    if mixed:                                                             # caller order -> slot order
+        idx = _caller_of_dev(out, dev)
+        T1, T0, norm, size_r, tab_dev = (None if v is None else v.index_select(0, idx) for v in (T1, T0, norm, size_r, tab_dev))
+    res = ops.match_error_by_pair(points, mr, T1, T0=T0, thr=thr, norm=norm, swapped=swapped, table_r=tab_dev, occl_rel=occl_rel, size_r=size_r,
+                                  conf=conf if (min_conf is not None or edges is not None) else None, min_conf=min_conf, edges=edges,
+                                  mask=None if mask is None else out[mask][3], **seg)
+    if mixed:                                                             # slots back to the caller's order
+        back = _slot_of_dev(out, cap, dev)
+        res = res[:2] + tuple(None if v is None else v.index_select(0, back) for v in res[2:])
+    out["match_error"] = res
+    return res
+
+
+def split_match_error_by_pair(out, cap):
+    """Host side, AFTER the step: per-pair (err [c] float64, status [c] uint8, tally [8], correct [n_thr], err_sum) of a
+    match_error_by_pair result - the rows of the lists that were lifted (the pair's full list for on="all", its top_count top-K rows
+    for on="topk"), views of the device tensors (their values are not read here), in the caller's order.  Raises on the capacity
+    overflows split_by_pair raises on, after the device-to-host copies split_verified_by_pair makes and no further one."""
+    if "match_error" not in out:
+        raise ValueError("split_match_error_by_pair: run match_error_by_pair first")
+    err, status, tally, correct, err_sum = out["match_error"][:5]
+    if out["lifted"][3] == "topk":                    # (lo, hi) per slot in the flat numbering of the lifted lists
+        K = int(out["topk"][0].shape[1])
+        o, counts = _read_topk_summary(out, cap)
+        _overflow_check(o, cap)
+        ext = [(p * K, p * K + counts[p]) for p in range(cap.pairs)]
+    else:
+        o = out["summary"].cpu().tolist()             # the one synchronisation of a batch
+        _overflow_check(o, cap)
+        ext = [(o[p], o[p + 1]) for p in range(cap.pairs)]
+    per_slot = [(err[lo:hi], status[lo:hi]) for lo, hi in ext]
+    return [es + (tally[i], correct[i], err_sum[i]) for i, es in enumerate(_caller_order(out, cap, per_slot))]

@@ -12,6 +12,7 @@
 //                       takes lane l + 32, + 16, ... + 1), the waves in index order by the threshold's thread: the order depends on
 //                       n alone, no atomics.  Dynamic LDS: 8 bytes per slot, 128 KiB at AUC_MAX_N
 #include "common.hpp"
+#include "gt_pose.hpp"
 
 #include <atomic>
 
@@ -33,49 +34,20 @@ __device__ __forceinline__ double perr_angle(double c) {
     return acos(c) * DEG_PER_RAD;
 }
 
-__device__ __forceinline__ bool perr_finite12(const double* __restrict__ T) {         // the upper 3 x 4 of a row-major 4 x 4
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) ok = ok && __builtin_isfinite(T[k]);
-    return ok;
-}
-
 __global__ void __launch_bounds__(PERR_THREADS)
 pose_error_kernel(const double* __restrict__ R_in, const double* __restrict__ t_in, const double* __restrict__ T1, const double* __restrict__ T0,
                   const int64_t* __restrict__ counts, int64_t pairs, int64_t min_matches, double min_gt_t, double* __restrict__ err_R,
                   double* __restrict__ err_t, double* __restrict__ err, int32_t* __restrict__ status) {
     const int64_t p = (int64_t)blockIdx.x * PERR_THREADS + threadIdx.x;
     if (p >= pairs) return;
-    double R[9], t[3], A[12];
+    double R[9], t[3];
     bool pose_ok = true, moves = false;
 #pragma unroll
     for (int k = 0; k < 9; ++k) { R[k] = R_in[p * 9 + k]; pose_ok = pose_ok && __builtin_isfinite(R[k]); }
 #pragma unroll
     for (int k = 0; k < 3; ++k) { t[k] = t_in[p * 3 + k]; pose_ok = pose_ok && __builtin_isfinite(t[k]); moves = moves || t[k] != 0.0; }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) A[k] = T1[p * 16 + k];
-    bool gt_ok = perr_finite12(A);
     double G[9], g[3];
-    if (T0 != nullptr) {                                // R_gt = R1 R0^T, t_gt = t1 - R_gt t0
-        double B[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) B[k] = T0[p * 16 + k];
-        gt_ok = gt_ok && perr_finite12(B);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) G[i * 3 + j] = (A[i * 4] * B[j * 4] + A[i * 4 + 1] * B[j * 4 + 1]) + A[i * 4 + 2] * B[j * 4 + 2];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) g[i] = A[i * 4 + 3] - ((G[i * 3] * B[3] + G[i * 3 + 1] * B[7]) + G[i * 3 + 2] * B[11]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) G[i * 3 + j] = A[i * 4 + j];
-            g[i] = A[i * 4 + 3];
-        }
-    }
+    const bool gt_ok = gt_relative_pose(T1, T0, p, G, g);           // gt_pose.hpp: R_gt = R1 R0^T, t_gt = t1 - R_gt t0
     int st = 0;
     if (counts != nullptr && counts[p] < min_matches) st = 1;
     else if (!pose_ok || !moves) st = 2;

@@ -3368,3 +3368,95 @@ def absolute_polish_by_pair(points, matches_r, models, thr, best=None, rounds=4,
     _check(_L().pats_absolute_polish_by_pair_f32(*lists, *seg, *models, *thr_norm, *gate, *walk, _ptr(out[0]),
                                                  _ptr(out[1]), inl, _ptr(out[3]), _ptr(out[4]), _ptr(out[5]), _stream()), fn)
     return out
+
+
+# ---- the match-level yardstick (csrc/match_error.hip; include/pats_amd.h, "Per-pair match error against ground truth") -----------
+def match_error_by_pair(points, matches_r, T1, T0=None, thr=(1.0, 3.0, 5.0), norm=None, swapped=False, depths_r=None, table_r=None,
+                        occl_rel=0.2, size_r=None, conf=None, min_conf=None, edges=None, mask=None, pair_off=None, stride=None, counts=None,
+                        out=None, pairs=None):
+    """Each pair's matches scored against depth-and-pose ground truth, ON THE DEVICE, one launch, no host read
+    (pats_match_error_by_pair_f64; include/pats_amd.h holds the definition): the lifted left point is carried through the ground-truth
+    pose into the right image, and err is the distance of the matched right point from that projection, in pixels, float64.
+    points [cap,3] float32 = lift_by_pair's, matches_r [cap,2] the right list in un-normalised pixels, the segments (pair_off, or
+    stride + counts) as the lift took them; norm [pairs,8]: what the lift was given (its right half takes the projection back to
+    pixels).  T1 / T0 [pairs,4,4] float64 as pose_error_by_pair takes them; swapped: they are in the reference's (x, y) frame.
+    depths_r: the RIGHT images' depth maps as lift_table takes them - or table_r= a lift_table(...) made earlier (or its [pairs,4]
+    int64 GPU tensor) -: a match must then be covisible, abs(depth - map) <= occl_rel * map at the nearest tap.  size_r [pairs,2]
+    float32: (h, w) of the right image's content, a projection outside it is not scored.  conf [cap] with min_conf: the
+    verification's gate.  thr: 1 .. 8 ascending pixel thresholds (host values).  edges: 1 .. 64 ascending confidence floors (host
+    values; needs conf).  mask [cap] uint8: e.g. a verification's inlier mask.
+    Returns (err [cap] float64 - NaN for a match that is not scored, 0 outside the segments -, status [cap] uint8 - 1 scored, 0 takes
+    no part, 2 no depth, 3 behind the camera, 4 out of view, 5 no right depth, 6 not covisible -, tally [pairs,8] int64 the rows per
+    status, correct [pairs,n_thr] int64 the scored matches within each threshold, err_sum [pairs] float64, sweep [pairs,B,1+n_thr]
+    int64 - per confidence floor the scored matches at or above it and those of them within each threshold; None without edges -,
+    confusion [pairs,4] int64 - (mask & good, mask & !good, !mask & good, !mask & !good) with good = err <= thr[0]; None without
+    mask).  Bit-reproducible.  out: the destinations that are not None, in that order."""
+    fn = "match_error_by_pair"
+    f64 = torch.float64
+    _bp_layout(fn, [(points, "points"), (matches_r, "matches_r"), (T1, "T1"), (T0, "T0"), (norm, "norm"), (size_r, "size_r"), (conf, "conf"),
+                    (mask, "mask"), (pair_off, "pair_off"), (counts, "counts")],
+               {"T1": f64, "T0": f64, "mask": torch.uint8, "pair_off": torch.int64, "counts": torch.int64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if min_conf is not None and conf is None:
+        raise RuntimeError("%s: min_conf needs conf" % fn)
+    if edges is not None and conf is None:
+        raise RuntimeError("%s: edges need conf" % fn)
+    if depths_r is not None and table_r is not None:
+        raise RuntimeError("%s: give depths_r or table_r, not both" % fn)
+    thr = [float(v) for v in thr]
+    edges = None if edges is None else [float(v) for v in edges]
+    n_thr, B = len(thr), 0 if edges is None else len(edges)
+    if not 1 <= n_thr <= 8:
+        raise RuntimeError("%s: thr must hold 1 .. 8 numbers, got %d" % (fn, n_thr))
+    if edges is not None and not 1 <= B <= 64:
+        raise RuntimeError("%s: edges must hold 1 .. 64 numbers, got %d" % (fn, B))
+    X, mr, cap = _bp_matches(fn, points, matches_r, _ABS)
+    _, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    dev = X.device
+    T1 = _dev(T1, "T1", f64)
+    if tuple(T1.shape) != (pairs, 4, 4):
+        raise RuntimeError("%s: T1 must be [pairs,4,4]" % fn)
+    if T0 is not None:
+        T0 = _dev(T0, "T0", f64)
+        if tuple(T0.shape) != (pairs, 4, 4):
+            raise RuntimeError("%s: T0 must be [pairs,4,4]" % fn)
+    conf, norm = _bp_conf_norm(fn, conf, cap, norm, pairs)
+    if size_r is not None:
+        size_r = _dev(size_r, "size_r")
+        if tuple(size_r.shape) != (pairs, 2):
+            raise RuntimeError("%s: size_r must be [pairs,2]" % fn)
+    if mask is not None:
+        mask = _dev(mask, "mask", torch.uint8).reshape(-1)
+        if mask.numel() != cap:
+            raise RuntimeError("%s: mask must be [cap]" % fn)
+    tab = None
+    if depths_r is not None:
+        if len(depths_r) != pairs:
+            raise RuntimeError("%s: depths_r must hold one map (or None) per pair (%d), got %d" % (fn, pairs, len(depths_r)))
+        table_r = lift_table(depths_r, device=dev)
+    if table_r is not None:
+        tab = _dev(table_r.dev if isinstance(table_r, DepthTable) else table_r, "table_r", torch.int64)
+        if tuple(tab.shape) != (pairs, 4) or not tab.is_contiguous():
+            raise RuntimeError("%s: the right depth table must be a contiguous [pairs,4] int64 tensor (%d pairs), got %s" % (fn, pairs, list(tab.shape)))
+    want = [("err", f64, (cap,)), ("status", torch.uint8, (cap,)), ("tally", torch.int64, (pairs, 8)), ("correct", torch.int64, (pairs, n_thr)),
+            ("err_sum", f64, (pairs,))]
+    if edges is not None:
+        want.append(("sweep", torch.int64, (pairs, B, 1 + n_thr)))
+    if mask is not None:
+        want.append(("confusion", torch.int64, (pairs, 4)))
+    out = _bp_outputs(fn, want, out, dev)
+    sweep = out[5] if edges is not None else None
+    confusion = out[-1] if mask is not None else None
+    err, status = out[0], out[1]
+    if cap == 0:
+        X = mr = _bp_placeholder(dev)
+        err = _bp_placeholder(dev, f64)
+        status = _bp_placeholder(dev, torch.uint8)
+        conf = None if conf is None else X
+        mask = None if mask is None else status
+    _check(_L().pats_match_error_by_pair_f64(_ptr(X), _ptr(mr), _ptr(conf), off_p, stride, counts_p, pairs, cap, _ptr(norm), _ptr(T1), _ptr(T0),
+                                             1 if swapped else 0, _ptr(tab), float(occl_rel), _ptr(size_r), 0 if min_conf is None else 1,
+                                             0.0 if min_conf is None else float(min_conf), (ctypes.c_double * n_thr)(*thr), n_thr,
+                                             None if edges is None else (ctypes.c_float * B)(*edges), B, _ptr(mask), _ptr(err), _ptr(status),
+                                             _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(sweep), _ptr(confusion), _stream()), fn)
+    return tuple(out[:5]) + (sweep, confusion)
