@@ -6,7 +6,7 @@
 //
 //   lift        absolute_lift_kernel: one workgroup of ABS_LIFT_THREADS per pair walks the segment; abs_lift_one is the whole
 //               definition of one match (float32, no contraction).  Every row of the segment is stored (a point, or three NaNs), the
-//               rows outside every segment were zeroed before the launch; the count is ballots + popcounts
+//               rows outside every segment were zeroed before the launch; the count is the count fold of epipolar.hpp
 //   hypotheses  absolute_hypotheses_kernel: one thread per pair and sample; epi_draw<3> on the pair's pool, the three points and right
 //               points widened to float64, p3p_solve (p3p.hpp), the kept solutions rounded to float32
 //   score       absolute_score_kernel: grid = pairs x model chunks, ABS_THREADS threads.  The workgroup stages the pair's segment ONCE
@@ -111,7 +111,7 @@ absolute_lift_kernel(const float* __restrict__ matches_, const int64_t* __restri
             x0 = q.x; x1 = q.y;
             if (norm) { x0 = (x0 - nm.c0l) * nm.s0l; x1 = (x1 - nm.c1l) * nm.s1l; }     // one subtract, one multiply
         }
-        cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok));
+        cnt += wave_count(ok);
         if (i < n) {
             const int64_t r = lo + i;
             points[r * 3 + 0] = ok ? x0 * d : nan;
@@ -120,14 +120,9 @@ absolute_lift_kernel(const float* __restrict__ matches_, const int64_t* __restri
             valid[r] = ok ? (uint8_t)1 : (uint8_t)0;
         }
     }
-    if (lane == 0) s_cnt[wave] = cnt;
+    wave_parts_store(s_cnt, wave, lane, cnt);
     wg_barrier();
-    if (tid == 0) {
-        int64_t total = 0;
-#pragma unroll
-        for (int w = 0; w < ABS_LIFT_WAVES; ++w) total += s_cnt[w];
-        lift_count[p] = total;
-    }
+    if (tid == 0) lift_count[p] = (int64_t)wave_parts_total(s_cnt);
 }
 
 // ---- hypotheses ------------------------------------------------------------------------------------------------------------------
@@ -664,19 +659,15 @@ extern "C" int pats_lift_by_pair_f32(const float* matches, const int64_t* pair_o
                                      int64_t cap, const float* norm, const int64_t* depth_table, const float* max_depth, int interp,
                                      int use_max_jump, float max_jump, float* points, uint8_t* valid, int64_t* lift_count,
                                      pats_stream_t stream) {
-    PATS_REQUIRE_PTR("lift_by_pair", matches, 8);
-    PATS_REQUIRE_PTR("lift_by_pair", depth_table, 8);
-    PATS_REQUIRE_PTR("lift_by_pair", points, 4);
-    PATS_REQUIRE(valid, "lift_by_pair: null valid");
-    PATS_REQUIRE_PTR("lift_by_pair", lift_count, 8);
-    PATS_REQUIRE_ALIGNED("lift_by_pair", norm, 4);      // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("lift_by_pair", max_depth, 4);
-    PATS_REQUIRE_ALIGNED("lift_by_pair", pair_off, 8);
-    PATS_REQUIRE_ALIGNED("lift_by_pair", counts_in, 8);
-    int rc = epi_check_segments("lift_by_pair", pair_off, counts_in, stride, pairs, cap);
+    const char* who = "lift_by_pair";
+    int rc = epi_check_args(who, {{"matches", matches, 8}, {"depth_table", depth_table, 8}, {"points", points, 4}, {"valid", valid, 1},
+                                  {"lift_count", lift_count, 8}}, true);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(interp == 0 || interp == 1, "lift_by_pair: interp = %d must be 0 (nearest) or 1 (bilinear)", interp);
-    PATS_REQUIRE(use_max_jump == 0 || use_max_jump == 1, "lift_by_pair: use_max_jump = %d must be 0 or 1", use_max_jump);
+    rc = epi_check_args(who, {{"norm", norm, 4}, {"max_depth", max_depth, 4}, {"pair_off", pair_off, 8}, {"counts_in", counts_in, 8}}, false);
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap)) != PATS_OK) return rc;
+    PATS_REQUIRE(interp == 0 || interp == 1, "%s: interp = %d must be 0 (nearest) or 1 (bilinear)", who, interp);
+    PATS_REQUIRE(use_max_jump == 0 || use_max_jump == 1, "%s: use_max_jump = %d must be 0 or 1", who, use_max_jump);
     hipStream_t st = as_stream(stream);
     // every byte of both per-match outputs is defined: zeros here, the kernel stores every row of every segment
     if ((rc = fill_bytes(points, 0, (size_t)cap * 3 * sizeof(float), st)) != PATS_OK) return rc;

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <initializer_list>
 
 #include "../../include/pats_amd.h"
 
@@ -51,13 +52,25 @@ int* gnn_overflow_flag();
         }                                     \
     } while (0)
 
-// A pointer argument of the entry point `fn` (a string literal): non-null and aligned, or - an optional one, null is aligned -
-// only aligned.  Macros, because the message names the argument.
-#define PATS_REQUIRE_ALIGNED(fn, ptr, align) \
-    PATS_REQUIRE((uintptr_t)(ptr) % (align) == 0, fn ": " #ptr " must be " #align "-byte aligned")
-#define PATS_REQUIRE_PTR(fn, ptr, align)     \
-    PATS_REQUIRE(ptr, fn ": null " #ptr);    \
-    PATS_REQUIRE_ALIGNED(fn, ptr, align)
+// THE pointer check of the per-pair entry points (`who` = the entry's name in its messages): a pointer comes with the name the
+// message gives it and is non-null and aligned (required), or - an optional one: null is aligned - only aligned.  align = 1: any
+// address (a byte mask, a host array)
+struct EpiArg { const char* name; const void* ptr; unsigned align; };
+
+inline int epi_check_arg(const char* who, const EpiArg& a, bool required) {
+    PATS_REQUIRE(a.ptr || !required, "%s: null %s", who, a.name);
+    PATS_REQUIRE((uintptr_t)a.ptr % a.align == 0, "%s: %s must be %u-byte aligned", who, a.name, a.align);
+    return PATS_OK;
+}
+
+// the pointers of `args` in their order, all required or all optional
+inline int epi_check_args(const char* who, std::initializer_list<EpiArg> args, bool required) {
+    for (const EpiArg& a : args) {
+        const int rc = epi_check_arg(who, a, required);
+        if (rc != PATS_OK) return rc;
+    }
+    return PATS_OK;
+}
 
 // ---- wave-level reductions: 4 DPP steps inside each 16-lane row, then two half-swaps -------
 // Every lane ends up with the full 64-lane result (all-reduce).

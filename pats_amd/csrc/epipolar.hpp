@@ -5,8 +5,6 @@
 // optimisations and of the refit source, and the raising of a kernel's dynamic LDS limit (absolute.hip is a caller of these too).
 // include/pats_amd.h states all of it.
 #pragma once
-#include <initializer_list>
-
 #include "common.hpp"
 
 namespace pats {
@@ -55,6 +53,70 @@ __device__ __forceinline__ void epi_load(const float2* __restrict__ ml, const fl
     if (gate) ok = ok && conf[i] >= min_conf;           // false for a NaN confidence
     l1 = a.y; r0 = b.x; r1 = b.y;
     if (ok) l0 = a.x;
+}
+
+// match i of the segment for a walk behind a byte mask (the verification's inliers, a pose's front mask): epi_load without the
+// confidence gate, then THE mask rule - a match whose mask byte is 0 is not used: l0 = NaN.  Returns l0 as it was before the mask
+// (NaN unless the four coordinates are finite), for the one walk that also tests the unmasked match
+__device__ __forceinline__ float epi_load_masked(const float2* __restrict__ ml, const float2* __restrict__ mr, const uint8_t* __restrict__ mask,
+                                                 uint32_t i, uint32_t n, bool has_norm, const EpiNorm& nm, float& l0, float& l1, float& r0,
+                                                 float& r1) {
+    epi_load(ml, mr, nullptr, i, n, has_norm, nm, false, 0.0f, l0, l1, r0, r1);
+    const float unmasked = l0;
+    if (i < n && mask[i] == 0) l0 = __builtin_nanf("");
+    return unmasked;
+}
+
+// ---- the frame change of `swapped` (include/pats_amd.h): P = [[0,1,0],[1,0,0],[0,0,1]] exchanges the first two components ------
+// i -> P i for the index of a 3-vector (P t), k -> P k P for the index of a row-major 3x3 (P R P: rows and columns)
+__device__ __forceinline__ int frame_perm(int i, int swapped) { return swapped ? (i == 2 ? 2 : 1 - i) : i; }
+__device__ __forceinline__ int hom_perm(int k, int swapped) {
+    const int i = k / 3, j = k - 3 * i;
+    return frame_perm(i, swapped) * 3 + frame_perm(j, swapped);
+}
+
+// ---- what a one-workgroup-per-pair walk folds: counts (integers: no order) and float64 sums (a FIXED order) --------------------
+// the lanes of this wave whose pred holds, in every lane
+__device__ __forceinline__ int wave_count(bool pred) { return __builtin_popcountll(__builtin_amdgcn_ballot_w64(pred)); }
+
+// lane 0 of every wave stores the wave's partial - a count, or a sum lane 0 holds - to its slot of s (one partial per wave), or its
+// C partials to columns at .. at + C - 1 of its row of s; behind a wg_barrier() whichever thread needs a total adds the waves in
+// index order with wave_parts_total.  The total is added in the partials' own type: a count of matches fits it because a pair has
+// fewer than 2^31 matches (epi_check_segments)
+template <int WAVES, class T>
+__device__ __forceinline__ void wave_parts_store(T (&s)[WAVES], int wave, int lane, T part) {
+    if (lane == 0) s[wave] = part;
+}
+template <int C, int WAVES, int COLS, class T>
+__device__ __forceinline__ void wave_parts_store(T (&s)[WAVES][COLS], int wave, int lane, const T (&part)[C], int at = 0) {
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) s[wave][at + c] = part[c];
+    }
+}
+template <int WAVES, class T>
+__device__ __forceinline__ T wave_parts_total(const T (&s)[WAVES]) {
+    T total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) total += s[w];
+    return total;
+}
+template <int WAVES, int COLS, class T>
+__device__ __forceinline__ T wave_parts_total(const T (&s)[WAVES][COLS], int c) {
+    T total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) total += s[w][c];
+    return total;
+}
+
+// the float64 sum of a wave by a fixed tree - lane l takes lane l + 32, then + 16, ... + 1: lane 0 holds
+// ((l0 + l32) + (l16 + l48)) + ..., the other lanes hold partial trees.  With the waves added in index order a sum depends on the
+// sizes alone, never on the scheduling.  This is also the xor tree (lane ^ 32, ^ 16, ...) of include/pats_amd.h as lane 0 sees it:
+// every lane that feeds lane 0 holds at each step what the xor form gives it, and a + b is b + a bit for bit
+__device__ __forceinline__ double wave_sum_tree_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
 }
 
 // the winner of pair p among its H models: model h clamped into 0 .. H - 1, h = best[p]
@@ -151,28 +213,8 @@ __device__ __forceinline__ EpiSample epi_sample(const float* __restrict__ ml_, c
     return finite ? EPI_SAMPLE_READY : EPI_SAMPLE_NOT_FINITE;
 }
 
-// ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name) ------
-// PATS_REQUIRE_PTR / PATS_REQUIRE_ALIGNED for a host function that serves several entry points: a pointer comes with the name the
-// message gives it - the first list is matches_l for most entries and points for the absolute ones, the outputs differ from entry to
-// entry - and is non-null and aligned (required), or - an optional one: null is aligned - only aligned.  align = 1: any address (a
-// byte mask)
-struct EpiArg { const char* name; const void* ptr; unsigned align; };
-
-inline int epi_check_arg(const char* who, const EpiArg& a, bool required) {
-    PATS_REQUIRE(a.ptr || !required, "%s: null %s", who, a.name);
-    PATS_REQUIRE((uintptr_t)a.ptr % a.align == 0, "%s: %s must be %u-byte aligned", who, a.name, a.align);
-    return PATS_OK;
-}
-
-// the pointers of `args` in their order, all required or all optional
-inline int epi_check_args(const char* who, std::initializer_list<EpiArg> args, bool required) {
-    for (const EpiArg& a : args) {
-        const int rc = epi_check_arg(who, a, required);
-        if (rc != PATS_OK) return rc;
-    }
-    return PATS_OK;
-}
-
+// ---- host side: what every per-pair stage checks of its arguments before any launch (`what` = the entry point's name); the
+// pointers go through epi_check_args (common.hpp) ------------------------------------------------------------------------------
 // exactly one segment form, and sizes the kernels' 32-bit indices and epi_segment's clamps rely on
 inline int epi_check_segments(const char* what, const int64_t* pair_off, const int64_t* counts_in, int64_t stride, int64_t pairs,
                               int64_t cap) {

@@ -85,20 +85,15 @@ extern "C" int pats_fundamental_refit_by_pair_f64(const int64_t* best_count, con
                                                   double* F_px, double* eig, double* sigma, double* f_refit, void* workspace,
                                                   size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("fundamental_refit_by_pair", best_count, 8);
-    PATS_REQUIRE_PTR("fundamental_refit_by_pair", F, 8);
-    PATS_REQUIRE_PTR("fundamental_refit_by_pair", eig, 8);
-    PATS_REQUIRE_PTR("fundamental_refit_by_pair", sigma, 8);
-    PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", moments, 8);    // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", models, 4);
-    PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", best, 4);
-    PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", norm, 4);
-    PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", F_px, 8);
-    PATS_REQUIRE_ALIGNED("fundamental_refit_by_pair", f_refit, 8);
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "fundamental_refit_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    const int rc = epi_check_refit_source("fundamental_refit_by_pair", moments, models, best, H, swapped);
+    const char* who = "fundamental_refit_by_pair";
+    int rc = epi_check_args(who, {{"best_count", best_count, 8}, {"F", F, 8}, {"eig", eig, 8}, {"sigma", sigma, 8}}, true);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(workspace_bytes >= pats_fundamental_refit_workspace_bytes(pairs), "fundamental_refit_by_pair: workspace too small");
+    rc = epi_check_args(who, {{"moments", moments, 8}, {"models", models, 4}, {"best", best, 4}, {"norm", norm, 4}, {"F_px", F_px, 8},
+                              {"f_refit", f_refit, 8}}, false);
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "%s: pairs = %lld (1 .. 2^31 - 1)", who, (long long)pairs);
+    if ((rc = epi_check_refit_source(who, moments, models, best, H, swapped)) != PATS_OK) return rc;
+    PATS_REQUIRE(workspace_bytes >= pats_fundamental_refit_workspace_bytes(pairs), "%s: workspace too small", who);
     hipLaunchKernelGGL(fundamental_refit_kernel, dim3((unsigned)pairs), dim3(FUND_REFIT_THREADS), 0, as_stream(stream), best_count, moments,
                        models, (int)H, best, norm, swapped, F, F_px, eig, sigma, f_refit);
     return check_launch("fundamental_refit kernel");

@@ -81,18 +81,14 @@ extern "C" int pats_homography_refit_by_pair_f64(const int64_t* best_count, cons
                                                  double* H_px, double* eig, void* workspace, size_t workspace_bytes,
                                                  pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("homography_refit_by_pair", best_count, 8);
-    PATS_REQUIRE_PTR("homography_refit_by_pair", H_out, 8);
-    PATS_REQUIRE_PTR("homography_refit_by_pair", eig, 8);
-    PATS_REQUIRE_ALIGNED("homography_refit_by_pair", moments, 8);     // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("homography_refit_by_pair", models, 4);
-    PATS_REQUIRE_ALIGNED("homography_refit_by_pair", best, 4);
-    PATS_REQUIRE_ALIGNED("homography_refit_by_pair", norm, 4);
-    PATS_REQUIRE_ALIGNED("homography_refit_by_pair", H_px, 8);
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "homography_refit_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    const int rc = epi_check_refit_source("homography_refit_by_pair", moments, models, best, H, swapped);
+    const char* who = "homography_refit_by_pair";
+    int rc = epi_check_args(who, {{"best_count", best_count, 8}, {"H_out", H_out, 8}, {"eig", eig, 8}}, true);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(workspace_bytes >= pats_homography_refit_workspace_bytes(pairs), "homography_refit_by_pair: workspace too small");
+    rc = epi_check_args(who, {{"moments", moments, 8}, {"models", models, 4}, {"best", best, 4}, {"norm", norm, 4}, {"H_px", H_px, 8}}, false);
+    if (rc != PATS_OK) return rc;
+    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "%s: pairs = %lld (1 .. 2^31 - 1)", who, (long long)pairs);
+    if ((rc = epi_check_refit_source(who, moments, models, best, H, swapped)) != PATS_OK) return rc;
+    PATS_REQUIRE(workspace_bytes >= pats_homography_refit_workspace_bytes(pairs), "%s: workspace too small", who);
     hipLaunchKernelGGL(homography_refit_kernel, dim3((unsigned)pairs), dim3(HOM_REFIT_THREADS), 0, as_stream(stream), best_count, moments,
                        models, (int)H, best, norm, swapped, H_out, H_px, eig);
     return check_launch("homography_refit kernel");

@@ -12,7 +12,8 @@
 //           a scored match with a confidence at or above the lowest edge adds one to its bin's row of the LDS histogram
 //           (bins x (1 + n_thr) uint32, integer LDS atomics: the order of arrival does not show)
 //   reduce  the integer tallies over the wave by wave_sum_u32 (lane_reduce.hpp), the waves added by the thread that stores the
-//           tally; the error sum by the FIXED tree the header states: the xor tree over the wave, the waves in index order
+//           tally; the error sum by the FIXED tree the header states - wave_sum_tree_f64 (epipolar.hpp) is its xor tree as lane 0
+//           sees it, and only lane 0's value is used -, the waves in index order
 //   sweep   bins into ">= edge" counts: a suffix sum per column, one thread each
 #include "common.hpp"
 #include "epipolar.hpp"
@@ -105,17 +106,10 @@ __global__ void __launch_bounds__(MERR_THREADS) match_error_kernel(MerrArgs a) {
     {
         double G[9], t[3];
         (void)gt_relative_pose(a.T1, a.T0, p, G, t);    // a ground truth that is not finite gives a Y that is not: status 3
-        const bool sw = a.swapped != 0;                 // P R_gt P, P t_gt: P exchanges the first two components
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int si = i == 2 ? 2 : 1 - i;
+        for (int k = 0; k < 9; ++k) g.R[k] = a.swapped ? G[hom_perm(k, 1)] : G[k];            // P R_gt P, P t_gt
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int sj = j == 2 ? 2 : 1 - j;
-                g.R[i * 3 + j] = sw ? G[si * 3 + sj] : G[i * 3 + j];
-            }
-            g.t[i] = sw ? t[si] : t[i];
-        }
+        for (int i = 0; i < 3; ++i) g.t[i] = a.swapped ? t[frame_perm(i, 1)] : t[i];
     }
     g.has_norm = a.norm != nullptr;
     g.c0 = g.c1 = 0.0; g.s0 = g.s1 = 1.0;
@@ -196,28 +190,17 @@ __global__ void __launch_bounds__(MERR_THREADS) match_error_kernel(MerrArgs a) {
 
     // ---- reduce -----------------------------------------------------------------------------------------------------------------
 #pragma unroll
-    for (int k = 0; k < MERR_COUNTERS; ++k) {
-        const uint32_t w = wave_sum_u32(cnt[k], lane);  // < 2^31 per wave: n < 2^31
-        if (lane == 0) s_cnt[wave][k] = w;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);          // a + b is b + a: every lane ends with the same bits
-    if (lane == 0) s_sum[wave] = sum;
+    for (int k = 0; k < MERR_COUNTERS; ++k) cnt[k] = wave_sum_u32(cnt[k], lane);      // every counter < 2^31 for the pair: n < 2^31
+    wave_parts_store(s_cnt, wave, lane, cnt);
+    wave_parts_store(s_sum, wave, lane, wave_sum_tree_f64(sum));
     wg_barrier();
     if (tid < MERR_COUNTERS) {
-        int64_t total = 0;
-#pragma unroll
-        for (int w = 0; w < MERR_WAVES; ++w) total += (int64_t)s_cnt[w][tid];
+        const int64_t total = (int64_t)wave_parts_total(s_cnt, tid);
         if (tid < MERR_TALLY) a.tally[p * MERR_TALLY + tid] = total;             // slot 7 was never counted: zero
         else if (tid < MERR_TALLY + MERR_MAX_THR) { if (tid - MERR_TALLY < n_thr) a.correct[p * n_thr + (tid - MERR_TALLY)] = total; }
         else if (a.confusion != nullptr) a.confusion[p * 4 + (tid - MERR_TALLY - MERR_MAX_THR)] = total;
     }
-    if (tid == 0) {
-        double total = 0.0;
-#pragma unroll
-        for (int w = 0; w < MERR_WAVES; ++w) total += s_sum[w];
-        a.err_sum[p] = total;
-    }
+    if (tid == 0) a.err_sum[p] = wave_parts_total(s_sum);
 
     // ---- sweep: bin b of column c counts conf in [edges[b], edges[b + 1]); the suffix sum counts conf >= edges[b] -----------------
     if (sweep && tid <= n_thr) {                        // the histogram is complete: the barrier above follows the walk

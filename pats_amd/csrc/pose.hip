@@ -9,9 +9,9 @@
 //           all indices static (refit.hpp, shared with polish.hip): the eigenvector, G^T G of it as a 3x3 G, a 3x3 Jacobi for the
 //           right singular vectors, u_i = G v_i (Gram-Schmidt), u_3 = u_1 x u_2, v_3 = v_1 x v_2 (det U = det V = +1 by
 //           construction), E, R1, R2, u.  They go to LDS in float64 and float32.
-//   vote    the workgroup walks the segment with epi_load; a match that is not used carries a NaN x_l.  pose_front4 gives the four
-//           verdicts of a match as bits (R1 and R2 share everything up to the two signs); ballots + popcounts per wave, the waves
-//           added in LDS by thread 0 (integer adds: no order), which picks the candidate and writes the per-pair outputs.
+//   vote    the workgroup walks the segment with epi_load_masked; pose_front4 gives the four verdicts of a match as bits (R1 and R2
+//           share everything up to the two signs); the count fold of epipolar.hpp, thread 0 picks the candidate and writes the
+//           per-pair outputs, R, t and E in the frame `swapped` asks for (hom_perm, frame_perm, hom_write).
 //   mask    a second walk with the same device function writes the chosen candidate's bit: front.sum() == front_count exactly.
 #include "common.hpp"
 #include "epipolar.hpp"
@@ -109,18 +109,13 @@ epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
 #pragma unroll
         for (int k = 0; k < 3; ++k) uf[k] = sUf[k];
         for (uint32_t i0 = 0; i0 < n; i0 += POSE_THREADS) {
-            const uint32_t i = i0 + tid;
             float l0, l1, r0, r1;
-            epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
-            if (i < n && inl[i] == 0) l0 = __builtin_nanf("");          // not an inlier of the verification: not used
+            epi_load_masked(ml, mr, inl, i0 + tid, n, norm != nullptr, nm, l0, l1, r0, r1);
             const unsigned bits = pose_front4(Rf, uf, l0, l1, r0, r1);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) cnt[c] += __builtin_popcountll(__builtin_amdgcn_ballot_w64((bits >> c) & 1u));
+            for (int c = 0; c < 4; ++c) cnt[c] += wave_count((bits >> c) & 1u);
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) s_cnt[wave][c] = cnt[c];
-        }
+        wave_parts_store(s_cnt, wave, lane, cnt);
     }
     wg_barrier();
     if (tid == 0) {
@@ -128,10 +123,7 @@ epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
         int ch = 0, top = 0;
         if (ok) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                for (int w = 0; w < POSE_WAVES; ++w) tot[c] += s_cnt[w][c];
-            }
+            for (int c = 0; c < 4; ++c) tot[c] = wave_parts_total(s_cnt, c);
             top = tot[0];
 #pragma unroll
             for (int c = 1; c < 4; ++c)
@@ -145,27 +137,16 @@ epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
     }
     wg_barrier();
     const int ch = s_choice;
-    if (tid < 9) {                                      // the pose in the reference's frame: rows and columns 0 and 1 exchanged
+    if (tid < 9) {                                      // the pose in the reference's frame: P R P, P t
         const int i = tid / 3, j = tid - 3 * i;
-        const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
-        R_out[p * 9 + tid] = ok ? sR[ch & 1][si * 3 + sj] : (i == j ? 1.0 : 0.0);
-        if (j == 0) t_out[p * 3 + i] = ok ? ((ch & 2) ? -sU[si] : sU[si]) : 0.0;
+        R_out[p * 9 + tid] = ok ? sR[ch & 1][hom_perm(tid, swapped)] : (i == j ? 1.0 : 0.0);
+        if (j == 0) t_out[p * 3 + i] = ok ? ((ch & 2) ? -sU[frame_perm(i, swapped)] : sU[frame_perm(i, swapped)]) : 0.0;
     }
     if (tid == 64) {                                    // E, its sign judged on the values written
-        double big = -1.0, at = 0.0;
-        for (int k = 0; k < 9; ++k) {
-            const int i = k / 3, j = k - 3 * i;
-            const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
-            const double v = ok ? sE[si * 3 + sj] : 0.0;
-            if (__builtin_fabs(v) > big) { big = __builtin_fabs(v); at = v; }
-        }
-        const bool flip = at < 0.0;
-        for (int k = 0; k < 9; ++k) {
-            const int i = k / 3, j = k - 3 * i;
-            const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
-            const double v = ok ? sE[si * 3 + sj] : 0.0;
-            E_out[p * 9 + k] = flip ? -v : v;
-        }
+        double E[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) E[k] = ok ? sE[k] : 0.0;
+        hom_write(E, ok, swapped, E_out + p * 9);
     }
 
     // ---- mask -------------------------------------------------------------------------------------------------------------------
@@ -173,8 +154,7 @@ epipolar_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ mr
     for (uint32_t i0 = 0; i0 < n; i0 += POSE_THREADS) {
         const uint32_t i = i0 + tid;
         float l0, l1, r0, r1;
-        epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
-        if (i < n && inl[i] == 0) l0 = __builtin_nanf("");
+        epi_load_masked(ml, mr, inl, i, n, norm != nullptr, nm, l0, l1, r0, r1);
         const unsigned bits = pose_front4(Rf, uf, l0, l1, r0, r1);
         if (i < n) front[lo + i] = (uint8_t)((bits >> ch) & 1u);
     }
@@ -196,28 +176,17 @@ extern "C" int pats_epipolar_pose_by_pair_f64(const float* matches_l, const floa
                                               int32_t* front_counts, int32_t* choice, int64_t* front_count, uint8_t* front,
                                               double* e_refit, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", matches_l, 8);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", matches_r, 8);
-    PATS_REQUIRE(inlier, "epipolar_pose_by_pair: null inlier");
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", best_count, 8);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", E, 8);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", R, 8);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", t, 8);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", front_counts, 4);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", choice, 4);
-    PATS_REQUIRE_PTR("epipolar_pose_by_pair", front_count, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", moments, 8);     // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", models, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", best, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", norm, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", pair_off, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", counts_in, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_pose_by_pair", e_refit, 8);
-    int rc = epi_check_segments("epipolar_pose_by_pair", pair_off, counts_in, stride, pairs, cap);
+    const char* who = "epipolar_pose_by_pair";
+    int rc = epi_check_args(who, {{"matches_l", matches_l, 8}, {"matches_r", matches_r, 8}, {"inlier", inlier, 1}, {"best_count", best_count, 8},
+                                  {"E", E, 8}, {"R", R, 8}, {"t", t, 8}, {"front_counts", front_counts, 4}, {"choice", choice, 4},
+                                  {"front_count", front_count, 8}}, true);
     if (rc != PATS_OK) return rc;
-    rc = epi_check_refit_source("epipolar_pose_by_pair", moments, models, best, H, swapped);
+    rc = epi_check_args(who, {{"moments", moments, 8}, {"models", models, 4}, {"best", best, 4}, {"norm", norm, 4}, {"pair_off", pair_off, 8},
+                              {"counts_in", counts_in, 8}, {"e_refit", e_refit, 8}}, false);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(workspace_bytes >= pats_epipolar_pose_workspace_bytes(pairs, cap), "epipolar_pose_by_pair: workspace too small");
+    if ((rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap)) != PATS_OK) return rc;
+    if ((rc = epi_check_refit_source(who, moments, models, best, H, swapped)) != PATS_OK) return rc;
+    PATS_REQUIRE(workspace_bytes >= pats_epipolar_pose_workspace_bytes(pairs, cap), "%s: workspace too small", who);
     hipStream_t st = as_stream(stream);
     if (front) {
         rc = fill_bytes(front, 0, (size_t)cap, st);

@@ -8,10 +8,11 @@
 //   pose_auc_kernel     ONE workgroup of AUC_THREADS threads: the errors go to LDS as order-preserving 64-bit keys (a NaN as +inf's),
 //                       padded to the next power of two with the largest key and sorted ascending by a bitonic network (equal keys
 //                       are equal values: any network gives the same list); a thread per threshold finds k by bisection; the
-//                       trapezoids are added per thread with a stride of AUC_THREADS, the lanes of a wave by a fixed tree (lane l
-//                       takes lane l + 32, + 16, ... + 1), the waves in index order by the threshold's thread: the order depends on
-//                       n alone, no atomics.  Dynamic LDS: 8 bytes per slot, 128 KiB at AUC_MAX_N
+//                       trapezoids are added per thread with a stride of AUC_THREADS, the lanes of a wave by wave_sum_tree_f64
+//                       (epipolar.hpp), the waves in index order by the threshold's thread: the order depends on n alone, no
+//                       atomics.  Dynamic LDS: 8 bytes per slot, 128 KiB at AUC_MAX_N
 #include "common.hpp"
+#include "epipolar.hpp"
 #include "gt_pose.hpp"
 
 #include <atomic>
@@ -144,16 +145,13 @@ __global__ void __launch_bounds__(AUC_THREADS) pose_auc_kernel(AucArgs g) {
             const double x0 = i == 0 ? 0.0 : auc_value(auc_keys[i - 1]), x1 = auc_value(auc_keys[i]);
             sum += ((x1 - x0) * ((double)i * inv + (double)(i + 1) * inv)) * 0.5;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);        // lane 0: the wave's sum, a fixed tree
+        sum = wave_sum_tree_f64(sum);
         if (lane == 0) s_part[wave][j] = sum;
     }
     wg_barrier();
     if (tid < g.n_thr) {
         const int k = s_k[tid];
-        double area = 0.0;
-#pragma unroll
-        for (int w = 0; w < AUC_WAVES; ++w) area += s_part[w][tid];
+        double area = wave_parts_total(s_part, tid);
         const double xk = k == 0 ? 0.0 : auc_value(auc_keys[k - 1]);
         area += (g.thr[tid] - xk) * ((double)k * inv);
         g.auc[tid] = area / g.thr[tid];
@@ -184,18 +182,14 @@ using namespace pats;
 extern "C" int pats_pose_error_by_pair_f64(const double* R, const double* t, const double* T1, const double* T0, const int64_t* counts,
                                            int64_t pairs, int64_t min_matches, double min_gt_t, double* err_R, double* err_t, double* err,
                                            int32_t* status, pats_stream_t stream) {
-    PATS_REQUIRE_PTR("pose_error_by_pair", R, 8);
-    PATS_REQUIRE_PTR("pose_error_by_pair", t, 8);
-    PATS_REQUIRE_PTR("pose_error_by_pair", T1, 8);
-    PATS_REQUIRE_PTR("pose_error_by_pair", err_R, 8);
-    PATS_REQUIRE_PTR("pose_error_by_pair", err_t, 8);
-    PATS_REQUIRE_PTR("pose_error_by_pair", err, 8);
-    PATS_REQUIRE_PTR("pose_error_by_pair", status, 4);
-    PATS_REQUIRE_ALIGNED("pose_error_by_pair", T0, 8);                          // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("pose_error_by_pair", counts, 8);
-    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "pose_error_by_pair: pairs = %lld (1 .. 2^31 - 1)", (long long)pairs);
-    PATS_REQUIRE(min_matches >= 0, "pose_error_by_pair: min_matches = %lld must not be negative", (long long)min_matches);
-    PATS_REQUIRE(min_gt_t >= 0.0, "pose_error_by_pair: min_gt_t = %g must be a non-negative number", min_gt_t);       // false for a NaN
+    const char* who = "pose_error_by_pair";
+    int rc = epi_check_args(who, {{"R", R, 8}, {"t", t, 8}, {"T1", T1, 8}, {"err_R", err_R, 8}, {"err_t", err_t, 8}, {"err", err, 8},
+                                  {"status", status, 4}}, true);
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_args(who, {{"T0", T0, 8}, {"counts", counts, 8}}, false)) != PATS_OK) return rc;
+    PATS_REQUIRE(pairs >= 1 && pairs <= 0x7fffffff, "%s: pairs = %lld (1 .. 2^31 - 1)", who, (long long)pairs);
+    PATS_REQUIRE(min_matches >= 0, "%s: min_matches = %lld must not be negative", who, (long long)min_matches);
+    PATS_REQUIRE(min_gt_t >= 0.0, "%s: min_gt_t = %g must be a non-negative number", who, min_gt_t);                   // false for a NaN
     hipLaunchKernelGGL(pose_error_kernel, dim3((unsigned)ceil_div(pairs, PERR_THREADS)), dim3(PERR_THREADS), 0, as_stream(stream), R, t, T1,
                        T0, counts, pairs, min_matches, min_gt_t, err_R, err_t, err, status);
     return check_launch("pose_error kernel");
@@ -205,11 +199,9 @@ extern "C" int64_t pats_pose_auc_max_n(void) { return AUC_MAX_N; }
 
 extern "C" int pats_pose_auc_f64(const double* errors, int64_t n, const double* thresholds, int64_t n_thr, double* auc, int64_t* below,
                                  double* sorted, pats_stream_t stream) {
-    PATS_REQUIRE_PTR("pose_auc", errors, 8);
-    PATS_REQUIRE(thresholds, "pose_auc: null thresholds");
-    PATS_REQUIRE_PTR("pose_auc", auc, 8);
-    PATS_REQUIRE_PTR("pose_auc", below, 8);
-    PATS_REQUIRE_ALIGNED("pose_auc", sorted, 8);                                // optional
+    int rc = epi_check_args("pose_auc", {{"errors", errors, 8}, {"thresholds", thresholds, 1}, {"auc", auc, 8}, {"below", below, 8}}, true);
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_arg("pose_auc", {"sorted", sorted, 8}, false)) != PATS_OK) return rc;
     PATS_REQUIRE(n >= 0 && n <= AUC_MAX_N, "pose_auc: n = %lld (0 .. max_n = %d)", (long long)n, AUC_MAX_N);
     PATS_REQUIRE(n_thr >= 1 && n_thr <= AUC_MAX_THR, "pose_auc: n_thr = %lld (1 .. %d)", (long long)n_thr, AUC_MAX_THR);
     AucArgs g{};

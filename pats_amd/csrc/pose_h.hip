@@ -6,9 +6,9 @@
 //   solve   float64.  The 9x9 moments and the accumulated rotations live in LDS; wave 0 runs the round-robin cyclic Jacobi of
 //           jacobi9.hpp.  Thread 0 then holds the rest (refit.hpp: hom_spectrum, hom_rotation, hom_decompose) and hands G', V and the
 //           two ratios over in LDS: the sign of G' is a vote of the workgroup that stands between the spectrum and the candidates.
-//   walks   three over the segment with epi_load, each a ballot + popcount per wave, the waves added in LDS by thread 0 (integer
-//           adds: no order): the sign vote, the visibility and support counts, the mask.  hpose_side is THE visibility test: the counts
-//           and the mask both call it, so front.sum() == front_count exactly.
+//   walks   three over the segment with epi_load_masked, the first two closed by the count fold of epipolar.hpp: the sign vote, the
+//           visibility and support counts, the mask.  hpose_side is THE visibility test: the counts and the mask both call it, so
+//           front.sum() == front_count exactly.  The outputs go out in the frame `swapped` asks for (hom_perm, frame_perm, hom_write).
 #include "common.hpp"
 #include "epipolar.hpp"
 #include "jacobi9.hpp"
@@ -80,34 +80,25 @@ homography_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ 
         float g[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) g[k] = sGf[k];
-        int used = 0, pos = 0, neg = 0;
+        int cnt[3] = {0, 0, 0};                         // used, q > 0, q < 0
         for (uint32_t i0 = 0; i0 < n; i0 += HPOSE_THREADS) {
-            const uint32_t i = i0 + tid;
             float l0, l1, r0, r1;
-            epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
-            if (i < n && inl[i] == 0) l0 = __builtin_nanf("");          // not an inlier of the verification: not used
+            epi_load_masked(ml, mr, inl, i0 + tid, n, norm != nullptr, nm, l0, l1, r0, r1);
             const float a0 = __builtin_fmaf(g[0], l0, __builtin_fmaf(g[1], l1, g[2]));
             const float a1 = __builtin_fmaf(g[3], l0, __builtin_fmaf(g[4], l1, g[5]));
             const float a2 = __builtin_fmaf(g[6], l0, __builtin_fmaf(g[7], l1, g[8]));
             const float q = __builtin_fmaf(r0, a0, __builtin_fmaf(r1, a1, a2));
-            used += __builtin_popcountll(__builtin_amdgcn_ballot_w64(l0 == l0));
-            pos += __builtin_popcountll(__builtin_amdgcn_ballot_w64(q > 0.0f));
-            neg += __builtin_popcountll(__builtin_amdgcn_ballot_w64(q < 0.0f));
+            cnt[0] += wave_count(l0 == l0);
+            cnt[1] += wave_count(q > 0.0f);
+            cnt[2] += wave_count(q < 0.0f);
         }
-        if (lane == 0) { s_cnt[wave][0] = used; s_cnt[wave][1] = pos; s_cnt[wave][2] = neg; }
+        wave_parts_store(s_cnt, wave, lane, cnt);
     }
     wg_barrier();
 
     // ---- the candidates ----------------------------------------------------------------------------------------------------------------
-    int used_total = 0;
-    if (ok) {
-#pragma unroll
-        for (int w = 0; w < HPOSE_WAVES; ++w) used_total += s_cnt[w][0];
-    }
     if (tid == 0 && ok) {
-        int pos = 0, neg = 0;
-#pragma unroll
-        for (int w = 0; w < HPOSE_WAVES; ++w) { pos += s_cnt[w][1]; neg += s_cnt[w][2]; }
+        const int pos = wave_parts_total(s_cnt, 1), neg = wave_parts_total(s_cnt, 2);
         double Gp[9], V[3][3];
 #pragma unroll
         for (int k = 0; k < 9; ++k) { Gp[k] = neg > pos ? -sG[k] : sG[k]; V[k / 3][k % 3] = sW[k / 3][k % 3]; }
@@ -160,27 +151,21 @@ homography_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ 
         const float t2 = th * th;
         int cnt[6] = {0, 0, 0, 0, 0, 0};
         for (uint32_t i0 = 0; i0 < n; i0 += HPOSE_THREADS) {
-            const uint32_t i = i0 + tid;
-            float l0, l1, r0, r1;
-            epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
-            const float f0 = l0;                        // NaN unless the four coordinates are finite
-            if (i < n && inl[i] == 0) l0 = __builtin_nanf("");
+            float l0, l1, r0, r1;                       // the support is every finite match's: f0 is l0 before the mask
+            const float f0 = epi_load_masked(ml, mr, inl, i0 + tid, n, norm != nullptr, nm, l0, l1, r0, r1);
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const float d = hpose_side(nf[c], l0, l1);
-                cnt[c] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(d > 0.0f));
-                cnt[2 + c] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(d < 0.0f));
+                cnt[c] += wave_count(d > 0.0f);
+                cnt[2 + c] += wave_count(d < 0.0f);
                 if (support) {                          // workgroup-uniform
                     v2f s, lim, w;
                     Epipolar::test2(ef[c], t2, pk_splat(f0), pk_splat(l1), pk_splat(r0), pk_splat(r1), s, lim, w);
-                    cnt[4 + c] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(w.x > 0.0f && s.x <= lim.x));
+                    cnt[4 + c] += wave_count(w.x > 0.0f && s.x <= lim.x);
                 }
             }
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) s_cnt[wave][c + 2] = cnt[c];    // [wave][0] keeps the used count
-        }
+        wave_parts_store(s_cnt, wave, lane, cnt, 2);   // column 0 keeps the used count
     }
     wg_barrier();
     if (tid == 0) {
@@ -188,18 +173,13 @@ homography_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ 
         int ch = 0;
         if (status == 1) {
 #pragma unroll
-            for (int w = 0; w < HPOSE_WAVES; ++w) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) vis[c] += s_cnt[w][2 + c];
-                sup[0] += s_cnt[w][6]; sup[1] += s_cnt[w][7];
-            }
-            sup[2] = sup[0]; sup[3] = sup[1];
+            for (int c = 0; c < 4; ++c) { vis[c] = wave_parts_total(s_cnt, 2 + c); sup[c] = wave_parts_total(s_cnt, 6 + (c & 1)); }
 #pragma unroll
             for (int c = 1; c < 4; ++c)
                 if (vis[c] > vis[ch] || (vis[c] == vis[ch] && sup[c] > sup[ch])) ch = c;
         } else if (status == 2) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) vis[c] = used_total;
+            for (int c = 0; c < 4; ++c) vis[c] = wave_parts_total(s_cnt, 0);
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) { vis_out[p * 4 + c] = vis[c]; sup_out[p * 4 + c] = sup[c]; }
@@ -211,10 +191,9 @@ homography_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ 
     }
     wg_barrier();
     const int ch = s_choice;
-    if (tid < 9) {                                      // the pose in the reference's frame: rows and columns 0 and 1 exchanged
+    if (tid < 9) {                                      // the pose in the reference's frame: P R P, P t, P n
         const int i = tid / 3, j = tid - 3 * i;
-        const int si = swapped ? (i == 2 ? 2 : 1 - i) : i;
-        const int k = hom_perm(tid, swapped);
+        const int si = frame_perm(i, swapped), k = hom_perm(tid, swapped);
         R_out[p * 9 + tid] = ok ? sR[ch & 1][k] : (i == j ? 1.0 : 0.0);
         if (j == 0) {
             double tv = 0.0, nv = 0.0;
@@ -251,8 +230,7 @@ homography_pose_kernel(const float* __restrict__ ml_, const float* __restrict__ 
     for (uint32_t i0 = 0; i0 < n; i0 += HPOSE_THREADS) {
         const uint32_t i = i0 + tid;
         float l0, l1, r0, r1;
-        epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
-        if (i < n && inl[i] == 0) l0 = __builtin_nanf("");
+        epi_load_masked(ml, mr, inl, i, n, norm != nullptr, nm, l0, l1, r0, r1);
         bool bit = l0 == l0;                            // rotation only: every used match
         if (status == 1) {
             const float d = hpose_side(nf[ch & 1], l0, l1);
@@ -320,38 +298,21 @@ extern "C" int pats_homography_pose_by_pair_f64(const float* matches_l, const fl
                                                 double* cand_n, uint8_t* front, void* workspace, size_t workspace_bytes,
                                                 pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("homography_pose_by_pair", matches_l, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", matches_r, 8);
-    PATS_REQUIRE(inlier, "homography_pose_by_pair: null inlier");
-    PATS_REQUIRE_PTR("homography_pose_by_pair", best_count, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", E, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", R, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", t, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", n, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", baseline, 8);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", vis, 4);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", sup, 4);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", choice, 4);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", status, 4);
-    PATS_REQUIRE_PTR("homography_pose_by_pair", front_count, 8);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", moments, 8);     // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", models, 4);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", best, 4);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", norm, 4);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", thr, 4);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", pair_off, 8);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", counts_in, 8);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", cand_R, 8);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", cand_t, 8);
-    PATS_REQUIRE_ALIGNED("homography_pose_by_pair", cand_n, 8);
+    const char* who = "homography_pose_by_pair";
+    int rc = epi_check_args(who, {{"matches_l", matches_l, 8}, {"matches_r", matches_r, 8}, {"inlier", inlier, 1}, {"best_count", best_count, 8},
+                                  {"E", E, 8}, {"R", R, 8}, {"t", t, 8}, {"n", n, 8}, {"baseline", baseline, 8}, {"vis", vis, 4}, {"sup", sup, 4},
+                                  {"choice", choice, 4}, {"status", status, 4}, {"front_count", front_count, 8}}, true);
+    if (rc != PATS_OK) return rc;
+    rc = epi_check_args(who, {{"moments", moments, 8}, {"models", models, 4}, {"best", best, 4}, {"norm", norm, 4}, {"thr", thr, 4},
+                              {"pair_off", pair_off, 8}, {"counts_in", counts_in, 8}, {"cand_R", cand_R, 8}, {"cand_t", cand_t, 8},
+                              {"cand_n", cand_n, 8}}, false);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE((cand_R != nullptr) == (cand_t != nullptr) && (cand_R != nullptr) == (cand_n != nullptr),
-                 "homography_pose_by_pair: cand_R, cand_t and cand_n must be given together");
-    int rc = epi_check_segments("homography_pose_by_pair", pair_off, counts_in, stride, pairs, cap);
-    if (rc != PATS_OK) return rc;
-    rc = epi_check_refit_source("homography_pose_by_pair", moments, models, best, H, swapped);
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(min_baseline >= 0.0, "homography_pose_by_pair: min_baseline = %g must be a number >= 0", min_baseline);     // false for a NaN
-    PATS_REQUIRE(workspace_bytes >= pats_homography_pose_workspace_bytes(pairs, cap), "homography_pose_by_pair: workspace too small");
+                 "%s: cand_R, cand_t and cand_n must be given together", who);
+    if ((rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap)) != PATS_OK) return rc;
+    if ((rc = epi_check_refit_source(who, moments, models, best, H, swapped)) != PATS_OK) return rc;
+    PATS_REQUIRE(min_baseline >= 0.0, "%s: min_baseline = %g must be a number >= 0", who, min_baseline);     // false for a NaN
+    PATS_REQUIRE(workspace_bytes >= pats_homography_pose_workspace_bytes(pairs, cap), "%s: workspace too small", who);
     hipStream_t st = as_stream(stream);
     if (front) {
         rc = fill_bytes(front, 0, (size_t)cap, st);
@@ -376,32 +337,17 @@ extern "C" int pats_pose_select_by_pair(const int64_t* pair_off, int64_t stride,
                                         double* R, double* t, double* E, int64_t* front_count, int32_t* branch, uint8_t* inlier_sel,
                                         uint8_t* front_sel, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("pose_select_by_pair", R_e, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", t_e, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", E_e, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", front_count_e, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", best_count_e, 8);
-    PATS_REQUIRE(inlier_e, "pose_select_by_pair: null inlier_e");
-    PATS_REQUIRE_PTR("pose_select_by_pair", R_h, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", t_h, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", E_h, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", front_count_h, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", status_h, 4);
-    PATS_REQUIRE_PTR("pose_select_by_pair", best_count_h, 8);
-    PATS_REQUIRE(inlier_h, "pose_select_by_pair: null inlier_h");
-    PATS_REQUIRE_PTR("pose_select_by_pair", ratio, 4);
-    PATS_REQUIRE_PTR("pose_select_by_pair", R, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", t, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", E, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", front_count, 8);
-    PATS_REQUIRE_PTR("pose_select_by_pair", branch, 4);
-    PATS_REQUIRE(inlier_sel, "pose_select_by_pair: null inlier_sel");
-    PATS_REQUIRE_ALIGNED("pose_select_by_pair", pair_off, 8);
-    PATS_REQUIRE_ALIGNED("pose_select_by_pair", counts_in, 8);
-    PATS_REQUIRE(!front_sel || (front_e && front_h), "pose_select_by_pair: front_sel needs front_e and front_h");
-    const int rc = epi_check_segments("pose_select_by_pair", pair_off, counts_in, stride, pairs, cap);
+    const char* who = "pose_select_by_pair";
+    int rc = epi_check_args(who, {{"R_e", R_e, 8}, {"t_e", t_e, 8}, {"E_e", E_e, 8}, {"front_count_e", front_count_e, 8},
+                                  {"best_count_e", best_count_e, 8}, {"inlier_e", inlier_e, 1}, {"R_h", R_h, 8}, {"t_h", t_h, 8}, {"E_h", E_h, 8},
+                                  {"front_count_h", front_count_h, 8}, {"status_h", status_h, 4}, {"best_count_h", best_count_h, 8},
+                                  {"inlier_h", inlier_h, 1}, {"ratio", ratio, 4}, {"R", R, 8}, {"t", t, 8}, {"E", E, 8},
+                                  {"front_count", front_count, 8}, {"branch", branch, 4}, {"inlier_sel", inlier_sel, 1}}, true);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(workspace_bytes >= pats_pose_select_workspace_bytes(pairs, cap), "pose_select_by_pair: workspace too small");
+    if ((rc = epi_check_args(who, {{"pair_off", pair_off, 8}, {"counts_in", counts_in, 8}}, false)) != PATS_OK) return rc;
+    PATS_REQUIRE(!front_sel || (front_e && front_h), "%s: front_sel needs front_e and front_h", who);
+    if ((rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap)) != PATS_OK) return rc;
+    PATS_REQUIRE(workspace_bytes >= pats_pose_select_workspace_bytes(pairs, cap), "%s: workspace too small", who);
     hipStream_t st = as_stream(stream);
     int rf = fill_bytes(inlier_sel, 0, (size_t)cap, st);
     if (rf != PATS_OK) return rf;

@@ -119,10 +119,9 @@ extern "C" int64_t pats_prepare_images_max_side(void) { return PREP_MAX_SIDE; }
 extern "C" int pats_prepare_images_u8(const pats_prepare_image_t* images_host, const pats_prepare_image_t* images, int64_t n_img,
                                       void* left, int64_t left_elems, void* right, int64_t right_elems, pats_img_dtype_t dtype,
                                       pats_stream_t stream) {
-    PATS_REQUIRE(images_host, "prepare_images: null images_host");
-    PATS_REQUIRE_PTR("prepare_images", images, 8);
-    PATS_REQUIRE_PTR("prepare_images", left, 16);
-    PATS_REQUIRE_PTR("prepare_images", right, 16);
+    const int rc = epi_check_args("prepare_images", {{"images_host", images_host, 1}, {"images", images, 8}, {"left", left, 16},
+                                                     {"right", right, 16}}, true);
+    if (rc != PATS_OK) return rc;
     PATS_REQUIRE(dtype == PATS_IMG_F32 || dtype == PATS_IMG_F16 || dtype == PATS_IMG_BF16 || dtype == PATS_IMG_U8,
                  "prepare_images: unknown output dtype %d", (int)dtype);
     PATS_REQUIRE(n_img >= 1 && n_img <= 65535, "prepare_images: n_img = %lld (1 .. 65535)", (long long)n_img);

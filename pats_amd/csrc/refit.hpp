@@ -290,14 +290,7 @@ __device__ __forceinline__ bool fund_from_moments(const double (&sA)[9][9], cons
     return ok && fund_project(e, F, sig);
 }
 
-// k -> P k for the permutation P = [[0,1,0],[1,0,0],[0,0,1]] applied to rows and columns of a row-major 3x3
-__device__ __forceinline__ int hom_perm(int k, int swapped) {
-    const int i = k / 3, j = k - 3 * i;
-    const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
-    return si * 3 + sj;
-}
-
-// out[k] = +-v[P k]: the permutation, then the sign rule judged on the values written (the lowest index among equals)
+// out[k] = +-v[P k P]: the frame change (hom_perm, epipolar.hpp), then the sign rule judged on the values written (the lowest index among equals)
 __device__ __forceinline__ void hom_write(const double (&v)[9], bool ok, int swapped, double* __restrict__ out) {
     double big = -1.0, at = 0.0;
     for (int k = 0; k < 9; ++k) {

@@ -189,7 +189,9 @@ extern "C" int pats_topk_by_pair_f32(const float* matches_l, const float* matche
                                      float* top_r, float* top_conf, int32_t* top_idx, int64_t* top_count, void* workspace,
                                      size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_TOPK_REQUIRE_ARGS("topk_by_pair", pats_topk_by_pair_workspace_bytes(pairs, K));
+    const int rc = topk_check_args("topk_by_pair", matches_l, matches_r, conf, pair_off, pairs, cap, K, use_min_conf, min_conf, top_l, top_r,
+                                   top_conf, top_idx, top_count, workspace_bytes, pats_topk_by_pair_workspace_bytes(pairs, K));
+    if (rc != PATS_OK) return rc;
     TopkArgs g{matches_l, matches_r, conf, pair_off, cap, (int)K, use_min_conf ? topk_key(__builtin_bit_cast(uint32_t, min_conf)) : 0u,
                top_l, top_r, top_conf, top_idx, top_count};
     hipLaunchKernelGGL(topk_by_pair_kernel, dim3((unsigned)pairs), dim3(TOPK_THREADS), 0, as_stream(stream), g);

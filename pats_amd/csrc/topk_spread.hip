@@ -168,8 +168,10 @@ extern "C" int pats_topk_spread_by_pair_f32(const float* matches_l, const float*
                                             int32_t* top_idx, int64_t* top_count, int64_t* occupied, void* workspace,
                                             size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_TOPK_REQUIRE_ARGS("topk_spread_by_pair", pats_topk_spread_by_pair_workspace_bytes(pairs, K, grid0, grid1));
-    PATS_REQUIRE_PTR("topk_spread_by_pair", occupied, 8);
+    int rc = topk_check_args("topk_spread_by_pair", matches_l, matches_r, conf, pair_off, pairs, cap, K, use_min_conf, min_conf, top_l, top_r,
+                             top_conf, top_idx, top_count, workspace_bytes, pats_topk_spread_by_pair_workspace_bytes(pairs, K, grid0, grid1));
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_arg("topk_spread_by_pair", {"occupied", occupied, 8}, true)) != PATS_OK) return rc;
     PATS_REQUIRE(side == 0 || side == 1, "topk_spread_by_pair: side = %d (0 = matches_l, 1 = matches_r)", side);
     PATS_REQUIRE(cell >= 1 && cell <= TOPK_SPREAD_MAX_CELL, "topk_spread_by_pair: cell = %lld (1 .. %d pixels)", (long long)cell,
                  TOPK_SPREAD_MAX_CELL);

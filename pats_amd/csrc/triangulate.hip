@@ -4,13 +4,13 @@
 // host read.  include/pats_amd.h states the definition; docs/kernels.md 4.9.1 the design.
 //
 //   one workgroup per pair, TRI_THREADS = 256 threads, decided by the sizes alone (the pose's vote walk)
-//   pose    twelve threads bring R_p, t_p (the pose in the frame of the points: rows and columns 0 and 1 exchanged back for
-//           swapped) to LDS in float64 and judge it: a non-finite entry or t = 0 leaves the pair without a valid match
-//   walk    the workgroup walks the segment with epi_load; a match that is not used carries a NaN x_l.  tri_match is the whole
-//           definition of one match, float64, no contraction.  Only valid rows are stored: the fills defined everything else
-//   count   ballots + popcounts per wave, the waves added by thread 0 (integer adds: no order)
-//   sum     a thread adds the e2 of its valid matches in walk order, the lanes of a wave are added by a fixed tree (lane l takes
-//           lane l + 32, + 16, ... + 1), thread 0 adds the waves in index order: the order depends on the sizes alone, no atomics
+//   pose    twelve threads bring R_p, t_p (the pose in the frame of the points: hom_perm, frame_perm) to LDS in float64 and judge
+//           it: a non-finite entry or t = 0 leaves the pair without a valid match
+//   walk    the workgroup walks the segment with epi_load_masked.  tri_match is the whole definition of one match, float64, no
+//           contraction.  Only valid rows are stored: the fills defined everything else
+//   count   the count fold of epipolar.hpp
+//   sum     a thread adds the e2 of its valid matches in walk order, the lanes of a wave by wave_sum_tree_f64, thread 0 adds the
+//           waves in index order: the order depends on the sizes alone, no atomics
 #include "common.hpp"
 #include "epipolar.hpp"
 
@@ -83,15 +83,13 @@ epipolar_triangulate_kernel(const float* __restrict__ ml_, const float* __restri
     wg_barrier();
 
     // ---- pose -------------------------------------------------------------------------------------------------------------------
-    if (tid < 9) {                                      // R_p = P R P for swapped: rows and columns 0 and 1 exchanged
-        const int i = tid / 3, j = tid - 3 * i;
-        const int si = swapped ? (i == 2 ? 2 : 1 - i) : i, sj = swapped ? (j == 2 ? 2 : 1 - j) : j;
-        const double v = R_in[p * 9 + si * 3 + sj];
+    if (tid < 9) {                                      // R_p = P R P, t_p = P t for swapped
+        const double v = R_in[p * 9 + hom_perm(tid, swapped)];
         sR[tid] = v;
         if (!__builtin_isfinite(v)) s_bad = 1;          // the same value from every writer
     } else if (tid < 12) {
         const int i = tid - 9;
-        const double v = t_in[p * 3 + (swapped ? (i == 2 ? 2 : 1 - i) : i)];
+        const double v = t_in[p * 3 + frame_perm(i, swapped)];
         sT[i] = v;
         if (!__builtin_isfinite(v)) s_bad = 1;
         if (v != 0.0) s_moves = 1;
@@ -117,10 +115,9 @@ epipolar_triangulate_kernel(const float* __restrict__ ml_, const float* __restri
         for (uint32_t i0 = 0; i0 < n; i0 += TRI_THREADS) {
             const uint32_t i = i0 + tid;
             float l0, l1, r0, r1;
-            epi_load(ml, mr, nullptr, i, n, norm != nullptr, nm, false, 0.0f, l0, l1, r0, r1);
-            if (i < n && msk[i] == 0) l0 = __builtin_nanf("");          // masked out: not used
+            epi_load_masked(ml, mr, msk, i, n, norm != nullptr, nm, l0, l1, r0, r1);
             const TriMatch m = tri_match(R, t, l0, l1, r0, r1, has_r, lim_r2, has_c, lim_cos);
-            cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.valid));
+            cnt += wave_count(m.valid);
             if (m.valid) {                              // i < n: a row past the segment carries the NaN l0
                 const int64_t row = lo + i;
                 sum += m.e2;
@@ -134,18 +131,14 @@ epipolar_triangulate_kernel(const float* __restrict__ ml_, const float* __restri
                 valid[row] = (uint8_t)1;
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);        // lane 0: the wave's sum, a fixed tree
+        sum = wave_sum_tree_f64(sum);
     }
-    if (lane == 0) { s_cnt[wave] = cnt; s_sum[wave] = sum; }
+    wave_parts_store(s_cnt, wave, lane, cnt);
+    wave_parts_store(s_sum, wave, lane, sum);
     wg_barrier();
     if (tid == 0) {
-        int64_t total = 0;
-        double e = 0.0;
-#pragma unroll
-        for (int w = 0; w < TRI_WAVES; ++w) { total += s_cnt[w]; e += s_sum[w]; }
-        tri_count[p] = total;
-        reproj_sum[p] = e;
+        tri_count[p] = (int64_t)wave_parts_total(s_cnt);
+        reproj_sum[p] = wave_parts_total(s_sum);
     }
 }
 
@@ -165,27 +158,17 @@ extern "C" int pats_epipolar_triangulate_by_pair_f64(const float* matches_l, con
                                                      float* reproj, float* cos_parallax, uint8_t* valid, int64_t* tri_count,
                                                      double* reproj_sum, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     (void)workspace;
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", matches_l, 8);
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", matches_r, 8);
-    PATS_REQUIRE(mask, "epipolar_triangulate_by_pair: null mask");
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", R, 8);
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", t, 8);
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", points, 4);
-    PATS_REQUIRE(valid, "epipolar_triangulate_by_pair: null valid");
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", tri_count, 8);
-    PATS_REQUIRE_PTR("epipolar_triangulate_by_pair", reproj_sum, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", norm, 4);            // optional pointers: null is aligned
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", max_reproj, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", max_cos, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", depths, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", reproj, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", cos_parallax, 4);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", pair_off, 8);
-    PATS_REQUIRE_ALIGNED("epipolar_triangulate_by_pair", counts_in, 8);
-    int rc = epi_check_segments("epipolar_triangulate_by_pair", pair_off, counts_in, stride, pairs, cap);
+    const char* who = "epipolar_triangulate_by_pair";
+    int rc = epi_check_args(who, {{"matches_l", matches_l, 8}, {"matches_r", matches_r, 8}, {"mask", mask, 1}, {"R", R, 8}, {"t", t, 8},
+                                  {"points", points, 4}, {"valid", valid, 1}, {"tri_count", tri_count, 8}, {"reproj_sum", reproj_sum, 8}}, true);
     if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(swapped == 0 || swapped == 1, "epipolar_triangulate_by_pair: swapped = %d must be 0 or 1", swapped);
-    PATS_REQUIRE(workspace_bytes >= pats_epipolar_triangulate_workspace_bytes(pairs, cap), "epipolar_triangulate_by_pair: workspace too small");
+    rc = epi_check_args(who, {{"norm", norm, 4}, {"max_reproj", max_reproj, 4}, {"max_cos", max_cos, 4}, {"depths", depths, 4},
+                              {"reproj", reproj, 4}, {"cos_parallax", cos_parallax, 4}, {"pair_off", pair_off, 8}, {"counts_in", counts_in, 8}},
+                        false);
+    if (rc != PATS_OK) return rc;
+    if ((rc = epi_check_segments(who, pair_off, counts_in, stride, pairs, cap)) != PATS_OK) return rc;
+    PATS_REQUIRE(swapped == 0 || swapped == 1, "%s: swapped = %d must be 0 or 1", who, swapped);
+    PATS_REQUIRE(workspace_bytes >= pats_epipolar_triangulate_workspace_bytes(pairs, cap), "%s: workspace too small", who);
     hipStream_t st = as_stream(stream);
     // every byte of every per-match output is defined: zeros here, the kernel stores the valid rows
     if ((rc = fill_bytes(points, 0, (size_t)cap * 3 * sizeof(float), st)) != PATS_OK) return rc;

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Byte comparison of two builds of the per-pair geometry branch (the generators, the four consumers of the refit source, the mask
-and the local optimisation) - what a device-side refactor of csrc/epipolar.hpp or csrc/refit.hpp is checked with.
+and the local optimisation; the back end: the poses, the E-or-H choice, the triangulation, the pose and match errors, the lift and
+the selections) - what a device-side refactor of csrc/epipolar.hpp or csrc/refit.hpp is checked with.
 
   dump OUT.npz          calls every touched `ops` entry of THIS checkout on seeded inputs and writes every output array
   compare A.npz B.npz   the two dumps hold the same names, dtypes and shapes, and numpy.array_equal on the raw bytes (NaNs included)
 
 Run `dump` once in a checkout of the parent commit (copy this file there) and once in the tree, each a fresh process under its own
-time limit; `compare` needs no GPU.  The shapes are the smallest that reach every branch of the shared code (docs/kernels.md 4.16)."""
+time limit; `compare` needs no GPU.  The shapes are the smallest that reach every branch of the shared code (docs/kernels.md 4.16,
+4.24)."""
 import itertools
 import os
 import sys
@@ -42,7 +44,8 @@ def dump(path):
 
     def keep(tag, out):
         for i, t in enumerate(out if isinstance(out, (tuple, list)) else (out,)):
-            arrays["%05d_%s_%d" % (len(arrays), tag, i)] = t.detach().cpu().numpy()
+            if t is not None:                             # an output the call was not asked for
+                arrays["%05d_%s_%d" % (len(arrays), tag, i)] = t.detach().cpu().numpy()
 
     def gpu(a, dtype=None):
         return torch.as_tensor(np.asarray(a), dtype=dtype).to(dev)
@@ -116,6 +119,106 @@ def dump(path):
     for name, fn, f in (("E", ops.epipolar_polish_by_pair, fam["E"]), ("H", ops.homography_polish_by_pair, fam["H"]),
                         ("F", ops.fundamental_polish_by_pair, fam["E"])):
         keep("polish_" + name, fn(vl, vr, f["models"], thr, best=best, rounds=3, norm=nm, **seg))
+
+    # ---- the back end (docs/kernels.md 4.24): the masked walks, the count folds and the fixed-order sums at the edges of the
+    # 256-thread walk and the 64-lane ballots, ragged and strided, swapped both ways; a mask with zeros, one pair's all zero, one
+    # coordinate of each side not finite
+    lens = [0, 1, 63, 64, 65, 255, 256, 257, 513]
+    pairs, stride = len(lens), max(lens)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    parts = [scene(rng, n) for n in lens]
+    parts[7][0][100, 0] = np.nan
+    parts[8][1][300, 1] = np.inf
+    conf_parts = [rng.uniform(0, 1, n).astype(np.float32) for n in lens]
+    keep_parts = [(rng.uniform(0, 1, n) < 0.8).astype(np.uint8) for n in lens]
+    keep_parts[5][:] = 0
+    a = 0.1
+    T1 = np.tile(np.eye(4), (pairs, 1, 1))
+    T1[:, :3, :3] = [[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]
+    T1[:, :3, 3] = [0.6, 0.05, 0.1]
+    T1[3, 0, 3] = np.nan                                   # a ground truth that is not finite
+    b = 0.02
+    T0 = np.tile(np.eye(4), (pairs, 1, 1))
+    T0[:, :3, :3] = [[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]]
+    T0[:, :3, 3] = [0.01, -0.02, 0.03]
+    gT1, gT0 = gpu(T1), gpu(T0)
+    maps = []
+    for p in range(pairs):
+        d = rng.uniform(3.5, 8.5, (200, 210)).astype(np.float32)
+        d[rng.uniform(0, 1, d.shape) < 0.05] = 0.0
+        d[7, 9] = np.nan
+        maps.append(None if p == 6 else gpu(d)[:, :200])   # a view with a row stride; pair 6 has no map
+    nm, thr = norm_of(pairs), torch.full((pairs,), 0.01, device=dev)
+    seeds, ratio = gpu(np.arange(pairs) + 7, torch.int64), gpu(np.linspace(0.2, 1.8, pairs), torch.float32)
+    size_r = gpu(np.tile(np.array([200.0, 200.0], np.float32), (pairs, 1)))
+
+    def lay(chunks, strided):
+        """The per-pair chunks as one array: back to back, or each at its stride."""
+        if not strided:
+            return np.concatenate(chunks)
+        out = np.zeros((pairs * stride,) + chunks[0].shape[1:], chunks[0].dtype)
+        for p, c in enumerate(chunks):
+            out[p * stride:p * stride + len(c)] = c
+        return out
+
+    for strided in (False, True):
+        form = "strided" if strided else "ragged"
+        seg = dict(stride=stride, counts=gpu(lens, torch.int64)) if strided else dict(pair_off=gpu(off, torch.int64))
+        bl, br = gpu(lay([q[0] for q in parts], strided)), gpu(lay([q[1] for q in parts], strided))
+        cf, mask = gpu(lay(conf_parts, strided)), gpu(lay(keep_parts, strided))
+        ver = {}
+        for name, hyp, score in (("E", ops.epipolar_hypotheses_by_pair, ops.epipolar_score_by_pair),
+                                 ("H", ops.homography_hypotheses_by_pair, ops.homography_score_by_pair)):
+            ver[name] = score(bl, br, hyp(bl, br, 64, seeds, norm=nm, **seg), thr, norm=nm, moments=True, **seg)
+        lifts = {}                                         # the lift has no frame flag: once per form
+        for interp, jump in (("nearest", None), ("bilinear", None), ("bilinear", 0.3)):
+            lifts["%s_%s" % (interp, jump)] = ops.lift_by_pair(bl, maps, norm=nm, max_depth=torch.full((pairs,), 8.0, device=dev),
+                                                                interp=interp, max_jump=jump, **seg)
+            keep("be_lift_%s_%s_%s" % (form, interp, jump), lifts["%s_%s" % (interp, jump)])
+        keep("be_lift_bare_" + form, ops.lift_by_pair(bl, maps, **seg))
+        for swapped in (False, True):
+            tag = "%s_sw%d" % (form, swapped)
+            for inl_name, trim in (("inlier", 1), ("masked", mask)):       # the verification's mask, and that with the zeros on top
+                e, h = ver["E"], ver["H"]
+                pe = ops.epipolar_pose_by_pair(bl, br, e[3] * trim, e[2], moments=e[4], norm=nm, swapped=swapped, return_front=True,
+                                               return_refit=True, **seg)
+                ph = ops.homography_pose_by_pair(bl, br, h[3] * trim, h[2], moments=h[4], norm=nm, thr=thr, swapped=swapped,
+                                                 return_candidates=True, return_front=True, **seg)
+                keep("be_pose_%s_%s" % (tag, inl_name), pe)
+                keep("be_pose_h_%s_%s" % (tag, inl_name), ph)
+                keep("be_select_%s_%s" % (tag, inl_name), ops.pose_select_by_pair(pe[:4] + (pe[6],), e[2], e[3] * trim, ph[:4] + (ph[-1],), ph[9],
+                                                                                  h[2], h[3] * trim, ratio, **seg))
+                keep("be_select_nofront_%s_%s" % (tag, inl_name), ops.pose_select_by_pair(pe[:4], e[2], e[3] * trim, ph[:4], ph[9], h[2],
+                                                                                          h[3] * trim, ratio, **seg))
+                for lim in (False, True):
+                    kw = dict(max_reproj=torch.full((pairs,), 2e-3, device=dev), max_cos=torch.full((pairs,), 0.9999, device=dev)) if lim else {}
+                    for mname, m in (("front", pe[6]), ("trim", pe[6] * mask)):
+                        keep("be_tri_%s_%s_%s_lim%d" % (tag, inl_name, mname, lim),
+                             ops.epipolar_triangulate_by_pair(bl, br, m, pe[1], pe[2], norm=nm, swapped=swapped, return_depths=True,
+                                                              return_reproj=True, return_cos=True, **kw, **seg))
+                    keep("be_tri_bare_%s_%s_lim%d" % (tag, inl_name, lim),
+                         ops.epipolar_triangulate_by_pair(bl, br, mask, pe[1], pe[2], swapped=swapped, **kw, **seg))
+                for t0 in (None, gT0):
+                    perr = ops.pose_error_by_pair(pe[1], pe[2], gT1, T0=t0, counts=e[2], min_matches=15)
+                    keep("be_pose_error_%s_%s_T0%d" % (tag, inl_name, t0 is not None), perr)
+                    keep("be_pose_auc_%s_%s_T0%d" % (tag, inl_name, t0 is not None), ops.pose_auc(perr[2], return_sorted=True))
+            for key, lifted in lifts.items():
+                keep("be_merr_full_%s_%s" % (tag, key),
+                     ops.match_error_by_pair(lifted[0], br, gT1, T0=gT0, thr=(1.0, 3.0, 5.0), norm=nm, swapped=swapped, depths_r=maps,
+                                             occl_rel=0.2, size_r=size_r, conf=cf, min_conf=0.2, edges=(0.1, 0.3, 0.5, 0.7, 0.9), mask=mask,
+                                             **seg))
+                keep("be_merr_bare_%s_%s" % (tag, key),
+                     ops.match_error_by_pair(lifted[0], br, gT1, thr=(0.5, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0, 128.0), swapped=swapped, **seg))
+        if not strided:                                    # the selections take ragged segments only
+            for K, floor in ((1, None), (64, 0.3), (600, None)):
+                keep("be_topk_K%d" % K, ops.topk_by_pair(bl, br, cf, seg["pair_off"], K, min_conf=floor))
+                for side in ("left", "right"):
+                    keep("be_spread_K%d_%s" % (K, side), ops.topk_spread_by_pair(bl, br, cf, seg["pair_off"], K, 16, (13, 13), side=side,
+                                                                                 min_conf=floor))
+    for n in (0, 1, 63, 64, 65, 1023, 1024, 1025, 4097):   # the AUC's own sizes: around a wave, the workgroup and 64 KiB of keys
+        errs = rng.uniform(0, 30, n)
+        errs[rng.uniform(0, 1, n) < 0.1] = np.inf
+        keep("be_auc_n%d" % n, ops.pose_auc(gpu(errs), thresholds=(5.0, 10.0, 20.0), return_sorted=True))
     torch.cuda.synchronize()
     np.savez_compressed(path, **arrays)
     print("ab_geometry: %d arrays, %d bytes -> %s" % (len(arrays), sum(a.nbytes for a in arrays.values()), path))
