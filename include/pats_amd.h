@@ -1576,7 +1576,8 @@ int pats_homography_polish_by_pair_f32(const float* matches_l, const float* matc
  * are written as row-major 3x3 models: rank 2 by construction, the cheapest epipolar sample RANSAC can use.  What
  * cv2.findFundamentalMat's RANSAC solves per sample.  One launch, no host read, no workspace, deterministic.  No calibration is
  * needed: norm is the verification's normalisation, whatever it is (advice for uncalibrated callers: INTEGRATION.md).
- * What it is not: a plane-and-parallax (DEGENSAC) check, epipoles, rectification, self-calibration.
+ * What it is not: epipoles, rectification, self-calibration (the plane-and-parallax check is a stage of its own: "Per-pair
+ * plane-and-parallax hypotheses and hand-over" below).
  *   x          the verification's point, formed exactly as there: ((p0 - c0) * s0, (p1 - c1) * s1, 1) in float32 - one subtract,
  *              then one multiply, never contracted - or (p0, p1, 1) without norm.  The segment of pair p (n rows from lo on) in the
  *              same two forms, ragged (pair_off) or strided (stride, counts_in), with the same clamping as above
@@ -1629,7 +1630,7 @@ int pats_epipolar_hypotheses7_by_pair_f32(const float* matches_l, const float* m
  * least-squares refit of the winner's moments truncated to rank 2, taken back to the stored coordinates the way the homography
  * refit does, and the local optimisation that refits with it.  The sibling of pats_homography_refit_by_pair_f64: the same launch
  * shape (one wave per pair), the same Jacobi, the same arguments with two outputs more.  On the device, float64, no host read.
- * What it is not: epipoles, rectification, a plane-and-parallax check, self-calibration from F.
+ * What it is not: epipoles, rectification, self-calibration from F.
  * pats_fundamental_refit_by_pair_f64 - best_count [pairs] int64 and moments [pairs,9,9] float64 (or, moments null, models
  * [pairs,H,3,3] float32 with best [pairs] int32) as pats_epipolar_score_by_pair_f32 or a local optimisation returned them; norm
  * [pairs,8] float32 or null, what the verification was given; swapped 0 or 1.  Per pair p
@@ -1674,6 +1675,72 @@ int pats_fundamental_polish_by_pair_f32(const float* matches_l, const float* mat
                                         const int32_t* best, int rounds, float* model, int64_t* best_count, uint8_t* inlier,
                                         double* moments, int32_t* best_round, int32_t* counts, void* workspace, size_t workspace_bytes,
                                         pats_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-pair plane-and-parallax hypotheses and hand-over (ABI 8, symbols added): the uncalibrated branch's answer to a dominant plane
+ * (DEGENSAC: Chum, Werner, Matas, CVPR 2005).  Five or more of a 7-point sample on one plane give a family of fundamental matrices;
+ * verification crowns one that explains the plane and a few accidental points.  The plane's homography and TWO matches off the plane
+ * fix the epipolar geometry instead.  Two entries, each one workgroup per pair and one launch for the batch, no host read, no
+ * workspace, deterministic.
+ * What it is not: a sample-level H-degeneracy test of the seven points; a gate (the stage always runs, support alone decides); a
+ * calibrated variant (the calibrated branch has pats_pose_select_by_pair).
+ * pats_plane_parallax_hypotheses_by_pair_f32 - the arguments of pats_epipolar_hypotheses7_by_pair_f32 without progressive and
+ * n_models, and the plane: models_h [pairs,Mh,3,3] float32 with best_h [pairs] int32 as pats_homography_score_by_pair_f32 or the
+ * homography's local optimisation left them, thr [pairs] float32, and the host scalar parallax >= 1 (2 is the usual choice).  Per pair p
+ *   x, segment  as in "Per-pair 7-point hypotheses"
+ *   plane       Hp = models_h[p, clamp(best_h[p], 0, Mh-1)]; nine exact zeros are "no plane"
+ *   pool        match i of the segment is a member iff its four coordinates are finite after norm and it is off the plane at
+ *               parallax thr[p]:  d0^2 + d1^2 > t2 a2^2  or  a2^2 == 0,  with a = Hp x_l, d = (a0 - x_r0 a2, a1 - x_r1 a2),
+ *               t2 = (parallax thr[p])^2 - every operation the float32 FMA expression of the homography verification
+ *               (pats_homography_score_by_pair_f32), the products parallax thr[p] and its square rounded to float32.  A NaN on
+ *               either side of the comparison is no member.  The members in ascending i are the pool; its size is written to
+ *   pool_out    `pool` [pairs] int32, BEFORE clamping.  Only the first pats_plane_parallax_pool_max() (8192) members are drawn from:
+ *               m = min(pool size, pool_max)
+ *   sampler     the hypotheses' with two draws on 0 .. m - 1 (k, u_t, j_t as in "Per-pair 7-point hypotheses", t = 0, 1): draw t is
+ *               the j_t-th member of the pool not drawn before
+ *   sample_idx  [pairs,H,2] int32 (optional: null skips it): the two draws as positions inside the pair's SEGMENT, in draw order;
+ *               -1, -1 when m < 2 or there is no plane
+ *   solve       in float64 from the float32 points and Hp widened exactly:  a_i = Hp x_i,  l_i = x'_i x a_i  (the line through a match
+ *               and its transfer: it holds the epipole),  e = l_1 x l_2,  F = [e]x Hp (column j of F = e x column j of Hp)
+ *   models      [pairs,H,3,3] float32: F scaled to |F|_F = 1, the component of largest magnitude positive (the lowest index among
+ *               equals, judged on the float32 values written) - a `models` argument of pats_epipolar_score_by_pair_f32
+ *   zero        nine exact zeros: m < 2; no plane; |e| <= 1e-9 |l_1| |l_2| (the two parallax lines coincide); a non-finite value.
+ *               Never a NaN or an infinity
+ *   limits      1 <= H <= pats_epipolar_max_h(), 1 <= Mh <= pats_epipolar_max_h()
+ * Outputs - every call defines every byte of models, pool and (if given) sample_idx.  cap == 0 is a valid call.  Refused before any
+ * launch (pats_last_error names the argument): what pats_epipolar_hypotheses7_by_pair_f32 refuses, in its order and wording (with H
+ * itself against max_h); then parallax not finite or below 1; Mh outside 1 .. max_h; a null or misaligned (4 bytes) models_h, best_h
+ * or thr; a null or misaligned pool.  The kernel's LDS is static (32 KiB for the list): there is no PATS_ERR_UNSUPPORTED case.
+ * pats_plane_parallax_select_by_pair - the hand-over.  a = the standing verification of the pair's fundamental matrices, b = the
+ * verification of the plane-and-parallax models, each as pats_epipolar_score_by_pair_f32 left it: models_x [pairs,Hx,3,3] with
+ * best_x [pairs] int32, best_count_x [pairs] int64, inlier_x [cap] uint8 and (optional) moments_x [pairs,9,9] float64.  Per pair p
+ *   replaced    [pairs] uint8 = 1 iff best_count_b[p] > best_count_a[p] - strictly: a tie keeps the standing verification
+ *   kept        b where replaced, else a
+ *   best_count  [pairs] int64, inlier [cap] uint8 (the kept mask on the pair's segment as 0 / 1, 0 on every row outside the segments),
+ *               moments [pairs,9,9] float64 (optional: null skips it; needs moments_a and moments_b), model [pairs,3,3] float32 =
+ *               models_kept[p, clamp(best_kept[p], 0, H_kept - 1)]: the verification's standard form with H = 1 and best = 0
+ *   overlap     [pairs] int32: the matches of the segment with inlier_a != 0 and finite coordinates that are inliers of the plane at
+ *               thr[p] by the homography verification's test (a2^2 > 0 and d0^2 + d1^2 <= thr^2 a2^2; none for a NaN or negative
+ *               thr or without a plane) - the standing model's degeneracy measure, to be divided by best_count_a
+ * Every output byte of every pair is written; cap == 0 and zero counts are valid.  Refused before any launch: a null or misaligned
+ * required pointer in the order matches_l, matches_r, models_a, best_a, best_count_a, inlier_a, models_b, best_b, best_count_b,
+ * inlier_b, model, best_count, inlier, replaced, overlap; a misaligned norm, pair_off, counts_in, moments_a, moments_b, moments; the
+ * segments as everywhere; Ha, Hb outside 1 .. max_h; moments without moments_a and moments_b; then the plane's arguments as above. */
+int64_t pats_plane_parallax_pool_max(void);
+size_t pats_plane_parallax_hypotheses_workspace_bytes(int64_t pairs, int64_t H);
+int pats_plane_parallax_hypotheses_by_pair_f32(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                               const int64_t* counts_in, int64_t pairs, int64_t cap, int64_t H, const int64_t* pair_seed,
+                                               const float* norm, const float* models_h, int64_t Mh, const int32_t* best_h,
+                                               const float* thr, float parallax, float* models, int32_t* sample_idx, int32_t* pool,
+                                               void* workspace, size_t workspace_bytes, pats_stream_t stream);
+int pats_plane_parallax_select_by_pair(const float* matches_l, const float* matches_r, const int64_t* pair_off, int64_t stride,
+                                       const int64_t* counts_in, int64_t pairs, int64_t cap, const float* norm, const float* models_h,
+                                       int64_t Mh, const int32_t* best_h, const float* thr, const float* models_a, int64_t Ha,
+                                       const int32_t* best_a, const int64_t* best_count_a, const uint8_t* inlier_a,
+                                       const double* moments_a, const float* models_b, int64_t Hb, const int32_t* best_b,
+                                       const int64_t* best_count_b, const uint8_t* inlier_b, const double* moments_b, float* model,
+                                       int64_t* best_count, uint8_t* inlier, double* moments, uint8_t* replaced, int32_t* overlap,
+                                       pats_stream_t stream);
 
 /* attention(query, key, value) of the GNN layers (reference models/modules.py:84-88; the core of
  * MultiHeadedAttention.forward :100-105): scores = q^T k / dim**.5 per (batch, head), softmax over the

@@ -318,6 +318,20 @@ SIGNATURES = {
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "pats_fundamental_polish_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
     "pats_fundamental_polish_by_pair_f32": (c_int, _POLISH_ARGS),
+    # the plane-and-parallax (DEGENSAC) stage of the uncalibrated branch (csrc/plane_parallax.hip): the 7-point generator's arguments
+    # without progressive and n_models, then the plane (models_h, Mh, best_h, thr), parallax, models, sample_idx, pool; the hand-over:
+    # the lists and segments, norm, the plane, the standing and the new verification (models, H, best, best_count, inlier, moments
+    # each), then model, best_count, inlier, moments, replaced, overlap
+    "pats_plane_parallax_pool_max": (c_i64, []),
+    "pats_plane_parallax_hypotheses_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "pats_plane_parallax_hypotheses_by_pair_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p,
+                                                           c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_f, c_void_p, c_void_p,
+                                                           c_void_p, c_void_p, c_size, c_void_p]),
+    "pats_plane_parallax_select_by_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p,
+                                                   c_void_p, c_i64, c_void_p, c_void_p,
+                                                   c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # the absolute-pose branch (csrc/absolute.hip): the lift through a depth map, P3P hypotheses, reprojection verification
     "pats_lift_by_pair_f32": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_f,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -577,6 +577,16 @@ def split_topk_by_pair(out, cap):
     return _caller_order(out, cap, per_slot)
 
 
+def _pair_seeds(out, cap, seed, dev):
+    """The generators' per-pair seeds in slot order: pair i of the CALLER's order gets seed + i (int64, wrapping), built on the device
+    once per seed and kept in the result as `pair_seed`."""
+    seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)              # the int64 the bits of `seed` spell
+    if out.get("pair_seed", (None,))[0] != seed:
+        ids = _caller_of_dev(out, dev) if "caller_of" in out else torch.arange(cap.pairs, dtype=torch.int64, device=dev)
+        out["pair_seed"] = (seed, ids + seed)                             # slot order
+    return out["pair_seed"][1]
+
+
 def _sample_by_pair(fn, generate, out, cap, H, seed, norm, on, progressive, samples):
     """What hypothesize_by_pair, hypothesize5_by_pair and hypothesize7_by_pair share: the order handling, the per-pair seeds (pair i of the CALLER's order
     gets seed + i, built on the device once per seed and kept in the result), the permutation of norm to slot order and of the
@@ -585,12 +595,8 @@ def _sample_by_pair(fn, generate, out, cap, H, seed, norm, on, progressive, samp
     if progressive is None:
         progressive = on == "topk"
     dev = out["matches_l"].device
-    seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)              # the int64 the bits of `seed` spell
     mixed = "caller_of" in out                                            # slot s holds the caller's pair caller_of[s]
-    if out.get("pair_seed", (None,))[0] != seed:
-        ids = _caller_of_dev(out, dev) if mixed else torch.arange(cap.pairs, dtype=torch.int64, device=dev)
-        out["pair_seed"] = (seed, ids + seed)                             # slot order
-    pair_seed = out["pair_seed"][1]
+    pair_seed = _pair_seeds(out, cap, seed, dev)
     if mixed and norm is not None:
         norm = norm.index_select(0, _caller_of_dev(out, dev))
     ml, mr, _, seg = _lists_on(out, cap, on)
@@ -1105,6 +1111,63 @@ def fundamental_by_pair(out, cap, norm=None, swapped=False, pixel=False):
         back = _slot_of_dev(out, cap, best.device)
         res = tuple(t.index_select(0, back) for t in res)
     out["fundamental"] = res
+    return res
+
+
+def degensac_by_pair(out, cap, H, thr, seed=0, norm=None, parallax=2.0, min_conf=None, on="topk", samples=False):
+    """Device side, after verify_by_pair AND verify_h_by_pair (or their local optimisations) on the same lists: the plane-and-parallax
+    stage of the uncalibrated branch (DEGENSAC; no host read).  A dominant plane makes the 7-point
+    winner a member of a whole family of fundamental matrices; this stage takes the plane `verified_h` found, draws H pairs of
+    matches off it (ops.plane_parallax_hypotheses_by_pair: off the plane at parallax * thr), verifies the H models F = [e]x Hp like
+    any others (ops.epipolar_score_by_pair, with moments when `verified` has them) and keeps, per pair, whichever of the standing
+    and the new verification has more support (ops.plane_parallax_select_by_pair: a tie keeps the standing one).  There is no
+    gate: the stage always runs and only support decides.  thr [pairs], norm [pairs,8] or None in the CALLER's order and min_conf -
+    pass what the verifications were given -; seed as the hypothesize functions take it (pair i of the caller's order draws with
+    seed + i); on must be what both verifications were computed on.
+    REPLACES `verified` by the standard tuple of the kept model - (counts [pairs,1] int32, best = 0, best_count, inlier[, moments])
+    - and `verified_models` by model[:, None], in SLOT order, exactly the form polish_f_by_pair leaves: polish_f_by_pair,
+    fundamental_by_pair and split_verified_by_pair work on the result unchanged.  Stores and returns `degensac` = (replaced [pairs]
+    uint8, overlap [pairs] int32: the standing inliers the plane explains at thr - divide by count_before for the degeneracy share -,
+    pool [pairs] int32: the matches off the plane, count_before, count_pp [pairs] int64: the support of the standing and of the
+    best plane-and-parallax model[, sample_idx [pairs,H,2] int32 with samples=True]) in the CALLER's order.  Apart from the
+    generators' `pair_seed` nothing else of the result is touched."""
+    fn = "degensac_by_pair"
+    if "verified" not in out:
+        raise ValueError("%s: run verify_by_pair first" % fn)
+    if "verified_h" not in out or "verified_h_models" not in out:
+        raise ValueError("%s: run verify_h_by_pair first (the plane)" % fn)
+    _check_on(fn, out, on)
+    for key in ("verified", "verified_h"):
+        if out[key + "_on"] != on:
+            raise ValueError("%s: `%s` was computed on=\"%s\", the stage runs on=\"%s\": its mask is not aligned with these lists" %
+                             (fn, key, out[key + "_on"], on))
+    if min_conf is not None and "match_conf" not in out:
+        raise ValueError("%s: min_conf needs a result made with confidence=True" % fn)
+    ver, plane = out["verified"], out["verified_h"]
+    dev = ver[1].device
+    mixed = "caller_of" in out                            # slot s holds the caller's pair caller_of[s]
+    pair_seed = _pair_seeds(out, cap, seed, dev)
+    if mixed:
+        idx = _caller_of_dev(out, dev)
+        thr = thr.index_select(0, idx)
+        norm = None if norm is None else norm.index_select(0, idx)
+    ml, mr, conf, seg = _lists_on(out, cap, on)
+    hyp = ops.plane_parallax_hypotheses_by_pair(ml, mr, H, pair_seed, out["verified_h_models"], plane[1], thr, norm=norm, parallax=parallax,
+                                                return_samples=samples, **seg)
+    with_moments = len(ver) > 4
+    new = ops.epipolar_score_by_pair(ml, mr, hyp[0], thr, conf=conf if min_conf is not None else None, min_conf=min_conf, norm=norm,
+                                     moments=with_moments, **seg)
+    standing = (out["verified_models"], ver[1], ver[2], ver[3]) + tuple(ver[4:5])
+    sel = ops.plane_parallax_select_by_pair(ml, mr, thr, out["verified_h_models"], plane[1], standing, (hyp[0],) + tuple(new[1:]), norm=norm,
+                                            **seg)
+    model, best_count, inl = sel[:3]
+    out["verified"] = (best_count.to(torch.int32)[:, None], torch.zeros_like(ver[1]), best_count, inl) + tuple(sel[3:4] if with_moments else ())
+    out["verified_models"] = model[:, None]
+    res = (sel[-2], sel[-1], hyp[1], ver[2], new[2]) + tuple(hyp[2:3])
+    if mixed:                                                             # slots back to the caller's order
+        back = _slot_of_dev(out, cap, dev)
+        res = tuple(t.index_select(0, back) for t in res)
+    out["degensac"] = res
     return res
 
 

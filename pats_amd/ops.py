@@ -18,6 +18,7 @@ Reference call sites (paths relative to zju3dv/pats):
 """
 import collections
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -2023,6 +2024,135 @@ def epipolar_hypotheses7_by_pair(matches_l, matches_r, H, seed, pair_off=None, s
     return _hypotheses_by_pair("epipolar_hypotheses7_by_pair", 7, 3, _L().pats_epipolar_hypotheses7_by_pair_f32,
                                _L().pats_epipolar_hypotheses7_workspace_bytes, matches_l, matches_r, H, seed, pair_off, stride, counts, norm,
                                progressive, return_samples, return_counts, out, pairs)
+
+
+def plane_parallax_pool_max():
+    """The number of off-plane matches plane_parallax_hypotheses_by_pair draws from at most (pats_plane_parallax_pool_max)."""
+    return int(_L().pats_plane_parallax_pool_max())
+
+
+def _pp_plane(fn, models_h, best_h, pairs):
+    """The plane of the plane-and-parallax entries, checked -> (models_h [pairs,Mh,3,3], best_h [pairs] as GPU tensors, Mh)."""
+    models_h, best_h = _dev(models_h, "models_h"), _bp_vector(best_h, "best_h", torch.int32)
+    if models_h.dim() != 4 or tuple(models_h.shape[2:]) != (3, 3) or models_h.shape[0] != pairs or best_h.numel() != pairs:
+        raise RuntimeError("%s: models_h must be [pairs,Mh,3,3] and best_h [pairs], %d pairs" % (fn, pairs))
+    Mh = int(models_h.shape[1])
+    if not 1 <= Mh <= epipolar_max_h():
+        raise RuntimeError("%s: Mh = %d, must lie in 1 .. %d" % (fn, Mh, epipolar_max_h()))
+    return models_h, best_h, Mh
+
+
+def plane_parallax_hypotheses_by_pair(matches_l, matches_r, H, seed, models_h, best_h, thr, pair_off=None, stride=None, counts=None,
+                                      norm=None, parallax=2.0, return_samples=False, out=None, pairs=None):
+    """H plane-and-parallax hypotheses per pair, ON THE DEVICE, one launch, no host read (pats_plane_parallax_hypotheses_by_pair_f32;
+    include/pats_amd.h, "Per-pair plane-and-parallax hypotheses and hand-over", holds the definition): the matches of the pair that
+    are finite and off the plane Hp = models_h[p, best_h[p]] at parallax * thr[p] - by the homography verification's own test - form
+    the pair's pool in segment order; for every h two of them are drawn by the hypotheses' generator and F = [e]x Hp, e the
+    intersection of the two lines x'_i x Hp x_i, is written as a unit model with the branch's sign rule.  matches_l / matches_r, the
+    segments, seed and norm as epipolar_hypotheses7_by_pair takes them; models_h [pairs,Mh,3,3] float32, best_h [pairs] int32 and
+    thr [pairs] float32 as homography_score_by_pair (or homography_polish_by_pair) took and left them; parallax >= 1.
+    Returns (models [pairs,H,3,3] float32 - nine exact zeros where there is no plane (a zero Hp), fewer than two pool members, two
+    coinciding lines or a non-finite value -, pool [pairs] int32: the pool's size, of which the first plane_parallax_pool_max()
+    members are drawn from) and, with return_samples=True, sample_idx [pairs,H,2] int32: the draws as positions inside the pair's
+    list, -1 where nothing was drawn.  out: the destinations, a tuple in that order."""
+    fn = "plane_parallax_hypotheses_by_pair"
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (seed, "seed"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm"), (models_h, "models_h"), (best_h, "best_h"), (thr, "thr")],
+               {"pair_off": torch.int64, "counts": torch.int64, "seed": torch.int64, "best_h": torch.int32})
+    _bp_one_form(fn, pair_off, stride, counts)
+    if not isinstance(seed, torch.Tensor):
+        raise RuntimeError("%s: seed must be an int64 GPU tensor [pairs]" % fn)
+    parallax = float(parallax)
+    if not (math.isfinite(parallax) and parallax >= 1.0):
+        raise RuntimeError("%s: parallax = %r must be a finite number >= 1" % (fn, parallax))
+    a, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    H = int(H)
+    seed = _bp_vector(seed, "seed", torch.int64)
+    _, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    if seed.numel() != pairs:
+        raise RuntimeError("%s: seed must hold one int64 per pair (%d), got %d" % (fn, pairs, seed.numel()))
+    if not 1 <= H <= epipolar_max_h():
+        raise RuntimeError("%s: H = %d, must lie in 1 .. %d" % (fn, H, epipolar_max_h()))
+    norm = _bp_norm(fn, norm, pairs)
+    models_h, best_h, Mh = _pp_plane(fn, models_h, best_h, pairs)
+    thr = _bp_vector(thr, "thr")
+    if thr.numel() != pairs:
+        raise RuntimeError("%s: thr must hold one float32 per pair (%d), got %d" % (fn, pairs, thr.numel()))
+    want = [("models", torch.float32, (pairs, H, 3, 3)), ("pool", torch.int32, (pairs,))]
+    if return_samples:
+        want.append(("sample_idx", torch.int32, (pairs, H, 2)))
+    out = _bp_outputs(fn, want, out, a.device)
+    if cap == 0:
+        a = mr = _bp_placeholder(a.device)
+    nws = _L().pats_plane_parallax_hypotheses_workspace_bytes(pairs, H)
+    ws = _workspace(nws, out[0].device) if nws else None
+    _check(_L().pats_plane_parallax_hypotheses_by_pair_f32(_ptr(a), _ptr(mr), off_p, stride, counts_p, pairs, cap, H, _ptr(seed), _ptr(norm),
+                                                           _ptr(models_h), Mh, _ptr(best_h), _ptr(thr), parallax, _ptr(out[0]),
+                                                           _ptr(out[2]) if return_samples else None, _ptr(out[1]), _ptr(ws), nws,
+                                                           _stream()), fn)
+    return out
+
+
+def plane_parallax_select_by_pair(matches_l, matches_r, thr, models_h, best_h, standing, candidate, pair_off=None, stride=None,
+                                  counts=None, norm=None, out=None, pairs=None):
+    """The hand-over of the plane-and-parallax stage, ON THE DEVICE, one launch, no host read (pats_plane_parallax_select_by_pair;
+    include/pats_amd.h holds the definition): standing and candidate are two verifications of the same lists, each a tuple (models
+    [pairs,H,3,3] float32, best [pairs] int32, best_count [pairs] int64, inlier [cap] uint8[, moments [pairs,9,9] float64]) as
+    epipolar_score_by_pair took and left them - the standing one of the pair's fundamental matrices, the candidate of
+    plane_parallax_hypotheses_by_pair's models.  A pair keeps the standing one unless the candidate's best_count is STRICTLY larger.
+    The lists, the segments, thr and norm as the verifications took them; models_h, best_h: the plane.
+    Returns (model [pairs,3,3] float32, best_count [pairs] int64, inlier [cap] uint8[, moments [pairs,9,9] float64 - when both
+    tuples carry moments], replaced [pairs] uint8, overlap [pairs] int32: the standing inliers that are inliers of the plane at thr,
+    the standing model's degeneracy measure).  out: the destinations, a tuple in that order."""
+    fn = "plane_parallax_select_by_pair"
+    sides = []
+    for side, name in ((standing, "standing"), (candidate, "candidate")):
+        if not isinstance(side, (tuple, list)) or len(side) not in (4, 5):
+            raise RuntimeError("%s: %s must be (models, best, best_count, inlier[, moments])" % (fn, name))
+        sides.append(tuple(side) + (None,) * (5 - len(side)))
+    (ma, ba, ca, ia, qa), (mb, bb, cb, ib, qb) = sides
+    _bp_layout(fn, [(matches_l, "matches_l"), (matches_r, "matches_r"), (thr, "thr"), (pair_off, "pair_off"), (counts, "counts"),
+                    (norm, "norm"), (models_h, "models_h"), (best_h, "best_h"), (ma, "standing models"), (ba, "standing best"),
+                    (ca, "standing best_count"), (ia, "standing inlier"), (qa, "standing moments"), (mb, "candidate models"),
+                    (bb, "candidate best"), (cb, "candidate best_count"), (ib, "candidate inlier"), (qb, "candidate moments")],
+               {"pair_off": torch.int64, "counts": torch.int64, "best_h": torch.int32, "standing best": torch.int32,
+                "candidate best": torch.int32, "standing best_count": torch.int64, "candidate best_count": torch.int64,
+                "standing inlier": torch.uint8, "candidate inlier": torch.uint8, "standing moments": torch.float64,
+                "candidate moments": torch.float64})
+    _bp_one_form(fn, pair_off, stride, counts)
+    a, mr, cap = _bp_matches(fn, matches_l, matches_r)
+    _, pairs, stride, off_p, counts_p = _bp_segments(fn, pair_off, stride, counts, pairs, cap)
+    norm = _bp_norm(fn, norm, pairs)
+    models_h, best_h, Mh = _pp_plane(fn, models_h, best_h, pairs)
+    thr = _bp_vector(thr, "thr")
+    if thr.numel() != pairs:
+        raise RuntimeError("%s: thr must hold one float32 per pair (%d), got %d" % (fn, pairs, thr.numel()))
+    args, with_moments = [], qa is not None and qb is not None
+    for name, (m, b, c, i, q) in (("standing", sides[0]), ("candidate", sides[1])):
+        _, m, b, Hx = _bp_refit_source("%s: %s" % (fn, name), pairs, None, m, b)
+        c, i = _bp_vector(c, name + " best_count", torch.int64), _bp_vector(i, name + " inlier", torch.uint8)
+        if c.numel() != pairs or i.numel() != cap:
+            raise RuntimeError("%s: %s best_count must be [pairs] and inlier [cap]" % (fn, name))
+        if with_moments:
+            q = _dev(q, name + " moments", torch.float64)
+            if tuple(q.shape) != (pairs, 9, 9):
+                raise RuntimeError("%s: %s moments must be [pairs,9,9]" % (fn, name))
+        if cap == 0:
+            i = _bp_placeholder(a.device, torch.uint8)
+        args += [_ptr(m), Hx, _ptr(b), _ptr(c), _ptr(i), _ptr(q) if with_moments else None]
+    want = [("model", torch.float32, (pairs, 3, 3)), ("best_count", torch.int64, (pairs,)), ("inlier", torch.uint8, (cap,))]
+    if with_moments:
+        want.append(("moments", torch.float64, (pairs, 9, 9)))
+    want += [("replaced", torch.uint8, (pairs,)), ("overlap", torch.int32, (pairs,))]
+    out = _bp_outputs(fn, want, out, a.device)
+    inl = out[2]
+    if cap == 0:
+        a = mr = _bp_placeholder(a.device)
+        inl = _bp_placeholder(a.device, torch.uint8)
+    _check(_L().pats_plane_parallax_select_by_pair(_ptr(a), _ptr(mr), off_p, stride, counts_p, pairs, cap, _ptr(norm), _ptr(models_h), Mh,
+                                                   _ptr(best_h), _ptr(thr), *args, _ptr(out[0]), _ptr(out[1]), _ptr(inl),
+                                                   _ptr(out[3]) if with_moments else None, _ptr(out[-2]), _ptr(out[-1]), _stream()), fn)
+    return out
 
 
 def epipolar_pose_by_pair(matches_l, matches_r, inlier, best_count, moments=None, models=None, best=None, pair_off=None, stride=None,
