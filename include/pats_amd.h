@@ -71,7 +71,9 @@ int pats_sinkhorn_fallbacks(int64_t* count, int reset);
 /* Of those, the 145 x 145 problems whose STABILISED linear re-solve (sinkhorn_rc_kernel, linear == 2) failed its final guard as
  * well and were solved by the log-sum-exp sweeps behind it, in the same launch: problems with non-finite scores, or whose
  * scalings run away within a single sweep.  The plan is the same either way, so nothing else shows that the stabilised form
- * stopped working.  Same synchronisation and reset as pats_sinkhorn_fallbacks, a counter of its own.  No reference counterpart. */
+ * stopped working.  The count also covers the third level's 65 x 65 stabilised re-solve (third_fused3_stab_kernel): a problem it
+ * leaves to third_fused_kernel's log-sum-exp sweeps because a scaling left (0, 3e38] within one sweep.
+ * Same synchronisation and reset as pats_sinkhorn_fallbacks, a counter of its own.  No reference counterpart. */
 int pats_sinkhorn_tail_solves(int64_t* count, int reset);
 
 /* ---- a1-a3: cost build -------------------------------------------------------------------

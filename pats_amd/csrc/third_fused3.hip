@@ -416,7 +416,10 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
             auto band = [](float x) { return x >= 9.5367431640625e-07f && x <= 1048576.0f; };       // [2^-20, 2^20]
             auto fin = [](float x) { return x > 0.f && x <= 3.0e38f; };
             if (!(__all(band(a) && band(b)) && band(a64) && band(b64))) {          // wave-uniform
-                if (!(__all(fin(a) && fin(b)) && fin(a64) && fin(b64))) return;     // out of fp32 in one sweep: the log-sum-exp kernel
+                if (!(__all(fin(a) && fin(b)) && fin(a64) && fin(b64))) {          // out of fp32 in one sweep: the log-sum-exp kernel,
+                    if (lane == 0 && g.fallbacks) atomicAdd(g.fallbacks + 1, 1ull);  // counted apart (pats_sinkhorn_tail_solves)
+                    return;
+                }
                 // absorb: the scalings go into the stabilisers (logs) and K is built again from the scores - exact exponents; a
                 // product a_i K_ij b_j would keep the entries the first K lost below 2^-126 lost, and those are the ones that carry
                 // the plan once a b has grown by 2^100
@@ -446,6 +449,9 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
             g.cr.ifm[p * 16] = THIRD_REDO;
             if (g.fallbacks) atomicAdd(g.fallbacks, 1ull);
         }
+        // ST, after at least one sweep, never gets here (a scaling outside the band was absorbed or bailed out above); were it to,
+        // the problem would take the same tail and is counted as such
+        if (ST && lane == 0 && g.fallbacks) atomicAdd(g.fallbacks + 1, 1ull);
         return;
     }
 

@@ -196,7 +196,8 @@ def sinkhorn_fallbacks(reset=True):
 
 def sinkhorn_tail_solves(reset=True):
     """Of sinkhorn_fallbacks(), the 145 x 145 problems whose stabilised linear re-solve failed its guard as well and ended in the
-    log-sum-exp sweeps of the same launch (pats_sinkhorn_tail_solves; synchronises; a counter of its own)."""
+    log-sum-exp sweeps of the same launch, and the third level's 65 x 65 problems whose stabilised re-solve bailed out to the
+    log-sum-exp kernel (pats_sinkhorn_tail_solves; synchronises; a counter of its own)."""
     n = ctypes.c_int64(0)
     _check(_L().pats_sinkhorn_tail_solves(ctypes.byref(n), 1 if reset else 0), "sinkhorn_tail_solves")
     return int(n.value)
