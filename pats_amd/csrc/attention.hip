@@ -20,6 +20,7 @@
 // The n x m score matrix never reaches HBM (the stock path writes and re-reads it three times).
 // Tokens on this path: 65 / 145 / 300 (768 at YFCC size) per side, dim = 32 / 66 / 112, 4 heads;
 // the [rows][m] slab must fit the CU's 160 KB of LDS: 32 query rows per workgroup up to m = 1024, 16 / 8 / 4 beyond (m <= 8416).
+#include "launch.hpp"
 #include "cost65_device.hpp"
 
 namespace pats {
@@ -288,11 +289,6 @@ attention65_kernel(AttnArgs g) {
 }  // namespace pats
 
 using namespace pats;
-
-namespace pats {
-int launch_attention(const float* query, const float* key, const float* value, int64_t batch, int dim, int heads, int n, int m,
-                     float* out, float* prob, pats_stream_t stream, const int* gate);
-}
 
 extern "C" int pats_attention_f32(const float* query, const float* key, const float* value, int64_t batch,
                                   int dim, int heads, int n, int m, float* out, float* prob,

@@ -16,18 +16,15 @@
 //   4. out^T / sum leaves through LDS as whole rows of queries.
 // 60 KB of LDS and 96 registers: two workgroups (20 waves) per CU - one stages or stores while the other multiplies.
 // Range: |q|, |k|, |v| < 1023; a non-finite output raises *flag and the general kernel, queued behind and gated on it, redoes the launch.
-#include "common.hpp"
+#include "launch.hpp"
+#include "split_f16.hpp"
 
 namespace pats {
 
 namespace {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
-constexpr float PRE = 64.0f, UNS = 1.0f / 4096.0f;
 constexpr int A_T = 10;                    // 16-token tiles per side (160 tokens)
 constexpr int A_KS = 3;                    // 32-channel k-steps of the first product (96 channels)
 constexpr int A_DT = 5;                    // 16-channel row tiles of the second product (80 channels)
@@ -45,24 +42,6 @@ struct A145Args {
     int* flag;                             // raised if an output is not finite
     const int* gate;                       // optional: no-op unless *gate != 0
 };
-
-__device__ __forceinline__ void split4(const f4v v, h4v& hi, h4v& lo) {
-    const f4v s = v * PRE;
-    hi = __builtin_convertvector(s, h4v);
-    lo = __builtin_convertvector(s - __builtin_convertvector(hi, f4v), h4v);
-}
-__device__ __forceinline__ void split8(const f4v a, const f4v b, h8v& hi, h8v& lo) {
-    h4v ah, al, bh, bl;
-    split4(a, ah, al);
-    split4(b, bh, bl);
-    hi = h8v{ah.x, ah.y, ah.z, ah.w, bh.x, bh.y, bh.z, bh.w};
-    lo = h8v{al.x, al.y, al.z, al.w, bl.x, bl.y, bl.z, bl.w};
-}
-__device__ __forceinline__ f4v mfma3(const h8v ah, const h8v al, const h8v bh, const h8v bl, f4v c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);       // small terms first
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-}
 
 }  // namespace
 

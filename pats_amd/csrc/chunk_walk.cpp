@@ -14,11 +14,10 @@
 
 using namespace pats;
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 extern "C" size_t pats_chunk_fine_tail_workspace_bytes(int64_t B, int64_t pairs, int H, int W) {
     if (B <= 0 || pairs <= 0) return 0;
-    return al256(std::max({pats_cost_ot_workspace_bytes(B, 264, 145, 145, 2), pats_merge_batch_workspace_bytes(pairs, H, W),
+    return align256(std::max({pats_cost_ot_workspace_bytes(B, 264, 145, 145, 2), pats_merge_batch_workspace_bytes(pairs, H, W),
                            pats_compact_workspace_bytes(B * 144)}));
 }
 
@@ -56,7 +55,7 @@ extern "C" int pats_chunk_fine_tail_f32(const float* d0, const float* d1, int64_
 
 extern "C" size_t pats_chunk_third_tail_workspace_bytes(int64_t B, int h, int w) {
     if (B <= 0) return 0;
-    return al256(std::max(pats_compact_workspace_bytes(B * 144), pats_get_result_workspace_bytes((int64_t)h * w, B, 2304)));
+    return align256(std::max(pats_compact_workspace_bytes(B * 144), pats_get_result_workspace_bytes((int64_t)h * w, B, 2304)));
 }
 
 extern "C" int pats_chunk_third_tail_f32(const float* feat0, const float* feat1, int64_t P_cap, const int64_t* P_dev, const float* scale,

@@ -18,6 +18,12 @@ constexpr float LN2 = 0.6931471805599453f;
 constexpr float LN2_HI = 0.693145751953125f;           // ln 2 in two parts, the first with 15 significant bits
 constexpr float LN2_LO = 1.42860682030941723212e-6f;
 constexpr float ZERO_F = 1e-14f;  // the reference's `zero` (utils/utils.py:1201)
+// THE guard band of the linear-domain Sinkhorn solvers (sinkhorn.hip describes the iteration): entries of the kernel matrix K below
+// 2^-126 flush to zero; their true mass is < 2^-126 * a_i * b_j, so the result is unaffected as long as the scalings stay below 2^30.
+// Each problem checks that its scalings lie in (0, 2^30] - a NaN fails both comparisons - and is otherwise solved again with
+// sweeps that have no range restriction (stabilised linear or max-subtracted log-sum-exp: each solver's own re-solve).
+constexpr float SCALE_GUARD = 1073741824.0f;   // 2^30
+__device__ __forceinline__ bool scaling_ok(float x) { return x <= SCALE_GUARD && x > 0.f; }
 
 // ---- environment switches -----------------------------------------------------------------------------------------------------
 // The PRODUCTION library reads exactly the switches INTEGRATION.md lists (section "Environment switches": each selects a TESTED
@@ -153,6 +159,8 @@ __device__ __forceinline__ float wave_allreduce(float v, Op op) {
     return v;
 }
 __device__ __forceinline__ float wave_sum(float v) { return wave_allreduce(v, OpSum()); }
+// a value the caller knows to be the same in every lane, moved to an SGPR (v_readfirstlane)
+__device__ __forceinline__ float uni(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
 // 64-lane sum delivered as a wave-uniform value (SGPR): four in-row DPP steps, then the GFX9 row
 // broadcasts (row 0->1 and 2->3, then lane 31 -> rows 2,3) leave the total in row 3 and one
@@ -302,6 +310,7 @@ inline hipStream_t as_stream(pats_stream_t s) { return reinterpret_cast<hipStrea
 int fill_bytes(void* p, int value, size_t n, hipStream_t st);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace sections start on 256-byte boundaries
 
 // ---- the shapes of a throughput batch (include/pats_amd.h, pats_pair_table_t) ----------------------------------------------
 // Uniform batch (shape == nullptr): every pair has the grid h x w, n cells (n = h w for the row table) and an H x W image at

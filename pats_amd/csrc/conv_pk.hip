@@ -33,7 +33,8 @@
 // memory pipe (activations in and out at 4 bytes a lane, 360 KB of weights per tile) is what bounds it, not HBM and not the MFMAs.
 // Range: |activation| < 1023; a non-finite output raises *redo - the layer's one flag: the round-2 composition queued behind the
 // layer, gated on it, recomputes the whole layer (gnn.hip, propagation_impl).
-#include "common.hpp"
+#include "launch.hpp"
+#include "split_f16.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -46,13 +47,8 @@ namespace pats {
 
 namespace {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef const __attribute__((address_space(1))) h8v* gptr_h8;
 
-constexpr float PRE = 64.0f, UNS = 1.0f / 4096.0f;
 constexpr int FR = 2 * 64;                 // h8v per fragment (hi | lo)
 constexpr int PK_NT = 4, PK_NC = 16 * PK_NT;      // 16-column tiles per workgroup: 64 columns
 constexpr int PK_KS_BYTES = 2 * PK_NT * 1024;     // one k-step of activations in LDS: (hi | lo) x 4 tiles x 64 lanes x 16 B
@@ -100,18 +96,6 @@ struct PkArgs {
 #else
 #define PK_TS(k) do { } while (0)
 #endif
-
-__device__ __forceinline__ gptr_h8 uniform_ptr(const h8v* p) {
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (gptr_h8)(((uint64_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void split4(const f4v v, h4v& hi, h4v& lo) {
-    const f4v s = v * PRE;
-    hi = __builtin_convertvector(s, h4v);
-    lo = __builtin_convertvector(s - __builtin_convertvector(hi, f4v), h4v);
-}
 
 }  // namespace
 

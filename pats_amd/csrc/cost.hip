@@ -12,6 +12,7 @@
 // the matrix edge are CLAMPED, not predicated (they only feed output rows / columns that are never stored, and the
 // main loop stays free of branches).  Scale and the reference's two-step `/ sqrt(D)`, `* 0.1` rounding are applied
 // in the epilogue.
+#include "launch.hpp"
 #include "mfma_tile.hpp"
 
 #include <cstdlib>
@@ -77,13 +78,6 @@ cost_mfma_kernel(const T* __restrict__ d0, const T* __restrict__ d1, int D, int 
 
 }  // namespace pats
 
-namespace pats {
-template <typename T> int launch_cost65(const T*, const T*, int, int64_t, float*, hipStream_t);      // sinkhorn.hip
-int launch_cost(const float* d0, const float* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
-                const int64_t* live);
-int launch_cost_typed(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, float* out,
-                      pats_stream_t stream, const int64_t* live);
-}
 using namespace pats;
 
 extern "C" int pats_cost_f32(const float* d0, const float* d1, int64_t batch, int D, int n, int m,

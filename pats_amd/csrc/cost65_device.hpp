@@ -2,7 +2,7 @@
 // standalone cost kernel, sinkhorn65_kernel (sinkhorn.hip) and the block-layout fused kernel
 // (third_fused.hip).
 #pragma once
-#include "common.hpp"
+#include "split_f16.hpp"
 
 namespace pats {
 
@@ -135,16 +135,14 @@ __device__ __forceinline__ void cost65_accumulate(const T* __restrict__ A, const
 // (pre-scaled) fp16 hi part to inf -> NaN scores -> the Sinkhorn guard hands the problem to the fp32 kernel.
 // Lane l supplies A[i = l & 31][k = 8 (l >> 5) + e], e = 0..7, so each lane loads eight consecutive descriptor rows
 // per 16-channel step (same eight-byte loads, same even / odd column tiling, same D fragment layout as above).
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef float f2p __attribute__((ext_vector_type(2)));
 
-constexpr float C65_PRESCALE = 64.0f;      // 2^6 on both operands, 2^-12 on the product: see below
+// PRE (split_f16.hpp): 2^6 on both operands, 2^-12 on the product: see below
 __device__ __forceinline__ void split_pair(float x0, float x1, h2v& hi, h2v& lo) {
     // fp16 keeps 11 bits but only 5 of exponent: the lo half of an operand below 0.25 would be subnormal (and the
     // matrix pipe flushes subnormal fp16 inputs - measured: one target coordinate in 18 000 moved by 2e-2 px).  Scaling
     // by 2^6 first is exact and keeps lo normal down to |x| = 0.004; hi then overflows only beyond |x| = 1023.
-    const f2p x = f2p{x0, x1} * C65_PRESCALE;
+    const f2p x = f2p{x0, x1} * PRE;
     hi = __builtin_convertvector(x, h2v);
     const f2p r = x - __builtin_convertvector(hi, f2p);
     lo = __builtin_convertvector(r, h2v);
@@ -250,8 +248,7 @@ __device__ __forceinline__ void cost65_accumulate_f16x2(const float* __restrict_
     o.er0 = er0 + __shfl_xor(er0, 32); o.er1 = er1 + __shfl_xor(er1, 32);
     o.ec0 = ec0 + __shfl_xor(ec0, 32); o.ec1 = ec1 + __shfl_xor(ec1, 32);
     o.cn = cn + __shfl_xor(cn, 32);
-    constexpr float UNSCALE = 1.0f / (C65_PRESCALE * C65_PRESCALE);            // exact power of two
-    o.c00 = c00 * UNSCALE; o.c01 = c01 * UNSCALE; o.c10 = c10 * UNSCALE; o.c11 = c11 * UNSCALE;
+    o.c00 = c00 * UNS; o.c01 = c01 * UNS; o.c10 = c10 * UNS; o.c11 = c11 * UNS;
 }
 
 struct Cost65Scale {

@@ -3,31 +3,10 @@
 //   variant 2: second_layer.py:100-105 / third_layer.py:156-158 (log_optimal_transport2)
 // The score matrix lives only in the caller's workspace (L2 / Infinity-Cache resident between the
 // MFMA kernel and the Sinkhorn kernel on the same stream); nothing is returned to the host side.
-#include "common.hpp"
+#include "launch.hpp"
 
 using namespace pats;
 
-namespace pats {
-int launch_cost_ot65(const void*, const void*, int dtype, int64_t, int, const float*, const float*, int, float, float*,
-                     pats_stream_t);
-int launch_col_flags(const float* Z, int64_t batch, int M, int N, uint8_t* col_nomatch, const int* only_if,
-                     hipStream_t st);
-}
-
-namespace pats {
-int launch_fine145_fused(const float* d0, const float* d1, int D, int64_t batch, const float* ns, const float* one, int iters,
-                         float bias_k, float* out, int* fail, uint8_t* col_nomatch, hipStream_t st, bool* applied,
-                         const int64_t* live);
-int launch_cost(const float* d0, const float* d1, int64_t batch, int D, int n, int m, float* out, pats_stream_t stream,
-                const int64_t* live);
-int launch_cost_typed(const void* d0, const void* d1, int dtype, int64_t batch, int D, int n, int m, float* out,
-                      pats_stream_t stream, const int64_t* live);
-int ot2_flags_live(const float* scores, int64_t batch, int m, int n, const float* one, const float* ns, int iters, float bias_k,
-                   float* Z, uint8_t* col_nomatch, void* workspace, size_t workspace_bytes, pats_stream_t stream,
-                   const int64_t* live);
-}
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Measurement hook (bench.py): an event the next cost_ot call of THIS THREAD records between its two launches (cost build |
 // Sinkhorn), so that the two kernels of the one C call can be timed inside a step instead of on their own afterwards.

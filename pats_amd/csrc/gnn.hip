@@ -18,6 +18,7 @@
 //     statistics, in train mode = batch statistics from the bn_* kernels below: PATS.eval leaves the third layer in train
 //     mode, pats.py:112-120), and the epilogue adds the bias and an optional residual (desc + delta).
 // The attention core in the middle is pats_attention_f32 (attention.hip).
+#include "launch.hpp"
 #include "mfma_tile.hpp"
 
 #include <algorithm>
@@ -284,7 +285,7 @@ conv_lean_kernel(ConvArgs g) {
             const int row = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * kg;
             if (row < M) {
                 const int64_t o = ((int64_t)b * M + row) * n + tk;
-                float v = acc[tj][e] * mt::UNSCALE;
+                float v = acc[tj][e] * UNS;
                 bad |= !(fabsf(v) <= 3.0e38f);
                 if (g.bias) v += g.bias[row];
                 if (g.residual) v = g.residual[o] + v;
@@ -436,7 +437,7 @@ conv_ws_kernel(ConvArgs g, int row_tiles) {
                     const int row = i0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * kg;
                     if (row < M) {
                         const int64_t o = ((int64_t)b * M + row) * n + tkk;
-                        float v = acc[tj][e] * mt::UNSCALE;
+                        float v = acc[tj][e] * UNS;
                         bad |= !(fabsf(v) <= 3.0e38f);
                         if (g.bias) v += g.bias[row];
                         if (g.residual) v = g.residual[o] + v;
@@ -539,16 +540,6 @@ bn_finish_kernel(const double* __restrict__ part, int64_t total, int C, const fl
     shift[c] = beta[c] - (float)mean * sc;
 }
 
-// `redo`: one int of workspace, zero on entry (conv_lean_kernel raises it; see there).  null -> conv1x1_kernel only.
-int launch_conv_pk(const void* packed, const float* x0, const float* x1, int K0, int K1, int M, int n, int64_t cols,
-                   const float* in_scale, const float* in_shift, const float* bias, const float* residual, float* y, int* redo,
-                   const int* gate, hipStream_t st, int layout);                                            // conv_pk.hip
-bool conv_pk_ready();
-size_t conv_packed_bytes(int K, int M);
-size_t packed_fused_bytes(int C, int heads);                                                                // gnn_fused.hip
-bool gnn_fold_enabled();                                                                                    // (merge folded into mlp[0])
-const float* packed_folded_bias(const void* packed, int C, int heads);
-
 static int launch_conv(const ConvArgs& g0, int* redo, hipStream_t st, const int* gate = nullptr) {
     ConvArgs g = g0;
     g.gate = gate;
@@ -625,53 +616,18 @@ static int launch_conv(const ConvArgs& g0, int* redo, hipStream_t st, const int*
 
 using namespace pats;
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-namespace pats {
-int fine_layer_supported(int C, int heads, int n, int m);          // gnn_fine.hip
-size_t fine_scratch_bytes(int64_t P);
-}
-
 extern "C" size_t pats_attentional_propagation_workspace_bytes(int64_t batch, int C, int n, int m) {
     if (batch < 0 || C <= 0 || n <= 0 || m <= 0) return 0;
-    const size_t qb = al256((size_t)batch * C * n * sizeof(float)), kb = al256((size_t)batch * C * m * sizeof(float));
+    const size_t qb = align256((size_t)batch * C * n * sizeof(float)), kb = align256((size_t)batch * C * m * sizeof(float));
     // q, attention output, message [b,C,n]; k, v [b,C,m]; hidden [b,2C,n]; BN scale / shift [2C] each; BN partial sums
     // (BatchNorm partial sums: BN_SPLITS per channel for the composition, one per workgroup of the fused kernel's grid - at most 512)
     // (+ the fine level's one-kernel layer: its per-workgroup scratch blocks; its descriptor images overlay q / att / msg / k)
-    const size_t fine = pats::fine_layer_supported(C, 4, n, m) ? al256(pats::fine_scratch_bytes(batch)) : 0;
-    return 3 * qb + 2 * kb + al256((size_t)batch * 2 * C * n * sizeof(float)) + 2 * al256((size_t)2 * C * sizeof(float)) +
-           al256((size_t)2 * C * 512 * 2 * sizeof(double)) + 256 /* seven redo flags + the fused layer's flag */ + fine;
+    const size_t fine = pats::fine_layer_supported(C, 4, n, m) ? align256(pats::fine_scratch_bytes(batch)) : 0;
+    return 3 * qb + 2 * kb + align256((size_t)batch * 2 * C * n * sizeof(float)) + 2 * align256((size_t)2 * C * sizeof(float)) +
+           align256((size_t)2 * C * 512 * 2 * sizeof(double)) + 256 /* seven redo flags + the fused layer's flag */ + fine;
 }
 
 namespace pats {
-int launch_attention(const float* query, const float* key, const float* value, int64_t batch, int dim, int heads, int n, int m,
-                     float* out, float* prob, pats_stream_t stream, const int* gate);                     // attention.hip
-int launch_attention145(const float* query, const float* key, const float* value, int64_t batch, int dim, int heads, int n, int m,
-                        float* out, int* flag, const int* gate, hipStream_t st);                          // attention145.hip
-int fused_layer_supported(int C, int heads, int n, int m);                                                // gnn_fused.hip
-int launch_fused_layer(const float* x, const float* source, int64_t batch, const void* packed, const float* bn_a, const float* bn_b,
-                       int bn_train, const float* residual, float* out, float* hid, int* flag, double* bn_part, int* splits_out,
-                       hipStream_t st, const int64_t* live = nullptr, int64_t live_off = 0);
-int launch_gnn_tail(const float* hid, int64_t batch, const void* packed, const float* scale, const float* shift, const float* residual,
-                    float* out, int* flag, hipStream_t st);
-// the fine level's one-kernel layer (gnn_fine.hip)
-int fine_layer_supported(int C, int heads, int n, int m);
-const void* packed_fine_section(const void* packed, int C, int heads);                                   // gnn_fused.hip
-size_t fine_scratch_bytes(int64_t P);
-size_t fine_image_bytes(int64_t P);
-int launch_fine_in(const float* x, int64_t P, char* tf, hipStream_t st);
-int launch_fine_out(const char* tf, int64_t P, float* y, hipStream_t st, const int64_t* live = nullptr, int64_t live_off = 0,
-                    const float* add = nullptr);
-int launch_fine_layer(const char* tf_x, const char* tf_s, int64_t shift, int residual, int64_t P, const void* section,
-                      char* tf_out, char* tf_att, char* qkv, int* flag, const int* gate, hipStream_t st, int sets,
-                      const int64_t* live, int64_t live_off);
-int launch_fine_qkv(const char* tf, int64_t P, const void* section, char* qkv, int want_q, int want_kv, const int* gate, hipStream_t st, int sets,
-                    const int64_t* live, int64_t live_off);
-int launch_fine_attn(const char* qkv, int64_t shift, char* tf_att, int64_t P, const int* gate, hipStream_t st, int sets, const int64_t* live,
-                     int64_t live_off);
-int launch_fine_mlp(const char* tf_x, const char* tf_att, int residual, const void* section, char* tf_out, const void* next_section, char* qkv,
-                    int64_t P, int* flag, const int* gate, hipStream_t st, int sets, const int64_t* live, int64_t live_off);
-
 // The copy behind a gated redo over a capacity: dst = src for the rows below clamp(*live - live_off, 0, rows) (every row without a
 // count), nothing at all unless *gate != 0.  Rows past the count are NOT copied: the redo computed them from padding inputs, and
 // what the fast path left there (zeros / untouched) must survive it (round-5 advice).
@@ -761,16 +717,16 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
                  "attentional_propagation: workspace too small");
     hipStream_t st = as_stream(stream);
     char* p = (char*)workspace;
-    const size_t qb = al256((size_t)batch * C * n * sizeof(float)), kb = al256((size_t)batch * C * m * sizeof(float));
+    const size_t qb = align256((size_t)batch * C * n * sizeof(float)), kb = align256((size_t)batch * C * m * sizeof(float));
     float* q = (float*)p; p += qb;
     float* att = (float*)p; p += qb;
     float* msg = (float*)p; p += qb;
     float* k = (float*)p; p += kb;
     float* v = (float*)p; p += kb;
-    float* hid = (float*)p; p += al256((size_t)batch * 2 * C * n * sizeof(float));
-    float* bsc = (float*)p; p += al256((size_t)2 * C * sizeof(float));
-    float* bsh = (float*)p; p += al256((size_t)2 * C * sizeof(float));
-    double* bpart = (double*)p; p += al256((size_t)2 * C * 512 * 2 * sizeof(double));
+    float* hid = (float*)p; p += align256((size_t)batch * 2 * C * n * sizeof(float));
+    float* bsc = (float*)p; p += align256((size_t)2 * C * sizeof(float));
+    float* bsh = (float*)p; p += align256((size_t)2 * C * sizeof(float));
+    double* bpart = (double*)p; p += align256((size_t)2 * C * 512 * 2 * sizeof(double));
     int* redo = (int*)p; p += 256;
     char* fine_scratch = p;
     // deferred overflow protocol (pats_set_gnn_redo_mode(1), host.cpp): the one-kernel / packed-weights branches raise the device's
@@ -912,9 +868,9 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
 extern "C" size_t pats_attentional_gnn_packed_workspace_bytes(int64_t batch, int C, int heads, int n) {
     if (batch <= 0 || !fine_layer_supported(C, heads, n, n)) return 0;
     const int64_t P = 2 * batch;
-    const size_t fused = 3 * al256(fine_image_bytes(P));
-    const size_t redo = 4 * al256((size_t)batch * C * n * sizeof(float)) + al256(pats_attentional_propagation_workspace_bytes(batch, C, n, n));
-    return std::max(fused, redo) + al256(fine_scratch_bytes(P)) + 256;
+    const size_t fused = 3 * align256(fine_image_bytes(P));
+    const size_t redo = 4 * align256((size_t)batch * C * n * sizeof(float)) + align256(pats_attentional_propagation_workspace_bytes(batch, C, n, n));
+    return std::max(fused, redo) + align256(fine_scratch_bytes(P)) + 256;
 }
 extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* desc1, int64_t batch, const int64_t* live, int64_t live_off,
                                                int C, int heads, int n, int layers,
@@ -933,13 +889,13 @@ extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* 
     const int64_t P = 2 * batch;
     const size_t elems = (size_t)batch * C * n;
     char* p = (char*)workspace;
-    const size_t fused = 3 * al256(fine_image_bytes(P));
-    const size_t redo_b = 4 * al256(elems * sizeof(float)) + al256(pats_attentional_propagation_workspace_bytes(batch, C, n, n));
-    char* tf[2] = {p, p + al256(fine_image_bytes(P))};
-    char* tf_att = p + 2 * al256(fine_image_bytes(P));
+    const size_t fused = 3 * align256(fine_image_bytes(P));
+    const size_t redo_b = 4 * align256(elems * sizeof(float)) + align256(pats_attentional_propagation_workspace_bytes(batch, C, n, n));
+    char* tf[2] = {p, p + align256(fine_image_bytes(P))};
+    char* tf_att = p + 2 * align256(fine_image_bytes(P));
     char* scratch = p + std::max(fused, redo_b);
     const bool deferred = gnn_redo_deferred();          // no redo chain: the device's sticky flag, read by the caller (host.cpp)
-    int* flag = deferred ? gnn_overflow_flag() : (int*)(scratch + al256(fine_scratch_bytes(P)));
+    int* flag = deferred ? gnn_overflow_flag() : (int*)(scratch + align256(fine_scratch_bytes(P)));
     if (!deferred && fill_bytes(flag, 0, sizeof(int), st)) return PATS_ERR_LAUNCH;
     int rc;
     // in: the two descriptor sets into one array of problems
@@ -960,9 +916,9 @@ extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* 
     if ((rc = launch_fine_out(tf[cur] + fine_image_bytes(batch), batch, out1, st, live, live_off))) return rc;
     if (deferred) return check_launch("attentional_gnn_packed");
     // the redo chain (no-ops unless the flag is up): the layers one by one on the round-2 composition, from the inputs
-    float* d[2][2] = {{(float*)p, (float*)(p + al256(elems * sizeof(float)))},
-                      {(float*)(p + 2 * al256(elems * sizeof(float))), (float*)(p + 3 * al256(elems * sizeof(float)))}};
-    void* cws = p + 4 * al256(elems * sizeof(float));
+    float* d[2][2] = {{(float*)p, (float*)(p + align256(elems * sizeof(float)))},
+                      {(float*)(p + 2 * align256(elems * sizeof(float))), (float*)(p + 3 * align256(elems * sizeof(float)))}};
+    void* cws = p + 4 * align256(elems * sizeof(float));
     const size_t cws_b = pats_attentional_propagation_workspace_bytes(batch, C, n, n);
     const float *c0 = desc0, *c1 = desc1;
     for (int l = 0; l < layers; ++l) {
@@ -996,7 +952,7 @@ extern "C" int pats_conv1x1_f32(const float* w_t, const float* bias, const float
 }
 
 extern "C" size_t pats_bn_fold_workspace_bytes(int C) {
-    return C > 0 ? al256((size_t)C * pats::BN_SPLITS * 2 * sizeof(double)) : 0;
+    return C > 0 ? align256((size_t)C * pats::BN_SPLITS * 2 * sizeof(double)) : 0;
 }
 
 extern "C" int pats_bn_fold_f32(const float* h, int64_t batch, int C, int n, const float* gamma, const float* beta,

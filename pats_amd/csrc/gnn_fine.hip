@@ -32,7 +32,8 @@
 //     hi.hi + lo.hi + hi.lo of both channels.
 // BatchNorm in eval mode only (the second layer always is: pats.py:112-114).  Range: |activation| < 1023; a non-finite output raises
 // *flag and the round-2 composition queued behind, gated on it, redoes the layer.
-#include "common.hpp"
+#include "launch.hpp"
+#include "split_f16.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -46,15 +47,7 @@ namespace pats {
 
 namespace {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(1))) h8v* gptr_h8;
-
 constexpr int FC = 264, FN = 145, FNT = 10;
-constexpr float PRE = 64.0f, UNS = 1.0f / 4096.0f;
 constexpr int TFB = 9 * 1024 + 64;            // one (k-step, hi | lo) block: nine full token tiles + token 144 (four 16-byte pieces)
 constexpr int TFR = 9 * 256 + 16;             // the ragged k-step (channels 256..263: lanes k / 8 = 0 only), per plane
 constexpr int TF_MAIN = 16 * TFB;             // 148 480
@@ -87,26 +80,8 @@ __device__ __forceinline__ int tf_off(bool ragged, int t, int lane) {
     return t < 9 ? t * 256 + (lane & 15) * 16 : 2304;
 }
 
-__device__ __forceinline__ void split4_pre(const f4v s, h4v& hi, h4v& lo) {       // s already carries the factor PRE
-    hi = __builtin_convertvector(s, h4v);
-    lo = __builtin_convertvector(s - __builtin_convertvector(hi, f4v), h4v);
-}
-__device__ __forceinline__ f4v fma4(const f4v a, const f4v b, const f4v c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f4v bcast4(float x) { return f4v{x, x, x, x}; }
 __device__ __forceinline__ f4v load4(const float* p) { return *reinterpret_cast<const f4v*>(p); }
 __device__ __forceinline__ h8v zero8() { return h8v{0, 0, 0, 0, 0, 0, 0, 0}; }
-
-__device__ __forceinline__ f4v mfma3(const h8v ah, const h8v al, const h8v bh, const h8v bl, f4v c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);       // small terms first
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ gptr_h8 uniform_ptr(const h8v* p) {
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (gptr_h8)(((uint64_t)hi << 32) | lo);
-}
 
 // ---- global -> LDS, 16 bytes a lane, no registers (bytes % 16 == 0; src 16-byte aligned).  Completion: vmcnt. ----------------
 template <int BYTES>

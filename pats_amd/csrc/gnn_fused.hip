@@ -32,7 +32,8 @@
 // LDS: x | source -> q -> attention output -> hidden[0:128] | k -> message | v^T -> hidden[128:256] = 134 656 bytes.
 // Range: |activation| < 1023 (the hi half overflows beyond, as in the cost build).  A non-finite output raises *flag and the
 // host entry then runs the composition of gnn.hip behind it, gated on that flag (its kernels return at once otherwise).
-#include "common.hpp"
+#include "launch.hpp"
+#include "split_f16.hpp"
 
 #include <cstdlib>
 
@@ -40,12 +41,7 @@ namespace pats {
 
 namespace {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-
 constexpr int GC = 128, GN = 65;
-constexpr float PRE = 64.0f, UNS = 1.0f / 4096.0f;
 constexpr int TF_BLK = 4 * 1024 + 64;             // bytes of one (k-step, hi | lo) block
 constexpr int TF_BYTES = 4 * 2 * TF_BLK;          // [128 x 65] tensor: 33 280
 constexpr int TT_ROW = 68;                        // tokens per channel row of the token-major copy (65 + zero padding)
@@ -81,20 +77,6 @@ struct FusedArgs {
 __device__ __forceinline__ int tf_tile_off(int nt, int lane) {      // byte offset of this lane's 16-byte fragment piece in a block
     return nt < 4 ? nt * 1024 + lane * 16 : 4096 + (lane >> 4) * 16;
 }
-
-__device__ __forceinline__ void split4(const f4v v, h4v& hi, h4v& lo) {
-    const f4v s = v * PRE;
-    hi = __builtin_convertvector(s, h4v);
-    lo = __builtin_convertvector(s - __builtin_convertvector(hi, f4v), h4v);
-}
-
-// the same for a value that already carries the factor PRE (the epilogues fold it - a power of two - into their one fma)
-__device__ __forceinline__ void split4_pre(const f4v s, h4v& hi, h4v& lo) {
-    hi = __builtin_convertvector(s, h4v);
-    lo = __builtin_convertvector(s - __builtin_convertvector(hi, f4v), h4v);
-}
-__device__ __forceinline__ f4v fma4(const f4v a, const f4v b, const f4v c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f4v bcast4(float x) { return f4v{x, x, x, x}; }
 
 // rows 16 mt + 4 q' + r (r = 0..3) of token 16 nt + j -> the TF tensor at dst.  PRESCALED: v = PRE x the value
 template <bool PRESCALED = false>
@@ -144,28 +126,12 @@ __device__ __forceinline__ void store_in(const InRegs& q, char* dst, int t) {
     }
 }
 
-__device__ __forceinline__ f4v mfma3(const h8v ah, const h8v al, const h8v bh, const h8v bl, f4v c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);       // small terms first
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
-    return c;
-}
-
 // Weight fragments of a stage: a ring of four k-steps per row tile (hi, lo), loaded AHEAD - the first four k-steps of stage
 // s + 1 are issued before the epilogue and the barrier of stage s, so that their L2 round trip (the weights are streamed by
 // every workgroup, 640 KB per problem) runs under them; the counters of the first version showed the waves waiting 73 % of
 // their cycles with the matrix pipe 21 % busy: the one-k-step-ahead fetch of 240 MFMA cycles did not cover the latency.
 // (depth 4 for one row tile per wave, 2 for two: a k-step of two row tiles is 30 MFMAs per wave, twice the cover)
-// A fragment's address is wave-uniform + lane * 16: the uniform part is forced into SGPRs (readfirstlane), so that a load is
-// `global_load_dwordx4 v, v_lane, s[base] offset:0 | 1024`.  Left to itself the compiler kept one 64-bit VECTOR address per
-// load, spilled them, and every reload put an s_waitcnt vmcnt(0) in front of the next weight load - no prefetch at all.
-typedef const __attribute__((address_space(1))) h8v* gptr_h8;        // explicitly GLOBAL: the integer round trip below would otherwise
-                                                                     // leave a generic pointer and flat_load (which also counts on lgkmcnt)
-__device__ __forceinline__ gptr_h8 uniform_ptr(const h8v* p) {
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (gptr_h8)(((uint64_t)hi << 32) | lo);
-}
+// (a fragment's address is wave-uniform + lane * 16: uniform_ptr() of split_f16.hpp)
 template <int MT>
 struct WRing {
     static constexpr int D = MT == 1 ? 4 : 2;
@@ -687,8 +653,6 @@ namespace pats {
 size_t packed_fused_bytes(int C, int heads) {
     return (C == GC && heads == 4) ? (((size_t)PW_END * sizeof(h8v) + (size_t)PB_END * sizeof(float) + 255) & ~(size_t)255) : 0;
 }
-size_t conv_packed_bytes(int K, int M);                                                                     // conv_pk.hip
-int launch_conv_pack(const float* wt, int K, int M, void* packed, hipStream_t st);
 // merge folded into mlp[0] (gnn_fold_kernel): on unless PATS_GNN_FOLD=0; the same answer at pack time and at run time
 bool gnn_fold_enabled() {
     static const bool on = [] { const char* e = env_switch("PATS_GNN_FOLD"); return !(e && atoi(e) == 0); }();
@@ -702,8 +666,6 @@ const float* packed_folded_bias(const void* packed, int C, int heads) {
     return (const float*)((const char*)packed + packed_matrices_bytes(C, heads)) + (size_t)4 * C * C;
 }
 // and behind those (round 5): the fine level's one-kernel layer has its own fragment set (gnn_fine.hip; only C = 264, 4 heads)
-size_t packed_fine_bytes(int C, int heads);
-int launch_fine_pack(const pats_propagation_weights& w, void* section, hipStream_t st);
 static size_t packed_fine_offset(int C, int heads) {
     return (packed_matrices_bytes(C, heads) + ((size_t)4 * C * C + 2 * C) * sizeof(float) + 255) & ~(size_t)255;
 }

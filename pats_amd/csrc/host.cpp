@@ -1,5 +1,5 @@
 // Host-side pieces of libpats_amd.so: error plumbing, version, and the chunk planner.
-#include "common.hpp"
+#include "launch.hpp"
 #include <stdlib.h>
 #include "chunk_plan.hpp"
 

@@ -8,7 +8,7 @@
 //   reduce8_consecutive: result for index J lands in lane (I, J)      (row_half_mirror, quad xor 2, xor 1)
 //   reduce8_strided    : result for index I lands in lane (I, J)      (permlane32_swap, permlane16_swap, row_ror:8)
 #pragma once
-#include "common.hpp"
+#include "split_f16.hpp"      // f4v
 
 namespace pats {
 
@@ -81,6 +81,16 @@ __device__ __forceinline__ float reduce8_strided(const float (&p)[8], Op op, int
     const bool b3 = lane & 8;
     const float keep = b3 ? q[1] : q[0], send = b3 ? q[0] : q[1];
     return op(keep, dpp_f<DPP_ROW_ROR8>(send));
+}
+
+// ---- shared by the two fine-level block solvers (sinkhorn_blk.hip, sinkhorn_blk2w.hip) --------------------------------------------
+// num / den on the raw reciprocal unit (v_rcp_f32, 1 ulp): the solvers' a = mu / sum, b = nu / sum
+__device__ __forceinline__ float mul_rcp(float num, float den) { return num * __builtin_amdgcn_rcpf(den); }
+// a lane group's nine scalings from their padded, 16-byte aligned slot in LDS: two 16-byte reads and one dword
+__device__ __forceinline__ void load9(const float* v, float (&o)[9]) {
+    const f4v a = *reinterpret_cast<const f4v*>(v), b = *reinterpret_cast<const f4v*>(v + 4);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    o[8] = v[8];
 }
 
 // value of lane (lane ^ X), X < 32: ds_swizzle bit-mask mode (and = 0x1f, or = 0, xor = X)

@@ -21,7 +21,7 @@
 //    (no flag buffer, no second launch, no host involvement; inputs that are themselves inf / NaN take the same
 //    route and come out as the fp32 chain has them).  fp16 subnormals are flushed by the matrix pipe; the 2^6
 //    prescale keeps `lo` normal down to |x| = 0.004, below which an operand is carried with an absolute error
-//    <= 2^-20 (at most 1e-6 |y| in one product).  Accumulators come out scaled by 2^12 (UNSCALE undoes it exactly).
+//    <= 2^-20 (at most 1e-6 |y| in one product).  Accumulators come out scaled by 2^12 (UNS of split_f16.hpp undoes it exactly).
 //
 //  * tile_f32 (v_mfma_f32_32x32x2_f32; bitwise a k-ordered fmaf chain): slabs of 8 channels x 160 columns per
 //    side, staged global -> registers -> LDS, double-buffered.
@@ -42,7 +42,7 @@
 // 1.98 ms): 320-thread workgroups with one tile row per wave (balanced, 80 accumulator registers, but two 5-wave
 // workgroups do not pack onto four SIMDs: 2.5-3.1 ms with dword loads, 16-byte loads or 32-channel chunks alike).
 #pragma once
-#include "common.hpp"
+#include "split_f16.hpp"
 
 namespace pats {
 namespace mt {
@@ -55,8 +55,6 @@ typedef unsigned u4c __attribute__((ext_vector_type(4)));
 
 constexpr int CT = 160, KC = 8, CPT = KC * CT / 256;      // workgroup tile edge; fp32 path: k-chunk, floats per thread per slab
 constexpr int SKC = 16, SQ = 2 * SKC * CT / (4 * 256);    // split path: channels per chunk, 4-channel items per thread (5)
-constexpr float PRESCALE = 64.0f;                         // 1023 * 64 < 65504, the largest fp16
-constexpr float UNSCALE = 1.0f / (PRESCALE * PRESCALE);   // exact power of two
 
 struct __attribute__((aligned(16))) LdsF32 {
     float a[2][KC][CT];
@@ -129,8 +127,8 @@ __device__ __forceinline__ void tile_f32(Src& src, LdsF32& lds, f32x16 (&acc)[7]
 // x * 2^6 = hi + lo for two consecutive channels of one column.  Scalar multiplies / fmas on purpose (build with
 // -fno-slp-vectorize): packed fp32 math would first have to move the operands into adjacent registers.
 __device__ __forceinline__ void split2(float x0, float x1, unsigned& hi, unsigned& lo) {
-    const h2c h = __builtin_convertvector(f2c{x0 * PRESCALE, x1 * PRESCALE}, h2c);                 // v_cvt_pk_f16_f32, RNE
-    const float r0 = fmaf(x0, PRESCALE, -(float)h.x), r1 = fmaf(x1, PRESCALE, -(float)h.y);        // exact
+    const h2c h = __builtin_convertvector(f2c{x0 * PRE, x1 * PRE}, h2c);                 // v_cvt_pk_f16_f32, RNE
+    const float r0 = fmaf(x0, PRE, -(float)h.x), r1 = fmaf(x1, PRE, -(float)h.y);        // exact
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f2c{r0, r1}, h2c));
 }
@@ -336,7 +334,7 @@ __device__ __forceinline__ float tile(Src& s0, Src* s1, Lds& lds, f32x16 (&acc)[
     if (SPLIT) {
         split_accumulate<ROW4>(s0, lds.s, acc, row4, t, wave);
         if (s1) split_accumulate<ROW4>(*s1, lds.s, acc, row4, t, wave);
-        if (split_finite<ROW4>(s0, acc, row4, t, wave)) return UNSCALE;
+        if (split_finite<ROW4>(s0, acc, row4, t, wave)) return UNS;
         clear(acc);
     }
     tile_f32<ROW4>(s0, lds.f, acc, row4, t, wave);

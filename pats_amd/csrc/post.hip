@@ -6,7 +6,7 @@
 //                                                   first_layer.py:162  second_layer.py:243
 // All HBM-bound single-pass kernels; column-direction work maps lanes to consecutive columns so
 // every wave load is one contiguous segment.
-#include "common.hpp"
+#include "launch.hpp"
 
 namespace pats {
 

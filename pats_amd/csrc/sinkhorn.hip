@@ -18,7 +18,7 @@
 // log-sum-exp:  lse(t) = (log2(sum_j 2^(t_j*log2e - mI)) + mI) * ln2  with the integer
 // stabiliser mI = ceil(max_j t_j * log2e): max-subtracted like ATen's logsumexp, exact stabiliser
 // arithmetic, one v_exp_f32 per element.
-#include "common.hpp"
+#include "launch.hpp"
 #include "third_device.hpp"
 #include "cost65_device.hpp"
 #include <stdlib.h>
@@ -64,14 +64,10 @@ ot_prep_kernel(const float* __restrict__ ns, int ns_len, int M, int N, float ms_
 // i.e. the same fixed-point sequence (same iterate after every sweep), but one FMA per element per
 // half-sweep instead of add/max/sub/exp/add.  The duals return to log space once at the end:
 // u_i = log a_i - r_i, v_j = log b_j - c_j, Z_out = ((Z + u) + v) - norm from the ORIGINAL Z.
-// Guard: entries of K below 2^-126 flush to zero; their true mass is < 2^-126 * a_i * b_j, so the
-// result is unaffected as long as the scalings stay below 2^30.  Each problem checks
-// max(a, b) <= 2^30 and finiteness at the end and otherwise re-runs itself with the max-subtracted
-// log-sum-exp sweeps (the code below each linear block), which have no range restriction.
-constexpr float SCALE_GUARD = 1073741824.0f;   // 2^30
+// Guard (SCALE_GUARD / scaling_ok of common.hpp): each problem checks its scalings at the end and otherwise re-runs itself with the
+// max-subtracted log-sum-exp sweeps (the code below each linear block), which have no range restriction.
 
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ bool scaling_ok(float x) { return x <= SCALE_GUARD && x > 0.f; }
 
 __device__ __forceinline__ float lse_finish(float s, float mI) {
     return (fast_log2(s) + mI) * LN2;
@@ -1179,8 +1175,6 @@ sinkhorn_cu2_kernel(SrcView src, int M, int N, const float* __restrict__ log_mu,
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t stream_workspace_bytes(int64_t batch, int M, int N);
 static inline size_t al256_fwd(int64_t batch, int M, int N) { return align256(stream_workspace_bytes(batch, M, N)); }
 static inline bool stream_shape(int M, int N) { return (int64_t)M * N > 304 * 320 && N <= 512 * 9; }
 
@@ -1222,10 +1216,6 @@ static int launch_wg(const SrcView& src, int64_t batch, int M, int N, const floa
     return check_launch("sinkhorn_wg_kernel");
 }
 
-int launch_stream(const float* base, int64_t stride, int ld, int rows, int cols, const float* alpha,
-                  int64_t batch, int M, int N, const float* log_mu, const float* log_nu, const float* norm,
-                  int iters, float* out, void* ws, int* fail, hipStream_t st);
-
 constexpr int CU_RPW = 19, CU_CPL = 5;            // 16 * 19 = 304 rows, 64 * 5 = 320 columns
 static inline bool cu_shape(int M, int N) { return M <= 16 * CU_RPW && N <= 64 * CU_CPL && M * N >= 96 * 96; }
 
@@ -1263,18 +1253,6 @@ static inline int redo_mode() {
     return m;
 }
 
-namespace pats {
-int launch_blk145(int mode, const float* Z, int64_t batch, const float* log_mu, const float* log_nu,
-                  const float* ns, const float* one, int iters, float bias_k, float* out, int* fail,
-                  uint8_t* col_nomatch, hipStream_t st, const int64_t* live = nullptr);     // sinkhorn_blk.hip
-int launch_col_flags(const float* Z, int64_t batch, int M, int N, uint8_t* col_nomatch, const int* only_if,
-                     hipStream_t st);                       // post.hip
-bool fine_w2_enabled();                                     // sinkhorn_blk2w.hip: the two-wave form of the same kernel
-int launch_blk145_w2(int mode, const float* Z, int64_t batch, const float* log_mu, const float* log_nu, const float* ns,
-                     const float* one, int iters, float bias_k, float* out, int* fail, uint8_t* col_nomatch, hipStream_t st,
-                     const int64_t* live);
-}
-
 // 145 x 145: the register-block kernel solves in the linear domain and flags the problems whose
 // scalings left the guard band; sinkhorn_rc_kernel then re-solves exactly those with log-sum-exp
 // sweeps.  Without flag storage (no workspace), for iters == 0 or in forced-log mode the rc kernel
@@ -1307,9 +1285,6 @@ static int launch_fine145(int mode, const float* Z, int64_t batch, const float* 
 // band come back as their raw scores in `out` and the log-domain kernel redoes them IN PLACE (it stages the whole matrix in
 // LDS before it writes).  *applied = false: the caller takes the two-kernel path (the default; also forced log domain, iters == 0).
 namespace pats {
-bool fine_fused();       // host.cpp
-int launch_blk145_fused(const float* d0, const float* d1, int D, int64_t batch, const float* ns, const float* one, int iters,
-                        float bias_k, float* out, int* fail, uint8_t* col_nomatch, hipStream_t st, const int64_t* live);
 int launch_fine145_fused(const float* d0, const float* d1, int D, int64_t batch, const float* ns, const float* one, int iters,
                          float bias_k, float* out, int* fail, uint8_t* col_nomatch, hipStream_t st, bool* applied,
                          const int64_t* live) {
@@ -1524,24 +1499,37 @@ extern "C" int pats_third_level_f32(const float* feat0, const float* feat1, int6
 }
 
 // Both of the above on descriptors of any pats_map_dtype_t: P_dev == NULL is pats_third_level_f32 (scale_x / scale_y required,
-// Z optional), a count is pats_third_level_counted_f32 (scale_x / scale_y both NULL or both given, no Z).
+// Z optional), a count is pats_third_level_counted_f32 (scale_x / scale_y both NULL or both given, no Z).  THE checked body of the
+// typed entries (`who` = the entry's name in its messages); want_conf: the entry takes conf [P_cap,16] and requires it.
+static int third_level_typed_impl(const char* who, const void* feat0, const void* feat1, pats_map_dtype_t dtype, int64_t P_cap,
+                                  const int64_t* P_dev, int D, const float* scale, const float* scale_x, const float* scale_y,
+                                  const int64_t* p_s, const int64_t* p_t, int iters, int outdoor, float* mkpts0_f, float* mkpts1_f,
+                                  float* label, uint8_t* if_matching1, float* Z, bool want_conf, float* conf, pats_stream_t stream) {
+    PATS_REQUIRE(known_elem_type((int)dtype), "%s: unknown descriptor dtype %d", who, (int)dtype);
+    PATS_REQUIRE(P_cap >= 0 && D > 0 && (D % 32) == 0 && D <= 512 && iters >= 0,
+                 "%s: bad shape (D must be a multiple of 32, at most 512)", who);
+    if (P_cap == 0) return PATS_OK;
+    if (want_conf) {
+        PATS_REQUIRE(conf, "%s: null conf", who);
+        PATS_REQUIRE((uintptr_t)conf % 4 == 0, "%s: conf must be 4-byte aligned", who);
+    }
+    PATS_REQUIRE(feat0 && feat1 && scale && p_s && p_t && mkpts0_f && mkpts1_f && label && if_matching1 &&
+                     (P_dev ? (scale_x == nullptr) == (scale_y == nullptr) : scale_x && scale_y),
+                 "%s: null pointer", who);
+    PATS_REQUIRE(!(P_dev && Z), "%s: the plan is not available with a device-side count", who);
+    PATS_REQUIRE((uintptr_t)feat0 % desc_elem_bytes((int)dtype) == 0 && (uintptr_t)feat1 % desc_elem_bytes((int)dtype) == 0,
+                 "%s: descriptors must be aligned to their element size (%d bytes)", who, (int)desc_elem_bytes((int)dtype));
+    return third_level_impl(feat0, feat1, (int)dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
+                            mkpts0_f, mkpts1_f, label, if_matching1, Z, stream, conf);
+}
+
 extern "C" int pats_third_level_typed(const void* feat0, const void* feat1, pats_map_dtype_t dtype, int64_t P_cap,
                                       const int64_t* P_dev, int D, const float* scale, const float* scale_x,
                                       const float* scale_y, const int64_t* p_s, const int64_t* p_t, int iters, int outdoor,
                                       float* mkpts0_f, float* mkpts1_f, float* label, uint8_t* if_matching1, float* Z,
                                       pats_stream_t stream) {
-    PATS_REQUIRE(known_elem_type((int)dtype), "third_level_typed: unknown descriptor dtype %d", (int)dtype);
-    PATS_REQUIRE(P_cap >= 0 && D > 0 && (D % 32) == 0 && D <= 512 && iters >= 0,
-                 "third_level_typed: bad shape (D must be a multiple of 32, at most 512)");
-    if (P_cap == 0) return PATS_OK;
-    PATS_REQUIRE(feat0 && feat1 && scale && p_s && p_t && mkpts0_f && mkpts1_f && label && if_matching1 &&
-                     (P_dev ? (scale_x == nullptr) == (scale_y == nullptr) : scale_x && scale_y),
-                 "third_level_typed: null pointer");
-    PATS_REQUIRE(!(P_dev && Z), "third_level_typed: the plan is not available with a device-side count");
-    PATS_REQUIRE((uintptr_t)feat0 % desc_elem_bytes((int)dtype) == 0 && (uintptr_t)feat1 % desc_elem_bytes((int)dtype) == 0,
-                 "third_level_typed: descriptors must be aligned to their element size (%d bytes)", (int)desc_elem_bytes((int)dtype));
-    return third_level_impl(feat0, feat1, (int)dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
-                            mkpts0_f, mkpts1_f, label, if_matching1, Z, stream);
+    return third_level_typed_impl("third_level_typed", feat0, feat1, dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters,
+                                  outdoor, mkpts0_f, mkpts1_f, label, if_matching1, Z, false, nullptr, stream);
 }
 
 // pats_third_level_typed that also writes the per-match confidence conf [P_cap,16] (rows past *P_dev are not written): the same
@@ -1551,20 +1539,8 @@ extern "C" int pats_third_level_typed_conf(const void* feat0, const void* feat1,
                                            const float* scale_y, const int64_t* p_s, const int64_t* p_t, int iters, int outdoor,
                                            float* mkpts0_f, float* mkpts1_f, float* label, uint8_t* if_matching1, float* Z,
                                            float* conf, pats_stream_t stream) {
-    PATS_REQUIRE(known_elem_type((int)dtype), "third_level_typed_conf: unknown descriptor dtype %d", (int)dtype);
-    PATS_REQUIRE(P_cap >= 0 && D > 0 && (D % 32) == 0 && D <= 512 && iters >= 0,
-                 "third_level_typed_conf: bad shape (D must be a multiple of 32, at most 512)");
-    if (P_cap == 0) return PATS_OK;
-    PATS_REQUIRE(conf, "third_level_typed_conf: null conf");
-    PATS_REQUIRE((uintptr_t)conf % 4 == 0, "third_level_typed_conf: conf must be 4-byte aligned");
-    PATS_REQUIRE(feat0 && feat1 && scale && p_s && p_t && mkpts0_f && mkpts1_f && label && if_matching1 &&
-                     (P_dev ? (scale_x == nullptr) == (scale_y == nullptr) : scale_x && scale_y),
-                 "third_level_typed_conf: null pointer");
-    PATS_REQUIRE(!(P_dev && Z), "third_level_typed_conf: the plan is not available with a device-side count");
-    PATS_REQUIRE((uintptr_t)feat0 % desc_elem_bytes((int)dtype) == 0 && (uintptr_t)feat1 % desc_elem_bytes((int)dtype) == 0,
-                 "third_level_typed_conf: descriptors must be aligned to their element size (%d bytes)", (int)desc_elem_bytes((int)dtype));
-    return third_level_impl(feat0, feat1, (int)dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t, iters, outdoor,
-                            mkpts0_f, mkpts1_f, label, if_matching1, Z, stream, conf);
+    return third_level_typed_impl("third_level_typed_conf", feat0, feat1, dtype, P_cap, P_dev, D, scale, scale_x, scale_y, p_s, p_t,
+                                  iters, outdoor, mkpts0_f, mkpts1_f, label, if_matching1, Z, true, conf, stream);
 }
 
 // validated arguments.  P_dev: throughput mode - no host read between the merge that decides P and this launch: the grid

@@ -19,6 +19,7 @@
 // half-sweep through LDS and needs 13 KB of LDS, so three workgroups share a CU and the sweeps are
 // VALU-bound.  A problem whose scalings leave the guard band sets fail[p]; the host re-runs those
 // with sinkhorn_rc_kernel's log-sum-exp sweeps.
+#include "launch.hpp"
 #include "lane_reduce.hpp"
 #include "mfma_tile.hpp"
 #include <stdlib.h>
@@ -28,15 +29,6 @@ namespace pats {
 namespace {
 
 constexpr int N_ = 145, NB = 144, BS = 9, VS = 12;     // VS: padded stride of a 9-float group in LDS
-constexpr float BLK_GUARD = 1073741824.0f;              // 2^30, as sinkhorn.hip
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool ok_scale(float x) { return x <= BLK_GUARD && x > 0.f; }
-__device__ __forceinline__ float uni(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
-}
-
 struct __attribute__((aligned(16))) BlkLds {
     float va[16 * VS];           // row-indexed vector: entry 9I + r at [I * VS + r]
     float vb[16 * VS];           // column-indexed vector: entry 9J + c at [J * VS + c]
@@ -75,14 +67,6 @@ __device__ __forceinline__ f2e blk_mul2(f2e a, f2e b) {
 #else
     return a * b;
 #endif
-}
-
-__device__ __forceinline__ float mul_rcp(float num, float den) { return num * __builtin_amdgcn_rcpf(den); }
-
-__device__ __forceinline__ void load9(const float* v, float (&o)[BS]) {
-    const f4v a = *reinterpret_cast<const f4v*>(v), b = *reinterpret_cast<const f4v*>(v + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    o[8] = v[8];
 }
 
 // sum over the 16 lanes of a DPP row of nine values; value J lands in lane J (J < 9)
@@ -394,7 +378,7 @@ sinkhorn_blk145_kernel(const float* __restrict__ Zin, const float* __restrict__ 
     }
 
     // ---- guard: every scaling finite, positive, <= 2^30 ---------------------------------------------------
-    const bool okl = (!rown || ok_scale(a)) && (!cown || ok_scale(b)) && ok_scale(a_d) && ok_scale(b_d);
+    const bool okl = (!rown || scaling_ok(a)) && (!cown || scaling_ok(b)) && scaling_ok(a_d) && scaling_ok(b_d);
     const bool okw = __all(okl);
     wg_barrier();
     if (lane == 0) lds.misc[wave] = okw ? 1.f : 0.f;

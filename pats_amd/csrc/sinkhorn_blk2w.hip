@@ -18,6 +18,7 @@
 // the score matrix; ~235 registers: two waves per SIMD.  Same guard, same flags, same epilogue arithmetic as the four-wave kernel;
 // summation ORDER differs (results agree to rounding; the match flags of a plan are those of its own values).
 // PATS_FINE_W2=0 selects the four-wave kernel (read once per process).
+#include "launch.hpp"
 #include "lane_reduce.hpp"
 #include <stdlib.h>
 
@@ -27,16 +28,7 @@ namespace {
 
 constexpr int N_ = 145, NB = 144, BR = 9, BC = 18;
 constexpr int VA_S = 12, VB_S = 20;                     // padded strides of a lane group's 9 / 18 floats in LDS (16-byte reads)
-constexpr float W2_GUARD = 1073741824.0f;               // 2^30, as sinkhorn.hip
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f4a __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ bool ok_scale(float x) { return x <= W2_GUARD && x > 0.f; }
-__device__ __forceinline__ float uni(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
-}
-__device__ __forceinline__ float mul_rcp(float num, float den) { return num * __builtin_amdgcn_rcpf(den); }
 
 // (wave_lds_sync(): common.hpp - every intra-wave hand-over of this kernel sits behind it)
 
@@ -56,11 +48,6 @@ struct __attribute__((aligned(16))) W2Lds {
     float misc[8];
 };
 
-__device__ __forceinline__ void load9(const float* v, float (&o)[BR]) {
-    const f4v a = *reinterpret_cast<const f4v*>(v), b = *reinterpret_cast<const f4v*>(v + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    o[8] = v[8];
-}
 __device__ __forceinline__ void load18(const float* v, float (&o)[BC]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -330,8 +317,8 @@ sinkhorn_blk145w2_kernel(const float* __restrict__ Zin, const float* __restrict_
     }
 
     // ---- guard: every scaling finite, positive, <= 2^30 ----------------------------------------------------------------------------
-    const bool okl = ok_scale(aA) && (!own8 || ok_scale(a8)) && ok_scale(bA) && ok_scale(bB) && (!ownC || ok_scale(bC)) && ok_scale(a_d) &&
-                     ok_scale(b_d);
+    const bool okl = scaling_ok(aA) && (!own8 || scaling_ok(a8)) && scaling_ok(bA) && scaling_ok(bB) && (!ownC || scaling_ok(bC)) && scaling_ok(a_d) &&
+                     scaling_ok(b_d);
     const bool okw = __all(okl);
     wg_barrier();                                  // (the last sweep's reads of red[] are done)
     if (lane == 0) lds.misc[w] = okw ? 1.f : 0.f;

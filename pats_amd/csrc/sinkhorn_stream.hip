@@ -24,7 +24,7 @@
 //
 // Set-up (row max, column max of Z - r, K build) and the epilogue (duals back to log space,
 // Z_out = ((Z + u) + v) - norm, guard) are plain streaming kernels.  Deterministic: no atomics.
-#include "common.hpp"
+#include "launch.hpp"
 #include "lane_reduce.hpp"
 #include <algorithm>
 #ifdef PATS_DIAG
@@ -501,11 +501,11 @@ stream_guard_kernel(const float* __restrict__ a, int M, const float* __restrict_
     float bad = 0.f;
     for (int i = threadIdx.x; i < M; i += ST) {
         const float x = a[(int64_t)b * M + i];
-        if (!(x <= 1073741824.0f && x > 0.f)) bad = 1.f;
+        if (!scaling_ok(x)) bad = 1.f;
     }
     for (int j = threadIdx.x; j < N; j += ST) {
         const float x = bvec[(int64_t)b * N + j];
-        if (!(x <= 1073741824.0f && x > 0.f)) bad = 1.f;
+        if (!scaling_ok(x)) bad = 1.f;
     }
     bad = block_allreduce(bad, OpMax(), scratch);
     if (threadIdx.x == 0) fail[b] = (bad > 0.f || (err && *err != 0)) ? 1 : 0;      // err: the resident kernel gave up at a barrier
@@ -533,7 +533,6 @@ stream_finish_kernel(SrcViewS src, int M, int N, const float* __restrict__ a,
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // A problem's share of the `partial` area in floats: ceil(M / 16) rows of N, rounded up to a multiple of FOUR floats.  The resident
 // kernel puts every problem's rows (pitch NP = N rounded to 4) and its 8-byte {b_j, tag} granules at partial + problem * stride: an odd
@@ -550,11 +549,11 @@ __global__ void stream_granule_clear_kernel(float* partial, int64_t stride, size
 
 size_t stream_workspace_bytes(int64_t batch, int M, int N) {
     size_t f = 0;
-    f += al256((size_t)batch * M * N * 4);          // K
-    f += al256((size_t)batch * res_partial_stride(M, N) * 4);   // partial (a problem's share rounded to 16 bytes: see res_partial_stride)
-    f += 2 * al256((size_t)batch * M * 4);          // r, a
-    f += 2 * al256((size_t)batch * N * 4);          // c, b
-    f += al256(512 * (size_t)batch + 512);          // the resident kernel's arrival counters (8 x 64 B a problem) and its give-up flag
+    f += align256((size_t)batch * M * N * 4);          // K
+    f += align256((size_t)batch * res_partial_stride(M, N) * 4);   // partial (a problem's share rounded to 16 bytes: see res_partial_stride)
+    f += 2 * align256((size_t)batch * M * 4);          // r, a
+    f += 2 * align256((size_t)batch * N * 4);          // c, b
+    f += align256(512 * (size_t)batch + 512);          // the resident kernel's arrival counters (8 x 64 B a problem) and its give-up flag
     return f;
 }
 
@@ -586,12 +585,12 @@ int launch_stream(const float* base, int64_t stride, int ld, int rows, int cols,
     const int RBr = rb17 ? 17 : 16;
     const int nblk = (M + RBr - 1) / RBr;
     char* p = (char*)ws;
-    float* K = (float*)p;        p += al256((size_t)batch * M * N * 4);
-    float* partial = (float*)p;  p += al256((size_t)batch * res_partial_stride(M, N) * 4);  // sized for blocks of 16, 16-byte shares
-    float* r = (float*)p;        p += al256((size_t)batch * M * 4);
-    float* a = (float*)p;        p += al256((size_t)batch * M * 4);
-    float* c = (float*)p;        p += al256((size_t)batch * N * 4);
-    float* bv = (float*)p;       p += al256((size_t)batch * N * 4);
+    float* K = (float*)p;        p += align256((size_t)batch * M * N * 4);
+    float* partial = (float*)p;  p += align256((size_t)batch * res_partial_stride(M, N) * 4);  // sized for blocks of 16, 16-byte shares
+    float* r = (float*)p;        p += align256((size_t)batch * M * 4);
+    float* a = (float*)p;        p += align256((size_t)batch * M * 4);
+    float* c = (float*)p;        p += align256((size_t)batch * N * 4);
+    float* bv = (float*)p;       p += align256((size_t)batch * N * 4);
     unsigned* cnt = (unsigned*)p;
     int* err = (int*)(p + 512 * (size_t)batch);
     const dim3 rows_grid(M, (unsigned)batch), blk_grid(nblk, (unsigned)batch), col_grid((N + 63) / 64, (unsigned)batch);

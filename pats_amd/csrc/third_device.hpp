@@ -50,13 +50,12 @@ __device__ __forceinline__ int64_t live_problems(const Fused65Args& g) {
 constexpr uint8_t THIRD_REDO = 0xEE; // if_matching1[p*16] of a problem the log-domain kernel must redo
 // conf: [P,16] per-match confidence or null.  Not a member of Fused65Args: the *_conf_kernel instantiations take it as a kernel
 // argument of their own, so the plain kernels' argument block - and with it their code - stays what it was.
-int launch_third_fused(const Fused65Args& g, hipStream_t st, float* conf = nullptr);
+int launch_third_fused(const Fused65Args& g, hipStream_t st, float* conf = nullptr);      // third_fused.hip
+// its linear-domain solve (third_fused3.hip): flags the problems that leave the guard band with THIRD_REDO
+int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf);
 
 // ---- shared by the two register-block files (third_fused.hip, third_fused3.hip) ---------------------------------------------
 constexpr int SST = 36;                 // staging row stride (floats): 16-byte aligned rows
-constexpr float GUARD = 1073741824.0f;  // 2^30
-__device__ __forceinline__ bool sc_ok(float x) { return x <= GUARD && x > 0.f; }
-__device__ __forceinline__ float uni(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
 // Every problem takes the same time, so without this all resident waves stay phase-locked: the
 // chip alternates between "everyone streams descriptors" (HBM-bound, VALU idle) and "everyone

@@ -27,11 +27,6 @@
 
 namespace pats {
 
-int sinkhorn_mode();
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-
 struct __attribute__((aligned(16))) BlkLds {
     float va[72];                // row-indexed vector (r, then a / u); [64] = dustbin row's value
     float vb[72];                // column-indexed vector (c, then b / v); [64] = dustbin column's value
@@ -210,7 +205,7 @@ __device__ __forceinline__ void third_v2_problem(const Fused65Args& g, const int
                     lds.vb[colj] = b;
                 }
             }
-            if (__all(sc_ok(a) && sc_ok(b)) && sc_ok(a64) && sc_ok(b64)) {
+            if (__all(scaling_ok(a) && scaling_ok(b)) && scaling_ok(a64) && scaling_ok(b64)) {
                 sc_r = a; sc_c = b; sc_c64 = b64;
                 // u = log a - r, v = log b - c; the plan only needs the products below
                 dual_r = logf(a) - r_own; dual_c = logf(b) - c_own;
@@ -385,8 +380,6 @@ static void launch_v2(const Fused65Args& g, dim3 grid, hipStream_t st, float* co
         return 0;
     });
 }
-
-int launch_third_fused3(const Fused65Args& g0, hipStream_t st, float* conf);      // third_fused3.hip
 
 int launch_third_fused(const Fused65Args& g0, hipStream_t st, float* conf) {
     Fused65Args g = g0;

@@ -39,9 +39,6 @@
 
 namespace pats {
 
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-
 struct __attribute__((aligned(16))) Blk3Lds {
     float vb[72];                // column-indexed vector (c, then b)
     float erow[72];              // Z[64][j]
@@ -442,7 +439,7 @@ __device__ __forceinline__ void third3_problem(const Fused65Args& g, const int64
 #ifdef PATS_DIAG
     const unsigned ab_bits = wave_xor_bits(fbits(a) ^ (fbits(b) * 3u) ^ (fbits(a64) * 5u) ^ (fbits(b64) * 7u));
 #endif
-    if (!(__all(sc_ok(a) && sc_ok(b)) && sc_ok(a64) && sc_ok(b64))) {
+    if (!(__all(scaling_ok(a) && scaling_ok(b)) && scaling_ok(a64) && scaling_ok(b64))) {
         // guard tripped: the stabilised instantiation of this solve, then third_fused_kernel (log-sum-exp sweeps), redo this problem
         // in scan mode (ST: the sentinel is already there and the trip already counted)
         if (!ST && lane == 0) {

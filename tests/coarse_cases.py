@@ -31,7 +31,7 @@ SWEEPS_OT = (1, 100)
 B_SINKHORN, B_OT = 3, 2
 AMPS = (0.5, 3.0)
 ALPHAS = (0.0, 0.5, 1.3)
-SCALE_GUARD = 2.0 ** 30                    # csrc/sinkhorn.hip: a linear-domain solve whose scalings leave (0, 2^30] is redone
+SCALE_GUARD = 2.0 ** 30                    # csrc/common.hpp: a linear-domain solve whose scalings leave (0, 2^30] is redone
 
 # ---- the dispatch, mirrored (csrc/sinkhorn.hip: cu_shape, stream_shape, launch_wg) ------------------------------------------
 CU_ROWS, CU_COLS = 16 * 19, 64 * 5         # 304 x 320
