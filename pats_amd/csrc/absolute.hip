@@ -704,7 +704,8 @@ extern "C" int pats_absolute_score_by_pair_f32(const float* points, const float*
     PATS_REQUIRE(chunks <= 0x7fffffff / pairs, "%s: pairs = %lld gives a grid of %lld x %lld workgroups (< 2^31)", who, (long long)pairs,
                  (long long)pairs, (long long)chunks);
     const int stage_n = abs_stage_slots(counts_in, stride, cap, 2);
-    if (!epi_lds_raised<absolute_score_kernel>(ABS_LDS)) {
+    static DeviceGrants grants;
+    if (!grants.get({{(const void*)absolute_score_kernel, ABS_LDS}}).granted) {
         set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, ABS_LDS);
         return PATS_ERR_UNSUPPORTED;
     }
@@ -740,7 +741,8 @@ extern "C" int pats_absolute_polish_by_pair_f32(const float* points, const float
     PATS_REQUIRE(steps >= 1 && steps <= ABS_POLISH_MAX_STEPS, "%s: steps = %d (1 .. %d)", who, steps, ABS_POLISH_MAX_STEPS);
     PATS_REQUIRE(best || M == 1, "%s: null best needs M == 1, got M = %lld", who, (long long)M);
     const int stage_n = abs_stage_slots(counts_in, stride, cap, 1);
-    if (!epi_lds_raised<absolute_polish_kernel>(ABS_LDS)) {
+    static DeviceGrants grants;
+    if (!grants.get({{(const void*)absolute_polish_kernel, ABS_LDS}}).granted) {
         set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, ABS_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

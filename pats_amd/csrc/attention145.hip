@@ -220,15 +220,8 @@ int launch_attention145(const float* query, const float* key, const float* value
     static const bool off = [] { const char* e = diag_env("PATS_ATTN145"); return e && atoi(e) == 0; }();     // A/B switch
     if (off || n > 16 * A_T || m > 16 * A_T || n <= 96 || m <= 96 || dim > 16 * A_DT || dim <= 32 || !flag) return PATS_ERR_UNSUPPORTED;
     if (batch * heads + 8 >= (1ll << 31)) return PATS_ERR_UNSUPPORTED;
-    static int state[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); dev = 0; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)attention145_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    if (state[dev] != 1) return PATS_ERR_UNSUPPORTED;
+    static DeviceGrants grants;
+    if (!grants.get({{(const void*)attention145_kernel, A_LDS}}).granted) return PATS_ERR_UNSUPPORTED;
     const int64_t items = batch * heads, per_xcd = (items + 7) / 8;
     A145Args g{query, key, value, out, dim, heads, n, m, items, per_xcd, (float)((double)UNS / sqrt((double)dim) * 1.4426950408889634), flag, gate};
     hipLaunchKernelGGL(attention145_kernel, dim3((unsigned)(8 * per_xcd)), dim3(640), A_LDS, st, g);

@@ -50,6 +50,23 @@ unsigned long long* fallback_counter();
 bool gnn_redo_deferred();
 int* gnn_overflow_flag();
 
+// ---- what a DEVICE grants (host.cpp) -------------------------------------------------------------------------------------------
+// A launch gets 64 KiB of dynamic LDS unasked; a kernel that needs more has its limit raised, and both that grant and the CU count
+// that sizes a persistent grid belong to a DEVICE (one process may drive several GPUs), never to the process.  A call site keeps a
+// function-local `static DeviceGrants`: get() asks - once per device - for the kernels' limits in the order given, up to the first
+// refusal (remembered, not retried; the runtime's last error cleared), and answers {all granted, the device's CUs}; an empty list
+// asks for the CUs alone.  No current device, or an id outside 0..63: {false, 256}.  Lock-free: host threads that meet at the first
+// call ask for the same limits and store the same answer.  (attention.hip sets its attribute on every launch instead - see there.)
+constexpr int MAX_DEVICES = 64;
+int device_slot();                                      // the current device's id if it is one of 0 .. MAX_DEVICES - 1, else -1
+struct LdsLimit { const void* kernel; int bytes; };
+struct DeviceGrant { bool granted; int n_cu; };         // n_cu: 256 where the device does not say
+struct DeviceGrants {
+    int state[MAX_DEVICES];                             // zero-initialised (static): 0 = not asked yet, 1 = granted, -1 = refused
+    int n_cu[MAX_DEVICES];
+    DeviceGrant get(std::initializer_list<LdsLimit> limits);
+};
+
 #define PATS_REQUIRE(cond, ...)               \
     do {                                      \
         if (!(cond)) {                        \

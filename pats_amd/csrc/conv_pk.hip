@@ -393,17 +393,9 @@ int launch_conv_pack(const float* wt, int K, int M, void* packed, hipStream_t st
 
 // 1 if this device grants the kernel its 72 KB of dynamic LDS (asked once per device)
 bool conv_pk_ready() {
-    static int state[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); dev = 0; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)conv_pk_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PK_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)conv_pk_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PK_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)conv_pk_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PK_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1;
+    static DeviceGrants grants;
+    return grants.get({{(const void*)conv_pk_kernel<1, false>, PK_LDS}, {(const void*)conv_pk_kernel<1, true>, PK_LDS},
+                       {(const void*)conv_pk_kernel<2, true>, PK_LDS}}).granted;
 }
 
 // y = W . (x0 | x1) with packed W; K0, K1 multiples of 8.  redo: as conv_lean_kernel (the caller queues conv1x1_kernel behind).

@@ -281,21 +281,6 @@ inline int epi_check_scored(const char* who, const EpiArg& first, const float* m
     return PATS_OK;
 }
 
-// A launch gets 64 KiB of LDS unasked; a kernel whose staging can exceed them has its limit of dynamic LDS raised to `bytes`, once
-// per device.  One instantiation, and with it one state, per kernel
-template <auto Kernel>
-inline bool epi_lds_raised(int bytes) {
-    static int state[64] = {0};                         // per device: 0 = not tried yet, 1 = raised, -1 = refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1;
-}
-
 // the source of a refit - moments, or models and best - and its frame flag.  With moments the kernels get no models: models is
 // nulled and H set to 1, the launch's arguments
 inline int epi_check_refit_source(const char* who, const double* moments, const float*& models, const int32_t* best, int64_t& H, int swapped) {

@@ -540,63 +540,54 @@ bn_finish_kernel(const double* __restrict__ part, int64_t total, int C, const fl
     shift[c] = beta[c] - (float)mean * sc;
 }
 
-static int launch_conv(const ConvArgs& g0, int* redo, hipStream_t st, const int* gate = nullptr) {
+// Which tile runs in front of conv1x1_kernel (which always follows - behind a tile, on the tile's redo flag): a pure function of
+// the shape, the grant and the switches
+enum class ConvTile { plain, lean, ws };
+static ConvTile conv_tile(const ConvArgs& g, bool has_redo, bool ws_granted) {
+    static const bool no_lean = [] { const char* e = diag_env("PATS_CONV_LEAN"); return e && atoi(e) == 0; }();    // A/B switch
+    static const int ws_mode = [] { const char* e = env_switch("PATS_CONV_WS"); return e ? atoi(e) : 1; }();     // A/B switch: 0 off, 2 = also on small grids (tests)
+    if (!has_redo || cost_f32_only() || no_lean || (g.residual && g.residual == g.y)) return ConvTile::plain;
+    // weights-stationary tile: exactly 128 channels in from one source, at most 128 out, and enough column tiles for a
+    // persistent grid of 4 x CUs groups to pay (the third level: 26 325 tiles)
+    const int Kt = g.K0 + g.K1;
+    const bool two = g.K1 > 0;
+    const bool ws = ws_mode != 0 && ws_granted && ((Kt == 128 && !two) || (Kt == 256 && (!two || g.K0 == 128))) &&
+                    g.cols * (int64_t)std::max(g.K0, 1) < (1ll << 31) && (g.cols >= 64 * 4096 || ws_mode == 2);
+    return ws ? ConvTile::ws : ConvTile::lean;
+}
+
+static int launch_conv(const ConvArgs& g0, int* redo, hipStream_t st, const int* gate) {
     ConvArgs g = g0;
     g.gate = gate;
     const bool fp32_only = cost_f32_only();
-    static const bool no_lean = [] { const char* e = diag_env("PATS_CONV_LEAN"); return e && atoi(e) == 0; }();    // A/B switch
     PATS_REQUIRE(g.cols < (1ll << 31), "attentional_propagation: grid too large (split the batch)");
-    const bool lean = redo && !fp32_only && !no_lean && !(g.residual && g.residual == g.y);
-    // weights-stationary tile: exactly 128 channels in from one source, at most 128 out, and enough column tiles for a
-    // persistent grid of 4 x CUs groups to pay (the third level: 26 325 tiles)
-    static const int ws_mode = [] { const char* e = env_switch("PATS_CONV_WS"); return e ? atoi(e) : 1; }();     // A/B switch: 0 off, 2 = also on small grids (tests)
-    const int Kt = g.K0 + g.K1;
-    const bool two = g.K1 > 0;
-    // the tile needs up to the CU's whole 160 KB of LDS as dynamic shared memory: if the runtime will not grant it, the lean
-    // tile computes the same bits
-    // Both the attribute and the CU count belong to a DEVICE: cached per device id (one process may drive several GPUs;
-    // attention.hip sets its attribute on every launch for the same reason), never process-wide.
-    struct PerDevice { int state = 0; int n_cu = 256; };      // state: 0 unknown, 1 granted, -1 refused
-    static PerDevice per_dev[64];
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) { (void)hipGetLastError(); dev_id = 0; }
-    PerDevice& pd = per_dev[dev_id];
-    if (pd.state == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)conv_ws_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)conv_ws_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)conv_ws_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        int v = 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess) (void)hipGetLastError();
-        pd.n_cu = v > 0 ? v : 256;
-        pd.state = ok ? 1 : -1;
-    }
-    const bool ws_lds_ok = pd.state == 1;
-    const bool ws = lean && ws_mode != 0 && ws_lds_ok && ((Kt == 128 && !two) || (Kt == 256 && (!two || g.K0 == 128))) &&
-                    g.cols * (int64_t)std::max(g.K0, 1) < (1ll << 31) && (g.cols >= 64 * 4096 || ws_mode == 2);
-    if (ws) {
-        const int n_cu = pd.n_cu;
+    // the weights-stationary tile needs up to the CU's whole 160 KB of LDS as dynamic shared memory: if the runtime will not grant
+    // it, the lean tile computes the same bits
+    static DeviceGrants grants;
+    const DeviceGrant dev = grants.get({{(const void*)conv_ws_kernel<8, false>, 160 * 1024}, {(const void*)conv_ws_kernel<16, false>, 160 * 1024},
+                                        {(const void*)conv_ws_kernel<16, true>, 160 * 1024}});
+    const ConvTile tile = conv_tile(g, redo != nullptr, dev.granted);
+    g.redo = tile == ConvTile::plain ? nullptr : redo;
+    if (tile == ConvTile::ws) {
+        const int Kt = g.K0 + g.K1;
+        const bool two = g.K1 > 0;
         // weights of one 128-row tile (hi | lo planes, K x 512 bytes) + four groups' double-buffered 4 KB stages: 96 KB at
         // K = 128, the CU's whole 160 KB at K = 256
         const size_t lds = (size_t)2 * (Kt / 4) * LR * sizeof(uint2) + (size_t)4 * 2 * 2 * 4 * WS_LC * sizeof(uint2);
         const int row_tiles = (g.M + LR - 1) / LR;
         const int64_t tiles = (g.cols + WS_LC - 1) / WS_LC;
-        int grid = (int)std::min<int64_t>(n_cu, ((tiles + 3) / 4) * row_tiles);
+        int grid = (int)std::min<int64_t>(dev.n_cu, ((tiles + 3) / 4) * row_tiles);
         grid = std::max(row_tiles, grid - grid % row_tiles);       // whole groups of row tiles
-        g.redo = redo;
         if (Kt == 128) hipLaunchKernelGGL((conv_ws_kernel<8, false>), dim3((unsigned)grid), dim3(1024), lds, st, g, row_tiles);
         else if (!two) hipLaunchKernelGGL((conv_ws_kernel<16, false>), dim3((unsigned)grid), dim3(1024), lds, st, g, row_tiles);
         else hipLaunchKernelGGL((conv_ws_kernel<16, true>), dim3((unsigned)grid), dim3(1024), lds, st, g, row_tiles);
-    } else if (lean) {
+    } else if (tile == ConvTile::lean) {
         static const int nt = diag_env("PATS_CONV_NT") ? atoi(diag_env("PATS_CONV_NT")) : 2;       // A/B switch: 2 or 4 column tiles
         const int lc = 32 * (nt == 4 ? 4 : 2);
         const int64_t lt = (int64_t)((g.M + LR - 1) / LR) * ((g.cols + lc - 1) / lc);
         PATS_REQUIRE(lt < (1ll << 31), "attentional_propagation: grid too large (split the batch)");
-        g.redo = redo;
         if (nt == 4) hipLaunchKernelGGL(conv_lean_kernel<4>, dim3((unsigned)lt), dim3(256), 0, st, g);
         else hipLaunchKernelGGL(conv_lean_kernel<2>, dim3((unsigned)lt), dim3(256), 0, st, g);
-    } else {
-        g.redo = nullptr;
     }
     // 128-row workgroup tiles when they divide M (the 128- and 256-row products of the third level): four full tile
     // rows per workgroup and the kernel without the fifth one - 32 registers less, no spill, no 96-row remainder tile
@@ -615,17 +606,6 @@ static int launch_conv(const ConvArgs& g0, int* redo, hipStream_t st, const int*
 }  // namespace pats
 
 using namespace pats;
-
-extern "C" size_t pats_attentional_propagation_workspace_bytes(int64_t batch, int C, int n, int m) {
-    if (batch < 0 || C <= 0 || n <= 0 || m <= 0) return 0;
-    const size_t qb = align256((size_t)batch * C * n * sizeof(float)), kb = align256((size_t)batch * C * m * sizeof(float));
-    // q, attention output, message [b,C,n]; k, v [b,C,m]; hidden [b,2C,n]; BN scale / shift [2C] each; BN partial sums
-    // (BatchNorm partial sums: BN_SPLITS per channel for the composition, one per workgroup of the fused kernel's grid - at most 512)
-    // (+ the fine level's one-kernel layer: its per-workgroup scratch blocks; its descriptor images overlay q / att / msg / k)
-    const size_t fine = pats::fine_layer_supported(C, 4, n, m) ? align256(pats::fine_scratch_bytes(batch)) : 0;
-    return 3 * qb + 2 * kb + align256((size_t)batch * 2 * C * n * sizeof(float)) + 2 * align256((size_t)2 * C * sizeof(float)) +
-           align256((size_t)2 * C * 512 * 2 * sizeof(double)) + 256 /* seven redo flags + the fused layer's flag */ + fine;
-}
 
 namespace pats {
 // The copy behind a gated redo over a capacity: dst = src for the rows below clamp(*live - live_off, 0, rows) (every row without a
@@ -655,19 +635,246 @@ static int launch_gated_copy(const float* src, float* dst, size_t elems, int64_t
     else hipLaunchKernelGGL((gated_copy_kernel<float>), dim3(grid), dim3(256), 0, st, src, dst, n, gate, row_elems, live, live_off);
     return check_launch("gated_copy_kernel");
 }
+
+// ---- the layer's workspace: offsets from the shape, written once ------------------------------------------------------------------
+// q, attention output, message [b,C,n]; k, v [b,C,m]; hidden [b,2C,n]; BN scale / shift [2C] each; BN partial sums (BN_SPLITS per
+// channel for the composition, one per workgroup of the fused kernel's grid - at most 512); seven redo flags + the fast paths' flag;
+// the per-problem scratch blocks of the fine level's one-kernel layer (its descriptor images overlay q / att / msg / k:
+// fine_layer_path).  pats_attentional_propagation_workspace_bytes returns the total, propagation_impl carves from the offsets.
+struct LayerWorkspace { size_t q, att, msg, k, v, hid, bsc, bsh, bpart, redo, fine_scratch, total; };
+static LayerWorkspace layer_workspace(int64_t batch, int C, int n, int m) {
+    const size_t qb = align256((size_t)batch * C * n * sizeof(float)), kb = align256((size_t)batch * C * m * sizeof(float));
+    const size_t bn = align256((size_t)2 * C * sizeof(float));
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t off = at; at += bytes; return off; };
+    LayerWorkspace L;
+    L.q = take(qb); L.att = take(qb); L.msg = take(qb); L.k = take(kb); L.v = take(kb);
+    L.hid = take(align256((size_t)batch * 2 * C * n * sizeof(float)));
+    L.bsc = take(bn); L.bsh = take(bn);
+    L.bpart = take(align256((size_t)2 * C * 512 * 2 * sizeof(double)));
+    L.redo = take(256);
+    L.fine_scratch = take(fine_layer_supported(C, 4, n, m) ? align256(fine_scratch_bytes(batch)) : 0);
+    L.total = at;
+    return L;
 }
 
+// The stack's (pats_attentional_gnn_packed_f32, P = 2 batch problems): the two descriptor images the layers alternate between and the
+// attention image; OVERLAID on the three - the redo chain runs behind the last launch that reads them - the chain's descriptor buffers
+// d[layer parity][set] and the composition's own workspace; then the projections' scratch area and the flag.
+struct StackWorkspace { size_t tf[2], tf_att, d[2][2], layer, layer_bytes, scratch, flag, total; };
+static StackWorkspace stack_workspace(int64_t batch, int C, int n) {
+    const int64_t P = 2 * batch;
+    const size_t img = align256(fine_image_bytes(P)), db = align256((size_t)batch * C * n * sizeof(float));
+    StackWorkspace S;
+    S.tf[0] = 0; S.tf[1] = img; S.tf_att = 2 * img;
+    S.d[0][0] = 0; S.d[0][1] = db; S.d[1][0] = 2 * db; S.d[1][1] = 3 * db;          // the overlay: from offset 0 again
+    S.layer = 4 * db;
+    S.layer_bytes = layer_workspace(batch, C, n, n).total;
+    S.scratch = std::max(3 * img, S.layer + align256(S.layer_bytes));
+    S.flag = S.scratch + align256(fine_scratch_bytes(P));
+    S.total = S.flag + 256;
+    return S;
+}
+
+// One call of the layer: what the entry was handed, and its workspace carved
+struct LayerCall {
+    const float *x, *source;
+    int64_t batch;
+    int C, heads, n, m;
+    const pats_propagation_weights* w;
+    int bn_train;
+    float bn_eps;
+    const float* residual;
+    float* out;
+    float *q, *att, *msg, *k, *v, *hid, *bsc, *bsh;     // the workspace
+    double* bpart;
+    int* redo;
+    char* fine_scratch;
+    pats_stream_t stream;
+    hipStream_t st;
+    const int64_t* live;
+    int64_t live_off;
+};
+
+// ---- the layer's four paths.  The three fast ones raise `flag` where an activation left the fp16 range of their split operands and
+// return PATS_OK (the call is taken), PATS_ERR_UNSUPPORTED (the device refused the LDS: the next path) or an error ---------------
+
+// The fine level (round 5, gnn_fine.hip): the whole layer in one kernel on (fp32 blocked, TF image) descriptors.  This single-layer
+// entry converts on the way in and out (pats_attentional_gnn_packed_f32 keeps a stack in that form).
+static int fine_layer_path(const LayerCall& c, const void* packed, int* flag) {
+    // OVERLAY: the images and blocked copies lie on the composition's q / att / msg / k buffers, which only the gated redo would use
+    char* tf_x = (char*)c.q;
+    char* tf_s = c.source == c.x ? tf_x : (char*)c.att;
+    char* tf_att = (char*)c.msg;
+    char* tf_out = (char*)c.k;
+    int rc;
+    if ((rc = launch_fine_in(c.x, c.batch, tf_x, c.st))) return rc;
+    if (c.source != c.x && (rc = launch_fine_in(c.source, c.batch, tf_s, c.st))) return rc;
+    // the kernels add the layer's own x (what AttentionalGNN.forward does); any other residual is added by the conversion out
+    rc = launch_fine_layer(tf_x, tf_s, 0, c.residual == c.x ? 1 : 0, c.batch, packed_fine_section(packed, c.C, c.heads), tf_out, tf_att,
+                           c.fine_scratch, flag, nullptr, c.st, 1, c.live, c.live_off);
+    if (rc) return rc;
+    return launch_fine_out(tf_out, c.batch, c.out, c.st, c.live, c.live_off, c.residual && c.residual != c.x ? c.residual : nullptr);
+}
+
+// The third level (gnn_fused.hip): the layer as one kernel; on batch statistics the kernel stops behind mlp[0] and leaves
+// per-workgroup partial sums of the hidden tensor: scale / shift from them, then mlp[1..3] from the hidden tensor in one kernel
+static int fused_layer_path(const LayerCall& c, const void* packed, int* flag) {
+    int splits = 0;
+    int rc = launch_fused_layer(c.x, c.source, c.batch, packed, c.w->bn_a, c.w->bn_b, c.bn_train, c.residual, c.out, c.hid, flag, c.bpart,
+                                &splits, c.st, c.live, c.live_off);
+    if (rc || !c.bn_train) return rc;
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((2 * c.C + 63) / 64)), dim3(64), 0, c.st, c.bpart, c.batch * (int64_t)c.n, 2 * c.C,
+                       c.w->bn_a, c.w->bn_b, c.bn_eps, c.bsc, c.bsh, (const int*)nullptr, splits);
+    if ((rc = check_launch("bn_finish_kernel"))) return rc;
+    return launch_gnn_tail(c.hid, c.batch, packed, c.bsc, c.bsh, c.residual, c.out, flag, c.st);
+}
+
+// Packed weights at any other shape (round 4): six conv_pk_kernel launches around the attention core, the message and the hidden
+// tensor - the layer's own intermediates - channel-BLOCKED ([batch, C / 8, n, 8]: 16-byte accesses both ways).  No fp32 path in
+// these kernels: a non-finite output anywhere raises the ONE flag.  (The caller has asked conv_pk_ready().)
+static int packed_composition(const LayerCall& c, const void* packed, int* flag) {
+    const pats_propagation_weights* w = c.w;
+    const int C = c.C, heads = c.heads, n = c.n, m = c.m;
+    const int64_t batch = c.batch;
+    hipStream_t st = c.st;
+    const char* q0 = (const char*)packed + packed_fused_bytes(C, heads);
+    const size_t cc = conv_packed_bytes(C, C);
+    const char* pk4 = q0 + 4 * cc;
+    const char* pk5 = pk4 + conv_packed_bytes(2 * C, 2 * C);
+    int rc;
+    if ((rc = launch_conv_pk(q0, c.x, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bq, nullptr, c.q, flag, nullptr, st, 0))) return rc;
+    if ((rc = launch_conv_pk(q0 + cc, c.source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bk, nullptr, c.k, flag, nullptr, st, 0))) return rc;
+    if ((rc = launch_conv_pk(q0 + 2 * cc, c.source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bv, nullptr, c.v, flag, nullptr, st, 0))) return rc;
+    // the attention core: at the fine level's shape with its scores in registers (attention145.hip), else the general kernel
+    rc = launch_attention145(c.q, c.k, c.v, batch, C / heads, heads, n, m, c.att, flag, nullptr, st);
+    if (rc == PATS_ERR_UNSUPPORTED) rc = launch_attention(c.q, c.k, c.v, batch, C / heads, heads, n, m, c.att, nullptr, c.stream, nullptr);
+    if (rc) return rc;
+    if (gnn_fold_enabled()) {
+        // the merge is folded into mlp[0]'s packed weights and bias (gnn_fold_kernel): hidden = W1x x + (W1m Wm) att + b1'
+        if ((rc = launch_conv_pk(pk4, c.x, c.att, C, C, 2 * C, n, batch * n, nullptr, nullptr, packed_folded_bias(packed, C, heads), nullptr, c.hid, flag, nullptr, st, 4))) return rc;
+    } else {
+        if ((rc = launch_conv_pk(q0 + 3 * cc, c.att, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bm, nullptr, c.msg, flag, nullptr, st, 4))) return rc;
+        if ((rc = launch_conv_pk(pk4, c.x, c.msg, C, C, 2 * C, n, batch * n, nullptr, nullptr, w->b1, nullptr, c.hid, flag, nullptr, st, 2 | 4))) return rc;
+    }
+    const float *sc = w->bn_a, *sh = w->bn_b;
+    if (c.bn_train) {
+        hipLaunchKernelGGL(bn_partial_blocked_kernel, dim3((unsigned)(2 * C / 8), BN_SPLITS), dim3(256), 0, st, c.hid, batch, 2 * C, n, c.bpart,
+                           (const int*)nullptr);
+        hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((2 * C + 63) / 64)), dim3(64), 0, st, c.bpart, batch * (int64_t)n, 2 * C,
+                           w->bn_a, w->bn_b, c.bn_eps, c.bsc, c.bsh, (const int*)nullptr);
+        if ((rc = check_launch("bn_stats kernels"))) return rc;
+        sc = c.bsc; sh = c.bsh;
+    }
+    return launch_conv_pk(pk5, c.hid, nullptr, 2 * C, 0, C, n, batch * n, sc, sh, w->b2, c.residual, c.out, flag, nullptr, st, 1);
+}
+
+// The round-2 composition: five products around the attention core, each with its own redo flag (conv_lean_kernel raises it,
+// conv1x1_kernel behind it redoes the product in fp32).  gate: every kernel is a no-op unless *gate != 0 - the fallback behind a
+// fast path, then conv1x1_kernel alone (it has the fp32 redo inside), i.e. nine empty launches per layer instead of fifteen.
+// y: where the layer's output goes.
+static int composition(const LayerCall& c, const int* gate, float* y) {
+    const pats_propagation_weights* w = c.w;
+    const int C = c.C, n = c.n, m = c.m;
+    const int64_t batch = c.batch;
+    auto conv = [&](const ConvArgs& a, int k) { return launch_conv(a, gate ? nullptr : c.redo + k, c.st, gate); };
+    int rc;
+    // projections (modules.py:101-102)
+    if ((rc = conv(ConvArgs{w->wq_t, c.x, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bq, nullptr, c.q}, 0))) return rc;
+    if ((rc = conv(ConvArgs{w->wk_t, c.source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bk, nullptr, c.k}, 1))) return rc;
+    if ((rc = conv(ConvArgs{w->wv_t, c.source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bv, nullptr, c.v}, 2))) return rc;
+    // attention core (:103): the [b, C, n] projections ARE the [b, dim, heads, n] views
+    if ((rc = launch_attention(c.q, c.k, c.v, batch, C / c.heads, c.heads, n, m, c.att, nullptr, c.stream, gate))) return rc;
+    // merge (:104)
+    if ((rc = conv(ConvArgs{w->wm_t, c.att, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bm, nullptr, c.msg}, 3))) return rc;
+    // mlp[0] on cat([x, message]) without the cat (:116, MLP :64)
+    if ((rc = conv(ConvArgs{w->w1_t, c.x, c.msg, C, C, 2 * C, n, batch * n, nullptr, nullptr, w->b1, nullptr, c.hid}, 4))) return rc;
+    // mlp[1] BatchNorm1d: eval -> the caller's folded running statistics (bn_a = scale, bn_b = shift);
+    //                      train -> batch statistics with bn_a = gamma, bn_b = beta
+    const float *sc = w->bn_a, *sh = w->bn_b;
+    if (c.bn_train) {
+        hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)(2 * C), BN_SPLITS), dim3(256), 0, c.st, c.hid, batch, 2 * C, n, c.bpart, gate);
+        hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((2 * C + 63) / 64)), dim3(64), 0, c.st, c.bpart, batch * (int64_t)n, 2 * C,
+                           w->bn_a, w->bn_b, c.bn_eps, c.bsc, c.bsh, gate);
+        if ((rc = check_launch("bn_stats kernels"))) return rc;
+        sc = c.bsc; sh = c.bsh;
+    }
+    // mlp[2] ReLU + mlp[3] Conv1d(2C, C), BN affine + ReLU applied while staging; optional residual (desc + delta, :133)
+    return conv(ConvArgs{w->w2_t, c.hid, nullptr, 2 * C, 0, C, n, batch * n, sc, sh, w->b2, c.residual, y}, 5);
+}
+}  // namespace pats
+
+extern "C" size_t pats_attentional_propagation_workspace_bytes(int64_t batch, int C, int n, int m) {
+    if (batch < 0 || C <= 0 || n <= 0 || m <= 0) return 0;
+    return layer_workspace(batch, C, n, m).total;
+}
+
+// The layer, as a decision list.  ext_gate: run ONLY the round-2 composition, every kernel of it gated on *ext_gate (the redo chain
+// behind a fused stack, pats_attentional_gnn_packed_f32): no-ops unless that flag is raised.
 static int propagation_impl(const float* x, const float* source, int64_t batch, int C, int heads, int n, int m,
                             const pats_propagation_weights* w, int bn_train, float bn_eps, const float* residual, float* out,
                             void* workspace, size_t workspace_bytes, pats_stream_t stream, const void* packed,
-                            const int* ext_gate = nullptr, const int64_t* live = nullptr, int64_t live_off = 0);
+                            const int* ext_gate, const int64_t* live, int64_t live_off) {
+    // 1. the checks
+    PATS_REQUIRE(batch >= 0 && C > 0 && heads > 0 && n > 0 && m > 0 && (C % heads) == 0,
+                 "attentional_propagation: bad shape");
+    PATS_REQUIRE((C % 8) == 0, "attentional_propagation: feature_dim must be a multiple of 8 (operand slabs of 8 channels)");
+    if (batch == 0) return PATS_OK;
+    PATS_REQUIRE(x && source && w && out, "attentional_propagation: null pointer");
+    PATS_REQUIRE(w->wq_t && w->bq && w->wk_t && w->bk && w->wv_t && w->bv && w->wm_t && w->bm && w->w1_t && w->b1 &&
+                     w->w2_t && w->b2 && w->bn_a && w->bn_b, "attentional_propagation: null weight pointer");
+    const LayerWorkspace L = layer_workspace(batch, C, n, m);
+    PATS_REQUIRE(workspace && workspace_bytes >= L.total, "attentional_propagation: workspace too small");
+    char* const ws = (char*)workspace;
+    const LayerCall c{x, source, batch, C, heads, n, m, w, bn_train, bn_eps, residual, out,
+                      (float*)(ws + L.q), (float*)(ws + L.att), (float*)(ws + L.msg), (float*)(ws + L.k), (float*)(ws + L.v),
+                      (float*)(ws + L.hid), (float*)(ws + L.bsc), (float*)(ws + L.bsh), (double*)(ws + L.bpart), (int*)(ws + L.redo),
+                      ws + L.fine_scratch, stream, as_stream(stream), live, live_off};
+    // 2. which flag the fast paths raise.  Deferred overflow protocol (pats_set_gnn_redo_mode(1), host.cpp): the device's sticky flag
+    // instead of a per-call one, and NO gated composition is queued behind them; the caller reads the flag at its own
+    // synchronisation point (pats_gnn_overflows) and repeats the work in the default mode if it is up
+    const bool deferred = gnn_redo_deferred() && !ext_gate && packed;
+    int* const flag = deferred ? gnn_overflow_flag() : c.redo + 7;
+    if (!deferred && fill_bytes(c.redo, 0, 8 * sizeof(int), c.st)) return PATS_ERR_LAUNCH;      // (a pats:: kernel: the steps hold no runtime fill)
+    // 3. the fast paths, the first that takes the call.  None with ext_gate.  None with residual == out (round-4 advice): the
+    // kernels themselves read and write each element once, but the gated redo behind them would read the residual the first attempt
+    // has already overwritten - such a call takes the composition alone
+    const bool fast = packed && !ext_gate && !(residual && residual == out);
+    static const bool no_pk = [] { const char* e = diag_env("PATS_CONV_PK"); return e && atoi(e) == 0; }();         // A/B switch
+    int rc = PATS_ERR_UNSUPPORTED;                       // = no path has taken the call yet
+    bool honours_count = true;                           // the one-kernel layers skip the problems past the device-side count
+    if (fast && !bn_train && fine_layer_supported(C, heads, n, m) && gnn_fold_enabled()) rc = fine_layer_path(c, packed, flag);
+    if (rc == PATS_ERR_UNSUPPORTED && fast && fused_layer_supported(C, heads, n, m)) rc = fused_layer_path(c, packed, flag);
+    if (rc == PATS_ERR_UNSUPPORTED && fast && !no_pk && !cost_f32_only() && conv_pk_ready() && batch * (int64_t)std::max(n, m) < (1ll << 31)) {
+        if ((rc = packed_composition(c, packed, flag))) return rc;
+        honours_count = false;
+    }
+    if (rc != PATS_OK && rc != PATS_ERR_UNSUPPORTED) return rc;
+    // 4. what being taken means: the composition below runs only if the path raised the flag.  counted: a one-kernel layer honoured
+    // the device-side count, and the gated composition behind it runs over the whole capacity - so it writes into the message buffer
+    // (dead once mlp[0] has read it) and only the rows below the count are copied out: the rows past it keep what the one-kernel
+    // layer left there (zeros at the fine level, untouched at the third)
+    const int* gate = ext_gate;
+    bool counted = false;
+    if (rc == PATS_OK) {
+        if (deferred) return PATS_OK;
+        gate = flag;
+        counted = honours_count && live && !bn_train;
+    } else if (deferred && fill_bytes(c.redo, 0, 8 * sizeof(int), c.st)) {      // no fast path took the call: the composition's flags
+        return PATS_ERR_LAUNCH;
+    }
+    // 5. the composition and the gated copy
+    float* const y = counted ? c.msg : out;
+    if ((rc = composition(c, gate, y))) return rc;
+    return counted ? launch_gated_copy(y, out, (size_t)batch * C * n, (int64_t)C * n, gate, live, live_off, 256, c.st) : PATS_OK;
+}
 
 extern "C" int pats_attentional_propagation_f32(const float* x, const float* source, int64_t batch, int C, int heads,
                                                 int n, int m, const pats_propagation_weights* w, int bn_train,
                                                 float bn_eps, const float* residual, float* out, void* workspace,
                                                 size_t workspace_bytes, pats_stream_t stream) {
     return propagation_impl(x, source, batch, C, heads, n, m, w, bn_train, bn_eps, residual, out, workspace, workspace_bytes, stream,
-                            nullptr);
+                            nullptr, nullptr, nullptr, 0);
 }
 
 // The same layer with the weights additionally handed over PACKED (pats_propagation_pack_f32, once per layer): at the third
@@ -681,7 +888,7 @@ extern "C" int pats_attentional_propagation_packed_f32(const float* x, const flo
                                                        void* workspace, size_t workspace_bytes, pats_stream_t stream) {
     PATS_REQUIRE(packed, "attentional_propagation_packed: null packed weights");
     return propagation_impl(x, source, batch, C, heads, n, m, w, bn_train, bn_eps, residual, out, workspace, workspace_bytes, stream,
-                            packed);
+                            packed, nullptr, nullptr, 0);
 }
 
 // The packed layer over a CAPACITY with the problem count on the device (throughput mode: the third level's P, the fine level's row
@@ -700,161 +907,6 @@ extern "C" int pats_attentional_propagation_packed_counted_f32(const float* x, c
                             packed, nullptr, live, live_off);
 }
 
-static int propagation_impl(const float* x, const float* source, int64_t batch, int C, int heads, int n, int m,
-                            const pats_propagation_weights* w, int bn_train, float bn_eps, const float* residual, float* out,
-                            void* workspace, size_t workspace_bytes, pats_stream_t stream, const void* packed,
-                            const int* ext_gate, const int64_t* live, int64_t live_off) {
-    // ext_gate: run ONLY the round-2 composition, every kernel of it gated on *ext_gate (the redo chain behind a fused stack,
-    // pats_attentional_gnn_packed_f32): no-ops unless that flag is raised
-    PATS_REQUIRE(batch >= 0 && C > 0 && heads > 0 && n > 0 && m > 0 && (C % heads) == 0,
-                 "attentional_propagation: bad shape");
-    PATS_REQUIRE((C % 8) == 0, "attentional_propagation: feature_dim must be a multiple of 8 (operand slabs of 8 channels)");
-    if (batch == 0) return PATS_OK;
-    PATS_REQUIRE(x && source && w && out, "attentional_propagation: null pointer");
-    PATS_REQUIRE(w->wq_t && w->bq && w->wk_t && w->bk && w->wv_t && w->bv && w->wm_t && w->bm && w->w1_t && w->b1 &&
-                     w->w2_t && w->b2 && w->bn_a && w->bn_b, "attentional_propagation: null weight pointer");
-    PATS_REQUIRE(workspace && workspace_bytes >= pats_attentional_propagation_workspace_bytes(batch, C, n, m),
-                 "attentional_propagation: workspace too small");
-    hipStream_t st = as_stream(stream);
-    char* p = (char*)workspace;
-    const size_t qb = align256((size_t)batch * C * n * sizeof(float)), kb = align256((size_t)batch * C * m * sizeof(float));
-    float* q = (float*)p; p += qb;
-    float* att = (float*)p; p += qb;
-    float* msg = (float*)p; p += qb;
-    float* k = (float*)p; p += kb;
-    float* v = (float*)p; p += kb;
-    float* hid = (float*)p; p += align256((size_t)batch * 2 * C * n * sizeof(float));
-    float* bsc = (float*)p; p += align256((size_t)2 * C * sizeof(float));
-    float* bsh = (float*)p; p += align256((size_t)2 * C * sizeof(float));
-    double* bpart = (double*)p; p += align256((size_t)2 * C * 512 * 2 * sizeof(double));
-    int* redo = (int*)p; p += 256;
-    char* fine_scratch = p;
-    // deferred overflow protocol (pats_set_gnn_redo_mode(1), host.cpp): the one-kernel / packed-weights branches raise the device's
-    // sticky flag instead of a per-call one and NO gated composition is queued behind them; the caller reads the flag at its own
-    // synchronisation point (pats_gnn_overflows) and repeats the work in the default mode if it is up
-    const bool deferred = gnn_redo_deferred() && !ext_gate && packed;
-    int* const fast_flag = deferred ? gnn_overflow_flag() : redo + 7;
-    if (!deferred && fill_bytes(redo, 0, 8 * sizeof(int), st)) return PATS_ERR_LAUNCH;      // (a pats:: kernel: the steps hold no runtime fill)
-    int rc;
-    const int* gate = ext_gate;
-    if (ext_gate) packed = nullptr;
-    // set when a one-kernel layer below honoured the device-side count: the gated composition behind it runs over the whole
-    // capacity, so it writes into the workspace and only the rows below the count are copied out - the rows past it keep what
-    // the one-kernel layer left there (zeros at the fine level, untouched at the third)
-    bool counted = false;
-    if (packed && !bn_train && fine_layer_supported(C, heads, n, m) && gnn_fold_enabled() && !(residual && residual == out)) {
-        // The fine level (round 5, gnn_fine.hip): the whole layer in one kernel on (fp32 blocked, TF image) descriptors.  This
-        // single-layer entry converts on the way in and out (pats_attentional_gnn_packed_f32 keeps a stack in that form); the
-        // images and blocked copies overlay the composition's q / att / msg / k buffers, which only the gated redo would use.
-        int* flag = fast_flag;
-        char* tf_x = (char*)q;
-        char* tf_s = source == x ? tf_x : (char*)att;
-        char* tf_att = (char*)msg;
-        char* tf_out = (char*)k;
-        if ((rc = launch_fine_in(x, batch, tf_x, st))) return rc;
-        if (source != x && (rc = launch_fine_in(source, batch, tf_s, st))) return rc;
-        // the kernels add the layer's own x (what AttentionalGNN.forward does); any other residual is added by the conversion out
-        rc = launch_fine_layer(tf_x, tf_s, 0, residual == x ? 1 : 0, batch, packed_fine_section(packed, C, heads), tf_out, tf_att, fine_scratch,
-                               flag, nullptr, st, 1, live, live_off);
-        if (rc == PATS_OK) {
-            if ((rc = launch_fine_out(tf_out, batch, out, st, live, live_off, residual && residual != x ? residual : nullptr))) return rc;
-            if (deferred) return PATS_OK;
-            gate = flag;         // the composition below runs only if the kernel raised it
-            counted = live != nullptr;
-        } else if (rc != PATS_ERR_UNSUPPORTED) {
-            return rc;
-        }
-    }
-    if (packed && !gate && fused_layer_supported(C, heads, n, m) && !(residual && residual == out)) {
-        // residual == out is excluded (round-4 advice): the kernel itself reads and writes each element once, but the gated redo
-        // behind it would read the residual the first attempt has already overwritten - such a call takes the composition alone
-        int* flag = fast_flag;
-        int splits = 0;
-        rc = launch_fused_layer(x, source, batch, packed, w->bn_a, w->bn_b, bn_train, residual, out, hid, flag, bpart, &splits, st, live, live_off);
-        if (rc == PATS_OK) {
-            if (bn_train) {      // the fused kernel stopped behind mlp[0] and left per-workgroup partial sums of the hidden tensor:
-                                 // scale / shift from them, then mlp[1..3] from the hidden tensor in one kernel
-                hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((2 * C + 63) / 64)), dim3(64), 0, st, bpart, batch * (int64_t)n,
-                                   2 * C, w->bn_a, w->bn_b, bn_eps, bsc, bsh, (const int*)nullptr, splits);
-                if ((rc = check_launch("bn_finish_kernel"))) return rc;
-                if ((rc = launch_gnn_tail(hid, batch, packed, bsc, bsh, residual, out, flag, st))) return rc;
-            }
-            if (deferred) return PATS_OK;
-            gate = flag;         // the composition below runs only if the fused kernel raised it
-            counted = live != nullptr && !bn_train;
-        } else if (rc != PATS_ERR_UNSUPPORTED) {
-            return rc;
-        }
-    }
-    // Packed weights at any other shape (round 4): six conv_pk_kernel launches around the attention core, the message and the hidden
-    // tensor - the layer's own intermediates - channel-BLOCKED ([batch, C / 8, n, 8]: 16-byte accesses both ways).  No fp32 path in
-    // these kernels: a non-finite output anywhere raises ONE flag, and the round-2 composition below - gated on it, its kernels
-    // return at once otherwise - redoes the layer.  (residual == out: the redo would read what the first attempt wrote.)
-    static const bool no_pk = [] { const char* e = diag_env("PATS_CONV_PK"); return e && atoi(e) == 0; }();         // A/B switch
-    const bool fp32_only = cost_f32_only();
-    if (packed && !gate && !no_pk && !fp32_only && !(residual && residual == out) && conv_pk_ready() && batch * (int64_t)std::max(n, m) < (1ll << 31)) {
-        int* flag = fast_flag;
-        const char* q0 = (const char*)packed + packed_fused_bytes(C, heads);
-        const size_t cc = conv_packed_bytes(C, C);
-        const char* pk4 = q0 + 4 * cc;
-        const char* pk5 = pk4 + conv_packed_bytes(2 * C, 2 * C);
-        if ((rc = launch_conv_pk(q0, x, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bq, nullptr, q, flag, nullptr, st, 0))) return rc;
-        if ((rc = launch_conv_pk(q0 + cc, source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bk, nullptr, k, flag, nullptr, st, 0))) return rc;
-        if ((rc = launch_conv_pk(q0 + 2 * cc, source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bv, nullptr, v, flag, nullptr, st, 0))) return rc;
-        // the attention core: at the fine level's shape with its scores in registers (attention145.hip), else the general kernel
-        rc = launch_attention145(q, k, v, batch, C / heads, heads, n, m, att, flag, nullptr, st);
-        if (rc == PATS_ERR_UNSUPPORTED) rc = launch_attention(q, k, v, batch, C / heads, heads, n, m, att, nullptr, stream, nullptr);
-        if (rc) return rc;
-        if (gnn_fold_enabled()) {
-            // the merge is folded into mlp[0]'s packed weights and bias (gnn_fold_kernel): hidden = W1x x + (W1m Wm) att + b1'
-            if ((rc = launch_conv_pk(pk4, x, att, C, C, 2 * C, n, batch * n, nullptr, nullptr, packed_folded_bias(packed, C, heads), nullptr, hid, flag, nullptr, st, 4))) return rc;
-        } else {
-            if ((rc = launch_conv_pk(q0 + 3 * cc, att, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bm, nullptr, msg, flag, nullptr, st, 4))) return rc;
-            if ((rc = launch_conv_pk(pk4, x, msg, C, C, 2 * C, n, batch * n, nullptr, nullptr, w->b1, nullptr, hid, flag, nullptr, st, 2 | 4))) return rc;
-        }
-        const float *sc = w->bn_a, *sh = w->bn_b;
-        if (bn_train) {
-            hipLaunchKernelGGL(bn_partial_blocked_kernel, dim3((unsigned)(2 * C / 8), BN_SPLITS), dim3(256), 0, st, hid, batch, 2 * C, n, bpart,
-                               (const int*)nullptr);
-            hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((2 * C + 63) / 64)), dim3(64), 0, st, bpart, batch * (int64_t)n, 2 * C,
-                               w->bn_a, w->bn_b, bn_eps, bsc, bsh, (const int*)nullptr);
-            if ((rc = check_launch("bn_stats kernels"))) return rc;
-            sc = bsc; sh = bsh;
-        }
-        if ((rc = launch_conv_pk(pk5, hid, nullptr, 2 * C, 0, C, n, batch * n, sc, sh, w->b2, residual, out, flag, nullptr, st, 1))) return rc;
-        if (deferred) return PATS_OK;
-        gate = flag;             // the composition below runs only if one of the kernels above raised it
-    }
-    if (deferred && fill_bytes(redo, 0, 8 * sizeof(int), st)) return PATS_ERR_LAUNCH;     // no fast branch took the call: the composition's flags
-    // (as the gated fallback behind the fused layer / the packed-weights kernels: conv1x1_kernel alone - it has the fp32 redo inside -
-    //  i.e. nine empty launches per layer instead of fifteen)
-    // projections (modules.py:101-102)
-    if ((rc = launch_conv(ConvArgs{w->wq_t, x, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bq, nullptr, q}, gate ? nullptr : redo + 0, st, gate))) return rc;
-    if ((rc = launch_conv(ConvArgs{w->wk_t, source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bk, nullptr, k}, gate ? nullptr : redo + 1, st, gate))) return rc;
-    if ((rc = launch_conv(ConvArgs{w->wv_t, source, nullptr, C, 0, C, m, batch * m, nullptr, nullptr, w->bv, nullptr, v}, gate ? nullptr : redo + 2, st, gate))) return rc;
-    // attention core (:103): the [b, C, n] projections ARE the [b, dim, heads, n] views
-    if ((rc = launch_attention(q, k, v, batch, C / heads, heads, n, m, att, nullptr, stream, gate))) return rc;
-    // merge (:104)
-    if ((rc = launch_conv(ConvArgs{w->wm_t, att, nullptr, C, 0, C, n, batch * n, nullptr, nullptr, w->bm, nullptr, msg}, gate ? nullptr : redo + 3, st, gate))) return rc;
-    // mlp[0] on cat([x, message]) without the cat (:116, MLP :64)
-    if ((rc = launch_conv(ConvArgs{w->w1_t, x, msg, C, C, 2 * C, n, batch * n, nullptr, nullptr, w->b1, nullptr, hid}, gate ? nullptr : redo + 4, st, gate))) return rc;
-    // mlp[1] BatchNorm1d: eval -> the caller's folded running statistics (bn_a = scale, bn_b = shift);
-    //                      train -> batch statistics with bn_a = gamma, bn_b = beta
-    const float *sc = w->bn_a, *sh = w->bn_b;
-    if (bn_train) {
-        hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)(2 * C), BN_SPLITS), dim3(256), 0, st, hid, batch, 2 * C, n, bpart, gate);
-        hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((2 * C + 63) / 64)), dim3(64), 0, st, bpart, batch * (int64_t)n, 2 * C,
-                           w->bn_a, w->bn_b, bn_eps, bsc, bsh, gate);
-        if ((rc = check_launch("bn_stats kernels"))) return rc;
-        sc = bsc; sh = bsh;
-    }
-    // mlp[2] ReLU + mlp[3] Conv1d(2C, C), BN affine + ReLU applied while staging; optional residual (desc + delta, :133)
-    // (counted: into the message buffer - dead once mlp[0] has read it - and the live rows from there)
-    float* const y = counted ? msg : out;
-    if ((rc = launch_conv(ConvArgs{w->w2_t, hid, nullptr, 2 * C, 0, C, n, batch * n, sc, sh, w->b2, residual, y}, gate ? nullptr : redo + 5, st, gate)))
-        return rc;
-    return counted ? launch_gated_copy(y, out, (size_t)batch * C * n, (int64_t)C * n, gate, live, live_off, 256, st) : PATS_OK;
-}
 
 // ---- AttentionalGNN.forward (modules.py:127-134) at the fine level's shape, descriptors kept in the one-kernel layer's own form ----
 // (round 5) desc0, desc1 [batch, 264, 145] -> one array of P = 2 batch problems as (fp32 channel-blocked, TF image), `layers` launches
@@ -867,10 +919,7 @@ static int propagation_impl(const float* x, const float* source, int64_t batch, 
 // (the gated copy out leaves rows past the device-side count alone: gnn_fine_out_kernel's zeros survive a redo)
 extern "C" size_t pats_attentional_gnn_packed_workspace_bytes(int64_t batch, int C, int heads, int n) {
     if (batch <= 0 || !fine_layer_supported(C, heads, n, n)) return 0;
-    const int64_t P = 2 * batch;
-    const size_t fused = 3 * align256(fine_image_bytes(P));
-    const size_t redo = 4 * align256((size_t)batch * C * n * sizeof(float)) + align256(pats_attentional_propagation_workspace_bytes(batch, C, n, n));
-    return std::max(fused, redo) + align256(fine_scratch_bytes(P)) + 256;
+    return stack_workspace(batch, C, n).total;
 }
 extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* desc1, int64_t batch, const int64_t* live, int64_t live_off,
                                                int C, int heads, int n, int layers,
@@ -883,19 +932,18 @@ extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* 
     PATS_REQUIRE(desc0 && desc1 && out0 && out1 && (layers == 0 || (weights && packed && cross)), "attentional_gnn_packed: null pointer");
     // (round-5 advice) the inline redo chain re-reads the inputs AFTER the fast path has written the outputs
     PATS_REQUIRE(out0 != desc0 && out0 != desc1 && out1 != desc0 && out1 != desc1, "attentional_gnn_packed: the outputs must not alias the inputs");
-    PATS_REQUIRE(workspace && workspace_bytes >= pats_attentional_gnn_packed_workspace_bytes(batch, C, heads, n), "attentional_gnn_packed: workspace too small");
+    const StackWorkspace S = stack_workspace(batch, C, n);
+    PATS_REQUIRE(workspace && workspace_bytes >= S.total, "attentional_gnn_packed: workspace too small");
     for (int l = 0; l < layers; ++l) PATS_REQUIRE(weights[l] && packed[l], "attentional_gnn_packed: null layer");
     hipStream_t st = as_stream(stream);
     const int64_t P = 2 * batch;
     const size_t elems = (size_t)batch * C * n;
     char* p = (char*)workspace;
-    const size_t fused = 3 * align256(fine_image_bytes(P));
-    const size_t redo_b = 4 * align256(elems * sizeof(float)) + align256(pats_attentional_propagation_workspace_bytes(batch, C, n, n));
-    char* tf[2] = {p, p + align256(fine_image_bytes(P))};
-    char* tf_att = p + 2 * align256(fine_image_bytes(P));
-    char* scratch = p + std::max(fused, redo_b);
+    char* tf[2] = {p + S.tf[0], p + S.tf[1]};
+    char* tf_att = p + S.tf_att;
+    char* scratch = p + S.scratch;
     const bool deferred = gnn_redo_deferred();          // no redo chain: the device's sticky flag, read by the caller (host.cpp)
-    int* flag = deferred ? gnn_overflow_flag() : (int*)(scratch + align256(fine_scratch_bytes(P)));
+    int* flag = deferred ? gnn_overflow_flag() : (int*)(p + S.flag);
     if (!deferred && fill_bytes(flag, 0, sizeof(int), st)) return PATS_ERR_LAUNCH;
     int rc;
     // in: the two descriptor sets into one array of problems
@@ -915,17 +963,15 @@ extern "C" int pats_attentional_gnn_packed_f32(const float* desc0, const float* 
     if ((rc = launch_fine_out(tf[cur], batch, out0, st, live, live_off))) return rc;
     if ((rc = launch_fine_out(tf[cur] + fine_image_bytes(batch), batch, out1, st, live, live_off))) return rc;
     if (deferred) return check_launch("attentional_gnn_packed");
-    // the redo chain (no-ops unless the flag is up): the layers one by one on the round-2 composition, from the inputs
-    float* d[2][2] = {{(float*)p, (float*)(p + align256(elems * sizeof(float)))},
-                      {(float*)(p + 2 * align256(elems * sizeof(float))), (float*)(p + 3 * align256(elems * sizeof(float)))}};
-    void* cws = p + 4 * align256(elems * sizeof(float));
-    const size_t cws_b = pats_attentional_propagation_workspace_bytes(batch, C, n, n);
+    // the redo chain (no-ops unless the flag is up): the layers one by one on the round-2 composition, from the inputs.
+    // OVERLAY: its descriptor buffers S.d and the composition's workspace S.layer lie on the images, which nothing reads any more
+    void* cws = p + S.layer;
     const float *c0 = desc0, *c1 = desc1;
     for (int l = 0; l < layers; ++l) {
-        float *n0 = d[l & 1][0], *n1 = d[l & 1][1];
+        float *n0 = (float*)(p + S.d[l & 1][0]), *n1 = (float*)(p + S.d[l & 1][1]);
         const float *s0 = cross[l] ? c1 : c0, *s1 = cross[l] ? c0 : c1;
-        if ((rc = propagation_impl(c0, s0, batch, C, heads, n, n, weights[l], 0, bn_eps, c0, n0, cws, cws_b, stream, nullptr, flag))) return rc;
-        if ((rc = propagation_impl(c1, s1, batch, C, heads, n, n, weights[l], 0, bn_eps, c1, n1, cws, cws_b, stream, nullptr, flag))) return rc;
+        if ((rc = propagation_impl(c0, s0, batch, C, heads, n, n, weights[l], 0, bn_eps, c0, n0, cws, S.layer_bytes, stream, nullptr, flag, nullptr, 0))) return rc;
+        if ((rc = propagation_impl(c1, s1, batch, C, heads, n, n, weights[l], 0, bn_eps, c1, n1, cws, S.layer_bytes, stream, nullptr, flag, nullptr, 0))) return rc;
         c0 = n0; c1 = n1;
     }
     if ((rc = launch_gated_copy(c0, out0, elems, (int64_t)C * n, flag, live, live_off, 4096, st))) return rc;
@@ -948,7 +994,7 @@ extern "C" int pats_conv1x1_f32(const float* w_t, const float* bias, const float
     hipStream_t st = as_stream(stream);
     int* redo = (int*)workspace;
     if (fill_bytes(redo, 0, sizeof(int), st)) return PATS_ERR_LAUNCH;
-    return launch_conv(ConvArgs{w_t, x, nullptr, K, 0, M, n, batch * n, in_scale, in_shift, bias, residual, y}, redo, st);
+    return launch_conv(ConvArgs{w_t, x, nullptr, K, 0, M, n, batch * n, in_scale, in_shift, bias, residual, y}, redo, st, nullptr);
 }
 
 extern "C" size_t pats_bn_fold_workspace_bytes(int C) {

@@ -1176,23 +1176,10 @@ int launch_fine_pack(const pats_propagation_weights& w, void* section, hipStream
 
 // CUs of the device (0: the kernels' LDS attributes were refused)
 static int fine_cus() {
-    struct PerDevice { int state = 0; int n_cu = 256; };
-    static PerDevice per_dev[64];
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) { (void)hipGetLastError(); dev_id = 0; }
-    PerDevice& pd = per_dev[dev_id];
-    if (pd.state == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)gnn_fine_tile_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_fine_tile_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_fine_tile_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_fine_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        int v = 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess) (void)hipGetLastError();
-        pd.n_cu = v > 0 ? v : 256;
-        pd.state = ok ? 1 : -1;
-    }
-    return pd.state == 1 ? pd.n_cu : 0;
+    static DeviceGrants grants;
+    const DeviceGrant d = grants.get({{(const void*)gnn_fine_tile_kernel<true, false>, MLP_LDS}, {(const void*)gnn_fine_tile_kernel<true, true>, MLP_LDS},
+                                      {(const void*)gnn_fine_tile_kernel<false, true>, MLP_LDS}, {(const void*)gnn_fine_attn_kernel, ATT_LDS}});
+    return d.granted ? d.n_cu : 0;
 }
 size_t fine_scratch_bytes(int64_t P) { return (size_t)P * QKV_BYTES + 256; }      // the per-problem blocks of projections + the sink of masked stores
 size_t fine_image_bytes(int64_t P) { return (size_t)P * TF_BYTES; }

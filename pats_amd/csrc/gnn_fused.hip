@@ -724,31 +724,23 @@ extern "C" int pats_propagation_pack_f32(const pats_propagation_weights* w, int 
 }
 
 namespace pats {
+// the LDS of the layer's kernels and of its batch-statistics tail, and the CUs their grids are sized by
+static DeviceGrant fused_grant() {
+    static DeviceGrants grants;
+    return grants.get({{(const void*)gnn_tail_kernel, 2 * TF_BYTES}, {(const void*)gnn_layer_fused_kernel<false, false>, FUSED_LDS},
+                       {(const void*)gnn_layer_fused_kernel<true, false>, FUSED_LDS}, {(const void*)gnn_layer_fused_kernel<false, true>, FUSED_LDS},
+                       {(const void*)gnn_layer_fused_kernel<true, true>, FUSED_LDS}});
+}
+
 // The layer (eval: whole; train: up to the hidden tensor) for batch problems.  flag: one int, zero on entry.
 int launch_fused_layer(const float* x, const float* source, int64_t batch, const void* packed, const float* bn_a, const float* bn_b,
                        int bn_train, const float* residual, float* out, float* hid, int* flag, double* bn_part, int* splits_out,
                        hipStream_t st, const int64_t* live, int64_t live_off) {
-    struct PerDevice { int state = 0; int n_cu = 256; };
-    static PerDevice per_dev[64];
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) { (void)hipGetLastError(); dev_id = 0; }
-    PerDevice& pd = per_dev[dev_id];
-    if (pd.state == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)gnn_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TF_BYTES) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_layer_fused_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_layer_fused_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_layer_fused_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) == hipSuccess &&
-                        hipFuncSetAttribute((const void*)gnn_layer_fused_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        int v = 256;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess) (void)hipGetLastError();
-        pd.n_cu = v > 0 ? v : 256;
-        pd.state = ok ? 1 : -1;
-    }
-    if (pd.state != 1) return PATS_ERR_UNSUPPORTED;
+    const DeviceGrant dev = fused_grant();
+    if (!dev.granted) return PATS_ERR_UNSUPPORTED;
     const h8v* pw = (const h8v*)packed;
     FusedArgs g{x, source, residual, out, hid, pw, (const float*)(pw + PW_END), bn_a, bn_b, batch, flag, bn_part, bn_train ? nullptr : live, live_off};
-    const unsigned grid = (unsigned)std::min<int64_t>(batch, std::min(pd.n_cu, FUSED_MAX_GRID));
+    const unsigned grid = (unsigned)std::min<int64_t>(batch, std::min(dev.n_cu, FUSED_MAX_GRID));
     if (splits_out) *splits_out = (int)grid;
     const bool fold = gnn_fold_enabled();
     if (bn_train && fold) hipLaunchKernelGGL((gnn_layer_fused_kernel<true, true>), dim3(grid), dim3(512), FUSED_LDS, st, g);
@@ -761,9 +753,7 @@ int launch_fused_layer(const float* x, const float* source, int64_t batch, const
 // mlp[1..3] of the layer on batch statistics, from the hidden tensor (see gnn_tail_kernel)
 int launch_gnn_tail(const float* hid, int64_t batch, const void* packed, const float* scale, const float* shift, const float* residual,
                     float* out, int* flag, hipStream_t st) {
-    int dev_id = 0, n_cu = 256;
-    if (hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); dev_id = 0; }
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess || n_cu <= 0) { (void)hipGetLastError(); n_cu = 256; }
+    const int n_cu = fused_grant().n_cu;                // (asked for by launch_fused_layer, which every caller has come through)
     const h8v* pw = (const h8v*)packed;
     FusedArgs g{nullptr, nullptr, residual, out, const_cast<float*>(hid), pw, (const float*)(pw + PW_END), nullptr, nullptr, batch, flag, nullptr, nullptr, 0};
     const unsigned grid = (unsigned)std::min<int64_t>(batch, 2 * (int64_t)n_cu);

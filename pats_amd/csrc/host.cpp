@@ -51,11 +51,36 @@ int fill_bytes(void* p, int value, size_t n, hipStream_t st) {
 static int g_mode = PATS_SINKHORN_AUTO;
 int sinkhorn_mode() { return g_mode; }
 
-static unsigned long long* g_fallbacks[64];
+int device_slot() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) { (void)hipGetLastError(); return -1; }
+    return dev;
+}
+
+DeviceGrant DeviceGrants::get(std::initializer_list<LdsLimit> limits) {
+    const int dev = device_slot();
+    if (dev < 0) return {false, 256};
+    int s = __atomic_load_n(&state[dev], __ATOMIC_ACQUIRE);
+    if (s == 0) {
+        bool ok = true;
+        for (const LdsLimit& l : limits) {
+            ok = hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l.bytes) == hipSuccess;
+            if (!ok) { (void)hipGetLastError(); break; }
+        }
+        int v = 256;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) (void)hipGetLastError();
+        n_cu[dev] = v > 0 ? v : 256;
+        s = ok ? 1 : -1;
+        __atomic_store_n(&state[dev], s, __ATOMIC_RELEASE);     // behind n_cu: a thread that reads the state reads the count
+    }
+    return {s == 1, n_cu[dev]};
+}
+
+static unsigned long long* g_fallbacks[MAX_DEVICES];
 static std::mutex g_fallbacks_mu;
 unsigned long long* fallback_counter() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return nullptr; }
+    const int dev = device_slot();
+    if (dev < 0) return nullptr;
     std::lock_guard<std::mutex> lock(g_fallbacks_mu);           // first use may race between host threads
     if (!g_fallbacks[dev]) {
         unsigned long long* p = nullptr;
@@ -77,10 +102,10 @@ unsigned long long* fallback_counter() {
 // (pats_gnn_overflows) and, if it is raised, repeats the work in mode 0 - outputs of a call that raised it are not valid.
 static std::atomic<int> g_gnn_redo_mode{0};
 bool gnn_redo_deferred() { return g_gnn_redo_mode.load(std::memory_order_relaxed) == 1; }
-static int* g_gnn_overflow[64];
+static int* g_gnn_overflow[MAX_DEVICES];
 int* gnn_overflow_flag() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return nullptr; }
+    const int dev = device_slot();
+    if (dev < 0) return nullptr;
     std::lock_guard<std::mutex> lock(g_fallbacks_mu);
     if (!g_gnn_overflow[dev]) {
         int* p = nullptr;

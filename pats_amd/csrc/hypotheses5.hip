@@ -47,19 +47,6 @@ epipolar_hypotheses5_kernel(const float* __restrict__ ml_, const float* __restri
     if (n_models) n_models[p * H + h] = count;
 }
 
-// the kernel's LDS is above the 64 KiB a launch gets unasked: raised once per device
-static bool e5_lds_ready() {
-    static int state[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)epipolar_hypotheses5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, E5_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1;
-}
-
 }  // namespace pats
 
 using namespace pats;
@@ -80,7 +67,8 @@ extern "C" int pats_epipolar_hypotheses5_by_pair_f32(const float* matches_l, con
                                         H, pair_seed, norm, progressive, models, sample_idx, n_models, E5_MAX_MODELS, E5_THREADS, chunks);
     if (rc != PATS_OK) return rc;
     PATS_REQUIRE(workspace_bytes >= pats_epipolar_hypotheses5_workspace_bytes(pairs, H), "epipolar_hypotheses5_by_pair: workspace too small");
-    if (!e5_lds_ready()) {
+    static DeviceGrants grants;                         // the kernel's LDS is above the 64 KiB a launch gets unasked
+    if (!grants.get({{(const void*)epipolar_hypotheses5_kernel, E5_LDS}}).granted) {
         set_error("epipolar_hypotheses5_by_pair: the device refused %d bytes of LDS per workgroup", E5_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

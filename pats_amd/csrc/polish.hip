@@ -259,7 +259,8 @@ static int verify_polish_by_pair(const char* who, const float* matches_l, const 
     PATS_REQUIRE(best || H == 1, "%s: null best needs H == 1, got H = %lld", who, (long long)H);
     const int64_t longest = counts_in ? stride : cap;   // the staging comes from the sizes alone: no host read of the counts
     const int stage_n = (int)(longest < POLISH_STAGE ? longest : POLISH_STAGE);
-    if (!epi_lds_raised<verify_polish_kernel<T>>(POLISH_LDS)) {          // the staging can exceed what a launch gets unasked
+    static DeviceGrants grants;                         // (one per T) the staging can exceed what a launch gets unasked
+    if (!grants.get({{(const void*)verify_polish_kernel<T>, POLISH_LDS}}).granted) {
         set_error("%s: the device refused %d bytes of dynamic LDS per workgroup", who, POLISH_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

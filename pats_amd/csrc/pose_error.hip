@@ -15,8 +15,6 @@
 #include "epipolar.hpp"
 #include "gt_pose.hpp"
 
-#include <atomic>
-
 namespace pats {
 
 constexpr int PERR_THREADS = 64;                       // pairs per workgroup (one wave)
@@ -159,22 +157,6 @@ __global__ void __launch_bounds__(AUC_THREADS) pose_auc_kernel(AucArgs g) {
     }
 }
 
-// the keys (plus the kernel's static LDS) can exceed the 64 KiB a launch gets unasked: raised once per device.  Two host threads
-// that meet here first both set the attribute to the same value
-static bool auc_lds_ready() {
-    static std::atomic<int> state[64];                  // zero-initialised: 0 = not asked yet, 1 = granted, -1 = refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
-    int s = state[dev].load(std::memory_order_acquire);
-    if (s == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)pose_auc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, AUC_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        s = ok ? 1 : -1;
-        state[dev].store(s, std::memory_order_release);
-    }
-    return s == 1;
-}
-
 }  // namespace pats
 
 using namespace pats;
@@ -215,7 +197,10 @@ extern "C" int pats_pose_auc_f64(const double* errors, int64_t n, const double* 
     g.errors = errors; g.n = (int)n; g.S = S; g.n_thr = (int)n_thr;
     g.auc = auc; g.below = below; g.sorted = sorted;
     const size_t lds = (size_t)S * sizeof(unsigned long long);
-    if (!auc_lds_ready()) {                             // every call, as polish.hip does: static + dynamic LDS passes 64 KiB from n = 4097 on
+    // the keys (plus the kernel's static LDS) can exceed the 64 KiB a launch gets unasked.  Asked for at every n, as polish.hip
+    // does: static + dynamic LDS passes 64 KiB from n = 4097 on
+    static DeviceGrants grants;
+    if (!grants.get({{(const void*)pose_auc_kernel, AUC_LDS}}).granted) {
         set_error("pose_auc: the device refused %d bytes of dynamic LDS per workgroup", AUC_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

@@ -575,11 +575,8 @@ int launch_stream(const float* base, int64_t stride, int ld, int rows, int cols,
     // Rows per workgroup.  With 7+ columns per thread the K piece alone is 112+ VGPRs, so one workgroup fills a CU
     // and the grid runs in rounds of one workgroup per CU: 4097 rows in blocks of 16 are 257 workgroups - a second
     // round for ONE block on a 256-CU part.  Blocks of 17 rows (241 workgroups) finish in one.
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    static DeviceGrants grants;                         // (no LDS limit to raise: the device's CU count alone)
+    const int n_cu = grants.get({}).n_cu;
     auto rounds = [&](int rb) { return (batch * ((M + rb - 1) / rb) + n_cu - 1) / n_cu; };
     const bool rb17 = cpt >= 7 && rounds(17) < rounds(16);
     const int RBr = rb17 ? 17 : 16;

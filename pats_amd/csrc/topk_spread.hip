@@ -21,7 +21,7 @@ namespace pats {
 constexpr int TOPK_SPREAD_MAX_CELLS = 16384;    // = pats_topk_spread_by_pair_max_cells(): 8 bytes per cell, 128 KiB of the 160 a workgroup may allocate
 constexpr int TOPK_SPREAD_MAX_CELL = 65536;     // pixels along a cell's edge
 constexpr int TOPK_SPREAD_LDS = TOPK_SPREAD_MAX_CELLS * 8;
-constexpr int TOPK_SPREAD_LDS_UNASKED = 65536;  // the dynamic LDS a launch gets without hipFuncSetAttribute
+constexpr int TOPK_SPREAD_LDS_UNASKED = 65536;  // the dynamic LDS a launch gets unasked (common.hpp, DeviceGrants)
 
 struct TopkSpreadArgs {
     const float* ml; const float* mr; const float* conf; const int64_t* pair_off;
@@ -138,19 +138,6 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_spread_by_pair_kernel(TopkS
     if (tid == 0) { g.top_count[p] = (int64_t)count; g.occupied[p] = (int64_t)occ; }
 }
 
-// grids above 64 KiB of table exceed what a launch gets unasked: raised once per device
-static bool spread_lds_ready() {
-    static int state[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
-    if (state[dev] == 0) {
-        const bool ok = hipFuncSetAttribute((const void*)topk_spread_by_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_SPREAD_LDS) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-        state[dev] = ok ? 1 : -1;
-    }
-    return state[dev] == 1;
-}
-
 }  // namespace pats
 
 using namespace pats;
@@ -184,7 +171,8 @@ extern "C" int pats_topk_spread_by_pair_f32(const float* matches_l, const float*
     uint32_t slots = 1;                         // the table the sort may use: the next power of two above the cells
     while (slots < (uint32_t)(grid0 * grid1)) slots <<= 1;
     const size_t lds = (size_t)slots * sizeof(unsigned long long);
-    if (lds > (size_t)TOPK_SPREAD_LDS_UNASKED && !spread_lds_ready()) {
+    static DeviceGrants grants;                 // grids above 64 KiB of table exceed what a launch gets unasked
+    if (lds > (size_t)TOPK_SPREAD_LDS_UNASKED && !grants.get({{(const void*)topk_spread_by_pair_kernel, TOPK_SPREAD_LDS}}).granted) {
         set_error("topk_spread_by_pair: the device refused %d bytes of dynamic LDS per workgroup", TOPK_SPREAD_LDS);
         return PATS_ERR_UNSUPPORTED;
     }

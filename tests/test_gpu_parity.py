@@ -1661,12 +1661,15 @@ def test_conv1d_edge_cases(ops, oracle):
 
 
 @pytest.mark.parametrize("C,b,n,m", [(8, 37, 3, 5), (24, 9, 70, 33), (72, 4, 161, 20), (136, 3, 65, 65), (160, 3, 100, 160), (320, 2, 160, 97),
-                                     (296, 2, 129, 145)])
+                                     (296, 2, 129, 145), (64, 3, 20, 33)])
 def test_attentional_propagation_small_widths_against_oracle(ops, oracle, C, b, n, m):
     """Single-chunk and ragged reductions (K = 8 .. 272, the two-pass reduction of the MLP's first product with a
-    zero-filled tail in each pass), column tiles that cover many problems, train and eval BatchNorm, residual.  The last three
-    are attention145_kernel's corners (40 / 80 / 74 channels per head, 97 .. 160 tokens, n != m) and, for the packed-weights
-    convolutions, 10 / 20 / 19 row tiles and reductions of 160 .. 640 channels in one to three passes."""
+    zero-filled tail in each pass), column tiles that cover many problems, train and eval BatchNorm, residual.  Cases five to
+    seven are attention145_kernel's corners (40 / 80 / 74 channels per head, 97 .. 160 tokens, n != m) and, for the packed-weights
+    convolutions, 10 / 20 / 19 row tiles and reductions of 160 .. 640 channels in one to three passes.
+    Both compositions of the layer (docs/kernels.md 4.27): these shapes have no one-kernel layer, so the call takes the
+    packed-weights composition; the same call with its residual as the output (residual == out takes no fast path) is the round-2
+    composition on its own, ungated - against the same oracle values, at the same tolerance."""
     params = synth.gnn_params(seed=100 + C, C=C)
     inp = synth.gnn_inputs(seed=200 + C, b=b, C=C, n=n, m=m)
     P = ops.PropagationParams(params)
@@ -1675,6 +1678,9 @@ def test_attentional_propagation_small_widths_against_oracle(ops, oracle, C, b, 
         y = ops.attentional_propagation(x, s, P, bn_train=train, residual=x).cpu().numpy()
         want = oracle.attentional_propagation(inp["x"], inp["source"], params, bn_train=train, residual=inp["x"])
         np.testing.assert_allclose(y, want, atol=1e-4, rtol=2e-4)
+        r = x.clone()
+        assert ops.attentional_propagation(x, s, P, bn_train=train, residual=r, out=r) is r
+        np.testing.assert_allclose(r.cpu().numpy(), want, atol=1e-4, rtol=2e-4)
 
 
 def test_fine_level_layer_operands_beyond_the_fp16_range(ops, oracle):
@@ -1701,6 +1707,36 @@ def test_attentional_propagation_operands_beyond_the_fp16_range(ops, oracle):
     want = oracle.attentional_propagation(inp["x"], inp["source"], params)
     assert np.isfinite(y).all()
     np.testing.assert_allclose(y, want, atol=5e-3, rtol=5e-4)          # outputs reach 1e3 next to the spikes
+
+
+def test_packed_composition_operands_beyond_the_fp16_range(ops, oracle):
+    """The same spikes at a shape without a one-kernel layer ([3, 64, 20] against [3, 64, 33]: the packed-weights composition, whose
+    kernels have no fp32 path).  Deferred mode: the device's flag rises.  Inline mode: the gated round-2 composition behind redoes the
+    layer - the composition the test above reaches behind the fused layer, on shorter reductions, so its tolerance holds here.
+    And the call no fast path takes (residual == out), deferred: the inline call's bits, the flag down."""
+    params = synth.gnn_params(seed=13, C=64)
+    inp = synth.gnn_inputs(seed=14, b=3, C=64, n=20, m=33)
+    P = ops.PropagationParams(params)
+    clean_x, s_clean = cu(inp["x"]), cu(inp["source"])
+    r_inline = clean_x.clone()
+    ops.attentional_propagation(clean_x, s_clean, P, residual=r_inline, out=r_inline)
+    inp["x"][2, 17, 11] = 3000.0
+    inp["source"][1, 40, 3] = -2500.0
+    x, s = cu(inp["x"]), cu(inp["source"])
+    prev = ops.set_gnn_redo("deferred")
+    try:
+        ops.gnn_overflows(reset=True)
+        r = clean_x.clone()
+        ops.attentional_propagation(clean_x, s_clean, P, residual=r, out=r)
+        assert not ops.gnn_overflows(reset=True) and torch.equal(r, r_inline)
+        ops.attentional_propagation(x, s, P)
+        assert ops.gnn_overflows(reset=True), "the spikes did not raise the overflow flag"
+    finally:
+        assert ops.set_gnn_redo(prev) == "deferred"
+    y = ops.attentional_propagation(x, s, P).cpu().numpy()
+    want = oracle.attentional_propagation(inp["x"], inp["source"], params)
+    assert np.isfinite(y).all()
+    np.testing.assert_allclose(y, want, atol=5e-3, rtol=5e-4)
 
 
 def test_dropin_runs_a_gnn_module_on_the_hip_kernels(ops):
