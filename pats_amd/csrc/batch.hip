@@ -13,6 +13,7 @@
 // Everything is sized by capacities known on the host (rows_cap, Cmax); the actual counts stay on the device.
 #include "common.hpp"
 #include "chunk_plan.hpp"
+#include "lane_reduce.hpp"
 
 namespace pats {
 
@@ -40,15 +41,6 @@ struct ChunkRowsArgs {
     int srow;                 // entries of a pair in second / third: 2 * (max h + 1)
 };
 
-__device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 // one 256-thread workgroup per pair: cumulative match count, chunk plan, rows per chunk
 __global__ void __launch_bounds__(256)
 chunk_plan_kernel(ChunkRowsArgs g) {
@@ -65,7 +57,7 @@ chunk_plan_kernel(ChunkRowsArgs g) {
     for (int q0 = 0; q0 < N; q0 += 256) {
         const int q = q0 + t;
         const int keep = (q < N) ? (f[q] == 0) : 0;
-        const int incl = wave_incl_scan_i(keep, lane);
+        const int incl = (int)wave_scan_inclusive_u32((uint32_t)keep, lane);
         if (lane == 63) wsum[wave] = incl;
         wg_barrier();
         int base = carry;
@@ -108,7 +100,7 @@ chunk_prefix_kernel(ChunkRowsArgs g) {
     for (int64_t i0 = 0; i0 < n; i0 += 256) {
         const int64_t i = i0 + t;
         const int v = i < n ? g.counts[i] : 0;
-        const int incl = wave_incl_scan_i(v, lane);
+        const int incl = (int)wave_scan_inclusive_u32((uint32_t)v, lane);
         if (lane == 63) wsum[wave] = incl;
         wg_barrier();
         int64_t base = carry;

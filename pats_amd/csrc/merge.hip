@@ -10,6 +10,7 @@
 // own output slot; the merge is a gather ("new": each output entry finds its unique writer) or a
 // last-writer-wins scatter made deterministic with atomicMax on (source order, value) ("old").
 #include "common.hpp"
+#include "lane_reduce.hpp"
 
 namespace pats {
 
@@ -18,13 +19,38 @@ namespace pats {
 // before tile t (after scan_tiles_kernel); total = kept elements overall.
 constexpr int SCAN_TILE = 2048;
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+// a thread's K consecutive flags from i0 (I: the kernel's index type): keep[k] = 1 for a kept one; -> how many it keeps
+template <int K, class I>
+__device__ __forceinline__ int count_flags(const uint8_t* __restrict__ flags, I i0, I n, int (&keep)[K]) {
+    int c = 0;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d);
-        if (lane >= d) v += o;
+    for (int k = 0; k < K; ++k) {
+        keep[k] = (i0 + k < n) ? (flags[i0 + k] == 0) : 0;
+        c += keep[k];
     }
-    return v;
+    return c;
+}
+
+// their exclusive offsets, counting on from `run`; -> run past the thread's last flag
+template <int K, class I>
+__device__ __forceinline__ int write_offsets(int32_t* __restrict__ offs, I i0, I n, const int (&keep)[K], int run) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (i0 + k < n) offs[i0 + k] = run;
+        run += keep[k];
+    }
+    return run;
+}
+
+// a workgroup's scan of one value a thread: incl = the inclusive scan inside the thread's wave; -> the sum over the waves before
+// it, handed through wsum behind ONE wg_barrier()
+__device__ __forceinline__ int waves_before(int v, int lane, int wave, int* wsum, int& incl) {
+    incl = (int)wave_scan_inclusive_u32((uint32_t)v, lane);
+    if (lane == 63) wsum[wave] = incl;
+    wg_barrier();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += wsum[w];
+    return base;
 }
 
 __global__ void __launch_bounds__(256)
@@ -33,23 +59,10 @@ scan_flags_kernel(const uint8_t* __restrict__ flags, int64_t n, int32_t* __restr
     __shared__ int wsum[4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t i0 = (int64_t)blockIdx.x * SCAN_TILE + t * 8;
-    int keep[8], c = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        keep[k] = (i0 + k < n) ? (flags[i0 + k] == 0) : 0;
-        c += keep[k];
-    }
-    const int incl = wave_incl_scan(c, lane);
-    if (lane == 63) wsum[wave] = incl;
-    wg_barrier();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    int run = base + incl - c;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (i0 + k < n) offs[i0 + k] = run;
-        run += keep[k];
-    }
+    int keep[8], incl;
+    const int c = count_flags(flags, i0, n, keep);
+    const int base = waves_before(c, lane, wave, wsum, incl);
+    const int run = write_offsets(offs, i0, n, keep, base + incl - c);
     if (t == 255) tile_base[blockIdx.x] = run;
 }
 
@@ -62,11 +75,9 @@ scan_tiles_kernel(int32_t* __restrict__ tile_base, int tiles, int64_t* __restric
     wg_barrier();
     for (int b0 = 0; b0 < tiles; b0 += 1024) {
         const int v = (b0 + t < tiles) ? tile_base[b0 + t] : 0;
-        const int incl = wave_incl_scan(v, lane);
-        if (lane == 63) wsum[wave] = incl;
-        wg_barrier();
-        int base = carry;
-        for (int w = 0; w < wave; ++w) base += wsum[w];
+        int incl;
+        int base = waves_before(v, lane, wave, wsum, incl);
+        base += carry;
         if (b0 + t < tiles) tile_base[b0 + t] = base + incl - v;
         wg_barrier();
         if (t == 1023) carry = base + incl;
@@ -84,23 +95,12 @@ scan_small_kernel(const uint8_t* __restrict__ flags, int n, int32_t* __restrict_
                   int64_t* __restrict__ total) {
     __shared__ int wsum[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, i0 = t * 16;
-    int keep[16], c = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        keep[k] = (i0 + k < n) ? (flags[i0 + k] == 0) : 0;
-        c += keep[k];
-    }
-    const int incl = wave_incl_scan(c, lane);
-    if (lane == 63) wsum[wave] = incl;
-    wg_barrier();
-    int base = 0, all = 0;
-    for (int w = 0; w < 16; ++w) { if (w < wave) base += wsum[w]; all += wsum[w]; }
-    int run = base + incl - c;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (i0 + k < n) offs[i0 + k] = run;
-        run += keep[k];
-    }
+    int keep[16], incl;
+    const int c = count_flags(flags, i0, n, keep);
+    const int base = waves_before(c, lane, wave, wsum, incl);
+    int all = 0;
+    for (int w = 0; w < 16; ++w) all += wsum[w];
+    write_offsets(offs, i0, n, keep, base + incl - c);
     if (t < tiles) tile_base[t] = 0;
     if (t == 0 && total) *total = all;
 }
@@ -163,27 +163,31 @@ merge_slots_kernel(const uint8_t* __restrict__ ifn_L1, Scan sc, int64_t NP, int6
     slot[q] = (int32_t)s;
 }
 
-// border weighting, flag update, score hand-over into scores_back (second_layer.py:140-149,161-163 / :192-201,210-211)
-// for element e = row b, window cell `cell` of the trust / flag tensors
-__device__ __forceinline__ void merge_prepare_el(int merge_new, int64_t e, float* __restrict__ trust, uint8_t* __restrict__ ifn_L2,
-                                                 const int32_t* __restrict__ patch_of, double* __restrict__ scores_back) {
-    const int64_t b = e / 144;
-    const int cell = (int)(e - b * 144), x = cell % 12, y = cell / 12;
-    float t = trust[e];
+// cell `cell` of a row's 12 x 12 window: column x, row y; the window is 3 x 3 patches of 4 x 4 fine cells, so the cell is fine
+// cell (r, s) of the patch (a, c) places from the window's corner
+struct WinCell {
+    int x, y, a, r, c, s;
+    __device__ __forceinline__ explicit WinCell(int cell) : x(cell % 12), y(cell / 12), a(y / 4), r(y % 4), c(x / 4), s(x % 4) {}
+    // where patch q keeps this cell's score in scores_back [cells,16,9]
+    __device__ __forceinline__ int64_t back(int64_t q) const { return (q * 16 + r * 4 + s) * 9 + a * 3 + c; }
+};
+
+// second_layer.py:194-201 (:140-149 for merge_old, which does not take the 10000 off) for one cell: weighted trust score and
+// updated flag from the raw ones
+__device__ __forceinline__ float merge_prepared(float t, uint8_t f_in, int x, int y, int merge_new, uint8_t& f_out) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
         if (x < 3 - i || x > 7 + i || y < 3 - i || y > 7 + i) t *= 2.0f;
-    uint8_t f = ifn_L2[e];
+    uint8_t f = f_in;
     if (t > 2.0f) f = 1;
     if (x < 1 || x > 10 || y < 1 || y > 10) f = 1;
     if (merge_new && !f) t -= 10000.0f;
-    trust[e] = t;
-    ifn_L2[e] = f;
-    const int a = y / 4, r = y % 4, c = x / 4, s = x % 4;
-    const int64_t q = patch_of[b];
-    if (q >= 0) scores_back[(q * 16 + r * 4 + s) * 9 + a * 3 + c] = (double)t;
+    f_out = f;
+    return t;
 }
 
+// border weighting, flag update, score hand-over into scores_back (second_layer.py:140-149,161-163 / :192-201,210-211)
+// for element e = row b, window cell `cell` of the trust / flag tensors
 __global__ void __launch_bounds__(256)
 merge_prepare_kernel(int merge_new, RowBlock rb, float* __restrict__ trust, uint8_t* __restrict__ ifn_L2,
                      const int32_t* __restrict__ patch_of, double* __restrict__ scores_back) {
@@ -191,7 +195,14 @@ merge_prepare_kernel(int merge_new, RowBlock rb, float* __restrict__ trust, uint
     rb.get(base, B);
     const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (el >= B * 144) return;
-    merge_prepare_el(merge_new, el + base * 144, trust, ifn_L2, patch_of, scores_back);
+    const int64_t e = el + base * 144, b = e / 144;
+    const WinCell wc((int)(e - b * 144));
+    uint8_t f;
+    const float t = merge_prepared(trust[e], ifn_L2[e], wc.x, wc.y, merge_new, f);
+    trust[e] = t;
+    ifn_L2[e] = f;
+    const int64_t q = patch_of[b];
+    if (q >= 0) scores_back[wc.back(q)] = (double)t;
 }
 
 struct MergeGeom {
@@ -212,47 +223,44 @@ __device__ __forceinline__ MergeGeom pair_geom(const MergeGeom& g, const PairSha
 // choice is the first minimum of ITS OWNER's nine scores (+100000 for windows leaving the grid) -
 // argsort runs on scores_back_use, not on the re-gathered copy (:232).  The value scattered is
 // if_matching2[Y, X, sb] = if_matching at the entry itself, i.e. the (updated) L2 flag.
-__device__ __forceinline__ void merge_select_new_el(const MergeGeom& g, int64_t e, const int32_t* __restrict__ patch_of,
-                                                    const uint8_t* __restrict__ ifn_L2, const double* __restrict__ scores_back,
-                                                    const uint8_t* __restrict__ row_forced, uint8_t* __restrict__ out) {
+// the choice of fine cell (Y, X): the first minimum of the nine scores of its owner, score(k) for window k = 3a + c, with 100000
+// on a window that leaves the grid (second_layer.py:226-232)
+template <class Score>
+__device__ __forceinline__ int merge_first_min(const MergeGeom& g, int Y, int X, Score score) {
+    int sb = 0;
+    double best = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        double v = score(k);
+        const int by = Y + 4 * (k / 3 - 1), bx = X + 4 * (k % 3 - 1);
+        if (by < 0 || by >= g.h4 || bx < 0 || bx >= g.w4) v += 100000.0;
+        if (k == 0 || v < best) { best = v; sb = k; }
+    }
+    return sb;
+}
+
+// the single-chunk call: one thread per (row, window cell) of the B rows, the scores from scores_back as merge_prepare_kernel left it
+__global__ void __launch_bounds__(256)
+merge_select_new_kernel(MergeGeom g, int64_t B, const int32_t* __restrict__ patch_of, const uint8_t* __restrict__ ifn_L2,
+                        const double* __restrict__ scores_back, uint8_t* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= B * 144) return;
     const int64_t b = e / 144;
-    const int cell = (int)(e - b * 144), x = cell % 12, y = cell / 12;
-    const int a = y / 4, r = y % 4, c = x / 4, s = x % 4;
+    const WinCell wc((int)(e - b * 144));
     const int64_t q = patch_of[b];
     uint8_t res = 1;
     if (q >= 0) {
         const int hw = g.h * g.w;
         const int64_t bt = q / hw;
         const int p = (int)(q - bt * hw), hh = p / g.w, ww = p % g.w;
-        const int Y = 4 * hh + r + 4 * (a - 1), X = 4 * ww + s + 4 * (c - 1);
+        const int Y = 4 * hh + wc.r + 4 * (wc.a - 1), X = 4 * ww + wc.s + 4 * (wc.c - 1);
         if (Y >= 0 && Y < g.h4 && X >= 0 && X < g.w4) {
             const int64_t qs = bt * hw + (Y / 4) * g.w + X / 4;
             const double* u = scores_back + (qs * 16 + (Y % 4) * 4 + X % 4) * 9;
-            int sb = 0;
-            double best = 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const int by = Y + 4 * (k / 3 - 1), bx = X + 4 * (k % 3 - 1);
-                double v = u[k];
-                if (by < 0 || by >= g.h4 || bx < 0 || bx >= g.w4) v += 100000.0;
-                if (k == 0 || v < best) { best = v; sb = k; }
-            }
-            if (sb == 8 - (a * 3 + c)) res = ifn_L2[e];
+            if (merge_first_min(g, Y, X, [&](int k) { return u[k]; }) == 8 - (wc.a * 3 + wc.c)) res = ifn_L2[e];
         }
     }
-    if (row_forced && row_forced[b]) res = 1;          // pats.py:38-39 on the returned flags (batch mode)
     out[e] = res;
-}
-
-__global__ void __launch_bounds__(256)
-merge_select_new_kernel(MergeGeom g, RowBlock rb, const int32_t* __restrict__ patch_of,
-                        const uint8_t* __restrict__ ifn_L2, const double* __restrict__ scores_back,
-                        const uint8_t* __restrict__ row_forced, uint8_t* __restrict__ out) {
-    int64_t base, B;
-    rb.get(base, B);
-    const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (el >= B * 144) return;
-    merge_select_new_el(g, el + base * 144, patch_of, ifn_L2, scores_back, row_forced, out);
 }
 
 // "old" (second_layer.py:165-189): one thread per fine cell re-gathers its nine candidates by geometry
@@ -304,12 +312,16 @@ merge_scatter_old_kernel(MergeGeom g, PairShapes ps, int batch_num, const int32_
     merge_scatter_old_cell(g, bt * g.h * g.w, e - bt * cells, slot, ifn_L2, scores_back, winner);
 }
 
-__device__ __forceinline__ void merge_finish_old_el(const MergeGeom& g0, const PairShapes& ps, int64_t e,
-                                                    const int32_t* __restrict__ patch_of, const unsigned* __restrict__ winner,
-                                                    const uint8_t* __restrict__ row_forced, uint8_t* __restrict__ out) {
-    const int64_t b = e / 144;
-    const int cell = (int)(e - b * 144), x = cell % 12, y = cell / 12;
-    const int a = y / 4, r = y % 4, c = x / 4, s = x % 4;
+__global__ void __launch_bounds__(256)
+merge_finish_old_kernel(MergeGeom g0, PairShapes ps, RowBlock rb, const int32_t* __restrict__ patch_of,
+                        const unsigned* __restrict__ winner, const uint8_t* __restrict__ row_forced,
+                        uint8_t* __restrict__ out) {
+    int64_t base, B;
+    rb.get(base, B);
+    const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (el >= B * 144) return;
+    const int64_t e = el + base * 144, b = e / 144;
+    const WinCell wc((int)(e - b * 144));
     const int64_t q = patch_of[b];
     uint8_t res = 1;
     if (q >= 0) {
@@ -317,29 +329,18 @@ __device__ __forceinline__ void merge_finish_old_el(const MergeGeom& g0, const P
         const MergeGeom g = pair_geom(g0, ps, bt);
         const int64_t cb = ps.shape ? ps.base(bt) : bt * g.h * g.w;
         const int p = (int)(q - cb), hh = p / g.w, ww = p % g.w;
-        const unsigned v = winner[cb * 144 + ((int64_t)(4 * hh + r) * g.w4 + 4 * ww + s) * 9 + a * 3 + c];
+        const unsigned v = winner[cb * 144 + ((int64_t)(4 * hh + wc.r) * g.w4 + 4 * ww + wc.s) * 9 + wc.a * 3 + wc.c];
         if (v) res = (uint8_t)(v & 1u);
     }
     if (row_forced && row_forced[b]) res = 1;
     out[e] = res;
 }
 
-__global__ void __launch_bounds__(256)
-merge_finish_old_kernel(MergeGeom g, PairShapes ps, RowBlock rb, const int32_t* __restrict__ patch_of,
-                        const unsigned* __restrict__ winner, const uint8_t* __restrict__ row_forced,
-                        uint8_t* __restrict__ out) {
-    int64_t base, B;
-    rb.get(base, B);
-    const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (el >= B * 144) return;
-    merge_finish_old_el(g, ps, el + base * 144, patch_of, winner, row_forced, out);
-}
-
 // ---- merge_patches_new for SEVERAL chunks of a row table in two fully parallel launches ---------------------------------------
 // The reference walks the chunks in order because they couple through scores_back (pats.py:32,37): the select of chunk c reads,
 // for every candidate window, the score its owner patch left there - written by the prepare of the LATEST chunk <= c that holds the
 // owner (a patch of the grid row two chunks share is in both), or what scores_back held before.  That value is a function of the
-// owner row's RAW trust score and flag alone (merge_prepared below), so nothing has to be written before it is read:
+// owner row's RAW trust score and flag alone (merge_prepared above), so nothing has to be written before it is read:
 //   select   one thread per (row, window cell): finds each candidate owner's row through the table (row_slot of chunk c, c - 1, ...),
 //            recomputes the nine prepared scores from the raw tensors, falls back to the scores_back it was handed (zeros when the
 //            call starts a pair) and writes `out`.  Reads trust / flags, writes only `out`.
@@ -357,19 +358,6 @@ struct MergeTable {
     const int32_t* row_pair;      // ragged: the row's pair (uniform: row_cell / N)
 };
 
-// second_layer.py:194-201 for one cell: weighted trust score and updated flag from the raw ones
-__device__ __forceinline__ float merge_prepared(float t, uint8_t f_in, int x, int y, uint8_t& f_out) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if (x < 3 - i || x > 7 + i || y < 3 - i || y > 7 + i) t *= 2.0f;
-    uint8_t f = f_in;
-    if (t > 2.0f) f = 1;
-    if (x < 1 || x > 10 || y < 1 || y > 10) f = 1;
-    if (!f) t -= 10000.0f;
-    f_out = f;
-    return t;
-}
-
 __global__ void __launch_bounds__(256)
 merge_select_new_par_kernel(MergeGeom g0, MergeTable tb, const float* __restrict__ trust, const uint8_t* __restrict__ ifn_L2,
                             const double* __restrict__ scores_back, int fresh, uint8_t* __restrict__ out) {
@@ -380,7 +368,8 @@ merge_select_new_par_kernel(MergeGeom g0, MergeTable tb, const float* __restrict
     const int64_t el = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (el >= (last - first) * 144) return;
     const int64_t row = first + el / 144;
-    const int cell = (int)(el % 144), x = cell % 12, y = cell / 12;
+    const int cell = (int)(el % 144);
+    const WinCell wc(cell);
     int c = tb.c_lo;
     while (c + 1 < tb.c_hi && row >= tb.chunk_base[c + 1]) ++c;       // the row's chunk
     const int64_t NP = tb.ps.cells;
@@ -390,35 +379,24 @@ merge_select_new_par_kernel(MergeGeom g0, MergeTable tb, const float* __restrict
     uint8_t res = 1;
     if (q >= 0) {
         uint8_t f_own;
-        (void)merge_prepared(trust[e], ifn_L2[e], x, y, f_own);
+        (void)merge_prepared(trust[e], ifn_L2[e], wc.x, wc.y, 1, f_own);
         const int bt = tb.row_pair ? tb.row_pair[row] : q / (g0.h * g0.w);
         const MergeGeom g = pair_geom(g0, tb.ps, bt);
         const int64_t cb = tb.ps.shape ? tb.ps.base(bt) : (int64_t)bt * g.h * g.w;
         const int pl = (int)(q - cb), hh = pl / g.w, ww = pl - hh * g.w;
-        const int a = y >> 2, r = y & 3, cc = x >> 2, s_ = x & 3;
-        const int Y = 4 * hh + r + 4 * (a - 1), X = 4 * ww + s_ + 4 * (cc - 1);
+        const int Y = 4 * hh + wc.r + 4 * (wc.a - 1), X = 4 * ww + wc.s + 4 * (wc.c - 1);
         if (Y >= 0 && Y < g.h4 && X >= 0 && X < g.w4) {
             const int64_t qs = cb + (Y >> 2) * g.w + (X >> 2);                   // the owner of fine cell (Y, X)
             int64_t rs = -1;                                                  // its row in the latest chunk <= c of the walk
             for (int c2 = c; c2 >= tb.c_lo && rs < 0; --c2) rs = tb.row_slot[(int64_t)c2 * NP + qs];
             const double* u = scores_back + (qs * 16 + (Y & 3) * 4 + (X & 3)) * 9;
-            int sb = 0;
-            double best = 0.0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                double v;
-                if (rs >= 0) {
-                    const int yy = (k / 3) * 4 + (Y & 3), xx = (k % 3) * 4 + (X & 3);
-                    uint8_t fk;
-                    v = (double)merge_prepared(trust[rs * 144 + yy * 12 + xx], ifn_L2[rs * 144 + yy * 12 + xx], xx, yy, fk);
-                } else {
-                    v = fresh ? 0.0 : u[k];
-                }
-                const int by = Y + 4 * (k / 3 - 1), bx = X + 4 * (k % 3 - 1);
-                if (by < 0 || by >= g.h4 || bx < 0 || bx >= g.w4) v += 100000.0;
-                if (k == 0 || v < best) { best = v; sb = k; }
-            }
-            if (sb == 8 - (a * 3 + cc)) res = f_own;
+            const int sb = merge_first_min(g, Y, X, [&](int k) {
+                if (rs < 0) return fresh ? 0.0 : u[k];
+                const int yy = (k / 3) * 4 + (Y & 3), xx = (k % 3) * 4 + (X & 3);      // recomputed from the owner's raw row
+                uint8_t fk;
+                return (double)merge_prepared(trust[rs * 144 + yy * 12 + xx], ifn_L2[rs * 144 + yy * 12 + xx], xx, yy, 1, fk);
+            });
+            if (sb == 8 - (wc.a * 3 + wc.c)) res = f_own;
         }
     }
     if (tb.row_forced[row]) res = 1;                    // pats.py:38-39 on the returned flags
@@ -440,9 +418,9 @@ merge_prepare_new_par_kernel(MergeTable tb, float* __restrict__ trust, uint8_t* 
     if (i >= tb.rows_local * 144) return;
     const int64_t row = tb.row_origin + i / 144;
     if (row < first || row >= last) { out[i] = 1; return; }            // rows outside the walked blocks: "no match"
-    const int cell = (int)(i % 144), x = cell % 12, y = cell / 12;
+    const WinCell wc((int)(i % 144));
     uint8_t f;
-    const float t = merge_prepared(trust[i], ifn_L2[i], x, y, f);
+    const float t = merge_prepared(trust[i], ifn_L2[i], wc.x, wc.y, 1, f);
     trust[i] = t;
     ifn_L2[i] = f;
     const int32_t q = tb.row_cell[row];
@@ -451,7 +429,7 @@ merge_prepare_new_par_kernel(MergeTable tb, float* __restrict__ trust, uint8_t* 
     while (c + 1 < tb.c_hi && row >= tb.chunk_base[c + 1]) ++c;
     for (int c2 = c + 1; c2 < tb.c_hi; ++c2)
         if (tb.row_slot[(int64_t)c2 * NP + q] >= 0) return;           // a later chunk of the walk holds the patch again: its row writes
-    scores_back[((int64_t)q * 16 + (y & 3) * 4 + (x & 3)) * 9 + (y >> 2) * 3 + (x >> 2)] = (double)t;
+    scores_back[wc.back(q)] = (double)t;
 }
 
 // ---- third-level inputs, pats.py:53-58 ---------------------------------------------------------------
@@ -615,6 +593,46 @@ using namespace pats;
 
 static inline unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// the two confidence arrays of a *_conf entry: both given (a may be null where the entry has no rows of it) and 4-byte aligned
+static int conf_pair(const char* who, const char* name_a, const void* a, const char* name_b, const void* b, bool a_optional = false) {
+    PATS_REQUIRE((a || a_optional) && b, "%s: null %s / %s", who, name_a, name_b);
+    PATS_REQUIRE((uintptr_t)a % 4 == 0 && (uintptr_t)b % 4 == 0, "%s: %s / %s must be 4-byte aligned", who, name_a, name_b);
+    return PATS_OK;
+}
+
+// the grid of an H x W image: h x w coarse patches of 32 px, 4h x 4w fine cells with nine scores each
+static MergeGeom merge_geom(int H, int W) {
+    const int h = H / 32, w = W / 32;
+    return MergeGeom{h, w, 4 * h, 4 * w, (int64_t)h * 4 * w * 4 * 9};
+}
+
+// One chunk of merge_old in its four launches: prepare, clear the winners, scatter, finish.  rb: the chunk's rows, a launch
+// covering n_rows of them; slot / patch_of: cell -> row and row -> cell of THIS chunk; trust / flags / out are indexed by the row
+// numbers rb yields (the chunk walk passes shifted pointers).  The fills around the chain are the caller's.
+static int merge_old_step(const MergeGeom& g, const PairShapes& ps, const RowBlock& rb, int64_t n_rows, const int32_t* slot,
+                          const int32_t* patch_of, const uint8_t* row_forced, float* trust, uint8_t* flags, uint8_t* out,
+                          double* scores_back, unsigned* winner, hipStream_t st) {
+    const int64_t fine_cells = ps.cells * 16;                      // the scatter's threads: every pair's 4h x 4w, uniform or ragged
+    hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(n_rows * 144)), dim3(256), 0, st, 0, rb, trust, flags, patch_of, scores_back);
+    if (fill_bytes(winner, 0, sizeof(unsigned) * (size_t)(ps.cells * 144), st)) return PATS_ERR_LAUNCH;
+    hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256(fine_cells)), dim3(256), 0, st, g, ps, (int)ps.pairs, slot, flags,
+                       scores_back, winner);
+    hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(n_rows * 144)), dim3(256), 0, st, g, ps, rb, patch_of, winner, row_forced,
+                       out);
+    return PATS_OK;
+}
+
+// merge_new over chunks [tb.c_lo, tb.c_hi) of a table in its two launches (merge_select_new_par_kernel): n_select / n_prepare rows
+// of threads each, as the caller sizes them
+static int launch_merge_new_par(const MergeGeom& g, const MergeTable& tb, float* trust, uint8_t* flags, double* scores_back, int fresh,
+                                uint8_t* out, int64_t n_select, int64_t n_prepare, const char* what, hipStream_t st) {
+    hipLaunchKernelGGL(merge_select_new_par_kernel, dim3(blocks256(n_select * 144)), dim3(256), 0, st, g, tb, trust, flags, scores_back,
+                       fresh, out);
+    hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n_prepare * 144)), dim3(256), 0, st, tb, trust, flags, scores_back,
+                       fresh, out);
+    return check_launch(what);
+}
+
 extern "C" size_t pats_merge_workspace_bytes(int64_t B, int H, int W, int batch_num) {
     if (B < 0 || H < 32 || W < 32 || batch_num < 1) return 0;
     const int64_t NP = (int64_t)batch_num * (H / 32) * (W / 32);
@@ -632,7 +650,7 @@ extern "C" int pats_merge_patches(int merge_new, int64_t B, float* trust_score, 
     PATS_REQUIRE(workspace && workspace_bytes >= pats_merge_workspace_bytes(B, H, W, batch_num),
                  "merge_patches: workspace too small");
     hipStream_t st = as_stream(stream);
-    MergeGeom g{H / 32, W / 32, 4 * (H / 32), 4 * (W / 32), (int64_t)(H / 32) * 4 * (W / 32) * 4 * 9};
+    const MergeGeom g = merge_geom(H, W);
     const int64_t NP = (int64_t)batch_num * g.h * g.w;
     char* ws = static_cast<char*>(workspace);
     Scan sc;
@@ -644,19 +662,15 @@ extern "C" int pats_merge_patches(int merge_new, int64_t B, float* trust_score, 
     if (hipMemsetAsync(patch_of, 0xff, sizeof(int32_t) * (size_t)B, st) != hipSuccess) return check_launch("merge memset");
     hipLaunchKernelGGL(merge_slots_kernel, dim3(blocks256(NP)), dim3(256), 0, st, if_nomatching1_L1, sc, NP, B, slot, patch_of);
     const RowBlock rb{nullptr, B};
-    hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, merge_new, rb, trust_score,
-                       if_nomatching1_L2, patch_of, scores_back);
     if (merge_new) {
-        hipLaunchKernelGGL(merge_select_new_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, g, rb, patch_of,
-                           if_nomatching1_L2, scores_back, (const uint8_t*)nullptr, out);
-    } else {
-        if (hipMemsetAsync(winner, 0, sizeof(unsigned) * (size_t)(batch_num * g.per), st) != hipSuccess)
-            return check_launch("merge memset");
-        const PairShapes ps = uniform_shapes(batch_num, g.h, g.w, (int64_t)g.h * g.w);
-        hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * batch_num)), dim3(256), 0, st, g, ps,
-                           batch_num, slot, if_nomatching1_L2, scores_back, winner);
-        hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, g, ps, rb, patch_of, winner,
-                           (const uint8_t*)nullptr, out);
+        hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, 1, rb, trust_score, if_nomatching1_L2,
+                           patch_of, scores_back);
+        hipLaunchKernelGGL(merge_select_new_kernel, dim3(blocks256(B * 144)), dim3(256), 0, st, g, B, patch_of, if_nomatching1_L2,
+                           scores_back, out);
+    } else {                                        // (what becomes of scores_back afterwards, second_layer.py:191, is Python's)
+        rc = merge_old_step(g, uniform_shapes(batch_num, g.h, g.w, (int64_t)g.h * g.w), rb, B, slot, patch_of, nullptr, trust_score,
+                            if_nomatching1_L2, out, scores_back, winner, st);
+        if (rc != PATS_OK) return rc;
     }
     return check_launch("merge_patches");
 }
@@ -667,42 +681,24 @@ static int merge_batch_impl(int merge_new, int Cmax, const MergeGeom& g, const P
                             const int32_t* row_cell, const int32_t* row_pair, const int32_t* row_slot, const uint8_t* row_forced,
                             float* trust_score, uint8_t* if_nomatching1_L2, double* scores_back, int zero_scores_back, uint8_t* out,
                             void* workspace, hipStream_t st) {
-    const int64_t pairs = ps.pairs, NP = ps.cells;
-    const int64_t block_cap = NP < rows_cap ? NP : rows_cap;       // a chunk block holds at most one row per coarse cell
-    unsigned* winner = reinterpret_cast<unsigned*>(workspace);
-    // merge_new: two parallel launches for all chunks (merge_select_new_par_kernel); PATS_MERGE_PER_CHUNK=1 (diagnostic library, uniform
-    // batches): the launch chain per chunk of rounds 3-5.  merge_old (indoor: one chunk, cap 512) keeps its chain.
-    static const bool per_chunk = [] { const char* e = diag_env("PATS_MERGE_PER_CHUNK"); return e && atoi(e) != 0; }();
-    if (merge_new && (!per_chunk || ps.shape)) {
-        const MergeTable tb{Cmax, 0, Cmax, pairs, 0, rows_cap, chunk_base, row_cell, row_slot, row_forced, ps, row_pair};
-        hipLaunchKernelGGL(merge_select_new_par_kernel, dim3(blocks256(rows_cap * 144)), dim3(256), 0, st, g, tb, trust_score, if_nomatching1_L2,
-                           scores_back, zero_scores_back, out);
-        const int64_t n2 = rows_cap > NP ? rows_cap : NP;
-        hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n2 * 144)), dim3(256), 0, st, tb, trust_score, if_nomatching1_L2,
-                           scores_back, zero_scores_back, out);
-        return check_launch("merge_patches_batch");
+    const int64_t NP = ps.cells;
+    // merge_new: two parallel launches for all chunks.  merge_old (indoor: one chunk, cap 512) walks the chunks with its chain.
+    if (merge_new) {
+        const MergeTable tb{Cmax, 0, Cmax, ps.pairs, 0, rows_cap, chunk_base, row_cell, row_slot, row_forced, ps, row_pair};
+        return launch_merge_new_par(g, tb, trust_score, if_nomatching1_L2, scores_back, zero_scores_back, out, rows_cap,
+                                    rows_cap > NP ? rows_cap : NP, "merge_patches_batch", st);
     }
     // rows outside every block (padding past the total) are never visited: "no match"
     if (fill_bytes(out, 1, (size_t)rows_cap * 144, st)) return PATS_ERR_LAUNCH;
     // pats.py:32: every pair starts from a zeroed scores_back
     if (zero_scores_back && fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
-    const int64_t fine_cells = ps.shape ? NP * 16 : (int64_t)g.h4 * g.w4 * pairs;
+    const int64_t block_cap = NP < rows_cap ? NP : rows_cap;       // a chunk block holds at most one row per coarse cell
     for (int c = 0; c < Cmax; ++c) {
-        const RowBlock rb{chunk_base + c, 0};
-        hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, merge_new, rb, trust_score,
-                           if_nomatching1_L2, row_cell, scores_back);
-        if (merge_new) {
-            hipLaunchKernelGGL(merge_select_new_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, rb, row_cell,
-                               if_nomatching1_L2, scores_back, row_forced, out);
-        } else {
-            if (fill_bytes(winner, 0, sizeof(unsigned) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
-            hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256(fine_cells)), dim3(256), 0, st, g, ps,
-                               (int)pairs, row_slot + (int64_t)c * NP, if_nomatching1_L2, scores_back, winner);
-            hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, ps, rb, row_cell, winner,
-                               row_forced, out);
-            // merge_patches_old hands back a zeroed scores_back (second_layer.py:191): the next chunk starts from zeros
-            if (fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
-        }
+        const int rc = merge_old_step(g, ps, RowBlock{chunk_base + c, 0}, block_cap, row_slot + (int64_t)c * NP, row_cell, row_forced,
+                                      trust_score, if_nomatching1_L2, out, scores_back, reinterpret_cast<unsigned*>(workspace), st);
+        if (rc != PATS_OK) return rc;
+        // merge_patches_old hands back a zeroed scores_back (second_layer.py:191): the next chunk starts from zeros
+        if (fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
     }
     return check_launch("merge_patches_batch");
 }
@@ -723,7 +719,7 @@ extern "C" int pats_merge_patches_batch(int merge_new, int Cmax, int64_t pairs, 
                  "merge_patches_batch: null pointer");
     PATS_REQUIRE(merge_new || (workspace && workspace_bytes >= pats_merge_batch_workspace_bytes(pairs, H, W)),
                  "merge_patches_batch: workspace too small");
-    MergeGeom g{H / 32, W / 32, 4 * (H / 32), 4 * (W / 32), (int64_t)(H / 32) * 4 * (W / 32) * 4 * 9};
+    const MergeGeom g = merge_geom(H, W);
     return merge_batch_impl(merge_new, Cmax, g, uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w), rows_cap, chunk_base, row_cell,
                             nullptr, row_slot, row_forced, trust_score, if_nomatching1_L2, scores_back, zero_scores_back, out, workspace,
                             as_stream(stream));
@@ -745,35 +741,24 @@ extern "C" int pats_merge_patches_chunks(int merge_new, int Cmax, int c_lo, int 
                  "merge_patches_chunks: null pointer");
     PATS_REQUIRE(merge_new || (workspace && workspace_bytes >= pats_merge_batch_workspace_bytes(pairs, H, W)),
                  "merge_patches_chunks: workspace too small");
-    MergeGeom g{H / 32, W / 32, 4 * (H / 32), 4 * (W / 32), (int64_t)(H / 32) * 4 * (W / 32) * 4 * 9};
+    const MergeGeom g = merge_geom(H, W);
     hipStream_t st = as_stream(stream);
-    const int64_t NP = pairs * g.h * g.w;
+    const PairShapes ps = uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w);
+    const int64_t NP = ps.cells;
     if (merge_new) {
-        const MergeTable tb{Cmax, c_lo, c_hi, pairs, row_origin, rows_local, chunk_base, row_cell, row_slot, row_forced,
-                            uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w), nullptr};
-        hipLaunchKernelGGL(merge_select_new_par_kernel, dim3(blocks256(rows_local * 144)), dim3(256), 0, st, g, tb, trust_score,
-                           if_nomatching1_L2, scores_back, zero_scores_back, out);
-        const int64_t n2 = zero_scores_back && NP > rows_local ? NP : rows_local;
-        hipLaunchKernelGGL(merge_prepare_new_par_kernel, dim3(blocks256(n2 * 144)), dim3(256), 0, st, tb, trust_score, if_nomatching1_L2,
-                           scores_back, zero_scores_back, out);
-        return check_launch("merge_patches_chunks");
+        const MergeTable tb{Cmax, c_lo, c_hi, pairs, row_origin, rows_local, chunk_base, row_cell, row_slot, row_forced, ps, nullptr};
+        return launch_merge_new_par(g, tb, trust_score, if_nomatching1_L2, scores_back, zero_scores_back, out, rows_local,
+                                    zero_scores_back && NP > rows_local ? NP : rows_local, "merge_patches_chunks", st);
     }
     // merge_old: the per-chunk chain on pointers shifted to table rows
-    unsigned* winner = reinterpret_cast<unsigned*>(workspace);
-    float* tr = trust_score - row_origin * 144;
-    uint8_t* fl = if_nomatching1_L2 - row_origin * 144;
-    uint8_t* ou = out - row_origin * 144;
     if (fill_bytes(out, 1, (size_t)rows_local * 144, st)) return PATS_ERR_LAUNCH;
     if (zero_scores_back && fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
     const int64_t block_cap = NP < rows_local ? NP : rows_local;
     for (int c = c_lo; c < c_hi; ++c) {
-        const RowBlock rb{chunk_base + c, 0};
-        hipLaunchKernelGGL(merge_prepare_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, 0, rb, tr, fl, row_cell, scores_back);
-        if (fill_bytes(winner, 0, sizeof(unsigned) * (size_t)(pairs * g.per), st)) return PATS_ERR_LAUNCH;
-        const PairShapes ps = uniform_shapes(pairs, g.h, g.w, (int64_t)g.h * g.w);
-        hipLaunchKernelGGL(merge_scatter_old_kernel, dim3(blocks256((int64_t)g.h4 * g.w4 * pairs)), dim3(256), 0, st, g, ps, (int)pairs,
-                           row_slot + (int64_t)c * NP, fl, scores_back, winner);
-        hipLaunchKernelGGL(merge_finish_old_kernel, dim3(blocks256(block_cap * 144)), dim3(256), 0, st, g, ps, rb, row_cell, winner, row_forced, ou);
+        const int rc = merge_old_step(g, ps, RowBlock{chunk_base + c, 0}, block_cap, row_slot + (int64_t)c * NP, row_cell, row_forced,
+                                      trust_score - row_origin * 144, if_nomatching1_L2 - row_origin * 144, out - row_origin * 144,
+                                      scores_back, reinterpret_cast<unsigned*>(workspace), st);
+        if (rc != PATS_OK) return rc;
         if (fill_bytes(scores_back, 0, sizeof(double) * (size_t)(NP * 144), st)) return PATS_ERR_LAUNCH;
     }
     return check_launch("merge_patches_chunks");
@@ -859,22 +844,15 @@ __global__ void __launch_bounds__(256) bypair_offsets_kernel(ByPairArgs g) {    
         wg_barrier();
     }
 }
-__global__ void __launch_bounds__(256) bypair_copy_kernel(ByPairArgs g) {
+// CONF: the matches' confidences beside them
+template <bool CONF>
+__global__ void __launch_bounds__(256) bypair_copy_kernel(ByPairArgs g, const float* __restrict__ conf, float* __restrict__ out_conf) {
     const int64_t M = *g.M;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
         const int64_t k = bypair_key(g, i), d = g.seg_dst[k] + (i - g.seg_lo[k]);
         reinterpret_cast<float2*>(g.out_l)[d] = reinterpret_cast<const float2*>(g.ml)[i];
         reinterpret_cast<float2*>(g.out_r)[d] = reinterpret_cast<const float2*>(g.mr)[i];
-    }
-}
-// the same copy with the matches' confidences beside them
-__global__ void __launch_bounds__(256) bypair_copy_conf_kernel(ByPairArgs g, const float* __restrict__ conf, float* __restrict__ out_conf) {
-    const int64_t M = *g.M;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
-        const int64_t k = bypair_key(g, i), d = g.seg_dst[k] + (i - g.seg_lo[k]);
-        reinterpret_cast<float2*>(g.out_l)[d] = reinterpret_cast<const float2*>(g.ml)[i];
-        reinterpret_cast<float2*>(g.out_r)[d] = reinterpret_cast<const float2*>(g.mr)[i];
-        out_conf[d] = conf[i];
+        if (CONF) out_conf[d] = conf[i];
     }
 }
 }  // namespace pats
@@ -887,7 +865,23 @@ static int matches_by_pair_impl(const float* matches_l, const float* matches_r, 
                                 const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                 float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
                                 void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair = nullptr,
-                                const float* match_conf = nullptr, float* out_conf = nullptr);
+                                const float* match_conf = nullptr, float* out_conf = nullptr) {
+    PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && N >= 1, "matches_by_pair: bad shape");
+    PATS_REQUIRE(matches_l && matches_r && match_row && M_dev && (row_cell || row_pair) && chunk_base && out_l && out_r && pair_off,
+                 "matches_by_pair: null pointer");
+    PATS_REQUIRE(workspace && workspace_bytes >= pats_matches_by_pair_workspace_bytes(Cmax, pairs), "matches_by_pair: workspace too small");
+    hipStream_t st = as_stream(stream);
+    int64_t* ws = reinterpret_cast<int64_t*>(workspace);
+    const int64_t nseg = (int64_t)Cmax * pairs;
+    if (fill_bytes(ws, 0, sizeof(int64_t) * (size_t)(2 * nseg), st)) return PATS_ERR_LAUNCH;        // runs without matches: lo = hi = 0
+    ByPairArgs g{matches_l, matches_r, match_row, M_dev, row_cell, chunk_base, Cmax, pairs, N, out_l, out_r, pair_off, ws, ws + nseg,
+                 ws + 2 * nseg, P_dev, status, row_pair};
+    hipLaunchKernelGGL(bypair_runs_kernel, dim3(2048), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(bypair_offsets_kernel, dim3(1), dim3(256), 0, st, g);
+    if (out_conf) hipLaunchKernelGGL(bypair_copy_kernel<true>, dim3(2048), dim3(256), 0, st, g, match_conf, out_conf);
+    else hipLaunchKernelGGL(bypair_copy_kernel<false>, dim3(2048), dim3(256), 0, st, g, match_conf, out_conf);
+    return check_launch("matches_by_pair kernels");
+}
 extern "C" int pats_matches_by_pair_f32(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
                                         const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
                                         float* out_l, float* out_r, int64_t* pair_off, void* workspace, size_t workspace_bytes,
@@ -916,16 +910,13 @@ extern "C" int pats_matches_by_row_pair_summary_f32(const float* matches_l, cons
 }
 // the regroup entries that carry the matches' confidences along: match_conf [cap] in, out_conf [cap] out, in the slots of
 // matches_l / out_l.  status may be null for both (pair_off then holds the pairs + 1 offsets only, P_dev is ignored).
-#define PATS_CONF_PAIR(who, in, out)                                                                      \
-    PATS_REQUIRE((in) && (out), who ": null match_conf / out_conf");                                      \
-    PATS_REQUIRE((uintptr_t)(in) % 4 == 0 && (uintptr_t)(out) % 4 == 0, who ": match_conf / out_conf must be 4-byte aligned")
 extern "C" int pats_matches_by_pair_summary_conf_f32(const float* matches_l, const float* matches_r, const float* match_conf,
                                                      const int32_t* match_row, const int64_t* M_dev, const int32_t* row_cell,
                                                      const int64_t* chunk_base, int Cmax, int64_t pairs, int N, float* out_l,
                                                      float* out_r, float* out_conf, int64_t* pair_off, const int64_t* P_dev,
                                                      const int32_t* status, void* workspace, size_t workspace_bytes,
                                                      pats_stream_t stream) {
-    PATS_CONF_PAIR("matches_by_pair_summary_conf", match_conf, out_conf);
+    if (const int rc = conf_pair("matches_by_pair_summary_conf", "match_conf", match_conf, "out_conf", out_conf)) return rc;
     PATS_REQUIRE(row_cell, "matches_by_pair_summary_conf: null row_cell");
     return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, row_cell, chunk_base, Cmax, pairs, N, out_l, out_r, pair_off, P_dev,
                                 status, workspace, workspace_bytes, stream, nullptr, match_conf, out_conf);
@@ -936,31 +927,10 @@ extern "C" int pats_matches_by_row_pair_summary_conf_f32(const float* matches_l,
                                                          float* out_r, float* out_conf, int64_t* pair_off, const int64_t* P_dev,
                                                          const int32_t* status, void* workspace, size_t workspace_bytes,
                                                          pats_stream_t stream) {
-    PATS_CONF_PAIR("matches_by_row_pair_summary_conf", match_conf, out_conf);
+    if (const int rc = conf_pair("matches_by_row_pair_summary_conf", "match_conf", match_conf, "out_conf", out_conf)) return rc;
     PATS_REQUIRE(row_pair, "matches_by_row_pair_summary_conf: null row_pair");
     return matches_by_pair_impl(matches_l, matches_r, match_row, M_dev, nullptr, chunk_base, Cmax, pairs, 1, out_l, out_r, pair_off, P_dev,
                                 status, workspace, workspace_bytes, stream, row_pair, match_conf, out_conf);
-}
-static int matches_by_pair_impl(const float* matches_l, const float* matches_r, const int32_t* match_row, const int64_t* M_dev,
-                                const int32_t* row_cell, const int64_t* chunk_base, int Cmax, int64_t pairs, int N,
-                                float* out_l, float* out_r, int64_t* pair_off, const int64_t* P_dev, const int32_t* status,
-                                void* workspace, size_t workspace_bytes, pats_stream_t stream, const int32_t* row_pair,
-                                const float* match_conf, float* out_conf) {
-    PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && N >= 1, "matches_by_pair: bad shape");
-    PATS_REQUIRE(matches_l && matches_r && match_row && M_dev && (row_cell || row_pair) && chunk_base && out_l && out_r && pair_off,
-                 "matches_by_pair: null pointer");
-    PATS_REQUIRE(workspace && workspace_bytes >= pats_matches_by_pair_workspace_bytes(Cmax, pairs), "matches_by_pair: workspace too small");
-    hipStream_t st = as_stream(stream);
-    int64_t* ws = reinterpret_cast<int64_t*>(workspace);
-    const int64_t nseg = (int64_t)Cmax * pairs;
-    if (fill_bytes(ws, 0, sizeof(int64_t) * (size_t)(2 * nseg), st)) return PATS_ERR_LAUNCH;        // runs without matches: lo = hi = 0
-    ByPairArgs g{matches_l, matches_r, match_row, M_dev, row_cell, chunk_base, Cmax, pairs, N, out_l, out_r, pair_off, ws, ws + nseg,
-                 ws + 2 * nseg, P_dev, status, row_pair};
-    hipLaunchKernelGGL(bypair_runs_kernel, dim3(2048), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(bypair_offsets_kernel, dim3(1), dim3(256), 0, st, g);
-    if (out_conf) hipLaunchKernelGGL(bypair_copy_conf_kernel, dim3(2048), dim3(256), 0, st, g, match_conf, out_conf);
-    else hipLaunchKernelGGL(bypair_copy_kernel, dim3(2048), dim3(256), 0, st, g);
-    return check_launch("matches_by_pair kernels");
 }
 
 extern "C" size_t pats_compact_workspace_bytes(int64_t n) { return n < 0 ? 0 : scan_bytes(n) + 64; }
@@ -984,29 +954,6 @@ extern "C" int pats_third_inputs_f32(const uint8_t* if_nomatching, const float* 
 
 static int refine_scatter_impl(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f, const float* label,
                                int label_stride, int64_t B, int64_t P, uint8_t* if_nomatching16, float* pts16, void* workspace,
-                               size_t workspace_bytes, pats_stream_t stream, const float* conf, float* conf16);
-extern "C" int pats_refine_scatter_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f,
-                                       const float* label, int label_stride, int64_t B, int64_t P,
-                                       uint8_t* if_nomatching16, float* pts16, void* workspace,
-                                       size_t workspace_bytes, pats_stream_t stream) {
-    return refine_scatter_impl(if_nomatching, pts, mkpts1_f, label, label_stride, B, P, if_nomatching16, pts16, workspace,
-                               workspace_bytes, stream, nullptr, nullptr);
-}
-// pats_refine_scatter_f32 that also scatters conf [P,16] onto conf16 [B,2304] (0 where if_nomatching16 is set).  conf may be
-// null when P == 0, as mkpts1_f.
-extern "C" int pats_refine_scatter_conf_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f,
-                                            const float* label, int label_stride, const float* conf, int64_t B, int64_t P,
-                                            uint8_t* if_nomatching16, float* pts16, float* conf16, void* workspace,
-                                            size_t workspace_bytes, pats_stream_t stream) {
-    PATS_REQUIRE(B >= 0 && P >= 0 && label_stride >= 1, "refine_scatter_conf: bad shape");
-    if (B == 0) return PATS_OK;
-    PATS_REQUIRE(conf16 && (P == 0 || conf), "refine_scatter_conf: null conf / conf16");
-    PATS_REQUIRE((uintptr_t)conf % 4 == 0 && (uintptr_t)conf16 % 4 == 0, "refine_scatter_conf: conf / conf16 must be 4-byte aligned");
-    return refine_scatter_impl(if_nomatching, pts, mkpts1_f, label, label_stride, B, P, if_nomatching16, pts16, workspace,
-                               workspace_bytes, stream, conf, conf16);
-}
-static int refine_scatter_impl(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f, const float* label,
-                               int label_stride, int64_t B, int64_t P, uint8_t* if_nomatching16, float* pts16, void* workspace,
                                size_t workspace_bytes, pats_stream_t stream, const float* conf, float* conf16) {
     PATS_REQUIRE(B >= 0 && P >= 0 && label_stride >= 1, "refine_scatter: bad shape");
     if (B == 0) return PATS_OK;
@@ -1024,6 +971,25 @@ static int refine_scatter_impl(const uint8_t* if_nomatching, const float* pts, c
         hipLaunchKernelGGL(refine_scatter_kernel, dim3(blocks256(B * 2304)), dim3(256), 0, as_stream(stream), if_nomatching, pts,
                            mkpts1_f, label, label_stride, P, B * 2304, sc, if_nomatching16, pts16);
     return check_launch("refine_scatter_kernel");
+}
+extern "C" int pats_refine_scatter_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f,
+                                       const float* label, int label_stride, int64_t B, int64_t P,
+                                       uint8_t* if_nomatching16, float* pts16, void* workspace,
+                                       size_t workspace_bytes, pats_stream_t stream) {
+    return refine_scatter_impl(if_nomatching, pts, mkpts1_f, label, label_stride, B, P, if_nomatching16, pts16, workspace,
+                               workspace_bytes, stream, nullptr, nullptr);
+}
+// pats_refine_scatter_f32 that also scatters conf [P,16] onto conf16 [B,2304] (0 where if_nomatching16 is set).  conf may be
+// null when P == 0, as mkpts1_f.
+extern "C" int pats_refine_scatter_conf_f32(const uint8_t* if_nomatching, const float* pts, const float* mkpts1_f,
+                                            const float* label, int label_stride, const float* conf, int64_t B, int64_t P,
+                                            uint8_t* if_nomatching16, float* pts16, float* conf16, void* workspace,
+                                            size_t workspace_bytes, pats_stream_t stream) {
+    PATS_REQUIRE(B >= 0 && P >= 0 && label_stride >= 1, "refine_scatter_conf: bad shape");
+    if (B == 0) return PATS_OK;
+    if (const int rc = conf_pair("refine_scatter_conf", "conf", conf, "conf16", conf16, P == 0)) return rc;
+    return refine_scatter_impl(if_nomatching, pts, mkpts1_f, label, label_stride, B, P, if_nomatching16, pts16, workspace,
+                               workspace_bytes, stream, conf, conf16);
 }
 
 extern "C" size_t pats_get_result_workspace_bytes(int64_t cells0, int64_t rows1, int64_t cells1) {
@@ -1089,18 +1055,47 @@ extern "C" int pats_get_result_f32(int batch_size, const uint8_t* if_nomatching0
 // Cmax * pairs chunk masks of batch.hip, level-1 rows = the row table; pts_new / scales are the PER-PAIR tensors
 // [pairs, N, 2] (never expanded over the chunks), points un-flipped; match_row tells which row - hence which pair -
 // every match belongs to.
+// the checked body of the four entries below.  ragged: the grids come from `tab` (pairs and patch_size0 are not read - patch_size0
+// would only carry the level-0 step, 32); want_conf: the sub-cells' confidences conf16 [rows_cap, n1] are compacted beside the
+// matches, match_conf[M] = conf16 of the sub-cell whose match went to matches_l[M] / matches_r[M] (the same scan, the same slots)
+static int get_result_chunks_impl(const char* who, bool ragged, const pats_pair_table_t* tab, int Cmax, int64_t pairs,
+                                  const uint8_t* masks, const uint8_t* if_nomatching16, int64_t rows_cap, const float* pts_new,
+                                  const float* pts16, const float* scales, bool want_conf, const float* conf16, const int* patch_size0,
+                                  const int* patch_size1, const uint8_t* left_choice0, const uint8_t* left_choice1, float* matches_l,
+                                  float* matches_r, float* match_conf, int32_t* match_row, int64_t capacity, int64_t* count,
+                                  void* workspace, size_t workspace_bytes, pats_stream_t stream) {
+    if (want_conf)
+        if (const int rc = conf_pair(who, "conf16", conf16, "match_conf", match_conf)) return rc;
+    PairShapes ps;
+    const int ps0[3] = {32, 1, 1};
+    int64_t period0;
+    if (ragged) {
+        int hmax = 0;
+        const int rc = ragged_shapes(tab, &ps, &hmax, who);
+        if (rc != PATS_OK) return rc;
+        PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && ps.cells * Cmax < (1ll << 31), "%s: bad shape", who);
+        pairs = ps.pairs;
+        patch_size0 = ps0;
+        period0 = ps.cells;
+    } else {
+        PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && patch_size0, "%s: bad shape", who);
+        PATS_REQUIRE((int64_t)Cmax * pairs < (1ll << 31), "%s: batch too large", who);
+        period0 = pairs * (int64_t)patch_size0[1] * patch_size0[2];
+    }
+    return get_result_impl((int)(Cmax * pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0, patch_size0,
+                           patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count, workspace, workspace_bytes,
+                           stream, period0, 32.0f, 2.0f, match_row, ragged ? &ps : nullptr, conf16, match_conf);
+}
+
 extern "C" int pats_get_result_chunks_f32(int Cmax, int64_t pairs, const uint8_t* masks, const uint8_t* if_nomatching16,
                                           int64_t rows_cap, const float* pts_new, const float* pts16, const float* scales,
                                           const int* patch_size0, const int* patch_size1, const uint8_t* left_choice0,
                                           const uint8_t* left_choice1, float* matches_l, float* matches_r,
                                           int32_t* match_row, int64_t capacity, int64_t* count, void* workspace,
                                           size_t workspace_bytes, pats_stream_t stream) {
-    PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && patch_size0, "get_result_chunks: bad shape");
-    PATS_REQUIRE((int64_t)Cmax * pairs < (1ll << 31), "get_result_chunks: batch too large");
-    const int64_t period0 = pairs * (int64_t)patch_size0[1] * patch_size0[2];
-    return get_result_impl((int)(Cmax * pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0,
-                           patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count,
-                           workspace, workspace_bytes, stream, period0, 32.0f, 2.0f, match_row, nullptr);
+    return get_result_chunks_impl("get_result_chunks", false, nullptr, Cmax, pairs, masks, if_nomatching16, rows_cap, pts_new, pts16, scales,
+                                  false, nullptr, patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r, nullptr,
+                                  match_row, capacity, count, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pats_get_result_chunks_ragged_f32(const pats_pair_table_t* tab, int Cmax, const uint8_t* masks, const uint8_t* if_nomatching16,
@@ -1108,34 +1103,20 @@ extern "C" int pats_get_result_chunks_ragged_f32(const pats_pair_table_t* tab, i
                                                  const int* patch_size1, const uint8_t* left_choice0, const uint8_t* left_choice1,
                                                  float* matches_l, float* matches_r, int32_t* match_row, int64_t capacity, int64_t* count,
                                                  void* workspace, size_t workspace_bytes, pats_stream_t stream) {
-    PairShapes ps;
-    int hmax = 0;
-    const int rc = ragged_shapes(tab, &ps, &hmax, "get_result_chunks_ragged");
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && ps.cells * Cmax < (1ll << 31), "get_result_chunks_ragged: bad shape");
-    // patch_size0 only carries the level-0 step (32); each pair's grid comes from the table
-    const int ps0[3] = {32, 1, 1};
-    return get_result_impl((int)(Cmax * ps.pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0, ps0,
-                           patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count, workspace, workspace_bytes,
-                           stream, ps.cells, 32.0f, 2.0f, match_row, &ps);
+    return get_result_chunks_impl("get_result_chunks_ragged", true, tab, Cmax, 0, masks, if_nomatching16, rows_cap, pts_new, pts16, scales,
+                                  false, nullptr, nullptr, patch_size1, left_choice0, left_choice1, matches_l, matches_r, nullptr,
+                                  match_row, capacity, count, workspace, workspace_bytes, stream);
 }
 
-// The two entries above with the sub-cells' confidences compacted beside the matches: match_conf[M] = conf16 of the sub-cell
-// whose match went to matches_l[M] / matches_r[M] (the same scan, the same slots).  conf16 [rows_cap, n1], match_conf [capacity].
 extern "C" int pats_get_result_chunks_conf_f32(int Cmax, int64_t pairs, const uint8_t* masks, const uint8_t* if_nomatching16,
                                                int64_t rows_cap, const float* pts_new, const float* pts16, const float* scales,
                                                const float* conf16, const int* patch_size0, const int* patch_size1,
                                                const uint8_t* left_choice0, const uint8_t* left_choice1, float* matches_l,
                                                float* matches_r, float* match_conf, int32_t* match_row, int64_t capacity,
                                                int64_t* count, void* workspace, size_t workspace_bytes, pats_stream_t stream) {
-    PATS_REQUIRE(conf16 && match_conf, "get_result_chunks_conf: null conf16 / match_conf");
-    PATS_REQUIRE((uintptr_t)conf16 % 4 == 0 && (uintptr_t)match_conf % 4 == 0, "get_result_chunks_conf: conf16 / match_conf must be 4-byte aligned");
-    PATS_REQUIRE(Cmax >= 1 && pairs >= 1 && patch_size0, "get_result_chunks_conf: bad shape");
-    PATS_REQUIRE((int64_t)Cmax * pairs < (1ll << 31), "get_result_chunks_conf: batch too large");
-    const int64_t period0 = pairs * (int64_t)patch_size0[1] * patch_size0[2];
-    return get_result_impl((int)(Cmax * pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0,
-                           patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count,
-                           workspace, workspace_bytes, stream, period0, 32.0f, 2.0f, match_row, nullptr, conf16, match_conf);
+    return get_result_chunks_impl("get_result_chunks_conf", false, nullptr, Cmax, pairs, masks, if_nomatching16, rows_cap, pts_new, pts16,
+                                  scales, true, conf16, patch_size0, patch_size1, left_choice0, left_choice1, matches_l, matches_r,
+                                  match_conf, match_row, capacity, count, workspace, workspace_bytes, stream);
 }
 
 extern "C" int pats_get_result_chunks_ragged_conf_f32(const pats_pair_table_t* tab, int Cmax, const uint8_t* masks,
@@ -1145,16 +1126,7 @@ extern "C" int pats_get_result_chunks_ragged_conf_f32(const pats_pair_table_t* t
                                                       const uint8_t* left_choice1, float* matches_l, float* matches_r,
                                                       float* match_conf, int32_t* match_row, int64_t capacity, int64_t* count,
                                                       void* workspace, size_t workspace_bytes, pats_stream_t stream) {
-    PATS_REQUIRE(conf16 && match_conf, "get_result_chunks_ragged_conf: null conf16 / match_conf");
-    PATS_REQUIRE((uintptr_t)conf16 % 4 == 0 && (uintptr_t)match_conf % 4 == 0,
-                 "get_result_chunks_ragged_conf: conf16 / match_conf must be 4-byte aligned");
-    PairShapes ps;
-    int hmax = 0;
-    const int rc = ragged_shapes(tab, &ps, &hmax, "get_result_chunks_ragged_conf");
-    if (rc != PATS_OK) return rc;
-    PATS_REQUIRE(Cmax >= 1 && Cmax <= hmax + 1 && ps.cells * Cmax < (1ll << 31), "get_result_chunks_ragged_conf: bad shape");
-    const int ps0[3] = {32, 1, 1};
-    return get_result_impl((int)(Cmax * ps.pairs), masks, if_nomatching16, rows_cap, pts_new, pts16, scales, nullptr, 0, ps0,
-                           patch_size1, left_choice0, left_choice1, matches_l, matches_r, capacity, count, workspace, workspace_bytes,
-                           stream, ps.cells, 32.0f, 2.0f, match_row, &ps, conf16, match_conf);
+    return get_result_chunks_impl("get_result_chunks_ragged_conf", true, tab, Cmax, 0, masks, if_nomatching16, rows_cap, pts_new, pts16,
+                                  scales, true, conf16, nullptr, patch_size1, left_choice0, left_choice1, matches_l, matches_r,
+                                  match_conf, match_row, capacity, count, workspace, workspace_bytes, stream);
 }

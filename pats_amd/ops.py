@@ -1093,16 +1093,31 @@ def _as_flags(t, name):
     return t.contiguous()
 
 
+def _merge_tensors(trust_score, if_nomatching1_L2, rows, who=None):
+    """-> whether the merges' in-place tensors are what the C entries take: trust_score float32 and if_nomatching1_L2 bool, both
+    contiguous and [rows,144].  With `who`, a wrong dtype or layout (or a trust_score off the GPU) raises that wrapper's message
+    for the tensor instead, and only the extents are answered."""
+    for t, name, dtype, kind in ((trust_score, "trust_score", torch.float32, "float32 GPU"),
+                                 (if_nomatching1_L2, "if_nomatching1_L2", torch.bool, "bool")):
+        if t.dtype != dtype or not t.is_contiguous() or (who and t is trust_score and not t.is_cuda):
+            if who:
+                raise RuntimeError("%s: %s must be a contiguous %s tensor (it is updated in place)" % (who, name, kind))
+            return False
+    return trust_score.numel() == rows * 144 and if_nomatching1_L2.numel() == rows * 144
+
+
+def _merge_scores_back(scores_back, cells=None):
+    """-> whether scores_back is what the merges take: float64, contiguous, [cells,16,9] (None: any extent)"""
+    return scores_back.dtype == torch.float64 and scores_back.is_contiguous() and (cells is None or scores_back.numel() == cells * 144)
+
+
 def _merge(merge_new, patch_num, trust_score, original_image_shape, if_nomatching1_L1, if_nomatching1_L2,
            scores_back, validate):
-    if trust_score.dtype != torch.float32 or not trust_score.is_cuda or not trust_score.is_contiguous():
-        raise RuntimeError("merge_patches: trust_score must be a contiguous float32 GPU tensor (it is updated in place)")
-    if if_nomatching1_L2.dtype != torch.bool or not if_nomatching1_L2.is_contiguous():
-        raise RuntimeError("merge_patches: if_nomatching1_L2 must be a contiguous bool tensor (it is updated in place)")
-    if scores_back.dtype != torch.float64 or not scores_back.is_contiguous():
-        raise RuntimeError("merge_patches: scores_back must be a contiguous float64 tensor (it is updated in place)")
     B = trust_score.shape[0]
-    if trust_score.numel() != B * 144 or if_nomatching1_L2.numel() != B * 144 or int(patch_num) != B:
+    shaped = _merge_tensors(trust_score, if_nomatching1_L2, B, "merge_patches")
+    if not _merge_scores_back(scores_back):
+        raise RuntimeError("merge_patches: scores_back must be a contiguous float64 tensor (it is updated in place)")
+    if not shaped or int(patch_num) != B:
         raise RuntimeError("merge_patches: trust_score / if_nomatching1_L2 must be [patch_num,144]")
     H, W = int(original_image_shape[0]), int(original_image_shape[1])
     l1 = _as_flags(if_nomatching1_L1, "if_nomatching1_L1")
@@ -1352,10 +1367,6 @@ def merge_patches_batch(merge_new, rows, trust_score, original_image_shape, if_n
     """SecondLayer.merge_patches_new / _old (second_layer.py:137-238) for every chunk of every pair of a ChunkRows table,
     chunk blocks in order, pats.py:38-39 applied.  trust_score / if_nomatching1_L2 [rows_cap,144] are updated in place;
     scores_back [pairs, N, 16, 9] float64 (zeros if None, pats.py:32).  Returns if_nomatching [rows_cap,144] bool."""
-    if trust_score.dtype != torch.float32 or not trust_score.is_cuda or not trust_score.is_contiguous():
-        raise RuntimeError("merge_patches_batch: trust_score must be a contiguous float32 GPU tensor (it is updated in place)")
-    if if_nomatching1_L2.dtype != torch.bool or not if_nomatching1_L2.is_contiguous():
-        raise RuntimeError("merge_patches_batch: if_nomatching1_L2 must be a contiguous bool tensor (it is updated in place)")
     table = rows.table
     if table is None:
         H, W = int(original_image_shape[0]), int(original_image_shape[1])
@@ -1366,13 +1377,13 @@ def merge_patches_batch(merge_new, rows, trust_score, original_image_shape, if_n
         on_grid, cells, sb_shape = True, table.cells, (table.cells, 16, 9)
         entry, what, sizer, size_args = "pats_merge_patches_ragged", "merge_patches_ragged", "pats_merge_ragged_workspace_bytes", (cells,)
         head, pair_arg = (table.ref(), 1 if merge_new else 0, rows.Cmax, rows.rows_cap), (_ptr(rows.row_pair),)
-    if trust_score.numel() != rows.rows_cap * 144 or if_nomatching1_L2.numel() != rows.rows_cap * 144 or not on_grid:
+    if not _merge_tensors(trust_score, if_nomatching1_L2, rows.rows_cap, "merge_patches_batch") or not on_grid:
         raise RuntimeError("merge_patches_batch: tensors must be [rows_cap,144]" + (" on the table's grid" if table is None else ""))
     dev = trust_score.device
     fresh = scores_back is None
     if fresh:
         scores_back = torch.empty(sb_shape, dtype=torch.float64, device=dev)            # cleared by the call
-    elif scores_back.dtype != torch.float64 or not scores_back.is_contiguous() or scores_back.numel() != cells * 144:
+    elif not _merge_scores_back(scores_back, cells):
         raise RuntimeError("merge_patches_batch: scores_back must be a contiguous float64 [%s, 16, 9] tensor"
                            % ("pairs, N" if table is None else "sum N"))
     out = torch.empty((rows.rows_cap, 144), dtype=torch.bool, device=dev)
@@ -1392,10 +1403,9 @@ def merge_patches_chunk(merge_new, rows, c, row_origin, trust_score, original_im
     call (first=True clears it, pats.py:32).  Returns if_nomatching [B,144] bool (pats.py:38-39 applied)."""
     B = trust_score.shape[0]
     H, W = int(original_image_shape[0]), int(original_image_shape[1])
-    if trust_score.dtype != torch.float32 or not trust_score.is_contiguous() or if_nomatching1_L2.dtype != torch.bool or \
-            not if_nomatching1_L2.is_contiguous() or trust_score.numel() != B * 144 or if_nomatching1_L2.numel() != B * 144:
+    if not _merge_tensors(trust_score, if_nomatching1_L2, B):
         raise RuntimeError("merge_patches_chunk: trust_score / if_nomatching1_L2 must be contiguous [B,144] float32 / bool")
-    if scores_back.dtype != torch.float64 or not scores_back.is_contiguous() or scores_back.numel() != rows.pairs * rows.h * rows.w * 144:
+    if not _merge_scores_back(scores_back, rows.pairs * rows.h * rows.w):
         raise RuntimeError("merge_patches_chunk: scores_back must be a contiguous float64 [pairs, N, 16, 9] tensor")
     dev = trust_score.device
     out = torch.empty((B, 144), dtype=torch.bool, device=dev)
@@ -3156,7 +3166,6 @@ def fundamental_polish_by_pair(matches_l, matches_r, models, thr, best=None, rou
 
 
 # ---- the image front end (csrc/prepare.hip; include/pats_amd.h, "Image front end") ----------------------------------------------
-_IMG_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}        # pats_img_dtype_t
 # pats_prepare_image_t
 _PREPARE_IMAGE = np.dtype([("src", np.uint64), ("dst", np.int64), ("scale_x", np.float64), ("scale_y", np.float64)] +
                           [(n, np.int32) for n in ("h0", "w0", "y0", "x0", "h_c", "w_c", "h_t", "w_t", "H", "W", "side", "bgr")], align=True)

@@ -266,6 +266,58 @@ def test_batched_merge_and_result_against_the_single_chunk_ops(new):
     assert bool((mrow[:m] >= 0).all()) and bool((mrow[:m] < total).all())
 
 
+@pytest.mark.parametrize("new", [True, False])
+def test_ragged_merge_against_the_single_chunk_ops(new):
+    """ops.merge_patches_batch on a RAGGED table (two pairs, grids 6 x 7 and 5 x 9) against ops.merge_patches_new / _old walked per
+    pair and chunk on the pair's own grid, with the scores_back hand-over and the pats.py:38-39 tail rows: `out`, the in-place
+    trust_score and the flags bit-identical.  A ragged batch plans every pair with its own cap 2 w_p (first_layer.py:131-135), so
+    the chunk count is set by how many cells match: 6 % unmatched gives both pairs three chunks, and every chunk boundary falls
+    inside a matched grid row - that row's patches have a row in both chunks, which is what sends the select's row_slot walk back
+    over an earlier chunk.  Both are checked on the host split plan before anything runs."""
+    from pats_amd import ops
+    rng = np.random.default_rng(314 + int(new))
+    shapes = [(6, 7), (5, 9)]
+    flags = [rng.random(h * w) < 0.06 for h, w in shapes]
+    for (h, w), f in zip(shapes, flags):
+        n, second, _ = ops.split_patches(np.cumsum(~f).astype(np.int32), h, w, 2 * w)
+        assert n >= 3, "pair %d x %d: %d chunks" % (h, w, n)
+        assert any(second[c][1] > second[c + 1][0] for c in range(n - 1)), "no chunk boundary inside a matched grid row"
+    table = ops.PairTable(shapes, torch.device("cuda"))
+    rows = ops.chunk_rows_ragged(cu(np.concatenate(flags)), table)
+    assert int(rows.status.item()) == 0 and rows.Cmax >= 3
+    total, R = int(rows.chunk_base[-1].item()), rows.rows_cap
+    trust = (rng.random((R, 144)) * 1.2).astype(np.float32)
+    ifn2 = rng.random((R, 144)) < 0.3
+    t_b, f_b = cu(trust.copy()), cu(ifn2.copy())
+    merged = ops.merge_patches_batch(new, rows, t_b, None, f_b)
+    cell, pair, base = rows.row_cell.cpu().numpy(), rows.row_pair.cpu().numpy(), rows.chunk_base.cpu().numpy()
+    masks, third, slot = rows.masks.cpu().numpy(), rows.third.cpu().numpy(), rows.row_slot.cpu().numpy()
+    want = np.ones((R, 144), bool)
+    want_t, want_f = trust.copy(), ifn2.copy()
+    merge = ops.merge_patches_new if new else ops.merge_patches_old
+    for p, (h, w) in enumerate(shapes):
+        lo, hi = int(table.cell_base_host[p]), int(table.cell_base_host[p + 1])
+        both = (slot[:-1, lo:hi] >= 0) & (slot[1:, lo:hi] >= 0)
+        assert both.any(), "pair %d: no patch with a row in two consecutive chunks" % p
+        sb = torch.zeros((1, h * w, 16, 9), dtype=torch.float64, device="cuda")
+        for c in range(rows.Cmax):
+            idx = np.nonzero(pair[base[c]:base[c + 1]] == p)[0] + int(base[c])
+            if len(idx) == 0:
+                continue
+            assert np.array_equal(cell[idx], lo + np.nonzero(~masks[c, lo:hi])[0])
+            t_in, f_in = cu(trust[idx].copy()), cu(ifn2[idx].copy())
+            out, sb = merge(len(idx), t_in, (32 * h, 32 * w), cu(masks[c:c + 1, lo:hi]), f_in, sb)
+            want_t[idx], want_f[idx] = t_in.cpu().numpy(), f_in.cpu().numpy()
+            out = out.cpu().numpy()
+            tail = int(third[p, c, 1])
+            if tail != 0:
+                out[-tail:, :] = True
+            want[idx] = out
+    assert 0 < total < R and np.array_equal(merged.cpu().numpy(), want)
+    assert merged[total:].all()
+    assert np.array_equal(t_b.cpu().numpy()[:total], want_t[:total]) and np.array_equal(f_b.cpu().numpy()[:total], want_f[:total])
+
+
 @pytest.mark.parametrize("layout", ["nchw", "channels_last"])
 def test_counted_fine_level_launches_skip_the_padding_rows(layout):
     """The fine level over a CAPACITY with the row count on the device (pats_cost_ot_flags_counted_f32,
