@@ -1329,6 +1329,8 @@ static int launch_by_shape(const SrcView& src, int64_t batch, int M, int N, cons
     if (use_linear() && cu_shape(M, N))
         return launch_cu_then_fallback(src, batch, M, N, log_mu, log_nu, norm, iters, out, w, st);
     if (use_linear() && stream_shape(M, N) && batch <= 65535) {
+        // launch_wg's bound, ahead of the streaming launches: the hand-over would refuse the shape only after they were queued
+        PATS_REQUIRE((size_t)(M + N) * sizeof(float) <= 64 * 1024, "sinkhorn: M+N=%d too large for the one-workgroup kernel", M + N);
         int rc = launch_stream(src.base, src.stride, src.ld, src.rows, src.cols, src.alpha, batch, M, N, log_mu, log_nu, norm,
                                iters, out, w.stream, w.fail, st);
         if (rc) return rc;
